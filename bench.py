@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/sec of the Phase-2 DETR detect path (BASELINE.json: detr-resnet-50, batch 8, 800x1333).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 works both ways: started by ``torch.distributed.run`` (RANK / LOCAL_RANK / WORLD_SIZE in the environment: one rank per
 GPU) or as a plain ``python bench.py --gpus N`` — then this process, before it imports torch or touches a GPU, starts N fresh
@@ -22,6 +22,10 @@ that handle: `stage_ms` / `roofline.graph_ms_per_step` from stage marks recorded
 (`roofline_serial.closes`: graph_ms_per_step <= serial.ms_per_step), `roofline` from HIP event pairs around every launch of
 an eagerly launched forward (true kernel durations; their sum, `kernel_ms_per_step`, carries ~10 us of eager dispatch and
 event overhead per launch and therefore exceeds the step it dissects).
+
+``--dump-outputs DIR`` writes what the timed path handed its caller in its last timed step (rank 0's records after the person
+filter + NMS, see `dump_outputs`) as ``DIR/<name>.npy``.  Frames and weights are seeded, so two builds run with the same arguments
+can be compared output for output.
 """
 
 from __future__ import annotations
@@ -124,6 +128,29 @@ def cpu_baseline(path: str, H: int, W: int, batch: int = 4, iters: int = 3) -> d
                       f"(all: {', '.join(f'{t:.2f}' for t in times[1:])})"}
 
 
+def dump_outputs(out_dir: str, recs, counts, Q: int) -> dict:
+    """The detections of one step as a caller of the path receives them: frame f owns records [f * Q, f * Q + counts[f]) of `recs`
+    (opd_det viewed as int32 [n][8]; a negative count marks a padding slot).  Every field goes to its own float32 / float64 file
+    (integer fields as float64, exact), records of all frames concatenated in frame order; at most a few hundred KB."""
+    import numpy as np
+
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    recs = np.asarray(recs, dtype=np.int32).reshape(-1, 8)
+    rows = [recs[f * Q:f * Q + max(int(c), 0)] for f, c in enumerate(counts)]
+    r = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 8), np.int32))
+    fl = r.view(np.float32)
+    arrays = {"boxes_xyxy": np.ascontiguousarray(fl[:, 0:4]),   # pixels of the original frame
+              "scores": np.ascontiguousarray(fl[:, 4]),
+              "labels": r[:, 5].astype(np.float64),
+              "query_index": r[:, 6].astype(np.float64),
+              "frame": r[:, 7].astype(np.float64),
+              "counts": counts.astype(np.float64)}   # per frame slot of the global batch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": {k: list(a.shape) for k, a in arrays.items()}}
+
+
 def _capi_unique_id(lib):
     buf = C.create_string_buffer(128)
     if lib.opd_comm_unique_id(buf) != 0:
@@ -152,10 +179,16 @@ def parse_args(argv=None):
                     help="one blocking detect call per step (default: steps are submitted asynchronously, results of step i-1 are "
                          "fetched while step i computes)")
     ap.add_argument("--serial-steps", type=int, default=30, help="steps of the serial cross-check leg (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (rank 0's detection records "
+                         "after NMS) as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--cpu-rehearsal", action="store_true",
                     help="no GPU: exercise launch, rendezvous (gloo), the step loop's collective and the rank-0 JSON with the "
                          "device compute left out — a plumbing test, never a measurement")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main() -> int:
@@ -304,6 +337,7 @@ def main() -> int:
 
     g_recs = np.zeros((world * B * Q, 8), np.int32)
     g_counts = np.zeros((world * B,), np.int32)
+    last = {}   # rank 0: the records + counts of the most recently collected step (what --dump-outputs writes)
 
     def collect(buf, j=0):
         """records (+ counts) of one finished step -> the orchestrator's host memory (the path's one exchange step for N > 1),
@@ -329,6 +363,7 @@ def main() -> int:
             recs, counts = h[:NREC].reshape(B * Q, 8), h[NREC:]
         _capi.check(lib.opd_person_nms_batch(recs.ctypes.data_as(DetP), counts.ctypes.data_as(I32P), len(counts), Q, 1, 0.4),
                     "opd_person_nms_batch")
+        last["recs"], last["counts"] = recs, counts
         return counts
 
     def detect_blocking(h, buf):
@@ -402,6 +437,8 @@ def main() -> int:
         t = torch.tensor([elapsed], dtype=torch.float64, device=gdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # the last timed step's outputs, written before any later leg reuses the buffers they live in
+    dumped = dump_outputs(args.dump_outputs, last["recs"], last["counts"], Q) if args.dump_outputs and rank == 0 else None
 
     # ---- sustained leg: the same handles over a window of >= 2 s.  The driver's --steps 20 times 55 ms of GPU work; this leg, in the same
     # JSON line, shows whether that burst is representative (all ranks take part: it is bracketed like the timed region).
@@ -574,6 +611,8 @@ def main() -> int:
             "exchange": exchange,
             "detections_last_step": int(np.asarray(counts).clip(min=0).sum()) if counts is not None else None,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if rehearsal:
             out["rehearsal"] = "cpu: no device compute, not a measurement"
         if roof is not None and serial is not None and roof.get("graph_ms_per_step"):

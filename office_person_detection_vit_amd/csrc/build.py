@@ -66,9 +66,10 @@ def build(verbose: bool = False, force: bool = False) -> str:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
 
-    if jobs:   # independent translation units: compile them side by side (bounded by the host's cores)
+    if jobs:   # independent translation units: compile them side by side (bounded by MAX_JOBS, else the cores this process may use)
         from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), os.cpu_count() or 1))) as pool:
+        cores = int(os.environ.get("MAX_JOBS") or 0) or len(os.sched_getaffinity(0))
+        with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), cores))) as pool:
             list(pool.map(compile_one, jobs))
     test_objs = {os.path.join(objdir, os.path.splitext(s)[0] + ".o") for s in TEST_ONLY}
     for lib, members in ((LIB, [o for o in objs if o not in test_objs]), (TEST_LIB, objs)):

@@ -61,3 +61,32 @@ def test_mismatched_world_size_is_refused():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--cpu-rehearsal"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and "WORLD_SIZE=2" in p.stderr
+
+
+def test_dump_outputs_writes_the_last_step_records(tmp_path):
+    """``--dump-outputs DIR``: rank 0's records of the last timed step, one float32 / float64 .npy per field, named in the JSON line.  The
+    rehearsal's records are empty, so this pins the files, their dtypes and the per-frame-slot counts of the global batch."""
+    import numpy as np
+
+    out_dir = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--cpu-rehearsal",
+                        "--dump-outputs", str(out_dir)], env=_clean_env(), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert out["dump_outputs"]["dir"] == str(out_dir)
+    names = {"boxes_xyxy", "scores", "labels", "query_index", "frame", "counts"}
+    assert set(out["dump_outputs"]["arrays"]) == names
+    assert sorted(os.listdir(out_dir)) == sorted(n + ".npy" for n in names)
+    arrays = {n: np.load(out_dir / (n + ".npy")) for n in names}
+    for n, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        assert list(a.shape) == out["dump_outputs"]["arrays"][n]
+    assert arrays["counts"].shape == (16,) and not arrays["counts"].any()
+    assert arrays["boxes_xyxy"].shape == (0, 4) and arrays["scores"].shape == (0,)
+
+
+def test_zero_steps_is_refused():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--cpu-rehearsal"], env=_clean_env(),
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--steps" in p.stderr

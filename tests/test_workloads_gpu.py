@@ -433,6 +433,36 @@ def test_bench_pipelined_loop_through_a_one_rank_communicator():
         assert out["steps"] == 11 and out["value"] > 0 and out["detections_last_step"] is not None
 
 
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """``bench.py --dump-outputs``: the last timed step's person detections after NMS, the same from run to run with the same arguments
+    (seeded frames and weights, no atomics on the path), consistent with the JSON line and with the NMS contract."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "OPD_TEST_HOOKS")}
+    env["OPD_BENCH_SUSTAINED"] = "0"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    H, W, B = 256, 320, 2
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "7", "--warmup", "2", "--batch", str(B), "--height", str(H),
+                            "--width", str(W), "--no-cpu-baseline", "--serial-steps", "0", "--dump-outputs", str(d)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+        assert out["steps"] == 7 and out["ms_per_step"] > 0
+        a = {n: np.load(d / (n + ".npy")) for n in out["dump_outputs"]["arrays"]}
+        counts = a["counts"].astype(np.int64)
+        assert counts.shape == (B,) and int(counts.sum()) == out["detections_last_step"] == len(a["scores"])
+        assert a["boxes_xyxy"].dtype == np.float32 and a["boxes_xyxy"].shape == (len(a["scores"]), 4)
+        assert np.array_equal(a["frame"], np.repeat(np.arange(B, dtype=np.float64), counts))
+        assert (a["labels"] == 1).all() and (a["scores"] > 0.5).all() and (a["query_index"] >= 0).all()
+        for f in range(B):   # NMS order: descending score within a frame
+            s = a["scores"][a["frame"] == f]
+            assert (np.diff(s) <= 0).all()
+        dumps.append(a)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
 def test_measurement_abi_modes_are_consistent(mild_path):
     """opd_detr_set_profiling / stage_times / kernel_times / kernel_table had no test.  (a) outputs are bit-identical under
     modes 0, 1 and 2; (b) mode 2: every stage mark > 0 and their sum <= the wall time of the call; (c) mode 1: flops4 sums to the
