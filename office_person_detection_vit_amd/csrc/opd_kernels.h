@@ -136,21 +136,18 @@ struct BtailParams {
     // tail can rebuild the y it needs as its residual from the 64-channel tensors that made it instead of reading 274 MB back:
     //   y == null      -> y is not stored at all (the consumer recomputes it);
     //   a1_out         -> [M][C1] fp16: this block's a1 = relu(3x3), stored for that consumer (natural channel order);
-    //   rc = 1         -> residual = relu(rc_b[0] + rc_w2[0] . rc_a1[0] + rc_wsc . rc_xs), the previous block's output rebuilt per 64-channel
+    //   rc = 1         -> residual = relu(rc_b + rc_w2 . rc_a1 + rc_wsc . rc_xs), the previous block's output rebuilt per 64-channel
     //                     chunk with that block's own instruction order (bit-identical to what its tail would have stored); res must be null;
-    //   rc = 2         -> two levels: index [1] = the block before the previous one (the one with the shortcut: rc_b[1] = its b2 + bsc), index [0] = the
-    //                     previous block; residual = relu(rc_b[0] + rc_w2[0] . rc_a1[0] + relu(rc_b[1] + rc_w2[1] . rc_a1[1] + rc_wsc . rc_xs)); C3 = 128;
     //   y_stride2 = 1  -> y is stored only at pixels with even (oh, ow): the only ones a stride-2 1x1 shortcut of the next stage reads
     //                     (valid when the next block's reduce is fused as z, i.e. nobody else reads y).
     f16_t* a1_out;
-    const f16_t* rc_a1[2];
+    const f16_t* rc_a1;
     const f16_t* rc_xs;
-    const f16_t* rc_w2[2];
+    const f16_t* rc_w2;
     const f16_t* rc_wsc;
-    const float* rc_b[2];
+    const float* rc_b;
     int rc;
     int y_stride2;
-    int nw;   // waves per workgroup of the C1 = 64 / 128 kernels: 0 / 4 = 128-pixel tiles, two workgroups per CU; 8 = 256-pixel tiles, one per CU (identical bits)
 };
 bool opd_btail_supported(int C1, int C3);
 hipError_t opd_launch_btail(const BtailParams& p, hipStream_t stream);

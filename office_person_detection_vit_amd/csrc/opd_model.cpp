@@ -87,7 +87,7 @@ static int make_conv(opd_detr* m, const StateDict& sd, const std::string& prefix
                 for (int kh = 0; kh < 7; ++kh)
                     for (int kw = 0; kw < 7; ++kw)
                         cw[(size_t)o * 147 + (kh * 7 + kw) * 3 + ci] = w.data[(((size_t)o * 3 + ci) * 7 + kh) * 7 + kw] * scale[o];
-        if (m->wround) round_f16_diffused(cw.data(), (size_t)Cout, 49, 3, m->dtype == OPD_DT_BF16);
+        if (m->sw.wround) round_f16_diffused(cw.data(), (size_t)Cout, 49, 3, m->dtype == OPD_DT_BF16);
         wt.assign((size_t)Cout * 256, 0.f);
         for (int o = 0; o < Cout; ++o)
             for (int kh = 0; kh < 7; ++kh)
@@ -103,10 +103,10 @@ static int make_conv(opd_detr* m, const StateDict& sd, const std::string& prefix
                         wt[(size_t)o * c->K + (size_t)(kh * KW + kw) * Cin + ci] =
                             w.data[(((size_t)o * Cin + ci) * KH + kh) * KW + kw] * scale[o];
         // the fp16 image of the folded kernel: error diffusion along the reduction (opd_host.h) instead of round-to-nearest
-        if (m->wround) round_f16_diffused(wt.data(), (size_t)Cout, KH * KW, Cin, m->dtype == OPD_DT_BF16);
+        if (m->sw.wround) round_f16_diffused(wt.data(), (size_t)Cout, KH * KW, Cin, m->dtype == OPD_DT_BF16);
     }
     RCCHK(upload_f16(m, &c->w, wt));
-    if (KH == 1 && KW == 1 && Cin % 32 == 0 && Cin <= 1024) {  // operands of kernels_btail.hip / kernels_btail3.hip (stages 1-3)
+    if (conv_has_kperm(*c)) {  // operands of kernels_btail.hip / kernels_btail3.hip (stages 1-3)
         std::vector<float> wp(wt.size());
         for (int o = 0; o < Cout; ++o)
             for (int b = 0; b < Cin; b += 32)
@@ -151,13 +151,13 @@ static int build_weights(opd_detr* m, const StateDict& sd) {
             RCCHK(make_conv(m, sd, p + ".layer.0", 1, &b.c0));
             RCCHK(make_conv(m, sd, p + ".layer.1", stride, &b.c1));
             RCCHK(make_conv(m, sd, p + ".layer.2", 1, &b.c2));
-            if (b.has_sc && b.sc.Cout == b.c2.Cout) {
+            if (block_has_bias2sc(b)) {
                 std::vector<float> b2(b.c2.Cout), bs(b.c2.Cout);
                 HIPCHK(hipMemcpy(b2.data(), b.c2.bias, b2.size() * 4, hipMemcpyDeviceToHost));
                 HIPCHK(hipMemcpy(bs.data(), b.sc.bias, bs.size() * 4, hipMemcpyDeviceToHost));
                 for (size_t j = 0; j < b2.size(); ++j) b2[j] += bs[j];
                 RCCHK(upload_f32(m, &b.bias2sc, b2));
-                if (b.sc.KH == 1 && b.c2.KH == 1 && b.c2.Cout % 128 == 0 && b.c2.Cin >= 128) {   // stages 2-4: [W2 | Wsc]
+                if (block_has_w2sc(b)) {   // stages 2-4: [W2 | Wsc]
                     const size_t K1 = (size_t)b.c2.K, K2 = (size_t)b.sc.K, N = (size_t)b.c2.Cout;
                     std::vector<f16_t> h2(N * K1), hs(N * K2), cat(N * (K1 + K2));
                     HIPCHK(hipMemcpy(h2.data(), b.c2.w, h2.size() * 2, hipMemcpyDeviceToHost));
@@ -436,8 +436,8 @@ static int build_workspace(opd_detr* m) {
     RCCHK(dalloc(m, &m->d_dq16, Md * D, false));
     RCCHK(dalloc(m, &m->d_dk16, B * 8 * 8 * 512, false));   // (fragment order: 8 heads x 8 key tiles x 1 KiB per frame)
     RCCHK(dalloc(m, &m->d_dvT, B * 8 * 8 * 512, false));
-    RCCHK(dalloc(m, &m->d_part_o, (size_t)m->dec_splits * Md * D, false));
-    RCCHK(dalloc(m, &m->d_part_ml, (size_t)m->dec_splits * Md * a.heads * 2, false));
+    RCCHK(dalloc(m, &m->d_part_o, (size_t)m->sw.dec_splits * Md * D, false));
+    RCCHK(dalloc(m, &m->d_part_ml, (size_t)m->sw.dec_splits * Md * a.heads * 2, false));
     RCCHK(dalloc(m, &m->d_ffn_part, (size_t)(a.ffn / OPD_DEC_FFN_CHUNK + 1) * Md * D, false));
     RCCHK(fill_qc0(m));
     RCCHK(dalloc(m, &m->d_logits, Md * a.ncls, false));
@@ -565,7 +565,7 @@ static int tap(opd_detr* m, const char* name, const void* p, size_t bytes) {
 // at hand -- a frame's low-order bits must not depend on the call it travels in -- and applies only where the unsplit launch would leave most
 // CUs without a workgroup.  Returns 1 (no split) or a divisor of the k-step count.
 static int conv_splits(const opd_detr* m, const Conv& c, int stage) {
-    if (!m->small_splitk || stage < 0 || stage > 3 || c.stem || c.K % 64 != 0 || c.Cout % 64 != 0) return 1;
+    if (!m->sw.small_splitk || stage < 0 || stage > 3 || c.stem || c.K % 64 != 0 || c.Cout % 64 != 0) return 1;
     const long long px = (long long)m->cfg.max_batch * (long long)m->stage_px[stage];
     const long long tiles = ((px + 127) / 128) * (c.Cout / 64);
     const int nk = c.K / 64;
@@ -582,7 +582,7 @@ static int run_conv(opd_detr* m, const Conv& c, const f16_t* x, int B, int H, in
     p.x = x; p.w = c.w; p.bias = c.bias; p.res16 = res16; p.res32 = nullptr; p.out = out; p.out16_aux = nullptr; p.zero16 = m->zero_bias;
     p.B = B; p.H = H; p.W = W; p.Cin = c.Cin; p.OH = OH; p.OW = OW; p.N = c.Cout; p.KH = c.KH; p.KW = c.KW;
     p.stride = c.stride; p.pad = c.pad; p.M = B * OH * OW; p.K = c.K; p.relu = relu ? 1 : 0; p.bias_period = 0;
-    p.out_f32 = 0; p.stem = c.stem ? 1 : 0; p.dbg = m->dbg_gemm; p.wprefetch = m->wprefetch & 1;
+    p.out_f32 = 0; p.stem = c.stem ? 1 : 0; p.dbg = m->sw.dbg_gemm; p.wprefetch = m->sw.wprefetch & 1;
     // algorithmic FLOPs (2 x MAC over the real taps/channels; the stem's zero padding is not counted)
     if (const int splits = res16 ? 1 : conv_splits(m, c, stage); splits > 1 && (size_t)splits * p.M * c.Cout <= m->slab_floats) {
         p.out = m->d_slab; p.out_f32 = 1; p.relu = 0; p.split_k = splits;
@@ -599,10 +599,10 @@ static int run_conv(opd_detr* m, const Conv& c, const f16_t* x, int B, int H, in
     // Wide layers with few row tiles (stage 4) through the eight-wave kernel (kernels_w8.hip; identical bits).  The choice follows the handle's
     // CONFIGURATION (max_batch and the layer), never the batch at hand.  OPD_W8: bit 0 = 3x3, bit 1 = 1x1 with K >= 1024, bit 2 = 1x1 with K = 512.
     bool w8 = false;
-    if (m->w8 && c.Cout % 256 == 0 && c.Cout >= 512) {
+    if (m->sw.w8 && c.Cout % 256 == 0 && c.Cout >= 512) {
         const long long tiles = (((long long)OH * OW * m->cfg.max_batch + 127) / 128) * (c.Cout / 256);
         const bool few = tiles <= 3LL * m->num_cus;
-        const int kind = c.KH == 3 ? (m->w8 & 1) : (c.K >= 1024 ? (m->w8 & 2) : (c.K == 512 ? (m->w8 & 4) : 0));
+        const int kind = c.KH == 3 ? (m->sw.w8 & 1) : (c.K >= 1024 ? (m->sw.w8 & 2) : (c.K == 512 ? (m->sw.w8 & 4) : 0));
         w8 = few && kind && opd_conv_w8_supported(p);
     }
     HIPCHK(w8 ? opd_launch_conv_w8(p, m->stream) : opd_launch_conv_gemm(p, m->stream));
@@ -620,7 +620,7 @@ static int run_gemm(opd_detr* m, const f16_t* x, const f16_t* w, const float* bi
     p.x_alt = x_alt; p.alt_mod = alt_mod; p.alt_cols = alt_cols;
     p.x = x; p.w = w; p.bias = bias; p.res16 = nullptr; p.res32 = res32; p.out = out; p.out16_aux = nullptr; p.zero16 = m->zero_bias;
     p.B = M; p.H = 1; p.W = 1; p.Cin = K; p.OH = 1; p.OW = 1; p.N = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
-    p.M = M; p.K = K; p.relu = relu ? 1 : 0; p.bias_period = bias_period; p.out_f32 = out_f32 ? 1 : 0; p.stem = 0; p.dbg = m->dbg_gemm; p.wprefetch = m->wprefetch & 1;
+    p.M = M; p.K = K; p.relu = relu ? 1 : 0; p.bias_period = bias_period; p.out_f32 = out_f32 ? 1 : 0; p.stem = 0; p.dbg = m->sw.dbg_gemm; p.wprefetch = m->sw.wprefetch & 1;
     RCCHK(timed_begin(m, CLS_GEMM, 2.0 * M * (double)N * K));
     HIPCHK(opd_launch_conv_gemm(p, m->stream));
     RCCHK(timed_end(m));
@@ -702,10 +702,107 @@ static int run_attn(opd_detr* m, const f16_t* q, int ldq, const f16_t* k, int ld
     return OPD_OK;
 }
 
+// The trunk plan (opd_model.h).  Every decision about how a bottleneck block runs is made here, from shapes and configuration only;
+// enqueue_forward's run_blocks walks the steps and launches.
+TrunkPlan plan_trunk(const Arch& a, const std::vector<Block>& blocks, const opd_config& cfg, const Switches& sw, int B, int H2, int W2, int num_cus,
+                     bool taps, int profiling, bool has_stream2) {
+    TrunkPlan plan;
+    plan.steps.resize(blocks.size());
+    plan.split = B;
+    const bool multi = (cfg.flags & OPD_FLAG_MULTI_STREAM) != 0;
+    int ch = H2, cw = W2, oh3 = 0, ow3 = 0;
+    for (int s = 0, bi = 0; s < 4; ++s) {
+        for (int l = 0; l < a.depths[s]; ++l, ++bi) {
+            const Block& b = blocks[bi];
+            const Block* nbk = bi + 1 < (int)blocks.size() ? &blocks[bi + 1] : nullptr;
+            const int oh = (b.c1.stride == 2) ? down2(ch) : ch, ow = (b.c1.stride == 2) ? down2(cw) : cw;
+            const int C1 = b.c1.Cin;
+            // first block of stage 1 (64 -> 256 channels, stride 1): the shortcut runs inside the fused tail (kernels_btail.hip, SC)
+            const bool sc_in_tail = b.has_sc && sw.fuse_shortcut && sw.fuse_btail && block_has_bias2sc(b) && b.sc.KH == 1 && b.sc.stride == 1 &&
+                                    b.sc.Cin == 64 && b.c1.Cin == 64 && b.c1.stride == 1 && b.c2.Cout == 256 && nbk && conv_has_kperm(nbk->c0) &&
+                                    nbk->c0.Cin == 256 && nbk->c0.Cout == 64;
+            bool tail = sw.fuse_btail && b.c1.KH == 3 && b.c1.Cout == C1 && b.c2.Cin == C1 && b.c2.Cout == 4 * C1 && conv_has_kperm(b.c2) &&
+                        opd_btail_supported(C1, 0);
+            // first block of stage 2: 3x3 + dual-source expand (+ the next reduce on its own) beats shortcut launch + fused tail
+            // (stage 2: 0.674 -> 0.657 ms; OPD_DUAL_OVER_TAIL=0 restores the tail)
+            if (sw.dual_over_tail && tail && b.has_sc && !sc_in_tail && block_has_w2sc(b)) tail = false;
+            // Stage 3: the eight-wave tail holds one 160-KiB workgroup per CU, so a launch costs whole ROUNDS of ~70 us whatever they hold.
+            // Rounds that are only partly filled because the batch does not divide into them are dealt with by the frame split below; what
+            // remains is the case of too few tiles for even one round (small frames / batches: the three launches win there).  The choice is
+            // made from the handle's configuration (max_batch and the frame size), never from the batch at hand: the two paths differ in
+            // the last bit (kernels_btail3.hip), and a frame's low-order bits must not depend on the batch it travels in.  Handles that
+            // keep several batches in flight (OPD_FLAG_MULTI_STREAM) always take the fused tail: other streams fill its idle CUs.
+            if (C1 == 256 && tail) {
+                const long long tiles = ((long long)cfg.max_batch * oh * ow + 127) / 128;
+                const bool pays = tiles * 10 >= (long long)num_cus * 6;
+                if (sw.tail3 == 0 || (sw.tail3 == 1 && !pays && !multi)) tail = false;
+            }
+            // first block of stages 3 / 4: the shortcut is extra K of the 1x1 expand (conv_gemm_dma_kernel, DUAL)
+            const bool sc_in_expand = b.has_sc && sw.fuse_shortcut && block_has_w2sc(b) && !sc_in_tail && !tail;
+            tail = tail && (size_t)B * ch * cw * C1 * 2 < 0x7ff00000ull;
+            TrunkStep& t = plan.steps[bi];
+            t.path = tail ? PATH_TAIL : sc_in_expand ? PATH_DUAL : PATH_CONVS;
+            t.sc = !b.has_sc ? SC_NONE : (sc_in_tail && tail) ? SC_TAIL : sc_in_expand ? SC_EXPAND : SC_LAUNCH;
+            t.res = (t.sc == SC_TAIL || t.sc == SC_EXPAND) ? RES_NONE : t.sc == SC_LAUNCH ? RES_SHORTCUT : RES_TRUNK;
+            t.store = STORE_Y;
+            t.C3 = 0;
+            if (tail && nbk && conv_has_kperm(nbk->c0) && nbk->c0.Cin == 4 * C1 && opd_btail_supported(C1, nbk->c0.Cout)) t.C3 = nbk->c0.Cout;
+            // The last block of stage 1 hands the next stage its reduce output z (fused above); the block output itself is then read
+            // by that stage's stride-2 shortcut only, i.e. at even (oh, ow): the other three quarters of its 274 MB are not stored.
+            if (tail && sw.y_stride2 && t.C3 && b.c1.stride == 1 && l + 1 == a.depths[s] && nbk && nbk->has_sc && nbk->sc.stride == 2 && nbk->sc.KH == 1 &&
+                nbk->c1.stride == 2 && !taps)
+                t.store = STORE_Y_STRIDE2;
+            // Stage 1, residual rebuild (BtailParams::rc), decided per pair: the previous block stores its a1 (64 channels) instead of its output
+            // (256) only if THIS block rebuilds that output chunk by chunk from a1 and the previous block's input (the shortcut's input) as its
+            // residual -- which the rc kernel does for a 64 -> 64 tail without a shortcut behind a tail with the shortcut inside.  Bit-identical
+            // results (tests/test_kernels_gpu.py, OPD_TAIL_RC=0/1 end to end); 344 MB less HBM traffic per forward at batch 8.
+            if (l > 0 && sw.tail_rc && !taps) {
+                TrunkStep& prev = plan.steps[bi - 1];
+                if (prev.path == PATH_TAIL && prev.sc == SC_TAIL && prev.C3 == 64 && prev.store == STORE_Y && tail && C1 == 64 && t.C3 == 64 &&
+                    t.res == RES_TRUNK) {
+                    prev.store = STORE_A1;
+                    t.res = RES_REBUILD;
+                }
+            }
+            if (s == 2 && l == 0) { oh3 = oh; ow3 = ow; }
+            ch = oh; cw = ow;
+        }
+    }
+    // Stage 3.  Frame split: with the fused tails a launch of T tiles costs ceil(T / CUs) rounds, and batch 8 at 800x1333 is 263 tiles on
+    // 256 CUs.  Frames are independent, so blocks 1 .. n-1 of the stage (all tensors there have one per-frame size, the buffers of the
+    // two chains never overlap) run as TWO chains on two streams -- frames [0, split) = whole rounds, the rest on `stream2` -- whose
+    // workgroups the hardware packs onto whatever CU is free: 5 tails of 263 workgroup-lives take ~5.3 rounds instead of 10.  Per-row
+    // arithmetic does not depend on the tiling, so this is invisible in the results (any batch, any split).  Captured into the graph
+    // as a fork / join; not under profiling (event pairs on one stream) or diagnostic taps, and not for handles that keep several batches
+    // in flight (there other handles' kernels fill the idle CUs; measured on one box, 1000 steps x 2: three streams 2841 frames/s with
+    // one launch per tail, 2783 with the split, 2793 unfused; one stream 2045 / 2112 / 2090).
+    const int s3 = a.depths[0] + a.depths[1], s4 = s3 + a.depths[2];
+    bool fused3 = a.depths[2] > 2 && profiling != 1 && !taps && has_stream2 && sw.tail3_split && !multi && B >= 2;
+    for (int bi = s3 + 1; bi < s4 && fused3; ++bi) fused3 = plan.steps[bi].path == PATH_TAIL;
+    if (fused3) {
+        auto tiles_of = [&](int frames) { return ((long long)frames * oh3 * ow3 + 127) / 128; };
+        const long long total = tiles_of(B), cus = num_cus, last = total % cus;
+        if (total > cus && last > 0 && last < cus / 2) {
+            const long long whole = (total / cus) * cus;
+            int bA = B - 1;
+            while (bA > 1 && tiles_of(bA) > whole) --bA;
+            if (tiles_of(bA) <= whole) plan.split = bA;
+        }
+    }
+    // consecutive fused tails walk their tiles in alternating directions (Switches::tail_rev), counted in launch order: the split's second
+    // chain comes between the first chain and stage 4
+    int n = 0;
+    auto rev = [&](const TrunkStep& t) { return t.path == PATH_TAIL && sw.tail_rev ? (n++ & 1) : 0; };
+    for (int bi = 0; bi < s4; ++bi) plan.steps[bi].rev = rev(plan.steps[bi]);
+    for (int bi = s3 + 1; bi < s4 && plan.split < B; ++bi) plan.steps[bi].rev_b = rev(plan.steps[bi]);
+    for (int bi = s4; bi < (int)blocks.size(); ++bi) plan.steps[bi].rev = rev(plan.steps[bi]);
+    return plan;
+}
+
 #define MARK(i)                                                   \
     do {                                                          \
         if (m->profiling) HIPCHK(hipEventRecord(m->ev[i], m->stream)); \
-        opd_dbg_skip_launch = (m->dbg_skip >> (i)) & 1;           \
+        opd_dbg_skip_launch = (m->sw.dbg_skip >> (i)) & 1;           \
     } while (0)
 
 // Enqueues the whole forward on m->stream.  `pixels` must already be on the device.
@@ -764,7 +861,7 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
     if (pixel_format == OPD_PIXELS_U8_BGR_HWC) RCCHK(tap(m, "pixels_u8", d_pixels, (size_t)B * H * W * 3));
     MARK(0);
     const int Hp = 2 * d.H1 + 6, Wp = 2 * d.W1 + 6;  // padded image seen by the stem: rows/cols 2*o + k, k = 0..7
-    const bool prep_in_stem = m->fuse_prep && m->fuse_stem_pool && pixel_format == OPD_PIXELS_U8_BGR_HWC;
+    const bool prep_in_stem = m->sw.fuse_prep && m->sw.fuse_stem_pool && pixel_format == OPD_PIXELS_U8_BGR_HWC;
     if (!prep_in_stem) {
         RCCHK(timed_begin(m, CLS_OTHER, 0.0));
         if (pixel_format == OPD_PIXELS_U8_BGR_HWC)
@@ -779,7 +876,7 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
                                        d.H2, d.W2, m->stream, m->dtype));
         RCCHK(timed_end(m));
         RCCHK(tap(m, "stem_pool_u8", m->d_pool, (size_t)B * d.H2 * d.W2 * 64 * 2));
-    } else if (m->fuse_stem_pool) {
+    } else if (m->sw.fuse_stem_pool) {
         RCCHK(timed_begin(m, CLS_CONV, 2.0 * B * d.H1 * d.W1 * 64.0 * 147.0));
         HIPCHK(opd_launch_stem_pool(m->d_x4, m->stem.w, m->stem.bias, m->d_pool, B, Hp, Wp, d.H1, d.W1, d.H2, d.W2, m->stream, m->dtype));
         RCCHK(timed_end(m));
@@ -796,17 +893,11 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
         RCCHK(timed_end(m));
     }
     MARK(1);
-    // ---- trunk.  Stages 1-2 may run in SUB-BATCHES (cfg: trunk_subbatch frames at a time through both stages, then the next
-    // frames): their block outputs are 274 / 137 MB at batch 8 — each one written by a fused tail and read back by the next as its
-    // residual — and the Infinity Cache holds 256 MiB, so at full batch that read comes from HBM; with 4 frames a tensor is
-    // 137 / 68 MB and the consumer finds it on the die.  Same kernels, same per-row arithmetic (tiles are cut from the flattened
-    // row index either way), so results do not change; buffers: every tensor of sub-batch [b0, b0 + nb) lives at frame offset b0
-    // of the buffer the full batch would use, the finished stage-2 outputs of earlier sub-batches sit below the regions later
-    // ones touch (per-frame sizes shrink from stage to stage).
-    struct TrunkState { int cur_id; int ch, cw; int z_id; };   // cur_id 0 = pool, 1 = t0, 2 = t1; z_id -1 / 0 = m0 / 1 = m1
-    int tail_no = 0;   // consecutive fused tails walk the tiles in alternating directions (tail_rev)
-    int rc_prev = -1, rc_prev2 = -1;   // blocks whose tails stored a1 instead of y (their successors rebuild the residual: BtailParams::rc)
-    const f16_t* rc_xs = nullptr;
+    // ---- trunk: the blocks of stages 1-4 as plan_trunk decided.  run_blocks launches blocks [l_begin, l_end) of stages [s_begin, s_end) for
+    // frames [b0, b0 + nb): every tensor of those frames lives at frame offset b0 of its buffer (b0 > 0: the stage-3 split's second chain).
+    const TrunkPlan tp = plan_trunk(a, m->blocks, m->cfg, m->sw, B, d.H2, d.W2, m->num_cus, m->taps != 0, m->profiling, m->stream2 != nullptr);
+    struct TrunkState { int cur_id; int ch, cw; int z_id; int prev_id; };   // cur_id / prev_id (the previous block's input) 0 = pool, 1 = t0, 2 = t1;
+                                                                            // z_id -1 / 0 = m0 / 1 = m1: the z a fused tail computed for the next block
     auto run_blocks = [&](int s_begin, int s_end, int b0, int nb, TrunkState& st, int l_begin = 0, int l_end = 1 << 30) -> int {
         auto trunk = [&](int id, size_t per_frame) { return (id == 0 ? m->d_pool : id == 1 ? m->d_t0 : m->d_t1) + (size_t)b0 * per_frame; };
         auto mid = [&](int id, size_t per_frame) { return (id ? m->d_m1 : m->d_m0) + (size_t)b0 * per_frame; };
@@ -814,41 +905,16 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
             for (int l = l_begin; l < a.depths[s] && l < l_end; ++l) {   // (a block range only makes sense with s_end == s_begin + 1)
                 const int bi = m->stage_first[s] + l;
                 const Block& b = m->blocks[bi];
-                const Block* nbk = bi + 1 < (int)m->blocks.size() ? &m->blocks[bi + 1] : nullptr;
+                const TrunkStep& t = tp.steps[bi];
                 const int ch = st.ch, cw = st.cw;
                 const int oh = (b.c1.stride == 2) ? down2(ch) : ch, ow = (b.c1.stride == 2) ? down2(cw) : cw;
-                const int C1 = b.c1.Cin, C2 = b.c2.Cout;
+                const int C1 = b.c1.Cin, C2 = b.c2.Cout, C3 = t.C3;
                 const f16_t* cur = trunk(st.cur_id, (size_t)ch * cw * b.c0.Cin);
                 const int out_id = st.cur_id == 1 ? 2 : 1;
                 f16_t* out = trunk(out_id, (size_t)oh * ow * C2);
-                const f16_t* res = cur;
-                // first block of stage 1 (64 -> 256 channels, stride 1): the shortcut runs inside the fused tail (kernels_btail.hip, SC)
-                const bool sc_in_tail = b.has_sc && m->fuse_shortcut && m->fuse_btail && b.bias2sc && b.sc.KH == 1 && b.sc.stride == 1 &&
-                                        b.sc.Cin == 64 && b.c1.Cin == 64 && b.c1.stride == 1 && b.c2.Cout == 256 && nbk && nbk->c0.wp &&
-                                        nbk->c0.Cin == 256 && nbk->c0.Cout == 64;
-                // first block of stages 3 / 4: the shortcut is extra K of the 1x1 expand (conv_gemm_dma_kernel, DUAL)
-                bool tail_kernel = m->fuse_btail && b.c1.KH == 3 && b.c1.Cout == C1 && b.c2.Cin == C1 && b.c2.Cout == 4 * C1 && b.c2.wp &&
-                                   opd_btail_supported(C1, 0);
-                // first block of stage 2: 3x3 + dual-source expand (+ the next reduce on its own) beats shortcut launch + fused tail
-                // (stage 2: 0.674 -> 0.657 ms; OPD_DUAL_OVER_TAIL=0 restores the tail)
-                if (m->dual_over_tail && tail_kernel && b.has_sc && !sc_in_tail && b.w2sc) tail_kernel = false;
-                // Stage 3: the eight-wave tail holds one 160-KiB workgroup per CU, so a launch costs whole ROUNDS of ~70 us whatever they hold.
-                // Rounds that are only partly filled because the batch does not divide into them are dealt with by the frame split below; what
-                // remains is the case of too few tiles for even one round (small frames / batches: the three launches win there).  The choice is
-                // made from the handle's configuration (max_batch and the frame size), never from the batch at hand: the two paths differ in
-                // the last bit (kernels_btail3.hip), and a frame's low-order bits must not depend on the batch it travels in.  Handles that
-                // keep several batches in flight (OPD_FLAG_MULTI_STREAM) always take the fused tail: other streams fill its idle CUs.
-                if (C1 == 256 && tail_kernel) {
-                    const long long tiles = ((long long)m->cfg.max_batch * oh * ow + 127) / 128;
-                    const bool pays = tiles * 10 >= (long long)m->num_cus * 6;
-                    if (m->tail3 == 0 || (m->tail3 == 1 && !pays && !(m->cfg.flags & OPD_FLAG_MULTI_STREAM))) tail_kernel = false;
-                }
-                const bool sc_in_expand = b.has_sc && m->fuse_shortcut && b.w2sc && !sc_in_tail && !tail_kernel;
-                if (b.has_sc && !sc_in_tail && !sc_in_expand) {
-                    f16_t* scb = m->d_sc + (size_t)b0 * oh * ow * C2;
-                    RCCHK(run_conv(m, b.sc, cur, nb, ch, cw, oh, ow, scb, false, nullptr));
-                    res = scb;
-                }
+                f16_t* const scb = m->d_sc + (size_t)b0 * oh * ow * C2;
+                if (t.sc == SC_LAUNCH) RCCHK(run_conv(m, b.sc, cur, nb, ch, cw, oh, ow, scb, false, nullptr));
+                const f16_t* res = t.res == RES_TRUNK ? cur : t.res == RES_SHORTCUT ? scb : nullptr;
                 int x1_id = st.z_id;
                 const f16_t* x1 = nullptr;
                 if (x1_id >= 0) {
@@ -860,48 +926,26 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
                     x1 = c0out;
                 }
                 st.z_id = -1;
-                const bool tail_ok = tail_kernel && (size_t)nb * ch * cw * C1 * 2 < 0x7ff00000ull;
-                if (tail_ok) {
-                    int C3 = 0;
-                    if (nbk && nbk->c0.wp && nbk->c0.Cin == 4 * C1 && opd_btail_supported(C1, nbk->c0.Cout)) C3 = nbk->c0.Cout;
-                    // (a sub-batch pipeline ends with stage 2: its last tail cannot hand z to stage 3 anyway — 256 channels)
+                if (t.path == PATH_TAIL) {
+                    const Block* nbk = C3 ? &m->blocks[bi + 1] : nullptr;
                     BtailParams p{}; p.dtype = m->dtype;
-                    p.x1 = x1; p.w1 = b.c1.w; p.b1 = b.c1.bias; p.w2p = C1 == 256 ? b.c2.wp : b.c2.w; p.b2 = b.c2.bias; p.res = res; p.y = out;   // (K-permuted copies: stage-3 kernel only)
-                    if (sc_in_tail) { p.res = nullptr; p.xs = cur; p.wsc = b.sc.w; p.b2 = b.bias2sc; }
+                    p.x1 = x1; p.w1 = b.c1.w; p.b1 = b.c1.bias; p.w2p = C1 == 256 ? b.c2.wp : b.c2.w; p.b2 = b.c2.bias; p.res = res;   // (K-permuted copies: stage-3 kernel only)
+                    p.y = t.store == STORE_A1 ? nullptr : out;
+                    if (t.sc == SC_TAIL) { p.xs = cur; p.wsc = b.sc.w; p.b2 = b.bias2sc; }
                     f16_t* z = mid(1 - x1_id, (size_t)oh * ow * C3);
                     if (C3) { p.w3p = C1 == 256 ? nbk->c0.wp : nbk->c0.w; p.b3 = nbk->c0.bias; p.z = z; }
-                    // Stage 1, residual rebuild (BtailParams::rc): block 0 stores its a1 (64 channels) instead of its output (256), block 1 rebuilds
-                    // that output chunk by chunk from a1 and the pooled map (the shortcut's input) as its residual.  Bit-identical results
-                    // (tests/test_kernels_gpu.py, OPD_TAIL_RC=0/1 end to end); 344 MB less HBM traffic per forward at batch 8.  The a1 tensor lives in
-                    // the shortcut buffer, which a fused shortcut leaves unused.
-                    // tail_rc == 2 (NOT the default: measured slower, opd_model.h) goes one block further: block 1 stores ITS a1 as well and block 2 (the last of stage 1, C3 = 128)
-                    // rebuilds both outputs (btail_rc2_kernel): stage 1 then moves 64-channel tensors only, plus the quarter of its last output
-                    // that the next stage's shortcut reads -- another 276 MB less per forward.
-                    const bool rc_ok = m->tail_rc && s == 0 && C1 == 64 && a.depths[0] >= 2 && !m->taps;
-                    const bool rc2_ok = rc_ok && m->tail_rc >= 2 && a.depths[0] == 3;
-                    f16_t* const a1_keep0 = m->d_sc + (size_t)b0 * oh * ow * 64;                                          // block 0's a1
-                    f16_t* const a1_keep1 = m->d_sc + (size_t)m->cfg.max_batch * oh * ow * 64 + (size_t)b0 * oh * ow * 64;   // block 1's a1 (behind the whole batch's block-0 tensor)
-                    if (rc_ok && C3 == 64 && sc_in_tail && l == 0) { p.y = nullptr; p.a1_out = a1_keep0; rc_prev = bi; rc_xs = cur; }
-                    else if (rc_ok && C3 == 64 && l == 1 && rc_prev == bi - 1 && !b.has_sc) {
+                    // stage 1's a1 hand-over (STORE_A1 -> RES_REBUILD) lives in the shortcut buffer, which a fused shortcut leaves unused
+                    f16_t* const a1_keep = m->d_sc + (size_t)b0 * oh * ow * C1;
+                    if (t.store == STORE_A1) p.a1_out = a1_keep;
+                    if (t.res == RES_REBUILD) {
                         const Block& pb = m->blocks[bi - 1];
-                        p.res = nullptr; p.rc = 1; p.rc_a1[0] = a1_keep0; p.rc_xs = rc_xs; p.rc_w2[0] = pb.c2.w; p.rc_wsc = pb.sc.w; p.rc_b[0] = pb.bias2sc;
-                        if (rc2_ok && nbk && !nbk->has_sc && nbk->c1.Cin == 64) { p.y = nullptr; p.a1_out = a1_keep1; rc_prev2 = bi; }
-                    } else if (rc2_ok && C3 == 128 && l == 2 && rc_prev2 == bi - 1 && rc_prev == bi - 2 && !b.has_sc) {
-                        const Block &p1 = m->blocks[bi - 1], &p0 = m->blocks[bi - 2];
-                        p.res = nullptr; p.rc = 2; p.rc_xs = rc_xs; p.rc_wsc = p0.sc.w;
-                        p.rc_a1[0] = a1_keep1; p.rc_w2[0] = p1.c2.w; p.rc_b[0] = p1.c2.bias;
-                        p.rc_a1[1] = a1_keep0; p.rc_w2[1] = p0.c2.w; p.rc_b[1] = p0.bias2sc;
+                        p.rc = 1; p.rc_a1 = a1_keep; p.rc_xs = trunk(st.prev_id, (size_t)ch * cw * pb.c0.Cin); p.rc_w2 = pb.c2.w; p.rc_wsc = pb.sc.w; p.rc_b = pb.bias2sc;
                     }
-                    // The last block of stage 1 hands the next stage its reduce output z (fused above); the block output itself is then read
-                    // by that stage's stride-2 shortcut only, i.e. at even (oh, ow): the other three quarters of its 274 MB are not stored.
-                    if (m->y_stride2 && C3 && b.c1.stride == 1 && l + 1 == a.depths[s] && nbk && nbk->has_sc && nbk->sc.stride == 2 && nbk->sc.KH == 1 &&
-                        nbk->c1.stride == 2 && !m->taps)
-                        p.y_stride2 = 1;
+                    p.y_stride2 = t.store == STORE_Y_STRIDE2;
                     p.B = nb; p.H = ch; p.W = cw; p.OH = oh; p.OW = ow; p.stride = b.c1.stride; p.M = nb * oh * ow; p.C1 = C1; p.C3 = C3;
-                    p.rev = m->tail_rev ? (tail_no++ & 1) : 0;
-                    p.dbg = m->dbg_btail;
-                    p.nw = (C1 == 256 || p.rc == 2) ? 0 : m->tail_nw;
-                    RCCHK(timed_begin(m, CLS_CONV, 2.0 * p.M * ((double)C1 * 9 * C1 + 4.0 * C1 * C1 + 4.0 * C1 * C3 + (sc_in_tail ? 64.0 * 256 : 0.0))));
+                    p.rev = b0 ? t.rev_b : t.rev;
+                    p.dbg = m->sw.dbg_btail;
+                    RCCHK(timed_begin(m, CLS_CONV, 2.0 * p.M * ((double)C1 * 9 * C1 + 4.0 * C1 * C1 + 4.0 * C1 * C3 + (t.sc == SC_TAIL ? 64.0 * 256 : 0.0))));
                     HIPCHK(opd_launch_btail(p, m->stream));
                     RCCHK(timed_end(m));
                     if (p.y) RCCHK(tap(m, "btail_y", out, (size_t)p.M * 4 * C1 * 2));
@@ -910,12 +954,12 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
                 } else {
                     f16_t* a1 = mid(1 - x1_id, (size_t)oh * ow * C1);
                     RCCHK(run_conv(m, b.c1, x1, nb, ch, cw, oh, ow, a1, true, nullptr, s));
-                    if (sc_in_expand) {
+                    if (t.path == PATH_DUAL) {
                         ConvGemmParams p{}; p.dtype = m->dtype;
                         p.x = a1; p.w = b.w2sc; p.bias = b.bias2sc; p.out = out; p.zero16 = m->zero_bias;
                         p.B = nb; p.H = oh; p.W = ow; p.Cin = C1; p.OH = oh; p.OW = ow; p.N = C2; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
                         p.M = nb * oh * ow; p.K1 = C1; p.K = C1 + b.sc.Cin; p.relu = 1;
-                        p.x2 = cur; p.H2 = ch; p.W2 = cw; p.Cin2 = b.sc.Cin; p.stride2 = b.sc.stride; p.dbg = m->dbg_gemm; p.wprefetch = m->wprefetch & 1;
+                        p.x2 = cur; p.H2 = ch; p.W2 = cw; p.Cin2 = b.sc.Cin; p.stride2 = b.sc.stride; p.dbg = m->sw.dbg_gemm; p.wprefetch = m->sw.wprefetch & 1;
                         RCCHK(timed_begin(m, CLS_CONV, 2.0 * p.M * (double)C2 * p.K));
                         HIPCHK(opd_launch_conv_gemm(p, m->stream));
                         RCCHK(timed_end(m));
@@ -924,75 +968,38 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
                         RCCHK(run_conv(m, b.c2, a1, nb, oh, ow, oh, ow, out, true, res));
                     }
                 }
-                st.cur_id = out_id; st.ch = oh; st.cw = ow;
+                st.prev_id = st.cur_id; st.cur_id = out_id; st.ch = oh; st.cw = ow;
             }
             if (b0 + nb == B && l_end >= a.depths[s]) MARK(2 + s);
         }
         return OPD_OK;
     };
-    TrunkState st{0, d.H2, d.W2, -1};
-    {
-        const int sub = (m->trunk_subbatch > 0 && m->trunk_subbatch < B && B % m->trunk_subbatch == 0) ? m->trunk_subbatch : B;
-        TrunkState done = st;
-        for (int b0 = 0; b0 < B; b0 += sub) {
-            TrunkState t = st;
-            RCCHK(run_blocks(0, 2, b0, sub, t));
-            done = t;
-        }
-        st = done;
-        st.z_id = -1;   // (stage 2's last tail has no fused reduce)
-        // Stage 3.  Frame split: with the fused tails a launch of T tiles costs ceil(T / CUs) rounds, and batch 8 at 800x1333 is 263 tiles on
-        // 256 CUs.  Frames are independent, so blocks 1 .. n-1 of the stage (all tensors there have one per-frame size, the buffers of the
-        // two chains never overlap) run as TWO chains on two streams -- frames [0, nbA) = whole rounds, the rest on `stream2` -- whose
-        // workgroups the hardware packs onto whatever CU is free: 5 tails of 263 workgroup-lives take ~5.3 rounds instead of 10.  Per-row
-        // arithmetic does not depend on the tiling, so this is invisible in the results (any batch, any split).  Captured into the graph
-        // as a fork / join; not under profiling (event pairs on one stream) or diagnostic taps, and not for handles that keep several batches
-        // in flight (there other handles' kernels fill the idle CUs; measured on one box, 1000 steps x 2: three streams 2841 frames/s with
-        // one launch per tail, 2783 with the split, 2793 unfused; one stream 2045 / 2112 / 2090).
-        int nbA = B;
-        {
-            const Block& b1 = m->blocks[m->stage_first[2] + (a.depths[2] > 1 ? 1 : 0)];
-            const int oh3 = down2(st.ch), ow3 = down2(st.cw);
-            const bool fused3 = m->fuse_btail && a.depths[2] > 2 && b1.c1.Cin == 256 && opd_btail_supported(256, 0) && b1.c2.wp && m->profiling != 1 && !m->taps &&
-                                m->stream2 && m->tail3_split && !(m->cfg.flags & OPD_FLAG_MULTI_STREAM) && B >= 2 && [&] {   // the policy of run_blocks, evaluated for this stage
-                                    const long long tiles = ((long long)m->cfg.max_batch * oh3 * ow3 + 127) / 128;
-                                    return m->tail3 == 2 || (m->tail3 == 1 && (tiles * 10 >= (long long)m->num_cus * 6 || (m->cfg.flags & OPD_FLAG_MULTI_STREAM)));
-                                }();
-            if (fused3) {
-                auto tiles_of = [&](int frames) { return ((long long)frames * oh3 * ow3 + 127) / 128; };
-                const long long total = tiles_of(B), cus = m->num_cus, last = total % cus;
-                if (total > cus && last > 0 && last < cus / 2) {
-                    const long long whole = (total / cus) * cus;
-                    int bA = B - 1;
-                    while (bA > 1 && tiles_of(bA) > whole) --bA;
-                    if (tiles_of(bA) <= whole) nbA = bA;
-                }
-            }
-        }
-        RCCHK(run_blocks(2, 3, 0, B, st, 0, 1));   // first block (stride 2, shortcut): whole batch
-        if (nbA < B) {
-            TrunkState ta = st, tb = st;
-            HIPCHK(hipEventRecord(m->ev_fork, m->stream));
-            HIPCHK(hipStreamWaitEvent(m->stream2, m->ev_fork, 0));
-            // whatever happens in either chain, `stream2` is rejoined before this function returns (an unjoined fork would leak into
-            // the next forward's events, or leave a capture with a dangling branch) and m->stream is the main stream again
-            hipStream_t main_stream = m->stream;
-            const int rc_a = run_blocks(2, 3, 0, nbA, ta, 1);
-            m->stream = m->stream2;
-            const int rc_b = rc_a == OPD_OK ? run_blocks(2, 3, nbA, B - nbA, tb, 1) : OPD_OK;
-            m->stream = main_stream;
-            const hipError_t ej = hipEventRecord(m->ev_join, m->stream2);
-            const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(m->stream, m->ev_join, 0) : ej;
-            RCCHK(rc_a);
-            RCCHK(rc_b);
-            HIPCHK(ew);
-            MARK(4);   // (stage 3 ends at the join, not where the second chain's own mark fell)
-            st = ta;
-        } else {
-            RCCHK(run_blocks(2, 3, 0, B, st, 1));
-        }
-        RCCHK(run_blocks(3, 4, 0, B, st));
+    TrunkState st{0, d.H2, d.W2, -1, -1};
+    RCCHK(run_blocks(0, 2, 0, B, st));
+    const int nbA = tp.split;
+    RCCHK(run_blocks(2, 3, 0, B, st, 0, 1));   // first block (stride 2, shortcut): whole batch
+    if (nbA < B) {
+        TrunkState ta = st, tb = st;
+        HIPCHK(hipEventRecord(m->ev_fork, m->stream));
+        HIPCHK(hipStreamWaitEvent(m->stream2, m->ev_fork, 0));
+        // whatever happens in either chain, `stream2` is rejoined before this function returns (an unjoined fork would leak into
+        // the next forward's events, or leave a capture with a dangling branch) and m->stream is the main stream again
+        hipStream_t main_stream = m->stream;
+        const int rc_a = run_blocks(2, 3, 0, nbA, ta, 1);
+        m->stream = m->stream2;
+        const int rc_b = rc_a == OPD_OK ? run_blocks(2, 3, nbA, B - nbA, tb, 1) : OPD_OK;
+        m->stream = main_stream;
+        const hipError_t ej = hipEventRecord(m->ev_join, m->stream2);
+        const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(m->stream, m->ev_join, 0) : ej;
+        RCCHK(rc_a);
+        RCCHK(rc_b);
+        HIPCHK(ew);
+        MARK(4);   // (stage 3 ends at the join, not where the second chain's own mark fell)
+        st = ta;
+    } else {
+        RCCHK(run_blocks(2, 3, 0, B, st, 1));
     }
+    RCCHK(run_blocks(3, 4, 0, B, st));
     const f16_t* cur = st.cur_id == 1 ? m->d_t0 : m->d_t1;
     const int ch = st.ch, cw = st.cw;
     // ---- input projection -> encoder ------------------------------------------------------------------------------
@@ -1001,7 +1008,7 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
     // reads that for its q / k column tiles and x for its v tiles, with a plain bias vector -- instead of x everywhere plus a [hw][768]
     // fp32 table W.pos + b added per output tile (two divisions and 16 dependent table loads per lane in front of the first MFMA:
     // 14.2 us per launch against 9.4 for the same GEMM with a bias vector; decoder K/V 44.7 against 24-27)
-    const bool shadow = m->pos_shadow && D == 256 && m->enc[0].bqkv && m->bkv_all;
+    const bool shadow = m->sw.pos_shadow && D == 256 && m->enc[0].bqkv && m->bkv_all;
     const PosShadow psh{plan->d_pos, pos_ptrs, hw, m->d_xp16};
     const PosShadow* ps = shadow ? &psh : nullptr;
     // Deep-K row-owner launches (kernels_rowln.hip::gemm_ln256_ring_kernel) for the two K = 2048 -> 256 linears of the encoder side:
@@ -1022,9 +1029,9 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
     // each -- at max_batch = 1 that is 22 workgroups walking 2.2 MB apiece (42 us per layer, 27 us for the input projection).  Where the handle's
     // CONFIGURATION bounds the token count below ~1400 the same linears run as tiled GEMMs with the reduction split eight ways over workgroups
     // and the fixed-order reduce + LayerNorm kernel (the round-1 path): encoder stage 0.41 -> 0.32 ms at batch 1.  Never per batch.
-    const bool small_enc = m->small_enc && (size_t)m->cfg.max_batch * m->stage_px[3] <= 1400;
+    const bool small_enc = m->sw.small_enc && (size_t)m->cfg.max_batch * m->stage_px[3] <= 1400;
     const int enc_splits = small_enc ? 8 : 4;
-    const bool deep_ok = m->deep_fc2 && D == 256 && !small_enc;
+    const bool deep_ok = m->sw.deep_fc2 && D == 256 && !small_enc;
     if (deep_ok && m->proj.K % 64 == 0 && (size_t)M * m->proj.K * 2 < 0x7fffff00ull)
         RCCHK(run_deep(cur, nullptr, m->proj.w, m->proj.bias, m->proj.K, nullptr, nullptr, CLS_CONV));
     else
@@ -1039,10 +1046,10 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
         else
             RCCHK(run_gemm(m, m->d_x16, L.wqkv, plan->rb_enc[i], hw, M, 3 * D, D, m->d_qkv16, false, false, nullptr, enc_bias_ptrs[i], 3 * D, 2 * D));   // (pos enters q and k only)
         RCCHK(run_attn(m, m->d_qkv16, 3 * D, m->d_qkv16 + D, 3 * D, m->d_qkv16 + 2 * D, 3 * D, m->d_attn16, D, B, hw, hw, d_keyv, cw));
-        const bool ffn_fused = m->fused_enc_ffn && m->fuse_gemm_ln && L.ffn_pack && D == 256 && !small_enc;
-        const bool front = ffn_fused && L.front && m->enc_front;   // the output projection + LayerNorm run inside the FFN launch
+        const bool ffn_fused = m->sw.fused_enc_ffn && m->sw.fuse_gemm_ln && L.ffn_pack && D == 256 && !small_enc;
+        const bool front = ffn_fused && L.front && m->sw.enc_front;   // the output projection + LayerNorm run inside the FFN launch
         if (front) {
-        } else if (m->fuse_gemm_ln && D == 256) {
+        } else if (m->sw.fuse_gemm_ln && D == 256) {
             RCCHK(run_gemm_ln(m, m->d_attn16, L.o.w, L.o.b, M, D, m->d_x32, L.ln1, m->d_x32, m->d_x16));
         } else {
             RCCHK(run_gemm(m, m->d_attn16, L.o.w, L.o.b, 0, M, D, D, m->d_y32, true, false, m->d_x32));
@@ -1052,7 +1059,7 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
         }
         if (ffn_fused) {
             // the whole FFN block as ONE row-owner launch: the [M][F] hidden tensor never leaves LDS (kernels_rowln.hip::enc_ffn_kernel)
-            EncFfnParams fp{}; fp.dtype = m->dtype; fp.wprefetch = (m->wprefetch >> 1) & 1;
+            EncFfnParams fp{}; fp.dtype = m->dtype; fp.wprefetch = (m->sw.wprefetch >> 1) & 1;
             fp.x = m->d_x16; fp.wpack = L.ffn_pack; fp.b2 = L.fc2.b; fp.res32 = m->d_x32; fp.gamma = L.ln2.g; fp.beta = L.ln2.b;
             fp.y32 = m->d_x32; fp.y16 = m->d_x16; fp.M = M; fp.F = F; fp.pack_tail = L.tail; fp.pack_front = L.front;
             if (front) { fp.attn = m->d_attn16; fp.bo = L.o.b; fp.gamma1 = L.ln1.g; fp.beta1 = L.ln1.b; }
@@ -1060,7 +1067,7 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
             const bool last = i + 1 == a.enc_layers;
             qkv_done = false;
             // the tail projection: what consumes this block's output (only on the position-shadow path: x + pos with plain bias vectors)
-            if (ps && m->enc_tail && L.tail && L.tail_ld == (last ? NKV : 3 * D) && (last ? (size_t)M * NKV * 2 < (1ull << 32) : true)) {
+            if (ps && m->sw.enc_tail && L.tail && L.tail_ld == (last ? NKV : 3 * D) && (last ? (size_t)M * NKV * 2 < (1ull << 32) : true)) {
                 fp.tail = L.tail; fp.tail_pos = L.tail_pos; fp.tail_ld = L.tail_ld;
                 fp.tail_out = last ? m->d_memkv16 : m->d_qkv16;
                 for (int t = 0; t < L.tail; ++t) fp.tail_col[t] = L.tail_col[t];
@@ -1090,17 +1097,17 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
         RCCHK(run_gemm(m, m->d_xp16, m->wkv_all, m->bkv_all, 0, M, NKV, D, m->d_memkv16, false, false, nullptr, nullptr, 0, 0, m->d_x16, 2 * D, D));
     else
         RCCHK(run_gemm(m, m->d_x16, m->wkv_all, plan->rb_kv, hw, M, NKV, D, m->d_memkv16, false, false, nullptr, kv_bias_ptrs, 2 * D, D));   // (per layer [k | v]: pos enters k only)
-    const bool dec0 = m->fuse_dec0 && m->dec0_h && D == 256;
+    const bool dec0 = m->sw.fuse_dec0 && m->dec0_h && D == 256;
     // The fused decoder (kernels_dec.hip): five launches per layer on split fp16 operands; layer 0 starts at its cross-attention (its
     // self-attention block and its queries are constants of the weights).  Taken when the architecture fits the kernels' fixed shapes.
-    const bool fused_dec = m->fused_dec && dec0 && m->qc0 && a.heads == 8 && Q <= 128 && (Q & 3) == 0 && F % OPD_DEC_FFN_CHUNK == 0 && F / OPD_DEC_FFN_CHUNK <= 16 && m->dec_splits <= 6 && D == 256 && m->dec[0].wqkv_f &&
+    const bool fused_dec = m->sw.fused_dec && dec0 && m->qc0 && a.heads == 8 && Q <= 128 && (Q & 3) == 0 && F % OPD_DEC_FFN_CHUNK == 0 && F / OPD_DEC_FFN_CHUNK <= 16 && m->sw.dec_splits <= 6 && D == 256 && m->dec[0].wqkv_f &&
                            (size_t)M * NKV * 2 < (1ull << 32);
     const float* dec_final_h = m->d_h32;   // the state the heads read (fused: before the last FFN, whose partial sums travel with it)
     if (fused_dec) {
-        const int S = m->dec_splits, nchunk = F / OPD_DEC_FFN_CHUNK;
+        const int S = m->sw.dec_splits, nchunk = F / OPD_DEC_FFN_CHUNK;
         float* hbuf[2] = {m->d_h32, m->d_yd32};
         int cur = 0;   // hbuf[cur] holds the layer's state from its self-attention block on
-        for (int i = 0; i < a.dec_layers && i < m->dbg_dec_layers; ++i) {
+        for (int i = 0; i < a.dec_layers && i < m->sw.dbg_dec_layers; ++i) {
             const DecLayer& L = m->dec[i];
             f16_t* qd = m->d_qd16 + (size_t)i * m->cfg.max_batch * Q * D;   // (per-layer regions of max_batch frames: layer 0's constants stay put)
             if (i > 0) {
@@ -1165,14 +1172,14 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
         HIPCHK(hipMemsetAsync(m->d_h32, 0, (size_t)Md * D * 4, m->stream));
         HIPCHK(hipMemsetAsync(m->d_h16, 0, (size_t)Md * D * 2, m->stream));
     }
-    for (int i = 0; i < a.dec_layers && i < m->dbg_dec_layers; ++i) {
+    for (int i = 0; i < a.dec_layers && i < m->sw.dbg_dec_layers; ++i) {
         const DecLayer& L = m->dec[i];
-        const bool small = m->small_m_gemm && D == 256 && F % 256 == 0 && F / 256 <= 8;
+        const bool small = m->sw.small_m_gemm && D == 256 && F % 256 == 0 && F / 256 <= 8;
         if (!(dec0 && i == 0)) {   // (layer 0's self-attention block is the broadcast above)
         if (small) RCCHK(run_small_gemm(m, m->d_h16, L.wqkv, L.rb_self, Q, Md, 3 * D, D, m->d_qkvd16, false));
         else RCCHK(run_gemm(m, m->d_h16, L.wqkv, L.rb_self, Q, Md, 3 * D, D, m->d_qkvd16, false, false, nullptr));
         RCCHK(run_attn(m, m->d_qkvd16, 3 * D, m->d_qkvd16 + D, 3 * D, m->d_qkvd16 + 2 * D, 3 * D, m->d_attnd16, D, B, Q, Q));
-        if (m->fuse_gemm_ln && D == 256)
+        if (m->sw.fuse_gemm_ln && D == 256)
             RCCHK(run_gemm_ln(m, m->d_attnd16, L.so.w, L.so.b, Md, D, m->d_h32, L.ln1, m->d_h32, m->d_h16));
         else
             RCCHK(run_gemm_splitk_ln(m, m->d_attnd16, L.so.w, L.so.b, Md, D, D, 4, m->d_h32, &L.ln1, m->d_h32, m->d_h16, CLS_GEMM));
@@ -1182,7 +1189,7 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
         else RCCHK(run_gemm(m, m->d_h16, L.wq_c, L.rb_q, Q, Md, D, D, qd, false, false, nullptr));
         RCCHK(run_attn(m, qd, D, m->d_memkv16 + (size_t)i * 2 * D, NKV, m->d_memkv16 + (size_t)i * 2 * D + D, NKV,
                        m->d_attnd16, D, B, Q, hw, d_keyv, cw));
-        if (m->fuse_gemm_ln && D == 256)
+        if (m->sw.fuse_gemm_ln && D == 256)
             RCCHK(run_gemm_ln(m, m->d_attnd16, L.co.w, L.co.b, Md, D, m->d_h32, L.ln2, m->d_h32, m->d_h16));
         else
             RCCHK(run_gemm_splitk_ln(m, m->d_attnd16, L.co.w, L.co.b, Md, D, D, 4, m->d_h32, &L.ln2, m->d_h32, m->d_h16, CLS_GEMM));
@@ -1200,7 +1207,7 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
         const DecLayer& P = m->dec[a.dec_layers - 1];
         hp.hs = dec_final_h; hp.partials = m->d_ffn_part; hp.nsplit = F / OPD_DEC_FFN_CHUNK; hp.ffn_b2 = P.fc2.b; hp.ln3_gamma = P.ln3.g; hp.ln3_beta = P.ln3.b;
         hp.ln_gamma = m->dec_ln.g; hp.ln_beta = m->dec_ln.b;
-    } else if (m->fuse_gemm_ln) {   // the final LayerNorm runs inside the heads kernel
+    } else if (m->sw.fuse_gemm_ln) {   // the final LayerNorm runs inside the heads kernel
         hp.hs = m->d_h32; hp.ln_gamma = m->dec_ln.g; hp.ln_beta = m->dec_ln.b;
     } else {
         RCCHK(timed_begin(m, CLS_OTHER, 0.0));
@@ -1209,7 +1216,7 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
         hp.hs = m->d_hs32;
     } hp.wc = m->wc; hp.bc = m->bc; hp.w1 = m->w1; hp.b1 = m->b1; hp.w2 = m->w2; hp.b2 = m->b2;
     hp.w3 = m->w3; hp.b3 = m->b3; hp.logits = m->d_logits; hp.boxes = m->d_boxes; hp.rows = Md; hp.ncls = a.ncls;
-    if (m->heads2 && m->wc_f && m->w1_f && m->w2_f) { hp.wc_f = m->wc_f; hp.w1_f = m->w1_f; hp.w2_f = m->w2_f; }
+    if (m->sw.heads2 && m->wc_f && m->w1_f && m->w2_f) { hp.wc_f = m->wc_f; hp.w1_f = m->w1_f; hp.w2_f = m->w2_f; }
     RCCHK(timed_begin(m, CLS_OTHER, 2.0 * Md * 256.0 * (a.ncls + 256 + 256 + 4)));
     HIPCHK(opd_launch_heads(hp, m->stream));
     RCCHK(timed_end(m));
@@ -1473,6 +1480,38 @@ static int guarded(const char* what, F&& body) {
         return fail(OPD_EINVAL, std::string(what) + ": unknown C++ exception");
     }
 }
+// The forward-plan switches: defaults, overridden by environment variables (A/B switches for benchmarking and ablations)
+static Switches read_switches(int flags) {
+    Switches sw;
+    auto env = [](const char* name, int* v) { if (const char* e = getenv(name)) *v = atoi(e); };
+    env("OPD_DUAL_OVER_TAIL", &sw.dual_over_tail);
+    env("OPD_TAIL_REV", &sw.tail_rev);
+    env("OPD_TAIL3", &sw.tail3);
+    env("OPD_TAIL_RC", &sw.tail_rc);
+    sw.tail_rc = sw.tail_rc != 0;
+    env("OPD_WPREFETCH", &sw.wprefetch);
+    env("OPD_W8", &sw.w8);
+    if (sw.w8 < 0) sw.w8 = (flags & OPD_FLAG_MULTI_STREAM) ? 1 : 0;
+    env("OPD_SMALL_SPLITK", &sw.small_splitk);
+    env("OPD_SMALL_ENC", &sw.small_enc);
+    env("OPD_Y_STRIDE2", &sw.y_stride2);
+    env("OPD_TAIL3_SPLIT", &sw.tail3_split);
+    env("OPD_FUSE_PREP", &sw.fuse_prep);
+    env("OPD_POS_SHADOW", &sw.pos_shadow);
+    env("OPD_DEEP_FC2", &sw.deep_fc2);
+    env("OPD_WROUND", &sw.wround);
+    env("OPD_FUSED_DEC", &sw.fused_dec);
+    env("OPD_FUSED_ENC_FFN", &sw.fused_enc_ffn);
+    env("OPD_ENC_TAIL", &sw.enc_tail);
+    env("OPD_ENC_FRONT", &sw.enc_front);
+    env("OPD_HEADS2", &sw.heads2);
+    env("OPD_DBG_DEC_LAYERS", &sw.dbg_dec_layers);   // timing ablation (tools/dec_cost.sh): results are wrong
+    env("OPD_DBG_BTAIL", &sw.dbg_btail);             // timing ablations of the whole forward: BtailParams::dbg / ConvGemmParams::dbg
+    env("OPD_DBG_SKIP", &sw.dbg_skip);               // bit i: no kernel launches in segment i of stage_ms (stem, stages 1-4, encoder, decoder, post-process)
+    env("OPD_DBG_GEMM", &sw.dbg_gemm);               // of every fused tail / implicit-GEMM launch (results are wrong)
+    return sw;
+}
+
 extern "C" {
 
 const char* opd_version(void) { return "opd_hip 0.2 gfx950 (fp16 MFMA operands, fp32 accumulate; OPD_FLAG_BF16: bf16 operands)"; }
@@ -1501,32 +1540,7 @@ static int create_impl(const opd_config* cfg, const char* weights_path, int devi
     if (rc) return fail(rc, err);
     m->cfg = *cfg;
     m->dtype = (cfg->flags & OPD_FLAG_BF16) ? OPD_DT_BF16 : OPD_DT_F16;
-    if (const char* v = getenv("OPD_TRUNK_SUBBATCH")) m->trunk_subbatch = atoi(v);   // A/B switches for benchmarking
-    if (const char* v = getenv("OPD_DUAL_OVER_TAIL")) m->dual_over_tail = atoi(v);
-    if (const char* v = getenv("OPD_TAIL_REV")) m->tail_rev = atoi(v);
-    if (const char* v = getenv("OPD_TAIL3")) m->tail3 = atoi(v);
-    if (const char* v = getenv("OPD_TAIL_RC")) m->tail_rc = atoi(v);
-    if (const char* v = getenv("OPD_WPREFETCH")) m->wprefetch = atoi(v);
-    if (const char* v = getenv("OPD_TAIL_NW")) m->tail_nw = atoi(v) == 8 ? 8 : 4;
-    if (const char* v = getenv("OPD_W8")) m->w8 = atoi(v);
-    if (m->w8 < 0) m->w8 = (cfg->flags & OPD_FLAG_MULTI_STREAM) ? 1 : 0;
-    if (const char* v = getenv("OPD_SMALL_SPLITK")) m->small_splitk = atoi(v);
-    if (const char* v = getenv("OPD_SMALL_ENC")) m->small_enc = atoi(v);
-    if (const char* v = getenv("OPD_Y_STRIDE2")) m->y_stride2 = atoi(v);
-    if (const char* v = getenv("OPD_TAIL3_SPLIT")) m->tail3_split = atoi(v);
-    if (const char* v = getenv("OPD_FUSE_PREP")) m->fuse_prep = atoi(v);
-    if (const char* v = getenv("OPD_POS_SHADOW")) m->pos_shadow = atoi(v);
-    if (const char* v = getenv("OPD_DEEP_FC2")) m->deep_fc2 = atoi(v);
-    if (const char* v = getenv("OPD_WROUND")) m->wround = atoi(v);
-    if (const char* v = getenv("OPD_FUSED_DEC")) m->fused_dec = atoi(v);
-    if (const char* v = getenv("OPD_FUSED_ENC_FFN")) m->fused_enc_ffn = atoi(v);
-    if (const char* v = getenv("OPD_ENC_TAIL")) m->enc_tail = atoi(v);
-    if (const char* v = getenv("OPD_ENC_FRONT")) m->enc_front = atoi(v);
-    if (const char* v = getenv("OPD_HEADS2")) m->heads2 = atoi(v);
-    if (const char* v = getenv("OPD_DBG_DEC_LAYERS")) m->dbg_dec_layers = atoi(v);   // timing ablation (tools/dec_cost.sh): results are wrong
-    if (const char* v = getenv("OPD_DBG_BTAIL")) m->dbg_btail = atoi(v);             // timing ablations of the whole forward: BtailParams::dbg / ConvGemmParams::dbg
-    if (const char* v = getenv("OPD_DBG_SKIP")) m->dbg_skip = atoi(v);               // bit i: no kernel launches in segment i of stage_ms (stem, stages 1-4, encoder, decoder, post-process)
-    if (const char* v = getenv("OPD_DBG_GEMM")) m->dbg_gemm = atoi(v);               // of every fused tail / implicit-GEMM launch (results are wrong)
+    m->sw = read_switches(cfg->flags);
     m->device = device_ordinal;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -1566,13 +1580,11 @@ static int clone_impl(const opd_detr* src, opd_detr** out) {
     m->weights = src->weights; m->weights_sealed = true; m->weight_bytes = src->weight_bytes;
     m->stem = src->stem; m->blocks = src->blocks; m->stage_first = src->stage_first; m->proj = src->proj;
     m->enc = src->enc; m->dec = src->dec; m->wkv_all = src->wkv_all; m->bkv_all = src->bkv_all; m->dec_ln = src->dec_ln;
-    m->wc = src->wc; m->bc = src->bc; m->w1 = src->w1; m->b1 = src->b1; m->w2 = src->w2; m->b2 = src->b2; m->w3 = src->w3; m->b3 = src->b3; m->wc_f = src->wc_f; m->w1_f = src->w1_f; m->w2_f = src->w2_f; m->heads2 = src->heads2;
+    m->wc = src->wc; m->bc = src->bc; m->w1 = src->w1; m->b1 = src->b1; m->w2 = src->w2; m->b2 = src->b2; m->w3 = src->w3; m->b3 = src->b3; m->wc_f = src->wc_f; m->w1_f = src->w1_f; m->w2_f = src->w2_f;
     m->zero_bias = src->zero_bias;
     m->h_enc_cat_w = src->h_enc_cat_w; m->h_enc_cat_b = src->h_enc_cat_b; m->h_kv_cat_w = src->h_kv_cat_w; m->h_kv_cat_b = src->h_kv_cat_b;
-    m->small_m_gemm = src->small_m_gemm; m->fuse_gemm_ln = src->fuse_gemm_ln; m->deep_fc2 = src->deep_fc2;
-    m->fuse_btail = src->fuse_btail; m->fuse_shortcut = src->fuse_shortcut; m->fuse_stem_pool = src->fuse_stem_pool; m->fuse_prep = src->fuse_prep; m->pos_shadow = src->pos_shadow; m->trunk_subbatch = src->trunk_subbatch; m->dual_over_tail = src->dual_over_tail; m->tail_rev = src->tail_rev; m->tail3 = src->tail3; m->num_cus = src->num_cus; m->tail3_split = src->tail3_split;
-    m->dec0_h = src->dec0_h; m->fuse_dec0 = src->fuse_dec0; m->qc0 = src->qc0; m->fused_dec = src->fused_dec; m->fused_enc_ffn = src->fused_enc_ffn; m->enc_tail = src->enc_tail; m->enc_front = src->enc_front; m->dec_splits = src->dec_splits; m->wround = src->wround; m->dbg_dec_layers = src->dbg_dec_layers; m->dbg_skip = src->dbg_skip;
-    m->tail_rc = src->tail_rc; m->y_stride2 = src->y_stride2; m->dbg_btail = src->dbg_btail; m->dbg_gemm = src->dbg_gemm; m->wprefetch = src->wprefetch; m->w8 = src->w8; m->tail_nw = src->tail_nw; m->small_splitk = src->small_splitk; m->small_enc = src->small_enc;
+    m->dec0_h = src->dec0_h; m->qc0 = src->qc0;
+    m->sw = src->sw; m->num_cus = src->num_cus;
     auto cleanup = [&](int code) {
         for (void* p : m->allocs) (void)hipFree(p);
         drop_streams(m.get());

@@ -59,6 +59,12 @@ struct Block {
     float* bias2sc = nullptr;   // c2.bias + sc.bias (fp32): the fused bottleneck tail adds the shortcut GEMM into the expand's accumulators
     f16_t* w2sc = nullptr;      // [Cout][c2.K + sc.Cin] = [W2 | Wsc] per output channel: the dual-source expand GEMM of stages 3-4
 };
+// Which packed weight forms build_weights creates: one rule each, read by build_weights and by plan_trunk (which must not probe pointers)
+inline bool conv_has_kperm(const Conv& c) { return c.KH == 1 && c.KW == 1 && c.Cin % 32 == 0 && c.Cin <= 1024; }   // Conv::wp
+inline bool block_has_bias2sc(const Block& b) { return b.has_sc && b.sc.Cout == b.c2.Cout; }                      // Block::bias2sc
+inline bool block_has_w2sc(const Block& b) {                                                                       // Block::w2sc
+    return block_has_bias2sc(b) && b.sc.KH == 1 && b.c2.KH == 1 && b.c2.Cout % 128 == 0 && b.c2.Cin >= 128;
+}
 struct EncLayer {
     f16_t* wqkv = nullptr;  // [768][256] = [Wq; Wk; Wv]
     float* bqkv = nullptr;  // [768] = [bq; bk; bv] (pos_shadow path: plain bias vector)
@@ -97,6 +103,69 @@ struct Dims {
 
 inline int down2(int n) { return (n - 1) / 2 + 1; }
 
+// Switches of the forward plan: read from the environment by read_switches at opd_detr_create, copied whole by opd_detr_clone, flipped
+// one by one by the test hooks (opd_test_api.cpp).
+struct Switches {
+    int small_m_gemm = 1;    // decoder linears (M = B x queries): one-shot K = 256 kernel (0: the general k-loop kernel)
+    int fuse_gemm_ln = 1;    // attention output projections: Linear + residual + LayerNorm in one kernel (0: GEMM, then LN)
+    int deep_fc2 = 1;        // encoder FFN-2 (K = 2048) + residual + LayerNorm as ONE row-owner launch (0: split-K slabs + reduce launch)
+    int fuse_dec0 = 1;       // decoder layer 0's self-attention block from opd_detr::dec0_h (0: its four launches on the zero state like every other layer)
+    int enc_front = 1;       // encoder FFN launch with the attention output projection + LayerNorm in front, from the attention output (env OPD_ENC_FRONT)
+    int enc_tail = 0;        // ... with the next layer's q / k / v projection (last layer: the decoder's memory k / v) as its tail (env OPD_ENC_TAIL)
+    int fused_enc_ffn = 1;   // the encoder's FFN block as one launch (kernels_rowln.hip::enc_ffn_kernel; 0: fc1 GEMM + deep-K ring launch; env OPD_FUSED_ENC_FFN)
+    int fused_dec = 1;       // the decoder as five launches per layer on split fp16 operands (kernels_dec.hip; 0: the round-3 chain of nine launches
+                             // per layer on single fp16 operands, also taken when the architecture does not fit: d_model != 256, heads != 8, queries % 4)
+    int dec_splits = 3;      // key ranges of the fused decoder's cross-attention
+    int heads2 = 1;          // the heads through kernels_dec.hip::heads2_kernel (0: kernels_misc.hip::heads_kernel on the fp32 matrix pipe; env OPD_HEADS2)
+    int fuse_btail = 1;      // stages 1-2: 3x3 -> expand + residual -> next reduce in one kernel (0: three launches)
+    int fuse_shortcut = 1;   // first block of stage 1: the shortcut convolution as a second GEMM inside the fused tail (0: own launch)
+    int dual_over_tail = 1;  // first block of stage 2: 3x3 + dual-source expand instead of shortcut launch + fused tail (-17 us)
+    int tail_rev = 1;        // consecutive fused tails walk their tiles in opposite directions (Infinity Cache reuse of the block output)
+    int tail3 = 1;           // stage 3 (256-channel blocks) through the eight-wave fused tail (kernels_btail3.hip) where it pays (plan_trunk);
+                             // 0: never (three launches per block), 2: always
+    int tail3_split = 1;     // stage 3: frames beyond whole rounds of the fused tail run as a second chain on `stream2` (0: one launch per tail)
+    int tail_rc = 1;         // stage 1: block 0 stores a1 instead of y; block 1 rebuilds y as its residual (kernels_btail.hip, RC; env OPD_TAIL_RC, 0 = off)
+    int y_stride2 = 1;       // last tail of stage 1: y stored only where the next stage's stride-2 shortcut reads it (env OPD_Y_STRIDE2)
+    int wprefetch = 3;       // L2 warm-up of a launch's weights by its own workgroups: bit 0 implicit GEMM, bit 1 the encoder's FFN launch (env OPD_WPREFETCH)
+    int w8 = -1;             // wide stage-4 layers through the eight-wave GEMM (kernels_w8.hip; identical bits): bit 0 3x3, bit 1 1x1 K >= 1024, bit 2 1x1 K = 512
+                             // (env OPD_W8).  -1 = by the handle's flags: the 3x3 for OPD_FLAG_MULTI_STREAM handles (132 one-per-CU workgroups cost 22 % less
+                             // CU time than 424 four-wave ones and leave the other CUs to the other streams: +1.1 %, 8 of 8 interleaved pairs), nothing for a
+                             // single-stream handle (there half the chip would idle: stage 4 0.43 -> 0.46 ms)
+    int small_splitk = 1;    // handles whose deep convolutions would fill a fraction of the CUs (small max_batch x frame): split their reduction over
+                             // workgroups, fp32 slabs + reduce_act16_kernel (run_conv; env OPD_SMALL_SPLITK)
+    int small_enc = 1;       // handles bounded to <= 1400 tokens: the encoder side's deep linears as split-K GEMMs + reduce / LayerNorm instead of the
+                             // row-owner launches (enqueue_forward; env OPD_SMALL_ENC)
+    int fuse_stem_pool = 1;  // stem conv + max-pool in one kernel (0: two kernels, for cross-checking)
+    int fuse_prep = 1;       // uint8 frames: pre-processing inside that kernel (0: preprocess_u8_kernel writes the padded NHWC4 image first)
+    int pos_shadow = 1;      // q / k projections read a second fp16 shadow "x + position embedding" (written by the producer of x) instead
+                             // of adding a row-periodic fp32 bias table W.pos + b per output tile (0: the table, the round-1 form)
+    int wround = 1;          // fp16 images of the folded convolution kernels by error diffusion along the reduction (opd_host.h::round_f16_diffused;
+                             // 0: round to nearest).  Identical for weights that are fp16-exact already.
+    int dbg_btail = 0, dbg_gemm = 0;   // timing ablations only (OPD_DBG_BTAIL / OPD_DBG_GEMM): the kernels' dbg bits for every launch of the forward
+    int dbg_dec_layers = 1 << 20;      // timing ablation only (OPD_DBG_DEC_LAYERS): run this many decoder layers
+    int dbg_skip = 0;                  // timing ablation only (OPD_DBG_SKIP): bit i = segment i of stage_ms launches nothing
+};
+
+// The trunk plan: how each bottleneck block of stages 1-4 runs.
+enum TrunkPath { PATH_TAIL, PATH_CONVS, PATH_DUAL };   // fused tail (kernels_btail*.hip) / 3x3 and 1x1 expand as two launches / 3x3 + dual-source expand
+enum TrunkShortcut { SC_NONE, SC_TAIL, SC_EXPAND, SC_LAUNCH };   // no shortcut / a second GEMM of the fused tail / extra K of the dual expand / own launch
+enum TrunkResidual { RES_NONE, RES_TRUNK, RES_SHORTCUT, RES_REBUILD };   // none (the shortcut sums into the expand) / the block input / the shortcut's
+                                                                         // output / rebuilt from the previous block's a1 and input (BtailParams::rc)
+enum TrunkStore { STORE_Y, STORE_A1, STORE_Y_STRIDE2 };   // block output stored whole / a1 only (the next block rebuilds y) / at even (oh, ow) only
+struct TrunkStep {
+    int path, sc, res, store;
+    int C3;           // fused tails: channels of the next block's reduce, computed here as z (0: none)
+    int rev, rev_b;   // BtailParams::rev of the launch; rev_b: of its launch in the stage-3 split's second chain
+};
+struct TrunkPlan {
+    std::vector<TrunkStep> steps;   // one per block, in stage order
+    int split = 0;                  // stage 3, blocks 1..: frames [0, split) on `stream`, [split, B) as a second chain on `stream2` (split == B: one chain)
+};
+// Pure over shapes and configuration (reads block shapes, never device pointers): called by enqueue_forward, i.e. per eager forward and per
+// graph capture.  B x H2 x W2: the call's batch and stage-1 input map; `taps`, `profiling`, `has_stream2`: the handle's diagnostic modes and branch stream.
+TrunkPlan plan_trunk(const Arch& a, const std::vector<Block>& blocks, const opd_config& cfg, const Switches& sw, int B, int H2, int W2, int num_cus,
+                     bool taps, int profiling, bool has_stream2);
+
 }  // namespace opd
 
 using namespace opd;   // (private header: every includer is library code)
@@ -119,6 +188,7 @@ struct WeightSet {
 struct opd_detr {
     Arch arch;
     opd_config cfg{};
+    Switches sw;                            // forward-plan switches (copied by opd_detr_clone: a clone plans like its source)
     int dtype = 0;                          // OPD_DT_F16 / OPD_DT_BF16 (cfg.flags & OPD_FLAG_BF16): the 16-bit operand type of every activation buffer and GEMM weight
     int device = 0;
     hipStream_t stream = nullptr;
@@ -138,22 +208,11 @@ struct opd_detr {
     std::vector<DecLayer> dec;
     f16_t* wkv_all = nullptr;  // [dec_layers*512][256] = per layer [Wk_c; Wv_c]
     float* bkv_all = nullptr;  // [dec_layers*512] = per layer [bk_c; bv_c] (pos_shadow path)
-    float* dec0_h = nullptr;   // [256]: decoder state after the self-attention block of layer 0 (input independent, see build_weights)
-    int fuse_dec0 = 1;         // use it (0: run that block's four launches on the zero state like every other layer)
+    float* dec0_h = nullptr;   // [256]: decoder state after the self-attention block of layer 0 (input independent, see build_weights; Switches::fuse_dec0)
     f16_t* qc0 = nullptr;      // [Q][256]: layer 0's cross-attention queries (dec0_h + qpos) . Wq_c^T + bq_c: input independent as well (fp32 at load)
-    int enc_front = 1;         // ... with the attention output projection + LayerNorm in front, from the attention output (env OPD_ENC_FRONT)
-    int enc_tail = 0;          // ... with the next layer's q / k / v projection (last layer: the decoder's memory k / v) as its tail (env OPD_ENC_TAIL)
-    int fused_enc_ffn = 1;     // the encoder's FFN block as one launch (kernels_rowln.hip::enc_ffn_kernel; 0: fc1 GEMM + deep-K ring launch; env OPD_FUSED_ENC_FFN)
-    int fused_dec = 1;         // the decoder as five launches per layer on split fp16 operands (kernels_dec.hip; 0: the round-3 chain of nine launches
-                               // per layer on single fp16 operands, also taken when the architecture does not fit: d_model != 256, heads != 8, queries % 4)
-    int dec_splits = 3;        // key ranges of the fused decoder's cross-attention
-    int dbg_btail = 0, dbg_gemm = 0;   // timing ablations only (OPD_DBG_BTAIL / OPD_DBG_GEMM): the kernels' dbg bits for every launch of the forward
-    int dbg_dec_layers = 1 << 20;   // timing ablation only (OPD_DBG_DEC_LAYERS): run this many decoder layers
-    int dbg_skip = 0;               // timing ablation only (OPD_DBG_SKIP): bit i = segment i of stage_ms launches nothing
     LNp dec_ln;
     float *wc = nullptr, *bc = nullptr, *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr;
     f16_t *wc_f = nullptr, *w1_f = nullptr, *w2_f = nullptr;   // the heads' 256-wide layers as split fp16 pairs in fragment order (heads2_kernel)
-    int heads2 = 1;            // the heads through kernels_dec.hip::heads2_kernel (0: kernels_misc.hip::heads_kernel on the fp32 matrix pipe; env OPD_HEADS2)
     float* zero_bias = nullptr;  // [3072] zeros
 
     // host copies needed to build plans for new resolutions
@@ -208,40 +267,9 @@ struct opd_detr {
     hipEvent_t ev[10] = {};
     bool graph_marks = false;   // profiling mode 2: the last forward was a graph replay (marks 0 .. 7 recorded by graph nodes, mark 9 eagerly behind it)
     float stage_ms[8] = {};
-    int small_m_gemm = 1;    // decoder linears (M = B x queries): one-shot K = 256 kernel (0: the general k-loop kernel)
-    int fuse_gemm_ln = 1;    // attention output projections: Linear + residual + LayerNorm in one kernel (0: GEMM, then LN)
-    int deep_fc2 = 1;        // encoder FFN-2 (K = 2048) + residual + LayerNorm as ONE row-owner launch (0: split-K slabs + reduce launch)
-    int fuse_btail = 1;      // stages 1-2: 3x3 -> expand + residual -> next reduce in one kernel (0: three launches)
-    int tail_rev = 1;        // consecutive fused tails walk their tiles in opposite directions (Infinity Cache reuse of the block output)
-    int tail3 = 1;           // stage 3 (256-channel blocks) through the eight-wave fused tail (kernels_btail3.hip) where it pays (see run_blocks);
-                             // 0: never (three launches per block), 2: always
-    int tail_rc = 1;         // stage 1: block 0 (and, at 2, block 1) stores a1 instead of y; the successor rebuilds y as its residual (kernels_btail.hip, RC; env OPD_TAIL_RC:
-                             // 0 / 1 / 2).  2 is bit-identical too but measured SLOWER (stage 1 0.555 -> 0.575 ms, three streams 3020 -> 2950 frames/s, A/B x 2 on one box):
-                             // eight half-chunk steps with three GEMMs each cost more than the 276 MB they save)
-    int y_stride2 = 1;       // last tail of stage 1: y stored only where the next stage's stride-2 shortcut reads it (env OPD_Y_STRIDE2)
-    int wprefetch = 3;       // L2 warm-up of a launch's weights by its own workgroups: bit 0 implicit GEMM, bit 1 the encoder's FFN launch (env OPD_WPREFETCH)
-    int tail_nw = 4;         // waves per workgroup of the stage 1-2 fused tails (BtailParams::nw; env OPD_TAIL_NW)
-    int w8 = -1;             // wide stage-4 layers through the eight-wave GEMM (kernels_w8.hip; identical bits): bit 0 3x3, bit 1 1x1 K >= 1024, bit 2 1x1 K = 512
-                             // (env OPD_W8).  -1 = by the handle's flags: the 3x3 for OPD_FLAG_MULTI_STREAM handles (132 one-per-CU workgroups cost 22 % less
-                             // CU time than 424 four-wave ones and leave the other CUs to the other streams: +1.1 %, 8 of 8 interleaved pairs), nothing for a
-                             // single-stream handle (there half the chip would idle: stage 4 0.43 -> 0.46 ms)
-    int small_splitk = 1;    // handles whose deep convolutions would fill a fraction of the CUs (small max_batch x frame): split their reduction over
-                             // workgroups, fp32 slabs + reduce_act16_kernel (run_conv; env OPD_SMALL_SPLITK)
-    int small_enc = 1;       // handles bounded to <= 1400 tokens: the encoder side's deep linears as split-K GEMMs + reduce / LayerNorm instead of the
-                             // row-owner launches (enqueue_forward; env OPD_SMALL_ENC)
     size_t slab_floats = 0;  // capacity of d_slab
     size_t stage_px[4] = {}; // per-frame pixel bound of the four stages' OUTPUT maps (build_workspace): what configuration-level plans count tiles with
     int num_cus = 256;
-    int tail3_split = 1;     // stage 3: frames beyond whole rounds of the fused tail run as a second chain on `stream2` (0: one launch per tail)
-    int dual_over_tail = 1;  // first block of stage 2: 3x3 + dual-source expand instead of shortcut launch + fused tail (-17 us)
-    int trunk_subbatch = 0;  // > 0: stages 1-2 run this many frames at a time (Infinity-Cache-sized block outputs); 0: whole batch
-    int fuse_shortcut = 1;   // first block of stage 1: the shortcut convolution as a second GEMM inside the fused tail (0: own launch)
-    int fuse_stem_pool = 1;  // stem conv + max-pool in one kernel (0: two kernels, for cross-checking)
-    int pos_shadow = 1;      // q / k projections read a second fp16 shadow "x + position embedding" (written by the producer of x) instead
-                             // of adding a row-periodic fp32 bias table W.pos + b per output tile (0: the table, the round-1 form)
-    int wround = 1;          // fp16 images of the folded convolution kernels by error diffusion along the reduction (opd_host.h::round_f16_diffused;
-                             // 0: round to nearest).  Identical for weights that are fp16-exact already.
-    int fuse_prep = 1;       // uint8 frames: pre-processing inside that kernel (0: preprocess_u8_kernel writes the padded NHWC4 image first)
 
     // hipGraph cache: the whole forward (~180 launches, many of them 5-10 us decoder kernels) replayed as one graph
     struct GraphEntry { int B, H, W, fmt, fh, fw; const void* pixels; int uses; hipGraphExec_t exec; unsigned epoch; };

@@ -548,8 +548,7 @@ int opd_test_btail_sc(const uint16_t* x1, const uint16_t* w1, const float* b1, c
 //   old: tail a stores y_a -> tail b reads it back as its residual -> tail c stores all of y_c;
 //   new: tail a stores a1 only -> tail b REBUILDS y_a (rc = 1) -> tail c stores y_c at even (oh, ow) only (y_stride2; the buffer is pre-filled
 //        with `fill` so the caller sees what was not written).
-//   new2: as new, but tail b stores its a1 too (no y_b at all) and tail c rebuilds BOTH previous outputs (rc = 2, btail_rc2_kernel).
-// Outputs: yb / zb [M][256] / [M][64], yc / zc [M][256] / [M][128], once per route (index 0 old, 1 new, 2 new2; yb[2] is left untouched).
+// Outputs: yb / zb [M][256] / [M][64], yc / zc [M][256] / [M][128], once per route (index 0 old, 1 new).
 int opd_test_btail_chain(const uint16_t* x1, const uint16_t* xs, const uint16_t* const* w1, const float* const* b1, const uint16_t* const* w2,
                          const float* const* b2, const uint16_t* wsc, const uint16_t* const* w3, const float* const* b3, uint16_t* const* yb,
                          uint16_t* const* zb, uint16_t* const* yc, uint16_t* const* zc, int B, int H, int W, int fill) {
@@ -570,13 +569,12 @@ int opd_test_btail_chain(const uint16_t* x1, const uint16_t* xs, const uint16_t*
     uint16_t* ya = dm.up<uint16_t>(nullptr, M * 256);
     uint16_t* za = dm.up<uint16_t>(nullptr, M * 64);
     uint16_t* a1a = dm.up<uint16_t>(nullptr, M * 64);
-    uint16_t* a1b = dm.up<uint16_t>(nullptr, M * 64);
     uint16_t* d_yb = dm.up<uint16_t>(nullptr, M * 256);
     uint16_t* d_zb = dm.up<uint16_t>(nullptr, M * 64);
     uint16_t* d_yc = dm.up<uint16_t>(nullptr, M * 256);
     uint16_t* d_zc = dm.up<uint16_t>(nullptr, M * 128);
-    if (!d_x1 || !d_xs || !d_wsc || !ya || !za || !a1a || !a1b || !d_yb || !d_zb || !d_yc || !d_zc) return tfail(OPD_ENOMEM, "test alloc failed");
-    for (int route = 0; route < 3; ++route) {
+    if (!d_x1 || !d_xs || !d_wsc || !ya || !za || !a1a || !d_yb || !d_zb || !d_yc || !d_zc) return tfail(OPD_ENOMEM, "test alloc failed");
+    for (int route = 0; route < 2; ++route) {
         TCHK(hipMemset(ya, 0xEE, M * 256 * 2));
         TCHK(hipMemset(d_yc, fill, M * 256 * 2));
         auto base = [&](int i, const uint16_t* in, uint16_t* y, uint16_t* z, int c3) {
@@ -590,22 +588,15 @@ int opd_test_btail_chain(const uint16_t* x1, const uint16_t* xs, const uint16_t*
         if (route) { pa.y = nullptr; pa.a1_out = a1a; }
         TCHK(opd_launch_btail(pa, nullptr));
         BtailParams pb = base(1, za, d_yb, d_zb, 64);
-        if (route) { pb.rc = 1; pb.rc_a1[0] = a1a; pb.rc_xs = d_xs; pb.rc_w2[0] = d_w2[0]; pb.rc_wsc = d_wsc; pb.rc_b[0] = d_b2[0]; }
+        if (route) { pb.rc = 1; pb.rc_a1 = a1a; pb.rc_xs = d_xs; pb.rc_w2 = d_w2[0]; pb.rc_wsc = d_wsc; pb.rc_b = d_b2[0]; }
         else pb.res = ya;
-        if (route == 2) { pb.y = nullptr; pb.a1_out = a1b; }
         TCHK(opd_launch_btail(pb, nullptr));
         BtailParams pc = base(2, d_zb, d_yc, d_zc, 128);
-        pc.y_stride2 = route ? 1 : 0;
-        if (route == 2) {
-            pc.rc = 2; pc.rc_xs = d_xs; pc.rc_wsc = d_wsc;
-            pc.rc_a1[0] = a1b; pc.rc_w2[0] = d_w2[1]; pc.rc_b[0] = d_b2[1];
-            pc.rc_a1[1] = a1a; pc.rc_w2[1] = d_w2[0]; pc.rc_b[1] = d_b2[0];
-        } else {
-            pc.res = d_yb;
-        }
+        pc.y_stride2 = route;
+        pc.res = d_yb;
         TCHK(opd_launch_btail(pc, nullptr));
         TCHK(hipDeviceSynchronize());
-        if (route < 2) TCHK(hipMemcpy(yb[route], d_yb, M * 256 * 2, hipMemcpyDeviceToHost));
+        TCHK(hipMemcpy(yb[route], d_yb, M * 256 * 2, hipMemcpyDeviceToHost));
         TCHK(hipMemcpy(zb[route], d_zb, M * 64 * 2, hipMemcpyDeviceToHost));
         TCHK(hipMemcpy(yc[route], d_yc, M * 256 * 2, hipMemcpyDeviceToHost));
         TCHK(hipMemcpy(zc[route], d_zc, M * 128 * 2, hipMemcpyDeviceToHost));
@@ -1008,6 +999,44 @@ int opd_test_resize_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* 
 }
 // host-only pieces of the ragged-batch path, exported for the CPU tests
 int opd_test_valid_prefix(int valid, int in, int out) { return valid_prefix(valid, in, out); }
+// plan_trunk (opd_model.cpp) for a ResNet trunk of the given stage depths with the bottleneck shapes infer_arch demands, default switches, a
+// branch stream, no taps, no profiling; a batch of B frames of H x W in a handle of max_batch frames.  steps_out[block][7] = path, shortcut,
+// residual, store, C3, rev, rev_b (opd_model.h); *split_out = TrunkPlan::split.  Returns the number of blocks.
+int opd_test_trunk_plan(const int* depths, int max_batch, int flags, int B, int H, int W, int num_cus, int* steps_out, int max_steps, int* split_out) {
+    if (!depths || !steps_out || !split_out || B < 1 || H < 1 || W < 1 || num_cus < 1) return tfail(OPD_EINVAL, "bad trunk_plan arguments");
+    Arch a;
+    std::vector<Block> blocks;
+    auto conv = [](int cin, int cout, int k, int stride) {
+        Conv c;
+        c.Cin = cin; c.Cout = cout; c.KH = c.KW = k; c.stride = stride; c.pad = k / 2; c.K = k * k * cin;
+        return c;
+    };
+    for (int s = 0, cin = 64; s < 4; ++s) {
+        a.depths[s] = depths[s];
+        if (depths[s] < 1) return tfail(OPD_EINVAL, "every stage needs a block");
+        const int cout = a.hidden[s], mid = cout / 4;
+        for (int l = 0; l < depths[s]; ++l) {
+            const int stride = (l == 0 && s > 0) ? 2 : 1;
+            Block b;
+            b.has_sc = l == 0;
+            if (b.has_sc) b.sc = conv(cin, cout, 1, stride);
+            b.c0 = conv(cin, mid, 1, 1); b.c1 = conv(mid, mid, 3, stride); b.c2 = conv(mid, cout, 1, 1);
+            blocks.push_back(b);
+            cin = cout;
+        }
+    }
+    if ((int)blocks.size() > max_steps) return tfail(OPD_EINVAL, "steps_out too small");
+    opd_config cfg{};
+    cfg.struct_size = sizeof(opd_config); cfg.max_batch = max_batch; cfg.max_height = H; cfg.max_width = W; cfg.flags = flags;
+    const TrunkPlan plan = plan_trunk(a, blocks, cfg, Switches{}, B, down2(down2(H)), down2(down2(W)), num_cus, false, 0, true);
+    for (size_t i = 0; i < plan.steps.size(); ++i) {
+        const TrunkStep& t = plan.steps[i];
+        const int row[7] = {t.path, t.sc, t.res, t.store, t.C3, t.rev, t.rev_b};
+        memcpy(steps_out + 7 * i, row, sizeof(row));
+    }
+    *split_out = plan.split;
+    return (int)blocks.size();
+}
 int opd_test_sine_pos_embed(int h, int w, int vh, int vw, int D, float* out) {
     if (!out || h < 1 || w < 1 || vh < 1 || vw < 1 || vh > h || vw > w || D < 2 || (D & 1)) return fail(OPD_EINVAL, "bad sine_pos_embed arguments");
     std::vector<float> pos;
@@ -1017,11 +1046,11 @@ int opd_test_sine_pos_embed(int h, int w, int vh, int vw, int D, float* out) {
 }
 int opd_test_set_fuse_gemm_ln(opd_detr* m, int on) {
     if (!m) return fail(OPD_EINVAL, "null model handle");
-    m->fuse_gemm_ln = on ? 1 : 0;
-    m->small_m_gemm = on ? 1 : 0;   // the switch covers the transformer-side specialisations
-    m->deep_fc2 = on ? 1 : 0;
-    m->fuse_dec0 = on ? 1 : 0;
-    m->fused_dec = on ? 1 : 0;   // (the unfused chain is the cross-check of the fused decoder as well)
+    m->sw.fuse_gemm_ln = on ? 1 : 0;
+    m->sw.small_m_gemm = on ? 1 : 0;   // the switch covers the transformer-side specialisations
+    m->sw.deep_fc2 = on ? 1 : 0;
+    m->sw.fuse_dec0 = on ? 1 : 0;
+    m->sw.fused_dec = on ? 1 : 0;   // (the unfused chain is the cross-check of the fused decoder as well)
     if (fill_qc0(m) != OPD_OK) return OPD_EHIP;
     for (auto& g : m->graphs)  // captured graphs hold the old launch sequence
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -1030,8 +1059,8 @@ int opd_test_set_fuse_gemm_ln(opd_detr* m, int on) {
 }
 int opd_test_set_fuse_btail(opd_detr* m, int on) {   // bit 0: fused bottleneck tails, bit 1: the shortcut of stage 1 inside its first tail
     if (!m) return fail(OPD_EINVAL, "null model handle");
-    m->fuse_btail = (on & 1) ? 1 : 0;
-    m->fuse_shortcut = (on & 2) ? 1 : 0;
+    m->sw.fuse_btail = (on & 1) ? 1 : 0;
+    m->sw.fuse_shortcut = (on & 2) ? 1 : 0;
     for (auto& g : m->graphs)  // captured graphs hold the old launch sequence
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     m->graphs.clear();
@@ -1039,7 +1068,7 @@ int opd_test_set_fuse_btail(opd_detr* m, int on) {   // bit 0: fused bottleneck 
 }
 int opd_test_set_pos_shadow(opd_detr* m, int on) {   // 0: row-periodic bias tables W.pos + b (round-1 form) instead of the fp16(x + pos) shadow
     if (!m) return fail(OPD_EINVAL, "null model handle");
-    m->pos_shadow = on ? 1 : 0;
+    m->sw.pos_shadow = on ? 1 : 0;
     for (auto& g : m->graphs)  // captured graphs hold the old launch sequence
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     m->graphs.clear();
@@ -1047,8 +1076,8 @@ int opd_test_set_pos_shadow(opd_detr* m, int on) {   // 0: row-periodic bias tab
 }
 int opd_test_set_fuse_stem_pool(opd_detr* m, int on) {
     if (!m) return fail(OPD_EINVAL, "null model handle");
-    m->fuse_stem_pool = (on & 1) ? 1 : 0;   // bit 0: stem + pool in one kernel; bit 1: pre-processing inside it as well
-    m->fuse_prep = (on & 2) ? 1 : 0;
+    m->sw.fuse_stem_pool = (on & 1) ? 1 : 0;   // bit 0: stem + pool in one kernel; bit 1: pre-processing inside it as well
+    m->sw.fuse_prep = (on & 2) ? 1 : 0;
     for (auto& g : m->graphs)  // captured graphs hold the old launch sequence
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     m->graphs.clear();
@@ -1335,7 +1364,7 @@ int opd_test_set_fused_dec(opd_detr* m, int on) {   // 0: the unfused decoder ch
     if (!m) return fail(OPD_EINVAL, "null model handle");
     HIPCHK(hipSetDevice(m->device));
     HIPCHK(hipStreamSynchronize(m->stream));
-    m->fused_dec = on ? 1 : 0;
+    m->sw.fused_dec = on ? 1 : 0;
     RCCHK(fill_qc0(m));
     for (auto& g : m->graphs)  // captured graphs hold the old launch sequence
         if (g.exec) (void)hipGraphExecDestroy(g.exec);

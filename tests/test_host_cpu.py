@@ -262,6 +262,82 @@ def test_mask_downsampling_matches_torch_nearest():
             assert lib.opd_test_valid_prefix(valid, size, out) == want, (size, out, valid)
 
 
+# csrc/opd_model.h: TrunkStep fields and enums
+TAIL, CONVS, DUAL = 0, 1, 2                       # path
+SC_NONE, SC_TAIL, SC_EXPAND, SC_LAUNCH = 0, 1, 2, 3
+RES_NONE, RES_TRUNK, RES_SHORTCUT, RES_REBUILD = 0, 1, 2, 3
+STORE_Y, STORE_A1, STORE_Y_STRIDE2 = 0, 1, 2
+
+
+def trunk_plan(lib, depths, max_batch, flags, B, H, W, num_cus=256):
+    steps = np.zeros((64, 7), np.int32)
+    split = C.c_int()
+    d = np.asarray(depths, np.int32)
+    n = lib.opd_test_trunk_plan(d.ctypes.data, max_batch, flags, B, H, W, num_cus, steps.ctypes.data, 64, C.byref(split))
+    assert n == sum(depths), lib.opd_last_error()
+    return [tuple(int(v) for v in r) for r in steps[:n]], split.value
+
+
+def test_trunk_plan_residual_rebuild_and_stage3_split_invariants():
+    """plan_trunk (csrc/opd_model.cpp), pure over shapes and configuration: a block drops its output (stores a1 only) only when the next
+    block of its stage is a fused tail that rebuilds it, every rebuild has such a predecessor, and stage 3 is split over two chains only
+    when its blocks 1.. all run as fused tails.  depths[0] == 2 used to drop block 0's output with nobody to rebuild it."""
+    lib = _capi.load_library()
+    for depths in ((1, 4, 6, 3), (2, 4, 6, 3), (3, 4, 6, 3), (3, 4, 23, 3)):
+        first = [sum(depths[:s]) for s in range(4)]
+        stage = [s for s in range(4) for _ in range(depths[s])]
+        for max_batch in (1, 2, 8):
+            for flags in (0, _capi.OPD_FLAG_MULTI_STREAM):
+                for H, W in ((256, 320), (800, 1333)):
+                    steps, split = trunk_plan(lib, depths, max_batch, flags, max_batch, H, W)
+                    where = (depths, max_batch, flags, H, W)
+                    for i, (path, sc, res, store, c3, rev, rev_b) in enumerate(steps):
+                        if store == STORE_A1:
+                            assert i + 1 < len(steps) and stage[i + 1] == stage[i], where
+                            assert steps[i + 1][0] == TAIL and steps[i + 1][2] == RES_REBUILD, where
+                            assert path == TAIL and sc == SC_TAIL and c3 == 64, where
+                        if res == RES_REBUILD:
+                            assert i > 0 and steps[i - 1][3] == STORE_A1 and path == TAIL and c3 == 64, where
+                        if path != TAIL:
+                            assert c3 == 0 and store == STORE_Y and rev == 0, where
+                    rebuilds = sum(s[2] == RES_REBUILD for s in steps)
+                    assert rebuilds == (1 if depths[0] >= 3 else 0), where
+                    assert 1 <= split <= max_batch
+                    if split < max_batch:
+                        assert all(s[0] == TAIL for s in steps[first[2] + 1:first[3]]), where
+                        assert not flags & _capi.OPD_FLAG_MULTI_STREAM
+
+
+def test_trunk_plan_r50_batch8_matches_the_hand_derived_plan():
+    """The r50 plan at batch 8, 800 x 1333 (the benchmark workload) on a 256-CU device, step by step, as the launch code before the planner
+    decided it: stage 1 as three fused tails (shortcut inside the first, whose output the second rebuilds; the last stores its output at the
+    stride-2 positions only), stage 2 = dual-source expand + three tails, stage 3 = dual expand + five 256-channel tails split 7 + 1 frames
+    over two chains, stage 4 = dual expand + two unfused blocks; tile directions alternate over the fused tails in launch order."""
+    lib = _capi.load_library()
+    steps, split = trunk_plan(lib, (3, 4, 6, 3), 8, 0, 8, 800, 1333)
+    want = [
+        # path   shortcut   residual      store            C3  rev rev_b
+        (TAIL,  SC_TAIL,   RES_NONE,     STORE_A1,         64, 0, 0),
+        (TAIL,  SC_NONE,   RES_REBUILD,  STORE_Y,          64, 1, 0),
+        (TAIL,  SC_NONE,   RES_TRUNK,    STORE_Y_STRIDE2, 128, 0, 0),
+        (DUAL,  SC_EXPAND, RES_NONE,     STORE_Y,           0, 0, 0),
+        (TAIL,  SC_NONE,   RES_TRUNK,    STORE_Y,         128, 1, 0),
+        (TAIL,  SC_NONE,   RES_TRUNK,    STORE_Y,         128, 0, 0),
+        (TAIL,  SC_NONE,   RES_TRUNK,    STORE_Y,           0, 1, 0),
+        (DUAL,  SC_EXPAND, RES_NONE,     STORE_Y,           0, 0, 0),
+        (TAIL,  SC_NONE,   RES_TRUNK,    STORE_Y,         256, 0, 1),
+        (TAIL,  SC_NONE,   RES_TRUNK,    STORE_Y,         256, 1, 0),
+        (TAIL,  SC_NONE,   RES_TRUNK,    STORE_Y,         256, 0, 1),
+        (TAIL,  SC_NONE,   RES_TRUNK,    STORE_Y,         256, 1, 0),
+        (TAIL,  SC_NONE,   RES_TRUNK,    STORE_Y,           0, 0, 1),
+        (DUAL,  SC_EXPAND, RES_NONE,     STORE_Y,           0, 0, 0),
+        (CONVS, SC_NONE,   RES_TRUNK,    STORE_Y,           0, 0, 0),
+        (CONVS, SC_NONE,   RES_TRUNK,    STORE_Y,           0, 0, 0),
+    ]
+    assert steps == want
+    assert split == 7
+
+
 def test_masked_sine_position_embedding_matches_oracle():
     """Position embedding of a frame whose valid region is a top-left rectangle of the map: equals the oracle's
     cumulative-sum formulation (HF:modeling_detr.py:294-368) at EVERY position, padded ones included."""

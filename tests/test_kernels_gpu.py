@@ -672,10 +672,10 @@ def test_btail_residual_rebuild_and_strided_output_are_bit_identical(lib, B, H, 
     b2 = [f32(0.1 * rng.standard_normal(256)) for _ in range(3)]
     b3 = [f32(0.1 * rng.standard_normal(c3)) for c3 in (64, 64, 128)]
     arr = lambda xs_: (C.c_void_p * len(xs_))(*[x.ctypes.data for x in xs_])
-    yb = [np.empty((M, 256), np.uint16) for _ in range(3)]
-    zb = [np.empty((M, 64), np.uint16) for _ in range(3)]
-    yc = [np.empty((B, H, W, 256), np.uint16) for _ in range(3)]
-    zc = [np.empty((M, 128), np.uint16) for _ in range(3)]
+    yb = [np.empty((M, 256), np.uint16) for _ in range(2)]
+    zb = [np.empty((M, 64), np.uint16) for _ in range(2)]
+    yc = [np.empty((B, H, W, 256), np.uint16) for _ in range(2)]
+    zc = [np.empty((M, 128), np.uint16) for _ in range(2)]
     rc = lib.opd_test_btail_chain(_p(x1), _p(xs), arr(w1), arr(b1), arr(w2), arr(b2), _p(wsc), arr(w3), arr(b3), arr(yb), arr(zb), arr(yc), arr(zc),
                                   B, H, W, 0xA5)
     _capi.check(rc, "opd_test_btail_chain")
@@ -683,11 +683,10 @@ def test_btail_residual_rebuild_and_strided_output_are_bit_identical(lib, B, H, 
     assert np.array_equal(yb[0], yb[1]), "second tail: y differs between a residual read back and a residual rebuilt"
     untouched = np.ones((B, H, W), bool)
     untouched[:, ::2, ::2] = False
-    for route in (1, 2):   # 2: the second tail stores no output at all and the third rebuilds both (btail_rc2_kernel)
-        assert np.array_equal(zb[0], zb[route]), route
-        assert np.array_equal(zc[0], zc[route]), route
-        assert np.array_equal(yc[0][:, ::2, ::2], yc[route][:, ::2, ::2]), f"route {route}: third tail's y at the positions a stride-2 1x1 reads"
-        assert (yc[route][untouched] == 0xA5A5).all(), f"route {route}: third tail stored y at positions nobody reads"
+    assert np.array_equal(zb[0], zb[1])
+    assert np.array_equal(zc[0], zc[1])
+    assert np.array_equal(yc[0][:, ::2, ::2], yc[1][:, ::2, ::2]), "third tail's y at the positions a stride-2 1x1 reads"
+    assert (yc[1][untouched] == 0xA5A5).all(), "third tail stored y at positions nobody reads"
     assert not (yc[0] == 0xA5A5).all()
 
 

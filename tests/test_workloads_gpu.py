@@ -577,17 +577,22 @@ def test_device_mem_kinds_refuse_pointers_that_are_not_device_memory(mild_path):
         lib.opd_detr_destroy(h)
 
 
-def test_stage1_residual_rebuild_is_invisible_end_to_end(mild_path):
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("depths", [(3, 4, 6, 3), (2, 2, 2, 2)])
+def test_stage1_residual_rebuild_is_invisible_end_to_end(mild_path, weight_cache, depths, dtype):
     """OPD_TAIL_RC / OPD_Y_STRIDE2 (round 5: stage 1's first tail stores a1 instead of its output, the second rebuilds it, the last stores its
     output only where the next stage reads it): logits, boxes and the encoder map of a batch are bit-identical with the switches on and off,
-    eager, captured and replayed, also for a ragged last tile (203 x 333) and through a clone (the switches travel with opd_detr_clone)."""
+    eager, captured and replayed, also for a ragged last tile (203 x 333) and through a clone (the switches travel with opd_detr_clone), for
+    both element types.  depths (2, 2, 2, 2): stage 1's second block is its last, so nobody can rebuild the first one's output -- the plan
+    must store it (OPD_TAIL_RC=0 stores every block output: the reference)."""
+    path = mild_path if depths == (3, 4, 6, 3) else ensure_weight_file(weight_cache, DetrArch(depths=depths), 0, 1.0, "d2222")
     for (H, W, B) in ((256, 320, 3), (203, 333, 2)):
         frames = structured_frames(B, H, W, seed=515)
         outs = {}
         for flag in ("1", "0"):
             os.environ["OPD_TAIL_RC"] = flag; os.environ["OPD_Y_STRIDE2"] = flag
             try:
-                det = HipDetrDetector(model_path=mild_path, max_batch=B, max_size=(H, W), resize=False, streams=2)
+                det = HipDetrDetector(model_path=path, max_batch=B, max_size=(H, W), resize=False, streams=2, dtype=dtype)
                 det.load_model()
             finally:
                 del os.environ["OPD_TAIL_RC"], os.environ["OPD_Y_STRIDE2"]
@@ -598,30 +603,6 @@ def test_stage1_residual_rebuild_is_invisible_end_to_end(mild_path):
         for call in range(3):
             for x, y in zip(outs["1"][call], outs["0"][call]):
                 np.testing.assert_array_equal(x, y)
-
-
-@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
-def test_tail_workgroup_shape_is_invisible_end_to_end(mild_path, monkeypatch, dtype):
-    """OPD_TAIL_NW = 8 (the stage 1-2 fused tails as eight-wave workgroups on 256-pixel tiles: one set of weight tiles staged per 256 pixels)
-    against the four-wave form: a wave's arithmetic is the same, so logits, boxes and the encoder map are bit-identical -- with the
-    residual rebuild on and off (all tail variants), ragged last tiles (203 x 333: 4 250 / 1 092 pixels at stage 1 / 2 are not multiples of 256),
-    eager, captured and replayed."""
-    for (H, W, B) in ((256, 320, 3), (203, 333, 2)):
-        frames = structured_frames(B, H, W, seed=616)
-        for rc in ("1", "0"):
-            monkeypatch.setenv("OPD_TAIL_RC", rc)
-            outs = {}
-            for nw in ("4", "8"):
-                monkeypatch.setenv("OPD_TAIL_NW", nw)
-                det = HipDetrDetector(model_path=mild_path, max_batch=B, max_size=(H, W), resize=False, dtype=dtype)
-                det.load_model()
-                try:
-                    outs[nw] = [det.forward_raw(frames) for _ in range(3)]
-                finally:
-                    det.close()
-            for call in range(3):
-                for x, y in zip(outs["4"][call], outs["8"][call]):
-                    np.testing.assert_array_equal(x, y)
 
 
 @pytest.mark.parametrize("flag_bf16", [0, 1])
