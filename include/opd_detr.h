@@ -292,6 +292,43 @@ OPD_API int opd_detr_kernel_times(const opd_detr* m, float* ms4, int32_t* launch
 typedef struct opd_kernel_stat { char name[96]; int32_t launches; float ms; double flops; } opd_kernel_stat;
 OPD_API int opd_detr_kernel_table(const opd_detr* m, opd_kernel_stat* out, int capacity, int* count);
 
+/* ---- Re-ID features: the CLIP ViT image tower (second handle type, own weights, workspace, stream and graphs) ----------------------
+ * Replaces `CLIPReIDExtractor.extract_features` (reference src/tracking/reid_feature_extractor.py:108-153): per box, crop the frame at
+ * x1 = int(max(0, x)), x2 = int(min(W, x + w)) (same for y; an empty crop becomes a 224 x 224 zero image), BGR -> RGB,
+ * CLIPImageProcessor (Pillow bicubic resize to shortest edge 224, centre crop 224, /255, CLIP mean / std), then
+ * `CLIPModel.get_image_features` and an L2 normalisation: float32 [n_boxes][feature_dim] with rows of unit norm. */
+typedef struct opd_reid opd_reid; /* opaque Re-ID handle */
+
+typedef struct opd_reid_config {
+    int32_t struct_size; /* = sizeof(opd_reid_config) */
+    int32_t max_crops;   /* workspace and launch plans are sized for this many crops; a call with more boxes runs in chunks */
+    int32_t flags;       /* OPD_FLAG_NO_GRAPH: eager launches instead of one captured hipGraph per crop-count bucket */
+    int32_t reserved[5];
+} opd_reid_config;
+
+typedef struct opd_reid_model_info {
+    int32_t feature_dim, tokens, hidden, layers, heads, mlp_dim, patch, max_crops;
+    int32_t device_ordinal, reserved;
+    int64_t weight_bytes_device;
+    int64_t workspace_bytes_device;
+} opd_reid_model_info;
+
+/* Parse a safetensors file holding an HF `CLIPModel` or `CLIPVisionModelWithProjection` state dict (`vision_model.*` and
+ * `visual_projection.weight`; `text_model.*` is ignored), infer the architecture from the shapes (head_dim 64, or
+ * `num_attention_heads` of a config.json beside the file) and upload it.  The schema is checked before the device is touched:
+ * head_dim != 64, more than 64 tokens, a hidden size that is not a multiple of 128 (or above 1024), or an image size other than 224
+ * return OPD_ESCHEMA with a message naming the limit. */
+OPD_API int opd_reid_create(const opd_reid_config* cfg, const char* weights_path, int device_ordinal, opd_reid** out);
+OPD_API void opd_reid_destroy(opd_reid* r);
+OPD_API int opd_reid_info(const opd_reid* r, opd_reid_model_info* info);
+/* Features of `n_boxes` boxes (x, y, w, h in frame pixels, host [n_boxes][4]) on `n_frames` frames: box i lies on frame box_frame[i]
+ * (host int32; NULL = frame 0).  frames[f] = [h][w][3] uint8 BGR with (h, w) = frame_hw[2f], frame_hw[2f + 1] (host int32); host memory
+ * for OPD_MEM_HOST (only each crop's source window is copied to the device, packed into one transfer), device pointers read in place
+ * for OPD_MEM_DEVICE.  `out` = host float32 [n_boxes][feature_dim].  Synchronous. */
+OPD_API int opd_reid_extract(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, int n_frames, int mem_kind,
+                             const float* boxes_xywh, const int32_t* box_frame, int n_boxes, float* out);
+
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 OPD_API const char* opd_last_error(void);
 

@@ -48,6 +48,16 @@ class OpdModelInfo(C.Structure):
                 ("workspace_bytes_device", C.c_int64)]
 
 
+class OpdReidConfig(C.Structure):   # opd_reid_config (include/opd_detr.h)
+    _fields_ = [("struct_size", C.c_int32), ("max_crops", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class OpdReidModelInfo(C.Structure):   # opd_reid_model_info
+    _fields_ = [("feature_dim", C.c_int32), ("tokens", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
+                ("mlp_dim", C.c_int32), ("patch", C.c_int32), ("max_crops", C.c_int32), ("device_ordinal", C.c_int32),
+                ("reserved", C.c_int32), ("weight_bytes_device", C.c_int64), ("workspace_bytes_device", C.c_int64)]
+
+
 # name -> (restype, argtypes): every symbol include/opd_detr.h declares
 API = {
     "opd_detr_create": (C.c_int, [C.POINTER(OpdConfig), C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
@@ -95,6 +105,11 @@ API = {
     "opd_comm_buffers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "opd_comm_exchange": (C.c_int, [C.c_void_p]),
     "opd_comm_wait": (C.c_int, [C.c_void_p, C.POINTER(OpdDet), C.POINTER(C.c_int32)]),
+    "opd_reid_create": (C.c_int, [C.POINTER(OpdReidConfig), C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "opd_reid_destroy": (None, [C.c_void_p]),
+    "opd_reid_info": (C.c_int, [C.c_void_p, C.POINTER(OpdReidModelInfo)]),
+    "opd_reid_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_void_p]),
     "opd_last_error": (C.c_char_p, []),
     "opd_version": (C.c_char_p, []),
 }
@@ -162,6 +177,18 @@ TEST_API = {
     "opd_test_set_fused_dec": (C.c_int, [C.c_void_p, C.c_int]),
     "opd_test_set_elem_bf16": (C.c_int, [C.c_int]),
     "opd_test_trace_dec_self": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
+    # Re-ID hooks (csrc/opd_reid_test_api.cpp)
+    "opd_test_reid_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "opd_test_reid_coeffs": (C.c_int, [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int]),
+    "opd_test_reid_lut": (C.c_int, [C.c_void_p]),
+    "opd_test_reid_pixels_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "opd_test_reid_pixels": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_void_p]),
+    "opd_test_reid_attention": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3),
+    "opd_test_reid_layernorm": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3),
+    "opd_test_reid_gemm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3),
+    "opd_test_reid_kernel_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                             C.POINTER(OpdKernelStat), C.c_int, C.POINTER(C.c_int)]),
 }
 
 _lib: Optional[C.CDLL] = None

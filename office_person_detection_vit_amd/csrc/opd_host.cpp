@@ -96,17 +96,19 @@ void sine_pos_embed(int h, int w, int vh, int vw, int D, std::vector<float>* pos
 
 using namespace opd;
 
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc for the bilinear (triangle, support 1) filter over the whole axis
-// (box = [0, in_size)): per output position the first source index, the tap count, and the 22-bit fixed-point taps.
-void opd_resize_coeffs(int in_size, int out_size, std::vector<int32_t>* bounds, std::vector<int32_t>* coeffs, int* ksize_out) {
+// Pillow's precompute_coeffs + normalize_coeffs_8bpc over the whole axis (box = [0, in_size)): per output position the first source
+// index, the tap count, and the 22-bit fixed-point taps, for the outputs [first, first + count).  `bicubic`: Pillow's bicubic filter (a = -0.5, support 2) instead of the
+// bilinear triangle (support 1).
+void opd_resize_coeffs_filter(int in_size, int out_size, bool bicubic, int first, int count, std::vector<int32_t>* bounds,
+                              std::vector<int32_t>* coeffs, int* ksize_out) {
     const double scale = (double)in_size / out_size;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * filterscale;
+    const double support = (bicubic ? 2.0 : 1.0) * filterscale;
     const int ksize = (int)ceil(support) * 2 + 1;
-    bounds->assign((size_t)out_size * 2, 0);
-    coeffs->assign((size_t)out_size * ksize, 0);
+    bounds->assign((size_t)count * 2, 0);
+    coeffs->assign((size_t)count * ksize, 0);
     std::vector<double> k(ksize);
-    for (int xx = 0; xx < out_size; ++xx) {
+    for (int xx = first; xx < first + count; ++xx) {
         const double center = 0.0 + (xx + 0.5) * scale;
         double ww = 0.0;
         const double ss = 1.0 / filterscale;
@@ -118,19 +120,27 @@ void opd_resize_coeffs(int in_size, int out_size, std::vector<int32_t>* bounds, 
         for (int x = 0; x < xmax; ++x) {
             double a = (x + xmin - center + 0.5) * ss;
             if (a < 0.0) a = -a;
-            const double wgt = a < 1.0 ? 1.0 - a : 0.0;
+            double wgt;
+            if (bicubic)   // Pillow's bicubic_filter, a = -0.5
+                wgt = a < 1.0 ? ((-0.5 + 2.0) * a - (-0.5 + 3.0)) * a * a + 1 : a < 2.0 ? (((a - 5) * a + 8) * a - 4) * -0.5 : 0.0;
+            else
+                wgt = a < 1.0 ? 1.0 - a : 0.0;
             k[x] = wgt;
             ww += wgt;
         }
         for (int x = 0; x < xmax; ++x) {
             if (ww != 0.0) k[x] /= ww;
             const double v = k[x] * (double)(1 << 22);
-            (*coeffs)[(size_t)xx * ksize + x] = k[x] < 0 ? (int)(-0.5 + v) : (int)(0.5 + v);
+            (*coeffs)[(size_t)(xx - first) * ksize + x] = k[x] < 0 ? (int)(-0.5 + v) : (int)(0.5 + v);
         }
-        (*bounds)[2 * xx] = xmin;
-        (*bounds)[2 * xx + 1] = xmax;
+        (*bounds)[2 * (xx - first)] = xmin;
+        (*bounds)[2 * (xx - first) + 1] = xmax;
     }
     *ksize_out = ksize;
+}
+
+void opd_resize_coeffs(int in_size, int out_size, std::vector<int32_t>* bounds, std::vector<int32_t>* coeffs, int* ksize_out) {
+    opd_resize_coeffs_filter(in_size, out_size, false, 0, out_size, bounds, coeffs, ksize_out);
 }
 
 extern "C" {

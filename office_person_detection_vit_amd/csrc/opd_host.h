@@ -31,3 +31,7 @@ void round_f16_diffused(float* w, size_t rows, int taps, int cin, bool bf16 = fa
 
 // Pillow-exact bilinear coefficient tables (22-bit fixed point): bounds [out][2] = (first tap, taps), coeffs [out][ksize]
 void opd_resize_coeffs(int in_size, int out_size, std::vector<int32_t>* bounds, std::vector<int32_t>* coeffs, int* ksize_out);
+// The same tables for either Pillow filter: bilinear (= opd_resize_coeffs) or bicubic (a = -0.5, support 2; the Re-ID crops)
+// restricted to the outputs [first, first + count) (tables indexed from `first`)
+void opd_resize_coeffs_filter(int in_size, int out_size, bool bicubic, int first, int count, std::vector<int32_t>* bounds,
+                              std::vector<int32_t>* coeffs, int* ksize_out);

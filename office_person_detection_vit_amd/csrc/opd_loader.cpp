@@ -221,7 +221,7 @@ std::string normalise_key(const std::string& key_in) {
     return k;
 }
 
-int load_safetensors(const std::string& path, StateDict* out, std::string* err) {
+int load_safetensors(const std::string& path, StateDict* out, std::string* err, bool raw_keys) {
     FILE* f = fopen(path.c_str(), "rb");
     if (!f) { *err = "cannot open weight file '" + path + "'"; return OPD_EIO; }
     uint64_t hl = 0;
@@ -281,7 +281,7 @@ int load_safetensors(const std::string& path, StateDict* out, std::string* err) 
                     memcpy(&t.data[i], &x, 4);
                 }
             }
-            (*out)[normalise_key(name)] = std::move(t);
+            (*out)[raw_keys ? name : normalise_key(name)] = std::move(t);
         }
         if (c.fail) { fclose(f); *err = "malformed safetensors header"; return OPD_EIO; }
         if (c.eat(',')) continue;

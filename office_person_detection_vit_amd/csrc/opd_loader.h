@@ -23,8 +23,9 @@ using StateDict = std::map<std::string, HostTensor>;
 
 // Reads a .safetensors file (F32 / F16 / BF16 tensors).  Keys are normalised to the HF 5.x DETR names
 // (4.x `conv_encoder` / `out_proj` / `fc1` spellings and the timm ResNet layout are renamed).
+// `raw_keys`: keep the file's key names as they are (the CLIP checkpoint of the Re-ID path, whose `out_proj` / `fc1` names are not DETR's).
 // Returns 0 or a negative OPD_E* code with `err` filled.
-int load_safetensors(const std::string& path, StateDict* out, std::string* err);
+int load_safetensors(const std::string& path, StateDict* out, std::string* err, bool raw_keys = false);
 
 // HF 4.x / timm key -> 5.x key (identity for 5.x keys).  Exposed for tests.
 std::string normalise_key(const std::string& key);

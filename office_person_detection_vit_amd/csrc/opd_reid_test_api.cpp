@@ -1,0 +1,125 @@
+// opd_reid_test_api.cpp — kernel-level hooks of the Re-ID path for tests/ and tools/ (exported from libopd_hip_test.so only).
+// Host buffers in and out; each hook allocates its device buffers, runs one launcher on the null stream and copies the result back.
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "opd_model.h"
+#include "opd_reid.h"
+
+#define TAPI extern "C" __attribute__((visibility("default")))
+
+using namespace opd;
+
+namespace {
+
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+int up(DevBuf& d, const void* h, size_t bytes) {
+    HIPCHK(hipMalloc(&d.p, bytes ? bytes : 4));
+    if (h && bytes) HIPCHK(hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice));
+    else if (bytes) HIPCHK(hipMemset(d.p, 0, bytes));
+    return OPD_OK;
+}
+
+}  // namespace
+
+// Host-side geometry of n boxes on an H x W frame: out[i][13] = x1 y1 x2 y2 zero rh rw top left wy0 wx0 wy1 wx1
+TAPI int opd_test_reid_geometry(const float* boxes, int n, int H, int W, int32_t* out) {
+    for (int i = 0; i < n; ++i) {
+        ReidGeom g;
+        reid_geometry(boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3], H, W, &g);
+        const int32_t v[13] = {g.x1, g.y1, g.x2, g.y2, g.zero, g.rh, g.rw, g.top, g.left, g.wy0, g.wx0, g.wy1, g.wx1};
+        memcpy(out + 13 * i, v, sizeof v);
+    }
+    return OPD_OK;
+}
+
+// Pillow bicubic tables of one axis, outputs [first, first + count): bounds [count][2], coeffs [count][cap]; returns ksize or < 0
+TAPI int opd_test_reid_coeffs(int in_size, int out_size, int first, int count, int32_t* bounds, int32_t* coeffs, int cap) {
+    std::vector<int32_t> b, c;
+    int ks = 0;
+    reid_axis_tables(in_size, out_size, first, count, &b, &c, &ks);
+    if (ks > cap) return fail(OPD_EINVAL, "opd_test_reid_coeffs: ksize above cap");
+    memcpy(bounds, b.data(), b.size() * 4);
+    for (int i = 0; i < count; ++i) memcpy(coeffs + (size_t)i * cap, c.data() + (size_t)i * ks, (size_t)ks * 4);
+    return ks;
+}
+
+// the normalisation table: lut[c * 256 + u8] fp16 bits
+TAPI int opd_test_reid_lut(uint16_t* lut) {
+    reid_pixel_lut(lut);
+    return OPD_OK;
+}
+
+// host restatement of the pre-processing of n boxes on one frame: out [n][T][3 P P] fp16 bits
+TAPI int opd_test_reid_pixels_host(const uint8_t* frame, int H, int W, const float* boxes, int n, int P, int T, uint16_t* out) {
+    std::vector<uint16_t> lut(768);
+    reid_pixel_lut(lut.data());
+    const size_t per = (size_t)T * 3 * P * P;
+    for (int i = 0; i < n; ++i) {
+        ReidGeom g;
+        reid_geometry(boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3], H, W, &g);
+        reid_preprocess_host(frame, H, W, g, P, lut.data(), out + per * i);
+    }
+    return OPD_OK;
+}
+
+// the device pre-processing of one opd_reid_extract call (n <= max_crops): out [n][T][3 P P] fp16 bits
+TAPI int opd_test_reid_pixels(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, int n_frames, int mem_kind, const float* boxes,
+                              const int32_t* box_frame, int n, uint16_t* out) {
+    return reid_test_pixels(r, frames, frame_hw, n_frames, mem_kind, boxes, box_frame, n, out);
+}
+
+// attention of `crops` crops: qkv [crops * T][3H] fp16 bits (q already scaled) -> out [crops * T][H] fp16 bits
+TAPI int opd_test_reid_attention(const uint16_t* qkv, uint16_t* out, int crops, int T, int H) {
+    ApiScope api_scope;
+    DevBuf dq, dout;
+    RCCHK(up(dq, qkv, (size_t)crops * T * 3 * H * 2));
+    RCCHK(up(dout, nullptr, (size_t)crops * T * H * 2));
+    HIPCHK(opd_launch_reid_attention((const f16_t*)dq.p, (f16_t*)dout.p, crops, T, H, nullptr));
+    HIPCHK(hipMemcpy(out, dout.p, (size_t)crops * T * H * 2, hipMemcpyDeviceToHost));
+    return OPD_OK;
+}
+
+// LayerNorm of rows r * row_stride of x [rows * row_stride][H] fp32: y16 [rows][H] fp16 bits; y32 (may be null) = x rewritten
+TAPI int opd_test_reid_layernorm(const float* x, const float* g, const float* b, float* y32, uint16_t* y16, int rows, int row_stride, int H) {
+    ApiScope api_scope;
+    DevBuf dx, dg, db, dy;
+    const size_t xb = (size_t)rows * row_stride * H * 4;
+    RCCHK(up(dx, x, xb));
+    RCCHK(up(dg, g, (size_t)H * 4));
+    RCCHK(up(db, b, (size_t)H * 4));
+    RCCHK(up(dy, nullptr, (size_t)rows * H * 2));
+    HIPCHK(opd_launch_reid_layernorm((const float*)dx.p, row_stride, (const float*)dg.p, (const float*)db.p, y32 ? (float*)dx.p : nullptr,
+                                     (f16_t*)dy.p, rows, H, nullptr));
+    HIPCHK(hipMemcpy(y16, dy.p, (size_t)rows * H * 2, hipMemcpyDeviceToHost));
+    if (y32) HIPCHK(hipMemcpy(y32, dx.p, xb, hipMemcpyDeviceToHost));
+    return OPD_OK;
+}
+
+// one linear layer: X [M][K], W [N][K] fp16 bits, bias fp32 ([N], or [period][N] for REID_EPI_F32_PBIAS), out fp16 bits or fp32
+// [M][N] (for REID_EPI_F32_RESID `out` holds the residual on entry)
+TAPI int opd_test_reid_gemm(int epi, const uint16_t* X, const uint16_t* W, const float* bias, int period, void* out, int M, int N, int K) {
+    ApiScope api_scope;
+    DevBuf dx, dw, db, dout;
+    const bool f32 = epi == REID_EPI_F32_RESID || epi == REID_EPI_F32_PBIAS;
+    const size_t ob = (size_t)M * N * (f32 ? 4 : 2);
+    RCCHK(up(dx, X, (size_t)M * K * 2));
+    RCCHK(up(dw, W, (size_t)N * K * 2));
+    if (bias) RCCHK(up(db, bias, (size_t)(epi == REID_EPI_F32_PBIAS ? period : 1) * N * 4));
+    RCCHK(up(dout, epi == REID_EPI_F32_RESID ? out : nullptr, ob));
+    HIPCHK(opd_launch_reid_gemm(epi, (const f16_t*)dx.p, (const f16_t*)dw.p, (const float*)db.p, period, dout.p, M, N, K, nullptr));
+    HIPCHK(hipMemcpy(out, dout.p, ob, hipMemcpyDeviceToHost));
+    return OPD_OK;
+}
+
+// per-kernel table of `iters` eager forwards (opd_reid.cpp reid_test_kernel_table); *count = kernels seen, at most `capacity` written
+TAPI int opd_test_reid_kernel_table(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, int n_frames, const float* boxes,
+                                    const int32_t* box_frame, int n, int iters, opd_kernel_stat* out, int capacity, int* count) {
+    return reid_test_kernel_table(r, frames, frame_hw, n_frames, boxes, box_frame, n, iters, out, capacity, count);
+}

@@ -379,3 +379,93 @@ def ensure_weight_file(cache_dir: str, arch: DetrArch = DetrArch(), seed: int = 
         save_safetensors(synth_weights(arch, seed, attention_gain, device_exact=device_exact), tmp)
         os.replace(tmp, path)   # (atomic: several ranks may generate the same file at once)
     return path
+
+
+# ----------------------------------------------------------------------------------------------
+# CLIP ViT image tower (the Re-ID path, reid.py): seeded synthetic weights under the HF
+# ``CLIPVisionModelWithProjection`` key names (``vision_model.*`` + ``visual_projection.weight``).
+# ----------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class ClipArch:
+    hidden: int = 768
+    layers: int = 12
+    heads: int = 12
+    mlp: int = 3072
+    patch: int = 32
+    image: int = 224
+    proj: int = 512
+
+    @staticmethod
+    def vit_b32() -> "ClipArch":
+        return ClipArch()
+
+    @staticmethod
+    def tiny() -> "ClipArch":   # kernel tests: 2 layers, hidden 128, 2 heads
+        return ClipArch(hidden=128, layers=2, heads=2, mlp=512, proj=128)
+
+    @property
+    def tokens(self) -> int:
+        return (self.image // self.patch) ** 2 + 1
+
+    def hf_config(self):
+        from transformers import CLIPVisionConfig
+        return CLIPVisionConfig(hidden_size=self.hidden, intermediate_size=self.mlp, num_hidden_layers=self.layers,
+                                num_attention_heads=self.heads, patch_size=self.patch, image_size=self.image, projection_dim=self.proj,
+                                hidden_act="quick_gelu", layer_norm_eps=1e-5)
+
+
+def synth_clip_weights(cfg: ClipArch = ClipArch(), seed: int = 0, attention_gain: float = 1.0) -> "OrderedDict[str, np.ndarray]":
+    """Seeded fp32 CLIP vision weights.  Linear weights are N(0, 1/fan_in); q and k are multiplied by ``attention_gain``, so with
+    LayerNorm'd tokens the attention logits have a standard deviation of about ``attention_gain ** 2``: 0.5 gives nearly uniform
+    softmax rows ("mild"), 1.5 and above peaked ones ("sharp", where fp16 error in q / k / P shows).  Residual branches (out-proj,
+    fc2) at half strength keep the stream from being dominated by one layer.  A pure function of ``(cfg, seed, attention_gain)``."""
+    rng = np.random.default_rng(seed)
+    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    H, F, P, T = cfg.hidden, cfg.mlp, cfg.patch, cfg.tokens
+
+    def normal(shape, std):
+        return (rng.standard_normal(shape, dtype=np.float32) * np.float32(std)).astype(np.float32)
+
+    vm = "vision_model."
+    out[vm + "embeddings.class_embedding"] = normal((H,), 1.0)
+    out[vm + "embeddings.patch_embedding.weight"] = normal((H, 3, P, P), (3 * P * P) ** -0.5)
+    out[vm + "embeddings.position_embedding.weight"] = normal((T, H), 0.5)
+    out[vm + "pre_layrnorm.weight"] = 1.0 + normal((H,), 0.1)
+    out[vm + "pre_layrnorm.bias"] = normal((H,), 0.05)
+    for i in range(cfg.layers):
+        p = f"{vm}encoder.layers.{i}."
+        for n, gain in (("q_proj", attention_gain), ("k_proj", attention_gain), ("v_proj", 1.0), ("out_proj", 0.5)):
+            out[p + f"self_attn.{n}.weight"] = normal((H, H), gain * H ** -0.5)
+            out[p + f"self_attn.{n}.bias"] = normal((H,), 0.02)
+        out[p + "layer_norm1.weight"] = 1.0 + normal((H,), 0.1)
+        out[p + "layer_norm1.bias"] = normal((H,), 0.05)
+        out[p + "mlp.fc1.weight"] = normal((F, H), H ** -0.5)
+        out[p + "mlp.fc1.bias"] = normal((F,), 0.1)
+        out[p + "mlp.fc2.weight"] = normal((H, F), 0.5 * F ** -0.5)
+        out[p + "mlp.fc2.bias"] = normal((H,), 0.02)
+        out[p + "layer_norm2.weight"] = 1.0 + normal((H,), 0.1)
+        out[p + "layer_norm2.bias"] = normal((H,), 0.05)
+    out[vm + "post_layernorm.weight"] = 1.0 + normal((H,), 0.1)
+    out[vm + "post_layernorm.bias"] = normal((H,), 0.05)
+    out["visual_projection.weight"] = normal((cfg.proj, H), H ** -0.5)
+    return out
+
+
+CLIP_SETS = {   # tag -> (arch, seed, attention_gain): the weight sets the Re-ID tests and goldens use
+    "mild": (ClipArch.vit_b32(), 11, 0.5),
+    "sharp": (ClipArch.vit_b32(), 12, 1.6),
+    "tiny": (ClipArch.tiny(), 13, 1.0),
+}
+
+
+def ensure_clip_weight_file(cache_dir: str, tag: str = "mild") -> str:
+    """Write (once) and return the path of the safetensors file of one of ``CLIP_SETS``."""
+    cfg, seed, gain = CLIP_SETS[tag]
+    os.makedirs(cache_dir, exist_ok=True)
+    path = os.path.join(cache_dir, f"clip_{tag}_seed{seed}_ga{gain:g}_h{cfg.hidden}_l{cfg.layers}.safetensors")
+    if not os.path.exists(path):
+        tmp = path + f".tmp{os.getpid()}"
+        save_safetensors(synth_clip_weights(cfg, seed, gain), tmp)
+        os.replace(tmp, path)
+    return path
