@@ -292,23 +292,34 @@ OPD_API int opd_detr_kernel_times(const opd_detr* m, float* ms4, int32_t* launch
 typedef struct opd_kernel_stat { char name[96]; int32_t launches; float ms; double flops; } opd_kernel_stat;
 OPD_API int opd_detr_kernel_table(const opd_detr* m, opd_kernel_stat* out, int capacity, int* count);
 
-/* ---- Re-ID features: the CLIP ViT image tower (second handle type, own weights, workspace, stream and graphs) ----------------------
- * Replaces `CLIPReIDExtractor.extract_features` (reference src/tracking/reid_feature_extractor.py:108-153): per box, crop the frame at
- * x1 = int(max(0, x)), x2 = int(min(W, x + w)) (same for y; an empty crop becomes a 224 x 224 zero image), BGR -> RGB,
- * CLIPImageProcessor (Pillow bicubic resize to shortest edge 224, centre crop 224, /255, CLIP mean / std), then
- * `CLIPModel.get_image_features` and an L2 normalisation: float32 [n_boxes][feature_dim] with rows of unit norm. */
+/* ---- Re-ID features: the CLIP ViT image tower or OSNet (second handle type, own weights, workspace, stream and graphs) ---------------
+ * One handle type serves the reference's two `ReIDFeatureExtractor` models (src/tracking/reid_feature_extractor.py:369-463), chosen by
+ * opd_reid_config.model.  Per box, both crop the frame at x1 = int(max(0, x)), x2 = int(min(W, x + w)) (same for y), BGR -> RGB, and
+ * return float32 [n_boxes][feature_dim] rows of unit L2 norm.
+ *  - OPD_REID_MODEL_CLIP replaces `CLIPReIDExtractor.extract_features` (lines 108-153): an empty crop becomes a 224 x 224 zero image;
+ *    CLIPImageProcessor (Pillow bicubic resize to shortest edge 224, centre crop 224, /255, CLIP mean / std), then
+ *    `CLIPModel.get_image_features`.
+ *  - OPD_REID_MODEL_OSNET replaces `OSNetReIDExtractor.extract_features` (lines 295-350): an empty crop becomes a 256 x 128 zero image;
+ *    Pillow bilinear resize to 256 x 128 (no aspect ratio kept, no centre crop), ToTensor, ImageNet mean / std, then torchreid's
+ *    `osnet_x1_0` in eval mode without its classifier (512 features after fc + BatchNorm1d + ReLU). */
 typedef struct opd_reid opd_reid; /* opaque Re-ID handle */
+
+#define OPD_REID_MODEL_CLIP 0  /* HF CLIP vision tower (a zeroed config means CLIP) */
+#define OPD_REID_MODEL_OSNET 1 /* torchreid OSNet */
 
 typedef struct opd_reid_config {
     int32_t struct_size; /* = sizeof(opd_reid_config) */
     int32_t max_crops;   /* workspace and launch plans are sized for this many crops; a call with more boxes runs in chunks */
     int32_t flags;       /* OPD_FLAG_NO_GRAPH: eager launches instead of one captured hipGraph per crop-count bucket */
-    int32_t reserved[5];
+    int32_t model;       /* OPD_REID_MODEL_CLIP or OPD_REID_MODEL_OSNET; any other value is OPD_EINVAL */
+    int32_t reserved[4];
 } opd_reid_config;
 
+/* CLIP fills every field.  OSNet fills feature_dim (512), hidden (the last stage width, 512 for x1.0), max_crops, device_ordinal, model
+ * and the two byte counts; tokens, layers, heads, mlp_dim and patch are 0. */
 typedef struct opd_reid_model_info {
     int32_t feature_dim, tokens, hidden, layers, heads, mlp_dim, patch, max_crops;
-    int32_t device_ordinal, reserved;
+    int32_t device_ordinal, model;
     int64_t weight_bytes_device;
     int64_t workspace_bytes_device;
 } opd_reid_model_info;
@@ -317,7 +328,15 @@ typedef struct opd_reid_model_info {
  * `visual_projection.weight`; `text_model.*` is ignored), infer the architecture from the shapes (head_dim 64, or
  * `num_attention_heads` of a config.json beside the file) and upload it.  The schema is checked before the device is touched:
  * head_dim != 64, more than 64 tokens, a hidden size that is not a multiple of 128 (or above 1024), or an image size other than 224
- * return OPD_ESCHEMA with a message naming the limit. */
+ * return OPD_ESCHEMA with a message naming the limit.
+ * OPD_REID_MODEL_OSNET: a safetensors file holding torchreid's OSNet state dict under its own key names (`conv1.conv.weight`,
+ * `conv2.0.conv2b.1.bn.running_var`, `fc.1.weight`, ...; `classifier.*` and integer tensors such as `num_batches_tracked` are ignored).
+ * The four stage widths and the blocks per stage are inferred from the shapes; BatchNorm is folded into the convolutions and into fc in
+ * fp32 at load.  OPD_ESCHEMA (checked before the device is touched) names a missing tensor, a tensor of the wrong shape, an
+ * instance-norm variant (osnet_ain / osnet_ibn: a `bn` without running statistics, or `IN` tensors), an fc width other than 512, or a
+ * width the kernels cannot run: the stem width must be a multiple of 16 up to 64 and every stage width a multiple of 64 (the last one
+ * up to 512).  osnet_x1_0 (64, 256, 384, 512) and osnet_x0_5 (32, 128, 192, 256) run; osnet_x0_75 (stage width 288) and osnet_x0_25
+ * (stage widths 64, 96 with stem 16: 96 is refused) do not. */
 OPD_API int opd_reid_create(const opd_reid_config* cfg, const char* weights_path, int device_ordinal, opd_reid** out);
 OPD_API void opd_reid_destroy(opd_reid* r);
 OPD_API int opd_reid_info(const opd_reid* r, opd_reid_model_info* info);

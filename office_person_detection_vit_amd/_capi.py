@@ -21,6 +21,8 @@ OPD_MEM_DEVICE = 1
 OPD_MEM_HOST_PIXELS_DEVICE_OUT = 2
 OPD_FLAG_NO_GRAPH = 1
 OPD_FLAG_MULTI_STREAM = 2
+OPD_REID_MODEL_CLIP = 0
+OPD_REID_MODEL_OSNET = 1
 OPD_FLAG_BF16 = 4
 OPD_COMM_ID_BYTES = 128
 OPD_OK, OPD_EINVAL, OPD_EIO, OPD_ESCHEMA, OPD_EHIP, OPD_ENOMEM, OPD_ESTATE = 0, -1, -2, -3, -4, -5, -6   # include/opd_detr.h
@@ -49,13 +51,13 @@ class OpdModelInfo(C.Structure):
 
 
 class OpdReidConfig(C.Structure):   # opd_reid_config (include/opd_detr.h)
-    _fields_ = [("struct_size", C.c_int32), ("max_crops", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 5)]
+    _fields_ = [("struct_size", C.c_int32), ("max_crops", C.c_int32), ("flags", C.c_int32), ("model", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class OpdReidModelInfo(C.Structure):   # opd_reid_model_info
     _fields_ = [("feature_dim", C.c_int32), ("tokens", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("mlp_dim", C.c_int32), ("patch", C.c_int32), ("max_crops", C.c_int32), ("device_ordinal", C.c_int32),
-                ("reserved", C.c_int32), ("weight_bytes_device", C.c_int64), ("workspace_bytes_device", C.c_int64)]
+                ("model", C.c_int32), ("weight_bytes_device", C.c_int64), ("workspace_bytes_device", C.c_int64)]
 
 
 # name -> (restype, argtypes): every symbol include/opd_detr.h declares
@@ -187,6 +189,17 @@ TEST_API = {
     "opd_test_reid_attention": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3),
     "opd_test_reid_layernorm": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3),
     "opd_test_reid_gemm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3),
+    # OSNet hooks (csrc/opd_osnet_test_api.cpp)
+    "opd_test_osnet_lut": (C.c_int, [C.c_void_p]),
+    "opd_test_osnet_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "opd_test_osnet_pixels_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "opd_test_osnet_stem": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 2),
+    "opd_test_osnet_gemm": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_void_p] + [C.c_int] * 6),
+    "opd_test_osnet_dwconv": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7),
+    "opd_test_osnet_gate": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4),
+    "opd_test_osnet_avgpool2": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4),
+    "opd_test_osnet_head": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3),
     "opd_test_reid_kernel_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                              C.POINTER(OpdKernelStat), C.c_int, C.POINTER(C.c_int)]),
 }

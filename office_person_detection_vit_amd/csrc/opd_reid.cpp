@@ -1,7 +1,8 @@
 // opd_reid.cpp — the Re-ID handle (include/opd_detr.h, opd_reid_*): CLIP ViT image tower weights, workspace sized once for max_crops,
-// its own stream, one captured hipGraph per crop-count bucket, host staging of each crop's source window.
+// its own stream, one captured hipGraph per crop-count bucket, host staging of each crop's source window.  A handle created with
+// OPD_REID_MODEL_OSNET holds an OsnetModel (opd_osnet.cpp) instead of the CLIP weights and shares everything else.
 //
-// Forward of nb crops (nb = the bucket of the call, padded crops are zero images whose features are discarded):
+// CLIP forward of nb crops (nb = the bucket of the call, padded crops are zero images whose features are discarded):
 //   reid_preprocess -> patch GEMM (+ class / position bias table) -> pre_layrnorm (fp32 stream rewritten)
 //   per layer: LN1 -> QKV GEMM (q pre-scaled by 1/8) -> attention -> out-proj GEMM + residual -> LN2 -> fc1 GEMM + quick_gelu
 //              -> fc2 GEMM + residual
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "opd_model.h"
+#include "opd_osnet.h"
 #include "opd_reid.h"
 
 using namespace opd;
@@ -47,6 +49,7 @@ struct opd_reid {
     f16_t *lut = nullptr, *wpatch = nullptr, *wproj = nullptr;
     float *pbias = nullptr, *preg = nullptr, *preb = nullptr, *postg = nullptr, *postb = nullptr;
     std::vector<ReidLayer> layers;
+    std::unique_ptr<OsnetModel> os;   // OPD_REID_MODEL_OSNET: the OSNet weights and workspace (the CLIP pointers above stay null)
     // workspace (max_crops)
     void* ws = nullptr;
     size_t wsbytes = 0;
@@ -221,6 +224,13 @@ int next_event(opd_reid* r, hipEvent_t* e) {
     } while (0)
 
 int enqueue_forward(opd_reid* r, int nb) {
+    if (r->os) {
+        hipStream_t s = r->stream;
+        return osnet_enqueue(*r->os, nb, reinterpret_cast<const ReidCrop*>(r->d_up), r->d_up, s, [&](double fl, const std::function<hipError_t()>& fn) {
+            LCHK(fn(), fl);
+            return OPD_OK;
+        });
+    }
     const ReidArch& a = r->a;
     const int M = nb * a.T;
     hipStream_t s = r->stream;
@@ -285,6 +295,8 @@ int stage(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, in
           const int32_t* box_frame, int n, int nb, size_t* used) {
     struct Plan { ReidGeom g; int f; std::vector<int32_t> bx, by, ch, cv; int ksh = 0, ksv = 0; size_t toff = 0, woff = 0; };
     std::vector<Plan> plan((size_t)n);
+    const bool os = r->os != nullptr;
+    const int OW = os ? OSNET_W : REID_IMG, OH = os ? OSNET_H : REID_IMG;   // outputs per row / column of the pre-processed image
     size_t off = align_up(sizeof(ReidCrop) * (size_t)nb, 256);
     for (int i = 0; i < n; ++i) {
         Plan& p = plan[i];
@@ -292,18 +304,21 @@ int stage(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, in
         if (p.f < 0 || p.f >= n_frames) return fail(OPD_EINVAL, "opd_reid_extract: box " + std::to_string(i) + " names frame " + std::to_string(p.f));
         const int H = frame_hw[2 * p.f], W = frame_hw[2 * p.f + 1];
         if (H < 1 || W < 1 || !frames[p.f]) return fail(OPD_EINVAL, "opd_reid_extract: frame " + std::to_string(p.f) + " has no pixels");
-        reid_geometry(boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3], H, W, &p.g);
+        if (os) osnet_geometry(boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3], H, W, &p.g);
+        else reid_geometry(boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3], H, W, &p.g);
         if (p.g.zero) continue;
-        std::vector<int32_t> bxa, bya;
-        reid_axis_tables(p.g.x2 - p.g.x1, p.g.rw, p.g.left, REID_IMG, &p.bx, &p.ch, &p.ksh);
-        reid_axis_tables(p.g.y2 - p.g.y1, p.g.rh, p.g.top, REID_IMG, &p.by, &p.cv, &p.ksv);
-        // first taps relative to the window
-        for (int k = 0; k < REID_IMG; ++k) {
-            p.bx[2 * k] -= p.g.wx0 - p.g.x1;
-            p.by[2 * k] -= p.g.wy0 - p.g.y1;
+        if (os) {
+            osnet_axis_tables(p.g.x2 - p.g.x1, OW, &p.bx, &p.ch, &p.ksh);
+            osnet_axis_tables(p.g.y2 - p.g.y1, OH, &p.by, &p.cv, &p.ksv);
+        } else {
+            reid_axis_tables(p.g.x2 - p.g.x1, p.g.rw, p.g.left, REID_IMG, &p.bx, &p.ch, &p.ksh);
+            reid_axis_tables(p.g.y2 - p.g.y1, p.g.rh, p.g.top, REID_IMG, &p.by, &p.cv, &p.ksv);
         }
+        // first taps relative to the window
+        for (int k = 0; k < OW; ++k) p.bx[2 * k] -= p.g.wx0 - p.g.x1;
+        for (int k = 0; k < OH; ++k) p.by[2 * k] -= p.g.wy0 - p.g.y1;
         p.toff = off;
-        off = align_up(off + 4 * (size_t)(4 * REID_IMG + REID_IMG * (p.ksh + p.ksv)), 16);
+        off = align_up(off + 4 * (size_t)(2 * OW + 2 * OH + OW * p.ksh + OH * p.ksv), 16);
     }
     if (mem_kind == OPD_MEM_HOST)
         for (int i = 0; i < n; ++i) {
@@ -326,10 +341,10 @@ int stage(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, in
         c.ks_v = p.ksv;
         c.tables = (int64_t)p.toff;
         int32_t* t = reinterpret_cast<int32_t*>(r->h_up + p.toff);
-        memcpy(t, p.bx.data(), 4 * 2 * REID_IMG);
-        memcpy(t + 2 * REID_IMG, p.by.data(), 4 * 2 * REID_IMG);
-        memcpy(t + 4 * REID_IMG, p.ch.data(), 4 * (size_t)REID_IMG * p.ksh);
-        memcpy(t + 4 * REID_IMG + (size_t)REID_IMG * p.ksh, p.cv.data(), 4 * (size_t)REID_IMG * p.ksv);
+        memcpy(t, p.bx.data(), 4 * 2 * (size_t)OW);
+        memcpy(t + 2 * OW, p.by.data(), 4 * 2 * (size_t)OH);
+        memcpy(t + 2 * OW + 2 * OH, p.ch.data(), 4 * (size_t)OW * p.ksh);
+        memcpy(t + 2 * OW + 2 * OH + (size_t)OW * p.ksh, p.cv.data(), 4 * (size_t)OH * p.ksv);
         const size_t fstart = ((size_t)p.g.wy0 * W + p.g.wx0) * 3;
         if (mem_kind == OPD_MEM_HOST) {
             const size_t rowb = (size_t)(p.g.wx1 - p.g.wx0) * 3;
@@ -373,15 +388,50 @@ struct ReidDeleter {
     void operator()(opd_reid* r) const { destroy_impl(r); }
 };
 
+int create_osnet(const opd_reid_config* cfg, const StateDict& sd, int device, opd_reid** out) {
+    OsnetArchC a;
+    RCCHK(osnet_infer(sd, &a));   // the schema is settled before the device is touched
+    std::unique_ptr<opd_reid, ReidDeleter> r(new opd_reid);
+    r->cfg = *cfg;
+    r->device = device;
+    r->os.reset(new OsnetModel);
+    r->os->a = a;
+    for (int b = 8; b < cfg->max_crops; b *= 2) r->buckets.push_back(b);
+    r->buckets.push_back(cfg->max_crops);
+    std::vector<uint16_t> h16;
+    std::vector<float> h32;
+    OsnetOffsets offs;
+    osnet_pack(sd, a, &h16, &h32, &offs);
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+    const size_t b16 = align_up(h16.size() * 2, 256), b32 = h32.size() * 4;
+    r->wbytes = b16 + b32;
+    HIPCHK(hipMalloc(&r->wmem, r->wbytes));
+    unsigned char* wb = static_cast<unsigned char*>(r->wmem);
+    HIPCHK(hipMemcpy(wb, h16.data(), h16.size() * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(wb + b16, h32.data(), b32, hipMemcpyHostToDevice));
+    osnet_bind(r->os.get(), offs, reinterpret_cast<const f16_t*>(wb), reinterpret_cast<const float*>(wb + b16));
+    r->wsbytes = osnet_workspace(r->os.get(), cfg->max_crops, nullptr);
+    HIPCHK(hipMalloc(&r->ws, r->wsbytes));
+    osnet_workspace(r->os.get(), cfg->max_crops, static_cast<unsigned char*>(r->ws));
+    RCCHK(ensure_upload(r.get(), align_up(sizeof(ReidCrop) * (size_t)cfg->max_crops, 256) + (size_t)cfg->max_crops * 4 * (OSNET_H + OSNET_W) * 8));
+    *out = r.release();
+    ++g_handle_epoch;
+    return OPD_OK;
+}
+
 int create_impl(const opd_reid_config* cfg, const char* weights_path, int device, opd_reid** out) {
     if (!cfg || !weights_path || !out) return fail(OPD_EINVAL, "opd_reid_create: null argument");
     *out = nullptr;
     if (cfg->struct_size != (int32_t)sizeof(opd_reid_config)) return fail(OPD_EINVAL, "opd_reid_config.struct_size mismatch");
     if (cfg->max_crops < 1 || cfg->max_crops > 4096) return fail(OPD_EINVAL, "opd_reid_config.max_crops must be 1 .. 4096");
+    if (cfg->model != OPD_REID_MODEL_CLIP && cfg->model != OPD_REID_MODEL_OSNET)
+        return fail(OPD_EINVAL, "opd_reid_config.model " + std::to_string(cfg->model) + " is neither OPD_REID_MODEL_CLIP (0) nor OPD_REID_MODEL_OSNET (1)");
     StateDict sd;
     std::string err;
     int rc = load_safetensors(weights_path, &sd, &err, /*raw_keys=*/true);
     if (rc) return fail(rc, err);
+    if (cfg->model == OPD_REID_MODEL_OSNET) return create_osnet(cfg, sd, device, out);
     ReidArch a;
     RCCHK(infer_reid_arch(sd, weights_path, &a));   // the schema is settled before the device is touched
     std::unique_ptr<opd_reid, ReidDeleter> r(new opd_reid);   // a failure below releases whatever was already made
@@ -601,6 +651,12 @@ int reid_test_pixels(opd_reid* r, const uint8_t* const* frames, const int32_t* f
     size_t used = 0;
     RCCHK(stage(r, frames, frame_hw, n_frames, mem_kind, boxes, box_frame, n, n, &used));
     HIPCHK(hipMemcpyAsync(r->d_up, r->h_up, used, hipMemcpyHostToDevice, r->stream));
+    if (r->os) {   // OSNet: [n][256][128][4]
+        HIPCHK(opd_launch_osnet_preprocess(reinterpret_cast<const ReidCrop*>(r->d_up), r->d_up, r->os->lut, r->os->img, n, r->stream));
+        HIPCHK(hipMemcpyAsync(out, r->os->img, (size_t)n * OSNET_H * OSNET_W * 4 * 2, hipMemcpyDeviceToHost, r->stream));
+        HIPCHK(hipStreamSynchronize(r->stream));
+        return OPD_OK;
+    }
     HIPCHK(opd_launch_reid_preprocess(reinterpret_cast<const ReidCrop*>(r->d_up), r->d_up, r->lut, r->patches, n, r->a.P, r->a.T, r->stream));
     HIPCHK(hipMemcpyAsync(out, r->patches, (size_t)n * r->a.T * r->a.KP * 2, hipMemcpyDeviceToHost, r->stream));
     HIPCHK(hipStreamSynchronize(r->stream));
@@ -671,6 +727,17 @@ void opd_reid_destroy(opd_reid* r) {
 int opd_reid_info(const opd_reid* r, opd_reid_model_info* info) {
     if (!r || !info) return fail(OPD_EINVAL, "opd_reid_info: null argument");
     memset(info, 0, sizeof *info);
+    if (r->os) {   // OSNet: tokens, layers, heads, mlp_dim and patch stay 0
+        info->model = OPD_REID_MODEL_OSNET;
+        info->feature_dim = OSNET_FEAT;
+        info->hidden = r->os->a.widths[3];
+        info->max_crops = r->cfg.max_crops;
+        info->device_ordinal = r->device;
+        info->weight_bytes_device = (int64_t)r->wbytes;
+        info->workspace_bytes_device = (int64_t)(r->wsbytes + r->up_cap);
+        return OPD_OK;
+    }
+    info->model = OPD_REID_MODEL_CLIP;
     info->feature_dim = r->a.E;
     info->tokens = r->a.T;
     info->hidden = r->a.H;
@@ -692,7 +759,8 @@ int opd_reid_extract(opd_reid* r, const uint8_t* const* frames, const int32_t* f
         RCCHK(check_extract_args(r, frames, frame_hw, n_frames, mem_kind, boxes_xywh, n_boxes, out));
         if (n_boxes == 0) return OPD_OK;
         HIPCHK(hipSetDevice(r->device));
-        const int E = r->a.E;
+        const int E = r->os ? OSNET_FEAT : r->a.E;
+        const float* feat = r->os ? r->os->feat : r->feat;
         for (int c0 = 0; c0 < n_boxes; c0 += r->cfg.max_crops) {   // more boxes than max_crops: chunks of max_crops
             const int n = std::min(r->cfg.max_crops, n_boxes - c0);
             const int nb = bucket_of(r, n);
@@ -700,7 +768,7 @@ int opd_reid_extract(opd_reid* r, const uint8_t* const* frames, const int32_t* f
             RCCHK(stage(r, frames, frame_hw, n_frames, mem_kind, boxes_xywh + 4 * (size_t)c0, box_frame ? box_frame + c0 : nullptr, n, nb, &used));
             HIPCHK(hipMemcpyAsync(r->d_up, r->h_up, used, hipMemcpyHostToDevice, r->stream));
             RCCHK(run_forward(r, nb));
-            HIPCHK(hipMemcpyAsync(out + (size_t)c0 * E, r->feat, (size_t)n * E * 4, hipMemcpyDeviceToHost, r->stream));
+            HIPCHK(hipMemcpyAsync(out + (size_t)c0 * E, feat, (size_t)n * E * 4, hipMemcpyDeviceToHost, r->stream));
             HIPCHK(hipStreamSynchronize(r->stream));   // (the pinned staging image is rewritten by the next chunk)
         }
         return OPD_OK;

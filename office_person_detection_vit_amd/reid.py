@@ -4,13 +4,19 @@
 ``model_type="clip"``: ``extract_features(image, bboxes)`` returns float32 ``(N, 512)`` rows of unit norm, computed by
 ``opd_reid_extract`` (``include/opd_detr.h``): crop, BGR -> RGB, Pillow-exact bicubic resize + centre crop + normalisation, the
 ViT forward and the L2 normalisation all run in HIP kernels (``csrc/kernels_reid.hip``).  Weights come from a local safetensors
-file; nothing is downloaded.  OSNet is not provided by this build.
+file; nothing is downloaded.
+
+``HipOSNetReIDExtractor`` mirrors the reference's ``OSNetReIDExtractor`` (lines 175-365): torchreid's ``osnet_x1_0`` without its
+classifier, Pillow-exact bilinear resize to 256 x 128 and ImageNet normalisation, all on the device (``csrc/kernels_osnet.hip``),
+from a local ``.safetensors`` or torchreid ``.pth`` / ``.pth.tar`` file.  ``create_reid_extractor`` is the façade's dispatch.
 """
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
+import tempfile
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -44,7 +50,8 @@ class HipReIDExtractor:
                  device: str = "hip:0", max_crops: int = 64, use_graph: bool = True):
         model_type = str(model_type).lower()   # (the reference lower-cases it too)
         if model_type != "clip":
-            raise ValueError(f"Re-ID model_type {model_type!r} is not provided by this build (only 'clip' runs on the device)")
+            raise ValueError(f"HipReIDExtractor runs CLIP only, not model_type {model_type!r}: use HipOSNetReIDExtractor for 'osnet', "
+                             "or create_reid_extractor(model_type=...)")
         self.model_type = model_type
         self.model_name = model_name
         self.model_path = model_path
@@ -59,19 +66,31 @@ class HipReIDExtractor:
         d = str(self.device)
         return int(d.split(":", 1)[1]) if ":" in d else 0
 
+    _model_code = _capi.OPD_REID_MODEL_CLIP
+    _model_label = "CLIP"
+
+    def _resolve(self) -> str:
+        return _resolve_weights(self.model_path, self.model_name)
+
+    @contextlib.contextmanager
+    def _weights_file(self, path: str):
+        yield path
+
     def load_model(self) -> None:
         if self._handle is not None:
             return
-        path = _resolve_weights(self.model_path, self.model_name)
+        path = self._resolve()
         lib = _capi.load_library()
         cfg = _capi.OpdReidConfig()
         cfg.struct_size = C.sizeof(_capi.OpdReidConfig)
         cfg.max_crops = self.max_crops
         cfg.flags = 0 if self.use_graph else _capi.OPD_FLAG_NO_GRAPH
+        cfg.model = self._model_code
         h = C.c_void_p()
-        rc = lib.opd_reid_create(C.byref(cfg), path.encode(), self._ordinal(), C.byref(h))
+        with self._weights_file(path) as wpath:
+            rc = lib.opd_reid_create(C.byref(cfg), wpath.encode(), self._ordinal(), C.byref(h))
         if rc != 0:
-            raise RuntimeError(f"Failed to load CLIP Re-ID model: {_capi.last_error()} (code {rc})")
+            raise RuntimeError(f"Failed to load {self._model_label} Re-ID model: {_capi.last_error()} (code {rc})")
         self._handle = h
         info = _capi.OpdReidModelInfo()
         _capi.check(lib.opd_reid_info(h, C.byref(info)), "opd_reid_info")
@@ -139,3 +158,70 @@ class HipReIDExtractor:
         """Features of one already-cropped BGR image: (feature_dim,)."""
         h, w = crop.shape[:2]
         return self.extract_features(crop, [(0.0, 0.0, float(w), float(h))])[0]
+
+
+def torchreid_state_dict(path: str) -> "dict[str, np.ndarray]":
+    """The float tensors of a torchreid checkpoint (``.pth`` / ``.pth.tar``) as torchreid's ``load_pretrained_weights`` sees them:
+    ``state_dict`` unwrapped when present, a ``module.`` prefix stripped, ``classifier.*`` dropped.  Read with
+    ``torch.load(map_location="cpu", weights_only=True)``; torch is imported only here."""
+    import torch
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    sd = ck["state_dict"] if isinstance(ck, dict) and "state_dict" in ck else ck
+    out = {}
+    for k, v in sd.items():
+        if k.startswith("module."):
+            k = k[7:]
+        if k.startswith("classifier.") or not torch.is_tensor(v) or not v.is_floating_point():
+            continue
+        out[k] = v.detach().float().contiguous().numpy()
+    return out
+
+
+class HipOSNetReIDExtractor(HipReIDExtractor):
+    """Drop-in for the reference's ``OSNetReIDExtractor`` (``ReIDFeatureExtractor(model_type="osnet")``): torchreid ``osnet_x1_0``
+    features (512, unit rows) on the device.  ``model_path`` is a ``.safetensors`` file with torchreid's key names or a torchreid
+    ``.pth`` / ``.pth.tar`` checkpoint; nothing is downloaded (the reference's ImageNet download and ResNet18 fallback do not exist
+    here)."""
+
+    _model_code = _capi.OPD_REID_MODEL_OSNET
+    _model_label = "OSNet"
+
+    def __init__(self, model_path: Optional[str] = None, device: str = "hip:0", max_crops: int = 64, use_graph: bool = True):
+        super().__init__(model_type="clip", model_path=model_path, device=device, max_crops=max_crops, use_graph=use_graph)
+        self.model_type = "osnet"
+
+    def _resolve(self) -> str:
+        if not self.model_path:
+            raise FileNotFoundError("OSNet needs model_path= a local .safetensors or torchreid .pth / .pth.tar file; this build never "
+                                    "downloads weights and has no ResNet18 fallback")
+        if not os.path.isfile(self.model_path):
+            raise FileNotFoundError(f"OSNet weight file {self.model_path!r} does not exist (this build never downloads weights)")
+        return self.model_path
+
+    @contextlib.contextmanager
+    def _weights_file(self, path: str):
+        if path.endswith(".safetensors"):
+            yield path
+            return
+        from .weights import save_safetensors
+        sd = torchreid_state_dict(path)
+        fd, tmp = tempfile.mkstemp(suffix=".safetensors")
+        os.close(fd)
+        try:
+            save_safetensors(sd, tmp)
+            yield tmp
+        finally:
+            os.remove(tmp)
+
+
+def create_reid_extractor(model_type: str = "clip", model_name: Optional[str] = None, model_path: Optional[str] = None,
+                          device: str = "hip:0", max_crops: int = 64, use_graph: bool = True):
+    """The reference façade's dispatch (``ReIDFeatureExtractor(model_type=...)``): ``"clip"`` -> ``HipReIDExtractor``, ``"osnet"`` ->
+    ``HipOSNetReIDExtractor`` (case-insensitive); anything else raises ``ValueError``.  ``model_name`` only applies to CLIP."""
+    kind = str(model_type).lower()
+    if kind == "clip":
+        return HipReIDExtractor(model_type="clip", model_name=model_name, model_path=model_path, device=device, max_crops=max_crops,
+                                use_graph=use_graph)
+    if kind == "osnet":
+        return HipOSNetReIDExtractor(model_path=model_path, device=device, max_crops=max_crops, use_graph=use_graph)
+    raise ValueError(f"unknown Re-ID model_type {model_type!r}: expected 'clip' or 'osnet'")

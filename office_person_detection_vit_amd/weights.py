@@ -469,3 +469,193 @@ def ensure_clip_weight_file(cache_dir: str, tag: str = "mild") -> str:
         save_safetensors(synth_clip_weights(cfg, seed, gain), tmp)
         os.replace(tmp, path)
     return path
+
+
+# ----------------------------------------------------------------------------------------------
+# OSNet (the second Re-ID model, reid.py HipOSNetReIDExtractor): seeded synthetic weights under
+# torchreid's ``osnet_x1_0`` key names, BN running statistics calibrated on frame crops.
+# ----------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class OsnetArch:
+    widths: Tuple[int, int, int, int] = (64, 256, 384, 512)   # stem, conv2, conv3, conv4 (osnet_x1_0)
+    blocks: int = 2                                             # OSBlocks per stage (torchreid: [2, 2, 2])
+    feature_dim: int = 512
+
+    @staticmethod
+    def x1_0() -> "OsnetArch":
+        return OsnetArch()
+
+    @staticmethod
+    def x0_5() -> "OsnetArch":
+        return OsnetArch(widths=(32, 128, 192, 256))
+
+
+def osnet_param_specs(arch: OsnetArch) -> Iterator[Tuple[str, Tuple[int, ...], str]]:
+    """(key, shape, kind) of every float tensor of torchreid's OSNet state dict without ``classifier.*``, in module order;
+    kind is conv / bn / gate_w / gate_b / fc_w / fc_b."""
+    def bn(p, c):
+        for n in _BN:
+            yield f"{p}.{n}", (c,), "bn"
+
+    def conv(p, cout, cin, k=1, groups=1):
+        yield f"{p}.weight", (cout, cin // groups, k, k), "conv"
+
+    def conv_bn(p, cout, cin, k=1):
+        yield from conv(p + ".conv", cout, cin, k)
+        yield from bn(p + ".bn", cout)
+
+    def light(p, m):
+        yield from conv(p + ".conv1", m, m)
+        yield from conv(p + ".conv2", m, m, 3, m)
+        yield from bn(p + ".bn", m)
+
+    def block(p, cin, cout):
+        mid = cout // 4
+        yield from conv_bn(p + ".conv1", mid, cin)
+        yield from light(p + ".conv2a", mid)
+        for s, depth in (("b", 2), ("c", 3), ("d", 4)):
+            for j in range(depth):
+                yield from light(f"{p}.conv2{s}.{j}", mid)
+        yield f"{p}.gate.fc1.weight", (mid // 16, mid, 1, 1), "gate_w"
+        yield f"{p}.gate.fc1.bias", (mid // 16,), "gate_b"
+        yield f"{p}.gate.fc2.weight", (mid, mid // 16, 1, 1), "gate_w"
+        yield f"{p}.gate.fc2.bias", (mid,), "gate_b"
+        yield from conv_bn(p + ".conv3", cout, mid)
+        if cin != cout:
+            yield from conv_bn(p + ".downsample", cout, cin)
+
+    c0, c2, c3, c4 = arch.widths
+    yield from conv_bn("conv1", c0, 3, 7)
+    cin = c0
+    for s, cout, pool in (("conv2", c2, True), ("conv3", c3, True), ("conv4", c4, False)):
+        for i in range(arch.blocks):
+            yield from block(f"{s}.{i}", cin, cout)
+            cin = cout
+        if pool:
+            yield from conv_bn(f"{s}.{arch.blocks}.0", cout, cout)
+    yield from conv_bn("conv5", c4, c4)
+    yield "fc.0.weight", (arch.feature_dim, c4), "fc_w"
+    yield "fc.0.bias", (arch.feature_dim,), "fc_b"
+    yield from bn("fc.1", arch.feature_dim)
+
+
+def _osnet_calibrate(w: "OrderedDict[str, np.ndarray]", arch: OsnetArch, crops: np.ndarray) -> None:
+    """Set every BN's running statistics to the batch statistics of its input on ``crops`` ([n][3][256][128] normalised), in fp64:
+    each BN then maps its channels to about N(beta, gamma^2), so no channel is dead or saturated.  Statistics are rounded to 12
+    mantissa bits so that the file does not depend on the last bit of a threaded fp64 reduction."""
+    import torch
+    import torch.nn.functional as F
+
+    T = lambda k: torch.from_numpy(w[k]).double()
+
+    def bn(x, p, relu):
+        dims = [0, 2, 3] if x.dim() == 4 else [0]
+        mean, var = x.mean(dims), x.var(dims, unbiased=False)
+        w[p + ".running_mean"] = _round_mantissa(mean.float().numpy())
+        w[p + ".running_var"] = _round_mantissa(var.float().numpy())
+        shape = [1, -1] + [1] * (x.dim() - 2)
+        y = (x - T(p + ".running_mean").view(shape)) / torch.sqrt(T(p + ".running_var").view(shape) + 1e-5)
+        y = y * T(p + ".weight").view(shape) + T(p + ".bias").view(shape)
+        return F.relu(y) if relu else y
+
+    def conv_bn(x, p, relu=True, stride=1, pad=0):
+        return bn(F.conv2d(x, T(p + ".conv.weight"), stride=stride, padding=pad), p + ".bn", relu)
+
+    def light(x, p):
+        m = x.shape[1]
+        x = F.conv2d(x, T(p + ".conv1.weight"))
+        return bn(F.conv2d(x, T(p + ".conv2.weight"), padding=1, groups=m), p + ".bn", True)
+
+    def gate(x, p):
+        g = F.relu(F.conv2d(x.mean((2, 3), keepdim=True), T(p + ".fc1.weight"), T(p + ".fc1.bias")))
+        return x * torch.sigmoid(F.conv2d(g, T(p + ".fc2.weight"), T(p + ".fc2.bias")))
+
+    def block(x, p):
+        x1 = conv_bn(x, p + ".conv1")
+        x2 = 0
+        for s, depth in (("a", 1), ("b", 2), ("c", 3), ("d", 4)):
+            y = x1
+            for j in range(depth):
+                y = light(y, f"{p}.conv2a" if s == "a" else f"{p}.conv2{s}.{j}")
+            x2 = x2 + gate(y, p + ".gate")
+        x3 = conv_bn(x2, p + ".conv3", relu=False)
+        ident = conv_bn(x, p + ".downsample", relu=False) if (p + ".downsample.conv.weight") in w else x
+        return F.relu(x3 + ident)
+
+    with torch.no_grad():
+        x = torch.from_numpy(crops).double()
+        x = F.max_pool2d(conv_bn(x, "conv1", stride=2, pad=3), 3, 2, 1)
+        for s, pool in (("conv2", True), ("conv3", True), ("conv4", False)):
+            for i in range(arch.blocks):
+                x = block(x, f"{s}.{i}")
+            if pool:
+                x = F.avg_pool2d(conv_bn(x, f"{s}.{arch.blocks}.0"), 2, 2)
+        x = conv_bn(x, "conv5").mean((2, 3))
+        bn(F.linear(x, T("fc.0.weight"), T("fc.0.bias")), "fc.1", True)
+
+
+def osnet_calibration_crops(n: int = 8) -> np.ndarray:
+    """n crops [n][3][256][128] (ImageNet-normalised fp32) of person-sized windows of structured frames: the BN calibration input."""
+    from .frames import structured_frames
+    frames = structured_frames(2, 512, 640, seed=97)
+    mean = np.array([0.485, 0.456, 0.406], np.float32)[:, None, None]
+    std = np.array([0.229, 0.224, 0.225], np.float32)[:, None, None]
+    out = np.zeros((n, 3, 256, 128), np.float32)
+    for i in range(n):
+        f = frames[i % 2]
+        y, x = 40 * (i // 2), 120 * (i // 2) + 20
+        crop = f[y:y + 256, x:x + 128, ::-1].transpose(2, 0, 1).astype(np.float32) / np.float32(255)
+        out[i] = (crop - mean) / std
+    return out
+
+
+def synth_osnet_weights(arch: OsnetArch = OsnetArch(), seed: int = 0, gain: float = 1.0) -> "OrderedDict[str, np.ndarray]":
+    """Seeded fp32 OSNet weights under torchreid's key names.  Convolutions are N(0, 2 / fan_in); BN gammas are ``gain`` * (1 +
+    0.1 N), betas 0.1 N, gate fc weights N(0, gain^2 / fan_in) with biases 0.1 N; running statistics are calibrated on frame crops
+    (_osnet_calibrate).  The gamma of each block's conv3 BN (the residual branch) is quartered: at full strength the random network
+    amplifies a 1e-4 input perturbation to 1e-4 in 1 - cos of the features, and no fp16 path could be told apart from a wrong one.  ``gain`` 1 gives a "mild" set; larger gains sharpen the gates towards 0 / 1 and widen the BN outputs, so a
+    wrong gate, stream or fold shows in the features.  A pure function of ``(arch, seed, gain)``."""
+    rng = np.random.default_rng(seed)
+    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+
+    def normal(shape, std):
+        return (rng.standard_normal(shape, dtype=np.float32) * np.float32(std)).astype(np.float32)
+
+    for key, shape, kind in osnet_param_specs(arch):
+        if kind in ("conv", "fc_w"):
+            fan_in = int(np.prod(shape[1:]))
+            out[key] = normal(shape, (2.0 / fan_in) ** 0.5)
+        elif kind == "gate_w":
+            out[key] = normal(shape, gain * shape[1] ** -0.5)
+        elif kind in ("gate_b", "fc_b"):
+            out[key] = normal(shape, 0.1)
+        elif key.endswith(".weight"):   # BN gamma; an OSBlock's conv3 (its residual branch) at quarter strength
+            out[key] = gain * (1.0 + normal(shape, 0.1)) * np.float32(0.25 if key.endswith("conv3.bn.weight") else 1.0)
+        elif key.endswith(".bias"):
+            out[key] = normal(shape, 0.1)
+        elif key.endswith(".running_mean"):
+            out[key] = np.zeros(shape, np.float32)
+        else:
+            out[key] = np.ones(shape, np.float32)
+    _osnet_calibrate(out, arch, osnet_calibration_crops())
+    return out
+
+
+OSNET_SETS = {   # tag -> (arch, seed, gain): the weight sets the OSNet tests and goldens use
+    "mild": (OsnetArch.x1_0(), 21, 1.0),
+    "sharp": (OsnetArch.x1_0(), 22, 2.5),
+    "half": (OsnetArch.x0_5(), 23, 1.0),
+}
+
+
+def ensure_osnet_weight_file(cache_dir: str, tag: str = "mild") -> str:
+    """Write (once) and return the path of the safetensors file of one of ``OSNET_SETS``."""
+    arch, seed, gain = OSNET_SETS[tag]
+    os.makedirs(cache_dir, exist_ok=True)
+    path = os.path.join(cache_dir, f"osnet_{tag}_seed{seed}_g{gain:g}_w{'-'.join(map(str, arch.widths))}.safetensors")
+    if not os.path.exists(path):
+        tmp = path + f".tmp{os.getpid()}"
+        save_safetensors(synth_osnet_weights(arch, seed, gain), tmp)
+        os.replace(tmp, path)
+    return path

@@ -1,9 +1,10 @@
 """Re-ID throughput on one MI355X: opd_reid_extract on 1280x720 host frames at n = 1, 8, 20 and 160 crops per call, captured graph
 against eager launches, ms per call, crops/s and achieved TFLOP/s from the ViT-B/32 count (4.41 G multiply-adds = 8.83 GFLOP per crop:
-12 x (QKV 88.5 M + out-proj 29.5 M + MLP 235.9 M + attention 3.8 M) + patch embedding 115.6 M; the projection is left out).
+12 x (QKV 88.5 M + out-proj 29.5 M + MLP 235.9 M + attention 3.8 M) + patch embedding 115.6 M; the projection is left out), or with
+--model osnet the OSNet x1.0 count (0.979 G multiply-adds = 1.96 GFLOP per crop at 256 x 128).
 The per-kernel table comes from a rocprofv3 --kernel-trace --stats pass over this script (profiles/NOTES.md).
 
-    python tools/bench_reid.py [--iters 50] [--json out.json]
+    python tools/bench_reid.py [--model clip|osnet] [--iters 50] [--json out.json]
 """
 
 from __future__ import annotations
@@ -22,9 +23,9 @@ import numpy as np  # noqa: E402
 
 from office_person_detection_vit_amd import _capi  # noqa: E402
 from office_person_detection_vit_amd.frames import structured_frames  # noqa: E402
-from office_person_detection_vit_amd.weights import ensure_clip_weight_file  # noqa: E402
+from office_person_detection_vit_amd.weights import ensure_clip_weight_file, ensure_osnet_weight_file  # noqa: E402
 
-GFLOP_PER_CROP = 2 * (12 * (88.5e6 + 29.5e6 + 235.9e6 + 3.8e6) + 115.6e6) / 1e9
+GFLOP_PER_CROP = {"clip": 2 * (12 * (88.5e6 + 29.5e6 + 235.9e6 + 3.8e6) + 115.6e6) / 1e9, "osnet": 1.96}
 
 
 def kernel_table(lib, h, ptrs, hw, n_frames, boxes, owner, n, iters):
@@ -49,6 +50,7 @@ def kernel_table(lib, h, ptrs, hw, n_frames, boxes, owner, n, iters):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("clip", "osnet"), default="clip")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sizes", default="1,8,20,160")
@@ -56,7 +58,9 @@ def main():
     ap.add_argument("--no-table", action="store_true", help="skip the per-kernel table")
     args = ap.parse_args()
     lib = _capi.load_library(test_hooks=True)
-    path = ensure_clip_weight_file(os.environ.get("OPD_WEIGHT_CACHE", "/tmp/opd_weights"), "mild")
+    cache = os.environ.get("OPD_WEIGHT_CACHE", "/tmp/opd_weights")
+    path = ensure_osnet_weight_file(cache, "mild") if args.model == "osnet" else ensure_clip_weight_file(cache, "mild")
+    gflop = GFLOP_PER_CROP[args.model]
     frames = [np.ascontiguousarray(f) for f in structured_frames(4, 720, 1280, seed=99)]
     hw = np.array([f.shape[:2] for f in frames], np.int32)
     ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
@@ -68,6 +72,7 @@ def main():
         cfg.struct_size = C.sizeof(_capi.OpdReidConfig)
         cfg.max_crops = max(sizes)
         cfg.flags = flags
+        cfg.model = _capi.OPD_REID_MODEL_OSNET if args.model == "osnet" else _capi.OPD_REID_MODEL_CLIP
         h = C.c_void_p()
         _capi.check(lib.opd_reid_create(C.byref(cfg), path.encode(), 0, C.byref(h)), "opd_reid_create")
         for n in sizes:
@@ -83,8 +88,8 @@ def main():
             for _ in range(args.iters):
                 call()
             ms = (time.perf_counter() - t) / args.iters * 1e3
-            row = {"mode": mode, "n": n, "ms_per_call": round(ms, 4), "crops_per_s": round(n / ms * 1e3, 1),
-                   "tflops": round(n * GFLOP_PER_CROP / ms, 2)}
+            row = {"model": args.model, "mode": mode, "n": n, "ms_per_call": round(ms, 4), "crops_per_s": round(n / ms * 1e3, 1),
+                   "tflops": round(n * gflop / ms, 2)}
             print(json.dumps(row), flush=True)
             if mode == "graph" and not args.no_table:
                 row["table"] = kernel_table(lib, h, ptrs, hw, len(frames), boxes, owner, n, 10)
@@ -92,7 +97,7 @@ def main():
         lib.opd_reid_destroy(h)
     if args.json:
         with open(args.json, "w") as f:
-            json.dump({"gflop_per_crop": GFLOP_PER_CROP, "rows": rows}, f, indent=1)
+            json.dump({"model": args.model, "gflop_per_crop": gflop, "rows": rows}, f, indent=1)
 
 
 if __name__ == "__main__":
