@@ -189,6 +189,7 @@ TEST_API = {
     "opd_test_reid_attention": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3),
     "opd_test_reid_layernorm": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3),
     "opd_test_reid_gemm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3),
+    "opd_test_reid_l2norm": (C.c_int, [C.c_void_p] + [C.c_int] * 2),
     # OSNet hooks (csrc/opd_osnet_test_api.cpp)
     "opd_test_osnet_lut": (C.c_int, [C.c_void_p]),
     "opd_test_osnet_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

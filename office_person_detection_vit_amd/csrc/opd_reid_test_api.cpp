@@ -118,6 +118,16 @@ TAPI int opd_test_reid_gemm(int epi, const uint16_t* X, const uint16_t* W, const
     return OPD_OK;
 }
 
+// L2 normalisation of `rows` rows of y [rows][E] fp32, in place
+TAPI int opd_test_reid_l2norm(float* y, int rows, int E) {
+    ApiScope api_scope;
+    DevBuf dy;
+    RCCHK(up(dy, y, (size_t)rows * E * 4));
+    HIPCHK(opd_launch_reid_l2norm((float*)dy.p, rows, E, nullptr));
+    HIPCHK(hipMemcpy(y, dy.p, (size_t)rows * E * 4, hipMemcpyDeviceToHost));
+    return OPD_OK;
+}
+
 // per-kernel table of `iters` eager forwards (opd_reid.cpp reid_test_kernel_table); *count = kernels seen, at most `capacity` written
 TAPI int opd_test_reid_kernel_table(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, int n_frames, const float* boxes,
                                     const int32_t* box_frame, int n, int iters, opd_kernel_stat* out, int capacity, int* count) {

@@ -404,6 +404,10 @@ class ClipArch:
     def tiny() -> "ClipArch":   # kernel tests: 2 layers, hidden 128, 2 heads
         return ClipArch(hidden=128, layers=2, heads=2, mlp=512, proj=128)
 
+    @staticmethod
+    def p56() -> "ClipArch":   # patch 56 (17 tokens), hidden 256, 4 heads: the loader's non-B/32 shapes
+        return ClipArch(hidden=256, layers=2, heads=4, mlp=1024, patch=56, proj=512)
+
     @property
     def tokens(self) -> int:
         return (self.image // self.patch) ** 2 + 1
@@ -456,6 +460,7 @@ CLIP_SETS = {   # tag -> (arch, seed, attention_gain): the weight sets the Re-ID
     "mild": (ClipArch.vit_b32(), 11, 0.5),
     "sharp": (ClipArch.vit_b32(), 12, 1.6),
     "tiny": (ClipArch.tiny(), 13, 1.0),
+    "p56": (ClipArch.p56(), 14, 1.0),
 }
 
 
@@ -489,6 +494,10 @@ class OsnetArch:
     @staticmethod
     def x0_5() -> "OsnetArch":
         return OsnetArch(widths=(32, 128, 192, 256))
+
+    @staticmethod
+    def odd() -> "OsnetArch":   # every branch osnet_x1_0 misses: stem 16, streams 16 / 48 / 80 wide, gate hidden 1 / 3 / 5, one block
+        return OsnetArch(widths=(16, 64, 192, 320), blocks=1)
 
 
 def osnet_param_specs(arch: OsnetArch) -> Iterator[Tuple[str, Tuple[int, ...], str]]:
@@ -646,6 +655,7 @@ OSNET_SETS = {   # tag -> (arch, seed, gain): the weight sets the OSNet tests an
     "mild": (OsnetArch.x1_0(), 21, 1.0),
     "sharp": (OsnetArch.x1_0(), 22, 2.5),
     "half": (OsnetArch.x0_5(), 23, 1.0),
+    "odd": (OsnetArch.odd(), 24, 1.0),
 }
 
 

@@ -23,6 +23,17 @@ STD = (0.229, 0.224, 0.225)
 EMU_MAX_ABS, EMU_ONE_MINUS_COS = 1.7e-3, 1.2e-5
 FEAT_MAX_ABS, FEAT_MIN_COS = 3 * EMU_MAX_ABS, 1.0 - 3 * EMU_ONE_MINUS_COS
 
+# The same 3x rule per weight set: x1.0 (mild, sharp) above; the x0.5 widths (half) and the odd widths (odd) measured by emulate_device
+# on their own goldens.  test_osnet_cpu.py re-measures every row.
+EMU_BY_SET = {"mild": (EMU_MAX_ABS, EMU_ONE_MINUS_COS), "sharp": (EMU_MAX_ABS, EMU_ONE_MINUS_COS), "half": (1.6e-3, 8.5e-6),
+              "odd": (1.3e-3, 8.0e-6)}
+
+
+def feat_bounds(tag):
+    """(max |d|, min cos) the device's features must meet against the golden of weight set `tag`."""
+    d, c = EMU_BY_SET[tag]
+    return 3 * d, 1.0 - 3 * c
+
 
 # ---- the model: torchreid osnet.py restated (eval mode) -----------------------------------------------------------------------------
 class ConvLayer(nn.Module):

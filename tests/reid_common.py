@@ -16,6 +16,17 @@ FRAME_H, FRAME_W = 720, 1280
 # the mild and sharp sets; the bounds allow about 3x / 5x that for the device's different accumulation order, and no more, so that a
 # misplaced rounding point or a wrong epsilon shows.
 FEAT_MAX_ABS, FEAT_MIN_COS = 6e-4, 0.999997
+# The same rule (3x max |d|, 5x 1 - cos) for the small sets, from emulate_device against their goldens (37 boxes): tiny (hidden 128,
+# patch 32) measured 1.2e-4 / 9.4e-8, p56 (hidden 256, patch 56, 17 tokens) 7.9e-5 / 1.0e-7.  test_reid_cpu.py re-measures them.
+EMU_BY_SET = {"tiny": (1.2e-4, 9.4e-8), "p56": (7.9e-5, 1.0e-7)}
+
+
+def feat_bounds(tag):
+    """(max |d|, min cos) the device's features must meet against the golden of weight set `tag`."""
+    if tag not in EMU_BY_SET:
+        return FEAT_MAX_ABS, FEAT_MIN_COS
+    d, c = EMU_BY_SET[tag]
+    return 3 * d, 1.0 - 5 * c
 FRAME_SEED = 4321
 N_GOLDEN = 37
 

@@ -34,7 +34,7 @@ def _set(tag):
 def test_golden_reproduces(golden_dir):
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     frames = O.golden_frames()
-    for tag in ("mild", "sharp"):
+    for tag in ("mild", "sharp", "half", "odd"):
         g = np.load(os.path.join(golden_dir, f"osnet_{tag}.npz"))
         assert int(g["frame_seed"]) == O.R.FRAME_SEED and tuple(g["frame_hw"]) == (O.R.FRAME_H, O.R.FRAME_W)
         boxes, owner = O.golden_boxes()
@@ -97,12 +97,13 @@ def test_restatement_keys_are_torchreids(mild_weights):
 def test_goldens_discriminate(golden_dir):
     """The smallest 1 - cos between two different non-degenerate golden crops is >= 100x the asserted bound: the bound cannot pass a
     feature of the wrong crop."""
-    for tag in ("mild", "sharp"):
+    for tag in ("mild", "sharp", "half", "odd"):
         f = np.load(os.path.join(golden_dir, f"osnet_{tag}.npz"))["features"].astype(np.float64)
         keep = [i for i in range(len(f)) if i != 5]   # box 5 is the degenerate one
         c = f[keep] @ f[keep].T
         np.fill_diagonal(c, -1.0)
         assert 1.0 - c.max() >= 100 * (1.0 - O.FEAT_MIN_COS), (tag, 1.0 - c.max())
+        assert 1.0 - c.max() >= 100 * (1.0 - O.feat_bounds(tag)[1]), (tag, 1.0 - c.max())
 
 
 def test_fp16_emulation_within_feature_bounds(golden_dir):
@@ -119,6 +120,14 @@ def test_fp16_emulation_within_feature_bounds(golden_dir):
         worst_d, worst_c = max(worst_d, d), max(worst_c, 1.0 - cos)
     assert worst_d <= O.EMU_MAX_ABS and worst_c <= O.EMU_ONE_MINUS_COS, (worst_d, worst_c)
     assert worst_d >= O.EMU_MAX_ABS / 2 and worst_c >= O.EMU_ONE_MINUS_COS / 3, (worst_d, worst_c)   # the constants are not slack
+    from office_person_detection_vit_amd.weights import OSNET_SETS
+    for tag in ("half", "odd"):   # the per-set rows of osnet_common.EMU_BY_SET, held the same way
+        emu_d, emu_c = O.EMU_BY_SET[tag]
+        g = np.load(os.path.join(golden_dir, f"osnet_{tag}.npz"))
+        _, w = O.osnet_model(tag)
+        d, cos = O.drift(O.emulate_device(w, px, OSNET_SETS[tag][0].blocks), g["features"])
+        assert d <= emu_d and 1.0 - cos <= emu_c, (tag, d, 1.0 - cos)
+        assert d >= emu_d / 2 and 1.0 - cos >= emu_c / 3, (tag, d, 1.0 - cos)
 
 
 def test_host_pixels_equal_pil(lib):

@@ -228,19 +228,23 @@ def test_head(lib):
 
 
 # ---- 3. features against the goldens ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tag", ["mild", "sharp"])
+@pytest.mark.parametrize("tag", ["mild", "sharp", "half", "odd"])
 def test_features_match_golden(lib, weight_cache, golden_dir, frames, parity_log, tag):
+    """x1.0 (mild, sharp), x0.5 (half) and the odd widths 16 / 64 / 192 / 320 with one block per stage (odd), each within its own
+    bound (osnet_common.feat_bounds; the x1.0 ones are FEAT_MAX_ABS / FEAT_MIN_COS)."""
     g = np.load(os.path.join(golden_dir, f"osnet_{tag}.npz"))
+    max_abs, min_cos = O.feat_bounds(tag)
+    name = {"half": "osnet-x0.5", "odd": "osnet-odd"}.get(tag, "osnet-x1.0")
     h = Handle(lib, ensure_osnet_weight_file(weight_cache, tag), 64)
     try:
         for n in (1, 7, 37):
             got = h.extract(frames, g["boxes"][:n], g["owner"][:n])
             d, cos = O.drift(got, g["features"][:n])
-            parity_log(f"reid osnet-x1.0 {tag} n={n} (unit features; dprob = 1 - min cos)", dprob=1.0 - cos, denc=d,
-                       note=f"bound {O.FEAT_MAX_ABS:g} / {O.FEAT_MIN_COS}")
+            parity_log(f"reid {name} {tag} n={n} (unit features; dprob = 1 - min cos)", dprob=1.0 - cos, denc=d,
+                       note=f"bound {max_abs:g} / {min_cos}")
             assert np.all(np.isfinite(got))
             np.testing.assert_allclose(np.linalg.norm(got, axis=1), 1.0, atol=1e-5)
-            assert d <= O.FEAT_MAX_ABS and cos >= O.FEAT_MIN_COS, (tag, n, d, cos)
+            assert d <= max_abs and cos >= min_cos, (tag, n, d, cos)
     finally:
         h.close()
 
@@ -268,6 +272,29 @@ def test_bit_identical_across_batches_chunks_graph_and_memory(lib, weight_cache,
     dev = mild.extract(frames, boxes, owner, _capi.OPD_MEM_DEVICE, [t.data_ptr() for t in keep])
     np.testing.assert_array_equal(dev, full)
     assert mild.extract(frames, boxes[:0], owner[:0]).shape == (0, 512)
+
+
+@pytest.mark.parametrize("tag", ["half", "odd"])
+def test_bit_identical_across_batches_chunks_and_graph_other_widths(lib, weight_cache, frames, tag):
+    """The determinism above at the x0.5 widths and the odd widths (one block per stage)."""
+    boxes, owner = O.golden_boxes()
+    path = ensure_osnet_weight_file(weight_cache, tag)
+    h = Handle(lib, path, 64)
+    eager = Handle(lib, path, 64, _capi.OPD_FLAG_NO_GRAPH)
+    chunked = Handle(lib, path, 16)
+    try:
+        full = h.extract(frames, boxes, owner)
+        np.testing.assert_array_equal(h.extract(frames, boxes, owner), full)
+        for i in (0, 9, 36):
+            np.testing.assert_array_equal(h.extract(frames, boxes[i:i + 1], owner[i:i + 1])[0], full[i])
+        perm = np.random.default_rng(3).permutation(len(boxes))
+        np.testing.assert_array_equal(h.extract(frames, boxes[perm], owner[perm]), full[perm])
+        np.testing.assert_array_equal(eager.extract(frames, boxes, owner), full)
+        np.testing.assert_array_equal(chunked.extract(frames, boxes, owner), full)
+    finally:
+        h.close()
+        eager.close()
+        chunked.close()
 
 
 def test_two_threads_bit_identical(lib, weight_cache, frames, mild):

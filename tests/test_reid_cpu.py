@@ -30,7 +30,7 @@ def _hook_geometry(lib, boxes, H, W):
 def test_golden_reproduces_from_hf(golden_dir):
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     frames = R.golden_frames()
-    for tag in ("mild", "sharp"):
+    for tag in ("mild", "sharp", "tiny", "p56"):
         g = np.load(os.path.join(golden_dir, f"reid_{tag}.npz"))
         assert int(g["frame_seed"]) == R.FRAME_SEED and tuple(g["frame_hw"]) == (R.FRAME_H, R.FRAME_W)
         boxes, owner = R.golden_boxes()
@@ -151,6 +151,21 @@ def test_fp16_emulation_within_feature_bounds():
         model, w = R.hf_model(tag)
         d, cos = R.drift(R.emulate_device(w, pv), R.hf_features(model, pv))
         assert d <= R.FEAT_MAX_ABS and cos >= R.FEAT_MIN_COS, (tag, d, cos)
+
+
+def test_fp16_emulation_within_feature_bounds_small_sets(golden_dir):
+    """The per-set bounds of the tiny (hidden 128) and p56 (patch 56, 17 tokens) sets: emulate_device against their goldens, all 37
+    boxes, within reid_common.EMU_BY_SET and not far below it (the constants are not slack)."""
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    frames = R.golden_frames()
+    boxes, owner = R.golden_boxes()
+    pv = R.hf_pixel_values(frames, boxes, owner)
+    for tag, (emu_d, emu_c) in R.EMU_BY_SET.items():
+        g = np.load(os.path.join(golden_dir, f"reid_{tag}.npz"))
+        _, w = R.hf_model(tag)
+        d, cos = R.drift(R.emulate_device(w, pv), g["features"])
+        assert d <= emu_d and 1.0 - cos <= emu_c, (tag, d, 1.0 - cos)
+        assert d >= emu_d / 2 and 1.0 - cos >= emu_c / 3, (tag, d, 1.0 - cos)
 
 
 def _write_clip(tmp_path, cfg, name="model.safetensors", heads=None):

@@ -37,12 +37,12 @@ class Handle:
         self.lib, self.h = lib, C.c_void_p()
         _capi.check(lib.opd_reid_create(C.byref(cfg), path.encode(), 0, C.byref(self.h)), "opd_reid_create")
 
-    def extract(self, frames, boxes, owner, mem_kind=_capi.OPD_MEM_HOST, ptrs=None):
+    def extract(self, frames, boxes, owner, mem_kind=_capi.OPD_MEM_HOST, ptrs=None, dim=512):
         boxes = np.ascontiguousarray(boxes, np.float32)
         owner = np.ascontiguousarray(owner, np.int32)
         hw = np.array([f.shape[:2] for f in frames], np.int32)
         p = (C.c_void_p * len(frames))(*(ptrs or [f.ctypes.data for f in frames]))
-        out = np.zeros((len(boxes), 512), np.float32)
+        out = np.zeros((len(boxes), dim), np.float32)
         _capi.check(self.lib.opd_reid_extract(self.h, p, hw.ctypes.data, len(frames), mem_kind, boxes.ctypes.data, owner.ctypes.data,
                                               len(boxes), out.ctypes.data), "opd_reid_extract")
         return out
@@ -82,17 +82,21 @@ def test_device_pixels_equal_hf_fp16(lib, weight_cache, frames, mem_kind):
 
 
 # ---- 2. features against HF ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tag", ["mild", "sharp"])
+@pytest.mark.parametrize("tag", ["mild", "sharp", "tiny", "p56"])
 def test_features_match_hf(lib, weight_cache, golden_dir, frames, parity_log, tag):
+    """B/32 (mild, sharp), hidden 128 (tiny) and patch 56 / 17 tokens / hidden 256 (p56), each within its own bound
+    (reid_common.feat_bounds; the B/32 ones are FEAT_MAX_ABS / FEAT_MIN_COS)."""
     g = np.load(os.path.join(golden_dir, f"reid_{tag}.npz"))
+    max_abs, min_cos = R.feat_bounds(tag)
+    name = "clip-b32" if tag in ("mild", "sharp") else "clip"
     h = Handle(lib, ensure_clip_weight_file(weight_cache, tag), 64)
     try:
         for n in (1, 7, 37):
-            got = h.extract(frames, g["boxes"][:n], g["owner"][:n])
+            got = h.extract(frames, g["boxes"][:n], g["owner"][:n], dim=g["features"].shape[1])
             d, cos = R.drift(got, g["features"][:n])
-            parity_log(f"reid clip-b32 {tag} n={n} (unit features; dprob = 1 - min cos)", dprob=1.0 - cos, denc=d, note=f"bound {FEAT_MAX_ABS:g} / {FEAT_MIN_COS}")
+            parity_log(f"reid {name} {tag} n={n} (unit features; dprob = 1 - min cos)", dprob=1.0 - cos, denc=d, note=f"bound {max_abs:g} / {min_cos}")
             assert np.all(np.isfinite(got))
-            assert d <= FEAT_MAX_ABS and cos >= FEAT_MIN_COS, (tag, n, d, cos)
+            assert d <= max_abs and cos >= min_cos, (tag, n, d, cos)
     finally:
         h.close()
 
@@ -116,6 +120,30 @@ def test_batch_independence_bit_identical(lib, weight_cache, frames, mild):
         np.testing.assert_array_equal(eager.extract(frames, boxes, owner), full)
         np.testing.assert_array_equal(chunked.extract(frames, boxes, owner), full)
     finally:
+        eager.close()
+        chunked.close()
+
+
+@pytest.mark.parametrize("tag", ["tiny", "p56"])
+def test_batch_independence_bit_identical_small_sets(lib, weight_cache, frames, tag):
+    """The batch independence above at hidden 128 / 2 heads (tiny) and patch 56 / 17 tokens / 4 heads (p56)."""
+    boxes, owner = R.golden_boxes()
+    dim = 128 if tag == "tiny" else 512
+    path = ensure_clip_weight_file(weight_cache, tag)
+    h = Handle(lib, path, 64)
+    eager = Handle(lib, path, 64, _capi.OPD_FLAG_NO_GRAPH)
+    chunked = Handle(lib, path, 16)
+    try:
+        full = h.extract(frames, boxes, owner, dim=dim)
+        np.testing.assert_array_equal(h.extract(frames, boxes, owner, dim=dim), full)
+        for i in (0, 9, 36):
+            np.testing.assert_array_equal(h.extract(frames, boxes[i:i + 1], owner[i:i + 1], dim=dim)[0], full[i])
+        perm = np.random.default_rng(3).permutation(len(boxes))
+        np.testing.assert_array_equal(h.extract(frames, boxes[perm], owner[perm], dim=dim), full[perm])
+        np.testing.assert_array_equal(eager.extract(frames, boxes, owner, dim=dim), full)
+        np.testing.assert_array_equal(chunked.extract(frames, boxes, owner, dim=dim), full)
+    finally:
+        h.close()
         eager.close()
         chunked.close()
 

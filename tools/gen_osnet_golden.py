@@ -1,10 +1,10 @@
-"""Write tests/golden/osnet_{mild,sharp}.npz: the reference's crop + torchvision pre-processing (through Pillow) and the fp32 torch
+"""Write tests/golden/osnet_{mild,sharp,half,odd}.npz: the reference's crop + torchvision pre-processing (through Pillow) and the fp32 torch
 restatement of torchreid's OSNet (tests/osnet_common.py, eval mode, L2 normalised as the reference does; its fp32 weights and pixels
 evaluated in float64 and the features rounded to float32, so that the file reproduces on any CPU) on the CPU, for the seeded
 synthetic weight sets of weights.OSNET_SETS and the 37 golden boxes of tests/reid_common.py.  Weights and frames are not stored: they are
 regenerated from their seeds; the file keeps the boxes, the frame seed and shape, and the features.
 
-    python tools/gen_osnet_golden.py
+    python tools/gen_osnet_golden.py [tag ...]     (default: every tag)
 """
 
 from __future__ import annotations
@@ -29,8 +29,11 @@ def golden(tag):
     return boxes, owner, feats
 
 
+TAGS = ("mild", "sharp", "half", "odd")
+
+
 def main():
-    for tag in ("mild", "sharp"):
+    for tag in sys.argv[1:] or TAGS:
         boxes, owner, feats = golden(tag)
         path = os.path.join(ROOT, "tests", "golden", f"osnet_{tag}.npz")
         np.savez_compressed(path, boxes=boxes, owner=owner, features=feats, frame_seed=np.int64(O.R.FRAME_SEED),

@@ -1,9 +1,9 @@
-"""Write tests/golden/reid_{mild,sharp}.npz: HF `CLIPImageProcessorPil` + `CLIPVisionModelWithProjection` (`image_embeds`, then L2
+"""Write tests/golden/reid_{mild,sharp,tiny,p56}.npz: HF `CLIPImageProcessorPil` + `CLIPVisionModelWithProjection` (`image_embeds`, then L2
 normalised as the reference does) in fp32 on the CPU, for the seeded synthetic CLIP weight sets of weights.CLIP_SETS and the golden
 boxes of tests/reid_common.py.  The weights and the frames are not stored: they are regenerated from their seeds
 (weights.synth_clip_weights, frames.structured_frames); the file keeps the boxes, the frame seed and shape, and the features.
 
-    python tools/gen_reid_golden.py
+    python tools/gen_reid_golden.py [tag ...]     (default: every tag)
 """
 
 from __future__ import annotations
@@ -20,11 +20,14 @@ import numpy as np  # noqa: E402
 import reid_common as R  # noqa: E402
 
 
+TAGS = ("mild", "sharp", "tiny", "p56")
+
+
 def main():
     frames = R.golden_frames()
     boxes, owner = R.golden_boxes()
     pv = R.hf_pixel_values(frames, boxes, owner)
-    for tag in ("mild", "sharp"):
+    for tag in sys.argv[1:] or TAGS:
         model, _ = R.hf_model(tag)
         feats = R.hf_features(model, pv).astype(np.float32)
         path = os.path.join(ROOT, "tests", "golden", f"reid_{tag}.npz")
