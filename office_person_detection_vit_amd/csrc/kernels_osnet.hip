@@ -30,48 +30,18 @@ __device__ __forceinline__ float4v mfma16(const half8& a, const half8& b, const 
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
-__device__ __forceinline__ int clip8(int v) {
-    v >>= 22;   // arithmetic shift, then clip to uint8 (Pillow's clip8)
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
 // ---- pre-processing ---------------------------------------------------------------------------------------------------------------------
-// grid (256 output rows, crops), block 128 (output columns).  Pillow's bilinear resampler runs the horizontal pass, rounds it to uint8, then
-// the vertical pass over those rows; each output pixel depends only on its row's and column's taps.
+// grid (256 output rows, crops), block 128 (output columns): one output pixel per thread (opd_crop.h), stored through the normalisation
+// table as four halves.
 __global__ __launch_bounds__(128) void osnet_preprocess_kernel(const opd::ReidCrop* __restrict__ crops, const unsigned char* __restrict__ base,
                                                                const _Float16* __restrict__ lut, _Float16* __restrict__ img) {
     const opd::ReidCrop c = crops[blockIdx.y];
     const int yo = blockIdx.x, xo = threadIdx.x;
-    int rgb[3] = {0, 0, 0};
-    if (!c.zero) {
-        const int32_t* bx = reinterpret_cast<const int32_t*>(base + c.tables);
-        const int32_t* by = bx + 2 * opd::OSNET_W;
-        const int32_t* ch = by + 2 * opd::OSNET_H + (size_t)xo * c.ks_h;
-        const int32_t* cv = by + 2 * opd::OSNET_H + (size_t)opd::OSNET_W * c.ks_h + (size_t)yo * c.ks_v;
-        const int xmin = bx[2 * xo], xcnt = bx[2 * xo + 1];
-        const int ymin = by[2 * yo], ycnt = by[2 * yo + 1];
-        const int half = 1 << 21;
-        int a0 = half, a1 = half, a2 = half;
-        for (int j = 0; j < ycnt; ++j) {
-            const uint8_t* row = c.src + (size_t)(ymin + j) * c.pitch + (size_t)xmin * 3;
-            int s0 = half, s1 = half, s2 = half;
-            for (int k = 0; k < xcnt; ++k) {
-                const int w = ch[k];
-                s0 += (int)row[3 * k] * w;
-                s1 += (int)row[3 * k + 1] * w;
-                s2 += (int)row[3 * k + 2] * w;
-            }
-            const int w = cv[j];
-            a0 += clip8(s0) * w; a1 += clip8(s1) * w; a2 += clip8(s2) * w;
-        }
-        rgb[0] = clip8(a2);   // BGR -> RGB
-        rgb[1] = clip8(a1);
-        rgb[2] = clip8(a0);
-    }
+    const opd::CropRgb rgb = opd::crop_resample_pixel(c, base, xo, yo, opd::OSNET_W, opd::OSNET_H);
     half4 o;
-    o[0] = lut[rgb[0]];
-    o[1] = lut[256 + rgb[1]];
-    o[2] = lut[512 + rgb[2]];
+    o[0] = lut[rgb.c[0]];
+    o[1] = lut[256 + rgb.c[1]];
+    o[2] = lut[512 + rgb.c[2]];
     o[3] = (_Float16)0.f;
     *reinterpret_cast<half4*>(img + (((size_t)blockIdx.y * opd::OSNET_H + yo) * opd::OSNET_W + xo) * 4) = o;
 }

@@ -1,4 +1,4 @@
-// kernels_reid.hip — the CLIP ViT image tower of the Re-ID path (opd_reid.cpp), gfx950, fp16 operands with fp32 accumulation.
+// kernels_reid.hip — the CLIP ViT image tower of the Re-ID path (opd_clip.cpp), gfx950, fp16 operands with fp32 accumulation.
 //
 //   reid_preprocess_kernel   crop + BGR->RGB + Pillow-exact bicubic resize (centre 224 x 224 window only) + /255 + mean/std -> patch rows
 //   reid_gemm_kernel<EPI>    every linear layer: 64 x 64 output tile per workgroup, K in steps of 64 through LDS, v_mfma_f32_16x16x32_f16
@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "opd_reid.h"
+#include "opd_clip.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -28,9 +28,8 @@ __device__ __forceinline__ float4v mfma16(const half8& a, const half8& b, const 
 }
 
 // ---- pre-processing -------------------------------------------------------------------------------------------------------------------
-// grid (224 output rows, crops), block 224 (output columns).  Pillow's two-pass resampler rounds the horizontal pass to uint8 and then
-// runs the vertical pass over those rows; every output pixel depends only on its own row's and column's taps, so computing the centre
-// window alone is bit-identical with resizing the whole crop and cutting it.
+// grid (224 output rows, crops), block 224 (output columns): one output pixel of the centre window per thread (opd_crop.h), stored into
+// its patch row through the normalisation table.
 __global__ __launch_bounds__(224) void reid_preprocess_kernel(const opd::ReidCrop* __restrict__ crops, const unsigned char* __restrict__ base,
                                                               const f16_t* __restrict__ lut, f16_t* __restrict__ patches, int P, int T) {
     const opd::ReidCrop c = crops[blockIdx.y];
@@ -40,41 +39,11 @@ __global__ __launch_bounds__(224) void reid_preprocess_kernel(const opd::ReidCro
     const int yo = blockIdx.x, xo = threadIdx.x;
     if (yo == 0)
         for (int i = xo; i < KP; i += blockDim.x) dst[i] = 0;   // row 0: the class token's slot (its value comes through the bias table)
-    int rgb[3] = {0, 0, 0};
-    if (!c.zero) {
-        const int32_t* bx = reinterpret_cast<const int32_t*>(base + c.tables);
-        const int32_t* by = bx + 2 * opd::REID_IMG;
-        const int32_t* ch = by + 2 * opd::REID_IMG + (size_t)xo * c.ks_h;
-        const int32_t* cv = by + 2 * opd::REID_IMG + (size_t)opd::REID_IMG * c.ks_h + (size_t)yo * c.ks_v;
-        const int xmin = bx[2 * xo], xcnt = bx[2 * xo + 1];
-        const int ymin = by[2 * yo], ycnt = by[2 * yo + 1];
-        const int half = 1 << 21;
-        int a0 = half, a1 = half, a2 = half;
-        for (int j = 0; j < ycnt; ++j) {
-            const uint8_t* row = c.src + (size_t)(ymin + j) * c.pitch + (size_t)xmin * 3;
-            int s0 = half, s1 = half, s2 = half;
-            for (int k = 0; k < xcnt; ++k) {
-                const int w = ch[k];
-                s0 += (int)row[3 * k] * w;
-                s1 += (int)row[3 * k + 1] * w;
-                s2 += (int)row[3 * k + 2] * w;
-            }
-            s0 >>= 22; s1 >>= 22; s2 >>= 22;   // arithmetic shift, then clip8
-            s0 = s0 < 0 ? 0 : (s0 > 255 ? 255 : s0);
-            s1 = s1 < 0 ? 0 : (s1 > 255 ? 255 : s1);
-            s2 = s2 < 0 ? 0 : (s2 > 255 ? 255 : s2);
-            const int w = cv[j];
-            a0 += s0 * w; a1 += s1 * w; a2 += s2 * w;
-        }
-        a0 >>= 22; a1 >>= 22; a2 >>= 22;
-        rgb[0] = a2 < 0 ? 0 : (a2 > 255 ? 255 : a2);   // BGR -> RGB
-        rgb[1] = a1 < 0 ? 0 : (a1 > 255 ? 255 : a1);
-        rgb[2] = a0 < 0 ? 0 : (a0 > 255 ? 255 : a0);
-    }
+    const opd::CropRgb rgb = opd::crop_resample_pixel(c, base, xo, yo, opd::REID_IMG, opd::REID_IMG);
     const int p = (yo / P) * gw + xo / P;
     f16_t* o = dst + (size_t)(1 + p) * KP + ((yo % P) * P + xo % P) * 3;
 #pragma unroll
-    for (int ch3 = 0; ch3 < 3; ++ch3) o[ch3] = lut[ch3 * 256 + rgb[ch3]];
+    for (int ch3 = 0; ch3 < 3; ++ch3) o[ch3] = lut[ch3 * 256 + rgb.c[ch3]];
 }
 
 // ---- linear layers ----------------------------------------------------------------------------------------------------------------------

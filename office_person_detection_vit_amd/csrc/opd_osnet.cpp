@@ -15,12 +15,17 @@
 #include <string>
 #include <vector>
 
-#include "opd_model.h"
 #include "opd_osnet.h"
 
 namespace opd {
 
 namespace {
+
+struct OsnetArchC {
+    int widths[4] = {0, 0, 0, 0};   // stem, conv2, conv3, conv4 stage widths
+    int blocks[3] = {0, 0, 0};      // OSBlocks per stage
+    int feat = 0;                   // fc width
+};
 
 const char* STREAM_NAMES = "abcd";
 
@@ -83,7 +88,53 @@ std::string shape_str(const std::vector<int64_t>& s) {
 
 }  // namespace
 
-int osnet_infer(const StateDict& sd, OsnetArchC* a) {
+// device pointers of one OSBlock (all weights BN-folded; 16-bit = fp16)
+struct OsnetBlockW {
+    int cin, cout, mid, hid;
+    bool down;
+    const f16_t* w1; const float* b1;       // conv1 [mid][cin]
+    const f16_t* wl[4];                     // level t: [(5 - t) streams][mid][mid] (level 1: [4 mid][mid])
+    const float* dw[4]; const float* dwb[4];   // level t: depthwise [9][4 mid], bias [4 mid] (streams < t - 1 unused)
+    const float *g1w, *g1b, *g2w, *g2b;     // gate fc1 [hid][mid], fc2 [mid][hid]
+    const f16_t* w3; const float* b3;       // [conv3 | downsample] [cout][mid (+ cin)], bias summed
+};
+
+struct OsnetModel final : ReidModel {
+    OsnetArchC a;
+    std::vector<size_t> o16, o32;           // pack(): where each tensor starts in h16 / h32, in the order bind() resolves them
+    // weights
+    const f16_t* lut = nullptr;             // [3][256] fp16 normalisation table
+    const f16_t* wstem = nullptr; const float* bstem = nullptr;   // [147][64] fp16 (channels padded to 64), bias [64]
+    std::vector<OsnetBlockW> blocks;        // in forward order
+    const f16_t* wtr[2] = {nullptr, nullptr}; const float* btr[2] = {nullptr, nullptr};   // transitions conv2 / conv3
+    const f16_t* w5 = nullptr; const float* b5 = nullptr;
+    const float* wfc = nullptr; const float* bfc = nullptr;   // fc^T [C][512] with BN1d folded
+    // workspace (max_crops)
+    f16_t *img = nullptr, *stem = nullptr, *act[3] = {nullptr, nullptr, nullptr}, *x1 = nullptr, *u = nullptr, *t = nullptr, *x2 = nullptr;
+    float *gates = nullptr, *feat = nullptr;
+
+    const CropSpec& crop() const override { return CROP_OSNET; }
+    int feature_dim() const override { return OSNET_FEAT; }
+    const float* features() const override { return feat; }
+    const void* image() const override { return img; }
+    size_t image_bytes() const override { return (size_t)OSNET_H * OSNET_W * 4 * 2; }
+    void fill_info(opd_reid_model_info* info) const override {   // tokens, layers, heads, mlp_dim and patch stay 0
+        info->model = OPD_REID_MODEL_OSNET;
+        info->feature_dim = OSNET_FEAT;
+        info->hidden = a.widths[3];
+    }
+    void pack(const StateDict& sd, std::vector<uint16_t>* h16, std::vector<float>* h32) override;
+    void bind(const f16_t* w16, const float* w32) override;
+    size_t workspace(int max_crops, unsigned char* base) override;
+    hipError_t preprocess(int nb, const ReidCrop* crops, const unsigned char* base, hipStream_t s) const override {
+        return opd_launch_osnet_preprocess(crops, base, lut, img, nb, s);
+    }
+    int enqueue(int nb, const ReidCrop* crops, const unsigned char* base, ReidLauncher& Q) const override;
+};
+
+// Infer and check the architecture of a torchreid OSNet state dict (every tensor the forward reads, with its shape).  OPD_ESCHEMA names
+// a missing tensor or the kernel limit a width breaks.
+static int osnet_infer(const StateDict& sd, OsnetArchC* a) {
     auto get = [&](const std::string& k) -> const HostTensor* { auto it = sd.find(k); return it == sd.end() ? nullptr : &it->second; };
     for (const auto& kv : sd)
         if (kv.first.find(".IN.") != std::string::npos || kv.first.rfind("IN.", 0) == 0)
@@ -129,11 +180,11 @@ int osnet_infer(const StateDict& sd, OsnetArchC* a) {
     return OPD_OK;
 }
 
-void osnet_pack(const StateDict& sd, const OsnetArchC& a, std::vector<uint16_t>* h16, std::vector<float>* h32, OsnetOffsets* offs) {
+void OsnetModel::pack(const StateDict& sd, std::vector<uint16_t>* h16, std::vector<float>* h32) {
     auto T = [&](const std::string& k) -> const std::vector<float>& { return sd.at(k).data; };
     // every tensor starts 16-byte aligned (the kernels read weights and biases as 8 halves / 4 floats)
-    auto mark16 = [&] { h16->resize((h16->size() + 7) / 8 * 8, 0); offs->o16.push_back(h16->size()); };
-    auto mark32 = [&] { h32->resize((h32->size() + 3) / 4 * 4, 0.f); offs->o32.push_back(h32->size()); };
+    auto mark16 = [&] { h16->resize((h16->size() + 7) / 8 * 8, 0); o16.push_back(h16->size()); };
+    auto mark32 = [&] { h32->resize((h32->size() + 3) / 4 * 4, 0.f); o32.push_back(h32->size()); };
     // BN (eval) as scale / shift in fp32
     auto bn = [&](const std::string& p, std::vector<float>* sc, std::vector<float>* sh) {
         const std::vector<float>&g = T(p + ".weight"), &b = T(p + ".bias"), &m = T(p + ".running_mean"), &v = T(p + ".running_var");
@@ -148,7 +199,7 @@ void osnet_pack(const StateDict& sd, const OsnetArchC& a, std::vector<uint16_t>*
     // normalisation table, stem
     mark16();
     h16->resize(h16->size() + 768);
-    osnet_pixel_lut(h16->data() + offs->o16.back());
+    osnet_pixel_lut(h16->data() + o16.back());
     const int c0 = a.widths[0];
     bn("conv1.bn", &sc, &sh);
     mark16();
@@ -174,7 +225,7 @@ void osnet_pack(const StateDict& sd, const OsnetArchC& a, std::vector<uint16_t>*
     };
     int cin = c0;
     for (int s = 0; s < 3; ++s) {
-        const int cout = a.widths[s + 1], mid = cout / 4, hid = mid / 16;
+        const int cout = a.widths[s + 1], mid = cout / 4;
         for (int i = 0; i < a.blocks[s]; ++i) {
             const std::string p = block_prefix(s, i);
             conv1x1(p + ".conv1", true);
@@ -206,7 +257,6 @@ void osnet_pack(const StateDict& sd, const OsnetArchC& a, std::vector<uint16_t>*
                 const std::vector<float>& v = T(p + n);
                 h32->insert(h32->end(), v.begin(), v.end());
             }
-            (void)hid;
             // [conv3 | downsample] rows, biases summed
             const bool down = cin != cout;
             std::vector<float> sc3, sh3, scd, shd;
@@ -239,15 +289,14 @@ void osnet_pack(const StateDict& sd, const OsnetArchC& a, std::vector<uint16_t>*
     for (int e = 0; e < OSNET_FEAT; ++e) h32->push_back((bf[e] - mf[e]) * sc[e] + T("fc.1.bias")[e]);
 }
 
-void osnet_bind(OsnetModel* m, const OsnetOffsets& offs, const f16_t* w16, const float* w32) {
+void OsnetModel::bind(const f16_t* w16, const float* w32) {
     size_t i16 = 0, i32 = 0;
-    auto n16 = [&] { return w16 + offs.o16[i16++]; };
-    auto n32 = [&] { return w32 + offs.o32[i32++]; };
-    const OsnetArchC& a = m->a;
-    m->lut = n16();
-    m->wstem = n16();
-    m->bstem = n32();
-    m->blocks.clear();
+    auto n16 = [&] { return w16 + o16[i16++]; };
+    auto n32 = [&] { return w32 + o32[i32++]; };
+    lut = n16();
+    wstem = n16();
+    bstem = n32();
+    blocks.clear();
     int cin = a.widths[0];
     for (int s = 0; s < 3; ++s) {
         const int cout = a.widths[s + 1], mid = cout / 4;
@@ -255,89 +304,83 @@ void osnet_bind(OsnetModel* m, const OsnetOffsets& offs, const f16_t* w16, const
             OsnetBlockW b{};
             b.cin = cin; b.cout = cout; b.mid = mid; b.hid = mid / 16; b.down = cin != cout;
             b.w1 = n16(); b.b1 = n32();
-            for (int t = 0; t < 4; ++t) b.wl[t] = n16();
-            for (int t = 0; t < 4; ++t) { b.dw[t] = n32(); b.dwb[t] = n32(); }
+            for (int lv = 0; lv < 4; ++lv) b.wl[lv] = n16();
+            for (int lv = 0; lv < 4; ++lv) { b.dw[lv] = n32(); b.dwb[lv] = n32(); }
             b.g1w = n32(); b.g1b = n32(); b.g2w = n32(); b.g2b = n32();
             b.w3 = n16(); b.b3 = n32();
-            m->blocks.push_back(b);
+            blocks.push_back(b);
             cin = cout;
         }
-        if (s < 2) { m->wtr[s] = n16(); m->btr[s] = n32(); }
+        if (s < 2) { wtr[s] = n16(); btr[s] = n32(); }
     }
-    m->w5 = n16(); m->b5 = n32();
-    m->wfc = n32(); m->bfc = n32();
+    w5 = n16(); b5 = n32();
+    wfc = n32(); bfc = n32();
 }
 
-namespace {
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-}  // namespace
-
-size_t osnet_workspace(OsnetModel* m, int max_crops, unsigned char* base) {
-    const OsnetArchC& a = m->a;
+size_t OsnetModel::workspace(int max_crops, unsigned char* base) {
     const size_t C = (size_t)max_crops;
     const int hw[3] = {64 * 32, 32 * 16, 16 * 8};
-    size_t act = (size_t)hw[0] * a.widths[0], mid = 0;
+    size_t actsz = (size_t)hw[0] * a.widths[0], mid = 0;
     for (int s = 0; s < 3; ++s) {
-        act = std::max(act, (size_t)hw[s] * a.widths[s + 1]);
+        actsz = std::max(actsz, (size_t)hw[s] * a.widths[s + 1]);
         mid = std::max(mid, (size_t)hw[s] * (a.widths[s + 1] / 4));
     }
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align256(off + bytes); return base ? base + o : nullptr; };
-    m->img = reinterpret_cast<f16_t*>(take(C * OSNET_H * OSNET_W * 4 * 2));
-    m->stem = reinterpret_cast<f16_t*>(take(C * (OSNET_H / 2) * (OSNET_W / 2) * a.widths[0] * 2));
-    for (int i = 0; i < 3; ++i) m->act[i] = reinterpret_cast<f16_t*>(take(C * act * 2));
-    m->x1 = reinterpret_cast<f16_t*>(take(C * mid * 2));
-    m->x2 = reinterpret_cast<f16_t*>(take(C * mid * 2));
-    m->u = reinterpret_cast<f16_t*>(take(C * mid * 4 * 2));
-    m->t = reinterpret_cast<f16_t*>(take(C * mid * 4 * 2));
+    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) / 256 * 256; return base ? base + o : nullptr; };
+    img = reinterpret_cast<f16_t*>(take(C * OSNET_H * OSNET_W * 4 * 2));
+    stem = reinterpret_cast<f16_t*>(take(C * (OSNET_H / 2) * (OSNET_W / 2) * a.widths[0] * 2));
+    for (int i = 0; i < 3; ++i) act[i] = reinterpret_cast<f16_t*>(take(C * actsz * 2));
+    x1 = reinterpret_cast<f16_t*>(take(C * mid * 2));
+    x2 = reinterpret_cast<f16_t*>(take(C * mid * 2));
+    u = reinterpret_cast<f16_t*>(take(C * mid * 4 * 2));
+    t = reinterpret_cast<f16_t*>(take(C * mid * 4 * 2));
     const size_t maxmid = (size_t)std::max(a.widths[1], std::max(a.widths[2], a.widths[3])) / 4;
-    m->gates = reinterpret_cast<float*>(take(C * 4 * maxmid * 4));
-    m->feat = reinterpret_cast<float*>(take(C * OSNET_FEAT * 4));
+    gates = reinterpret_cast<float*>(take(C * 4 * maxmid * 4));
+    feat = reinterpret_cast<float*>(take(C * OSNET_FEAT * 4));
     return off;
 }
 
-int osnet_enqueue(const OsnetModel& m, int nb, const ReidCrop* crops, const unsigned char* base, hipStream_t s, const OsnetLaunch& launch) {
-    const OsnetArchC& a = m.a;
-    RCCHK(launch(0.0, [&] { return opd_launch_osnet_preprocess(crops, base, m.lut, m.img, nb, s); }));
-    RCCHK(launch(2.0 * nb * (OSNET_H / 2) * (OSNET_W / 2) * a.widths[0] * 147,
-                 [&] { return opd_launch_osnet_stem(m.img, m.wstem, m.bstem, m.stem, nb, a.widths[0], s); }));
-    RCCHK(launch(0.0, [&] { return opd_launch_osnet_maxpool(m.stem, m.act[0], nb, OSNET_H / 2, OSNET_W / 2, a.widths[0], s); }));
-    auto gemm = [&](int epi, const OsnetGemm& p, int groups) {
-        return launch(2.0 * p.M * p.N * (p.k1 + p.k2) * groups, [&] { return opd_launch_osnet_gemm(epi, p, groups, s); });
+int OsnetModel::enqueue(int nb, const ReidCrop* crops, const unsigned char* base, ReidLauncher& Q) const {
+    hipStream_t s = Q.stream;
+    LCHK(Q, preprocess(nb, crops, base, s), 0.0);
+    LCHK(Q, opd_launch_osnet_stem(img, wstem, bstem, stem, nb, a.widths[0], s), 2.0 * nb * (OSNET_H / 2) * (OSNET_W / 2) * a.widths[0] * 147);
+    LCHK(Q, opd_launch_osnet_maxpool(stem, act[0], nb, OSNET_H / 2, OSNET_W / 2, a.widths[0], s), 0.0);
+    auto gemm = [&](int epi, const OsnetGemm& p, int groups) -> int {
+        LCHK(Q, opd_launch_osnet_gemm(epi, p, groups, s), 2.0 * p.M * p.N * (p.k1 + p.k2) * groups);
+        return OPD_OK;
     };
     int cur = 0, H = OSNET_H / 4, W = OSNET_W / 4;
     size_t bi = 0;
     for (int st = 0; st < 3; ++st) {
         const int HW = H * W, M = nb * HW;
         for (int i = 0; i < a.blocks[st]; ++i) {
-            const OsnetBlockW& b = m.blocks[bi++];
+            const OsnetBlockW& b = blocks[bi++];
             const int mid = b.mid, ld = 4 * mid;
-            f16_t* x = m.act[cur];
-            f16_t* y = m.act[(cur + 1) % 3];
+            f16_t* x = act[cur];
+            f16_t* y = act[(cur + 1) % 3];
             OsnetGemm p{};
             p.M = M;
             // conv1: x -> x1
-            p.a1 = x; p.lda1 = b.cin; p.k1 = b.cin; p.w = b.w1; p.bias = b.b1; p.out = m.x1; p.ldo = mid; p.N = mid;
+            p.a1 = x; p.lda1 = b.cin; p.k1 = b.cin; p.w = b.w1; p.bias = b.b1; p.out = x1; p.ldo = mid; p.N = mid;
             RCCHK(gemm(OSNET_EPI_RELU, p, 1));
             // level 1: the four streams' 1x1 on x1 as one GEMM, then the depthwise over all 4 mid channels
             p = OsnetGemm{};
-            p.M = M; p.a1 = m.x1; p.lda1 = mid; p.k1 = mid; p.w = b.wl[0]; p.out = m.u; p.ldo = ld; p.N = ld;
+            p.M = M; p.a1 = x1; p.lda1 = mid; p.k1 = mid; p.w = b.wl[0]; p.out = u; p.ldo = ld; p.N = ld;
             RCCHK(gemm(OSNET_EPI_NONE, p, 1));
-            RCCHK(launch(2.0 * M * ld * 9, [&] { return opd_launch_osnet_dwconv(m.u, m.t, b.dw[0], b.dwb[0], nb, H, W, ld, 0, ld, ld, s); }));
-            // levels 2 .. 4: streams t - 1 .. 3, one mid x mid weight each
-            for (int t = 2; t <= 4; ++t) {
-                const int c0 = (t - 1) * mid, S = 5 - t;
+            LCHK(Q, opd_launch_osnet_dwconv(u, t, b.dw[0], b.dwb[0], nb, H, W, ld, 0, ld, ld, s), 2.0 * M * ld * 9);
+            // levels 2 .. 4: streams lv - 1 .. 3, one mid x mid weight each
+            for (int lv = 2; lv <= 4; ++lv) {
+                const int c0 = (lv - 1) * mid, S = 5 - lv;
                 p = OsnetGemm{};
-                p.M = M; p.a1 = m.t + c0; p.lda1 = ld; p.k1 = mid; p.a_gcol = mid; p.w = b.wl[t - 1]; p.out = m.u + c0; p.ldo = ld; p.o_gcol = mid;
+                p.M = M; p.a1 = t + c0; p.lda1 = ld; p.k1 = mid; p.a_gcol = mid; p.w = b.wl[lv - 1]; p.out = u + c0; p.ldo = ld; p.o_gcol = mid;
                 p.N = mid;
                 RCCHK(gemm(OSNET_EPI_NONE, p, S));
-                RCCHK(launch(2.0 * M * S * mid * 9,
-                             [&] { return opd_launch_osnet_dwconv(m.u, m.t, b.dw[t - 1], b.dwb[t - 1], nb, H, W, ld, c0, S * mid, ld, s); }));
+                LCHK(Q, opd_launch_osnet_dwconv(u, t, b.dw[lv - 1], b.dwb[lv - 1], nb, H, W, ld, c0, S * mid, ld, s), 2.0 * M * S * mid * 9);
             }
-            RCCHK(launch(0.0, [&] { return opd_launch_osnet_gate(m.t, b.g1w, b.g1b, b.g2w, b.g2b, m.gates, nb, HW, mid, b.hid, s); }));
-            RCCHK(launch(0.0, [&] { return opd_launch_osnet_combine(m.t, m.gates, m.x2, nb, HW, mid, s); }));
+            LCHK(Q, opd_launch_osnet_gate(t, b.g1w, b.g1b, b.g2w, b.g2b, gates, nb, HW, mid, b.hid, s), 0.0);
+            LCHK(Q, opd_launch_osnet_combine(t, gates, x2, nb, HW, mid, s), 0.0);
             p = OsnetGemm{};
-            p.M = M; p.a1 = m.x2; p.lda1 = mid; p.k1 = mid; p.w = b.w3; p.bias = b.b3; p.out = y; p.ldo = b.cout; p.N = b.cout;
+            p.M = M; p.a1 = x2; p.lda1 = mid; p.k1 = mid; p.w = b.w3; p.bias = b.b3; p.out = y; p.ldo = b.cout; p.N = b.cout;
             if (b.down) {
                 p.a2 = x; p.lda2 = b.cin; p.k2 = b.cin;
                 RCCHK(gemm(OSNET_EPI_RELU, p, 1));
@@ -350,9 +393,9 @@ int osnet_enqueue(const OsnetModel& m, int nb, const ReidCrop* crops, const unsi
         if (st < 2) {   // transition: Conv1x1 -> 2x2 average pool
             const int C = a.widths[st + 1];
             OsnetGemm p{};
-            p.M = M; p.a1 = m.act[cur]; p.lda1 = C; p.k1 = C; p.w = m.wtr[st]; p.bias = m.btr[st]; p.out = m.act[(cur + 1) % 3]; p.ldo = C; p.N = C;
+            p.M = M; p.a1 = act[cur]; p.lda1 = C; p.k1 = C; p.w = wtr[st]; p.bias = btr[st]; p.out = act[(cur + 1) % 3]; p.ldo = C; p.N = C;
             RCCHK(gemm(OSNET_EPI_RELU, p, 1));
-            RCCHK(launch(0.0, [&] { return opd_launch_osnet_avgpool2(m.act[(cur + 1) % 3], m.act[(cur + 2) % 3], nb, H, W, C, s); }));
+            LCHK(Q, opd_launch_osnet_avgpool2(act[(cur + 1) % 3], act[(cur + 2) % 3], nb, H, W, C, s), 0.0);
             cur = (cur + 2) % 3;
             H /= 2;
             W /= 2;
@@ -360,36 +403,20 @@ int osnet_enqueue(const OsnetModel& m, int nb, const ReidCrop* crops, const unsi
     }
     const int C = a.widths[3], HW = H * W;
     OsnetGemm p{};
-    p.M = nb * HW; p.a1 = m.act[cur]; p.lda1 = C; p.k1 = C; p.w = m.w5; p.bias = m.b5; p.out = m.act[(cur + 1) % 3]; p.ldo = C; p.N = C;
+    p.M = nb * HW; p.a1 = act[cur]; p.lda1 = C; p.k1 = C; p.w = w5; p.bias = b5; p.out = act[(cur + 1) % 3]; p.ldo = C; p.N = C;
     RCCHK(gemm(OSNET_EPI_RELU, p, 1));
-    RCCHK(launch(2.0 * nb * C * OSNET_FEAT, [&] { return opd_launch_osnet_head(m.act[(cur + 1) % 3], m.wfc, m.bfc, m.feat, nb, HW, C, s); }));
+    LCHK(Q, opd_launch_osnet_head(act[(cur + 1) % 3], wfc, bfc, feat, nb, HW, C, s), 2.0 * nb * C * OSNET_FEAT);
     return OPD_OK;
 }
 
-// ---- pre-processing geometry, tables, normalisation -----------------------------------------------------------------------------------
-void osnet_axis_tables(int in_size, int out_size, std::vector<int32_t>* bounds, std::vector<int32_t>* coeffs, int* ksize) {
-    opd_resize_coeffs_filter(in_size, out_size, /*bicubic=*/false, 0, out_size, bounds, coeffs, ksize);
+int osnet_create(const StateDict& sd, std::unique_ptr<ReidModel>* out) {
+    std::unique_ptr<OsnetModel> m(new OsnetModel);
+    RCCHK(osnet_infer(sd, &m->a));
+    *out = std::move(m);
+    return OPD_OK;
 }
 
-void osnet_geometry(double x, double y, double w, double h, int H, int W, ReidGeom* g) {
-    reid_geometry(x, y, w, h, H, W, g);   // x1 .. y2 and `zero` follow the same expressions (reference lines 313-315)
-    g->rh = OSNET_H;
-    g->rw = OSNET_W;
-    g->top = g->left = 0;
-    g->wy0 = g->wx0 = g->wy1 = g->wx1 = 0;
-    if (g->zero) return;
-    std::vector<int32_t> b, c;
-    int ks;
-    osnet_axis_tables(g->x2 - g->x1, OSNET_W, &b, &c, &ks);
-    g->wx0 = g->x2;
-    g->wx1 = g->x1;
-    for (int k = 0; k < OSNET_W; ++k) { g->wx0 = std::min(g->wx0, g->x1 + b[2 * k]); g->wx1 = std::max(g->wx1, g->x1 + b[2 * k] + b[2 * k + 1]); }
-    osnet_axis_tables(g->y2 - g->y1, OSNET_H, &b, &c, &ks);
-    g->wy0 = g->y2;
-    g->wy1 = g->y1;
-    for (int k = 0; k < OSNET_H; ++k) { g->wy0 = std::min(g->wy0, g->y1 + b[2 * k]); g->wy1 = std::max(g->wy1, g->y1 + b[2 * k] + b[2 * k + 1]); }
-}
-
+// ---- normalisation and the host restatement of the pre-processing ----------------------------------------------------------------------
 void osnet_pixel_lut(uint16_t* lut) {
     // torchvision ToTensor: u8.float().div(255); Normalize: sub_(float32 mean).div_(float32 std), each one fp32 rounding
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
@@ -401,34 +428,13 @@ void osnet_pixel_lut(uint16_t* lut) {
         }
 }
 
-void osnet_preprocess_host(const uint8_t* frame, int H, int W, const ReidGeom& g, const uint16_t* lut, uint16_t* out) {
-    (void)H;
-    std::vector<int32_t> bx, by, chh, cvv;
-    int ksh = 0, ksv = 0;
-    if (!g.zero) {
-        osnet_axis_tables(g.x2 - g.x1, OSNET_W, &bx, &chh, &ksh);
-        osnet_axis_tables(g.y2 - g.y1, OSNET_H, &by, &cvv, &ksv);
+void osnet_preprocess_host(const uint8_t* frame, int W, const ReidGeom& g, const uint16_t* lut, uint16_t* out) {
+    std::vector<uint8_t> rgb((size_t)OSNET_H * OSNET_W * 3);
+    crop_resample_host(CROP_OSNET, frame, W, g, rgb.data());
+    for (size_t i = 0; i < (size_t)OSNET_H * OSNET_W; ++i) {
+        for (int c = 0; c < 3; ++c) out[4 * i + c] = lut[c * 256 + rgb[3 * i + c]];
+        out[4 * i + 3] = 0;
     }
-    auto clip8 = [](int v) { v >>= 22; return v < 0 ? 0 : (v > 255 ? 255 : v); };
-    for (int yo = 0; yo < OSNET_H; ++yo)
-        for (int xo = 0; xo < OSNET_W; ++xo) {
-            int rgb[3] = {0, 0, 0};
-            if (!g.zero) {
-                const int half = 1 << 21;
-                int a[3] = {half, half, half};
-                for (int j = 0; j < by[2 * yo + 1]; ++j) {
-                    const uint8_t* row = frame + ((size_t)(g.y1 + by[2 * yo] + j) * W + g.x1 + bx[2 * xo]) * 3;
-                    int s[3] = {half, half, half};
-                    for (int k = 0; k < bx[2 * xo + 1]; ++k)
-                        for (int c = 0; c < 3; ++c) s[c] += (int)row[3 * k + c] * chh[(size_t)xo * ksh + k];
-                    for (int c = 0; c < 3; ++c) a[c] += clip8(s[c]) * cvv[(size_t)yo * ksv + j];
-                }
-                for (int c = 0; c < 3; ++c) rgb[2 - c] = clip8(a[c]);
-            }
-            uint16_t* o = out + ((size_t)yo * OSNET_W + xo) * 4;
-            for (int c = 0; c < 3; ++c) o[c] = lut[c * 256 + rgb[c]];
-            o[3] = 0;
-        }
 }
 
 }  // namespace opd

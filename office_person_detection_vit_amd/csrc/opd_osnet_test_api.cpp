@@ -5,28 +5,10 @@
 #include <string>
 #include <vector>
 
-#include "opd_model.h"
 #include "opd_osnet.h"
-
-#define TAPI extern "C" __attribute__((visibility("default")))
+#include "opd_reid_test_util.h"
 
 using namespace opd;
-
-namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-int up(DevBuf& d, const void* h, size_t bytes) {
-    HIPCHK(hipMalloc(&d.p, bytes ? bytes : 4));
-    if (h && bytes) HIPCHK(hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice));
-    else if (bytes) HIPCHK(hipMemset(d.p, 0, bytes));
-    return OPD_OK;
-}
-
-}  // namespace
 
 // the normalisation table: lut[c * 256 + u8] fp16 bits
 TAPI int opd_test_osnet_lut(uint16_t* lut) {
@@ -36,12 +18,7 @@ TAPI int opd_test_osnet_lut(uint16_t* lut) {
 
 // host geometry of n boxes: out[i][13] = x1 y1 x2 y2 zero rh rw top left wy0 wx0 wy1 wx1
 TAPI int opd_test_osnet_geometry(const float* boxes, int n, int H, int W, int32_t* out) {
-    for (int i = 0; i < n; ++i) {
-        ReidGeom g;
-        osnet_geometry(boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3], H, W, &g);
-        const int32_t v[13] = {g.x1, g.y1, g.x2, g.y2, g.zero, g.rh, g.rw, g.top, g.left, g.wy0, g.wx0, g.wy1, g.wx1};
-        memcpy(out + 13 * i, v, sizeof v);
-    }
+    geometry_rows(CROP_OSNET, boxes, n, H, W, out);
     return OPD_OK;
 }
 
@@ -51,8 +28,8 @@ TAPI int opd_test_osnet_pixels_host(const uint8_t* frame, int H, int W, const fl
     osnet_pixel_lut(lut.data());
     for (int i = 0; i < n; ++i) {
         ReidGeom g;
-        osnet_geometry(boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3], H, W, &g);
-        osnet_preprocess_host(frame, H, W, g, lut.data(), out + (size_t)i * OSNET_H * OSNET_W * 4);
+        crop_geometry(CROP_OSNET, boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3], H, W, &g);
+        osnet_preprocess_host(frame, W, g, lut.data(), out + (size_t)i * OSNET_H * OSNET_W * 4);
     }
     return OPD_OK;
 }

@@ -5,37 +5,14 @@
 #include <string>
 #include <vector>
 
-#include "opd_model.h"
-#include "opd_reid.h"
-
-#define TAPI extern "C" __attribute__((visibility("default")))
+#include "opd_clip.h"
+#include "opd_reid_test_util.h"
 
 using namespace opd;
 
-namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-int up(DevBuf& d, const void* h, size_t bytes) {
-    HIPCHK(hipMalloc(&d.p, bytes ? bytes : 4));
-    if (h && bytes) HIPCHK(hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice));
-    else if (bytes) HIPCHK(hipMemset(d.p, 0, bytes));
-    return OPD_OK;
-}
-
-}  // namespace
-
 // Host-side geometry of n boxes on an H x W frame: out[i][13] = x1 y1 x2 y2 zero rh rw top left wy0 wx0 wy1 wx1
 TAPI int opd_test_reid_geometry(const float* boxes, int n, int H, int W, int32_t* out) {
-    for (int i = 0; i < n; ++i) {
-        ReidGeom g;
-        reid_geometry(boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3], H, W, &g);
-        const int32_t v[13] = {g.x1, g.y1, g.x2, g.y2, g.zero, g.rh, g.rw, g.top, g.left, g.wy0, g.wx0, g.wy1, g.wx1};
-        memcpy(out + 13 * i, v, sizeof v);
-    }
+    geometry_rows(CROP_CLIP, boxes, n, H, W, out);
     return OPD_OK;
 }
 
@@ -43,7 +20,7 @@ TAPI int opd_test_reid_geometry(const float* boxes, int n, int H, int W, int32_t
 TAPI int opd_test_reid_coeffs(int in_size, int out_size, int first, int count, int32_t* bounds, int32_t* coeffs, int cap) {
     std::vector<int32_t> b, c;
     int ks = 0;
-    reid_axis_tables(in_size, out_size, first, count, &b, &c, &ks);
+    opd_resize_coeffs_filter(in_size, out_size, CROP_CLIP.bicubic, first, count, &b, &c, &ks);
     if (ks > cap) return fail(OPD_EINVAL, "opd_test_reid_coeffs: ksize above cap");
     memcpy(bounds, b.data(), b.size() * 4);
     for (int i = 0; i < count; ++i) memcpy(coeffs + (size_t)i * cap, c.data() + (size_t)i * ks, (size_t)ks * 4);
@@ -63,8 +40,8 @@ TAPI int opd_test_reid_pixels_host(const uint8_t* frame, int H, int W, const flo
     const size_t per = (size_t)T * 3 * P * P;
     for (int i = 0; i < n; ++i) {
         ReidGeom g;
-        reid_geometry(boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3], H, W, &g);
-        reid_preprocess_host(frame, H, W, g, P, lut.data(), out + per * i);
+        crop_geometry(CROP_CLIP, boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3], H, W, &g);
+        reid_preprocess_host(frame, W, g, P, lut.data(), out + per * i);
     }
     return OPD_OK;
 }

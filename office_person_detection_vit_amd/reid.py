@@ -43,16 +43,12 @@ def _resolve_weights(model_path: Optional[str], model_name: Optional[str]) -> st
                             "downloads weights: pass model_path= a safetensors file or model_name= a local directory")
 
 
-class HipReIDExtractor:
-    """Drop-in for the reference's ``ReIDFeatureExtractor(model_type="clip")``."""
+class _ReIDExtractorBase:
+    """Lifecycle and ``extract_*`` of one ``opd_reid`` handle.  A subclass states ``model_type``, the C-ABI's model code, the label of
+    its error messages, how its weight file is found (``_resolve``) and, if the file needs converting, ``_weights_file``."""
 
-    def __init__(self, model_type: str = "clip", model_name: Optional[str] = None, model_path: Optional[str] = None,
-                 device: str = "hip:0", max_crops: int = 64, use_graph: bool = True):
-        model_type = str(model_type).lower()   # (the reference lower-cases it too)
-        if model_type != "clip":
-            raise ValueError(f"HipReIDExtractor runs CLIP only, not model_type {model_type!r}: use HipOSNetReIDExtractor for 'osnet', "
-                             "or create_reid_extractor(model_type=...)")
-        self.model_type = model_type
+    def __init__(self, model_name: Optional[str], model_path: Optional[str], device: str, max_crops: int, use_graph: bool):
+        self.model_type = type(self).model_type
         self.model_name = model_name
         self.model_path = model_path
         self.device = device
@@ -65,12 +61,6 @@ class HipReIDExtractor:
     def _ordinal(self) -> int:
         d = str(self.device)
         return int(d.split(":", 1)[1]) if ":" in d else 0
-
-    _model_code = _capi.OPD_REID_MODEL_CLIP
-    _model_label = "CLIP"
-
-    def _resolve(self) -> str:
-        return _resolve_weights(self.model_path, self.model_name)
 
     @contextlib.contextmanager
     def _weights_file(self, path: str):
@@ -177,18 +167,37 @@ def torchreid_state_dict(path: str) -> "dict[str, np.ndarray]":
     return out
 
 
-class HipOSNetReIDExtractor(HipReIDExtractor):
+class HipReIDExtractor(_ReIDExtractorBase):
+    """Drop-in for the reference's ``ReIDFeatureExtractor(model_type="clip")``."""
+
+    model_type = "clip"
+    _model_code = _capi.OPD_REID_MODEL_CLIP
+    _model_label = "CLIP"
+
+    def __init__(self, model_type: str = "clip", model_name: Optional[str] = None, model_path: Optional[str] = None,
+                 device: str = "hip:0", max_crops: int = 64, use_graph: bool = True):
+        model_type = str(model_type).lower()   # (the reference lower-cases it too)
+        if model_type != "clip":
+            raise ValueError(f"HipReIDExtractor runs CLIP only, not model_type {model_type!r}: use HipOSNetReIDExtractor for 'osnet', "
+                             "or create_reid_extractor(model_type=...)")
+        super().__init__(model_name, model_path, device, max_crops, use_graph)
+
+    def _resolve(self) -> str:
+        return _resolve_weights(self.model_path, self.model_name)
+
+
+class HipOSNetReIDExtractor(_ReIDExtractorBase):
     """Drop-in for the reference's ``OSNetReIDExtractor`` (``ReIDFeatureExtractor(model_type="osnet")``): torchreid ``osnet_x1_0``
     features (512, unit rows) on the device.  ``model_path`` is a ``.safetensors`` file with torchreid's key names or a torchreid
     ``.pth`` / ``.pth.tar`` checkpoint; nothing is downloaded (the reference's ImageNet download and ResNet18 fallback do not exist
     here)."""
 
+    model_type = "osnet"
     _model_code = _capi.OPD_REID_MODEL_OSNET
     _model_label = "OSNet"
 
     def __init__(self, model_path: Optional[str] = None, device: str = "hip:0", max_crops: int = 64, use_graph: bool = True):
-        super().__init__(model_type="clip", model_path=model_path, device=device, max_crops=max_crops, use_graph=use_graph)
-        self.model_type = "osnet"
+        super().__init__(None, model_path, device, max_crops, use_graph)
 
     def _resolve(self) -> str:
         if not self.model_path:
