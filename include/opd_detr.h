@@ -184,6 +184,14 @@ OPD_API int opd_detr_detect_frames(opd_detr* m, const uint8_t* const* frames, in
  * without a record of that class are NOT written (whatever the buffer held).  Suppression (opd_person_nms) happens afterwards on the host: a suppressed record's row is simply unused. */
 OPD_API int opd_detr_detect_frames_features(opd_detr* m, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
                                             int label, opd_det* out, int32_t* counts, float* features);
+/* The same call with the reference's DEFAULT appearance feature instead (`YOLOv8Detector.extract_features`, yolov8_detector.py:161-190, which
+ * `detect_with_features` calls: crop every detection, `FeatureExtractor.extract_batch`): the colour histogram of opd_color_features for every
+ * record of class `label`, computed from the CAMERA-resolution frames this call has just uploaded (h x w, at most 4096 x 4096) under the
+ * record's box (x1, y1, float32(x2 - x1), float32(y2 - y1)) -- the float32 (x, y, w, h) the Python shim passes on for a `Detection.bbox` --
+ * so a row is bit-identical to opd_color_features on that box.  features: [B][num_queries][256] fp32 (host), row = the record's
+ * query_index; rows of queries without a record of that class are NOT written.  Needs d_model = 256 (the handle's feature area). */
+OPD_API int opd_detr_detect_frames_color(opd_detr* m, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
+                                         int label, opd_det* out, int32_t* counts, float* features);
 /* Ragged-batch form (see opd_detr_forward_ragged); `valid_hw` and `orig_hw` are host arrays. */
 OPD_API int opd_detr_detect_ragged(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W,
                            const int32_t* valid_hw, float threshold, const int32_t* orig_hw, opd_det* out, int32_t* counts);
@@ -220,6 +228,19 @@ OPD_API int opd_similarity_matrix(int device_ordinal, const float* feats1, const
  * L2-normalise (x / (||x|| + 1e-8)).  `features` = host [n][D] f32.  Runs on the device. */
 OPD_API int opd_detr_roi_features(opd_detr* m, int frame, const float* boxes_xywh, int n, int orig_h, int orig_w,
                           float* features);
+
+/* Replaces `FeatureExtractor.extract_batch` on the crops `YOLOv8Detector.extract_features` cuts (src/tracking/feature_extractor.py:90-137,
+ * src/detection/yolov8_detector.py:176-185), the tracker's appearance feature whenever `tracking.reid.enabled` is false (the default).
+ * Box i = (x, y, w, h) float32 in pixels of frame box_frame[i] (host int32; NULL = frame 0); frames[f] = [h][w][3] uint8 BGR with
+ * (h, w) = frame_hw[2f], frame_hw[2f + 1] (host int32), at most 4096 x 4096.  The crop is x1 = int(max(0, x)), x2 = int(min(W, x + w)),
+ * same for y; x2 <= x1 or y2 <= y1 takes the reference's 64 x 32 zero image.  Row = 64 bin counts (bin = value >> 2) of B, of G, of R,
+ * then mean, std of B, of G, of R (population std), zeros up to 256, the whole row divided by (its L2 norm + 1e-8).  Counts and sums are
+ * integers on the device and the statistics and the norm are fp64, so a row depends on its pixels alone (not on the other boxes, the
+ * launch shape or mem_kind) and lies within 2^-24 of the exactly evaluated formula.  OPD_MEM_DEVICE: frames are device pointers, read in
+ * place.  OPD_MEM_HOST: one transfer of the crops' source windows, or of the named frames whole when that is fewer bytes; one host wait.
+ * `out` = host float32 [n_boxes][256].  n_boxes == 0 is OPD_OK.  Runs on device `device_ordinal`; needs no model handle. */
+OPD_API int opd_color_features(int device_ordinal, const uint8_t* const* frames, const int32_t* frame_hw, int n_frames, int mem_kind,
+                               const float* boxes_xywh, const int32_t* box_frame, int n_boxes, float* out);
 
 /* Replaces `get_attention_map` / `_extract_attention_map` (deleted vit_detector.py 392-446, `coverage.json:1`; the surviving stand-in
  * returns None, `src/detection/yolov8_detector.py:243-254`; consumer: `Visualizer.draw_attention_map`, `src/visualization/visualizer.py:148-200`,

@@ -76,6 +76,8 @@ API = {
     "opd_detr_detect_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 6 + [C.c_float, C.POINTER(OpdDet), C.POINTER(C.c_int32)]),
     "opd_detr_detect_frames_features": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.POINTER(OpdDet), C.POINTER(C.c_int32),
                                                    C.POINTER(C.c_float)]),
+    "opd_detr_detect_frames_color": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.POINTER(OpdDet), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_float)]),
     "opd_detr_postprocess": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.POINTER(OpdDet), C.POINTER(C.c_int32)]),
     "opd_detr_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                   C.c_void_p, C.POINTER(OpdDet), C.POINTER(C.c_int32)]),
@@ -91,6 +93,7 @@ API = {
     "opd_similarity_matrix": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p]),
     "opd_detr_roi_features": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "opd_color_features": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "opd_detr_attention_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "opd_detr_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "opd_detr_stage_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),

@@ -320,6 +320,51 @@ hipError_t opd_launch_similarity_matrix(const float* f1, const float* b1, const 
                                         const uint8_t* has2, int n2, int D, double aw, double mw, int as_distance, float* out,
                                         hipStream_t stream);
 
+// ---- colour-histogram appearance features (kernels_hist.hip) -----------------------------------------------------------------------
+// FeatureExtractor.extract_batch (src/tracking/feature_extractor.py:90-137) on crops read IN PLACE from BGR uint8 frames: per crop 3 x 64
+// bin counts (bin = v >> 2), mean and population std of B, G, R, zero-padded to 256 floats, L2-normalised (x / (||x|| + 1e-8)).
+// Accumulation is integer (counts, sum v, sum v^2 per channel), so a row does not depend on grid shape, scheduling or its neighbours.
+constexpr int OPD_COLOR_DIM = 256;
+constexpr int OPD_COLOR_ACC_WORDS = 204;   // per crop: uint32 hist[3][64], then uint64 sum[3], sumsq[3] (8-byte aligned: 768 bytes in)
+constexpr int OPD_COLOR_MAX_EDGE = 4096;   // frames up to 4096 x 4096: counts <= 2^24 are exact in fp32, n * sum v^2 fits 64 bits
+struct ColorCrop {
+    const uint8_t* src;   // top-left pixel of the crop (any byte alignment)
+    int32_t pitch;        // bytes per source row
+    int32_t w, h;         // crop size in pixels; w <= 0 or h <= 0: the reference's dummy crop (64 x 32 zeros)
+    int32_t row;          // output row; < 0: skip
+};
+// Python's int() of a float (truncation), saturated far outside any frame; NaN -> 0 never reaches it (fmax / fmin return the number)
+__host__ __device__ inline int opd_py_int(double v) {
+    if (!(v == v)) return 0;
+    if (v > 1e9) return 1000000000;
+    if (v < -1e9) return -1000000000;
+    return (int)v;
+}
+// The crop of an (x, y, w, h) box on an H x W frame (yolov8_detector.py:176-185): x1 = int(max(0, x)), x2 = int(min(W, x + w)), same for y;
+// false = degenerate (x2 <= x1 or y2 <= y1).  One function for the host planner and the kernel that reads device records.
+__host__ __device__ inline bool opd_color_rect(double x, double y, double w, double h, int H, int W, int* x1, int* y1, int* x2, int* y2) {
+    *x1 = opd_py_int(fmax(0.0, x));
+    *y1 = opd_py_int(fmax(0.0, y));
+    *x2 = opd_py_int(fmin((double)W, x + w));
+    *y2 = opd_py_int(fmin((double)H, y + h));
+    return *x2 > *x1 && *y2 > *y1;
+}
+struct ColorParams {
+    const ColorCrop* crops;   // [n] descriptors, or null: crops come from the records below
+    // records mode (opd_detr_detect_frames_color): crop b * Q + i = record i of frame b when i < counts[b] and its class is `label`;
+    // box (x1, y1, float32(x2 - x1), float32(y2 - y1)) as the Python shim hands a Detection.bbox to opd_color_features; output row
+    // b * Q + query_index; other rows are not written
+    const void* records;      // opd_det [B][Q]
+    const int32_t* counts;    // [B]
+    const uint8_t* frames;    // [B][fh][fw][3]
+    int Q, fh, fw, label;
+    int n;                    // crops (records mode: B * Q)
+    uint32_t* acc;            // [n][OPD_COLOR_ACC_WORDS] scratch (zeroed by the launcher)
+    float* out;               // [rows][256]
+};
+// memset of acc + accumulation (grid: n crops x `spans` row spans each) + finish (one wave per crop)
+hipError_t opd_launch_color_features(const ColorParams& p, int spans, hipStream_t stream);
+
 // ---- fused decoder (kernels_dec.hip) -----------------------------------------------------------------------------------------------
 // The decoder (M = batch x queries rows, 2 % of the FLOPs) is a latency chain and the part of the path whose fp16 operand rounding
 // moves the boxes most (tools/drift_split.py), so it runs as FIVE launches per layer on SPLIT operands: every GEMM input x and weight

@@ -1833,6 +1833,45 @@ int opd_detr_detect_frames_features(opd_detr* m, const uint8_t* const* frames, i
     return fetch_records(m, out, counts, OPD_MEM_HOST, features);   // records, counts and feature rows: one copy, one wait
 }
 
+// The colour-histogram twin: same upload, same forward and post-process; the histogram kernels read the CAMERA-resolution frames this call
+// has just put on the device (d_src when it resizes, d_u8 when it does not) under the boxes of the records the post-process left there.
+int opd_detr_detect_frames_color(opd_detr* m, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold, int label,
+                                 opd_det* out, int32_t* counts, float* features) {
+    ApiScope api_scope;
+    if (!m) return fail(OPD_EINVAL, "null model handle");
+    RCCHK(check_shape(m, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, B, H, W));
+    for (int b = 0; b < B; ++b)
+        if (!frames[b]) return fail(OPD_EINVAL, "opd_detr_detect_frames_color: null frame pointer");
+    if (!out || !counts || !features) return fail(OPD_EINVAL, "opd_detr_detect_frames_color: null output buffer");
+    if (m->arch.d_model != OPD_COLOR_DIM) return fail(OPD_EINVAL, "opd_detr_detect_frames_color: the feature area of the handle is sized for d_model = 256");
+    if (h < 1 || w < 1 || h > OPD_COLOR_MAX_EDGE || w > OPD_COLOR_MAX_EDGE)
+        return fail(OPD_EINVAL, "opd_detr_detect_frames_color: frames of " + std::to_string(h) + " x " + std::to_string(w) +
+                                    " are outside the 4096 x 4096 the exact integer sums are sized for");
+    HIPCHK(hipSetDevice(m->device));
+    const int Q = m->arch.queries;
+    if (!m->d_color_acc) RCCHK(dalloc(m, &m->d_color_acc, (size_t)m->cfg.max_batch * Q * OPD_COLOR_ACC_WORDS, false));
+    const bool resized = !(h == H && w == W);
+    if (!resized) {
+        const size_t n1 = (size_t)H * W * 3;
+        for (int b = 0; b < B; ++b) HIPCHK(hipMemcpyAsync(m->d_u8 + b * n1, frames[b], n1, hipMemcpyHostToDevice, m->stream));
+    } else {
+        RCCHK(enqueue_resize(m, nullptr, OPD_MEM_HOST, B, h, w, H, W, frames));
+    }
+    RCCHK(run_forward(m, m->d_u8, OPD_PIXELS_U8_BGR_HWC, B, H, W, nullptr));
+    std::vector<int32_t> orig((size_t)2 * B);
+    for (int b = 0; b < B; ++b) { orig[2 * b] = h; orig[2 * b + 1] = w; }
+    RCCHK(enqueue_postprocess(m, threshold, orig.data()));
+    ColorParams cp{};
+    cp.records = m->d_records; cp.counts = m->d_counts;
+    cp.frames = resized ? m->d_src : m->d_u8;
+    cp.Q = Q; cp.fh = h; cp.fw = w; cp.label = label;
+    cp.n = B * Q;
+    cp.acc = m->d_color_acc;
+    cp.out = m->d_feat_all;
+    HIPCHK(opd_launch_color_features(cp, std::min(64, (h + 15) / 16), m->stream));
+    return fetch_records(m, out, counts, OPD_MEM_HOST, features);   // records, counts and feature rows: one copy, one wait
+}
+
 int opd_host_alloc(size_t bytes, void** out) {
     ApiScope api_scope;
     if (!out || bytes == 0) return fail(OPD_EINVAL, "opd_host_alloc: null output or zero size");

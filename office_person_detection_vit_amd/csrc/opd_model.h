@@ -248,6 +248,7 @@ struct opd_detr {
     struct AsyncHost { void* pinned = nullptr; opd_det* out = nullptr; int32_t* counts = nullptr; int B = 0; };
     AsyncHost async_host[4];
     void* sync_pinned = nullptr;   // page-locked staging of the blocking entry points: [records of max_batch frames | counts]
+    uint32_t* d_color_acc = nullptr;   // [max_batch][queries][OPD_COLOR_ACC_WORDS] integer sums of opd_detr_detect_frames_color (allocated by its first call)
     float* d_feat_all = nullptr;   // [max_batch][queries][d_model] behind the counts in the d_records allocation: features of a batch's records (opd_detr_detect_frames_features)
     // device-side resize (camera resolution -> model resolution): source staging (grown on demand) and coefficient tables
     uint8_t* d_src = nullptr;

@@ -451,21 +451,27 @@ class HipDetrDetector:
             logger.error(f"Detection failed: {e}")
             raise
 
-    def detect_with_features(self, frame: np.ndarray) -> Tuple[List[Detection], np.ndarray]:
-        """Detection + (N, 256) appearance features pooled from the DETR encoder map; assigns ``det.features``
-        (``yolov8_detector.py:134-159``; deleted vit_detector.py 148-171, 224-273)."""
+    def detect_with_features(self, frame: np.ndarray, features: str = "encoder") -> Tuple[List[Detection], np.ndarray]:
+        """Detection + (N, 256) appearance features; assigns ``det.features`` (``yolov8_detector.py:134-159``).
+        ``features="encoder"``: pooled from the DETR encoder map (deleted vit_detector.py 148-171, 224-273).
+        ``features="color"``: the colour histogram of every detection's crop of ``frame``, the feature the reference's
+        ``detect_with_features`` returns today (``yolov8_detector.py:161-190``)."""
         self._require_model()
+        if features not in ("encoder", "color"):
+            raise ValueError(f"features must be 'encoder' or 'color', got {features!r}")
+        color = features == "color"
         target = self._frame_list_target([frame]) if (self.frame_lists and isinstance(frame, np.ndarray)) else None
-        if target is not None and self._info.d_model == 256:
-            # one C-ABI call: the records and the pooled feature of every person record come back behind one host wait
+        if target is not None and self._info.d_model == 256 and not (color and max(frame.shape[:2]) > 4096):
+            # one C-ABI call: the records and the feature of every person record come back behind one host wait
             Q, D = self._info.num_queries, self._info.d_model
             recs, counts = (_capi.OpdDet * Q)(), (C.c_int32 * 1)()
             feats = np.empty((1, Q, D), np.float32)
             ptrs = (C.c_void_p * 1)(frame.ctypes.data)
-            rc = self._lib.opd_detr_detect_frames_features(C.c_void_p(self.model), ptrs, 1, int(frame.shape[0]), int(frame.shape[1]), target[0], target[1],
-                                                           float(self.confidence_threshold), PERSON_LABEL, recs, counts,
-                                                           feats.ctypes.data_as(C.POINTER(C.c_float)))
-            _capi.check(rc, "opd_detr_detect_frames_features")
+            name = "opd_detr_detect_frames_color" if color else "opd_detr_detect_frames_features"
+            rc = getattr(self._lib, name)(C.c_void_p(self.model), ptrs, 1, int(frame.shape[0]), int(frame.shape[1]), target[0], target[1],
+                                          float(self.confidence_threshold), PERSON_LABEL, recs, counts,
+                                          feats.ctypes.data_as(C.POINTER(C.c_float)))
+            _capi.check(rc, name)
             self._last_orig = [(int(frame.shape[0]), int(frame.shape[1]))]
             detections = self._postprocess_batch(recs, counts, Q)[0]
             features = feats[0, [d.query_index for d in detections]] if detections else np.array([])
@@ -473,11 +479,31 @@ class HipDetrDetector:
                 det.features = features[i]
             return detections, features
         detections = self.detect(frame)
-        features = self.extract_features(frame, detections)
+        features = self.extract_color_features(frame, detections) if color else self.extract_features(frame, detections)
         for i, det in enumerate(detections):
             if i < len(features):
                 det.features = features[i]
         return detections, features
+
+    def extract_color_features(self, frame: np.ndarray, detections: List[Detection]) -> np.ndarray:
+        """(N, 256) float32 colour-histogram features of the detections' crops of ``frame`` (BGR uint8 ``[H, W, 3]``), on the
+        device: ``FeatureExtractor.extract_batch`` on the crops ``YOLOv8Detector.extract_features`` cuts
+        (``yolov8_detector.py:161-190``).  Boxes travel as float32, as in ``extract_features``.  Returns ``np.array([])`` for no
+        detections (``yolov8_detector.py:171-172``)."""
+        if len(detections) == 0:
+            return np.array([])
+        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+            raise ValueError("frame must be a uint8 [H, W, 3] BGR array")
+        frame = np.ascontiguousarray(frame)
+        boxes = np.ascontiguousarray(np.asarray([d.bbox for d in detections], dtype=np.float32).reshape(-1, 4))
+        hw = np.array(frame.shape[:2], np.int32)
+        feats = np.empty((len(boxes), 256), np.float32)
+        ptrs = (C.c_void_p * 1)(frame.ctypes.data)
+        lib = self._lib or _capi.load_library()   # (needs no model handle)
+        rc = lib.opd_color_features(int(self.device_ordinal), ptrs, hw.ctypes.data_as(C.c_void_p), 1, _capi.OPD_MEM_HOST,
+                                    boxes.ctypes.data_as(C.c_void_p), None, len(boxes), feats.ctypes.data_as(C.c_void_p))
+        _capi.check(rc, "opd_color_features")
+        return feats
 
     def extract_features(self, frame: np.ndarray, detections: List[Detection]) -> np.ndarray:
         """ROI mean-pool + L2 norm on the encoder map of the LAST forward (frame 0), on the device
