@@ -1,0 +1,700 @@
+// opd_api.cpp — the C-ABI of include/opd_detr.h for the detector: handle creation / cloning / destruction, the argument checks of every
+// entry point, and the ONE detect pipeline behind them (frame source -> device pixels -> forward -> post-process -> feature step -> records).
+// The model itself (weights, workspace, plans, the forward and its graph cache) is opd_model.cpp.
+#include <algorithm>
+#include <new>
+#include <stdexcept>
+
+#include "opd_model.h"
+
+namespace opd {
+
+// mem_kind: where the pixels come from / where the outputs go
+static inline bool pixels_on_device(int mem_kind) { return mem_kind == OPD_MEM_DEVICE; }
+static inline bool outputs_on_device(int mem_kind) { return mem_kind != OPD_MEM_HOST; }
+
+// A pointer that kernels will dereference must be memory the HIP runtime knows as device-accessible (device, page-locked host or managed):
+// an ordinary host pointer handed over with a DEVICE mem_kind would make a kernel fault the GPU -- for every process on it -- instead of
+// returning an error (hipPointerGetAttributes: 0.06 us per call).
+static bool device_accessible(const void* p) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged;
+}
+static int check_device_outputs(int mem_kind, const void* out, const void* counts, const char* who) {
+    if (!outputs_on_device(mem_kind)) return OPD_OK;
+    if (!device_accessible(out) || !device_accessible(counts))
+        return fail(OPD_EINVAL, std::string(who) + ": this mem_kind takes DEVICE output pointers; the ones given are not device-accessible memory");
+    return OPD_OK;
+}
+
+int check_shape(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W) {
+    if (!m) return fail(OPD_EINVAL, "null model handle");
+    if (!pixels) return fail(OPD_EINVAL, "null pixel buffer");
+    if (pixel_format != OPD_PIXELS_U8_BGR_HWC && pixel_format != OPD_PIXELS_F32_NCHW) return fail(OPD_EINVAL, "unknown pixel_format");
+    if (mem_kind != OPD_MEM_HOST && mem_kind != OPD_MEM_DEVICE && mem_kind != OPD_MEM_HOST_PIXELS_DEVICE_OUT)
+        return fail(OPD_EINVAL, "unknown mem_kind");
+    if (pixels_on_device(mem_kind) && !device_accessible(pixels))
+        return fail(OPD_EINVAL, "OPD_MEM_DEVICE: the pixel pointer is not device-accessible memory");
+    const int edge = std::max(m->cfg.max_height, m->cfg.max_width);   // either orientation: see build_workspace
+    if (B < 1 || B > m->cfg.max_batch || H < 32 || W < 32 || H > edge || W > edge ||
+        (size_t)H * W > (size_t)m->cfg.max_height * m->cfg.max_width)
+        return fail(OPD_EINVAL, "frame batch [" + std::to_string(B) + "," + std::to_string(H) + "," + std::to_string(W) +
+                                    "] outside the configured maximum [" + std::to_string(m->cfg.max_batch) + "," +
+                                    std::to_string(m->cfg.max_height) + "," + std::to_string(m->cfg.max_width) + "] (either orientation)");
+    return OPD_OK;
+}
+
+static int stage_pixels(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W, const void** d_pixels) {
+    if (pixels_on_device(mem_kind)) { *d_pixels = pixels; return OPD_OK; }
+    const size_t n = (size_t)B * H * W * 3;
+    if (pixel_format == OPD_PIXELS_U8_BGR_HWC) {
+        HIPCHK(hipMemcpyAsync(m->d_u8, pixels, n, hipMemcpyHostToDevice, m->stream));
+        *d_pixels = m->d_u8;
+    } else {
+        HIPCHK(hipMemcpyAsync(m->d_pv, pixels, n * 4, hipMemcpyHostToDevice, m->stream));
+        *d_pixels = m->d_pv;
+    }
+    return OPD_OK;
+}
+
+// Frames at camera resolution -> m->d_u8 at model resolution (Pillow-exact bilinear, kernels_misc.hip).
+// (`list` != null: one host pointer per frame instead of the contiguous block `frames`)
+static int enqueue_resize(opd_detr* m, const uint8_t* frames, int mem_kind, int B, int h, int w, int oh, int ow, const uint8_t* const* list = nullptr) {
+    if (h < 1 || w < 1 || (size_t)h * w > (size_t)1 << 26) return fail(OPD_EINVAL, "source frame size out of range");
+    const size_t need = (size_t)B * h * w * 3;
+    const uint8_t* d_in = frames;
+    if (!pixels_on_device(mem_kind)) {
+        if (need > m->src_bytes) {
+            HIPCHK(hipStreamSynchronize(m->stream));
+            if (m->d_src) (void)hipFree(m->d_src);
+            m->d_src = nullptr; m->src_bytes = 0;
+            void* q = nullptr;
+            if (hipMalloc(&q, need) != hipSuccess) return fail(OPD_ENOMEM, "source frame staging allocation failed");
+            m->d_src = reinterpret_cast<uint8_t*>(q);
+            m->src_bytes = need;
+        }
+        if (list) {
+            for (int b = 0; b < B; ++b) HIPCHK(hipMemcpyAsync(m->d_src + (size_t)b * h * w * 3, list[b], (size_t)h * w * 3, hipMemcpyHostToDevice, m->stream));
+        } else {
+            HIPCHK(hipMemcpyAsync(m->d_src, frames, need, hipMemcpyHostToDevice, m->stream));
+        }
+        d_in = m->d_src;
+    }
+    const opd_detr::ResizeTab* tab = nullptr;
+    for (const auto& t : m->resize_tabs)
+        if (t.h == h && t.w == w && t.oh == oh && t.ow == ow) tab = &t;
+    if (!tab) {
+        std::vector<int32_t> bh, kh, bv, kv;
+        opd_detr::ResizeTab t{h, w, oh, ow, 0, 0, nullptr, nullptr, nullptr, nullptr};
+        opd_resize_coeffs(w, ow, &bh, &kh, &t.ksh);
+        opd_resize_coeffs(h, oh, &bv, &kv, &t.ksv);
+        auto up = [&](const std::vector<int32_t>& v, int32_t** d) -> int {
+            RCCHK(dalloc(m, d, v.size(), false));
+            HIPCHK(hipMemcpy(*d, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+            return OPD_OK;
+        };
+        RCCHK(up(bh, &t.bh)); RCCHK(up(kh, &t.kh)); RCCHK(up(bv, &t.bv)); RCCHK(up(kv, &t.kv));
+        m->resize_tabs.push_back(t);
+        tab = &m->resize_tabs.back();
+    }
+    HIPCHK(opd_launch_resize_u8(d_in, m->d_u8, B, h, w, oh, ow, tab->bh, tab->kh, tab->ksh, tab->bv, tab->kv, tab->ksv, m->stream));
+    return OPD_OK;
+}
+
+// The source step of every detect / forward entry point: the frames of `src` -> `*d_pixels`, device pixels at model resolution H x W.
+// `*d_camera`: where the camera-resolution frames now lie on the device (d_src, or the caller's block, when they were resized; d_u8 when not).
+static int stage_frames(opd_detr* m, const FrameSource& src, int B, int H, int W, const void** d_pixels, const uint8_t** d_camera) {
+    if (src.kind == SRC_PIXELS) return stage_pixels(m, src.frames, src.pixel_format, src.mem_kind, B, H, W, d_pixels);
+    const uint8_t* block = src.kind == SRC_BLOCK ? static_cast<const uint8_t*>(src.frames) : nullptr;
+    const uint8_t* const* list = src.kind == SRC_LIST ? static_cast<const uint8_t* const*>(src.frames) : nullptr;
+    *d_pixels = *d_camera = m->d_u8;
+    if (list && src.h == H && src.w == W) {
+        const size_t n1 = (size_t)H * W * 3;
+        for (int b = 0; b < B; ++b) HIPCHK(hipMemcpyAsync(m->d_u8 + b * n1, list[b], n1, hipMemcpyHostToDevice, m->stream));
+        return OPD_OK;
+    }
+    RCCHK(enqueue_resize(m, block, src.mem_kind, B, src.h, src.w, H, W, list));
+    *d_camera = pixels_on_device(src.mem_kind) ? block : m->d_src;
+    return OPD_OK;
+}
+
+// `orig_hw` (nullable): the frame sizes the boxes are scaled to, else h x w for every frame.  `dev_out` / `dev_counts` (nullable): device buffers of the
+// caller; the kernel then writes there directly instead of the library's own record buffers (no device-to-device copies afterwards).
+static int enqueue_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, int h, int w, opd_det* dev_out, int32_t* dev_counts) {
+    const int B = m->last_B;
+    std::vector<int32_t> hw((size_t)B * 2);
+    for (int b = 0; b < B; ++b) {
+        hw[2 * b] = orig_hw ? orig_hw[2 * b] : h;
+        hw[2 * b + 1] = orig_hw ? orig_hw[2 * b + 1] : w;
+    }
+    if (hw != m->h_orig_hw) {   // the frame sizes of a video do not change from call to call: upload only when they do
+        HIPCHK(hipStreamSynchronize(m->stream));   // (an earlier asynchronous copy may still be reading the old host vector)
+        m->h_orig_hw = hw;      // member: must outlive the async copy
+        HIPCHK(hipMemcpyAsync(m->d_orig_hw, m->h_orig_hw.data(), m->h_orig_hw.size() * 4, hipMemcpyHostToDevice, m->stream));
+    }
+    PostParams pp{};
+    pp.logits = m->d_logits; pp.boxes = m->d_boxes; pp.orig_hw = m->d_orig_hw;
+    pp.records = dev_out ? dev_out : m->d_records;
+    pp.counts = dev_counts ? dev_counts : m->d_counts;
+    pp.B = B; pp.Q = m->arch.queries; pp.ncls = m->arch.ncls; pp.threshold = threshold;
+    RCCHK(timed_begin(m, CLS_OTHER, 0.0));
+    HIPCHK(opd_launch_postprocess(pp, m->stream));
+    RCCHK(timed_end(m));
+    MARK(8);
+    return OPD_OK;
+}
+
+// The records leave the device as ONE block, the d_records allocation as it lies: [records of max_batch frames | counts | feature rows]
+static size_t rec_bytes(const opd_detr* m) { return (size_t)m->cfg.max_batch * m->arch.queries * sizeof(opd_det); }   // = offset of the counts
+static size_t feat_off(const opd_detr* m) { return reinterpret_cast<const char*>(m->d_feat_all) - reinterpret_cast<const char*>(m->d_records); }
+static size_t feat_row(const opd_detr* m) { return (size_t)m->arch.queries * m->arch.d_model * 4; }   // a frame's feature rows
+// ... and a page-locked copy of it is taken apart into the caller's arrays here (fetch_records, opd_detr_wait)
+static void unpack_records(const opd_detr* m, const void* pinned, int B, opd_det* out, int32_t* counts, float* features = nullptr) {
+    const char* p = static_cast<const char*>(pinned);
+    memcpy(out, p, (size_t)B * m->arch.queries * sizeof(opd_det));
+    memcpy(counts, p + rec_bytes(m), (size_t)B * 4);
+    if (features) memcpy(features, p + feat_off(m), (size_t)B * feat_row(m));
+}
+
+// (`features` != null: the [B][Q][d_model] feature rows behind the counts travel in the same copy)
+static int fetch_records(opd_detr* m, opd_det* out, int32_t* counts, int mem_kind, float* features = nullptr) {
+    const int B = m->last_B;
+    if (!outputs_on_device(mem_kind)) {   // (device callers had the post-process kernel write into their buffers)
+        // one copy of [records of max_batch frames | counts (| features)] into page-locked memory (a copy into the caller's pageable arrays is
+        // staged by the runtime anyway, once per call), handed over after the wait
+        if (!m->sync_pinned) HIPCHK(hipHostMalloc(&m->sync_pinned, feat_off(m) + m->cfg.max_batch * feat_row(m), hipHostMallocDefault));
+        HIPCHK(hipMemcpyAsync(m->sync_pinned, m->d_records, features ? feat_off(m) + B * feat_row(m) : rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
+        unpack_records(m, m->sync_pinned, B, out, counts, features);
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (m->profiling) {
+        for (int i = 0; i < 8; ++i) {
+            float ms = 0.f;
+            // (mode 2: marks 0 .. 7 are nodes of the replayed graph, mark 8 is recorded eagerly behind the post-process launch: events of the
+            //  two kinds do not subtract meaningfully, so the last stage runs from the eager mark 9 behind the graph launch)
+            hipEvent_t from = (i == 7 && m->profiling == 2 && m->graph_marks) ? m->ev[9] : m->ev[i];
+            if (hipEventElapsedTime(&ms, from, m->ev[i + 1]) == hipSuccess) m->stage_ms[i] = ms;
+            else (void)hipGetLastError();   // (a mark that was never recorded: not this call's error)
+        }
+        if (m->profiling == 1) timed_collect(m);
+    }
+    return OPD_OK;
+}
+
+// The back half, on the outputs of the last forward (opd_detr_postprocess enters here): post-process, feature kernel, the sink's way of handing
+// the records over.  (h, w): the source's camera resolution (0: none); d_camera: its frames on the device at that resolution (FEAT_COLOR).
+static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera) {
+    const int B = m->last_B, Q = m->arch.queries;
+    const bool dev = outputs_on_device(s.mem_kind);
+    RCCHK(enqueue_postprocess(m, s.threshold, s.orig_hw, h ? h : m->last_H, h ? w : m->last_W, dev ? s.out : nullptr, dev ? s.counts : nullptr));
+    if (s.feature == FEAT_ROI)
+        HIPCHK(opd_launch_roi_features_records(m->d_x32, m->d_records, m->d_counts, m->d_orig_hw, s.label, m->d_feat_all, B, Q, m->last_fh, m->last_fw, m->stream));
+    if (s.feature == FEAT_COLOR) {   // the histogram kernels read the CAMERA-resolution frames under the boxes of the records the post-process left
+        ColorParams cp{};
+        cp.records = m->d_records; cp.counts = m->d_counts; cp.frames = d_camera; cp.acc = m->d_color_acc; cp.out = m->d_feat_all;
+        cp.Q = Q; cp.fh = h; cp.fw = w; cp.label = s.label; cp.n = B * Q;
+        HIPCHK(opd_launch_color_features(cp, std::min(64, (h + 15) / 16), m->stream));
+    }
+    if (s.wait == WAIT_NONE) return OPD_OK;
+    if (s.wait == WAIT_BLOCKING) return fetch_records(m, s.out, s.counts, s.mem_kind, s.features);   // records, counts and feature rows: one copy, one wait
+    opd_detr::AsyncHost& slot = m->async_host[s.ticket];
+    slot.out = nullptr;
+    if (!dev) {   // host outputs: pinned staging so that the copy stays asynchronous; delivered by opd_detr_wait
+        if (!slot.pinned) HIPCHK(hipHostMalloc(&slot.pinned, rec_bytes(m) + (size_t)m->cfg.max_batch * 4, hipHostMallocDefault));
+        HIPCHK(hipMemcpyAsync(slot.pinned, m->d_records, rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));   // (records | counts: one copy)
+        slot.out = s.out; slot.counts = s.counts; slot.B = B;
+    }
+    HIPCHK(hipEventRecord(m->ev_async[s.ticket], m->stream));
+    m->async_pending[s.ticket] = true;
+    ++m->async_next;
+    return OPD_OK;
+}
+
+// The front half: the source step and the forward
+static int forward_frames(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, const uint8_t** d_camera) {
+    const void* d_pixels = nullptr;
+    RCCHK(stage_frames(m, src, B, H, W, &d_pixels, d_camera));
+    return run_forward(m, d_pixels, src.pixel_format, B, H, W, valid_hw);
+}
+
+int detect_pipeline(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, const RecordSink& sink) {
+    const uint8_t* d_camera = nullptr;
+    RCCHK(forward_frames(m, src, B, H, W, valid_hw, &d_camera));
+    return deliver_records(m, sink, src.kind == SRC_PIXELS ? 0 : src.h, src.w, d_camera);
+}
+
+// The front half alone (opd_detr_forward*): the raw outputs go to host or device memory according to src.mem_kind
+static int forward_device(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, float* logits, float* boxes,
+                          float* enc_features) {
+    const uint8_t* d_camera = nullptr;
+    RCCHK(forward_frames(m, src, B, H, W, valid_hw, &d_camera));
+    const hipMemcpyKind kind = outputs_on_device(src.mem_kind) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t Md = (size_t)B * m->arch.queries;
+    if (logits) HIPCHK(hipMemcpyAsync(logits, m->d_logits, Md * m->arch.ncls * 4, kind, m->stream));
+    if (boxes) HIPCHK(hipMemcpyAsync(boxes, m->d_boxes, Md * 4 * 4, kind, m->stream));
+    if (enc_features)
+        HIPCHK(hipMemcpyAsync(enc_features, m->d_x32, (size_t)B * m->last_fh * m->last_fw * m->arch.d_model * 4, kind, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (m->profiling == 1) timed_collect(m);
+    return OPD_OK;
+}
+
+}  // namespace opd
+
+// =====================================================================================================================
+// C-ABI
+// =====================================================================================================================
+static void drop_streams(opd_detr* m) {
+    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
+    if (m->ev_join) (void)hipEventDestroy(m->ev_join);
+    if (m->stream2) (void)hipStreamDestroy(m->stream2);
+    if (m->stream) (void)hipStreamDestroy(m->stream);
+    m->ev_fork = m->ev_join = nullptr; m->stream2 = m->stream = nullptr;
+}
+
+// No C++ exception may cross the C-ABI: creation parses an untrusted file and allocates, so its body runs under a catch-all.
+template <typename F>
+static int guarded(const char* what, F&& body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return fail(OPD_ENOMEM, std::string(what) + ": out of host memory");
+    } catch (const std::out_of_range& e) {
+        return fail(OPD_ESCHEMA, std::string(what) + ": weight file lacks a tensor the model needs (" + e.what() + ")");
+    } catch (const std::exception& e) {
+        return fail(OPD_EINVAL, std::string(what) + ": " + e.what());
+    } catch (...) {
+        return fail(OPD_EINVAL, std::string(what) + ": unknown C++ exception");
+    }
+}
+// The forward-plan switches: defaults, overridden by environment variables (A/B switches for benchmarking and ablations)
+static Switches read_switches(int flags) {
+    Switches sw;
+    auto env = [](const char* name, int* v) { if (const char* e = getenv(name)) *v = atoi(e); };
+    env("OPD_DUAL_OVER_TAIL", &sw.dual_over_tail);
+    env("OPD_TAIL_REV", &sw.tail_rev);
+    env("OPD_TAIL3", &sw.tail3);
+    env("OPD_TAIL_RC", &sw.tail_rc);
+    sw.tail_rc = sw.tail_rc != 0;
+    env("OPD_WPREFETCH", &sw.wprefetch);
+    env("OPD_W8", &sw.w8);
+    if (sw.w8 < 0) sw.w8 = (flags & OPD_FLAG_MULTI_STREAM) ? 1 : 0;
+    env("OPD_SMALL_SPLITK", &sw.small_splitk);
+    env("OPD_SMALL_ENC", &sw.small_enc);
+    env("OPD_Y_STRIDE2", &sw.y_stride2);
+    env("OPD_TAIL3_SPLIT", &sw.tail3_split);
+    env("OPD_FUSE_PREP", &sw.fuse_prep);
+    env("OPD_POS_SHADOW", &sw.pos_shadow);
+    env("OPD_DEEP_FC2", &sw.deep_fc2);
+    env("OPD_WROUND", &sw.wround);
+    env("OPD_FUSED_DEC", &sw.fused_dec);
+    env("OPD_FUSED_ENC_FFN", &sw.fused_enc_ffn);
+    env("OPD_ENC_TAIL", &sw.enc_tail);
+    env("OPD_ENC_FRONT", &sw.enc_front);
+    env("OPD_HEADS2", &sw.heads2);
+    env("OPD_DBG_DEC_LAYERS", &sw.dbg_dec_layers);   // timing ablation (tools/dec_cost.sh): results are wrong
+    env("OPD_DBG_BTAIL", &sw.dbg_btail);             // timing ablations of the whole forward: BtailParams::dbg / ConvGemmParams::dbg
+    env("OPD_DBG_SKIP", &sw.dbg_skip);               // bit i: no kernel launches in segment i of stage_ms (stem, stages 1-4, encoder, decoder, post-process)
+    env("OPD_DBG_GEMM", &sw.dbg_gemm);               // of every fused tail / implicit-GEMM launch (results are wrong)
+    return sw;
+}
+
+// What creation and cloning share: the handle's streams, workspace and events (creation: its weights from `sd` too; a clone shares its source's)
+static int open_handle(std::unique_ptr<opd_detr> m, const StateDict* sd, opd_detr** out) {
+    auto cleanup = [&](int code) {
+        for (void* p : m->allocs) (void)hipFree(p);
+        drop_streams(m.get());
+        return code;
+    };
+    hipError_t he = hipSetDevice(m->device);
+    if (he == hipSuccess) he = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
+    // second branch of the forward (stage-3 frame split): a stream and two untimed events per handle
+    if (he == hipSuccess) he = hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking);
+    if (he == hipSuccess) he = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming);
+    if (he == hipSuccess) he = hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming);
+    if (he != hipSuccess) { drop_streams(m.get()); return fail(OPD_EHIP, std::string("device/stream setup failed: ") + hipGetErrorString(he)); }
+    int rc;
+    if (sd) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device) == hipSuccess && cus > 0) m->num_cus = cus;
+        m->weights = std::make_shared<WeightSet>();
+        m->weights->device = m->device;
+        if ((rc = build_weights(m.get(), *sd))) return cleanup(rc);
+    }
+    m->weights_sealed = true;
+    if ((rc = build_workspace(m.get()))) return cleanup(rc);
+    for (auto& e : m->ev)
+        if (hipEventCreate(&e) != hipSuccess) return cleanup(fail(OPD_EHIP, "hipEventCreate failed"));
+    *out = m.release();
+    ++g_handle_epoch;
+    return OPD_OK;
+}
+
+static int create_impl(const opd_config* cfg, const char* weights_path, int device_ordinal, opd_detr** out) {
+    if (!cfg || !weights_path || !out) return fail(OPD_EINVAL, "opd_detr_create: null argument");
+    if (cfg->struct_size != (int32_t)sizeof(opd_config)) return fail(OPD_EINVAL, "opd_config.struct_size mismatch");
+    if (cfg->max_batch < 1 || cfg->max_height < 32 || cfg->max_width < 32) return fail(OPD_EINVAL, "opd_config maxima must be >= 1 x 32 x 32");
+    StateDict sd;
+    std::string err;
+    int rc = load_safetensors(weights_path, &sd, &err);
+    if (rc) return fail(rc, err);
+    std::unique_ptr<opd_detr> m(new opd_detr());
+    rc = infer_arch(sd, &m->arch, &err);
+    if (rc) return fail(rc, err);
+    m->cfg = *cfg;
+    m->dtype = (cfg->flags & OPD_FLAG_BF16) ? OPD_DT_BF16 : OPD_DT_F16;
+    m->sw = read_switches(cfg->flags);
+    m->device = device_ordinal;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(OPD_EHIP, "no HIP device visible (this library has no CPU fallback)");
+    if (device_ordinal < 0 || device_ordinal >= ndev) return fail(OPD_EINVAL, "device_ordinal out of range");
+    return open_handle(std::move(m), &sd, out);
+}
+
+static int clone_impl(const opd_detr* src, opd_detr** out) {
+    if (!src || !out) return fail(OPD_EINVAL, "opd_detr_clone: null argument");
+    std::unique_ptr<opd_detr> m(new opd_detr());
+    static_cast<DetrWeights&>(*m) = *src;   // everything build_weights produced, whole
+    m->weights = src->weights;
+    m->arch = src->arch; m->cfg = src->cfg; m->device = src->device; m->dtype = src->dtype;
+    m->sw = src->sw; m->num_cus = src->num_cus;
+    return open_handle(std::move(m), nullptr, out);
+}
+
+extern "C" {
+
+const char* opd_version(void) { return "opd_hip 0.2 gfx950 (fp16 MFMA operands, fp32 accumulate; OPD_FLAG_BF16: bf16 operands)"; }
+
+int opd_detr_create(const opd_config* cfg, const char* weights_path, int device_ordinal, opd_detr** out) {
+    ApiScope api_scope;
+    if (out) *out = nullptr;
+    return guarded("opd_detr_create", [&] { return create_impl(cfg, weights_path, device_ordinal, out); });
+}
+int opd_detr_clone(const opd_detr* src, opd_detr** out) {
+    ApiScope api_scope;
+    if (out) *out = nullptr;
+    return guarded("opd_detr_clone", [&] { return clone_impl(src, out); });
+}
+void opd_detr_destroy(opd_detr* m) {
+    ApiScope api_scope;
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    if (m->stream) (void)hipStreamSynchronize(m->stream);
+    comm_detach_all(m);   // communicator lanes bound to this handle refuse work from here on (their own destroy still frees them)
+    for (void* p : m->allocs) (void)hipFree(p);
+    if (m->d_src) (void)hipFree(m->d_src);
+    for (auto& e : m->ev_async)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& a : m->async_host)
+        if (a.pinned) (void)hipHostFree(a.pinned);
+    if (m->sync_pinned) { (void)hipHostFree(m->sync_pinned); m->sync_pinned = nullptr; }
+    for (auto& e : m->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : m->event_pool) (void)hipEventDestroy(e);
+    for (auto& g : m->graphs)
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    drop_streams(m);
+    delete m;
+    ++g_handle_epoch;
+}
+
+int opd_detr_info(const opd_detr* m, opd_model_info* info) {
+    if (!m || !info) return fail(OPD_EINVAL, "opd_detr_info: null argument");
+    for (int i = 0; i < 4; ++i) info->depths[i] = m->arch.depths[i];
+    info->d_model = m->arch.d_model; info->heads = m->arch.heads; info->ffn_dim = m->arch.ffn;
+    info->encoder_layers = m->arch.enc_layers; info->decoder_layers = m->arch.dec_layers;
+    info->num_queries = m->arch.queries; info->num_classes_plus1 = m->arch.ncls;
+    info->max_batch = m->cfg.max_batch; info->max_height = m->cfg.max_height; info->max_width = m->cfg.max_width;
+    info->device_ordinal = m->device;
+    info->weight_bytes_device = m->weight_bytes; info->workspace_bytes_device = m->workspace_bytes;
+    return OPD_OK;
+}
+
+int opd_detr_forward(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W, float* logits,
+                     float* boxes, float* enc_features) {
+    ApiScope api_scope;
+    return opd_detr_forward_ragged(m, pixels, pixel_format, mem_kind, B, H, W, nullptr, logits, boxes, enc_features);
+}
+int opd_detr_forward_ragged(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W,
+                            const int32_t* valid_hw, float* logits, float* boxes, float* enc_features) {
+    ApiScope api_scope;
+    RCCHK(check_shape(m, pixels, pixel_format, mem_kind, B, H, W));
+    HIPCHK(hipSetDevice(m->device));
+    return forward_device(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, valid_hw, logits, boxes, enc_features);
+}
+int opd_detr_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, opd_det* out, int32_t* counts) {
+    ApiScope api_scope;
+    if (!m || !out || !counts) return fail(OPD_EINVAL, "opd_detr_postprocess: null argument");
+    if (m->last_B == 0) return fail(OPD_ESTATE, "opd_detr_postprocess called before any forward");
+    HIPCHK(hipSetDevice(m->device));
+    return deliver_records(m, {threshold, orig_hw, out, counts, OPD_MEM_HOST, WAIT_BLOCKING}, 0, 0, nullptr);
+}
+int opd_detr_resize_u8(opd_detr* m, const uint8_t* frames, int B, int h, int w, int out_h, int out_w, uint8_t* out) {
+    ApiScope api_scope;
+    if (!m) return fail(OPD_EINVAL, "null model handle");
+    if (!frames || !out) return fail(OPD_EINVAL, "opd_detr_resize_u8: null buffer");
+    uint8_t dummy = 0;
+    RCCHK(check_shape(m, &dummy, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, B, out_h, out_w));
+    HIPCHK(hipSetDevice(m->device));
+    RCCHK(enqueue_resize(m, frames, OPD_MEM_HOST, B, h, w, out_h, out_w));
+    HIPCHK(hipMemcpyAsync(out, m->d_u8, (size_t)B * out_h * out_w * 3, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return OPD_OK;
+}
+int opd_detr_forward_resized(opd_detr* m, const uint8_t* frames, int mem_kind, int B, int h, int w, int H, int W, float* logits,
+                             float* boxes, float* enc_features) {
+    ApiScope api_scope;
+    RCCHK(check_shape(m, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, B, H, W));
+    HIPCHK(hipSetDevice(m->device));
+    return forward_device(m, {SRC_BLOCK, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, h, w}, B, H, W, nullptr, logits, boxes, enc_features);
+}
+int opd_detr_detect(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W, float threshold,
+                    const int32_t* orig_hw, opd_det* out, int32_t* counts) {
+    ApiScope api_scope;
+    return opd_detr_detect_ragged(m, pixels, pixel_format, mem_kind, B, H, W, nullptr, threshold, orig_hw, out, counts);
+}
+int opd_detr_detect_ragged(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W,
+                           const int32_t* valid_hw, float threshold, const int32_t* orig_hw, opd_det* out, int32_t* counts) {
+    ApiScope api_scope;
+    RCCHK(check_shape(m, pixels, pixel_format, mem_kind, B, H, W));
+    if (!out || !counts) return fail(OPD_EINVAL, "opd_detr_detect: null output buffer");
+    RCCHK(check_device_outputs(mem_kind, out, counts, "opd_detr_detect"));
+    HIPCHK(hipSetDevice(m->device));
+    return detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, valid_hw, {threshold, orig_hw, out, counts, mem_kind, WAIT_BLOCKING});
+}
+int opd_detr_detect_async(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W, float threshold,
+                          const int32_t* orig_hw, opd_det* out, int32_t* counts, int* ticket) {
+    ApiScope api_scope;
+    RCCHK(check_shape(m, pixels, pixel_format, mem_kind, B, H, W));
+    if (!out || !counts || !ticket) return fail(OPD_EINVAL, "opd_detr_detect_async: null argument");
+    RCCHK(check_device_outputs(mem_kind, out, counts, "opd_detr_detect_async"));
+    if (m->profiling) return fail(OPD_ESTATE, "opd_detr_detect_async is not available in profiling mode");
+    HIPCHK(hipSetDevice(m->device));
+    const int t = (int)(m->async_next & 3u);
+    if (m->async_pending[t])
+        return fail(OPD_ESTATE, "opd_detr_detect_async: 4 submissions are outstanding on this handle; opd_detr_wait the oldest ticket first");
+    if (!m->ev_async[t]) HIPCHK(hipEventCreateWithFlags(&m->ev_async[t], hipEventDisableTiming));
+    RCCHK(detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, nullptr, {threshold, orig_hw, out, counts, mem_kind, WAIT_TICKET, t}));
+    *ticket = t;
+    return OPD_OK;
+}
+int opd_detr_wait(opd_detr* m, int ticket) {
+    ApiScope api_scope;
+    if (!m || ticket < 0 || ticket > 3 || !m->ev_async[ticket]) return fail(OPD_EINVAL, "opd_detr_wait: bad handle or ticket");
+    if (!m->async_pending[ticket]) return fail(OPD_ESTATE, "opd_detr_wait: this ticket is not outstanding (already waited for?)");
+    HIPCHK(hipSetDevice(m->device));
+    HIPCHK(hipEventSynchronize(m->ev_async[ticket]));
+    opd_detr::AsyncHost& slot = m->async_host[ticket];
+    if (slot.out) {
+        unpack_records(m, slot.pinned, slot.B, slot.out, slot.counts);
+        slot.out = nullptr;
+    }
+    m->async_pending[ticket] = false;
+    return OPD_OK;
+}
+int opd_detr_detect_resized(opd_detr* m, const uint8_t* frames, int mem_kind, int B, int h, int w, int H, int W, float threshold,
+                            opd_det* out, int32_t* counts) {
+    ApiScope api_scope;
+    RCCHK(check_shape(m, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, B, H, W));
+    if (!out || !counts) return fail(OPD_EINVAL, "opd_detr_detect_resized: null output buffer");
+    RCCHK(check_device_outputs(mem_kind, out, counts, "opd_detr_detect_resized"));
+    HIPCHK(hipSetDevice(m->device));
+    return detect_pipeline(m, {SRC_BLOCK, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, h, w}, B, H, W, nullptr, {threshold, nullptr, out, counts, mem_kind, WAIT_BLOCKING});
+}
+
+// The three frame-list entries: the argument checks they share, worded with the entry's own name
+static int check_frame_list(opd_detr* m, const uint8_t* const* frames, int mem_kind, int B, int H, int W, bool have_outputs, const std::string& who) {
+    RCCHK(check_shape(m, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, B, H, W));
+    for (int b = 0; b < B; ++b)
+        if (!frames[b]) return fail(OPD_EINVAL, who + ": null frame pointer");
+    if (!have_outputs) return fail(OPD_EINVAL, who + ": null output buffer");
+    return OPD_OK;
+}
+int opd_detr_detect_frames(opd_detr* m, const uint8_t* const* frames, int mem_kind, int B, int h, int w, int H, int W, float threshold,
+                           opd_det* out, int32_t* counts) {
+    ApiScope api_scope;
+    if (!m) return fail(OPD_EINVAL, "null model handle");
+    if (mem_kind != OPD_MEM_HOST && mem_kind != OPD_MEM_HOST_PIXELS_DEVICE_OUT) return fail(OPD_EINVAL, "opd_detr_detect_frames takes host frames");
+    RCCHK(check_frame_list(m, frames, mem_kind, B, H, W, out && counts, "opd_detr_detect_frames"));
+    RCCHK(check_device_outputs(mem_kind, out, counts, "opd_detr_detect_frames"));
+    HIPCHK(hipSetDevice(m->device));
+    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, h, w}, B, H, W, nullptr, {threshold, nullptr, out, counts, mem_kind, WAIT_BLOCKING});
+}
+
+int opd_detr_detect_frames_features(opd_detr* m, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold, int label,
+                                    opd_det* out, int32_t* counts, float* features) {
+    ApiScope api_scope;
+    RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && features, "opd_detr_detect_frames_features"));
+    if (m->arch.d_model != 256) return fail(OPD_EINVAL, "opd_detr_detect_frames_features: the pooling kernel is built for d_model = 256");
+    HIPCHK(hipSetDevice(m->device));
+    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr,
+                           {threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_ROI, label, features});
+}
+
+// The colour-histogram twin: same upload, same forward and post-process; the histogram kernels read the CAMERA-resolution frames this call
+// has just put on the device (d_src when it resizes, d_u8 when it does not) under the boxes of the records the post-process left there.
+int opd_detr_detect_frames_color(opd_detr* m, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold, int label,
+                                 opd_det* out, int32_t* counts, float* features) {
+    ApiScope api_scope;
+    RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && features, "opd_detr_detect_frames_color"));
+    if (m->arch.d_model != OPD_COLOR_DIM) return fail(OPD_EINVAL, "opd_detr_detect_frames_color: the feature area of the handle is sized for d_model = 256");
+    if (h < 1 || w < 1 || h > OPD_COLOR_MAX_EDGE || w > OPD_COLOR_MAX_EDGE)
+        return fail(OPD_EINVAL, "opd_detr_detect_frames_color: frames of " + std::to_string(h) + " x " + std::to_string(w) +
+                                    " are outside the 4096 x 4096 the exact integer sums are sized for");
+    HIPCHK(hipSetDevice(m->device));
+    if (!m->d_color_acc) RCCHK(dalloc(m, &m->d_color_acc, (size_t)m->cfg.max_batch * m->arch.queries * OPD_COLOR_ACC_WORDS, false));
+    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr,
+                           {threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_COLOR, label, features});
+}
+
+int opd_host_alloc(size_t bytes, void** out) {
+    ApiScope api_scope;
+    if (!out || bytes == 0) return fail(OPD_EINVAL, "opd_host_alloc: null output or zero size");
+    *out = nullptr;
+    HIPCHK(hipHostMalloc(out, bytes, hipHostMallocDefault));
+    return OPD_OK;
+}
+void opd_host_free(void* p) {
+    ApiScope api_scope;
+    if (p) (void)hipHostFree(p);
+}
+
+int opd_similarity_matrix(int device_ordinal, const float* feats1, const float* boxes1, const uint8_t* has1, int n1,
+                          const float* feats2, const float* boxes2, const uint8_t* has2, int n2, int D, double appearance_weight,
+                          double motion_weight, int as_distance, float* out) {
+    ApiScope api_scope;
+    if (n1 < 0 || n2 < 0 || D < 1) return fail(OPD_EINVAL, "opd_similarity_matrix: bad sizes");
+    if (n1 == 0 || n2 == 0) return OPD_OK;
+    if (!boxes1 || !boxes2 || !out) return fail(OPD_EINVAL, "opd_similarity_matrix: null boxes / output");
+    if (fabs(appearance_weight + motion_weight - 1.0) > 1e-6)
+        return fail(OPD_EINVAL, "appearance_weight + motion_weight must equal 1.0");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(OPD_EHIP, "no HIP device visible (this library has no CPU fallback)");
+    HIPCHK(hipSetDevice(device_ordinal));
+    struct Tmp {
+        std::vector<void*> p;
+        ~Tmp() { for (void* q : p) (void)hipFree(q); }
+    } tmp;
+    auto up = [&](const void* h, size_t bytes, void** d) -> int {
+        *d = nullptr;
+        if (!h) return OPD_OK;
+        if (hipMalloc(d, bytes) != hipSuccess) return fail(OPD_ENOMEM, "opd_similarity_matrix: device allocation failed");
+        tmp.p.push_back(*d);
+        HIPCHK(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
+        return OPD_OK;
+    };
+    void *df1, *df2, *db1, *db2, *dh1, *dh2, *dout = nullptr;
+    RCCHK(up(feats1, (size_t)n1 * D * 4, &df1)); RCCHK(up(feats2, (size_t)n2 * D * 4, &df2));
+    RCCHK(up(boxes1, (size_t)n1 * 16, &db1)); RCCHK(up(boxes2, (size_t)n2 * 16, &db2));
+    RCCHK(up(has1, (size_t)n1, &dh1)); RCCHK(up(has2, (size_t)n2, &dh2));
+    if (hipMalloc(&dout, (size_t)n1 * n2 * 4) != hipSuccess) return fail(OPD_ENOMEM, "opd_similarity_matrix: device allocation failed");
+    tmp.p.push_back(dout);
+    HIPCHK(opd_launch_similarity_matrix((const float*)df1, (const float*)db1, (const uint8_t*)dh1, n1, (const float*)df2, (const float*)db2,
+                                        (const uint8_t*)dh2, n2, D, appearance_weight, motion_weight, as_distance,
+                                        (float*)dout, nullptr));
+    HIPCHK(hipMemcpy(out, dout, (size_t)n1 * n2 * 4, hipMemcpyDeviceToHost));
+    return OPD_OK;
+}
+
+int opd_detr_roi_features(opd_detr* m, int frame, const float* boxes_xywh, int n, int orig_h, int orig_w, float* features) {
+    ApiScope api_scope;
+    if (!m || (n > 0 && (!boxes_xywh || !features))) return fail(OPD_EINVAL, "opd_detr_roi_features: null argument");
+    if (m->last_B == 0) return fail(OPD_ESTATE, "opd_detr_roi_features called before any forward");
+    if (frame < 0 || frame >= m->last_B || n < 0 || n > 128 || orig_h <= 0 || orig_w <= 0)
+        return fail(OPD_EINVAL, "opd_detr_roi_features: frame / n / image size out of range");
+    if (n == 0) return OPD_OK;
+    HIPCHK(hipSetDevice(m->device));
+    const int h = m->last_fh, w = m->last_fw;
+    std::vector<int32_t> rois(n * 4);
+    for (int i = 0; i < n; ++i) {  // same int-truncation and clamping as the reference (feature_extractor.py:68-78)
+        const double x = boxes_xywh[4 * i], y = boxes_xywh[4 * i + 1], bw = boxes_xywh[4 * i + 2], bh = boxes_xywh[4 * i + 3];
+        int x0 = (int)((x / orig_w) * w), y0 = (int)((y / orig_h) * h);
+        int x1 = (int)(((x + bw) / orig_w) * w), y1 = (int)(((y + bh) / orig_h) * h);
+        x0 = std::max(0, std::min(x0, w - 1)); y0 = std::max(0, std::min(y0, h - 1));
+        x1 = std::max(x0 + 1, std::min(x1, w)); y1 = std::max(y0 + 1, std::min(y1, h));
+        rois[4 * i] = x0; rois[4 * i + 1] = y0; rois[4 * i + 2] = x1; rois[4 * i + 3] = y1;
+    }
+    HIPCHK(hipMemcpyAsync(m->d_rois, rois.data(), rois.size() * 4, hipMemcpyHostToDevice, m->stream));
+    const float* enc = m->d_x32 + (size_t)frame * h * w * m->arch.d_model;
+    HIPCHK(opd_launch_roi_features(enc, m->d_rois, m->d_roi_out, n, h, w, m->stream));
+    HIPCHK(hipMemcpyAsync(features, m->d_roi_out, (size_t)n * m->arch.d_model * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return OPD_OK;
+}
+
+int opd_detr_attention_map(opd_detr* m, int frame, int layer, const int32_t* queries, int n_queries, float* out, int out_capacity) {
+    ApiScope api_scope;
+    if (!m || !out) return fail(OPD_EINVAL, "opd_detr_attention_map: null argument");
+    if (m->last_B == 0) return fail(OPD_ESTATE, "opd_detr_attention_map called before any forward");
+    const int L = m->arch.dec_layers, Q = m->arch.queries, D = m->arch.d_model;
+    if (layer < 0) layer += L;
+    if (frame < 0 || frame >= m->last_B || layer < 0 || layer >= L || n_queries < 0 || n_queries > Q || (n_queries > 0 && !queries))
+        return fail(OPD_EINVAL, "opd_detr_attention_map: frame / layer / queries out of range");
+    std::vector<int32_t> sel;
+    if (n_queries == 0) { sel.resize(Q); for (int i = 0; i < Q; ++i) sel[i] = i; }
+    else {
+        sel.assign(queries, queries + n_queries);
+        for (int q : sel) if (q < 0 || q >= Q) return fail(OPD_EINVAL, "opd_detr_attention_map: query index out of range");
+    }
+    HIPCHK(hipSetDevice(m->device));
+    const int hw = m->last_fh * m->last_fw, NKV = L * 2 * D, Md = m->last_B * Q;
+    if (out_capacity < hw)
+        return fail(OPD_EINVAL, "opd_detr_attention_map: the last forward's map has " + std::to_string(m->last_fh) + " x " + std::to_string(m->last_fw) +
+                                    " positions, the output buffer holds " + std::to_string(out_capacity));
+    HIPCHK(hipMemcpyAsync(m->d_amap_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, m->stream));
+    const f16_t* q = m->d_qd16 + (size_t)layer * m->cfg.max_batch * Q * D + (size_t)frame * Q * D;
+    const f16_t* k = m->d_memkv16 + (size_t)frame * hw * NKV + (size_t)layer * 2 * D;
+    const float scale = 1.0f / sqrtf((float)(D / m->arch.heads));
+    HIPCHK(opd_launch_attention_map(q, D, k, NKV, m->d_amap_sel, (int)sel.size(), m->arch.heads, hw, scale,
+                                    m->last_ragged ? m->d_key_valid + 2 * frame : nullptr, m->last_fw, m->d_amap_stat, m->d_amap, m->stream, m->dtype));
+    HIPCHK(hipMemcpyAsync(out, m->d_amap, (size_t)hw * 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return OPD_OK;
+}
+
+int opd_detr_set_profiling(opd_detr* m, int enabled) {
+    if (!m) return fail(OPD_EINVAL, "null model handle");
+    ApiScope api_scope;
+    const int mode = enabled == 2 ? 2 : (enabled ? 1 : 0);
+    if (mode != m->profiling) {   // the stage marks of mode 2 are nodes of the captured graph: graphs of another mode do not carry them
+        HIPCHK(hipSetDevice(m->device));
+        HIPCHK(hipStreamSynchronize(m->stream));
+        for (auto& g : m->graphs)
+            if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        m->graphs.clear();
+    }
+    m->profiling = mode;
+    return OPD_OK;
+}
+
+int opd_detr_stage_times(const opd_detr* m, float* ms8) {
+    ApiScope api_scope;
+    if (!m || !ms8) return fail(OPD_EINVAL, "opd_detr_stage_times: null argument");
+    for (int i = 0; i < 8; ++i) ms8[i] = m->stage_ms[i];
+    return OPD_OK;
+}
+
+int opd_detr_kernel_table(const opd_detr* m, opd_kernel_stat* out, int capacity, int* count) {
+    ApiScope api_scope;
+    if (!m || !count || capacity < 0 || (capacity > 0 && !out)) return fail(OPD_EINVAL, "opd_detr_kernel_table: bad argument");
+    *count = (int)m->ktable.size();
+    for (int i = 0; i < capacity && i < (int)m->ktable.size(); ++i) {
+        const auto& r = m->ktable[i];
+        memset(&out[i], 0, sizeof out[i]);
+        snprintf(out[i].name, sizeof out[i].name, "%s", r.name.c_str());
+        out[i].launches = r.launches; out[i].ms = r.ms; out[i].flops = r.flops;
+    }
+    return OPD_OK;
+}
+
+int opd_detr_kernel_times(const opd_detr* m, float* ms4, int32_t* launches4, double* flops4) {
+    ApiScope api_scope;
+    if (!m || !ms4 || !launches4 || !flops4) return fail(OPD_EINVAL, "opd_detr_kernel_times: null argument");
+    for (int i = 0; i < 4; ++i) { ms4[i] = m->class_ms[i]; launches4[i] = m->class_launches[i]; flops4[i] = m->class_flops[i]; }
+    return OPD_OK;
+}
+
+}  // extern "C"

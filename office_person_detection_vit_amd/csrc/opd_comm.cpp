@@ -268,13 +268,10 @@ int opd_comm_detect(opd_comm* c, int slot0, const void* pixels, int pixel_format
     if (!s || slot0 < 0 || slot0 + B > s->slots) return fail(OPD_EINVAL, "opd_comm_detect: frames do not fit the slots of opd_comm_begin");
     if (m->profiling) return fail(OPD_ESTATE, "opd_comm_detect is not available in profiling mode");
     HIPCHK(hipSetDevice(m->device));
-    const void* d_pixels = nullptr;
-    RCCHK(stage_pixels(m, pixels, pixel_format, mem_kind, B, H, W, &d_pixels));
-    RCCHK(run_forward(m, d_pixels, pixel_format, B, H, W, nullptr));
     const size_t Q = (size_t)m->arch.queries;
     opd_det* recs = reinterpret_cast<opd_det*>(s->d_send) + (size_t)slot0 * Q;
     int32_t* counts = s->d_send + (size_t)s->slots * Q * 8 + slot0;
-    return enqueue_postprocess(m, threshold, orig_hw, recs, counts);
+    return detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, nullptr, {threshold, orig_hw, recs, counts, OPD_MEM_DEVICE, WAIT_NONE});   // (into the lane's send buffer; the wait is opd_comm_wait's)
 }
 
 int opd_comm_buffers(opd_comm* c, int slot0, void** records, void** counts) {

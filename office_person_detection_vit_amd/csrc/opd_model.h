@@ -1,6 +1,7 @@
 // opd_model.h — PRIVATE header of libopd_hip: the device model (weights, workspace, per-resolution plans, graph cache) behind the opaque
-// `opd_detr` handle of include/opd_detr.h.  Included by opd_model.cpp (the C-ABI), opd_decoder.cpp and opd_test_api.cpp (the test hooks
-// of libopd_hip_test.so, which reach into a handle to flip its fusion switches); never installed, never seen by a caller.
+// `opd_detr` handle of include/opd_detr.h.  Included by opd_model.cpp (weights, workspace, plans, the forward), opd_api.cpp (the C-ABI and the
+// detect pipeline behind it), opd_comm.cpp and opd_test_api.cpp (the test hooks of libopd_hip_test.so, which reach into a handle to flip its
+// fusion switches); never installed, never seen by a caller.
 #pragma once
 #include <math.h>
 #include <stdlib.h>
@@ -35,7 +36,6 @@
 namespace opd {
 
 // (g_err / fail: opd_host.cpp)
-
 
 struct Conv {
     f16_t* w = nullptr;
@@ -185,21 +185,10 @@ struct WeightSet {
     }
 };
 
-struct opd_detr {
-    Arch arch;
-    opd_config cfg{};
-    Switches sw;                            // forward-plan switches (copied by opd_detr_clone: a clone plans like its source)
-    int dtype = 0;                          // OPD_DT_F16 / OPD_DT_BF16 (cfg.flags & OPD_FLAG_BF16): the 16-bit operand type of every activation buffer and GEMM weight
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;   // second branch of the forward (stage-3 frame split, see enqueue_forward); joins the capture of `stream`
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    std::vector<void*> allocs;              // this handle's own buffers: workspace, per-resolution plans
-    std::vector<RedZoned> zoned;            // poison mode only: the same buffers with their red zones
-    std::shared_ptr<WeightSet> weights;     // the model's weights (shared with clones)
-    bool weights_sealed = false;            // set once the weights are built: later "weight" allocations (plans) are the handle's own
-    int64_t weight_bytes = 0, workspace_bytes = 0;
-
+// Everything build_weights fills: device pointers into the shared WeightSet and the host copies the plans are folded from.  opd_detr_clone
+// copies this struct with ONE assignment, so a new product of build_weights goes HERE and nowhere else.
+struct DetrWeights {
+    int64_t weight_bytes = 0;
     Conv stem;
     std::vector<Block> blocks;
     std::vector<int> stage_first;  // index of first block of each stage
@@ -218,6 +207,22 @@ struct opd_detr {
     // host copies needed to build plans for new resolutions
     std::vector<std::vector<float>> h_enc_cat_w, h_enc_cat_b;  // per enc layer: [768*256] ([Wq;Wk;0]), [768]
     std::vector<float> h_kv_cat_w, h_kv_cat_b;                 // [L*512*256] ([Wk;0] per layer), [L*512]
+};
+
+struct opd_detr : DetrWeights {
+    Arch arch;
+    opd_config cfg{};
+    Switches sw;                            // forward-plan switches (copied by opd_detr_clone: a clone plans like its source)
+    int dtype = 0;                          // OPD_DT_F16 / OPD_DT_BF16 (cfg.flags & OPD_FLAG_BF16): the 16-bit operand type of every activation buffer and GEMM weight
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;   // second branch of the forward (stage-3 frame split, see enqueue_forward); joins the capture of `stream`
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    std::vector<void*> allocs;              // this handle's own buffers: workspace, per-resolution plans
+    std::vector<RedZoned> zoned;            // poison mode only: the same buffers with their red zones
+    std::shared_ptr<WeightSet> weights;     // the model's weights (shared with clones)
+    bool weights_sealed = false;            // set once the weights are built: later "weight" allocations (plans) are the handle's own
+    int64_t workspace_bytes = 0;
 
     // workspace
     uint8_t* d_u8 = nullptr;
@@ -326,12 +331,44 @@ inline int dalloc(opd_detr* m, T** p, size_t count, bool weight) {
 }
 
 void comm_detach_all(opd_detr* m);   // opd_comm.cpp: called by opd_detr_destroy
-int fill_qc0(opd_detr* m);   // opd_model.cpp
-// forward / post-process building blocks shared with opd_comm.cpp (all enqueue on m->stream; none synchronises unless it must)
+// opd_model.cpp, for opd_api.cpp: what a handle is made of, the forward through the graph cache, the per-launch timing of profiling mode 1
+int fill_qc0(opd_detr* m);
+int build_weights(opd_detr* m, const StateDict& sd);
+int build_workspace(opd_detr* m);
 int run_forward(opd_detr* m, const void* d_pixels, int pixel_format, int B, int H, int W, const int32_t* valid_hw = nullptr);
+enum { CLS_CONV = 0, CLS_GEMM = 1, CLS_ATTN = 2, CLS_OTHER = 3 };
+int timed_begin(opd_detr* m, int cls, double flops);
+int timed_end(opd_detr* m);
+void timed_collect(opd_detr* m);
+#define MARK(i)                                                   \
+    do {                                                          \
+        if (m->profiling) HIPCHK(hipEventRecord(m->ev[i], m->stream)); \
+        opd_dbg_skip_launch = (m->sw.dbg_skip >> (i)) & 1;           \
+    } while (0)
+
+// The detect pipeline (opd_api.cpp): frame source -> device pixels -> forward -> post-process -> feature kernel -> record sink, all enqueued on
+// m->stream.  Every detect entry point, opd_comm_detect included, is its own argument checks plus ONE call of detect_pipeline.
+enum { SRC_PIXELS, SRC_BLOCK, SRC_LIST };
+struct FrameSource {
+    int kind;
+    const void* frames;           // SRC_PIXELS: pixels of `pixel_format` at model resolution.  SRC_BLOCK: ONE block of camera frames [B][h][w][3], always resized.
+                                  // SRC_LIST: const uint8_t* const*, one HOST pointer per camera frame (resized when h x w is not the model size, else uploaded as is)
+    int pixel_format, mem_kind;   // (where the frames lie)
+    int h, w;                     // camera resolution, to which boxes are scaled (SRC_PIXELS: unused)
+};
+enum { WAIT_BLOCKING, WAIT_TICKET, WAIT_NONE };   // fetch the records and wait / hand them to async slot `ticket` (opd_detr_wait) / leave them on the stream
+enum { FEAT_NONE, FEAT_ROI, FEAT_COLOR };         // between post-process and fetch: nothing / ROI pooling on the records / their colour histograms
+struct RecordSink {
+    float threshold;
+    const int32_t* orig_hw;       // [B][2] frame sizes of the caller; null: the source's camera resolution, without one the model resolution
+    opd_det* out; int32_t* counts;
+    int mem_kind;                 // where out / counts lie: device ones are written by the post-process kernel itself, host ones filled from the library's
+    int wait, ticket;
+    int feature, label;           // FEAT_*: feature rows of the records labelled `label` -> `features` (host; WAIT_BLOCKING)
+    float* features;
+};
 int check_shape(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W);
-int stage_pixels(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W, const void** d_pixels);
-int enqueue_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, opd_det* dev_out = nullptr, int32_t* dev_counts = nullptr);
+int detect_pipeline(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, const RecordSink& sink);
 
 // Stream capture and other threads: the Python shim drives several handles from worker threads (HipDetrDetector(streams=N)).
 // ROCm invalidates a capture in progress when ANOTHER thread allocates or frees memory, pins host memory or runs its
