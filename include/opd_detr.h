@@ -368,6 +368,36 @@ OPD_API int opd_reid_info(const opd_reid* r, opd_reid_model_info* info);
 OPD_API int opd_reid_extract(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, int n_frames, int mem_kind,
                              const float* boxes_xywh, const int32_t* box_frame, int n_boxes, float* out);
 
+/* ---- Sparse optical flow: pyramidal Lucas-Kanade between consecutive frames (third handle type: two gray pyramids, own stream) --------
+ * Replaces the per-frame work of `OpticalFlowTracker.track` (src/tracking/lightweight_tracker.py:141-202), which the reference's hybrid
+ * tracker runs on every frame its detector skips: cv2.cvtColor(BGR2GRAY) and cv2.calcOpticalFlowPyrLK(prev_gray, gray, points, winSize,
+ * maxLevel, criteria).  The arithmetic is OpenCV's (gray weights, 5 x 5 pyramid filter, Scharr derivatives, the same range, eigenvalue
+ * and stopping tests) with the window interpolation and sums in float32 where OpenCV uses 14-bit fixed point.  Nothing
+ * here is compared against cv2: the kernels are pinned to a float64 restatement of this arithmetic and to analytically known
+ * displacements. */
+typedef struct opd_flow opd_flow; /* opaque flow handle */
+
+typedef struct opd_flow_config {
+    int max_h, max_w;        /* buffers are sized for frames up to max_h x max_w pixels (each up to 8192) */
+    int max_points;          /* ... and up to this many points per call */
+    int win;                 /* window edge, odd, 3 .. 21 (0 = 21: winSize (21, 21)) */
+    int max_level;           /* pyramid levels above level 0, up to 7 (0 = 3; a level no larger than the window ends the pyramid) */
+    int max_iter;            /* iterations per level (0 = 30) */
+    float epsilon;           /* stop when the step is at most this long (0 = 0.01; negative = never by this test) */
+    float min_eig_threshold; /* a point is lost when the smaller eigenvalue of its gradient matrix / win^2 is below this (0 = 1e-4) */
+} opd_flow_config;
+
+OPD_API int opd_flow_create(const opd_flow_config* cfg, int device_ordinal, opd_flow** out);
+OPD_API void opd_flow_destroy(opd_flow* f);
+/* The frame points will be tracked FROM (`prev_gray`): [h][w][3] uint8 BGR, host memory (OPD_MEM_HOST) or a device pointer read in
+ * place (OPD_MEM_DEVICE), h <= max_h, w <= max_w.  Any earlier reference is dropped; the size may change here. */
+OPD_API int opd_flow_set_reference(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w);
+/* Where the `n` points pts_xy [n][2] (x, y; host float32) of the reference frame lie in frame `bgr` (same size as the reference):
+ * next_xy [n][2] and status [n] (1 = found, 0 = lost: outside the frame by more than the window, or no texture), both host memory.
+ * Afterwards `bgr` is the reference (also when n = 0).  OPD_ESTATE before a reference was set.  Synchronous: one wait.  A device frame must be
+ * complete before the call: the handle's stream is not ordered after the stream that wrote it. */
+OPD_API int opd_flow_track(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w, const float* pts_xy, int n, float* next_xy,
+                           uint8_t* status);
 
 /* Thread-local description of the last error returned on this thread ("" if none). */
 OPD_API const char* opd_last_error(void);

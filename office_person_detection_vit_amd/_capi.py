@@ -60,6 +60,11 @@ class OpdReidModelInfo(C.Structure):   # opd_reid_model_info
                 ("model", C.c_int32), ("weight_bytes_device", C.c_int64), ("workspace_bytes_device", C.c_int64)]
 
 
+class OpdFlowConfig(C.Structure):   # opd_flow_config (zeros = the defaults of cv2.calcOpticalFlowPyrLK as the reference calls it)
+    _fields_ = [("max_h", C.c_int), ("max_w", C.c_int), ("max_points", C.c_int), ("win", C.c_int), ("max_level", C.c_int),
+                ("max_iter", C.c_int), ("epsilon", C.c_float), ("min_eig_threshold", C.c_float)]
+
+
 # name -> (restype, argtypes): every symbol include/opd_detr.h declares
 API = {
     "opd_detr_create": (C.c_int, [C.POINTER(OpdConfig), C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
@@ -115,6 +120,10 @@ API = {
     "opd_reid_info": (C.c_int, [C.c_void_p, C.POINTER(OpdReidModelInfo)]),
     "opd_reid_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_void_p]),
+    "opd_flow_create": (C.c_int, [C.POINTER(OpdFlowConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "opd_flow_destroy": (None, [C.c_void_p]),
+    "opd_flow_set_reference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "opd_flow_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "opd_last_error": (C.c_char_p, []),
     "opd_version": (C.c_char_p, []),
 }
@@ -206,6 +215,8 @@ TEST_API = {
     "opd_test_osnet_head": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3),
     "opd_test_reid_kernel_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                              C.POINTER(OpdKernelStat), C.c_int, C.POINTER(C.c_int)]),
+    # optical-flow hook (csrc/opd_flow_test_api.cpp)
+    "opd_flow_test_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,191 @@
+// opd_flow.cpp — the optical-flow handle of include/opd_detr.h (opd_flow_*): two gray pyramids on the device that swap roles after every
+// track call (`prev_gray = gray`), a stream, and one page-locked staging buffer.  A call stages the points (and a host frame) in it,
+// enqueues the uploads, gray + pyramid + the one-wave-per-point LK launch of kernels_flow.hip and the download, and waits once.
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+
+#include "opd_flow.h"
+#include "opd_model.h"
+
+using namespace opd;
+
+namespace {
+
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+bool device_accessible(const void* p) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged;
+}
+
+// the effective top level: the largest l <= max_level with every level 1 .. l wider and taller than the window
+int plan_levels(int h, int w, int win, int max_level, int* lh, int* lw, int* lp) {
+    lh[0] = h; lw[0] = w; lp[0] = flow_pitch(w);
+    int top = 0;
+    for (int l = 1; l <= max_level; ++l) {
+        const int nh = (lh[l - 1] + 1) / 2, nw = (lw[l - 1] + 1) / 2;
+        if (nh <= win || nw <= win) break;
+        lh[l] = nh; lw[l] = nw; lp[l] = flow_pitch(nw);
+        top = l;
+    }
+    return top;
+}
+
+int check_frame(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w) {
+    const std::string me(who);
+    if (!f) return fail(OPD_EINVAL, me + ": null handle");
+    if (!bgr) return fail(OPD_EINVAL, me + ": null frame pointer");
+    if (mem_kind != OPD_MEM_HOST && mem_kind != OPD_MEM_DEVICE) return fail(OPD_EINVAL, me + ": mem_kind must be OPD_MEM_HOST or OPD_MEM_DEVICE");
+    if (h < 1 || w < 1 || h > f->cfg.max_h || w > f->cfg.max_w)
+        return fail(OPD_EINVAL, me + ": frame of " + std::to_string(h) + " x " + std::to_string(w) + " pixels, the handle was created for up to " +
+                                    std::to_string(f->cfg.max_h) + " x " + std::to_string(f->cfg.max_w));
+    if (mem_kind == OPD_MEM_DEVICE) {
+        HIPCHK(hipSetDevice(f->device));
+        if (!device_accessible(bgr)) return fail(OPD_EINVAL, me + ": OPD_MEM_DEVICE, but the frame is not device-accessible memory");
+    }
+    return OPD_OK;
+}
+
+// gray + pyramid of `bgr` into pyr[which], enqueued on the handle's stream.  The `pts_bytes` of points the caller has put at the head of the
+// staging image and a host frame (behind the points region) travel as two copies of exactly their bytes on the same stream.
+int enqueue_pyramid(opd_flow* f, int which, const uint8_t* bgr, int mem_kind, int h, int w, size_t pts_bytes) {
+    const uint8_t* d_bgr = bgr;
+    if (pts_bytes) HIPCHK(hipMemcpyAsync(f->d_io, f->h_pin, pts_bytes, hipMemcpyHostToDevice, f->stream));
+    if (mem_kind == OPD_MEM_HOST) {
+        const size_t bytes = (size_t)h * w * 3;
+        memcpy(f->h_pin + f->frame_off, bgr, bytes);
+        d_bgr = f->d_io + f->frame_off;
+        HIPCHK(hipMemcpyAsync(f->d_io + f->frame_off, f->h_pin + f->frame_off, bytes, hipMemcpyHostToDevice, f->stream));
+    }
+    const FlowPyramid& p = f->pyr[which];
+    HIPCHK(opd_launch_flow_gray(d_bgr, p.base + p.off[0], h, w, f->lp[0], f->stream));
+    for (int l = 1; l <= f->top; ++l)
+        HIPCHK(opd_launch_flow_pyrdown(p.base + p.off[l - 1], f->lh[l - 1], f->lw[l - 1], f->lp[l - 1], p.base + p.off[l], f->lp[l], f->stream));
+    return OPD_OK;
+}
+
+}  // namespace
+
+extern "C" int opd_flow_create(const opd_flow_config* cfg, int device_ordinal, opd_flow** out) {
+    ApiScope api_scope;
+    if (!cfg || !out) return fail(OPD_EINVAL, "opd_flow_create: null argument");
+    *out = nullptr;
+    opd_flow_config c = *cfg;
+    if (c.win == 0) c.win = 21;
+    if (c.max_level == 0) c.max_level = 3;
+    if (c.max_iter == 0) c.max_iter = 30;
+    if (c.epsilon == 0.f) c.epsilon = 0.01f;
+    if (c.min_eig_threshold == 0.f) c.min_eig_threshold = 1e-4f;
+    if (c.max_h < 1 || c.max_w < 1 || c.max_h > 8192 || c.max_w > 8192) return fail(OPD_EINVAL, "opd_flow_create: max_h and max_w must lie in 1 .. 8192");
+    if (c.max_points < 1 || c.max_points > (1 << 20)) return fail(OPD_EINVAL, "opd_flow_create: max_points must lie in 1 .. 1048576");
+    if (c.win < 3 || c.win > OPD_FLOW_MAX_WIN || c.win % 2 == 0)
+        return fail(OPD_EINVAL, "opd_flow_create: win = " + std::to_string(c.win) + ", the window edge must be odd and lie in 3 .. 21");
+    if (c.max_level < 0 || c.max_level >= OPD_FLOW_MAX_LEVELS) return fail(OPD_EINVAL, "opd_flow_create: max_level must lie in 0 .. 7");
+    if (c.max_iter < 1 || c.max_iter > 1000) return fail(OPD_EINVAL, "opd_flow_create: max_iter must lie in 1 .. 1000");
+    if (!(c.min_eig_threshold > 0.f)) return fail(OPD_EINVAL, "opd_flow_create: min_eig_threshold must be positive");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(OPD_EHIP, "no HIP device visible (this library has no CPU fallback)");
+    if (device_ordinal < 0 || device_ordinal >= ndev) return fail(OPD_EINVAL, "opd_flow_create: no device " + std::to_string(device_ordinal));
+    HIPCHK(hipSetDevice(device_ordinal));
+    opd_flow* f = new opd_flow();
+    f->cfg = c;
+    f->device = device_ordinal;
+    // the largest pyramid: level sizes fall with the frame size, so offsets planned for max_h x max_w hold every smaller frame
+    int lh[OPD_FLOW_MAX_LEVELS], lw[OPD_FLOW_MAX_LEVELS], lp[OPD_FLOW_MAX_LEVELS];
+    size_t bytes = 0, off[OPD_FLOW_MAX_LEVELS] = {};
+    lh[0] = c.max_h; lw[0] = c.max_w;
+    for (int l = 0; l <= c.max_level; ++l) {
+        if (l) { lh[l] = (lh[l - 1] + 1) / 2; lw[l] = (lw[l - 1] + 1) / 2; }
+        lp[l] = flow_pitch(lw[l]);
+        off[l] = bytes;
+        bytes += align_up((size_t)lp[l] * lh[l], 256);
+    }
+    f->pts_bytes = align_up((size_t)c.max_points * 8, 256);
+    f->frame_off = f->pts_bytes;
+    f->out_off = f->frame_off + align_up((size_t)c.max_h * c.max_w * 3, 256);
+    f->io_bytes = f->out_off + align_up((size_t)c.max_points * 9, 256);
+    int rc = OPD_OK;
+    auto hip = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && rc == OPD_OK) { (void)hipGetLastError(); rc = fail(OPD_ENOMEM, std::string("opd_flow_create: ") + what + " failed: " + hipGetErrorString(e)); }
+    };
+    hip(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking), "stream creation");
+    for (int k = 0; k < 2 && rc == OPD_OK; ++k) {
+        hip(hipMalloc((void**)&f->pyr[k].base, bytes), "pyramid allocation");
+        memcpy(f->pyr[k].off, off, sizeof off);
+    }
+    if (rc == OPD_OK) hip(hipMalloc((void**)&f->d_io, f->io_bytes), "staging allocation");
+    if (rc == OPD_OK) hip(hipHostMalloc((void**)&f->h_pin, f->io_bytes, hipHostMallocDefault), "page-locked allocation");
+    if (rc != OPD_OK) { opd_flow_destroy(f); return rc; }
+    *out = f;
+    return OPD_OK;
+}
+
+extern "C" void opd_flow_destroy(opd_flow* f) {
+    if (!f) return;
+    ApiScope api_scope;
+    (void)hipSetDevice(f->device);
+    if (f->stream) { (void)hipStreamSynchronize(f->stream); (void)hipStreamDestroy(f->stream); }
+    for (int k = 0; k < 2; ++k) if (f->pyr[k].base) (void)hipFree(f->pyr[k].base);
+    if (f->d_io) (void)hipFree(f->d_io);
+    if (f->h_pin) (void)hipHostFree(f->h_pin);
+    delete f;
+}
+
+extern "C" int opd_flow_set_reference(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w) {
+    ApiScope api_scope;
+    RCCHK(check_frame(f, "opd_flow_set_reference", bgr, mem_kind, h, w));
+    HIPCHK(hipSetDevice(f->device));
+    f->has_ref = f->other_valid = false;   // (a failure below leaves no reference)
+    f->h = h; f->w = w;
+    f->top = plan_levels(h, w, f->cfg.win, f->cfg.max_level, f->lh, f->lw, f->lp);
+    RCCHK(enqueue_pyramid(f, f->ref, bgr, mem_kind, h, w, 0));
+    HIPCHK(hipStreamSynchronize(f->stream));
+    f->has_ref = true;
+    return OPD_OK;
+}
+
+extern "C" int opd_flow_track(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w, const float* pts_xy, int n, float* next_xy,
+                              uint8_t* status) {
+    ApiScope api_scope;
+    RCCHK(check_frame(f, "opd_flow_track", bgr, mem_kind, h, w));
+    if (n < 0 || n > f->cfg.max_points)
+        return fail(OPD_EINVAL, "opd_flow_track: " + std::to_string(n) + " points, the handle was created for up to " + std::to_string(f->cfg.max_points));
+    if (n > 0 && (!pts_xy || !next_xy || !status)) return fail(OPD_EINVAL, "opd_flow_track: null point, result or status buffer");
+    if (!f->has_ref) return fail(OPD_ESTATE, "opd_flow_track: no reference frame yet (call opd_flow_set_reference first)");
+    if (h != f->h || w != f->w)
+        return fail(OPD_EINVAL, "opd_flow_track: frame of " + std::to_string(h) + " x " + std::to_string(w) + " pixels, the reference has " +
+                                    std::to_string(f->h) + " x " + std::to_string(f->w));
+    HIPCHK(hipSetDevice(f->device));
+    const int cur = 1 - f->ref;
+    f->other_valid = false;
+    const size_t pts_bytes = (size_t)n * 8;
+    if (n) memcpy(f->h_pin, pts_xy, pts_bytes);
+    RCCHK(enqueue_pyramid(f, cur, bgr, mem_kind, h, w, pts_bytes));
+    if (n) {
+        FlowParams p{};
+        for (int l = 0; l <= f->top; ++l)
+            p.lv[l] = FlowLevel{f->pyr[f->ref].base + f->pyr[f->ref].off[l], f->pyr[cur].base + f->pyr[cur].off[l], f->lw[l], f->lh[l], f->lp[l]};
+        p.top = f->top;
+        p.n = n;
+        p.win = f->cfg.win;
+        p.max_iter = f->cfg.max_iter;
+        p.eps2 = f->cfg.epsilon < 0.f ? -1.f : f->cfg.epsilon * f->cfg.epsilon;
+        p.min_eig = f->cfg.min_eig_threshold;
+        p.pts = reinterpret_cast<const float*>(f->d_io);
+        p.next = reinterpret_cast<float*>(f->d_io + f->out_off);
+        p.status = f->d_io + f->out_off + pts_bytes;
+        HIPCHK(opd_launch_flow_lk(p, f->stream));
+        HIPCHK(hipMemcpyAsync(f->h_pin + f->out_off, f->d_io + f->out_off, pts_bytes + (size_t)n, hipMemcpyDeviceToHost, f->stream));
+    }
+    HIPCHK(hipStreamSynchronize(f->stream));
+    if (n) {
+        memcpy(next_xy, f->h_pin + f->out_off, pts_bytes);
+        memcpy(status, f->h_pin + f->out_off + pts_bytes, (size_t)n);
+    }
+    f->ref = cur;   // the frame just seen is the reference of the next call
+    f->other_valid = true;
+    return OPD_OK;
+}

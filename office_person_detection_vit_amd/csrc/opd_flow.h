@@ -1,0 +1,50 @@
+// opd_flow.h — PRIVATE header of the optical-flow handle (`opd_flow`, include/opd_detr.h): the launch parameters of kernels_flow.hip and the
+// handle itself.  Included by kernels_flow.hip, opd_flow.cpp and opd_flow_test_api.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/opd_detr.h"
+
+enum { OPD_FLOW_MAX_LEVELS = 8, OPD_FLOW_MAX_WIN = 21 };   // pyramid levels incl. level 0; the LK kernel's LDS and registers are sized for a 21 x 21 window
+
+// One pyramid level: uint8 gray, rows `pitch` bytes apart (a multiple of 16; bytes behind column w - 1 are scratch, never read as pixels)
+struct FlowLevel {
+    const uint8_t* ref;   // the reference frame's level
+    const uint8_t* cur;   // the new frame's level (same geometry)
+    int32_t w, h, pitch;
+};
+struct FlowParams {
+    FlowLevel lv[OPD_FLOW_MAX_LEVELS];
+    int32_t top;          // effective top level L (levels 0 .. L exist)
+    int32_t n, win, max_iter;
+    float eps2, min_eig;  // epsilon^2; threshold on the smaller eigenvalue of A / win^2
+    const float* pts;     // [n][2] (x, y) in the reference frame
+    float* next;          // [n][2]
+    uint8_t* status;      // [n]
+};
+
+hipError_t opd_launch_flow_gray(const uint8_t* bgr, uint8_t* gray, int h, int w, int pitch, hipStream_t stream);
+hipError_t opd_launch_flow_pyrdown(const uint8_t* src, int sh, int sw, int spitch, uint8_t* dst, int dpitch, hipStream_t stream);
+hipError_t opd_launch_flow_lk(const FlowParams& p, hipStream_t stream);
+
+inline int flow_pitch(int w) { return (w + 15) / 16 * 16; }
+
+struct FlowPyramid {
+    uint8_t* base = nullptr;                   // one allocation; level l at base + off[l]
+    size_t off[OPD_FLOW_MAX_LEVELS] = {};
+};
+
+struct opd_flow {
+    opd_flow_config cfg{};                     // with the defaults filled in
+    int device = 0;
+    hipStream_t stream = nullptr;
+    FlowPyramid pyr[2];                        // pyr[ref] is the reference; a track call builds the other one and swaps
+    int ref = 0;
+    bool has_ref = false, other_valid = false; // other_valid: pyr[1 - ref] holds the frame the reference replaced
+    int h = 0, w = 0, top = 0;                 // geometry of the reference (and of pyr[1 - ref] when other_valid)
+    int lw[OPD_FLOW_MAX_LEVELS] = {}, lh[OPD_FLOW_MAX_LEVELS] = {}, lp[OPD_FLOW_MAX_LEVELS] = {};
+    uint8_t* h_pin = nullptr;                  // page-locked: [points | frame] up, [next | status] down
+    uint8_t* d_io = nullptr;                   // device image of the same: [points | frame] and, behind it, [next | status]
+    size_t pts_bytes = 0, frame_off = 0, out_off = 0, io_bytes = 0;
+};
