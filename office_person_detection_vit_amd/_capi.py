@@ -175,6 +175,13 @@ TEST_API = {
     "opd_test_roi_features": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p]),
     "opd_test_set_conv_flags": (C.c_int, [C.c_int]),
     "opd_test_set_gemm_ln_kloop": (C.c_int, [C.c_int]),
+    "opd_test_set_encffn_wprefetch": (C.c_int, [C.c_int]),
+    "opd_test_set_pos_frames": (C.c_int, [C.c_int]),
+    "opd_test_conv_splitk": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 13),
+    "opd_test_reduce_act16": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p]),
+    "opd_test_gemm_alt": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5),
+    "opd_test_gemm_frame_bias": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7),
+    "opd_test_reduce_ln_pos": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int]),
     "opd_test_set_graph_guard": (C.c_int, [C.c_int]),
     "opd_test_set_alloc_poison": (C.c_int, [C.c_int]),
     "opd_test_check_redzones": (C.c_int, [C.c_void_p]),

@@ -40,9 +40,15 @@ struct DevMem {
 extern "C" {
 
 // Launch options of the hooks below (test infrastructure only; the kernel tests are single-threaded): bits 8-10 = forced tile height
-// (4 / 5 / 6 x 32 rows), bit 5 = flat-address tile staging (the path tensors beyond 2 GiB take), bit 0 of the second word = k-loop
-// gemm + LayerNorm kernel also for K == 256.
+// (4 / 5 / 6 x 32 rows), bit 5 = flat-address tile staging (the path tensors beyond 2 GiB take), bit 13 = the L2 warm-up of the weights at
+// launch start (ConvGemmParams::wprefetch, what the model's forward sets), bit 0 of the second word = k-loop gemm + LayerNorm kernel also
+// for K == 256.
 static int g_conv_flags = 0, g_gemm_ln_kloop = 0, g_test_dtype = 0;
+// enc_ffn_kernel's own warm-up (EncFfnParams::wprefetch), and the number of per-frame position tables of the position-shadow hooks
+// (0: `pos` is one [period][256] table; B > 0: `pos` is [B][period][256] and the kernels read it through a device array of B pointers)
+static int g_encffn_wprefetch = 0, g_pos_frames = 0;
+int opd_test_set_encffn_wprefetch(int on) { g_encffn_wprefetch = on ? 1 : 0; return OPD_OK; }
+int opd_test_set_pos_frames(int frames) { g_pos_frames = frames > 0 ? frames : 0; return OPD_OK; }
 // the 16-bit operand type the kernel hooks below launch with: their uint16 buffers then hold bfloat16 bit patterns (OPD_DT_BF16)
 int opd_test_set_elem_bf16(int on) { g_test_dtype = on ? OPD_DT_BF16 : OPD_DT_F16; return OPD_OK; }
 int opd_test_set_conv_flags(int flags) { g_conv_flags = flags; return OPD_OK; }
@@ -50,6 +56,16 @@ int opd_test_set_gemm_ln_kloop(int on) { g_gemm_ln_kloop = on ? 1 : 0; return OP
 static void apply_conv_flags(ConvGemmParams& p, int flags) {
     p.force_mt = (flags >> 8) & 7;
     p.flat_staging = (flags >> 5) & 1;
+    p.wprefetch = (flags >> 13) & 1;
+}
+// B per-frame tables [B][rows][cols] fp32 -> one device copy and a device array of B pointers into it (bias_ptrs / pos_ptrs)
+static const float* const* upload_frame_tables(DevMem& dm, const float* tables, int B, size_t rows, size_t cols, const float** first) {
+    const float* d = dm.up(tables, (size_t)B * rows * cols);
+    if (!d) return nullptr;
+    std::vector<const float*> h((size_t)B);
+    for (int b = 0; b < B; ++b) h[(size_t)b] = d + (size_t)b * rows * cols;
+    *first = d;
+    return dm.up(h.data(), h.size());
 }
 
 // x: NHWC fp16 bits [B][H][W][Cin] (stem: NHWC4); w: [N][K] fp16 bits; bias fp32 [N] (or [period][N]);
@@ -112,9 +128,128 @@ int opd_test_conv_dual(const uint16_t* x, const uint16_t* w1, const uint16_t* x2
     if (!p.x || !p.x2 || !p.w || !p.bias || !p.out || !p.zero16) return tfail(OPD_ENOMEM, "test alloc failed");
     p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.N = N; p.KH = KH; p.KW = KH; p.stride = stride; p.pad = pad;
     p.M = (int)M; p.K = K; p.K1 = K1; p.relu = relu; p.H2 = H2; p.W2 = W2; p.Cin2 = Cin2; p.stride2 = stride2;
+    apply_conv_flags(p, g_conv_flags);
     TCHK(opd_launch_conv_gemm(p, nullptr));
     TCHK(hipDeviceSynchronize());
     TCHK(hipMemcpy(out, p.out, M * N * 2, hipMemcpyDeviceToHost));
+    return OPD_OK;
+}
+
+// Split-K convolution the way the model's run_conv runs it: `splits` K slices into fp32 slabs (slab stride M * N, bias in slab 0), then
+// opd_launch_reduce_act16 sums them in slice order, applies the ReLU and rounds once.  Launch options as opd_test_conv_gemm.
+int opd_test_conv_splitk(const uint16_t* x, const uint16_t* w, const float* bias, uint16_t* out16, int B, int H, int W, int Cin, int OH, int OW,
+                         int N, int KH, int KW, int stride, int pad, int relu, int splits) {
+    if (splits < 2) return tfail(OPD_EINVAL, "conv_splitk: splits must be >= 2");
+    DevMem dm;
+    const size_t M = (size_t)B * OH * OW;
+    const int K = KH * KW * Cin;
+    ConvGemmParams p{}; p.dtype = g_test_dtype;
+    p.x = dm.up(x, (size_t)B * H * W * Cin);
+    p.w = dm.up(w, (size_t)N * K);
+    p.bias = dm.up(bias, (size_t)N);
+    std::vector<float> zeros((size_t)N, 0.f);   // (slices > 0 take their "bias" from here)
+    p.zero16 = dm.up(zeros.data(), zeros.size());
+    float* slab = dm.up<float>(nullptr, (size_t)splits * M * N);
+    uint16_t* dout = dm.up<uint16_t>(nullptr, M * N);
+    if (!p.x || !p.w || !p.bias || !p.zero16 || !slab || !dout) return tfail(OPD_ENOMEM, "test alloc failed");
+    p.out = slab;
+    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.N = N; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
+    p.M = (int)M; p.K = K; p.out_f32 = 1; p.relu = 0; p.split_k = splits;
+    apply_conv_flags(p, g_conv_flags);
+    TCHK(opd_launch_conv_gemm(p, nullptr));
+    TCHK(opd_launch_reduce_act16(slab, splits, M * N, dout, M * N, relu ? 1 : 0, nullptr, g_test_dtype));
+    TCHK(hipDeviceSynchronize());
+    TCHK(hipMemcpy(out16, dout, M * N * 2, hipMemcpyDeviceToHost));
+    return OPD_OK;
+}
+
+// reduce_act16_kernel alone: partials [nsplit] slabs of n floats, slab_stride floats apart (host array of (nsplit - 1) * slab_stride + n floats)
+int opd_test_reduce_act16(const float* partials, int nsplit, long long slab_stride, long long n, int relu, uint16_t* out16) {
+    if (nsplit < 1 || n <= 0 || slab_stride < n) return tfail(OPD_EINVAL, "reduce_act16: bad arguments");
+    DevMem dm;
+    const float* dp = dm.up(partials, (size_t)(nsplit - 1) * slab_stride + n);
+    uint16_t* dout = dm.up<uint16_t>(nullptr, (size_t)n);
+    if (!dp || !dout) return tfail(OPD_ENOMEM, "test alloc failed");
+    TCHK(opd_launch_reduce_act16(dp, nsplit, (size_t)slab_stride, dout, (size_t)n, relu, nullptr, g_test_dtype));
+    TCHK(hipDeviceSynchronize());
+    TCHK(hipMemcpy(out16, dout, (size_t)n * 2, hipMemcpyDeviceToHost));
+    return OPD_OK;
+}
+
+// pointwise GEMM with two activation sources (the fused q | k | v projection): out[:, n] = (n mod alt_mod < alt_cols ? x : x_alt) . w[n] + bias[n]
+int opd_test_gemm_alt(const uint16_t* x, const uint16_t* x_alt, const uint16_t* w, const float* bias, uint16_t* out16, int M, int N, int K,
+                      int alt_mod, int alt_cols) {
+    DevMem dm;
+    ConvGemmParams p{}; p.dtype = g_test_dtype;
+    p.x = dm.up(x, (size_t)M * K);
+    p.x_alt = dm.up(x_alt, (size_t)M * K);
+    p.w = dm.up(w, (size_t)N * K);
+    p.bias = dm.up(bias, (size_t)N);
+    const uint32_t zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    p.zero16 = dm.up(zeros, 8);
+    p.out = dm.up<unsigned char>(nullptr, (size_t)M * N * 2);
+    if (!p.x || !p.x_alt || !p.w || !p.bias || !p.zero16 || !p.out) return tfail(OPD_ENOMEM, "test alloc failed");
+    p.B = M; p.H = 1; p.W = 1; p.Cin = K; p.OH = 1; p.OW = 1; p.N = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
+    p.M = M; p.K = K; p.alt_mod = alt_mod; p.alt_cols = alt_cols;
+    apply_conv_flags(p, g_conv_flags);
+    TCHK(opd_launch_conv_gemm(p, nullptr));
+    TCHK(hipDeviceSynchronize());
+    TCHK(hipMemcpy(out16, p.out, (size_t)M * N * 2, hipMemcpyDeviceToHost));
+    return OPD_OK;
+}
+
+// pointwise GEMM with one row-periodic bias table PER FRAME of `period` rows (ragged batches): tables [B][period][N] fp32, B = ceil(M / period);
+// the kernel reads them through a device array of B pointers (bias_ptrs), `bias` is table 0 as in the model.  out fp16 bits or fp32 [M][N].
+int opd_test_gemm_frame_bias(const uint16_t* x, const uint16_t* w, const float* tables, void* out, int M, int N, int K, int period, int pmod,
+                             int pcols, int out_f32) {
+    if (M <= 0 || period <= 0) return tfail(OPD_EINVAL, "gemm_frame_bias: bad arguments");
+    DevMem dm;
+    const int B = (M + period - 1) / period;
+    ConvGemmParams p{}; p.dtype = g_test_dtype;
+    p.x = dm.up(x, (size_t)M * K);
+    p.w = dm.up(w, (size_t)N * K);
+    p.bias_ptrs = upload_frame_tables(dm, tables, B, (size_t)period, (size_t)N, &p.bias);
+    const uint32_t zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    p.zero16 = dm.up(zeros, 8);
+    const size_t obytes = (size_t)M * N * (out_f32 ? 4 : 2);
+    p.out = dm.up<unsigned char>(nullptr, obytes);
+    if (!p.x || !p.w || !p.bias_ptrs || !p.zero16 || !p.out) return tfail(OPD_ENOMEM, "test alloc failed");
+    p.B = M; p.H = 1; p.W = 1; p.Cin = K; p.OH = 1; p.OW = 1; p.N = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
+    p.M = M; p.K = K; p.bias_period = period; p.bias_pmod = pmod; p.bias_pcols = pcols; p.out_f32 = out_f32;
+    apply_conv_flags(p, g_conv_flags);
+    TCHK(opd_launch_conv_gemm(p, nullptr));
+    TCHK(hipDeviceSynchronize());
+    TCHK(hipMemcpy(out, p.out, obytes, hipMemcpyDeviceToHost));
+    return OPD_OK;
+}
+
+// reduce_ln256_kernel with the position shadow: y = LN(sum_z partials[z] + res) (gamma == null: the plain sum), y16 = fp16(y),
+// yp16 = fp16(y + table[row / period][row % period]).  partials: nsplit slabs of M * 256 floats; pos: one [period][256] table, or
+// pos_tables [B][period][256] (B > 0) read through a device array of B pointers, with table 0 as `pos`.
+int opd_test_reduce_ln_pos(const float* partials, int nsplit, const float* res32, const float* gamma, const float* beta, const float* pos,
+                           const float* pos_tables, int B, int period, float* y, uint16_t* y16, uint16_t* yp16, int M) {
+    if (M <= 0 || nsplit < 1 || period <= 0 || (!pos && !pos_tables) || (pos_tables && (size_t)B * period < (size_t)M))
+        return tfail(OPD_EINVAL, "reduce_ln_pos: bad arguments");
+    DevMem dm;
+    const size_t MN = (size_t)M * 256;
+    const float* dp = dm.up(partials, (size_t)nsplit * MN);
+    const float* dres = res32 ? dm.up(res32, MN) : nullptr;
+    const float* dg = gamma ? dm.up(gamma, 256) : nullptr;
+    const float* db = beta ? dm.up(beta, 256) : nullptr;
+    const float* dpos = nullptr;
+    const float* const* dptrs = nullptr;
+    if (pos_tables) dptrs = upload_frame_tables(dm, pos_tables, B, (size_t)period, 256, &dpos);
+    else dpos = dm.up(pos, (size_t)period * 256);
+    float* dy = dm.up<float>(nullptr, MN);
+    uint16_t* dy16 = dm.up<uint16_t>(nullptr, MN);
+    uint16_t* dyp16 = dm.up<uint16_t>(nullptr, MN);
+    if (!dp || (res32 && !dres) || (gamma && !dg) || (beta && !db) || !dpos || (pos_tables && !dptrs) || !dy || !dy16 || !dyp16)
+        return tfail(OPD_ENOMEM, "test alloc failed");
+    TCHK(opd_launch_reduce_ln_pos(dp, nsplit, MN, dres, dg, db, dy, dy16, M, dpos, dptrs, period, dyp16, nullptr, g_test_dtype));
+    TCHK(hipDeviceSynchronize());
+    TCHK(hipMemcpy(y, dy, MN * 4, hipMemcpyDeviceToHost));
+    TCHK(hipMemcpy(y16, dy16, MN * 2, hipMemcpyDeviceToHost));
+    TCHK(hipMemcpy(yp16, dyp16, MN * 2, hipMemcpyDeviceToHost));
     return OPD_OK;
 }
 
@@ -183,7 +318,13 @@ int opd_test_gemm_ln_deep(const uint16_t* x, const uint16_t* w, const float* bia
     p.beta = beta ? dm.up(beta, 256) : nullptr;
     p.y32 = (in_place && res) ? res : dm.up<float>(nullptr, (size_t)M * 256);   // the model writes the residual stream in place
     p.y16 = dm.up<uint16_t>(nullptr, (size_t)M * 256);
-    p.pos = pos ? dm.up(pos, (size_t)period * 256) : nullptr;
+    if (pos && g_pos_frames) {   // per-frame tables (ragged batches): the single table stays set to frame 0's, as in the model
+        if ((size_t)g_pos_frames * period < (size_t)M) return tfail(OPD_EINVAL, "gemm_ln_deep: fewer position tables than frames");
+        p.pos_ptrs = upload_frame_tables(dm, pos, g_pos_frames, (size_t)period, 256, &p.pos);
+        if (!p.pos_ptrs) return tfail(OPD_ENOMEM, "test alloc failed");
+    } else {
+        p.pos = pos ? dm.up(pos, (size_t)period * 256) : nullptr;
+    }
     p.pos_period = period;
     p.yp16 = pos ? dm.up<uint16_t>(nullptr, (size_t)M * 256) : nullptr;
     if (!p.x || !p.w || !p.bias || (gamma && (!p.gamma || !p.beta)) || !p.y32 || !p.y16 || (res32 && !p.res32) || (pos && (!p.pos || !p.yp16)))
@@ -256,8 +397,15 @@ int opd_test_enc_ffn(const uint16_t* x, const uint16_t* w1, const float* b1, con
     }
     p.y32 = in_place ? res : dm.up<float>(nullptr, (size_t)M * 256);
     p.y16 = (in_place && !wo) ? dx : dm.up<uint16_t>(nullptr, (size_t)M * 256);
-    p.pos = pos ? dm.up(pos, (size_t)period * 256) : nullptr;
+    if (pos && g_pos_frames) {   // per-frame tables, as in opd_test_gemm_ln_deep
+        if ((size_t)g_pos_frames * period < (size_t)M) return tfail(OPD_EINVAL, "enc_ffn: fewer position tables than frames");
+        p.pos_ptrs = upload_frame_tables(dm, pos, g_pos_frames, (size_t)period, 256, &p.pos);
+        if (!p.pos_ptrs) return tfail(OPD_ENOMEM, "test alloc failed");
+    } else {
+        p.pos = pos ? dm.up(pos, (size_t)period * 256) : nullptr;
+    }
     p.pos_period = period;
+    p.wprefetch = g_encffn_wprefetch;
     p.yp16 = pos ? dm.up<uint16_t>(nullptr, (size_t)M * 256) : nullptr;
     if (!dx || !p.wpack || !p.b2 || !p.res32 || !p.gamma || !p.beta || !p.y32 || !p.y16 || (pos && (!p.pos || !p.yp16))) return tfail(OPD_ENOMEM, "test alloc failed");
     p.M = M; p.F = F; p.pack_tail = tail; p.tail = tail; p.tail_pos = tail_pos;

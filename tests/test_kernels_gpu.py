@@ -23,10 +23,11 @@ def lib():
     return _capi.load_library()
 
 
-@pytest.fixture(params=[0, 0x400, 0x500, 0x600, 0x20], ids=["auto_tiles", "128rows", "160rows", "192rows", "flat_staging"])
+@pytest.fixture(params=[0, 0x400, 0x500, 0x600, 0x20, 0x2000], ids=["auto_tiles", "128rows", "160rows", "192rows", "flat_staging", "wprefetch"])
 def gemm_variant(request, lib):
     """Every instantiation of the implicit-GEMM kernel the dispatcher can pick: the quantisation-aware tile height, each height
-    forced, and the flat-address staging path that tensors beyond 2 GiB take (opd_test_set_conv_flags)."""
+    forced, the flat-address staging path that tensors beyond 2 GiB take, and the L2 warm-up of the weights at launch start that
+    the model's forward turns on (opd_test_set_conv_flags)."""
     lib.opd_test_set_conv_flags(request.param)
     yield request.param
     lib.opd_test_set_conv_flags(0)
