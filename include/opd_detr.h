@@ -399,6 +399,80 @@ OPD_API int opd_flow_set_reference(opd_flow* f, const uint8_t* bgr, int mem_kind
 OPD_API int opd_flow_track(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w, const float* pts_xy, int n, float* next_xy,
                            uint8_t* status);
 
+/* ---- Floor map: camera pixels -> floor-map pixels / mm and zone membership (fourth handle type: an immutable model, own stream) ---------
+ * The reference's Phase 3 per detection (`TransformPhase.execute`, src/pipeline/phases/transform.py:257-330): foot point of the box ->
+ * optional lens undistortion (piecewise-affine and thin-plate-spline only) -> homography / piecewise affine / thin-plate spline ->
+ * floor pixels, mm and the bounds test -> `ZoneClassifier.classify`.  All arithmetic is float64, one wave per record, without fused
+ * multiply-adds: the operations of the numpy restatement in tests/floor_common.py, one for one.  A record's
+ * result depends on its box and the model only.  Triangulation, the affine matrices and the spline coefficients come from the host
+ * (floor.py: scipy / numpy, as the reference computes them); the device never triangulates. */
+typedef struct opd_floor opd_floor; /* opaque floor-map handle */
+
+#define OPD_FLOOR_HOMOGRAPHY 0
+#define OPD_FLOOR_PWA 1
+#define OPD_FLOOR_TPS 2
+#define OPD_FLOOR_MAX_POINTS 256
+#define OPD_FLOOR_MAX_TRIANGLES 512
+#define OPD_FLOOR_MAX_ZONES 64
+#define OPD_FLOOR_MAX_VERTICES 64 /* per polygon */
+#define OPD_FLOOR_VALID 1u        /* opd_floor_rec.flags: always set (the reference's transformers never fail a point) */
+#define OPD_FLOOR_WITHIN 2u       /* 0 <= px[0] < width_px && 0 <= px[1] < height_px */
+#define OPD_FLOOR_EXTRAPOLATED 4u /* piecewise affine: no triangle holds the point, the one with the nearest centroid was used */
+
+/* Everything is copied at creation.  Arrays a method does not use may be NULL. */
+typedef struct opd_floor_config {
+    int32_t method;               /* OPD_FLOOR_HOMOGRAPHY, OPD_FLOOR_PWA or OPD_FLOOR_TPS */
+    int32_t n_points;             /* control points (PWA, TPS): 3 .. 256 */
+    int32_t n_triangles;          /* PWA: 1 .. 512 */
+    int32_t n_zones;              /* 0 .. 64 */
+    int32_t has_distortion;       /* != 0: undistort with `intrinsics` and `distortion` first (ignored for the homography, as in the reference) */
+    int32_t allow_overlap;        /* 0: keep only the zone with the smallest (priority or +inf, position in the list) */
+    int32_t width_px, height_px;  /* floor map size, for the bounds test */
+    double H[9];                  /* homography, row-major; |det| >= 1e-10 */
+    double scale_x_mm_per_px, scale_y_mm_per_px;
+    double intrinsics[4];         /* fx, fy, cx, cy */
+    double distortion[5];         /* k1, k2, p1, p2, k3 (OpenCV's order) */
+    double tps_affine[6];         /* TPS: a0, a1, a2 of x, then of y: a0 + a1 x + a2 y */
+    const double* points;         /* [n_points][2] control points in camera pixels */
+    const int32_t* triangles;     /* PWA: [n_triangles][3] indices into `points` (scipy.spatial.Delaunay.simplices) */
+    const double* affine;         /* PWA: [n_triangles][6], rows x and y of the triangle's matrix: (a0 x + a1 y) + a2 */
+    const double* tps_weights;    /* TPS: [n_points][2] (w_x, w_y) */
+    const double* zone_vertices;  /* [zone_offsets[n_zones]][2] floor pixels, the polygons one behind the other */
+    const int32_t* zone_offsets;  /* [n_zones + 1] first vertex of every polygon; 3 .. 64 vertices each */
+    const double* zone_priority;  /* [n_zones]; NaN = the zone has none.  NULL = none has one */
+} opd_floor_config;
+
+typedef struct opd_floor_rec {
+    double px[2];       /* floor-map pixels */
+    double mm[2];       /* px * scale */
+    uint64_t zone_mask; /* bit z: zone z holds px (after the allow_overlap rule) */
+    int32_t triangle;   /* PWA: the triangle used; -1 for the other methods */
+    uint32_t flags;     /* OPD_FLOOR_VALID | OPD_FLOOR_WITHIN | OPD_FLOOR_EXTRAPOLATED */
+} opd_floor_rec;
+
+typedef struct opd_floor_model_info {
+    int32_t method, n_points, n_triangles, n_zones, n_edges, has_distortion, allow_overlap, device_ordinal;
+} opd_floor_model_info;
+
+/* OPD_EINVAL, before the device is touched, for: an unknown method, a count above the limits, fewer than 3 control points, a singular H
+ * (|det| < 1e-10, the reference's test), a triangle index outside the points, a polygon of fewer than 3 or more than 64 vertices, a
+ * missing array, a zero focal length with has_distortion. */
+OPD_API int opd_floor_create(const opd_floor_config* cfg, int device_ordinal, opd_floor** out);
+OPD_API void opd_floor_destroy(opd_floor* f);
+OPD_API int opd_floor_info(const opd_floor* f, opd_floor_model_info* info);
+/* `transform_batch` + `classify`: boxes_xywh [n][4] float32 (host for OPD_MEM_HOST, a device pointer read in place for OPD_MEM_DEVICE) ->
+ * out [n] (host).  The foot point is (x + w / 2, y + h) in float64.  One upload, one launch, one download, one wait; n = 0 is OPD_OK. */
+OPD_API int opd_floor_transform(opd_floor* f, const float* boxes_xywh, int n, int mem_kind, opd_floor_rec* out);
+/* `transform_pixel` + `classify` of n camera points pts_xy [n][2] float64 (host): no foot-point step. */
+OPD_API int opd_floor_transform_points(opd_floor* f, const double* pts_xy, int n, opd_floor_rec* out);
+/* `classify_batch` of n floor points floor_xy [n][2] float64 (host) -> masks [n] (host). */
+OPD_API int opd_floor_classify(opd_floor* f, const double* floor_xy, int n, uint64_t* masks);
+/* opd_detr_detect_frames on host frames plus a floor record for every record of class `label`, computed while the records are on the
+ * device from the box the Python shim derives, (x1, y1, float32(x2 - x1), float32(y2 - y1)).  `floor` = host [B][num_queries]; the row of
+ * a record is its query_index; rows of queries without such a record are not written.  One host wait.  `m` and `f` must be on one device. */
+OPD_API int opd_detr_detect_frames_floor(opd_detr* m, opd_floor* f, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
+                                         int label, opd_det* out, int32_t* counts, opd_floor_rec* floor);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 OPD_API const char* opd_last_error(void);
 

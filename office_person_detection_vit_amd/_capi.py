@@ -24,6 +24,9 @@ OPD_FLAG_MULTI_STREAM = 2
 OPD_REID_MODEL_CLIP = 0
 OPD_REID_MODEL_OSNET = 1
 OPD_FLAG_BF16 = 4
+OPD_FLOOR_HOMOGRAPHY, OPD_FLOOR_PWA, OPD_FLOOR_TPS = 0, 1, 2
+OPD_FLOOR_VALID, OPD_FLOOR_WITHIN, OPD_FLOOR_EXTRAPOLATED = 1, 2, 4
+OPD_FLOOR_MAX_POINTS, OPD_FLOOR_MAX_TRIANGLES, OPD_FLOOR_MAX_ZONES, OPD_FLOOR_MAX_VERTICES = 256, 512, 64, 64
 OPD_COMM_ID_BYTES = 128
 OPD_OK, OPD_EINVAL, OPD_EIO, OPD_ESCHEMA, OPD_EHIP, OPD_ENOMEM, OPD_ESTATE = 0, -1, -2, -3, -4, -5, -6   # include/opd_detr.h
 
@@ -63,6 +66,22 @@ class OpdReidModelInfo(C.Structure):   # opd_reid_model_info
 class OpdFlowConfig(C.Structure):   # opd_flow_config (zeros = the defaults of cv2.calcOpticalFlowPyrLK as the reference calls it)
     _fields_ = [("max_h", C.c_int), ("max_w", C.c_int), ("max_points", C.c_int), ("win", C.c_int), ("max_level", C.c_int),
                 ("max_iter", C.c_int), ("epsilon", C.c_float), ("min_eig_threshold", C.c_float)]
+
+
+class OpdFloorConfig(C.Structure):   # opd_floor_config: everything is copied at creation
+    _fields_ = [("method", C.c_int32), ("n_points", C.c_int32), ("n_triangles", C.c_int32), ("n_zones", C.c_int32), ("has_distortion", C.c_int32),
+                ("allow_overlap", C.c_int32), ("width_px", C.c_int32), ("height_px", C.c_int32), ("H", C.c_double * 9),
+                ("scale_x_mm_per_px", C.c_double), ("scale_y_mm_per_px", C.c_double), ("intrinsics", C.c_double * 4), ("distortion", C.c_double * 5),
+                ("tps_affine", C.c_double * 6), ("points", C.c_void_p), ("triangles", C.c_void_p), ("affine", C.c_void_p), ("tps_weights", C.c_void_p),
+                ("zone_vertices", C.c_void_p), ("zone_offsets", C.c_void_p), ("zone_priority", C.c_void_p)]
+
+
+class OpdFloorRec(C.Structure):   # opd_floor_rec (48 bytes)
+    _fields_ = [("px", C.c_double * 2), ("mm", C.c_double * 2), ("zone_mask", C.c_uint64), ("triangle", C.c_int32), ("flags", C.c_uint32)]
+
+
+class OpdFloorModelInfo(C.Structure):   # opd_floor_model_info
+    _fields_ = [(n, C.c_int32) for n in ("method", "n_points", "n_triangles", "n_zones", "n_edges", "has_distortion", "allow_overlap", "device_ordinal")]
 
 
 # name -> (restype, argtypes): every symbol include/opd_detr.h declares
@@ -124,6 +143,14 @@ API = {
     "opd_flow_destroy": (None, [C.c_void_p]),
     "opd_flow_set_reference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "opd_flow_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "opd_floor_create": (C.c_int, [C.POINTER(OpdFloorConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "opd_floor_destroy": (None, [C.c_void_p]),
+    "opd_floor_info": (C.c_int, [C.c_void_p, C.POINTER(OpdFloorModelInfo)]),
+    "opd_floor_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "opd_floor_transform_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "opd_floor_classify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "opd_detr_detect_frames_floor": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.POINTER(OpdDet), C.POINTER(C.c_int32),
+                                                C.c_void_p]),
     "opd_last_error": (C.c_char_p, []),
     "opd_version": (C.c_char_p, []),
 }
@@ -224,6 +251,8 @@ TEST_API = {
                                              C.POINTER(OpdKernelStat), C.c_int, C.POINTER(C.c_int)]),
     # optical-flow hook (csrc/opd_flow_test_api.cpp)
     "opd_flow_test_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    # floor-map hook (csrc/opd_floor_test_api.cpp)
+    "opd_floor_test_tables": (C.c_int, [C.POINTER(OpdFloorConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
 }
 
 _lib: Optional[C.CDLL] = None

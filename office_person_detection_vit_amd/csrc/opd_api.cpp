@@ -5,6 +5,7 @@
 #include <new>
 #include <stdexcept>
 
+#include "opd_floor.h"
 #include "opd_model.h"
 
 namespace opd {
@@ -158,15 +159,25 @@ static void unpack_records(const opd_detr* m, const void* pinned, int B, opd_det
 }
 
 // (`features` != null: the [B][Q][d_model] feature rows behind the counts travel in the same copy)
-static int fetch_records(opd_detr* m, opd_det* out, int32_t* counts, int mem_kind, float* features = nullptr) {
+// (`fmap_out` != null: the floor records of the batch follow in a copy of their own, before the same wait; only rows of records labelled `label` are handed on)
+static int fetch_records(opd_detr* m, opd_det* out, int32_t* counts, int mem_kind, float* features = nullptr, opd_floor_rec* fmap_out = nullptr, int label = 0) {
     const int B = m->last_B;
     if (!outputs_on_device(mem_kind)) {   // (device callers had the post-process kernel write into their buffers)
         // one copy of [records of max_batch frames | counts (| features)] into page-locked memory (a copy into the caller's pageable arrays is
         // staged by the runtime anyway, once per call), handed over after the wait
         if (!m->sync_pinned) HIPCHK(hipHostMalloc(&m->sync_pinned, feat_off(m) + m->cfg.max_batch * feat_row(m), hipHostMallocDefault));
         HIPCHK(hipMemcpyAsync(m->sync_pinned, m->d_records, features ? feat_off(m) + B * feat_row(m) : rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
+        if (fmap_out) HIPCHK(hipMemcpyAsync(m->h_floor, m->d_floor, (size_t)B * m->arch.queries * sizeof(opd_floor_rec), hipMemcpyDeviceToHost, m->stream));
         HIPCHK(hipStreamSynchronize(m->stream));
         unpack_records(m, m->sync_pinned, B, out, counts, features);
+        if (fmap_out) {
+            const int Q = m->arch.queries;
+            for (int b = 0; b < B; ++b)
+                for (int i = 0; i < counts[b] && i < Q; ++i) {
+                    const opd_det& r = out[(size_t)b * Q + i];
+                    if (r.label == label && (unsigned)r.query_index < (unsigned)Q) fmap_out[(size_t)b * Q + r.query_index] = m->h_floor[(size_t)b * Q + r.query_index];
+                }
+        }
     }
     HIPCHK(hipStreamSynchronize(m->stream));
     if (m->profiling) {
@@ -197,8 +208,16 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
         cp.Q = Q; cp.fh = h; cp.fw = w; cp.label = s.label; cp.n = B * Q;
         HIPCHK(opd_launch_color_features(cp, std::min(64, (h + 15) / 16), m->stream));
     }
+    if (s.fmap) {   // the floor record of every record of the class, from the box the Python shim derives, while the records are on the device
+        FloorParams fp{};
+        fp.m = s.fmap->model;
+        fp.mode = FLOOR_IN_RECORDS; fp.n = B * Q;
+        fp.records = m->d_records; fp.counts = m->d_counts; fp.Q = Q; fp.label = s.label;
+        fp.out = m->d_floor;
+        HIPCHK(opd_launch_floor(fp, m->stream));
+    }
     if (s.wait == WAIT_NONE) return OPD_OK;
-    if (s.wait == WAIT_BLOCKING) return fetch_records(m, s.out, s.counts, s.mem_kind, s.features);   // records, counts and feature rows: one copy, one wait
+    if (s.wait == WAIT_BLOCKING) return fetch_records(m, s.out, s.counts, s.mem_kind, s.features, s.fmap ? s.fmap_out : nullptr, s.label);   // records, counts and feature rows: one copy, one wait
     opd_detr::AsyncHost& slot = m->async_host[s.ticket];
     slot.out = nullptr;
     if (!dev) {   // host outputs: pinned staging so that the copy stays asynchronous; delivered by opd_detr_wait
@@ -391,6 +410,7 @@ void opd_detr_destroy(opd_detr* m) {
     for (auto& a : m->async_host)
         if (a.pinned) (void)hipHostFree(a.pinned);
     if (m->sync_pinned) { (void)hipHostFree(m->sync_pinned); m->sync_pinned = nullptr; }
+    if (m->h_floor) { (void)hipHostFree(m->h_floor); m->h_floor = nullptr; }
     for (auto& e : m->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : m->event_pool) (void)hipEventDestroy(e);
@@ -548,6 +568,25 @@ int opd_detr_detect_frames_color(opd_detr* m, const uint8_t* const* frames, int 
     if (!m->d_color_acc) RCCHK(dalloc(m, &m->d_color_acc, (size_t)m->cfg.max_batch * m->arch.queries * OPD_COLOR_ACC_WORDS, false));
     return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr,
                            {threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_COLOR, label, features});
+}
+
+// The floor-map twin: same upload, forward and post-process; one wave per record slot then maps the foot point of every record of the class
+// with `f`'s model (read-only device tables: any stream may read them), and the rows travel behind the records before the one wait.
+int opd_detr_detect_frames_floor(opd_detr* m, opd_floor* f, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
+                                 int label, opd_det* out, int32_t* counts, opd_floor_rec* floor) {
+    ApiScope api_scope;
+    if (!f) return fail(OPD_EINVAL, "opd_detr_detect_frames_floor: null floor-map handle");
+    RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && floor, "opd_detr_detect_frames_floor"));
+    if (f->device != m->device)
+        return fail(OPD_EINVAL, "opd_detr_detect_frames_floor: the detector is on device " + std::to_string(m->device) + ", the floor map on device " + std::to_string(f->device));
+    HIPCHK(hipSetDevice(m->device));
+    if (!m->d_floor) {
+        const size_t n = (size_t)m->cfg.max_batch * m->arch.queries;
+        RCCHK(dalloc(m, &m->d_floor, n, false));
+        HIPCHK(hipHostMalloc((void**)&m->h_floor, n * sizeof(opd_floor_rec), hipHostMallocDefault));
+    }
+    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr,
+                           {threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_NONE, label, nullptr, f, floor});
 }
 
 int opd_host_alloc(size_t bytes, void** out) {

@@ -254,6 +254,8 @@ struct opd_detr : DetrWeights {
     AsyncHost async_host[4];
     void* sync_pinned = nullptr;   // page-locked staging of the blocking entry points: [records of max_batch frames | counts]
     uint32_t* d_color_acc = nullptr;   // [max_batch][queries][OPD_COLOR_ACC_WORDS] integer sums of opd_detr_detect_frames_color (allocated by its first call)
+    opd_floor_rec* d_floor = nullptr;   // [max_batch][queries] floor records of opd_detr_detect_frames_floor (allocated, with its page-locked twin, by its first call)
+    opd_floor_rec* h_floor = nullptr;
     float* d_feat_all = nullptr;   // [max_batch][queries][d_model] behind the counts in the d_records allocation: features of a batch's records (opd_detr_detect_frames_features)
     // device-side resize (camera resolution -> model resolution): source staging (grown on demand) and coefficient tables
     uint8_t* d_src = nullptr;
@@ -366,6 +368,8 @@ struct RecordSink {
     int wait, ticket;
     int feature, label;           // FEAT_*: feature rows of the records labelled `label` -> `features` (host; WAIT_BLOCKING)
     float* features;
+    const opd_floor* fmap;        // non-null: a floor record of every record labelled `label` -> `fmap_out` [B][queries] (host; WAIT_BLOCKING)
+    opd_floor_rec* fmap_out;
 };
 int check_shape(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W);
 int detect_pipeline(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, const RecordSink& sink);

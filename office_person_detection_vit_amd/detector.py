@@ -312,6 +312,24 @@ class HipDetrDetector:
         self._detect_into(frames, model, C.addressof(recs), C.addressof(counts), on_device=False)
         return recs, counts, Q
 
+    def _detect_records_floor(self, frames: Sequence[np.ndarray], floor_map, handle: Optional[int] = None):
+        """``_detect_records`` plus the ``[B * Q]`` floor records of the person records (row = frame * Q + query_index), from ONE
+        ``opd_detr_detect_frames_floor`` call, when the chunk can go down as a list of host frames; else ``None`` in their place
+        (the caller then runs ``floor_map.apply`` on the detections)."""
+        target = self._frame_list_target(frames) if (self.frame_lists and len(frames)) else None
+        if target is None or int(floor_map.device) != self.device_ordinal:
+            return (*self._detect_records(frames, handle), None)
+        model = self.model if handle is None else handle
+        B, Q = len(frames), self._info.num_queries
+        recs, counts = (_capi.OpdDet * (B * Q))(), (C.c_int32 * B)()
+        floor = np.zeros(B * Q, floor_map.REC_DTYPE)
+        ptrs = (C.c_void_p * B)(*[f.ctypes.data for f in frames])
+        rc = self._lib.opd_detr_detect_frames_floor(C.c_void_p(model), floor_map._require(), ptrs, B, int(frames[0].shape[0]), int(frames[0].shape[1]),
+                                                    target[0], target[1], float(self.confidence_threshold), PERSON_LABEL, recs, counts, floor.ctypes.data)
+        _capi.check(rc, "opd_detr_detect_frames_floor")
+        self._last_orig = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
+        return recs, counts, Q, floor
+
     def _frame_list_target(self, frames: Sequence[np.ndarray]) -> Optional[Tuple[int, int]]:
         """(H, W) of the model input when the chunk can go down as a LIST of frame pointers (``opd_detr_detect_frames``: every frame
         uploaded from where it lies, no stacked copy): contiguous uint8 [h, w, 3] frames of ONE size, model size reached on the device."""
@@ -386,8 +404,9 @@ class HipDetrDetector:
         if len(frames):
             self._detect_into(frames, self.model, int(rec_ptr), int(cnt_ptr), on_device=True)
 
-    def _postprocess_batch(self, recs, counts, Q: int) -> List[List[Detection]]:
-        """``_postprocess_batch`` (deleted vit_detector.py 591-647): person filter + NMS (C-ABI), xyxy -> xywh, foot point."""
+    def _postprocess_batch(self, recs, counts, Q: int, floor=None, floor_map=None) -> List[List[Detection]]:
+        """``_postprocess_batch`` (deleted vit_detector.py 591-647): person filter + NMS (C-ABI), xyxy -> xywh, foot point.
+        ``floor``: the fused call's floor records; every kept detection takes the row of its query (Phase 3's four fields)."""
         rc = self._lib.opd_person_nms_batch(recs, counts, len(counts), Q, PERSON_LABEL, float(self.nms_threshold))   # in place
         _capi.check(rc, "opd_person_nms_batch")
         results: List[List[Detection]] = []
@@ -398,28 +417,43 @@ class HipDetrDetector:
                 bbox = (float(r.x1), float(r.y1), float(r.x2 - r.x1), float(r.y2 - r.y1))
                 dets.append(Detection(bbox=bbox, confidence=float(r.score), class_id=PERSON_LABEL, class_name="person",
                                       camera_coords=self._get_foot_position(bbox), query_index=int(r.query_index)))
+                if floor is not None:
+                    floor_map._fill(dets[-1], floor[b * Q + int(r.query_index)])
             results.append(dets)
         return results
 
-    def detect_batch(self, frames: List[np.ndarray]) -> List[List[Detection]]:
-        """Batched detection (deleted vit_detector.py 508-550; ``.kiro/specs/office-person-detection/design.md:646-653``)."""
+    def _detect_chunk(self, chunk: Sequence[np.ndarray], floor_map, handle: Optional[int] = None):
+        """(detections per frame, whether their floor fields are filled) of one ``max_batch`` chunk."""
+        if floor_map is None:
+            return self._postprocess_batch(*self._detect_records(chunk, handle)), True
+        recs, counts, Q, floor = self._detect_records_floor(chunk, floor_map, handle)
+        return self._postprocess_batch(recs, counts, Q, floor, floor_map), floor is not None
+
+    def detect_batch(self, frames: List[np.ndarray], floor_map=None) -> List[List[Detection]]:
+        """Batched detection (deleted vit_detector.py 508-550; ``.kiro/specs/office-person-detection/design.md:646-653``).
+        ``floor_map``: a ``HipFloorMapper``; the detections come back with ``floor_coords``, ``floor_coords_mm``, ``camera_coords`` and
+        ``zone_ids`` filled as the reference's Phase 3 fills them: inside the detect call where the chunk goes down as a list of host
+        frames, by ``floor_map.apply`` afterwards where it does not (ragged or pre-resized batches)."""
         self._require_model()
         if len(frames) == 0:
             return []
         try:
             chunks = [frames[i:i + self.max_batch] for i in range(0, len(frames), self.max_batch)]
             if len(self._handles) > 1 and len(chunks) > 1:
-                return self._detect_chunks_overlapped(chunks)
+                return self._detect_chunks_overlapped(chunks, floor_map)
             out: List[List[Detection]] = []
             for chunk in chunks:
-                recs, counts, Q = self._detect_records(chunk)
-                out.extend(self._postprocess_batch(recs, counts, Q))
+                dets, filled = self._detect_chunk(chunk, floor_map)
+                if not filled:
+                    for d in dets:
+                        floor_map.apply(d)
+                out.extend(dets)
             return out
         except Exception as e:
             logger.error(f"Detection failed: {e}")
             raise
 
-    def _detect_chunks_overlapped(self, chunks: List[List[np.ndarray]]) -> List[List[Detection]]:
+    def _detect_chunks_overlapped(self, chunks: List[List[np.ndarray]], floor_map=None) -> List[List[Detection]]:
         """Chunk k runs on handle ``k % streams``; one worker thread per handle drives its chunks in order.
 
         The C-ABI calls release the GIL and every handle owns its stream, so host preprocessing, uploads and the
@@ -428,23 +462,29 @@ class HipDetrDetector:
         """
         n = len(self._handles)
         results: List[Optional[List[List[Detection]]]] = [None] * len(chunks)
+        filled = [True] * len(chunks)
 
         def worker(j: int) -> None:
             for k in range(j, len(chunks), n):
-                recs, counts, Q = self._detect_records(chunks[k], self._handles[j])
-                results[k] = self._postprocess_batch(recs, counts, Q)
+                results[k], filled[k] = self._detect_chunk(chunks[k], floor_map, self._handles[j])
 
         with ThreadPoolExecutor(max_workers=n) as pool:
             for fut in [pool.submit(worker, j) for j in range(min(n, len(chunks)))]:
                 fut.result()
+        for k, r in enumerate(results):   # (the mapper's own calls use ONE stream and staging buffer: made here, by one thread)
+            if not filled[k]:
+                for dets in r:
+                    floor_map.apply(dets)
         return [dets for r in results for dets in r]
 
-    def detect(self, frame: np.ndarray) -> List[Detection]:
-        """Single-frame detection (``yolov8_detector.py:90-132``)."""
+    def detect(self, frame: np.ndarray, floor_map=None) -> List[Detection]:
+        """Single-frame detection (``yolov8_detector.py:90-132``); ``floor_map``: see ``detect_batch``."""
         self._require_model()
         try:
-            recs, counts, Q = self._detect_records([frame])
-            dets = self._postprocess_batch(recs, counts, Q)[0]
+            dets, filled = self._detect_chunk([frame], floor_map)
+            dets = dets[0]
+            if not filled:
+                floor_map.apply(dets)
             logger.debug(f"Detected {len(dets)} persons")
             return dets
         except Exception as e:
