@@ -14,14 +14,6 @@ namespace opd {
 static inline bool pixels_on_device(int mem_kind) { return mem_kind == OPD_MEM_DEVICE; }
 static inline bool outputs_on_device(int mem_kind) { return mem_kind != OPD_MEM_HOST; }
 
-// A pointer that kernels will dereference must be memory the HIP runtime knows as device-accessible (device, page-locked host or managed):
-// an ordinary host pointer handed over with a DEVICE mem_kind would make a kernel fault the GPU -- for every process on it -- instead of
-// returning an error (hipPointerGetAttributes: 0.06 us per call).
-static bool device_accessible(const void* p) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged;
-}
 static int check_device_outputs(int mem_kind, const void* out, const void* counts, const char* who) {
     if (!outputs_on_device(mem_kind)) return OPD_OK;
     if (!device_accessible(out) || !device_accessible(counts))
@@ -66,21 +58,13 @@ static int enqueue_resize(opd_detr* m, const uint8_t* frames, int mem_kind, int 
     const size_t need = (size_t)B * h * w * 3;
     const uint8_t* d_in = frames;
     if (!pixels_on_device(mem_kind)) {
-        if (need > m->src_bytes) {
-            HIPCHK(hipStreamSynchronize(m->stream));
-            if (m->d_src) (void)hipFree(m->d_src);
-            m->d_src = nullptr; m->src_bytes = 0;
-            void* q = nullptr;
-            if (hipMalloc(&q, need) != hipSuccess) return fail(OPD_ENOMEM, "source frame staging allocation failed");
-            m->d_src = reinterpret_cast<uint8_t*>(q);
-            m->src_bytes = need;
-        }
+        RCCHK(m->src.reserve("source frames", 0, need, m->stream));
         if (list) {
-            for (int b = 0; b < B; ++b) HIPCHK(hipMemcpyAsync(m->d_src + (size_t)b * h * w * 3, list[b], (size_t)h * w * 3, hipMemcpyHostToDevice, m->stream));
+            for (int b = 0; b < B; ++b) HIPCHK(hipMemcpyAsync(m->src.dev + (size_t)b * h * w * 3, list[b], (size_t)h * w * 3, hipMemcpyHostToDevice, m->stream));
         } else {
-            HIPCHK(hipMemcpyAsync(m->d_src, frames, need, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(m->src.dev, frames, need, hipMemcpyHostToDevice, m->stream));
         }
-        d_in = m->d_src;
+        d_in = m->src.dev;
     }
     const opd_detr::ResizeTab* tab = nullptr;
     for (const auto& t : m->resize_tabs)
@@ -116,7 +100,7 @@ static int stage_frames(opd_detr* m, const FrameSource& src, int B, int H, int W
         return OPD_OK;
     }
     RCCHK(enqueue_resize(m, block, src.mem_kind, B, src.h, src.w, H, W, list));
-    *d_camera = pixels_on_device(src.mem_kind) ? block : m->d_src;
+    *d_camera = pixels_on_device(src.mem_kind) ? block : m->src.dev;
     return OPD_OK;
 }
 
@@ -273,21 +257,6 @@ static void drop_streams(opd_detr* m) {
     m->ev_fork = m->ev_join = nullptr; m->stream2 = m->stream = nullptr;
 }
 
-// No C++ exception may cross the C-ABI: creation parses an untrusted file and allocates, so its body runs under a catch-all.
-template <typename F>
-static int guarded(const char* what, F&& body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        return fail(OPD_ENOMEM, std::string(what) + ": out of host memory");
-    } catch (const std::out_of_range& e) {
-        return fail(OPD_ESCHEMA, std::string(what) + ": weight file lacks a tensor the model needs (" + e.what() + ")");
-    } catch (const std::exception& e) {
-        return fail(OPD_EINVAL, std::string(what) + ": " + e.what());
-    } catch (...) {
-        return fail(OPD_EINVAL, std::string(what) + ": unknown C++ exception");
-    }
-}
 // The forward-plan switches: defaults, overridden by environment variables (A/B switches for benchmarking and ablations)
 static Switches read_switches(int flags) {
     Switches sw;
@@ -366,10 +335,7 @@ static int create_impl(const opd_config* cfg, const char* weights_path, int devi
     m->dtype = (cfg->flags & OPD_FLAG_BF16) ? OPD_DT_BF16 : OPD_DT_F16;
     m->sw = read_switches(cfg->flags);
     m->device = device_ordinal;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(OPD_EHIP, "no HIP device visible (this library has no CPU fallback)");
-    if (device_ordinal < 0 || device_ordinal >= ndev) return fail(OPD_EINVAL, "device_ordinal out of range");
+    RCCHK(use_device("opd_detr_create", device_ordinal, "device_ordinal out of range"));
     return open_handle(std::move(m), &sd, out);
 }
 
@@ -404,7 +370,7 @@ void opd_detr_destroy(opd_detr* m) {
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     comm_detach_all(m);   // communicator lanes bound to this handle refuse work from here on (their own destroy still frees them)
     for (void* p : m->allocs) (void)hipFree(p);
-    if (m->d_src) (void)hipFree(m->d_src);
+    m->src.release();
     for (auto& e : m->ev_async)
         if (e) (void)hipEventDestroy(e);
     for (auto& a : m->async_host)
@@ -610,30 +576,14 @@ int opd_similarity_matrix(int device_ordinal, const float* feats1, const float* 
     if (!boxes1 || !boxes2 || !out) return fail(OPD_EINVAL, "opd_similarity_matrix: null boxes / output");
     if (fabs(appearance_weight + motion_weight - 1.0) > 1e-6)
         return fail(OPD_EINVAL, "appearance_weight + motion_weight must equal 1.0");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(OPD_EHIP, "no HIP device visible (this library has no CPU fallback)");
-    HIPCHK(hipSetDevice(device_ordinal));
-    struct Tmp {
-        std::vector<void*> p;
-        ~Tmp() { for (void* q : p) (void)hipFree(q); }
-    } tmp;
-    auto up = [&](const void* h, size_t bytes, void** d) -> int {
-        *d = nullptr;
-        if (!h) return OPD_OK;
-        if (hipMalloc(d, bytes) != hipSuccess) return fail(OPD_ENOMEM, "opd_similarity_matrix: device allocation failed");
-        tmp.p.push_back(*d);
-        HIPCHK(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
-        return OPD_OK;
-    };
-    void *df1, *df2, *db1, *db2, *dh1, *dh2, *dout = nullptr;
-    RCCHK(up(feats1, (size_t)n1 * D * 4, &df1)); RCCHK(up(feats2, (size_t)n2 * D * 4, &df2));
-    RCCHK(up(boxes1, (size_t)n1 * 16, &db1)); RCCHK(up(boxes2, (size_t)n2 * 16, &db2));
-    RCCHK(up(has1, (size_t)n1, &dh1)); RCCHK(up(has2, (size_t)n2, &dh2));
-    if (hipMalloc(&dout, (size_t)n1 * n2 * 4) != hipSuccess) return fail(OPD_ENOMEM, "opd_similarity_matrix: device allocation failed");
-    tmp.p.push_back(dout);
-    HIPCHK(opd_launch_similarity_matrix((const float*)df1, (const float*)db1, (const uint8_t*)dh1, n1, (const float*)df2, (const float*)db2,
-                                        (const uint8_t*)dh2, n2, D, appearance_weight, motion_weight, as_distance,
-                                        (float*)dout, nullptr));
+    RCCHK(use_device("opd_similarity_matrix", device_ordinal));
+    DevMem tmp;
+    auto up = [&](auto* h, size_t count) { return h ? tmp.up(h, count) : nullptr; };   // (features and flags are optional)
+    const float *df1 = up(feats1, (size_t)n1 * D), *df2 = up(feats2, (size_t)n2 * D), *db1 = up(boxes1, (size_t)n1 * 4), *db2 = up(boxes2, (size_t)n2 * 4);
+    const uint8_t *dh1 = up(has1, (size_t)n1), *dh2 = up(has2, (size_t)n2);
+    float* dout = tmp.alloc<float>((size_t)n1 * n2);
+    if (!tmp.ok) return fail(OPD_ENOMEM, "opd_similarity_matrix: device allocation failed");
+    HIPCHK(opd_launch_similarity_matrix(df1, db1, dh1, n1, df2, db2, dh2, n2, D, appearance_weight, motion_weight, as_distance, dout, nullptr));
     HIPCHK(hipMemcpy(out, dout, (size_t)n1 * n2 * 4, hipMemcpyDeviceToHost));
     return OPD_OK;
 }

@@ -9,7 +9,8 @@
 #include <string>
 #include <vector>
 
-#include "opd_model.h"
+#include "opd_device.h"
+#include "opd_kernels.h"
 
 using namespace opd;
 
@@ -18,38 +19,9 @@ namespace {
 struct ColorScratch {
     std::mutex mu;   // one call at a time per device
     hipStream_t stream = nullptr;
-    unsigned char* h_up = nullptr;
-    unsigned char* d_buf = nullptr;
-    size_t h_cap = 0, d_cap = 0;
+    Staging io;      // up: [descriptors | pixels]; the device side holds the accumulators and the output behind them
 };
 ColorScratch g_scratch[16];   // one node: <= 16 GPUs
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-int ensure(ColorScratch& s, size_t up_bytes, size_t dev_bytes) {
-    if (!s.stream) HIPCHK(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    if (up_bytes > s.h_cap) {
-        if (s.h_up) (void)hipHostFree(s.h_up);
-        s.h_up = nullptr; s.h_cap = 0;
-        const size_t cap = std::max(up_bytes, (size_t)1 << 16);
-        HIPCHK(hipHostMalloc((void**)&s.h_up, cap, hipHostMallocDefault));
-        s.h_cap = cap;
-    }
-    if (dev_bytes > s.d_cap) {
-        if (s.d_buf) (void)hipFree(s.d_buf);
-        s.d_buf = nullptr; s.d_cap = 0;
-        const size_t cap = std::max(dev_bytes, (size_t)1 << 16);
-        if (hipMalloc((void**)&s.d_buf, cap) != hipSuccess) { (void)hipGetLastError(); return fail(OPD_ENOMEM, "opd_color_features: device allocation failed"); }
-        s.d_cap = cap;
-    }
-    return OPD_OK;
-}
-
-bool device_accessible(const void* p) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged;
-}
 
 }  // namespace
 
@@ -87,10 +59,8 @@ extern "C" int opd_color_features(int device_ordinal, const uint8_t* const* fram
         window_bytes += align_up((size_t)p.h * p.w * 3, 16);
         max_rows = std::max(max_rows, p.h);
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(OPD_EHIP, "no HIP device visible (this library has no CPU fallback)");
-    if (device_ordinal < 0 || device_ordinal >= ndev || device_ordinal >= 16) return fail(OPD_EINVAL, "opd_color_features: no device " + std::to_string(device_ordinal));
-    HIPCHK(hipSetDevice(device_ordinal));
+    RCCHK(use_device("opd_color_features", device_ordinal));
+    if (device_ordinal >= 16) return fail(OPD_EINVAL, "opd_color_features: no device " + std::to_string(device_ordinal));   // (g_scratch)
     if (mem_kind == OPD_MEM_DEVICE)
         for (int f = 0; f < n_frames; ++f)
             if (named[f] && !device_accessible(frames[f]))
@@ -106,16 +76,18 @@ extern "C" int opd_color_features(int device_ordinal, const uint8_t* const* fram
     const size_t acc_off = align_up(up_bytes, 256), out_off = acc_off + align_up((size_t)n_boxes * OPD_COLOR_ACC_WORDS * 4, 256);
     ColorScratch& s = g_scratch[device_ordinal];
     std::lock_guard<std::mutex> guard(s.mu);
-    RCCHK(ensure(s, up_bytes, out_off + (size_t)n_boxes * OPD_COLOR_DIM * 4));
-    ColorCrop* desc = reinterpret_cast<ColorCrop*>(s.h_up);
+    if (!s.stream) HIPCHK(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    const size_t floor_bytes = (size_t)1 << 16;   // what the first call allocates at least
+    RCCHK(s.io.reserve("opd_color_features", std::max(up_bytes, floor_bytes), std::max(out_off + (size_t)n_boxes * OPD_COLOR_DIM * 4, floor_bytes), s.stream));
+    ColorCrop* desc = reinterpret_cast<ColorCrop*>(s.io.host);
     if (whole)
         for (int f = 0; f < n_frames; ++f)
-            if (named[f]) memcpy(s.h_up + frame_off[f], frames[f], (size_t)frame_hw[2 * f] * frame_hw[2 * f + 1] * 3);
+            if (named[f]) memcpy(s.io.host + frame_off[f], frames[f], (size_t)frame_hw[2 * f] * frame_hw[2 * f + 1] * 3);
     size_t woff = desc_bytes;
     for (int i = 0; i < n_boxes; ++i) {
         const Plan& p = plan[i];
         ColorCrop& c = desc[i];
-        c.src = s.d_buf;
+        c.src = s.io.dev;
         c.pitch = 0;
         c.w = p.w; c.h = p.h;
         c.row = i;
@@ -126,22 +98,22 @@ extern "C" int opd_color_features(int device_ordinal, const uint8_t* const* fram
             c.src = frames[p.f] + start;
             c.pitch = 3 * W;
         } else if (whole) {
-            c.src = s.d_buf + frame_off[p.f] + start;
+            c.src = s.io.dev + frame_off[p.f] + start;
             c.pitch = 3 * W;
         } else {
             const size_t rowb = (size_t)p.w * 3;
-            for (int y = 0; y < p.h; ++y) memcpy(s.h_up + woff + (size_t)y * rowb, frames[p.f] + start + (size_t)y * W * 3, rowb);
-            c.src = s.d_buf + woff;
+            for (int y = 0; y < p.h; ++y) memcpy(s.io.host + woff + (size_t)y * rowb, frames[p.f] + start + (size_t)y * W * 3, rowb);
+            c.src = s.io.dev + woff;
             c.pitch = (int32_t)rowb;
             woff += align_up((size_t)p.h * rowb, 16);
         }
     }
-    HIPCHK(hipMemcpyAsync(s.d_buf, s.h_up, up_bytes, hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(s.io.dev, s.io.host, up_bytes, hipMemcpyHostToDevice, s.stream));
     ColorParams cp{};
-    cp.crops = reinterpret_cast<const ColorCrop*>(s.d_buf);
+    cp.crops = reinterpret_cast<const ColorCrop*>(s.io.dev);
     cp.n = n_boxes;
-    cp.acc = reinterpret_cast<uint32_t*>(s.d_buf + acc_off);
-    cp.out = reinterpret_cast<float*>(s.d_buf + out_off);
+    cp.acc = reinterpret_cast<uint32_t*>(s.io.dev + acc_off);
+    cp.out = reinterpret_cast<float*>(s.io.dev + out_off);
     // row spans per crop: about 16 rows each, so that a frame-sized crop spreads over the CUs (the result does not depend on it)
     HIPCHK(opd_launch_color_features(cp, std::min(64, (max_rows + 15) / 16), s.stream));
     HIPCHK(hipMemcpyAsync(out, cp.out, (size_t)n_boxes * OPD_COLOR_DIM * 4, hipMemcpyDeviceToHost, s.stream));

@@ -6,11 +6,12 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <numeric>
 #include <string>
 
 #include "opd_floor.h"
-#include "opd_model.h"
+#include "opd_kernels.h"
 
 #pragma clang fp contract(off)
 
@@ -18,44 +19,22 @@ using namespace opd;
 
 namespace {
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-bool device_accessible(const void* p) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged;
-}
-
 const size_t IN_BYTES = 16;   // per record: four float32 or two float64
-
-// d_io / h_pin for n records: [n inputs of 16 bytes | n results]
-int reserve(opd_floor* f, int n) {
-    if ((size_t)n <= f->cap) return OPD_OK;
-    HIPCHK(hipStreamSynchronize(f->stream));
-    if (f->d_io) (void)hipFree(f->d_io);
-    if (f->h_pin) (void)hipHostFree(f->h_pin);
-    f->d_io = f->h_pin = nullptr;
-    f->cap = 0;
-    const size_t cap = std::max<size_t>(256, align_up((size_t)n, 256));
-    const size_t bytes = cap * (IN_BYTES + sizeof(opd_floor_rec));
-    if (hipMalloc((void**)&f->d_io, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(OPD_ENOMEM, "opd_floor: staging allocation failed"); }
-    if (hipHostMalloc((void**)&f->h_pin, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(OPD_ENOMEM, "opd_floor: page-locked allocation failed"); }
-    f->cap = cap;
-    return OPD_OK;
-}
 
 // upload `in_bytes` of inputs (host; null: the kernel reads the caller's device memory), launch, download `out_bytes` per record, wait
 int run(opd_floor* f, FloorParams& p, const void* host_in, size_t out_each, void* host_out) {
     const int n = p.n;
     HIPCHK(hipSetDevice(f->device));
-    RCCHK(reserve(f, n));
-    uint8_t* d_out = f->d_io + f->cap * IN_BYTES;
-    uint8_t* h_out = f->h_pin + f->cap * IN_BYTES;
+    const size_t each = IN_BYTES + sizeof(opd_floor_rec), bytes = align_up((size_t)n, 256) * each;
+    RCCHK(f->io.reserve("opd_floor", bytes, bytes, f->stream));   // whole blocks of 256 records: [inputs of 16 bytes | results]
+    const size_t cap = f->io.dev_cap / each;
+    uint8_t* d_out = f->io.dev + cap * IN_BYTES;
+    uint8_t* h_out = f->io.host + cap * IN_BYTES;
     if (host_in) {
-        memcpy(f->h_pin, host_in, (size_t)n * IN_BYTES);
-        HIPCHK(hipMemcpyAsync(f->d_io, f->h_pin, (size_t)n * IN_BYTES, hipMemcpyHostToDevice, f->stream));
-        p.boxes = reinterpret_cast<const float*>(f->d_io);
-        p.pts = reinterpret_cast<const double*>(f->d_io);
+        memcpy(f->io.host, host_in, (size_t)n * IN_BYTES);
+        HIPCHK(hipMemcpyAsync(f->io.dev, f->io.host, (size_t)n * IN_BYTES, hipMemcpyHostToDevice, f->stream));
+        p.boxes = reinterpret_cast<const float*>(f->io.dev);
+        p.pts = reinterpret_cast<const double*>(f->io.dev);
     }
     p.m = f->model;
     p.out = reinterpret_cast<opd_floor_rec*>(d_out);
@@ -163,11 +142,8 @@ extern "C" int opd_floor_create(const opd_floor_config* cfg, int device_ordinal,
     const opd_floor_config& c = *cfg;
     FloorTables t;
     floor_build_tables(c, &t);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(OPD_EHIP, "no HIP device visible (this library has no CPU fallback)");
-    if (device_ordinal < 0 || device_ordinal >= ndev) return fail(OPD_EINVAL, "opd_floor_create: no device " + std::to_string(device_ordinal));
-    HIPCHK(hipSetDevice(device_ordinal));
-    opd_floor* f = new opd_floor();
+    RCCHK(use_device("opd_floor_create", device_ordinal));
+    std::unique_ptr<opd_floor, decltype(&opd_floor_destroy)> f(new opd_floor(), opd_floor_destroy);   // a failure below releases whatever was already made
     f->device = device_ordinal;
     FloorModel& m = f->model;
     m.method = c.method;
@@ -194,14 +170,9 @@ extern "C" int opd_floor_create(const opd_floor_config* cfg, int device_ordinal,
     put(o_pts, t.points.data(), t.points.size() * 8); put(o_tri, t.tri.data(), t.tri.size() * 8); put(o_aff, t.affine.data(), t.affine.size() * 8);
     put(o_w, t.tps_w.data(), t.tps_w.size() * 8); put(o_edge, t.edges.data(), t.edges.size() * 8);
     put(o_ez, t.edge_zone.data(), t.edge_zone.size() * 4); put(o_rank, t.zone_rank.data(), t.zone_rank.size() * 4);
-    int rc = OPD_OK;
-    auto hip = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == OPD_OK) { (void)hipGetLastError(); rc = fail(OPD_ENOMEM, std::string("opd_floor_create: ") + what + " failed: " + hipGetErrorString(e)); }
-    };
-    hip(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking), "stream creation");
-    if (rc == OPD_OK) hip(hipMalloc((void**)&f->d_model, image.size()), "model allocation");
-    if (rc == OPD_OK) hip(hipMemcpy(f->d_model, image.data(), image.size(), hipMemcpyHostToDevice), "model upload");
-    if (rc != OPD_OK) { opd_floor_destroy(f); return rc; }
+    RCCHK(made("opd_floor_create", "stream creation", hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking)));
+    RCCHK(made("opd_floor_create", "model allocation", hipMalloc((void**)&f->d_model, image.size())));
+    RCCHK(made("opd_floor_create", "model upload", hipMemcpy(f->d_model, image.data(), image.size(), hipMemcpyHostToDevice)));
     m.points = reinterpret_cast<const double*>(f->d_model + o_pts);
     m.tri = reinterpret_cast<const double*>(f->d_model + o_tri);
     m.affine = reinterpret_cast<const double*>(f->d_model + o_aff);
@@ -209,7 +180,7 @@ extern "C" int opd_floor_create(const opd_floor_config* cfg, int device_ordinal,
     m.edges = reinterpret_cast<const double*>(f->d_model + o_edge);
     m.edge_zone = reinterpret_cast<const int32_t*>(f->d_model + o_ez);
     m.zone_rank = reinterpret_cast<const int32_t*>(f->d_model + o_rank);
-    *out = f;
+    *out = f.release();
     return OPD_OK;
 }
 
@@ -219,8 +190,7 @@ extern "C" void opd_floor_destroy(opd_floor* f) {
     (void)hipSetDevice(f->device);
     if (f->stream) { (void)hipStreamSynchronize(f->stream); (void)hipStreamDestroy(f->stream); }
     if (f->d_model) (void)hipFree(f->d_model);
-    if (f->d_io) (void)hipFree(f->d_io);
-    if (f->h_pin) (void)hipHostFree(f->h_pin);
+    f->io.release();
     delete f;
 }
 

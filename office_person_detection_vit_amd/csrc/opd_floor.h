@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/opd_detr.h"
+#include "opd_device.h"
 
 enum { FLOOR_TRI_LD = 8, FLOOR_AFF_LD = 6, FLOOR_EDGE_LD = 4 };
 
@@ -56,7 +56,5 @@ struct opd_floor {
     int device = 0;
     hipStream_t stream = nullptr;
     uint8_t* d_model = nullptr;       // the tables
-    uint8_t* d_io = nullptr;          // [inputs | results], grown on demand
-    uint8_t* h_pin = nullptr;         // page-locked image of the same
-    size_t cap = 0;                   // records d_io / h_pin hold
+    opd::Staging io;                  // [inputs | results] on the device and its page-locked image, grown on demand
 };

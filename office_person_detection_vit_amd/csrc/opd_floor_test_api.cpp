@@ -2,7 +2,6 @@
 #include <string.h>
 
 #include "opd_floor.h"
-#include "opd_model.h"
 
 using namespace opd;
 

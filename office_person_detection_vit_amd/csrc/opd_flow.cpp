@@ -4,22 +4,15 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 
 #include "opd_flow.h"
-#include "opd_model.h"
+#include "opd_kernels.h"
 
 using namespace opd;
 
 namespace {
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-bool device_accessible(const void* p) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged;
-}
 
 // the effective top level: the largest l <= max_level with every level 1 .. l wider and taller than the window
 int plan_levels(int h, int w, int win, int max_level, int* lh, int* lw, int* lp) {
@@ -53,12 +46,12 @@ int check_frame(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, 
 // staging image and a host frame (behind the points region) travel as two copies of exactly their bytes on the same stream.
 int enqueue_pyramid(opd_flow* f, int which, const uint8_t* bgr, int mem_kind, int h, int w, size_t pts_bytes) {
     const uint8_t* d_bgr = bgr;
-    if (pts_bytes) HIPCHK(hipMemcpyAsync(f->d_io, f->h_pin, pts_bytes, hipMemcpyHostToDevice, f->stream));
+    if (pts_bytes) HIPCHK(hipMemcpyAsync(f->io.dev, f->io.host, pts_bytes, hipMemcpyHostToDevice, f->stream));
     if (mem_kind == OPD_MEM_HOST) {
         const size_t bytes = (size_t)h * w * 3;
-        memcpy(f->h_pin + f->frame_off, bgr, bytes);
-        d_bgr = f->d_io + f->frame_off;
-        HIPCHK(hipMemcpyAsync(f->d_io + f->frame_off, f->h_pin + f->frame_off, bytes, hipMemcpyHostToDevice, f->stream));
+        memcpy(f->io.host + f->frame_off, bgr, bytes);
+        d_bgr = f->io.dev + f->frame_off;
+        HIPCHK(hipMemcpyAsync(f->io.dev + f->frame_off, f->io.host + f->frame_off, bytes, hipMemcpyHostToDevice, f->stream));
     }
     const FlowPyramid& p = f->pyr[which];
     HIPCHK(opd_launch_flow_gray(d_bgr, p.base + p.off[0], h, w, f->lp[0], f->stream));
@@ -86,11 +79,8 @@ extern "C" int opd_flow_create(const opd_flow_config* cfg, int device_ordinal, o
     if (c.max_level < 0 || c.max_level >= OPD_FLOW_MAX_LEVELS) return fail(OPD_EINVAL, "opd_flow_create: max_level must lie in 0 .. 7");
     if (c.max_iter < 1 || c.max_iter > 1000) return fail(OPD_EINVAL, "opd_flow_create: max_iter must lie in 1 .. 1000");
     if (!(c.min_eig_threshold > 0.f)) return fail(OPD_EINVAL, "opd_flow_create: min_eig_threshold must be positive");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(OPD_EHIP, "no HIP device visible (this library has no CPU fallback)");
-    if (device_ordinal < 0 || device_ordinal >= ndev) return fail(OPD_EINVAL, "opd_flow_create: no device " + std::to_string(device_ordinal));
-    HIPCHK(hipSetDevice(device_ordinal));
-    opd_flow* f = new opd_flow();
+    RCCHK(use_device("opd_flow_create", device_ordinal));
+    std::unique_ptr<opd_flow, decltype(&opd_flow_destroy)> f(new opd_flow(), opd_flow_destroy);   // a failure below releases whatever was already made
     f->cfg = c;
     f->device = device_ordinal;
     // the largest pyramid: level sizes fall with the frame size, so offsets planned for max_h x max_w hold every smaller frame
@@ -106,20 +96,14 @@ extern "C" int opd_flow_create(const opd_flow_config* cfg, int device_ordinal, o
     f->pts_bytes = align_up((size_t)c.max_points * 8, 256);
     f->frame_off = f->pts_bytes;
     f->out_off = f->frame_off + align_up((size_t)c.max_h * c.max_w * 3, 256);
-    f->io_bytes = f->out_off + align_up((size_t)c.max_points * 9, 256);
-    int rc = OPD_OK;
-    auto hip = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == OPD_OK) { (void)hipGetLastError(); rc = fail(OPD_ENOMEM, std::string("opd_flow_create: ") + what + " failed: " + hipGetErrorString(e)); }
-    };
-    hip(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking), "stream creation");
-    for (int k = 0; k < 2 && rc == OPD_OK; ++k) {
-        hip(hipMalloc((void**)&f->pyr[k].base, bytes), "pyramid allocation");
+    const size_t io_bytes = f->out_off + align_up((size_t)c.max_points * 9, 256);
+    RCCHK(made("opd_flow_create", "stream creation", hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking)));
+    for (int k = 0; k < 2; ++k) {
+        RCCHK(made("opd_flow_create", "pyramid allocation", hipMalloc((void**)&f->pyr[k].base, bytes)));
         memcpy(f->pyr[k].off, off, sizeof off);
     }
-    if (rc == OPD_OK) hip(hipMalloc((void**)&f->d_io, f->io_bytes), "staging allocation");
-    if (rc == OPD_OK) hip(hipHostMalloc((void**)&f->h_pin, f->io_bytes, hipHostMallocDefault), "page-locked allocation");
-    if (rc != OPD_OK) { opd_flow_destroy(f); return rc; }
-    *out = f;
+    RCCHK(f->io.reserve("opd_flow_create", io_bytes, io_bytes, f->stream));   // sized once: the handle's maxima bound every call
+    *out = f.release();
     return OPD_OK;
 }
 
@@ -129,8 +113,7 @@ extern "C" void opd_flow_destroy(opd_flow* f) {
     (void)hipSetDevice(f->device);
     if (f->stream) { (void)hipStreamSynchronize(f->stream); (void)hipStreamDestroy(f->stream); }
     for (int k = 0; k < 2; ++k) if (f->pyr[k].base) (void)hipFree(f->pyr[k].base);
-    if (f->d_io) (void)hipFree(f->d_io);
-    if (f->h_pin) (void)hipHostFree(f->h_pin);
+    f->io.release();
     delete f;
 }
 
@@ -162,7 +145,7 @@ extern "C" int opd_flow_track(opd_flow* f, const uint8_t* bgr, int mem_kind, int
     const int cur = 1 - f->ref;
     f->other_valid = false;
     const size_t pts_bytes = (size_t)n * 8;
-    if (n) memcpy(f->h_pin, pts_xy, pts_bytes);
+    if (n) memcpy(f->io.host, pts_xy, pts_bytes);
     RCCHK(enqueue_pyramid(f, cur, bgr, mem_kind, h, w, pts_bytes));
     if (n) {
         FlowParams p{};
@@ -174,16 +157,16 @@ extern "C" int opd_flow_track(opd_flow* f, const uint8_t* bgr, int mem_kind, int
         p.max_iter = f->cfg.max_iter;
         p.eps2 = f->cfg.epsilon < 0.f ? -1.f : f->cfg.epsilon * f->cfg.epsilon;
         p.min_eig = f->cfg.min_eig_threshold;
-        p.pts = reinterpret_cast<const float*>(f->d_io);
-        p.next = reinterpret_cast<float*>(f->d_io + f->out_off);
-        p.status = f->d_io + f->out_off + pts_bytes;
+        p.pts = reinterpret_cast<const float*>(f->io.dev);
+        p.next = reinterpret_cast<float*>(f->io.dev + f->out_off);
+        p.status = f->io.dev + f->out_off + pts_bytes;
         HIPCHK(opd_launch_flow_lk(p, f->stream));
-        HIPCHK(hipMemcpyAsync(f->h_pin + f->out_off, f->d_io + f->out_off, pts_bytes + (size_t)n, hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(hipMemcpyAsync(f->io.host + f->out_off, f->io.dev + f->out_off, pts_bytes + (size_t)n, hipMemcpyDeviceToHost, f->stream));
     }
     HIPCHK(hipStreamSynchronize(f->stream));
     if (n) {
-        memcpy(next_xy, f->h_pin + f->out_off, pts_bytes);
-        memcpy(status, f->h_pin + f->out_off + pts_bytes, (size_t)n);
+        memcpy(next_xy, f->io.host + f->out_off, pts_bytes);
+        memcpy(status, f->io.host + f->out_off + pts_bytes, (size_t)n);
     }
     f->ref = cur;   // the frame just seen is the reference of the next call
     f->other_valid = true;

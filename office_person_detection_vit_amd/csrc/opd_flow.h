@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/opd_detr.h"
+#include "opd_device.h"
 
 enum { OPD_FLOW_MAX_LEVELS = 8, OPD_FLOW_MAX_WIN = 21 };   // pyramid levels incl. level 0; the LK kernel's LDS and registers are sized for a 21 x 21 window
 
@@ -44,7 +44,6 @@ struct opd_flow {
     bool has_ref = false, other_valid = false; // other_valid: pyr[1 - ref] holds the frame the reference replaced
     int h = 0, w = 0, top = 0;                 // geometry of the reference (and of pyr[1 - ref] when other_valid)
     int lw[OPD_FLOW_MAX_LEVELS] = {}, lh[OPD_FLOW_MAX_LEVELS] = {}, lp[OPD_FLOW_MAX_LEVELS] = {};
-    uint8_t* h_pin = nullptr;                  // page-locked: [points | frame] up, [next | status] down
-    uint8_t* d_io = nullptr;                   // device image of the same: [points | frame] and, behind it, [next | status]
-    size_t pts_bytes = 0, frame_off = 0, out_off = 0, io_bytes = 0;
+    opd::Staging io;                           // page-locked: [points | frame] up, [next | status] down; device: [points | frame] and, behind it, [next | status]
+    size_t pts_bytes = 0, frame_off = 0, out_off = 0;
 };

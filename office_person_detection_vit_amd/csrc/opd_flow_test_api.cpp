@@ -2,7 +2,6 @@
 #include <string>
 
 #include "opd_flow.h"
-#include "opd_model.h"
 
 using namespace opd;
 

@@ -1238,7 +1238,7 @@ int run_forward(opd_detr* m, const void* d_pixels, int pixel_format, int B, int 
         m->graphs.push_back({B, H, W, pixel_format, 0, 0, d_pixels, 0, nullptr, 0u});
         e = &m->graphs.back();
     }
-    if (e->exec && g_graph_guard.load() && e->epoch != g_handle_epoch.load()) {   // handles came or went since the capture: capture again (see g_handle_epoch)
+    if (e->exec && graph_stale(e->epoch)) {   // handles came or went since the capture: capture again (see g_handle_epoch)
         (void)hipGraphExecDestroy(e->exec);
         e->exec = nullptr;
         e->uses = 1;
@@ -1250,31 +1250,9 @@ int run_forward(opd_detr* m, const void* d_pixels, int pixel_format, int B, int 
         return OPD_OK;
     }
     if (e->uses++ == 0) return enqueue_forward(m, d_pixels, pixel_format, B, H, W);
-    hipGraph_t graph = nullptr;
-    int rc;
-    hipError_t ec;
-    {
-        CaptureExclusive alone;
-        HIPCHK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_forward(m, d_pixels, pixel_format, B, H, W);
-        ec = hipStreamEndCapture(m->stream, &graph);
-    }
-    if (rc != OPD_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    // A refused capture or instantiation is an ERROR of the call, not a reason to go on eagerly without saying so (round 3 did): the
-    // caller asked for the graph path, and a runtime that rejects the recorded launch sequence has a reason a caller should see.
-    if (ec != hipSuccess || !graph) {
-        e->uses = 1;   // (the next call tries again)
-        (void)hipGetLastError();
-        return fail(OPD_EHIP, std::string("hipStreamEndCapture refused the forward: ") + hipGetErrorString(ec) + " (OPD_FLAG_NO_GRAPH runs eagerly)");
-    }
     hipGraphExec_t exec = nullptr;
-    const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ei != hipSuccess) {
-        e->uses = 1;
-        (void)hipGetLastError();
-        return fail(OPD_EHIP, std::string("hipGraphInstantiate failed: ") + hipGetErrorString(ei) + " (OPD_FLAG_NO_GRAPH runs eagerly)");
-    }
+    const int rc = capture_graph(m->stream, "the forward", [&] { return enqueue_forward(m, d_pixels, pixel_format, B, H, W); }, &exec);
+    if (rc != OPD_OK) { e->uses = 1; return rc; }   // (the next call tries again)
     e->exec = exec; e->fh = m->last_fh; e->fw = m->last_fw; e->epoch = g_handle_epoch.load();
     HIPCHK(hipGraphLaunch(exec, m->stream));
     if (m->profiling == 2) { HIPCHK(hipEventRecord(m->ev[9], m->stream)); m->graph_marks = true; }

@@ -14,24 +14,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/opd_detr.h"
+#include "opd_device.h"
 #include "opd_kernels.h"
 #include "opd_loader.h"
-#include "opd_host.h"
-
-#define HIPCHK(expr)                                                                                           \
-    do {                                                                                                       \
-        hipError_t _e = (expr);                                                                                \
-        if (_e != hipSuccess)                                                                                  \
-            return opd::fail(OPD_EHIP, std::string(#expr) + " failed: " + hipGetErrorString(_e) + " (" + __FILE__ + \
-                                           ":" + std::to_string(__LINE__) + ")");                              \
-    } while (0)
-
-#define RCCHK(expr)            \
-    do {                       \
-        int _rc = (expr);      \
-        if (_rc != 0) return _rc; \
-    } while (0)
 
 namespace opd {
 
@@ -257,9 +242,8 @@ struct opd_detr : DetrWeights {
     opd_floor_rec* d_floor = nullptr;   // [max_batch][queries] floor records of opd_detr_detect_frames_floor (allocated, with its page-locked twin, by its first call)
     opd_floor_rec* h_floor = nullptr;
     float* d_feat_all = nullptr;   // [max_batch][queries][d_model] behind the counts in the d_records allocation: features of a batch's records (opd_detr_detect_frames_features)
-    // device-side resize (camera resolution -> model resolution): source staging (grown on demand) and coefficient tables
-    uint8_t* d_src = nullptr;
-    size_t src_bytes = 0;
+    // device-side resize (camera resolution -> model resolution): source staging (device side only, grown on demand) and coefficient tables
+    Staging src;
     struct ResizeTab { int h, w, oh, ow, ksh, ksv; int32_t *bh, *kh, *bv, *kv; };
     std::vector<ResizeTab> resize_tabs;
     float *d_amap = nullptr, *d_amap_stat = nullptr;   // opd_detr_attention_map: output [hw], row statistics
@@ -373,66 +357,5 @@ struct RecordSink {
 };
 int check_shape(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W);
 int detect_pipeline(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, const RecordSink& sink);
-
-// Stream capture and other threads: the Python shim drives several handles from worker threads (HipDetrDetector(streams=N)).
-// ROCm invalidates a capture in progress when ANOTHER thread allocates or frees memory, pins host memory or runs its
-// one-time eager setup meanwhile, even in thread-local capture mode ("operation failed due to a previous error during
-// capture").  Every entry point therefore holds this lock shared; a capture takes it exclusively for its few milliseconds.
-extern std::shared_mutex g_api_mu;
-// Handle churn and captured graphs.  Round 2 saw replays of a graph captured BEFORE another handle was destroyed and a third one
-// created give wrong (finite or NaN) outputs, while the same launches issued eagerly stayed bit-exact; re-capturing after every
-// handle creation / destruction (this epoch) made the symptom go away.  Round 3 went after the cause (profiles/r03_graph_churn_*.txt,
-// tools/graph_churn_probe.py, tools/fresh_box_probe.sh) and did NOT find one:
-//   * the round-2 binary with the guard patched out reproduced the corruption ONCE (first GPU process of a freshly acquired box) and
-//     then 0 times in 22 further runs, 17 of them as the first GPU process of a fresh container; HEAD with the guard off: 0 of 26;
-//   * per-launch checksum taps captured INTO the graph (opd_test_set_taps) never differed between capture run and replay;
-//   * with every device buffer pre-filled with 0x00 / 0xFF and fenced by 256-KiB red zones (opd_test_set_alloc_poison) outputs are
-//     bit-identical to an unpoisoned handle and every red zone stays intact, at HEAD and at the round-2 revision: no kernel reads
-//     memory it has not written or writes next to its buffers (tests/test_workloads_gpu.py keeps this under test);
-//   * foreign allocations between capture and replay (torch's caching allocator: 1 GiB of NaNs allocated, freed to the driver,
-//     re-allocated; an RCCL communicator created and destroyed), pinned or pageable staging, captured memset nodes: no effect.
-// Round 4 read the one bad log instead of provoking more (profiles/r03_graph_churn_bisect.txt: both replays of handle A after the churn
-// differ from before by the SAME 4.198907): the CPU oracle gives max |logits_A(probe frames) - logits_B(golden frames)| = 4.2078 for
-// handle B = the sharp-weights handle created during the churn, run on ITS frames -- equal to the recorded value within the fp16 noise
-// of the device logits (|dlogit| ~ 1e-2), and no other candidate comes close (A's weights on the capture-time frames: 2.48, B's weights on
-// A's frames: 3.34).  So the replay did not read stale weights, plans or pixels through A's baked pointers: A's caller got B's RESULTS,
-// i.e. A's output buffers held what B's eager forward had written and A's replay wrote nothing over them -- device memory handed to B
-// while A still owned it, or a dropped replay, below this library (every address baked into A's graph belongs to A or to A's weight
-// set; neither is freed while A lives; red zones and poison runs rule out this library's kernels writing outside their buffers).  Nothing
-// the capture code does wrong was found: launch errors inside a capture surface as the call's error (enqueue_forward's return code), and
-// since round 4 a refused capture / instantiation does too instead of falling back to eager launches silently.
-// Round 5 connected the log to round 4's own finding (counted waits that let register loads fly in front of LDS-DMA data prove nothing on this
-// hardware): tools/scan_dma_waits.py over the ISA of the revision that produced the bad log (f889722; profiles/r05_scan_dma_waits_round2_revision.txt)
-// finds 14 of its 20 barriers with LDS-DMA data in flight UNSOUND -- the first barrier of every fused-tail instantiation (six requests, then four
-// or eight bias loads, `vmcnt(4)` / `vmcnt(8)`), gemm_ln256_kernel, gemm_ln256_os_kernel, three of the FFN kernel -- all on the path of that
-// forward, and the one reproduction was the first GPU process of a freshly acquired box, i.e. cold requests, exactly when a request loses the
-// race against a younger load.  So that binary COULD compute on LDS bytes that had not landed; HEAD cannot (0 of 157 such barriers, both element
-// types, no kernel exempted; tests/test_isa_cpu.py).  What the scan does not explain is the VALUE: the same wrong number on two replays, equal to
-// handle B's result within fp16 noise -- stale LDS bytes would have to be B's tiles, left in the CUs' LDS by B's forward just before, which is
-// possible (LDS is not cleared between workgroups) but not shown.  Verdict: a sufficient mechanism existed at that revision and is gone; the
-// "below the HIP API" reading is no longer needed to explain the log, nor excluded by it.  The guard stays ON (it costs one re-capture per
-// handle creation / destruction, nothing per forward) and is no longer called load-bearing: the regression test
-// test_graph_replay_survives_foreign_allocations_and_handle_churn runs with the guard OFF at HEAD and passes (round-5 GPU suite).
-extern std::atomic<unsigned> g_handle_epoch;
-extern std::atomic<int> g_graph_guard;   // opd_test_set_graph_guard(0): leave stale-epoch graphs alone (diagnosis only)
-extern thread_local std::shared_lock<std::shared_mutex>* tl_api_lock;
-struct ApiScope {   // first statement of every HIP-calling entry point; entry points calling each other nest harmlessly
-    std::shared_lock<std::shared_mutex> lk;
-    bool outer;
-    ApiScope() : lk(g_api_mu, std::defer_lock), outer(tl_api_lock == nullptr) {
-        if (outer) { lk.lock(); tl_api_lock = &lk; }
-    }
-    ~ApiScope() { if (outer) tl_api_lock = nullptr; }
-};
-struct ApiUnlocked {   // a blocking host wait inside an entry point (an event of another rank's making): the shared hold is dropped meanwhile
-    std::shared_lock<std::shared_mutex>* s;
-    ApiUnlocked() : s(tl_api_lock && tl_api_lock->owns_lock() ? tl_api_lock : nullptr) { if (s) s->unlock(); }
-    ~ApiUnlocked() { if (s) s->lock(); }
-};
-struct CaptureExclusive {   // the calling thread's shared hold is handed back for the duration
-    std::shared_lock<std::shared_mutex>* s;
-    CaptureExclusive() : s(tl_api_lock) { if (s) s->unlock(); g_api_mu.lock(); }
-    ~CaptureExclusive() { g_api_mu.unlock(); if (s) s->lock(); }
-};
 
 }  // namespace opd

@@ -37,16 +37,17 @@ TAPI int opd_test_osnet_pixels_host(const uint8_t* frame, int H, int W, const fl
 // stem + max-pool: img [nb][256][128][4], w [147][64] fp16 bits, bias [64] -> out [nb][64][32][C0] fp16 bits
 TAPI int opd_test_osnet_stem(const uint16_t* img, const uint16_t* w, const float* bias, uint16_t* out, int nb, int C0) {
     ApiScope api_scope;
-    DevBuf di, dw, db, ds, dout;
-    RCCHK(up(di, img, (size_t)nb * OSNET_H * OSNET_W * 4 * 2));
-    RCCHK(up(dw, w, 147 * 64 * 2));
-    RCCHK(up(db, bias, 64 * 4));
-    RCCHK(up(ds, nullptr, (size_t)nb * (OSNET_H / 2) * (OSNET_W / 2) * C0 * 2));
+    DevMem dm;
+    void* di = dm.up_bytes(img, (size_t)nb * OSNET_H * OSNET_W * 4 * 2);
+    void* dw = dm.up_bytes(w, 147 * 64 * 2);
+    void* db = dm.up_bytes(bias, 64 * 4);
+    void* ds = dm.up_bytes(nullptr, (size_t)nb * (OSNET_H / 2) * (OSNET_W / 2) * C0 * 2);
     const size_t ob = (size_t)nb * (OSNET_H / 4) * (OSNET_W / 4) * C0 * 2;
-    RCCHK(up(dout, nullptr, ob));
-    HIPCHK(opd_launch_osnet_stem((const f16_t*)di.p, (const f16_t*)dw.p, (const float*)db.p, (f16_t*)ds.p, nb, C0, nullptr));
-    HIPCHK(opd_launch_osnet_maxpool((const f16_t*)ds.p, (f16_t*)dout.p, nb, OSNET_H / 2, OSNET_W / 2, C0, nullptr));
-    HIPCHK(hipMemcpy(out, dout.p, ob, hipMemcpyDeviceToHost));
+    void* dout = dm.up_bytes(nullptr, ob);
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    HIPCHK(opd_launch_osnet_stem((const f16_t*)di, (const f16_t*)dw, (const float*)db, (f16_t*)ds, nb, C0, nullptr));
+    HIPCHK(opd_launch_osnet_maxpool((const f16_t*)ds, (f16_t*)dout, nb, OSNET_H / 2, OSNET_W / 2, C0, nullptr));
+    HIPCHK(hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost));
     return OPD_OK;
 }
 
@@ -56,18 +57,20 @@ TAPI int opd_test_osnet_gemm(int epi, const uint16_t* a1, int lda1, int k1, cons
                              const float* bias, const uint16_t* res, int ldr, uint16_t* out, int ldo, int M, int N, int groups, int a_gcol,
                              int o_gcol) {
     ApiScope api_scope;
-    DevBuf da1, da2, dw, db, dr, dout;
-    RCCHK(up(da1, a1, (size_t)M * lda1 * 2));
-    if (k2) RCCHK(up(da2, a2, (size_t)M * lda2 * 2));
-    RCCHK(up(dw, w, (size_t)groups * N * (k1 + k2) * 2));
-    if (bias) RCCHK(up(db, bias, (size_t)groups * N * 4));
-    if (res) RCCHK(up(dr, res, (size_t)M * ldr * 2));
-    RCCHK(up(dout, out, (size_t)M * ldo * 2));
+    DevMem dm;
+    void *da2 = nullptr, *db = nullptr, *dr = nullptr;
+    void* da1 = dm.up_bytes(a1, (size_t)M * lda1 * 2);
+    if (k2) da2 = dm.up_bytes(a2, (size_t)M * lda2 * 2);
+    void* dw = dm.up_bytes(w, (size_t)groups * N * (k1 + k2) * 2);
+    if (bias) db = dm.up_bytes(bias, (size_t)groups * N * 4);
+    if (res) dr = dm.up_bytes(res, (size_t)M * ldr * 2);
+    void* dout = dm.up_bytes(out, (size_t)M * ldo * 2);
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     OsnetGemm p{};
-    p.a1 = da1.p; p.lda1 = lda1; p.k1 = k1; p.a2 = da2.p; p.lda2 = lda2; p.k2 = k2; p.w = dw.p; p.bias = (const float*)db.p;
-    p.res = dr.p; p.ldr = ldr; p.out = dout.p; p.ldo = ldo; p.M = M; p.N = N; p.a_gcol = a_gcol; p.o_gcol = o_gcol;
+    p.a1 = da1; p.lda1 = lda1; p.k1 = k1; p.a2 = da2; p.lda2 = lda2; p.k2 = k2; p.w = dw; p.bias = (const float*)db;
+    p.res = dr; p.ldr = ldr; p.out = dout; p.ldo = ldo; p.M = M; p.N = N; p.a_gcol = a_gcol; p.o_gcol = o_gcol;
     HIPCHK(opd_launch_osnet_gemm(epi, p, groups, nullptr));
-    HIPCHK(hipMemcpy(out, dout.p, (size_t)M * ldo * 2, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, dout, (size_t)M * ldo * 2, hipMemcpyDeviceToHost));
     return OPD_OK;
 }
 
@@ -75,14 +78,15 @@ TAPI int opd_test_osnet_gemm(int epi, const uint16_t* a1, int lda1, int k1, cons
 TAPI int opd_test_osnet_dwconv(const uint16_t* in, uint16_t* out, const float* w, const float* bias, int nb, int H, int W, int ld, int c0, int nc,
                                int ldw) {
     ApiScope api_scope;
-    DevBuf di, dout, dw, db;
+    DevMem dm;
     const size_t bytes = (size_t)nb * H * W * ld * 2;
-    RCCHK(up(di, in, bytes));
-    RCCHK(up(dout, out, bytes));
-    RCCHK(up(dw, w, (size_t)9 * ldw * 4));
-    RCCHK(up(db, bias, (size_t)ldw * 4));
-    HIPCHK(opd_launch_osnet_dwconv((const f16_t*)di.p, (f16_t*)dout.p, (const float*)dw.p, (const float*)db.p, nb, H, W, ld, c0, nc, ldw, nullptr));
-    HIPCHK(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+    void* di = dm.up_bytes(in, bytes);
+    void* dout = dm.up_bytes(out, bytes);
+    void* dw = dm.up_bytes(w, (size_t)9 * ldw * 4);
+    void* db = dm.up_bytes(bias, (size_t)ldw * 4);
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    HIPCHK(opd_launch_osnet_dwconv((const f16_t*)di, (f16_t*)dout, (const float*)dw, (const float*)db, nb, H, W, ld, c0, nc, ldw, nullptr));
+    HIPCHK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
     return OPD_OK;
 }
 
@@ -90,42 +94,45 @@ TAPI int opd_test_osnet_dwconv(const uint16_t* in, uint16_t* out, const float* w
 TAPI int opd_test_osnet_gate(const uint16_t* t, const float* w1, const float* b1, const float* w2, const float* b2, float* gates, uint16_t* x2,
                              int nb, int HW, int mid, int hid) {
     ApiScope api_scope;
-    DevBuf dt, d1, db1, d2, db2, dg, dx;
-    RCCHK(up(dt, t, (size_t)nb * HW * 4 * mid * 2));
-    RCCHK(up(d1, w1, (size_t)hid * mid * 4));
-    RCCHK(up(db1, b1, (size_t)hid * 4));
-    RCCHK(up(d2, w2, (size_t)mid * hid * 4));
-    RCCHK(up(db2, b2, (size_t)mid * 4));
-    RCCHK(up(dg, nullptr, (size_t)nb * 4 * mid * 4));
-    RCCHK(up(dx, nullptr, (size_t)nb * HW * mid * 2));
-    HIPCHK(opd_launch_osnet_gate((const f16_t*)dt.p, (const float*)d1.p, (const float*)db1.p, (const float*)d2.p, (const float*)db2.p, (float*)dg.p,
+    DevMem dm;
+    void* dt = dm.up_bytes(t, (size_t)nb * HW * 4 * mid * 2);
+    void* d1 = dm.up_bytes(w1, (size_t)hid * mid * 4);
+    void* db1 = dm.up_bytes(b1, (size_t)hid * 4);
+    void* d2 = dm.up_bytes(w2, (size_t)mid * hid * 4);
+    void* db2 = dm.up_bytes(b2, (size_t)mid * 4);
+    void* dg = dm.up_bytes(nullptr, (size_t)nb * 4 * mid * 4);
+    void* dx = dm.up_bytes(nullptr, (size_t)nb * HW * mid * 2);
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    HIPCHK(opd_launch_osnet_gate((const f16_t*)dt, (const float*)d1, (const float*)db1, (const float*)d2, (const float*)db2, (float*)dg,
                                  nb, HW, mid, hid, nullptr));
-    HIPCHK(opd_launch_osnet_combine((const f16_t*)dt.p, (const float*)dg.p, (f16_t*)dx.p, nb, HW, mid, nullptr));
-    HIPCHK(hipMemcpy(gates, dg.p, (size_t)nb * 4 * mid * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(x2, dx.p, (size_t)nb * HW * mid * 2, hipMemcpyDeviceToHost));
+    HIPCHK(opd_launch_osnet_combine((const f16_t*)dt, (const float*)dg, (f16_t*)dx, nb, HW, mid, nullptr));
+    HIPCHK(hipMemcpy(gates, dg, (size_t)nb * 4 * mid * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(x2, dx, (size_t)nb * HW * mid * 2, hipMemcpyDeviceToHost));
     return OPD_OK;
 }
 
 // 2x2 average pool [nb][H][W][C] -> [nb][H/2][W/2][C], fp16 bits
 TAPI int opd_test_osnet_avgpool2(const uint16_t* in, uint16_t* out, int nb, int H, int W, int C) {
     ApiScope api_scope;
-    DevBuf di, dout;
-    RCCHK(up(di, in, (size_t)nb * H * W * C * 2));
-    RCCHK(up(dout, nullptr, (size_t)nb * H * W * C / 2));
-    HIPCHK(opd_launch_osnet_avgpool2((const f16_t*)di.p, (f16_t*)dout.p, nb, H, W, C, nullptr));
-    HIPCHK(hipMemcpy(out, dout.p, (size_t)nb * H * W * C / 2, hipMemcpyDeviceToHost));
+    DevMem dm;
+    void* di = dm.up_bytes(in, (size_t)nb * H * W * C * 2);
+    void* dout = dm.up_bytes(nullptr, (size_t)nb * H * W * C / 2);
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    HIPCHK(opd_launch_osnet_avgpool2((const f16_t*)di, (f16_t*)dout, nb, H, W, C, nullptr));
+    HIPCHK(hipMemcpy(out, dout, (size_t)nb * H * W * C / 2, hipMemcpyDeviceToHost));
     return OPD_OK;
 }
 
 // head: x [nb][HW][C] fp16 bits, wt [C][512], b [512] -> feat [nb][512] fp32
 TAPI int opd_test_osnet_head(const uint16_t* x, const float* wt, const float* b, float* feat, int nb, int HW, int C) {
     ApiScope api_scope;
-    DevBuf dx, dw, db, df;
-    RCCHK(up(dx, x, (size_t)nb * HW * C * 2));
-    RCCHK(up(dw, wt, (size_t)C * 512 * 4));
-    RCCHK(up(db, b, 512 * 4));
-    RCCHK(up(df, nullptr, (size_t)nb * 512 * 4));
-    HIPCHK(opd_launch_osnet_head((const f16_t*)dx.p, (const float*)dw.p, (const float*)db.p, (float*)df.p, nb, HW, C, nullptr));
-    HIPCHK(hipMemcpy(feat, df.p, (size_t)nb * 512 * 4, hipMemcpyDeviceToHost));
+    DevMem dm;
+    void* dx = dm.up_bytes(x, (size_t)nb * HW * C * 2);
+    void* dw = dm.up_bytes(wt, (size_t)C * 512 * 4);
+    void* db = dm.up_bytes(b, 512 * 4);
+    void* df = dm.up_bytes(nullptr, (size_t)nb * 512 * 4);
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    HIPCHK(opd_launch_osnet_head((const f16_t*)dx, (const float*)dw, (const float*)db, (float*)df, nb, HW, C, nullptr));
+    HIPCHK(hipMemcpy(feat, df, (size_t)nb * 512 * 4, hipMemcpyDeviceToHost));
     return OPD_OK;
 }

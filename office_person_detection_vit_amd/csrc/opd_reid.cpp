@@ -26,9 +26,7 @@ struct opd_reid {
     void* ws = nullptr;     // workspace (max_crops)
     size_t wsbytes = 0;
     // staging: [ReidCrop x max_crops][tables][windows], pinned host image + device copy, grown on demand
-    unsigned char* h_up = nullptr;
-    unsigned char* d_up = nullptr;
-    size_t up_cap = 0;
+    Staging up;
     std::vector<int> buckets;
     struct Graph { hipGraphExec_t exec; unsigned epoch; };
     std::map<int, Graph> graphs;
@@ -36,25 +34,17 @@ struct opd_reid {
 
 namespace {
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 void destroy_graphs(opd_reid* r) {
     for (auto& kv : r->graphs) (void)hipGraphExecDestroy(kv.second.exec);
     r->graphs.clear();
 }
 
 int ensure_upload(opd_reid* r, size_t bytes) {
-    if (bytes <= r->up_cap) return OPD_OK;
-    const size_t cap = std::max(bytes, r->up_cap * 2);
-    destroy_graphs(r);   // the captured kernels hold the old base pointer
-    if (r->h_up) (void)hipHostFree(r->h_up);
-    if (r->d_up) (void)hipFree(r->d_up);
-    r->h_up = r->d_up = nullptr;
-    r->up_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&r->h_up, cap, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&r->d_up, cap));
-    r->up_cap = cap;
-    return OPD_OK;
+    const size_t cap = bytes <= r->up.dev_cap ? bytes : std::max(bytes, r->up.dev_cap * 2);   // grows by doubling
+    bool moved = false;
+    const int rc = r->up.reserve("opd_reid", cap, cap, r->launch.stream, &moved);   // (nothing may be launched between this and the next line)
+    if (moved) destroy_graphs(r);   // the captured kernels hold the old base pointer
+    return rc;
 }
 
 int bucket_of(const opd_reid* r, int n) {
@@ -63,38 +53,19 @@ int bucket_of(const opd_reid* r, int n) {
     return r->buckets.back();
 }
 
-int enqueue_forward(opd_reid* r, int nb) { return r->model->enqueue(nb, reinterpret_cast<const ReidCrop*>(r->d_up), r->d_up, r->launch); }
+int enqueue_forward(opd_reid* r, int nb) { return r->model->enqueue(nb, reinterpret_cast<const ReidCrop*>(r->up.dev), r->up.dev, r->launch); }
 
 int run_forward(opd_reid* r, int nb) {
     if (r->launch.prof || (r->cfg.flags & OPD_FLAG_NO_GRAPH)) return enqueue_forward(r, nb);
     auto it = r->graphs.find(nb);
-    if (it != r->graphs.end() && g_graph_guard.load() && it->second.epoch != g_handle_epoch.load()) {   // handles came or went since the
-        (void)hipGraphExecDestroy(it->second.exec);                                                       // capture: capture again, as the
-        r->graphs.erase(it);                                                                              // detector does (opd_model.h)
+    if (it != r->graphs.end() && graph_stale(it->second.epoch)) {   // handles came or went since the capture: capture again (see g_handle_epoch)
+        (void)hipGraphExecDestroy(it->second.exec);
+        r->graphs.erase(it);
         it = r->graphs.end();
     }
     if (it == r->graphs.end()) {
-        hipGraph_t graph = nullptr;
-        int rc;
-        hipError_t ec;
-        {
-            CaptureExclusive alone;
-            HIPCHK(hipStreamBeginCapture(r->launch.stream, hipStreamCaptureModeThreadLocal));
-            rc = enqueue_forward(r, nb);
-            ec = hipStreamEndCapture(r->launch.stream, &graph);
-        }
-        if (rc != OPD_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (ec != hipSuccess || !graph) {
-            (void)hipGetLastError();
-            return fail(OPD_EHIP, std::string("hipStreamEndCapture refused the Re-ID forward: ") + hipGetErrorString(ec) + " (OPD_FLAG_NO_GRAPH runs eagerly)");
-        }
         hipGraphExec_t exec = nullptr;
-        const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ei != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(OPD_EHIP, std::string("hipGraphInstantiate failed for the Re-ID forward: ") + hipGetErrorString(ei));
-        }
+        RCCHK(capture_graph(r->launch.stream, "the Re-ID forward", [&] { return enqueue_forward(r, nb); }, &exec));
         it = r->graphs.emplace(nb, opd_reid::Graph{exec, g_handle_epoch.load()}).first;
     }
     HIPCHK(hipGraphLaunch(it->second.exec, r->launch.stream));
@@ -134,7 +105,7 @@ int stage(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, in
             off = align_up(off + (size_t)(p.g.wy1 - p.g.wy0) * (p.g.wx1 - p.g.wx0) * 3, 16);
         }
     RCCHK(ensure_upload(r, off));
-    ReidCrop* rec = reinterpret_cast<ReidCrop*>(r->h_up);
+    ReidCrop* rec = reinterpret_cast<ReidCrop*>(r->up.host);
     for (int i = 0; i < nb; ++i) {
         ReidCrop& c = rec[i];
         memset(&c, 0, sizeof c);
@@ -146,7 +117,7 @@ int stage(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, in
         c.ks_h = p.ksh;
         c.ks_v = p.ksv;
         c.tables = (int64_t)p.toff;
-        int32_t* t = reinterpret_cast<int32_t*>(r->h_up + p.toff);
+        int32_t* t = reinterpret_cast<int32_t*>(r->up.host + p.toff);
         memcpy(t, p.bx.data(), 4 * 2 * (size_t)OW);
         memcpy(t + 2 * OW, p.by.data(), 4 * 2 * (size_t)OH);
         memcpy(t + 2 * OW + 2 * OH, p.ch.data(), 4 * (size_t)OW * p.ksh);
@@ -155,8 +126,8 @@ int stage(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, in
         if (mem_kind == OPD_MEM_HOST) {
             const size_t rowb = (size_t)(p.g.wx1 - p.g.wx0) * 3;
             for (int y = p.g.wy0; y < p.g.wy1; ++y)
-                memcpy(r->h_up + p.woff + (size_t)(y - p.g.wy0) * rowb, frames[p.f] + fstart + (size_t)(y - p.g.wy0) * W * 3, rowb);
-            c.src = r->d_up + p.woff;
+                memcpy(r->up.host + p.woff + (size_t)(y - p.g.wy0) * rowb, frames[p.f] + fstart + (size_t)(y - p.g.wy0) * W * 3, rowb);
+            c.src = r->up.dev + p.woff;
             c.pitch = (int32_t)rowb;
         } else {
             c.src = frames[p.f] + fstart;
@@ -182,8 +153,7 @@ void destroy_impl(opd_reid* r) {
     if (r->launch.stream) (void)hipStreamSynchronize(r->launch.stream);
     destroy_graphs(r);
     for (hipEvent_t e : r->launch.event_pool) (void)hipEventDestroy(e);
-    if (r->h_up) (void)hipHostFree(r->h_up);
-    if (r->d_up) (void)hipFree(r->d_up);
+    r->up.release();
     if (r->ws) (void)hipFree(r->ws);
     if (r->wmem) (void)hipFree(r->wmem);
     if (r->launch.stream) (void)hipStreamDestroy(r->launch.stream);
@@ -217,7 +187,7 @@ int create_impl(const opd_reid_config* cfg, const char* weights_path, int device
     std::vector<float> h32;
     r->model->pack(sd, &h16, &h32);
     sd.clear();
-    HIPCHK(hipSetDevice(device));
+    RCCHK(use_device("opd_reid_create", device));
     HIPCHK(hipStreamCreateWithFlags(&r->launch.stream, hipStreamNonBlocking));
     const size_t b16 = align_up(h16.size() * 2, 256), b32 = h32.size() * 4;
     r->wbytes = b16 + b32;
@@ -234,21 +204,6 @@ int create_impl(const opd_reid_config* cfg, const char* weights_path, int device
     *out = r.release();
     ++g_handle_epoch;
     return OPD_OK;
-}
-
-template <class F>
-int reid_guarded(const char* what, F&& body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        return fail(OPD_ENOMEM, std::string(what) + ": out of host memory");
-    } catch (const std::out_of_range& e) {
-        return fail(OPD_ESCHEMA, std::string(what) + ": weight file lacks a tensor the model needs (" + e.what() + ")");
-    } catch (const std::exception& e) {
-        return fail(OPD_EINVAL, std::string(what) + ": " + e.what());
-    } catch (...) {
-        return fail(OPD_EINVAL, std::string(what) + ": unknown C++ exception");
-    }
 }
 
 }  // namespace
@@ -284,8 +239,8 @@ int reid_test_pixels(opd_reid* r, const uint8_t* const* frames, const int32_t* f
     HIPCHK(hipSetDevice(r->device));
     size_t used = 0;
     RCCHK(stage(r, frames, frame_hw, n_frames, mem_kind, boxes, box_frame, n, n, &used));
-    HIPCHK(hipMemcpyAsync(r->d_up, r->h_up, used, hipMemcpyHostToDevice, r->launch.stream));
-    HIPCHK(r->model->preprocess(n, reinterpret_cast<const ReidCrop*>(r->d_up), r->d_up, r->launch.stream));
+    HIPCHK(hipMemcpyAsync(r->up.dev, r->up.host, used, hipMemcpyHostToDevice, r->launch.stream));
+    HIPCHK(r->model->preprocess(n, reinterpret_cast<const ReidCrop*>(r->up.dev), r->up.dev, r->launch.stream));
     HIPCHK(hipMemcpyAsync(out, r->model->image(), (size_t)n * r->model->image_bytes(), hipMemcpyDeviceToHost, r->launch.stream));
     HIPCHK(hipStreamSynchronize(r->launch.stream));
     return OPD_OK;
@@ -300,7 +255,7 @@ int reid_test_kernel_table(opd_reid* r, const uint8_t* const* frames, const int3
     const int nb = bucket_of(r, n);
     size_t used = 0;
     RCCHK(stage(r, frames, frame_hw, n_frames, OPD_MEM_HOST, boxes, box_frame, n, nb, &used));
-    HIPCHK(hipMemcpyAsync(r->d_up, r->h_up, used, hipMemcpyHostToDevice, r->launch.stream));
+    HIPCHK(hipMemcpyAsync(r->up.dev, r->up.host, used, hipMemcpyHostToDevice, r->launch.stream));
     std::vector<std::string> names;
     std::vector<opd_kernel_stat> rows;
     r->launch.prof = true;
@@ -342,7 +297,7 @@ extern "C" {
 
 int opd_reid_create(const opd_reid_config* cfg, const char* weights_path, int device_ordinal, opd_reid** out) {
     ApiScope api_scope;
-    return reid_guarded("opd_reid_create", [&] { return create_impl(cfg, weights_path, device_ordinal, out); });
+    return guarded("opd_reid_create", [&] { return create_impl(cfg, weights_path, device_ordinal, out); });
 }
 
 void opd_reid_destroy(opd_reid* r) {
@@ -359,14 +314,14 @@ int opd_reid_info(const opd_reid* r, opd_reid_model_info* info) {
     info->max_crops = r->cfg.max_crops;
     info->device_ordinal = r->device;
     info->weight_bytes_device = (int64_t)r->wbytes;
-    info->workspace_bytes_device = (int64_t)(r->wsbytes + r->up_cap);
+    info->workspace_bytes_device = (int64_t)(r->wsbytes + r->up.dev_cap);
     return OPD_OK;
 }
 
 int opd_reid_extract(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, int n_frames, int mem_kind, const float* boxes_xywh,
                      const int32_t* box_frame, int n_boxes, float* out) {
     ApiScope api_scope;
-    return reid_guarded("opd_reid_extract", [&]() -> int {
+    return guarded("opd_reid_extract", [&]() -> int {
         RCCHK(check_extract_args(r, frames, frame_hw, n_frames, mem_kind, boxes_xywh, n_boxes, out));
         if (n_boxes == 0) return OPD_OK;
         HIPCHK(hipSetDevice(r->device));
@@ -377,7 +332,7 @@ int opd_reid_extract(opd_reid* r, const uint8_t* const* frames, const int32_t* f
             const int nb = bucket_of(r, n);
             size_t used = 0;
             RCCHK(stage(r, frames, frame_hw, n_frames, mem_kind, boxes_xywh + 4 * (size_t)c0, box_frame ? box_frame + c0 : nullptr, n, nb, &used));
-            HIPCHK(hipMemcpyAsync(r->d_up, r->h_up, used, hipMemcpyHostToDevice, r->launch.stream));
+            HIPCHK(hipMemcpyAsync(r->up.dev, r->up.host, used, hipMemcpyHostToDevice, r->launch.stream));
             RCCHK(run_forward(r, nb));
             HIPCHK(hipMemcpyAsync(out + (size_t)c0 * E, feat, (size_t)n * E * 4, hipMemcpyDeviceToHost, r->launch.stream));
             HIPCHK(hipStreamSynchronize(r->launch.stream));   // (the pinned staging image is rewritten by the next chunk)

@@ -8,8 +8,9 @@
 
 #include "../../include/opd_detr.h"
 #include "opd_crop.h"
+#include "opd_device.h"
 #include "opd_kernels.h"
-#include "opd_model.h"
+#include "opd_loader.h"
 
 namespace opd {
 

@@ -55,27 +55,29 @@ TAPI int opd_test_reid_pixels(opd_reid* r, const uint8_t* const* frames, const i
 // attention of `crops` crops: qkv [crops * T][3H] fp16 bits (q already scaled) -> out [crops * T][H] fp16 bits
 TAPI int opd_test_reid_attention(const uint16_t* qkv, uint16_t* out, int crops, int T, int H) {
     ApiScope api_scope;
-    DevBuf dq, dout;
-    RCCHK(up(dq, qkv, (size_t)crops * T * 3 * H * 2));
-    RCCHK(up(dout, nullptr, (size_t)crops * T * H * 2));
-    HIPCHK(opd_launch_reid_attention((const f16_t*)dq.p, (f16_t*)dout.p, crops, T, H, nullptr));
-    HIPCHK(hipMemcpy(out, dout.p, (size_t)crops * T * H * 2, hipMemcpyDeviceToHost));
+    DevMem dm;
+    void* dq = dm.up_bytes(qkv, (size_t)crops * T * 3 * H * 2);
+    void* dout = dm.up_bytes(nullptr, (size_t)crops * T * H * 2);
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    HIPCHK(opd_launch_reid_attention((const f16_t*)dq, (f16_t*)dout, crops, T, H, nullptr));
+    HIPCHK(hipMemcpy(out, dout, (size_t)crops * T * H * 2, hipMemcpyDeviceToHost));
     return OPD_OK;
 }
 
 // LayerNorm of rows r * row_stride of x [rows * row_stride][H] fp32: y16 [rows][H] fp16 bits; y32 (may be null) = x rewritten
 TAPI int opd_test_reid_layernorm(const float* x, const float* g, const float* b, float* y32, uint16_t* y16, int rows, int row_stride, int H) {
     ApiScope api_scope;
-    DevBuf dx, dg, db, dy;
+    DevMem dm;
     const size_t xb = (size_t)rows * row_stride * H * 4;
-    RCCHK(up(dx, x, xb));
-    RCCHK(up(dg, g, (size_t)H * 4));
-    RCCHK(up(db, b, (size_t)H * 4));
-    RCCHK(up(dy, nullptr, (size_t)rows * H * 2));
-    HIPCHK(opd_launch_reid_layernorm((const float*)dx.p, row_stride, (const float*)dg.p, (const float*)db.p, y32 ? (float*)dx.p : nullptr,
-                                     (f16_t*)dy.p, rows, H, nullptr));
-    HIPCHK(hipMemcpy(y16, dy.p, (size_t)rows * H * 2, hipMemcpyDeviceToHost));
-    if (y32) HIPCHK(hipMemcpy(y32, dx.p, xb, hipMemcpyDeviceToHost));
+    void* dx = dm.up_bytes(x, xb);
+    void* dg = dm.up_bytes(g, (size_t)H * 4);
+    void* db = dm.up_bytes(b, (size_t)H * 4);
+    void* dy = dm.up_bytes(nullptr, (size_t)rows * H * 2);
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    HIPCHK(opd_launch_reid_layernorm((const float*)dx, row_stride, (const float*)dg, (const float*)db, y32 ? (float*)dx : nullptr,
+                                     (f16_t*)dy, rows, H, nullptr));
+    HIPCHK(hipMemcpy(y16, dy, (size_t)rows * H * 2, hipMemcpyDeviceToHost));
+    if (y32) HIPCHK(hipMemcpy(y32, dx, xb, hipMemcpyDeviceToHost));
     return OPD_OK;
 }
 
@@ -83,25 +85,28 @@ TAPI int opd_test_reid_layernorm(const float* x, const float* g, const float* b,
 // [M][N] (for REID_EPI_F32_RESID `out` holds the residual on entry)
 TAPI int opd_test_reid_gemm(int epi, const uint16_t* X, const uint16_t* W, const float* bias, int period, void* out, int M, int N, int K) {
     ApiScope api_scope;
-    DevBuf dx, dw, db, dout;
+    DevMem dm;
+    void *db = nullptr;
     const bool f32 = epi == REID_EPI_F32_RESID || epi == REID_EPI_F32_PBIAS;
     const size_t ob = (size_t)M * N * (f32 ? 4 : 2);
-    RCCHK(up(dx, X, (size_t)M * K * 2));
-    RCCHK(up(dw, W, (size_t)N * K * 2));
-    if (bias) RCCHK(up(db, bias, (size_t)(epi == REID_EPI_F32_PBIAS ? period : 1) * N * 4));
-    RCCHK(up(dout, epi == REID_EPI_F32_RESID ? out : nullptr, ob));
-    HIPCHK(opd_launch_reid_gemm(epi, (const f16_t*)dx.p, (const f16_t*)dw.p, (const float*)db.p, period, dout.p, M, N, K, nullptr));
-    HIPCHK(hipMemcpy(out, dout.p, ob, hipMemcpyDeviceToHost));
+    void* dx = dm.up_bytes(X, (size_t)M * K * 2);
+    void* dw = dm.up_bytes(W, (size_t)N * K * 2);
+    if (bias) db = dm.up_bytes(bias, (size_t)(epi == REID_EPI_F32_PBIAS ? period : 1) * N * 4);
+    void* dout = dm.up_bytes(epi == REID_EPI_F32_RESID ? out : nullptr, ob);
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    HIPCHK(opd_launch_reid_gemm(epi, (const f16_t*)dx, (const f16_t*)dw, (const float*)db, period, dout, M, N, K, nullptr));
+    HIPCHK(hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost));
     return OPD_OK;
 }
 
 // L2 normalisation of `rows` rows of y [rows][E] fp32, in place
 TAPI int opd_test_reid_l2norm(float* y, int rows, int E) {
     ApiScope api_scope;
-    DevBuf dy;
-    RCCHK(up(dy, y, (size_t)rows * E * 4));
-    HIPCHK(opd_launch_reid_l2norm((float*)dy.p, rows, E, nullptr));
-    HIPCHK(hipMemcpy(y, dy.p, (size_t)rows * E * 4, hipMemcpyDeviceToHost));
+    DevMem dm;
+    void* dy = dm.up_bytes(y, (size_t)rows * E * 4);
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    HIPCHK(opd_launch_reid_l2norm((float*)dy, rows, E, nullptr));
+    HIPCHK(hipMemcpy(y, dy, (size_t)rows * E * 4, hipMemcpyDeviceToHost));
     return OPD_OK;
 }
 

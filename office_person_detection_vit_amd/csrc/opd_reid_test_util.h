@@ -8,19 +8,6 @@
 
 namespace opd {
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-// a device buffer of `bytes` holding a copy of h, or zeros when h is null
-inline int up(DevBuf& d, const void* h, size_t bytes) {
-    HIPCHK(hipMalloc(&d.p, bytes ? bytes : 4));
-    if (h && bytes) HIPCHK(hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice));
-    else if (bytes) HIPCHK(hipMemset(d.p, 0, bytes));
-    return OPD_OK;
-}
-
 // Host-side geometry of n boxes on an H x W frame: out[i][13] = x1 y1 x2 y2 zero rh rw top left wy0 wx0 wy1 wx1
 inline void geometry_rows(const CropSpec& spec, const float* boxes, int n, int H, int W, int32_t* out) {
     for (int i = 0; i < n; ++i) {

@@ -15,20 +15,6 @@ int tfail(int code, const std::string& msg) {
     opd::g_err = msg;
     return code;
 }
-struct DevMem {
-    std::vector<void*> ptrs;
-    ~DevMem() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    T* up(const T* host, size_t count) {
-        void* d = nullptr;
-        if (hipMalloc(&d, count * sizeof(T) + 16) != hipSuccess) return nullptr;
-        ptrs.push_back(d);
-        if (host && hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return reinterpret_cast<T*>(d);
-    }
-};
 #define TCHK(expr)                                                                                          \
     do {                                                                                                    \
         hipError_t _e = (expr);                                                                             \
@@ -84,7 +70,7 @@ int opd_test_conv_gemm(const uint16_t* x, const uint16_t* w, const float* bias, 
     p.res16 = res16 ? dm.up(res16, M * N) : nullptr;
     p.res32 = res32 ? dm.up(res32, M * N) : nullptr;
     const size_t obytes = M * N * (out_f32 ? 4 : 2);
-    p.out = dm.up<unsigned char>(nullptr, obytes);
+    p.out = dm.alloc<unsigned char>(obytes);
     {
         const uint32_t zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         p.zero16 = dm.up(zeros, 8);
@@ -122,7 +108,7 @@ int opd_test_conv_dual(const uint16_t* x, const uint16_t* w1, const uint16_t* x2
     p.x2 = dm.up(x2, (size_t)B * H2 * W2 * Cin2);
     p.w = dm.up(wc.data(), wc.size());
     p.bias = dm.up(bias, (size_t)N);
-    p.out = dm.up<unsigned char>(nullptr, M * N * 2);
+    p.out = dm.alloc<unsigned char>(M * N * 2);
     const uint32_t zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     p.zero16 = dm.up(zeros, 8);
     if (!p.x || !p.x2 || !p.w || !p.bias || !p.out || !p.zero16) return tfail(OPD_ENOMEM, "test alloc failed");
@@ -149,8 +135,8 @@ int opd_test_conv_splitk(const uint16_t* x, const uint16_t* w, const float* bias
     p.bias = dm.up(bias, (size_t)N);
     std::vector<float> zeros((size_t)N, 0.f);   // (slices > 0 take their "bias" from here)
     p.zero16 = dm.up(zeros.data(), zeros.size());
-    float* slab = dm.up<float>(nullptr, (size_t)splits * M * N);
-    uint16_t* dout = dm.up<uint16_t>(nullptr, M * N);
+    float* slab = dm.alloc<float>((size_t)splits * M * N);
+    uint16_t* dout = dm.alloc<uint16_t>(M * N);
     if (!p.x || !p.w || !p.bias || !p.zero16 || !slab || !dout) return tfail(OPD_ENOMEM, "test alloc failed");
     p.out = slab;
     p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.N = N; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
@@ -168,7 +154,7 @@ int opd_test_reduce_act16(const float* partials, int nsplit, long long slab_stri
     if (nsplit < 1 || n <= 0 || slab_stride < n) return tfail(OPD_EINVAL, "reduce_act16: bad arguments");
     DevMem dm;
     const float* dp = dm.up(partials, (size_t)(nsplit - 1) * slab_stride + n);
-    uint16_t* dout = dm.up<uint16_t>(nullptr, (size_t)n);
+    uint16_t* dout = dm.alloc<uint16_t>((size_t)n);
     if (!dp || !dout) return tfail(OPD_ENOMEM, "test alloc failed");
     TCHK(opd_launch_reduce_act16(dp, nsplit, (size_t)slab_stride, dout, (size_t)n, relu, nullptr, g_test_dtype));
     TCHK(hipDeviceSynchronize());
@@ -187,7 +173,7 @@ int opd_test_gemm_alt(const uint16_t* x, const uint16_t* x_alt, const uint16_t* 
     p.bias = dm.up(bias, (size_t)N);
     const uint32_t zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     p.zero16 = dm.up(zeros, 8);
-    p.out = dm.up<unsigned char>(nullptr, (size_t)M * N * 2);
+    p.out = dm.alloc<unsigned char>((size_t)M * N * 2);
     if (!p.x || !p.x_alt || !p.w || !p.bias || !p.zero16 || !p.out) return tfail(OPD_ENOMEM, "test alloc failed");
     p.B = M; p.H = 1; p.W = 1; p.Cin = K; p.OH = 1; p.OW = 1; p.N = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
     p.M = M; p.K = K; p.alt_mod = alt_mod; p.alt_cols = alt_cols;
@@ -212,7 +198,7 @@ int opd_test_gemm_frame_bias(const uint16_t* x, const uint16_t* w, const float* 
     const uint32_t zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     p.zero16 = dm.up(zeros, 8);
     const size_t obytes = (size_t)M * N * (out_f32 ? 4 : 2);
-    p.out = dm.up<unsigned char>(nullptr, obytes);
+    p.out = dm.alloc<unsigned char>(obytes);
     if (!p.x || !p.w || !p.bias_ptrs || !p.zero16 || !p.out) return tfail(OPD_ENOMEM, "test alloc failed");
     p.B = M; p.H = 1; p.W = 1; p.Cin = K; p.OH = 1; p.OW = 1; p.N = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
     p.M = M; p.K = K; p.bias_period = period; p.bias_pmod = pmod; p.bias_pcols = pcols; p.out_f32 = out_f32;
@@ -240,9 +226,9 @@ int opd_test_reduce_ln_pos(const float* partials, int nsplit, const float* res32
     const float* const* dptrs = nullptr;
     if (pos_tables) dptrs = upload_frame_tables(dm, pos_tables, B, (size_t)period, 256, &dpos);
     else dpos = dm.up(pos, (size_t)period * 256);
-    float* dy = dm.up<float>(nullptr, MN);
-    uint16_t* dy16 = dm.up<uint16_t>(nullptr, MN);
-    uint16_t* dyp16 = dm.up<uint16_t>(nullptr, MN);
+    float* dy = dm.alloc<float>(MN);
+    uint16_t* dy16 = dm.alloc<uint16_t>(MN);
+    uint16_t* dyp16 = dm.alloc<uint16_t>(MN);
     if (!dp || (res32 && !dres) || (gamma && !dg) || (beta && !db) || !dpos || (pos_tables && !dptrs) || !dy || !dy16 || !dyp16)
         return tfail(OPD_ENOMEM, "test alloc failed");
     TCHK(opd_launch_reduce_ln_pos(dp, nsplit, MN, dres, dg, db, dy, dy16, M, dpos, dptrs, period, dyp16, nullptr, g_test_dtype));
@@ -264,12 +250,12 @@ int opd_test_gemm_splitk_ln(const uint16_t* x, const uint16_t* w, const float* b
     p.bias = dm.up(bias, N);
     std::vector<float> zeros(N, 0.f);
     p.zero16 = dm.up(zeros.data(), N);
-    float* slab = dm.up<float>(nullptr, (size_t)splits * M * N);
+    float* slab = dm.alloc<float>((size_t)splits * M * N);
     const float* dres = res32 ? dm.up(res32, (size_t)M * N) : nullptr;
     const float* dg = gamma ? dm.up(gamma, N) : nullptr;
     const float* db = beta ? dm.up(beta, N) : nullptr;
-    float* dy = dm.up<float>(nullptr, (size_t)M * N);
-    uint16_t* dy16 = dm.up<uint16_t>(nullptr, (size_t)M * N);
+    float* dy = dm.alloc<float>((size_t)M * N);
+    uint16_t* dy16 = dm.alloc<uint16_t>((size_t)M * N);
     if (!p.x || !p.w || !p.bias || !p.zero16 || !slab || !dy || !dy16) return tfail(OPD_ENOMEM, "test alloc failed");
     p.out = slab;
     p.B = M; p.H = 1; p.W = 1; p.Cin = K; p.OH = 1; p.OW = 1; p.N = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
@@ -293,8 +279,8 @@ int opd_test_gemm_ln(const uint16_t* x, const uint16_t* w, const float* bias, co
     p.res32 = res32 ? dm.up(res32, (size_t)M * 256) : nullptr;
     p.gamma = dm.up(gamma, 256);
     p.beta = dm.up(beta, 256);
-    p.y32 = dm.up<float>(nullptr, (size_t)M * 256);
-    p.y16 = dm.up<uint16_t>(nullptr, (size_t)M * 256);
+    p.y32 = dm.alloc<float>((size_t)M * 256);
+    p.y16 = dm.alloc<uint16_t>((size_t)M * 256);
     if (!p.x || !p.w || !p.bias || !p.gamma || !p.beta || !p.y32 || !p.y16 || (res32 && !p.res32)) return tfail(OPD_ENOMEM, "test alloc failed");
     p.M = M; p.K = K; p.kloop = g_gemm_ln_kloop;
     TCHK(opd_launch_gemm_ln(p, nullptr));
@@ -316,8 +302,8 @@ int opd_test_gemm_ln_deep(const uint16_t* x, const uint16_t* w, const float* bia
     p.res32 = res;
     p.gamma = gamma ? dm.up(gamma, 256) : nullptr;   // null: no LayerNorm (the input projection)
     p.beta = beta ? dm.up(beta, 256) : nullptr;
-    p.y32 = (in_place && res) ? res : dm.up<float>(nullptr, (size_t)M * 256);   // the model writes the residual stream in place
-    p.y16 = dm.up<uint16_t>(nullptr, (size_t)M * 256);
+    p.y32 = (in_place && res) ? res : dm.alloc<float>((size_t)M * 256);   // the model writes the residual stream in place
+    p.y16 = dm.alloc<uint16_t>((size_t)M * 256);
     if (pos && g_pos_frames) {   // per-frame tables (ragged batches): the single table stays set to frame 0's, as in the model
         if ((size_t)g_pos_frames * period < (size_t)M) return tfail(OPD_EINVAL, "gemm_ln_deep: fewer position tables than frames");
         p.pos_ptrs = upload_frame_tables(dm, pos, g_pos_frames, (size_t)period, 256, &p.pos);
@@ -326,7 +312,7 @@ int opd_test_gemm_ln_deep(const uint16_t* x, const uint16_t* w, const float* bia
         p.pos = pos ? dm.up(pos, (size_t)period * 256) : nullptr;
     }
     p.pos_period = period;
-    p.yp16 = pos ? dm.up<uint16_t>(nullptr, (size_t)M * 256) : nullptr;
+    p.yp16 = pos ? dm.alloc<uint16_t>((size_t)M * 256) : nullptr;
     if (!p.x || !p.w || !p.bias || (gamma && (!p.gamma || !p.beta)) || !p.y32 || !p.y16 || (res32 && !p.res32) || (pos && (!p.pos || !p.yp16)))
         return tfail(OPD_ENOMEM, "test alloc failed");
     p.M = M; p.K = K; p.deep_k = 1;
@@ -342,11 +328,11 @@ int opd_test_gemm_ln_deep(const uint16_t* x, const uint16_t* w, const float* bia
 int opd_test_bench_gemm_ln(int M, int K, int deep, int iters, float* us_out) {
     DevMem dm;
     GemmLnParams p{}; p.dtype = g_test_dtype;
-    uint16_t* x = dm.up<uint16_t>(nullptr, (size_t)M * K);
-    uint16_t* w = dm.up<uint16_t>(nullptr, (size_t)256 * K);
-    float* f = dm.up<float>(nullptr, 1024);
-    float* res = dm.up<float>(nullptr, (size_t)M * 256);
-    uint16_t* y16 = dm.up<uint16_t>(nullptr, (size_t)M * 256);
+    uint16_t* x = dm.alloc<uint16_t>((size_t)M * K);
+    uint16_t* w = dm.alloc<uint16_t>((size_t)256 * K);
+    float* f = dm.alloc<float>(1024);
+    float* res = dm.alloc<float>((size_t)M * 256);
+    uint16_t* y16 = dm.alloc<uint16_t>((size_t)M * 256);
     if (!x || !w || !f || !res || !y16) return tfail(OPD_ENOMEM, "bench alloc failed");
     TCHK(hipMemset(x, 0x2c, (size_t)M * K * 2));
     TCHK(hipMemset(w, 0x1c, (size_t)256 * K * 2));
@@ -395,8 +381,8 @@ int opd_test_enc_ffn(const uint16_t* x, const uint16_t* w1, const float* b1, con
     } else {
         p.x = dx;
     }
-    p.y32 = in_place ? res : dm.up<float>(nullptr, (size_t)M * 256);
-    p.y16 = (in_place && !wo) ? dx : dm.up<uint16_t>(nullptr, (size_t)M * 256);
+    p.y32 = in_place ? res : dm.alloc<float>((size_t)M * 256);
+    p.y16 = (in_place && !wo) ? dx : dm.alloc<uint16_t>((size_t)M * 256);
     if (pos && g_pos_frames) {   // per-frame tables, as in opd_test_gemm_ln_deep
         if ((size_t)g_pos_frames * period < (size_t)M) return tfail(OPD_EINVAL, "enc_ffn: fewer position tables than frames");
         p.pos_ptrs = upload_frame_tables(dm, pos, g_pos_frames, (size_t)period, 256, &p.pos);
@@ -406,12 +392,12 @@ int opd_test_enc_ffn(const uint16_t* x, const uint16_t* w1, const float* b1, con
     }
     p.pos_period = period;
     p.wprefetch = g_encffn_wprefetch;
-    p.yp16 = pos ? dm.up<uint16_t>(nullptr, (size_t)M * 256) : nullptr;
+    p.yp16 = pos ? dm.alloc<uint16_t>((size_t)M * 256) : nullptr;
     if (!dx || !p.wpack || !p.b2 || !p.res32 || !p.gamma || !p.beta || !p.y32 || !p.y16 || (pos && (!p.pos || !p.yp16))) return tfail(OPD_ENOMEM, "test alloc failed");
     p.M = M; p.F = F; p.pack_tail = tail; p.tail = tail; p.tail_pos = tail_pos;
     if (tail) {
         p.tail_ld = tail * 256;
-        p.tail_out = dm.up<uint16_t>(nullptr, (size_t)M * p.tail_ld);
+        p.tail_out = dm.alloc<uint16_t>((size_t)M * p.tail_ld);
         if (!p.tail_out) return tfail(OPD_ENOMEM, "test alloc failed");
         for (int t = 0; t < tail; ++t) p.tail_col[t] = 256 * t;
     }
@@ -429,13 +415,13 @@ int opd_test_bench_enc_ffn(int M, int F, int iters, int dbg, int tail, int front
     if (M <= 0 || F <= 0 || F % 128) return tfail(OPD_EINVAL, "bench_enc_ffn: F must be a multiple of 128");
     DevMem dm;
     EncFfnParams p{}; p.dtype = g_test_dtype;
-    uint16_t* x = dm.up<uint16_t>(nullptr, (size_t)M * 256);
-    unsigned char* wp = dm.up<unsigned char>(nullptr, opd_encffn_pack_bytes(F, tail, 1));
-    uint16_t* tout = tail ? dm.up<uint16_t>(nullptr, (size_t)M * tail * 256) : nullptr;
+    uint16_t* x = dm.alloc<uint16_t>((size_t)M * 256);
+    unsigned char* wp = dm.alloc<unsigned char>(opd_encffn_pack_bytes(F, tail, 1));
+    uint16_t* tout = tail ? dm.alloc<uint16_t>((size_t)M * tail * 256) : nullptr;
     if (tail && !tout) return tfail(OPD_ENOMEM, "bench alloc failed");
-    float* f = dm.up<float>(nullptr, 1024);
-    float* res = dm.up<float>(nullptr, (size_t)M * 256);
-    uint16_t* y16 = dm.up<uint16_t>(nullptr, (size_t)M * 256);
+    float* f = dm.alloc<float>(1024);
+    float* res = dm.alloc<float>((size_t)M * 256);
+    uint16_t* y16 = dm.alloc<uint16_t>((size_t)M * 256);
     if (!x || !wp || !f || !res || !y16) return tfail(OPD_ENOMEM, "bench alloc failed");
     TCHK(hipMemset(x, 0x2c, (size_t)M * 256 * 2));
     TCHK(hipMemset(wp, 0x1c, opd_encffn_pack_bytes(F, tail, 1)));
@@ -467,9 +453,9 @@ int opd_test_gemm_k256(const uint16_t* x, const uint16_t* w, const float* bias, 
     p.x = dm.up(x, (size_t)M * K);
     p.w = dm.up(w, (size_t)N * K);
     p.bias = dm.up(bias, (size_t)N * (bias_period > 0 ? bias_period : 1));
-    p.out16 = slices == 1 ? dm.up<uint16_t>(nullptr, (size_t)M * N) : nullptr;
-    p.out32 = slices > 1 ? dm.up<float>(nullptr, (size_t)slices * M * N) : nullptr;
-    float* sum = slices > 1 ? dm.up<float>(nullptr, (size_t)M * N) : nullptr;
+    p.out16 = slices == 1 ? dm.alloc<uint16_t>((size_t)M * N) : nullptr;
+    p.out32 = slices > 1 ? dm.alloc<float>((size_t)slices * M * N) : nullptr;
+    float* sum = slices > 1 ? dm.alloc<float>((size_t)M * N) : nullptr;
     if (!p.x || !p.w || !p.bias || (!p.out16 && !p.out32)) return tfail(OPD_ENOMEM, "test alloc failed");
     p.M = M; p.N = N; p.ldx = K; p.ldw = K; p.slices = slices; p.bias_period = bias_period; p.relu = relu;
     TCHK(opd_launch_gemm_k256(p, nullptr));
@@ -492,12 +478,12 @@ int opd_test_bench_conv(int B, int H, int W, int Cin, int N, int KH, int stride,
     const int pad = KH / 2, OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
     const size_t M = (size_t)B * OH * OW, K = (size_t)KH * KH * Cin;
     ConvGemmParams p{}; p.dtype = g_test_dtype;
-    uint16_t* x = dm.up<uint16_t>(nullptr, (size_t)B * H * W * Cin);
-    uint16_t* w = dm.up<uint16_t>(nullptr, (size_t)N * K);
-    float* bias = dm.up<float>(nullptr, N);
-    uint16_t* res = with_res ? dm.up<uint16_t>(nullptr, M * N) : nullptr;
-    uint16_t* out = dm.up<uint16_t>(nullptr, M * N);
-    float* zero = dm.up<float>(nullptr, 4096);
+    uint16_t* x = dm.alloc<uint16_t>((size_t)B * H * W * Cin);
+    uint16_t* w = dm.alloc<uint16_t>((size_t)N * K);
+    float* bias = dm.alloc<float>(N);
+    uint16_t* res = with_res ? dm.alloc<uint16_t>(M * N) : nullptr;
+    uint16_t* out = dm.alloc<uint16_t>(M * N);
+    float* zero = dm.alloc<float>(4096);
     if (!x || !w || !bias || !out || !zero || (with_res && !res)) return tfail(OPD_ENOMEM, "bench alloc failed");
     TCHK(hipMemset(x, 0x2c, (size_t)B * H * W * Cin * 2));  // fp16 0x2c2c ~ 0.065
     TCHK(hipMemset(w, 0x1c, (size_t)N * K * 2));
@@ -531,13 +517,13 @@ int opd_test_trace_conv(int B, int H, int W, int Cin, int N, int KH, int stride,
     const int pad = KH / 2, OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
     const size_t M = (size_t)B * OH * OW, K = (size_t)KH * KH * Cin;
     ConvGemmParams p{}; p.dtype = g_test_dtype;
-    uint16_t* x = dm.up<uint16_t>(nullptr, (size_t)B * H * W * Cin);
-    uint16_t* w = dm.up<uint16_t>(nullptr, (size_t)N * K);
-    float* bias = dm.up<float>(nullptr, N);
-    uint16_t* res = with_res ? dm.up<uint16_t>(nullptr, M * N) : nullptr;
-    uint16_t* out = dm.up<uint16_t>(nullptr, M * N * (split_k > 1 ? 2 * (size_t)split_k : 1));   // split-K: fp32 slabs
-    float* zero = dm.up<float>(nullptr, 4096);
-    unsigned long long* tr = dm.up<unsigned long long>(nullptr, (size_t)max_wgs * 8);
+    uint16_t* x = dm.alloc<uint16_t>((size_t)B * H * W * Cin);
+    uint16_t* w = dm.alloc<uint16_t>((size_t)N * K);
+    float* bias = dm.alloc<float>(N);
+    uint16_t* res = with_res ? dm.alloc<uint16_t>(M * N) : nullptr;
+    uint16_t* out = dm.alloc<uint16_t>(M * N * (split_k > 1 ? 2 * (size_t)split_k : 1));   // split-K: fp32 slabs
+    float* zero = dm.alloc<float>(4096);
+    unsigned long long* tr = dm.alloc<unsigned long long>((size_t)max_wgs * 8);
     if (!x || !w || !bias || !out || !zero || !tr || (with_res && !res)) return tfail(OPD_ENOMEM, "trace alloc failed");
     TCHK(hipMemset(x, 0x2c, (size_t)B * H * W * Cin * 2));
     TCHK(hipMemset(w, 0x1c, (size_t)N * K * 2));
@@ -551,7 +537,7 @@ int opd_test_trace_conv(int B, int H, int W, int Cin, int N, int KH, int stride,
     if (split_k > 1) { p.split_k = split_k; p.out_f32 = 1; p.relu = 0; }
     // `warm` traced launches back to back; the LAST THREE are kept (trace_out [3][max_wgs][8]): the spacing of their wall-clock stamps is
     // the cost of a launch boundary (drain of one kernel, dispatch of the next) on a busy stream
-    unsigned long long* tr3 = dm.up<unsigned long long>(nullptr, (size_t)3 * max_wgs * 8);
+    unsigned long long* tr3 = dm.alloc<unsigned long long>((size_t)3 * max_wgs * 8);
     if (!tr3) return tfail(OPD_ENOMEM, "trace alloc failed");
     TCHK(hipMemset(tr3, 0, (size_t)3 * max_wgs * 64));
     p.trace = tr;
@@ -592,10 +578,10 @@ int opd_test_btail(const uint16_t* x1, const uint16_t* w1, const float* b1, cons
     p.w2p = dm.up(w2p.data(), w2p.size());
     p.b2 = dm.up(b2, C2);
     p.res = res ? dm.up(res, M * C2) : nullptr;
-    p.y = dm.up<uint16_t>(nullptr, M * C2);
+    p.y = dm.alloc<uint16_t>(M * C2);
     p.w3p = C3 ? dm.up(w3p.data(), w3p.size()) : nullptr;
     p.b3 = C3 ? dm.up(b3, C3) : nullptr;
-    p.z = C3 ? dm.up<uint16_t>(nullptr, M * C3) : nullptr;
+    p.z = C3 ? dm.alloc<uint16_t>(M * C3) : nullptr;
     if (!p.x1 || !p.w1 || !p.b1 || !p.w2p || !p.b2 || !p.y || (res && !p.res) || (C3 && (!p.w3p || !p.b3 || !p.z)))
         return tfail(OPD_ENOMEM, "test alloc failed");
     p.B = B; p.H = H; p.W = W; p.OH = OH; p.OW = OW; p.stride = stride; p.M = (int)M; p.C1 = C1; p.C3 = C3;
@@ -626,11 +612,11 @@ int opd_test_btail_repeat(const uint16_t* x1, const uint16_t* w1, const float* b
     }
     BtailParams p{}; p.dtype = g_test_dtype;
     p.x1 = dm.up(x1, M * C1); p.w1 = dm.up(w1, (size_t)C1 * 9 * C1); p.b1 = dm.up(b1, C1); p.w2p = dm.up(w2p.data(), w2p.size());
-    p.b2 = dm.up(b2, C2); p.res = dm.up(res, M * C2); p.y = dm.up<uint16_t>(nullptr, M * C2); p.w3p = dm.up(w3p.data(), w3p.size());
-    p.b3 = dm.up(b3, C3); p.z = dm.up<uint16_t>(nullptr, M * C3);
+    p.b2 = dm.up(b2, C2); p.res = dm.up(res, M * C2); p.y = dm.alloc<uint16_t>(M * C2); p.w3p = dm.up(w3p.data(), w3p.size());
+    p.b3 = dm.up(b3, C3); p.z = dm.alloc<uint16_t>(M * C3);
     const size_t noise_bytes = (size_t)256 << 20;
-    unsigned char* noise = dm.up<unsigned char>(nullptr, 2 * noise_bytes);
-    unsigned long long* sums = dm.up<unsigned long long>(nullptr, (size_t)reps * 2 * OPD_TAP_BLOCKS);
+    unsigned char* noise = dm.alloc<unsigned char>(2 * noise_bytes);
+    unsigned long long* sums = dm.alloc<unsigned long long>((size_t)reps * 2 * OPD_TAP_BLOCKS);
     if (!p.x1 || !p.w1 || !p.b1 || !p.w2p || !p.b2 || !p.res || !p.y || !p.w3p || !p.b3 || !p.z || !noise || !sums) return tfail(OPD_ENOMEM, "test alloc failed");
     p.B = B; p.H = H; p.W = W; p.OH = H; p.OW = W; p.stride = 1; p.M = (int)M; p.C1 = C1; p.C3 = C3;
     hipStream_t side = nullptr;
@@ -678,10 +664,10 @@ int opd_test_btail_sc(const uint16_t* x1, const uint16_t* w1, const float* b1, c
     p.b2 = dm.up(b2sc, C2);
     p.xs = dm.up(xs, M * 64);
     p.wsc = dm.up(wsc, (size_t)C2 * 64);
-    p.y = dm.up<uint16_t>(nullptr, M * C2);
+    p.y = dm.alloc<uint16_t>(M * C2);
     p.w3p = dm.up(w3p.data(), w3p.size());
     p.b3 = dm.up(b3, C3);
-    p.z = dm.up<uint16_t>(nullptr, M * C3);
+    p.z = dm.alloc<uint16_t>(M * C3);
     if (!p.x1 || !p.w1 || !p.b1 || !p.w2p || !p.b2 || !p.xs || !p.wsc || !p.y || !p.w3p || !p.b3 || !p.z) return tfail(OPD_ENOMEM, "test alloc failed");
     p.B = B; p.H = H; p.W = W; p.OH = H; p.OW = W; p.stride = 1; p.M = (int)M; p.C1 = C1; p.C3 = C3;
     TCHK(opd_launch_btail(p, nullptr));
@@ -714,13 +700,13 @@ int opd_test_btail_chain(const uint16_t* x1, const uint16_t* xs, const uint16_t*
         d_w3[i] = dm.up(w3[i], (size_t)c3 * 256); d_b3[i] = dm.up(b3[i], c3);
         if (!d_w1[i] || !d_b1[i] || !d_w2[i] || !d_b2[i] || !d_w3[i] || !d_b3[i]) return tfail(OPD_ENOMEM, "test alloc failed");
     }
-    uint16_t* ya = dm.up<uint16_t>(nullptr, M * 256);
-    uint16_t* za = dm.up<uint16_t>(nullptr, M * 64);
-    uint16_t* a1a = dm.up<uint16_t>(nullptr, M * 64);
-    uint16_t* d_yb = dm.up<uint16_t>(nullptr, M * 256);
-    uint16_t* d_zb = dm.up<uint16_t>(nullptr, M * 64);
-    uint16_t* d_yc = dm.up<uint16_t>(nullptr, M * 256);
-    uint16_t* d_zc = dm.up<uint16_t>(nullptr, M * 128);
+    uint16_t* ya = dm.alloc<uint16_t>(M * 256);
+    uint16_t* za = dm.alloc<uint16_t>(M * 64);
+    uint16_t* a1a = dm.alloc<uint16_t>(M * 64);
+    uint16_t* d_yb = dm.alloc<uint16_t>(M * 256);
+    uint16_t* d_zb = dm.alloc<uint16_t>(M * 64);
+    uint16_t* d_yc = dm.alloc<uint16_t>(M * 256);
+    uint16_t* d_zc = dm.alloc<uint16_t>(M * 128);
     if (!d_x1 || !d_xs || !d_wsc || !ya || !za || !a1a || !d_yb || !d_zb || !d_yc || !d_zc) return tfail(OPD_ENOMEM, "test alloc failed");
     for (int route = 0; route < 2; ++route) {
         TCHK(hipMemset(ya, 0xEE, M * 256 * 2));
@@ -762,15 +748,15 @@ int opd_test_trace_btail(int B, int H, int W, int C1, int C3, int dbg, unsigned 
     const size_t M = (size_t)B * H * W;
     const int wgs = (int)((M + 127) / 128);
     if (wgs > max_wgs) return tfail(OPD_EINVAL, "trace buffer too small");
-    uint16_t* x1 = dm.up<uint16_t>(nullptr, M * C1);
-    uint16_t* w1 = dm.up<uint16_t>(nullptr, (size_t)C1 * 9 * C1);
-    uint16_t* w2 = dm.up<uint16_t>(nullptr, (size_t)C2 * C1);
-    uint16_t* w3 = dm.up<uint16_t>(nullptr, (size_t)C3 * C2);
-    float* bias = dm.up<float>(nullptr, C2);
-    uint16_t* res = dm.up<uint16_t>(nullptr, M * C2);
-    uint16_t* y = dm.up<uint16_t>(nullptr, M * C2);
-    uint16_t* z = dm.up<uint16_t>(nullptr, M * C3);
-    unsigned long long* tr = dm.up<unsigned long long>(nullptr, (size_t)wgs * 16);
+    uint16_t* x1 = dm.alloc<uint16_t>(M * C1);
+    uint16_t* w1 = dm.alloc<uint16_t>((size_t)C1 * 9 * C1);
+    uint16_t* w2 = dm.alloc<uint16_t>((size_t)C2 * C1);
+    uint16_t* w3 = dm.alloc<uint16_t>((size_t)C3 * C2);
+    float* bias = dm.alloc<float>(C2);
+    uint16_t* res = dm.alloc<uint16_t>(M * C2);
+    uint16_t* y = dm.alloc<uint16_t>(M * C2);
+    uint16_t* z = dm.alloc<uint16_t>(M * C3);
+    unsigned long long* tr = dm.alloc<unsigned long long>((size_t)wgs * 16);
     if (!x1 || !w1 || !w2 || !w3 || !bias || !res || !y || !z || !tr) return tfail(OPD_ENOMEM, "trace alloc failed");
     TCHK(hipMemset(x1, 0x2c, M * C1 * 2));
     TCHK(hipMemset(w1, 0x1c, (size_t)C1 * 9 * C1 * 2));
@@ -796,16 +782,16 @@ int opd_test_bench_btail(int B, int H, int W, int C1, int C3, int stride, int db
     DevMem dm;
     const int C2 = 4 * C1, OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
     const size_t M = (size_t)B * OH * OW;
-    uint16_t* x1 = dm.up<uint16_t>(nullptr, (size_t)B * H * W * C1);
-    uint16_t* w1 = dm.up<uint16_t>(nullptr, (size_t)C1 * 9 * C1);
-    uint16_t* w2 = dm.up<uint16_t>(nullptr, (size_t)C2 * C1);
-    uint16_t* w3 = dm.up<uint16_t>(nullptr, (size_t)(C3 ? C3 : 64) * C2);
-    float* bias = dm.up<float>(nullptr, C2);
-    uint16_t* res = dm.up<uint16_t>(nullptr, M * C2);
-    uint16_t* a1 = dm.up<uint16_t>(nullptr, M * C1);
-    uint16_t* y = dm.up<uint16_t>(nullptr, M * C2);
-    uint16_t* z = dm.up<uint16_t>(nullptr, M * (C3 ? C3 : 64));
-    float* zero = dm.up<float>(nullptr, 4096);
+    uint16_t* x1 = dm.alloc<uint16_t>((size_t)B * H * W * C1);
+    uint16_t* w1 = dm.alloc<uint16_t>((size_t)C1 * 9 * C1);
+    uint16_t* w2 = dm.alloc<uint16_t>((size_t)C2 * C1);
+    uint16_t* w3 = dm.alloc<uint16_t>((size_t)(C3 ? C3 : 64) * C2);
+    float* bias = dm.alloc<float>(C2);
+    uint16_t* res = dm.alloc<uint16_t>(M * C2);
+    uint16_t* a1 = dm.alloc<uint16_t>(M * C1);
+    uint16_t* y = dm.alloc<uint16_t>(M * C2);
+    uint16_t* z = dm.alloc<uint16_t>(M * (C3 ? C3 : 64));
+    float* zero = dm.alloc<float>(4096);
     if (!x1 || !w1 || !w2 || !w3 || !bias || !res || !a1 || !y || !z || !zero) return tfail(OPD_ENOMEM, "bench alloc failed");
     TCHK(hipMemset(x1, 0x2c, (size_t)B * H * W * C1 * 2));
     TCHK(hipMemset(w1, 0x1c, (size_t)C1 * 9 * C1 * 2));
@@ -853,7 +839,7 @@ int opd_test_bench_attention(const uint16_t* q, const uint16_t* k, const uint16_
     p.q = dm.up(q, (size_t)B * Lq * ldq);
     p.k = dm.up(k, (size_t)B * Lk * ldkv);
     p.v = dm.up(v, (size_t)B * Lk * ldkv);
-    p.o = dm.up<uint16_t>(nullptr, (size_t)B * Lq * heads * 32);
+    p.o = dm.alloc<uint16_t>((size_t)B * Lq * heads * 32);
     if (!p.q || !p.k || !p.v || !p.o) return tfail(OPD_ENOMEM, "bench alloc failed");
     p.B = B; p.heads = heads; p.Lq = Lq; p.Lk = Lk; p.ldq = ldq; p.ldk = p.ldv = ldkv; p.ldo = heads * 32; p.scale = scale;
     hipEvent_t a, b;
@@ -879,9 +865,9 @@ int opd_test_trace_attention(const uint16_t* q, const uint16_t* k, const uint16_
     p.q = dm.up(q, (size_t)B * Lq * ldq);
     p.k = dm.up(k, (size_t)B * Lk * ldkv);
     p.v = dm.up(v, (size_t)B * Lk * ldkv);
-    p.o = dm.up<uint16_t>(nullptr, (size_t)B * Lq * heads * 32);
+    p.o = dm.alloc<uint16_t>((size_t)B * Lq * heads * 32);
     const int total = ((Lq + 63) / 64) * heads * B, grid = 8 * ((total + 7) / 8);
-    unsigned long long* tr = dm.up<unsigned long long>(nullptr, (size_t)grid * 12);
+    unsigned long long* tr = dm.alloc<unsigned long long>((size_t)grid * 12);
     if (!p.q || !p.k || !p.v || !p.o || !tr) return tfail(OPD_ENOMEM, "trace alloc failed");
     TCHK(hipMemset(tr, 0, (size_t)grid * 96));
     p.B = B; p.heads = heads; p.Lq = Lq; p.Lk = Lk; p.ldq = ldq; p.ldk = p.ldv = ldkv; p.ldo = heads * 32; p.scale = scale;
@@ -903,7 +889,7 @@ int opd_test_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, 
     p.q = dm.up(q, (size_t)B * Lq * D);
     p.k = dm.up(k, (size_t)B * Lk * D);
     p.v = dm.up(v, (size_t)B * Lk * D);
-    p.o = dm.up<uint16_t>(nullptr, (size_t)B * Lq * D);
+    p.o = dm.alloc<uint16_t>((size_t)B * Lq * D);
     if (!p.q || !p.k || !p.v || !p.o) return tfail(OPD_ENOMEM, "test alloc failed");
     p.B = B; p.heads = heads; p.Lq = Lq; p.Lk = Lk; p.ldq = p.ldk = p.ldv = p.ldo = D; p.scale = scale;
     TCHK(opd_launch_attention(p, nullptr));
@@ -921,7 +907,7 @@ int opd_test_attention_masked(const uint16_t* q, const uint16_t* k, const uint16
     p.q = dm.up(q, (size_t)B * Lq * D);
     p.k = dm.up(k, (size_t)B * Lk * D);
     p.v = dm.up(v, (size_t)B * Lk * D);
-    p.o = dm.up<uint16_t>(nullptr, (size_t)B * Lq * D);
+    p.o = dm.alloc<uint16_t>((size_t)B * Lq * D);
     p.key_valid = dm.up(key_valid, (size_t)B * 2);
     if (!p.q || !p.k || !p.v || !p.o || !p.key_valid) return tfail(OPD_ENOMEM, "test alloc failed");
     p.B = B; p.heads = heads; p.Lq = Lq; p.Lk = Lk; p.ldq = p.ldk = p.ldv = p.ldo = D; p.scale = scale;
@@ -937,8 +923,8 @@ int opd_test_layernorm(const float* x, const float* g, const float* b, float* y,
     const float* dx = dm.up(x, (size_t)rows * 256);
     const float* dg = dm.up(g, 256);
     const float* db = dm.up(b, 256);
-    float* dy = dm.up<float>(nullptr, (size_t)rows * 256);
-    uint16_t* dy16 = dm.up<uint16_t>(nullptr, (size_t)rows * 256);
+    float* dy = dm.alloc<float>((size_t)rows * 256);
+    uint16_t* dy16 = dm.alloc<uint16_t>((size_t)rows * 256);
     if (!dx || !dg || !db || !dy || !dy16) return tfail(OPD_ENOMEM, "test alloc failed");
     TCHK(opd_launch_layernorm(dx, dg, db, dy, dy16, rows, nullptr));
     TCHK(hipDeviceSynchronize());
@@ -950,7 +936,7 @@ int opd_test_layernorm(const float* x, const float* g, const float* b, float* y,
 int opd_test_maxpool(const uint16_t* x, uint16_t* out, int B, int H, int W, int C, int OH, int OW) {
     DevMem dm;
     const uint16_t* dx = dm.up(x, (size_t)B * H * W * C);
-    uint16_t* dout = dm.up<uint16_t>(nullptr, (size_t)B * OH * OW * C);
+    uint16_t* dout = dm.alloc<uint16_t>((size_t)B * OH * OW * C);
     if (!dx || !dout) return tfail(OPD_ENOMEM, "test alloc failed");
     TCHK(opd_launch_maxpool(dx, dout, B, H, W, C, OH, OW, nullptr));
     TCHK(hipDeviceSynchronize());
@@ -962,7 +948,7 @@ int opd_test_maxpool(const uint16_t* x, uint16_t* out, int B, int H, int W, int 
 int opd_test_preprocess_u8(const uint8_t* frames, uint16_t* out, int B, int H, int W, int Hp, int Wp, const int32_t* valid_hw) {
     DevMem dm;
     const uint8_t* din = dm.up(frames, (size_t)B * H * W * 3);
-    uint16_t* dout = dm.up<uint16_t>(nullptr, (size_t)B * Hp * Wp * 4);
+    uint16_t* dout = dm.alloc<uint16_t>((size_t)B * Hp * Wp * 4);
     const int32_t* dvalid = valid_hw ? dm.up(valid_hw, (size_t)B * 2) : nullptr;
     if (!din || !dout || (valid_hw && !dvalid)) return tfail(OPD_ENOMEM, "test alloc failed");
     TCHK(opd_launch_preprocess_u8(din, dout, B, H, W, Hp, Wp, dvalid, nullptr));
@@ -981,7 +967,7 @@ int opd_test_stem2(const uint16_t* x4p, const uint16_t* w, const float* bias, ui
     p.bias = dm.up(bias, 64);
     std::vector<float> zeros(64, 0.f);
     p.zero16 = dm.up(zeros.data(), 64);
-    p.out = dm.up<uint16_t>(nullptr, M * 64);
+    p.out = dm.alloc<uint16_t>(M * 64);
     if (!p.x || !p.w || !p.bias || !p.zero16 || !p.out) return tfail(OPD_ENOMEM, "test alloc failed");
     p.B = B; p.H = Hp; p.W = Wp; p.Cin = 256; p.OH = OH; p.OW = OW; p.N = 64; p.KH = 1; p.KW = 1; p.stride = 2; p.pad = 0;
     p.M = (int)M; p.K = 256; p.relu = 1; p.stem = 2;
@@ -998,7 +984,7 @@ int opd_test_stem_pool(const uint16_t* x4p, const uint16_t* w, const float* bias
     const uint16_t* dx = dm.up(x4p, (size_t)B * Hp * Wp * 4);
     const uint16_t* dw = dm.up(w, (size_t)64 * 256);
     const float* db = dm.up(bias, 64);
-    uint16_t* dout = dm.up<uint16_t>(nullptr, (size_t)B * PH * PW * 64);
+    uint16_t* dout = dm.alloc<uint16_t>((size_t)B * PH * PW * 64);
     if (!dx || !dw || !db || !dout) return tfail(OPD_ENOMEM, "test alloc failed");
     TCHK(opd_launch_stem_pool(dx, dw, db, dout, B, Hp, Wp, OH, OW, PH, PW, nullptr));
     TCHK(hipDeviceSynchronize());
@@ -1016,9 +1002,9 @@ int opd_test_stem_pool_u8(const uint8_t* frames, const int32_t* valid_hw, const 
     const int32_t* dv = valid_hw ? dm.up(valid_hw, (size_t)2 * B) : nullptr;
     const uint16_t* dw = dm.up(w, (size_t)64 * 256);
     const float* db = dm.up(bias, 64);
-    uint16_t* dx = dm.up<uint16_t>(nullptr, (size_t)B * Hp * Wp * 4);
-    uint16_t* d1 = dm.up<uint16_t>(nullptr, (size_t)B * PH * PW * 64);
-    uint16_t* d2 = dm.up<uint16_t>(nullptr, (size_t)B * PH * PW * 64);
+    uint16_t* dx = dm.alloc<uint16_t>((size_t)B * Hp * Wp * 4);
+    uint16_t* d1 = dm.alloc<uint16_t>((size_t)B * PH * PW * 64);
+    uint16_t* d2 = dm.alloc<uint16_t>((size_t)B * PH * PW * 64);
     if (!df || !dw || !db || !dx || !d1 || !d2 || (valid_hw && !dv)) return tfail(OPD_ENOMEM, "test alloc failed");
     TCHK(opd_launch_stem_pool_u8(df, dv, dw, db, d1, B, H, W, OH, OW, PH, PW, nullptr));
     TCHK(opd_launch_preprocess_u8(df, dx, B, H, W, Hp, Wp, dv, nullptr));
@@ -1065,8 +1051,8 @@ int opd_test_heads(const float* hs, const float* ln_g, const float* ln_b, const 
     p.w1 = tr(w1, 256, 256); p.b1 = dm.up(b1, 256);
     p.w2 = tr(w2, 256, 256); p.b2 = dm.up(b2, 256);
     p.w3 = tr(w3, 4, 256); p.b3 = dm.up(b3, 4);
-    p.logits = dm.up<float>(nullptr, (size_t)rows * ncls);
-    p.boxes = dm.up<float>(nullptr, (size_t)rows * 4);
+    p.logits = dm.alloc<float>((size_t)rows * ncls);
+    p.boxes = dm.alloc<float>((size_t)rows * 4);
     if (!p.hs || !p.wc || !p.bc || !p.w1 || !p.b1 || !p.w2 || !p.b2 || !p.w3 || !p.b3 || !p.logits || !p.boxes) return tfail(OPD_ENOMEM, "test alloc failed");
     p.rows = rows; p.ncls = ncls;
     if (!heads_frags(dm, p, wc, w1, w2, ncls)) return tfail(OPD_ENOMEM, "test alloc failed");
@@ -1085,8 +1071,8 @@ int opd_test_postprocess(const float* logits, const float* boxes, const int32_t*
     p.logits = dm.up(logits, (size_t)B * Q * ncls);
     p.boxes = dm.up(boxes, (size_t)B * Q * 4);
     p.orig_hw = dm.up(orig_hw, (size_t)B * 2);
-    opd_det* rec = dm.up<opd_det>(nullptr, (size_t)B * Q);
-    p.counts = dm.up<int32_t>(nullptr, B);
+    opd_det* rec = dm.alloc<opd_det>((size_t)B * Q);
+    p.counts = dm.alloc<int32_t>(B);
     if (!p.logits || !p.boxes || !p.orig_hw || !rec || !p.counts) return tfail(OPD_ENOMEM, "test alloc failed");
     TCHK(hipMemset(rec, 0, (size_t)B * Q * sizeof(opd_det)));
     p.records = rec; p.B = B; p.Q = Q; p.ncls = ncls; p.threshold = threshold;
@@ -1102,7 +1088,7 @@ int opd_test_roi_features(const float* enc, const int32_t* rois, int n, int h, i
     DevMem dm;
     const float* d_enc = dm.up(enc, (size_t)h * w * 256);
     const int32_t* d_rois = dm.up(rois, (size_t)n * 4);
-    float* d_out = dm.up<float>(nullptr, (size_t)n * 256);
+    float* d_out = dm.alloc<float>((size_t)n * 256);
     if (!d_enc || !d_rois || !d_out) return tfail(OPD_ENOMEM, "test alloc failed");
     TCHK(opd_launch_roi_features(d_enc, d_rois, d_out, n, h, w, nullptr));
     TCHK(hipDeviceSynchronize());
@@ -1320,7 +1306,7 @@ int opd_test_dec_qkv(const float* h_in, const float* partials, int nsplit, const
     const size_t n = (size_t)M * 256, nv = (size_t)(M / Q) * 8 * 8 * 512;
     if (partials) {
         p.h_in = dm.up(h_in, n); p.partials = dm.up(partials, n * nsplit); p.nsplit = nsplit; p.b2 = dm.up(b2, 256); p.ln_g = dm.up(ln_g, 256); p.ln_b = dm.up(ln_b, 256);
-        p.h_out = dm.up<float>(nullptr, n);
+        p.h_out = dm.alloc<float>(n);
         if (!p.h_in || !p.partials || !p.b2 || !p.ln_g || !p.ln_b) return tfail(OPD_ENOMEM, "test alloc failed");
     } else {
         p.h_out = dm.up(const_cast<const float*>(h_in), n);
@@ -1328,7 +1314,7 @@ int opd_test_dec_qkv(const float* h_in, const float* partials, int nsplit, const
     p.w = up_frag(dm, w, 768, 256);
     if (!p.w) return tfail(OPD_ENOMEM, "test alloc failed");
     p.bias = dm.up(bias, (size_t)Q * 768);
-    p.q16 = dm.up<uint16_t>(nullptr, n); p.k16 = dm.up<uint16_t>(nullptr, nv); p.vT = dm.up<uint16_t>(nullptr, nv);
+    p.q16 = dm.alloc<uint16_t>(n); p.k16 = dm.alloc<uint16_t>(nv); p.vT = dm.alloc<uint16_t>(nv);
     if (!p.h_out || !p.bias || !p.q16 || !p.k16 || !p.vT) return tfail(OPD_ENOMEM, "test alloc failed");
     TCHK(hipMemset(p.vT, 0, nv * 2));
     TCHK(hipMemset(p.k16, 0, nv * 2));
@@ -1349,7 +1335,7 @@ int opd_test_dec_self(const uint16_t* q16, const uint16_t* k16, const uint16_t* 
     const size_t n = (size_t)B * Q * 256, nv = (size_t)B * 8 * 8 * 512;
     p.q16 = dm.up(q16, n); p.k16 = dm.up(k16, nv); p.vT = dm.up(vT, nv); p.h = dm.up(const_cast<const float*>(h), n);
     p.bo = dm.up(bo, 256); p.ln_g = dm.up(ln_g, 256); p.ln_b = dm.up(ln_b, 256); p.rbq = dm.up(rbq, (size_t)Q * 256);
-    p.qc16 = dm.up<uint16_t>(nullptr, n);
+    p.qc16 = dm.alloc<uint16_t>(n);
     p.wo = up_frag(dm, wo, 256, 256); p.wq = up_frag(dm, wq, 256, 256);
     if (!p.wo || !p.wq) return tfail(OPD_ENOMEM, "test alloc failed");
     if (!p.q16 || !p.k16 || !p.vT || !p.h || !p.bo || !p.ln_g || !p.ln_b || !p.rbq || !p.qc16) return tfail(OPD_ENOMEM, "test alloc failed");
@@ -1369,7 +1355,7 @@ int opd_test_attention_split(const uint16_t* q, const uint16_t* k, const uint16_
     p.q = dm.up(q, (size_t)B * Lq * D); p.k = dm.up(k, (size_t)B * Lk * D); p.v = dm.up(v, (size_t)B * Lk * D);
     p.key_valid = key_valid ? dm.up(key_valid, (size_t)B * 2) : nullptr;
     const size_t no = (size_t)splits * B * Lq * D, nm = (size_t)splits * B * Lq * heads * 2;
-    p.part_o = dm.up<float>(nullptr, no); p.part_ml = dm.up<float>(nullptr, nm);
+    p.part_o = dm.alloc<float>(no); p.part_ml = dm.alloc<float>(nm);
     if (!p.q || !p.k || !p.v || !p.part_o || !p.part_ml || (key_valid && !p.key_valid)) return tfail(OPD_ENOMEM, "test alloc failed");
     p.B = B; p.heads = heads; p.Lq = Lq; p.Lk = Lk; p.ldq = p.ldk = p.ldv = p.ldo = D; p.scale = scale; p.key_row = key_row; p.splits = splits;
     TCHK(opd_launch_attention(p, nullptr));
@@ -1385,7 +1371,7 @@ int opd_test_dec_cross_out(const float* part_o, const float* part_ml, int splits
     const size_t n = (size_t)M * 256;
     p.part_o = dm.up(part_o, n * splits); p.part_ml = dm.up(part_ml, (size_t)splits * M * 16); p.splits = splits;
     p.res = dm.up(res, res_period > 0 ? (size_t)res_period * 256 : n); p.res_period = res_period;
-    p.h = dm.up<float>(nullptr, n); p.bo = dm.up(bo, 256); p.ln_g = dm.up(ln_g, 256); p.ln_b = dm.up(ln_b, 256); p.M = M;
+    p.h = dm.alloc<float>(n); p.bo = dm.up(bo, 256); p.ln_g = dm.up(ln_g, 256); p.ln_b = dm.up(ln_b, 256); p.M = M;
     p.wo = up_frag(dm, wo, 256, 256);
     if (!p.wo) return tfail(OPD_ENOMEM, "test alloc failed");
     if (!p.part_o || !p.part_ml || !p.res || !p.h || !p.bo || !p.ln_g || !p.ln_b) return tfail(OPD_ENOMEM, "test alloc failed");
@@ -1399,7 +1385,7 @@ int opd_test_dec_ffn(const float* h, const float* w1, const float* b1, const flo
     DevMem dm;
     DecFfnParams p{};
     const size_t n = (size_t)M * 256, np = n * (F / OPD_DEC_FFN_CHUNK);
-    p.h = dm.up(h, n); p.b1 = dm.up(b1, (size_t)F); p.partials = dm.up<float>(nullptr, np); p.M = M; p.F = F;
+    p.h = dm.up(h, n); p.b1 = dm.up(b1, (size_t)F); p.partials = dm.alloc<float>(np); p.M = M; p.F = F;
     p.w1 = up_frag(dm, w1, F, 256); p.w2 = up_frag(dm, w2, 256, F);
     if (!p.w1 || !p.w2) return tfail(OPD_ENOMEM, "test alloc failed");
     if (!p.h || !p.b1 || !p.partials) return tfail(OPD_ENOMEM, "test alloc failed");
@@ -1414,8 +1400,8 @@ int opd_test_bench_dec(int B, int Q, int Lk, int F, int splits, int iters, float
     DevMem dm;
     const int M = B * Q;
     const size_t n = (size_t)M * 256;
-    auto z16 = [&](size_t c) { uint16_t* p = dm.up<uint16_t>(nullptr, c); if (p) (void)hipMemset(p, 0, c * 2); return p; };
-    auto z32 = [&](size_t c) { float* p = dm.up<float>(nullptr, c); if (p) (void)hipMemset(p, 0, c * 4); return p; };
+    auto z16 = [&](size_t c) { uint16_t* p = dm.alloc<uint16_t>(c); if (p) (void)hipMemset(p, 0, c * 2); return p; };
+    auto z32 = [&](size_t c) { float* p = dm.alloc<float>(c); if (p) (void)hipMemset(p, 0, c * 4); return p; };
     DecQkvParams a{}; DecSelfParams b{}; AttnParams c{}; DecCrossOutParams d{}; DecFfnParams e{};
     const int nchunk = F / OPD_DEC_FFN_CHUNK;
     float *h0 = z32(n), *h1 = z32(n), *part = z32(n * nchunk), *vec = z32(4096), *tabs = z32((size_t)Q * 768), *po = z32(n * splits), *pml = z32((size_t)splits * M * 16);
@@ -1458,14 +1444,14 @@ int opd_test_bench_dec(int B, int Q, int Lk, int F, int splits, int iters, float
 int opd_test_trace_dec_self(int B, int Q, unsigned long long* trace_out) {
     DevMem dm;
     const size_t n = (size_t)B * Q * 256;
-    auto z16 = [&](size_t c) { uint16_t* p = dm.up<uint16_t>(nullptr, c); if (p) (void)hipMemset(p, 0, c * 2); return p; };
-    auto z32 = [&](size_t c) { float* p = dm.up<float>(nullptr, c); if (p) (void)hipMemset(p, 0, c * 4); return p; };
+    auto z16 = [&](size_t c) { uint16_t* p = dm.alloc<uint16_t>(c); if (p) (void)hipMemset(p, 0, c * 2); return p; };
+    auto z32 = [&](size_t c) { float* p = dm.alloc<float>(c); if (p) (void)hipMemset(p, 0, c * 4); return p; };
     DecSelfParams b{};
     const int wgs = ((Q + 15) / 16) * B;
     b.q16 = z16(n); b.k16 = z16((size_t)B * 8 * 8 * 512); b.vT = z16((size_t)B * 8 * 8 * 512); b.h = z32(n); b.wo = z16(2 * 65536); b.wq = z16(2 * 65536);
     float* vec = z32(4096);
     b.bo = vec; b.ln_g = vec; b.ln_b = vec; b.rbq = z32((size_t)Q * 256); b.qc16 = z16(n); b.B = B; b.Q = Q; b.scale = 0.17677669f;
-    unsigned long long* tr = dm.up<unsigned long long>(nullptr, (size_t)wgs * 8);
+    unsigned long long* tr = dm.alloc<unsigned long long>((size_t)wgs * 8);
     if (!b.q16 || !b.k16 || !b.vT || !b.h || !b.wo || !b.wq || !vec || !b.rbq || !b.qc16 || !tr) return tfail(OPD_ENOMEM, "test alloc failed");
     for (int i = 0; i < 3; ++i) TCHK(opd_launch_dec_self(b, nullptr));   // warm: code and weights in the caches
     b.trace = tr;
@@ -1494,8 +1480,8 @@ int opd_test_heads_fused(const float* hs, const float* partials, int nsplit, con
     p.w1 = tr(w1, 256, 256); p.b1 = dm.up(b1, 256);
     p.w2 = tr(w2, 256, 256); p.b2 = dm.up(b2, 256);
     p.w3 = tr(w3, 4, 256); p.b3 = dm.up(b3, 4);
-    p.logits = dm.up<float>(nullptr, (size_t)rows * ncls);
-    p.boxes = dm.up<float>(nullptr, (size_t)rows * 4);
+    p.logits = dm.alloc<float>((size_t)rows * ncls);
+    p.boxes = dm.alloc<float>((size_t)rows * 4);
     if (!p.hs || !p.partials || !p.ffn_b2 || !p.ln3_gamma || !p.ln3_beta || !p.ln_gamma || !p.ln_beta || !p.wc || !p.bc || !p.w1 || !p.b1 || !p.w2 || !p.b2 ||
         !p.w3 || !p.b3 || !p.logits || !p.boxes)
         return tfail(OPD_ENOMEM, "test alloc failed");

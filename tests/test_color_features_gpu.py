@@ -60,6 +60,31 @@ def _host(frame, boxes):
     return FeatureExtractor().extract_batch(crop_boxes(frame, boxes))
 
 
+def test_staging_pair_regrown_between_calls(lib, bound):
+    """The per-device staging pair starts at 64 KiB and lives as long as the process: one 8 x 8 box on a 32 x 32 frame, then a whole
+    160 x 160 frame (76 800 bytes of window: as the first test of the module this frees the pair and allocates it anew), then the first
+    input again.  The first and third rows are the same bits; the second meets the parity test's bound.  Then the same once more around a
+    whole 1100 x 1930 frame, larger than any frame another test of this module stages, so that a regrow happens wherever the test runs."""
+    small = np.ascontiguousarray(structured_frames(1, 32, 32, seed=5)[0]).copy()
+    large = np.ascontiguousarray(structured_frames(1, 160, 160, seed=6)[0]).copy()
+    box, whole = np.array([(8, 8, 8, 8)], np.float32), np.array([(0, 0, 160, 160)], np.float32)
+    first = CC.device_color_features(lib, [small], box)
+    second = CC.device_color_features(lib, [large], whole)
+    third = CC.device_color_features(lib, [small], box)
+    assert np.isfinite(first).all() and first.tobytes() == third.tobytes()
+    d = float(np.abs(second.astype(np.float64) - _host(large, whole).astype(np.float64)).max())
+    d_exact = float(np.abs(second.astype(np.float64) - CC.exact_rows([large])).max())
+    print(f"160x160 whole-frame crop across a regrow: max |device - host| = {d:.3e}, |device - exact| = {d_exact:.3e}, bound {bound:.3e}")
+    assert d <= bound and d_exact <= bound
+    huge = np.ascontiguousarray(np.tile(large, (7, 13, 1))[:1100, :1930])   # (tiled: cheap to make)
+    everything = np.array([(0, 0, 1930, 1100)], np.float32)
+    fourth = CC.device_color_features(lib, [huge], everything)
+    fifth = CC.device_color_features(lib, [small], box)
+    d = float(np.abs(fourth.astype(np.float64) - _host(huge, everything).astype(np.float64)).max())
+    print(f"1100x1930 whole-frame crop across a regrow: max |device - host| = {d:.3e}, bound {bound:.3e}")
+    assert first.tobytes() == fifth.tobytes() and d <= bound
+
+
 @pytest.mark.parametrize("hw", [(720, 1280), (1080, 1920)])
 def test_parity_with_the_host_restatement(lib, bound, hw):
     h, w = hw

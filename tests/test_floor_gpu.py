@@ -154,6 +154,28 @@ def test_rows_do_not_depend_on_the_batch(lib, golden, name):
         lib.opd_floor_destroy(h)
 
 
+def test_staging_pair_regrown_between_calls(lib, golden):
+    """A handle's staging pair starts at 256 records: 8 points, then 300 (the pair is freed and allocated anew), then the 8 again.  The
+    shared rows are the same bits in all three calls, and the 300 rows meet the fixture test's comparison."""
+    name = "tps_n65"
+    model, pts = F.case_model(golden, name), golden[f"{name}_pts"]
+    assert len(pts) == 300
+    h = F.create(lib, model)
+    try:
+        small = F.device_transform(lib, h, pts=pts[:8])
+        big = F.device_transform(lib, h, pts=pts)
+        again = F.device_transform(lib, h, pts=pts[:8])
+    finally:
+        lib.opd_floor_destroy(h)
+    assert small.tobytes() == big[:8].tobytes() == again.tobytes()
+    px, tri, flags, masks = F.run(model, pts=pts)
+    d, limit = float(np.abs(big["px"] - px).max()), F.bound(golden, name)
+    print(f"{name} across a regrow: max |device - float64 restatement| = {d:.3e} px (bound {limit:.3e})")
+    assert np.array_equal(big["flags"], flags) and np.array_equal(big["triangle"], tri) and np.array_equal(big["zone_mask"], masks)
+    assert d <= limit
+    assert np.array_equal(big["mm"], big["px"] * np.asarray(model["fm"][2:4]))
+
+
 def test_two_mappers_on_one_device(lib, golden):
     a_model, b_model = F.case_model(golden, "pwa_t_mid"), F.case_model(golden, "tps_n64")
     a_in, b_in = _inputs(golden, "pwa_t_mid"), _inputs(golden, "tps_n64")
