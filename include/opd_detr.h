@@ -473,6 +473,67 @@ OPD_API int opd_floor_classify(opd_floor* f, const double* floor_xy, int n, uint
 OPD_API int opd_detr_detect_frames_floor(opd_detr* m, opd_floor* f, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
                                          int label, opd_det* out, int32_t* counts, opd_floor_rec* floor);
 
+/* ---- Tracker: the reference's `Tracker.update` per frame (fifth handle type: per-track state on the device, own stream) ----------------
+ * DeepSORT-style tracking as src/tracking/tracker.py runs it once per frame: Kalman predict of every track, up to five association stages
+ * (appearance, appearance + IoU behind a distance gate, IoU, the low-confidence rescue, tentative tracks), Kalman update with the
+ * observation-centric re-update after an occlusion, new tracks, deletion after max_age frames.  The numeric state (Kalman x and P, last
+ * observation, box, the last ten feature vectors) lives on the device for the life of the handle; slot list, ids and counters live in
+ * the handle on the host.  One update is two launches and one host wait: the first launch predicts and writes three cost matrices, the host
+ * solves the assignments over sub-blocks of them, the second launch commits and is not waited for (the next call orders behind it).
+ * Arithmetic is float32 in a fixed order without fused multiply-adds; a track's numbers do not depend on how many other tracks or
+ * detections there are, nor on its slot.  Which of several equally cheap assignments is taken is not specified. */
+typedef struct opd_track opd_track; /* opaque tracker handle */
+
+/* The reference's constructor keywords; a zeroed field means the reference's default.  What can therefore not be expressed: max_age = 0,
+ * min_hits = 0 (the same as 1: a track is born with one hit), high_conf_threshold = 0 (use a tiny positive value), both weights zero
+ * (the reference refuses that itself) and max_position_distance = 0 (its meaning there, "no gate", is spelled as a negative value). */
+typedef struct opd_track_config {
+    int32_t struct_size;          /* = sizeof(opd_track_config) */
+    int32_t max_tracks;           /* slots: tracks alive at one time, 1 .. 1024 (0 = 128) */
+    int32_t max_dets;             /* detections per update, 1 .. 1024 (0 = 128) */
+    int32_t feature_dim;          /* width D of a feature vector, 1 .. 2048 (0 = 512) */
+    int32_t max_age;              /* a track is dropped once it went this many frames without a match (0 = 30) */
+    int32_t min_hits;             /* matches that confirm a track (0 = 3) */
+    double iou_threshold;         /* (0 = 0.3) kept for the interface: the reference stores it and never reads it */
+    double appearance_weight;     /* with motion_weight: both 0 = 0.7 and 0.3; otherwise they must sum to 1 within 1e-6 */
+    double motion_weight;
+    double max_position_distance; /* gate of the combined cost in pixels (0 = 150; negative = no gate) */
+    double high_conf_threshold;   /* detections at or above start and match tracks, those below only rescue confirmed tracks (0 = 0.5) */
+} opd_track_config;
+
+typedef struct opd_track_rec {
+    int32_t track_id, age, hits, time_since_update;
+    float x[4];   /* Kalman state: position and velocity */
+    float box[4]; /* xywh of the detection matched last */
+} opd_track_rec;
+
+typedef struct opd_track_status {
+    int32_t max_tracks, max_dets, feature_dim, max_age, min_hits, device_ordinal;
+    int32_t n_tracks, next_id;
+    int32_t last_launches, last_waits; /* kernel launches and host waits of the last update */
+} opd_track_status;
+
+/* OPD_EINVAL, before the device is touched, for a size outside its range, a negative count or weights that do not sum to 1. */
+OPD_API int opd_track_create(const opd_track_config* cfg, int device_ordinal, opd_track** out);
+OPD_API void opd_track_destroy(opd_track* t);
+/* Drop every track and start again at id 1, as `Tracker.reset`. */
+OPD_API int opd_track_reset(opd_track* t);
+OPD_API int opd_track_info(const opd_track* t, opd_track_status* info);
+/* One frame.  boxes_xywh [n][4], foot_xy [n][2] (`camera_coords`), confidence [n]: host float32.  features [n][feature_dim] float32 or
+ * NULL (no detection has one): host memory for OPD_MEM_HOST, device-accessible memory read by a device copy for OPD_MEM_DEVICE (it must be
+ * complete before the call, and may be reused after it returns).  has_feature [n] (host) or NULL (every detection has one).  out_ids [n]
+ * (host): the track id given to each detection, -1 where the reference leaves None (a low-confidence detection that rescued nothing).
+ * n > max_dets is OPD_EINVAL and changes nothing.  More live tracks than max_tracks is OPD_EINVAL too: the frame then counts as one
+ * without detections (every track aged, none matched or created), so the handle stays usable. */
+OPD_API int opd_track_update(opd_track* t, const float* boxes_xywh, const float* foot_xy, const float* confidence, const float* features,
+                             const uint8_t* has_feature, int feat_mem_kind, int n, int32_t* out_ids);
+/* The live tracks in creation order: out [capacity], *count = how many there are (OPD_EINVAL when capacity is smaller; out may be NULL
+ * with capacity 0 to ask for the count).  Waits for the last update's second launch. */
+OPD_API int opd_track_get(opd_track* t, opd_track_rec* out, int capacity, int* count);
+/* The solver of the association on its own (host only): cost [rows][cols] row-major -> row_to_col [rows], -1 for a row left alone;
+ * min(rows, cols) pairs of smallest total cost, as scipy.optimize.linear_sum_assignment. */
+OPD_API int opd_assign(const double* cost, int rows, int cols, int32_t* row_to_col);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 OPD_API const char* opd_last_error(void);
 

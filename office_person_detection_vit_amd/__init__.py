@@ -13,6 +13,7 @@ from .optical_flow import HipOpticalFlowTracker  # noqa: F401
 from .reid import HipOSNetReIDExtractor, HipReIDExtractor, create_reid_extractor  # noqa: F401
 from .similarity import SimilarityCalculator  # noqa: F401
 from .tiling import TiledDetector  # noqa: F401
+from .tracker import HipTracker  # noqa: F401
 
-__all__ = ["Detection", "HipDetrDetector", "FeatureExtractor", "HipFloorMapper", "HipOpticalFlowTracker", "HipReIDExtractor", "HipOSNetReIDExtractor", "create_reid_extractor", "SimilarityCalculator", "TiledDetector", "detections_to_coco", "write_coco",
+__all__ = ["Detection", "HipDetrDetector", "FeatureExtractor", "HipFloorMapper", "HipOpticalFlowTracker", "HipTracker", "HipReIDExtractor", "HipOSNetReIDExtractor", "create_reid_extractor", "SimilarityCalculator", "TiledDetector", "detections_to_coco", "write_coco",
            "model_input_size"]

@@ -84,6 +84,22 @@ class OpdFloorModelInfo(C.Structure):   # opd_floor_model_info
     _fields_ = [(n, C.c_int32) for n in ("method", "n_points", "n_triangles", "n_zones", "n_edges", "has_distortion", "allow_overlap", "device_ordinal")]
 
 
+class OpdTrackConfig(C.Structure):   # opd_track_config (64 bytes): zeros = the reference's defaults
+    _fields_ = [("struct_size", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("feature_dim", C.c_int32), ("max_age", C.c_int32),
+                ("min_hits", C.c_int32), ("iou_threshold", C.c_double), ("appearance_weight", C.c_double), ("motion_weight", C.c_double),
+                ("max_position_distance", C.c_double), ("high_conf_threshold", C.c_double)]
+
+
+class OpdTrackRec(C.Structure):   # opd_track_rec (48 bytes)
+    _fields_ = [("track_id", C.c_int32), ("age", C.c_int32), ("hits", C.c_int32), ("time_since_update", C.c_int32), ("x", C.c_float * 4),
+                ("box", C.c_float * 4)]
+
+
+class OpdTrackStatus(C.Structure):   # opd_track_status
+    _fields_ = [(n, C.c_int32) for n in ("max_tracks", "max_dets", "feature_dim", "max_age", "min_hits", "device_ordinal", "n_tracks", "next_id",
+                                         "last_launches", "last_waits")]
+
+
 # name -> (restype, argtypes): every symbol include/opd_detr.h declares
 API = {
     "opd_detr_create": (C.c_int, [C.POINTER(OpdConfig), C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
@@ -149,6 +165,13 @@ API = {
     "opd_floor_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "opd_floor_transform_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "opd_floor_classify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "opd_track_create": (C.c_int, [C.POINTER(OpdTrackConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "opd_track_destroy": (None, [C.c_void_p]),
+    "opd_track_reset": (C.c_int, [C.c_void_p]),
+    "opd_track_info": (C.c_int, [C.c_void_p, C.POINTER(OpdTrackStatus)]),
+    "opd_track_update": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
+    "opd_track_get": (C.c_int, [C.c_void_p, C.POINTER(OpdTrackRec), C.c_int, C.POINTER(C.c_int)]),
+    "opd_assign": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "opd_detr_detect_frames_floor": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.POINTER(OpdDet), C.POINTER(C.c_int32),
                                                 C.c_void_p]),
     "opd_last_error": (C.c_char_p, []),
@@ -253,6 +276,9 @@ TEST_API = {
     "opd_flow_test_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     # floor-map hook (csrc/opd_floor_test_api.cpp)
     "opd_floor_test_tables": (C.c_int, [C.POINTER(OpdFloorConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    # tracker hooks (csrc/opd_track_test_api.cpp)
+    "opd_track_test_matrices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "opd_track_test_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

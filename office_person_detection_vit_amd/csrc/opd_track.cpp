@@ -1,0 +1,279 @@
+// opd_track.cpp — the tracker handle of include/opd_detr.h (opd_track_*).  An update stages the frame's detections in page-locked memory,
+// enqueues one upload, the predict / cost launch and the download of the three cost matrices on the handle's stream and waits once;
+// associates on the host (opd_assoc.cpp); updates ids and counters; uploads the list of matched and new tracks and enqueues the commit
+// launch without waiting for it.  The staging buffers have their full size from creation, so no call allocates.
+//
+// Why nothing needs a second wait: the list of the commit launch is written into its own region of the page-locked image AFTER the call's
+// wait, which also covers the previous call's upload of that region; the inputs are written before the wait, and their previous upload
+// was covered by the previous call's wait.
+#include <math.h>
+#include <string.h>
+
+#include <memory>
+#include <string>
+
+#include "opd_assoc.h"
+#include "opd_track.h"
+
+#pragma clang fp contract(off)
+
+using namespace opd;
+
+namespace {
+
+TrackDets dets_of(const opd_track* t, const uint8_t* base, int n, bool with_features) {
+    TrackDets d{};
+    d.boxes = reinterpret_cast<const float*>(base + t->o_boxes);
+    d.foot = reinterpret_cast<const float*>(base + t->o_foot);
+    d.feat = with_features ? reinterpret_cast<const float*>(base + t->o_feat) : nullptr;
+    d.has = base + t->o_has;
+    d.n = n;
+    return d;
+}
+
+void drop_all(opd_track* t) {
+    t->tracks.clear();
+    t->free_slots.clear();
+    for (int s = t->S - 1; s >= 0; --s) t->free_slots.push_back(s);   // slot 0 is handed out first
+    t->next_id = 1;
+    t->last_T = t->last_N = 0;
+}
+
+int update_body(opd_track* t, const float* boxes, const float* foot, const float* conf, const float* features, const uint8_t* has, int kind, int n,
+                int32_t* out_ids) {
+    const int T = (int)t->tracks.size(), D = t->D;
+    HIPCHK(hipSetDevice(t->device));
+    const bool with_features = features != nullptr && n > 0;
+    if (with_features && kind == OPD_MEM_DEVICE && !device_accessible(features))
+        return fail(OPD_EINVAL, "opd_track_update: OPD_MEM_DEVICE, but the features are not device-accessible memory");
+    uint8_t* h = t->io.host;
+    uint8_t* d = t->io.dev;
+    t->last_launches = t->last_waits = 0;
+    // ---- upload: [slots | boxes | foot | has] in one copy (the regions are adjacent), the features in a second one
+    int32_t* h_slots = reinterpret_cast<int32_t*>(h + t->o_slots);
+    for (int i = 0; i < T; ++i) h_slots[i] = t->tracks[i].slot;
+    if (n > 0) {
+        memcpy(h + t->o_boxes, boxes, (size_t)n * 16);
+        memcpy(h + t->o_foot, foot, (size_t)n * 8);
+        if (with_features && has) memcpy(h + t->o_has, has, (size_t)n);
+        else memset(h + t->o_has, with_features ? 1 : 0, (size_t)n);
+    }
+    HIPCHK(hipMemcpyAsync(d + t->o_slots, h + t->o_slots, t->o_feat - t->o_slots, hipMemcpyHostToDevice, t->stream));
+    if (with_features) {
+        if (kind == OPD_MEM_HOST) {
+            memcpy(h + t->o_feat, features, (size_t)n * D * 4);
+            HIPCHK(hipMemcpyAsync(d + t->o_feat, h + t->o_feat, (size_t)n * D * 4, hipMemcpyHostToDevice, t->stream));
+        } else {
+            HIPCHK(hipMemcpyAsync(d + t->o_feat, features, (size_t)n * D * 4, hipMemcpyDeviceToDevice, t->stream));
+        }
+    }
+    // ---- launch 1 and the matrices
+    const size_t mat = (size_t)T * n * 4;
+    if (T > 0) {
+        TrackPredictParams p{};
+        p.s = t->st;
+        p.d = dets_of(t, d, n, with_features);
+        p.T = T; p.D = D;
+        p.slots = reinterpret_cast<const int32_t*>(d + t->o_slots);
+        p.app = reinterpret_cast<float*>(d + t->o_app);
+        p.iou = reinterpret_cast<float*>(d + t->o_iou);
+        p.comb = reinterpret_cast<float*>(d + t->o_comb);
+        p.aw = t->aw; p.mw = t->mw;
+        p.max_dist = (float)t->max_dist;
+        HIPCHK(opd_launch_track_predict_cost(p, t->stream));
+        ++t->last_launches;
+        if (mat) {
+            HIPCHK(hipMemcpyAsync(h + t->o_app, d + t->o_app, mat, hipMemcpyDeviceToHost, t->stream));
+            HIPCHK(hipMemcpyAsync(h + t->o_iou, d + t->o_iou, mat, hipMemcpyDeviceToHost, t->stream));
+            HIPCHK(hipMemcpyAsync(h + t->o_comb, d + t->o_comb, mat, hipMemcpyDeviceToHost, t->stream));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(t->stream));
+    ++t->last_waits;
+    t->last_T = T; t->last_N = n;
+    // ---- association over the three matrices
+    for (TrackEntry& e : t->tracks) ++e.tsu;   // `Track.predict`
+    std::vector<int32_t> hits(T);
+    for (int i = 0; i < T; ++i) hits[i] = t->tracks[i].hits;
+    AssocResult a;
+    associate(reinterpret_cast<const float*>(h + t->o_app), reinterpret_cast<const float*>(h + t->o_iou), reinterpret_cast<const float*>(h + t->o_comb), T, n,
+              hits.data(), conf, t->min_hits, t->high_conf, &a);
+    for (int j = 0; j < n; ++j) out_ids[j] = -1;
+    int rc = OPD_OK;
+    if (a.new_dets.size() > t->free_slots.size()) {
+        rc = fail(OPD_EINVAL, "opd_track_update: " + std::to_string(T) + " live tracks and " + std::to_string(a.new_dets.size()) + " new ones exceed max_tracks = " +
+                                  std::to_string(t->S) + "; the frame was counted as one without detections");
+        a.matches.clear();
+        a.new_dets.clear();
+    }
+    // ---- counters, ids and the list of the commit launch
+    int32_t* ops = reinterpret_cast<int32_t*>(h + t->o_ops);
+    int M = 0;
+    for (const auto& m : a.matches) {
+        TrackEntry& e = t->tracks[m.first];
+        ops[4 * M] = e.slot; ops[4 * M + 1] = m.second; ops[4 * M + 2] = TRACK_OP_MATCHED; ops[4 * M + 3] = e.tsu;
+        ++M;
+        ++e.age; ++e.hits; e.tsu = 0;
+        out_ids[m.second] = e.id;
+    }
+    for (int j : a.new_dets) {
+        TrackEntry e{t->free_slots.back(), t->next_id++, 1, 1, 0};
+        t->free_slots.pop_back();
+        ops[4 * M] = e.slot; ops[4 * M + 1] = j; ops[4 * M + 2] = TRACK_OP_NEW; ops[4 * M + 3] = 0;
+        ++M;
+        t->tracks.push_back(e);
+        out_ids[j] = e.id;
+    }
+    if (M > 0) {
+        HIPCHK(hipMemcpyAsync(d + t->o_ops, h + t->o_ops, (size_t)M * 16, hipMemcpyHostToDevice, t->stream));
+        TrackCommitParams c{};
+        c.s = t->st;
+        c.d = dets_of(t, d, n, with_features);
+        c.M = M; c.D = D;
+        c.ops = reinterpret_cast<const int32_t*>(d + t->o_ops);
+        HIPCHK(opd_launch_track_commit(c, t->stream));
+        ++t->last_launches;
+    }
+    // ---- tracks that went max_age frames without a match leave; their slots are free for the next frame
+    size_t keep = 0;
+    for (size_t i = 0; i < t->tracks.size(); ++i) {
+        if (t->tracks[i].tsu < t->max_age) t->tracks[keep++] = t->tracks[i];
+        else t->free_slots.push_back(t->tracks[i].slot);
+    }
+    t->tracks.resize(keep);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int opd_track_create(const opd_track_config* cfg, int device_ordinal, opd_track** out) {
+    ApiScope api_scope;
+    return guarded("opd_track_create", [&]() -> int {
+        const std::string me = "opd_track_create: ";
+        if (!out) return fail(OPD_EINVAL, me + "null argument");
+        *out = nullptr;
+        if (!cfg) return fail(OPD_EINVAL, me + "null configuration");
+        if (cfg->struct_size != (int32_t)sizeof(opd_track_config))
+            return fail(OPD_EINVAL, me + "struct_size " + std::to_string(cfg->struct_size) + ", this library's opd_track_config has " + std::to_string(sizeof(opd_track_config)) + " bytes");
+        const opd_track_config& c = *cfg;
+        const int S = c.max_tracks ? c.max_tracks : 128, NM = c.max_dets ? c.max_dets : 128, D = c.feature_dim ? c.feature_dim : 512;
+        if (S < 1 || S > TRACK_MAX_TRACKS) return fail(OPD_EINVAL, me + "max_tracks " + std::to_string(S) + " outside 1 .. 1024");
+        if (NM < 1 || NM > TRACK_MAX_DETS) return fail(OPD_EINVAL, me + "max_dets " + std::to_string(NM) + " outside 1 .. 1024");
+        if (D < 1 || D > TRACK_MAX_DIM) return fail(OPD_EINVAL, me + "feature_dim " + std::to_string(D) + " outside 1 .. 2048");
+        if (c.max_age < 0 || c.min_hits < 0) return fail(OPD_EINVAL, me + "max_age and min_hits must not be negative");
+        double aw = c.appearance_weight, mw = c.motion_weight;
+        if (aw == 0.0 && mw == 0.0) { aw = 0.7; mw = 0.3; }
+        if (!(aw >= 0.0) || !(mw >= 0.0) || !(fabs(aw + mw - 1.0) <= 1e-6))
+            return fail(OPD_EINVAL, me + "appearance_weight (" + std::to_string(aw) + ") + motion_weight (" + std::to_string(mw) + ") must equal 1.0");
+        if (!(c.high_conf_threshold == c.high_conf_threshold) || !(c.max_position_distance == c.max_position_distance))
+            return fail(OPD_EINVAL, me + "a threshold is not a number");
+        RCCHK(use_device("opd_track_create", device_ordinal));
+        std::unique_ptr<opd_track, decltype(&opd_track_destroy)> t(new opd_track(), opd_track_destroy);   // a failure below releases whatever was already made
+        t->device = device_ordinal;
+        t->S = S; t->NM = NM; t->D = D;
+        t->max_age = c.max_age ? c.max_age : 30;
+        t->min_hits = c.min_hits ? c.min_hits : 3;
+        t->iou_threshold = c.iou_threshold != 0.0 ? c.iou_threshold : 0.3;
+        t->aw = aw; t->mw = mw;
+        t->max_dist = c.max_position_distance == 0.0 ? 150.0 : c.max_position_distance;
+        t->high_conf = c.high_conf_threshold != 0.0 ? c.high_conf_threshold : 0.5;
+        RCCHK(made("opd_track_create", "stream creation", hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)));
+        // the state: one allocation, zeroed
+        size_t off = 0;
+        auto place = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+        const size_t s_x = place((size_t)S * 16), s_P = place((size_t)S * 64), s_last = place((size_t)S * 8), s_box = place((size_t)S * 16);
+        const size_t s_ring = place((size_t)S * TRACK_RING * D * 4), s_meta = place((size_t)S * 8), s_smooth = place((size_t)S * D * 4);
+        RCCHK(made("opd_track_create", "state allocation", hipMalloc((void**)&t->d_state, off)));
+        RCCHK(made("opd_track_create", "state clearing", hipMemset(t->d_state, 0, off)));
+        t->st.x = reinterpret_cast<float*>(t->d_state + s_x);
+        t->st.P = reinterpret_cast<float*>(t->d_state + s_P);
+        t->st.last = reinterpret_cast<float*>(t->d_state + s_last);
+        t->st.box = reinterpret_cast<float*>(t->d_state + s_box);
+        t->st.ring = reinterpret_cast<float*>(t->d_state + s_ring);
+        t->st.ring_meta = reinterpret_cast<int32_t*>(t->d_state + s_meta);
+        t->st.smooth = reinterpret_cast<float*>(t->d_state + s_smooth);
+        // the staging pair: inputs (adjacent, one copy), the commit list, the three matrices
+        off = 0;
+        t->o_slots = place((size_t)S * 4); t->o_boxes = place((size_t)NM * 16); t->o_foot = place((size_t)NM * 8); t->o_has = place((size_t)NM);
+        t->o_feat = place((size_t)NM * D * 4); t->o_ops = place((size_t)S * 16);
+        t->o_app = place((size_t)S * NM * 4); t->o_iou = place((size_t)S * NM * 4); t->o_comb = place((size_t)S * NM * 4);
+        t->io_bytes = off;
+        RCCHK(t->io.reserve("opd_track_create", off, off, t->stream));
+        memset(t->io.host, 0, off);
+        drop_all(t.get());
+        ++g_handle_epoch;   // device memory changed hands: graphs captured before are captured again (opd_device.h)
+        *out = t.release();
+        return OPD_OK;
+    });
+}
+
+extern "C" void opd_track_destroy(opd_track* t) {
+    if (!t) return;
+    ApiScope api_scope;
+    (void)hipSetDevice(t->device);
+    if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
+    if (t->d_state) (void)hipFree(t->d_state);
+    t->io.release();
+    delete t;
+    ++g_handle_epoch;
+}
+
+extern "C" int opd_track_reset(opd_track* t) {
+    ApiScope api_scope;
+    if (!t) return fail(OPD_EINVAL, "opd_track_reset: null handle");
+    drop_all(t);   // (a new track initialises every number of its slot: nothing on the device needs clearing)
+    return OPD_OK;
+}
+
+extern "C" int opd_track_info(const opd_track* t, opd_track_status* info) {
+    if (!t || !info) return fail(OPD_EINVAL, "opd_track_info: null argument");
+    *info = opd_track_status{t->S, t->NM, t->D, t->max_age, t->min_hits, t->device, (int32_t)t->tracks.size(), t->next_id, t->last_launches, t->last_waits};
+    return OPD_OK;
+}
+
+extern "C" int opd_track_update(opd_track* t, const float* boxes_xywh, const float* foot_xy, const float* confidence, const float* features,
+                                const uint8_t* has_feature, int feat_mem_kind, int n, int32_t* out_ids) {
+    ApiScope api_scope;
+    return guarded("opd_track_update", [&]() -> int {
+        if (!t) return fail(OPD_EINVAL, "opd_track_update: null handle");
+        if (n < 0) return fail(OPD_EINVAL, "opd_track_update: negative detection count");
+        if (n > t->NM) return fail(OPD_EINVAL, "opd_track_update: " + std::to_string(n) + " detections, the handle was made for max_dets = " + std::to_string(t->NM));
+        if (n > 0 && (!boxes_xywh || !foot_xy || !confidence || !out_ids)) return fail(OPD_EINVAL, "opd_track_update: null boxes, foot points, confidences or output");
+        if (feat_mem_kind != OPD_MEM_HOST && feat_mem_kind != OPD_MEM_DEVICE) return fail(OPD_EINVAL, "opd_track_update: feat_mem_kind must be OPD_MEM_HOST or OPD_MEM_DEVICE");
+        return update_body(t, boxes_xywh, foot_xy, confidence, features, has_feature, feat_mem_kind, n, out_ids);
+    });
+}
+
+extern "C" int opd_track_get(opd_track* t, opd_track_rec* out, int capacity, int* count) {
+    ApiScope api_scope;
+    return guarded("opd_track_get", [&]() -> int {
+        if (!t || !count) return fail(OPD_EINVAL, "opd_track_get: null argument");
+        const int T = (int)t->tracks.size();
+        *count = T;
+        if (!out && capacity == 0) return OPD_OK;
+        if (!out || capacity < T) return fail(OPD_EINVAL, "opd_track_get: " + std::to_string(T) + " tracks, room for " + std::to_string(capacity));
+        if (T == 0) return OPD_OK;
+        HIPCHK(hipSetDevice(t->device));
+        std::vector<float> x((size_t)t->S * 4), box((size_t)t->S * 4);
+        HIPCHK(hipMemcpyAsync(x.data(), t->st.x, x.size() * 4, hipMemcpyDeviceToHost, t->stream));
+        HIPCHK(hipMemcpyAsync(box.data(), t->st.box, box.size() * 4, hipMemcpyDeviceToHost, t->stream));
+        HIPCHK(hipStreamSynchronize(t->stream));
+        for (int i = 0; i < T; ++i) {
+            const TrackEntry& e = t->tracks[i];
+            out[i] = opd_track_rec{e.id, e.age, e.hits, e.tsu, {}, {}};
+            memcpy(out[i].x, x.data() + 4 * (size_t)e.slot, 16);
+            memcpy(out[i].box, box.data() + 4 * (size_t)e.slot, 16);
+        }
+        return OPD_OK;
+    });
+}
+
+extern "C" int opd_assign(const double* cost, int rows, int cols, int32_t* row_to_col) {
+    return guarded("opd_assign", [&]() -> int {
+        if (rows < 0 || cols < 0) return fail(OPD_EINVAL, "opd_assign: negative size");
+        if (rows > 0 && !row_to_col) return fail(OPD_EINVAL, "opd_assign: null output");
+        if (rows > 0 && cols > 0 && !cost) return fail(OPD_EINVAL, "opd_assign: null cost matrix");
+        assign_rect(cost, rows, cols, row_to_col);
+        return OPD_OK;
+    });
+}

@@ -1,0 +1,173 @@
+"""``HipTracker``: the reference's ``Tracker`` (src/tracking/tracker.py) with the per-frame work on the device.
+
+``update(detections)`` is one ``opd_track_update``: Kalman predict, the three cost matrices, the five association stages, Kalman update with
+the re-update after an occlusion, new tracks and deletions (``csrc/kernels_track.hip``, ``csrc/opd_assoc.cpp``, ``csrc/opd_track.cpp``).
+The Kalman state, the boxes and the feature history live on the device; what ``TrackingPhase`` and the exporters read of a track
+(``track_id``, ``detection``, counters, ``trajectory``) is kept here on the host.  In ``TrackingPhase.initialize`` the swap is one line:
+
+    self.tracker = HipTracker(max_age=..., min_hits=..., iou_threshold=..., appearance_weight=..., motion_weight=...)
+
+One difference from the reference: a low-confidence detection never starts a track, also when no track is alive (the reference starts
+one from every detection in that one case)."""
+
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass, field
+import logging
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+
+from . import _capi
+from .data_models import Detection
+
+logger = logging.getLogger(__name__)
+
+
+@dataclass
+class HipTrack:
+    """What the reference's ``Track`` shows to its readers; the Kalman state is fetched from the device on demand."""
+
+    track_id: int
+    detection: Detection
+    age: int = 1
+    hits: int = 1
+    time_since_update: int = 0
+    trajectory: List[Tuple[float, float]] = field(default_factory=list)
+    _owner: Optional["HipTracker"] = field(default=None, repr=False, compare=False)
+
+    def is_confirmed(self, min_hits: int = 3) -> bool:
+        return self.hits >= min_hits
+
+    def is_tentative(self) -> bool:
+        return not self.is_confirmed()
+
+    def get_state(self) -> dict:
+        x = self._owner._state_of(self.track_id) if self._owner is not None else [float("nan")] * 4
+        return {"track_id": self.track_id, "position": [x[0], x[1]], "velocity": [x[2], x[3]], "age": self.age, "hits": self.hits,
+                "time_since_update": self.time_since_update, "trajectory_length": len(self.trajectory)}
+
+
+class HipTracker:
+    def __init__(self, max_age: int = 30, min_hits: int = 3, iou_threshold: float = 0.3, appearance_weight: float = 0.7, motion_weight: float = 0.3,
+                 max_position_distance: float = 150.0, high_conf_threshold: float = 0.5, *, feature_dim: int = 512, max_tracks: int = 256,
+                 max_dets: int = 256, device: str = "hip:0"):
+        if abs(appearance_weight + motion_weight - 1.0) > 1e-6:   # SimilarityCalculator.__init__
+            raise ValueError(f"appearance_weight ({appearance_weight}) + motion_weight ({motion_weight}) must equal 1.0")
+        for name, v in (("max_age", max_age), ("min_hits", min_hits), ("high_conf_threshold", high_conf_threshold)):
+            if not v > 0:
+                raise ValueError(f"{name} must be positive (a zero means 'the default' to the native library)")
+        self.max_age, self.min_hits, self.iou_threshold = max_age, min_hits, iou_threshold
+        self.appearance_weight, self.motion_weight = appearance_weight, motion_weight
+        self.max_position_distance, self.high_conf_threshold = max_position_distance, high_conf_threshold
+        self.feature_dim, self.max_tracks, self.max_dets = int(feature_dim), int(max_tracks), int(max_dets)
+        self.device_ordinal = int(str(device).split(":")[1]) if ":" in str(device) else 0
+        self.tracks: List[HipTrack] = []
+        self.next_id = 1
+        self._lib = _capi.load_library()   # raises when the library was not built: there is no host fallback
+        self._h = C.c_void_p()   # made by the first update: constructing a tracker touches no device, as the reference's does not
+        logger.info("HipTracker initialized: max_age=%s, min_hits=%s, high_conf_threshold=%s, feature_dim=%s", max_age, min_hits, high_conf_threshold, feature_dim)
+
+    def _ensure(self) -> None:
+        if self._h:
+            return
+        weights_default = self.appearance_weight == 0.7 and self.motion_weight == 0.3
+        cfg = _capi.OpdTrackConfig(struct_size=C.sizeof(_capi.OpdTrackConfig), max_tracks=self.max_tracks, max_dets=self.max_dets, feature_dim=self.feature_dim,
+                                   max_age=int(self.max_age), min_hits=int(self.min_hits), iou_threshold=float(self.iou_threshold),
+                                   appearance_weight=0.0 if weights_default else float(self.appearance_weight),
+                                   motion_weight=0.0 if weights_default else float(self.motion_weight),
+                                   max_position_distance=float(self.max_position_distance) if self.max_position_distance > 0 else -1.0,
+                                   high_conf_threshold=float(self.high_conf_threshold))
+        _capi.check(self._lib.opd_track_create(C.byref(cfg), self.device_ordinal, C.byref(self._h)), "opd_track_create")
+
+    # ---- the reference's surface ----------------------------------------------------------------------------------------------------
+    def update(self, detections: List[Detection]) -> List[Detection]:
+        """Sets ``track_id`` on the detections in place and returns those that have one."""
+        n, D = len(detections), self.feature_dim
+        boxes, foot, conf = np.zeros((n, 4), np.float32), np.zeros((n, 2), np.float32), np.zeros(n, np.float32)
+        has = np.zeros(n, np.uint8)
+        feats = None
+        for j, det in enumerate(detections):
+            if det.camera_coords is None:
+                raise ValueError(f"detection {j} has no camera_coords: a track cannot be started or updated without a foot point")
+            boxes[j], foot[j], conf[j] = det.bbox, det.camera_coords, det.confidence
+            if det.features is not None:
+                f = np.asarray(det.features, np.float32).reshape(-1)
+                if f.shape[0] != D:
+                    raise ValueError(f"detection {j} has a feature of width {f.shape[0]}, the tracker was made for {D}")
+                if feats is None:
+                    feats = np.zeros((n, D), np.float32)
+                feats[j], has[j] = f, 1
+        self._ensure()
+        ids = np.full(max(n, 1), -1, np.int32)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        rc = self._lib.opd_track_update(self._h, p(boxes), p(foot), p(conf), p(feats), p(has), _capi.OPD_MEM_HOST, n, p(ids))
+        if rc != 0 and "counted as one without detections" in _capi.last_error():
+            self._apply([], ids[:0])   # out of slots: the native side aged every track and matched none; the mirror follows before the error is raised
+        _capi.check(rc, "opd_track_update")
+        self._apply(detections, ids[:n])
+        return [det for det in detections if det.track_id is not None]
+
+    def get_tracks(self) -> List[HipTrack]:
+        return self.tracks.copy()
+
+    def get_confirmed_tracks(self) -> List[HipTrack]:
+        return [t for t in self.tracks if t.is_confirmed(self.min_hits)]
+
+    def reset(self) -> None:
+        if self._h:
+            _capi.check(self._lib.opd_track_reset(self._h), "opd_track_reset")
+        self.tracks, self.next_id = [], 1
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.opd_track_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown
+            pass
+
+    # ---- the host mirror ------------------------------------------------------------------------------------------------------------
+    def _records(self):
+        n = C.c_int()
+        _capi.check(self._lib.opd_track_get(self._h, None, 0, C.byref(n)), "opd_track_get")
+        recs = (_capi.OpdTrackRec * max(n.value, 1))()
+        _capi.check(self._lib.opd_track_get(self._h, recs, n.value, C.byref(n)), "opd_track_get")
+        return [recs[i] for i in range(n.value)]
+
+    def _state_of(self, track_id: int) -> List[float]:
+        for r in self._records():
+            if r.track_id == track_id:
+                return [float(v) for v in r.x]
+        raise KeyError(f"track {track_id} is not alive")
+
+    def _apply(self, detections: List[Detection], ids: np.ndarray) -> None:
+        """Replay on the host objects what the native update did to its counters: predict, matches, new tracks, deletions."""
+        by_id: Dict[int, HipTrack] = {t.track_id: t for t in self.tracks}
+        for t in self.tracks:
+            t.time_since_update += 1
+        for det, tid in zip(detections, ids.tolist()):
+            if tid < 0:
+                continue
+            det.track_id = tid
+            t = by_id.get(tid)
+            if t is None:
+                t = HipTrack(track_id=tid, detection=det, trajectory=[det.camera_coords], _owner=self)
+                self.tracks.append(t)
+                by_id[tid] = t
+            else:
+                t.detection = det
+                t.age += 1
+                t.hits += 1
+                t.time_since_update = 0
+                t.trajectory.append(det.camera_coords)
+        self.tracks = [t for t in self.tracks if t.time_since_update < self.max_age]
+        info = _capi.OpdTrackStatus()
+        _capi.check(self._lib.opd_track_info(self._h, C.byref(info)), "opd_track_info")
+        self.next_id = info.next_id
+        if info.n_tracks != len(self.tracks):
+            raise RuntimeError(f"host mirror out of step with the native tracker: {len(self.tracks)} tracks here, {info.n_tracks} there")
