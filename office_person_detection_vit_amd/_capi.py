@@ -12,7 +12,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libopd_hip.so")
-TEST_LIB_PATH = os.path.join(_HERE, "libopd_hip_test.so")   # the same objects + csrc/opd_test_api.cpp: tests/ and tools/ only
+TEST_LIB_PATH = os.path.join(_HERE, "libopd_hip_test.so")   # the same objects + csrc/opd_*test*_api.cpp: tests/ and tools/ only
 
 OPD_PIXELS_U8_BGR_HWC = 0
 OPD_PIXELS_F32_NCHW = 1
@@ -178,7 +178,8 @@ API = {
     "opd_version": (C.c_char_p, []),
 }
 
-# kernel-level test hooks (csrc/opd_test_api.cpp); not part of the boundary
+# test hooks (csrc/opd_test_api.cpp: kernels; opd_test_bench_api.cpp: tools/ timing and traces; opd_test_model_api.cpp: host helpers and
+# handle switches); not part of the boundary
 TEST_API = {
     "opd_test_conv_gemm": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 15),
     "opd_test_gemm_splitk_ln": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 3),
@@ -245,7 +246,6 @@ TEST_API = {
     "opd_test_dec_ffn": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
     "opd_test_bench_dec": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_float)]),
     "opd_test_heads_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 13 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "opd_test_set_fused_dec": (C.c_int, [C.c_void_p, C.c_int]),
     "opd_test_set_elem_bf16": (C.c_int, [C.c_int]),
     "opd_test_trace_dec_self": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
     # Re-ID hooks (csrc/opd_reid_test_api.cpp)
@@ -261,7 +261,6 @@ TEST_API = {
     "opd_test_reid_l2norm": (C.c_int, [C.c_void_p] + [C.c_int] * 2),
     # OSNet hooks (csrc/opd_osnet_test_api.cpp)
     "opd_test_osnet_lut": (C.c_int, [C.c_void_p]),
-    "opd_test_osnet_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "opd_test_osnet_pixels_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "opd_test_osnet_stem": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 2),
     "opd_test_osnet_gemm": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -289,7 +288,7 @@ def load_library(test_hooks: bool = False) -> C.CDLL:
     """dlopen libopd_hip.so (built in-tree by ``csrc/build.py``) and attach prototypes.  Raises if it is missing.
 
     ``test_hooks=True`` (tests/ and tools/ only; also ``OPD_TEST_HOOKS=1`` in the environment) loads ``libopd_hip_test.so`` instead:
-    the same objects plus the ``opd_test_*`` hooks of ``csrc/opd_test_api.cpp``.  One process uses ONE of the two (the hooks flip
+    the same objects plus the ``opd_test_*`` hooks of ``csrc/opd_*test*_api.cpp``.  One process uses ONE of the two (the hooks flip
     process-wide switches of the library they live in), so asking for the hooks after the product library has been loaded raises."""
     global _lib, _lib_has_hooks
     test_hooks = test_hooks or os.environ.get("OPD_TEST_HOOKS") == "1"

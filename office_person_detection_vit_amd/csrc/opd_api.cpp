@@ -380,8 +380,7 @@ void opd_detr_destroy(opd_detr* m) {
     for (auto& e : m->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : m->event_pool) (void)hipEventDestroy(e);
-    for (auto& g : m->graphs)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    drop_graphs(m);
     drop_streams(m);
     delete m;
     ++g_handle_epoch;
@@ -651,9 +650,7 @@ int opd_detr_set_profiling(opd_detr* m, int enabled) {
     if (mode != m->profiling) {   // the stage marks of mode 2 are nodes of the captured graph: graphs of another mode do not carry them
         HIPCHK(hipSetDevice(m->device));
         HIPCHK(hipStreamSynchronize(m->stream));
-        for (auto& g : m->graphs)
-            if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        m->graphs.clear();
+        drop_graphs(m);
     }
     m->profiling = mode;
     return OPD_OK;

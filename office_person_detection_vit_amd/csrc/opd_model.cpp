@@ -1220,6 +1220,13 @@ std::atomic<unsigned> g_handle_epoch{0};
 std::atomic<int> g_graph_guard{1};   // opd_test_set_graph_guard(0): leave stale-epoch graphs alone (diagnosis only)
 thread_local std::shared_lock<std::shared_mutex>* tl_api_lock = nullptr;
 
+// Every captured graph of the handle holds the launch sequence of the switches, taps and profiling mode it was captured under
+void drop_graphs(opd_detr* m) {
+    for (auto& g : m->graphs)
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    m->graphs.clear();
+}
+
 // Forward through the graph cache.  First call of a (shape, pixel pointer) key runs eagerly (one-time function-attribute
 // setup and plan building are not capturable); the second call captures the stream into a hipGraph; later calls replay it.
 int run_forward(opd_detr* m, const void* d_pixels, int pixel_format, int B, int H, int W, const int32_t* valid_hw) {

@@ -1,7 +1,7 @@
 // opd_model.h — PRIVATE header of libopd_hip: the device model (weights, workspace, per-resolution plans, graph cache) behind the opaque
 // `opd_detr` handle of include/opd_detr.h.  Included by opd_model.cpp (weights, workspace, plans, the forward), opd_api.cpp (the C-ABI and the
-// detect pipeline behind it), opd_comm.cpp and opd_test_api.cpp (the test hooks of libopd_hip_test.so, which reach into a handle to flip its
-// fusion switches); never installed, never seen by a caller.
+// detect pipeline behind it), opd_comm.cpp, and opd_test_model_api.cpp / opd_test_bench_api.cpp (the test hooks of libopd_hip_test.so that reach into a handle to flip
+// its fusion switches, or plan a trunk); never installed, never seen by a caller.
 #pragma once
 #include <math.h>
 #include <stdlib.h>
@@ -322,6 +322,7 @@ int fill_qc0(opd_detr* m);
 int build_weights(opd_detr* m, const StateDict& sd);
 int build_workspace(opd_detr* m);
 int run_forward(opd_detr* m, const void* d_pixels, int pixel_format, int B, int H, int W, const int32_t* valid_hw = nullptr);
+void drop_graphs(opd_detr* m);   // destroy the handle's graph executables and clear the cache: the next forwards run eagerly, then capture anew
 enum { CLS_CONV = 0, CLS_GEMM = 1, CLS_ATTN = 2, CLS_OTHER = 3 };
 int timed_begin(opd_detr* m, int cls, double flops);
 int timed_end(opd_detr* m);

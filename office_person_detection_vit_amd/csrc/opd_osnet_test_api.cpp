@@ -6,19 +6,13 @@
 #include <vector>
 
 #include "opd_osnet.h"
-#include "opd_reid_test_util.h"
+#include "opd_test_util.h"
 
 using namespace opd;
 
 // the normalisation table: lut[c * 256 + u8] fp16 bits
 TAPI int opd_test_osnet_lut(uint16_t* lut) {
     osnet_pixel_lut(lut);
-    return OPD_OK;
-}
-
-// host geometry of n boxes: out[i][13] = x1 y1 x2 y2 zero rh rw top left wy0 wx0 wy1 wx1
-TAPI int opd_test_osnet_geometry(const float* boxes, int n, int H, int W, int32_t* out) {
-    geometry_rows(CROP_OSNET, boxes, n, H, W, out);
     return OPD_OK;
 }
 

@@ -6,7 +6,7 @@
 #include <vector>
 
 #include "opd_clip.h"
-#include "opd_reid_test_util.h"
+#include "opd_test_util.h"
 
 using namespace opd;
 
