@@ -367,6 +367,20 @@ OPD_API int opd_reid_info(const opd_reid* r, opd_reid_model_info* info);
  * for OPD_MEM_DEVICE.  `out` = host float32 [n_boxes][feature_dim].  Synchronous. */
 OPD_API int opd_reid_extract(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, int n_frames, int mem_kind,
                              const float* boxes_xywh, const int32_t* box_frame, int n_boxes, float* out);
+/* opd_detr_detect_frames (host frames, host outputs) plus the Re-ID feature row of the first `slots` records labelled `label`, taken in
+ * (frame, record index) order, behind ONE host wait: the crops are planned on the device from the records (box = x1, y1,
+ * float32(x2 - x1), float32(y2 - y1), as opd_reid_extract would be handed it) and read in place from the camera-resolution frames this
+ * call uploaded.  `features` = host float32 [slots][feature_dim]; row k belongs to record slot_map[k] = frame * num_queries +
+ * query_index (host int32 [slots]); *n_person = the number of such records in the batch.  Rows and slot_map entries k >= min(*n_person,
+ * slots) are not written.  *n_person > slots is not an error: the caller fetches the remaining rows with opd_reid_extract.  Suppression
+ * (opd_person_nms) stays on the host afterwards; a suppressed record's row is unused.  OPD_EINVAL before any device work: a null
+ * handle or output, slots < 1 or > max_crops, handles on different devices, B > max_batch, frame sizes outside the detector handle's
+ * limits.
+ * A Re-ID handle serves ONE call at a time: a thread that enters this call or opd_reid_extract while another call on the same opd_reid
+ * is running waits for it to finish. */
+OPD_API int opd_detr_detect_frames_reid(opd_detr* m, opd_reid* r, const uint8_t* const* frames, int B, int h, int w, int H, int W,
+                                        float threshold, int label, int slots, opd_det* out, int32_t* counts,
+                                        float* features /*[slots][feature_dim]*/, int32_t* slot_map /*[slots]*/, int32_t* n_person);
 
 /* ---- Sparse optical flow: pyramidal Lucas-Kanade between consecutive frames (third handle type: two gray pyramids, own stream) --------
  * Replaces the per-frame work of `OpticalFlowTracker.track` (src/tracking/lightweight_tracker.py:141-202), which the reference's hybrid

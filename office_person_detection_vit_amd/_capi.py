@@ -155,6 +155,8 @@ API = {
     "opd_reid_info": (C.c_int, [C.c_void_p, C.POINTER(OpdReidModelInfo)]),
     "opd_reid_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_void_p]),
+    "opd_detr_detect_frames_reid": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int, C.POINTER(OpdDet),
+                                               C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "opd_flow_create": (C.c_int, [C.POINTER(OpdFlowConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "opd_flow_destroy": (None, [C.c_void_p]),
     "opd_flow_set_reference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -271,6 +273,10 @@ TEST_API = {
     "opd_test_osnet_head": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3),
     "opd_test_reid_kernel_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                              C.POINTER(OpdKernelStat), C.c_int, C.POINTER(C.c_int)]),
+    # crop-planner hooks (csrc/opd_crop_test_api.cpp): model, boxes, n, H, W, geom, meta, src_off, bx, by, ch, cv, cap
+    "opd_test_crop_plan_device": (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 7 + [C.c_int]),
+    "opd_test_crop_plan_host": (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 7 + [C.c_int]),
+    "opd_test_crop_plan_staged": (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 7 + [C.c_int]),
     # optical-flow hook (csrc/opd_flow_test_api.cpp)
     "opd_flow_test_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     # floor-map hook (csrc/opd_floor_test_api.cpp)

@@ -7,6 +7,7 @@
 
 #include "opd_floor.h"
 #include "opd_model.h"
+#include "opd_reid.h"
 
 namespace opd {
 
@@ -144,7 +145,9 @@ static void unpack_records(const opd_detr* m, const void* pinned, int B, opd_det
 
 // (`features` != null: the [B][Q][d_model] feature rows behind the counts travel in the same copy)
 // (`fmap_out` != null: the floor records of the batch follow in a copy of their own, before the same wait; only rows of records labelled `label` are handed on)
-static int fetch_records(opd_detr* m, opd_det* out, int32_t* counts, int mem_kind, float* features = nullptr, opd_floor_rec* fmap_out = nullptr, int label = 0) {
+// (`reid` != null: the Re-ID rows, slot map and person count of its call follow likewise)
+static int fetch_records(opd_detr* m, opd_det* out, int32_t* counts, int mem_kind, float* features = nullptr, opd_floor_rec* fmap_out = nullptr, int label = 0,
+                         ReidFusedCall* reid = nullptr) {
     const int B = m->last_B;
     if (!outputs_on_device(mem_kind)) {   // (device callers had the post-process kernel write into their buffers)
         // one copy of [records of max_batch frames | counts (| features)] into page-locked memory (a copy into the caller's pageable arrays is
@@ -152,6 +155,7 @@ static int fetch_records(opd_detr* m, opd_det* out, int32_t* counts, int mem_kin
         if (!m->sync_pinned) HIPCHK(hipHostMalloc(&m->sync_pinned, feat_off(m) + m->cfg.max_batch * feat_row(m), hipHostMallocDefault));
         HIPCHK(hipMemcpyAsync(m->sync_pinned, m->d_records, features ? feat_off(m) + B * feat_row(m) : rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
         if (fmap_out) HIPCHK(hipMemcpyAsync(m->h_floor, m->d_floor, (size_t)B * m->arch.queries * sizeof(opd_floor_rec), hipMemcpyDeviceToHost, m->stream));
+        if (reid) RCCHK(reid->copy_back(m->stream));
         HIPCHK(hipStreamSynchronize(m->stream));
         unpack_records(m, m->sync_pinned, B, out, counts, features);
         if (fmap_out) {
@@ -199,6 +203,13 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
         fp.records = m->d_records; fp.counts = m->d_counts; fp.Q = Q; fp.label = s.label;
         fp.out = m->d_floor;
         HIPCHK(opd_launch_floor(fp, m->stream));
+    }
+    if (s.feature == FEAT_REID) {   // select, plan and the Re-ID forward behind the post-process; the rows come back behind the records, before the one wait
+        ReidFusedCall call(s.reid);
+        RCCHK(call.enqueue(m->stream, m->d_records, m->d_counts, d_camera, B, Q, h, w, s.label, s.slots));
+        RCCHK(fetch_records(m, s.out, s.counts, s.mem_kind, nullptr, nullptr, s.label, &call));
+        call.deliver(s.features, s.slot_map, s.n_person);
+        return OPD_OK;
     }
     if (s.wait == WAIT_NONE) return OPD_OK;
     if (s.wait == WAIT_BLOCKING) return fetch_records(m, s.out, s.counts, s.mem_kind, s.features, s.fmap ? s.fmap_out : nullptr, s.label);   // records, counts and feature rows: one copy, one wait
@@ -552,6 +563,22 @@ int opd_detr_detect_frames_floor(opd_detr* m, opd_floor* f, const uint8_t* const
     }
     return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr,
                            {threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_NONE, label, nullptr, f, floor});
+}
+
+// The Re-ID twin: same upload, forward and post-process; two small kernels then pick the records of the class and plan their crops from the boxes
+// the Python shim derives, read in place from the CAMERA-resolution frames this call has just put on the device; `r`'s forward runs on its own
+// stream between two events, and its rows travel behind the records before the one wait.
+int opd_detr_detect_frames_reid(opd_detr* m, opd_reid* r, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold, int label,
+                                int slots, opd_det* out, int32_t* counts, float* features, int32_t* slot_map, int32_t* n_person) {
+    ApiScope api_scope;
+    if (!r) return fail(OPD_EINVAL, "opd_detr_detect_frames_reid: null Re-ID handle");
+    RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && features && slot_map && n_person, "opd_detr_detect_frames_reid"));
+    RCCHK(reid_fused_check(r, m->device, slots, "opd_detr_detect_frames_reid"));
+    if (h < 1 || w < 1 || (size_t)h * w > (size_t)1 << 26)
+        return fail(OPD_EINVAL, "opd_detr_detect_frames_reid: source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
+    HIPCHK(hipSetDevice(m->device));
+    RecordSink sink{threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_REID, label, features, nullptr, nullptr, r, slots, slot_map, n_person};
+    return guarded("opd_detr_detect_frames_reid", [&] { return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr, sink); });
 }
 
 int opd_host_alloc(size_t bytes, void** out) {

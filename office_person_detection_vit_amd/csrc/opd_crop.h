@@ -1,10 +1,14 @@
 // opd_crop.h — the Pillow-exact crop path both Re-ID models share (opd_crop.cpp): what a model asks of it (CropSpec), the geometry of one
-// box, the coefficient tables of one axis, the host resampler, and the device resampler the two pre-processing kernels call.
+// box, the coefficient tables of one axis, the host resampler, the per-output restatement of geometry and tables that the device crop
+// planner (kernels_crop.hip) and the host share, and the device resampler the two pre-processing kernels call.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <vector>
+
+#include "../../include/opd_detr.h"
 
 namespace opd {
 
@@ -49,6 +53,122 @@ void crop_axis_tables(const CropSpec& spec, const ReidGeom& g, bool horizontal, 
 
 // Host restatement of the device resampler for ONE crop of frame [H][W][3] BGR: uint8 RGB [out_h][out_w][3] (zeros for a degenerate box)
 void crop_resample_host(const CropSpec& spec, const uint8_t* frame, int W, const ReidGeom& g, uint8_t* rgb);
+
+// ---- shared by the host and the device crop planner (kernels_crop.hip) -----------------------------------------------------------------
+// The pieces of crop_geometry and of opd_resize_coeffs_filter (opd_host.cpp) restated per box and per OUTPUT, so that one thread can
+// evaluate one output column or row: the same double operations in the same order, no fused multiply-adds (the pragma in every body;
+// kernels_crop.hip is compiled with -ffp-contract=off besides).  tests/test_crop_plan_cpu.py holds the host instantiation to the two
+// originals bit for bit, tests/test_detect_reid_gpu.py the device instantiation to the host one.
+#define OPD_HD __host__ __device__ inline
+
+OPD_HD int crop_py_int(double v) {   // Python's int() of a finite float (truncation), saturated far outside any frame; NaN -> 0
+    if (!(v == v)) return 0;
+    if (v > 1e9) return 1000000000;
+    if (v < -1e9) return -1000000000;
+    return (int)v;
+}
+
+// crop_geometry without the source window: crop rectangle, degeneracy, resized size, window offset
+OPD_HD void crop_box_geometry(const CropSpec& spec, double x, double y, double w, double h, int H, int W, ReidGeom* g) {
+#pragma clang fp contract(off)
+    *g = ReidGeom{};
+    g->x1 = crop_py_int(fmax(0.0, x));
+    g->y1 = crop_py_int(fmax(0.0, y));
+    g->x2 = crop_py_int(fmin((double)W, x + w));
+    g->y2 = crop_py_int(fmin((double)H, y + h));
+    g->zero = g->x2 <= g->x1 || g->y2 <= g->y1;
+    g->rh = spec.out_h;
+    g->rw = spec.out_w;
+    if (g->zero || !spec.keep_aspect_centre_crop) return;
+    const int ch = g->y2 - g->y1, cw = g->x2 - g->x1;
+    const int shrt = cw <= ch ? cw : ch, lng = cw <= ch ? ch : cw;
+    const int nl = (int)((double)((int64_t)spec.out_h * lng) / (double)shrt);   // int(out * long / short)
+    if (cw <= ch) g->rh = nl; else g->rw = nl;
+    g->top = (g->rh - spec.out_h) / 2;
+    g->left = (g->rw - spec.out_w) / 2;
+}
+
+// taps per output of an axis resized from in_size to out_size (precompute_coeffs' ksize)
+OPD_HD int crop_ksize(int in_size, int out_size, bool bicubic) {
+#pragma clang fp contract(off)
+    const double scale = (double)in_size / out_size;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = (bicubic ? 2.0 : 1.0) * filterscale;
+    return (int)ceil(support) * 2 + 1;
+}
+
+OPD_HD double crop_filter_weight(bool bicubic, double a) {
+#pragma clang fp contract(off)
+    if (a < 0.0) a = -a;
+    if (bicubic)   // Pillow's bicubic_filter, a = -0.5
+        return a < 1.0 ? ((-0.5 + 2.0) * a - (-0.5 + 3.0)) * a * a + 1 : a < 2.0 ? (((a - 5) * a + 8) * a - 4) * -0.5 : 0.0;
+    return a < 1.0 ? 1.0 - a : 0.0;
+}
+
+// Output `xx` of that axis: first source index, tap count, and coeffs[0, ksize) (22-bit fixed point, zeros behind the taps).  The taps
+// are summed one after the other, then each is evaluated again and normalised: no array of doubles, the same values.
+OPD_HD void crop_coeffs_one(int in_size, int out_size, bool bicubic, int xx, int ksize, int32_t* first, int32_t* count, int32_t* coeffs) {
+#pragma clang fp contract(off)
+    const double scale = (double)in_size / out_size;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = (bicubic ? 2.0 : 1.0) * filterscale;
+    const double center = 0.0 + (xx + 0.5) * scale;
+    double ww = 0.0;
+    const double ss = 1.0 / filterscale;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in_size) xmax = in_size;
+    xmax -= xmin;
+    for (int x = 0; x < xmax; ++x) ww += crop_filter_weight(bicubic, (x + xmin - center + 0.5) * ss);
+    for (int x = 0; x < ksize; ++x) {
+        int32_t c = 0;
+        if (x < xmax) {
+            double k = crop_filter_weight(bicubic, (x + xmin - center + 0.5) * ss);
+            if (ww != 0.0) k /= ww;
+            const double v = k * (double)(1 << 22);
+            c = k < 0 ? (int)(-0.5 + v) : (int)(0.5 + v);
+        }
+        coeffs[x] = c;
+    }
+    *first = xmin;
+    *count = xmax;
+}
+
+// The staging layout of a fused call (opd_detr_detect_frames_reid): every crop slot owns `stride` bytes of tables, sized for the
+// largest tap counts a crop of an h x w frame can have.  An axis is never resized from more than the frame's edge to less than the
+// spec's, and ksize grows with in / out, so the whole frame stretched to the output bounds it.
+struct CropSlots { int ksh_max, ksv_max; size_t stride; };
+inline CropSlots crop_slots(const CropSpec& spec, int h, int w) {
+    CropSlots s;
+    s.ksh_max = crop_ksize(w, spec.out_w, spec.bicubic);
+    s.ksv_max = crop_ksize(h, spec.out_h, spec.bicubic);
+    s.stride = (4 * ((size_t)2 * spec.out_w + 2 * spec.out_h + (size_t)spec.out_w * s.ksh_max + (size_t)spec.out_h * s.ksv_max) + 15) / 16 * 16;
+    return s;
+}
+
+// crop_select_kernel: the records [B][Q] labelled `label`, in (frame, record index) order -> slot[k] = frame * Q + query_index and
+// rec[k] = frame * Q + record index for k < slots, and their number *n_person (which may exceed slots)
+struct CropSelectParams {
+    const opd_det* records; const int32_t* counts;
+    int B, Q, label, slots;
+    int32_t *slot, *rec, *n_person;
+};
+// crop_plan_kernel: one workgroup per crop slot k < nb writes crops[k] and its tables at base + tables_off + k * stride.  The box is that
+// of record rec[k] (k < min(*n_person, slots), else a zero crop) or, for the test hook, boxes[k] on frame 0.
+struct CropPlanParams {
+    CropSpec spec;
+    const opd_det* records; const int32_t* rec; const int32_t* n_person;
+    const float* boxes;           // non-null: [nb][4] xywh instead of the records
+    const uint8_t* frames;        // [B][h][w][3]
+    int Q, h, w, slots;
+    unsigned char* base;          // the upload base: crops at 0
+    size_t tables_off, stride;
+    int ksh_max, ksv_max;
+    int32_t* geom;                // nullable (test hook): [nb][13] as opd_test_reid_geometry
+};
+hipError_t opd_launch_crop_select(const CropSelectParams& p, hipStream_t stream);
+hipError_t opd_launch_crop_plan(const CropPlanParams& p, int nb, hipStream_t stream);
 
 // ---- device side --------------------------------------------------------------------------------------------------------------------
 struct CropRgb { int c[3]; };

@@ -344,7 +344,8 @@ struct FrameSource {
     int h, w;                     // camera resolution, to which boxes are scaled (SRC_PIXELS: unused)
 };
 enum { WAIT_BLOCKING, WAIT_TICKET, WAIT_NONE };   // fetch the records and wait / hand them to async slot `ticket` (opd_detr_wait) / leave them on the stream
-enum { FEAT_NONE, FEAT_ROI, FEAT_COLOR };         // between post-process and fetch: nothing / ROI pooling on the records / their colour histograms
+enum { FEAT_NONE, FEAT_ROI, FEAT_COLOR, FEAT_REID };   // between post-process and fetch: nothing / ROI pooling on the records / their colour histograms /
+                                                       // the Re-ID model's rows of the first `slots` of them (opd_reid.h: ReidFusedCall)
 struct RecordSink {
     float threshold;
     const int32_t* orig_hw;       // [B][2] frame sizes of the caller; null: the source's camera resolution, without one the model resolution
@@ -355,6 +356,9 @@ struct RecordSink {
     float* features;
     const opd_floor* fmap;        // non-null: a floor record of every record labelled `label` -> `fmap_out` [B][queries] (host; WAIT_BLOCKING)
     opd_floor_rec* fmap_out;
+    opd_reid* reid;               // FEAT_REID: the Re-ID handle; `features` is then [slots][feature_dim], one row per slot_map[k] = frame * queries + query_index,
+    int slots;                    // k < min(*n_person, slots) (host; WAIT_BLOCKING)
+    int32_t* slot_map; int32_t* n_person;
 };
 int check_shape(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W);
 int detect_pipeline(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, const RecordSink& sink);

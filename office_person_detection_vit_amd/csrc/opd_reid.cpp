@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -30,6 +31,11 @@ struct opd_reid {
     std::vector<int> buckets;
     struct Graph { hipGraphExec_t exec; unsigned epoch; };
     std::map<int, Graph> graphs;
+    // One call at a time: opd_reid_extract and the fused detect call (opd_detr_detect_frames_reid) both rewrite the staging buffer and
+    // replay the same graphs.  A second thread waits here, with its hold of the entry-point lock handed back meanwhile (a capture
+    // inside the first call takes that lock exclusively).
+    std::mutex call_mu;
+    hipEvent_t ev_planned = nullptr, ev_done = nullptr;   // fused call: the detector's stream -> this handle's stream and back
 };
 
 namespace {
@@ -46,6 +52,14 @@ int ensure_upload(opd_reid* r, size_t bytes) {
     if (moved) destroy_graphs(r);   // the captured kernels hold the old base pointer
     return rc;
 }
+
+struct CallLock {
+    std::unique_lock<std::mutex> lk;
+    explicit CallLock(opd_reid* r) : lk(r->call_mu, std::defer_lock) {
+        ApiUnlocked waiting;
+        lk.lock();
+    }
+};
 
 int bucket_of(const opd_reid* r, int n) {
     for (int b : r->buckets)
@@ -153,6 +167,8 @@ void destroy_impl(opd_reid* r) {
     if (r->launch.stream) (void)hipStreamSynchronize(r->launch.stream);
     destroy_graphs(r);
     for (hipEvent_t e : r->launch.event_pool) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {r->ev_planned, r->ev_done})
+        if (e) (void)hipEventDestroy(e);
     r->up.release();
     if (r->ws) (void)hipFree(r->ws);
     if (r->wmem) (void)hipFree(r->wmem);
@@ -189,6 +205,8 @@ int create_impl(const opd_reid_config* cfg, const char* weights_path, int device
     sd.clear();
     RCCHK(use_device("opd_reid_create", device));
     HIPCHK(hipStreamCreateWithFlags(&r->launch.stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&r->ev_planned, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&r->ev_done, hipEventDisableTiming));
     const size_t b16 = align_up(h16.size() * 2, 256), b32 = h32.size() * 4;
     r->wbytes = b16 + b32;
     HIPCHK(hipMalloc(&r->wmem, r->wbytes));
@@ -229,6 +247,72 @@ int ReidLauncher::after(double flops, hipEvent_t e0, hipEvent_t e1) {
     return OPD_OK;
 }
 
+// ---- the Re-ID half of the fused detect call (opd_api.cpp: opd_detr_detect_frames_reid) ------------------------------------------------
+// Staging layout of a fused call: [ReidCrop x max_crops | slot[max_crops], rec[max_crops], n_person | tables: one fixed stride per crop]
+static size_t fused_sel_off(const opd_reid* r) { return align_up(sizeof(ReidCrop) * (size_t)r->cfg.max_crops, 256); }
+static size_t fused_tables_off(const opd_reid* r) { return fused_sel_off(r) + align_up(4 * (2 * (size_t)r->cfg.max_crops + 1), 256); }
+
+int reid_fused_check(const opd_reid* r, int device, int slots, const char* who) {
+    if (!r) return fail(OPD_EINVAL, std::string(who) + ": null Re-ID handle");
+    if (slots < 1 || slots > r->cfg.max_crops)
+        return fail(OPD_EINVAL, std::string(who) + ": slots = " + std::to_string(slots) + " outside 1 .. max_crops = " + std::to_string(r->cfg.max_crops));
+    if (r->device != device)
+        return fail(OPD_EINVAL, std::string(who) + ": the detector is on device " + std::to_string(device) + ", the Re-ID model on device " + std::to_string(r->device));
+    return OPD_OK;
+}
+
+int reid_feature_dim(const opd_reid* r) { return r->model->feature_dim(); }
+
+ReidFusedCall::ReidFusedCall(opd_reid* r_) : r(r_), lk(r_->call_mu, std::defer_lock) {
+    ApiUnlocked waiting;
+    lk.lock();
+}
+
+int ReidFusedCall::enqueue(hipStream_t s, const opd_det* records, const int32_t* counts, const uint8_t* frames, int B, int Q, int h, int w, int label, int slots_) {
+    slots = slots_;
+    const int C = r->cfg.max_crops, E = r->model->feature_dim();
+    const CropSpec& spec = r->model->crop();
+    const CropSlots cs = crop_slots(spec, h, w);
+    const size_t out_bytes = (size_t)slots * E * 4 + 4 * (2 * (size_t)C + 1);   // what comes back through the pinned side
+    RCCHK(ensure_upload(r, std::max(fused_tables_off(r) + (size_t)C * cs.stride, out_bytes)));   // (drops the graphs only when it had to grow: a larger frame size)
+    const int nb = bucket_of(r, slots);
+    int32_t* sel = reinterpret_cast<int32_t*>(r->up.dev + fused_sel_off(r));
+    CropSelectParams sp{};
+    sp.records = records; sp.counts = counts; sp.B = B; sp.Q = Q; sp.label = label; sp.slots = slots;
+    sp.slot = sel; sp.rec = sel + C; sp.n_person = sel + 2 * C;
+    HIPCHK(opd_launch_crop_select(sp, s));
+    CropPlanParams pp{};
+    pp.spec = spec;
+    pp.records = records; pp.rec = sp.rec; pp.n_person = sp.n_person;
+    pp.frames = frames; pp.Q = Q; pp.h = h; pp.w = w; pp.slots = slots;
+    pp.base = r->up.dev; pp.tables_off = fused_tables_off(r); pp.stride = cs.stride;
+    pp.ksh_max = cs.ksh_max; pp.ksv_max = cs.ksv_max;
+    HIPCHK(opd_launch_crop_plan(pp, nb, s));
+    HIPCHK(hipEventRecord(r->ev_planned, s));
+    HIPCHK(hipStreamWaitEvent(r->launch.stream, r->ev_planned, 0));
+    RCCHK(run_forward(r, nb));
+    HIPCHK(hipEventRecord(r->ev_done, r->launch.stream));
+    HIPCHK(hipStreamWaitEvent(s, r->ev_done, 0));
+    return OPD_OK;
+}
+
+int ReidFusedCall::copy_back(hipStream_t s) {
+    const int C = r->cfg.max_crops, E = r->model->feature_dim();
+    const size_t fb = (size_t)slots * E * 4;
+    HIPCHK(hipMemcpyAsync(r->up.host, r->model->features(), fb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(r->up.host + fb, r->up.dev + fused_sel_off(r), 4 * (2 * (size_t)C + 1), hipMemcpyDeviceToHost, s));
+    return OPD_OK;
+}
+
+void ReidFusedCall::deliver(float* features, int32_t* slot_map, int32_t* n_person) const {
+    const int C = r->cfg.max_crops, E = r->model->feature_dim();
+    const int32_t* sel = reinterpret_cast<const int32_t*>(r->up.host + (size_t)slots * E * 4);
+    const int np = sel[2 * C], n = std::min(np, slots);
+    *n_person = np;
+    memcpy(features, r->up.host, (size_t)n * E * 4);
+    memcpy(slot_map, sel, (size_t)n * 4);
+}
+
 // test hook body (opd_reid_test_api.cpp): stage + pre-process only, the model's image of each crop back to the host
 int reid_test_pixels(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, int n_frames, int mem_kind, const float* boxes,
                      const int32_t* box_frame, int n, uint16_t* out) {
@@ -236,6 +320,7 @@ int reid_test_pixels(opd_reid* r, const uint8_t* const* frames, const int32_t* f
     RCCHK(check_extract_args(r, frames, frame_hw, n_frames, mem_kind, boxes, n, out));
     if (n > r->cfg.max_crops) return fail(OPD_EINVAL, "reid_test_pixels: more boxes than max_crops");
     if (n == 0) return OPD_OK;
+    CallLock one_call(r);
     HIPCHK(hipSetDevice(r->device));
     size_t used = 0;
     RCCHK(stage(r, frames, frame_hw, n_frames, mem_kind, boxes, box_frame, n, n, &used));
@@ -251,6 +336,7 @@ int reid_test_kernel_table(opd_reid* r, const uint8_t* const* frames, const int3
     ApiScope api_scope;
     RCCHK(check_extract_args(r, frames, frame_hw, n_frames, OPD_MEM_HOST, boxes, n, out));
     if (n < 1 || n > r->cfg.max_crops || iters < 1 || !count) return fail(OPD_EINVAL, "reid_test_kernel_table: bad arguments");
+    CallLock one_call(r);
     HIPCHK(hipSetDevice(r->device));
     const int nb = bucket_of(r, n);
     size_t used = 0;
@@ -324,6 +410,7 @@ int opd_reid_extract(opd_reid* r, const uint8_t* const* frames, const int32_t* f
     return guarded("opd_reid_extract", [&]() -> int {
         RCCHK(check_extract_args(r, frames, frame_hw, n_frames, mem_kind, boxes_xywh, n_boxes, out));
         if (n_boxes == 0) return OPD_OK;
+        CallLock one_call(r);
         HIPCHK(hipSetDevice(r->device));
         const int E = r->model->feature_dim();
         const float* feat = r->model->features();

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
 #include <vector>
 
 #include "../../include/opd_detr.h"
@@ -53,6 +54,27 @@ struct ReidModel {
     virtual const void* image() const = 0;               // what preprocess() writes, image_bytes() per crop
     virtual size_t image_bytes() const = 0;
     virtual void fill_info(opd_reid_model_info* info) const = 0;   // model and the architecture fields (the rest are the handle's)
+};
+
+// The Re-ID half of opd_detr_detect_frames_reid (opd_api.cpp runs the detector half and the one wait).  reid_fused_check: the argument
+// checks that need the handle, before any HIP call.  A ReidFusedCall holds the handle for the duration of the call (one call at a time:
+// a second thread waits in the constructor):
+//   enqueue    on the detector's stream `s`, behind the post-process kernel: crop_select_kernel and crop_plan_kernel (kernels_crop.hip)
+//              plan the crops of the first `slots` records labelled `label` into the handle's staging buffer, read in place from `frames`
+//              ([B][h][w][3] on the device); an event; the forward of bucket_of(slots) crops on the handle's own stream through its graph
+//              cache; an event back, which `s` waits for
+//   copy_back  on `s`: [slots][feature_dim] rows, the slot map and the person count into the handle's page-locked side
+//   deliver    after the caller's wait on `s`: rows and slot map of k < min(n_person, slots) into the caller's arrays
+int reid_fused_check(const opd_reid* r, int device, int slots, const char* who);
+int reid_feature_dim(const opd_reid* r);
+struct ReidFusedCall {
+    opd_reid* r;
+    std::unique_lock<std::mutex> lk;
+    int slots = 0;
+    explicit ReidFusedCall(opd_reid* r);
+    int enqueue(hipStream_t s, const opd_det* records, const int32_t* counts, const uint8_t* frames, int B, int Q, int h, int w, int label, int slots);
+    int copy_back(hipStream_t s);
+    void deliver(float* features, int32_t* slot_map, int32_t* n_person) const;
 };
 
 // Stage n <= max_crops boxes as opd_reid_extract does and run the pre-processing kernel alone: the model's image of each crop (fp16

@@ -491,14 +491,22 @@ class HipDetrDetector:
             logger.error(f"Detection failed: {e}")
             raise
 
-    def detect_with_features(self, frame: np.ndarray, features: str = "encoder") -> Tuple[List[Detection], np.ndarray]:
+    def detect_with_features(self, frame: np.ndarray, features: str = "encoder", reid=None,
+                             reid_slots: int = 32) -> Tuple[List[Detection], np.ndarray]:
         """Detection + (N, 256) appearance features; assigns ``det.features`` (``yolov8_detector.py:134-159``).
         ``features="encoder"``: pooled from the DETR encoder map (deleted vit_detector.py 148-171, 224-273).
         ``features="color"``: the colour histogram of every detection's crop of ``frame``, the feature the reference's
-        ``detect_with_features`` returns today (``yolov8_detector.py:161-190``)."""
+        ``detect_with_features`` returns today (``yolov8_detector.py:161-190``).
+        ``features="reid"``: the (N, 512) rows of ``reid`` (a loaded ``HipReIDExtractor`` / ``HipOSNetReIDExtractor``), what the
+        reference's configured pipeline gets from ``ReIDFeatureExtractor.extract_features(frame, bboxes)`` after the detect
+        call: here inside it, for the first ``reid_slots`` person records (``opd_detr_detect_frames_reid``)."""
         self._require_model()
-        if features not in ("encoder", "color"):
-            raise ValueError(f"features must be 'encoder' or 'color', got {features!r}")
+        if features not in ("encoder", "color", "reid"):
+            raise ValueError(f"features must be 'encoder', 'color' or 'reid', got {features!r}")
+        if features == "reid":
+            if reid is None:
+                raise ValueError("features='reid' needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
+            return self._detect_with_reid(frame, reid, int(reid_slots))
         color = features == "color"
         target = self._frame_list_target([frame]) if (self.frame_lists and isinstance(frame, np.ndarray)) else None
         if target is not None and self._info.d_model == 256 and not (color and max(frame.shape[:2]) > 4096):
@@ -524,6 +532,39 @@ class HipDetrDetector:
             if i < len(features):
                 det.features = features[i]
         return detections, features
+
+    def _detect_with_reid(self, frame: np.ndarray, reid, slots: int) -> Tuple[List[Detection], np.ndarray]:
+        if not reid.is_loaded:
+            raise RuntimeError("Re-ID model is not loaded: call load_model() first")
+        slots = max(1, min(slots, int(reid.max_crops)))
+        target = self._frame_list_target([frame]) if (self.frame_lists and isinstance(frame, np.ndarray)) else None
+        E = int(reid.feature_dim)
+        if target is None or reid._ordinal() != self.device_ordinal:   # (ragged or pre-resized chunk, or another GPU: two calls)
+            detections = self.detect(frame)
+            rows = reid.extract_features(frame, [d.bbox for d in detections])
+        else:
+            # one C-ABI call: the records and the Re-ID row of every person record (up to `slots`) come back behind one host wait
+            Q = self._info.num_queries
+            recs, counts = (_capi.OpdDet * Q)(), (C.c_int32 * 1)()
+            feats, slot_map, n_person = np.empty((slots, E), np.float32), np.empty(slots, np.int32), C.c_int32(0)
+            ptrs = (C.c_void_p * 1)(frame.ctypes.data)
+            rc = self._lib.opd_detr_detect_frames_reid(C.c_void_p(self.model), reid._handle, ptrs, 1, int(frame.shape[0]), int(frame.shape[1]),
+                                                       target[0], target[1], float(self.confidence_threshold), PERSON_LABEL, slots, recs, counts,
+                                                       feats.ctypes.data, slot_map.ctypes.data, C.byref(n_person))
+            _capi.check(rc, "opd_detr_detect_frames_reid")
+            self._last_orig = [(int(frame.shape[0]), int(frame.shape[1]))]
+            detections = self._postprocess_batch(recs, counts, Q)[0]
+            row_of = {int(q): k for k, q in enumerate(slot_map[:min(int(n_person.value), slots)])}   # (one frame: slot = query_index)
+            rows = np.zeros((len(detections), E), np.float32)
+            missing = [i for i, d in enumerate(detections) if d.query_index not in row_of]
+            for i, d in enumerate(detections):
+                if d.query_index in row_of:
+                    rows[i] = feats[row_of[d.query_index]]
+            if missing:   # more person records than slots: the remainder through the standalone call
+                rows[missing] = reid.extract_features(frame, [detections[i].bbox for i in missing])
+        for i, det in enumerate(detections):
+            det.features = rows[i]
+        return detections, rows
 
     def extract_color_features(self, frame: np.ndarray, detections: List[Detection]) -> np.ndarray:
         """(N, 256) float32 colour-histogram features of the detections' crops of ``frame`` (BGR uint8 ``[H, W, 3]``), on the

@@ -9,6 +9,9 @@ file; nothing is downloaded.
 ``HipOSNetReIDExtractor`` mirrors the reference's ``OSNetReIDExtractor`` (lines 175-365): torchreid's ``osnet_x1_0`` without its
 classifier, Pillow-exact bilinear resize to 256 x 128 and ImageNet normalisation, all on the device (``csrc/kernels_osnet.hip``),
 from a local ``.safetensors`` or torchreid ``.pth`` / ``.pth.tar`` file.  ``create_reid_extractor`` is the façade's dispatch.
+
+Either extractor can also be handed to ``HipDetrDetector.detect_with_features(frame, features="reid", reid=extractor)``: the rows
+then come back inside the detect call (``opd_detr_detect_frames_reid``), the same bits as ``extract_features(frame, bboxes)``.
 """
 
 from __future__ import annotations
