@@ -1,6 +1,6 @@
 // opd_api.cpp — the C-ABI of include/opd_detr.h for the detector: handle creation / cloning / destruction, the argument checks of every
 // entry point, and the ONE detect pipeline behind them (frame source -> device pixels -> forward -> post-process -> feature step -> records).
-// The model itself (weights, workspace, plans, the forward and its graph cache) is opd_model.cpp.
+// The model itself is opd_weights.cpp (the weights) and opd_model.cpp (workspace, plans, the forward and its graph cache).
 #include <algorithm>
 #include <new>
 #include <stdexcept>
@@ -124,9 +124,7 @@ static int enqueue_postprocess(opd_detr* m, float threshold, const int32_t* orig
     pp.records = dev_out ? dev_out : m->d_records;
     pp.counts = dev_counts ? dev_counts : m->d_counts;
     pp.B = B; pp.Q = m->arch.queries; pp.ncls = m->arch.ncls; pp.threshold = threshold;
-    RCCHK(timed_begin(m, CLS_OTHER, 0.0));
-    HIPCHK(opd_launch_postprocess(pp, m->stream));
-    RCCHK(timed_end(m));
+    RCCHK(launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_postprocess(pp, m->stream); }));
     MARK(8);
     return OPD_OK;
 }

@@ -1,4 +1,5 @@
-// opd_model.cpp — device model, per-resolution plan and the forward with its graph cache (the C-ABI on top of it: opd_api.cpp).
+// opd_model.cpp — workspace, per-resolution plans, per-launch timing, the trunk plan and the forward with its graph cache (the weights under it:
+// opd_weights.cpp; the C-ABI on top of it: opd_api.cpp).
 //
 // Host-side orchestration of the DETR detect path:
 //   preprocess -> stem 7x7 -> maxpool -> 16/33 bottlenecks -> input_projection -> 6 x encoder layer ->
@@ -15,343 +16,12 @@ namespace opd {
 
 std::atomic<int> g_alloc_poison{-1};   // opd_model.h: diagnostic allocation mode
 
-static int upload_f32(opd_detr* m, float** dst, const std::vector<float>& v) {
-    RCCHK(dalloc(m, dst, v.size(), true));
-    HIPCHK(hipMemcpy(*dst, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    return OPD_OK;
-}
-static int upload_f16(opd_detr* m, f16_t** dst, const std::vector<float>& v) {
-    std::vector<f16_t> h(v.size());   // the 16-bit operand type of this handle: fp16, or bf16 under OPD_FLAG_BF16
-    if (m->dtype == OPD_DT_BF16) for (size_t i = 0; i < v.size(); ++i) h[i] = f32_to_bf16(v[i]);
-    else for (size_t i = 0; i < v.size(); ++i) h[i] = f32_to_f16(v[i]);
-    RCCHK(dalloc(m, dst, h.size(), true));
-    HIPCHK(hipMemcpy(*dst, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    return OPD_OK;
-}
-
-// a linear layer's weights [N][K] as the fused decoder's split pair in MFMA-fragment order (opd_split_f16_frag)
-static int upload_frag(opd_detr* m, f16_t** dst, const std::vector<float>& v, int N, int K) {
-    if ((size_t)N * K != v.size() || N % 16 || K % 32) return fail(OPD_ESCHEMA, "decoder weight matrix does not tile into 16 x 32 fragments");
-    std::vector<f16_t> f(v.size() * 2);
-    opd_split_f16_frag(v.data(), N, K, f.data());
-    RCCHK(dalloc(m, dst, f.size(), true));
-    HIPCHK(hipMemcpy(*dst, f.data(), f.size() * 2, hipMemcpyHostToDevice));
-    return OPD_OK;
-}
-
-static const HostTensor& T(const StateDict& sd, const std::string& k) { return sd.at(k); }
-
-// the encoder FFN's weights (+ the rows of its tail projection, pass order) as enc_ffn_kernel's per-wave fragment streams, in the handle's 16-bit
-// operand type
-static int upload_encffn(opd_detr* m, unsigned char** dst, const std::vector<float>& w1, const std::vector<float>& b1, const std::vector<float>& w2, int F,
-                         const std::vector<float>& wt, const std::vector<float>& bt, int tail, const std::vector<float>& wo) {
-    std::vector<uint16_t> h1(w1.size()), h2(w2.size()), ht(wt.size()), ho(wo.size());
-    const bool bf = m->dtype == OPD_DT_BF16;
-    auto cv = [&](const std::vector<float>& v, std::vector<uint16_t>& h) { for (size_t i = 0; i < v.size(); ++i) h[i] = bf ? f32_to_bf16(v[i]) : f32_to_f16(v[i]); };
-    cv(w1, h1); cv(w2, h2); cv(wt, ht); cv(wo, ho);
-    if (!ho.empty() && ho.size() != (size_t)256 * 256) return fail(OPD_ESCHEMA, "encoder front projection: unexpected weight shape");
-    if (ht.size() != (size_t)tail * 256 * 256 || bt.size() != (size_t)tail * 256) return fail(OPD_ESCHEMA, "encoder tail projection: unexpected weight shape");
-    std::vector<unsigned char> pk(opd_encffn_pack_bytes(F, tail, ho.empty() ? 0 : 1));
-    opd_encffn_pack(h1.data(), b1.data(), h2.data(), F, ht.data(), bt.data(), tail, ho.empty() ? nullptr : ho.data(), pk.data());
-    RCCHK(dalloc(m, dst, pk.size(), true));
-    HIPCHK(hipMemcpy(*dst, pk.data(), pk.size(), hipMemcpyHostToDevice));
-    return OPD_OK;
-}
-
-// conv + FrozenBN -> folded fp16 [Cout][KH][KW][Cin] + fp32 bias (HF:models/detr/modeling_detr.py:207-215)
-static int make_conv(opd_detr* m, const StateDict& sd, const std::string& prefix, int stride, Conv* c) {
-    const HostTensor& w = T(sd, prefix + ".convolution.weight");
-    const int Cout = (int)w.shape[0], Cin = (int)w.shape[1], KH = (int)w.shape[2], KW = (int)w.shape[3];
-    const std::string n = prefix + ".normalization";
-    const auto& g = T(sd, n + ".weight").data;
-    const auto& bt = T(sd, n + ".bias").data;
-    const auto& mu = T(sd, n + ".running_mean").data;
-    const auto& var = T(sd, n + ".running_var").data;
-    std::vector<float> scale(Cout), bias(Cout);
-    for (int o = 0; o < Cout; ++o) {
-        scale[o] = g[o] * (1.0f / sqrtf(var[o] + 1e-5f));
-        bias[o] = bt[o] - mu[o] * scale[o];
-    }
-    c->Cin = Cin; c->Cout = Cout; c->KH = KH; c->KW = KW; c->stride = stride; c->pad = KH / 2;
-    std::vector<float> wt;
-    if (Cin == 3) {  // stem: [64][8][8][4], zero padded (kh = 7, kw = 7, c = 3)
-        c->stem = true;
-        c->K = 256;
-        std::vector<float> cw((size_t)Cout * 147);   // folded, [o][kh][kw][ci] without the padding: what gets rounded
-        for (int o = 0; o < Cout; ++o)
-            for (int ci = 0; ci < 3; ++ci)
-                for (int kh = 0; kh < 7; ++kh)
-                    for (int kw = 0; kw < 7; ++kw)
-                        cw[(size_t)o * 147 + (kh * 7 + kw) * 3 + ci] = w.data[(((size_t)o * 3 + ci) * 7 + kh) * 7 + kw] * scale[o];
-        if (m->sw.wround) round_f16_diffused(cw.data(), (size_t)Cout, 49, 3, m->dtype == OPD_DT_BF16);
-        wt.assign((size_t)Cout * 256, 0.f);
-        for (int o = 0; o < Cout; ++o)
-            for (int kh = 0; kh < 7; ++kh)
-                for (int kw = 0; kw < 7; ++kw)
-                    for (int ci = 0; ci < 3; ++ci) wt[(size_t)o * 256 + kh * 32 + kw * 4 + ci] = cw[(size_t)o * 147 + (kh * 7 + kw) * 3 + ci];
-    } else {
-        c->K = KH * KW * Cin;
-        wt.resize((size_t)Cout * c->K);
-        for (int o = 0; o < Cout; ++o)
-            for (int ci = 0; ci < Cin; ++ci)
-                for (int kh = 0; kh < KH; ++kh)
-                    for (int kw = 0; kw < KW; ++kw)
-                        wt[(size_t)o * c->K + (size_t)(kh * KW + kw) * Cin + ci] =
-                            w.data[(((size_t)o * Cin + ci) * KH + kh) * KW + kw] * scale[o];
-        // the fp16 image of the folded kernel: error diffusion along the reduction (opd_host.h) instead of round-to-nearest
-        if (m->sw.wround) round_f16_diffused(wt.data(), (size_t)Cout, KH * KW, Cin, m->dtype == OPD_DT_BF16);
-    }
-    RCCHK(upload_f16(m, &c->w, wt));
-    if (conv_has_kperm(*c)) {  // operands of kernels_btail.hip / kernels_btail3.hip (stages 1-3)
-        std::vector<float> wp(wt.size());
-        for (int o = 0; o < Cout; ++o)
-            for (int b = 0; b < Cin; b += 32)
-                for (int g = 0; g < 4; ++g)
-                    for (int e = 0; e < 4; ++e) {
-                        wp[(size_t)o * Cin + b + 8 * g + e] = wt[(size_t)o * Cin + b + 4 * g + e];
-                        wp[(size_t)o * Cin + b + 8 * g + 4 + e] = wt[(size_t)o * Cin + b + 16 + 4 * g + e];
-                    }
-        RCCHK(upload_f16(m, &c->wp, wp));
-    }
-    RCCHK(upload_f32(m, &c->bias, bias));
-    return OPD_OK;
-}
-
-static int make_lin(opd_detr* m, const StateDict& sd, const std::string& prefix, Lin* l) {
-    const HostTensor& w = T(sd, prefix + ".weight");
-    l->N = (int)w.shape[0];
-    l->K = (int)w.shape[1];
-    RCCHK(upload_f16(m, &l->w, w.data));
-    RCCHK(upload_f32(m, &l->b, T(sd, prefix + ".bias").data));
-    return OPD_OK;
-}
-static int make_ln(opd_detr* m, const StateDict& sd, const std::string& prefix, LNp* l) {
-    RCCHK(upload_f32(m, &l->g, T(sd, prefix + ".weight").data));
-    RCCHK(upload_f32(m, &l->b, T(sd, prefix + ".bias").data));
-    return OPD_OK;
-}
-static void append(std::vector<float>& dst, const std::vector<float>& src) { dst.insert(dst.end(), src.begin(), src.end()); }
-
-int build_weights(opd_detr* m, const StateDict& sd) {
-    const Arch& a = m->arch;
-    const std::string bb = "model.backbone.model.";
-    RCCHK(make_conv(m, sd, bb + "embedder.embedder", 2, &m->stem));
-    for (int s = 0; s < 4; ++s) {
-        m->stage_first.push_back((int)m->blocks.size());
-        for (int l = 0; l < a.depths[s]; ++l) {
-            const std::string p = bb + "encoder.stages." + std::to_string(s) + ".layers." + std::to_string(l);
-            const int stride = (l == 0 && s > 0) ? 2 : 1;
-            Block b;
-            b.has_sc = sd.count(p + ".shortcut.convolution.weight") > 0;
-            if (b.has_sc) RCCHK(make_conv(m, sd, p + ".shortcut", stride, &b.sc));
-            RCCHK(make_conv(m, sd, p + ".layer.0", 1, &b.c0));
-            RCCHK(make_conv(m, sd, p + ".layer.1", stride, &b.c1));
-            RCCHK(make_conv(m, sd, p + ".layer.2", 1, &b.c2));
-            if (block_has_bias2sc(b)) {
-                std::vector<float> b2(b.c2.Cout), bs(b.c2.Cout);
-                HIPCHK(hipMemcpy(b2.data(), b.c2.bias, b2.size() * 4, hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(bs.data(), b.sc.bias, bs.size() * 4, hipMemcpyDeviceToHost));
-                for (size_t j = 0; j < b2.size(); ++j) b2[j] += bs[j];
-                RCCHK(upload_f32(m, &b.bias2sc, b2));
-                if (block_has_w2sc(b)) {   // stages 2-4: [W2 | Wsc]
-                    const size_t K1 = (size_t)b.c2.K, K2 = (size_t)b.sc.K, N = (size_t)b.c2.Cout;
-                    std::vector<f16_t> h2(N * K1), hs(N * K2), cat(N * (K1 + K2));
-                    HIPCHK(hipMemcpy(h2.data(), b.c2.w, h2.size() * 2, hipMemcpyDeviceToHost));
-                    HIPCHK(hipMemcpy(hs.data(), b.sc.w, hs.size() * 2, hipMemcpyDeviceToHost));
-                    for (size_t n = 0; n < N; ++n) {
-                        memcpy(&cat[n * (K1 + K2)], &h2[n * K1], K1 * 2);
-                        memcpy(&cat[n * (K1 + K2) + K1], &hs[n * K2], K2 * 2);
-                    }
-                    RCCHK(dalloc(m, &b.w2sc, cat.size(), true));
-                    HIPCHK(hipMemcpy(b.w2sc, cat.data(), cat.size() * 2, hipMemcpyHostToDevice));
-                }
-            }
-            m->blocks.push_back(b);
-        }
-    }
-    {  // input_projection: plain 1x1 conv with bias, no BN
-        const HostTensor& w = T(sd, "model.input_projection.weight");
-        m->proj.Cin = (int)w.shape[1]; m->proj.Cout = (int)w.shape[0]; m->proj.K = m->proj.Cin;
-        RCCHK(upload_f16(m, &m->proj.w, w.data));
-        RCCHK(upload_f32(m, &m->proj.bias, T(sd, "model.input_projection.bias").data));
-    }
-    const int D = a.d_model;
-    const std::vector<float> zerosW((size_t)D * D, 0.f);
-    auto cat3 = [&](const std::string& p, std::vector<float>* w_full, std::vector<float>* w_pos, std::vector<float>* b_cat) {
-        // w_full = [Wq;Wk;Wv] (GEMM weights), w_pos = [Wq;Wk;0] and b_cat = [bq;bk;bv] (row-bias fold)
-        w_full->clear(); w_pos->clear(); b_cat->clear();
-        append(*w_full, T(sd, p + ".q_proj.weight").data); append(*w_full, T(sd, p + ".k_proj.weight").data);
-        append(*w_full, T(sd, p + ".v_proj.weight").data);
-        append(*w_pos, T(sd, p + ".q_proj.weight").data); append(*w_pos, T(sd, p + ".k_proj.weight").data);
-        append(*w_pos, zerosW);
-        append(*b_cat, T(sd, p + ".q_proj.bias").data); append(*b_cat, T(sd, p + ".k_proj.bias").data);
-        append(*b_cat, T(sd, p + ".v_proj.bias").data);
-    };
-    m->enc.resize(a.enc_layers);
-    m->h_enc_cat_w.resize(a.enc_layers);
-    m->h_enc_cat_b.resize(a.enc_layers);
-    for (int i = 0; i < a.enc_layers; ++i) {
-        const std::string p = "model.encoder.layers." + std::to_string(i);
-        EncLayer& L = m->enc[i];
-        std::vector<float> wfull;
-        cat3(p + ".self_attn", &wfull, &m->h_enc_cat_w[i], &m->h_enc_cat_b[i]);
-        RCCHK(upload_f16(m, &L.wqkv, wfull));
-        RCCHK(upload_f32(m, &L.bqkv, m->h_enc_cat_b[i]));
-        RCCHK(make_lin(m, sd, p + ".self_attn.o_proj", &L.o));
-        RCCHK(make_ln(m, sd, p + ".self_attn_layer_norm", &L.ln1));
-        RCCHK(make_lin(m, sd, p + ".mlp.fc1", &L.fc1));
-        RCCHK(make_lin(m, sd, p + ".mlp.fc2", &L.fc2));
-        RCCHK(make_ln(m, sd, p + ".final_layer_norm", &L.ln2));
-    }
-    // decoder: query-position folds are resolution independent -> build them now with the fp32 plan GEMM
-    float* d_qpos = nullptr;
-    RCCHK(upload_f32(m, &d_qpos, T(sd, "model.query_position_embeddings.weight").data));
-    const int Q = a.queries;
-    m->dec.resize(a.dec_layers);
-    std::vector<float> kv_full;
-    for (int i = 0; i < a.dec_layers; ++i) {
-        const std::string p = "model.decoder.layers." + std::to_string(i);
-        DecLayer& L = m->dec[i];
-        std::vector<float> wfull, wpos, bcat;
-        cat3(p + ".self_attn", &wfull, &wpos, &bcat);
-        RCCHK(upload_f16(m, &L.wqkv, wfull));
-        float *d_w = nullptr, *d_b = nullptr;
-        RCCHK(upload_f32(m, &d_w, wpos));
-        RCCHK(upload_f32(m, &d_b, bcat));
-        RCCHK(dalloc(m, &L.rb_self, (size_t)Q * 768, true));
-        HIPCHK(opd_launch_gemm_f32(d_qpos, d_w, d_b, L.rb_self, Q, 768, D, 768, m->stream));
-        RCCHK(make_lin(m, sd, p + ".self_attn.o_proj", &L.so));
-        RCCHK(make_ln(m, sd, p + ".self_attn_layer_norm", &L.ln1));
-        // cross attention: q from the decoder state, k/v from the encoder memory
-        RCCHK(upload_f16(m, &L.wq_c, T(sd, p + ".encoder_attn.q_proj.weight").data));
-        float *d_wq = nullptr, *d_bq = nullptr;
-        RCCHK(upload_f32(m, &d_wq, T(sd, p + ".encoder_attn.q_proj.weight").data));
-        RCCHK(upload_f32(m, &d_bq, T(sd, p + ".encoder_attn.q_proj.bias").data));
-        RCCHK(dalloc(m, &L.rb_q, (size_t)Q * D, true));
-        HIPCHK(opd_launch_gemm_f32(d_qpos, d_wq, d_bq, L.rb_q, Q, D, D, D, m->stream));
-        append(kv_full, T(sd, p + ".encoder_attn.k_proj.weight").data);
-        append(kv_full, T(sd, p + ".encoder_attn.v_proj.weight").data);
-        append(m->h_kv_cat_w, T(sd, p + ".encoder_attn.k_proj.weight").data);
-        append(m->h_kv_cat_w, zerosW);
-        append(m->h_kv_cat_b, T(sd, p + ".encoder_attn.k_proj.bias").data);
-        append(m->h_kv_cat_b, T(sd, p + ".encoder_attn.v_proj.bias").data);
-        RCCHK(make_lin(m, sd, p + ".encoder_attn.o_proj", &L.co));
-        RCCHK(make_ln(m, sd, p + ".encoder_attn_layer_norm", &L.ln2));
-        RCCHK(make_lin(m, sd, p + ".mlp.fc1", &L.fc1));
-        RCCHK(make_lin(m, sd, p + ".mlp.fc2", &L.fc2));
-        RCCHK(make_ln(m, sd, p + ".final_layer_norm", &L.ln3));
-        // split pairs for the fused decoder
-        if (D % 32 == 0 && a.ffn % 32 == 0) {
-            RCCHK(upload_frag(m, &L.wqkv_f, wfull, 3 * D, D));
-            RCCHK(upload_frag(m, &L.so_f, T(sd, p + ".self_attn.o_proj.weight").data, D, D));
-            RCCHK(upload_frag(m, &L.wqc_f, T(sd, p + ".encoder_attn.q_proj.weight").data, D, D));
-            RCCHK(upload_frag(m, &L.co_f, T(sd, p + ".encoder_attn.o_proj.weight").data, D, D));
-            RCCHK(upload_frag(m, &L.fc1_f, T(sd, p + ".mlp.fc1.weight").data, a.ffn, D));
-            RCCHK(upload_frag(m, &L.fc2_f, T(sd, p + ".mlp.fc2.weight").data, D, a.ffn));
-        }
-    }
-    RCCHK(upload_f16(m, &m->wkv_all, kv_full));
-    RCCHK(upload_f32(m, &m->bkv_all, m->h_kv_cat_b));
-    if (a.d_model == 256 && a.ffn % 128 == 0) {   // the encoder FFN blocks as single launches, each with the projection that consumes its output
-        const int D = 256, L = a.dec_layers;
-        for (int i = 0; i < a.enc_layers; ++i) {
-            EncLayer& E = m->enc[i];
-            const std::string p = "model.encoder.layers." + std::to_string(i);
-            std::vector<float> wt, bt;
-            if (i + 1 < a.enc_layers) {   // the next layer's q, k (on x + pos), v
-                const std::string n = "model.encoder.layers." + std::to_string(i + 1) + ".self_attn.";
-                for (const char* pr : {"q_proj", "k_proj", "v_proj"}) { append(wt, T(sd, n + pr + ".weight").data); append(bt, T(sd, n + pr + ".bias").data); }
-                E.tail = 3; E.tail_pos = 2; E.tail_ld = 3 * D;
-                for (int t = 0; t < 3; ++t) E.tail_col[t] = t * D;
-            } else if (2 * L <= 16 && kv_full.size() == (size_t)L * 2 * D * D && m->h_kv_cat_b.size() == (size_t)L * 2 * D) {
-                // the decoder's memory projections, [k_l | v_l] per layer in wkv_all: passes k_0 .. k_{L-1} (on x + pos), then v_0 .. v_{L-1}
-                for (int kv = 0; kv < 2; ++kv)
-                    for (int l = 0; l < L; ++l) {
-                        wt.insert(wt.end(), kv_full.begin() + (size_t)(2 * l + kv) * D * D, kv_full.begin() + (size_t)(2 * l + kv + 1) * D * D);
-                        bt.insert(bt.end(), m->h_kv_cat_b.begin() + (size_t)(2 * l + kv) * D, m->h_kv_cat_b.begin() + (size_t)(2 * l + kv + 1) * D);
-                        E.tail_col[kv * L + l] = (2 * l + kv) * D;
-                    }
-                E.tail = 2 * L; E.tail_pos = L; E.tail_ld = 2 * L * D;
-            }
-            RCCHK(upload_encffn(m, &E.ffn_pack, T(sd, p + ".mlp.fc1.weight").data, T(sd, p + ".mlp.fc1.bias").data, T(sd, p + ".mlp.fc2.weight").data, a.ffn, wt, bt, E.tail,
-                                T(sd, p + ".self_attn.o_proj.weight").data));
-            E.front = 1;
-        }
-    }
-    {   // The decoder starts from h = 0 (HF:models/detr/modeling_detr.py:1243-1251), so in layer 0 the self-attention values are the
-        // same row for every query, v = 0 . Wv^T + bv, the softmax weights of a row sum to one, and the block's output
-        // LN(0 + Wo . bv + bo) is ONE vector, whatever the frame shows: computed here once in fp32, broadcast at run time instead of
-        // two memsets, the QKV projection, the attention and the output projection + LayerNorm of that layer.
-        const std::string p0 = "model.decoder.layers.0";
-        const auto& bv = T(sd, p0 + ".self_attn.v_proj.bias").data;
-        const auto& wo = T(sd, p0 + ".self_attn.o_proj.weight").data;
-        const auto& bo = T(sd, p0 + ".self_attn.o_proj.bias").data;
-        const auto& g = T(sd, p0 + ".self_attn_layer_norm.weight").data;
-        const auto& be = T(sd, p0 + ".self_attn_layer_norm.bias").data;
-        std::vector<float> x(D), c(D);
-        for (int n = 0; n < D; ++n) {
-            float acc = 0.f;
-            for (int k = 0; k < D; ++k) acc += wo[(size_t)n * D + k] * bv[k];
-            x[n] = acc + bo[n];
-        }
-        float mean = 0.f, var = 0.f;
-        for (int n = 0; n < D; ++n) mean += x[n];
-        mean /= (float)D;
-        for (int n = 0; n < D; ++n) var += (x[n] - mean) * (x[n] - mean);
-        var /= (float)D;
-        const float rstd = 1.0f / sqrtf(var + 1e-5f);
-        for (int n = 0; n < D; ++n) c[n] = (x[n] - mean) * rstd * g[n] + be[n];
-        RCCHK(upload_f32(m, &m->dec0_h, c));
-        // ... and so are layer 0's cross-attention queries, (h1 + qpos) . Wq_c^T + bq_c: one [Q][D] table (fp32 sums, stored as the fp16 operand
-        // the attention kernel reads)
-        const auto& qpos = T(sd, "model.query_position_embeddings.weight").data;
-        const auto& wq = T(sd, p0 + ".encoder_attn.q_proj.weight").data;
-        const auto& bq = T(sd, p0 + ".encoder_attn.q_proj.bias").data;
-        std::vector<float> q0((size_t)Q * D);
-        for (int q = 0; q < Q; ++q)
-            for (int n = 0; n < D; ++n) {
-                double acc = bq[n];
-                for (int k = 0; k < D; ++k) acc += ((double)c[k] + qpos[(size_t)q * D + k]) * wq[(size_t)n * D + k];
-                q0[(size_t)q * D + n] = (float)acc;
-            }
-        RCCHK(upload_f16(m, &m->qc0, q0));
-    }
-    RCCHK(make_ln(m, sd, "model.decoder.layernorm", &m->dec_ln));
-    auto transposed = [&](const std::string& key) {  // [out][in] -> [in][out] (coalesced reads in heads_kernel)
-        const HostTensor& w = T(sd, key);
-        const int O = (int)w.shape[0], I = (int)w.shape[1];
-        std::vector<float> t((size_t)O * I);
-        for (int o = 0; o < O; ++o)
-            for (int i = 0; i < I; ++i) t[(size_t)i * O + o] = w.data[(size_t)o * I + i];
-        return t;
-    };
-    RCCHK(upload_f32(m, &m->wc, transposed("class_labels_classifier.weight")));
-    RCCHK(upload_f32(m, &m->bc, T(sd, "class_labels_classifier.bias").data));
-    if (a.d_model == 256 && a.ncls <= 128) {   // the heads on split fp16 operands (kernels_dec.hip::heads2_kernel): class matrix padded to 128 rows
-        std::vector<float> wcp((size_t)128 * 256, 0.f);
-        const auto& wcs = T(sd, "class_labels_classifier.weight").data;
-        std::copy(wcs.begin(), wcs.end(), wcp.begin());
-        RCCHK(upload_frag(m, &m->wc_f, wcp, 128, 256));
-        RCCHK(upload_frag(m, &m->w1_f, T(sd, "bbox_predictor.layers.0.weight").data, 256, 256));
-        RCCHK(upload_frag(m, &m->w2_f, T(sd, "bbox_predictor.layers.1.weight").data, 256, 256));
-    }
-    RCCHK(upload_f32(m, &m->w1, transposed("bbox_predictor.layers.0.weight")));
-    RCCHK(upload_f32(m, &m->b1, T(sd, "bbox_predictor.layers.0.bias").data));
-    RCCHK(upload_f32(m, &m->w2, transposed("bbox_predictor.layers.1.weight")));
-    RCCHK(upload_f32(m, &m->b2, T(sd, "bbox_predictor.layers.1.bias").data));
-    RCCHK(upload_f32(m, &m->w3, transposed("bbox_predictor.layers.2.weight")));
-    RCCHK(upload_f32(m, &m->b3, T(sd, "bbox_predictor.layers.2.bias").data));
-    RCCHK(upload_f32(m, &m->zero_bias, std::vector<float>(4096, 0.f)));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return OPD_OK;
-}
-
 static void compute_dims(int B, int H, int W, Dims* d) {
     d->B = B; d->H = H; d->W = W;
     d->H1 = down2(H); d->W1 = down2(W);
     d->H2 = down2(d->H1); d->W2 = down2(d->W1);
-    d->sh[0] = d->H2; d->sw[0] = d->W2;
-    for (int s = 1; s < 4; ++s) { d->sh[s] = down2(d->sh[s - 1]); d->sw[s] = down2(d->sw[s - 1]); }
+    d->stage_h[0] = d->H2; d->stage_w[0] = d->W2;
+    for (int s = 1; s < 4; ++s) { d->stage_h[s] = down2(d->stage_h[s - 1]); d->stage_w[s] = down2(d->stage_w[s - 1]); }
 }
 
 // Layer 0's cross-attention queries do not depend on the frames (build_weights: qc0): the fused decoder reads them from layer 0's region of
@@ -364,7 +34,23 @@ int fill_qc0(opd_detr* m) {
     return OPD_OK;
 }
 
-static int conv_splits(const opd_detr* m, const Conv& c, int stage);   // (below, with run_conv)
+// Split-K plan of a deep convolution for SMALL handles (round 5).  A max_batch = 1 handle at 800 x 1333 runs stage 4's 3x3 as 72 workgroups
+// that each walk 72 k-steps (50 us: the launch lasts one workgroup's life, 184 CUs idle); cut eight ways it is 576 workgroups of 9 k-steps
+// plus a 3-us reduction.  The split follows the handle's CONFIGURATION (max_batch, the frame-size bounds, the layer), never the batch or frame
+// at hand -- a frame's low-order bits must not depend on the call it travels in -- and applies only where the unsplit launch would leave most
+// CUs without a workgroup.  Returns 1 (no split) or a divisor of the k-step count.
+static int conv_splits(const opd_detr* m, const Conv& c, int stage) {
+    if (!m->sw.small_splitk || stage < 0 || stage > 3 || c.stem || c.K % 64 != 0 || c.Cout % 64 != 0) return 1;
+    const long long px = (long long)m->cfg.max_batch * (long long)m->stage_px[stage];
+    const long long tiles = ((px + 127) / 128) * (c.Cout / 64);
+    const int nk = c.K / 64;
+    if (tiles > 160 || nk < 24) return 1;
+    int best = 1;
+    for (int s : {2, 3, 4, 6, 8})
+        if (nk % s == 0 && nk / s >= 6 && tiles * s <= 640) best = s;
+    return best;
+}
+
 int build_workspace(opd_detr* m) {
     const Arch& a = m->arch;
     // Frames may come in either orientation (the HF size rule maps a portrait camera frame to about 1333 x 750): the handle
@@ -475,53 +161,45 @@ static int get_plan(opd_detr* m, int fh, int fw, int vh, int vw, Plan** out) {
     RCCHK(upload_f32(m, &d_pos, pos));
     p->d_pos = d_pos;
     p->rb_enc.resize(a.enc_layers);
-    for (int i = 0; i < a.enc_layers; ++i) {
-        float *d_w = nullptr, *d_b = nullptr;
-        RCCHK(upload_f32(m, &d_w, m->h_enc_cat_w[i]));
-        RCCHK(upload_f32(m, &d_b, m->h_enc_cat_b[i]));
-        RCCHK(dalloc(m, &p->rb_enc[i], (size_t)hw * 768, true));
-        HIPCHK(opd_launch_gemm_f32(d_pos, d_w, d_b, p->rb_enc[i], hw, 768, D, 768, m->stream));
-    }
-    {
-        const int NKV = a.dec_layers * 512;
-        float *d_w = nullptr, *d_b = nullptr;
-        RCCHK(upload_f32(m, &d_w, m->h_kv_cat_w));
-        RCCHK(upload_f32(m, &d_b, m->h_kv_cat_b));
-        RCCHK(dalloc(m, &p->rb_kv, (size_t)hw * NKV, true));
-        HIPCHK(opd_launch_gemm_f32(d_pos, d_w, d_b, p->rb_kv, hw, NKV, D, NKV, m->stream));
-    }
+    for (int i = 0; i < a.enc_layers; ++i) RCCHK(upload_fold(m, d_pos, m->h_enc_cat_w[i], m->h_enc_cat_b[i], hw, 768, D, &p->rb_enc[i]));
+    RCCHK(upload_fold(m, d_pos, m->h_kv_cat_w, m->h_kv_cat_b, hw, a.dec_layers * 512, D, &p->rb_kv));
     HIPCHK(hipStreamSynchronize(m->stream));
     *out = p.get();
     plans.push_back(std::move(p));
     return OPD_OK;
 }
 
-// ---- per-launch timing --------------------------------------------------------------------------------------------
-int timed_begin(opd_detr* m, int cls, double flops) {
+// ---- one launch of the forward (opd_model.h: launch) ---------------------------------------------------------------
+// profiling mode 1: an event pair around the launch, for the kernel table
+int launch_begin(opd_detr* m, hipStream_t s, int cls, double flops) {
     if (m->profiling != 1) return OPD_OK;
-    hipEvent_t e[2];
-    for (int i = 0; i < 2; ++i) {
-        if (m->pool_next == m->event_pool.size()) {
-            hipEvent_t ne;
-            HIPCHK(hipEventCreate(&ne));
-            m->event_pool.push_back(ne);
-        }
-        e[i] = m->event_pool[m->pool_next++];
+    while (m->event_pool.size() < m->pool_next + 2) {
+        hipEvent_t ne;
+        HIPCHK(hipEventCreate(&ne));
+        m->event_pool.push_back(ne);
     }
-    HIPCHK(hipEventRecord(e[0], m->stream));
+    const hipEvent_t* e = &m->event_pool[m->pool_next];
+    m->pool_next += 2;
+    HIPCHK(hipEventRecord(e[0], s));
     m->timed.push_back({cls, e[0], e[1], flops, nullptr});
     opd_last_kernel_name = nullptr;
     return OPD_OK;
 }
-int timed_end(opd_detr* m) {
-    if (m->profiling != 1) return OPD_OK;
-    HIPCHK(hipEventRecord(m->timed.back().b, m->stream));
-    m->timed.back().name = opd_last_kernel_name;   // what the launcher just launched (OPD_LAUNCH): the name rocprofv3 prints, minus namespace and signature
+static int tap(opd_detr* m, hipStream_t s, const Tap& t) {
+    if (!m->taps || !m->d_taps || m->tap_next >= OPD_MAX_TAPS) return OPD_OK;
+    HIPCHK(opd_launch_checksum(t.p, t.bytes, m->d_taps + (size_t)m->tap_next * OPD_TAP_BLOCKS, s));
+    if ((int)m->tap_names.size() <= m->tap_next) m->tap_names.resize(m->tap_next + 1);
+    m->tap_names[m->tap_next++] = t.name;
     return OPD_OK;
 }
-static void timed_reset(opd_detr* m) {
-    m->timed.clear();
-    m->pool_next = 0;
+int launch_end(opd_detr* m, hipStream_t s, std::initializer_list<Tap> taps) {
+    if (m->profiling == 1) {
+        HIPCHK(hipEventRecord(m->timed.back().b, s));
+        m->timed.back().name = opd_last_kernel_name;   // what the launcher just launched (OPD_LAUNCH): the name rocprofv3 prints, minus namespace and signature
+    }
+    for (const Tap& t : taps)
+        if (t.name && t.p) RCCHK(tap(m, s, t));
+    return OPD_OK;
 }
 void timed_collect(opd_detr* m) {
     for (int c = 0; c < 4; ++c) { m->class_ms[c] = 0.f; m->class_launches[c] = 0; m->class_flops[c] = 0.0; }
@@ -545,159 +223,160 @@ void timed_collect(opd_detr* m) {
     std::sort(m->ktable.begin(), m->ktable.end(), [](const opd_detr::KernelRow& a, const opd_detr::KernelRow& b) { return a.ms > b.ms; });
 }
 
-static int tap(opd_detr* m, const char* name, const void* p, size_t bytes) {
-    if (!m->taps || !m->d_taps || m->tap_next >= OPD_MAX_TAPS) return OPD_OK;
-    HIPCHK(opd_launch_checksum(p, bytes, m->d_taps + (size_t)m->tap_next * OPD_TAP_BLOCKS, m->stream));
-    if ((int)m->tap_names.size() <= m->tap_next) m->tap_names.resize(m->tap_next + 1);
-    m->tap_names[m->tap_next++] = name;
-    return OPD_OK;
-}
+// ---- the per-call context of one forward ---------------------------------------------------------------------------
+struct PosShadow { const float* pos; const float* const* pos_ptrs; int period; f16_t* yp16; };   // second fp16 output of a reduce + LN
+struct Fwd {
+    opd_detr* m;
+    hipStream_t stream;   // where this chain of the forward launches: m->stream, or m->stream2 for the stage-3 split's second chain
+    int B, H, W;
+    Dims d;
+    int D, F, Q, Md, NKV;   // d_model, FFN width, queries, decoder rows (B x Q), columns of the memory K/V projection
+    Plan* plan = nullptr;
+    // ragged batches only: device arrays of B per-frame pointers (bias folds per encoder layer, K/V fold, position embeddings), valid sizes
+    const float* const* enc_bias_ptrs[16] = {};
+    const float* const* kv_bias_ptrs = nullptr;
+    const float* const* pos_ptrs = nullptr;
+    const int32_t *d_valid = nullptr, *d_keyv = nullptr;
+    // from the trunk on: the feature map [B][fh][fw][proj.K], its tokens per frame and in all
+    const f16_t* feat = nullptr;
+    int fh = 0, fw = 0, hw = 0, M = 0;
+    bool shadow = false;   // the position shadow is in use (fwd_encoder)
+    PosShadow psh{};
+    const PosShadow* ps() const { return shadow ? &psh : nullptr; }
+    template <typename Fn>
+    int launch(int cls, double flops, Fn&& issue, std::initializer_list<Tap> taps = {}) const { return opd::launch(m, stream, cls, flops, issue, taps); }
+};
 
-// Split-K plan of a deep convolution for SMALL handles (round 5).  A max_batch = 1 handle at 800 x 1333 runs stage 4's 3x3 as 72 workgroups
-// that each walk 72 k-steps (50 us: the launch lasts one workgroup's life, 184 CUs idle); cut eight ways it is 576 workgroups of 9 k-steps
-// plus a 3-us reduction.  The split follows the handle's CONFIGURATION (max_batch, the frame-size bounds, the layer), never the batch or frame
-// at hand -- a frame's low-order bits must not depend on the call it travels in -- and applies only where the unsplit launch would leave most
-// CUs without a workgroup.  Returns 1 (no split) or a divisor of the k-step count.
-static int conv_splits(const opd_detr* m, const Conv& c, int stage) {
-    if (!m->sw.small_splitk || stage < 0 || stage > 3 || c.stem || c.K % 64 != 0 || c.Cout % 64 != 0) return 1;
-    const long long px = (long long)m->cfg.max_batch * (long long)m->stage_px[stage];
-    const long long tiles = ((px + 127) / 128) * (c.Cout / 64);
-    const int nk = c.K / 64;
-    if (tiles > 160 || nk < 24) return 1;
-    int best = 1;
-    for (int s : {2, 3, 4, 6, 8})
-        if (nk % s == 0 && nk / s >= 6 && tiles * s <= 640) best = s;
-    return best;
-}
-
-static int run_conv(opd_detr* m, const Conv& c, const f16_t* x, int B, int H, int W, int OH, int OW, void* out, bool relu,
-                    const f16_t* res16, int stage = -1) {
+// ---- parameter builders: what every implicit-GEMM / attention launch of the forward has in common ------------------
+// a pointwise GEMM out[M][N] = x[M][K] . w[N][K]^T + bias, as a 1x1 "convolution" over M pixels
+static ConvGemmParams gemm_params(const opd_detr* m, const f16_t* x, const f16_t* w, const float* bias, void* out, int M, int N, int K) {
     ConvGemmParams p{}; p.dtype = m->dtype;
-    p.x = x; p.w = c.w; p.bias = c.bias; p.res16 = res16; p.res32 = nullptr; p.out = out; p.out16_aux = nullptr; p.zero16 = m->zero_bias;
-    p.B = B; p.H = H; p.W = W; p.Cin = c.Cin; p.OH = OH; p.OW = OW; p.N = c.Cout; p.KH = c.KH; p.KW = c.KW;
-    p.stride = c.stride; p.pad = c.pad; p.M = B * OH * OW; p.K = c.K; p.relu = relu ? 1 : 0; p.bias_period = 0;
-    p.out_f32 = 0; p.stem = c.stem ? 1 : 0; p.dbg = m->sw.dbg_gemm; p.wprefetch = m->sw.wprefetch & 1;
+    p.x = x; p.w = w; p.bias = bias; p.out = out; p.zero16 = m->zero_bias;
+    p.B = M; p.H = 1; p.W = 1; p.Cin = K; p.OH = 1; p.OW = 1; p.N = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
+    p.M = M; p.K = K; p.dbg = m->sw.dbg_gemm; p.wprefetch = m->sw.wprefetch & 1;
+    return p;
+}
+static ConvGemmParams conv_params(const opd_detr* m, const Conv& c, const f16_t* x, int B, int H, int W, int OH, int OW, void* out, bool relu) {
+    ConvGemmParams p = gemm_params(m, x, c.w, c.bias, out, B * OH * OW, c.Cout, c.K);
+    p.B = B; p.H = H; p.W = W; p.Cin = c.Cin; p.OH = OH; p.OW = OW; p.KH = c.KH; p.KW = c.KW; p.stride = c.stride; p.pad = c.pad;
+    p.relu = relu ? 1 : 0; p.stem = c.stem ? 1 : 0;
+    return p;
+}
+static AttnParams attn_params(const Fwd& c, const f16_t* q, int ldq, const f16_t* k, int ldk, const f16_t* v, int ldv, f16_t* o, int ldo, int Lq, int Lk,
+                              const int32_t* key_valid, int key_row) {
+    AttnParams p{}; p.dtype = c.m->dtype;
+    p.key_valid = key_valid; p.key_row = key_row;
+    p.q = q; p.k = k; p.v = v; p.o = o; p.B = c.B; p.heads = c.m->arch.heads; p.Lq = Lq; p.Lk = Lk;
+    p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+    p.scale = 1.0f / sqrtf((float)(c.m->arch.d_model / c.m->arch.heads));
+    return p;
+}
+static double attn_flops(const AttnParams& p) { return 4.0 * p.B * (double)p.heads * p.Lq * p.Lk * 32; }
+
+// a convolution of `B` frames (the stage-3 split's chains run part of the batch)
+static int run_conv(const Fwd& c, const Conv& cv, const f16_t* x, int B, int H, int W, int OH, int OW, void* out, bool relu, const f16_t* res16, int stage = -1) {
+    opd_detr* m = c.m;
+    ConvGemmParams p = conv_params(m, cv, x, B, H, W, OH, OW, out, relu);
+    p.res16 = res16;
     // algorithmic FLOPs (2 x MAC over the real taps/channels; the stem's zero padding is not counted)
-    if (const int splits = res16 ? 1 : conv_splits(m, c, stage); splits > 1 && (size_t)splits * p.M * c.Cout <= m->slab_floats) {
+    const double flops = 2.0 * p.M * (double)cv.Cout * cv.KH * cv.KW * cv.Cin;
+    const size_t n = (size_t)p.M * cv.Cout;
+    const Tap t{cv.KH == 3 ? "conv3x3" : "conv1x1", out, n * 2};
+    if (const int splits = res16 ? 1 : conv_splits(m, cv, stage); splits > 1 && (size_t)splits * n <= m->slab_floats) {
         p.out = m->d_slab; p.out_f32 = 1; p.relu = 0; p.split_k = splits;
-        RCCHK(timed_begin(m, CLS_CONV, 2.0 * p.M * (double)c.Cout * c.KH * c.KW * c.Cin));
-        HIPCHK(opd_launch_conv_gemm(p, m->stream));
-        RCCHK(timed_end(m));
-        RCCHK(timed_begin(m, CLS_OTHER, 0.0));
-        HIPCHK(opd_launch_reduce_act16(m->d_slab, splits, (size_t)p.M * c.Cout, reinterpret_cast<f16_t*>(out), (size_t)p.M * c.Cout, relu ? 1 : 0, m->stream, m->dtype));
-        RCCHK(timed_end(m));
-        RCCHK(tap(m, c.KH == 3 ? "conv3x3" : "conv1x1", out, (size_t)p.M * c.Cout * 2));
-        return OPD_OK;
+        RCCHK(c.launch(CLS_CONV, flops, [&] { return opd_launch_conv_gemm(p, c.stream); }));
+        return c.launch(CLS_OTHER, 0.0, [&] { return opd_launch_reduce_act16(m->d_slab, splits, n, reinterpret_cast<f16_t*>(out), n, relu ? 1 : 0, c.stream, m->dtype); }, {t});
     }
-    RCCHK(timed_begin(m, CLS_CONV, 2.0 * p.M * (double)c.Cout * c.KH * c.KW * c.Cin));
     // Wide layers with few row tiles (stage 4) through the eight-wave kernel (kernels_w8.hip; identical bits).  The choice follows the handle's
     // CONFIGURATION (max_batch and the layer), never the batch at hand.  OPD_W8: bit 0 = 3x3, bit 1 = 1x1 with K >= 1024, bit 2 = 1x1 with K = 512.
     bool w8 = false;
-    if (m->sw.w8 && c.Cout % 256 == 0 && c.Cout >= 512) {
-        const long long tiles = (((long long)OH * OW * m->cfg.max_batch + 127) / 128) * (c.Cout / 256);
+    if (m->sw.w8 && cv.Cout % 256 == 0 && cv.Cout >= 512) {
+        const long long tiles = (((long long)OH * OW * m->cfg.max_batch + 127) / 128) * (cv.Cout / 256);
         const bool few = tiles <= 3LL * m->num_cus;
-        const int kind = c.KH == 3 ? (m->sw.w8 & 1) : (c.K >= 1024 ? (m->sw.w8 & 2) : (c.K == 512 ? (m->sw.w8 & 4) : 0));
+        const int kind = cv.KH == 3 ? (m->sw.w8 & 1) : (cv.K >= 1024 ? (m->sw.w8 & 2) : (cv.K == 512 ? (m->sw.w8 & 4) : 0));
         w8 = few && kind && opd_conv_w8_supported(p);
     }
-    HIPCHK(w8 ? opd_launch_conv_w8(p, m->stream) : opd_launch_conv_gemm(p, m->stream));
-    RCCHK(timed_end(m));
-    RCCHK(tap(m, c.KH == 3 ? "conv3x3" : "conv1x1", out, (size_t)p.M * c.Cout * 2));
-    return OPD_OK;
+    return c.launch(CLS_CONV, flops, [&] { return w8 ? opd_launch_conv_w8(p, c.stream) : opd_launch_conv_gemm(p, c.stream); }, {t});
 }
 
-// out[M][N] = x16[M][K] . w[N][K]^T + bias (+ res32), as a 1x1 "convolution" over M pixels
-static int run_gemm(opd_detr* m, const f16_t* x, const f16_t* w, const float* bias, int bias_period, int M, int N, int K,
-                    void* out, bool out_f32, bool relu, const float* res32, const float* const* bias_ptrs = nullptr, int bias_pmod = 0,
-                    int bias_pcols = 0, const f16_t* x_alt = nullptr, int alt_mod = 0, int alt_cols = 0) {
-    ConvGemmParams p{}; p.dtype = m->dtype;
-    p.bias_ptrs = bias_ptrs; p.bias_pmod = bias_pmod; p.bias_pcols = bias_pcols;
-    p.x_alt = x_alt; p.alt_mod = alt_mod; p.alt_cols = alt_cols;
-    p.x = x; p.w = w; p.bias = bias; p.res16 = nullptr; p.res32 = res32; p.out = out; p.out16_aux = nullptr; p.zero16 = m->zero_bias;
-    p.B = M; p.H = 1; p.W = 1; p.Cin = K; p.OH = 1; p.OW = 1; p.N = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
-    p.M = M; p.K = K; p.relu = relu ? 1 : 0; p.bias_period = bias_period; p.out_f32 = out_f32 ? 1 : 0; p.stem = 0; p.dbg = m->sw.dbg_gemm; p.wprefetch = m->sw.wprefetch & 1;
-    RCCHK(timed_begin(m, CLS_GEMM, 2.0 * M * (double)N * K));
-    HIPCHK(opd_launch_conv_gemm(p, m->stream));
-    RCCHK(timed_end(m));
-    RCCHK(tap(m, "gemm", out, (size_t)M * N * (out_f32 ? 4 : 2)));
-    return OPD_OK;
+// a pointwise GEMM the caller has described (gemm_params + what differs)
+static int run_gemm(const Fwd& c, const ConvGemmParams& p) {
+    return c.launch(CLS_GEMM, 2.0 * p.M * (double)p.N * p.K, [&] { return opd_launch_conv_gemm(p, c.stream); }, {{"gemm", p.out, (size_t)p.M * p.N * (p.out_f32 ? 4 : 2)}});
+}
+// out16 = x16 . w^T + bias, bias a vector or (period > 0) a row-periodic table; optionally ReLU
+static int run_linear(const Fwd& c, const f16_t* x, const f16_t* w, const float* bias, int bias_period, int M, int N, int K, f16_t* out, bool relu) {
+    ConvGemmParams p = gemm_params(c.m, x, w, bias, out, M, N, K);
+    p.bias_period = bias_period; p.relu = relu ? 1 : 0;
+    return run_gemm(c, p);
+}
+// A projection of the encoder's tokens whose first `pos_cols` of every `mod` output columns see x + pos and the others x: either from the position
+// shadow with the plain bias vector, or from x alone with the [hw][N] table W.pos + b (`table_ptrs`: one table per frame, ragged batches)
+static int run_pos_proj(const Fwd& c, const f16_t* w, const float* bias_vec, const float* table, const float* const* table_ptrs, int N, int mod, int pos_cols, f16_t* out) {
+    opd_detr* m = c.m;
+    ConvGemmParams p = gemm_params(m, c.shadow ? m->d_xp16 : m->d_x16, w, c.shadow ? bias_vec : table, out, c.M, N, c.D);
+    if (c.shadow) { p.x_alt = m->d_x16; p.alt_mod = mod; p.alt_cols = pos_cols; }
+    else { p.bias_period = c.hw; p.bias_ptrs = table_ptrs; p.bias_pmod = mod; p.bias_pcols = pos_cols; }
+    return run_gemm(c, p);
 }
 
 // Split-K flavour for skinny / deep-K linears: slices write fp32 slabs, then ONE fused kernel reduces them in slice
 // order, adds the residual stream and applies the post-LayerNorm (gamma == nullptr: plain sum, e.g. input_projection).
-struct PosShadow { const float* pos; const float* const* pos_ptrs; int period; f16_t* yp16; };   // second fp16 output of a reduce + LN
-static int run_gemm_splitk_ln(opd_detr* m, const f16_t* x, const f16_t* w, const float* bias, int M, int N, int K, int splits,
-                              const float* res32, const LNp* ln, float* y32, f16_t* y16, int cls, const PosShadow* ps = nullptr) {
-    ConvGemmParams p{}; p.dtype = m->dtype;
-    p.x = x; p.w = w; p.bias = bias; p.out = m->d_slab; p.zero16 = m->zero_bias;
-    p.B = M; p.H = 1; p.W = 1; p.Cin = K; p.OH = 1; p.OW = 1; p.N = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
-    p.M = M; p.K = K; p.out_f32 = 1; p.split_k = splits;
-    RCCHK(timed_begin(m, cls, 2.0 * M * (double)N * K));
-    HIPCHK(opd_launch_conv_gemm(p, m->stream));
-    RCCHK(timed_end(m));
-    RCCHK(tap(m, "splitk_slabs", m->d_slab, (size_t)splits * M * N * 4));
-    RCCHK(timed_begin(m, CLS_OTHER, 0.0));
-    HIPCHK(opd_launch_reduce_ln_pos(m->d_slab, splits, (size_t)M * N, res32, ln ? ln->g : nullptr, ln ? ln->b : nullptr, y32, y16, M,
-                                    ps ? ps->pos : nullptr, ps ? ps->pos_ptrs : nullptr, ps ? ps->period : 0, ps ? ps->yp16 : nullptr, m->stream, m->dtype));
-    RCCHK(timed_end(m));
-    RCCHK(tap(m, "reduce_ln", y32, (size_t)M * N * 4));
-    return OPD_OK;
+static int run_gemm_splitk_ln(const Fwd& c, const f16_t* x, const f16_t* w, const float* bias, int M, int N, int K, int splits, const float* res32,
+                              const LNp* ln, float* y32, f16_t* y16, int cls, const PosShadow* ps = nullptr) {
+    opd_detr* m = c.m;
+    ConvGemmParams p = gemm_params(m, x, w, bias, m->d_slab, M, N, K);
+    p.out_f32 = 1; p.split_k = splits; p.dbg = 0; p.wprefetch = 0;   // (the sliced launch takes neither the ablation bits nor the weight warm-up)
+    RCCHK(c.launch(cls, 2.0 * M * (double)N * K, [&] { return opd_launch_conv_gemm(p, c.stream); }, {{"splitk_slabs", m->d_slab, (size_t)splits * M * N * 4}}));
+    return c.launch(CLS_OTHER, 0.0, [&] {
+        return opd_launch_reduce_ln_pos(m->d_slab, splits, (size_t)M * N, res32, ln ? ln->g : nullptr, ln ? ln->b : nullptr, y32, y16, M, ps ? ps->pos : nullptr,
+                                        ps ? ps->pos_ptrs : nullptr, ps ? ps->period : 0, ps ? ps->yp16 : nullptr, c.stream, m->dtype);
+    }, {{"reduce_ln", y32, (size_t)M * N * 4}});
 }
 
 // y = LayerNorm(x16 . w^T + bias + res32): one launch (kernels_rowln.hip); y32 may alias res32
-static int run_gemm_ln(opd_detr* m, const f16_t* x, const f16_t* w, const float* bias, int M, int K, const float* res32,
-                       const LNp& ln, float* y32, f16_t* y16) {
-    GemmLnParams p{}; p.dtype = m->dtype;
+static int run_gemm_ln(const Fwd& c, const f16_t* x, const f16_t* w, const float* bias, int M, int K, const float* res32, const LNp& ln, float* y32, f16_t* y16) {
+    GemmLnParams p{}; p.dtype = c.m->dtype;
     p.x = x; p.w = w; p.bias = bias; p.res32 = res32; p.gamma = ln.g; p.beta = ln.b; p.y32 = y32; p.y16 = y16; p.M = M; p.K = K;
-    RCCHK(timed_begin(m, CLS_GEMM, 2.0 * M * 256.0 * K));
-    HIPCHK(opd_launch_gemm_ln(p, m->stream));
-    RCCHK(timed_end(m));
-    RCCHK(tap(m, "gemm_ln", y32, (size_t)M * 256 * 4));
-    return OPD_OK;
+    return c.launch(CLS_GEMM, 2.0 * M * 256.0 * K, [&] { return opd_launch_gemm_ln(p, c.stream); }, {{"gemm_ln", y32, (size_t)M * 256 * 4}});
+}
+// Deep-K row-owner launches (kernels_rowln.hip::gemm_ln256_ring_kernel) for the two K = 2048 -> 256 linears of the encoder side:
+// the input projection (no LayerNorm) and every layer's FFN-2 (+ residual + LayerNorm); both also write the position shadow
+static int run_deep(const Fwd& c, const f16_t* x, const f16_t* w, const float* bias, int K, const float* res32, const LNp* ln, int cls) {
+    opd_detr* m = c.m;
+    GemmLnParams gp{}; gp.dtype = m->dtype;
+    gp.x = x; gp.w = w; gp.bias = bias; gp.res32 = res32; gp.gamma = ln ? ln->g : nullptr; gp.beta = ln ? ln->b : nullptr;
+    gp.y32 = m->d_x32; gp.y16 = m->d_x16; gp.M = c.M; gp.K = K; gp.deep_k = 1;
+    if (const PosShadow* ps = c.ps()) { gp.pos = ps->pos; gp.pos_ptrs = ps->pos_ptrs; gp.pos_period = ps->period; gp.yp16 = ps->yp16; }
+    return c.launch(cls, 2.0 * c.M * (double)c.D * K, [&] { return opd_launch_gemm_ln(gp, c.stream); }, {{ln ? "fc2_ln_ring" : "input_proj_ring", m->d_x32, (size_t)c.M * c.D * 4}});
 }
 
 // Decoder-sized linear layer (M = B x queries, K a multiple of 256): the one-shot kernel of kernels_rowln.hip; K > 256 is
 // cut into 256-wide slices whose fp32 slabs are summed by the fused reduce + residual + LayerNorm kernel.
-static int run_small_gemm(opd_detr* m, const f16_t* x, const f16_t* w, const float* bias, int bias_period, int M, int N, int K,
-                          f16_t* out16, bool relu) {
-    GemmK256Params p{}; p.dtype = m->dtype;
+static int run_small_gemm(const Fwd& c, const f16_t* x, const f16_t* w, const float* bias, int bias_period, int M, int N, int K, f16_t* out16, bool relu) {
+    GemmK256Params p{}; p.dtype = c.m->dtype;
     p.x = x; p.w = w; p.bias = bias; p.out16 = out16; p.M = M; p.N = N; p.ldx = K; p.ldw = K; p.slices = 1;
     p.bias_period = bias_period; p.relu = relu ? 1 : 0;
-    RCCHK(timed_begin(m, CLS_GEMM, 2.0 * M * (double)N * K));
-    HIPCHK(opd_launch_gemm_k256(p, m->stream));
-    RCCHK(timed_end(m));
-    RCCHK(tap(m, "gemm_k256", out16, (size_t)M * N * 2));
-    return OPD_OK;
+    return c.launch(CLS_GEMM, 2.0 * M * (double)N * K, [&] { return opd_launch_gemm_k256(p, c.stream); }, {{"gemm_k256", out16, (size_t)M * N * 2}});
 }
-static int run_small_gemm_ln(opd_detr* m, const f16_t* x, const f16_t* w, const float* bias, int M, int K, const float* res32,
-                             const LNp& ln, float* y32, f16_t* y16) {
+static int run_small_gemm_ln(const Fwd& c, const f16_t* x, const f16_t* w, const float* bias, int M, int K, const float* res32, const LNp& ln, float* y32, f16_t* y16) {
+    opd_detr* m = c.m;
     GemmK256Params p{}; p.dtype = m->dtype;
     p.x = x; p.w = w; p.bias = bias; p.out32 = m->d_slab; p.M = M; p.N = 256; p.ldx = K; p.ldw = K; p.slices = K / 256;
-    RCCHK(timed_begin(m, CLS_GEMM, 2.0 * M * 256.0 * K));
-    HIPCHK(opd_launch_gemm_k256(p, m->stream));
-    RCCHK(timed_end(m));
-    RCCHK(timed_begin(m, CLS_OTHER, 0.0));
-    HIPCHK(opd_launch_reduce_ln(m->d_slab, p.slices, (size_t)M * 256, res32, ln.g, ln.b, y32, y16, M, m->stream, m->dtype));
-    RCCHK(timed_end(m));
-    RCCHK(tap(m, "small_gemm_ln", y32, (size_t)M * 256 * 4));
-    return OPD_OK;
+    RCCHK(c.launch(CLS_GEMM, 2.0 * M * 256.0 * K, [&] { return opd_launch_gemm_k256(p, c.stream); }));
+    return c.launch(CLS_OTHER, 0.0, [&] { return opd_launch_reduce_ln(m->d_slab, p.slices, (size_t)M * 256, res32, ln.g, ln.b, y32, y16, M, c.stream, m->dtype); },
+                    {{"small_gemm_ln", y32, (size_t)M * 256 * 4}});
 }
 
-static int run_attn(opd_detr* m, const f16_t* q, int ldq, const f16_t* k, int ldk, const f16_t* v, int ldv, f16_t* o, int ldo,
-                    int B, int Lq, int Lk, const int32_t* key_valid = nullptr, int key_row = 0) {
-    AttnParams p{}; p.dtype = m->dtype;
-    p.key_valid = key_valid; p.key_row = key_row;
-    p.q = q; p.k = k; p.v = v; p.o = o; p.B = B; p.heads = m->arch.heads; p.Lq = Lq; p.Lk = Lk;
-    p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-    p.scale = 1.0f / sqrtf((float)(m->arch.d_model / m->arch.heads));
-    RCCHK(timed_begin(m, CLS_ATTN, 4.0 * B * (double)m->arch.heads * Lq * Lk * 32));
-    HIPCHK(opd_launch_attention(p, m->stream));
-    RCCHK(timed_end(m));
-    if (ldo == m->arch.d_model) RCCHK(tap(m, "attention", o, (size_t)B * Lq * ldo * 2));
-    return OPD_OK;
+// attention into [B][Lq][d_model] rows
+static int run_attn(const Fwd& c, const f16_t* q, int ldq, const f16_t* k, int ldk, const f16_t* v, int ldv, f16_t* o, int Lq, int Lk,
+                    const int32_t* key_valid = nullptr, int key_row = 0) {
+    const int D = c.m->arch.d_model;
+    const AttnParams p = attn_params(c, q, ldq, k, ldk, v, ldv, o, D, Lq, Lk, key_valid, key_row);
+    return c.launch(CLS_ATTN, attn_flops(p), [&] { return opd_launch_attention(p, c.stream); }, {{"attention", o, (size_t)c.B * Lq * D * 2}});
 }
 
 // The trunk plan (opd_model.h).  Every decision about how a bottleneck block runs is made here, from shapes and configuration only;
-// enqueue_forward's run_blocks walks the steps and launches.
+// trunk_blocks walks the steps and launches.
 TrunkPlan plan_trunk(const Arch& a, const std::vector<Block>& blocks, const opd_config& cfg, const Switches& sw, int B, int H2, int W2, int num_cus,
                      bool taps, int profiling, bool has_stream2) {
     TrunkPlan plan;
@@ -793,7 +472,6 @@ TrunkPlan plan_trunk(const Arch& a, const std::vector<Block>& blocks, const opd_
     return plan;
 }
 
-// Enqueues the whole forward on m->stream.  `pixels` must already be on the device.
 // True when some frame of the batch does not fill the H x W canvas (a ragged batch: padding mask path).
 static bool is_ragged(const int32_t* valid_hw, int B, int H, int W) {
     if (!valid_hw) return false;
@@ -802,217 +480,188 @@ static bool is_ragged(const int32_t* valid_hw, int B, int H, int W) {
     return false;
 }
 
-// `valid_hw` (host, nullable): [B][2] = (h, w) of each frame inside the H x W canvas.
-static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, int B, int H, int W, const int32_t* valid_hw = nullptr) {
+// ---- the forward, stage by stage (enqueue_forward below lists them) ------------------------------------------------
+// A ragged batch: one plan per frame's valid feature map, their fold pointers and the valid sizes uploaded for the kernels that mask
+static int fwd_prepare_ragged(Fwd& c, const int32_t* valid_hw) {
+    opd_detr* m = c.m;
     const Arch& a = m->arch;
-    Dims d;
-    compute_dims(B, H, W, &d);
-    const int fh = d.sh[3], fw = d.sw[3];
-    const bool ragged = is_ragged(valid_hw, B, H, W);
-    Plan* plan = nullptr;
-    const float* const* enc_bias_ptrs[16] = {};   // per encoder layer: device array of B per-frame fold pointers (ragged only)
-    const float* const* kv_bias_ptrs = nullptr;
-    const float* const* pos_ptrs = nullptr;       // per-frame position embeddings (ragged only)
-    const int32_t *d_valid = nullptr, *d_keyv = nullptr;
-    if (!ragged) {
-        RCCHK(get_plan(m, fh, fw, fh, fw, &plan));
-    } else {
-        if (a.enc_layers > 16) return fail(OPD_EINVAL, "ragged batches: at most 16 encoder layers");
-        m->h_valid_hw.assign(valid_hw, valid_hw + 2 * B);
-        m->h_key_valid.resize((size_t)2 * B);
-        m->h_bias_ptrs.assign((size_t)(a.enc_layers + 2) * B, nullptr);
-        for (int b = 0; b < B; ++b) {
-            const int vh = valid_hw[2 * b], vw = valid_hw[2 * b + 1];
-            if (vh < 1 || vw < 1 || vh > H || vw > W) return fail(OPD_EINVAL, "valid_hw outside the frame canvas");
-            const int vfh = valid_prefix(vh, H, fh), vfw = valid_prefix(vw, W, fw);
-            if (vfh < 1 || vfw < 1) return fail(OPD_EINVAL, "frame too small: no valid feature-map position");
-            m->h_key_valid[2 * b] = vfh; m->h_key_valid[2 * b + 1] = vfw;
-            Plan* pb = nullptr;
-            RCCHK(get_plan(m, fh, fw, vfh, vfw, &pb));
-            if (b == 0) plan = pb;
-            for (int i = 0; i < a.enc_layers; ++i) m->h_bias_ptrs[(size_t)i * B + b] = pb->rb_enc[i];
-            m->h_bias_ptrs[(size_t)a.enc_layers * B + b] = pb->rb_kv;
-            m->h_bias_ptrs[(size_t)(a.enc_layers + 1) * B + b] = pb->d_pos;
-        }
-        // (member vectors: they outlive the asynchronous copies; every entry point synchronises before it returns)
-        HIPCHK(hipMemcpyAsync(m->d_valid_hw, m->h_valid_hw.data(), (size_t)2 * B * 4, hipMemcpyHostToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync(m->d_key_valid, m->h_key_valid.data(), (size_t)2 * B * 4, hipMemcpyHostToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync(m->d_bias_ptrs, m->h_bias_ptrs.data(), m->h_bias_ptrs.size() * sizeof(float*), hipMemcpyHostToDevice, m->stream));
-        for (int i = 0; i < a.enc_layers; ++i) enc_bias_ptrs[i] = m->d_bias_ptrs + (size_t)i * B;
-        kv_bias_ptrs = m->d_bias_ptrs + (size_t)a.enc_layers * B;
-        pos_ptrs = m->d_bias_ptrs + (size_t)(a.enc_layers + 1) * B;
-        d_valid = m->d_valid_hw;
-        d_keyv = m->d_key_valid;
+    const int B = c.B, fh = c.d.stage_h[3], fw = c.d.stage_w[3];
+    if (a.enc_layers > 16) return fail(OPD_EINVAL, "ragged batches: at most 16 encoder layers");
+    m->h_valid_hw.assign(valid_hw, valid_hw + 2 * B);
+    m->h_key_valid.resize((size_t)2 * B);
+    m->h_bias_ptrs.assign((size_t)(a.enc_layers + 2) * B, nullptr);
+    for (int b = 0; b < B; ++b) {
+        const int vh = valid_hw[2 * b], vw = valid_hw[2 * b + 1];
+        if (vh < 1 || vw < 1 || vh > c.H || vw > c.W) return fail(OPD_EINVAL, "valid_hw outside the frame canvas");
+        const int vfh = valid_prefix(vh, c.H, fh), vfw = valid_prefix(vw, c.W, fw);
+        if (vfh < 1 || vfw < 1) return fail(OPD_EINVAL, "frame too small: no valid feature-map position");
+        m->h_key_valid[2 * b] = vfh; m->h_key_valid[2 * b + 1] = vfw;
+        Plan* pb = nullptr;
+        RCCHK(get_plan(m, fh, fw, vfh, vfw, &pb));
+        if (b == 0) c.plan = pb;
+        for (int i = 0; i < a.enc_layers; ++i) m->h_bias_ptrs[(size_t)i * B + b] = pb->rb_enc[i];
+        m->h_bias_ptrs[(size_t)a.enc_layers * B + b] = pb->rb_kv;
+        m->h_bias_ptrs[(size_t)(a.enc_layers + 1) * B + b] = pb->d_pos;
     }
-    timed_reset(m);
-    m->tap_next = 0;
-    if (pixel_format == OPD_PIXELS_U8_BGR_HWC) RCCHK(tap(m, "pixels_u8", d_pixels, (size_t)B * H * W * 3));
-    MARK(0);
+    // (member vectors: they outlive the asynchronous copies; every entry point synchronises before it returns)
+    HIPCHK(hipMemcpyAsync(m->d_valid_hw, m->h_valid_hw.data(), (size_t)2 * B * 4, hipMemcpyHostToDevice, c.stream));
+    HIPCHK(hipMemcpyAsync(m->d_key_valid, m->h_key_valid.data(), (size_t)2 * B * 4, hipMemcpyHostToDevice, c.stream));
+    HIPCHK(hipMemcpyAsync(m->d_bias_ptrs, m->h_bias_ptrs.data(), m->h_bias_ptrs.size() * sizeof(float*), hipMemcpyHostToDevice, c.stream));
+    for (int i = 0; i < a.enc_layers; ++i) c.enc_bias_ptrs[i] = m->d_bias_ptrs + (size_t)i * B;
+    c.kv_bias_ptrs = m->d_bias_ptrs + (size_t)a.enc_layers * B;
+    c.pos_ptrs = m->d_bias_ptrs + (size_t)(a.enc_layers + 1) * B;
+    c.d_valid = m->d_valid_hw;
+    c.d_keyv = m->d_key_valid;
+    return OPD_OK;
+}
+
+// pre-processing, stem 7x7 and max-pool -> d_pool
+static int fwd_stem(const Fwd& c, const void* d_pixels, int pixel_format) {
+    opd_detr* m = c.m;
+    const Dims& d = c.d;
+    const int B = c.B, H = c.H, W = c.W;
     const int Hp = 2 * d.H1 + 6, Wp = 2 * d.W1 + 6;  // padded image seen by the stem: rows/cols 2*o + k, k = 0..7
-    const bool prep_in_stem = m->sw.fuse_prep && m->sw.fuse_stem_pool && pixel_format == OPD_PIXELS_U8_BGR_HWC;
-    if (!prep_in_stem) {
-        RCCHK(timed_begin(m, CLS_OTHER, 0.0));
-        if (pixel_format == OPD_PIXELS_U8_BGR_HWC)
-            HIPCHK(opd_launch_preprocess_u8(reinterpret_cast<const uint8_t*>(d_pixels), m->d_x4, B, H, W, Hp, Wp, d_valid, m->stream, m->dtype));
-        else
-            HIPCHK(opd_launch_preprocess_f32(reinterpret_cast<const float*>(d_pixels), m->d_x4, B, H, W, Hp, Wp, d_valid, m->stream, m->dtype));
-        RCCHK(timed_end(m));
-    }
-    if (prep_in_stem) {
-        RCCHK(timed_begin(m, CLS_CONV, 2.0 * B * d.H1 * d.W1 * 64.0 * 147.0));
-        HIPCHK(opd_launch_stem_pool_u8(reinterpret_cast<const uint8_t*>(d_pixels), d_valid, m->stem.w, m->stem.bias, m->d_pool, B, H, W, d.H1, d.W1,
-                                       d.H2, d.W2, m->stream, m->dtype));
-        RCCHK(timed_end(m));
-        RCCHK(tap(m, "stem_pool_u8", m->d_pool, (size_t)B * d.H2 * d.W2 * 64 * 2));
-    } else if (m->sw.fuse_stem_pool) {
-        RCCHK(timed_begin(m, CLS_CONV, 2.0 * B * d.H1 * d.W1 * 64.0 * 147.0));
-        HIPCHK(opd_launch_stem_pool(m->d_x4, m->stem.w, m->stem.bias, m->d_pool, B, Hp, Wp, d.H1, d.W1, d.H2, d.W2, m->stream, m->dtype));
-        RCCHK(timed_end(m));
-    } else {
-        ConvGemmParams p{}; p.dtype = m->dtype;
-        p.x = m->d_x4; p.w = m->stem.w; p.bias = m->stem.bias; p.out = m->d_stem; p.zero16 = m->zero_bias;
-        p.B = B; p.H = Hp; p.W = Wp; p.Cin = 256; p.OH = d.H1; p.OW = d.W1; p.N = 64; p.KH = 1; p.KW = 1; p.stride = 2; p.pad = 0;
-        p.M = B * d.H1 * d.W1; p.K = 256; p.relu = 1; p.stem = 2;
-        RCCHK(timed_begin(m, CLS_CONV, 2.0 * p.M * 64.0 * 147.0));
-        HIPCHK(opd_launch_conv_gemm(p, m->stream));
-        RCCHK(timed_end(m));
-        RCCHK(timed_begin(m, CLS_OTHER, 0.0));
-        HIPCHK(opd_launch_maxpool(m->d_stem, m->d_pool, B, d.H1, d.W1, 64, d.H2, d.W2, m->stream, m->dtype));
-        RCCHK(timed_end(m));
-    }
-    MARK(1);
-    // ---- trunk: the blocks of stages 1-4 as plan_trunk decided.  run_blocks launches blocks [l_begin, l_end) of stages [s_begin, s_end) for
-    // frames [b0, b0 + nb): every tensor of those frames lives at frame offset b0 of its buffer (b0 > 0: the stage-3 split's second chain).
-    const TrunkPlan tp = plan_trunk(a, m->blocks, m->cfg, m->sw, B, d.H2, d.W2, m->num_cus, m->taps != 0, m->profiling, m->stream2 != nullptr);
-    struct TrunkState { int cur_id; int ch, cw; int z_id; int prev_id; };   // cur_id / prev_id (the previous block's input) 0 = pool, 1 = t0, 2 = t1;
-                                                                            // z_id -1 / 0 = m0 / 1 = m1: the z a fused tail computed for the next block
-    auto run_blocks = [&](int s_begin, int s_end, int b0, int nb, TrunkState& st, int l_begin = 0, int l_end = 1 << 30) -> int {
-        auto trunk = [&](int id, size_t per_frame) { return (id == 0 ? m->d_pool : id == 1 ? m->d_t0 : m->d_t1) + (size_t)b0 * per_frame; };
-        auto mid = [&](int id, size_t per_frame) { return (id ? m->d_m1 : m->d_m0) + (size_t)b0 * per_frame; };
-        for (int s = s_begin; s < s_end; ++s) {
-            for (int l = l_begin; l < a.depths[s] && l < l_end; ++l) {   // (a block range only makes sense with s_end == s_begin + 1)
-                const int bi = m->stage_first[s] + l;
-                const Block& b = m->blocks[bi];
-                const TrunkStep& t = tp.steps[bi];
-                const int ch = st.ch, cw = st.cw;
-                const int oh = (b.c1.stride == 2) ? down2(ch) : ch, ow = (b.c1.stride == 2) ? down2(cw) : cw;
-                const int C1 = b.c1.Cin, C2 = b.c2.Cout, C3 = t.C3;
-                const f16_t* cur = trunk(st.cur_id, (size_t)ch * cw * b.c0.Cin);
-                const int out_id = st.cur_id == 1 ? 2 : 1;
-                f16_t* out = trunk(out_id, (size_t)oh * ow * C2);
-                f16_t* const scb = m->d_sc + (size_t)b0 * oh * ow * C2;
-                if (t.sc == SC_LAUNCH) RCCHK(run_conv(m, b.sc, cur, nb, ch, cw, oh, ow, scb, false, nullptr));
-                const f16_t* res = t.res == RES_TRUNK ? cur : t.res == RES_SHORTCUT ? scb : nullptr;
-                int x1_id = st.z_id;
-                const f16_t* x1 = nullptr;
-                if (x1_id >= 0) {
-                    x1 = mid(x1_id, (size_t)ch * cw * C1);
-                } else {
-                    x1_id = 0;
-                    f16_t* c0out = mid(0, (size_t)ch * cw * b.c0.Cout);
-                    RCCHK(run_conv(m, b.c0, cur, nb, ch, cw, ch, cw, c0out, true, nullptr, (l == 0 && s > 0) ? s - 1 : s));
-                    x1 = c0out;
-                }
-                st.z_id = -1;
-                if (t.path == PATH_TAIL) {
-                    const Block* nbk = C3 ? &m->blocks[bi + 1] : nullptr;
-                    BtailParams p{}; p.dtype = m->dtype;
-                    p.x1 = x1; p.w1 = b.c1.w; p.b1 = b.c1.bias; p.w2p = C1 == 256 ? b.c2.wp : b.c2.w; p.b2 = b.c2.bias; p.res = res;   // (K-permuted copies: stage-3 kernel only)
-                    p.y = t.store == STORE_A1 ? nullptr : out;
-                    if (t.sc == SC_TAIL) { p.xs = cur; p.wsc = b.sc.w; p.b2 = b.bias2sc; }
-                    f16_t* z = mid(1 - x1_id, (size_t)oh * ow * C3);
-                    if (C3) { p.w3p = C1 == 256 ? nbk->c0.wp : nbk->c0.w; p.b3 = nbk->c0.bias; p.z = z; }
-                    // stage 1's a1 hand-over (STORE_A1 -> RES_REBUILD) lives in the shortcut buffer, which a fused shortcut leaves unused
-                    f16_t* const a1_keep = m->d_sc + (size_t)b0 * oh * ow * C1;
-                    if (t.store == STORE_A1) p.a1_out = a1_keep;
-                    if (t.res == RES_REBUILD) {
-                        const Block& pb = m->blocks[bi - 1];
-                        p.rc = 1; p.rc_a1 = a1_keep; p.rc_xs = trunk(st.prev_id, (size_t)ch * cw * pb.c0.Cin); p.rc_w2 = pb.c2.w; p.rc_wsc = pb.sc.w; p.rc_b = pb.bias2sc;
-                    }
-                    p.y_stride2 = t.store == STORE_Y_STRIDE2;
-                    p.B = nb; p.H = ch; p.W = cw; p.OH = oh; p.OW = ow; p.stride = b.c1.stride; p.M = nb * oh * ow; p.C1 = C1; p.C3 = C3;
-                    p.rev = b0 ? t.rev_b : t.rev;
-                    p.dbg = m->sw.dbg_btail;
-                    RCCHK(timed_begin(m, CLS_CONV, 2.0 * p.M * ((double)C1 * 9 * C1 + 4.0 * C1 * C1 + 4.0 * C1 * C3 + (t.sc == SC_TAIL ? 64.0 * 256 : 0.0))));
-                    HIPCHK(opd_launch_btail(p, m->stream));
-                    RCCHK(timed_end(m));
-                    if (p.y) RCCHK(tap(m, "btail_y", out, (size_t)p.M * 4 * C1 * 2));
-                    if (C3) RCCHK(tap(m, "btail_z", z, (size_t)p.M * C3 * 2));
-                    if (C3) st.z_id = 1 - x1_id;
-                } else {
-                    f16_t* a1 = mid(1 - x1_id, (size_t)oh * ow * C1);
-                    RCCHK(run_conv(m, b.c1, x1, nb, ch, cw, oh, ow, a1, true, nullptr, s));
-                    if (t.path == PATH_DUAL) {
-                        ConvGemmParams p{}; p.dtype = m->dtype;
-                        p.x = a1; p.w = b.w2sc; p.bias = b.bias2sc; p.out = out; p.zero16 = m->zero_bias;
-                        p.B = nb; p.H = oh; p.W = ow; p.Cin = C1; p.OH = oh; p.OW = ow; p.N = C2; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
-                        p.M = nb * oh * ow; p.K1 = C1; p.K = C1 + b.sc.Cin; p.relu = 1;
-                        p.x2 = cur; p.H2 = ch; p.W2 = cw; p.Cin2 = b.sc.Cin; p.stride2 = b.sc.stride; p.dbg = m->sw.dbg_gemm; p.wprefetch = m->sw.wprefetch & 1;
-                        RCCHK(timed_begin(m, CLS_CONV, 2.0 * p.M * (double)C2 * p.K));
-                        HIPCHK(opd_launch_conv_gemm(p, m->stream));
-                        RCCHK(timed_end(m));
-                        RCCHK(tap(m, "dual_expand", out, (size_t)p.M * C2 * 2));
-                    } else {
-                        RCCHK(run_conv(m, b.c2, a1, nb, oh, ow, oh, ow, out, true, res));
-                    }
-                }
-                st.prev_id = st.cur_id; st.cur_id = out_id; st.ch = oh; st.cw = ow;
-            }
-            if (b0 + nb == B && l_end >= a.depths[s]) MARK(2 + s);
+    const bool u8 = pixel_format == OPD_PIXELS_U8_BGR_HWC;
+    const double flops = 2.0 * B * d.H1 * d.W1 * 64.0 * 147.0;
+    if (m->sw.fuse_prep && m->sw.fuse_stem_pool && u8)
+        return c.launch(CLS_CONV, flops, [&] {
+            return opd_launch_stem_pool_u8(reinterpret_cast<const uint8_t*>(d_pixels), c.d_valid, m->stem.w, m->stem.bias, m->d_pool, B, H, W, d.H1, d.W1, d.H2, d.W2,
+                                           c.stream, m->dtype);
+        }, {{"stem_pool_u8", m->d_pool, (size_t)B * d.H2 * d.W2 * 64 * 2}});
+    RCCHK(c.launch(CLS_OTHER, 0.0, [&] {
+        return u8 ? opd_launch_preprocess_u8(reinterpret_cast<const uint8_t*>(d_pixels), m->d_x4, B, H, W, Hp, Wp, c.d_valid, c.stream, m->dtype)
+                  : opd_launch_preprocess_f32(reinterpret_cast<const float*>(d_pixels), m->d_x4, B, H, W, Hp, Wp, c.d_valid, c.stream, m->dtype);
+    }));
+    if (m->sw.fuse_stem_pool)
+        return c.launch(CLS_CONV, flops, [&] { return opd_launch_stem_pool(m->d_x4, m->stem.w, m->stem.bias, m->d_pool, B, Hp, Wp, d.H1, d.W1, d.H2, d.W2, c.stream, m->dtype); });
+    // two kernels, for cross-checking: the stem as a stride-2 pointwise GEMM over the padded NHWC4 image's 8 x 8 x 4 windows, then the pool
+    ConvGemmParams p = gemm_params(m, m->d_x4, m->stem.w, m->stem.bias, m->d_stem, B * d.H1 * d.W1, 64, 256);
+    p.B = B; p.H = Hp; p.W = Wp; p.OH = d.H1; p.OW = d.W1; p.stride = 2; p.relu = 1; p.stem = 2;
+    p.dbg = 0; p.wprefetch = 0;   // (this launch takes neither the ablation bits nor the weight warm-up)
+    RCCHK(c.launch(CLS_CONV, 2.0 * p.M * 64.0 * 147.0, [&] { return opd_launch_conv_gemm(p, c.stream); }));
+    return c.launch(CLS_OTHER, 0.0, [&] { return opd_launch_maxpool(m->d_stem, m->d_pool, B, d.H1, d.W1, 64, d.H2, d.W2, c.stream, m->dtype); });
+}
+
+// ---- trunk: the blocks of stages 1-4 as plan_trunk decided.  trunk_blocks launches blocks [l_begin, l_end) of stage s for frames
+// [b0, b0 + nb) on c.stream: every tensor of those frames lives at frame offset b0 of its buffer (b0 > 0: the stage-3 split's second chain).
+struct TrunkState { int cur_id; int ch, cw; int z_id; int prev_id; };   // cur_id / prev_id (the previous block's input) 0 = pool, 1 = t0, 2 = t1;
+                                                                        // z_id -1 / 0 = m0 / 1 = m1: the z a fused tail computed for the next block
+static int trunk_blocks(const Fwd& c, const TrunkPlan& tp, int s, int b0, int nb, TrunkState& st, int l_begin = 0, int l_end = 1 << 30) {
+    opd_detr* m = c.m;
+    auto trunk = [&](int id, size_t per_frame) { return (id == 0 ? m->d_pool : id == 1 ? m->d_t0 : m->d_t1) + (size_t)b0 * per_frame; };
+    auto mid = [&](int id, size_t per_frame) { return (id ? m->d_m1 : m->d_m0) + (size_t)b0 * per_frame; };
+    for (int l = l_begin; l < m->arch.depths[s] && l < l_end; ++l) {
+        const int bi = m->stage_first[s] + l;
+        const Block& b = m->blocks[bi];
+        const TrunkStep& t = tp.steps[bi];
+        const int ch = st.ch, cw = st.cw;
+        const int oh = (b.c1.stride == 2) ? down2(ch) : ch, ow = (b.c1.stride == 2) ? down2(cw) : cw;
+        const int C1 = b.c1.Cin, C2 = b.c2.Cout, C3 = t.C3;
+        const f16_t* cur = trunk(st.cur_id, (size_t)ch * cw * b.c0.Cin);
+        const int out_id = st.cur_id == 1 ? 2 : 1;
+        f16_t* out = trunk(out_id, (size_t)oh * ow * C2);
+        f16_t* const scb = m->d_sc + (size_t)b0 * oh * ow * C2;
+        if (t.sc == SC_LAUNCH) RCCHK(run_conv(c, b.sc, cur, nb, ch, cw, oh, ow, scb, false, nullptr));
+        const f16_t* res = t.res == RES_TRUNK ? cur : t.res == RES_SHORTCUT ? scb : nullptr;
+        int x1_id = st.z_id;
+        const f16_t* x1 = nullptr;
+        if (x1_id >= 0) {
+            x1 = mid(x1_id, (size_t)ch * cw * C1);
+        } else {
+            x1_id = 0;
+            f16_t* c0out = mid(0, (size_t)ch * cw * b.c0.Cout);
+            RCCHK(run_conv(c, b.c0, cur, nb, ch, cw, ch, cw, c0out, true, nullptr, (l == 0 && s > 0) ? s - 1 : s));
+            x1 = c0out;
         }
-        return OPD_OK;
-    };
-    TrunkState st{0, d.H2, d.W2, -1, -1};
-    RCCHK(run_blocks(0, 2, 0, B, st));
-    const int nbA = tp.split;
-    RCCHK(run_blocks(2, 3, 0, B, st, 0, 1));   // first block (stride 2, shortcut): whole batch
-    if (nbA < B) {
-        TrunkState ta = st, tb = st;
-        HIPCHK(hipEventRecord(m->ev_fork, m->stream));
-        HIPCHK(hipStreamWaitEvent(m->stream2, m->ev_fork, 0));
-        // whatever happens in either chain, `stream2` is rejoined before this function returns (an unjoined fork would leak into
-        // the next forward's events, or leave a capture with a dangling branch) and m->stream is the main stream again
-        hipStream_t main_stream = m->stream;
-        const int rc_a = run_blocks(2, 3, 0, nbA, ta, 1);
-        m->stream = m->stream2;
-        const int rc_b = rc_a == OPD_OK ? run_blocks(2, 3, nbA, B - nbA, tb, 1) : OPD_OK;
-        m->stream = main_stream;
-        const hipError_t ej = hipEventRecord(m->ev_join, m->stream2);
-        const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(m->stream, m->ev_join, 0) : ej;
-        RCCHK(rc_a);
-        RCCHK(rc_b);
-        HIPCHK(ew);
-        MARK(4);   // (stage 3 ends at the join, not where the second chain's own mark fell)
-        st = ta;
-    } else {
-        RCCHK(run_blocks(2, 3, 0, B, st, 1));
+        st.z_id = -1;
+        if (t.path == PATH_TAIL) {
+            const Block* nbk = C3 ? &m->blocks[bi + 1] : nullptr;
+            BtailParams p{}; p.dtype = m->dtype;
+            p.x1 = x1; p.w1 = b.c1.w; p.b1 = b.c1.bias; p.w2p = C1 == 256 ? b.c2.wp : b.c2.w; p.b2 = b.c2.bias; p.res = res;   // (K-permuted copies: stage-3 kernel only)
+            p.y = t.store == STORE_A1 ? nullptr : out;
+            if (t.sc == SC_TAIL) { p.xs = cur; p.wsc = b.sc.w; p.b2 = b.bias2sc; }
+            f16_t* z = mid(1 - x1_id, (size_t)oh * ow * C3);
+            if (C3) { p.w3p = C1 == 256 ? nbk->c0.wp : nbk->c0.w; p.b3 = nbk->c0.bias; p.z = z; }
+            // stage 1's a1 hand-over (STORE_A1 -> RES_REBUILD) lives in the shortcut buffer, which a fused shortcut leaves unused
+            f16_t* const a1_keep = m->d_sc + (size_t)b0 * oh * ow * C1;
+            if (t.store == STORE_A1) p.a1_out = a1_keep;
+            if (t.res == RES_REBUILD) {
+                const Block& pb = m->blocks[bi - 1];
+                p.rc = 1; p.rc_a1 = a1_keep; p.rc_xs = trunk(st.prev_id, (size_t)ch * cw * pb.c0.Cin); p.rc_w2 = pb.c2.w; p.rc_wsc = pb.sc.w; p.rc_b = pb.bias2sc;
+            }
+            p.y_stride2 = t.store == STORE_Y_STRIDE2;
+            p.B = nb; p.H = ch; p.W = cw; p.OH = oh; p.OW = ow; p.stride = b.c1.stride; p.M = nb * oh * ow; p.C1 = C1; p.C3 = C3;
+            p.rev = b0 ? t.rev_b : t.rev;
+            p.dbg = m->sw.dbg_btail;
+            RCCHK(c.launch(CLS_CONV, 2.0 * p.M * ((double)C1 * 9 * C1 + 4.0 * C1 * C1 + 4.0 * C1 * C3 + (t.sc == SC_TAIL ? 64.0 * 256 : 0.0)),
+                           [&] { return opd_launch_btail(p, c.stream); },
+                           {{"btail_y", p.y ? out : nullptr, (size_t)p.M * 4 * C1 * 2}, {"btail_z", C3 ? z : nullptr, (size_t)p.M * C3 * 2}}));
+            if (C3) st.z_id = 1 - x1_id;
+        } else {
+            f16_t* a1 = mid(1 - x1_id, (size_t)oh * ow * C1);
+            RCCHK(run_conv(c, b.c1, x1, nb, ch, cw, oh, ow, a1, true, nullptr, s));
+            if (t.path == PATH_DUAL) {   // the 1x1 expand over [a1 | the block input]: the shortcut as extra K
+                ConvGemmParams p = gemm_params(m, a1, b.w2sc, b.bias2sc, out, nb * oh * ow, C2, C1 + b.sc.Cin);
+                p.B = nb; p.H = oh; p.W = ow; p.OH = oh; p.OW = ow; p.Cin = C1; p.K1 = C1; p.relu = 1;
+                p.x2 = cur; p.H2 = ch; p.W2 = cw; p.Cin2 = b.sc.Cin; p.stride2 = b.sc.stride;
+                RCCHK(c.launch(CLS_CONV, 2.0 * p.M * (double)C2 * p.K, [&] { return opd_launch_conv_gemm(p, c.stream); }, {{"dual_expand", out, (size_t)p.M * C2 * 2}}));
+            } else {
+                RCCHK(run_conv(c, b.c2, a1, nb, oh, ow, oh, ow, out, true, res));
+            }
+        }
+        st.prev_id = st.cur_id; st.cur_id = out_id; st.ch = oh; st.cw = ow;
     }
-    RCCHK(run_blocks(3, 4, 0, B, st));
-    const f16_t* cur = st.cur_id == 1 ? m->d_t0 : m->d_t1;
-    const int ch = st.ch, cw = st.cw;
-    // ---- input projection -> encoder ------------------------------------------------------------------------------
-    const int hw = ch * cw, M = B * hw, D = a.d_model, F = a.ffn;
+    return OPD_OK;
+}
+
+// Stage 3 with the frame split of plan_trunk: its first block (stride 2, shortcut) for the whole batch, then blocks 1.. as two chains of frames
+static int trunk_stage3_split(const Fwd& c, const TrunkPlan& tp, TrunkState& st) {
+    opd_detr* m = c.m;
+    RCCHK(trunk_blocks(c, tp, 2, 0, c.B, st, 0, 1));
+    if (tp.split == c.B) return trunk_blocks(c, tp, 2, 0, c.B, st, 1);
+    TrunkState ta = st, tb = st;
+    Fwd c2 = c;   // the second chain: the same call, launching on the branch stream
+    c2.stream = m->stream2;
+    HIPCHK(hipEventRecord(m->ev_fork, c.stream));
+    HIPCHK(hipStreamWaitEvent(m->stream2, m->ev_fork, 0));
+    // whatever happens in either chain, `stream2` is rejoined before this function returns (an unjoined fork would leak into
+    // the next forward's events, or leave a capture with a dangling branch)
+    const int rc_a = trunk_blocks(c, tp, 2, 0, tp.split, ta, 1);
+    const int rc_b = rc_a == OPD_OK ? trunk_blocks(c2, tp, 2, tp.split, c.B - tp.split, tb, 1) : OPD_OK;
+    const hipError_t ej = hipEventRecord(m->ev_join, m->stream2);
+    const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(c.stream, m->ev_join, 0) : ej;
+    RCCHK(rc_a);
+    RCCHK(rc_b);
+    HIPCHK(ew);
+    st = ta;
+    return OPD_OK;
+}
+
+static int fwd_trunk(Fwd& c) {
+    opd_detr* m = c.m;
+    const TrunkPlan tp = plan_trunk(m->arch, m->blocks, m->cfg, m->sw, c.B, c.d.H2, c.d.W2, m->num_cus, m->taps != 0, m->profiling, m->stream2 != nullptr);
+    TrunkState st{0, c.d.H2, c.d.W2, -1, -1};
+    for (int s = 0; s < 4; ++s) {
+        RCCHK(s == 2 ? trunk_stage3_split(c, tp, st) : trunk_blocks(c, tp, s, 0, c.B, st));
+        MARK(2 + s);   // (stage 3 ends at the join of its two chains)
+    }
+    c.feat = st.cur_id == 1 ? m->d_t0 : m->d_t1;
+    c.fh = st.ch; c.fw = st.cw; c.hw = st.ch * st.cw; c.M = c.B * c.hw;
+    return OPD_OK;
+}
+
+// ---- input projection -> encoder; *kv_done: the last layer's FFN launch has written the decoder's memory keys / values as its tail
+static int fwd_encoder(Fwd& c, bool* kv_done) {
+    opd_detr* m = c.m;
+    const Arch& a = m->arch;
+    const int M = c.M, D = c.D, F = c.F;
     // pos_shadow: whoever writes x (input projection, each layer's last LayerNorm) also writes fp16(x + pos); the fused QKV projection
     // reads that for its q / k column tiles and x for its v tiles, with a plain bias vector -- instead of x everywhere plus a [hw][768]
     // fp32 table W.pos + b added per output tile (two divisions and 16 dependent table loads per lane in front of the first MFMA:
     // 14.2 us per launch against 9.4 for the same GEMM with a bias vector; decoder K/V 44.7 against 24-27)
-    const bool shadow = m->sw.pos_shadow && D == 256 && m->enc[0].bqkv && m->bkv_all;
-    const PosShadow psh{plan->d_pos, pos_ptrs, hw, m->d_xp16};
-    const PosShadow* ps = shadow ? &psh : nullptr;
-    // Deep-K row-owner launches (kernels_rowln.hip::gemm_ln256_ring_kernel) for the two K = 2048 -> 256 linears of the encoder side:
-    // the input projection (no LayerNorm) and every layer's FFN-2 (+ residual + LayerNorm); both also write the position shadow
-    auto run_deep = [&](const f16_t* x, const Lin* lin, const f16_t* w, const float* bias, int K, const float* res32, const LNp* ln, int cls) -> int {
-        GemmLnParams gp{}; gp.dtype = m->dtype;
-        gp.x = x; gp.w = w; gp.bias = bias; gp.res32 = res32; gp.gamma = ln ? ln->g : nullptr; gp.beta = ln ? ln->b : nullptr;
-        gp.y32 = m->d_x32; gp.y16 = m->d_x16; gp.M = M; gp.K = K; gp.deep_k = 1;
-        if (ps) { gp.pos = ps->pos; gp.pos_ptrs = ps->pos_ptrs; gp.pos_period = ps->period; gp.yp16 = ps->yp16; }
-        RCCHK(timed_begin(m, cls, 2.0 * M * (double)D * K));
-        HIPCHK(opd_launch_gemm_ln(gp, m->stream));
-        RCCHK(timed_end(m));
-        RCCHK(tap(m, ln ? "fc2_ln_ring" : "input_proj_ring", m->d_x32, (size_t)M * D * 4));
-        (void)lin;
-        return OPD_OK;
-    };
+    c.shadow = m->sw.pos_shadow && D == 256 && m->enc[0].bqkv && m->bkv_all;
+    c.psh = PosShadow{c.plan->d_pos, c.pos_ptrs, c.hw, m->d_xp16};
+    const PosShadow* ps = c.ps();
     // Small handles (round 5): the row-owner launches of the encoder side own 48 / 64 rows per workgroup and stream a whole weight matrix through
     // each -- at max_batch = 1 that is 22 workgroups walking 2.2 MB apiece (42 us per layer, 27 us for the input projection).  Where the handle's
     // CONFIGURATION bounds the token count below ~1400 the same linears run as tiled GEMMs with the reduction split eight ways over workgroups
@@ -1021,30 +670,25 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
     const int enc_splits = small_enc ? 8 : 4;
     const bool deep_ok = m->sw.deep_fc2 && D == 256 && !small_enc;
     if (deep_ok && m->proj.K % 64 == 0 && (size_t)M * m->proj.K * 2 < 0x7fffff00ull)
-        RCCHK(run_deep(cur, nullptr, m->proj.w, m->proj.bias, m->proj.K, nullptr, nullptr, CLS_CONV));
+        RCCHK(run_deep(c, c.feat, m->proj.w, m->proj.bias, m->proj.K, nullptr, nullptr, CLS_CONV));
     else
-        RCCHK(run_gemm_splitk_ln(m, cur, m->proj.w, m->proj.bias, M, D, m->proj.K, (m->proj.K / 64) % enc_splits == 0 ? enc_splits : 4, nullptr, nullptr, m->d_x32, m->d_x16, CLS_CONV, ps));
-    bool qkv_done = false, kv_done = false;
-    const int Q = a.queries, Md = B * Q, NKV = a.dec_layers * 2 * D;
+        RCCHK(run_gemm_splitk_ln(c, c.feat, m->proj.w, m->proj.bias, M, D, m->proj.K, (m->proj.K / 64) % enc_splits == 0 ? enc_splits : 4, nullptr, nullptr, m->d_x32, m->d_x16, CLS_CONV, ps));
+    bool qkv_done = false;   // written by the previous layer's FFN launch (its tail projection)
     for (int i = 0; i < a.enc_layers; ++i) {
         const EncLayer& L = m->enc[i];
-        if (qkv_done) {   // written by the previous layer's FFN launch (its tail projection)
-        } else if (shadow)
-            RCCHK(run_gemm(m, m->d_xp16, L.wqkv, L.bqkv, 0, M, 3 * D, D, m->d_qkv16, false, false, nullptr, nullptr, 0, 0, m->d_x16, 3 * D, 2 * D));
-        else
-            RCCHK(run_gemm(m, m->d_x16, L.wqkv, plan->rb_enc[i], hw, M, 3 * D, D, m->d_qkv16, false, false, nullptr, enc_bias_ptrs[i], 3 * D, 2 * D));   // (pos enters q and k only)
-        RCCHK(run_attn(m, m->d_qkv16, 3 * D, m->d_qkv16 + D, 3 * D, m->d_qkv16 + 2 * D, 3 * D, m->d_attn16, D, B, hw, hw, d_keyv, cw));
+        if (!qkv_done) RCCHK(run_pos_proj(c, L.wqkv, L.bqkv, c.plan->rb_enc[i], c.enc_bias_ptrs[i], 3 * D, 3 * D, 2 * D, m->d_qkv16));   // (pos enters q and k only)
+        RCCHK(run_attn(c, m->d_qkv16, 3 * D, m->d_qkv16 + D, 3 * D, m->d_qkv16 + 2 * D, 3 * D, m->d_attn16, c.hw, c.hw, c.d_keyv, c.fw));
         const bool ffn_fused = m->sw.fused_enc_ffn && m->sw.fuse_gemm_ln && L.ffn_pack && D == 256 && !small_enc;
         const bool front = ffn_fused && L.front && m->sw.enc_front;   // the output projection + LayerNorm run inside the FFN launch
-        if (front) {
-        } else if (m->sw.fuse_gemm_ln && D == 256) {
-            RCCHK(run_gemm_ln(m, m->d_attn16, L.o.w, L.o.b, M, D, m->d_x32, L.ln1, m->d_x32, m->d_x16));
-        } else {
-            RCCHK(run_gemm(m, m->d_attn16, L.o.w, L.o.b, 0, M, D, D, m->d_y32, true, false, m->d_x32));
-            RCCHK(timed_begin(m, CLS_OTHER, 0.0));
-            HIPCHK(opd_launch_layernorm(m->d_y32, L.ln1.g, L.ln1.b, m->d_x32, m->d_x16, M, m->stream, m->dtype));
-            RCCHK(timed_end(m));
+        if (!front && m->sw.fuse_gemm_ln && D == 256) {
+            RCCHK(run_gemm_ln(c, m->d_attn16, L.o.w, L.o.b, M, D, m->d_x32, L.ln1, m->d_x32, m->d_x16));
+        } else if (!front) {
+            ConvGemmParams p = gemm_params(m, m->d_attn16, L.o.w, L.o.b, m->d_y32, M, D, D);
+            p.out_f32 = 1; p.res32 = m->d_x32;
+            RCCHK(run_gemm(c, p));
+            RCCHK(c.launch(CLS_OTHER, 0.0, [&] { return opd_launch_layernorm(m->d_y32, L.ln1.g, L.ln1.b, m->d_x32, m->d_x16, M, c.stream, m->dtype); }));
         }
+        qkv_done = false;
         if (ffn_fused) {
             // the whole FFN block as ONE row-owner launch: the [M][F] hidden tensor never leaves LDS (kernels_rowln.hip::enc_ffn_kernel)
             EncFfnParams fp{}; fp.dtype = m->dtype; fp.wprefetch = (m->sw.wprefetch >> 1) & 1;
@@ -1053,164 +697,173 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
             if (front) { fp.attn = m->d_attn16; fp.bo = L.o.b; fp.gamma1 = L.ln1.g; fp.beta1 = L.ln1.b; }
             if (ps) { fp.pos = ps->pos; fp.pos_ptrs = ps->pos_ptrs; fp.pos_period = ps->period; fp.yp16 = ps->yp16; }
             const bool last = i + 1 == a.enc_layers;
-            qkv_done = false;
             // the tail projection: what consumes this block's output (only on the position-shadow path: x + pos with plain bias vectors)
-            if (ps && m->sw.enc_tail && L.tail && L.tail_ld == (last ? NKV : 3 * D) && (last ? (size_t)M * NKV * 2 < (1ull << 32) : true)) {
+            if (ps && m->sw.enc_tail && L.tail && L.tail_ld == (last ? c.NKV : 3 * D) && (last ? (size_t)M * c.NKV * 2 < (1ull << 32) : true)) {
                 fp.tail = L.tail; fp.tail_pos = L.tail_pos; fp.tail_ld = L.tail_ld;
                 fp.tail_out = last ? m->d_memkv16 : m->d_qkv16;
                 for (int t = 0; t < L.tail; ++t) fp.tail_col[t] = L.tail_col[t];
-                (last ? kv_done : qkv_done) = true;
+                (last ? *kv_done : qkv_done) = true;
             }
-            RCCHK(timed_begin(m, CLS_GEMM, 4.0 * M * (double)D * F + 2.0 * M * (double)D * 256 * (fp.tail + (front ? 1 : 0))));
-            HIPCHK(opd_launch_enc_ffn(fp, m->stream));
-            RCCHK(timed_end(m));
-            RCCHK(tap(m, "enc_ffn", m->d_x32, (size_t)M * D * 4));
+            RCCHK(c.launch(CLS_GEMM, 4.0 * M * (double)D * F + 2.0 * M * (double)D * 256 * (fp.tail + (front ? 1 : 0)), [&] { return opd_launch_enc_ffn(fp, c.stream); },
+                           {{"enc_ffn", m->d_x32, (size_t)M * D * 4}}));
         } else {
-            qkv_done = false;
-            RCCHK(run_gemm(m, m->d_x16, L.fc1.w, L.fc1.b, 0, M, F, D, m->d_ffn16, false, true, nullptr));
+            RCCHK(run_linear(c, m->d_x16, L.fc1.w, L.fc1.b, 0, M, F, D, m->d_ffn16, true));
             // fc2 + residual + LayerNorm (+ the position shadow) as ONE row-owner launch of the three-stage ring kernel: 36.9 us in the
             // forward against 19.4 + 12.2 us for split-K slabs + reduce, but 514 MB less HBM traffic per forward and half the CUs left to
             // other batches (+1.3 % with three streams, -5 us per layer for a lone stream; profiles/NOTES.md "Deep-K row owners")
-            if (deep_ok && F % 64 == 0 && (size_t)M * F * 2 < 0x7fffff00ull) {
-                RCCHK(run_deep(m->d_ffn16, nullptr, L.fc2.w, L.fc2.b, F, m->d_x32, &L.ln2, CLS_GEMM));
-            } else {
-                RCCHK(run_gemm_splitk_ln(m, m->d_ffn16, L.fc2.w, L.fc2.b, M, D, F, (F / 64) % enc_splits == 0 ? enc_splits : 4, m->d_x32, &L.ln2, m->d_x32, m->d_x16, CLS_GEMM, ps));
-            }
+            if (deep_ok && F % 64 == 0 && (size_t)M * F * 2 < 0x7fffff00ull)
+                RCCHK(run_deep(c, m->d_ffn16, L.fc2.w, L.fc2.b, F, m->d_x32, &L.ln2, CLS_GEMM));
+            else
+                RCCHK(run_gemm_splitk_ln(c, m->d_ffn16, L.fc2.w, L.fc2.b, M, D, F, (F / 64) % enc_splits == 0 ? enc_splits : 4, m->d_x32, &L.ln2, m->d_x32, m->d_x16, CLS_GEMM, ps));
         }
     }
-    MARK(6);
-    // ---- decoder -----------------------------------------------------------------------------------------------
-    if (kv_done) {   // written by the last encoder layer's FFN launch
-    } else if (shadow)
-        RCCHK(run_gemm(m, m->d_xp16, m->wkv_all, m->bkv_all, 0, M, NKV, D, m->d_memkv16, false, false, nullptr, nullptr, 0, 0, m->d_x16, 2 * D, D));
-    else
-        RCCHK(run_gemm(m, m->d_x16, m->wkv_all, plan->rb_kv, hw, M, NKV, D, m->d_memkv16, false, false, nullptr, kv_bias_ptrs, 2 * D, D));   // (per layer [k | v]: pos enters k only)
-    const bool dec0 = m->sw.fuse_dec0 && m->dec0_h && D == 256;
-    // The fused decoder (kernels_dec.hip): five launches per layer on split fp16 operands; layer 0 starts at its cross-attention (its
-    // self-attention block and its queries are constants of the weights).  Taken when the architecture fits the kernels' fixed shapes.
-    const bool fused_dec = m->sw.fused_dec && dec0 && m->qc0 && a.heads == 8 && Q <= 128 && (Q & 3) == 0 && F % OPD_DEC_FFN_CHUNK == 0 && F / OPD_DEC_FFN_CHUNK <= 16 && m->sw.dec_splits <= 6 && D == 256 && m->dec[0].wqkv_f &&
-                           (size_t)M * NKV * 2 < (1ull << 32);
-    const float* dec_final_h = m->d_h32;   // the state the heads read (fused: before the last FFN, whose partial sums travel with it)
-    if (fused_dec) {
-        const int S = m->sw.dec_splits, nchunk = F / OPD_DEC_FFN_CHUNK;
-        float* hbuf[2] = {m->d_h32, m->d_yd32};
-        int cur = 0;   // hbuf[cur] holds the layer's state from its self-attention block on
-        for (int i = 0; i < a.dec_layers && i < m->sw.dbg_dec_layers; ++i) {
-            const DecLayer& L = m->dec[i];
-            f16_t* qd = m->d_qd16 + (size_t)i * m->cfg.max_batch * Q * D;   // (per-layer regions of max_batch frames: layer 0's constants stay put)
-            if (i > 0) {
-                const DecLayer& P = m->dec[i - 1];
-                DecQkvParams qp{};
-                qp.h_in = hbuf[cur]; qp.partials = m->d_ffn_part; qp.nsplit = nchunk; qp.b2 = P.fc2.b; qp.ln_g = P.ln3.g; qp.ln_b = P.ln3.b;
-                qp.h_out = hbuf[cur ^ 1]; qp.w = L.wqkv_f; qp.bias = L.rb_self;
-                qp.q16 = m->d_dq16; qp.k16 = m->d_dk16; qp.vT = m->d_dvT; qp.M = Md; qp.Q = Q;
-                RCCHK(timed_begin(m, CLS_GEMM, 2.0 * Md * 768.0 * D));
-                HIPCHK(opd_launch_dec_qkv(qp, m->stream));
-                RCCHK(timed_end(m));
-                cur ^= 1;
-                RCCHK(tap(m, "dec_qkv_h", hbuf[cur], (size_t)Md * D * 4));
-                DecSelfParams sp{};
-                sp.q16 = m->d_dq16; sp.k16 = m->d_dk16; sp.vT = m->d_dvT; sp.h = hbuf[cur]; sp.wo = L.so_f; sp.bo = L.so.b;
-                sp.ln_g = L.ln1.g; sp.ln_b = L.ln1.b; sp.wq = L.wqc_f; sp.rbq = L.rb_q; sp.qc16 = qd; sp.qc_bf16 = m->dtype == OPD_DT_BF16; sp.B = B; sp.Q = Q;
-                sp.scale = 1.0f / sqrtf((float)(D / a.heads));
-                RCCHK(timed_begin(m, CLS_GEMM, 4.0 * Md * (double)D * D + 4.0 * B * (double)a.heads * Q * Q * 32));
-                HIPCHK(opd_launch_dec_self(sp, m->stream));
-                RCCHK(timed_end(m));
-                RCCHK(tap(m, "dec_self_h", hbuf[cur], (size_t)Md * D * 4));
-            }
-            {   // cross-attention over S key ranges: unnormalised partials
-                AttnParams ap{}; ap.dtype = m->dtype;
-                ap.q = qd; ap.k = m->d_memkv16 + (size_t)i * 2 * D; ap.v = m->d_memkv16 + (size_t)i * 2 * D + D; ap.o = nullptr;
-                ap.B = B; ap.heads = a.heads; ap.Lq = Q; ap.Lk = hw; ap.ldq = D; ap.ldk = NKV; ap.ldv = NKV; ap.ldo = D;
-                ap.scale = 1.0f / sqrtf((float)(D / a.heads)); ap.key_valid = d_keyv; ap.key_row = cw;
-                ap.splits = S; ap.part_o = m->d_part_o; ap.part_ml = m->d_part_ml;
-                RCCHK(timed_begin(m, CLS_ATTN, 4.0 * B * (double)a.heads * Q * hw * 32));
-                HIPCHK(opd_launch_attention(ap, m->stream));
-                RCCHK(timed_end(m));
-                RCCHK(tap(m, "dec_cross_part", m->d_part_o, (size_t)S * Md * D * 4));
-            }
-            {
-                DecCrossOutParams cp{};
-                cp.part_o = m->d_part_o; cp.part_ml = m->d_part_ml; cp.splits = S;
-                cp.res = i == 0 ? m->dec0_h : hbuf[cur]; cp.res_period = i == 0 ? 1 : 0; cp.h = hbuf[cur];
-                cp.wo = L.co_f; cp.bo = L.co.b; cp.ln_g = L.ln2.g; cp.ln_b = L.ln2.b; cp.M = Md;
-                RCCHK(timed_begin(m, CLS_GEMM, 2.0 * Md * (double)D * D));
-                HIPCHK(opd_launch_dec_cross_out(cp, m->stream));
-                RCCHK(timed_end(m));
-                RCCHK(tap(m, "dec_cross_h", hbuf[cur], (size_t)Md * D * 4));
-            }
-            {
-                DecFfnParams fp{};
-                fp.h = hbuf[cur]; fp.w1 = L.fc1_f; fp.b1 = L.fc1.b; fp.w2 = L.fc2_f;
-                fp.partials = m->d_ffn_part; fp.M = Md; fp.F = F;
-                RCCHK(timed_begin(m, CLS_GEMM, 4.0 * Md * (double)D * F));
-                HIPCHK(opd_launch_dec_ffn(fp, m->stream));
-                RCCHK(timed_end(m));
-                RCCHK(tap(m, "dec_ffn_part", m->d_ffn_part, (size_t)nchunk * Md * D * 4));
-            }
-        }
-        dec_final_h = hbuf[cur];
-    } else {
-    if (dec0) {
-        RCCHK(timed_begin(m, CLS_OTHER, 0.0));
-        HIPCHK(opd_launch_broadcast_rows(m->dec0_h, m->d_h32, m->d_h16, Md, m->stream, m->dtype));
-        RCCHK(timed_end(m));
-        RCCHK(tap(m, "dec0_broadcast", m->d_h32, (size_t)Md * D * 4));
-    } else {
-        HIPCHK(hipMemsetAsync(m->d_h32, 0, (size_t)Md * D * 4, m->stream));
-        HIPCHK(hipMemsetAsync(m->d_h16, 0, (size_t)Md * D * 2, m->stream));
-    }
+    return OPD_OK;
+}
+
+// memory keys / values of all decoder layers in one GEMM (per layer [k | v]: pos enters k only)
+static int fwd_memory_kv(const Fwd& c) {
+    return run_pos_proj(c, c.m->wkv_all, c.m->bkv_all, c.plan->rb_kv, c.kv_bias_ptrs, c.NKV, 2 * c.D, c.D, c.m->d_memkv16);
+}
+
+// The fused decoder (kernels_dec.hip): five launches per layer on split fp16 operands; layer 0 starts at its cross-attention (its
+// self-attention block and its queries are constants of the weights).  *final_h: the state the heads read (before the last FFN, whose
+// partial sums travel with it)
+static int fwd_decoder_fused(const Fwd& c, const float** final_h) {
+    opd_detr* m = c.m;
+    const Arch& a = m->arch;
+    const int B = c.B, D = c.D, F = c.F, Q = c.Q, Md = c.Md;
+    const int S = m->sw.dec_splits, nchunk = F / OPD_DEC_FFN_CHUNK;
+    float* hbuf[2] = {m->d_h32, m->d_yd32};
+    int cur = 0;   // hbuf[cur] holds the layer's state from its self-attention block on
     for (int i = 0; i < a.dec_layers && i < m->sw.dbg_dec_layers; ++i) {
         const DecLayer& L = m->dec[i];
-        const bool small = m->sw.small_m_gemm && D == 256 && F % 256 == 0 && F / 256 <= 8;
+        f16_t* qd = m->d_qd16 + (size_t)i * m->cfg.max_batch * Q * D;   // (per-layer regions of max_batch frames: layer 0's constants stay put)
+        if (i > 0) {
+            const DecLayer& P = m->dec[i - 1];
+            DecQkvParams qp{};
+            qp.h_in = hbuf[cur]; qp.partials = m->d_ffn_part; qp.nsplit = nchunk; qp.b2 = P.fc2.b; qp.ln_g = P.ln3.g; qp.ln_b = P.ln3.b;
+            qp.h_out = hbuf[cur ^ 1]; qp.w = L.wqkv_f; qp.bias = L.rb_self;
+            qp.q16 = m->d_dq16; qp.k16 = m->d_dk16; qp.vT = m->d_dvT; qp.M = Md; qp.Q = Q;
+            cur ^= 1;
+            RCCHK(c.launch(CLS_GEMM, 2.0 * Md * 768.0 * D, [&] { return opd_launch_dec_qkv(qp, c.stream); }, {{"dec_qkv_h", hbuf[cur], (size_t)Md * D * 4}}));
+            DecSelfParams sp{};
+            sp.q16 = m->d_dq16; sp.k16 = m->d_dk16; sp.vT = m->d_dvT; sp.h = hbuf[cur]; sp.wo = L.so_f; sp.bo = L.so.b;
+            sp.ln_g = L.ln1.g; sp.ln_b = L.ln1.b; sp.wq = L.wqc_f; sp.rbq = L.rb_q; sp.qc16 = qd; sp.qc_bf16 = m->dtype == OPD_DT_BF16; sp.B = B; sp.Q = Q;
+            sp.scale = 1.0f / sqrtf((float)(D / a.heads));
+            RCCHK(c.launch(CLS_GEMM, 4.0 * Md * (double)D * D + 4.0 * B * (double)a.heads * Q * Q * 32, [&] { return opd_launch_dec_self(sp, c.stream); },
+                           {{"dec_self_h", hbuf[cur], (size_t)Md * D * 4}}));
+        }
+        // cross-attention over S key ranges: unnormalised partials
+        AttnParams ap = attn_params(c, qd, D, m->d_memkv16 + (size_t)i * 2 * D, c.NKV, m->d_memkv16 + (size_t)i * 2 * D + D, c.NKV, nullptr, D, Q, c.hw, c.d_keyv, c.fw);
+        ap.splits = S; ap.part_o = m->d_part_o; ap.part_ml = m->d_part_ml;
+        RCCHK(c.launch(CLS_ATTN, attn_flops(ap), [&] { return opd_launch_attention(ap, c.stream); }, {{"dec_cross_part", m->d_part_o, (size_t)S * Md * D * 4}}));
+        DecCrossOutParams cp{};
+        cp.part_o = m->d_part_o; cp.part_ml = m->d_part_ml; cp.splits = S;
+        cp.res = i == 0 ? m->dec0_h : hbuf[cur]; cp.res_period = i == 0 ? 1 : 0; cp.h = hbuf[cur];
+        cp.wo = L.co_f; cp.bo = L.co.b; cp.ln_g = L.ln2.g; cp.ln_b = L.ln2.b; cp.M = Md;
+        RCCHK(c.launch(CLS_GEMM, 2.0 * Md * (double)D * D, [&] { return opd_launch_dec_cross_out(cp, c.stream); }, {{"dec_cross_h", hbuf[cur], (size_t)Md * D * 4}}));
+        DecFfnParams fp{};
+        fp.h = hbuf[cur]; fp.w1 = L.fc1_f; fp.b1 = L.fc1.b; fp.w2 = L.fc2_f;
+        fp.partials = m->d_ffn_part; fp.M = Md; fp.F = F;
+        RCCHK(c.launch(CLS_GEMM, 4.0 * Md * (double)D * F, [&] { return opd_launch_dec_ffn(fp, c.stream); }, {{"dec_ffn_part", m->d_ffn_part, (size_t)nchunk * Md * D * 4}}));
+    }
+    *final_h = hbuf[cur];
+    return OPD_OK;
+}
+
+// The unfused decoder: the round-3 chain of nine launches per layer on single fp16 operands (the cross-check of the fused one); state in d_h32 / d_h16
+static int fwd_decoder_chain(const Fwd& c, bool dec0) {
+    opd_detr* m = c.m;
+    const Arch& a = m->arch;
+    const int D = c.D, F = c.F, Q = c.Q, Md = c.Md;
+    if (dec0) {
+        RCCHK(c.launch(CLS_OTHER, 0.0, [&] { return opd_launch_broadcast_rows(m->dec0_h, m->d_h32, m->d_h16, Md, c.stream, m->dtype); },
+                       {{"dec0_broadcast", m->d_h32, (size_t)Md * D * 4}}));
+    } else {
+        HIPCHK(hipMemsetAsync(m->d_h32, 0, (size_t)Md * D * 4, c.stream));
+        HIPCHK(hipMemsetAsync(m->d_h16, 0, (size_t)Md * D * 2, c.stream));
+    }
+    const bool small = m->sw.small_m_gemm && D == 256 && F % 256 == 0 && F / 256 <= 8;
+    auto linear = [&](const f16_t* x, const f16_t* w, const float* bias, int bias_period, int N, int K, f16_t* out, bool relu) {
+        return small ? run_small_gemm(c, x, w, bias, bias_period, Md, N, K, out, relu) : run_linear(c, x, w, bias, bias_period, Md, N, K, out, relu);
+    };
+    auto out_proj_ln = [&](const Lin& o, const LNp& ln) {   // attention output projection + residual + LayerNorm on the state
+        return m->sw.fuse_gemm_ln && D == 256 ? run_gemm_ln(c, m->d_attnd16, o.w, o.b, Md, D, m->d_h32, ln, m->d_h32, m->d_h16)
+                                              : run_gemm_splitk_ln(c, m->d_attnd16, o.w, o.b, Md, D, D, 4, m->d_h32, &ln, m->d_h32, m->d_h16, CLS_GEMM);
+    };
+    for (int i = 0; i < a.dec_layers && i < m->sw.dbg_dec_layers; ++i) {
+        const DecLayer& L = m->dec[i];
         if (!(dec0 && i == 0)) {   // (layer 0's self-attention block is the broadcast above)
-        if (small) RCCHK(run_small_gemm(m, m->d_h16, L.wqkv, L.rb_self, Q, Md, 3 * D, D, m->d_qkvd16, false));
-        else RCCHK(run_gemm(m, m->d_h16, L.wqkv, L.rb_self, Q, Md, 3 * D, D, m->d_qkvd16, false, false, nullptr));
-        RCCHK(run_attn(m, m->d_qkvd16, 3 * D, m->d_qkvd16 + D, 3 * D, m->d_qkvd16 + 2 * D, 3 * D, m->d_attnd16, D, B, Q, Q));
-        if (m->sw.fuse_gemm_ln && D == 256)
-            RCCHK(run_gemm_ln(m, m->d_attnd16, L.so.w, L.so.b, Md, D, m->d_h32, L.ln1, m->d_h32, m->d_h16));
-        else
-            RCCHK(run_gemm_splitk_ln(m, m->d_attnd16, L.so.w, L.so.b, Md, D, D, 4, m->d_h32, &L.ln1, m->d_h32, m->d_h16, CLS_GEMM));
+            RCCHK(linear(m->d_h16, L.wqkv, L.rb_self, Q, 3 * D, D, m->d_qkvd16, false));
+            RCCHK(run_attn(c, m->d_qkvd16, 3 * D, m->d_qkvd16 + D, 3 * D, m->d_qkvd16 + 2 * D, 3 * D, m->d_attnd16, Q, Q));
+            RCCHK(out_proj_ln(L.so, L.ln1));
         }
         f16_t* qd = m->d_qd16 + (size_t)i * m->cfg.max_batch * Q * D;
-        if (small) RCCHK(run_small_gemm(m, m->d_h16, L.wq_c, L.rb_q, Q, Md, D, D, qd, false));
-        else RCCHK(run_gemm(m, m->d_h16, L.wq_c, L.rb_q, Q, Md, D, D, qd, false, false, nullptr));
-        RCCHK(run_attn(m, qd, D, m->d_memkv16 + (size_t)i * 2 * D, NKV, m->d_memkv16 + (size_t)i * 2 * D + D, NKV,
-                       m->d_attnd16, D, B, Q, hw, d_keyv, cw));
-        if (m->sw.fuse_gemm_ln && D == 256)
-            RCCHK(run_gemm_ln(m, m->d_attnd16, L.co.w, L.co.b, Md, D, m->d_h32, L.ln2, m->d_h32, m->d_h16));
-        else
-            RCCHK(run_gemm_splitk_ln(m, m->d_attnd16, L.co.w, L.co.b, Md, D, D, 4, m->d_h32, &L.ln2, m->d_h32, m->d_h16, CLS_GEMM));
-        if (small) {
-            RCCHK(run_small_gemm(m, m->d_h16, L.fc1.w, L.fc1.b, 0, Md, F, D, m->d_ffnd16, true));
-            RCCHK(run_small_gemm_ln(m, m->d_ffnd16, L.fc2.w, L.fc2.b, Md, F, m->d_h32, L.ln3, m->d_h32, m->d_h16));
-        } else {
-            RCCHK(run_gemm(m, m->d_h16, L.fc1.w, L.fc1.b, 0, Md, F, D, m->d_ffnd16, false, true, nullptr));
-            RCCHK(run_gemm_splitk_ln(m, m->d_ffnd16, L.fc2.w, L.fc2.b, Md, D, F, 8, m->d_h32, &L.ln3, m->d_h32, m->d_h16, CLS_GEMM));
-        }
+        RCCHK(linear(m->d_h16, L.wq_c, L.rb_q, Q, D, D, qd, false));
+        RCCHK(run_attn(c, qd, D, m->d_memkv16 + (size_t)i * 2 * D, c.NKV, m->d_memkv16 + (size_t)i * 2 * D + D, c.NKV, m->d_attnd16, Q, c.hw, c.d_keyv, c.fw));
+        RCCHK(out_proj_ln(L.co, L.ln2));
+        RCCHK(linear(m->d_h16, L.fc1.w, L.fc1.b, 0, F, D, m->d_ffnd16, true));
+        if (small) RCCHK(run_small_gemm_ln(c, m->d_ffnd16, L.fc2.w, L.fc2.b, Md, F, m->d_h32, L.ln3, m->d_h32, m->d_h16));
+        else RCCHK(run_gemm_splitk_ln(c, m->d_ffnd16, L.fc2.w, L.fc2.b, Md, D, F, 8, m->d_h32, &L.ln3, m->d_h32, m->d_h16, CLS_GEMM));
     }
-    }
+    return OPD_OK;
+}
+
+// final LayerNorm + class / box heads.  `fused_h`: the fused decoder's state (null: the chain's d_h32)
+static int fwd_heads(const Fwd& c, const float* fused_h) {
+    opd_detr* m = c.m;
+    const Arch& a = m->arch;
     HeadParams hp{};
-    if (fused_dec) {   // the last layer's FFN sum + LN3 and the final LayerNorm run inside the heads kernel
+    if (fused_h) {   // the last layer's FFN sum + LN3 and the final LayerNorm run inside the heads kernel
         const DecLayer& P = m->dec[a.dec_layers - 1];
-        hp.hs = dec_final_h; hp.partials = m->d_ffn_part; hp.nsplit = F / OPD_DEC_FFN_CHUNK; hp.ffn_b2 = P.fc2.b; hp.ln3_gamma = P.ln3.g; hp.ln3_beta = P.ln3.b;
+        hp.hs = fused_h; hp.partials = m->d_ffn_part; hp.nsplit = c.F / OPD_DEC_FFN_CHUNK; hp.ffn_b2 = P.fc2.b; hp.ln3_gamma = P.ln3.g; hp.ln3_beta = P.ln3.b;
         hp.ln_gamma = m->dec_ln.g; hp.ln_beta = m->dec_ln.b;
     } else if (m->sw.fuse_gemm_ln) {   // the final LayerNorm runs inside the heads kernel
         hp.hs = m->d_h32; hp.ln_gamma = m->dec_ln.g; hp.ln_beta = m->dec_ln.b;
     } else {
-        RCCHK(timed_begin(m, CLS_OTHER, 0.0));
-        HIPCHK(opd_launch_layernorm(m->d_h32, m->dec_ln.g, m->dec_ln.b, m->d_hs32, nullptr, Md, m->stream, m->dtype));
-        RCCHK(timed_end(m));
+        RCCHK(c.launch(CLS_OTHER, 0.0, [&] { return opd_launch_layernorm(m->d_h32, m->dec_ln.g, m->dec_ln.b, m->d_hs32, nullptr, c.Md, c.stream, m->dtype); }));
         hp.hs = m->d_hs32;
-    } hp.wc = m->wc; hp.bc = m->bc; hp.w1 = m->w1; hp.b1 = m->b1; hp.w2 = m->w2; hp.b2 = m->b2;
-    hp.w3 = m->w3; hp.b3 = m->b3; hp.logits = m->d_logits; hp.boxes = m->d_boxes; hp.rows = Md; hp.ncls = a.ncls;
+    }
+    hp.wc = m->wc; hp.bc = m->bc; hp.w1 = m->w1; hp.b1 = m->b1; hp.w2 = m->w2; hp.b2 = m->b2;
+    hp.w3 = m->w3; hp.b3 = m->b3; hp.logits = m->d_logits; hp.boxes = m->d_boxes; hp.rows = c.Md; hp.ncls = a.ncls;
     if (m->sw.heads2 && m->wc_f && m->w1_f && m->w2_f) { hp.wc_f = m->wc_f; hp.w1_f = m->w1_f; hp.w2_f = m->w2_f; }
-    RCCHK(timed_begin(m, CLS_OTHER, 2.0 * Md * 256.0 * (a.ncls + 256 + 256 + 4)));
-    HIPCHK(opd_launch_heads(hp, m->stream));
-    RCCHK(timed_end(m));
-    RCCHK(tap(m, "heads_logits", m->d_logits, (size_t)Md * a.ncls * 4));
+    return c.launch(CLS_OTHER, 2.0 * c.Md * 256.0 * (a.ncls + 256 + 256 + 4), [&] { return opd_launch_heads(hp, c.stream); },
+                    {{"heads_logits", m->d_logits, (size_t)c.Md * a.ncls * 4}});
+}
+
+// Enqueues the whole forward on m->stream.  `d_pixels` must already be on the device.  `valid_hw` (host, nullable): [B][2] = (h, w) of each
+// frame inside the H x W canvas.
+static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, int B, int H, int W, const int32_t* valid_hw = nullptr) {
+    const Arch& a = m->arch;
+    Fwd c{};
+    c.m = m; c.stream = m->stream; c.B = B; c.H = H; c.W = W;
+    compute_dims(B, H, W, &c.d);
+    c.D = a.d_model; c.F = a.ffn; c.Q = a.queries; c.Md = B * c.Q; c.NKV = a.dec_layers * 2 * c.D;
+    const bool ragged = is_ragged(valid_hw, B, H, W);
+    if (ragged) RCCHK(fwd_prepare_ragged(c, valid_hw));
+    else RCCHK(get_plan(m, c.d.stage_h[3], c.d.stage_w[3], c.d.stage_h[3], c.d.stage_w[3], &c.plan));
+    m->timed.clear();   // the event pairs and the taps of the last forward
+    m->pool_next = 0;
+    m->tap_next = 0;
+    if (pixel_format == OPD_PIXELS_U8_BGR_HWC) RCCHK(tap(m, c.stream, {"pixels_u8", d_pixels, (size_t)B * H * W * 3}));
+    MARK(0);
+    RCCHK(fwd_stem(c, d_pixels, pixel_format));
+    MARK(1);
+    RCCHK(fwd_trunk(c));   // (marks 2 .. 5: one behind each stage)
+    bool kv_done = false;
+    RCCHK(fwd_encoder(c, &kv_done));
+    MARK(6);
+    if (!kv_done) RCCHK(fwd_memory_kv(c));
+    const bool dec0 = m->sw.fuse_dec0 && m->dec0_h && c.D == 256;
+    // the fused decoder is taken when the architecture fits its kernels' fixed shapes
+    const bool fused_dec = m->sw.fused_dec && dec0 && m->qc0 && a.heads == 8 && c.Q <= 128 && (c.Q & 3) == 0 && c.F % OPD_DEC_FFN_CHUNK == 0 && c.F / OPD_DEC_FFN_CHUNK <= 16 &&
+                           m->sw.dec_splits <= 6 && c.D == 256 && m->dec[0].wqkv_f && (size_t)c.M * c.NKV * 2 < (1ull << 32);
+    const float* fused_h = nullptr;
+    if (fused_dec) RCCHK(fwd_decoder_fused(c, &fused_h));
+    else RCCHK(fwd_decoder_chain(c, dec0));
+    RCCHK(fwd_heads(c, fused_h));
     MARK(7);
-    m->last_B = B; m->last_H = H; m->last_W = W; m->last_fh = ch; m->last_fw = cw;
+    m->last_B = B; m->last_H = H; m->last_W = W; m->last_fh = c.fh; m->last_fw = c.fw;
     m->last_ragged = ragged;
     return OPD_OK;
 }

@@ -1,5 +1,5 @@
 // opd_model.h — PRIVATE header of libopd_hip: the device model (weights, workspace, per-resolution plans, graph cache) behind the opaque
-// `opd_detr` handle of include/opd_detr.h.  Included by opd_model.cpp (weights, workspace, plans, the forward), opd_api.cpp (the C-ABI and the
+// `opd_detr` handle of include/opd_detr.h.  Included by opd_weights.cpp (build_weights), opd_model.cpp (workspace, plans, the forward), opd_api.cpp (the C-ABI and the
 // detect pipeline behind it), opd_comm.cpp, and opd_test_model_api.cpp / opd_test_bench_api.cpp (the test hooks of libopd_hip_test.so that reach into a handle to flip
 // its fusion switches, or plan a trunk); never installed, never seen by a caller.
 #pragma once
@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -83,7 +84,7 @@ struct Plan {  // everything that depends on the feature-map size (h, w)
 
 struct Dims {
     int B, H, W, H1, W1, H2, W2;
-    int sh[4], sw[4];
+    int stage_h[4], stage_w[4];   // output maps of stages 1-4
 };
 
 inline int down2(int n) { return (n - 1) / 2 + 1; }
@@ -119,7 +120,7 @@ struct Switches {
     int small_splitk = 1;    // handles whose deep convolutions would fill a fraction of the CUs (small max_batch x frame): split their reduction over
                              // workgroups, fp32 slabs + reduce_act16_kernel (run_conv; env OPD_SMALL_SPLITK)
     int small_enc = 1;       // handles bounded to <= 1400 tokens: the encoder side's deep linears as split-K GEMMs + reduce / LayerNorm instead of the
-                             // row-owner launches (enqueue_forward; env OPD_SMALL_ENC)
+                             // row-owner launches (fwd_encoder; env OPD_SMALL_ENC)
     int fuse_stem_pool = 1;  // stem conv + max-pool in one kernel (0: two kernels, for cross-checking)
     int fuse_prep = 1;       // uint8 frames: pre-processing inside that kernel (0: preprocess_u8_kernel writes the padded NHWC4 image first)
     int pos_shadow = 1;      // q / k projections read a second fp16 shadow "x + position embedding" (written by the producer of x) instead
@@ -146,7 +147,7 @@ struct TrunkPlan {
     std::vector<TrunkStep> steps;   // one per block, in stage order
     int split = 0;                  // stage 3, blocks 1..: frames [0, split) on `stream`, [split, B) as a second chain on `stream2` (split == B: one chain)
 };
-// Pure over shapes and configuration (reads block shapes, never device pointers): called by enqueue_forward, i.e. per eager forward and per
+// Pure over shapes and configuration (reads block shapes, never device pointers): called by fwd_trunk, i.e. per eager forward and per
 // graph capture.  B x H2 x W2: the call's batch and stage-1 input map; `taps`, `profiling`, `has_stream2`: the handle's diagnostic modes and branch stream.
 TrunkPlan plan_trunk(const Arch& a, const std::vector<Block>& blocks, const opd_config& cfg, const Switches& sw, int B, int H2, int W2, int num_cus,
                      bool taps, int profiling, bool has_stream2);
@@ -201,7 +202,7 @@ struct opd_detr : DetrWeights {
     int dtype = 0;                          // OPD_DT_F16 / OPD_DT_BF16 (cfg.flags & OPD_FLAG_BF16): the 16-bit operand type of every activation buffer and GEMM weight
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;   // second branch of the forward (stage-3 frame split, see enqueue_forward); joins the capture of `stream`
+    hipStream_t stream2 = nullptr;   // second branch of the forward (stage-3 frame split, see trunk_stage3_split); joins the capture of `stream`
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<void*> allocs;              // this handle's own buffers: workspace, per-resolution plans
     std::vector<RedZoned> zoned;            // poison mode only: the same buffers with their red zones
@@ -317,15 +318,29 @@ inline int dalloc(opd_detr* m, T** p, size_t count, bool weight) {
 }
 
 void comm_detach_all(opd_detr* m);   // opd_comm.cpp: called by opd_detr_destroy
-// opd_model.cpp, for opd_api.cpp: what a handle is made of, the forward through the graph cache, the per-launch timing of profiling mode 1
-int fill_qc0(opd_detr* m);
+// opd_weights.cpp: the checkpoint folded, rounded, packed and uploaded into the handle's DetrWeights; one fp32 vector as a weight allocation
 int build_weights(opd_detr* m, const StateDict& sd);
+int upload_f32(opd_detr* m, float** dst, const std::vector<float>& v);
+// a row-bias fold *out[rows][N] = d_x[rows][K] . w[N][K]^T + b, all fp32 (the plan GEMM): the query-position folds here, a plan's position folds
+int upload_fold(opd_detr* m, const float* d_x, const std::vector<float>& w, const std::vector<float>& b, int rows, int N, int K, float** out);
+// opd_model.cpp, for opd_api.cpp: the rest of what a handle is made of, the forward through the graph cache, the launch helper
+int fill_qc0(opd_detr* m);
 int build_workspace(opd_detr* m);
 int run_forward(opd_detr* m, const void* d_pixels, int pixel_format, int B, int H, int W, const int32_t* valid_hw = nullptr);
 void drop_graphs(opd_detr* m);   // destroy the handle's graph executables and clear the cache: the next forwards run eagerly, then capture anew
 enum { CLS_CONV = 0, CLS_GEMM = 1, CLS_ATTN = 2, CLS_OTHER = 3 };
-int timed_begin(opd_detr* m, int cls, double flops);
-int timed_end(opd_detr* m);
+// How a launch of the forward (and of the post-process behind it) is issued, written once: profiling mode 1's event pair (timing class
+// `cls`, algorithmic `flops`) opens, `issue()` launches on stream `s`, the pair closes, and with diagnostic taps on a checksum launch follows
+// for each of `taps` that has a name and a buffer.  A split-K pair is two calls, the tap on the second.
+struct Tap { const char* name; const void* p; size_t bytes; };
+int launch_begin(opd_detr* m, hipStream_t s, int cls, double flops);   // (the two halves of launch(): nothing else calls them)
+int launch_end(opd_detr* m, hipStream_t s, std::initializer_list<Tap> taps);
+template <typename F>
+int launch(opd_detr* m, hipStream_t s, int cls, double flops, F&& issue, std::initializer_list<Tap> taps = {}) {
+    RCCHK(launch_begin(m, s, cls, flops));
+    HIPCHK(issue());
+    return launch_end(m, s, taps);
+}
 void timed_collect(opd_detr* m);
 #define MARK(i)                                                   \
     do {                                                          \

@@ -291,7 +291,7 @@ def make_device_exact(weights: "OrderedDict[str, np.ndarray]") -> None:
     """Make every fp16 GEMM operand of the device path exactly representable (module docstring).
 
     * 2-D weights of the transformer linears and ``input_projection`` (consumed as fp16): rounded to the nearest fp16 value.
-    * convolution kernels: the device folds FrozenBN in fp32, ``w * (gamma * 1/sqrt(var + 1e-5))`` (``csrc/opd_model.cpp::make_conv``),
+    * convolution kernels: the device folds FrozenBN in fp32, ``w * (gamma * 1/sqrt(var + 1e-5))`` (``csrc/opd_weights.cpp::make_conv``),
       and stores THAT in fp16.  The kernel is replaced by ``fp16(w * scale) / scale`` (fp64 division, stored fp32): the fold then
       lands within 2e-7 relative of an fp16 value and rounds to it, while the fp32 reference, which keeps kernel and scale apart,
       computes with the same number to fp32 accuracy.

@@ -260,7 +260,7 @@ def test_parity_on_weights_that_are_not_device_exact(weight_cache, parity_log, s
 
 def test_stage3_frame_split_is_bit_identical(mild_path):
     """Single-stream handles run the frames of stage 3 beyond whole rounds of its fused tail as a second chain on a forked stream,
-    captured into the graph as a fork / join (csrc/opd_model.cpp::enqueue_forward).  Per-row arithmetic does not depend on the
+    captured into the graph as a fork / join (csrc/opd_model.cpp::trunk_stage3_split).  Per-row arithmetic does not depend on the
     tiling, so the split must be invisible: batch 8 at 800x1333, eager launch, capture and replay, each against a handle created with
     OPD_TAIL3_SPLIT=0 (one launch per tail) -- equal bits."""
     frames = structured_frames(8, 800, 1333, seed=808)
@@ -281,6 +281,48 @@ def test_stage3_frame_split_is_bit_identical(mild_path):
             np.testing.assert_array_equal(x, y)
         for x, y in zip(outs["1"][call], outs["1"][0]):
             np.testing.assert_array_equal(x, y)
+
+
+def test_taps_agree_eager_capture_replay(mild_path):
+    """The diagnostic taps (opd_test_set_taps: a checksum launch behind every launch of the forward, issued by the forward's one launch
+    helper and captured into the graph with it) on a large-handle plan: an eager forward, the capturing one and a replay give the same
+    non-empty list of names and the same sums; the list reaches from the stem to the heads; and logits / boxes are bit-equal across
+    the three and to a handle state with taps off (taps only switch off y_stride2, tail_rc and the frame split: bit-neutral)."""
+    lib = _capi.load_library(test_hooks=True)
+    H, W, B = 256, 320, 2
+    cfg = _capi.OpdConfig(struct_size=C.sizeof(_capi.OpdConfig), max_batch=2, max_height=800, max_width=1333, flags=0)
+    h = C.c_void_p()
+    _capi.check(lib.opd_detr_create(C.byref(cfg), mild_path.encode(), 0, C.byref(h)), "opd_detr_create")
+    try:
+        frames = np.stack(structured_frames(B, H, W, seed=1234))
+
+        def fwd():
+            logits, boxes = np.zeros((B, 100, 92), np.float32), np.zeros((B, 100, 4), np.float32)
+            _capi.check(lib.opd_detr_forward(h, frames.ctypes.data_as(C.c_void_p), _capi.OPD_PIXELS_U8_BGR_HWC, _capi.OPD_MEM_HOST, B, H, W,
+                                             logits.ctypes.data_as(C.c_void_p), boxes.ctypes.data_as(C.c_void_p), None), "opd_detr_forward")
+            return logits, boxes
+
+        def taps():
+            sums, names = (C.c_ulonglong * 512)(), C.create_string_buffer(1 << 16)
+            n = lib.opd_test_read_taps(h, sums, 512, names, len(names))
+            return [(nm, int(sums[i])) for i, nm in enumerate(names.value.decode().split("\n")[:n])]
+
+        plain = [fwd() for _ in range(3)][-1]   # taps off: eager, capture, replay
+        _capi.check(lib.opd_test_set_taps(h, 1), "opd_test_set_taps")
+        runs = []
+        for _ in range(3):   # eager, capture, replay
+            out = fwd()
+            runs.append((out, taps()))
+        names = [nm for nm, _ in runs[0][1]]
+        assert len(names) > 0
+        for want in ("stem_pool_u8", "btail_y", "enc_ffn", "dec_cross_h", "heads_logits"):
+            assert want in names, (want, names)
+        for out, t in runs:
+            assert t == runs[0][1]   # same count, names, order and sums
+            for x, y in zip(out, plain):
+                np.testing.assert_array_equal(x, y)
+    finally:
+        lib.opd_detr_destroy(h)
 
 
 def test_native_exchange_world_size_1(mild_path):
