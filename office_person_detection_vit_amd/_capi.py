@@ -249,6 +249,8 @@ TEST_API = {
     "opd_test_bench_dec": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_float)]),
     "opd_test_heads_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 13 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "opd_test_set_elem_bf16": (C.c_int, [C.c_int]),
+    "opd_test_set_btail_res_regs": (C.c_int, [C.c_int]),
+    "opd_test_stem_reduce": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 4),
     "opd_test_trace_dec_self": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
     # Re-ID hooks (csrc/opd_reid_test_api.cpp)
     "opd_test_reid_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

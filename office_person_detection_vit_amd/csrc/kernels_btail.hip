@@ -102,11 +102,29 @@ __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_OUTSTANDING) : "memory");
 }
 __device__ __forceinline__ void compiler_fence() { asm volatile("" ::: "memory"); }
+// Four 16-byte LDS reads the compiler does not see as such: in front of a `ds_read` whose address it cannot tell apart from the destinations
+// of the LDS-DMA requests in flight it waits vmcnt(0), which here would drain the operand requests a chunk step has just issued.  The caller
+// owns the vmcnt that proves the data has landed.  The reads and their lgkmcnt(0) are ONE statement: with the wait in a statement of its own
+// the compiler is free to copy the destination registers in between, i.e. before the data has arrived.
+__device__ __forceinline__ void lds_read16x4_raw(const unsigned char* const (&ptr)[4], uint4 (&r)[4]) {
+    uint4v v0, v1, v2, v3;
+    auto lds = [](const unsigned char* q) { return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)q; };
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
+                 : "v"(lds(ptr[0])), "v"(lds(ptr[1])), "v"(lds(ptr[2])), "v"(lds(ptr[3]))
+                 : "memory");
+    r[0] = make_uint4(v0[0], v0[1], v0[2], v0[3]);
+    r[1] = make_uint4(v1[0], v1[1], v1[2], v1[3]);
+    r[2] = make_uint4(v2[0], v2[1], v2[2], v2[3]);
+    r[3] = make_uint4(v3[0], v3[1], v3[2], v3[3]);
+}
 
-// RDMA = true (C1 == 64): the residual travels global -> LDS through LDS-DMA instead of global -> VGPR.  Loads through
+// RDMA = true: the residual travels global -> LDS through LDS-DMA instead of global -> VGPR.  Loads through
 // VGPRs move ~16 B/clk/CU, LDS-DMA 33-42 (tools/microbench/ldpath.hip); each wave stages only ITS OWN 32 rows (four
 // 8-row x 128-byte pieces per 64-channel chunk) into a wave-private quarter of two 16-KiB buffers, so no barrier and no
 // special wave are involved: chunk j+2 is requested right after the wave has read chunk j out of the same buffer.
+// C1 == 128 (RB1 below): the 32-KiB stage buffers leave room for ONE such buffer at two workgroups per CU, so chunk j+1 is requested right
+// after chunk j has been read, and read behind a wait that counts only the operand requests issued in between (`res_dma` below).
 // SC = true (first block of stage 1: C1 == 64, shortcut input of 64 channels at the output resolution): the block's 1x1 SHORTCUT
 // convolution is a second GEMM into the same accumulators, y = relu(a1 . W2^T + xs . Wsc^T + (b2 + bsc)), instead of a residual
 // that a separate launch wrote (274 MB at batch 8) and this kernel read back: the 64 shortcut channels of the wave's 32 pixels sit
@@ -128,7 +146,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     };
     if constexpr (TRACE) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tstamp[0])::"memory");
     stamp(1);
-    static_assert(!RDMA || C1 == 64, "residual staging buffers are budgeted for C1 == 64 (80 KiB of LDS per workgroup)");
+    static_assert(!RDMA || C1 == 64 || C1 == 128, "residual staging buffers are budgeted for C1 == 64 and C1 == 128 (80 KiB of LDS per workgroup)");
     static_assert(!RDMA || RC == 0, "a rebuilt residual is not staged");
     static_assert(!SC || (C1 == 64 && !RDMA), "fused shortcut: 64-channel tails only; it replaces the residual");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -150,6 +168,11 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     constexpr int CHUNK_BYTES = W2C_BYTES + C3 * ROW_BYTES + WSC_BYTES + RC_BYTES;
     constexpr int STAGE_BYTES = (A_BYTES + C1 * ROW_BYTES) > CHUNK_BYTES ? (A_BYTES + C1 * ROW_BYTES) : CHUNK_BYTES;   // a stage buffer holds a 3x3 k-step's tiles or a chunk's operands
     static_assert(RC == 0 || (RC == 1 && C1 == 64 && !RDMA && !SC), "residual rebuild: second block of stage 1");
+    // RDMA at C1 == 128: the stage buffers are 32 KiB each, which leaves room for ONE wave-private residual buffer (RB1) at two workgroups per CU
+    constexpr bool RB1 = RDMA && C1 == 128;
+    constexpr int RES_BUFS = RDMA ? (RB1 ? 1 : 2) : 0;
+    static_assert(!RDMA || 2 * STAGE_BYTES + RES_BUFS * NW * 4096 == 80 * 1024, "RDMA tails: 80 KiB of LDS, two workgroups per CU");
+    constexpr int OP_PIECES = W2_PIECES + W3_PIECES;   // LDS-DMA requests per wave of one chunk's operands (RB1 has neither SC nor RC)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -279,14 +302,14 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     const size_t pr_row[2] = {(size_t)(wm0 + li) * C2 + g * 8, (size_t)(wm0 + 16 + li) * C2 + g * 8};
     // RDMA: wave-private residual staging: rows of this wave, whole 128-byte rows, swizzled like every other tile
     constexpr int RES_BUF = NW * 4096;
-    unsigned char* const res_lds = smem + 2 * STAGE_BYTES + wave * 4096;   // + (j & 1) * RES_BUF for chunk j
+    unsigned char* const res_lds = smem + 2 * STAGE_BYTES + wave * 4096;   // + (j & 1) * RES_BUF for chunk j (RB1: one buffer)
     const __amdgpu_buffer_rsrc_t rsrc_r = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<f16_t*>(p.res ? p.res : p.x1), 0, p.res ? (unsigned)((size_t)p.M * C2 * 2) : 0u, 0x00020000);   // rows >= M: zeros
     const unsigned res_voff = (unsigned)((wm0 + lrow) * C2) * 2u + (unsigned)lchunk * 16u;
     auto issue_res = [&](int j) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_r, (__attribute__((address_space(3))) void*)(res_lds + (j & 1) * RES_BUF + i * 1024), 16,
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_r, (__attribute__((address_space(3))) void*)(res_lds + (RB1 ? 0 : (j & 1) * RES_BUF) + i * 1024), 16,
                                                      res_voff + (unsigned)(i * 8 * C2 * 2), j * 128, 0, 0);
     };
     const bool has_res = RC ? true : (!SC && p.res != nullptr && !(p.dbg & 4));
@@ -296,6 +319,10 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     // still on its way in > 90 % of the cases; with 4 younger LDS-DMA requests in none), so they must not be counted -- rounds 2-3 did, and
     // were saved only by the operands having been requested a whole chunk step earlier.  Hence: N = the residual pieces of chunk j + 2 when
     // they travel by LDS-DMA, otherwise 0; and the y stores of a step are issued AFTER its wait, so that a vmcnt(0) never waits for them.
+    // RB1 (one residual buffer): chunk j+1's pieces are requested in step j, right after chunk j has been read out of the buffer.  The barrier
+    // wait of step j leaves those four in flight (wave-private, the youngest requests); the wait in front of step j+1's read leaves the
+    // OP_PIECES operand requests of chunk j+2 in flight, which step j+1 has issued just before.  Nothing but LDS-DMA requests may sit among the
+    // counted ones, so a step's y stores and bias loads are fenced in front of its operand requests.
     const bool res_dma = RDMA && has_res;
     auto load_res = [&](int j, uint4 (&r)[4]) {
         if constexpr (RDMA) {
@@ -364,16 +391,23 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
         compute_main(ks & 1);
         __syncthreads();
     }
-    // last k-step: the free stage buffer receives chunk 0's operands; residual chunks 0 and 1 start their trip
+    // last k-step: the free stage buffer receives chunk 0's operands; residual chunks 0 and 1 (RB1: chunk 0) start their trip
+    float4v b2n[4];   // RB1: the expand bias of the next chunk step, loaded in front of that step's LDS-DMA requests
+    if constexpr (RB1) {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) b2n[nt] = *reinterpret_cast<const float4v*>(p.b2 + own_ch(nt, g));
+        compiler_fence();
+    }
     issue_chunk(0, nk & 1);
     compiler_fence();
     if constexpr (RC == 0) {
         load_res(0, res[0]);
-        load_res(1, res[1]);
+        if constexpr (!RB1) load_res(1, res[1]);
     }
     compiler_fence();
     compute_main((nk - 1) & 1);
-    if (res_dma) wait_vmcnt<4>();   // chunk 0 operands and residual chunk 0 landed (chunk 1's 4 pieces, younger LDS-DMA requests, may still fly)
+    if (res_dma) wait_vmcnt<4>();   // chunk 0 operands and residual chunk 0 landed (chunk 1's 4 pieces, younger LDS-DMA requests, may still fly);
+                                    // RB1: chunk 0's operands landed, its 4 residual pieces may still fly
     else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     stamp(3);
@@ -417,15 +451,38 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     for (int j = 0; j < NCH; ++j) {
         const int buf = (nk + j) & 1;
         uint4 (&res_cur)[4] = res[j % 3];
+        float4v b2c[4];
+        if constexpr (RB1) {   // (behind the previous step's y stores, in front of this step's requests)
+            compiler_fence();
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) b2c[nt] = b2n[nt];
+            if (j + 1 < NCH) {
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) b2n[nt] = *reinterpret_cast<const float4v*>(p.b2 + (j + 1) * 64 + own_ch(nt, g));
+            }
+            compiler_fence();
+        }
         if (j + 1 < NCH) issue_chunk(j + 1, buf ^ 1);
         compiler_fence();
         if constexpr (RDMA) {
-            if (has_res) {   // paired layout out of this wave's rows of the staged chunk; then the buffer is free for chunk j+2
+            if (has_res) {   // paired layout out of this wave's rows of the staged chunk; then the buffer is free for chunk j+2 (RB1: j+1)
+                if constexpr (RB1) {   // chunk j's pieces have landed: only the operand requests just issued are younger
+                    if (j + 1 < NCH) wait_vmcnt<OP_PIECES>();
+                    else wait_vmcnt<0>();
+                }
+                const unsigned char* src[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    res_cur[i] = *reinterpret_cast<const uint4*>(res_lds + (j & 1) * RES_BUF + swz((i & 1) * 16 + li, (i >> 1) * 4 + g));
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (j + 2 < NCH) issue_res(j + 2);
+                for (int i = 0; i < 4; ++i) {
+                    src[i] = res_lds + (RB1 ? 0 : (j & 1) * RES_BUF) + swz((i & 1) * 16 + li, (i >> 1) * 4 + g);
+                    if constexpr (!RB1) res_cur[i] = *reinterpret_cast<const uint4*>(src[i]);
+                }
+                if constexpr (RB1) {
+                    lds_read16x4_raw(src, res_cur);   // (read and waited for: the buffer is free again)
+                    if (j + 1 < NCH) issue_res(j + 1);
+                } else {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if (j + 2 < NCH) issue_res(j + 2);
+                }
             }
         } else if constexpr (RC == 0) {
             if (j + 2 < NCH) load_res(j + 2, res[(j + 2) % 3]);
@@ -469,7 +526,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
         float4v acc2[4][2];
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-            const float4v b = *reinterpret_cast<const float4v*>(p.b2 + j * 64 + own_ch(nt, g));
+            float4v b;
+            if constexpr (RB1) b = b2c[nt];
+            else b = *reinterpret_cast<const float4v*>(p.b2 + j * 64 + own_ch(nt, g));
             acc2[nt][0] = b;
             acc2[nt][1] = b;
         }
@@ -533,8 +592,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
         }
         if (j + 1 < NCH) {
             // chunk j+1's operands (requested at the top of this step) have landed; only the residual pieces of chunk j+2 (LDS-DMA requests
-            // younger than the operands') may stay in flight
-            if (res_dma && j + 2 < NCH) wait_vmcnt<4>();
+            // younger than the operands') may stay in flight; RB1: the pieces of chunk j+1
+            if (res_dma && (RB1 || j + 2 < NCH)) wait_vmcnt<4>();
             else wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
         }
@@ -581,8 +640,8 @@ template <int C1, int C3, bool RDMA, bool SC = false, bool TRACE = false, int RC
 hipError_t launch_btail_t(const BtailParams& p, hipStream_t stream) {
     constexpr int BM = 32 * NW;
     constexpr int MAIN = (BM + C1) * ROW_BYTES, CHUNK = 64 * C1 * 2 + C3 * ROW_BYTES + (SC ? 64 * ROW_BYTES : 0) + (RC ? 2 * 64 * ROW_BYTES : 0);
-    constexpr int LDS = 2 * (MAIN > CHUNK ? MAIN : CHUNK) + (RDMA ? 2 * NW * 4096 : 0);
-    static_assert(LDS <= 160 * 1024, "LDS per workgroup");
+    constexpr int LDS = 2 * (MAIN > CHUNK ? MAIN : CHUNK) + (RDMA ? (C1 == 128 ? 1 : 2) * NW * 4096 : 0);   // C1 == 128: one residual buffer
+    static_assert(LDS <= 160 * 1024 && (!RDMA || LDS == 80 * 1024), "LDS per workgroup");
     OPD_SET_MAX_LDS_ONCE((btail_kernel<C1, C3, RDMA, SC, TRACE, RC>), LDS);
     OPD_LAUNCH((btail_kernel<C1, C3, RDMA, SC, TRACE, RC>), dim3((p.M + BM - 1) / BM), dim3(64 * NW), LDS, stream, p);
     static const char* const kname = opd_kernel_name("btail_kernel<%d, %d, %s, %s, %s, %d>", C1, C3, OPD_BOOLSTR(RDMA), OPD_BOOLSTR(SC), OPD_BOOLSTR(TRACE), RC);
@@ -622,7 +681,8 @@ hipError_t OPD_SYM(opd_launch_btail)(const BtailParams& p_in, hipStream_t stream
     if (p.trace) {   // tools/trace_btail.py: the two shapes that dominate stages 1 and 2
         if (p.C1 == 64 && p.C3 == 64 && (p.dbg & 16)) return launch_btail_t<64, 64, false, false, true>(p, stream);
         if (p.C1 == 64 && p.C3 == 64) return launch_btail_t<64, 64, true, false, true>(p, stream);
-        if (p.C1 == 128 && p.C3 == 128) return launch_btail_t<128, 128, false, false, true>(p, stream);
+        if (p.C1 == 128 && p.C3 == 128 && (p.dbg & 16)) return launch_btail_t<128, 128, false, false, true>(p, stream);
+        if (p.C1 == 128 && p.C3 == 128) return launch_btail_t<128, 128, true, false, true>(p, stream);
         return hipErrorInvalidValue;
     }
     if (p.C1 == 64) {
@@ -631,8 +691,9 @@ hipError_t OPD_SYM(opd_launch_btail)(const BtailParams& p_in, hipStream_t stream
         if (p.C3 == 64) return rdma ? launch_btail_t<64, 64, true>(p, stream) : launch_btail_t<64, 64, false>(p, stream);
         return rdma ? launch_btail_t<64, 128, true>(p, stream) : launch_btail_t<64, 128, false>(p, stream);
     }
-    if (p.C3 == 0) return launch_btail_t<128, 0, false>(p, stream);
-    return launch_btail_t<128, 128, false>(p, stream);
+    const bool rdma = !(p.dbg & 16);
+    if (p.C3 == 0) return rdma ? launch_btail_t<128, 0, true>(p, stream) : launch_btail_t<128, 0, false>(p, stream);
+    return rdma ? launch_btail_t<128, 128, true>(p, stream) : launch_btail_t<128, 128, false>(p, stream);
 }
 
 #ifndef OPD_ELEM_BF16

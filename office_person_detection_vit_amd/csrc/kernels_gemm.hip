@@ -698,6 +698,7 @@ struct StemPoolParams {
     const uint8_t* frames;      // [B][H][W][3] uint8 BGR
     const int32_t* valid_hw;    // nullable [B][2]: frame sizes inside the canvas (ragged batch); outside -> zeros
     int H, W;
+    StemReduce red;             // optional (z0 != null): stage 1's first 1x1 reduce on the pooled map, see below
 };
 
 // 16-byte-chunk XOR swizzle that keeps ds_read_b128 fragment reads conflict free for rows of BKT halfs:
@@ -725,6 +726,9 @@ constexpr int STEM_TPW = 6;              // tiles per workgroup
 constexpr int STEM_PROW = 70 * 8;        // bytes per patch row (70 NHWC4 pixels)
 constexpr int STEM_PATCH = 9 * 1024;     // 15 rows x 560 B = 8400 B, staged as 9 one-KiB pieces
 constexpr int STEM_W_BYTES = 7 * 64 * 64;
+constexpr int STEM_ZT = 32 * 128;        // the pooled pixels of a tile as a B operand: [32 pixels][64 channels], 128-byte rows swizzled (swz_t<64>)
+constexpr int STEM_LDS = STEM_W_BYTES + 2 * STEM_PATCH + 160 * ROW_BYTES + 1024 + STEM_ZT;   // (+ the sink of the U8 form, + the reduce's tile)
+static_assert(STEM_LDS <= 80 * 1024, "stem: two workgroups per CU");
 
 // U8 = true: the kernel reads the uint8 BGR frames itself.  A patch chunk (2 pixels = 6 source bytes at an arbitrary byte address)
 // is fetched one tile ahead as three aligned dwords per chunk, realigned with v_alignbyte and normalised in registers:
@@ -736,6 +740,14 @@ constexpr int STEM_W_BYTES = 7 * 64 * 64;
 //  LDS-bound stem +43 us, more than the 34 us the removed launch took.)
 constexpr float STEM_NA[3] = {0.017124755308032036f, 0.017507001757621765f, 0.01742919534444809f};   // RGB: (1/255) / std
 constexpr float STEM_NB[3] = {2.1179039478302f, 2.0357141494750977f, 1.804444432258606f};            // RGB: mean / std
+
+// Stage 1's first 1x1 reduce inside the stem (StemReduce; z0 = relu(w0 . pool + b0), 64 -> 64 channels).  The pooled map is 68 MB at batch 8,
+// and the first thing the trunk does with it is a K = 64 pointwise GEMM: a launch that reads all of it back.  A pooling thread holds 8
+// consecutive channels of one pooled pixel, which is a piece of an MFMA B operand; so the 240 pooling threads also write their values into a
+// 4-KiB [32 pixels][64 ch] LDS tile, and wave w multiplies it by rows 16w .. 16w+15 of w0 (two A fragments, held in registers for all tiles
+// of the workgroup): 2 pixel tiles x 2 k-steps of the 16x16x32 MFMA per tile, accumulators from the bias, k-block 0 before k-block 1, ReLU,
+// one rounding -- conv_gemm_dma_kernel's arithmetic for this layer, hence its bits.  The GEMM of tile t runs behind the top barrier of tile
+// t+1 (the barrier the pooling of tile t is published by anyway) and once more behind one extra barrier after the last tile.
 
 // Row placement of the pooling patch in LDS.  The pooling threads of one ds_read_b128 lane group read pixels 2 apart (pooled neighbours),
 // i.e. rows of ONE parity: in plain row order those sit in the same half of the 256-byte bank line and collide two by two; the accumulator
@@ -751,6 +763,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_kernel(StemPoolParams p) {
     unsigned char* const Wl = smem;                              // [7][64][64 B], rows swizzled (swz_t<32>)
     unsigned char* const Pin = smem + STEM_W_BYTES;              // two input patches
     unsigned char* const patch = Pin + 2 * STEM_PATCH;           // [160 pixels][64 ch] fp16 convolution outputs for the pooling
+    unsigned char* const zt = patch + 160 * 128 + 1024;          // [32 pooled pixels][64 ch] of the last pooled tile (behind the U8 form's sink)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -871,6 +884,32 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_kernel(StemPoolParams p) {
     // the workgroup: their 14 fragments per wave (7 filter rows x 2 column tiles, 56 VGPRs) are read ONCE, after the first barrier, and stay
     // in registers for the up to six tiles — 35 KiB of fragment reads per wave and tile instead of 49 (round 4).
     half8 wf[7][2];
+    // the reduce: this wave's 16 output channels
+    const bool red = p.red.z0 != nullptr;
+    half8 w0f[2] = {};
+    float4v b0v = {};
+    if (red) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) w0f[kk] = *reinterpret_cast<const half8*>(p.red.w0 + (wave * 16 + li) * 64 + kk * 32 + g * 8);
+        b0v = *reinterpret_cast<const float4v*>(p.red.b0 + wave * 16 + g * 4);
+    }
+    auto reduce_tile = [&](const int rx0) {   // rx0: first pooled column of the tile whose pooled pixels sit in `zt`
+#pragma unroll
+        for (int pt = 0; pt < 2; ++pt) {
+            float4v a = b0v;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+                a = OPD_MFMA_16x16x32(w0f[kk], *reinterpret_cast<const half8*>(zt + swz_t<64>(pt * 16 + li, kk * 4 + g)), a);
+            const int pp = pt * 16 + li;         // lane (g, li): channels 16 wave + 4 g .. + 3 of pooled pixel pp (30 and 31 do not exist)
+            const int ly = pp >= 15 ? 1 : 0, lx = pp - ly * 15;
+            const int py = py0 + ly, px = rx0 + lx;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[r] = a[r] > 0.f ? a[r] : 0.f;
+            if (pp < 30 && py < p.PH && px < p.PW)
+                *reinterpret_cast<uint2*>(p.red.z0 + (((size_t)b * p.PH + py) * p.PW + px) * 64 + wave * 16 + g * 4) =
+                    make_uint2(pack2h(a[0], a[1]), pack2h(a[2], a[3]));
+        }
+    };
     for (int tx = tx_first; tx < tx_end; ++tx) {
         const int buf = (tx - tx_first) & 1;
         // this tile's patch (and, first time, the weights) landed; the previous tile's pooling is done.  LDS-DMA data (the weights; the patch of
@@ -885,6 +924,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_kernel(StemPoolParams p) {
                 for (int nt = 0; nt < 2; ++nt)
                     wf[kh][nt] = *reinterpret_cast<const half8*>(Wl + kh * 4096 + swz_t<32>(wn * 32 + nt * 16 + li, g));
         }
+        if (red && tx > tx_first) reduce_tile((tx - 1) * 15);   // (before the next patch is requested: no LDS-DMA in flight next to these reads)
         if constexpr (!U8)
             if (tx + 1 < tx_end) issue_patch(tx + 1, buf ^ 1);
         const int px0 = tx * 15, cx0 = 2 * px0 - 1;
@@ -958,8 +998,13 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_kernel(StemPoolParams p) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) m[j] = m[j] > (elem_t)0.f ? m[j] : (elem_t)0.f;   // ReLU (a -0 from a rounded tiny negative becomes +0, as in the unfused pair)
                 *reinterpret_cast<half8*>(p.out + (((size_t)b * p.PH + py) * p.PW + px) * 64 + c8 * 8) = m;
+                if (red) *reinterpret_cast<half8*>(zt + swz_t<64>(pp, c8)) = m;
             }
         }
+    }
+    if (red) {   // the last tile's pooled pixels
+        __syncthreads();
+        reduce_tile((tx_end - 1) * 15);
     }
 #endif
 }
@@ -1022,16 +1067,17 @@ hipError_t OPD_SYM(opd_launch_conv_gemm)(const ConvGemmParams& p_in, hipStream_t
 // Pre-processing + stem + max-pool in one launch: frames [B][H][W][3] uint8 BGR (valid_hw nullable [B][2]), geometry as below with
 // Hp = 2 OH + 6, Wp = 2 OW + 6 the size the materialised padded image would have.
 hipError_t OPD_SYM(opd_launch_stem_pool_u8)(const uint8_t* frames, const int32_t* valid_hw, const f16_t* w, const float* bias, f16_t* out, int B, int H,
-                                   int W, int OH, int OW, int PH, int PW, hipStream_t stream) {
+                                   int W, int OH, int OW, int PH, int PW, hipStream_t stream, const StemReduce& red) {
     if (B <= 0 || H <= 0 || W <= 0 || OH != (H - 1) / 2 + 1 || OW != (W - 1) / 2 + 1 || PH != (OH - 1) / 2 + 1 || PW != (OW - 1) / 2 + 1 ||
-        (size_t)B * H * W * 3 >= 0x7fffff00ull)
+        (size_t)B * H * W * 3 >= 0x7fffff00ull || (red.z0 && (!red.w0 || !red.b0)))
         return hipErrorInvalidValue;
     StemPoolParams p{};
+    p.red = red;
     p.frames = frames; p.valid_hw = valid_hw; p.H = H; p.W = W;
     p.w = w; p.bias = bias; p.out = out; p.B = B; p.Hp = 2 * OH + 6; p.Wp = 2 * OW + 6; p.OH = OH; p.OW = OW; p.PH = PH; p.PW = PW;
     p.tiles_y = (PH + 1) / 2;
     p.tiles_x = (PW + 14) / 15;
-    constexpr int LDS2 = STEM_W_BYTES + 2 * STEM_PATCH + 160 * ROW_BYTES + 1024;   // (+ the sink of the U8 form)
+    constexpr int LDS2 = STEM_LDS;
     OPD_SET_MAX_LDS_ONCE(stem_pool2_kernel<true>, LDS2);
     const int nseg = (p.tiles_x + STEM_TPW - 1) / STEM_TPW;
     OPD_LAUNCH(stem_pool2_kernel<true>, dim3(B * p.tiles_y * nseg), dim3(256), LDS2, stream, p);
@@ -1039,15 +1085,16 @@ hipError_t OPD_SYM(opd_launch_stem_pool_u8)(const uint8_t* frames, const int32_t
 }
 
 hipError_t OPD_SYM(opd_launch_stem_pool)(const f16_t* x4p, const f16_t* w, const float* bias, f16_t* out, int B, int Hp, int Wp, int OH,
-                                int OW, int PH, int PW, hipStream_t stream) {
+                                int OW, int PH, int PW, hipStream_t stream, const StemReduce& red) {
     if (Hp < 2 * OH + 6 || Wp < 2 * OW + 6 || (Wp & 1) || PH != (OH - 1) / 2 + 1 || PW != (OW - 1) / 2 + 1 ||
-        (size_t)B * Hp * Wp * 8 >= 0x7fffff00ull)
+        (size_t)B * Hp * Wp * 8 >= 0x7fffff00ull || (red.z0 && (!red.w0 || !red.b0)))
         return hipErrorInvalidValue;
     StemPoolParams p{};
+    p.red = red;
     p.x4p = x4p; p.w = w; p.bias = bias; p.out = out; p.B = B; p.Hp = Hp; p.Wp = Wp; p.OH = OH; p.OW = OW; p.PH = PH; p.PW = PW;
     p.tiles_y = (PH + 1) / 2;
     p.tiles_x = (PW + 14) / 15;
-    constexpr int LDS2 = STEM_W_BYTES + 2 * STEM_PATCH + 160 * ROW_BYTES + 1024;   // (+ the sink of the U8 form)
+    constexpr int LDS2 = STEM_LDS;
     OPD_SET_MAX_LDS_ONCE(stem_pool2_kernel<false>, LDS2);
     const int nseg = (p.tiles_x + STEM_TPW - 1) / STEM_TPW;
     OPD_LAUNCH(stem_pool2_kernel<false>, dim3(B * p.tiles_y * nseg), dim3(256), LDS2, stream, p);

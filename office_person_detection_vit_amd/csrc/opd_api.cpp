@@ -281,6 +281,8 @@ static Switches read_switches(int flags) {
     env("OPD_SMALL_SPLITK", &sw.small_splitk);
     env("OPD_SMALL_ENC", &sw.small_enc);
     env("OPD_Y_STRIDE2", &sw.y_stride2);
+    env("OPD_RES_DMA128", &sw.res_dma128);
+    env("OPD_STEM_REDUCE", &sw.stem_reduce);
     env("OPD_TAIL3_SPLIT", &sw.tail3_split);
     env("OPD_FUSE_PREP", &sw.fuse_prep);
     env("OPD_POS_SHADOW", &sw.pos_shadow);

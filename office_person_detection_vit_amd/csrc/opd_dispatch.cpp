@@ -7,12 +7,12 @@
 hipError_t opd_launch_conv_gemm(const ConvGemmParams& p, hipStream_t s) { return OPD_PICK(opd_launch_conv_gemm, p.dtype, p, s); }
 hipError_t opd_launch_conv_w8(const ConvGemmParams& p, hipStream_t s) { return OPD_PICK(opd_launch_conv_w8, p.dtype, p, s); }
 hipError_t opd_launch_stem_pool_u8(const uint8_t* frames, const int32_t* valid_hw, const f16_t* w, const float* bias, f16_t* out, int B, int H, int W, int OH,
-                                   int OW, int PH, int PW, hipStream_t s, int dtype) {
-    return OPD_PICK(opd_launch_stem_pool_u8, dtype, frames, valid_hw, w, bias, out, B, H, W, OH, OW, PH, PW, s);
+                                   int OW, int PH, int PW, hipStream_t s, int dtype, const StemReduce& red) {
+    return OPD_PICK(opd_launch_stem_pool_u8, dtype, frames, valid_hw, w, bias, out, B, H, W, OH, OW, PH, PW, s, red);
 }
 hipError_t opd_launch_stem_pool(const f16_t* x4p, const f16_t* w, const float* bias, f16_t* out, int B, int Hp, int Wp, int OH, int OW, int PH, int PW,
-                                hipStream_t s, int dtype) {
-    return OPD_PICK(opd_launch_stem_pool, dtype, x4p, w, bias, out, B, Hp, Wp, OH, OW, PH, PW, s);
+                                hipStream_t s, int dtype, const StemReduce& red) {
+    return OPD_PICK(opd_launch_stem_pool, dtype, x4p, w, bias, out, B, Hp, Wp, OH, OW, PH, PW, s, red);
 }
 hipError_t opd_launch_btail(const BtailParams& p, hipStream_t s) { return OPD_PICK(opd_launch_btail, p.dtype, p, s); }
 hipError_t opd_launch_btail256(const BtailParams& p, hipStream_t s) { return OPD_PICK(opd_launch_btail256, p.dtype, p, s); }

@@ -106,10 +106,17 @@ hipError_t opd_launch_conv_gemm(const ConvGemmParams& p, hipStream_t stream);
 bool opd_conv_w8_supported(const ConvGemmParams& p);
 hipError_t opd_launch_conv_w8(const ConvGemmParams& p, hipStream_t stream);
 // fused stem: 7x7 s2 conv + FrozenBN + ReLU + 3x3 s2 max-pool on the zero-bordered NHWC4 image -> pooled NHWC fp16
+// StemReduce (optional, z0 != null): the same launch also writes z0 [B][PH][PW][64] = relu(w0 . pooled + b0), w0 [64][64] -- the 1x1 stride-1
+// 64 -> 64 reduce that opens stage 1, with the bits opd_launch_conv_gemm gives for that layer
+struct StemReduce {
+    f16_t* z0 = nullptr;
+    const f16_t* w0 = nullptr;
+    const float* b0 = nullptr;
+};
 hipError_t opd_launch_stem_pool_u8(const uint8_t* frames, const int32_t* valid_hw, const f16_t* w, const float* bias, f16_t* out, int B, int H,
-                                   int W, int OH, int OW, int PH, int PW, hipStream_t stream, int dtype = 0);   // pre-processing inside the stem
+                                   int W, int OH, int OW, int PH, int PW, hipStream_t stream, int dtype = 0, const StemReduce& red = StemReduce());   // pre-processing inside the stem
 hipError_t opd_launch_stem_pool(const f16_t* x4p, const f16_t* w, const float* bias, f16_t* out, int B, int Hp, int Wp, int OH,
-                                int OW, int PH, int PW, hipStream_t stream, int dtype = 0);
+                                int OW, int PH, int PW, hipStream_t stream, int dtype = 0, const StemReduce& red = StemReduce());
 // fused bottleneck tail (kernels_btail.hip):  a1 = relu(conv3x3(x1, w1) + b1) ; y = relu(a1*w2 + b2 + res) ; z = relu(y*w3 + b3)
 // x1 [B][H][W][C1] fp16, y/res [M][4*C1], z [M][C3]  (M = B*OH*OW, 3x3 pad 1, stride 1 or 2).  w2p / w3p are the 1x1
 // weights: plain K order for C1 = 64 / 128, opd_permute_k32 applied along K for C1 = 256 (kernels_btail3.hip).  C3 == 0: no z.  (C1, C3) must satisfy opd_btail_supported.
@@ -127,7 +134,8 @@ struct BtailParams {
     const float* b3;
     f16_t* z;          // [M][C3]
     int B, H, W, OH, OW, stride, M, C1, C3;
-    int dbg;           // timing ablations for tools (0 = normal): 1 skip the 3x3 loop, 2 skip stores, 4 skip residual, 8 stop after the 3x3
+    int dbg;           // timing ablations for tools (0 = normal): 1 skip the 3x3 loop, 2 skip stores, 4 skip residual, 8 stop after the 3x3;
+                       // 16 is no ablation: the residual of the 64 / 128-channel tails through register loads instead of LDS-DMA (identical bits)
     FastDiv fd_ohw, fd_ow;   // filled by opd_launch_btail
     unsigned long long* trace;   // tools only: per-workgroup phase stamps [grid][16] (btail_kernel<..., TRACE>); null in the model
     int rev;           // 1: each XCD walks its tiles in descending order (results identical; see kernels_btail.hip)
@@ -455,9 +463,9 @@ hipError_t opd_launch_attention(const AttnParams& p, hipStream_t stream);
 OPD_DECL_ELEM(opd_launch_conv_gemm, const ConvGemmParams& p, hipStream_t stream)
 OPD_DECL_ELEM(opd_launch_conv_w8, const ConvGemmParams& p, hipStream_t stream)
 OPD_DECL_ELEM(opd_launch_stem_pool_u8, const uint8_t* frames, const int32_t* valid_hw, const f16_t* w, const float* bias, f16_t* out, int B, int H, int W, int OH,
-              int OW, int PH, int PW, hipStream_t stream)
+              int OW, int PH, int PW, hipStream_t stream, const StemReduce& red)
 OPD_DECL_ELEM(opd_launch_stem_pool, const f16_t* x4p, const f16_t* w, const float* bias, f16_t* out, int B, int Hp, int Wp, int OH, int OW, int PH, int PW,
-              hipStream_t stream)
+              hipStream_t stream, const StemReduce& red)
 OPD_DECL_ELEM(opd_launch_btail, const BtailParams& p, hipStream_t stream)
 OPD_DECL_ELEM(opd_launch_btail256, const BtailParams& p, hipStream_t stream)
 OPD_DECL_ELEM(opd_launch_gemm_ln, const GemmLnParams& p, hipStream_t stream)

@@ -515,25 +515,36 @@ static int fwd_prepare_ragged(Fwd& c, const int32_t* valid_hw) {
     return OPD_OK;
 }
 
-// pre-processing, stem 7x7 and max-pool -> d_pool
+// Stage 1's first 1x1 reduce (64 -> 64 on the pooled map) inside the fused stem launch (Switches::stem_reduce; kernels_gemm.hip, StemReduce):
+// the stem writes that block's c0 output into the buffer the launch would have written, and the trunk starts with it in hand.  Every other
+// case keeps the launch: another architecture, the two-kernel stem, diagnostic taps (which checksum every launch's own output).
+static bool stem_reduces(const opd_detr* m) {
+    if (!m->sw.stem_reduce || !m->sw.fuse_stem_pool || m->taps || m->blocks.empty() || m->arch.depths[0] < 1) return false;
+    const Conv& c0 = m->blocks[0].c0;
+    return c0.KH == 1 && c0.KW == 1 && c0.stride == 1 && c0.pad == 0 && c0.Cin == 64 && c0.Cout == 64 && c0.w && c0.bias;
+}
+
+// pre-processing, stem 7x7 and max-pool -> d_pool (and, stem_reduces: the first block's reduce -> d_m0)
 static int fwd_stem(const Fwd& c, const void* d_pixels, int pixel_format) {
     opd_detr* m = c.m;
     const Dims& d = c.d;
     const int B = c.B, H = c.H, W = c.W;
     const int Hp = 2 * d.H1 + 6, Wp = 2 * d.W1 + 6;  // padded image seen by the stem: rows/cols 2*o + k, k = 0..7
     const bool u8 = pixel_format == OPD_PIXELS_U8_BGR_HWC;
-    const double flops = 2.0 * B * d.H1 * d.W1 * 64.0 * 147.0;
+    StemReduce red;
+    if (stem_reduces(m)) { red.z0 = m->d_m0; red.w0 = m->blocks[0].c0.w; red.b0 = m->blocks[0].c0.bias; }
+    const double flops = 2.0 * B * d.H1 * d.W1 * 64.0 * 147.0 + (red.z0 ? 2.0 * B * d.H2 * d.W2 * 64.0 * 64.0 : 0.0);
     if (m->sw.fuse_prep && m->sw.fuse_stem_pool && u8)
         return c.launch(CLS_CONV, flops, [&] {
             return opd_launch_stem_pool_u8(reinterpret_cast<const uint8_t*>(d_pixels), c.d_valid, m->stem.w, m->stem.bias, m->d_pool, B, H, W, d.H1, d.W1, d.H2, d.W2,
-                                           c.stream, m->dtype);
+                                           c.stream, m->dtype, red);
         }, {{"stem_pool_u8", m->d_pool, (size_t)B * d.H2 * d.W2 * 64 * 2}});
     RCCHK(c.launch(CLS_OTHER, 0.0, [&] {
         return u8 ? opd_launch_preprocess_u8(reinterpret_cast<const uint8_t*>(d_pixels), m->d_x4, B, H, W, Hp, Wp, c.d_valid, c.stream, m->dtype)
                   : opd_launch_preprocess_f32(reinterpret_cast<const float*>(d_pixels), m->d_x4, B, H, W, Hp, Wp, c.d_valid, c.stream, m->dtype);
     }));
     if (m->sw.fuse_stem_pool)
-        return c.launch(CLS_CONV, flops, [&] { return opd_launch_stem_pool(m->d_x4, m->stem.w, m->stem.bias, m->d_pool, B, Hp, Wp, d.H1, d.W1, d.H2, d.W2, c.stream, m->dtype); });
+        return c.launch(CLS_CONV, flops, [&] { return opd_launch_stem_pool(m->d_x4, m->stem.w, m->stem.bias, m->d_pool, B, Hp, Wp, d.H1, d.W1, d.H2, d.W2, c.stream, m->dtype, red); });
     // two kernels, for cross-checking: the stem as a stride-2 pointwise GEMM over the padded NHWC4 image's 8 x 8 x 4 windows, then the pool
     ConvGemmParams p = gemm_params(m, m->d_x4, m->stem.w, m->stem.bias, m->d_stem, B * d.H1 * d.W1, 64, 256);
     p.B = B; p.H = Hp; p.W = Wp; p.OH = d.H1; p.OW = d.W1; p.stride = 2; p.relu = 1; p.stem = 2;
@@ -592,7 +603,7 @@ static int trunk_blocks(const Fwd& c, const TrunkPlan& tp, int s, int b0, int nb
             p.y_stride2 = t.store == STORE_Y_STRIDE2;
             p.B = nb; p.H = ch; p.W = cw; p.OH = oh; p.OW = ow; p.stride = b.c1.stride; p.M = nb * oh * ow; p.C1 = C1; p.C3 = C3;
             p.rev = b0 ? t.rev_b : t.rev;
-            p.dbg = m->sw.dbg_btail;
+            p.dbg = m->sw.dbg_btail | (C1 == 128 && !m->sw.res_dma128 ? 16 : 0);   // (bit 16: the residual through register loads)
             RCCHK(c.launch(CLS_CONV, 2.0 * p.M * ((double)C1 * 9 * C1 + 4.0 * C1 * C1 + 4.0 * C1 * C3 + (t.sc == SC_TAIL ? 64.0 * 256 : 0.0)),
                            [&] { return opd_launch_btail(p, c.stream); },
                            {{"btail_y", p.y ? out : nullptr, (size_t)p.M * 4 * C1 * 2}, {"btail_z", C3 ? z : nullptr, (size_t)p.M * C3 * 2}}));
@@ -640,7 +651,7 @@ static int trunk_stage3_split(const Fwd& c, const TrunkPlan& tp, TrunkState& st)
 static int fwd_trunk(Fwd& c) {
     opd_detr* m = c.m;
     const TrunkPlan tp = plan_trunk(m->arch, m->blocks, m->cfg, m->sw, c.B, c.d.H2, c.d.W2, m->num_cus, m->taps != 0, m->profiling, m->stream2 != nullptr);
-    TrunkState st{0, c.d.H2, c.d.W2, -1, -1};
+    TrunkState st{0, c.d.H2, c.d.W2, stem_reduces(m) ? 0 : -1, -1};   // (z_id 0: the stem launch has written the first block's reduce into d_m0)
     for (int s = 0; s < 4; ++s) {
         RCCHK(s == 2 ? trunk_stage3_split(c, tp, st) : trunk_blocks(c, tp, s, 0, c.B, st));
         MARK(2 + s);   // (stage 3 ends at the join of its two chains)

@@ -112,6 +112,9 @@ struct Switches {
     int tail3_split = 1;     // stage 3: frames beyond whole rounds of the fused tail run as a second chain on `stream2` (0: one launch per tail)
     int tail_rc = 1;         // stage 1: block 0 stores a1 instead of y; block 1 rebuilds y as its residual (kernels_btail.hip, RC; env OPD_TAIL_RC, 0 = off)
     int y_stride2 = 1;       // last tail of stage 1: y stored only where the next stage's stride-2 shortcut reads it (env OPD_Y_STRIDE2)
+    int stem_reduce = 1;     // stage 1's first 1x1 reduce inside the fused stem launch (kernels_gemm.hip, StemReduce; env OPD_STEM_REDUCE, 0: own launch)
+    int res_dma128 = 1;      // stage 2's 128-channel tails take their residual by LDS-DMA into one wave-private buffer (kernels_btail.hip, RB1; env
+                             // OPD_RES_DMA128, 0: through register loads, BtailParams::dbg bit 16 -- identical bits)
     int wprefetch = 3;       // L2 warm-up of a launch's weights by its own workgroups: bit 0 implicit GEMM, bit 1 the encoder's FFN launch (env OPD_WPREFETCH)
     int w8 = -1;             // wide stage-4 layers through the eight-wave GEMM (kernels_w8.hip; identical bits): bit 0 3x3, bit 1 1x1 K >= 1024, bit 2 1x1 K = 512
                              // (env OPD_W8).  -1 = by the handle's flags: the 3x3 for OPD_FLAG_MULTI_STREAM handles (132 one-per-CU workgroups cost 22 % less

@@ -14,12 +14,14 @@
 using namespace opd;
 
 // the launch options of the hooks below (opd_test_util.h) and their setters
-int opd::g_conv_flags = 0, opd::g_gemm_ln_kloop = 0, opd::g_test_dtype = 0, opd::g_encffn_wprefetch = 0, opd::g_pos_frames = 0;
+int opd::g_conv_flags = 0, opd::g_gemm_ln_kloop = 0, opd::g_test_dtype = 0, opd::g_encffn_wprefetch = 0, opd::g_pos_frames = 0, opd::g_btail_dbg = 0;
 TAPI int opd_test_set_encffn_wprefetch(int on) { g_encffn_wprefetch = on ? 1 : 0; return OPD_OK; }
 TAPI int opd_test_set_pos_frames(int frames) { g_pos_frames = frames > 0 ? frames : 0; return OPD_OK; }
 TAPI int opd_test_set_elem_bf16(int on) { g_test_dtype = on ? OPD_DT_BF16 : OPD_DT_F16; return OPD_OK; }
 TAPI int opd_test_set_conv_flags(int flags) { g_conv_flags = flags; return OPD_OK; }
 TAPI int opd_test_set_gemm_ln_kloop(int on) { g_gemm_ln_kloop = on ? 1 : 0; return OPD_OK; }
+// opd_test_btail / opd_test_btail_repeat: the residual of the 64 / 128-channel tails through register loads (BtailParams::dbg bit 16) instead of LDS-DMA
+TAPI int opd_test_set_btail_res_regs(int on) { g_btail_dbg = on ? 16 : 0; return OPD_OK; }
 
 // B per-frame tables [B][rows][cols] fp32 -> one device copy and a device array of B pointers into it (bias_ptrs / pos_ptrs)
 static const float* const* upload_frame_tables(DevMem& dm, const float* tables, int B, size_t rows, size_t cols, const float** first) {
@@ -366,6 +368,7 @@ TAPI int opd_test_btail(const uint16_t* x1, const uint16_t* w1, const float* b1,
     const int C2 = 4 * C1;
     BtailParams p{}; p.dtype = g_test_dtype;
     btail_geometry(p, B, H, W, stride, C1, C3);
+    p.dbg = g_btail_dbg;
     const size_t M = (size_t)p.M;
     p.x1 = dm.up(x1, (size_t)B * H * W * C1);
     p.w1 = dm.up(w1, (size_t)C1 * 9 * C1);
@@ -395,6 +398,7 @@ TAPI int opd_test_btail_repeat(const uint16_t* x1, const uint16_t* w1, const flo
     const size_t M = (size_t)B * H * W;
     BtailParams p{}; p.dtype = g_test_dtype;
     btail_geometry(p, B, H, W, 1, C1, C3);
+    p.dbg = g_btail_dbg;
     p.x1 = dm.up(x1, M * C1); p.w1 = dm.up(w1, (size_t)C1 * 9 * C1); p.b1 = dm.up(b1, C1);
     btail_weights(dm, p, C1, C3, w2, w3);
     p.b2 = dm.up(b2, C2); p.res = dm.up(res, M * C2); p.y = dm.alloc<uint16_t>(M * C2);
@@ -657,6 +661,44 @@ TAPI int opd_test_stem_pool_u8(const uint8_t* frames, const int32_t* valid_hw, c
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(out_fused, d1, n));
     return down(out_split, d2, n);
+}
+
+// The stem launch with stage 1's first 1x1 reduce inside (StemReduce) against the same launch without it followed by opd_launch_conv_gemm
+// (64 -> 64, ReLU) on the pooled map: frames [B][H][W][3] uint8 BGR (valid_hw nullable [B][2]); u8 = 1: the kernel that pre-processes the
+// frames itself, 0: preprocess_u8_kernel first, then the kernel that reads the fp16 image.  w [64][256], w0 [64][64] in the hooks' element
+// type; pool_* / z_* [B][PH][PW][64] (the caller checks bit-equality).
+TAPI int opd_test_stem_reduce(const uint8_t* frames, const int32_t* valid_hw, const uint16_t* w, const float* bias, const uint16_t* w0, const float* b0,
+                              uint16_t* pool_fused, uint16_t* z_fused, uint16_t* pool_ref, uint16_t* z_ref, int B, int H, int W, int u8) {
+    DevMem dm;
+    const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1, PH = (OH - 1) / 2 + 1, PW = (OW - 1) / 2 + 1, Hp = 2 * OH + 6, Wp = 2 * OW + 6;
+    const size_t n = (size_t)B * PH * PW * 64;
+    const uint8_t* df = dm.up(frames, (size_t)B * H * W * 3);
+    const int32_t* dv = valid_hw ? dm.up(valid_hw, (size_t)2 * B) : nullptr;
+    const uint16_t* dw = dm.up(w, (size_t)64 * 256);
+    const float* db = dm.up(bias, 64);
+    uint16_t* dx = dm.alloc<uint16_t>((size_t)B * Hp * Wp * 4);
+    uint16_t *p1 = dm.alloc<uint16_t>(n), *z1 = dm.alloc<uint16_t>(n), *p2 = dm.alloc<uint16_t>(n), *z2 = dm.alloc<uint16_t>(n);
+    StemReduce red;
+    red.z0 = z1; red.w0 = dm.up(w0, (size_t)64 * 64); red.b0 = dm.up(b0, 64);
+    ConvGemmParams c{}; c.dtype = g_test_dtype;
+    conv_geometry(c, B, PH, PW, 64, PH, PW, 64, 1, 1, 1, 0);
+    c.x = p2; c.w = red.w0; c.bias = red.b0; c.out = z2; c.zero16 = zeros<uint32_t>(dm, 8); c.relu = 1;
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    HIPCHK(hipMemsetAsync(z1, 0xff, n * 2, nullptr));   // (a pixel the fused launch forgets stays NaN)
+    if (u8) {
+        HIPCHK(opd_launch_stem_pool_u8(df, dv, dw, db, p1, B, H, W, OH, OW, PH, PW, nullptr, g_test_dtype, red));
+        HIPCHK(opd_launch_stem_pool_u8(df, dv, dw, db, p2, B, H, W, OH, OW, PH, PW, nullptr, g_test_dtype));
+    } else {
+        HIPCHK(opd_launch_preprocess_u8(df, dx, B, H, W, Hp, Wp, dv, nullptr, g_test_dtype));
+        HIPCHK(opd_launch_stem_pool(dx, dw, db, p1, B, Hp, Wp, OH, OW, PH, PW, nullptr, g_test_dtype, red));
+        HIPCHK(opd_launch_stem_pool(dx, dw, db, p2, B, Hp, Wp, OH, OW, PH, PW, nullptr, g_test_dtype));
+    }
+    HIPCHK(opd_launch_conv_gemm(c, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    RCCHK(down(pool_fused, p1, n));
+    RCCHK(down(z_fused, z1, n));
+    RCCHK(down(pool_ref, p2, n));
+    return down(z_ref, z2, n);
 }
 
 // heads_kernel alone: hs [rows][256] fp32 (+ optional final LayerNorm), weights in the reference's [out][in] layout (the hooks

@@ -20,7 +20,7 @@ namespace opd {
 // enc_ffn_kernel's own warm-up (EncFfnParams::wprefetch), and the number of per-frame position tables of the position-shadow hooks
 // (0: `pos` is one [period][256] table; B > 0: `pos` is [B][period][256] and the kernels read it through a device array of B pointers).
 // Set by the opd_test_set_* hooks of opd_test_api.cpp, which defines them.
-extern __attribute__((visibility("hidden"))) int g_conv_flags, g_gemm_ln_kloop, g_test_dtype, g_encffn_wprefetch, g_pos_frames;
+extern __attribute__((visibility("hidden"))) int g_conv_flags, g_gemm_ln_kloop, g_test_dtype, g_encffn_wprefetch, g_pos_frames, g_btail_dbg;
 
 inline void apply_conv_flags(ConvGemmParams& p, int flags) {
     p.force_mt = (flags >> 8) & 7;

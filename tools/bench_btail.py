@@ -1,5 +1,7 @@
 """Times the fused bottleneck tail against the three launches it replaces, at the batch-8 800x1333 trunk shapes.
-Run on the GPU box:  python tools/bench_btail.py"""
+Run on the GPU box:  python tools/bench_btail.py
+--res-path: instead, the residual by LDS-DMA (default) against register loads (dbg bit 16) for the stage-2 tail shapes and one 64-channel
+shape, four interleaved rounds in one process."""
 import ctypes as C
 import os
 import sys
@@ -19,6 +21,17 @@ SHAPES = [  # B, H, W, C1, C3, stride
     (8, 50, 84, 256, 0, 1),       # last stage-3 tail
     (8, 67, 120, 256, 256, 1),    # r101 at 1066x1920 (configs[3]): 22 of these
 ]
+if "--res-path" in sys.argv:
+    for s in [(8, 200, 334, 128, 128, 2), (8, 100, 167, 128, 128, 1), (8, 100, 167, 128, 0, 1), (8, 200, 334, 64, 64, 1)]:
+        t = {0: [], 16: []}
+        for _ in range(4):
+            for dbg in (0, 16):
+                us = (C.c_float * 4)()
+                _capi.check(lib.opd_test_bench_btail(*s, dbg, 20, us), "bench_btail")
+                t[dbg].append(us[0])
+        f = lambda v: " ".join("%7.1f" % x for x in v)
+        print(f"{str(s):>28s}  LDS-DMA: {f(t[0])}  registers: {f(t[16])}  min {min(t[0]):.1f} / {min(t[16]):.1f} us = {min(t[0]) / min(t[16]):.4f}", flush=True)
+    sys.exit(0)
 if "--s3" in sys.argv:
     SHAPES = SHAPES[-3:]
 print(f"{'shape':>28s} {'fused us':>9s} {'c1':>7s} {'c2':>7s} {'c0n':>7s} {'unfused':>8s} {'TB/s fused':>10s}")
