@@ -17,7 +17,7 @@ SOURCES = ["kernels_gemm.hip", "kernels_w8.hip", "kernels_btail.hip", "kernels_b
 TEST_ONLY = {"opd_test_api.cpp", "opd_test_bench_api.cpp", "opd_test_model_api.cpp", "opd_reid_test_api.cpp", "opd_osnet_test_api.cpp", "opd_flow_test_api.cpp", "opd_floor_test_api.cpp", "opd_track_test_api.cpp", "opd_crop_test_api.cpp"}
 # kernel files with 16-bit operands: ONE source, compiled for fp16 and (-DOPD_ELEM_BF16) for bf16 (opd_elem.h)
 ELEM_SOURCES = ["kernels_gemm.hip", "kernels_w8.hip", "kernels_btail.hip", "kernels_btail3.hip", "kernels_rowln.hip", "kernels_attn.hip", "kernels_misc.hip"]
-HEADERS = ["opd_kernels.h", "opd_elem.h", "opd_loader.h", "opd_host.h", "opd_device.h", "opd_model.h", "opd_crop.h", "opd_reid.h", "opd_clip.h", "opd_osnet.h", "opd_flow.h", "opd_floor.h", "opd_assoc.h", "opd_track.h", "opd_test_util.h", os.path.join("..", "..", "include", "opd_detr.h")]
+HEADERS = ["opd_kernels.h", "opd_elem.h", "opd_kprims.h", "opd_loader.h", "opd_host.h", "opd_device.h", "opd_model.h", "opd_crop.h", "opd_reid.h", "opd_clip.h", "opd_osnet.h", "opd_flow.h", "opd_floor.h", "opd_assoc.h", "opd_track.h", "opd_test_util.h", os.path.join("..", "..", "include", "opd_detr.h")]
 # code-generation flags of every translation unit, and per file: the attention kernel consumes its S = K.Q^T accumulators with VALU right
 # away, so its MFMAs should write VGPRs (the default AGPR form costs 56 v_accvgpr moves per key tile in a VALU-bound loop).
 # tools/scan_dma_waits.py imports these: the ISA it checks must be the ISA that ships.
@@ -32,6 +32,25 @@ BF16_FLAGS = ["-DOPD_ELEM_BF16=1"]
 
 def hipcc_path() -> str:
     return os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def kernel_files(csrc: str = HERE) -> list:
+    return sorted(f for f in os.listdir(csrc) if f.startswith("kernels_") and f.endswith(".hip"))
+
+
+def device_asm(path: str, csrc: str = HERE) -> dict:
+    """The gfx950 assembly of one kernel file as it ships, per instantiation ("f16", and "bf16" for an ELEM_SOURCES file): the compile
+    step of tools/scan_dma_waits.py and tools/isa_fingerprint.py (`csrc`: the include directory -- another revision's sources)."""
+    import tempfile
+    base = os.path.basename(path)
+    variants = [("f16", [])] + ([("bf16", BF16_FLAGS)] if base in ELEM_SOURCES and os.path.exists(os.path.join(csrc, "opd_elem.h")) else [])
+    out = {}
+    for tag, vflags in variants:
+        with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
+            cmd = [hipcc_path()] + COMMON_FLAGS + EXTRA_FLAGS.get(base, []) + vflags + ["-S", "--cuda-device-only", "-I" + csrc, path, "-o", tmp.name]
+            subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
+            out[tag] = open(tmp.name).read()
+    return out
 
 
 LIB = os.path.join(PKG, "libopd_hip.so")

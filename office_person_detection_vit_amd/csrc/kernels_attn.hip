@@ -31,13 +31,8 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <math.h>
-#include "opd_kernels.h"
-#include "opd_elem.h"
+#include "opd_kprims.h"
 
-typedef elem_t half8 __attribute__((ext_vector_type(8)));
-typedef elem_t half4 __attribute__((ext_vector_type(4)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float float2v __attribute__((ext_vector_type(2)));
 typedef short short4v __attribute__((__vector_size__(4 * sizeof(short))));
 
 namespace {
@@ -117,8 +112,8 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnParams p) {
 
     // LDS-DMA staging: wave w moves key rows 16 w .. 16 w + 15 (+ 64 i) of the tile.  Rows past Lk of the LAST frame fall outside
     // the descriptor (zeros); of earlier frames they are the next frame's rows: finite, and masked like every key >= Lk.
-    const __amdgpu_buffer_rsrc_t rsrc_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.k), 0, (unsigned)((size_t)p.B * p.Lk * p.ldk * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.v), 0, (unsigned)((size_t)p.B * p.Lk * p.ldv * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_k = buf_rsrc(p.k, (unsigned)((size_t)p.B * p.Lk * p.ldk * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_v = buf_rsrc(p.v, (unsigned)((size_t)p.B * p.Lk * p.ldv * 2));
     const int vr = ((lane >> 4) & 1) * 8 + ((lane >> 1) & 7), vc = (lane >> 5) * 2 + (lane & 1);   // the V cell of this lane's slot
     const unsigned koff = (unsigned)(((size_t)b * p.Lk + wave * 16 + (lane & 15)) * p.ldk + h * 32 + (lane >> 4) * 8) * 2u;
     const unsigned voff = (unsigned)(((size_t)b * p.Lk + wave * 16 + vr) * p.ldv + h * 32 + vc * 8) * 2u;
@@ -127,10 +122,8 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnParams p) {
 #pragma unroll
         for (int i = 0; i < RPT; ++i) {
             const int row0 = t * KT + i * 64;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_k, (__attribute__((address_space(3))) void*)(base + (i * 4 + wave) * 1024), 16, koff,
-                                                     (unsigned)(row0 * p.ldk) * 2u, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_v, (__attribute__((address_space(3))) void*)(base + K_BYTES + (i * 4 + wave) * 1024), 16, voff,
-                                                     (unsigned)(row0 * p.ldv) * 2u, 0, 0);
+            dma16_buf(rsrc_k, base + (i * 4 + wave) * 1024, koff, (unsigned)(row0 * p.ldk) * 2u);
+            dma16_buf(rsrc_v, base + K_BYTES + (i * 4 + wave) * 1024, voff, (unsigned)(row0 * p.ldv) * 2u);
         }
     };
 

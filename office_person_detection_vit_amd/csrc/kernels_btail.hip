@@ -36,72 +36,17 @@
 // input-stationary 3x3 loop on 8 x 16 pixel tiles with the halo patch of x1 in LDS (43 % fewer staged bytes: 188 us), a
 // start-up stagger between workgroups sharing a CU (no phase locking), three instead of two workgroups per CU (185 vs
 // 189 us).  PMC: no HBM credit stalls, the vector-memory address FIFO is full 45 % of the busy cycles.
-#include <hip/hip_runtime.h>
-#include "opd_kernels.h"
-#include "opd_elem.h"
-
-typedef elem_t half8 __attribute__((ext_vector_type(8)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
-typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
+#include "opd_kprims.h"
 
 namespace {
 
-constexpr int ROW_BYTES = 128;
 constexpr int NW = 4;   // waves per workgroup = 32-pixel row groups of a tile: 128-pixel tiles, two workgroups per CU
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * ROW_BYTES + ((chunk ^ (row & 7)) << 4); }
-
-__device__ __forceinline__ int xcd_logical_block(int bid, int nblocks) {
-    const int q = nblocks >> 3, r = nblocks & 7;
-    const int x = bid & 7, k = bid >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-}
 
 // LDS row -> weight row (output channel) of the tails' channel ownership: bits [t][g1 g0][r1 r0] <- [g1 g0][t][r1 r0] within a 32-block
 __device__ __forceinline__ int own_row(const int rho) { return (rho & ~31) | (((rho >> 2) & 3) << 3) | (((rho >> 4) & 1) << 2) | (rho & 3); }
 // first of the four consecutive channels lane group g holds in accumulator tile nt
 __device__ __forceinline__ int own_ch(const int nt, const int g) { return (nt >> 1) * 32 + g * 8 + (nt & 1) * 4; }
 
-__device__ __forceinline__ int fdiv(const int m, const FastDiv& f) {   // m >= 0
-    return f.one ? m : (int)(__umulhi((unsigned)m, f.mul) >> f.shift);
-}
-
-__device__ __forceinline__ int xcd_logical_block_rev(int bid, int nblocks) {
-    const int q = nblocks >> 3, r = nblocks & 7;
-    const int x = bid & 7, k = bid >> 3;
-    return (x < r ? x * (q + 1) + q - k : r * (q + 1) + (x - r) * q + q - 1 - k);
-}
-
-__device__ __forceinline__ unsigned pack2h(float a, float b) {
-    typedef elem_t half2v __attribute__((ext_vector_type(2)));
-    half2v h;
-    h[0] = (elem_t)a;
-    h[1] = (elem_t)b;
-    unsigned u;
-    __builtin_memcpy(&u, &h, 4);
-    return u;
-}
-__device__ __forceinline__ void unpack2h(unsigned u, float& a, float& b) {
-    typedef elem_t half2v __attribute__((ext_vector_type(2)));
-    half2v h;
-    __builtin_memcpy(&h, &u, 4);
-    a = (float)h[0];
-    b = (float)h[1];
-}
-__device__ __forceinline__ half8 as_half8(unsigned a, unsigned b, unsigned c, unsigned d) {
-    uint4v u = {a, b, c, d};
-    half8 h;
-    __builtin_memcpy(&h, &u, 16);
-    return h;
-}
-
-template <int N_OUTSTANDING>
-__device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N_OUTSTANDING >= 0 && N_OUTSTANDING <= 63, "vmcnt range");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_OUTSTANDING) : "memory");
-}
-__device__ __forceinline__ void compiler_fence() { asm volatile("" ::: "memory"); }
 // Four 16-byte LDS reads the compiler does not see as such: in front of a `ds_read` whose address it cannot tell apart from the destinations
 // of the LDS-DMA requests in flight it waits vmcnt(0), which here would drain the operand requests a chunk step has just issued.  The caller
 // owns the vmcnt that proves the data has landed.  The reads and their lgkmcnt(0) are ONE statement: with the wait in a statement of its own
@@ -187,13 +132,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     const int lrow = lane >> 3;
     const int lchunk = (lane & 7) ^ lrow;
     const unsigned backoff = (unsigned)(p.W + 1) * (unsigned)C1 * 2u;  // pad = 1: every in-image tap gets a non-negative offset
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(p.x1)) - backoff, 0, (unsigned)((size_t)p.B * p.H * p.W * C1 * 2) + backoff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.w1), 0, (unsigned)(C1 * 9 * C1 * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.w2p), 0, (unsigned)(C2 * C1 * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(C3 ? p.w3p : p.w2p), 0, (unsigned)((C3 ? C3 : 1) * C2 * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_sc = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(SC ? p.wsc : RC ? p.rc_wsc : p.w2p), 0, (unsigned)(C2 * 64 * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(RC ? p.rc_w2 : p.w2p), 0, (unsigned)(C2 * 64 * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a = buf_rsrc(reinterpret_cast<const char*>(p.x1) - backoff, (unsigned)((size_t)p.B * p.H * p.W * C1 * 2) + backoff);
+    const __amdgpu_buffer_rsrc_t rsrc_w1 = buf_rsrc(p.w1, (unsigned)(C1 * 9 * C1 * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_w2 = buf_rsrc(p.w2p, (unsigned)(C2 * C1 * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_w3 = buf_rsrc(C3 ? p.w3p : p.w2p, (unsigned)((C3 ? C3 : 1) * C2 * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_sc = buf_rsrc(SC ? p.wsc : RC ? p.rc_wsc : p.w2p, (unsigned)(C2 * 64 * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_rw = buf_rsrc(RC ? p.rc_w2 : p.w2p, (unsigned)(C2 * 64 * 2));
     unsigned rowoff[4], rowmask[4], woff1[W1_PIECES], woff2[W2_PIECES], woff3[W3_PIECES ? W3_PIECES : 1], woffsc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)   // rows 8 (SC_PIECES wave + i) + lrow of the 64-row chunk
@@ -201,24 +145,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     {
         const int ohw = p.OH * p.OW;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = m_base + (wave * 4 + i) * 8 + lrow;
-            const bool okm = m < p.M;
-            const int mm = okm ? m : 0;
-            const int b = fdiv(mm, p.fd_ohw);   // (host-computed reciprocals: a runtime division is ~40 VALU instructions)
-            const int r = mm - b * ohw;
-            const int oh = fdiv(r, p.fd_ow);
-            const int ow = r - oh * p.OW;
-            rowoff[i] = (unsigned)(((b * p.H + oh * p.stride) * p.W + ow * p.stride) * C1) * 2u + (unsigned)lchunk * 16u;
-            unsigned kwmask = 0, mask = 0;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw)
-                if ((unsigned)(ow * p.stride - 1 + kw) < (unsigned)p.W) kwmask |= 1u << kw;
-#pragma unroll
-            for (int kh = 0; kh < 3; ++kh)
-                if ((unsigned)(oh * p.stride - 1 + kh) < (unsigned)p.H) mask |= kwmask << (kh * 3);
-            rowmask[i] = okm ? mask : 0u;
-        }
+        for (int i = 0; i < 4; ++i) tail_row_coords<C1>(p, m_base + (wave * 4 + i) * 8 + lrow, ohw, lchunk, rowoff[i], rowmask[i]);
 #pragma unroll
         for (int i = 0; i < W1_PIECES; ++i)
             woff1[i] = (unsigned)(own_row((wave * W1_PIECES + i) * 8 + lrow) * (9 * C1)) * 2u + (unsigned)lchunk * 16u;
@@ -242,14 +169,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
         const int soff_a = ((tap_kh * p.W + tap_kw) * C1 + tap_c * 64) * 2;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const unsigned vo = ((rowmask[i] >> tap) & 1u) ? rowoff[i] : 0x80000000u;  // out of range -> zero fill
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (__attribute__((address_space(3))) void*)(As + (wave * 4 + i) * 1024), 16, vo,
-                                                     soff_a, 0, 0);
+            const unsigned vo = ((rowmask[i] >> tap) & 1u) ? rowoff[i] : DMA_ZERO_FILL;  // out of range -> zero fill
+            dma16_buf(rsrc_a, As + (wave * 4 + i) * 1024, vo, soff_a);
         }
 #pragma unroll
         for (int i = 0; i < W1_PIECES; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w1, (__attribute__((address_space(3))) void*)(Ws + (wave * W1_PIECES + i) * 1024),
-                                                     16, woff1[i], ks * 128, 0, 0);
+            dma16_buf(rsrc_w1, Ws + (wave * W1_PIECES + i) * 1024, woff1[i], ks * 128);
         if (++tap_c == kpc) {
             tap_c = 0;
             if (++tap_kw == 3) { tap_kw = 0; ++tap_kh; }
@@ -259,30 +184,25 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
         unsigned char* W2s = smem + buf * STAGE_BYTES;
 #pragma unroll
         for (int i = 0; i < W2_PIECES; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w2, (__attribute__((address_space(3))) void*)(W2s + (wave * W2_PIECES + i) * 1024),
-                                                     16, woff2[i], j * (64 * C1 * 2), 0, 0);
+            dma16_buf(rsrc_w2, W2s + (wave * W2_PIECES + i) * 1024, woff2[i], j * (64 * C1 * 2));
         if constexpr (C3 > 0) {
             unsigned char* W3s = W2s + W2C_BYTES;
 #pragma unroll
             for (int i = 0; i < W3_PIECES; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w3, (__attribute__((address_space(3))) void*)(W3s + (wave * W3_PIECES + i) * 1024),
-                                                         16, woff3[i], j * 128, 0, 0);
+                dma16_buf(rsrc_w3, W3s + (wave * W3_PIECES + i) * 1024, woff3[i], j * 128);
         }
         if constexpr (SC) {
             unsigned char* Wscs = W2s + W2C_BYTES + C3 * ROW_BYTES;
 #pragma unroll
             for (int i = 0; i < SC_PIECES; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_sc, (__attribute__((address_space(3))) void*)(Wscs + (wave * SC_PIECES + i) * 1024), 16,
-                                                         woffsc[i], j * (64 * 64 * 2), 0, 0);
+                dma16_buf(rsrc_sc, Wscs + (wave * SC_PIECES + i) * 1024, woffsc[i], j * (64 * 64 * 2));
         }
         if constexpr (RC) {   // the previous block's expand and shortcut slices: [64 rows][64 k] each, rows in this kernel's ownership order
             unsigned char* Wr = W2s + W2C_BYTES + C3 * ROW_BYTES;
 #pragma unroll
             for (int i = 0; i < SC_PIECES; ++i) {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_rw, (__attribute__((address_space(3))) void*)(Wr + (wave * SC_PIECES + i) * 1024), 16,
-                                                         woffsc[i], j * (64 * 64 * 2), 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_sc, (__attribute__((address_space(3))) void*)(Wr + 8192 + (wave * SC_PIECES + i) * 1024), 16,
-                                                         woffsc[i], j * (64 * 64 * 2), 0, 0);
+                dma16_buf(rsrc_rw, Wr + (wave * SC_PIECES + i) * 1024, woffsc[i], j * (64 * 64 * 2));
+                dma16_buf(rsrc_sc, Wr + 8192 + (wave * SC_PIECES + i) * 1024, woffsc[i], j * (64 * 64 * 2));
             }
         }
     };
@@ -303,22 +223,18 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     // RDMA: wave-private residual staging: rows of this wave, whole 128-byte rows, swizzled like every other tile
     constexpr int RES_BUF = NW * 4096;
     unsigned char* const res_lds = smem + 2 * STAGE_BYTES + wave * 4096;   // + (j & 1) * RES_BUF for chunk j (RB1: one buffer)
-    const __amdgpu_buffer_rsrc_t rsrc_r = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<f16_t*>(p.res ? p.res : p.x1), 0, p.res ? (unsigned)((size_t)p.M * C2 * 2) : 0u, 0x00020000);   // rows >= M: zeros
+    const __amdgpu_buffer_rsrc_t rsrc_r = buf_rsrc(p.res ? p.res : p.x1, p.res ? (unsigned)((size_t)p.M * C2 * 2) : 0u);   // rows >= M: zeros
     const unsigned res_voff = (unsigned)((wm0 + lrow) * C2) * 2u + (unsigned)lchunk * 16u;
     auto issue_res = [&](int j) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)   // (spelled out, not dma16_buf: through the function the RB1 kernels schedule three address instructions in another order)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_r, (__attribute__((address_space(3))) void*)(res_lds + (RB1 ? 0 : (j & 1) * RES_BUF) + i * 1024), 16,
                                                      res_voff + (unsigned)(i * 8 * C2 * 2), j * 128, 0, 0);
     };
     const bool has_res = RC ? true : (!SC && p.res != nullptr && !(p.dbg & 4));
-    // Counted waits: `s_waitcnt vmcnt(N)` proves that an LDS-DMA request has landed only if the N operations allowed to stay in flight are
-    // YOUNGER LDS-DMA requests.  Stores and loads into registers retire out of order with respect to an older LDS-DMA request
-    // (tools/microbench/vmorder.hip: with 4 younger stores, or 4 younger register loads, vmcnt(4) returns while the older request's data is
-    // still on its way in > 90 % of the cases; with 4 younger LDS-DMA requests in none), so they must not be counted -- rounds 2-3 did, and
-    // were saved only by the operands having been requested a whole chunk step earlier.  Hence: N = the residual pieces of chunk j + 2 when
-    // they travel by LDS-DMA, otherwise 0; and the y stores of a step are issued AFTER its wait, so that a vmcnt(0) never waits for them.
+    // Counted waits (the rule: opd_kprims.h -- only YOUNGER LDS-DMA requests may be among the N operations a vmcnt(N) leaves in flight).
+    // Here: N = the residual pieces of chunk j + 2 when they travel by LDS-DMA, otherwise 0; and the y stores of a step are issued AFTER its
+    // wait, so that a vmcnt(0) never waits for them.
     // RB1 (one residual buffer): chunk j+1's pieces are requested in step j, right after chunk j has been read out of the buffer.  The barrier
     // wait of step j leaves those four in flight (wave-private, the youngest requests); the wait in front of step j+1's read leaves the
     // OP_PIECES operand requests of chunk j+2 in flight, which step j+1 has issued just before.  Nothing but LDS-DMA requests may sit among the

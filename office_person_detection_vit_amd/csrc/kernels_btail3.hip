@@ -10,69 +10,17 @@
 //     (3x3: 2 x 128 channels; expand chunk of 64: 2 x 32; reduce: 2 x 128), so every wave holds 2 x 8 accumulator tiles at most;
 //   * what one wave of a pair produces and the other needs as a B operand (a1: once; the 64 channels of a y chunk: per chunk) crosses
 //     through LDS in operand form (16 bytes per lane, lane-linear: 8 KiB resp. 2 KiB per wave) — fp16-rounded 16x16 accumulator tiles
-//     ARE B operands under the k-permutation of opd_permute_k32, exactly as in kernels_btail.hip;
+//     ARE B operands under the k-permutation of opd_permute_k32, which the host applies to W2 / W3 of THIS kernel only (the 64 / 128-channel
+//     kernel of kernels_btail.hip takes plain K order: it permutes the weight ROWS while staging them, `own_row`, so that its tiles come
+//     out in natural k order);
 //   * weights stream by LDS-DMA: the 3x3 loop stages 48 KiB per k-step (128 pixel rows + 256 weight rows of 64 halfs), the 16 chunk
 //     steps stage W2[64 rows][256] and W3[256 rows][64-column slice] (32 KiB each) into separate double buffers, so ONE barrier per
 //     chunk orders everything: W2 of chunk j+2 and W3 of chunk j+1 are requested right after barrier j.
 // HBM traffic per block at batch 8 (M = 33 600): 172 MB (x1 17, residual 69, y 69, z 17) against 275 MB for the three launches; a1 and
 // the re-read of y disappear, and so do two launches' fill / drain phases.
-#include <hip/hip_runtime.h>
-#include "opd_kernels.h"
-#include "opd_elem.h"
-
-typedef elem_t half8 __attribute__((ext_vector_type(8)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
-typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
+#include "opd_kprims.h"
 
 namespace {
-
-constexpr int ROW_BYTES = 128;
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * ROW_BYTES + ((chunk ^ (row & 7)) << 4); }
-
-__device__ __forceinline__ int xcd_logical_block(int bid, int nblocks) {
-    const int q = nblocks >> 3, r = nblocks & 7;
-    const int x = bid & 7, k = bid >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-}
-__device__ __forceinline__ int xcd_logical_block_rev(int bid, int nblocks) {
-    const int q = nblocks >> 3, r = nblocks & 7;
-    const int x = bid & 7, k = bid >> 3;
-    return (x < r ? x * (q + 1) + q - k : r * (q + 1) + (x - r) * q + q - 1 - k);
-}
-__device__ __forceinline__ int fdiv(const int m, const FastDiv& f) { return f.one ? m : (int)(__umulhi((unsigned)m, f.mul) >> f.shift); }
-
-__device__ __forceinline__ unsigned pack2h(float a, float b) {
-    typedef elem_t half2v __attribute__((ext_vector_type(2)));
-    half2v h;
-    h[0] = (elem_t)a;
-    h[1] = (elem_t)b;
-    unsigned u;
-    __builtin_memcpy(&u, &h, 4);
-    return u;
-}
-__device__ __forceinline__ void unpack2h(unsigned u, float& a, float& b) {
-    typedef elem_t half2v __attribute__((ext_vector_type(2)));
-    half2v h;
-    __builtin_memcpy(&h, &u, 4);
-    a = (float)h[0];
-    b = (float)h[1];
-}
-__device__ __forceinline__ half8 as_half8(unsigned a, unsigned b, unsigned c, unsigned d) {
-    uint4v u = {a, b, c, d};
-    half8 h;
-    __builtin_memcpy(&h, &u, 16);
-    return h;
-}
-template <int N_OUTSTANDING>
-__device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N_OUTSTANDING >= 0 && N_OUTSTANDING <= 63, "vmcnt range");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_OUTSTANDING) : "memory");
-}
-__device__ __forceinline__ void compiler_fence() { asm volatile("" ::: "memory"); }
-// LDS writes / reads of this wave retired, then the workgroup barrier; nothing moves across it
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // LDS map (160 KiB):  [0, 32K) W2 buffer 0 | [32K, 64K) W2 buffer 1 | [64K, 96K) W3 buffer 0 | [96K, 128K) W3 buffer 1 | [128K, 160K) y exchange x 2
 // 3x3 phase: a RING of three 48-KiB stages (pixels 16 KiB + weights 32 KiB) at [0, 144K), two k-steps of DMA in flight: a lone workgroup
@@ -108,33 +56,15 @@ __global__ __launch_bounds__(512) void btail256_kernel(BtailParams p) {
     const int lrow = lane >> 3;
     const int lchunk = (lane & 7) ^ lrow;
     const unsigned backoff = (unsigned)(p.W + 1) * (unsigned)C1 * 2u;   // pad = 1: every in-image tap gets a non-negative offset
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(p.x1)) - backoff, 0, (unsigned)((size_t)p.B * p.H * p.W * C1 * 2) + backoff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.w1), 0, (unsigned)(C1 * 9 * C1 * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.w2p), 0, (unsigned)(C2 * C1 * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(C3 ? p.w3p : p.w2p), 0, (unsigned)((C3 ? C3 : 1) * C2 * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a = buf_rsrc(reinterpret_cast<const char*>(p.x1) - backoff, (unsigned)((size_t)p.B * p.H * p.W * C1 * 2) + backoff);
+    const __amdgpu_buffer_rsrc_t rsrc_w1 = buf_rsrc(p.w1, (unsigned)(C1 * 9 * C1 * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_w2 = buf_rsrc(p.w2p, (unsigned)(C2 * C1 * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_w3 = buf_rsrc(C3 ? p.w3p : p.w2p, (unsigned)((C3 ? C3 : 1) * C2 * 2));
     unsigned rowoff[2], rowmask[2], woff1[4], woff2[4], woff3[4];
     {
         const int ohw = p.OH * p.OW;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int m = m_base + (wave * 2 + i) * 8 + lrow;
-            const bool okm = m < p.M;
-            const int mm = okm ? m : 0;
-            const int b = fdiv(mm, p.fd_ohw);
-            const int r = mm - b * ohw;
-            const int oh = fdiv(r, p.fd_ow);
-            const int ow = r - oh * p.OW;
-            rowoff[i] = (unsigned)(((b * p.H + oh * p.stride) * p.W + ow * p.stride) * C1) * 2u + (unsigned)lchunk * 16u;
-            unsigned kwmask = 0, mask = 0;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw)
-                if ((unsigned)(ow * p.stride - 1 + kw) < (unsigned)p.W) kwmask |= 1u << kw;
-#pragma unroll
-            for (int kh = 0; kh < 3; ++kh)
-                if ((unsigned)(oh * p.stride - 1 + kh) < (unsigned)p.H) mask |= kwmask << (kh * 3);
-            rowmask[i] = okm ? mask : 0u;
-        }
+        for (int i = 0; i < 2; ++i) tail_row_coords<C1>(p, m_base + (wave * 2 + i) * 8 + lrow, ohw, lchunk, rowoff[i], rowmask[i]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int q = wave * 4 + i;
@@ -162,10 +92,10 @@ __global__ __launch_bounds__(512) void btail256_kernel(BtailParams p) {
     auto issue_piece = [&](int i, int stage_off) {   // i = 0, 1: pixel rows; 2 .. 5: weight rows
         unsigned char* As = smem + stage_off;
         if (i < 2) {
-            const unsigned vo = ((rowmask[i] >> is_tap) & 1u) ? rowoff[i] : 0x80000000u;   // out of range -> zero fill
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (__attribute__((address_space(3))) void*)(As + (wave * 2 + i) * 1024), 16, vo, is_soff_a, 0, 0);
+            const unsigned vo = ((rowmask[i] >> is_tap) & 1u) ? rowoff[i] : DMA_ZERO_FILL;   // out of range -> zero fill
+            dma16_buf(rsrc_a, As + (wave * 2 + i) * 1024, vo, is_soff_a);
         } else {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w1, (__attribute__((address_space(3))) void*)(As + 16384 + (wave * 4 + i - 2) * 1024), 16, woff1[i - 2], is_ks * 128, 0, 0);
+            dma16_buf(rsrc_w1, As + 16384 + (wave * 4 + i - 2) * 1024, woff1[i - 2], is_ks * 128);
         }
     };
     auto issue_main = [&](int ks, int stage_off) {
@@ -175,12 +105,12 @@ __global__ __launch_bounds__(512) void btail256_kernel(BtailParams p) {
     };
     auto issue_w2_piece = [&](int j, int i) {
         unsigned char* dst = smem + W2BUF + (j & 1) * 32768;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w2, (__attribute__((address_space(3))) void*)(dst + (wave * 4 + i) * 1024), 16, woff2[i], j * (64 * C1 * 2), 0, 0);
+        dma16_buf(rsrc_w2, dst + (wave * 4 + i) * 1024, woff2[i], j * (64 * C1 * 2));
     };
     auto issue_w3_piece = [&](int j, int i) {
         if constexpr (C3 > 0) {
             unsigned char* dst = smem + W3BUF + (j & 1) * 32768;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w3, (__attribute__((address_space(3))) void*)(dst + (wave * 4 + i) * 1024), 16, woff3[i], j * 128, 0, 0);
+            dma16_buf(rsrc_w3, dst + (wave * 4 + i) * 1024, woff3[i], j * 128);
         }
     };
 
@@ -191,8 +121,8 @@ __global__ __launch_bounds__(512) void btail256_kernel(BtailParams p) {
     const int pr_m = m_base + pair * 32 + (g & 1) * 16 + li;
     const bool has_res = p.res != nullptr && !(p.dbg & 4);
     const unsigned y_bytes = (unsigned)((size_t)p.M * C2 * 2);
-    const __amdgpu_buffer_rsrc_t rsrc_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(has_res ? p.res : p.x1), 0, has_res ? y_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (p.dbg & 2) ? 0u : y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_r = buf_rsrc(has_res ? p.res : p.x1, has_res ? y_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t rsrc_y = buf_rsrc(p.y, (p.dbg & 2) ? 0u : y_bytes);
     const unsigned pr_off = (unsigned)pr_m * (unsigned)(C2 * 2) + (unsigned)(half * 32 + (g >> 1) * 8) * 2u;   // bytes; rows >= M land beyond y_bytes
     auto load_res = [&](int j, uint4v (&r)[2]) {
 #pragma unroll
@@ -487,7 +417,7 @@ __global__ __launch_bounds__(512) void btail256_kernel(BtailParams p) {
 
     // ---- z = relu(c0') -----------------------------------------------------------------------------------------------------------
     if constexpr (C3 > 0) {
-        const __amdgpu_buffer_rsrc_t rsrc_z = __builtin_amdgcn_make_buffer_rsrc(p.z, 0, (p.dbg & 2) ? 0u : (unsigned)((size_t)p.M * C3 * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_z = buf_rsrc(p.z, (p.dbg & 2) ? 0u : (unsigned)((size_t)p.M * C3 * 2));
         const unsigned zoff = (unsigned)pr_m * (unsigned)(C3 * 2) + (unsigned)(half * 128 + (g >> 1) * 8) * 2u;
 #pragma unroll
         for (int nt = 0; nt < 8; ++nt) {

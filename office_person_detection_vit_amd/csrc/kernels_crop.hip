@@ -14,7 +14,7 @@
 #include <limits.h>
 
 #include "opd_crop.h"
-#include "opd_kernels.h"
+#include "opd_kprims.h"
 
 #pragma clang fp contract(off)
 

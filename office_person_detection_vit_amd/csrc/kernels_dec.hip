@@ -36,12 +36,7 @@
 // out[row li][n0 + 4g + r], r = 0 .. 3.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include "opd_kernels.h"
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float float2v __attribute__((ext_vector_type(2)));
+#include "opd_kprims.h"
 
 namespace {
 
@@ -116,9 +111,6 @@ __device__ __forceinline__ float acc3_get(const Acc3& a, const int j, const int 
 // registers retire out of order with respect to an older request (tools/microbench/vmorder.hip): they are never part of a count, and as
 // extra outstanding operations they only make a wait longer than necessary, never shorter.  Every index is a compile-time constant after
 // unrolling.
-__device__ __forceinline__ void dma1k(const unsigned char* src_lane, unsigned char* slot) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_lane, (__attribute__((address_space(3))) void*)slot, 16, 0, 0);
-}
 __device__ __forceinline__ void wait_vm(const int n) {
     switch (n) {
         case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
@@ -144,7 +136,7 @@ struct PieceRing {
     template <typename Src>
     __device__ __forceinline__ void prime(Src&& src) {
 #pragma unroll
-        for (int n = 0; n < (R < TOTAL ? R : TOTAL); ++n) dma1k(src(n) + lane16, ring + n * 1024);
+        for (int n = 0; n < (R < TOTAL ? R : TOTAL); ++n) dma16(src(n) + lane16, ring + n * 1024);
     }
     __device__ __forceinline__ void wait(const int first, const int last) const { wait_vm((TOTAL < R + first ? TOTAL : R + first) - 1 - last); }
     template <typename Src>
@@ -152,7 +144,7 @@ struct PieceRing {
         DEC_LGKM0();
 #pragma unroll
         for (int n = first; n < first + count; ++n)
-            if (n + R < TOTAL) dma1k(src(n + R) + lane16, ring + ((n + R) % R) * 1024);
+            if (n + R < TOTAL) dma16(src(n + R) + lane16, ring + ((n + R) % R) * 1024);
     }
     __device__ __forceinline__ const unsigned char* slot(const int n) const { return ring + (n % R) * 1024; }
 };

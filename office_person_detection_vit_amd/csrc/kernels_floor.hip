@@ -20,17 +20,11 @@
 #include <limits.h>
 
 #include "opd_floor.h"
-#include "opd_kernels.h"
+#include "opd_kprims.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);   // a + b == b + a: all 64 lanes end with the same bits
-    return v;
-}
 
 __device__ __forceinline__ unsigned long long wave_xor(unsigned long long v) {
 #pragma unroll

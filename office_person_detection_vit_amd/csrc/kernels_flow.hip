@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "opd_flow.h"
-#include "opd_kernels.h"
+#include "opd_kprims.h"
 
 namespace {
 
@@ -81,12 +81,6 @@ __global__ __launch_bounds__(256) void flow_pyrdown_kernel(const uint8_t* __rest
 #pragma unroll
     for (int o = 0; o < 4; ++o) out |= ((acc[o] + 128u) >> 8) << (8 * o);   // (columns >= ow of the last group: scratch behind the row)
     *reinterpret_cast<unsigned*>(dst + (size_t)oy * dpitch + 4 * t) = out;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);   // a + b == b + a: all 64 lanes end with the same bits
-    return v;
 }
 
 enum { PATCH_LD = OPD_FLOW_MAX_WIN + 4, DERIV_LD = OPD_FLOW_MAX_WIN + 2, SAMPLES = (OPD_FLOW_MAX_WIN * OPD_FLOW_MAX_WIN + 63) / 64 };

@@ -16,34 +16,12 @@
 //
 // MFMA operand orientation: the WEIGHT fragment is the A operand and the ACTIVATION fragment the B operand, so the
 // accumulator holds D[row = n][col = m]: lane l owns 4 consecutive n for one m (col = l & 15, row = 4*(l >> 4) + reg).
-#include <hip/hip_runtime.h>
-#include "opd_kernels.h"
-#include "opd_elem.h"
-
-typedef elem_t half8 __attribute__((ext_vector_type(8)));
-typedef float float4v __attribute__((ext_vector_type(4)));
+#include "opd_kprims.h"
 
 namespace {
 
 constexpr int BM = 128;
-constexpr int BK = 64;           // halfs per k-step = 128 bytes per tile row
-constexpr int ROW_BYTES = BK * 2;
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * ROW_BYTES + ((chunk ^ (row & 7)) << 4); }
-
-// XCD-aware block -> tile map (cdna_hip_programming.md T1, bijective form).  Workgroups are dealt round-robin over the 8
-// XCDs (blocks b and b+8 share an XCD and its private 4 MiB L2), so hand each XCD a CONTIGUOUS range of logical tile
-// ids: the n-tiles of one m-tile (which re-read the same activation rows) then run on one XCD, back to back, and the
-// rows are fetched from HBM / Infinity Cache once instead of once per n-tile.  Speed only, never correctness.
-__device__ __forceinline__ int xcd_logical_block(int bid, int nblocks) {
-    const int q = nblocks >> 3, r = nblocks & 7;
-    const int x = bid & 7, k = bid >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-}
-
-__device__ __forceinline__ int fdiv(const int m, const FastDiv& f) {   // m >= 0
-    return f.one ? m : (int)(__umulhi((unsigned)m, f.mul) >> f.shift);
-}
+constexpr int BK = 64;           // halfs per k-step = 128 bytes per tile row (ROW_BYTES)
 
 __device__ __forceinline__ uint4 ldg16(const void* p) { return *reinterpret_cast<const uint4*>(p); }
 __device__ __forceinline__ uint2 ldg8(const void* p) { return *reinterpret_cast<const uint2*>(p); }
@@ -59,30 +37,6 @@ __device__ __forceinline__ uint2 ldg8(const void* p) { return *reinterpret_cast<
 //   * accumulators go bias -> (+residual) -> ReLU -> fp16 in registers; v_permlane16_swap pairs the 4-wide n-quads of
 //     two m-tiles into 8 consecutive channels per lane, so stores (and residual loads) are 16 bytes per lane.
 // ---------------------------------------------------------------------------------------------------------------------
-typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ unsigned pack2h(float a, float b) {
-    typedef elem_t half2v __attribute__((ext_vector_type(2)));
-    half2v h;
-    h[0] = (elem_t)a;
-    h[1] = (elem_t)b;
-    unsigned u;
-    __builtin_memcpy(&u, &h, 4);
-    return u;
-}
-__device__ __forceinline__ void unpack2h(unsigned u, float& a, float& b) {
-    typedef elem_t half2v __attribute__((ext_vector_type(2)));
-    half2v h;
-    __builtin_memcpy(&h, &u, 4);
-    a = (float)h[0];
-    b = (float)h[1];
-}
-
 // Accumulators start from the bias (vector or row-periodic), so the bias loads overlap the first tile's DMA instead of
 // sitting on the epilogue's critical path.
 template <int NT, int MT = 4>
@@ -378,36 +332,24 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(ConvGemmParams p)
         const f16_t* xsrc = p.x;
         if constexpr (PW)
             if (p.x_alt && (n_base % p.alt_mod) >= p.alt_cols) xsrc = p.x_alt;   // (workgroup-uniform: a column tile lies in one group)
-        rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(xsrc)) - backoff, 0, a_bytes, 0x00020000);
-        rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.w), 0, (unsigned)((size_t)p.N * p.K * 2), 0x00020000);
+        rsrc_a = buf_rsrc(reinterpret_cast<const char*>(xsrc) - backoff, a_bytes);
+        rsrc_b = buf_rsrc(p.w, (unsigned)((size_t)p.N * p.K * 2));
         const int ohw = p.OH * p.OW;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const int m = m_base + (wave * MT + i) * 8 + lrow;
-            const bool okm = m < p.M;
-            if constexpr (PW) {   // row m of [M][Cin]; rows >= M read zeros through the descriptor's bounds check
-                rowoff[i] = okm ? (unsigned)m * (unsigned)(p.Cin * 2) + (unsigned)lchunk * 16u : 0x80000000u;
-                rowmask[i] = 1u;
+            if constexpr (PW) {
+                conv_row_coords<true>(p, m, ohw, lchunk, rowoff[i], rowmask[i]);
                 continue;
             }
-            const int mm = okm ? m : 0;
-            const int b = fdiv(mm, p.fd_ohw);
-            const int r = mm - b * ohw;
-            const int oh = fdiv(r, p.fd_ow);
-            const int ow = r - oh * p.OW;
+            const bool okm = m < p.M;
+            const RowPixel px = conv_row_pixel(p, okm ? m : 0, ohw);
             // stem == 2: padded NHWC4 image (8 bytes / pixel); a k-step is 2 filter rows x 8 pixels, so the lane's 16-byte
             // chunk sits at (row lchunk>>2, pixel pair lchunk&3) of the window
-            rowoff[i] = stem2 ? (unsigned)((b * p.H + oh * 2) * p.W + ow * 2) * 8u + (unsigned)((lchunk >> 2) * p.W) * 8u + (unsigned)(lchunk & 3) * 16u
-                              : (unsigned)(((b * p.H + oh * p.stride) * p.W + ow * p.stride) * p.Cin) * 2u + (unsigned)lchunk * 16u;
-            // separable validity in closed form (no loops, no branches): the valid kw form a contiguous range [lo_w, hi_w], likewise kh;
-            // the row bits are replicated to every valid kh by a multiplication with the matching bits of p.tap_rep = sum 1 << kh*KW
-            const int iw0 = ow * p.stride - p.pad, ih0 = oh * p.stride - p.pad;
-            const int lo_w = max(0, -iw0), hi_w = min(p.KW - 1, p.W - 1 - iw0);
-            const int lo_h = max(0, -ih0), hi_h = min(p.KH - 1, p.H - 1 - ih0);
-            auto below = [](const int n) { return n > 0 ? 0xffffffffu >> (32 - n) : 0u; };   // bits [0, n), n <= 32
-            const unsigned kwmask = hi_w >= lo_w ? below(hi_w + 1) & ~below(lo_w) : 0u;
-            const unsigned hsel = hi_h >= lo_h ? below((hi_h + 1) * p.KW) & ~below(lo_h * p.KW) : 0u;
-            rowmask[i] = okm ? kwmask * (p.tap_rep & hsel) : 0u;
+            rowoff[i] = stem2 ? (unsigned)((px.b * p.H + px.oh * 2) * p.W + px.ow * 2) * 8u + (unsigned)((lchunk >> 2) * p.W) * 8u + (unsigned)(lchunk & 3) * 16u
+                              : conv_row_off(p, px, lchunk);
+            const unsigned mask = conv_tap_mask(p, px);
+            rowmask[i] = okm ? mask : 0u;
         }
 #pragma unroll
         for (int i = 0; i < B_PIECES; ++i)
@@ -419,7 +361,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(ConvGemmParams p)
     if constexpr (DUAL) {
         static_assert(BUF, "the dual-source form uses buffer-descriptor staging");
         nk1 = p.K1 / BK;
-        rsrc_a2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.x2), 0, (unsigned)((size_t)p.B * p.H2 * p.W2 * p.Cin2 * 2), 0x00020000);
+        rsrc_a2 = buf_rsrc(p.x2, (unsigned)((size_t)p.B * p.H2 * p.W2 * p.Cin2 * 2));
         const int ohw = p.OH * p.OW;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
@@ -430,7 +372,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(ConvGemmParams p)
             const int oh = fdiv(r, p.fd_ow);
             const int ow = r - oh * p.OW;
             rowoff2[i] = m < p.M ? (unsigned)(((b * p.H2 + oh * p.stride2) * p.W2 + ow * p.stride2) * p.Cin2) * 2u + (unsigned)lchunk * 16u
-                                 : 0x80000000u;
+                                 : DMA_ZERO_FILL;
         }
     }
 
@@ -456,20 +398,17 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(ConvGemmParams p)
             if (DUAL && ks >= nk1) {   // second source: channels 64 (ks - nk1) .. of the strided 1x1 input
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a2, (__attribute__((address_space(3))) void*)(As + (wave * MT + i) * 1024),
-                                                             16, rowoff2[i], (ks - nk1) * (BK * 2), 0, 0);
+                    dma16_buf(rsrc_a2, As + (wave * MT + i) * 1024, rowoff2[i], (ks - nk1) * (BK * 2));
             } else if (!(p.dbg & 8))
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
-                const unsigned vo = (PW || ((rowmask[i] >> tap) & 1u)) ? rowoff[i] : 0x80000000u;  // out of range -> zeros
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (__attribute__((address_space(3))) void*)(As + (wave * MT + i) * 1024),
-                                                         16, vo, soff_a, 0, 0);
+                const unsigned vo = (PW || ((rowmask[i] >> tap) & 1u)) ? rowoff[i] : DMA_ZERO_FILL;  // out of range -> zeros
+                dma16_buf(rsrc_a, As + (wave * MT + i) * 1024, vo, soff_a);
             }
             if (!(p.dbg & 16))
 #pragma unroll
             for (int i = 0; i < B_PIECES; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (__attribute__((address_space(3))) void*)(Bs + (wave * B_PIECES + i) * 1024),
-                                                         16, woff[i], ks * (BK * 2), 0, 0);
+                dma16_buf(rsrc_b, Bs + (wave * B_PIECES + i) * 1024, woff[i], ks * (BK * 2));
         } else {
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
@@ -786,9 +725,9 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_kernel(StemPoolParams p) {
     const __amdgpu_buffer_rsrc_t rsrc_a =
         // (the frames' byte count rounded up to whole dwords: the bounds check works on dwords, and the last one may hold the final
         //  pixel's bytes next to <= 3 bytes of the allocation's own padding)
-        U8 ? __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.frames), 0, (unsigned)(((size_t)p.B * p.H * p.W * 3 + 3) & ~(size_t)3), 0x00020000)
-           : __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.x4p), 0, (unsigned)((size_t)p.B * p.Hp * p.Wp * 8), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.w), 0, 64 * 256 * 2, 0x00020000);
+        U8 ? buf_rsrc(p.frames, (unsigned)(((size_t)p.B * p.H * p.W * 3 + 3) & ~(size_t)3))
+           : buf_rsrc(p.x4p, (unsigned)((size_t)p.B * p.Hp * p.Wp * 8));
+    const __amdgpu_buffer_rsrc_t rsrc_b = buf_rsrc(p.w, 64 * 256 * 2);
     const int vh = U8 ? (p.valid_hw ? p.valid_hw[2 * b] : p.H) : 0, vw = U8 ? (p.valid_hw ? p.valid_hw[2 * b + 1] : p.W) : 0;
 
     // ---- weights: 28 pieces of 16 rows x 64 B (piece q: filter row q>>2, output channels 16*(q&3)..+15), 7 per wave ------
@@ -799,8 +738,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_kernel(StemPoolParams p) {
             const int q = wave * 7 + i;
             const int kh = q >> 2, n = (q & 3) * 16 + wrow;
             const int chunk = wslot ^ ((0 - (n >> 2)) & 3);       // source-side swizzle of a 64-byte row
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (__attribute__((address_space(3))) void*)(Wl + q * 1024), 16,
-                                                     (unsigned)((n * 256 + kh * 32 + chunk * 8) * 2), 0, 0, 0);
+            dma16_buf(rsrc_b, Wl + q * 1024, (unsigned)((n * 256 + kh * 32 + chunk * 8) * 2), 0);
         }
     }
     // ---- input patch: 525 chunks of 16 B (2 pixels); chunk c sits at patch row c / 35, pixel pair c % 35 ------------------
@@ -819,9 +757,8 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_kernel(StemPoolParams p) {
             if (q < 9) {
                 const int iy = iy0 + prow[i], ix = ix0 + 2 * pcol[i];
                 const bool ok = prow[i] < 15 && (unsigned)iy < (unsigned)p.Hp && ix >= 0 && ix < p.Wp;
-                const unsigned off = ok ? (unsigned)(((b * p.Hp + iy) * p.Wp + ix) * 8) : 0x80000000u;   // out of range -> zeros
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (__attribute__((address_space(3))) void*)(Pin + buf * STEM_PATCH + q * 1024),
-                                                         16, off, 0, 0, 0);
+                const unsigned off = ok ? (unsigned)(((b * p.Hp + iy) * p.Wp + ix) * 8) : DMA_ZERO_FILL;   // out of range -> zeros
+                dma16_buf(rsrc_a, Pin + buf * STEM_PATCH + q * 1024, off, 0);
             }
         }
     };
@@ -839,7 +776,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool2_kernel(StemPoolParams p) {
             const bool ok = (tid >> 6) + 4 * i < 9 && prow[i] < 15 && (unsigned)y < (unsigned)vh && x + 1 >= 0 && x < vw;
             // (a pair that starts left of the image, x = -1, is fetched from its second pixel: byte addresses never go negative
             //  -- hipcc merges the three loads into one dwordx3, and a start before the buffer would zero all of it)
-            const unsigned a = ok ? (unsigned)((((b * p.H + y) * p.W + (x < 0 ? 0 : x)) * 3) & ~3) : 0x80000000u;
+            const unsigned a = ok ? (unsigned)((((b * p.H + y) * p.W + (x < 0 ? 0 : x)) * 3) & ~3) : DMA_ZERO_FILL;
 #pragma unroll
             for (int d = 0; d < 3; ++d) pre[i][d] = __builtin_amdgcn_raw_buffer_load_b32(rsrc_a, a + 4u * d, 0, 0);   // past the end: zeros
         }
@@ -1017,9 +954,7 @@ hipError_t OPD_SYM(opd_launch_conv_gemm)(const ConvGemmParams& p_in, hipStream_t
     p.fd_ohw = opd_make_fastdiv((unsigned)p.OH * (unsigned)p.OW);
     p.fd_ow = opd_make_fastdiv((unsigned)p.OW);
     p.fd_period = opd_make_fastdiv((unsigned)(p.bias_period > 0 ? p.bias_period : 1));
-    p.tap_rep = 0u;
-    if (p.KH >= 1 && p.KW >= 1 && p.KH * p.KW <= 32)
-        for (int kh = 0; kh < p.KH; ++kh) p.tap_rep |= 1u << (kh * p.KW);
+    p.tap_rep = opd_tap_rep(p.KH, p.KW);
     // host-side shape contract of the kernel (checked before every launch: a violated assumption would fault the GPU)
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.N % 64) != 0 || (p.K % BK) != 0) return hipErrorInvalidValue;
     if (p.stem == 2) {  // padded-NHWC4 stem through the LDS-DMA kernel: [B][H = 2*OH+6][W = 2*OW+6][4], zero borders

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/opd_detr.h"
-#include "opd_kernels.h"
+#include "opd_kprims.h"
 
 namespace {
 
@@ -129,12 +129,6 @@ __global__ __launch_bounds__(256) void color_hist_kernel(const ColorParams p) {
     }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ __launch_bounds__(64) void color_finish_kernel(const ColorParams p) {
     ColorCrop c;
     if (!load_crop(p, blockIdx.x, &c)) return;
@@ -155,7 +149,7 @@ __global__ __launch_bounds__(64) void color_finish_kernel(const ColorParams p) {
     double ss = 0.0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) ss += (double)v[k] * (double)v[k];
-    const double den = sqrt(wave_sum_f64(ss)) + 1e-8;
+    const double den = sqrt(wave_sum(ss)) + 1e-8;
     float* out = p.out + (size_t)c.row * OPD_COLOR_DIM;
 #pragma unroll
     for (int k = 0; k < 4; ++k) out[l + 64 * k] = (float)((double)v[k] / den);   // (entries 198 .. 255: 0 / den)

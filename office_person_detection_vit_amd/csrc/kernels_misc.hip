@@ -9,12 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <vector>
-#include "opd_kernels.h"
-#include "opd_elem.h"
-
-typedef elem_t half8 __attribute__((ext_vector_type(8)));
-typedef elem_t half4 __attribute__((ext_vector_type(4)));
-typedef float float4v __attribute__((ext_vector_type(4)));
+#include "opd_kprims.h"
 
 namespace {
 
@@ -59,12 +54,11 @@ __global__ void preprocess_u8_kernel(const uint8_t* __restrict__ in, f16_t* __re
         }
     }
     if (xg * 4 + 3 < Wp && (Wp & 1) == 0) {   // rows are 8 Wp bytes long: the 32-byte groups are 16-byte aligned when Wp is even ...
-        typedef elem_t half8v __attribute__((ext_vector_type(8)));
-        half8v a, c;
+        half8 a, c;
 #pragma unroll
         for (int q = 0; q < 4; ++q) { a[q] = o[0][q]; a[4 + q] = o[1][q]; c[q] = o[2][q]; c[4 + q] = o[3][q]; }
-        *reinterpret_cast<half8v*>(orow + (size_t)xg * 16) = a;
-        *reinterpret_cast<half8v*>(orow + (size_t)xg * 16 + 8) = c;
+        *reinterpret_cast<half8*>(orow + (size_t)xg * 16) = a;
+        *reinterpret_cast<half8*>(orow + (size_t)xg * 16 + 8) = c;
     } else {                                    // ... otherwise (and for the last partial group) pixel by pixel
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -170,12 +164,6 @@ __global__ void maxpool_kernel(const f16_t* __restrict__ x, f16_t* __restrict__ 
     *reinterpret_cast<half8*>(out + (((size_t)b * OH + oh) * OW + ow) * C + c8 * 8) = m;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // One wave per row of 256: lane holds 4 consecutive elements; two-pass (mean, then centred variance) in fp32.
 __global__ __launch_bounds__(256) void layernorm256_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float* __restrict__ y,
@@ -204,7 +192,7 @@ __global__ __launch_bounds__(256) void layernorm256_kernel(const float* __restri
 }
 
 // y[row][:] = c[:] for every row (fp32 and an fp16 copy): the decoder's state after the self-attention block of layer 0, which does
-// not depend on the input (opd_model.cpp::build_weights, "dec0").
+// not depend on the input (opd_weights.cpp::build_weights, "dec0").
 __global__ __launch_bounds__(256) void broadcast_rows256_kernel(const float* __restrict__ c, float* __restrict__ y, f16_t* __restrict__ y16, int rows) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -286,7 +274,6 @@ __global__ void gemm_f32_kernel(const float* __restrict__ A, const float* __rest
 // 1024-thread block, every weight loaded once per 4 rows); what remains is six L2 round trips for the weights.
 constexpr int HEAD_ROWS = 16;
 constexpr int HEAD_LD = 260;   // fp32 words per LDS row (256 + 4: rows 8 apart do not share a bank)
-typedef float float4m __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(512) void heads_kernel(HeadParams p) {
     __shared__ float h[HEAD_ROWS][HEAD_LD];
@@ -317,12 +304,12 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadParams p) {
         };
         if (p.partials) {   // fused decoder: the last layer's FFN arrives as partial sums (kernels_dec.hip::dec_ffn_kernel): + b2, summed in order, LN3
             const size_t rc = (size_t)(row0 + r < p.rows ? row0 + r : p.rows - 1) * 256 + c0;
-            float4m pa[16], pb[16];
+            float4v pa[16], pb[16];
 #pragma unroll
             for (int sp = 0; sp < 16; ++sp) {   // every slab requested before the first one is needed (a dependent load costs ~1 us)
                 const float* ps = p.partials + (size_t)(sp < p.nsplit ? sp : p.nsplit - 1) * p.rows * 256 + rc;
-                pa[sp] = *reinterpret_cast<const float4m*>(ps);
-                pb[sp] = *reinterpret_cast<const float4m*>(ps + 4);
+                pa[sp] = *reinterpret_cast<const float4v*>(ps);
+                pb[sp] = *reinterpret_cast<const float4v*>(ps + 4);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -352,7 +339,7 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadParams p) {
         for (int nt = wave; nt < ntiles; nt += 16) {   // this wave's tiles nt and nt + 8, interleaved (two accumulator chains)
             const int nA = nt * 16 + li, nB = (nt + 8) * 16 + li;
             const bool okA = nA < N, okB = nt + 8 < ntiles && nB < N;
-            float4m accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
+            float4v accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
             // 2 x 32 weight operands (half the reduction of the tile pair) are requested before their first MFMA: the kernel is a
             // latency chain (every weight comes from L2, ~1 us away), so two round trips per tile pair instead of sixteen (46 us)
 #pragma unroll 1
@@ -376,19 +363,19 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadParams p) {
         }
     };
     // class logits: lane holds channels n .. n + 3 of row li
-    layer(h, p.wc, p.ncls, (p.ncls + 15) / 16, [&](const int n, const float4m acc) {
+    layer(h, p.wc, p.ncls, (p.ncls + 15) / 16, [&](const int n, const float4v acc) {
         if (row0 + li < p.rows)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (n + r < p.ncls) p.logits[(size_t)(row0 + li) * p.ncls + n + r] = acc[r] + p.bc[n + r];
     });
     // box MLP: 256 -> 256 -> 256 -> 4, ReLU between, sigmoid at the end
-    layer(h, p.w1, 256, 16, [&](const int n, const float4m acc) {
+    layer(h, p.w1, 256, 16, [&](const int n, const float4v acc) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) { const float v = acc[r] + p.b1[n + r]; t1[li][n + r] = v > 0.f ? v : 0.f; }
     });
     __syncthreads();   // t1 complete; every wave is done reading h
-    layer(t1, p.w2, 256, 16, [&](const int n, const float4m acc) {
+    layer(t1, p.w2, 256, 16, [&](const int n, const float4v acc) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) { const float v = acc[r] + p.b2[n + r]; h[li][n + r] = v > 0.f ? v : 0.f; }   // h is free: second hidden layer
     });
@@ -694,14 +681,13 @@ static __global__ __launch_bounds__(256) void reduce_act16_kernel(const float* _
         a += *reinterpret_cast<const float4v*>(partials + z * slab_stride + o);
         b += *reinterpret_cast<const float4v*>(partials + z * slab_stride + o + 4);
     }
-    typedef elem_t half8v __attribute__((ext_vector_type(8)));
-    half8v h;
+    half8 h;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         h[r] = (elem_t)(relu && a[r] < 0.f ? 0.f : a[r]);
         h[4 + r] = (elem_t)(relu && b[r] < 0.f ? 0.f : b[r]);
     }
-    *reinterpret_cast<half8v*>(reinterpret_cast<elem_t*>(out) + o) = h;
+    *reinterpret_cast<half8*>(reinterpret_cast<elem_t*>(out) + o) = h;
 }
 
 // Diagnostic tap (opd_test_set_taps): position-weighted 64-bit sum of a buffer's 32-bit words, one partial per block.

@@ -16,16 +16,9 @@
 #include <math.h>
 
 #include "opd_clip.h"
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float4v __attribute__((ext_vector_type(4)));
+#include "opd_kprims.h"
 
 namespace {
-
-__device__ __forceinline__ float4v mfma16(const half8& a, const half8& b, const float4v& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 
 // ---- pre-processing -------------------------------------------------------------------------------------------------------------------
 // grid (224 output rows, crops), block 224 (output columns): one output pixel of the centre window per thread (opd_crop.h), stored into

@@ -17,23 +17,14 @@
 // three-stage ring: the input projection), enc_ffn_kernel (round 4: everything behind an encoder layer's attention -- output projection +
 // LayerNorm + fc1 + ReLU + fc2 + LayerNorm -- in one launch, weights as per-wave fragment streams through wave-private rings) and
 // gemm_k256_kernel (small-M linears of the unfused decoder chain).
-#include <hip/hip_runtime.h>
-#include "opd_kernels.h"
-#include "opd_elem.h"
-
-typedef elem_t half8 __attribute__((ext_vector_type(8)));
-typedef elem_t half4 __attribute__((ext_vector_type(4)));
-typedef float float4v __attribute__((ext_vector_type(4)));
+#include "opd_kprims.h"
 
 namespace {
 
-constexpr int ROW_BYTES = 128;
 constexpr int TM = 32;                       // rows per workgroup
 constexpr int A_BYTES = TM * ROW_BYTES;      // 4 KiB
 constexpr int W_BYTES = 256 * ROW_BYTES;     // 32 KiB
 constexpr int STAGE_BYTES = A_BYTES + W_BYTES;
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * ROW_BYTES + ((chunk ^ (row & 7)) << 4); }
 
 __global__ __launch_bounds__(256, 2) void gemm_ln256_kernel(GemmLnParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -47,19 +38,18 @@ __global__ __launch_bounds__(256, 2) void gemm_ln256_kernel(GemmLnParams p) {
     const int lrow = lane >> 3, lchunk = (lane & 7) ^ lrow;
 
     // rows >= M fall outside the activation descriptor: zero fill
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.x), 0, (unsigned)((size_t)p.M * p.K * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.w), 0, (unsigned)((size_t)256 * p.K * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buf_rsrc(p.x, (unsigned)((size_t)p.M * p.K * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_w = buf_rsrc(p.w, (unsigned)((size_t)256 * p.K * 2));
     const unsigned xoff = (unsigned)((m_base + wave * 8 + lrow) * p.K) * 2u + (unsigned)lchunk * 16u;   // activation piece `wave`
     const unsigned woff = (unsigned)((wave * 64 + lrow) * p.K) * 2u + (unsigned)lchunk * 16u;           // weight rows 64w + 8i + lrow
     const unsigned wstep = (unsigned)(8 * p.K) * 2u;
     auto issue = [&](int ks, int buf) {
         unsigned char* As = smem + buf * STAGE_BYTES;
         unsigned char* Ws = As + A_BYTES;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(As + wave * 1024), 16, xoff, ks * 128, 0, 0);
+        dma16_buf(rsrc_x, As + wave * 1024, xoff, ks * 128);
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (__attribute__((address_space(3))) void*)(Ws + (wave * 8 + i) * 1024), 16,
-                                                     woff + (unsigned)i * wstep, ks * 128, 0, 0);
+            dma16_buf(rsrc_w, Ws + (wave * 8 + i) * 1024, woff + (unsigned)i * wstep, ks * 128);
     };
 
     issue(0, 0);
@@ -179,23 +169,21 @@ __global__ __launch_bounds__(64 * OS_NW, 1) void gemm_ln256_os_kernel(GemmLnPara
     constexpr int NT = 256 / 16 / OS_NW;     // column tiles per wave (2)
     constexpr int WP = 256 / 8 / OS_NW;      // weight pieces per wave and sub-tile (4)
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.x), 0, (unsigned)((size_t)p.M * 256 * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.w), 0, (unsigned)(256 * 256 * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buf_rsrc(p.x, (unsigned)((size_t)p.M * 256 * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_w = buf_rsrc(p.w, (unsigned)(256 * 256 * 2));
     // weights: wave w stages its own 32 rows (4 pieces) of each of the 4 sub-tiles; activations: 6 pieces per sub-tile, 24 in all,
     // 3 per wave (piece q = 3 wave + i -> sub-tile q / 6, rows 8 (q % 6) ..); rows >= M are outside the descriptor: zero fill
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
 #pragma unroll
         for (int i = 0; i < WP; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (__attribute__((address_space(3))) void*)(Ws + t * OS_WSUB + (wave * WP + i) * 1024), 16,
-                                                     (unsigned)((wave * (8 * WP) + i * 8 + lrow) * 256) * 2u + (unsigned)lchunk * 16u, t * 128, 0, 0);
+            dma16_buf(rsrc_w, Ws + t * OS_WSUB + (wave * WP + i) * 1024, (unsigned)((wave * (8 * WP) + i * 8 + lrow) * 256) * 2u + (unsigned)lchunk * 16u, t * 128);
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int q = wave * 3 + i, t = q / 6, r = (q % 6) * 8 + lrow;
         const int m = m_base + r;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(Xs + t * OS_XSUB + (q % 6) * 1024), 16,
-                                                 m < p.M ? (unsigned)(m * 256) * 2u + (unsigned)lchunk * 16u : 0x80000000u, t * 128, 0, 0);
+        dma16_buf(rsrc_x, Xs + t * OS_XSUB + (q % 6) * 1024, m < p.M ? (unsigned)(m * 256) * 2u + (unsigned)lchunk * 16u : DMA_ZERO_FILL, t * 128);
     }
     float4v acc[NT][3];
 #pragma unroll
@@ -435,8 +423,8 @@ __global__ __launch_bounds__(64 * RG_NW, 1) void gemm_ln256_ring_kernel(GemmLnPa
     constexpr int WP = 256 / 8 / RG_NW;          // weight pieces per wave and k-step (4)
     constexpr int PIECES = WP + 1;               // + one piece of the activation tile
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.x), 0, (unsigned)((size_t)p.M * p.K * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.w), 0, (unsigned)((size_t)256 * p.K * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buf_rsrc(p.x, (unsigned)((size_t)p.M * p.K * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_w = buf_rsrc(p.w, (unsigned)((size_t)256 * p.K * 2));
     // per k-step every wave issues exactly PIECES pieces: activation rows 8 wave + lrow (rows >= M fall outside the descriptor: zero
     // fill) and the WP pieces of its own 32 weight rows
     const unsigned xoff = (unsigned)((m_base + wave * 8 + lrow) * p.K) * 2u + (unsigned)lchunk * 16u;
@@ -445,11 +433,10 @@ __global__ __launch_bounds__(64 * RG_NW, 1) void gemm_ln256_ring_kernel(GemmLnPa
     auto issue = [&](int ks) {
         unsigned char* Xs = smem + (ks % RG_NS) * RG_STAGE;
         unsigned char* Ws = Xs + RG_XSUB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(Xs + wave * 1024), 16, xoff, ks * 128, 0, 0);
+        dma16_buf(rsrc_x, Xs + wave * 1024, xoff, ks * 128);
 #pragma unroll
         for (int i = 0; i < WP; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (__attribute__((address_space(3))) void*)(Ws + (wave * WP + i) * 1024), 16,
-                                                     woff + (unsigned)i * wstep, ks * 128, 0, 0);
+            dma16_buf(rsrc_w, Ws + (wave * WP + i) * 1024, woff + (unsigned)i * wstep, ks * 128);
     };
     const int nk = p.K / 64;
     issue(0);
@@ -548,8 +535,6 @@ constexpr int EF_RING0 = EF_X + 2 * EF_H;
 constexpr int EF_LDS = EF_RING0 + 8 * EF_R * 1024;
 constexpr int EF_PIECES(const int nch, const int tail, const int front) { return (front ? 16 : 0) + 14 + 17 * nch + (tail ? 17 * tail + 5 : 0); }   // per wave
 
-template <int N>
-__device__ __forceinline__ void ef_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 #define EF_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define EF_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
@@ -577,19 +562,16 @@ __global__ __launch_bounds__(512, 1) void enc_ffn_kernel(EncFfnParams p) {
     const unsigned skip = (p.pack_front && !p.attn) ? 16u * 1024u : 0u;                    // (a stream packed with the front projection, run without it)
     const unsigned total = stride - skip;
     const unsigned char* const wsrc = p.wpack + (size_t)wave * stride + skip + lane16;
-    auto dma = [&](const unsigned char* src_lane, unsigned char* slot) {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_lane, (__attribute__((address_space(3))) void*)slot, 16, 0, 0);
-    };
     // ---- the slab: rows 2 MT w .. + 2 MT - 1 by this wave (1 KiB = two rows; lane -> row, position; the position holds chunk position ^ (row & 15))
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
         const int row = 2 * MT * wave + 2 * i + (lane >> 5);
         const int c16 = (lane & 31) ^ (row & 15);
         const int grow = m_base + row < p.M ? m_base + row : p.M - 1;     // (rows past the end: a valid address, never stored)
-        dma(reinterpret_cast<const unsigned char*>(p.attn ? p.attn : p.x) + (size_t)grow * 512 + c16 * 16, X + (2 * MT * wave + 2 * i) * 512);
+        dma16(reinterpret_cast<const unsigned char*>(p.attn ? p.attn : p.x) + (size_t)grow * 512 + c16 * 16, X + (2 * MT * wave + 2 * i) * 512);
     }
 #pragma unroll
-    for (int n = 0; n < EF_R; ++n) dma(wsrc + n * 1024, ring + n * 1024);
+    for (int n = 0; n < EF_R; ++n) dma16(wsrc + n * 1024, ring + n * 1024);
     unsigned noff = EF_R * 1024u;      // stream offset of the next piece to request
     // Cooperative L2 warm-up of the weight stream (round 5).  Inside the forward the layer's 2.4 MB of weights are in nobody's L2 when the launch
     // starts, and every workgroup of an XCD walks the SAME stream from the same end: the leader takes every miss (13 KiB in flight per wave
@@ -614,14 +596,14 @@ __global__ __launch_bounds__(512, 1) void enc_ffn_kernel(EncFfnParams p) {
     auto take = [&]() { const unsigned s_ = slot; slot = slot + 1024u == EF_R * 1024u ? 0u : slot + 1024u; return s_; };
     // (past the end of the stream the last piece is requested again: the wait counts stay the same in every iteration, nobody reads the slot)
     constexpr int dbg = DBG;
-    auto reissue = [&](const unsigned s_) { if constexpr (!(dbg & 2)) dma(wsrc + (noff < total ? noff : total - 1024u), ring + s_); noff += 1024u; };
+    auto reissue = [&](const unsigned s_) { if constexpr (!(dbg & 2)) dma16(wsrc + (noff < total ? noff : total - 1024u), ring + s_); noff += 1024u; };
     auto frag = [&](const unsigned s_) { return *reinterpret_cast<const half8*>(ring + s_ + lane16); };
     float4v acc1[MT], acc2[2][MT];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc2[j][mt] = float4v{0.f, 0.f, 0.f, 0.f};
-    ef_wait_vm<EF_R>();                                       // the slab pieces are older than the ring's
+    wait_vmcnt<EF_R>();                                       // the slab pieces are older than the ring's
     __builtin_amdgcn_s_barrier();
     half8 xf[8][MT];                                          // this lane's B fragments of the slab: rows mt * 16 + li, k = 32 ks + 8 g .. + 7
 #pragma unroll
@@ -722,18 +704,18 @@ __global__ __launch_bounds__(512, 1) void enc_ffn_kernel(EncFfnParams p) {
     // ---- fc1 of chunk 0 (the pipeline fills), then the first group of chunk 1 into set A ------------------------------------------------
     unsigned s0[5], sa4[4];
     if (p.attn == nullptr) {
-        ef_wait_vm<EF_R - 5>();
+        wait_vmcnt<EF_R - 5>();
         take_g0(A);
     } else {
         // ---- FRONT phase (the slab holds the ATTENTION output): x = LayerNorm(res + attn . Wo^T + bo), HF:models/detr/modeling_detr.py:640-645.
         //      The stream starts with Wo's 16 pieces for this wave's two tiles (fc2's group format); same pipeline; x goes to y32 (the residual the
         //      epilogue reads back) and, as fp16, into the slab's place in LDS -- it never exists as a tensor of its own.
-        ef_wait_vm<EF_R - 4>();
+        wait_vmcnt<EF_R - 4>();
         take_w4(A, sa4);
-        EF_TAIL_STEP(A, 0, sa4, (ef_wait_vm<EF_R - 8>(), take_w4(B, sb)));
-        EF_TAIL_STEP(B, 2, sb, (ef_wait_vm<EF_R - 8>(), take_w4(A, sa4)));
-        EF_TAIL_STEP(A, 4, sa4, (ef_wait_vm<EF_R - 8>(), take_w4(B, sb)));
-        EF_TAIL_STEP(B, 6, sb, (ef_wait_vm<EF_R - 9>(), take_g0(A)));   // (the FFN's first group)
+        EF_TAIL_STEP(A, 0, sa4, (wait_vmcnt<EF_R - 8>(), take_w4(B, sb)));
+        EF_TAIL_STEP(B, 2, sb, (wait_vmcnt<EF_R - 8>(), take_w4(A, sa4)));
+        EF_TAIL_STEP(A, 4, sa4, (wait_vmcnt<EF_R - 8>(), take_w4(B, sb)));
+        EF_TAIL_STEP(B, 6, sb, (wait_vmcnt<EF_R - 9>(), take_g0(A)));   // (the FFN's first group)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int cidx = (2 * wave + j) * 16 + 4 * g;
@@ -759,8 +741,8 @@ __global__ __launch_bounds__(512, 1) void enc_ffn_kernel(EncFfnParams p) {
     }
 #pragma unroll
     for (int i = 0; i < 5; ++i) s0[i] = sa[i];
-    EF_FC1_STEP(A, 0, true, s0, 5, (ef_wait_vm<EF_R - 9>(), take_w4(B, sb)));
-    EF_FC1_STEP(B, 4, false, sb, 4, (ef_wait_vm<EF_R - 9>(), take_g0(A)));
+    EF_FC1_STEP(A, 0, true, s0, 5, (wait_vmcnt<EF_R - 9>(), take_w4(B, sb)));
+    EF_FC1_STEP(B, 4, false, sb, 4, (wait_vmcnt<EF_R - 9>(), take_g0(A)));
     write_h(H);
     EF_LGKM0();
     __builtin_amdgcn_s_barrier();
@@ -769,19 +751,19 @@ __global__ __launch_bounds__(512, 1) void enc_ffn_kernel(EncFfnParams p) {
         const unsigned char* const Hr = H + (c & 1) * EF_H;        // hidden chunk c (fc2 reads it)
         unsigned char* const Hw = H + ((c + 1) & 1) * EF_H;        // hidden chunk c + 1 (fc1 writes it)
         // step G0(c + 1): multiply A, request G1(c + 1) into B
-        EF_FC1_STEP(A, 0, true, sa, 5, (ef_wait_vm<EF_R - 9>(), take_w4(B, sb)));
+        EF_FC1_STEP(A, 0, true, sa, 5, (wait_vmcnt<EF_R - 9>(), take_w4(B, sb)));
         // step G1(c + 1): multiply B, request G2(c) into A (two k-steps of W2's tiles and of hidden chunk c), publish hidden chunk c + 1
-        EF_FC1_STEP(B, 4, false, sb, 4, (ef_wait_vm<EF_R - 8>(), take_w4(A, sa4), read_h(A, Hr, 0)));
+        EF_FC1_STEP(B, 4, false, sb, 4, (wait_vmcnt<EF_R - 8>(), take_w4(A, sa4), read_h(A, Hr, 0)));
         write_h(Hw);
         // step G2(c): multiply A, request G3(c) into B
-        EF_FC2_STEP(A, sa4, (ef_wait_vm<EF_R - 8>(), take_w4(B, sb), read_h(B, Hr, 2)));
+        EF_FC2_STEP(A, sa4, (wait_vmcnt<EF_R - 8>(), take_w4(B, sb), read_h(B, Hr, 2)));
         // step G3(c): multiply B, request G0(c + 2) into A
-        EF_FC2_STEP(B, sb, (ef_wait_vm<EF_R - 9>(), take_g0(A)));
+        EF_FC2_STEP(B, sb, (wait_vmcnt<EF_R - 9>(), take_g0(A)));
         EF_LGKM0();
         if constexpr (!(dbg & 8)) __builtin_amdgcn_s_barrier();   // hidden chunk c + 1 is complete, every read of chunk c has returned
     }
     const int T = p.tail;
-    if (T == 0) ef_wait_vm<0>();   // (the pieces requested past the end of the stream: no LDS-DMA may be in flight when the workgroup ends)
+    if (T == 0) wait_vmcnt<0>();   // (the pieces requested past the end of the stream: no LDS-DMA may be in flight when the workgroup ends)
     else {
 #pragma unroll
         for (int i = 0; i < 5; ++i) reissue(sa[i]);   // (the slots of the last, empty fc1 group: the stream continues with the tail's weights)
@@ -823,7 +805,7 @@ __global__ __launch_bounds__(512, 1) void enc_ffn_kernel(EncFfnParams p) {
         for (int i = 0; i < 4; ++i) f.w[i] = frag(sa[1 + i]);
     };
     load_img(p.tail_pos > 0 ? H : X);
-    ef_wait_vm<0>();                  // (once: the epilogue's stores; the ring is full)
+    wait_vmcnt<0>();                  // (once: the epilogue's stores; the ring is full)
     take_t0(A);
 #pragma unroll 1
     for (int t = 0; t < T; ++t) {
@@ -838,10 +820,10 @@ __global__ __launch_bounds__(512, 1) void enc_ffn_kernel(EncFfnParams p) {
         for (int i = 0; i < 4; ++i) s1[i] = sa[1 + i];
         const unsigned sbias = sa[0];
         // (slots are re-requested in ring order: the stream's next piece belongs into the slot that `take` will visit next)
-        EF_TAIL_STEP(A, 0, s1, (ef_wait_vm<EF_R - 9>(), take_w4(B, sb), reissue(sbias)));
-        EF_TAIL_STEP(B, 2, sb, (ef_wait_vm<EF_R - 8>(), take_w4(A, sa4)));
-        EF_TAIL_STEP(A, 4, sa4, (ef_wait_vm<EF_R - 8>(), take_w4(B, sb)));
-        EF_TAIL_STEP(B, 6, sb, (ef_wait_vm<EF_R - 9>(), take_t0(A)));   // (the next pass's bias + first group; after the last pass: five zero pieces)
+        EF_TAIL_STEP(A, 0, s1, (wait_vmcnt<EF_R - 9>(), take_w4(B, sb), reissue(sbias)));
+        EF_TAIL_STEP(B, 2, sb, (wait_vmcnt<EF_R - 8>(), take_w4(A, sa4)));
+        EF_TAIL_STEP(A, 4, sa4, (wait_vmcnt<EF_R - 8>(), take_w4(B, sb)));
+        EF_TAIL_STEP(B, 6, sb, (wait_vmcnt<EF_R - 9>(), take_t0(A)));   // (the next pass's bias + first group; after the last pass: five zero pieces)
         f16_t* const orow = p.tail_out + p.tail_col[t] + (2 * wave) * 16 + 4 * g;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
@@ -858,7 +840,7 @@ __global__ __launch_bounds__(512, 1) void enc_ffn_kernel(EncFfnParams p) {
         }
         EF_FENCE();
     }
-    ef_wait_vm<0>();
+    wait_vmcnt<0>();
 #endif
 }
 #undef EF_FC1_STEP
@@ -1019,8 +1001,8 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(GemmK256Params p) {
     const int k0 = z * 256;
     const int lrow = lane >> 3, lchunk = (lane & 7) ^ lrow;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.x), 0, (unsigned)((size_t)p.M * p.ldx * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.w), 0, (unsigned)((size_t)p.N * p.ldw * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buf_rsrc(p.x, (unsigned)((size_t)p.M * p.ldx * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_w = buf_rsrc(p.w, (unsigned)((size_t)p.N * p.ldw * 2));
     // wave w stages rows 16w..16w+15 of both operands: 2 row-pieces x 4 sub-tiles each; rows >= M are out of range -> zeros
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -1029,10 +1011,8 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(GemmK256Params p) {
         const unsigned wo = (unsigned)((n_base + r) * p.ldw + k0) * 2u + (unsigned)lchunk * 16u;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(As + t * SUB + (wave * 2 + i) * 1024), 16,
-                                                     m_base + r < p.M ? xo : 0x80000000u, t * 128, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (__attribute__((address_space(3))) void*)(Ws + t * SUB + (wave * 2 + i) * 1024), 16, wo,
-                                                     t * 128, 0, 0);
+            dma16_buf(rsrc_x, As + t * SUB + (wave * 2 + i) * 1024, m_base + r < p.M ? xo : DMA_ZERO_FILL, t * 128);
+            dma16_buf(rsrc_w, Ws + t * SUB + (wave * 2 + i) * 1024, wo, t * 128);
         }
     }
     // accumulators start from the bias (vector or row-periodic; slices z > 0 start from zero)

@@ -19,16 +19,10 @@
 //   track_commit_kernel        one workgroup per matched or new track: Kalman (thread 0), feature ring (all threads).
 #include <hip/hip_runtime.h>
 
-#include "opd_kernels.h"
+#include "opd_kprims.h"
 #include "opd_track.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);   // a + b == b + a: all 64 lanes end with the same bits
-    return v;
-}
 
 __device__ void kalman_predict(float* x, float* P) {
     const float q = 0.1f;

@@ -16,53 +16,14 @@
 // other CUs belong to the other streams meanwhile.  Per accumulator element the k order and the MFMA order are those of
 // conv_gemm_dma_kernel, so the two kernels give IDENTICAL bits (tests/test_kernels_gpu.py asserts it): which one runs a layer is a pure
 // speed choice, made per handle configuration.
-#include <hip/hip_runtime.h>
-#include "opd_kernels.h"
-#include "opd_elem.h"
-
-typedef elem_t half8 __attribute__((ext_vector_type(8)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
+#include "opd_kprims.h"
 
 namespace {
 
-constexpr int ROW_BYTES = 128;
 constexpr int W8_BM = 128, W8_BN = 256;
 constexpr int W8_A_BYTES = W8_BM * ROW_BYTES;                 // 16 KiB
 constexpr int W8_STAGE = W8_A_BYTES + W8_BN * ROW_BYTES;      // 48 KiB
 constexpr int W8_LDS = 3 * W8_STAGE;                          // 144 KiB: one workgroup per CU
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * ROW_BYTES + ((chunk ^ (row & 7)) << 4); }
-__device__ __forceinline__ int xcd_logical_block(int bid, int nblocks) {
-    const int q = nblocks >> 3, r = nblocks & 7;
-    const int x = bid & 7, k = bid >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-}
-__device__ __forceinline__ int fdiv(const int m, const FastDiv& f) { return f.one ? m : (int)(__umulhi((unsigned)m, f.mul) >> f.shift); }
-__device__ __forceinline__ unsigned pack2h(float a, float b) {
-    typedef elem_t half2v __attribute__((ext_vector_type(2)));
-    half2v h;
-    h[0] = (elem_t)a;
-    h[1] = (elem_t)b;
-    unsigned u;
-    __builtin_memcpy(&u, &h, 4);
-    return u;
-}
-__device__ __forceinline__ void unpack2h(unsigned u, float& a, float& b) {
-    typedef elem_t half2v __attribute__((ext_vector_type(2)));
-    half2v h;
-    __builtin_memcpy(&h, &u, 4);
-    a = (float)h[0];
-    b = (float)h[1];
-}
-template <int N_OUTSTANDING>
-__device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N_OUTSTANDING >= 0 && N_OUTSTANDING <= 63, "vmcnt range");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_OUTSTANDING) : "memory");
-}
-__device__ __forceinline__ void compiler_fence() { asm volatile("" ::: "memory"); }
-// LDS reads / writes of this wave retired, then the workgroup barrier; nothing moves across it
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // PW: 1x1 stride-1 convolution / linear layer (row m of [M][Cin]; no tap bookkeeping).
 // Requires (checked by the launcher): N % 256 == 0, Cin % 64 == 0, K / 64 >= 3, byte offsets below 2^31.
@@ -86,36 +47,13 @@ __global__ __launch_bounds__(512) void conv_w8_kernel(ConvGemmParams p) {
     const int lrow = lane >> 3;
     const int lchunk = (lane & 7) ^ lrow;
     const unsigned backoff = PW ? 0u : (unsigned)(p.pad * p.W + p.pad) * (unsigned)p.Cin * 2u;   // every in-image tap gets a non-negative offset
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(p.x)) - backoff, 0, (unsigned)((size_t)p.B * p.H * p.W * p.Cin * 2) + backoff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16_t*>(p.w), 0, (unsigned)((size_t)p.N * p.K * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a = buf_rsrc(reinterpret_cast<const char*>(p.x) - backoff, (unsigned)((size_t)p.B * p.H * p.W * p.Cin * 2) + backoff);
+    const __amdgpu_buffer_rsrc_t rsrc_b = buf_rsrc(p.w, (unsigned)((size_t)p.N * p.K * 2));
     unsigned rowoff[2], rowmask[2], woff[4];
     {
         const int ohw = p.OH * p.OW;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int m = m_base + (wave * 2 + i) * 8 + lrow;
-            const bool okm = m < p.M;
-            if constexpr (PW) {
-                rowoff[i] = okm ? (unsigned)m * (unsigned)(p.Cin * 2) + (unsigned)lchunk * 16u : 0x80000000u;   // rows >= M: zeros (bounds check)
-                rowmask[i] = 1u;
-                continue;
-            }
-            const int mm = okm ? m : 0;
-            const int b = fdiv(mm, p.fd_ohw);
-            const int r = mm - b * ohw;
-            const int oh = fdiv(r, p.fd_ow);
-            const int ow = r - oh * p.OW;
-            rowoff[i] = (unsigned)(((b * p.H + oh * p.stride) * p.W + ow * p.stride) * p.Cin) * 2u + (unsigned)lchunk * 16u;
-            // valid taps in closed form (kernels_gemm.hip): contiguous ranges of kw and kh, replicated by p.tap_rep = sum 1 << kh * KW
-            const int iw0 = ow * p.stride - p.pad, ih0 = oh * p.stride - p.pad;
-            const int lo_w = max(0, -iw0), hi_w = min(p.KW - 1, p.W - 1 - iw0);
-            const int lo_h = max(0, -ih0), hi_h = min(p.KH - 1, p.H - 1 - ih0);
-            auto below = [](const int n) { return n > 0 ? 0xffffffffu >> (32 - n) : 0u; };
-            const unsigned kwmask = hi_w >= lo_w ? below(hi_w + 1) & ~below(lo_w) : 0u;
-            const unsigned hsel = hi_h >= lo_h ? below((hi_h + 1) * p.KW) & ~below(lo_h * p.KW) : 0u;
-            rowmask[i] = okm ? kwmask * (p.tap_rep & hsel) : 0u;
-        }
+        for (int i = 0; i < 2; ++i) conv_row_coords<PW>(p, m_base + (wave * 2 + i) * 8 + lrow, ohw, lchunk, rowoff[i], rowmask[i]);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             woff[i] = (unsigned)((n_base + (wave * 4 + i) * 8 + lrow) * p.K) * 2u + (unsigned)lchunk * 16u;
@@ -143,11 +81,10 @@ __global__ __launch_bounds__(512) void conv_w8_kernel(ConvGemmParams p) {
     auto issue_piece = [&](int i, int stage_off) {   // i = 0, 1: pixel rows; 2 .. 5: weight rows
         unsigned char* As = smem + stage_off;
         if (i < 2) {
-            const unsigned vo = ((rowmask[i] >> is_tap) & 1u) ? rowoff[i] : 0x80000000u;   // out of image -> zero fill
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (__attribute__((address_space(3))) void*)(As + (wave * 2 + i) * 1024), 16, vo, is_soff_a, 0, 0);
+            const unsigned vo = ((rowmask[i] >> is_tap) & 1u) ? rowoff[i] : DMA_ZERO_FILL;   // out of image -> zero fill
+            dma16_buf(rsrc_a, As + (wave * 2 + i) * 1024, vo, is_soff_a);
         } else {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (__attribute__((address_space(3))) void*)(As + W8_A_BYTES + (wave * 4 + i - 2) * 1024), 16,
-                                                     woff[i - 2], is_ks * 128, 0, 0);
+            dma16_buf(rsrc_b, As + W8_A_BYTES + (wave * 4 + i - 2) * 1024, woff[i - 2], is_ks * 128);
         }
     };
     auto issue_main = [&](int ks, int stage_off) {
@@ -179,7 +116,7 @@ __global__ __launch_bounds__(512) void conv_w8_kernel(ConvGemmParams p) {
     //        (group 0) or B_(2k-1) (group 1);
     //   WAR  stage (k + 2) % 3 = stage (k - 1) % 3 is requested after B_(2k-1) at the earliest; its last readers are the P1(k-1) of both
     //        groups, whose lgkmcnt(0) sits in front of B_(2k-2) resp. B_(2k-1).
-    // Every counted wait counts LDS-DMA requests only (opd_kernels.h, OPD_DMA_BARRIER: register loads and stores retire out of order with
+    // Every counted wait counts LDS-DMA requests only (the counted-wait rule, opd_kprims.h: register loads and stores retire out of order with
     // respect to them): the bias loads are retired above, the residual loads go out behind the last counted wait.
     const int group = wave >> 2;
     half8 xf[2][2], wf[2][8];
@@ -303,8 +240,7 @@ hipError_t OPD_SYM(opd_launch_conv_w8)(const ConvGemmParams& p_in, hipStream_t s
     ConvGemmParams p = p_in;
     p.fd_ohw = opd_make_fastdiv((unsigned)p.OH * (unsigned)p.OW);
     p.fd_ow = opd_make_fastdiv((unsigned)p.OW);
-    p.tap_rep = 0u;
-    for (int kh = 0; kh < p.KH; ++kh) p.tap_rep |= 1u << (kh * p.KW);
+    p.tap_rep = opd_tap_rep(p.KH, p.KW);
     const int tiles_m = (p.M + W8_BM - 1) / W8_BM, tiles_n = p.N / W8_BN;
     p.fd_tilesn = opd_make_fastdiv((unsigned)tiles_n);
     const bool pw = p.KH == 1 && p.KW == 1 && p.pad == 0 && p.stride == 1 && p.H == p.OH && p.W == p.OW;

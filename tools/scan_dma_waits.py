@@ -13,24 +13,20 @@ instantiation of every ELEM_SOURCES file), and hipcc is resolved the way build.p
 No kernel and no barrier is exempted (round 4 skipped the wave-private ring kernels by NAME; round 5 checks them like any other: the one barrier
 that then stood out sat behind a tools-only trace store in dec_self_kernel, which now keeps its stamps in registers until the kernel ends).
 usage: scan_dma_waits.py [kernels_*.hip ...]   (default: every kernel file; exit code 1 if a suspicious barrier is found)"""
-import os, re, subprocess, sys, tempfile
+import os, re, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.environ.get("OPD_SCAN_CSRC") or os.path.join(ROOT, "office_person_detection_vit_amd", "csrc")   # (another revision's sources: a worktree's csrc)
 sys.path.insert(0, ROOT)
 from office_person_detection_vit_amd.csrc import build as B   # noqa: E402
 
-files = sys.argv[1:] or sorted(f for f in os.listdir(CSRC) if f.startswith("kernels_") and f.endswith(".hip"))
+files = sys.argv[1:] or B.kernel_files(CSRC)
 bad = checked = 0
 for f in files:
     path = f if os.path.isabs(f) else os.path.join(CSRC, f)
     base = os.path.basename(path)
-    variants = [("f16", [])] + ([("bf16", B.BF16_FLAGS)] if base in B.ELEM_SOURCES and os.path.exists(os.path.join(CSRC, "opd_elem.h")) else [])
-    for tag, vflags in variants:
-        with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
-            cmd = [B.hipcc_path()] + B.COMMON_FLAGS + B.EXTRA_FLAGS.get(base, []) + vflags + ["-S", "--cuda-device-only", "-I" + CSRC, path, "-o", tmp.name]
-            subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-            src = open(tmp.name).read().split("\n")
+    for tag, asm in B.device_asm(path, CSRC).items():
+        src = asm.split("\n")
         fn, seq, verdict = None, [], None   # seq: classes of the vector-memory operations that may be in flight ('D' LDS-DMA request, 'o' load into registers, 's' store)
         for i, l in enumerate(src):
             m = re.match(r"^(_Z\w+):", l)
