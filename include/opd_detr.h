@@ -181,7 +181,9 @@ OPD_API int opd_detr_detect_frames(opd_detr* m, const uint8_t* const* frames, in
  * src/tracking/feature_extractor.py:39-88): opd_detr_detect_frames on host frames + the appearance feature of every record of class `label`
  * (ROI mean-pool + L2 norm exactly as opd_detr_roi_features computes it for the record's box), pooled while the records are still on the
  * device -- one host wait instead of two.  features: [B][num_queries][d_model] fp32 (host), row = the record's query_index; rows of queries
- * without a record of that class are NOT written (whatever the buffer held).  Suppression (opd_person_nms) happens afterwards on the host: a suppressed record's row is simply unused. */
+ * without a record of that class are NOT written (whatever the buffer held).  Suppression: by default (opd_detr_set_nms off) it happens
+ * afterwards on the host (opd_person_nms), and a suppressed record's row is simply unused; with opd_detr_set_nms on, the records are
+ * suppressed on the device BEFORE the pooling, come back final in score order, and rows are written for kept records only. */
 OPD_API int opd_detr_detect_frames_features(opd_detr* m, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
                                             int label, opd_det* out, int32_t* counts, float* features);
 /* The same call with the reference's DEFAULT appearance feature instead (`YOLOv8Detector.extract_features`, yolov8_detector.py:161-190, which
@@ -205,6 +207,22 @@ OPD_API int opd_person_nms(opd_det* dets, int n, int person_label, float nms_thr
  * opd_detr_detect writes, stride = num_queries); every frame is compacted in place and `counts[f]` becomes its new count.
  * A negative `counts[f]` (padding slot of an uneven shard) is left alone.  Returns 0 or a negative error. */
 OPD_API int opd_person_nms_batch(opd_det* dets, int32_t* counts, int n_frames, int stride, int person_label, float nms_threshold);
+/* The same filter and suppression ON THE DEVICE, inside every call that delivers records.  Handle state; a negative `nms_threshold`
+ * turns it off, the state after opd_detr_create and opd_detr_clone.  While on, every entry point that delivers records (blocking,
+ * opd_detr_detect_async / opd_detr_wait, _resized, _ragged, _frames, _frames_features, _frames_color, _frames_floor, _frames_reid,
+ * opd_detr_postprocess, opd_comm_detect), from the next submission on, runs one more kernel directly behind the post-process, in place
+ * on whichever buffers it wrote (the handle's, or the caller's device pointers), before the feature, floor and Re-ID stages: the
+ * records come back FINAL, per frame in descending score order (ties in query order), exactly what opd_person_nms_batch(person_label,
+ * nms_threshold) makes of the unsuppressed records -- so host suppression applied again changes nothing.  `person_label` < 0 keeps
+ * every class; `nms_threshold` >= 1 filters and sorts without suppressing.  The forward graph is not recaptured.  OPD_EINVAL: a null
+ * handle, a NaN threshold. */
+OPD_API int opd_detr_set_nms(opd_detr* m, int person_label, float nms_threshold);
+/* opd_person_nms_batch for DEVICE-resident records (the gathered buffer of a sharded step, the outputs of a DEVICE_OUT call): `dets`
+ * [n_frames][stride] and `counts` [n_frames] are device-accessible memory on `m`'s device, rewritten in place on `m`'s stream; the call
+ * returns when they are final.  A negative count is left alone.  OPD_EINVAL before any device work: a null handle, n_frames < 0,
+ * stride < 1 or > 128, pointers that are not device-accessible memory.  OPD_EINVAL after the wait: a count above the stride (that
+ * frame's records and count are left as they were; the other frames are done). */
+OPD_API int opd_detr_nms_records(opd_detr* m, opd_det* dets, int32_t* counts, int n_frames, int stride, int person_label, float nms_threshold);
 
 /* Page-locked host memory for frame batches handed over with OPD_MEM_HOST: the upload of such a buffer is one asynchronous DMA
  * instead of the runtime's staged copy of pageable memory.  Optional (any host pointer is accepted everywhere); the Python shim
@@ -372,8 +390,10 @@ OPD_API int opd_reid_extract(opd_reid* r, const uint8_t* const* frames, const in
  * float32(x2 - x1), float32(y2 - y1), as opd_reid_extract would be handed it) and read in place from the camera-resolution frames this
  * call uploaded.  `features` = host float32 [slots][feature_dim]; row k belongs to record slot_map[k] = frame * num_queries +
  * query_index (host int32 [slots]); *n_person = the number of such records in the batch.  Rows and slot_map entries k >= min(*n_person,
- * slots) are not written.  *n_person > slots is not an error: the caller fetches the remaining rows with opd_reid_extract.  Suppression
- * (opd_person_nms) stays on the host afterwards; a suppressed record's row is unused.  OPD_EINVAL before any device work: a null
+ * slots) are not written.  *n_person > slots is not an error: the caller fetches the remaining rows with opd_reid_extract.  Suppression:
+ * by default (opd_detr_set_nms off) it stays on the host afterwards (opd_person_nms), the slots go to records in query order and a
+ * suppressed record's row is unused; with opd_detr_set_nms on, the records are suppressed on the device first, *n_person counts the
+ * KEPT records, and the slots go to the kept records of each frame in score order.  OPD_EINVAL before any device work: a null
  * handle or output, slots < 1 or > max_crops, handles on different devices, B > max_batch, frame sizes outside the detector handle's
  * limits.
  * A Re-ID handle serves ONE call at a time: a thread that enters this call or opd_reid_extract while another call on the same opd_reid
@@ -483,7 +503,8 @@ OPD_API int opd_floor_transform_points(opd_floor* f, const double* pts_xy, int n
 OPD_API int opd_floor_classify(opd_floor* f, const double* floor_xy, int n, uint64_t* masks);
 /* opd_detr_detect_frames on host frames plus a floor record for every record of class `label`, computed while the records are on the
  * device from the box the Python shim derives, (x1, y1, float32(x2 - x1), float32(y2 - y1)).  `floor` = host [B][num_queries]; the row of
- * a record is its query_index; rows of queries without such a record are not written.  One host wait.  `m` and `f` must be on one device. */
+ * a record is its query_index; rows of queries without such a record are not written.  One host wait.  `m` and `f` must be on one device.
+ * With opd_detr_set_nms on, the records are suppressed on the device first: rows are written for kept records only. */
 OPD_API int opd_detr_detect_frames_floor(opd_detr* m, opd_floor* f, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
                                          int label, opd_det* out, int32_t* counts, opd_floor_rec* floor);
 

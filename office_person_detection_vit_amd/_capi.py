@@ -128,6 +128,8 @@ API = {
     "opd_detr_wait": (C.c_int, [C.c_void_p, C.c_int]),
     "opd_person_nms": (C.c_int, [C.POINTER(OpdDet), C.c_int, C.c_int, C.c_float]),
     "opd_person_nms_batch": (C.c_int, [C.POINTER(OpdDet), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float]),
+    "opd_detr_set_nms": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "opd_detr_nms_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float]),
     "opd_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "opd_host_free": (None, [C.c_void_p]),
     "opd_similarity_matrix": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -279,6 +281,8 @@ TEST_API = {
     "opd_test_crop_plan_device": (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 7 + [C.c_int]),
     "opd_test_crop_plan_host": (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 7 + [C.c_int]),
     "opd_test_crop_plan_staged": (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 7 + [C.c_int]),
+    # suppression hook (csrc/opd_nms_test_api.cpp): the device kernel's algorithm on the host; dets, counts, n_frames, stride, label, threshold
+    "opd_test_nms_plan_host": (C.c_int, [C.POINTER(OpdDet), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float]),
     # optical-flow hook (csrc/opd_flow_test_api.cpp)
     "opd_flow_test_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     # floor-map hook (csrc/opd_floor_test_api.cpp)

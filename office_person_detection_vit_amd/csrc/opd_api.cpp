@@ -7,6 +7,7 @@
 
 #include "opd_floor.h"
 #include "opd_model.h"
+#include "opd_nms.h"
 #include "opd_reid.h"
 
 namespace opd {
@@ -105,6 +106,16 @@ static int stage_frames(opd_detr* m, const FrameSource& src, int B, int H, int W
     return OPD_OK;
 }
 
+// Person filter + greedy IoU-NMS in place on device records (kernels_nms.hip), through the launch helper like the post-process before it
+static int enqueue_nms(opd_detr* m, opd_det* dets, int32_t* counts, int n_frames, int stride, int label, float threshold) {
+    if (!m->d_nms_flag) {
+        RCCHK(dalloc(m, &m->d_nms_flag, 1, false));
+        HIPCHK(hipMemsetAsync(m->d_nms_flag, 0, 4, m->stream));
+    }
+    NmsParams np{dets, counts, m->d_nms_flag, n_frames, stride, label, threshold};
+    return launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_person_nms(np, m->stream); });
+}
+
 // `orig_hw` (nullable): the frame sizes the boxes are scaled to, else h x w for every frame.  `dev_out` / `dev_counts` (nullable): device buffers of the
 // caller; the kernel then writes there directly instead of the library's own record buffers (no device-to-device copies afterwards).
 static int enqueue_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, int h, int w, opd_det* dev_out, int32_t* dev_counts) {
@@ -125,6 +136,8 @@ static int enqueue_postprocess(opd_detr* m, float threshold, const int32_t* orig
     pp.counts = dev_counts ? dev_counts : m->d_counts;
     pp.B = B; pp.Q = m->arch.queries; pp.ncls = m->arch.ncls; pp.threshold = threshold;
     RCCHK(launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_postprocess(pp, m->stream); }));
+    if (m->nms_threshold >= 0.f)   // opd_detr_set_nms: the stages behind, and the caller, see final records in score order (in front of mark 8: the
+        RCCHK(enqueue_nms(m, static_cast<opd_det*>(pp.records), pp.counts, B, pp.Q, m->nms_label, m->nms_threshold));   // kernel's time is part of stage_ms[7])
     MARK(8);
     return OPD_OK;
 }
@@ -427,6 +440,33 @@ int opd_detr_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, o
     if (m->last_B == 0) return fail(OPD_ESTATE, "opd_detr_postprocess called before any forward");
     HIPCHK(hipSetDevice(m->device));
     return deliver_records(m, {threshold, orig_hw, out, counts, OPD_MEM_HOST, WAIT_BLOCKING}, 0, 0, nullptr);
+}
+int opd_detr_set_nms(opd_detr* m, int person_label, float nms_threshold) {
+    if (!m) return fail(OPD_EINVAL, "null model handle");
+    if (nms_threshold != nms_threshold) return fail(OPD_EINVAL, "opd_detr_set_nms: the threshold is NaN");
+    m->nms_label = person_label;
+    m->nms_threshold = nms_threshold < 0.f ? -1.0f : nms_threshold;
+    return OPD_OK;
+}
+int opd_detr_nms_records(opd_detr* m, opd_det* dets, int32_t* counts, int n_frames, int stride, int person_label, float nms_threshold) {
+    ApiScope api_scope;
+    if (!m) return fail(OPD_EINVAL, "null model handle");
+    if (n_frames < 0 || stride < 1 || stride > OPD_NMS_MAX) return fail(OPD_EINVAL, "opd_detr_nms_records: n_frames < 0, or a stride outside [1, 128]");
+    if (nms_threshold != nms_threshold) return fail(OPD_EINVAL, "opd_detr_nms_records: the threshold is NaN");
+    if (n_frames == 0) return OPD_OK;
+    HIPCHK(hipSetDevice(m->device));
+    if (!device_accessible(dets) || !device_accessible(counts))
+        return fail(OPD_EINVAL, "opd_detr_nms_records: records and counts must be device-accessible memory");
+    int32_t over = 0;
+    RCCHK(enqueue_nms(m, dets, counts, n_frames, stride, person_label, nms_threshold));
+    HIPCHK(hipMemcpyAsync(&over, m->d_nms_flag, 4, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (m->profiling == 1) timed_collect(m);   // (the launch's event pair: this call's row of opd_detr_kernel_table)
+    if (over) {
+        HIPCHK(hipMemsetAsync(m->d_nms_flag, 0, 4, m->stream));
+        return fail(OPD_EINVAL, "opd_detr_nms_records: a frame holds more records than its slots (left as it was)");
+    }
+    return OPD_OK;
 }
 int opd_detr_resize_u8(opd_detr* m, const uint8_t* frames, int B, int h, int w, int out_h, int out_w, uint8_t* out) {
     ApiScope api_scope;

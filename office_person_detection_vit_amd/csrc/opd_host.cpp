@@ -10,6 +10,7 @@
 #include "../../include/opd_detr.h"
 #include "opd_host.h"
 #include "opd_loader.h"
+#include "opd_nms.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -152,25 +153,19 @@ int opd_person_nms(opd_det* dets, int n, int person_label, float nms_threshold) 
     std::vector<int> idx;
     for (int i = 0; i < n; ++i)
         if (person_label < 0 || dets[i].label == person_label) idx.push_back(i);
-    // stable sort by descending score (ties keep query order), as the oracle's person_detections
+    // stable sort by descending score (ties keep query order), as the oracle's person_detections; the IoU is opd_nms.h's, the device kernel's too
     for (size_t i = 1; i < idx.size(); ++i) {
         const int v = idx[i];
         size_t j = i;
         while (j > 0 && dets[idx[j - 1]].score < dets[v].score) { idx[j] = idx[j - 1]; --j; }
         idx[j] = v;
     }
-    auto iou = [](const opd_det& a, const opd_det& b) {
-        const float ix1 = fmaxf(a.x1, b.x1), iy1 = fmaxf(a.y1, b.y1), ix2 = fminf(a.x2, b.x2), iy2 = fminf(a.y2, b.y2);
-        const float iw = fmaxf(0.f, ix2 - ix1), ih = fmaxf(0.f, iy2 - iy1), inter = iw * ih;
-        const float ua = fmaxf(0.f, a.x2 - a.x1) * fmaxf(0.f, a.y2 - a.y1) + fmaxf(0.f, b.x2 - b.x1) * fmaxf(0.f, b.y2 - b.y1) - inter;
-        return ua > 0.f ? inter / ua : 0.f;
-    };
     std::vector<opd_det> kept;
     for (int i : idx) {
         bool ok = true;
         if (nms_threshold < 1.0f)
             for (const auto& k : kept)
-                if (iou(dets[i], k) > nms_threshold) { ok = false; break; }
+                if (opd_nms_iou(dets[i], k) > nms_threshold) { ok = false; break; }
         if (ok) kept.push_back(dets[i]);
     }
     for (size_t i = 0; i < kept.size(); ++i) dets[i] = kept[i];

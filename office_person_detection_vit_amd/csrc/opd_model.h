@@ -256,6 +256,10 @@ struct opd_detr : DetrWeights {
     int32_t* d_rois = nullptr;
     float* d_roi_out = nullptr;
     std::vector<int32_t> h_orig_hw;
+    // device suppression (opd_detr_set_nms): off while nms_threshold < 0; the flag word of person_nms_kernel (allocated by the first use)
+    int nms_label = 0;
+    float nms_threshold = -1.0f;
+    int32_t* d_nms_flag = nullptr;
 
     // state of the last forward
     int last_B = 0, last_H = 0, last_W = 0, last_fh = 0, last_fw = 0;

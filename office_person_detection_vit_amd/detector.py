@@ -80,6 +80,7 @@ class HipDetrDetector:
         pinned_staging: bool = True,
         dtype: str = "fp16",
         frame_lists: bool = True,
+        device_nms: bool = False,
     ):
         """
         Args mirror ``config.yaml.disabled:33-44`` (``model_name``, ``confidence_threshold``, ``nms_threshold``,
@@ -98,6 +99,8 @@ class HipDetrDetector:
         one DMA; False stacks into ordinary numpy memory.
         ``frame_lists``: hand a chunk of same-sized contiguous frames to the library as a list of pointers
         (``opd_detr_detect_frames``: each frame is uploaded from where it lies) instead of stacking it first; False always stacks.
+        ``device_nms``: run the person filter and NMS on the device inside every detect call (``opd_detr_set_nms``) instead of on the
+        host behind it: the same ``Detection`` lists; feature, floor and Re-ID stages of the fused calls then work on final records only.
         """
         self.model_name = model_name
         self.model_path = model_path
@@ -120,6 +123,8 @@ class HipDetrDetector:
         self._handles: List[int] = []  # all handles, handle 0 first
         self.pinned_staging = bool(pinned_staging)
         self.frame_lists = bool(frame_lists)
+        self.device_nms = bool(device_nms)
+        self._nms_set: Optional[float] = None  # device_nms: the threshold the handles were last given
         self._staging: dict = {}  # handle slot -> (pinned pointer, capacity in bytes)
         self.feature_extractor = FeatureExtractor()
         self._lib = None
@@ -179,11 +184,29 @@ class HipDetrDetector:
             info = _capi.OpdModelInfo()
             _capi.check(lib.opd_detr_info(C.c_void_p(self._handles[0]), C.byref(info)), "opd_detr_info")
             self.model, self._info = self._handles[0], info
+            self._sync_nms()
             logger.info(f"Model loaded: {path}")
         except Exception as e:
             self.close()
             logger.error(f"Failed to load model: {e}")
             raise RuntimeError(f"Failed to load DETR model: {e}") from e
+
+    def _sync_nms(self) -> None:
+        """``device_nms``: hand ``nms_threshold`` to every handle when it has changed since the last time (callers assign the attribute;
+        assigning ``device_nms`` itself switches the mode from the next call on)."""
+        if not self.device_nms:
+            if self._nms_set is not None:
+                for h in self._handles:
+                    _capi.check(self._lib.opd_detr_set_nms(C.c_void_p(h), PERSON_LABEL, -1.0), "opd_detr_set_nms")
+                self._nms_set = None
+            return
+        thr = float(self.nms_threshold)
+        if self._nms_set is None or thr != self._nms_set:
+            if not thr >= 0.0:
+                raise ValueError(f"device_nms needs nms_threshold >= 0, got {thr!r}")
+            for h in self._handles:
+                _capi.check(self._lib.opd_detr_set_nms(C.c_void_p(h), PERSON_LABEL, thr), "opd_detr_set_nms")
+            self._nms_set = thr
 
     def close(self) -> None:
         # communicator lanes bound to this detector's handles go first (sharding.NativeExchange registers itself here); the library also
@@ -199,6 +222,7 @@ class HipDetrDetector:
         self._staging = {}
         self._handles = []
         self.model = None
+        self._nms_set = None
 
     def __del__(self):  # pragma: no cover - best effort
         try:
@@ -393,6 +417,7 @@ class HipDetrDetector:
             raise ValueError(f"{len(frames)} frames exceed max_batch = {self.max_batch}")
         if not (records.is_contiguous() and counts.is_contiguous()):
             raise ValueError("records / counts must be contiguous")
+        self._sync_nms()
         self._detect_into(frames, self.model, int(records.data_ptr()), int(counts.data_ptr()), on_device=bool(records.is_cuda))
 
     def detect_records_at(self, frames: Sequence[np.ndarray], rec_ptr: int, cnt_ptr: int) -> None:
@@ -402,13 +427,15 @@ class HipDetrDetector:
         if len(frames) > self.max_batch:
             raise ValueError(f"{len(frames)} frames exceed max_batch = {self.max_batch}")
         if len(frames):
+            self._sync_nms()
             self._detect_into(frames, self.model, int(rec_ptr), int(cnt_ptr), on_device=True)
 
     def _postprocess_batch(self, recs, counts, Q: int, floor=None, floor_map=None) -> List[List[Detection]]:
         """``_postprocess_batch`` (deleted vit_detector.py 591-647): person filter + NMS (C-ABI), xyxy -> xywh, foot point.
         ``floor``: the fused call's floor records; every kept detection takes the row of its query (Phase 3's four fields)."""
-        rc = self._lib.opd_person_nms_batch(recs, counts, len(counts), Q, PERSON_LABEL, float(self.nms_threshold))   # in place
-        _capi.check(rc, "opd_person_nms_batch")
+        if self._nms_set is None:   # (else the handles suppressed on the device, _sync_nms: the records are final already, in the same order)
+            rc = self._lib.opd_person_nms_batch(recs, counts, len(counts), Q, PERSON_LABEL, float(self.nms_threshold))   # in place
+            _capi.check(rc, "opd_person_nms_batch")
         results: List[List[Detection]] = []
         for b in range(len(counts)):
             dets = []
@@ -437,6 +464,7 @@ class HipDetrDetector:
         self._require_model()
         if len(frames) == 0:
             return []
+        self._sync_nms()
         try:
             chunks = [frames[i:i + self.max_batch] for i in range(0, len(frames), self.max_batch)]
             if len(self._handles) > 1 and len(chunks) > 1:
@@ -480,6 +508,7 @@ class HipDetrDetector:
     def detect(self, frame: np.ndarray, floor_map=None) -> List[Detection]:
         """Single-frame detection (``yolov8_detector.py:90-132``); ``floor_map``: see ``detect_batch``."""
         self._require_model()
+        self._sync_nms()
         try:
             dets, filled = self._detect_chunk([frame], floor_map)
             dets = dets[0]
@@ -503,6 +532,7 @@ class HipDetrDetector:
         self._require_model()
         if features not in ("encoder", "color", "reid"):
             raise ValueError(f"features must be 'encoder', 'color' or 'reid', got {features!r}")
+        self._sync_nms()
         if features == "reid":
             if reid is None:
                 raise ValueError("features='reid' needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")

@@ -2,9 +2,12 @@
 replaces (opd_detr_detect_frames, then opd_reid_extract on the boxes of the first `slots` person records), same handles, same build,
 in interleaved rounds.  The two-call sequence is the yardstick and its own round-to-round spread the margin.  The person count is
 whatever the frame yields at each threshold.  Then the Python surface: detect_with_features(features="reid") against detect() +
-extract_features().  Host clock around calls that end in a device wait.
+extract_features().  Host clock around calls that end in a device wait.  --device-nms: the Python rows in both suppression modes
+(host NMS behind the call / opd_detr_set_nms inside it) on the same handles, all four sequences interleaved in every round, and a row
+with person_nms_kernel's own time from opd_detr_kernel_table.
 
-    python tools/bench_detect_reid.py [--model osnet|clip] [--slots 8,32] [--thresholds 0.05,0.45] [--rounds 5] [--iters 100] [--json out.json]
+    python tools/bench_detect_reid.py [--model osnet|clip] [--slots 8,32] [--thresholds 0.05,0.45] [--rounds 5] [--iters 100] [--device-nms]
+                                      [--json out.json]
 """
 
 from __future__ import annotations
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--device-nms", action="store_true")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     lib = _capi.load_library()
@@ -124,6 +128,51 @@ def main():
                          "rows_bit_identical": same, "detect+extract_features": stats(t2), "detect_with_features(reid)": stats(tf),
                          "two_calls_spread_ms": round(max(t2) - min(t2), 4), "saved_ms": round(float(np.median(t2) - np.median(tf)), 4)})
             print(json.dumps(rows[-1]), flush=True)
+            if not args.device_nms:
+                continue
+
+            def in_mode(on, call):   # (the switch is one host call on the handle: outside the clock)
+                det.device_nms = on
+                det._sync_nms()
+                return call()
+
+            for _ in range(args.warmup):
+                in_mode(True, two)
+                in_mode(True, one)
+            same = bool(np.array_equal(in_mode(False, one)[1], in_mode(True, one)[1]) and np.array_equal(in_mode(True, two), in_mode(True, one)[1]))
+            ts = {"host:detect+extract_features": [], "host:detect_with_features(reid)": [], "device:detect+extract_features": [],
+                  "device:detect_with_features(reid)": []}
+            for _ in range(args.rounds):   # four sequences, interleaved: drift of the machine lands on all of them
+                for key, on, call in (("host:detect+extract_features", False, two), ("host:detect_with_features(reid)", False, one),
+                                      ("device:detect+extract_features", True, two), ("device:detect_with_features(reid)", True, one)):
+                    ts[key].append(in_mode(on, lambda: timed(call, args.iters)))
+            in_mode(False, lambda: None)
+            med = {k: float(np.median(v)) for k, v in ts.items()}
+            pairs = sum(a < b for a, b in zip(ts["device:detect_with_features(reid)"], ts["host:detect+extract_features"]))
+            rows.append({"what": "python device_nms", "model": args.model, "threshold": conf, "nms_threshold": nms, "slots": slots, "detections": ndet,
+                         "rows_bit_identical": same, **{k: stats(v) for k, v in ts.items()},
+                         "two_calls_spread_ms": round(max(ts["host:detect+extract_features"]) - min(ts["host:detect+extract_features"]), 4),
+                         "fused_device_vs_two_calls_host_ms": round(med["device:detect_with_features(reid)"] - med["host:detect+extract_features"], 4),
+                         "fused_device_vs_fused_host_ms": round(med["device:detect_with_features(reid)"] - med["host:detect_with_features(reid)"], 4),
+                         "two_calls_device_vs_two_calls_host_ms": round(med["device:detect+extract_features"] - med["host:detect+extract_features"], 4),
+                         "pairs_fused_device_faster_than_two_calls_host": f"{pairs} of {args.rounds}"})
+            print(json.dumps(rows[-1]), flush=True)
+    if args.device_nms:   # the kernel's own time: one profiled call (event pair around every launch) per confidence threshold
+        det.nms_threshold, det.device_nms = nms0, True
+        _capi.check(lib.opd_detr_set_profiling(C.c_void_p(det.model), 1), "opd_detr_set_profiling")
+        for conf in (0.05, float(args.thresholds.split(",")[-1])):
+            det.confidence_threshold = conf
+            ms = []
+            for _ in range(1 + args.rounds):
+                nrec = len(det.detect(frame))
+                tab, n = (_capi.OpdKernelStat * 256)(), C.c_int(0)
+                _capi.check(lib.opd_detr_kernel_table(C.c_void_p(det.model), tab, 256, C.byref(n)), "opd_detr_kernel_table")
+                ms += [tab[i].ms / max(tab[i].launches, 1) for i in range(min(n.value, 256)) if tab[i].name.decode() == "person_nms_kernel"]
+            rows.append({"what": "kernel", "name": "person_nms_kernel", "threshold": conf, "kept": nrec, "calls": len(ms), "event_pair": stats(ms[1:]) if len(ms) > 1 else None})
+            print(json.dumps(rows[-1]), flush=True)
+        _capi.check(lib.opd_detr_set_profiling(C.c_void_p(det.model), 0), "opd_detr_set_profiling")
+        det.device_nms = False
+        det._sync_nms()
     ext.cleanup()
     det.close()
     if args.json:
