@@ -569,6 +569,69 @@ OPD_API int opd_track_get(opd_track* t, opd_track_rec* out, int capacity, int* c
  * min(rows, cols) pairs of smallest total cost, as scipy.optimize.linear_sum_assignment. */
 OPD_API int opd_assign(const double* cost, int rows, int cols, int32_t* row_to_col);
 
+/* ---- Hybrid tracker: the reference's `LightweightTracker` (sixth handle type: per-track state and flow points on the device) ------------
+ * src/tracking/lightweight_tracker.py:211-455 as the reference's shipped configuration runs it (`tracking.hybrid_mode`): a detection frame
+ * goes through `update_with_detections` (Kalman predict, greedy IoU matching, Kalman update, new tracks, deletion after max_age frames,
+ * the flow points of `OpticalFlowTracker.initialize`), every frame in between through `interpolate` (pyramidal Lucas-Kanade on the box
+ * centres, Kalman update of the tracks whose point was followed, Kalman predict of the others).  Each is ONE call with one host wait, and
+ * no track number is computed on the host: tracks, ids, counters, the next id and the point list live on the device; the calls return
+ * ids and boxes.  The handle owns a flow handle and runs its gray, pyramid and LK launches on the same stream as its own two kernels.
+ * Arithmetic: P, S and K in float32, x in float32 until the first detection-frame match and in float64 from then on (what numpy's
+ * promotion makes of the reference's `KalmanFilter.update` with a float64 centre), IoU in float64, in a fixed order without fused
+ * multiply-adds; a track's numbers do not depend on the other tracks or on its position. */
+typedef struct opd_lwt opd_lwt; /* opaque hybrid-tracker handle */
+
+typedef struct opd_lwt_config {
+    int32_t struct_size;      /* = sizeof of this struct */
+    int32_t max_tracks;       /* tracks alive at one time, 1 .. 1024 (0 = 256) */
+    int32_t max_dets;         /* detections per update, and flow points, 1 .. 1024 (0 = 256) */
+    int32_t max_age;          /* a track is dropped once time_since_update exceeds this (0 = 30) */
+    int32_t use_optical_flow; /* 0: `interpolate` predicts every track and no frame is read */
+    int32_t reserved[3];      /* zero */
+    double iou_threshold;     /* matching stops below this IoU (0 = 0.3).  Negative is refused: the reference's loop would never end */
+    opd_flow_config flow;     /* frame limits and LK parameters as for the flow handle; max_points is ignored (max_dets is used) */
+} opd_lwt_config;
+
+typedef struct opd_lwt_rec {
+    int32_t track_id, reserved;
+    double bbox[4]; /* xywh */
+} opd_lwt_rec;
+
+typedef struct opd_lwt_track {
+    int32_t track_id, age, hits, time_since_update;
+    int32_t x_is_float32; /* 1: x holds float32 values and is still computed on in float32 */
+    int32_t reserved;
+    double bbox[4];       /* xywh (float32 values) */
+    double center[2];
+    double x[4];          /* Kalman state: position and velocity */
+    float P[16];          /* covariance, row-major */
+} opd_lwt_track;
+
+typedef struct opd_lwt_status {
+    int32_t max_tracks, max_dets, max_age, use_optical_flow, device_ordinal;
+    int32_t n_tracks, next_id, n_points; /* n_points: flow points held (`prev_points`) */
+    int32_t last_launches, last_waits;   /* kernel launches and host waits of the last update or interpolate call */
+    double iou_threshold;
+} opd_lwt_status;
+
+/* OPD_EINVAL, before the device is touched, for a size outside its range, a negative max_age or iou_threshold, a wrong struct_size. */
+OPD_API int opd_lwt_create(const opd_lwt_config* cfg, int device_ordinal, opd_lwt** out);
+OPD_API void opd_lwt_destroy(opd_lwt* t);
+/* Drop every track and point and start again at id 1, as `LightweightTracker.reset`. */
+OPD_API int opd_lwt_reset(opd_lwt* t);
+OPD_API int opd_lwt_info(const opd_lwt* t, opd_lwt_status* info);
+/* `update_with_detections`.  boxes_xywh [n][4] host float32; ids_out [n] host: the track id of every detection.  `bgr` [h][w][3] uint8 is
+ * the frame the points will be followed FROM: host memory or a device pointer read in place, as for the flow handle; without optical
+ * flow it is not read and may be NULL.  n > max_dets is OPD_EINVAL before anything is launched.  New tracks that would not fit beside
+ * the live ones are OPD_EINVAL too: the kernel finds that out after matching and before it writes, so tracks, ids, points and the
+ * reference frame are left as they were. */
+OPD_API int opd_lwt_update(opd_lwt* t, const uint8_t* bgr, int mem_kind, int h, int w, const float* boxes_xywh, int n, int32_t* ids_out);
+/* `interpolate`: recs_out [capacity] host, *count records, one per live track in creation order (OPD_EINVAL when capacity is smaller;
+ * *count then says how many there are). */
+OPD_API int opd_lwt_interpolate(opd_lwt* t, const uint8_t* bgr, int mem_kind, int h, int w, opd_lwt_rec* recs_out, int capacity, int* count);
+/* The live tracks in creation order (out may be NULL with capacity 0 to ask for the count).  A read-back for inspection: one more wait. */
+OPD_API int opd_lwt_get(opd_lwt* t, opd_lwt_track* out, int capacity, int* count);
+
 /* Thread-local description of the last error returned on this thread ("" if none). */
 OPD_API const char* opd_last_error(void);
 

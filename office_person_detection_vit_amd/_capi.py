@@ -100,6 +100,25 @@ class OpdTrackStatus(C.Structure):   # opd_track_status
                                          "last_launches", "last_waits")]
 
 
+class OpdLwtConfig(C.Structure):   # opd_lwt_config (72 bytes): zeros = the reference's defaults
+    _fields_ = [("struct_size", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("max_age", C.c_int32), ("use_optical_flow", C.c_int32),
+                ("reserved", C.c_int32 * 3), ("iou_threshold", C.c_double), ("flow", OpdFlowConfig)]
+
+
+class OpdLwtRec(C.Structure):   # opd_lwt_rec (40 bytes)
+    _fields_ = [("track_id", C.c_int32), ("reserved", C.c_int32), ("bbox", C.c_double * 4)]
+
+
+class OpdLwtTrack(C.Structure):   # opd_lwt_track (168 bytes)
+    _fields_ = [("track_id", C.c_int32), ("age", C.c_int32), ("hits", C.c_int32), ("time_since_update", C.c_int32), ("x_is_float32", C.c_int32),
+                ("reserved", C.c_int32), ("bbox", C.c_double * 4), ("center", C.c_double * 2), ("x", C.c_double * 4), ("P", C.c_float * 16)]
+
+
+class OpdLwtStatus(C.Structure):   # opd_lwt_status
+    _fields_ = [(n, C.c_int32) for n in ("max_tracks", "max_dets", "max_age", "use_optical_flow", "device_ordinal", "n_tracks", "next_id", "n_points",
+                                         "last_launches", "last_waits")] + [("iou_threshold", C.c_double)]
+
+
 # name -> (restype, argtypes): every symbol include/opd_detr.h declares
 API = {
     "opd_detr_create": (C.c_int, [C.POINTER(OpdConfig), C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
@@ -176,6 +195,13 @@ API = {
     "opd_track_update": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
     "opd_track_get": (C.c_int, [C.c_void_p, C.POINTER(OpdTrackRec), C.c_int, C.POINTER(C.c_int)]),
     "opd_assign": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "opd_lwt_create": (C.c_int, [C.POINTER(OpdLwtConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "opd_lwt_destroy": (None, [C.c_void_p]),
+    "opd_lwt_reset": (C.c_int, [C.c_void_p]),
+    "opd_lwt_info": (C.c_int, [C.c_void_p, C.POINTER(OpdLwtStatus)]),
+    "opd_lwt_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "opd_lwt_interpolate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(OpdLwtRec), C.c_int, C.POINTER(C.c_int)]),
+    "opd_lwt_get": (C.c_int, [C.c_void_p, C.POINTER(OpdLwtTrack), C.c_int, C.POINTER(C.c_int)]),
     "opd_detr_detect_frames_floor": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.POINTER(OpdDet), C.POINTER(C.c_int32),
                                                 C.c_void_p]),
     "opd_last_error": (C.c_char_p, []),
@@ -290,6 +316,8 @@ TEST_API = {
     # tracker hooks (csrc/opd_track_test_api.cpp)
     "opd_track_test_matrices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "opd_track_test_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    # hybrid-tracker hook (csrc/opd_lwt_test_api.cpp): handle, next_xy, status, records, capacity, count
+    "opd_test_lwt_interpolate_scripted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OpdLwtRec), C.c_int, C.POINTER(C.c_int)]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -117,35 +117,37 @@ extern "C" void opd_flow_destroy(opd_flow* f) {
     delete f;
 }
 
-extern "C" int opd_flow_set_reference(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w) {
-    ApiScope api_scope;
-    RCCHK(check_frame(f, "opd_flow_set_reference", bgr, mem_kind, h, w));
+// ---- the two entry points in halves: everything up to the wait (enqueue) and what follows it (finish).  opd_lwt.cpp puts launches of its
+//      own on the handle's stream between the two and waits itself.
+int opd::flow_enqueue_reference(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, int which) {
+    RCCHK(check_frame(f, who, bgr, mem_kind, h, w));
     HIPCHK(hipSetDevice(f->device));
     f->has_ref = f->other_valid = false;   // (a failure below leaves no reference)
     f->h = h; f->w = w;
     f->top = plan_levels(h, w, f->cfg.win, f->cfg.max_level, f->lh, f->lw, f->lp);
-    RCCHK(enqueue_pyramid(f, f->ref, bgr, mem_kind, h, w, 0));
-    HIPCHK(hipStreamSynchronize(f->stream));
-    f->has_ref = true;
-    return OPD_OK;
+    return enqueue_pyramid(f, which, bgr, mem_kind, h, w, 0);
 }
 
-extern "C" int opd_flow_track(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w, const float* pts_xy, int n, float* next_xy,
-                              uint8_t* status) {
-    ApiScope api_scope;
-    RCCHK(check_frame(f, "opd_flow_track", bgr, mem_kind, h, w));
+void opd::flow_finish_reference(opd_flow* f, int which) {
+    f->ref = which;
+    f->has_ref = true;
+}
+
+int opd::flow_enqueue_track(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, const float* host_pts, int n, const float* d_pts,
+                            float* d_next, uint8_t* d_status) {
+    const std::string me(who);
+    RCCHK(check_frame(f, who, bgr, mem_kind, h, w));
     if (n < 0 || n > f->cfg.max_points)
-        return fail(OPD_EINVAL, "opd_flow_track: " + std::to_string(n) + " points, the handle was created for up to " + std::to_string(f->cfg.max_points));
-    if (n > 0 && (!pts_xy || !next_xy || !status)) return fail(OPD_EINVAL, "opd_flow_track: null point, result or status buffer");
-    if (!f->has_ref) return fail(OPD_ESTATE, "opd_flow_track: no reference frame yet (call opd_flow_set_reference first)");
+        return fail(OPD_EINVAL, me + ": " + std::to_string(n) + " points, the handle was created for up to " + std::to_string(f->cfg.max_points));
+    if (!f->has_ref) return fail(OPD_ESTATE, me + ": no reference frame yet (call opd_flow_set_reference first)");
     if (h != f->h || w != f->w)
-        return fail(OPD_EINVAL, "opd_flow_track: frame of " + std::to_string(h) + " x " + std::to_string(w) + " pixels, the reference has " +
+        return fail(OPD_EINVAL, me + ": frame of " + std::to_string(h) + " x " + std::to_string(w) + " pixels, the reference has " +
                                     std::to_string(f->h) + " x " + std::to_string(f->w));
     HIPCHK(hipSetDevice(f->device));
     const int cur = 1 - f->ref;
     f->other_valid = false;
-    const size_t pts_bytes = (size_t)n * 8;
-    if (n) memcpy(f->io.host, pts_xy, pts_bytes);
+    const size_t pts_bytes = host_pts ? (size_t)n * 8 : 0;
+    if (pts_bytes) memcpy(f->io.host, host_pts, pts_bytes);
     RCCHK(enqueue_pyramid(f, cur, bgr, mem_kind, h, w, pts_bytes));
     if (n) {
         FlowParams p{};
@@ -157,18 +159,43 @@ extern "C" int opd_flow_track(opd_flow* f, const uint8_t* bgr, int mem_kind, int
         p.max_iter = f->cfg.max_iter;
         p.eps2 = f->cfg.epsilon < 0.f ? -1.f : f->cfg.epsilon * f->cfg.epsilon;
         p.min_eig = f->cfg.min_eig_threshold;
-        p.pts = reinterpret_cast<const float*>(f->io.dev);
-        p.next = reinterpret_cast<float*>(f->io.dev + f->out_off);
-        p.status = f->io.dev + f->out_off + pts_bytes;
+        p.pts = d_pts;
+        p.next = d_next;
+        p.status = d_status;
         HIPCHK(opd_launch_flow_lk(p, f->stream));
-        HIPCHK(hipMemcpyAsync(f->io.host + f->out_off, f->io.dev + f->out_off, pts_bytes + (size_t)n, hipMemcpyDeviceToHost, f->stream));
     }
+    return OPD_OK;
+}
+
+void opd::flow_finish_track(opd_flow* f) {
+    f->ref = 1 - f->ref;   // the frame just seen is the reference of the next call
+    f->other_valid = true;
+}
+
+extern "C" int opd_flow_set_reference(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w) {
+    ApiScope api_scope;
+    RCCHK(flow_enqueue_reference(f, "opd_flow_set_reference", bgr, mem_kind, h, w, f ? f->ref : 0));
+    HIPCHK(hipStreamSynchronize(f->stream));
+    flow_finish_reference(f, f->ref);
+    return OPD_OK;
+}
+
+extern "C" int opd_flow_track(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w, const float* pts_xy, int n, float* next_xy,
+                              uint8_t* status) {
+    ApiScope api_scope;
+    RCCHK(check_frame(f, "opd_flow_track", bgr, mem_kind, h, w));
+    if (n < 0 || n > f->cfg.max_points)
+        return fail(OPD_EINVAL, "opd_flow_track: " + std::to_string(n) + " points, the handle was created for up to " + std::to_string(f->cfg.max_points));
+    if (n > 0 && (!pts_xy || !next_xy || !status)) return fail(OPD_EINVAL, "opd_flow_track: null point, result or status buffer");
+    const size_t pts_bytes = (size_t)n * 8;
+    RCCHK(flow_enqueue_track(f, "opd_flow_track", bgr, mem_kind, h, w, n ? pts_xy : nullptr, n, reinterpret_cast<const float*>(f->io.dev),
+                             reinterpret_cast<float*>(f->io.dev + f->out_off), f->io.dev + f->out_off + pts_bytes));
+    if (n) HIPCHK(hipMemcpyAsync(f->io.host + f->out_off, f->io.dev + f->out_off, pts_bytes + (size_t)n, hipMemcpyDeviceToHost, f->stream));
     HIPCHK(hipStreamSynchronize(f->stream));
     if (n) {
         memcpy(next_xy, f->io.host + f->out_off, pts_bytes);
         memcpy(status, f->io.host + f->out_off + pts_bytes, (size_t)n);
     }
-    f->ref = cur;   // the frame just seen is the reference of the next call
-    f->other_valid = true;
+    flow_finish_track(f);
     return OPD_OK;
 }

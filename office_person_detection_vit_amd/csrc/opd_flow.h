@@ -47,3 +47,16 @@ struct opd_flow {
     opd::Staging io;                           // page-locked: [points | frame] up, [next | status] down; device: [points | frame] and, behind it, [next | status]
     size_t pts_bytes = 0, frame_off = 0, out_off = 0;
 };
+
+// opd_flow_set_reference and opd_flow_track in two halves each: everything up to the wait, on the handle's stream, and the bookkeeping after
+// it.  The tracker handle of opd_lwt.cpp enqueues its own launches between the two and waits once itself.  `which`: the pyramid the new
+// reference is built into (f->ref for opd_flow_set_reference; 1 - f->ref keeps the old reference intact until the finish).  The track half
+// reads its points at `d_pts` on the device (`host_pts`, when given, are staged and uploaded there first: d_pts is then the head of io.dev)
+// and leaves LK's results at `d_next` / `d_status` on the device.
+namespace opd {
+int flow_enqueue_reference(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, int which);
+void flow_finish_reference(opd_flow* f, int which);
+int flow_enqueue_track(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, const float* host_pts, int n, const float* d_pts,
+                       float* d_next, uint8_t* d_status);
+void flow_finish_track(opd_flow* f);
+}  // namespace opd

@@ -1,8 +1,8 @@
 """``HipOpticalFlowTracker``: the reference's ``OpticalFlowTracker`` (src/tracking/lightweight_tracker.py:57-208) on the device.
 
 Same constructor, attributes and methods; gray conversion, pyramid and pyramidal Lucas-Kanade run in ``csrc/kernels_flow.hip`` behind
-the ``opd_flow_*`` calls of ``include/opd_detr.h``.  The reference's ``LightweightTracker`` keeps its Kalman and IoU logic and takes
-this class as its ``of_tracker``.  The previous frame lives on the device as a gray pyramid (there is no ``prev_gray`` array here)."""
+the ``opd_flow_*`` calls of ``include/opd_detr.h``.  The reference's ``LightweightTracker`` can keep its Kalman and IoU logic and take
+this class as its ``of_tracker``; ``HipLightweightTracker`` (lightweight_tracker.py) replaces the whole of it.  The previous frame lives on the device as a gray pyramid (there is no ``prev_gray`` array here)."""
 
 from __future__ import annotations
 
