@@ -375,21 +375,22 @@ static int clone_impl(const opd_detr* src, opd_detr** out) {
 
 extern "C" {
 
-const char* opd_version(void) { return "opd_hip 0.2 gfx950 (fp16 MFMA operands, fp32 accumulate; OPD_FLAG_BF16: bf16 operands)"; }
+const char* opd_version(void) {
+    const char* text = "";
+    (void)api_call_unlocked("opd_version", [&] { text = "opd_hip 0.2 gfx950 (fp16 MFMA operands, fp32 accumulate; OPD_FLAG_BF16: bf16 operands)"; return OPD_OK; });
+    return text;
+}
 
-int opd_detr_create(const opd_config* cfg, const char* weights_path, int device_ordinal, opd_detr** out) {
-    ApiScope api_scope;
+int opd_detr_create(const opd_config* cfg, const char* weights_path, int device_ordinal, opd_detr** out) { return api_call("opd_detr_create", [&] {
     if (out) *out = nullptr;
-    return guarded("opd_detr_create", [&] { return create_impl(cfg, weights_path, device_ordinal, out); });
-}
-int opd_detr_clone(const opd_detr* src, opd_detr** out) {
-    ApiScope api_scope;
+    return create_impl(cfg, weights_path, device_ordinal, out);
+}, API_CREATE); }
+int opd_detr_clone(const opd_detr* src, opd_detr** out) { return api_call("opd_detr_clone", [&] {
     if (out) *out = nullptr;
-    return guarded("opd_detr_clone", [&] { return clone_impl(src, out); });
-}
-void opd_detr_destroy(opd_detr* m) {
-    ApiScope api_scope;
-    if (!m) return;
+    return clone_impl(src, out);
+}); }
+void opd_detr_destroy(opd_detr* m) { (void)api_call("opd_detr_destroy", [&]() -> int {
+    if (!m) return OPD_OK;
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     comm_detach_all(m);   // communicator lanes bound to this handle refuse work from here on (their own destroy still frees them)
@@ -403,14 +404,15 @@ void opd_detr_destroy(opd_detr* m) {
     if (m->h_floor) { (void)hipHostFree(m->h_floor); m->h_floor = nullptr; }
     for (auto& e : m->ev)
         if (e) (void)hipEventDestroy(e);
-    for (auto& e : m->event_pool) (void)hipEventDestroy(e);
+    m->timer.release();
     drop_graphs(m);
     drop_streams(m);
     delete m;
     ++g_handle_epoch;
-}
+    return OPD_OK;
+}); }
 
-int opd_detr_info(const opd_detr* m, opd_model_info* info) {
+int opd_detr_info(const opd_detr* m, opd_model_info* info) { return api_call_unlocked("opd_detr_info", [&]() -> int {
     if (!m || !info) return fail(OPD_EINVAL, "opd_detr_info: null argument");
     for (int i = 0; i < 4; ++i) info->depths[i] = m->arch.depths[i];
     info->d_model = m->arch.d_model; info->heads = m->arch.heads; info->ffn_dim = m->arch.ffn;
@@ -420,36 +422,32 @@ int opd_detr_info(const opd_detr* m, opd_model_info* info) {
     info->device_ordinal = m->device;
     info->weight_bytes_device = m->weight_bytes; info->workspace_bytes_device = m->workspace_bytes;
     return OPD_OK;
-}
+}); }
 
 int opd_detr_forward(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W, float* logits,
-                     float* boxes, float* enc_features) {
-    ApiScope api_scope;
+                     float* boxes, float* enc_features) { return api_call("opd_detr_forward", [&]() -> int {
     return opd_detr_forward_ragged(m, pixels, pixel_format, mem_kind, B, H, W, nullptr, logits, boxes, enc_features);
-}
+}); }
 int opd_detr_forward_ragged(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W,
-                            const int32_t* valid_hw, float* logits, float* boxes, float* enc_features) {
-    ApiScope api_scope;
+                            const int32_t* valid_hw, float* logits, float* boxes, float* enc_features) { return api_call("opd_detr_forward_ragged", [&]() -> int {
     RCCHK(check_shape(m, pixels, pixel_format, mem_kind, B, H, W));
     HIPCHK(hipSetDevice(m->device));
     return forward_device(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, valid_hw, logits, boxes, enc_features);
-}
-int opd_detr_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, opd_det* out, int32_t* counts) {
-    ApiScope api_scope;
+}); }
+int opd_detr_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, opd_det* out, int32_t* counts) { return api_call("opd_detr_postprocess", [&]() -> int {
     if (!m || !out || !counts) return fail(OPD_EINVAL, "opd_detr_postprocess: null argument");
     if (m->last_B == 0) return fail(OPD_ESTATE, "opd_detr_postprocess called before any forward");
     HIPCHK(hipSetDevice(m->device));
     return deliver_records(m, {threshold, orig_hw, out, counts, OPD_MEM_HOST, WAIT_BLOCKING}, 0, 0, nullptr);
-}
-int opd_detr_set_nms(opd_detr* m, int person_label, float nms_threshold) {
+}); }
+int opd_detr_set_nms(opd_detr* m, int person_label, float nms_threshold) { return api_call_unlocked("opd_detr_set_nms", [&]() -> int {
     if (!m) return fail(OPD_EINVAL, "null model handle");
     if (nms_threshold != nms_threshold) return fail(OPD_EINVAL, "opd_detr_set_nms: the threshold is NaN");
     m->nms_label = person_label;
     m->nms_threshold = nms_threshold < 0.f ? -1.0f : nms_threshold;
     return OPD_OK;
-}
-int opd_detr_nms_records(opd_detr* m, opd_det* dets, int32_t* counts, int n_frames, int stride, int person_label, float nms_threshold) {
-    ApiScope api_scope;
+}); }
+int opd_detr_nms_records(opd_detr* m, opd_det* dets, int32_t* counts, int n_frames, int stride, int person_label, float nms_threshold) { return api_call("opd_detr_nms_records", [&]() -> int {
     if (!m) return fail(OPD_EINVAL, "null model handle");
     if (n_frames < 0 || stride < 1 || stride > OPD_NMS_MAX) return fail(OPD_EINVAL, "opd_detr_nms_records: n_frames < 0, or a stride outside [1, 128]");
     if (nms_threshold != nms_threshold) return fail(OPD_EINVAL, "opd_detr_nms_records: the threshold is NaN");
@@ -467,9 +465,8 @@ int opd_detr_nms_records(opd_detr* m, opd_det* dets, int32_t* counts, int n_fram
         return fail(OPD_EINVAL, "opd_detr_nms_records: a frame holds more records than its slots (left as it was)");
     }
     return OPD_OK;
-}
-int opd_detr_resize_u8(opd_detr* m, const uint8_t* frames, int B, int h, int w, int out_h, int out_w, uint8_t* out) {
-    ApiScope api_scope;
+}); }
+int opd_detr_resize_u8(opd_detr* m, const uint8_t* frames, int B, int h, int w, int out_h, int out_w, uint8_t* out) { return api_call("opd_detr_resize_u8", [&]() -> int {
     if (!m) return fail(OPD_EINVAL, "null model handle");
     if (!frames || !out) return fail(OPD_EINVAL, "opd_detr_resize_u8: null buffer");
     uint8_t dummy = 0;
@@ -479,31 +476,27 @@ int opd_detr_resize_u8(opd_detr* m, const uint8_t* frames, int B, int h, int w, 
     HIPCHK(hipMemcpyAsync(out, m->d_u8, (size_t)B * out_h * out_w * 3, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     return OPD_OK;
-}
+}); }
 int opd_detr_forward_resized(opd_detr* m, const uint8_t* frames, int mem_kind, int B, int h, int w, int H, int W, float* logits,
-                             float* boxes, float* enc_features) {
-    ApiScope api_scope;
+                             float* boxes, float* enc_features) { return api_call("opd_detr_forward_resized", [&]() -> int {
     RCCHK(check_shape(m, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, B, H, W));
     HIPCHK(hipSetDevice(m->device));
     return forward_device(m, {SRC_BLOCK, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, h, w}, B, H, W, nullptr, logits, boxes, enc_features);
-}
+}); }
 int opd_detr_detect(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W, float threshold,
-                    const int32_t* orig_hw, opd_det* out, int32_t* counts) {
-    ApiScope api_scope;
+                    const int32_t* orig_hw, opd_det* out, int32_t* counts) { return api_call("opd_detr_detect", [&]() -> int {
     return opd_detr_detect_ragged(m, pixels, pixel_format, mem_kind, B, H, W, nullptr, threshold, orig_hw, out, counts);
-}
+}); }
 int opd_detr_detect_ragged(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W,
-                           const int32_t* valid_hw, float threshold, const int32_t* orig_hw, opd_det* out, int32_t* counts) {
-    ApiScope api_scope;
+                           const int32_t* valid_hw, float threshold, const int32_t* orig_hw, opd_det* out, int32_t* counts) { return api_call("opd_detr_detect_ragged", [&]() -> int {
     RCCHK(check_shape(m, pixels, pixel_format, mem_kind, B, H, W));
     if (!out || !counts) return fail(OPD_EINVAL, "opd_detr_detect: null output buffer");
     RCCHK(check_device_outputs(mem_kind, out, counts, "opd_detr_detect"));
     HIPCHK(hipSetDevice(m->device));
     return detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, valid_hw, {threshold, orig_hw, out, counts, mem_kind, WAIT_BLOCKING});
-}
+}); }
 int opd_detr_detect_async(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W, float threshold,
-                          const int32_t* orig_hw, opd_det* out, int32_t* counts, int* ticket) {
-    ApiScope api_scope;
+                          const int32_t* orig_hw, opd_det* out, int32_t* counts, int* ticket) { return api_call("opd_detr_detect_async", [&]() -> int {
     RCCHK(check_shape(m, pixels, pixel_format, mem_kind, B, H, W));
     if (!out || !counts || !ticket) return fail(OPD_EINVAL, "opd_detr_detect_async: null argument");
     RCCHK(check_device_outputs(mem_kind, out, counts, "opd_detr_detect_async"));
@@ -516,9 +509,8 @@ int opd_detr_detect_async(opd_detr* m, const void* pixels, int pixel_format, int
     RCCHK(detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, nullptr, {threshold, orig_hw, out, counts, mem_kind, WAIT_TICKET, t}));
     *ticket = t;
     return OPD_OK;
-}
-int opd_detr_wait(opd_detr* m, int ticket) {
-    ApiScope api_scope;
+}); }
+int opd_detr_wait(opd_detr* m, int ticket) { return api_call("opd_detr_wait", [&]() -> int {
     if (!m || ticket < 0 || ticket > 3 || !m->ev_async[ticket]) return fail(OPD_EINVAL, "opd_detr_wait: bad handle or ticket");
     if (!m->async_pending[ticket]) return fail(OPD_ESTATE, "opd_detr_wait: this ticket is not outstanding (already waited for?)");
     HIPCHK(hipSetDevice(m->device));
@@ -530,16 +522,15 @@ int opd_detr_wait(opd_detr* m, int ticket) {
     }
     m->async_pending[ticket] = false;
     return OPD_OK;
-}
+}); }
 int opd_detr_detect_resized(opd_detr* m, const uint8_t* frames, int mem_kind, int B, int h, int w, int H, int W, float threshold,
-                            opd_det* out, int32_t* counts) {
-    ApiScope api_scope;
+                            opd_det* out, int32_t* counts) { return api_call("opd_detr_detect_resized", [&]() -> int {
     RCCHK(check_shape(m, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, B, H, W));
     if (!out || !counts) return fail(OPD_EINVAL, "opd_detr_detect_resized: null output buffer");
     RCCHK(check_device_outputs(mem_kind, out, counts, "opd_detr_detect_resized"));
     HIPCHK(hipSetDevice(m->device));
     return detect_pipeline(m, {SRC_BLOCK, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, h, w}, B, H, W, nullptr, {threshold, nullptr, out, counts, mem_kind, WAIT_BLOCKING});
-}
+}); }
 
 // The three frame-list entries: the argument checks they share, worded with the entry's own name
 static int check_frame_list(opd_detr* m, const uint8_t* const* frames, int mem_kind, int B, int H, int W, bool have_outputs, const std::string& who) {
@@ -550,31 +541,28 @@ static int check_frame_list(opd_detr* m, const uint8_t* const* frames, int mem_k
     return OPD_OK;
 }
 int opd_detr_detect_frames(opd_detr* m, const uint8_t* const* frames, int mem_kind, int B, int h, int w, int H, int W, float threshold,
-                           opd_det* out, int32_t* counts) {
-    ApiScope api_scope;
+                           opd_det* out, int32_t* counts) { return api_call("opd_detr_detect_frames", [&]() -> int {
     if (!m) return fail(OPD_EINVAL, "null model handle");
     if (mem_kind != OPD_MEM_HOST && mem_kind != OPD_MEM_HOST_PIXELS_DEVICE_OUT) return fail(OPD_EINVAL, "opd_detr_detect_frames takes host frames");
     RCCHK(check_frame_list(m, frames, mem_kind, B, H, W, out && counts, "opd_detr_detect_frames"));
     RCCHK(check_device_outputs(mem_kind, out, counts, "opd_detr_detect_frames"));
     HIPCHK(hipSetDevice(m->device));
     return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, h, w}, B, H, W, nullptr, {threshold, nullptr, out, counts, mem_kind, WAIT_BLOCKING});
-}
+}); }
 
 int opd_detr_detect_frames_features(opd_detr* m, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold, int label,
-                                    opd_det* out, int32_t* counts, float* features) {
-    ApiScope api_scope;
+                                    opd_det* out, int32_t* counts, float* features) { return api_call("opd_detr_detect_frames_features", [&]() -> int {
     RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && features, "opd_detr_detect_frames_features"));
     if (m->arch.d_model != 256) return fail(OPD_EINVAL, "opd_detr_detect_frames_features: the pooling kernel is built for d_model = 256");
     HIPCHK(hipSetDevice(m->device));
     return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr,
                            {threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_ROI, label, features});
-}
+}); }
 
 // The colour-histogram twin: same upload, same forward and post-process; the histogram kernels read the CAMERA-resolution frames this call
 // has just put on the device (d_src when it resizes, d_u8 when it does not) under the boxes of the records the post-process left there.
 int opd_detr_detect_frames_color(opd_detr* m, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold, int label,
-                                 opd_det* out, int32_t* counts, float* features) {
-    ApiScope api_scope;
+                                 opd_det* out, int32_t* counts, float* features) { return api_call("opd_detr_detect_frames_color", [&]() -> int {
     RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && features, "opd_detr_detect_frames_color"));
     if (m->arch.d_model != OPD_COLOR_DIM) return fail(OPD_EINVAL, "opd_detr_detect_frames_color: the feature area of the handle is sized for d_model = 256");
     if (h < 1 || w < 1 || h > OPD_COLOR_MAX_EDGE || w > OPD_COLOR_MAX_EDGE)
@@ -584,13 +572,12 @@ int opd_detr_detect_frames_color(opd_detr* m, const uint8_t* const* frames, int 
     if (!m->d_color_acc) RCCHK(dalloc(m, &m->d_color_acc, (size_t)m->cfg.max_batch * m->arch.queries * OPD_COLOR_ACC_WORDS, false));
     return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr,
                            {threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_COLOR, label, features});
-}
+}); }
 
 // The floor-map twin: same upload, forward and post-process; one wave per record slot then maps the foot point of every record of the class
 // with `f`'s model (read-only device tables: any stream may read them), and the rows travel behind the records before the one wait.
 int opd_detr_detect_frames_floor(opd_detr* m, opd_floor* f, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
-                                 int label, opd_det* out, int32_t* counts, opd_floor_rec* floor) {
-    ApiScope api_scope;
+                                 int label, opd_det* out, int32_t* counts, opd_floor_rec* floor) { return api_call("opd_detr_detect_frames_floor", [&]() -> int {
     if (!f) return fail(OPD_EINVAL, "opd_detr_detect_frames_floor: null floor-map handle");
     RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && floor, "opd_detr_detect_frames_floor"));
     if (f->device != m->device)
@@ -603,14 +590,13 @@ int opd_detr_detect_frames_floor(opd_detr* m, opd_floor* f, const uint8_t* const
     }
     return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr,
                            {threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_NONE, label, nullptr, f, floor});
-}
+}); }
 
 // The Re-ID twin: same upload, forward and post-process; two small kernels then pick the records of the class and plan their crops from the boxes
 // the Python shim derives, read in place from the CAMERA-resolution frames this call has just put on the device; `r`'s forward runs on its own
 // stream between two events, and its rows travel behind the records before the one wait.
 int opd_detr_detect_frames_reid(opd_detr* m, opd_reid* r, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold, int label,
-                                int slots, opd_det* out, int32_t* counts, float* features, int32_t* slot_map, int32_t* n_person) {
-    ApiScope api_scope;
+                                int slots, opd_det* out, int32_t* counts, float* features, int32_t* slot_map, int32_t* n_person) { return api_call("opd_detr_detect_frames_reid", [&]() -> int {
     if (!r) return fail(OPD_EINVAL, "opd_detr_detect_frames_reid: null Re-ID handle");
     RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && features && slot_map && n_person, "opd_detr_detect_frames_reid"));
     RCCHK(reid_fused_check(r, m->device, slots, "opd_detr_detect_frames_reid"));
@@ -618,25 +604,23 @@ int opd_detr_detect_frames_reid(opd_detr* m, opd_reid* r, const uint8_t* const* 
         return fail(OPD_EINVAL, "opd_detr_detect_frames_reid: source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
     HIPCHK(hipSetDevice(m->device));
     RecordSink sink{threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_REID, label, features, nullptr, nullptr, r, slots, slot_map, n_person};
-    return guarded("opd_detr_detect_frames_reid", [&] { return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr, sink); });
-}
+    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr, sink);
+}); }
 
-int opd_host_alloc(size_t bytes, void** out) {
-    ApiScope api_scope;
+int opd_host_alloc(size_t bytes, void** out) { return api_call("opd_host_alloc", [&]() -> int {
     if (!out || bytes == 0) return fail(OPD_EINVAL, "opd_host_alloc: null output or zero size");
     *out = nullptr;
     HIPCHK(hipHostMalloc(out, bytes, hipHostMallocDefault));
     return OPD_OK;
-}
-void opd_host_free(void* p) {
-    ApiScope api_scope;
+}); }
+void opd_host_free(void* p) { (void)api_call("opd_host_free", [&]() -> int {
     if (p) (void)hipHostFree(p);
-}
+    return OPD_OK;
+}); }
 
 int opd_similarity_matrix(int device_ordinal, const float* feats1, const float* boxes1, const uint8_t* has1, int n1,
                           const float* feats2, const float* boxes2, const uint8_t* has2, int n2, int D, double appearance_weight,
-                          double motion_weight, int as_distance, float* out) {
-    ApiScope api_scope;
+                          double motion_weight, int as_distance, float* out) { return api_call("opd_similarity_matrix", [&]() -> int {
     if (n1 < 0 || n2 < 0 || D < 1) return fail(OPD_EINVAL, "opd_similarity_matrix: bad sizes");
     if (n1 == 0 || n2 == 0) return OPD_OK;
     if (!boxes1 || !boxes2 || !out) return fail(OPD_EINVAL, "opd_similarity_matrix: null boxes / output");
@@ -652,10 +636,9 @@ int opd_similarity_matrix(int device_ordinal, const float* feats1, const float* 
     HIPCHK(opd_launch_similarity_matrix(df1, db1, dh1, n1, df2, db2, dh2, n2, D, appearance_weight, motion_weight, as_distance, dout, nullptr));
     HIPCHK(hipMemcpy(out, dout, (size_t)n1 * n2 * 4, hipMemcpyDeviceToHost));
     return OPD_OK;
-}
+}); }
 
-int opd_detr_roi_features(opd_detr* m, int frame, const float* boxes_xywh, int n, int orig_h, int orig_w, float* features) {
-    ApiScope api_scope;
+int opd_detr_roi_features(opd_detr* m, int frame, const float* boxes_xywh, int n, int orig_h, int orig_w, float* features) { return api_call("opd_detr_roi_features", [&]() -> int {
     if (!m || (n > 0 && (!boxes_xywh || !features))) return fail(OPD_EINVAL, "opd_detr_roi_features: null argument");
     if (m->last_B == 0) return fail(OPD_ESTATE, "opd_detr_roi_features called before any forward");
     if (frame < 0 || frame >= m->last_B || n < 0 || n > 128 || orig_h <= 0 || orig_w <= 0)
@@ -678,10 +661,9 @@ int opd_detr_roi_features(opd_detr* m, int frame, const float* boxes_xywh, int n
     HIPCHK(hipMemcpyAsync(features, m->d_roi_out, (size_t)n * m->arch.d_model * 4, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     return OPD_OK;
-}
+}); }
 
-int opd_detr_attention_map(opd_detr* m, int frame, int layer, const int32_t* queries, int n_queries, float* out, int out_capacity) {
-    ApiScope api_scope;
+int opd_detr_attention_map(opd_detr* m, int frame, int layer, const int32_t* queries, int n_queries, float* out, int out_capacity) { return api_call("opd_detr_attention_map", [&]() -> int {
     if (!m || !out) return fail(OPD_EINVAL, "opd_detr_attention_map: null argument");
     if (m->last_B == 0) return fail(OPD_ESTATE, "opd_detr_attention_map called before any forward");
     const int L = m->arch.dec_layers, Q = m->arch.queries, D = m->arch.d_model;
@@ -708,11 +690,10 @@ int opd_detr_attention_map(opd_detr* m, int frame, int layer, const int32_t* que
     HIPCHK(hipMemcpyAsync(out, m->d_amap, (size_t)hw * 4, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     return OPD_OK;
-}
+}); }
 
-int opd_detr_set_profiling(opd_detr* m, int enabled) {
+int opd_detr_set_profiling(opd_detr* m, int enabled) { return api_call("opd_detr_set_profiling", [&]() -> int {
     if (!m) return fail(OPD_EINVAL, "null model handle");
-    ApiScope api_scope;
     const int mode = enabled == 2 ? 2 : (enabled ? 1 : 0);
     if (mode != m->profiling) {   // the stage marks of mode 2 are nodes of the captured graph: graphs of another mode do not carry them
         HIPCHK(hipSetDevice(m->device));
@@ -721,17 +702,15 @@ int opd_detr_set_profiling(opd_detr* m, int enabled) {
     }
     m->profiling = mode;
     return OPD_OK;
-}
+}); }
 
-int opd_detr_stage_times(const opd_detr* m, float* ms8) {
-    ApiScope api_scope;
+int opd_detr_stage_times(const opd_detr* m, float* ms8) { return api_call("opd_detr_stage_times", [&]() -> int {
     if (!m || !ms8) return fail(OPD_EINVAL, "opd_detr_stage_times: null argument");
     for (int i = 0; i < 8; ++i) ms8[i] = m->stage_ms[i];
     return OPD_OK;
-}
+}); }
 
-int opd_detr_kernel_table(const opd_detr* m, opd_kernel_stat* out, int capacity, int* count) {
-    ApiScope api_scope;
+int opd_detr_kernel_table(const opd_detr* m, opd_kernel_stat* out, int capacity, int* count) { return api_call("opd_detr_kernel_table", [&]() -> int {
     if (!m || !count || capacity < 0 || (capacity > 0 && !out)) return fail(OPD_EINVAL, "opd_detr_kernel_table: bad argument");
     *count = (int)m->ktable.size();
     for (int i = 0; i < capacity && i < (int)m->ktable.size(); ++i) {
@@ -741,13 +720,12 @@ int opd_detr_kernel_table(const opd_detr* m, opd_kernel_stat* out, int capacity,
         out[i].launches = r.launches; out[i].ms = r.ms; out[i].flops = r.flops;
     }
     return OPD_OK;
-}
+}); }
 
-int opd_detr_kernel_times(const opd_detr* m, float* ms4, int32_t* launches4, double* flops4) {
-    ApiScope api_scope;
+int opd_detr_kernel_times(const opd_detr* m, float* ms4, int32_t* launches4, double* flops4) { return api_call("opd_detr_kernel_times", [&]() -> int {
     if (!m || !ms4 || !launches4 || !flops4) return fail(OPD_EINVAL, "opd_detr_kernel_times: null argument");
     for (int i = 0; i < 4; ++i) { ms4[i] = m->class_ms[i]; launches4[i] = m->class_launches[i]; flops4[i] = m->class_flops[i]; }
     return OPD_OK;
-}
+}); }
 
 }  // extern "C"

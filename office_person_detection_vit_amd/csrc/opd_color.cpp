@@ -26,8 +26,7 @@ ColorScratch g_scratch[16];   // one node: <= 16 GPUs
 }  // namespace
 
 extern "C" int opd_color_features(int device_ordinal, const uint8_t* const* frames, const int32_t* frame_hw, int n_frames, int mem_kind,
-                                  const float* boxes_xywh, const int32_t* box_frame, int n_boxes, float* out) {
-    ApiScope api_scope;
+                                  const float* boxes_xywh, const int32_t* box_frame, int n_boxes, float* out) { return api_call("opd_color_features", [&]() -> int {
     if (n_boxes < 0) return fail(OPD_EINVAL, "opd_color_features: negative box count");
     if (n_boxes == 0) return OPD_OK;
     if (!frames || !frame_hw || !boxes_xywh || !out || n_frames < 1) return fail(OPD_EINVAL, "opd_color_features: null argument or no frames");
@@ -119,4 +118,4 @@ extern "C" int opd_color_features(int device_ordinal, const uint8_t* const* fram
     HIPCHK(hipMemcpyAsync(out, cp.out, (size_t)n_boxes * OPD_COLOR_DIM * 4, hipMemcpyDeviceToHost, s.stream));
     HIPCHK(hipStreamSynchronize(s.stream));
     return OPD_OK;
-}
+}); }

@@ -162,7 +162,7 @@ void opd::comm_detach_all(opd_detr* m) {
 
 extern "C" {
 
-int opd_comm_unique_id(void* id128) {
+int opd_comm_unique_id(void* id128) { return api_call("opd_comm_unique_id", [&]() -> int {
     if (!id128) return fail(OPD_EINVAL, "opd_comm_unique_id: null buffer");
     Rccl& r = rccl();
     if (!r.error.empty()) return fail(OPD_EHIP, "RCCL unavailable: " + r.error);
@@ -171,18 +171,17 @@ int opd_comm_unique_id(void* id128) {
     NCCLCHK(r.GetUniqueId(&id));
     memcpy(id128, &id, sizeof(id));
     return OPD_OK;
-}
+}); }
 
-int opd_comm_available(void) {
+int opd_comm_available(void) { return api_call("opd_comm_available", [&]() -> int {
     Rccl& r = rccl();
     if (!r.error.empty()) return fail(OPD_EHIP, "RCCL unavailable: " + r.error);
     return OPD_OK;
-}
+}); }
 
-int opd_comm_create(const void* id128, int rank, int world, opd_detr* m, opd_comm** out) {
+int opd_comm_create(const void* id128, int rank, int world, opd_detr* m, opd_comm** out) { return api_call("opd_comm_create", [&]() -> int {
     // (the API lock stays held across ncclCommInitRank: it allocates device memory, which must not run beside another thread's stream capture;
     //  set-up only.  A rank whose peers never arrive blocks here: callers bound the set-up with a watchdog, see sharding.py / bench.py)
-    ApiScope api_scope;
     if (out) *out = nullptr;
     if (!id128 || !m || !out || world < 1 || rank < 0 || rank >= world) return fail(OPD_EINVAL, "opd_comm_create: bad argument");
     Rccl& r = rccl();
@@ -196,20 +195,18 @@ int opd_comm_create(const void* id128, int rank, int world, opd_detr* m, opd_com
     memcpy(&id, id128, sizeof(id));
     NCCLCHK(r.CommInitRank(&sh->comm, world, id, rank));
     return make_lane(std::move(sh), m, out);
-}
+}); }
 
-int opd_comm_attach(opd_comm* parent, opd_detr* m, opd_comm** out) {
-    ApiScope api_scope;
+int opd_comm_attach(opd_comm* parent, opd_detr* m, opd_comm** out) { return api_call("opd_comm_attach", [&]() -> int {
     if (out) *out = nullptr;
     if (!parent || !m || !out) return fail(OPD_EINVAL, "opd_comm_attach: null argument");
     if (m->device != parent->sh->device) return fail(OPD_EINVAL, "opd_comm_attach: the handle lives on another device than the communicator");
     HIPCHK(hipSetDevice(m->device));
     return make_lane(parent->sh, m, out);
-}
+}); }
 
-void opd_comm_destroy(opd_comm* c) {
-    ApiScope api_scope;
-    if (!c) return;
+void opd_comm_destroy(opd_comm* c) { (void)api_call("opd_comm_destroy", [&]() -> int {
+    if (!c) return OPD_OK;
     (void)hipSetDevice(c->sh->device);
     (void)hipStreamSynchronize(c->sh->xstream);   // this lane's exchanges, if any, are over
     if (c->m) {
@@ -225,10 +222,10 @@ void opd_comm_destroy(opd_comm* c) {
         if (s.done) (void)hipEventDestroy(s.done);
     }
     delete c;   // (the communicator and its stream go with the last lane: ~CommShared)
-}
+    return OPD_OK;
+}); }
 
-int opd_comm_begin(opd_comm* c, int slots) {
-    ApiScope api_scope;
+int opd_comm_begin(opd_comm* c, int slots) { return api_call("opd_comm_begin", [&]() -> int {
     if (!c || slots < 1) return fail(OPD_EINVAL, "opd_comm_begin: bad argument");
     LANE_ALIVE(c, "opd_comm_begin");
     if (open_set(c)) return fail(OPD_ESTATE, "opd_comm_begin: the exchange begun before has not been issued (opd_comm_exchange)");
@@ -255,11 +252,10 @@ int opd_comm_begin(opd_comm* c, int slots) {
     s.state = 1;
     ++c->n_begun;
     return OPD_OK;
-}
+}); }
 
 int opd_comm_detect(opd_comm* c, int slot0, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W, float threshold,
-                    const int32_t* orig_hw) {
-    ApiScope api_scope;
+                    const int32_t* orig_hw) { return api_call("opd_comm_detect", [&]() -> int {
     if (!c) return fail(OPD_EINVAL, "opd_comm_detect: null communicator");
     LANE_ALIVE(c, "opd_comm_detect");
     opd_detr* m = c->m;
@@ -272,9 +268,9 @@ int opd_comm_detect(opd_comm* c, int slot0, const void* pixels, int pixel_format
     opd_det* recs = reinterpret_cast<opd_det*>(s->d_send) + (size_t)slot0 * Q;
     int32_t* counts = s->d_send + (size_t)s->slots * Q * 8 + slot0;
     return detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, nullptr, {threshold, orig_hw, recs, counts, OPD_MEM_DEVICE, WAIT_NONE});   // (into the lane's send buffer; the wait is opd_comm_wait's)
-}
+}); }
 
-int opd_comm_buffers(opd_comm* c, int slot0, void** records, void** counts) {
+int opd_comm_buffers(opd_comm* c, int slot0, void** records, void** counts) { return api_call_unlocked("opd_comm_buffers", [&]() -> int {
     if (!c || !records || !counts) return fail(OPD_EINVAL, "opd_comm_buffers: null argument");
     LANE_ALIVE(c, "opd_comm_buffers");
     LaneSet* s = open_set(c);
@@ -283,10 +279,9 @@ int opd_comm_buffers(opd_comm* c, int slot0, void** records, void** counts) {
     *records = reinterpret_cast<opd_det*>(s->d_send) + (size_t)slot0 * Q;
     *counts = s->d_send + (size_t)s->slots * Q * 8 + slot0;
     return OPD_OK;
-}
+}); }
 
-int opd_comm_exchange(opd_comm* c) {
-    ApiScope api_scope;
+int opd_comm_exchange(opd_comm* c) { return api_call("opd_comm_exchange", [&]() -> int {
     if (!c) return fail(OPD_EINVAL, "opd_comm_exchange: null communicator");
     LANE_ALIVE(c, "opd_comm_exchange");
     LaneSet* s = open_set(c);
@@ -305,10 +300,9 @@ int opd_comm_exchange(opd_comm* c) {
     }
     s->state = 2;
     return OPD_OK;
-}
+}); }
 
-int opd_comm_wait(opd_comm* c, opd_det* out_all, int32_t* counts_all) {
-    ApiScope api_scope;
+int opd_comm_wait(opd_comm* c, opd_det* out_all, int32_t* counts_all) { return api_call("opd_comm_wait", [&]() -> int {
     if (!c || !out_all || !counts_all) return fail(OPD_EINVAL, "opd_comm_wait: null argument");
     LANE_ALIVE(c, "opd_comm_wait");
     LaneSet& s = c->set[c->n_waited & 1];   // the OLDEST exchange not yet waited for
@@ -326,12 +320,12 @@ int opd_comm_wait(opd_comm* c, opd_det* out_all, int32_t* counts_all) {
     s.state = 0;
     ++c->n_waited;
     return OPD_OK;
-}
+}); }
 
-int opd_comm_info(const opd_comm* c, int* rank, int* world) {
+int opd_comm_info(const opd_comm* c, int* rank, int* world) { return api_call_unlocked("opd_comm_info", [&]() -> int {
     if (!c || !rank || !world) return fail(OPD_EINVAL, "opd_comm_info: null argument");
     *rank = c->sh->rank; *world = c->sh->world;
     return OPD_OK;
-}
+}); }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 // opd_device.h — PRIVATE header of libopd_hip: what every handle (detector, Re-ID, optical flow, floor map, the handle-less colour call)
 // needs from the device short of its own kernels: the error macros, the entry-point lock and the graph guard, device selection, the pointer
-// check, the page-locked / device staging pair, stream capture, the catch-all of the C-ABI, and a holder of temporary device memory.
+// check, the page-locked / device staging pair, stream capture and the graph slot that a handle's cache is made of, the per-launch timer of
+// the profiling modes, a holder of temporary device memory, and api_call: the wrapper (lock, then catch-all) that every function of
+// include/opd_detr.h is defined through (its lock-free form, api_call_unlocked, is opd_host.h's: opd_host.cpp builds without HIP).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -32,13 +34,15 @@
         if (_rc != 0) return _rc; \
     } while (0)
 
+extern thread_local const char* opd_last_kernel_name;   // (opd_kernels.h: OPD_LAUNCH notes the kernel it launches)
+
 namespace opd {
 
 // Stream capture and other threads: the Python shim drives several handles from worker threads (HipDetrDetector(streams=N)).
 // ROCm invalidates a capture in progress when ANOTHER thread allocates or frees memory, pins host memory or runs its
 // one-time eager setup meanwhile, even in thread-local capture mode ("operation failed due to a previous error during
 // capture").  Every entry point therefore holds this lock shared; a capture takes it exclusively for its few milliseconds.
-extern std::shared_mutex g_api_mu;
+// (g_api_mu and tl_api_lock: declared in opd_host.h, defined in opd_host.cpp)
 // Handle churn and captured graphs.  Round 2 saw replays of a graph captured BEFORE another handle was destroyed and a third one
 // created give wrong (finite or NaN) outputs, while the same launches issued eagerly stayed bit-exact; re-capturing after every
 // handle creation / destruction (this epoch) made the symptom go away.  Round 3 went after the cause (profiles/r03_graph_churn_*.txt,
@@ -75,8 +79,7 @@ extern std::shared_mutex g_api_mu;
 // test_graph_replay_survives_foreign_allocations_and_handle_churn runs with the guard OFF at HEAD and passes (round-5 GPU suite).
 extern std::atomic<unsigned> g_handle_epoch;
 extern std::atomic<int> g_graph_guard;   // opd_test_set_graph_guard(0): leave stale-epoch graphs alone (diagnosis only)
-extern thread_local std::shared_lock<std::shared_mutex>* tl_api_lock;
-struct ApiScope {   // first statement of every HIP-calling entry point; entry points calling each other nest harmlessly
+struct ApiScope {   // held by api_call around the body of every HIP-calling entry point; entry points calling each other nest harmlessly
     std::shared_lock<std::shared_mutex> lk;
     bool outer;
     ApiScope() : lk(g_api_mu, std::defer_lock), outer(tl_api_lock == nullptr) {
@@ -124,21 +127,90 @@ int capture_graph(hipStream_t stream, const char* what, F&& body, hipGraphExec_t
     return fail(OPD_EHIP, std::string("hipStreamEndCapture refused ") + what + ": " + hipGetErrorString(ec) + " (OPD_FLAG_NO_GRAPH runs eagerly)");
 }
 
-// No C++ exception may cross the C-ABI: creation parses an untrusted file and allocates, so its body runs under a catch-all.
-template <typename F>
-int guarded(const char* what, F&& body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        return fail(OPD_ENOMEM, std::string(what) + ": out of host memory");
-    } catch (const std::out_of_range& e) {
-        return fail(OPD_ESCHEMA, std::string(what) + ": weight file lacks a tensor the model needs (" + e.what() + ")");
-    } catch (const std::exception& e) {
-        return fail(OPD_EINVAL, std::string(what) + ": " + e.what());
-    } catch (...) {
-        return fail(OPD_EINVAL, std::string(what) + ": unknown C++ exception");
+// One cached graph: the executable and the handle epoch it was captured under.  run() drops a stale executable, captures `body` when the slot
+// is empty, stamps the epoch and launches.  Which slot a call uses, and when it may capture at all, is the owner's policy.
+struct GraphSlot {
+    hipGraphExec_t exec = nullptr;
+    unsigned epoch = 0;
+    void drop() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        exec = nullptr;
     }
+    bool ready() {   // handles came or went since the capture: capture again (see g_handle_epoch)
+        if (exec && graph_stale(epoch)) drop();
+        return exec != nullptr;
+    }
+    template <typename F>
+    int run(hipStream_t stream, const char* what, F&& body) {
+        if (!ready()) {
+            RCCHK(capture_graph(stream, what, body, &exec));
+            epoch = g_handle_epoch.load();
+        }
+        HIPCHK(hipGraphLaunch(exec, stream));
+        return OPD_OK;
+    }
+};
+
+// How every function of include/opd_detr.h that calls HIP is defined: its braces hold one statement,
+//     int opd_x(args) { return api_call("opd_x", [&]() -> int {
+//         ... the body, at a function's usual indentation ...
+//     }); }
+// The shared hold of the entry-point lock first, then the body under the catch-all (opd_host.h: api_call_unlocked, which the entries
+// without a HIP call use directly).  A `void` entry discards the code: its exception is swallowed.  tests/test_host_cpu.py holds every
+// function of the header to this form.
+template <typename F>
+int api_call(const char* name, F&& body, bool create = false) {
+    ApiScope api_scope;
+    return api_call_unlocked(name, body, create);
 }
+
+// Per-launch timing of eager launches (the detector's profiling mode 1, the Re-ID handle's kernel-table hook): begin() and end() bracket
+// a launch with two events of a pool that only grows, and note its class, the kernel the launcher named (OPD_LAUNCH) and its FLOPs.
+struct KernelRow { std::string name; int launches; float ms; double flops; };
+struct LaunchTimer {
+    struct Mark { int cls; const char* name; double flops; hipEvent_t e0, e1; float ms; };   // ms: filled by fold(), < 0 where unreadable
+    std::vector<hipEvent_t> pool;
+    size_t cursor = 0;
+    std::vector<Mark> marks;
+    int begin(hipStream_t s, int cls, double flops) {
+        while (pool.size() < cursor + 2) {
+            hipEvent_t e;
+            HIPCHK(hipEventCreate(&e));
+            pool.push_back(e);
+        }
+        HIPCHK(hipEventRecord(pool[cursor], s));
+        marks.push_back({cls, nullptr, flops, pool[cursor], pool[cursor + 1], -1.f});
+        cursor += 2;
+        opd_last_kernel_name = nullptr;
+        return OPD_OK;
+    }
+    int end(hipStream_t s) {
+        HIPCHK(hipEventRecord(marks.back().e1, s));
+        marks.back().name = opd_last_kernel_name;   // what the launcher just launched: the name rocprofv3 prints, minus namespace and signature
+        return OPD_OK;
+    }
+    void reset() { marks.clear(); cursor = 0; }   // the events are reused
+    void release() {                              // (the owner has drained its stream)
+        reset();
+        for (hipEvent_t e : pool) (void)hipEventDestroy(e);
+        pool.clear();
+    }
+    // The marks (their launches have completed) summed per kernel name into `rows`, appending to the rows already there in first-seen
+    // order; a launch whose launcher named no kernel counts under unnamed[cls].  Returns how many marks could not be read (left out).
+    int fold(std::vector<KernelRow>* rows, const char* const* unnamed) {
+        int unread = 0;
+        for (Mark& mk : marks) {
+            if (hipEventElapsedTime(&mk.ms, mk.e0, mk.e1) != hipSuccess) { (void)hipGetLastError(); mk.ms = -1.f; ++unread; continue; }
+            const char* nm = mk.name ? mk.name : unnamed[mk.cls];
+            KernelRow* row = nullptr;
+            for (auto& r : *rows)
+                if (r.name == nm) { row = &r; break; }
+            if (!row) { rows->push_back({nm, 0, 0.f, 0.0}); row = &rows->back(); }
+            row->launches += 1; row->ms += mk.ms; row->flops += mk.flops;
+        }
+        return unread;
+    }
+};
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

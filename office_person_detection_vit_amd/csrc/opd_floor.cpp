@@ -134,8 +134,7 @@ void floor_build_tables(const opd_floor_config& c, FloorTables* t) {
     for (int k = 0; k < c.n_zones; ++k) t->zone_rank[order[k]] = k;
 }
 
-extern "C" int opd_floor_create(const opd_floor_config* cfg, int device_ordinal, opd_floor** out) {
-    ApiScope api_scope;
+extern "C" int opd_floor_create(const opd_floor_config* cfg, int device_ordinal, opd_floor** out) { return api_call("opd_floor_create", [&]() -> int {
     if (!out) return fail(OPD_EINVAL, "opd_floor_create: null argument");
     *out = nullptr;
     RCCHK(floor_check_config(cfg));
@@ -182,27 +181,26 @@ extern "C" int opd_floor_create(const opd_floor_config* cfg, int device_ordinal,
     m.zone_rank = reinterpret_cast<const int32_t*>(f->d_model + o_rank);
     *out = f.release();
     return OPD_OK;
-}
+}); }
 
-extern "C" void opd_floor_destroy(opd_floor* f) {
-    if (!f) return;
-    ApiScope api_scope;
+extern "C" void opd_floor_destroy(opd_floor* f) { (void)api_call("opd_floor_destroy", [&]() -> int {
+    if (!f) return OPD_OK;
     (void)hipSetDevice(f->device);
     if (f->stream) { (void)hipStreamSynchronize(f->stream); (void)hipStreamDestroy(f->stream); }
     if (f->d_model) (void)hipFree(f->d_model);
     f->io.release();
     delete f;
-}
+    return OPD_OK;
+}); }
 
-extern "C" int opd_floor_info(const opd_floor* f, opd_floor_model_info* info) {
+extern "C" int opd_floor_info(const opd_floor* f, opd_floor_model_info* info) { return api_call_unlocked("opd_floor_info", [&]() -> int {
     if (!f || !info) return fail(OPD_EINVAL, "opd_floor_info: null argument");
     const FloorModel& m = f->model;
     *info = opd_floor_model_info{m.method, m.n_points, m.n_triangles, m.n_zones, m.n_edges, m.has_distortion, m.allow_overlap, f->device};
     return OPD_OK;
-}
+}); }
 
-extern "C" int opd_floor_transform(opd_floor* f, const float* boxes_xywh, int n, int mem_kind, opd_floor_rec* out) {
-    ApiScope api_scope;
+extern "C" int opd_floor_transform(opd_floor* f, const float* boxes_xywh, int n, int mem_kind, opd_floor_rec* out) { return api_call("opd_floor_transform", [&]() -> int {
     RCCHK(check_call(f, "opd_floor_transform", boxes_xywh, n, out));
     if (mem_kind != OPD_MEM_HOST && mem_kind != OPD_MEM_DEVICE) return fail(OPD_EINVAL, "opd_floor_transform: mem_kind must be OPD_MEM_HOST or OPD_MEM_DEVICE");
     if (n == 0) return OPD_OK;
@@ -214,22 +212,20 @@ extern "C" int opd_floor_transform(opd_floor* f, const float* boxes_xywh, int n,
         p.boxes = boxes_xywh;
     }
     return run(f, p, mem_kind == OPD_MEM_HOST ? boxes_xywh : nullptr, sizeof(opd_floor_rec), out);
-}
+}); }
 
-extern "C" int opd_floor_transform_points(opd_floor* f, const double* pts_xy, int n, opd_floor_rec* out) {
-    ApiScope api_scope;
+extern "C" int opd_floor_transform_points(opd_floor* f, const double* pts_xy, int n, opd_floor_rec* out) { return api_call("opd_floor_transform_points", [&]() -> int {
     RCCHK(check_call(f, "opd_floor_transform_points", pts_xy, n, out));
     if (n == 0) return OPD_OK;
     FloorParams p{};
     p.mode = FLOOR_IN_POINTS; p.n = n;
     return run(f, p, pts_xy, sizeof(opd_floor_rec), out);
-}
+}); }
 
-extern "C" int opd_floor_classify(opd_floor* f, const double* floor_xy, int n, uint64_t* masks) {
-    ApiScope api_scope;
+extern "C" int opd_floor_classify(opd_floor* f, const double* floor_xy, int n, uint64_t* masks) { return api_call("opd_floor_classify", [&]() -> int {
     RCCHK(check_call(f, "opd_floor_classify", floor_xy, n, masks));
     if (n == 0) return OPD_OK;
     FloorParams p{};
     p.mode = FLOOR_IN_FLOOR; p.n = n;
     return run(f, p, floor_xy, sizeof(uint64_t), masks);
-}
+}); }

@@ -14,17 +14,17 @@ using namespace opd;
 
 namespace {
 
-// the effective top level: the largest l <= max_level with every level 1 .. l wider and taller than the window
-int plan_levels(int h, int w, int win, int max_level, int* lh, int* lw, int* lp) {
-    lh[0] = h; lw[0] = w; lp[0] = flow_pitch(w);
-    int top = 0;
+// the frame size of `p` and its levels; the effective top level is the largest l <= max_level with every level 1 .. l wider and taller than the window
+void plan_levels(FlowPyramid* p, int h, int w, int win, int max_level) {
+    p->h = h; p->w = w;
+    p->lh[0] = h; p->lw[0] = w; p->lp[0] = flow_pitch(w);
+    p->top = 0;
     for (int l = 1; l <= max_level; ++l) {
-        const int nh = (lh[l - 1] + 1) / 2, nw = (lw[l - 1] + 1) / 2;
+        const int nh = (p->lh[l - 1] + 1) / 2, nw = (p->lw[l - 1] + 1) / 2;
         if (nh <= win || nw <= win) break;
-        lh[l] = nh; lw[l] = nw; lp[l] = flow_pitch(nw);
-        top = l;
+        p->lh[l] = nh; p->lw[l] = nw; p->lp[l] = flow_pitch(nw);
+        p->top = l;
     }
-    return top;
 }
 
 int check_frame(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w) {
@@ -42,7 +42,7 @@ int check_frame(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, 
     return OPD_OK;
 }
 
-// gray + pyramid of `bgr` into pyr[which], enqueued on the handle's stream.  The `pts_bytes` of points the caller has put at the head of the
+// gray + pyramid of `bgr` into pyr[which] (whose levels are planned for h x w), enqueued on the handle's stream.  The `pts_bytes` of points the caller has put at the head of the
 // staging image and a host frame (behind the points region) travel as two copies of exactly their bytes on the same stream.
 int enqueue_pyramid(opd_flow* f, int which, const uint8_t* bgr, int mem_kind, int h, int w, size_t pts_bytes) {
     const uint8_t* d_bgr = bgr;
@@ -54,16 +54,15 @@ int enqueue_pyramid(opd_flow* f, int which, const uint8_t* bgr, int mem_kind, in
         HIPCHK(hipMemcpyAsync(f->io.dev + f->frame_off, f->io.host + f->frame_off, bytes, hipMemcpyHostToDevice, f->stream));
     }
     const FlowPyramid& p = f->pyr[which];
-    HIPCHK(opd_launch_flow_gray(d_bgr, p.base + p.off[0], h, w, f->lp[0], f->stream));
-    for (int l = 1; l <= f->top; ++l)
-        HIPCHK(opd_launch_flow_pyrdown(p.base + p.off[l - 1], f->lh[l - 1], f->lw[l - 1], f->lp[l - 1], p.base + p.off[l], f->lp[l], f->stream));
+    HIPCHK(opd_launch_flow_gray(d_bgr, p.base + p.off[0], h, w, p.lp[0], f->stream));
+    for (int l = 1; l <= p.top; ++l)
+        HIPCHK(opd_launch_flow_pyrdown(p.base + p.off[l - 1], p.lh[l - 1], p.lw[l - 1], p.lp[l - 1], p.base + p.off[l], p.lp[l], f->stream));
     return OPD_OK;
 }
 
 }  // namespace
 
-extern "C" int opd_flow_create(const opd_flow_config* cfg, int device_ordinal, opd_flow** out) {
-    ApiScope api_scope;
+extern "C" int opd_flow_create(const opd_flow_config* cfg, int device_ordinal, opd_flow** out) { return api_call("opd_flow_create", [&]() -> int {
     if (!cfg || !out) return fail(OPD_EINVAL, "opd_flow_create: null argument");
     *out = nullptr;
     opd_flow_config c = *cfg;
@@ -105,32 +104,31 @@ extern "C" int opd_flow_create(const opd_flow_config* cfg, int device_ordinal, o
     RCCHK(f->io.reserve("opd_flow_create", io_bytes, io_bytes, f->stream));   // sized once: the handle's maxima bound every call
     *out = f.release();
     return OPD_OK;
-}
+}); }
 
-extern "C" void opd_flow_destroy(opd_flow* f) {
-    if (!f) return;
-    ApiScope api_scope;
+extern "C" void opd_flow_destroy(opd_flow* f) { (void)api_call("opd_flow_destroy", [&]() -> int {
+    if (!f) return OPD_OK;
     (void)hipSetDevice(f->device);
     if (f->stream) { (void)hipStreamSynchronize(f->stream); (void)hipStreamDestroy(f->stream); }
     for (int k = 0; k < 2; ++k) if (f->pyr[k].base) (void)hipFree(f->pyr[k].base);
     f->io.release();
     delete f;
-}
+    return OPD_OK;
+}); }
 
 // ---- the two entry points in halves: everything up to the wait (enqueue) and what follows it (finish).  opd_lwt.cpp puts launches of its
 //      own on the handle's stream between the two and waits itself.
 int opd::flow_enqueue_reference(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, int which) {
     RCCHK(check_frame(f, who, bgr, mem_kind, h, w));
     HIPCHK(hipSetDevice(f->device));
-    f->has_ref = f->other_valid = false;   // (a failure below leaves no reference)
-    f->h = h; f->w = w;
-    f->top = plan_levels(h, w, f->cfg.win, f->cfg.max_level, f->lh, f->lw, f->lp);
+    f->pyr[which].valid = false;   // (which == ref: a failure below leaves no reference)
+    plan_levels(&f->pyr[which], h, w, f->cfg.win, f->cfg.max_level);
     return enqueue_pyramid(f, which, bgr, mem_kind, h, w, 0);
 }
 
 void opd::flow_finish_reference(opd_flow* f, int which) {
     f->ref = which;
-    f->has_ref = true;
+    f->pyr[which].valid = true;
 }
 
 int opd::flow_enqueue_track(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, const float* host_pts, int n, const float* d_pts,
@@ -139,21 +137,23 @@ int opd::flow_enqueue_track(opd_flow* f, const char* who, const uint8_t* bgr, in
     RCCHK(check_frame(f, who, bgr, mem_kind, h, w));
     if (n < 0 || n > f->cfg.max_points)
         return fail(OPD_EINVAL, me + ": " + std::to_string(n) + " points, the handle was created for up to " + std::to_string(f->cfg.max_points));
-    if (!f->has_ref) return fail(OPD_ESTATE, me + ": no reference frame yet (call opd_flow_set_reference first)");
-    if (h != f->h || w != f->w)
+    const FlowPyramid& ref = f->pyr[f->ref];
+    if (!ref.valid) return fail(OPD_ESTATE, me + ": no reference frame yet (call opd_flow_set_reference first)");
+    if (h != ref.h || w != ref.w)
         return fail(OPD_EINVAL, me + ": frame of " + std::to_string(h) + " x " + std::to_string(w) + " pixels, the reference has " +
-                                    std::to_string(f->h) + " x " + std::to_string(f->w));
+                                    std::to_string(ref.h) + " x " + std::to_string(ref.w));
     HIPCHK(hipSetDevice(f->device));
     const int cur = 1 - f->ref;
-    f->other_valid = false;
+    f->pyr[cur].valid = false;
+    plan_levels(&f->pyr[cur], h, w, f->cfg.win, f->cfg.max_level);   // (the reference's size: the same levels)
     const size_t pts_bytes = host_pts ? (size_t)n * 8 : 0;
     if (pts_bytes) memcpy(f->io.host, host_pts, pts_bytes);
     RCCHK(enqueue_pyramid(f, cur, bgr, mem_kind, h, w, pts_bytes));
     if (n) {
         FlowParams p{};
-        for (int l = 0; l <= f->top; ++l)
-            p.lv[l] = FlowLevel{f->pyr[f->ref].base + f->pyr[f->ref].off[l], f->pyr[cur].base + f->pyr[cur].off[l], f->lw[l], f->lh[l], f->lp[l]};
-        p.top = f->top;
+        for (int l = 0; l <= ref.top; ++l)
+            p.lv[l] = FlowLevel{ref.base + ref.off[l], f->pyr[cur].base + f->pyr[cur].off[l], ref.lw[l], ref.lh[l], ref.lp[l]};
+        p.top = ref.top;
         p.n = n;
         p.win = f->cfg.win;
         p.max_iter = f->cfg.max_iter;
@@ -168,21 +168,19 @@ int opd::flow_enqueue_track(opd_flow* f, const char* who, const uint8_t* bgr, in
 }
 
 void opd::flow_finish_track(opd_flow* f) {
-    f->ref = 1 - f->ref;   // the frame just seen is the reference of the next call
-    f->other_valid = true;
+    f->ref = 1 - f->ref;   // the frame just seen is the reference of the next call; the old reference stays valid behind it
+    f->pyr[f->ref].valid = true;
 }
 
-extern "C" int opd_flow_set_reference(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w) {
-    ApiScope api_scope;
+extern "C" int opd_flow_set_reference(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w) { return api_call("opd_flow_set_reference", [&]() -> int {
     RCCHK(flow_enqueue_reference(f, "opd_flow_set_reference", bgr, mem_kind, h, w, f ? f->ref : 0));
     HIPCHK(hipStreamSynchronize(f->stream));
     flow_finish_reference(f, f->ref);
     return OPD_OK;
-}
+}); }
 
 extern "C" int opd_flow_track(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w, const float* pts_xy, int n, float* next_xy,
-                              uint8_t* status) {
-    ApiScope api_scope;
+                              uint8_t* status) { return api_call("opd_flow_track", [&]() -> int {
     RCCHK(check_frame(f, "opd_flow_track", bgr, mem_kind, h, w));
     if (n < 0 || n > f->cfg.max_points)
         return fail(OPD_EINVAL, "opd_flow_track: " + std::to_string(n) + " points, the handle was created for up to " + std::to_string(f->cfg.max_points));
@@ -198,4 +196,4 @@ extern "C" int opd_flow_track(opd_flow* f, const uint8_t* bgr, int mem_kind, int
     }
     flow_finish_track(f);
     return OPD_OK;
-}
+}); }

@@ -30,27 +30,30 @@ hipError_t opd_launch_flow_lk(const FlowParams& p, hipStream_t stream);
 
 inline int flow_pitch(int w) { return (w + 15) / 16 * 16; }
 
+// One gray pyramid and the frame it holds: the geometry lives with the pixels it describes, so building into the pyramid the reference does
+// not use changes nothing of the reference.
 struct FlowPyramid {
     uint8_t* base = nullptr;                   // one allocation; level l at base + off[l]
     size_t off[OPD_FLOW_MAX_LEVELS] = {};
+    bool valid = false;                        // holds a whole frame (false from the moment one is enqueued into it until the call's finish)
+    int h = 0, w = 0, top = 0;                 // the frame, and its effective top level
+    int lw[OPD_FLOW_MAX_LEVELS] = {}, lh[OPD_FLOW_MAX_LEVELS] = {}, lp[OPD_FLOW_MAX_LEVELS] = {};
 };
 
 struct opd_flow {
     opd_flow_config cfg{};                     // with the defaults filled in
     int device = 0;
     hipStream_t stream = nullptr;
-    FlowPyramid pyr[2];                        // pyr[ref] is the reference; a track call builds the other one and swaps
-    int ref = 0;
-    bool has_ref = false, other_valid = false; // other_valid: pyr[1 - ref] holds the frame the reference replaced
-    int h = 0, w = 0, top = 0;                 // geometry of the reference (and of pyr[1 - ref] when other_valid)
-    int lw[OPD_FLOW_MAX_LEVELS] = {}, lh[OPD_FLOW_MAX_LEVELS] = {}, lp[OPD_FLOW_MAX_LEVELS] = {};
+    FlowPyramid pyr[2];                        // pyr[ref] is the reference (once valid); a track call builds the other one and swaps, so that
+    int ref = 0;                               // pyr[1 - ref], while valid, holds the frame the reference replaced
     opd::Staging io;                           // page-locked: [points | frame] up, [next | status] down; device: [points | frame] and, behind it, [next | status]
     size_t pts_bytes = 0, frame_off = 0, out_off = 0;
 };
 
 // opd_flow_set_reference and opd_flow_track in two halves each: everything up to the wait, on the handle's stream, and the bookkeeping after
 // it.  The tracker handle of opd_lwt.cpp enqueues its own launches between the two and waits once itself.  `which`: the pyramid the new
-// reference is built into (f->ref for opd_flow_set_reference; 1 - f->ref keeps the old reference intact until the finish).  The track half
+// reference is built into (f->ref for opd_flow_set_reference; 1 - f->ref keeps the old reference intact, and a caller that never reaches
+// the finish has changed nothing but the contents of the pyramid the reference does not use).  The track half
 // reads its points at `d_pts` on the device (`host_pts`, when given, are staged and uploaded there first: d_pts is then the head of io.dev)
 // and leaves LK's results at `d_next` / `d_status` on the device.
 namespace opd {

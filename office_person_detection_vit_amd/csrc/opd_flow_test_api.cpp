@@ -13,12 +13,12 @@ TAPI int opd_flow_test_level(opd_flow* f, int which, int level, uint8_t* out, in
     ApiScope api_scope;
     if (!f || !h || !w || !levels) return fail(OPD_EINVAL, "opd_flow_test_level: null argument");
     if (which != 0 && which != 1) return fail(OPD_EINVAL, "opd_flow_test_level: which must be 0 or 1");
-    if (!f->has_ref || (which == 1 && !f->other_valid)) return fail(OPD_ESTATE, "opd_flow_test_level: that pyramid holds no frame");
-    if (level < 0 || level > f->top) return fail(OPD_EINVAL, "opd_flow_test_level: no level " + std::to_string(level));
-    *h = f->lh[level]; *w = f->lw[level]; *levels = f->top + 1;
+    const FlowPyramid& p = f->pyr[which == 0 ? f->ref : 1 - f->ref];
+    if (!f->pyr[f->ref].valid || !p.valid) return fail(OPD_ESTATE, "opd_flow_test_level: that pyramid holds no frame");
+    if (level < 0 || level > p.top) return fail(OPD_EINVAL, "opd_flow_test_level: no level " + std::to_string(level));
+    *h = p.lh[level]; *w = p.lw[level]; *levels = p.top + 1;
     if (!out) return OPD_OK;
     HIPCHK(hipSetDevice(f->device));
-    const FlowPyramid& p = f->pyr[which == 0 ? f->ref : 1 - f->ref];
-    HIPCHK(hipMemcpy2D(out, (size_t)*w, p.base + p.off[level], (size_t)f->lp[level], (size_t)*w, (size_t)*h, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(out, (size_t)*w, p.base + p.off[level], (size_t)p.lp[level], (size_t)*w, (size_t)*h, hipMemcpyDeviceToHost));
     return OPD_OK;
 }

@@ -28,6 +28,8 @@ const char* opd_kernel_name(const char* fmt, ...) {
 namespace opd {
 
 thread_local std::string g_err;
+std::shared_mutex g_api_mu;
+thread_local std::shared_lock<std::shared_mutex>* tl_api_lock = nullptr;
 
 int fail(int code, const std::string& msg) {
     g_err = msg;
@@ -146,9 +148,13 @@ void opd_resize_coeffs(int in_size, int out_size, std::vector<int32_t>* bounds, 
 
 extern "C" {
 
-const char* opd_last_error(void) { return opd::g_err.c_str(); }
+const char* opd_last_error(void) {
+    const char* text = "";
+    (void)api_call_unlocked("opd_last_error", [&] { text = opd::g_err.c_str(); return OPD_OK; });
+    return text;
+}
 
-int opd_person_nms(opd_det* dets, int n, int person_label, float nms_threshold) {
+static int person_nms(opd_det* dets, int n, int person_label, float nms_threshold) {
     if (n < 0 || (n > 0 && !dets)) return fail(OPD_EINVAL, "opd_person_nms: bad arguments");
     std::vector<int> idx;
     for (int i = 0; i < n; ++i)
@@ -172,16 +178,20 @@ int opd_person_nms(opd_det* dets, int n, int person_label, float nms_threshold) 
     return (int)kept.size();
 }
 
-int opd_person_nms_batch(opd_det* dets, int32_t* counts, int n_frames, int stride, int person_label, float nms_threshold) {
+int opd_person_nms(opd_det* dets, int n, int person_label, float nms_threshold) {
+    return api_call_unlocked("opd_person_nms", [&] { return person_nms(dets, n, person_label, nms_threshold); });
+}
+
+int opd_person_nms_batch(opd_det* dets, int32_t* counts, int n_frames, int stride, int person_label, float nms_threshold) { return api_call_unlocked("opd_person_nms_batch", [&]() -> int {
     if (n_frames < 0 || stride < 0 || (n_frames > 0 && (!dets || !counts))) return fail(OPD_EINVAL, "opd_person_nms_batch: bad arguments");
     for (int f = 0; f < n_frames; ++f) {
         if (counts[f] < 0) continue;
         if (counts[f] > stride) return fail(OPD_EINVAL, "opd_person_nms_batch: a frame holds more records than its slots");
-        const int kept = opd_person_nms(dets + (size_t)f * stride, counts[f], person_label, nms_threshold);
+        const int kept = person_nms(dets + (size_t)f * stride, counts[f], person_label, nms_threshold);
         if (kept < 0) return kept;
         counts[f] = kept;
     }
     return OPD_OK;
-}
+}); }
 
 }  // extern "C"

@@ -170,21 +170,6 @@ static int get_plan(opd_detr* m, int fh, int fw, int vh, int vw, Plan** out) {
 }
 
 // ---- one launch of the forward (opd_model.h: launch) ---------------------------------------------------------------
-// profiling mode 1: an event pair around the launch, for the kernel table
-int launch_begin(opd_detr* m, hipStream_t s, int cls, double flops) {
-    if (m->profiling != 1) return OPD_OK;
-    while (m->event_pool.size() < m->pool_next + 2) {
-        hipEvent_t ne;
-        HIPCHK(hipEventCreate(&ne));
-        m->event_pool.push_back(ne);
-    }
-    const hipEvent_t* e = &m->event_pool[m->pool_next];
-    m->pool_next += 2;
-    HIPCHK(hipEventRecord(e[0], s));
-    m->timed.push_back({cls, e[0], e[1], flops, nullptr});
-    opd_last_kernel_name = nullptr;
-    return OPD_OK;
-}
 static int tap(opd_detr* m, hipStream_t s, const Tap& t) {
     if (!m->taps || !m->d_taps || m->tap_next >= OPD_MAX_TAPS) return OPD_OK;
     HIPCHK(opd_launch_checksum(t.p, t.bytes, m->d_taps + (size_t)m->tap_next * OPD_TAP_BLOCKS, s));
@@ -193,34 +178,24 @@ static int tap(opd_detr* m, hipStream_t s, const Tap& t) {
     return OPD_OK;
 }
 int launch_end(opd_detr* m, hipStream_t s, std::initializer_list<Tap> taps) {
-    if (m->profiling == 1) {
-        HIPCHK(hipEventRecord(m->timed.back().b, s));
-        m->timed.back().name = opd_last_kernel_name;   // what the launcher just launched (OPD_LAUNCH): the name rocprofv3 prints, minus namespace and signature
-    }
+    if (m->profiling == 1) RCCHK(m->timer.end(s));
     for (const Tap& t : taps)
         if (t.name && t.p) RCCHK(tap(m, s, t));
     return OPD_OK;
 }
+// profiling mode 1: the timer's marks of the calls since the last forward began -> the kernel table (longest first) and the class sums
 void timed_collect(opd_detr* m) {
+    static const char* const cls_name[4] = {"(convolution)", "(linear layer)", "(attention)", "(other)"};
     for (int c = 0; c < 4; ++c) { m->class_ms[c] = 0.f; m->class_launches[c] = 0; m->class_flops[c] = 0.0; }
     m->ktable.clear();
-    static const char* const cls_name[4] = {"(convolution)", "(linear layer)", "(attention)", "(other)"};
-    for (const auto& t : m->timed) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) {
-            m->class_ms[t.cls] += ms;
-            m->class_launches[t.cls] += 1;
-            m->class_flops[t.cls] += t.flops;
-            std::string nm = t.name ? t.name : cls_name[t.cls];
-            if (!nm.empty() && nm.front() == '(' && nm.back() == ')' && t.name) nm = nm.substr(1, nm.size() - 2);   // OPD_LAUNCH((kernel<a, b>), ...)
-            opd_detr::KernelRow* row = nullptr;
-            for (auto& r : m->ktable)
-                if (r.name == nm) { row = &r; break; }
-            if (!row) { m->ktable.push_back({nm, 0, 0.f, 0.0}); row = &m->ktable.back(); }
-            row->launches += 1; row->ms += ms; row->flops += t.flops;
-        }
+    (void)m->timer.fold(&m->ktable, cls_name);
+    for (const auto& t : m->timer.marks)
+        if (t.ms >= 0.f) { m->class_ms[t.cls] += t.ms; m->class_launches[t.cls] += 1; m->class_flops[t.cls] += t.flops; }
+    std::sort(m->ktable.begin(), m->ktable.end(), [](const KernelRow& a, const KernelRow& b) { return a.ms > b.ms; });
+    for (auto& r : m->ktable) {   // OPD_LAUNCH((kernel<a, b>), ...): the name without its parentheses (the class labels keep theirs)
+        const bool label = std::find_if(cls_name, cls_name + 4, [&](const char* c) { return r.name == c; }) != cls_name + 4;
+        if (!label && r.name.size() > 1 && r.name.front() == '(' && r.name.back() == ')') r.name = r.name.substr(1, r.name.size() - 2);
     }
-    std::sort(m->ktable.begin(), m->ktable.end(), [](const opd_detr::KernelRow& a, const opd_detr::KernelRow& b) { return a.ms > b.ms; });
 }
 
 // ---- the per-call context of one forward ---------------------------------------------------------------------------
@@ -853,8 +828,7 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
     const bool ragged = is_ragged(valid_hw, B, H, W);
     if (ragged) RCCHK(fwd_prepare_ragged(c, valid_hw));
     else RCCHK(get_plan(m, c.d.stage_h[3], c.d.stage_w[3], c.d.stage_h[3], c.d.stage_w[3], &c.plan));
-    m->timed.clear();   // the event pairs and the taps of the last forward
-    m->pool_next = 0;
+    m->timer.reset();   // the event pairs and the taps of the last forward
     m->tap_next = 0;
     if (pixel_format == OPD_PIXELS_U8_BGR_HWC) RCCHK(tap(m, c.stream, {"pixels_u8", d_pixels, (size_t)B * H * W * 3}));
     MARK(0);
@@ -879,15 +853,12 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
     return OPD_OK;
 }
 
-std::shared_mutex g_api_mu;
 std::atomic<unsigned> g_handle_epoch{0};
 std::atomic<int> g_graph_guard{1};   // opd_test_set_graph_guard(0): leave stale-epoch graphs alone (diagnosis only)
-thread_local std::shared_lock<std::shared_mutex>* tl_api_lock = nullptr;
 
 // Every captured graph of the handle holds the launch sequence of the switches, taps and profiling mode it was captured under
 void drop_graphs(opd_detr* m) {
-    for (auto& g : m->graphs)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    for (auto& g : m->graphs) g.slot.drop();
     m->graphs.clear();
 }
 
@@ -903,30 +874,20 @@ int run_forward(opd_detr* m, const void* d_pixels, int pixel_format, int B, int 
         if (g.B == B && g.H == H && g.W == W && g.fmt == pixel_format && g.pixels == d_pixels) e = &g;
     if (!e) {
         if (m->graphs.size() >= 8) {  // bounded cache: drop the oldest entry
-            if (m->graphs.front().exec) (void)hipGraphExecDestroy(m->graphs.front().exec);
+            m->graphs.front().slot.drop();
             m->graphs.erase(m->graphs.begin());
         }
-        m->graphs.push_back({B, H, W, pixel_format, 0, 0, d_pixels, 0, nullptr, 0u});
+        m->graphs.push_back({B, H, W, pixel_format, 0, 0, d_pixels, 0, GraphSlot{}});
         e = &m->graphs.back();
     }
-    if (e->exec && graph_stale(e->epoch)) {   // handles came or went since the capture: capture again (see g_handle_epoch)
-        (void)hipGraphExecDestroy(e->exec);
-        e->exec = nullptr;
-        e->uses = 1;
-    }
-    if (e->exec) {
-        HIPCHK(hipGraphLaunch(e->exec, m->stream));
-        if (m->profiling == 2) { HIPCHK(hipEventRecord(m->ev[9], m->stream)); m->graph_marks = true; }   // eager mark behind the graph: the post-process stage is timed between eager events
-        m->last_B = B; m->last_H = H; m->last_W = W; m->last_fh = e->fh; m->last_fw = e->fw; m->last_ragged = false;
+    if (!e->slot.ready() && e->uses++ == 0) return enqueue_forward(m, d_pixels, pixel_format, B, H, W);   // (a stale graph is captured again at once; a failed capture, by the next call)
+    RCCHK(e->slot.run(m->stream, "the forward", [&]() -> int {
+        RCCHK(enqueue_forward(m, d_pixels, pixel_format, B, H, W));
+        e->fh = m->last_fh; e->fw = m->last_fw;
         return OPD_OK;
-    }
-    if (e->uses++ == 0) return enqueue_forward(m, d_pixels, pixel_format, B, H, W);
-    hipGraphExec_t exec = nullptr;
-    const int rc = capture_graph(m->stream, "the forward", [&] { return enqueue_forward(m, d_pixels, pixel_format, B, H, W); }, &exec);
-    if (rc != OPD_OK) { e->uses = 1; return rc; }   // (the next call tries again)
-    e->exec = exec; e->fh = m->last_fh; e->fw = m->last_fw; e->epoch = g_handle_epoch.load();
-    HIPCHK(hipGraphLaunch(exec, m->stream));
-    if (m->profiling == 2) { HIPCHK(hipEventRecord(m->ev[9], m->stream)); m->graph_marks = true; }
+    }));
+    if (m->profiling == 2) { HIPCHK(hipEventRecord(m->ev[9], m->stream)); m->graph_marks = true; }   // eager mark behind the graph: the post-process stage is timed between eager events
+    m->last_B = B; m->last_H = H; m->last_W = W; m->last_fh = e->fh; m->last_fw = e->fw; m->last_ragged = false;   // (a replay ran no host code of the forward)
     return OPD_OK;
 }
 

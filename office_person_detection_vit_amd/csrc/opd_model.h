@@ -272,16 +272,12 @@ struct opd_detr : DetrWeights {
     int num_cus = 256;
 
     // hipGraph cache: the whole forward (~180 launches, many of them 5-10 us decoder kernels) replayed as one graph
-    struct GraphEntry { int B, H, W, fmt, fh, fw; const void* pixels; int uses; hipGraphExec_t exec; unsigned epoch; };
+    struct GraphEntry { int B, H, W, fmt, fh, fw; const void* pixels; int uses; GraphSlot slot; };
     std::vector<GraphEntry> graphs;
 
-    // per-kernel-class timing (profiling mode only): event pairs around every launch of the last forward
-    struct Timed { int cls; hipEvent_t a, b; double flops; const char* name; };
-    struct KernelRow { std::string name; int launches; float ms; double flops; };
+    // per-kernel-class timing (profiling mode 1 only): event pairs around every launch of the last forward
+    LaunchTimer timer;
     std::vector<KernelRow> ktable;      // the last profiled forward by kernel (opd_detr_kernel_table), longest first
-    std::vector<Timed> timed;           // pairs used by the current forward
-    std::vector<hipEvent_t> event_pool;  // all events ever created (reused across forwards)
-    size_t pool_next = 0;
     float class_ms[4] = {};
     int class_launches[4] = {};
     double class_flops[4] = {};
@@ -336,15 +332,14 @@ int build_workspace(opd_detr* m);
 int run_forward(opd_detr* m, const void* d_pixels, int pixel_format, int B, int H, int W, const int32_t* valid_hw = nullptr);
 void drop_graphs(opd_detr* m);   // destroy the handle's graph executables and clear the cache: the next forwards run eagerly, then capture anew
 enum { CLS_CONV = 0, CLS_GEMM = 1, CLS_ATTN = 2, CLS_OTHER = 3 };
-// How a launch of the forward (and of the post-process behind it) is issued, written once: profiling mode 1's event pair (timing class
-// `cls`, algorithmic `flops`) opens, `issue()` launches on stream `s`, the pair closes, and with diagnostic taps on a checksum launch follows
+// How a launch of the forward (and of the post-process behind it) is issued, written once: profiling mode 1's event pair (the handle's
+// LaunchTimer; timing class `cls`, algorithmic `flops`) opens, `issue()` launches on stream `s`, the pair closes, and with diagnostic taps on a checksum launch follows
 // for each of `taps` that has a name and a buffer.  A split-K pair is two calls, the tap on the second.
 struct Tap { const char* name; const void* p; size_t bytes; };
-int launch_begin(opd_detr* m, hipStream_t s, int cls, double flops);   // (the two halves of launch(): nothing else calls them)
-int launch_end(opd_detr* m, hipStream_t s, std::initializer_list<Tap> taps);
+int launch_end(opd_detr* m, hipStream_t s, std::initializer_list<Tap> taps);   // (the pair's close and the taps: nothing but launch() calls it)
 template <typename F>
 int launch(opd_detr* m, hipStream_t s, int cls, double flops, F&& issue, std::initializer_list<Tap> taps = {}) {
-    RCCHK(launch_begin(m, s, cls, flops));
+    if (m->profiling == 1) RCCHK(m->timer.begin(s, cls, flops));
     HIPCHK(issue());
     return launch_end(m, s, taps);
 }

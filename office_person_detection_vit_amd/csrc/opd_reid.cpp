@@ -29,8 +29,7 @@ struct opd_reid {
     // staging: [ReidCrop x max_crops][tables][windows], pinned host image + device copy, grown on demand
     Staging up;
     std::vector<int> buckets;
-    struct Graph { hipGraphExec_t exec; unsigned epoch; };
-    std::map<int, Graph> graphs;
+    std::map<int, GraphSlot> graphs;   // by crop-count bucket, captured on first use
     // One call at a time: opd_reid_extract and the fused detect call (opd_detr_detect_frames_reid) both rewrite the staging buffer and
     // replay the same graphs.  A second thread waits here, with its hold of the entry-point lock handed back meanwhile (a capture
     // inside the first call takes that lock exclusively).
@@ -41,7 +40,7 @@ struct opd_reid {
 namespace {
 
 void destroy_graphs(opd_reid* r) {
-    for (auto& kv : r->graphs) (void)hipGraphExecDestroy(kv.second.exec);
+    for (auto& kv : r->graphs) kv.second.drop();
     r->graphs.clear();
 }
 
@@ -71,19 +70,7 @@ int enqueue_forward(opd_reid* r, int nb) { return r->model->enqueue(nb, reinterp
 
 int run_forward(opd_reid* r, int nb) {
     if (r->launch.prof || (r->cfg.flags & OPD_FLAG_NO_GRAPH)) return enqueue_forward(r, nb);
-    auto it = r->graphs.find(nb);
-    if (it != r->graphs.end() && graph_stale(it->second.epoch)) {   // handles came or went since the capture: capture again (see g_handle_epoch)
-        (void)hipGraphExecDestroy(it->second.exec);
-        r->graphs.erase(it);
-        it = r->graphs.end();
-    }
-    if (it == r->graphs.end()) {
-        hipGraphExec_t exec = nullptr;
-        RCCHK(capture_graph(r->launch.stream, "the Re-ID forward", [&] { return enqueue_forward(r, nb); }, &exec));
-        it = r->graphs.emplace(nb, opd_reid::Graph{exec, g_handle_epoch.load()}).first;
-    }
-    HIPCHK(hipGraphLaunch(it->second.exec, r->launch.stream));
-    return OPD_OK;
+    return r->graphs[nb].run(r->launch.stream, "the Re-ID forward", [&] { return enqueue_forward(r, nb); });
 }
 
 // Crop records, coefficient tables and (host frames) source windows of boxes [0, n) into the pinned staging image; padded crops up to
@@ -166,7 +153,7 @@ void destroy_impl(opd_reid* r) {
     (void)hipSetDevice(r->device);
     if (r->launch.stream) (void)hipStreamSynchronize(r->launch.stream);
     destroy_graphs(r);
-    for (hipEvent_t e : r->launch.event_pool) (void)hipEventDestroy(e);
+    r->launch.timer.release();
     for (hipEvent_t e : {r->ev_planned, r->ev_done})
         if (e) (void)hipEventDestroy(e);
     r->up.release();
@@ -227,25 +214,6 @@ int create_impl(const opd_reid_config* cfg, const char* weights_path, int device
 }  // namespace
 
 namespace opd {
-
-int ReidLauncher::before(hipEvent_t* e0, hipEvent_t* e1) {
-    for (hipEvent_t* e : {e0, e1}) {
-        if (events_used == event_pool.size()) {
-            hipEvent_t ev;
-            HIPCHK(hipEventCreate(&ev));
-            event_pool.push_back(ev);
-        }
-        *e = event_pool[events_used++];
-    }
-    HIPCHK(hipEventRecord(*e0, stream));
-    return OPD_OK;
-}
-
-int ReidLauncher::after(double flops, hipEvent_t e0, hipEvent_t e1) {
-    HIPCHK(hipEventRecord(e1, stream));
-    marks.push_back({opd_last_kernel_name, flops, e0, e1});
-    return OPD_OK;
-}
 
 // ---- the Re-ID half of the fused detect call (opd_api.cpp: opd_detr_detect_frames_reid) ------------------------------------------------
 // Staging layout of a fused call: [ReidCrop x max_crops | slot[max_crops], rec[max_crops], n_person | tables: one fixed stride per crop]
@@ -342,38 +310,25 @@ int reid_test_kernel_table(opd_reid* r, const uint8_t* const* frames, const int3
     size_t used = 0;
     RCCHK(stage(r, frames, frame_hw, n_frames, OPD_MEM_HOST, boxes, box_frame, n, nb, &used));
     HIPCHK(hipMemcpyAsync(r->up.dev, r->up.host, used, hipMemcpyHostToDevice, r->launch.stream));
-    std::vector<std::string> names;
-    std::vector<opd_kernel_stat> rows;
+    static const char* const unnamed[1] = {"(unnamed)"};   // (LCHK times every launch as class 0)
+    std::vector<KernelRow> rows;   // first-seen order, summed over the iterations
     r->launch.prof = true;
     int rc = OPD_OK;
     for (int it = 0; it < iters && rc == OPD_OK; ++it) {
-        r->launch.marks.clear();
-        r->launch.events_used = 0;
+        r->launch.timer.reset();
         rc = enqueue_forward(r, nb);
         if (rc == OPD_OK && hipStreamSynchronize(r->launch.stream) != hipSuccess) rc = fail(OPD_EHIP, "hipStreamSynchronize failed");
-        for (size_t i = 0; rc == OPD_OK && i < r->launch.marks.size(); ++i) {
-            const ReidLauncher::Mark& mk = r->launch.marks[i];
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, mk.e0, mk.e1) != hipSuccess) { rc = fail(OPD_EHIP, "hipEventElapsedTime failed"); break; }
-            size_t k = 0;
-            while (k < names.size() && names[k] != mk.name) ++k;
-            if (k == names.size()) {
-                names.push_back(mk.name);
-                opd_kernel_stat z;
-                memset(&z, 0, sizeof z);
-                snprintf(z.name, sizeof z.name, "%s", mk.name);
-                rows.push_back(z);
-            }
-            rows[k].launches += 1;
-            rows[k].ms += ms;
-            rows[k].flops += mk.flops;
-        }
+        if (rc == OPD_OK && r->launch.timer.fold(&rows, unnamed)) rc = fail(OPD_EHIP, "hipEventElapsedTime failed");
     }
     r->launch.prof = false;
-    r->launch.marks.clear();
+    r->launch.timer.reset();
     RCCHK(rc);
     *count = (int)rows.size();
-    for (int i = 0; i < (int)rows.size() && i < capacity; ++i) out[i] = rows[i];
+    for (int i = 0; i < (int)rows.size() && i < capacity; ++i) {
+        memset(&out[i], 0, sizeof out[i]);
+        snprintf(out[i].name, sizeof out[i].name, "%s", rows[i].name.c_str());
+        out[i].launches = rows[i].launches; out[i].ms = rows[i].ms; out[i].flops = rows[i].flops;
+    }
     return OPD_OK;
 }
 
@@ -382,18 +337,17 @@ int reid_test_kernel_table(opd_reid* r, const uint8_t* const* frames, const int3
 extern "C" {
 
 int opd_reid_create(const opd_reid_config* cfg, const char* weights_path, int device_ordinal, opd_reid** out) {
-    ApiScope api_scope;
-    return guarded("opd_reid_create", [&] { return create_impl(cfg, weights_path, device_ordinal, out); });
+    return api_call("opd_reid_create", [&] { return create_impl(cfg, weights_path, device_ordinal, out); }, API_CREATE);
 }
 
-void opd_reid_destroy(opd_reid* r) {
-    ApiScope api_scope;
-    if (!r) return;
+void opd_reid_destroy(opd_reid* r) { (void)api_call("opd_reid_destroy", [&]() -> int {
+    if (!r) return OPD_OK;
     destroy_impl(r);
     ++g_handle_epoch;
-}
+    return OPD_OK;
+}); }
 
-int opd_reid_info(const opd_reid* r, opd_reid_model_info* info) {
+int opd_reid_info(const opd_reid* r, opd_reid_model_info* info) { return api_call_unlocked("opd_reid_info", [&]() -> int {
     if (!r || !info) return fail(OPD_EINVAL, "opd_reid_info: null argument");
     memset(info, 0, sizeof *info);
     r->model->fill_info(info);
@@ -402,30 +356,27 @@ int opd_reid_info(const opd_reid* r, opd_reid_model_info* info) {
     info->weight_bytes_device = (int64_t)r->wbytes;
     info->workspace_bytes_device = (int64_t)(r->wsbytes + r->up.dev_cap);
     return OPD_OK;
-}
+}); }
 
 int opd_reid_extract(opd_reid* r, const uint8_t* const* frames, const int32_t* frame_hw, int n_frames, int mem_kind, const float* boxes_xywh,
-                     const int32_t* box_frame, int n_boxes, float* out) {
-    ApiScope api_scope;
-    return guarded("opd_reid_extract", [&]() -> int {
-        RCCHK(check_extract_args(r, frames, frame_hw, n_frames, mem_kind, boxes_xywh, n_boxes, out));
-        if (n_boxes == 0) return OPD_OK;
-        CallLock one_call(r);
-        HIPCHK(hipSetDevice(r->device));
-        const int E = r->model->feature_dim();
-        const float* feat = r->model->features();
-        for (int c0 = 0; c0 < n_boxes; c0 += r->cfg.max_crops) {   // more boxes than max_crops: chunks of max_crops
-            const int n = std::min(r->cfg.max_crops, n_boxes - c0);
-            const int nb = bucket_of(r, n);
-            size_t used = 0;
-            RCCHK(stage(r, frames, frame_hw, n_frames, mem_kind, boxes_xywh + 4 * (size_t)c0, box_frame ? box_frame + c0 : nullptr, n, nb, &used));
-            HIPCHK(hipMemcpyAsync(r->up.dev, r->up.host, used, hipMemcpyHostToDevice, r->launch.stream));
-            RCCHK(run_forward(r, nb));
-            HIPCHK(hipMemcpyAsync(out + (size_t)c0 * E, feat, (size_t)n * E * 4, hipMemcpyDeviceToHost, r->launch.stream));
-            HIPCHK(hipStreamSynchronize(r->launch.stream));   // (the pinned staging image is rewritten by the next chunk)
-        }
-        return OPD_OK;
-    });
-}
+                     const int32_t* box_frame, int n_boxes, float* out) { return api_call("opd_reid_extract", [&]() -> int {
+    RCCHK(check_extract_args(r, frames, frame_hw, n_frames, mem_kind, boxes_xywh, n_boxes, out));
+    if (n_boxes == 0) return OPD_OK;
+    CallLock one_call(r);
+    HIPCHK(hipSetDevice(r->device));
+    const int E = r->model->feature_dim();
+    const float* feat = r->model->features();
+    for (int c0 = 0; c0 < n_boxes; c0 += r->cfg.max_crops) {   // more boxes than max_crops: chunks of max_crops
+        const int n = std::min(r->cfg.max_crops, n_boxes - c0);
+        const int nb = bucket_of(r, n);
+        size_t used = 0;
+        RCCHK(stage(r, frames, frame_hw, n_frames, mem_kind, boxes_xywh + 4 * (size_t)c0, box_frame ? box_frame + c0 : nullptr, n, nb, &used));
+        HIPCHK(hipMemcpyAsync(r->up.dev, r->up.host, used, hipMemcpyHostToDevice, r->launch.stream));
+        RCCHK(run_forward(r, nb));
+        HIPCHK(hipMemcpyAsync(out + (size_t)c0 * E, feat, (size_t)n * E * 4, hipMemcpyDeviceToHost, r->launch.stream));
+        HIPCHK(hipStreamSynchronize(r->launch.stream));   // (the pinned staging image is rewritten by the next chunk)
+    }
+    return OPD_OK;
+}); }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // opd_reid.h — the Re-ID handle (opd_reid.cpp) and what it asks of a model: the ReidModel interface that the CLIP tower (opd_clip.*)
-// and OSNet (opd_osnet.*) implement, the launcher that brackets every launch of a forward, and the bodies of the handle's test hooks.
+// and OSNet (opd_osnet.*) implement, the launcher that every launch of a forward goes through, and the bodies of the handle's test hooks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,26 +15,20 @@
 
 namespace opd {
 
-// The launches of one forward on `stream`, through LCHK: while `prof` is set each is put between two events and noted with its kernel
-// name and algorithmic FLOPs (opd_test_reid_kernel_table).
+// The launches of one forward on `stream`, through LCHK: while `prof` is set each goes through the LaunchTimer of opd_device.h (two events,
+// the kernel's name and algorithmic FLOPs; opd_test_reid_kernel_table).
 struct ReidLauncher {
     hipStream_t stream = nullptr;
     bool prof = false;
-    struct Mark { const char* name; double flops; hipEvent_t e0, e1; };
-    std::vector<Mark> marks;
-    std::vector<hipEvent_t> event_pool;
-    size_t events_used = 0;
-    int before(hipEvent_t* e0, hipEvent_t* e1);
-    int after(double flops, hipEvent_t e0, hipEvent_t e1);
+    LaunchTimer timer;
 };
 
 // one launch of a forward: `expr` is a launcher call on L.stream
-#define LCHK(L, expr, fl)                                      \
-    do {                                                       \
-        hipEvent_t e0_ = nullptr, e1_ = nullptr;               \
-        if ((L).prof) RCCHK((L).before(&e0_, &e1_));           \
-        HIPCHK(expr);                                          \
-        if ((L).prof) RCCHK((L).after((fl), e0_, e1_));        \
+#define LCHK(L, expr, fl)                                            \
+    do {                                                             \
+        if ((L).prof) RCCHK((L).timer.begin((L).stream, 0, (fl)));   \
+        HIPCHK(expr);                                                \
+        if ((L).prof) RCCHK((L).timer.end((L).stream));              \
     } while (0)
 
 // A Re-ID model behind an opd_reid handle, which owns the stream, the weight and workspace allocations and the staging of the crops.

@@ -146,134 +146,122 @@ int update_body(opd_track* t, const float* boxes, const float* foot, const float
 
 }  // namespace
 
-extern "C" int opd_track_create(const opd_track_config* cfg, int device_ordinal, opd_track** out) {
-    ApiScope api_scope;
-    return guarded("opd_track_create", [&]() -> int {
-        const std::string me = "opd_track_create: ";
-        if (!out) return fail(OPD_EINVAL, me + "null argument");
-        *out = nullptr;
-        if (!cfg) return fail(OPD_EINVAL, me + "null configuration");
-        if (cfg->struct_size != (int32_t)sizeof(opd_track_config))
-            return fail(OPD_EINVAL, me + "struct_size " + std::to_string(cfg->struct_size) + ", this library's opd_track_config has " + std::to_string(sizeof(opd_track_config)) + " bytes");
-        const opd_track_config& c = *cfg;
-        const int S = c.max_tracks ? c.max_tracks : 128, NM = c.max_dets ? c.max_dets : 128, D = c.feature_dim ? c.feature_dim : 512;
-        if (S < 1 || S > TRACK_MAX_TRACKS) return fail(OPD_EINVAL, me + "max_tracks " + std::to_string(S) + " outside 1 .. 1024");
-        if (NM < 1 || NM > TRACK_MAX_DETS) return fail(OPD_EINVAL, me + "max_dets " + std::to_string(NM) + " outside 1 .. 1024");
-        if (D < 1 || D > TRACK_MAX_DIM) return fail(OPD_EINVAL, me + "feature_dim " + std::to_string(D) + " outside 1 .. 2048");
-        if (c.max_age < 0 || c.min_hits < 0) return fail(OPD_EINVAL, me + "max_age and min_hits must not be negative");
-        double aw = c.appearance_weight, mw = c.motion_weight;
-        if (aw == 0.0 && mw == 0.0) { aw = 0.7; mw = 0.3; }
-        if (!(aw >= 0.0) || !(mw >= 0.0) || !(fabs(aw + mw - 1.0) <= 1e-6))
-            return fail(OPD_EINVAL, me + "appearance_weight (" + std::to_string(aw) + ") + motion_weight (" + std::to_string(mw) + ") must equal 1.0");
-        if (!(c.high_conf_threshold == c.high_conf_threshold) || !(c.max_position_distance == c.max_position_distance))
-            return fail(OPD_EINVAL, me + "a threshold is not a number");
-        RCCHK(use_device("opd_track_create", device_ordinal));
-        std::unique_ptr<opd_track, decltype(&opd_track_destroy)> t(new opd_track(), opd_track_destroy);   // a failure below releases whatever was already made
-        t->device = device_ordinal;
-        t->S = S; t->NM = NM; t->D = D;
-        t->max_age = c.max_age ? c.max_age : 30;
-        t->min_hits = c.min_hits ? c.min_hits : 3;
-        t->iou_threshold = c.iou_threshold != 0.0 ? c.iou_threshold : 0.3;
-        t->aw = aw; t->mw = mw;
-        t->max_dist = c.max_position_distance == 0.0 ? 150.0 : c.max_position_distance;
-        t->high_conf = c.high_conf_threshold != 0.0 ? c.high_conf_threshold : 0.5;
-        RCCHK(made("opd_track_create", "stream creation", hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)));
-        // the state: one allocation, zeroed
-        size_t off = 0;
-        auto place = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
-        const size_t s_x = place((size_t)S * 16), s_P = place((size_t)S * 64), s_last = place((size_t)S * 8), s_box = place((size_t)S * 16);
-        const size_t s_ring = place((size_t)S * TRACK_RING * D * 4), s_meta = place((size_t)S * 8), s_smooth = place((size_t)S * D * 4);
-        RCCHK(made("opd_track_create", "state allocation", hipMalloc((void**)&t->d_state, off)));
-        RCCHK(made("opd_track_create", "state clearing", hipMemset(t->d_state, 0, off)));
-        t->st.x = reinterpret_cast<float*>(t->d_state + s_x);
-        t->st.P = reinterpret_cast<float*>(t->d_state + s_P);
-        t->st.last = reinterpret_cast<float*>(t->d_state + s_last);
-        t->st.box = reinterpret_cast<float*>(t->d_state + s_box);
-        t->st.ring = reinterpret_cast<float*>(t->d_state + s_ring);
-        t->st.ring_meta = reinterpret_cast<int32_t*>(t->d_state + s_meta);
-        t->st.smooth = reinterpret_cast<float*>(t->d_state + s_smooth);
-        // the staging pair: inputs (adjacent, one copy), the commit list, the three matrices
-        off = 0;
-        t->o_slots = place((size_t)S * 4); t->o_boxes = place((size_t)NM * 16); t->o_foot = place((size_t)NM * 8); t->o_has = place((size_t)NM);
-        t->o_feat = place((size_t)NM * D * 4); t->o_ops = place((size_t)S * 16);
-        t->o_app = place((size_t)S * NM * 4); t->o_iou = place((size_t)S * NM * 4); t->o_comb = place((size_t)S * NM * 4);
-        t->io_bytes = off;
-        RCCHK(t->io.reserve("opd_track_create", off, off, t->stream));
-        memset(t->io.host, 0, off);
-        drop_all(t.get());
-        ++g_handle_epoch;   // device memory changed hands: graphs captured before are captured again (opd_device.h)
-        *out = t.release();
-        return OPD_OK;
-    });
-}
+extern "C" int opd_track_create(const opd_track_config* cfg, int device_ordinal, opd_track** out) { return api_call("opd_track_create", [&]() -> int {
+    const std::string me = "opd_track_create: ";
+    if (!out) return fail(OPD_EINVAL, me + "null argument");
+    *out = nullptr;
+    if (!cfg) return fail(OPD_EINVAL, me + "null configuration");
+    if (cfg->struct_size != (int32_t)sizeof(opd_track_config))
+        return fail(OPD_EINVAL, me + "struct_size " + std::to_string(cfg->struct_size) + ", this library's opd_track_config has " + std::to_string(sizeof(opd_track_config)) + " bytes");
+    const opd_track_config& c = *cfg;
+    const int S = c.max_tracks ? c.max_tracks : 128, NM = c.max_dets ? c.max_dets : 128, D = c.feature_dim ? c.feature_dim : 512;
+    if (S < 1 || S > TRACK_MAX_TRACKS) return fail(OPD_EINVAL, me + "max_tracks " + std::to_string(S) + " outside 1 .. 1024");
+    if (NM < 1 || NM > TRACK_MAX_DETS) return fail(OPD_EINVAL, me + "max_dets " + std::to_string(NM) + " outside 1 .. 1024");
+    if (D < 1 || D > TRACK_MAX_DIM) return fail(OPD_EINVAL, me + "feature_dim " + std::to_string(D) + " outside 1 .. 2048");
+    if (c.max_age < 0 || c.min_hits < 0) return fail(OPD_EINVAL, me + "max_age and min_hits must not be negative");
+    double aw = c.appearance_weight, mw = c.motion_weight;
+    if (aw == 0.0 && mw == 0.0) { aw = 0.7; mw = 0.3; }
+    if (!(aw >= 0.0) || !(mw >= 0.0) || !(fabs(aw + mw - 1.0) <= 1e-6))
+        return fail(OPD_EINVAL, me + "appearance_weight (" + std::to_string(aw) + ") + motion_weight (" + std::to_string(mw) + ") must equal 1.0");
+    if (!(c.high_conf_threshold == c.high_conf_threshold) || !(c.max_position_distance == c.max_position_distance))
+        return fail(OPD_EINVAL, me + "a threshold is not a number");
+    RCCHK(use_device("opd_track_create", device_ordinal));
+    std::unique_ptr<opd_track, decltype(&opd_track_destroy)> t(new opd_track(), opd_track_destroy);   // a failure below releases whatever was already made
+    t->device = device_ordinal;
+    t->S = S; t->NM = NM; t->D = D;
+    t->max_age = c.max_age ? c.max_age : 30;
+    t->min_hits = c.min_hits ? c.min_hits : 3;
+    t->iou_threshold = c.iou_threshold != 0.0 ? c.iou_threshold : 0.3;
+    t->aw = aw; t->mw = mw;
+    t->max_dist = c.max_position_distance == 0.0 ? 150.0 : c.max_position_distance;
+    t->high_conf = c.high_conf_threshold != 0.0 ? c.high_conf_threshold : 0.5;
+    RCCHK(made("opd_track_create", "stream creation", hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)));
+    // the state: one allocation, zeroed
+    size_t off = 0;
+    auto place = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+    const size_t s_x = place((size_t)S * 16), s_P = place((size_t)S * 64), s_last = place((size_t)S * 8), s_box = place((size_t)S * 16);
+    const size_t s_ring = place((size_t)S * TRACK_RING * D * 4), s_meta = place((size_t)S * 8), s_smooth = place((size_t)S * D * 4);
+    RCCHK(made("opd_track_create", "state allocation", hipMalloc((void**)&t->d_state, off)));
+    RCCHK(made("opd_track_create", "state clearing", hipMemset(t->d_state, 0, off)));
+    t->st.x = reinterpret_cast<float*>(t->d_state + s_x);
+    t->st.P = reinterpret_cast<float*>(t->d_state + s_P);
+    t->st.last = reinterpret_cast<float*>(t->d_state + s_last);
+    t->st.box = reinterpret_cast<float*>(t->d_state + s_box);
+    t->st.ring = reinterpret_cast<float*>(t->d_state + s_ring);
+    t->st.ring_meta = reinterpret_cast<int32_t*>(t->d_state + s_meta);
+    t->st.smooth = reinterpret_cast<float*>(t->d_state + s_smooth);
+    // the staging pair: inputs (adjacent, one copy), the commit list, the three matrices
+    off = 0;
+    t->o_slots = place((size_t)S * 4); t->o_boxes = place((size_t)NM * 16); t->o_foot = place((size_t)NM * 8); t->o_has = place((size_t)NM);
+    t->o_feat = place((size_t)NM * D * 4); t->o_ops = place((size_t)S * 16);
+    t->o_app = place((size_t)S * NM * 4); t->o_iou = place((size_t)S * NM * 4); t->o_comb = place((size_t)S * NM * 4);
+    t->io_bytes = off;
+    RCCHK(t->io.reserve("opd_track_create", off, off, t->stream));
+    memset(t->io.host, 0, off);
+    drop_all(t.get());
+    ++g_handle_epoch;   // device memory changed hands: graphs captured before are captured again (opd_device.h)
+    *out = t.release();
+    return OPD_OK;
+}); }
 
-extern "C" void opd_track_destroy(opd_track* t) {
-    if (!t) return;
-    ApiScope api_scope;
+extern "C" void opd_track_destroy(opd_track* t) { (void)api_call("opd_track_destroy", [&]() -> int {
+    if (!t) return OPD_OK;
     (void)hipSetDevice(t->device);
     if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
     if (t->d_state) (void)hipFree(t->d_state);
     t->io.release();
     delete t;
     ++g_handle_epoch;
-}
+    return OPD_OK;
+}); }
 
-extern "C" int opd_track_reset(opd_track* t) {
-    ApiScope api_scope;
+extern "C" int opd_track_reset(opd_track* t) { return api_call("opd_track_reset", [&]() -> int {
     if (!t) return fail(OPD_EINVAL, "opd_track_reset: null handle");
     drop_all(t);   // (a new track initialises every number of its slot: nothing on the device needs clearing)
     return OPD_OK;
-}
+}); }
 
-extern "C" int opd_track_info(const opd_track* t, opd_track_status* info) {
+extern "C" int opd_track_info(const opd_track* t, opd_track_status* info) { return api_call_unlocked("opd_track_info", [&]() -> int {
     if (!t || !info) return fail(OPD_EINVAL, "opd_track_info: null argument");
     *info = opd_track_status{t->S, t->NM, t->D, t->max_age, t->min_hits, t->device, (int32_t)t->tracks.size(), t->next_id, t->last_launches, t->last_waits};
     return OPD_OK;
-}
+}); }
 
 extern "C" int opd_track_update(opd_track* t, const float* boxes_xywh, const float* foot_xy, const float* confidence, const float* features,
-                                const uint8_t* has_feature, int feat_mem_kind, int n, int32_t* out_ids) {
-    ApiScope api_scope;
-    return guarded("opd_track_update", [&]() -> int {
-        if (!t) return fail(OPD_EINVAL, "opd_track_update: null handle");
-        if (n < 0) return fail(OPD_EINVAL, "opd_track_update: negative detection count");
-        if (n > t->NM) return fail(OPD_EINVAL, "opd_track_update: " + std::to_string(n) + " detections, the handle was made for max_dets = " + std::to_string(t->NM));
-        if (n > 0 && (!boxes_xywh || !foot_xy || !confidence || !out_ids)) return fail(OPD_EINVAL, "opd_track_update: null boxes, foot points, confidences or output");
-        if (feat_mem_kind != OPD_MEM_HOST && feat_mem_kind != OPD_MEM_DEVICE) return fail(OPD_EINVAL, "opd_track_update: feat_mem_kind must be OPD_MEM_HOST or OPD_MEM_DEVICE");
-        return update_body(t, boxes_xywh, foot_xy, confidence, features, has_feature, feat_mem_kind, n, out_ids);
-    });
-}
+                                const uint8_t* has_feature, int feat_mem_kind, int n, int32_t* out_ids) { return api_call("opd_track_update", [&]() -> int {
+    if (!t) return fail(OPD_EINVAL, "opd_track_update: null handle");
+    if (n < 0) return fail(OPD_EINVAL, "opd_track_update: negative detection count");
+    if (n > t->NM) return fail(OPD_EINVAL, "opd_track_update: " + std::to_string(n) + " detections, the handle was made for max_dets = " + std::to_string(t->NM));
+    if (n > 0 && (!boxes_xywh || !foot_xy || !confidence || !out_ids)) return fail(OPD_EINVAL, "opd_track_update: null boxes, foot points, confidences or output");
+    if (feat_mem_kind != OPD_MEM_HOST && feat_mem_kind != OPD_MEM_DEVICE) return fail(OPD_EINVAL, "opd_track_update: feat_mem_kind must be OPD_MEM_HOST or OPD_MEM_DEVICE");
+    return update_body(t, boxes_xywh, foot_xy, confidence, features, has_feature, feat_mem_kind, n, out_ids);
+}); }
 
-extern "C" int opd_track_get(opd_track* t, opd_track_rec* out, int capacity, int* count) {
-    ApiScope api_scope;
-    return guarded("opd_track_get", [&]() -> int {
-        if (!t || !count) return fail(OPD_EINVAL, "opd_track_get: null argument");
-        const int T = (int)t->tracks.size();
-        *count = T;
-        if (!out && capacity == 0) return OPD_OK;
-        if (!out || capacity < T) return fail(OPD_EINVAL, "opd_track_get: " + std::to_string(T) + " tracks, room for " + std::to_string(capacity));
-        if (T == 0) return OPD_OK;
-        HIPCHK(hipSetDevice(t->device));
-        std::vector<float> x((size_t)t->S * 4), box((size_t)t->S * 4);
-        HIPCHK(hipMemcpyAsync(x.data(), t->st.x, x.size() * 4, hipMemcpyDeviceToHost, t->stream));
-        HIPCHK(hipMemcpyAsync(box.data(), t->st.box, box.size() * 4, hipMemcpyDeviceToHost, t->stream));
-        HIPCHK(hipStreamSynchronize(t->stream));
-        for (int i = 0; i < T; ++i) {
-            const TrackEntry& e = t->tracks[i];
-            out[i] = opd_track_rec{e.id, e.age, e.hits, e.tsu, {}, {}};
-            memcpy(out[i].x, x.data() + 4 * (size_t)e.slot, 16);
-            memcpy(out[i].box, box.data() + 4 * (size_t)e.slot, 16);
-        }
-        return OPD_OK;
-    });
-}
+extern "C" int opd_track_get(opd_track* t, opd_track_rec* out, int capacity, int* count) { return api_call("opd_track_get", [&]() -> int {
+    if (!t || !count) return fail(OPD_EINVAL, "opd_track_get: null argument");
+    const int T = (int)t->tracks.size();
+    *count = T;
+    if (!out && capacity == 0) return OPD_OK;
+    if (!out || capacity < T) return fail(OPD_EINVAL, "opd_track_get: " + std::to_string(T) + " tracks, room for " + std::to_string(capacity));
+    if (T == 0) return OPD_OK;
+    HIPCHK(hipSetDevice(t->device));
+    std::vector<float> x((size_t)t->S * 4), box((size_t)t->S * 4);
+    HIPCHK(hipMemcpyAsync(x.data(), t->st.x, x.size() * 4, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipMemcpyAsync(box.data(), t->st.box, box.size() * 4, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    for (int i = 0; i < T; ++i) {
+        const TrackEntry& e = t->tracks[i];
+        out[i] = opd_track_rec{e.id, e.age, e.hits, e.tsu, {}, {}};
+        memcpy(out[i].x, x.data() + 4 * (size_t)e.slot, 16);
+        memcpy(out[i].box, box.data() + 4 * (size_t)e.slot, 16);
+    }
+    return OPD_OK;
+}); }
 
-extern "C" int opd_assign(const double* cost, int rows, int cols, int32_t* row_to_col) {
-    return guarded("opd_assign", [&]() -> int {
-        if (rows < 0 || cols < 0) return fail(OPD_EINVAL, "opd_assign: negative size");
-        if (rows > 0 && !row_to_col) return fail(OPD_EINVAL, "opd_assign: null output");
-        if (rows > 0 && cols > 0 && !cost) return fail(OPD_EINVAL, "opd_assign: null cost matrix");
-        assign_rect(cost, rows, cols, row_to_col);
-        return OPD_OK;
-    });
-}
+extern "C" int opd_assign(const double* cost, int rows, int cols, int32_t* row_to_col) { return api_call_unlocked("opd_assign", [&]() -> int {
+    if (rows < 0 || cols < 0) return fail(OPD_EINVAL, "opd_assign: negative size");
+    if (rows > 0 && !row_to_col) return fail(OPD_EINVAL, "opd_assign: null output");
+    if (rows > 0 && cols > 0 && !cost) return fail(OPD_EINVAL, "opd_assign: null cost matrix");
+    assign_rect(cost, rows, cols, row_to_col);
+    return OPD_OK;
+}); }

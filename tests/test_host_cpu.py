@@ -53,6 +53,35 @@ def test_product_library_exports_exactly_the_header():
     assert not hasattr(raw, "opd_test_set_graph_guard") and not hasattr(raw, "opd_launch_conv_gemm")
 
 
+def test_every_declared_function_is_defined_through_the_entry_wrapper():
+    """Every function of include/opd_detr.h does its work as ONE statement, `api_call("<its name>", ...)` (lock, then the catch-all that
+    keeps C++ exceptions from crossing the C-ABI) or the lock-free `api_call_unlocked(...)` (csrc/opd_device.h, csrc/opd_host.h): the
+    first statement of its definition, after at most the local a `const char*` getter returns.  No entry point locks or catches by hand."""
+    header = open(os.path.join(ROOT, "include", "opd_detr.h")).read()
+    declared = set(re.findall(r"\b(opd_[a-z0-9_]+)\s*\(", header)) - {"opd_config", "opd_det", "opd_model_info"}
+    csrc = os.path.join(ROOT, "office_person_detection_vit_amd", "csrc")
+    files = ["opd_api.cpp", "opd_comm.cpp", "opd_reid.cpp", "opd_color.cpp", "opd_flow.cpp", "opd_floor.cpp", "opd_track.cpp", "opd_lwt.cpp", "opd_host.cpp"]
+    text = {f: open(os.path.join(csrc, f)).read() for f in files}
+    unlocked = set()
+    for name in sorted(declared):
+        definition = re.compile(r'^(?:extern "C" )?(?:const char\*|int|void) ' + name + r"\([^)]*\)\s*\{", re.M)
+        found = [(f, m) for f, s in text.items() for m in definition.finditer(s)]
+        assert len(found) == 1, (name, [f for f, _ in found])
+        f, m = found[0]
+        first = re.match(r'\s*(?:const char\* text = "";\s*)?(?:return |\(void\))(api_call|api_call_unlocked)\("([a-z0-9_]+)",', text[f][m.end():])
+        assert first, f"{f}: {name} is not defined through api_call / api_call_unlocked"
+        assert first.group(2) == name, f"{f}: {name} reports errors as {first.group(2)}"
+        if first.group(1) == "api_call_unlocked":
+            unlocked.add(name)
+    for f, s in text.items():   # and nothing beside the wrapper takes the entry-point lock or catches
+        hooks = len(re.findall(r"^int reid_test_\w+\(", s, re.M))   # (bodies of two test hooks, csrc/opd_reid.h: no functions of the header)
+        assert s.count("ApiScope api_scope") == hooks, f
+        assert "guarded(" not in s and "catch (" not in s, f
+    # the lock-free entries: the ones that make no HIP call (and must not wait behind another thread's capture)
+    assert unlocked == {"opd_version", "opd_last_error", "opd_detr_info", "opd_reid_info", "opd_floor_info", "opd_track_info", "opd_lwt_info",
+                        "opd_comm_info", "opd_comm_buffers", "opd_detr_set_nms", "opd_person_nms", "opd_person_nms_batch", "opd_assign"}
+
+
 def test_weight_rounding_by_error_diffusion():
     """csrc/opd_host.cpp::round_f16_diffused: every value lands on an fp16 value next to it, the errors of a row sum to at most
     half an ulp of its largest weight (round-to-nearest: a random walk), fp16-exact input is untouched, and the result is the

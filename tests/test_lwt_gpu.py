@@ -290,6 +290,60 @@ def test_fused_interpolate_equals_flow_track_fed_into_the_restatement(lib, hw, s
         lib.opd_flow_destroy(flow)
 
 
+def test_a_refused_update_leaves_the_reference_usable_on_real_pixels(lib):
+    """An update the kernel refuses has built its frame's pyramid (of ITS size and level count) into the slot the flow handle's reference
+    does not use and never reaches the finish: handle A, which sees refused updates -- one of the reference's size (97 x 131, three
+    levels), one after a frame of another size (64 x 80, two levels) -- and handle B, which sees only the accepted calls, agree bit for
+    bit in LK's interpolation of real frames, in every number of every track and in opd_lwt_info."""
+    f0, f1 = FC.structured_pair(97, 131, 503, (2, 1))
+    g0, g1 = FC.structured_pair(64, 80, 504, (1, 1))
+    four = np.array([[56, 43, 12, 14], [61, 14, 10, 12], [90, 20, 14, 16], [100, 60, 12, 18]], F32)   # the first two lie inside 64 x 80 as well
+    five = np.concatenate([four, np.array([[20, 70, 10, 12]], F32)])                                  # ... and one box that overlaps none
+    p = dict(max_age=30, iou_threshold=0.3, use_optical_flow=True)
+
+    def observe(h):
+        st = LC.info(lib, _capi, h)
+        return [a.tobytes() for a in LC.device_states(lib, _capi, h)], tuple(getattr(st, n) for n, _ in st._fields_)
+
+    def run(refusals):
+        h = LC.create(lib, _capi, max_tracks=4, max_dets=5, max_h=97, max_w=131, **p)
+        seen = []
+
+        def refused():
+            rc, _ = LC.device_update(lib, _capi, h, five, f1)
+            assert rc == _capi.OPD_EINVAL and "max_tracks = 4" in _capi.last_error(), _capi.last_error()
+
+        def interpolate(frame):
+            recs = LC.device_interpolate(lib, _capi, h, frame)
+            seen.append(([q[0] for q in recs], np.array([q[1] for q in recs], F64).tobytes(), observe(h)))
+            return LC.info(lib, _capi, h).n_points
+
+        try:
+            rc, ids = LC.device_update(lib, _capi, h, four, f0)
+            assert rc == 0 and ids.tolist() == [1, 2, 3, 4], _capi.last_error()
+            if refusals:
+                refused()
+            assert 0 < interpolate(f1) <= 4   # LK ran against f0's pyramid and followed points
+            rc, ids = LC.device_update(lib, _capi, h, four[:2], g0)
+            assert rc == 0 and ids.tolist() == [1, 2], _capi.last_error()
+            if refusals:
+                refused()   # (97 x 131 into the other slot: the reference's 64 x 80 geometry is its own)
+            assert 0 < interpolate(g1) <= 2
+            n = C.c_int()   # and a frame that is not the reference's size is refused with the reference's size in the text, here as there
+            ptr, kind, fh, fw = LC._frame_args(f1)
+            assert lib.opd_lwt_interpolate(h, ptr, kind, fh, fw, (_capi.OpdLwtRec * 4)(), 4, C.byref(n)) == _capi.OPD_EINVAL
+            seen.append((_capi.last_error(), observe(h)))
+            assert "the reference has 64 x 80" in seen[-1][0]
+            return seen
+        finally:
+            lib.opd_lwt_destroy(h)
+
+    a, b = run(True), run(False)
+    assert len(a) == len(b) == 3
+    for k, (x, y) in enumerate(zip(a, b)):
+        assert x == y, k
+
+
 # ---- 4. independence ----------------------------------------------------------------------------------------------------------------------
 def test_a_track_does_not_depend_on_the_others_or_on_its_row(lib):
     p = dict(max_age=30, iou_threshold=0.3, use_optical_flow=True)

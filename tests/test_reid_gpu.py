@@ -148,6 +148,40 @@ def test_batch_independence_bit_identical_small_sets(lib, weight_cache, frames, 
         chunked.close()
 
 
+def test_kernel_table_hook_sums_per_name_and_leaves_the_handle_as_it_was(lib, weight_cache, frames):
+    """opd_test_reid_kernel_table (tiny tower, 2 crops): the rows of one and of two timed forwards name the same kernels in the same
+    (first-seen) order, launches and FLOPs of every row double exactly, every row took time; and the hook leaves profiling off and the
+    captured graphs valid: an extract after it returns the bytes of the extract before it."""
+    boxes, owner = R.golden_boxes()
+    boxes, owner = np.ascontiguousarray(boxes[:2], np.float32), np.ascontiguousarray(owner[:2], np.int32)
+    h = Handle(lib, ensure_clip_weight_file(weight_cache, "tiny"), 16)
+    try:
+        before = h.extract(frames, boxes, owner, dim=128)
+        hw = np.array([f.shape[:2] for f in frames], np.int32)
+        ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
+
+        def table(iters):
+            cap = 64
+            rows, count = (_capi.OpdKernelStat * cap)(), C.c_int()
+            _capi.check(lib.opd_test_reid_kernel_table(h.h, ptrs, hw.ctypes.data, len(frames), boxes.ctypes.data, owner.ctypes.data, 2, iters, rows, cap,
+                                                       C.byref(count)), "opd_test_reid_kernel_table")
+            assert 0 < count.value <= cap
+            return [(rows[i].name.decode(), rows[i].launches, rows[i].ms, rows[i].flops) for i in range(count.value)]
+
+        one, two = table(1), table(2)
+        for r in one:
+            print(f"reid kernel table: {r[0]:60s} launches {r[1]:3d}  {r[2]:.4f} ms  {r[3]:.3e} flop")
+        assert [r[0] for r in one] == [r[0] for r in two] and len({r[0] for r in one}) == len(one)
+        assert all(r[0] and r[0] != "(unnamed)" for r in one)
+        assert [r[1] * 2 for r in one] == [r[1] for r in two] and all(r[1] > 0 for r in one)
+        assert [r[3] * 2 for r in one] == [r[3] for r in two] and any(r[3] > 0 for r in one)
+        assert all(r[2] > 0 for r in one + two)
+        after = h.extract(frames, boxes, owner, dim=128)
+        assert before.tobytes() == after.tobytes() and np.all(np.isfinite(after))
+    finally:
+        h.close()
+
+
 def test_handles_on_two_threads_bit_identical(lib, weight_cache, frames, mild):
     """Two Re-ID handles driven from two threads at once (graph captures, staging growth and copies interleaved) give the features a
     single thread gets: the entry points hold the library's API lock and a capture takes it exclusively."""
