@@ -271,6 +271,7 @@ TEST_API = {
     "opd_test_round_f16_diffused": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "opd_test_dec_qkv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p] * 4),
     "opd_test_dec_self": (C.c_int, [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "opd_test_attention_map": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     "opd_test_attention_split": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "opd_test_dec_cross_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]),
     "opd_test_dec_ffn": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),

@@ -233,7 +233,7 @@ TAPI int opd_test_gemm_splitk_ln(const uint16_t* x, const uint16_t* w, const flo
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     p.out = slab;
     HIPCHK(opd_launch_conv_gemm(p, nullptr));
-    HIPCHK(opd_launch_reduce_ln(slab, splits, MN, dres, dg, db, dy, dy16, M, nullptr));
+    HIPCHK(opd_launch_reduce_ln(slab, splits, MN, dres, dg, db, dy, dy16, M, nullptr, g_test_dtype));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(y, dy, MN));
     return down(y16, dy16, MN);
@@ -567,6 +567,30 @@ TAPI int opd_test_attention_split(const uint16_t* q, const uint16_t* k, const ui
     return down(part_ml, p.part_ml, nm);
 }
 
+// the cross-attention map of ONE frame and layer (attn_map_*_kernel): q [rows][ldq], k [Lk][ldk] (head h at columns 32 h; the hook sizes q by
+// the largest selected row), sel [nsel] rows of q, key_valid2 (nullable) = (rows, cols) of the valid keys; out [Lk]
+TAPI int opd_test_attention_map(const uint16_t* q, int ldq, const uint16_t* k, int ldk, const int32_t* sel, int nsel, int heads, int Lk, float scale,
+                                const int32_t* key_valid2, int key_row, float* out) {
+    if (!q || !k || !sel || !out || nsel <= 0 || heads <= 0 || Lk <= 0 || key_row <= 0 || ldq < heads * 32 || ldk < heads * 32)
+        return fail(OPD_EINVAL, "attention_map: bad arguments");
+    int qrows = 0;
+    for (int i = 0; i < nsel; ++i) {
+        if (sel[i] < 0) return fail(OPD_EINVAL, "attention_map: negative query index");
+        qrows = std::max(qrows, sel[i] + 1);
+    }
+    DevMem dm;
+    const uint16_t* dq = dm.up(q, (size_t)qrows * ldq);
+    const uint16_t* dk = dm.up(k, (size_t)Lk * ldk);
+    const int32_t* dsel = dm.up(sel, (size_t)nsel);
+    const int32_t* dvalid = key_valid2 ? dm.up(key_valid2, 2) : nullptr;
+    float* stat = dm.alloc<float>((size_t)nsel * heads * 2);
+    float* dout = dm.alloc<float>((size_t)Lk);
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    HIPCHK(opd_launch_attention_map(dq, ldq, dk, ldk, dsel, nsel, heads, Lk, scale, dvalid, key_row, stat, dout, nullptr, g_test_dtype));
+    HIPCHK(hipDeviceSynchronize());
+    return down(out, dout, (size_t)Lk);
+}
+
 TAPI int opd_test_layernorm(const float* x, const float* g, const float* b, float* y, uint16_t* y16, int rows) {
     DevMem dm;
     const size_t n = (size_t)rows * 256;
@@ -576,7 +600,7 @@ TAPI int opd_test_layernorm(const float* x, const float* g, const float* b, floa
     float* dy = dm.alloc<float>(n);
     uint16_t* dy16 = dm.alloc<uint16_t>(n);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_layernorm(dx, dg, db, dy, dy16, rows, nullptr));
+    HIPCHK(opd_launch_layernorm(dx, dg, db, dy, dy16, rows, nullptr, g_test_dtype));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(y, dy, n));
     return down(y16, dy16, n);
@@ -588,7 +612,7 @@ TAPI int opd_test_maxpool(const uint16_t* x, uint16_t* out, int B, int H, int W,
     const uint16_t* dx = dm.up(x, (size_t)B * H * W * C);
     uint16_t* dout = dm.alloc<uint16_t>(n);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_maxpool(dx, dout, B, H, W, C, OH, OW, nullptr));
+    HIPCHK(opd_launch_maxpool(dx, dout, B, H, W, C, OH, OW, nullptr, g_test_dtype));
     HIPCHK(hipDeviceSynchronize());
     return down(out, dout, n);
 }
@@ -601,7 +625,7 @@ TAPI int opd_test_preprocess_u8(const uint8_t* frames, uint16_t* out, int B, int
     uint16_t* dout = dm.alloc<uint16_t>(n);
     const int32_t* dvalid = valid_hw ? dm.up(valid_hw, (size_t)B * 2) : nullptr;
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_preprocess_u8(din, dout, B, H, W, Hp, Wp, dvalid, nullptr));
+    HIPCHK(opd_launch_preprocess_u8(din, dout, B, H, W, Hp, Wp, dvalid, nullptr, g_test_dtype));
     HIPCHK(hipDeviceSynchronize());
     return down(out, dout, n);
 }
@@ -635,7 +659,7 @@ TAPI int opd_test_stem_pool(const uint16_t* x4p, const uint16_t* w, const float*
     const float* db = dm.up(bias, 64);
     uint16_t* dout = dm.alloc<uint16_t>(n);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_stem_pool(dx, dw, db, dout, B, Hp, Wp, OH, OW, PH, PW, nullptr));
+    HIPCHK(opd_launch_stem_pool(dx, dw, db, dout, B, Hp, Wp, OH, OW, PH, PW, nullptr, g_test_dtype));
     HIPCHK(hipDeviceSynchronize());
     return down(out, dout, n);
 }
@@ -655,9 +679,9 @@ TAPI int opd_test_stem_pool_u8(const uint8_t* frames, const int32_t* valid_hw, c
     uint16_t* d1 = dm.alloc<uint16_t>(n);
     uint16_t* d2 = dm.alloc<uint16_t>(n);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_stem_pool_u8(df, dv, dw, db, d1, B, H, W, OH, OW, PH, PW, nullptr));
-    HIPCHK(opd_launch_preprocess_u8(df, dx, B, H, W, Hp, Wp, dv, nullptr));
-    HIPCHK(opd_launch_stem_pool(dx, dw, db, d2, B, Hp, Wp, OH, OW, PH, PW, nullptr));
+    HIPCHK(opd_launch_stem_pool_u8(df, dv, dw, db, d1, B, H, W, OH, OW, PH, PW, nullptr, g_test_dtype));
+    HIPCHK(opd_launch_preprocess_u8(df, dx, B, H, W, Hp, Wp, dv, nullptr, g_test_dtype));
+    HIPCHK(opd_launch_stem_pool(dx, dw, db, d2, B, Hp, Wp, OH, OW, PH, PW, nullptr, g_test_dtype));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(out_fused, d1, n));
     return down(out_split, d2, n);
@@ -838,7 +862,7 @@ TAPI int opd_test_dec_self(const uint16_t* q16, const uint16_t* k16, const uint1
     p.qc16 = dm.alloc<uint16_t>(n);
     p.wo = up_frag(dm, wo, 256, 256); p.wq = up_frag(dm, wq, 256, 256);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    p.B = B; p.Q = Q; p.scale = scale;
+    p.B = B; p.Q = Q; p.scale = scale; p.qc_bf16 = (g_test_dtype == OPD_DT_BF16);
     HIPCHK(opd_launch_dec_self(p, nullptr));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(h, p.h, n));
