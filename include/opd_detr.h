@@ -224,6 +224,38 @@ OPD_API int opd_detr_set_nms(opd_detr* m, int person_label, float nms_threshold)
  * frame's records and count are left as they were; the other frames are done). */
 OPD_API int opd_detr_nms_records(opd_detr* m, opd_det* dets, int32_t* counts, int n_frames, int stride, int person_label, float nms_threshold);
 
+/* ---- tiled detection: a frame cut into overlapping tiles of ONE size, detected and merged across the seams in one call ------------
+ * One merged detection (48 bytes), in pixels of the FRAME: what `tiling.merge_tile_detections` returns as `bbox` (x, y, w, h in
+ * float64), with the score, label and `query_index` of the per-tile record that opened it and the index of that record's tile. */
+typedef struct opd_tile_det { double x, y, w, h; float score; int32_t label, query_index, tile; } opd_tile_det;
+/* `struct_size` = sizeof of this struct (40).  `person_label` / `tile_nms_threshold`: the per-tile filter and suppression, as in
+ * opd_detr_set_nms (a threshold >= 1 filters and sorts only).  The merge (float64, the Python rule operation for operation): in
+ * descending score order a record is dropped when its IoU with a kept box exceeds `merge_nms_threshold` (>= 1: nothing is ever
+ * absorbed), and when it comes from another tile than the kept box, one of the two has a side within `edge_tolerance` x tile size of
+ * an INTERIOR tile edge and their intersection covers more than `merge_threshold` of the smaller, the kept box grows to their union. */
+typedef struct opd_tile_params { int32_t struct_size, person_label; float tile_nms_threshold; float pad;
+                                 double merge_nms_threshold, merge_threshold, edge_tolerance; } opd_tile_params;
+/* `frames`: n_frames HOST pointers, each a contiguous uint8 [h][w][3] BGR frame.  `tiles_yxhw`: [n_tiles][4] = (y0, x0, th, tw), the
+ * same windows for every frame.  Each frame is uploaded ONCE; its tiles are resampled to H x W from where it lies on the device
+ * (Pillow-exact, byte for byte opd_detr_resize_u8 of contiguous copies of the windows), go through one forward of n_frames x n_tiles
+ * images, are post-processed to tile pixels, filtered and suppressed per tile and merged per frame, all on the device behind ONE wait.
+ * `out`: [n_frames][n_tiles x num_queries] records, `counts`: [n_frames], host memory; frame f's records are out[f x n_tiles x
+ * num_queries ...), in the order the Python rule keeps them.  The handle's opd_detr_set_nms state is neither used nor changed.
+ * OPD_EINVAL before any device call: a null pointer, a wrong struct_size, a NaN or negative tile_nms_threshold,
+ * n_frames x n_tiles outside [1, max_batch], a window outside the frame, windows of MORE THAN ONE SIZE (one forward has one model
+ * size), n_tiles x num_queries > 1024 candidates per frame, H x W outside the handle's maximum. */
+OPD_API int opd_detr_detect_tiled(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w,
+                                  const int32_t* tiles_yxhw, int n_tiles, int H, int W, float threshold,
+                                  const opd_tile_params* p, opd_tile_det* out, int32_t* counts);
+/* The merge alone, on records of the caller (the gathered buffer of a sharded tiled step): HOST `recs` [n_frames x n_tiles][stride] in
+ * tile pixels and `tile_counts` [n_frames x n_tiles], taken as they are (no filter, no suppression: `person_label` and
+ * `tile_nms_threshold` are not read); the windows may differ in size.  Blocking; `out` [n_frames][n_tiles x stride], `counts`
+ * [n_frames].  A negative tile count counts as 0.  OPD_EINVAL before any device call: a null pointer, a wrong struct_size, n_frames < 0,
+ * n_tiles < 1, stride < 1, n_tiles x stride > 1024, a window outside the h x w frame.  OPD_EINVAL after the wait: a tile count above
+ * the stride (that frame comes back with count 0; the other frames are done). */
+OPD_API int opd_detr_merge_tiles(opd_detr* m, const opd_det* recs, const int32_t* tile_counts, int n_frames, int n_tiles, int stride,
+                                 const int32_t* tiles_yxhw, int h, int w, const opd_tile_params* p, opd_tile_det* out, int32_t* counts);
+
 /* Page-locked host memory for frame batches handed over with OPD_MEM_HOST: the upload of such a buffer is one asynchronous DMA
  * instead of the runtime's staged copy of pageable memory.  Optional (any host pointer is accepted everywhere); the Python shim
  * stacks the caller's frames (`detect_batch(frames: list[np.ndarray])`, the reference's calling convention) directly into it. */

@@ -45,6 +45,16 @@ class OpdDet(C.Structure):
                 ("label", C.c_int32), ("query_index", C.c_int32), ("frame", C.c_int32)]
 
 
+class OpdTileDet(C.Structure):   # opd_tile_det (48 bytes): a merged detection of a tiled frame, frame pixels
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("w", C.c_double), ("h", C.c_double), ("score", C.c_float), ("label", C.c_int32),
+                ("query_index", C.c_int32), ("tile", C.c_int32)]
+
+
+class OpdTileParams(C.Structure):   # opd_tile_params (40 bytes)
+    _fields_ = [("struct_size", C.c_int32), ("person_label", C.c_int32), ("tile_nms_threshold", C.c_float), ("pad", C.c_float),
+                ("merge_nms_threshold", C.c_double), ("merge_threshold", C.c_double), ("edge_tolerance", C.c_double)]
+
+
 class OpdModelInfo(C.Structure):
     _fields_ = [("depths", C.c_int32 * 4), ("d_model", C.c_int32), ("heads", C.c_int32), ("ffn_dim", C.c_int32),
                 ("encoder_layers", C.c_int32), ("decoder_layers", C.c_int32), ("num_queries", C.c_int32),
@@ -149,6 +159,12 @@ API = {
     "opd_person_nms_batch": (C.c_int, [C.POINTER(OpdDet), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float]),
     "opd_detr_set_nms": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "opd_detr_nms_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float]),
+    # frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, params, out, counts
+    "opd_detr_detect_tiled": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                        C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
+    # recs, tile_counts, n_frames, n_tiles, stride, tiles_yxhw, h, w, params, out, counts
+    "opd_detr_merge_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                       C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
     "opd_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "opd_host_free": (None, [C.c_void_p]),
     "opd_similarity_matrix": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -310,6 +326,11 @@ TEST_API = {
     "opd_test_crop_plan_staged": (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 7 + [C.c_int]),
     # suppression hook (csrc/opd_nms_test_api.cpp): the device kernel's algorithm on the host; dets, counts, n_frames, stride, label, threshold
     "opd_test_nms_plan_host": (C.c_int, [C.POINTER(OpdDet), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float]),
+    # tiled-detection hooks (csrc/opd_tile_test_api.cpp): opd_detr_merge_tiles's arguments without the handle, on the host; the tile resize kernel
+    # alone: frames, n_frames, h, w, tiles_yxhw, n_tiles, oh, ow, out
+    "opd_test_tile_merge_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                           C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
+    "opd_test_tile_resize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     # optical-flow hook (csrc/opd_flow_test_api.cpp)
     "opd_flow_test_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     # floor-map hook (csrc/opd_floor_test_api.cpp)

@@ -9,6 +9,7 @@
 #include "opd_model.h"
 #include "opd_nms.h"
 #include "opd_reid.h"
+#include "opd_tile.h"
 
 namespace opd {
 
@@ -53,6 +54,25 @@ static int stage_pixels(opd_detr* m, const void* pixels, int pixel_format, int m
     return OPD_OK;
 }
 
+// The handle's coefficient tables of a h x w -> oh x ow resize (opd_resize_coeffs), built and uploaded by the first call that needs them
+static int resize_tab(opd_detr* m, int h, int w, int oh, int ow, const opd_detr::ResizeTab** out) {
+    for (const auto& t : m->resize_tabs)
+        if (t.h == h && t.w == w && t.oh == oh && t.ow == ow) { *out = &t; return OPD_OK; }
+    std::vector<int32_t> bh, kh, bv, kv;
+    opd_detr::ResizeTab t{h, w, oh, ow, 0, 0, nullptr, nullptr, nullptr, nullptr};
+    opd_resize_coeffs(w, ow, &bh, &kh, &t.ksh);
+    opd_resize_coeffs(h, oh, &bv, &kv, &t.ksv);
+    auto up = [&](const std::vector<int32_t>& v, int32_t** d) -> int {
+        RCCHK(dalloc(m, d, v.size(), false));
+        HIPCHK(hipMemcpy(*d, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+        return OPD_OK;
+    };
+    RCCHK(up(bh, &t.bh)); RCCHK(up(kh, &t.kh)); RCCHK(up(bv, &t.bv)); RCCHK(up(kv, &t.kv));
+    m->resize_tabs.push_back(t);
+    *out = &m->resize_tabs.back();
+    return OPD_OK;
+}
+
 // Frames at camera resolution -> m->d_u8 at model resolution (Pillow-exact bilinear, kernels_misc.hip).
 // (`list` != null: one host pointer per frame instead of the contiguous block `frames`)
 static int enqueue_resize(opd_detr* m, const uint8_t* frames, int mem_kind, int B, int h, int w, int oh, int ow, const uint8_t* const* list = nullptr) {
@@ -69,22 +89,7 @@ static int enqueue_resize(opd_detr* m, const uint8_t* frames, int mem_kind, int 
         d_in = m->src.dev;
     }
     const opd_detr::ResizeTab* tab = nullptr;
-    for (const auto& t : m->resize_tabs)
-        if (t.h == h && t.w == w && t.oh == oh && t.ow == ow) tab = &t;
-    if (!tab) {
-        std::vector<int32_t> bh, kh, bv, kv;
-        opd_detr::ResizeTab t{h, w, oh, ow, 0, 0, nullptr, nullptr, nullptr, nullptr};
-        opd_resize_coeffs(w, ow, &bh, &kh, &t.ksh);
-        opd_resize_coeffs(h, oh, &bv, &kv, &t.ksv);
-        auto up = [&](const std::vector<int32_t>& v, int32_t** d) -> int {
-            RCCHK(dalloc(m, d, v.size(), false));
-            HIPCHK(hipMemcpy(*d, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-            return OPD_OK;
-        };
-        RCCHK(up(bh, &t.bh)); RCCHK(up(kh, &t.kh)); RCCHK(up(bv, &t.bv)); RCCHK(up(kv, &t.kv));
-        m->resize_tabs.push_back(t);
-        tab = &m->resize_tabs.back();
-    }
+    RCCHK(resize_tab(m, h, w, oh, ow, &tab));
     HIPCHK(opd_launch_resize_u8(d_in, m->d_u8, B, h, w, oh, ow, tab->bh, tab->kh, tab->ksh, tab->bv, tab->kv, tab->ksv, m->stream));
     return OPD_OK;
 }
@@ -118,7 +123,9 @@ static int enqueue_nms(opd_detr* m, opd_det* dets, int32_t* counts, int n_frames
 
 // `orig_hw` (nullable): the frame sizes the boxes are scaled to, else h x w for every frame.  `dev_out` / `dev_counts` (nullable): device buffers of the
 // caller; the kernel then writes there directly instead of the library's own record buffers (no device-to-device copies afterwards).
-static int enqueue_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, int h, int w, opd_det* dev_out, int32_t* dev_counts) {
+// `tiled` (nullable; opd_detr_detect_tiled): the suppression behind the post-process is this call's, not the handle's opd_detr_set_nms state.
+static int enqueue_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, int h, int w, opd_det* dev_out, int32_t* dev_counts,
+                               const opd_tile_params* tiled = nullptr) {
     const int B = m->last_B;
     std::vector<int32_t> hw((size_t)B * 2);
     for (int b = 0; b < B; ++b) {
@@ -136,8 +143,10 @@ static int enqueue_postprocess(opd_detr* m, float threshold, const int32_t* orig
     pp.counts = dev_counts ? dev_counts : m->d_counts;
     pp.B = B; pp.Q = m->arch.queries; pp.ncls = m->arch.ncls; pp.threshold = threshold;
     RCCHK(launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_postprocess(pp, m->stream); }));
-    if (m->nms_threshold >= 0.f)   // opd_detr_set_nms: the stages behind, and the caller, see final records in score order (in front of mark 8: the
-        RCCHK(enqueue_nms(m, static_cast<opd_det*>(pp.records), pp.counts, B, pp.Q, m->nms_label, m->nms_threshold));   // kernel's time is part of stage_ms[7])
+    const int nms_label = tiled ? tiled->person_label : m->nms_label;
+    const float nms_threshold = tiled ? tiled->tile_nms_threshold : m->nms_threshold;
+    if (nms_threshold >= 0.f)   // opd_detr_set_nms: the stages behind, and the caller, see final records in score order (in front of mark 8: the
+        RCCHK(enqueue_nms(m, static_cast<opd_det*>(pp.records), pp.counts, B, pp.Q, nms_label, nms_threshold));   // kernel's time is part of stage_ms[7])
     MARK(8);
     return OPD_OK;
 }
@@ -263,6 +272,103 @@ static int forward_device(opd_detr* m, const FrameSource& src, int B, int H, int
         HIPCHK(hipMemcpyAsync(enc_features, m->d_x32, (size_t)B * m->last_fh * m->last_fw * m->arch.d_model * 4, kind, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     if (m->profiling == 1) timed_collect(m);
+    return OPD_OK;
+}
+
+// ---- tiled detection ----------------------------------------------------------------------------------------------------
+// What the two tiled entries check alike, before any device call: the parameter block and the windows ([n_tiles][4] = y0, x0, th, tw) on an h x w frame
+static int check_tiles(const std::string& who, const opd_tile_params* p, const int32_t* tiles, int n_tiles, int h, int w, bool one_size) {
+    if (!p || !tiles) return fail(OPD_EINVAL, who + ": null argument");
+    if (p->struct_size != (int32_t)sizeof(opd_tile_params)) return fail(OPD_EINVAL, who + ": opd_tile_params.struct_size mismatch");
+    if (n_tiles < 1) return fail(OPD_EINVAL, who + ": n_tiles < 1");
+    if (h < 1 || w < 1 || (size_t)h * w > (size_t)1 << 26) return fail(OPD_EINVAL, who + ": frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
+    for (int t = 0; t < n_tiles; ++t) {
+        const int32_t* g = tiles + 4 * t;
+        if (g[0] < 0 || g[1] < 0 || g[2] < 1 || g[3] < 1 || (long long)g[0] + g[2] > h || (long long)g[1] + g[3] > w)
+            return fail(OPD_EINVAL, who + ": tile " + std::to_string(t) + " (y0 " + std::to_string(g[0]) + ", x0 " + std::to_string(g[1]) + ", " + std::to_string(g[2]) + " x " +
+                                        std::to_string(g[3]) + ") lies outside the " + std::to_string(h) + " x " + std::to_string(w) + " frame");
+        if (one_size && (g[2] != tiles[2] || g[3] != tiles[3]))
+            return fail(OPD_EINVAL, who + ": tiles of more than one size (" + std::to_string(tiles[2]) + " x " + std::to_string(tiles[3]) + " and " + std::to_string(g[2]) + " x " +
+                                        std::to_string(g[3]) + "): one forward has one model size");
+    }
+    return OPD_OK;
+}
+
+static size_t tile_out_off(const opd_detr* m) { return align_up((size_t)m->cfg.max_batch * 4, 64); }   // [counts | records]: where the records begin
+
+static int detect_tiled(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles, int n_tiles, int H, int W, float threshold,
+                        const opd_tile_params* p, opd_tile_det* out, int32_t* counts) {
+    const int B = n_frames * n_tiles, Q = m->arch.queries, th = tiles[2], tw = tiles[3];
+    const size_t off = tile_out_off(m), cap = off + (size_t)m->cfg.max_batch * Q * sizeof(opd_tile_det);
+    if (!m->d_tile_out) {
+        RCCHK(dalloc(m, &m->d_tiles, (size_t)m->cfg.max_batch * 4, false));
+        RCCHK(dalloc(m, &m->d_tile_out, cap, false));
+        HIPCHK(hipHostMalloc(&m->tile_pinned, cap, hipHostMallocDefault));
+    }
+    if (!m->d_nms_flag) {
+        RCCHK(dalloc(m, &m->d_nms_flag, 1, false));
+        HIPCHK(hipMemsetAsync(m->d_nms_flag, 0, 4, m->stream));
+    }
+    const std::vector<int32_t> win(tiles, tiles + (size_t)n_tiles * 4);
+    if (win != m->h_tiles) {   // the windows of a video do not change from call to call: upload only when they do
+        HIPCHK(hipStreamSynchronize(m->stream));   // (an earlier asynchronous copy may still be reading the old host vector)
+        m->h_tiles = win;
+        HIPCHK(hipMemcpyAsync(m->d_tiles, m->h_tiles.data(), m->h_tiles.size() * 4, hipMemcpyHostToDevice, m->stream));
+    }
+    // every frame once, whole
+    const size_t n1 = (size_t)h * w * 3;
+    RCCHK(m->src.reserve("source frames", 0, (size_t)n_frames * n1, m->stream));
+    for (int f = 0; f < n_frames; ++f) HIPCHK(hipMemcpyAsync(m->src.dev + f * n1, frames[f], n1, hipMemcpyHostToDevice, m->stream));
+    // its tiles from where it lies -> the stem's input block
+    const opd_detr::ResizeTab* tab = nullptr;
+    RCCHK(resize_tab(m, th, tw, H, W, &tab));
+    TileResizeParams rp{m->src.dev, m->d_u8, m->d_tiles, n_frames, n_tiles, h, w, th, tw, H, W, tab->bh, tab->kh, tab->bv, tab->kv, tab->ksh, tab->ksv};
+    m->timer.reset();
+    struct Hold { bool& b; explicit Hold(bool& x) : b(x) { b = true; } ~Hold() { b = false; } };
+    {
+        Hold hold(m->timer_hold);   // (the forward would drop the resize launch's event pair)
+        RCCHK(launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_tile_resize_u8(rp, m->stream); }));
+        RCCHK(run_forward(m, m->d_u8, OPD_PIXELS_U8_BGR_HWC, B, H, W));
+    }
+    // records in TILE pixels, filtered and suppressed per tile, then merged per frame
+    RCCHK(enqueue_postprocess(m, threshold, nullptr, th, tw, nullptr, nullptr, p));
+    TileMergeParams mp{};
+    mp.recs = m->d_records; mp.tile_counts = m->d_counts; mp.tiles_yxhw = m->d_tiles;
+    mp.counts = reinterpret_cast<int32_t*>(m->d_tile_out); mp.out = reinterpret_cast<opd_tile_det*>(m->d_tile_out + off); mp.flag = m->d_nms_flag;
+    mp.n_frames = n_frames; mp.n_tiles = n_tiles; mp.stride = Q; mp.frame_h = h; mp.frame_w = w;
+    mp.merge_nms_threshold = p->merge_nms_threshold; mp.merge_threshold = p->merge_threshold; mp.edge_tolerance = p->edge_tolerance;
+    RCCHK(launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_tile_merge(mp, m->stream); }));
+    const size_t rec = (size_t)B * Q * sizeof(opd_tile_det);
+    HIPCHK(hipMemcpyAsync(m->tile_pinned, m->d_tile_out, off + rec, hipMemcpyDeviceToHost, m->stream));   // [counts | records]: one copy, one wait
+    HIPCHK(hipStreamSynchronize(m->stream));
+    memcpy(counts, m->tile_pinned, (size_t)n_frames * 4);
+    memcpy(out, static_cast<const char*>(m->tile_pinned) + off, rec);
+    if (m->profiling == 1) timed_collect(m);
+    return OPD_OK;
+}
+
+// The merge kernel on host records of the caller: temporaries of the call, blocking
+static int merge_tiles(opd_detr* m, const opd_det* recs, const int32_t* tile_counts, int n_frames, int n_tiles, int stride, const int32_t* tiles, int h, int w,
+                       const opd_tile_params* p, opd_tile_det* out, int32_t* counts) {
+    const size_t nt = (size_t)n_frames * n_tiles, nr = nt * stride;
+    DevMem tmp;
+    TileMergeParams mp{};
+    mp.recs = tmp.up(recs, nr); mp.tile_counts = tmp.up(tile_counts, nt); mp.tiles_yxhw = tmp.up(tiles, (size_t)n_tiles * 4);
+    mp.out = tmp.alloc<opd_tile_det>(nr); mp.counts = tmp.alloc<int32_t>((size_t)n_frames);
+    const int32_t zero = 0;
+    mp.flag = tmp.up(&zero, 1);
+    if (!tmp.ok) return fail(OPD_ENOMEM, "opd_detr_merge_tiles: device allocation failed");
+    mp.n_frames = n_frames; mp.n_tiles = n_tiles; mp.stride = stride; mp.frame_h = h; mp.frame_w = w;
+    mp.merge_nms_threshold = p->merge_nms_threshold; mp.merge_threshold = p->merge_threshold; mp.edge_tolerance = p->edge_tolerance;
+    if (m->profiling == 1) m->timer.reset();
+    RCCHK(launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_tile_merge(mp, m->stream); }));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    int32_t over = 0;
+    HIPCHK(hipMemcpy(counts, mp.counts, (size_t)n_frames * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, mp.out, nr * sizeof(opd_tile_det), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&over, mp.flag, 4, hipMemcpyDeviceToHost));
+    if (m->profiling == 1) timed_collect(m);
+    if (over) return fail(OPD_EINVAL, "opd_detr_merge_tiles: a tile holds more records than its slots (its frame comes back empty)");
     return OPD_OK;
 }
 
@@ -401,6 +507,7 @@ void opd_detr_destroy(opd_detr* m) { (void)api_call("opd_detr_destroy", [&]() ->
     for (auto& a : m->async_host)
         if (a.pinned) (void)hipHostFree(a.pinned);
     if (m->sync_pinned) { (void)hipHostFree(m->sync_pinned); m->sync_pinned = nullptr; }
+    if (m->tile_pinned) { (void)hipHostFree(m->tile_pinned); m->tile_pinned = nullptr; }
     if (m->h_floor) { (void)hipHostFree(m->h_floor); m->h_floor = nullptr; }
     for (auto& e : m->ev)
         if (e) (void)hipEventDestroy(e);
@@ -465,6 +572,35 @@ int opd_detr_nms_records(opd_detr* m, opd_det* dets, int32_t* counts, int n_fram
         return fail(OPD_EINVAL, "opd_detr_nms_records: a frame holds more records than its slots (left as it was)");
     }
     return OPD_OK;
+}); }
+// Tiled detection: every refusal comes before the first device call (check_tiles; check_shape makes none for host pixels)
+int opd_detr_detect_tiled(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W, float threshold,
+                          const opd_tile_params* p, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled", [&]() -> int {
+    if (!frames || !out || !counts) return fail(OPD_EINVAL, "opd_detr_detect_tiled: null argument");
+    RCCHK(check_tiles("opd_detr_detect_tiled", p, tiles_yxhw, n_tiles, h, w, true));
+    if (!(p->tile_nms_threshold >= 0.f)) return fail(OPD_EINVAL, "opd_detr_detect_tiled: tile_nms_threshold is negative or NaN");
+    if (!m) return fail(OPD_EINVAL, "null model handle");
+    if ((long long)n_tiles * m->arch.queries > OPD_TILE_MAX_CAND)
+        return fail(OPD_EINVAL, "opd_detr_detect_tiled: " + std::to_string(n_tiles) + " tiles x " + std::to_string(m->arch.queries) + " queries exceed the 1024 candidates a frame's merge holds");
+    if (n_frames < 1 || (long long)n_frames * n_tiles > m->cfg.max_batch)
+        return fail(OPD_EINVAL, "opd_detr_detect_tiled: " + std::to_string(n_frames) + " frames x " + std::to_string(n_tiles) + " tiles outside [1, max_batch = " +
+                                    std::to_string(m->cfg.max_batch) + "]");
+    for (int f = 0; f < n_frames; ++f)
+        if (!frames[f]) return fail(OPD_EINVAL, "opd_detr_detect_tiled: null frame pointer");
+    RCCHK(check_shape(m, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, n_frames * n_tiles, H, W));
+    HIPCHK(hipSetDevice(m->device));
+    return detect_tiled(m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, out, counts);
+}); }
+int opd_detr_merge_tiles(opd_detr* m, const opd_det* recs, const int32_t* tile_counts, int n_frames, int n_tiles, int stride, const int32_t* tiles_yxhw, int h, int w,
+                         const opd_tile_params* p, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_merge_tiles", [&]() -> int {
+    RCCHK(check_tiles("opd_detr_merge_tiles", p, tiles_yxhw, n_tiles, h, w, false));
+    if (n_frames < 0 || stride < 1 || (long long)n_tiles * stride > OPD_TILE_MAX_CAND)
+        return fail(OPD_EINVAL, "opd_detr_merge_tiles: n_frames < 0, stride < 1, or n_tiles x stride above the 1024 candidates a frame's merge holds");
+    if (!m) return fail(OPD_EINVAL, "null model handle");
+    if (n_frames == 0) return OPD_OK;
+    if (!recs || !tile_counts || !out || !counts) return fail(OPD_EINVAL, "opd_detr_merge_tiles: null argument");
+    HIPCHK(hipSetDevice(m->device));
+    return merge_tiles(m, recs, tile_counts, n_frames, n_tiles, stride, tiles_yxhw, h, w, p, out, counts);
 }); }
 int opd_detr_resize_u8(opd_detr* m, const uint8_t* frames, int B, int h, int w, int out_h, int out_w, uint8_t* out) { return api_call("opd_detr_resize_u8", [&]() -> int {
     if (!m) return fail(OPD_EINVAL, "null model handle");

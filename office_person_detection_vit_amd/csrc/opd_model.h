@@ -260,6 +260,13 @@ struct opd_detr : DetrWeights {
     int nms_label = 0;
     float nms_threshold = -1.0f;
     int32_t* d_nms_flag = nullptr;
+    // tiled detection (opd_detr_detect_tiled; allocated by its first call): the tile windows, [counts of max_batch frames | merged records of
+    // max_batch x queries candidates] and its page-locked twin.  timer_hold: the tiled call's resize launch keeps its row of the kernel table
+    int32_t* d_tiles = nullptr;
+    std::vector<int32_t> h_tiles;
+    char* d_tile_out = nullptr;
+    void* tile_pinned = nullptr;
+    bool timer_hold = false;
 
     // state of the last forward
     int last_B = 0, last_H = 0, last_W = 0, last_fh = 0, last_fw = 0;

@@ -481,6 +481,59 @@ class HipDetrDetector:
             logger.error(f"Detection failed: {e}")
             raise
 
+    def detect_tiled(self, frames: Sequence[np.ndarray], tiles: Sequence[Tuple[int, int, int, int]], nms_threshold: float = 0.4,
+                     merge_threshold: float = 0.5, edge_tolerance: float = 0.01) -> List[List[Detection]]:
+        """Tiled detection in one native call per chunk (``opd_detr_detect_tiled``): every frame is uploaded once, its ``tiles``
+        (``tiling.tile_grid``'s ``(y0, x0, h, w)`` list, ONE size) are resampled on the device from where the frame lies, detected as a
+        batch, suppressed per tile at ``self.nms_threshold`` and merged across the seams on the device by ``tiling.merge_tile_detections``'s
+        rule (``nms_threshold``, ``merge_threshold``, ``edge_tolerance``: its arguments).  One list of frame-coordinate detections per frame,
+        what ``TiledDetector.detect_batch`` builds on the host, field for field."""
+        self._require_model()
+        frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
+        if not tiles or any(len(t) != 4 for t in tiles):
+            raise ValueError("tiles must be a non-empty list of (y0, x0, h, w)")
+        if len(tiles) > self.max_batch:
+            raise ValueError(f"the {len(tiles)} tiles of one frame exceed max_batch = {self.max_batch}")
+        if len({(t[2], t[3]) for t in tiles}) != 1:
+            raise ValueError("tiles of more than one size: one forward has one model size")
+        if len(frames) == 0:
+            return []
+        f0 = frames[0]
+        for f in frames:
+            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != f0.shape or not f.flags.c_contiguous:
+                raise ValueError("frames must be contiguous uint8 numpy arrays of shape (H, W, 3) in BGR order, all of one size")
+        h, w = int(f0.shape[0]), int(f0.shape[1])
+        th, tw = tiles[0][2], tiles[0][3]
+        H, W = model_input_size(th, tw, self.max_size[0], self.max_size[1]) if self.resize else (th, tw)
+        T, Q = len(tiles), self._info.num_queries
+        win = np.asarray(tiles, dtype=np.int32).reshape(T, 4)
+        params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
+                                     merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
+        per = max(1, self.max_batch // T)
+        out: List[List[Detection]] = []
+        try:
+            for i in range(0, len(frames), per):
+                chunk = frames[i:i + per]
+                n = len(chunk)
+                recs, counts = (_capi.OpdTileDet * (n * T * Q))(), (C.c_int32 * n)()
+                ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in chunk])
+                rc = self._lib.opd_detr_detect_tiled(C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, H, W,
+                                                     float(self.confidence_threshold), C.byref(params), recs, counts)
+                _capi.check(rc, "opd_detr_detect_tiled")
+                for b in range(n):
+                    dets = []
+                    for k in range(int(counts[b])):
+                        r = recs[b * T * Q + k]
+                        bbox = (r.x, r.y, r.w, r.h)
+                        dets.append(Detection(bbox=bbox, confidence=float(r.score), class_id=int(r.label), class_name="person",
+                                              camera_coords=(bbox[0] + bbox[2] / 2, bbox[1] + bbox[3]), features=None, query_index=int(r.query_index)))
+                    out.append(dets)
+            self._last_orig = [(h, w)] * len(frames)
+            return out
+        except Exception as e:
+            logger.error(f"Detection failed: {e}")
+            raise
+
     def _detect_chunks_overlapped(self, chunks: List[List[np.ndarray]], floor_map=None) -> List[List[Detection]]:
         """Chunk k runs on handle ``k % streams``; one worker thread per handle drives its chunks in order.
 

@@ -112,14 +112,28 @@ def merge_tile_detections(tile_dets: Sequence[Sequence[Detection]], origins: Seq
 
 class TiledDetector:
     """``detect`` / ``detect_batch`` on frames that are cut into ``rows x cols`` overlapping tiles first.  ``detector`` is
-    anything with ``detect_batch`` (a loaded ``HipDetrDetector`` or a ``ShardedDetector``)."""
+    anything with ``detect_batch`` (a loaded ``HipDetrDetector`` or a ``ShardedDetector``).
+
+    ``native=True``: a frame is ONE call of the wrapped detector's ``detect_tiled`` (``HipDetrDetector``: the frame is uploaded once, its
+    tiles are cut and resampled on the device and the merge below runs there in a kernel, the same lists field for field); a wrapped
+    detector without ``detect_tiled`` is refused, there is no silent fallback to the host path."""
 
     def __init__(self, detector, rows: int = 2, cols: int = 2, nms_threshold: float = 0.4, overlap: float = DEFAULT_OVERLAP,
-                 merge_threshold: float = 0.5):
+                 merge_threshold: float = 0.5, native: bool = False):
         self.detector, self.rows, self.cols, self.nms_threshold = detector, rows, cols, nms_threshold
-        self.overlap, self.merge_threshold = overlap, merge_threshold
+        self.overlap, self.merge_threshold, self.native = overlap, merge_threshold, bool(native)
 
     def detect_batch(self, frames: Sequence[np.ndarray]) -> List[List[Detection]]:
+        if self.native:
+            if not hasattr(self.detector, "detect_tiled"):
+                raise ValueError("native=True needs a detector with detect_tiled (a HipDetrDetector); "
+                                 f"{type(self.detector).__name__} has none")
+            if len(frames) == 0:
+                return []
+            if len({(f.shape[0], f.shape[1]) for f in frames}) != 1:
+                raise ValueError("native=True takes frames of one size")
+            grid = tile_grid(frames[0].shape[0], frames[0].shape[1], self.rows, self.cols, self.overlap)
+            return self.detector.detect_tiled(frames, grid, self.nms_threshold, self.merge_threshold)
         tiles, origins, sizes = [], [], []
         for f in frames:
             t, o = split_tiles(f, self.rows, self.cols, self.overlap)
