@@ -326,8 +326,15 @@ int infer_arch(const StateDict& sd, Arch* a, std::string* err) {
     }
     a->queries = (int)q->second.shape[0];
     a->ncls = (int)c->second.shape[0];
-    if (q->second.shape[1] != 256 || c->second.shape[1] != 256 || a->queries > 128 || a->ncls > 256) {
-        *err = "unsupported d_model / num_queries / num_labels (kernels are built for d_model 256, <=128 queries)";
+    // the accepted range is what EVERY kernel of the detect path serves: dec_qkv_kernel / dec_self_kernel / postprocess_kernel hold at most 128
+    // queries, postprocess_kernel holds at most 128 classifier rows (two per lane) and needs one class beside the no-object row
+    const auto dims = [&]() {
+        return "d_model " + std::to_string(q->second.shape[1]) + ", " + std::to_string(q->second.shape[0]) + " queries, " +
+               std::to_string(c->second.shape[0]) + " classifier rows";
+    };
+    if (q->second.shape[1] != 256 || c->second.shape[1] != 256 || q->second.shape[0] < 1 || q->second.shape[0] > 128 || c->second.shape[0] < 2 ||
+        c->second.shape[0] > 128) {
+        *err = "unsupported architecture (" + dims() + "): the detect path serves d_model 256, 1 to 128 queries, 2 to 128 classifier rows";
         return OPD_ESCHEMA;
     }
     int rc;

@@ -729,13 +729,19 @@ TAPI int opd_test_stem_reduce(const uint8_t* frames, const int32_t* valid_hw, co
 // transpose them as opd_model.cpp does); logits [rows][ncls], boxes [rows][4]
 static int g_test_heads2 = 1;   // heads hooks: 1 = heads2_kernel (split fp16 operands), 0 = heads_kernel (fp32 matrix pipe)
 TAPI int opd_test_set_heads2(int on) { g_test_heads2 = on; return OPD_OK; }
-// (the three 256-wide layers as split fp16 pairs in fragment order, class matrix padded to 128 rows)
+// heads hooks: `logits` / `boxes` carry this many rows behind `rows`; the device buffers start as the caller's arrays (a sentinel in the spare
+// rows) and come back whole, so that a store past the last row shows
+static int g_test_heads_spare = 0;
+TAPI int opd_test_set_heads_spare_rows(int rows) { g_test_heads_spare = rows > 0 ? rows : 0; return OPD_OK; }
+// (the three 256-wide layers as split fp16 pairs in fragment order, class matrix padded to 128 rows; above 128 classes to 256 rows, which
+// heads2_kernel cannot take: opd_launch_heads has to pick heads_kernel by ncls then, as it does in the model)
 static void heads_frags(DevMem& dm, HeadParams& p, const float* wc, const float* w1, const float* w2, int ncls) {
-    if (!g_test_heads2 || ncls > 128) return;
-    std::vector<float> wcp((size_t)128 * 256, 0.f);
+    if (!g_test_heads2 || ncls > 256) return;
+    const int pad = ncls <= 128 ? 128 : 256;
+    std::vector<float> wcp((size_t)pad * 256, 0.f);
     std::copy(wc, wc + (size_t)ncls * 256, wcp.begin());
-    std::vector<uint16_t> f((size_t)2 * 128 * 256);
-    opd_split_f16_frag(wcp.data(), 128, 256, f.data());
+    std::vector<uint16_t> f((size_t)2 * pad * 256);
+    opd_split_f16_frag(wcp.data(), pad, 256, f.data());
     p.wc_f = dm.up(f.data(), f.size());
     std::vector<uint16_t> f2((size_t)2 * 256 * 256);
     opd_split_f16_frag(w1, 256, 256, f2.data());
@@ -745,7 +751,7 @@ static void heads_frags(DevMem& dm, HeadParams& p, const float* wc, const float*
 }
 // what both heads hooks fill: the rows, the four layers ([out][in] -> [in][out]), the outputs, the fragment forms
 static void heads_params(DevMem& dm, HeadParams& p, const float* hs, const float* wc, const float* bc, const float* w1, const float* b1,
-                         const float* w2, const float* b2, const float* w3, const float* b3, int rows, int ncls) {
+                         const float* w2, const float* b2, const float* w3, const float* b3, int rows, int ncls, const float* logits, const float* boxes) {
     auto tr = [&](const float* w, int O, int I) -> const float* {
         std::vector<float> t((size_t)O * I);
         for (int o = 0; o < O; ++o)
@@ -757,8 +763,9 @@ static void heads_params(DevMem& dm, HeadParams& p, const float* hs, const float
     p.w1 = tr(w1, 256, 256); p.b1 = dm.up(b1, 256);
     p.w2 = tr(w2, 256, 256); p.b2 = dm.up(b2, 256);
     p.w3 = tr(w3, 4, 256); p.b3 = dm.up(b3, 4);
-    p.logits = dm.alloc<float>((size_t)rows * ncls);
-    p.boxes = dm.alloc<float>((size_t)rows * 4);
+    const size_t all = (size_t)rows + g_test_heads_spare;
+    p.logits = g_test_heads_spare ? dm.up(logits, all * ncls) : dm.alloc<float>(all * ncls);
+    p.boxes = g_test_heads_spare ? dm.up(boxes, all * 4) : dm.alloc<float>(all * 4);
     p.rows = rows; p.ncls = ncls;
     heads_frags(dm, p, wc, w1, w2, ncls);
 }
@@ -766,8 +773,9 @@ static int run_heads(DevMem& dm, const HeadParams& p, float* logits, float* boxe
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     HIPCHK(opd_launch_heads(p, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    RCCHK(down(logits, p.logits, (size_t)p.rows * p.ncls));
-    return down(boxes, p.boxes, (size_t)p.rows * 4);
+    const size_t all = (size_t)p.rows + g_test_heads_spare;
+    RCCHK(down(logits, p.logits, all * p.ncls));
+    return down(boxes, p.boxes, all * 4);
 }
 TAPI int opd_test_heads(const float* hs, const float* ln_g, const float* ln_b, const float* wc, const float* bc, const float* w1, const float* b1,
                         const float* w2, const float* b2, const float* w3, const float* b3, float* logits, float* boxes, int rows, int ncls) {
@@ -775,7 +783,7 @@ TAPI int opd_test_heads(const float* hs, const float* ln_g, const float* ln_b, c
     HeadParams p{};
     p.ln_gamma = ln_g ? dm.up(ln_g, 256) : nullptr;
     p.ln_beta = ln_b ? dm.up(ln_b, 256) : nullptr;
-    heads_params(dm, p, hs, wc, bc, w1, b1, w2, b2, w3, b3, rows, ncls);
+    heads_params(dm, p, hs, wc, bc, w1, b1, w2, b2, w3, b3, rows, ncls, logits, boxes);
     return run_heads(dm, p, logits, boxes);
 }
 // heads_kernel with the fused decoder's prologue: rows = LN3(hs + b2f + sum partials), then the final LayerNorm, then the heads
@@ -787,7 +795,7 @@ TAPI int opd_test_heads_fused(const float* hs, const float* partials, int nsplit
     p.partials = dm.up(partials, (size_t)nsplit * rows * 256); p.nsplit = nsplit; p.ffn_b2 = dm.up(b2f, 256);
     p.ln3_gamma = dm.up(ln3_g, 256); p.ln3_beta = dm.up(ln3_b, 256);
     p.ln_gamma = dm.up(ln_g, 256); p.ln_beta = dm.up(ln_b, 256);
-    heads_params(dm, p, hs, wc, bc, w1, b1, w2, b2, w3, b3, rows, ncls);
+    heads_params(dm, p, hs, wc, bc, w1, b1, w2, b2, w3, b3, rows, ncls, logits, boxes);
     return run_heads(dm, p, logits, boxes);
 }
 

@@ -181,6 +181,42 @@ def test_native_checkpoint_parse_and_schema(tmp_path):
     assert lib.opd_test_inspect_checkpoint(str(tmp_path / "nope.safetensors").encode(), info) == -2
 
 
+ARCH_RANGE = "the detect path serves d_model 256, 1 to 128 queries, 2 to 128 classifier rows"
+
+
+@pytest.mark.parametrize("queries,rows,accepted", [(128, 92, True), (129, 92, False), (1, 2, True), (20, 128, True), (20, 129, False), (20, 256, False),
+                                                   (20, 1, False), (0, 92, False)])
+def test_loader_accepts_exactly_the_architectures_the_kernels_serve(tmp_path, queries, rows, accepted):
+    """infer_arch takes 1 to 128 queries (dec_qkv / dec_self / postprocess_kernel hold 128) and 2 to 128 classifier rows (postprocess_kernel
+    holds two classes per lane and needs a class beside the no-object row; heads_kernel alone would go to 256).  Anything else is
+    OPD_ESCHEMA with a message that names what it found and the range: a checkpoint must not load and then fail inside its first detect."""
+    lib = _capi.load_library()
+    w = dict(synth_weights(DetrArch(depths=(1, 1, 1, 1), encoder_layers=1, decoder_layers=1, num_queries=20), 3, 1.0, calibrate=False))
+    w["model.query_position_embeddings.weight"] = np.zeros((queries, 256), np.float32)
+    w["class_labels_classifier.weight"] = np.zeros((rows, 256), np.float32)
+    w["class_labels_classifier.bias"] = np.zeros((rows,), np.float32)
+    path = str(tmp_path / "arch.safetensors")
+    save_safetensors(w, path)
+    info = (C.c_int32 * 8)()
+    rc = lib.opd_test_inspect_checkpoint(path.encode(), info)
+    if accepted:
+        assert rc == 0, _capi.last_error()
+        assert list(info) == [1, 1, 1, 1, 1, 1, queries, rows]
+    else:
+        assert rc == _capi.OPD_ESCHEMA
+        assert _capi.last_error() == f"unsupported architecture (d_model 256, {queries} queries, {rows} classifier rows): {ARCH_RANGE}"
+
+
+def test_loader_names_the_range_for_another_model_width(tmp_path):
+    lib = _capi.load_library()
+    w = dict(synth_weights(DetrArch(depths=(1, 1, 1, 1), encoder_layers=1, decoder_layers=1, num_queries=20), 3, 1.0, calibrate=False))
+    w["model.query_position_embeddings.weight"] = np.zeros((20, 512), np.float32)
+    path = str(tmp_path / "wide.safetensors")
+    save_safetensors(w, path)
+    assert lib.opd_test_inspect_checkpoint(path.encode(), (C.c_int32 * 8)()) == _capi.OPD_ESCHEMA
+    assert _capi.last_error() == f"unsupported architecture (d_model 512, 20 queries, 92 classifier rows): {ARCH_RANGE}"
+
+
 def test_size_rule_and_resize_match_hf(golden_dir):
     """``model_input_size`` + PIL bilinear ``resize_frame`` + the oracle's normalisation reproduce HF's image processor."""
     g = np.load(os.path.join(golden_dir, "hf_resize.npz"))

@@ -15,6 +15,8 @@ F_ = F  # (some tests use F as a size name)
 
 from office_person_detection_vit_amd import _capi
 
+from arch_common import DET, _p, compare_records, heads_case
+
 pytestmark = pytest.mark.gpu
 
 
@@ -33,18 +35,10 @@ def gemm_variant(request, lib):
     lib.opd_test_set_conv_flags(0)
 
 
-DET = np.dtype([("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("score", "<f4"), ("label", "<i4"), ("query_index", "<i4"),
-                ("frame", "<i4")])   # opd_det (include/opd_detr.h)
-
-
 def _h(a):
     """fp32 array -> (fp16-rounded fp32 array, uint16 bit pattern)."""
     h = np.ascontiguousarray(a, dtype=np.float32).astype(np.float16)
     return h.astype(np.float32), np.ascontiguousarray(h.view(np.uint16))
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def run_conv(lib, x_nhwc, w_oihw, bias, stride, pad, relu, res=None, res32=None, out_f32=False, bias_period=0):
@@ -1004,30 +998,9 @@ def test_heads_kernel_matches_torch(lib, rows, ln, split):
     """class_labels_classifier + DetrMLPPredictionHead + sigmoid (HF:models/detr/modeling_detr.py:1284-1300, 1410-1411), with and
     without the decoder's final LayerNorm inside, against float64 torch.  split = 1: kernels_dec.hip::heads2_kernel (the 256-wide layers
     on split fp16 pairs through the decoder's rings: fp32-grade products); split = 0: kernels_misc.hip::heads_kernel (fp32 matrix pipe)."""
-    lib.opd_test_set_heads2(split)
-    rng = np.random.default_rng(rows)
-    hs = rng.standard_normal((rows, 256)).astype(np.float32) * 1.5
-    g = (1.0 + 0.1 * rng.standard_normal(256)).astype(np.float32)
-    b = (0.1 * rng.standard_normal(256)).astype(np.float32)
-    wc = (rng.standard_normal((92, 256)) / 16 * 2).astype(np.float32); bc = rng.standard_normal(92).astype(np.float32)
-    w1 = (rng.standard_normal((256, 256)) / 11).astype(np.float32); b1 = rng.standard_normal(256).astype(np.float32) * 0.1
-    w2 = (rng.standard_normal((256, 256)) / 11).astype(np.float32); b2 = rng.standard_normal(256).astype(np.float32) * 0.1
-    w3 = (rng.standard_normal((4, 256)) / 8).astype(np.float32); b3 = rng.standard_normal(4).astype(np.float32) * 0.1
-    logits = np.empty((rows, 92), np.float32)
-    boxes = np.empty((rows, 4), np.float32)
-    _capi.check(lib.opd_test_heads(_p(hs), _p(g if ln else None), _p(b if ln else None), _p(wc), _p(bc), _p(w1), _p(b1), _p(w2), _p(b2), _p(w3),
-                                   _p(b3), _p(logits), _p(boxes), rows, 92), "opd_test_heads")
-    t = lambda a: torch.from_numpy(a).double()
-    x = t(hs)
-    if ln:
-        x = F.layer_norm(x, (256,), t(g), t(b), 1e-5)
-    want_logits = x @ t(wc).T + t(bc)
-    y = F.relu(x @ t(w1).T + t(b1))
-    y = F.relu(y @ t(w2).T + t(b2))
-    want_boxes = torch.sigmoid(y @ t(w3).T + t(b3))
-    lib.opd_test_set_heads2(1)
-    np.testing.assert_allclose(logits, want_logits.numpy(), atol=2e-5, rtol=1e-5)
-    np.testing.assert_allclose(boxes, want_boxes.numpy(), atol=2e-6)
+    logits, boxes, want_logits, want_boxes = heads_case(lib, rows, ln, split)
+    np.testing.assert_allclose(logits, want_logits, atol=2e-5, rtol=1e-5)
+    np.testing.assert_allclose(boxes, want_boxes, atol=2e-6)
 
 
 def test_postprocess_kernel_matches_oracle(lib):
@@ -1049,15 +1022,8 @@ def test_postprocess_kernel_matches_oracle(lib):
     thr = 0.3   # (a two-way tie scores just under 0.5)
     _capi.check(lib.opd_test_postprocess(_p(logits), _p(boxes), _p(hw), B, Q, C1, thr, _p(recs), _p(counts)), "opd_test_postprocess")
     want = O.post_process_object_detection(logits, boxes, thr, [tuple(int(v) for v in r) for r in hw])
-    assert counts.tolist() == [len(w["scores"]) for w in want] and counts[1] == 0 and counts[2] == Q
-    for b in range(B):
-        n = counts[b]
-        np.testing.assert_array_equal(recs[b, :n]["query_index"], want[b]["query_index"])
-        np.testing.assert_array_equal(recs[b, :n]["label"], want[b]["labels"])
-        assert (recs[b, :n]["frame"] == b).all()
-        np.testing.assert_allclose(recs[b, :n]["score"], want[b]["scores"], rtol=2e-6, atol=1e-7)
-        got_xyxy = np.stack([recs[b, :n][k] for k in ("x1", "y1", "x2", "y2")], -1) if n else np.zeros((0, 4), np.float32)
-        np.testing.assert_allclose(got_xyxy, want[b]["boxes"], rtol=1e-6, atol=1e-3)
+    assert counts[1] == 0 and counts[2] == Q
+    compare_records(recs, counts, want)
     q10 = np.flatnonzero(recs[3, :counts[3]]["query_index"] == 10)
     assert len(q10) == 1 and recs[3, q10[0]]["label"] == 5
 
