@@ -386,7 +386,7 @@ static void drop_streams(opd_detr* m) {
 }
 
 // The forward-plan switches: defaults, overridden by environment variables (A/B switches for benchmarking and ablations)
-static Switches read_switches(int flags) {
+Switches opd::read_switches(int flags) {
     Switches sw;
     auto env = [](const char* name, int* v) { if (const char* e = getenv(name)) *v = atoi(e); };
     env("OPD_DUAL_OVER_TAIL", &sw.dual_over_tail);

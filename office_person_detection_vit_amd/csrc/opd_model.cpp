@@ -1,4 +1,4 @@
-// opd_model.cpp — workspace, per-resolution plans, per-launch timing, the trunk plan and the forward with its graph cache (the weights under it:
+// opd_model.cpp — workspace, per-resolution plans, per-launch timing, the trunk and transformer plans and the forward with its graph cache (the weights under it:
 // opd_weights.cpp; the C-ABI on top of it: opd_api.cpp).
 //
 // Host-side orchestration of the DETR detect path:
@@ -51,18 +51,23 @@ static int conv_splits(const opd_detr* m, const Conv& c, int stage) {
     return best;
 }
 
+// Frames may come in either orientation (the HF size rule maps a portrait camera frame to about 1333 x 750): the handle
+// accepts every H x W with H, W <= max(max_height, max_width) and H * W <= max_height * max_width, so the buffers are sized by
+// bounds on the pixel COUNT of each pyramid level, not by one shape: down2(n) <= (n + 1) / 2, hence
+// H1 * W1 <= (H * W + H + W + 1) / 4 <= (n + 2 * L + 1) / 4 for a level with n pixels and sides <= L.
+FrameBounds frame_bounds(const opd_config& cfg) {
+    FrameBounds f;
+    f.lvl[0] = (size_t)cfg.max_height * cfg.max_width; f.side[0] = (size_t)std::max(cfg.max_height, cfg.max_width);
+    for (int k = 1; k < 6; ++k) { f.lvl[k] = (f.lvl[k - 1] + 2 * f.side[k - 1] + 1) / 4 + 1; f.side[k] = (size_t)down2((int)f.side[k - 1]); }
+    return f;
+}
+
 int build_workspace(opd_detr* m) {
     const Arch& a = m->arch;
-    // Frames may come in either orientation (the HF size rule maps a portrait camera frame to about 1333 x 750): the handle
-    // accepts every H x W with H, W <= max(max_height, max_width) and H * W <= max_height * max_width, so the buffers are sized by
-    // bounds on the pixel COUNT of each pyramid level, not by one shape: down2(n) <= (n + 1) / 2, hence
-    // H1 * W1 <= (H * W + H + W + 1) / 4 <= (n + 2 * L + 1) / 4 for a level with n pixels and sides <= L.
     const size_t B = m->cfg.max_batch;
-    size_t edge = (size_t)std::max(m->cfg.max_height, m->cfg.max_width);
     const size_t npix = B * (size_t)m->cfg.max_height * m->cfg.max_width;
-    size_t lvl[6], side[6];   // per-frame pixel bound / side bound of: image, stem, pool (= stage 1), stage 2, 3, 4
-    lvl[0] = (size_t)m->cfg.max_height * m->cfg.max_width; side[0] = edge;
-    for (int k = 1; k < 6; ++k) { lvl[k] = (lvl[k - 1] + 2 * side[k - 1] + 1) / 4 + 1; side[k] = (size_t)down2((int)side[k - 1]); }
+    const FrameBounds fb = frame_bounds(m->cfg);
+    const size_t *lvl = fb.lvl, *side = fb.side;
     RCCHK(dalloc(m, &m->d_u8, npix * 3, false));
     RCCHK(dalloc(m, &m->d_pv, npix * 3, false));
     RCCHK(dalloc(m, &m->d_x4, B * (4 * lvl[1] + 24 * side[1] + 36) * 4, false));  // zero-bordered NHWC4: (2 H1 + 6) x (2 W1 + 6)
@@ -447,6 +452,63 @@ TrunkPlan plan_trunk(const Arch& a, const std::vector<Block>& blocks, const opd_
     return plan;
 }
 
+// The transformer plan (opd_model.h).  Every decision about the launch sequence behind the trunk is made here; fwd_encoder, fwd_memory_kv,
+// fwd_decoder_fused / fwd_decoder_chain and fwd_heads walk it and launch.  Which packed weights exist comes from the rules build_weights
+// reads (opd_model.h); what build_weights makes unconditionally (bqkv, bkv_all, dec0_h, qc0) is not tested for.
+TransformerPlan plan_transformer(const Arch& a, const opd_config& cfg, const Switches& sw, size_t stage4_px, int B, int fh, int fw) {
+    TransformerPlan t;
+    const int D = a.d_model, F = a.ffn, Q = a.queries, Kp = a.hidden[3];
+    const size_t M = (size_t)B * fh * fw, NKV = (size_t)a.dec_layers * 2 * D;
+    const bool row256 = D == 256;   // the row-owner kernels' width (kernels_rowln.hip, kernels_dec.hip)
+    // pos_shadow: whoever writes x (input projection, each layer's last LayerNorm) also writes fp16(x + pos); the fused QKV projection
+    // reads that for its q / k column tiles and x for its v tiles, with a plain bias vector -- instead of x everywhere plus a [hw][768]
+    // fp32 table W.pos + b added per output tile (two divisions and 16 dependent table loads per lane in front of the first MFMA:
+    // 14.2 us per launch against 9.4 for the same GEMM with a bias vector; decoder K/V 44.7 against 24-27)
+    t.shadow = sw.pos_shadow && row256;
+    // Small handles (round 5): the row-owner launches of the encoder side own 48 / 64 rows per workgroup and stream a whole weight matrix through
+    // each -- at max_batch = 1 that is 22 workgroups walking 2.2 MB apiece (42 us per layer, 27 us for the input projection).  Where the handle's
+    // CONFIGURATION bounds the token count below ~1400 the same linears run as tiled GEMMs with the reduction split eight ways over workgroups
+    // and the fixed-order reduce + LayerNorm kernel (the round-1 path): encoder stage 0.41 -> 0.32 ms at batch 1.  Never per batch.
+    t.small_enc = sw.small_enc && (size_t)cfg.max_batch * stage4_px <= 1400;
+    t.enc_splits = t.small_enc ? 8 : 4;
+    auto splits_of = [&](int K) { return (K / 64) % t.enc_splits == 0 ? t.enc_splits : 4; };
+    // the deep-K row-owner launch of a K -> 256 linear over the M tokens (32-bit offsets into its input)
+    auto deep = [&](int K) { return sw.deep_fc2 && row256 && !t.small_enc && K % 64 == 0 && M * K * 2 < 0x7fffff00ull; };
+    t.proj_splits = deep(Kp) ? 0 : splits_of(Kp);
+    // the whole FFN block as ONE row-owner launch: the [M][F] hidden tensor never leaves LDS (kernels_rowln.hip::enc_ffn_kernel)
+    const bool ffn_one = sw.fused_enc_ffn && sw.fuse_gemm_ln && enc_has_ffn_pack(a) && !t.small_enc;
+    // fc2 + residual + LayerNorm (+ the position shadow) as ONE row-owner launch of the three-stage ring kernel: 36.9 us in the
+    // forward against 19.4 + 12.2 us for split-K slabs + reduce, but 514 MB less HBM traffic per forward and half the CUs left to
+    // other batches (+1.3 % with three streams, -5 us per layer for a lone stream; profiles/NOTES.md "Deep-K row owners")
+    const int ffn_two = deep(F) ? FFN_FC1_DEEP : FFN_FC1_SPLITK;
+    t.enc.resize(a.enc_layers);
+    bool prev_tail = false;
+    for (int i = 0; i < a.enc_layers; ++i) {
+        EncStep& e = t.enc[i];
+        const bool last = i + 1 == a.enc_layers;
+        e.qkv = prev_tail ? QKV_PREV_TAIL : QKV_LAUNCH;
+        e.oproj = ffn_one && sw.enc_front ? OPROJ_IN_FFN : sw.fuse_gemm_ln && row256 ? OPROJ_GEMM_LN : OPROJ_GEMM_THEN_LN;
+        e.ffn = ffn_one ? FFN_ONE_LAUNCH : ffn_two;
+        e.splits = e.ffn == FFN_FC1_SPLITK ? splits_of(F) : 0;
+        // the tail projection: what consumes this block's output (only on the position-shadow path: x + pos with plain bias vectors; the
+        // memory K/V rows are addressed with 32-bit byte offsets)
+        e.tail = ffn_one && t.shadow && sw.enc_tail && (!last || M * NKV * 2 < (1ull << 32)) ? enc_pack_tail(a, i) : 0;
+        prev_tail = e.tail > 0;
+    }
+    t.kv_launch = !prev_tail;
+    t.dec0 = sw.fuse_dec0 && row256;
+    // the fused decoder is taken when the architecture fits its kernels' fixed shapes
+    t.dec_fused = sw.fused_dec && t.dec0 && a.heads == 8 && Q <= 128 && (Q & 3) == 0 && F % OPD_DEC_FFN_CHUNK == 0 && F / OPD_DEC_FFN_CHUNK <= 16 &&
+                  sw.dec_splits <= 6 && dec_has_frag_weights(a) && M * NKV * 2 < (1ull << 32);
+    t.dec_splits = sw.dec_splits;
+    t.dec_small_m = sw.small_m_gemm && row256 && F % 256 == 0 && F / 256 <= 8;
+    t.dec_oproj = sw.fuse_gemm_ln && row256 ? OPROJ_GEMM_LN : OPROJ_GEMM_THEN_LN;
+    t.heads = sw.heads2 && heads_have_frag_weights(a) ? HEADS_SPLIT16 : HEADS_F32;
+    t.heads_ln3 = t.dec_fused;
+    t.heads_ln = t.dec_fused || sw.fuse_gemm_ln;
+    return t;
+}
+
 // True when some frame of the batch does not fill the H x W canvas (a ragged batch: padding mask path).
 static bool is_ragged(const int32_t* valid_hw, int B, int H, int W) {
     if (!valid_hw) return false;
@@ -636,89 +698,66 @@ static int fwd_trunk(Fwd& c) {
     return OPD_OK;
 }
 
-// ---- input projection -> encoder; *kv_done: the last layer's FFN launch has written the decoder's memory keys / values as its tail
-static int fwd_encoder(Fwd& c, bool* kv_done) {
+// ---- input projection -> encoder, as plan_transformer decided
+static int fwd_encoder(Fwd& c, const TransformerPlan& tp) {
     opd_detr* m = c.m;
     const Arch& a = m->arch;
     const int M = c.M, D = c.D, F = c.F;
-    // pos_shadow: whoever writes x (input projection, each layer's last LayerNorm) also writes fp16(x + pos); the fused QKV projection
-    // reads that for its q / k column tiles and x for its v tiles, with a plain bias vector -- instead of x everywhere plus a [hw][768]
-    // fp32 table W.pos + b added per output tile (two divisions and 16 dependent table loads per lane in front of the first MFMA:
-    // 14.2 us per launch against 9.4 for the same GEMM with a bias vector; decoder K/V 44.7 against 24-27)
-    c.shadow = m->sw.pos_shadow && D == 256 && m->enc[0].bqkv && m->bkv_all;
+    c.shadow = tp.shadow;
     c.psh = PosShadow{c.plan->d_pos, c.pos_ptrs, c.hw, m->d_xp16};
     const PosShadow* ps = c.ps();
-    // Small handles (round 5): the row-owner launches of the encoder side own 48 / 64 rows per workgroup and stream a whole weight matrix through
-    // each -- at max_batch = 1 that is 22 workgroups walking 2.2 MB apiece (42 us per layer, 27 us for the input projection).  Where the handle's
-    // CONFIGURATION bounds the token count below ~1400 the same linears run as tiled GEMMs with the reduction split eight ways over workgroups
-    // and the fixed-order reduce + LayerNorm kernel (the round-1 path): encoder stage 0.41 -> 0.32 ms at batch 1.  Never per batch.
-    const bool small_enc = m->sw.small_enc && (size_t)m->cfg.max_batch * m->stage_px[3] <= 1400;
-    const int enc_splits = small_enc ? 8 : 4;
-    const bool deep_ok = m->sw.deep_fc2 && D == 256 && !small_enc;
-    if (deep_ok && m->proj.K % 64 == 0 && (size_t)M * m->proj.K * 2 < 0x7fffff00ull)
-        RCCHK(run_deep(c, c.feat, m->proj.w, m->proj.bias, m->proj.K, nullptr, nullptr, CLS_CONV));
-    else
-        RCCHK(run_gemm_splitk_ln(c, c.feat, m->proj.w, m->proj.bias, M, D, m->proj.K, (m->proj.K / 64) % enc_splits == 0 ? enc_splits : 4, nullptr, nullptr, m->d_x32, m->d_x16, CLS_CONV, ps));
-    bool qkv_done = false;   // written by the previous layer's FFN launch (its tail projection)
+    if (!tp.proj_splits) RCCHK(run_deep(c, c.feat, m->proj.w, m->proj.bias, m->proj.K, nullptr, nullptr, CLS_CONV));
+    else RCCHK(run_gemm_splitk_ln(c, c.feat, m->proj.w, m->proj.bias, M, D, m->proj.K, tp.proj_splits, nullptr, nullptr, m->d_x32, m->d_x16, CLS_CONV, ps));
     for (int i = 0; i < a.enc_layers; ++i) {
         const EncLayer& L = m->enc[i];
-        if (!qkv_done) RCCHK(run_pos_proj(c, L.wqkv, L.bqkv, c.plan->rb_enc[i], c.enc_bias_ptrs[i], 3 * D, 3 * D, 2 * D, m->d_qkv16));   // (pos enters q and k only)
+        const EncStep& e = tp.enc[i];
+        if (e.qkv == QKV_LAUNCH) RCCHK(run_pos_proj(c, L.wqkv, L.bqkv, c.plan->rb_enc[i], c.enc_bias_ptrs[i], 3 * D, 3 * D, 2 * D, m->d_qkv16));   // (pos enters q and k only)
         RCCHK(run_attn(c, m->d_qkv16, 3 * D, m->d_qkv16 + D, 3 * D, m->d_qkv16 + 2 * D, 3 * D, m->d_attn16, c.hw, c.hw, c.d_keyv, c.fw));
-        const bool ffn_fused = m->sw.fused_enc_ffn && m->sw.fuse_gemm_ln && L.ffn_pack && D == 256 && !small_enc;
-        const bool front = ffn_fused && L.front && m->sw.enc_front;   // the output projection + LayerNorm run inside the FFN launch
-        if (!front && m->sw.fuse_gemm_ln && D == 256) {
+        if (e.oproj == OPROJ_GEMM_LN) {
             RCCHK(run_gemm_ln(c, m->d_attn16, L.o.w, L.o.b, M, D, m->d_x32, L.ln1, m->d_x32, m->d_x16));
-        } else if (!front) {
+        } else if (e.oproj == OPROJ_GEMM_THEN_LN) {
             ConvGemmParams p = gemm_params(m, m->d_attn16, L.o.w, L.o.b, m->d_y32, M, D, D);
             p.out_f32 = 1; p.res32 = m->d_x32;
             RCCHK(run_gemm(c, p));
             RCCHK(c.launch(CLS_OTHER, 0.0, [&] { return opd_launch_layernorm(m->d_y32, L.ln1.g, L.ln1.b, m->d_x32, m->d_x16, M, c.stream, m->dtype); }));
         }
-        qkv_done = false;
-        if (ffn_fused) {
-            // the whole FFN block as ONE row-owner launch: the [M][F] hidden tensor never leaves LDS (kernels_rowln.hip::enc_ffn_kernel)
+        if (e.ffn == FFN_ONE_LAUNCH) {
+            const bool front = e.oproj == OPROJ_IN_FFN, last = i + 1 == a.enc_layers;
             EncFfnParams fp{}; fp.dtype = m->dtype; fp.wprefetch = (m->sw.wprefetch >> 1) & 1;
             fp.x = m->d_x16; fp.wpack = L.ffn_pack; fp.b2 = L.fc2.b; fp.res32 = m->d_x32; fp.gamma = L.ln2.g; fp.beta = L.ln2.b;
-            fp.y32 = m->d_x32; fp.y16 = m->d_x16; fp.M = M; fp.F = F; fp.pack_tail = L.tail; fp.pack_front = L.front;
+            fp.y32 = m->d_x32; fp.y16 = m->d_x16; fp.M = M; fp.F = F; fp.pack_tail = enc_pack_tail(a, i); fp.pack_front = 1;
             if (front) { fp.attn = m->d_attn16; fp.bo = L.o.b; fp.gamma1 = L.ln1.g; fp.beta1 = L.ln1.b; }
             if (ps) { fp.pos = ps->pos; fp.pos_ptrs = ps->pos_ptrs; fp.pos_period = ps->period; fp.yp16 = ps->yp16; }
-            const bool last = i + 1 == a.enc_layers;
-            // the tail projection: what consumes this block's output (only on the position-shadow path: x + pos with plain bias vectors)
-            if (ps && m->sw.enc_tail && L.tail && L.tail_ld == (last ? c.NKV : 3 * D) && (last ? (size_t)M * c.NKV * 2 < (1ull << 32) : true)) {
-                fp.tail = L.tail; fp.tail_pos = L.tail_pos; fp.tail_ld = L.tail_ld;
+            if (e.tail) {   // the next layer's q | k | v, or the decoder's memory K/V
+                fp.tail = e.tail; fp.tail_pos = L.tail_pos; fp.tail_ld = L.tail_ld;
                 fp.tail_out = last ? m->d_memkv16 : m->d_qkv16;
-                for (int t = 0; t < L.tail; ++t) fp.tail_col[t] = L.tail_col[t];
-                (last ? *kv_done : qkv_done) = true;
+                for (int t = 0; t < e.tail; ++t) fp.tail_col[t] = L.tail_col[t];
             }
             RCCHK(c.launch(CLS_GEMM, 4.0 * M * (double)D * F + 2.0 * M * (double)D * 256 * (fp.tail + (front ? 1 : 0)), [&] { return opd_launch_enc_ffn(fp, c.stream); },
                            {{"enc_ffn", m->d_x32, (size_t)M * D * 4}}));
         } else {
             RCCHK(run_linear(c, m->d_x16, L.fc1.w, L.fc1.b, 0, M, F, D, m->d_ffn16, true));
-            // fc2 + residual + LayerNorm (+ the position shadow) as ONE row-owner launch of the three-stage ring kernel: 36.9 us in the
-            // forward against 19.4 + 12.2 us for split-K slabs + reduce, but 514 MB less HBM traffic per forward and half the CUs left to
-            // other batches (+1.3 % with three streams, -5 us per layer for a lone stream; profiles/NOTES.md "Deep-K row owners")
-            if (deep_ok && F % 64 == 0 && (size_t)M * F * 2 < 0x7fffff00ull)
-                RCCHK(run_deep(c, m->d_ffn16, L.fc2.w, L.fc2.b, F, m->d_x32, &L.ln2, CLS_GEMM));
-            else
-                RCCHK(run_gemm_splitk_ln(c, m->d_ffn16, L.fc2.w, L.fc2.b, M, D, F, (F / 64) % enc_splits == 0 ? enc_splits : 4, m->d_x32, &L.ln2, m->d_x32, m->d_x16, CLS_GEMM, ps));
+            if (e.ffn == FFN_FC1_DEEP) RCCHK(run_deep(c, m->d_ffn16, L.fc2.w, L.fc2.b, F, m->d_x32, &L.ln2, CLS_GEMM));
+            else RCCHK(run_gemm_splitk_ln(c, m->d_ffn16, L.fc2.w, L.fc2.b, M, D, F, e.splits, m->d_x32, &L.ln2, m->d_x32, m->d_x16, CLS_GEMM, ps));
         }
     }
     return OPD_OK;
 }
 
-// memory keys / values of all decoder layers in one GEMM (per layer [k | v]: pos enters k only)
-static int fwd_memory_kv(const Fwd& c) {
+// memory keys / values of all decoder layers in one GEMM (per layer [k | v]: pos enters k only), unless the encoder's last launch wrote them
+static int fwd_memory_kv(const Fwd& c, const TransformerPlan& tp) {
+    if (!tp.kv_launch) return OPD_OK;
     return run_pos_proj(c, c.m->wkv_all, c.m->bkv_all, c.plan->rb_kv, c.kv_bias_ptrs, c.NKV, 2 * c.D, c.D, c.m->d_memkv16);
 }
 
 // The fused decoder (kernels_dec.hip): five launches per layer on split fp16 operands; layer 0 starts at its cross-attention (its
 // self-attention block and its queries are constants of the weights).  *final_h: the state the heads read (before the last FFN, whose
 // partial sums travel with it)
-static int fwd_decoder_fused(const Fwd& c, const float** final_h) {
+static int fwd_decoder_fused(const Fwd& c, const TransformerPlan& tp, const float** final_h) {
     opd_detr* m = c.m;
     const Arch& a = m->arch;
     const int B = c.B, D = c.D, F = c.F, Q = c.Q, Md = c.Md;
-    const int S = m->sw.dec_splits, nchunk = F / OPD_DEC_FFN_CHUNK;
+    const int S = tp.dec_splits, nchunk = F / OPD_DEC_FFN_CHUNK;
     float* hbuf[2] = {m->d_h32, m->d_yd32};
     int cur = 0;   // hbuf[cur] holds the layer's state from its self-attention block on
     for (int i = 0; i < a.dec_layers && i < m->sw.dbg_dec_layers; ++i) {
@@ -758,28 +797,27 @@ static int fwd_decoder_fused(const Fwd& c, const float** final_h) {
 }
 
 // The unfused decoder: the round-3 chain of nine launches per layer on single fp16 operands (the cross-check of the fused one); state in d_h32 / d_h16
-static int fwd_decoder_chain(const Fwd& c, bool dec0) {
+static int fwd_decoder_chain(const Fwd& c, const TransformerPlan& tp) {
     opd_detr* m = c.m;
     const Arch& a = m->arch;
     const int D = c.D, F = c.F, Q = c.Q, Md = c.Md;
-    if (dec0) {
+    if (tp.dec0) {
         RCCHK(c.launch(CLS_OTHER, 0.0, [&] { return opd_launch_broadcast_rows(m->dec0_h, m->d_h32, m->d_h16, Md, c.stream, m->dtype); },
                        {{"dec0_broadcast", m->d_h32, (size_t)Md * D * 4}}));
     } else {
         HIPCHK(hipMemsetAsync(m->d_h32, 0, (size_t)Md * D * 4, c.stream));
         HIPCHK(hipMemsetAsync(m->d_h16, 0, (size_t)Md * D * 2, c.stream));
     }
-    const bool small = m->sw.small_m_gemm && D == 256 && F % 256 == 0 && F / 256 <= 8;
     auto linear = [&](const f16_t* x, const f16_t* w, const float* bias, int bias_period, int N, int K, f16_t* out, bool relu) {
-        return small ? run_small_gemm(c, x, w, bias, bias_period, Md, N, K, out, relu) : run_linear(c, x, w, bias, bias_period, Md, N, K, out, relu);
+        return tp.dec_small_m ? run_small_gemm(c, x, w, bias, bias_period, Md, N, K, out, relu) : run_linear(c, x, w, bias, bias_period, Md, N, K, out, relu);
     };
     auto out_proj_ln = [&](const Lin& o, const LNp& ln) {   // attention output projection + residual + LayerNorm on the state
-        return m->sw.fuse_gemm_ln && D == 256 ? run_gemm_ln(c, m->d_attnd16, o.w, o.b, Md, D, m->d_h32, ln, m->d_h32, m->d_h16)
+        return tp.dec_oproj == OPROJ_GEMM_LN ? run_gemm_ln(c, m->d_attnd16, o.w, o.b, Md, D, m->d_h32, ln, m->d_h32, m->d_h16)
                                               : run_gemm_splitk_ln(c, m->d_attnd16, o.w, o.b, Md, D, D, 4, m->d_h32, &ln, m->d_h32, m->d_h16, CLS_GEMM);
     };
     for (int i = 0; i < a.dec_layers && i < m->sw.dbg_dec_layers; ++i) {
         const DecLayer& L = m->dec[i];
-        if (!(dec0 && i == 0)) {   // (layer 0's self-attention block is the broadcast above)
+        if (!(tp.dec0 && i == 0)) {   // (layer 0's self-attention block is the broadcast above)
             RCCHK(linear(m->d_h16, L.wqkv, L.rb_self, Q, 3 * D, D, m->d_qkvd16, false));
             RCCHK(run_attn(c, m->d_qkvd16, 3 * D, m->d_qkvd16 + D, 3 * D, m->d_qkvd16 + 2 * D, 3 * D, m->d_attnd16, Q, Q));
             RCCHK(out_proj_ln(L.so, L.ln1));
@@ -789,31 +827,33 @@ static int fwd_decoder_chain(const Fwd& c, bool dec0) {
         RCCHK(run_attn(c, qd, D, m->d_memkv16 + (size_t)i * 2 * D, c.NKV, m->d_memkv16 + (size_t)i * 2 * D + D, c.NKV, m->d_attnd16, Q, c.hw, c.d_keyv, c.fw));
         RCCHK(out_proj_ln(L.co, L.ln2));
         RCCHK(linear(m->d_h16, L.fc1.w, L.fc1.b, 0, F, D, m->d_ffnd16, true));
-        if (small) RCCHK(run_small_gemm_ln(c, m->d_ffnd16, L.fc2.w, L.fc2.b, Md, F, m->d_h32, L.ln3, m->d_h32, m->d_h16));
+        if (tp.dec_small_m) RCCHK(run_small_gemm_ln(c, m->d_ffnd16, L.fc2.w, L.fc2.b, Md, F, m->d_h32, L.ln3, m->d_h32, m->d_h16));
         else RCCHK(run_gemm_splitk_ln(c, m->d_ffnd16, L.fc2.w, L.fc2.b, Md, D, F, 8, m->d_h32, &L.ln3, m->d_h32, m->d_h16, CLS_GEMM));
     }
     return OPD_OK;
 }
 
-// final LayerNorm + class / box heads.  `fused_h`: the fused decoder's state (null: the chain's d_h32)
-static int fwd_heads(const Fwd& c, const float* fused_h) {
+// final LayerNorm + class / box heads on the decoder's state `h`
+static int fwd_heads(const Fwd& c, const TransformerPlan& tp, const float* h) {
     opd_detr* m = c.m;
     const Arch& a = m->arch;
     HeadParams hp{};
-    if (fused_h) {   // the last layer's FFN sum + LN3 and the final LayerNorm run inside the heads kernel
+    hp.hs = h;
+    if (tp.heads_ln3) {   // the last layer's FFN sum + LN3 run inside the heads kernel
         const DecLayer& P = m->dec[a.dec_layers - 1];
-        hp.hs = fused_h; hp.partials = m->d_ffn_part; hp.nsplit = c.F / OPD_DEC_FFN_CHUNK; hp.ffn_b2 = P.fc2.b; hp.ln3_gamma = P.ln3.g; hp.ln3_beta = P.ln3.b;
+        hp.partials = m->d_ffn_part; hp.nsplit = c.F / OPD_DEC_FFN_CHUNK; hp.ffn_b2 = P.fc2.b; hp.ln3_gamma = P.ln3.g; hp.ln3_beta = P.ln3.b;
+    }
+    if (tp.heads_ln) {   // the final LayerNorm runs inside the heads kernel
         hp.ln_gamma = m->dec_ln.g; hp.ln_beta = m->dec_ln.b;
-    } else if (m->sw.fuse_gemm_ln) {   // the final LayerNorm runs inside the heads kernel
-        hp.hs = m->d_h32; hp.ln_gamma = m->dec_ln.g; hp.ln_beta = m->dec_ln.b;
     } else {
-        RCCHK(c.launch(CLS_OTHER, 0.0, [&] { return opd_launch_layernorm(m->d_h32, m->dec_ln.g, m->dec_ln.b, m->d_hs32, nullptr, c.Md, c.stream, m->dtype); }));
+        RCCHK(c.launch(CLS_OTHER, 0.0, [&] { return opd_launch_layernorm(h, m->dec_ln.g, m->dec_ln.b, m->d_hs32, nullptr, c.Md, c.stream, m->dtype); }));
         hp.hs = m->d_hs32;
     }
     hp.wc = m->wc; hp.bc = m->bc; hp.w1 = m->w1; hp.b1 = m->b1; hp.w2 = m->w2; hp.b2 = m->b2;
     hp.w3 = m->w3; hp.b3 = m->b3; hp.logits = m->d_logits; hp.boxes = m->d_boxes; hp.rows = c.Md; hp.ncls = a.ncls;
-    if (m->sw.heads2 && m->wc_f && m->w1_f && m->w2_f) { hp.wc_f = m->wc_f; hp.w1_f = m->w1_f; hp.w2_f = m->w2_f; }
-    return c.launch(CLS_OTHER, 2.0 * c.Md * 256.0 * (a.ncls + 256 + 256 + 4), [&] { return opd_launch_heads(hp, c.stream); },
+    const bool split16 = tp.heads == HEADS_SPLIT16;
+    if (split16) { hp.wc_f = m->wc_f; hp.w1_f = m->w1_f; hp.w2_f = m->w2_f; }
+    return c.launch(CLS_OTHER, 2.0 * c.Md * 256.0 * (a.ncls + 256 + 256 + 4), [&] { return split16 ? opd_launch_heads2(hp, c.stream) : opd_launch_heads(hp, c.stream); },
                     {{"heads_logits", m->d_logits, (size_t)c.Md * a.ncls * 4}});
 }
 
@@ -835,18 +875,14 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
     RCCHK(fwd_stem(c, d_pixels, pixel_format));
     MARK(1);
     RCCHK(fwd_trunk(c));   // (marks 2 .. 5: one behind each stage)
-    bool kv_done = false;
-    RCCHK(fwd_encoder(c, &kv_done));
+    const TransformerPlan tp = plan_transformer(a, m->cfg, m->sw, m->stage_px[3], B, c.fh, c.fw);
+    RCCHK(fwd_encoder(c, tp));
     MARK(6);
-    if (!kv_done) RCCHK(fwd_memory_kv(c));
-    const bool dec0 = m->sw.fuse_dec0 && m->dec0_h && c.D == 256;
-    // the fused decoder is taken when the architecture fits its kernels' fixed shapes
-    const bool fused_dec = m->sw.fused_dec && dec0 && m->qc0 && a.heads == 8 && c.Q <= 128 && (c.Q & 3) == 0 && c.F % OPD_DEC_FFN_CHUNK == 0 && c.F / OPD_DEC_FFN_CHUNK <= 16 &&
-                           m->sw.dec_splits <= 6 && c.D == 256 && m->dec[0].wqkv_f && (size_t)c.M * c.NKV * 2 < (1ull << 32);
-    const float* fused_h = nullptr;
-    if (fused_dec) RCCHK(fwd_decoder_fused(c, &fused_h));
-    else RCCHK(fwd_decoder_chain(c, dec0));
-    RCCHK(fwd_heads(c, fused_h));
+    RCCHK(fwd_memory_kv(c, tp));
+    const float* h = m->d_h32;   // the state the heads read: the chain's, or what the fused decoder hands back
+    if (tp.dec_fused) RCCHK(fwd_decoder_fused(c, tp, &h));
+    else RCCHK(fwd_decoder_chain(c, tp));
+    RCCHK(fwd_heads(c, tp, h));
     MARK(7);
     m->last_B = B; m->last_H = H; m->last_W = W; m->last_fh = c.fh; m->last_fw = c.fw;
     m->last_ragged = ragged;

@@ -1,7 +1,7 @@
 // opd_model.h — PRIVATE header of libopd_hip: the device model (weights, workspace, per-resolution plans, graph cache) behind the opaque
 // `opd_detr` handle of include/opd_detr.h.  Included by opd_weights.cpp (build_weights), opd_model.cpp (workspace, plans, the forward), opd_api.cpp (the C-ABI and the
 // detect pipeline behind it), opd_comm.cpp, and opd_test_model_api.cpp / opd_test_bench_api.cpp (the test hooks of libopd_hip_test.so that reach into a handle to flip
-// its fusion switches, or plan a trunk); never installed, never seen by a caller.
+// its fusion switches, or plan a trunk or the transformer behind it); never installed, never seen by a caller.
 #pragma once
 #include <math.h>
 #include <stdlib.h>
@@ -45,22 +45,32 @@ struct Block {
     float* bias2sc = nullptr;   // c2.bias + sc.bias (fp32): the fused bottleneck tail adds the shortcut GEMM into the expand's accumulators
     f16_t* w2sc = nullptr;      // [Cout][c2.K + sc.Cin] = [W2 | Wsc] per output channel: the dual-source expand GEMM of stages 3-4
 };
-// Which packed weight forms build_weights creates: one rule each, read by build_weights and by plan_trunk (which must not probe pointers)
+// Which packed weight forms build_weights creates: one rule each, read by build_weights and by the planners (which must not probe pointers)
 inline bool conv_has_kperm(const Conv& c) { return c.KH == 1 && c.KW == 1 && c.Cin % 32 == 0 && c.Cin <= 1024; }   // Conv::wp
 inline bool block_has_bias2sc(const Block& b) { return b.has_sc && b.sc.Cout == b.c2.Cout; }                      // Block::bias2sc
 inline bool block_has_w2sc(const Block& b) {                                                                       // Block::w2sc
     return block_has_bias2sc(b) && b.sc.KH == 1 && b.c2.KH == 1 && b.c2.Cout % 128 == 0 && b.c2.Cin >= 128;
 }
+inline bool enc_has_ffn_pack(const Arch& a) { return a.d_model == 256 && a.ffn % 128 == 0; }                      // EncLayer::ffn_pack
+// Tail passes (256 output columns each) that the pack of encoder layer i carries, *pos of them on x + pos: the next layer's q | k | v, or behind
+// the last layer the decoder's memory k of every layer, then v of every layer, while enc_ffn_kernel takes that many passes
+inline int enc_pack_tail(const Arch& a, int i, int* pos = nullptr) {
+    const bool last = i + 1 == a.enc_layers;
+    const int n = !last ? 3 : 2 * a.dec_layers <= 16 ? 2 * a.dec_layers : 0;
+    if (pos) *pos = !last ? 2 : n / 2;
+    return n;
+}
+inline bool dec_has_frag_weights(const Arch& a) { return a.d_model % 32 == 0 && a.ffn % 32 == 0; }                // DecLayer::*_f
+inline bool heads_have_frag_weights(const Arch& a) { return a.d_model == 256 && a.ncls <= 128; }                  // DetrWeights::wc_f, w1_f, w2_f
 struct EncLayer {
     f16_t* wqkv = nullptr;  // [768][256] = [Wq; Wk; Wv]
     float* bqkv = nullptr;  // [768] = [bq; bk; bv] (pos_shadow path: plain bias vector)
     Lin o, fc1, fc2;
     LNp ln1, ln2;
-    unsigned char* ffn_pack = nullptr;   // fc1 / b1 / fc2 as the eight per-wave streams of enc_ffn_kernel (opd_encffn_pack); null: does not tile
-    // ... followed by the weights of the block's TAIL projection: the next layer's q / k / v (3 passes of 256 columns, the first 2 on x + pos), or,
-    // after the last layer, the decoder's memory keys and values (k of every decoder layer on x + pos, then v of every layer)
-    int tail = 0, tail_pos = 0, tail_ld = 0;
-    int front = 0;                       // the stream leads with the attention output projection (front phase of the launch)
+    // the attention output projection, then fc1 / b1 / fc2, as the eight per-wave streams of enc_ffn_kernel (opd_encffn_pack; enc_has_ffn_pack),
+    // followed by the weights of the block's TAIL projection (enc_pack_tail passes).  Where a pass stores: column tail_col[t] of rows tail_ld wide
+    unsigned char* ffn_pack = nullptr;
+    int tail_pos = 0, tail_ld = 0;
     int tail_col[16] = {};
 };
 struct DecLayer {
@@ -90,7 +100,7 @@ struct Dims {
 inline int down2(int n) { return (n - 1) / 2 + 1; }
 
 // Switches of the forward plan: read from the environment by read_switches at opd_detr_create, copied whole by opd_detr_clone, flipped
-// one by one by the test hooks (opd_test_api.cpp).
+// one by one by the test hooks (opd_test_model_api.cpp).  plan_trunk and plan_transformer turn them into routes.
 struct Switches {
     int small_m_gemm = 1;    // decoder linears (M = B x queries): one-shot K = 256 kernel (0: the general k-loop kernel)
     int fuse_gemm_ln = 1;    // attention output projections: Linear + residual + LayerNorm in one kernel (0: GEMM, then LN)
@@ -123,7 +133,7 @@ struct Switches {
     int small_splitk = 1;    // handles whose deep convolutions would fill a fraction of the CUs (small max_batch x frame): split their reduction over
                              // workgroups, fp32 slabs + reduce_act16_kernel (run_conv; env OPD_SMALL_SPLITK)
     int small_enc = 1;       // handles bounded to <= 1400 tokens: the encoder side's deep linears as split-K GEMMs + reduce / LayerNorm instead of the
-                             // row-owner launches (fwd_encoder; env OPD_SMALL_ENC)
+                             // row-owner launches (plan_transformer; env OPD_SMALL_ENC)
     int fuse_stem_pool = 1;  // stem conv + max-pool in one kernel (0: two kernels, for cross-checking)
     int fuse_prep = 1;       // uint8 frames: pre-processing inside that kernel (0: preprocess_u8_kernel writes the padded NHWC4 image first)
     int pos_shadow = 1;      // q / k projections read a second fp16 shadow "x + position embedding" (written by the producer of x) instead
@@ -154,6 +164,42 @@ struct TrunkPlan {
 // graph capture.  B x H2 x W2: the call's batch and stage-1 input map; `taps`, `profiling`, `has_stream2`: the handle's diagnostic modes and branch stream.
 TrunkPlan plan_trunk(const Arch& a, const std::vector<Block>& blocks, const opd_config& cfg, const Switches& sw, int B, int H2, int W2, int num_cus,
                      bool taps, int profiling, bool has_stream2);
+
+// The transformer plan: which launches run behind the trunk -- input projection, encoder layers, memory K/V, decoder, heads.
+enum EncQkv { QKV_LAUNCH, QKV_PREV_TAIL };   // a layer's q | k | v: its own GEMM / written by the previous layer's FFN launch (its tail passes)
+enum OutProj { OPROJ_IN_FFN, OPROJ_GEMM_LN, OPROJ_GEMM_THEN_LN };   // attention output projection + residual + LayerNorm: the front phase of the encoder's FFN
+                                                                    // launch / one row-owner kernel / a GEMM, then the LayerNorm (decoder chain: split-K slabs, then reduce + LayerNorm)
+enum EncFfn { FFN_ONE_LAUNCH, FFN_FC1_DEEP, FFN_FC1_SPLITK };   // enc_ffn_kernel / fc1 GEMM + deep-K ring launch / fc1 GEMM + split-K slabs + reduce-LayerNorm
+enum HeadsKernel { HEADS_F32, HEADS_SPLIT16 };   // kernels_misc.hip::heads_kernel / kernels_dec.hip::heads2_kernel
+struct EncStep {
+    int qkv, oproj, ffn;
+    int splits;   // FFN_FC1_SPLITK: slices of fc2's reduction
+    int tail;     // FFN_ONE_LAUNCH: tail passes the launch runs (0, or all of enc_pack_tail)
+};
+struct TransformerPlan {
+    bool shadow = false;       // q / k projections read the fp16 shadow x + pos (0: x alone plus the row-periodic table W.pos + b)
+    bool small_enc = false;    // handle bounded to <= 1400 tokens: no row-owner launch on the encoder side
+    int enc_splits = 4;        // slices of the encoder side's split-K linears (where the k-steps divide; else 4)
+    int proj_splits = 0;       // input projection: 0 = the deep-K row-owner launch, else split-K in this many slices
+    std::vector<EncStep> enc;  // one per encoder layer
+    bool kv_launch = true;     // memory K/V of the decoder layers: its own GEMM (false: the last encoder layer's tail passes)
+    bool dec_fused = false;    // kernels_dec.hip, five launches per layer (false: the chain of nine)
+    int dec_splits = 0;        // fused: key ranges of the cross-attention
+    bool dec0 = false;         // chain: layer 0's self-attention block is the broadcast constant dec0_h (false: its launches on the zero state)
+    bool dec_small_m = false;  // chain: linears through the one-shot K = 256 kernel (false: the general k-loop GEMM)
+    int dec_oproj = OPROJ_GEMM_LN;   // chain: OPROJ_GEMM_LN or OPROJ_GEMM_THEN_LN
+    int heads = HEADS_F32;
+    bool heads_ln3 = false;    // the last decoder layer's FFN sum + LN3 run inside the heads kernel (the fused decoder)
+    bool heads_ln = false;     // the decoder's final LayerNorm runs inside the heads kernel (false: its own launch in front)
+};
+// Per-frame pixel bound lvl[k] / side bound side[k] of: image, stem, pool (= stage 1), stage 2, 3, 4 -- over every H x W the handle accepts
+// (H, W <= max(max_height, max_width), H * W <= max_height * max_width).  opd_detr::stage_px[s] = lvl[2 + s].
+struct FrameBounds { size_t lvl[6], side[6]; };
+FrameBounds frame_bounds(const opd_config& cfg);
+// Pure over the architecture, configuration and switches, `stage4_px` (opd_detr::stage_px[3]) and the call's batch and feature map: reads no
+// device pointer.  Called by enqueue_forward, i.e. per eager forward and per graph capture.
+TransformerPlan plan_transformer(const Arch& a, const opd_config& cfg, const Switches& sw, size_t stage4_px, int B, int fh, int fw);
+Switches read_switches(int flags);   // opd_api.cpp: the defaults overridden by the environment, as opd_detr_create reads them
 
 }  // namespace opd
 

@@ -733,15 +733,15 @@ TAPI int opd_test_set_heads2(int on) { g_test_heads2 = on; return OPD_OK; }
 // rows) and come back whole, so that a store past the last row shows
 static int g_test_heads_spare = 0;
 TAPI int opd_test_set_heads_spare_rows(int rows) { g_test_heads_spare = rows > 0 ? rows : 0; return OPD_OK; }
-// (the three 256-wide layers as split fp16 pairs in fragment order, class matrix padded to 128 rows; above 128 classes to 256 rows, which
-// heads2_kernel cannot take: opd_launch_heads has to pick heads_kernel by ncls then, as it does in the model)
+// which kernel the heads hooks run: heads2_kernel where it is selected and holds the class matrix (128 rows), else heads_kernel
+static bool heads_split16(int ncls) { return g_test_heads2 && ncls <= 128; }
+// (the three 256-wide layers as split fp16 pairs in fragment order, class matrix padded to 128 rows)
 static void heads_frags(DevMem& dm, HeadParams& p, const float* wc, const float* w1, const float* w2, int ncls) {
-    if (!g_test_heads2 || ncls > 256) return;
-    const int pad = ncls <= 128 ? 128 : 256;
-    std::vector<float> wcp((size_t)pad * 256, 0.f);
+    if (!heads_split16(ncls)) return;
+    std::vector<float> wcp((size_t)128 * 256, 0.f);
     std::copy(wc, wc + (size_t)ncls * 256, wcp.begin());
-    std::vector<uint16_t> f((size_t)2 * pad * 256);
-    opd_split_f16_frag(wcp.data(), pad, 256, f.data());
+    std::vector<uint16_t> f((size_t)2 * 128 * 256);
+    opd_split_f16_frag(wcp.data(), 128, 256, f.data());
     p.wc_f = dm.up(f.data(), f.size());
     std::vector<uint16_t> f2((size_t)2 * 256 * 256);
     opd_split_f16_frag(w1, 256, 256, f2.data());
@@ -771,7 +771,7 @@ static void heads_params(DevMem& dm, HeadParams& p, const float* hs, const float
 }
 static int run_heads(DevMem& dm, const HeadParams& p, float* logits, float* boxes) {
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_heads(p, nullptr));
+    HIPCHK(heads_split16(p.ncls) ? opd_launch_heads2(p, nullptr) : opd_launch_heads(p, nullptr));
     HIPCHK(hipDeviceSynchronize());
     const size_t all = (size_t)p.rows + g_test_heads_spare;
     RCCHK(down(logits, p.logits, all * p.ncls));

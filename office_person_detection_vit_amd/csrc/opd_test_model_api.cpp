@@ -94,6 +94,36 @@ TAPI int opd_test_trunk_plan(const int* depths, int max_batch, int flags, int B,
     *split_out = plan.split;
     return (int)blocks.size();
 }
+// plan_transformer (opd_model.cpp) for arch7 = d_model, heads, ffn, encoder layers, decoder layers, queries, classifier rows in a handle of
+// max_batch frames of at most max_height x max_width with `flags`, for a call of B frames of H x W; the switches as opd_detr_create reads
+// them (defaults overridden by the environment), the stage-4 pixel bound as build_workspace computes it.
+//   head_out[14] = shadow, small_enc, enc_splits, proj_splits (0: deep row-owner), kv_launch, dec_fused, dec_splits, dec0, dec_small_m,
+//                  dec_oproj, heads (HeadsKernel), heads_ln3, heads_ln, the handle's token bound max_batch x stage_px[3]
+//   enc_out[layer][5] = qkv (EncQkv), oproj (OutProj), ffn (EncFfn), splits, tail
+// Returns the number of encoder layers.
+TAPI int opd_test_transformer_plan(const int* arch7, int max_batch, int max_height, int max_width, int flags, int B, int H, int W, int* head_out, int* enc_out,
+                                   int max_layers) {
+    if (!arch7 || !head_out || !enc_out || max_batch < 1 || max_height < 32 || max_width < 32 || B < 1 || H < 1 || W < 1)
+        return fail(OPD_EINVAL, "bad transformer_plan arguments");
+    Arch a;
+    a.d_model = arch7[0]; a.heads = arch7[1]; a.ffn = arch7[2]; a.enc_layers = arch7[3]; a.dec_layers = arch7[4]; a.queries = arch7[5]; a.ncls = arch7[6];
+    if (a.enc_layers < 1 || a.dec_layers < 1 || a.enc_layers > max_layers) return fail(OPD_EINVAL, "transformer_plan: layer counts");
+    opd_config cfg{};
+    cfg.struct_size = sizeof(opd_config); cfg.max_batch = max_batch; cfg.max_height = max_height; cfg.max_width = max_width; cfg.flags = flags;
+    const size_t px = frame_bounds(cfg).lvl[5];
+    int fh = H, fw = W;
+    for (int k = 0; k < 5; ++k) { fh = down2(fh); fw = down2(fw); }   // stem, pool, stages 2-4
+    const TransformerPlan t = plan_transformer(a, cfg, read_switches(flags), px, B, fh, fw);
+    const int head[14] = {t.shadow, t.small_enc, t.enc_splits, t.proj_splits, t.kv_launch, t.dec_fused, t.dec_splits, t.dec0, t.dec_small_m,
+                          t.dec_oproj, t.heads, t.heads_ln3, t.heads_ln, (int)((size_t)max_batch * px)};
+    memcpy(head_out, head, sizeof(head));
+    for (size_t i = 0; i < t.enc.size(); ++i) {
+        const EncStep& e = t.enc[i];
+        const int row[5] = {e.qkv, e.oproj, e.ffn, e.splits, e.tail};
+        memcpy(enc_out + 5 * i, row, sizeof(row));
+    }
+    return (int)t.enc.size();
+}
 
 // ---- hooks that reach into a model handle: every switch that changes the launch sequence drops the captured graphs, which hold the old one ----
 TAPI int opd_test_set_fuse_gemm_ln(opd_detr* m, int on) {

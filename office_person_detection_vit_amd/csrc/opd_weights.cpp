@@ -184,18 +184,19 @@ static int build_encoder(opd_detr* m, const StateDict& sd) {
 // The encoder FFN blocks as single launches, each with the projection that consumes its output.  `kv_full`: build_decoder's [k_l | v_l] rows.
 static int build_encoder_ffn_packs(opd_detr* m, const StateDict& sd, const std::vector<float>& kv_full) {
     const Arch& a = m->arch;
-    if (a.d_model != 256 || a.ffn % 128 != 0) return OPD_OK;
+    if (!enc_has_ffn_pack(a)) return OPD_OK;
     const int D = 256, L = a.dec_layers;
     for (int i = 0; i < a.enc_layers; ++i) {
         EncLayer& E = m->enc[i];
         const std::string p = "model.encoder.layers." + std::to_string(i);
         std::vector<float> wt, bt;
+        const int tail = enc_pack_tail(a, i, &E.tail_pos);
+        E.tail_ld = tail * D;
         if (i + 1 < a.enc_layers) {   // the next layer's q, k (on x + pos), v
             const std::string n = "model.encoder.layers." + std::to_string(i + 1) + ".self_attn.";
             for (const char* pr : {"q_proj", "k_proj", "v_proj"}) { append(wt, T(sd, n + pr + ".weight").data); append(bt, T(sd, n + pr + ".bias").data); }
-            E.tail = 3; E.tail_pos = 2; E.tail_ld = 3 * D;
             for (int t = 0; t < 3; ++t) E.tail_col[t] = t * D;
-        } else if (2 * L <= 16 && kv_full.size() == (size_t)L * 2 * D * D && m->h_kv_cat_b.size() == (size_t)L * 2 * D) {
+        } else if (tail) {
             // the decoder's memory projections, [k_l | v_l] per layer in wkv_all: passes k_0 .. k_{L-1} (on x + pos), then v_0 .. v_{L-1}
             for (int kv = 0; kv < 2; ++kv)
                 for (int l = 0; l < L; ++l) {
@@ -203,11 +204,9 @@ static int build_encoder_ffn_packs(opd_detr* m, const StateDict& sd, const std::
                     bt.insert(bt.end(), m->h_kv_cat_b.begin() + (size_t)(2 * l + kv) * D, m->h_kv_cat_b.begin() + (size_t)(2 * l + kv + 1) * D);
                     E.tail_col[kv * L + l] = (2 * l + kv) * D;
                 }
-            E.tail = 2 * L; E.tail_pos = L; E.tail_ld = 2 * L * D;
         }
-        RCCHK(upload_encffn(m, &E.ffn_pack, T(sd, p + ".mlp.fc1.weight").data, T(sd, p + ".mlp.fc1.bias").data, T(sd, p + ".mlp.fc2.weight").data, a.ffn, wt, bt, E.tail,
+        RCCHK(upload_encffn(m, &E.ffn_pack, T(sd, p + ".mlp.fc1.weight").data, T(sd, p + ".mlp.fc1.bias").data, T(sd, p + ".mlp.fc2.weight").data, a.ffn, wt, bt, tail,
                             T(sd, p + ".self_attn.o_proj.weight").data));
-        E.front = 1;
     }
     return OPD_OK;
 }
@@ -286,7 +285,7 @@ static int build_decoder(opd_detr* m, const StateDict& sd, std::vector<float>* k
         RCCHK(make_lin(m, sd, p + ".mlp.fc2", &L.fc2));
         RCCHK(make_ln(m, sd, p + ".final_layer_norm", &L.ln3));
         // split pairs for the fused decoder
-        if (D % 32 == 0 && a.ffn % 32 == 0) {
+        if (dec_has_frag_weights(a)) {
             RCCHK(upload_frag(m, &L.wqkv_f, wfull, 3 * D, D));
             RCCHK(upload_frag(m, &L.so_f, T(sd, p + ".self_attn.o_proj.weight").data, D, D));
             RCCHK(upload_frag(m, &L.wqc_f, T(sd, p + ".encoder_attn.q_proj.weight").data, D, D));
@@ -313,7 +312,7 @@ static int build_heads(opd_detr* m, const StateDict& sd) {
     RCCHK(make_ln(m, sd, "model.decoder.layernorm", &m->dec_ln));
     RCCHK(upload_f32(m, &m->wc, transposed("class_labels_classifier.weight")));
     RCCHK(upload_f32(m, &m->bc, T(sd, "class_labels_classifier.bias").data));
-    if (a.d_model == 256 && a.ncls <= 128) {   // the heads on split fp16 operands (kernels_dec.hip::heads2_kernel): class matrix padded to 128 rows
+    if (heads_have_frag_weights(a)) {   // the heads on split fp16 operands (kernels_dec.hip::heads2_kernel): class matrix padded to 128 rows
         std::vector<float> wcp((size_t)128 * 256, 0.f);
         const auto& wcs = T(sd, "class_labels_classifier.weight").data;
         std::copy(wcs.begin(), wcs.end(), wcp.begin());

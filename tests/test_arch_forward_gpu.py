@@ -21,6 +21,7 @@ from office_person_detection_vit_amd.weights import DetrArch, ensure_weight_file
 from oracle import detr_oracle as O
 
 from arch_common import DET, compare_records
+from plan_common import FFN_ONE_LAUNCH, HEADS_SPLIT16, QKV_LAUNCH, transformer_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -188,6 +189,27 @@ def test_memory_kv_leaves_the_encoder_launch_above_eight_decoder_layers(ctx):
     # 2 encoder + 2 decoder layers: the tails save the second layer's q | k | v launch and the memory K/V launch
     diff = _launch_difference(outside["max_q_cls"], outside["max_q_cls" + TAIL])
     assert list(diff.values()) == [-2] and next(iter(diff)).startswith("conv_gemm"), diff
+
+
+def test_transformer_plan_agrees_with_the_kernel_table(ctx):
+    """plan_transformer, asked through its CPU hook for each handle's architecture, bounds and environment, names the launches that handle's
+    profiled forward ran: the one-launch encoder FFNs, the fused decoder's kernels (none for the chain), the heads kernel, and -- as the
+    count of implicit-GEMM launches beyond the trunk's, which every handle here shares -- each layer's own q | k | v projection and the
+    memory K/V projection."""
+    beyond_plan = {}
+    for key in list(ARCHS) + TAIL_KEYS:
+        e, d, q, l = ARCHS[key.replace(TAIL, "")]
+        head, enc = transformer_plan((e, d, q, l + 1), (480, 640, 8), 2, H, W, {"OPD_ENC_TAIL": "1"} if key.endswith(TAIL) else None)
+        table = ctx(key).kernel_table()
+        count = lambda prefix: sum(v for k, v in table.items() if k.startswith(prefix))
+        assert count("enc_ffn_kernel") == sum(step[2] == FFN_ONE_LAUNCH for step in enc), (key, table)
+        fused = {"dec_qkv_kernel": d - 1, "dec_self_kernel": d - 1, "dec_cross_out_kernel": d, "dec_ffn_kernel": d}
+        assert {k: count(k) for k in fused} == (fused if head["dec_fused"] else dict.fromkeys(fused, 0)), (key, table)
+        assert not {k for k in table if re.match(r"dec_\w+_kernel", k) and not k.startswith(tuple(fused))}, (key, table)
+        assert (count("heads2_kernel"), count("heads_kernel")) == ((1, 0) if head["heads"] == HEADS_SPLIT16 else (0, 1)), (key, table)
+        assert head["dec_fused"] or head["dec_small_m"]   # (the chain's linears here are gemm_k256 launches: none of them counts below)
+        beyond_plan[key] = count("conv_gemm") - sum(step[0] == QKV_LAUNCH for step in enc) - head["kv_launch"]
+    assert len(set(beyond_plan.values())) == 1, beyond_plan
 
 
 @pytest.mark.parametrize("key", list(ARCHS))

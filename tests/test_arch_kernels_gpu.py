@@ -113,7 +113,7 @@ def test_heads_kernel_above_128_classes(lib, ncls, rows):
 
 
 def test_heads_dispatch_leaves_heads2_above_128_classes(lib):
-    """With the split operands present and 129 classes opd_launch_heads must take heads_kernel (heads2_kernel pads the class matrix to 128
+    """With heads2_kernel selected and 129 classes the heads hook must take heads_kernel (heads2_kernel pads the class matrix to 128
     rows): both settings of the hook then run the same kernel on the same inputs and agree bit for bit; at 128 classes they are two
     kernels with different summation orders, which is what makes the equality at 129 say something."""
     a = heads_case(lib, 37, True, 1, ncls=129, spare=SPARE)

@@ -16,7 +16,10 @@ from office_person_detection_vit_amd.weights import (DetrArch, param_specs, rena
                                                      synth_weights)
 from oracle import detr_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from plan_common import (FFN_FC1_DEEP, FFN_FC1_SPLITK, FFN_ONE_LAUNCH, HEADS_F32, HEADS_SPLIT16, OPROJ_GEMM_LN, OPROJ_IN_FFN, QKV_LAUNCH,
+                         QKV_PREV_TAIL, R50, transformer_plan)
+
+ROOT =os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol():
@@ -402,6 +405,118 @@ def test_trunk_plan_r50_batch8_matches_the_hand_derived_plan():
     ]
     assert steps == want
     assert split == 7
+
+
+# ---- plan_transformer (csrc/opd_model.cpp): the launch sequence behind the trunk, pinned as the forward decided it inline before the planner ----
+R50_HANDLE, MID_HANDLE, SMALL_HANDLE = (800, 1333, 8), (480, 640, 8), (256, 320, 1)
+ARCH_PLANS = {"one_layer": (1, 1, 100, 92), "max_q_cls": (2, 2, 128, 128), "min_q_cls": (1, 2, 4, 3), "chain_q50": (1, 2, 50, 92),
+              "tail16": (1, 8, 20, 92), "kv_launch": (1, 9, 20, 92)}   # tests/test_arch_forward_gpu.py::ARCHS (classifier rows = labels + 1)
+ONE_LAUNCH_LAYER = (QKV_LAUNCH, OPROJ_IN_FFN, FFN_ONE_LAUNCH, 0, 0)
+TAIL_ON = {"OPD_ENC_TAIL": "1"}
+
+
+def _r50_plan(env=None):
+    return transformer_plan(R50, R50_HANDLE, 8, 800, 1333, env)
+
+
+def test_transformer_plan_r50_benchmark_shape_default_switches():
+    head, enc = _r50_plan()
+    assert head["shadow"] == 1 and head["small_enc"] == 0 and head["enc_splits"] == 4
+    assert head["proj_splits"] == 0                                  # the deep row-owner launch
+    assert enc == [ONE_LAUNCH_LAYER] * 6                             # own q|k|v, output projection inside the one FFN launch, no tail
+    assert head["kv_launch"] == 1
+    assert head["dec_fused"] == 1 and head["dec_splits"] == 3
+    assert (head["heads"], head["heads_ln3"], head["heads_ln"]) == (HEADS_SPLIT16, 1, 1)
+
+
+def test_transformer_plan_r50_with_encoder_tails():
+    head, enc = _r50_plan(TAIL_ON)
+    assert [e[4] for e in enc] == [3, 3, 3, 3, 3, 12]                # q | k | v of the next layer; k and v of the six decoder layers
+    assert [e[0] for e in enc] == [QKV_LAUNCH] + [QKV_PREV_TAIL] * 5
+    assert all(e[1:4] == ONE_LAUNCH_LAYER[1:4] for e in enc)
+    assert head["kv_launch"] == 0
+    default = _r50_plan()[0]
+    assert {k: v for k, v in head.items() if k != "kv_launch"} == {k: v for k, v in default.items() if k != "kv_launch"}
+
+
+def test_transformer_plan_small_handle_splits_the_deep_linears():
+    """256 x 320 x 1 bounds a frame to 101 tokens (<= 1400): split-K in eight instead of the row-owner launches.  480 x 640 x 8 (340 x 8) is not small."""
+    head, enc = transformer_plan(R50, SMALL_HANDLE, 1, 256, 320)
+    assert head["token_bound"] == 101 and head["small_enc"] == 1 and head["enc_splits"] == 8
+    assert head["proj_splits"] == 8
+    assert enc == [(QKV_LAUNCH, OPROJ_GEMM_LN, FFN_FC1_SPLITK, 8, 0)] * 6
+    assert head["kv_launch"] == 1 and head["dec_fused"] == 1 and head["heads"] == HEADS_SPLIT16
+    assert transformer_plan(R50, SMALL_HANDLE, 1, 256, 320, TAIL_ON) == (head, enc)   # no FFN launch to carry a tail
+    head, enc = transformer_plan(R50, MID_HANDLE, 2, 256, 320)
+    assert head["token_bound"] == 2720 and head["small_enc"] == 0 and head["proj_splits"] == 0 and enc == [ONE_LAUNCH_LAYER] * 6
+
+
+@pytest.mark.parametrize("tails", [False, True], ids=["default", "enc_tail"])
+@pytest.mark.parametrize("key", list(ARCH_PLANS))
+def test_transformer_plan_of_each_accepted_architecture(key, tails):
+    arch = ARCH_PLANS[key]
+    e_layers, d_layers = arch[:2]
+    head, enc = transformer_plan(arch, MID_HANDLE, 2, 256, 320, TAIL_ON if tails else None)
+    assert len(enc) == e_layers and head["small_enc"] == 0 and head["proj_splits"] == 0
+    assert all(e[1:4] == ONE_LAUNCH_LAYER[1:4] for e in enc)
+    if key == "chain_q50":                                           # Q & 3 != 0
+        assert (head["dec_fused"], head["dec0"], head["dec_small_m"], head["dec_oproj"]) == (0, 1, 1, OPROJ_GEMM_LN)
+        assert (head["heads_ln3"], head["heads_ln"]) == (0, 1)
+    else:
+        assert head["dec_fused"] == 1 and (head["heads_ln3"], head["heads_ln"]) == (1, 1)
+    assert head["heads"] == HEADS_SPLIT16                            # (max_q_cls: 128 rows, the most heads2_kernel holds)
+    if not tails:
+        assert [e[4] for e in enc] == [0] * e_layers and [e[0] for e in enc] == [QKV_LAUNCH] * e_layers and head["kv_launch"] == 1
+        return
+    last_tail = 2 * d_layers if 2 * d_layers <= 16 else 0
+    assert [e[4] for e in enc] == [3] * (e_layers - 1) + [last_tail]
+    assert [e[0] for e in enc] == [QKV_LAUNCH] + [QKV_PREV_TAIL] * (e_layers - 1)
+    assert head["kv_launch"] == (0 if last_tail else 1)
+    if key == "one_layer":
+        assert enc == [(QKV_LAUNCH, OPROJ_IN_FFN, FFN_ONE_LAUNCH, 0, 2)]   # first layer = last layer: memory K/V of the one decoder layer
+    if key == "tail16":
+        assert enc[-1][4] == 16 and head["kv_launch"] == 0
+    if key == "kv_launch":
+        assert enc[-1][4] == 0 and head["kv_launch"] == 1
+
+
+@pytest.mark.parametrize("env,oproj,ffn,proj_splits,dec_fused,heads", [
+    ({"OPD_FUSED_ENC_FFN": "0"}, OPROJ_GEMM_LN, FFN_FC1_DEEP, 0, 1, HEADS_SPLIT16),
+    ({"OPD_ENC_FRONT": "0"}, OPROJ_GEMM_LN, FFN_ONE_LAUNCH, 0, 1, HEADS_SPLIT16),
+    ({"OPD_DEEP_FC2": "0"}, OPROJ_IN_FFN, FFN_ONE_LAUNCH, 4, 1, HEADS_SPLIT16),
+    ({"OPD_FUSED_DEC": "0"}, OPROJ_IN_FFN, FFN_ONE_LAUNCH, 0, 0, HEADS_SPLIT16),
+    ({"OPD_HEADS2": "0"}, OPROJ_IN_FFN, FFN_ONE_LAUNCH, 0, 1, HEADS_F32)], ids=lambda v: next(iter(v)) if isinstance(v, dict) else None)
+def test_transformer_plan_one_switch_at_a_time(env, oproj, ffn, proj_splits, dec_fused, heads):
+    head, enc = _r50_plan(env)
+    assert enc == [(QKV_LAUNCH, oproj, ffn, 0, 0)] * 6
+    assert (head["proj_splits"], head["dec_fused"], head["heads"]) == (proj_splits, dec_fused, heads)
+    assert head["kv_launch"] == 1 and head["shadow"] == 1 and head["small_enc"] == 0
+    if not dec_fused:                                                # the chain: layer 0 from the constant, small-M kernels, GEMM+LN; LN3 ran in the chain
+        assert (head["dec0"], head["dec_small_m"], head["dec_oproj"], head["heads_ln3"], head["heads_ln"]) == (1, 1, OPROJ_GEMM_LN, 0, 1)
+
+
+def test_transformer_plan_invariants():
+    """Over the six architectures and r50 / r101 (one transformer: 6 + 6 layers, 100 queries, 92 rows), two handle sizes, tails off and on."""
+    for arch in list(ARCH_PLANS.values()) + [R50]:
+        for bounds in (MID_HANDLE, SMALL_HANDLE):
+            for env in (None, TAIL_ON):
+                where = (arch, bounds, env)
+                head, enc = transformer_plan(arch, bounds, 1, 256, 320, env)
+                for B in range(2, bounds[2] + 1):                    # a frame's bits must not depend on the batch it travels in
+                    assert transformer_plan(arch, bounds, B, 256, 320, env) == (head, enc), where + (B,)
+                assert enc[0][0] == QKV_LAUNCH, where
+                for prev, e in zip(enc, enc[1:]):
+                    assert (e[0] == QKV_PREV_TAIL) == (prev[4] > 0), where
+                assert head["kv_launch"] == (enc[-1][4] == 0), where
+                for qkv, oproj, ffn, splits, tail in enc:
+                    assert oproj != OPROJ_IN_FFN or ffn == FFN_ONE_LAUNCH, where
+                    assert tail == 0 or ffn == FFN_ONE_LAUNCH, where
+                    assert (splits > 0) == (ffn == FFN_FC1_SPLITK), where
+                    if head["small_enc"]:                            # no row-owner route for the deep linears
+                        assert ffn == FFN_FC1_SPLITK and oproj != OPROJ_IN_FFN and tail == 0, where
+                assert head["small_enc"] == (bounds == SMALL_HANDLE), where
+                if head["small_enc"]:
+                    assert head["proj_splits"] == 8, where
 
 
 def test_masked_sine_position_embedding_matches_oracle():

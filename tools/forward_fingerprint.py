@@ -9,7 +9,9 @@ Per configuration (handle bounds, test hooks, environment switches, pixel format
   out       SHA-256 of logits, boxes and encoder_last_hidden_state with taps off, eager and replay
   kernels   profiling mode 1 on a detect call: the kernel table's (name, launches, flops) rows, kernel_times' launch and FLOP totals
 and the benchmark shape (800 x 1333 x 8, the only one with the stage-3 frame split) its output hashes and which of the eight stage_times
-entries are non-zero under profiling mode 2.  Only the seeded weights of weights.ensure_weight_file are used.
+entries are non-zero under profiling mode 2.  Only the seeded weights of weights.ensure_weight_file are used: the r50 architecture, and for
+two routes it never takes -- the chain decoder (50 queries), the memory K/V launch behind an encoder with tails (9 decoder layers) -- the
+one-block-per-stage architectures of tests/test_arch_forward_gpu.py.
 """
 import ctypes as C
 import hashlib
@@ -28,7 +30,9 @@ from office_person_detection_vit_amd.frames import structured_frames  # noqa: E4
 from office_person_detection_vit_amd.weights import DetrArch, ensure_weight_file  # noqa: E402
 
 lib = _capi.load_library(test_hooks=True)
-MILD = ensure_weight_file(os.path.join(tempfile.gettempdir(), "opd_weights"), DetrArch.resnet50(), 0, 1.0, "r50")
+CACHE = os.path.join(tempfile.gettempdir(), "opd_weights")
+MILD = ensure_weight_file(CACHE, DetrArch.resnet50(), 0, 1.0, "r50")
+ARCHS = {"chain_q50": (1, 2, 50, 91), "kv_launch": (1, 9, 20, 91)}   # encoder layers, decoder layers, queries, labels
 RAGGED_SIZES = ((256, 320), (224, 288))   # the two sizes of tests/golden/r50_mild_ragged.npz
 VP = C.c_void_p
 
@@ -38,26 +42,33 @@ def sha(*arrays):
 
 
 class Handle:
-    def __init__(self, bounds, flags=0, env=None):
+    def __init__(self, bounds, flags=0, env=None, arch=None):
         env = env or {}
+        path = MILD
+        if arch:
+            e, d, q, l = ARCHS[arch]
+            path = ensure_weight_file(CACHE, DetrArch(depths=(1, 1, 1, 1), encoder_layers=e, decoder_layers=d, num_queries=q, num_labels=l), 0, 1.0, "arch_" + arch)
         os.environ.update(env)
         try:
             cfg = _capi.OpdConfig(struct_size=C.sizeof(_capi.OpdConfig), max_batch=bounds[2], max_height=bounds[0], max_width=bounds[1], flags=flags)
             self.h = VP()
-            _capi.check(lib.opd_detr_create(C.byref(cfg), MILD.encode(), 0, C.byref(self.h)), "opd_detr_create")
+            _capi.check(lib.opd_detr_create(C.byref(cfg), path.encode(), 0, C.byref(self.h)), "opd_detr_create")
         finally:
             for k in env:
                 del os.environ[k]
+        info = _capi.OpdModelInfo()
+        _capi.check(lib.opd_detr_info(self.h, C.byref(info)), "opd_detr_info")
+        self.Q, self.rows, self.D = info.num_queries, info.num_classes_plus1, info.d_model
 
     def forward(self, pixels, fmt, B, H, W, valid=None):
-        out = [np.zeros((B, 100, 92), np.float32), np.zeros((B, 100, 4), np.float32), np.zeros((B, _feature_hw(H) * _feature_hw(W), 256), np.float32)]
+        out = [np.zeros((B, self.Q, self.rows), np.float32), np.zeros((B, self.Q, 4), np.float32), np.zeros((B, _feature_hw(H) * _feature_hw(W), self.D), np.float32)]
         _capi.check(lib.opd_detr_forward_ragged(self.h, pixels.ctypes.data_as(VP), fmt, _capi.OPD_MEM_HOST, B, H, W,
                                                 valid.ctypes.data_as(VP) if valid is not None else None, *[o.ctypes.data_as(VP) for o in out]), "forward")
         return sha(*out)
 
     def detect(self, pixels, fmt, B, H, W):
         hw = np.asarray([[H, W]] * B, np.int32)
-        recs, cnts = np.zeros((B, 100, 8), np.int32), np.zeros(B, np.int32)
+        recs, cnts = np.zeros((B, self.Q, 8), np.int32), np.zeros(B, np.int32)
         _capi.check(lib.opd_detr_detect(self.h, pixels.ctypes.data_as(VP), fmt, _capi.OPD_MEM_HOST, B, H, W, 0.5, hw.ctypes.data_as(VP),
                                         recs.ctypes.data_as(C.POINTER(_capi.OpdDet)), cnts.ctypes.data_as(C.POINTER(C.c_int32))), "opd_detr_detect")
 
@@ -78,8 +89,8 @@ class Handle:
         lib.opd_detr_destroy(self.h)
 
 
-def fingerprint(bounds=(800, 1333, 2), flags=0, env=None, hook=None, f32=False, ragged=False, frames_n=2):
-    h = Handle(bounds, flags, env)
+def fingerprint(bounds=(800, 1333, 2), flags=0, env=None, hook=None, f32=False, ragged=False, frames_n=2, arch=None):
+    h = Handle(bounds, flags, env, arch)
     try:
         if hook:
             _capi.check(getattr(lib, hook[0])(h.h, hook[1]), hook[0])
@@ -142,6 +153,8 @@ def main(out_path):
     configs["f32_pixels"] = {"f32": True}
     configs["ragged"] = {"ragged": True}
     configs["no_graph"] = {"flags": _capi.OPD_FLAG_NO_GRAPH}
+    configs["chain_q50"] = {"arch": "chain_q50"}
+    configs["kv_launch OPD_ENC_TAIL=1"] = {"arch": "kv_launch", "env": {"OPD_ENC_TAIL": "1"}}
     result = {}
     for name, kw in configs.items():
         result[name] = fingerprint(**kw)
