@@ -567,12 +567,6 @@ hipError_t launch_btail_t(const BtailParams& p, hipStream_t stream) {
 
 }  // namespace
 
-#ifndef OPD_ELEM_BF16   // (shape predicates and the host-side weight permutation do not depend on the element type: defined once)
-bool opd_btail_supported(int C1, int C3) {
-    return (C1 == 64 && (C3 == 0 || C3 == 64 || C3 == 128)) || (C1 == 128 && (C3 == 0 || C3 == 128)) || opd_btail256_supported(C1, C3);
-}
-#endif
-
 hipError_t OPD_SYM(opd_launch_btail)(const BtailParams& p_in, hipStream_t stream) {
     if (!opd_btail_supported(p_in.C1, p_in.C3) || p_in.OH <= 0 || p_in.OW <= 0) return hipErrorInvalidValue;
     BtailParams p = p_in;
@@ -611,17 +605,3 @@ hipError_t OPD_SYM(opd_launch_btail)(const BtailParams& p_in, hipStream_t stream
     if (p.C3 == 0) return rdma ? launch_btail_t<128, 0, true>(p, stream) : launch_btail_t<128, 0, false>(p, stream);
     return rdma ? launch_btail_t<128, 128, true>(p, stream) : launch_btail_t<128, 128, false>(p, stream);
 }
-
-#ifndef OPD_ELEM_BF16
-// K-permutation of a [rows][K] fp16 weight matrix (K % 32 == 0) that makes two fp16-rounded 16x16 accumulator tiles a
-// valid B operand: within each 32-block, slot 8g+e <- channel 4g+e, slot 8g+4+e <- channel 16+4g+e.
-void opd_permute_k32(const f16_t* w, f16_t* out, int rows, int K) {
-    for (int n = 0; n < rows; ++n)
-        for (int b = 0; b < K; b += 32)
-            for (int g = 0; g < 4; ++g)
-                for (int e = 0; e < 4; ++e) {
-                    out[(size_t)n * K + b + 8 * g + e] = w[(size_t)n * K + b + 4 * g + e];
-                    out[(size_t)n * K + b + 8 * g + 4 + e] = w[(size_t)n * K + b + 16 + 4 * g + e];
-                }
-}
-#endif

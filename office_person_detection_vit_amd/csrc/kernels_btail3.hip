@@ -457,10 +457,6 @@ hipError_t launch_btail256_t(const BtailParams& p, hipStream_t stream) {
 
 }  // namespace
 
-#ifndef OPD_ELEM_BF16
-bool opd_btail256_supported(int C1, int C3) { return C1 == 256 && (C3 == 0 || C3 == 256); }
-#endif
-
 // called by opd_launch_btail (kernels_btail.hip) for C1 == 256, with the FastDiv fields filled and the offset ranges checked
 hipError_t OPD_SYM(opd_launch_btail256)(const BtailParams& p, hipStream_t stream) {
     if (!opd_btail256_supported(p.C1, p.C3) || p.xs) return hipErrorInvalidValue;

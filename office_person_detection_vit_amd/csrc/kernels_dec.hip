@@ -678,7 +678,7 @@ __global__ __launch_bounds__(512) void dec_ffn_kernel(DecFfnParams p) {
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // heads2_kernel: the class head (256 -> ncls <= 128) and the box MLP (256 -> 256 -> 256 -> 4, ReLU, sigmoid) on split fp16 operands
-// (HF:models/detr/modeling_detr.py:1284-1300, 1567-1583), grid = slabs of 16 rows, 512 threads.  The fp32-MFMA form (kernels_misc.hip::
+// (HF:models/detr/modeling_detr.py:1284-1300, 1567-1583), grid = slabs of 16 rows, 512 threads.  The fp32-MFMA form (kernels_untyped.hip::
 // heads_kernel) pulls 620 KB of fp32 weights per workgroup through register loads in fragment shape -- the slow path of
 // tools/microbench/oneshot.hip -- and takes 34 us; here the three 256-wide layers travel like every other decoder weight: fragment-order
 // hi / lo pairs through the wave-private rings.  Prologue as heads_kernel's (the last layer's FFN sum + LN3, the final decoder LayerNorm).
@@ -820,24 +820,6 @@ __global__ __launch_bounds__(512) void heads2_kernel(HeadParams p) {
 }
 
 }  // namespace
-
-// host: [N][K] fp32 -> the split pair in MFMA-fragment order: for every (16-row tile nt, 32-wide k-step ks) 1 KiB of hi = fp16(w) followed by
-// 1 KiB of lo = fp16((w - hi) * 2048); inside a KiB lane L = 16 g + li holds w[16 nt + li][32 ks + 8 g .. + 7].  out: 2 * N * K halves.
-void opd_split_f16_frag(const float* w, int N, int K, f16_t* out) {
-    const int nks = K / 32;
-    for (int nt = 0; nt < N / 16; ++nt)
-        for (int ks = 0; ks < nks; ++ks) {
-            f16_t* blk = out + ((size_t)nt * nks + ks) * 1024;
-            for (int L = 0; L < 64; ++L)
-                for (int e = 0; e < 8; ++e) {
-                    const float v = w[(size_t)(nt * 16 + (L & 15)) * K + ks * 32 + (L >> 4) * 8 + e];
-                    const _Float16 h = fabsf(v) < 6.103515625e-5f ? (_Float16)0.f : (_Float16)v;   // (no subnormal hi: see split1)
-                    const _Float16 l = (_Float16)((v - (float)h) * 2048.0f);
-                    __builtin_memcpy(&blk[L * 8 + e], &h, 2);
-                    __builtin_memcpy(&blk[512 + L * 8 + e], &l, 2);
-                }
-        }
-}
 
 hipError_t opd_launch_heads2(const HeadParams& p, hipStream_t stream) {
     if (p.rows <= 0 || p.ncls <= 0 || p.ncls > 128 || !p.hs || !p.wc_f || !p.w1_f || !p.w2_f || !p.bc || !p.b1 || !p.b2 || !p.w3 || !p.b3 || !p.logits || !p.boxes)

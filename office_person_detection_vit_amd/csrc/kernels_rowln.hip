@@ -18,6 +18,7 @@
 // LayerNorm + fc1 + ReLU + fc2 + LayerNorm -- in one launch, weights as per-wave fragment streams through wave-private rings) and
 // gemm_k256_kernel (small-M linears of the unfused decoder chain).
 #include "opd_kprims.h"
+#include "opd_pack.h"   // opd_encffn_pieces: the stream stride of enc_ffn_kernel
 
 namespace {
 
@@ -533,7 +534,6 @@ constexpr int EF_X = EF_TM * 512;
 constexpr int EF_H = EF_TM * 256;
 constexpr int EF_RING0 = EF_X + 2 * EF_H;
 constexpr int EF_LDS = EF_RING0 + 8 * EF_R * 1024;
-constexpr int EF_PIECES(const int nch, const int tail, const int front) { return (front ? 16 : 0) + 14 + 17 * nch + (tail ? 17 * tail + 5 : 0); }   // per wave
 
 #define EF_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define EF_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(512, 1) void enc_ffn_kernel(EncFfnParams p) {
     const int m_base = blockIdx.x * EF_TM;
     unsigned char* const ring = smem + EF_RING0 + wave * (EF_R * 1024);
     const int nch = p.F / 128;
-    const unsigned stride = (unsigned)EF_PIECES(nch, p.pack_tail, p.pack_front) * 1024u;   // bytes of a wave's stream
+    const unsigned stride = (unsigned)opd_encffn_pieces(nch, p.pack_tail, p.pack_front) * 1024u;   // bytes of a wave's stream
     const unsigned skip = (p.pack_front && !p.attn) ? 16u * 1024u : 0u;                    // (a stream packed with the front projection, run without it)
     const unsigned total = stride - skip;
     const unsigned char* const wsrc = p.wpack + (size_t)wave * stride + skip + lane16;
@@ -878,7 +878,7 @@ hipError_t OPD_SYM(opd_launch_enc_ffn)(const EncFfnParams& p, hipStream_t stream
     // residual the epilogue adds is what the front phase wrote (y32 == res32)
     if ((p.attn && !p.pack_front) || (p.attn && (!p.bo || !p.gamma1 || !p.beta1 || !p.y32 || p.y32 != p.res32))) return hipErrorInvalidValue;
     if (p.yp16 && (p.pos_period <= 0 || (!p.pos && !p.pos_ptrs))) return hipErrorInvalidValue;
-    if ((size_t)EF_PIECES(p.F / 128, p.pack_tail, p.pack_front) * 1024 >= 0x7fffff00ull) return hipErrorInvalidValue;   // 32-bit stream offsets
+    if ((size_t)opd_encffn_pieces(p.F / 128, p.pack_tail, p.pack_front) * 1024 >= 0x7fffff00ull) return hipErrorInvalidValue;   // 32-bit stream offsets
     if (p.pack_tail < 0 || p.pack_tail > 16 || (p.tail != 0 && p.tail != p.pack_tail) || p.tail < 0 || p.tail > 16 || p.tail_pos < 0 || p.tail_pos > p.tail || (p.tail && (!p.tail_out || p.tail_ld < 256))) return hipErrorInvalidValue;
     if (p.tail_pos > 0 && (p.pos_period <= 0 || (!p.pos && !p.pos_ptrs))) return hipErrorInvalidValue;
     const dim3 grid((p.M + EF_TM - 1) / EF_TM);
@@ -900,79 +900,6 @@ hipError_t OPD_SYM(opd_launch_enc_ffn)(const EncFfnParams& p, hipStream_t stream
         default: return hipErrorInvalidValue;
     }
 }
-
-#ifndef OPD_ELEM_BF16   // (a permutation of 16-bit words and fp32 biases: the same for both element types)
-size_t opd_encffn_pack_bytes(int F, int tail, int front) { return (size_t)8 * EF_PIECES(F / 128, tail, front) * 1024; }
-// host: w1 [F][256], w2 [256][F] as 16-bit elements (fp16 or bf16), b1 [F] fp32 -> the eight per-wave streams of enc_ffn_kernel, in the order the
-// kernel consumes them: G0(0) G1(0) G0(1) { G1(c+1) G2(c) G3(c) G0(c+2) } for c = 0 .. F/128 - 1 (zeros for fc1 chunks past the end).
-//   G0(c): the bias piece (lane L = 16 g + li: b1[128 c + 16 w + 4 g .. + 3] as fp32), then k-steps 0 .. 3 of W1's tile (lane L:
-//          w1[128 c + 16 w + li][32 ks + 8 g .. + 7]);  G1(c): k-steps 4 .. 7;
-//   G2(c) / G3(c): W2's k-steps i = 0, 1 / 2, 3 of the chunk for the wave's tiles j = 0, 1 at 2 (i & 1) + j (lane L:
-//          w2[(2 w + j) 16 + li][128 c + 32 i + 8 g .. + 7]).
-// Tail (optional): wt [tail * 256][256] = the weight rows of the tail projection in PASS order, bt [tail * 256] its biases; per pass the bias piece
-// (lane (g, li): bt[256 t + (2 w + (li >> 3)) 16 + 4 g .. + 3]) and 16 pieces in fc2's group format (group q: k-steps 2 q, 2 q + 1 of the wave's
-// tiles 2 w, 2 w + 1 of that pass); five zero pieces at the end.
-// Front (optional): wo [256][256] = the attention output projection; its 16 pieces (fc2's group format) lead every wave's stream.
-void opd_encffn_pack(const uint16_t* w1, const float* b1, const uint16_t* w2, int F, const uint16_t* wt, const float* bt, int tail, const uint16_t* wo, unsigned char* out) {
-    const int nch = F / 128;
-    const int front = wo != nullptr;
-    __builtin_memset(out, 0, opd_encffn_pack_bytes(F, tail, front));
-    for (int w = 0; w < 8; ++w) {
-        unsigned char* o = out + (size_t)w * EF_PIECES(nch, tail, front) * 1024;
-        if (front)
-            for (int q = 0; q < 4; ++q) {
-                for (int L = 0; L < 64; ++L) {
-                    const int g = L >> 4, li = L & 15;
-                    for (int i = 0; i < 2; ++i)
-                        for (int j = 0; j < 2; ++j)
-                            __builtin_memcpy(o + (2 * i + j) * 1024 + L * 16, wo + (size_t)((2 * w + j) * 16 + li) * 256 + 32 * (2 * q + i) + 8 * g, 16);
-                }
-                o += 4 * 1024;
-            }
-        auto g0 = [&](const int c) {   // 5 pieces
-            if (c < nch)
-                for (int L = 0; L < 64; ++L) {
-                    const int g = L >> 4, li = L & 15;
-                    __builtin_memcpy(o + L * 16, b1 + 128 * c + 16 * w + 4 * g, 16);
-                    for (int ks = 0; ks < 4; ++ks) __builtin_memcpy(o + (1 + ks) * 1024 + L * 16, w1 + (size_t)(128 * c + 16 * w + li) * 256 + 32 * ks + 8 * g, 16);
-                }
-            o += 5 * 1024;
-        };
-        auto g1 = [&](const int c) {   // 4 pieces
-            if (c < nch)
-                for (int L = 0; L < 64; ++L) {
-                    const int g = L >> 4, li = L & 15;
-                    for (int ks = 4; ks < 8; ++ks) __builtin_memcpy(o + (ks - 4) * 1024 + L * 16, w1 + (size_t)(128 * c + 16 * w + li) * 256 + 32 * ks + 8 * g, 16);
-                }
-            o += 4 * 1024;
-        };
-        auto g23 = [&](const int c, const int i0) {   // 4 pieces: k-steps i0, i0 + 1
-            for (int L = 0; L < 64; ++L) {
-                const int g = L >> 4, li = L & 15;
-                for (int i = 0; i < 2; ++i)
-                    for (int j = 0; j < 2; ++j)
-                        __builtin_memcpy(o + (2 * i + j) * 1024 + L * 16, w2 + (size_t)((2 * w + j) * 16 + li) * F + 128 * c + 32 * (i0 + i) + 8 * g, 16);
-            }
-            o += 4 * 1024;
-        };
-        g0(0); g1(0); g0(1);
-        for (int c = 0; c < nch; ++c) { g1(c + 1); g23(c, 0); g23(c, 2); g0(c + 2); }
-        for (int t = 0; t < tail; ++t) {
-            for (int L = 0; L < 64; ++L) __builtin_memcpy(o + L * 16, bt + 256 * t + (2 * w + ((L & 15) >> 3)) * 16 + 4 * (L >> 4), 16);
-            o += 1024;
-            for (int q = 0; q < 4; ++q) {
-                for (int L = 0; L < 64; ++L) {
-                    const int g = L >> 4, li = L & 15;
-                    for (int i = 0; i < 2; ++i)
-                        for (int j = 0; j < 2; ++j)
-                            __builtin_memcpy(o + (2 * i + j) * 1024 + L * 16, wt + (size_t)(t * 256 + (2 * w + j) * 16 + li) * 256 + 32 * (2 * q + i) + 8 * g, 16);
-                }
-                o += 4 * 1024;
-            }
-        }
-    }
-}
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Small-M linear layers of the decoder (M = batch x 100 queries): out = act(x[:, k0:k0+256] . W[:, k0:k0+256]^T + bias).

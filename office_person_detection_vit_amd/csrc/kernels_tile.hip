@@ -2,7 +2,7 @@
 // the frame where it lies, and the per-tile records are merged across the seams.  No 16-bit operands: compiled once.  float64 and integer
 // arithmetic only, no fused multiply-adds (compiled with -ffp-contract=off, and the pragmas of opd_tile.h).
 //
-//   tile_resize_u8_kernel  resize_bilinear_u8_kernel's arithmetic (kernels_misc.hip: Pillow's two 8-bit passes, 22-bit taps, the tables of
+//   tile_resize_u8_kernel  resize_bilinear_u8_kernel's arithmetic (kernels_untyped.hip: Pillow's two 8-bit passes, 22-bit taps, the tables of
 //                          opd_resize_coeffs, the same rounding and clipping in the same order) with another source addressing: one thread
 //                          per output pixel of batch index b = frame * n_tiles + tile reads rows y0[tile] + ... and columns x0[tile] + ...
 //                          of frame b / n_tiles, pitch 3 * frame_w.  Byte loads: 3 * x0 is of any alignment.

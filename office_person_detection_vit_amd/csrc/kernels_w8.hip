@@ -20,7 +20,7 @@
 
 namespace {
 
-constexpr int W8_BM = 128, W8_BN = 256;
+constexpr int W8_BM = 128, W8_BN = OPD_W8_COLS;
 constexpr int W8_A_BYTES = W8_BM * ROW_BYTES;                 // 16 KiB
 constexpr int W8_STAGE = W8_A_BYTES + W8_BN * ROW_BYTES;      // 48 KiB
 constexpr int W8_LDS = 3 * W8_STAGE;                          // 144 KiB: one workgroup per CU
@@ -222,18 +222,6 @@ __global__ __launch_bounds__(512) void conv_w8_kernel(ConvGemmParams p) {
 }
 
 }  // namespace
-
-#ifndef OPD_ELEM_BF16
-// shape contract of the eight-wave kernel (the caller falls back to opd_launch_conv_gemm otherwise)
-bool opd_conv_w8_supported(const ConvGemmParams& p) {
-    if (p.M <= 0 || p.N <= 0 || (p.N % W8_BN) != 0 || p.Cin <= 0 || (p.Cin % 64) != 0 || p.K != p.KH * p.KW * p.Cin || p.K / 64 < 3) return false;
-    if (p.KH < 1 || p.KW < 1 || p.KH * p.KW > 32 || p.stride < 1 || p.pad < 0 || p.OH <= 0 || p.OW <= 0) return false;
-    if ((long long)p.B * p.OH * p.OW != p.M) return false;
-    if (p.stem || p.x2 || p.x_alt || p.split_k > 1 || p.out_f32 || p.res32 || p.bias_period != 0 || p.bias_ptrs || p.out16_aux || !p.bias || !p.out) return false;
-    if ((size_t)p.B * p.H * p.W * p.Cin * 2 + (size_t)(p.pad * p.W + p.pad) * p.Cin * 2 >= 0x7fffff00ull || (size_t)p.N * p.K * 2 >= 0x7fffff00ull) return false;
-    return true;
-}
-#endif
 
 hipError_t OPD_SYM(opd_launch_conv_w8)(const ConvGemmParams& p_in, hipStream_t stream) {
     if (!opd_conv_w8_supported(p_in)) return hipErrorInvalidValue;

@@ -73,7 +73,7 @@ static int resize_tab(opd_detr* m, int h, int w, int oh, int ow, const opd_detr:
     return OPD_OK;
 }
 
-// Frames at camera resolution -> m->d_u8 at model resolution (Pillow-exact bilinear, kernels_misc.hip).
+// Frames at camera resolution -> m->d_u8 at model resolution (Pillow-exact bilinear, kernels_untyped.hip).
 // (`list` != null: one host pointer per frame instead of the contiguous block `frames`)
 static int enqueue_resize(opd_detr* m, const uint8_t* frames, int mem_kind, int B, int h, int w, int oh, int ow, const uint8_t* const* list = nullptr) {
     if (h < 1 || w < 1 || (size_t)h * w > (size_t)1 << 26) return fail(OPD_EINVAL, "source frame size out of range");

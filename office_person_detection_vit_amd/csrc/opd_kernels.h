@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
+#include "opd_pack.h"   // the host-side weight packers: opd_permute_k32, opd_split_f16_frag, opd_encffn_pack
 
 typedef uint16_t f16_t;  // raw 16-bit operand bits on the host side: IEEE half (default) or bfloat16 (OPD_FLAG_BF16)
 enum { OPD_DT_F16 = 0, OPD_DT_BF16 = 1 };   // operand type of a launch: every kernel file with 16-bit operands is compiled for both (opd_elem.h)
@@ -98,7 +99,16 @@ struct ConvGemmParams {
 };
 hipError_t opd_launch_conv_gemm(const ConvGemmParams& p, hipStream_t stream);
 // eight-wave form for wide layers (kernels_w8.hip: 128 x 256 tiles, one workgroup per CU, three-stage ring); bit-identical results
-bool opd_conv_w8_supported(const ConvGemmParams& p);
+constexpr int OPD_W8_COLS = 256;   // its column-tile width
+// shape contract of the eight-wave kernel (the caller falls back to opd_launch_conv_gemm otherwise)
+inline bool opd_conv_w8_supported(const ConvGemmParams& p) {
+    if (p.M <= 0 || p.N <= 0 || (p.N % OPD_W8_COLS) != 0 || p.Cin <= 0 || (p.Cin % 64) != 0 || p.K != p.KH * p.KW * p.Cin || p.K / 64 < 3) return false;
+    if (p.KH < 1 || p.KW < 1 || p.KH * p.KW > 32 || p.stride < 1 || p.pad < 0 || p.OH <= 0 || p.OW <= 0) return false;
+    if ((long long)p.B * p.OH * p.OW != p.M) return false;
+    if (p.stem || p.x2 || p.x_alt || p.split_k > 1 || p.out_f32 || p.res32 || p.bias_period != 0 || p.bias_ptrs || p.out16_aux || !p.bias || !p.out) return false;
+    if ((size_t)p.B * p.H * p.W * p.Cin * 2 + (size_t)(p.pad * p.W + p.pad) * p.Cin * 2 >= 0x7fffff00ull || (size_t)p.N * p.K * 2 >= 0x7fffff00ull) return false;
+    return true;
+}
 hipError_t opd_launch_conv_w8(const ConvGemmParams& p, hipStream_t stream);
 // fused stem: 7x7 s2 conv + FrozenBN + ReLU + 3x3 s2 max-pool on the zero-bordered NHWC4 image -> pooled NHWC fp16
 // StemReduce (optional, z0 != null): the same launch also writes z0 [B][PH][PW][64] = relu(w0 . pooled + b0), w0 [64][64] -- the 1x1 stride-1
@@ -152,11 +162,12 @@ struct BtailParams {
     int rc;
     int y_stride2;
 };
-bool opd_btail_supported(int C1, int C3);
+inline bool opd_btail256_supported(int C1, int C3) { return C1 == 256 && (C3 == 0 || C3 == 256); }
+inline bool opd_btail_supported(int C1, int C3) {
+    return (C1 == 64 && (C3 == 0 || C3 == 64 || C3 == 128)) || (C1 == 128 && (C3 == 0 || C3 == 128)) || opd_btail256_supported(C1, C3);
+}
 hipError_t opd_launch_btail(const BtailParams& p, hipStream_t stream);
-void opd_permute_k32(const f16_t* w, f16_t* out, int rows, int K);  // host
 // 256-channel blocks (stage 3): eight-wave form, kernels_btail3.hip; reached through opd_launch_btail
-bool opd_btail256_supported(int C1, int C3);
 hipError_t opd_launch_btail256(const BtailParams& p, hipStream_t stream);
 
 // ---- Linear(K -> 256) + bias + residual + LayerNorm in one kernel (kernels_rowln.hip) ---------------------------------
@@ -219,9 +230,6 @@ struct EncFfnParams {
     int tail_col[16];
 };
 hipError_t opd_launch_enc_ffn(const EncFfnParams& p, hipStream_t stream);
-size_t opd_encffn_pack_bytes(int F, int tail, int front);
-void opd_encffn_pack(const uint16_t* w1, const float* b1, const uint16_t* w2, int F, const uint16_t* wt, const float* bt, int tail, const uint16_t* wo,
-                     unsigned char* out);   // host
 // Small-M linear layer, reduction cut into 256-wide slices: slice z computes x[:, 256z : 256z+256] . w[:, 256z : 256z+256]^T.
 // slices == 1: out = act(. + bias) as fp16 (out16) or fp32 (out32).  slices > 1: fp32 slabs out32[z][M][N], bias in slab 0
 // (summed by opd_launch_reduce_ln).  bias_period > 0: row-periodic bias [period][N].
@@ -236,7 +244,7 @@ struct GemmK256Params {
 };
 hipError_t opd_launch_gemm_k256(const GemmK256Params& p, hipStream_t stream);
 
-// ---- element-wise / small kernels (kernels_misc.hip) ----------------------------------------------------------------
+// ---- element-wise / small kernels (kernels_misc.hip: those with a 16-bit operand, hence a dtype; kernels_untyped.hip: the others) ----
 // uint8 BGR HWC frames -> normalised fp16 NHWC4 (channel 3 = 0): (x/255 - mean)/std, RGB order, written into a
 // zero-bordered image [B][Hp][Wp][4] with the frame at offset (3, 3) (Hp >= H + 6, Wp >= W + 6): the stem's padding.
 // valid_hw (device, nullable): [B][2] = (h, w) of each frame inside the H x W canvas (ragged batch); the rest is zero.
@@ -376,7 +384,6 @@ hipError_t opd_launch_color_features(const ColorParams& p, int spans, hipStream_
 // or activations left on the decoder's residual path.  Weights are stored in MFMA-FRAGMENT ORDER (opd_split_f16_frag, host): per (16-row
 // tile, 32-wide k-step) 1 KiB of hi then 1 KiB of lo, lane L's 16 bytes at offset 16 L -- what a wave streams by LDS-DMA and reads back
 // lane-linear (kernels_dec.hip).  All `w*` pointers of the structs below are such [N][K] matrices (2 * N * K halves).
-void opd_split_f16_frag(const float* w, int N, int K, f16_t* out);   // host
 struct DecQkvParams {   // [previous layer: h = LN3(h_in + b2 + sum partials)] ; q | k | v = h . Wqkv^T + bias[row % Q]
     const float* h_in;       // [M][256] residual stream before the previous layer's FFN (null with partials == null: h_out is the input)
     const float* partials;   // [nsplit][M][256] fp32 partial sums of the previous layer's FFN-2 (null: no reduce / LayerNorm, h = h_out as it is)

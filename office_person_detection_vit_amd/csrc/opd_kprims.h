@@ -191,4 +191,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 // D = A . B + C on 16 x 16 x 32 fragments of the translation unit's operand type
 __device__ __forceinline__ float4v mfma16(const half8& a, const half8& b, const float4v& c) { return OPD_MFMA_16x16x32(a, b, c); }
 
+// (host, for the launchers) grid size of a one-thread-per-element kernel
+inline unsigned blocks_for(size_t n, unsigned threads) { return (unsigned)((n + threads - 1) / threads); }
+
 }  // namespace

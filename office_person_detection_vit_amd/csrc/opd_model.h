@@ -112,7 +112,7 @@ struct Switches {
     int fused_dec = 1;       // the decoder as five launches per layer on split fp16 operands (kernels_dec.hip; 0: the round-3 chain of nine launches
                              // per layer on single fp16 operands, also taken when the architecture does not fit: d_model != 256, heads != 8, queries % 4)
     int dec_splits = 3;      // key ranges of the fused decoder's cross-attention
-    int heads2 = 1;          // the heads through kernels_dec.hip::heads2_kernel (0: kernels_misc.hip::heads_kernel on the fp32 matrix pipe; env OPD_HEADS2)
+    int heads2 = 1;          // the heads through kernels_dec.hip::heads2_kernel (0: kernels_untyped.hip::heads_kernel on the fp32 matrix pipe; env OPD_HEADS2)
     int fuse_btail = 1;      // stages 1-2: 3x3 -> expand + residual -> next reduce in one kernel (0: three launches)
     int fuse_shortcut = 1;   // first block of stage 1: the shortcut convolution as a second GEMM inside the fused tail (0: own launch)
     int dual_over_tail = 1;  // first block of stage 2: 3x3 + dual-source expand instead of shortcut launch + fused tail (-17 us)
@@ -170,7 +170,7 @@ enum EncQkv { QKV_LAUNCH, QKV_PREV_TAIL };   // a layer's q | k | v: its own GEM
 enum OutProj { OPROJ_IN_FFN, OPROJ_GEMM_LN, OPROJ_GEMM_THEN_LN };   // attention output projection + residual + LayerNorm: the front phase of the encoder's FFN
                                                                     // launch / one row-owner kernel / a GEMM, then the LayerNorm (decoder chain: split-K slabs, then reduce + LayerNorm)
 enum EncFfn { FFN_ONE_LAUNCH, FFN_FC1_DEEP, FFN_FC1_SPLITK };   // enc_ffn_kernel / fc1 GEMM + deep-K ring launch / fc1 GEMM + split-K slabs + reduce-LayerNorm
-enum HeadsKernel { HEADS_F32, HEADS_SPLIT16 };   // kernels_misc.hip::heads_kernel / kernels_dec.hip::heads2_kernel
+enum HeadsKernel { HEADS_F32, HEADS_SPLIT16 };   // kernels_untyped.hip::heads_kernel / kernels_dec.hip::heads2_kernel
 struct EncStep {
     int qkv, oproj, ffn;
     int splits;   // FFN_FC1_SPLITK: slices of fc2's reduction

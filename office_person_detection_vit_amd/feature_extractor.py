@@ -1,6 +1,6 @@
 """``detector.feature_extractor``: the attribute the reference's callers expect (``src/pipeline/phases/tracking.py:195-207``).
 
-The detector pools appearance features on the device (``opd_detr_roi_features``, ``kernels_misc.hip::roi_features_kernel``).
+The detector pools appearance features on the device (``opd_detr_roi_features``, ``kernels_untyped.hip::roi_features_kernel``).
 This host class serves callers that hold an encoder map in numpy already.  Contract of the reference class
 (``src/tracking/feature_extractor.py:39-88``): boxes are (x, y, w, h) in image pixels, mapped to the (h, w, C) map by
 truncation, clamped to at least one cell, mean-pooled and L2-normalised with ``+1e-8``.  All boxes are pooled at once from

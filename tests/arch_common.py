@@ -208,7 +208,7 @@ def dec_ffn_case(lib, M, Fh):
     return parts, want.numpy(), c, want_c.numpy()
 
 
-# ---- heads (kernels_dec.hip::heads2_kernel for split = 1, kernels_misc.hip::heads_kernel for split = 0) ----------------------------------
+# ---- heads (kernels_dec.hip::heads2_kernel for split = 1, kernels_untyped.hip::heads_kernel for split = 0) ----------------------------------
 HEADS_SENTINEL = np.float32(-12345.5)
 
 
@@ -283,7 +283,7 @@ def heads_fused_case(lib, split, rows=800, ncls=92, spare=0):
     return logits, boxes, want_logits, want_boxes
 
 
-# ---- post-process (kernels_misc.hip::postprocess_kernel) -----------------------------------------------------------------------------------
+# ---- post-process (kernels_untyped.hip::postprocess_kernel) -----------------------------------------------------------------------------------
 def compare_records(recs, counts, want, atol_box=1e-3):
     """Records [B][Q] (DET) + counts [B] of the post-process kernel against the oracle's post_process_object_detection: the count, the
     compaction order (query_index), label and frame exactly, score and box within the kernel test's bounds."""

@@ -1,20 +1,24 @@
 // Sanitizer driver for the host-only pieces of the detect path (tests/test_host_sanitized_cpu.py builds this file together with
-// csrc/opd_loader.cpp and csrc/opd_host.cpp under -fsanitize=address,undefined and runs it on the CPU; never on the GPU box).
+// csrc/opd_loader.cpp, csrc/opd_host.cpp and csrc/opd_pack.cpp under -fsanitize=address,undefined and runs it on the CPU; never on the GPU box).
 //   driver <list-file>      every line of <list-file> is the path of a (possibly malformed) .safetensors file: parse + schema check
 // then the arithmetic helpers over ranges of arguments: resize coefficient tables, mask down-sampling, sine position embedding,
-// person filter + NMS on adversarial record sets.  Prints one line per file / check; sanitizer reports go to stderr and make the
-// process exit non-zero (-fno-sanitize-recover).
+// person filter + NMS on adversarial record sets, and the weight packers into buffers of exactly the documented sizes (their bytes go
+// to pack_*.bin next to <list-file>).  Prints one line per file / check; sanitizer reports go to stderr and make the process exit
+// non-zero (-fno-sanitize-recover).
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
 
 #include <fstream>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/opd_detr.h"
 #include "../../office_person_detection_vit_amd/csrc/opd_host.h"
 #include "../../office_person_detection_vit_amd/csrc/opd_loader.h"
+#include "../../office_person_detection_vit_amd/csrc/opd_pack.h"
 
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
@@ -98,5 +102,59 @@ int main(int argc, char** argv) {
         if (opd_person_nms_batch(c.data(), too_many, 1, 25, 1, 0.4f) == 0) return 7;
     }
     printf("nms kept %d; last error: %s\n", kept_total, opd_last_error());
+    // weight packers (csrc/opd_pack.cpp): every input and every output is a heap block of exactly its documented size, so an index
+    // term that is off reads or writes outside one; the packed bytes go to files next to the list file for the test's numpy restatement
+    const std::string list_path = argv[1];
+    const size_t cut = list_path.find_last_of('/');
+    const std::string dir = cut == std::string::npos ? "" : list_path.substr(0, cut + 1);
+    auto dump = [&](const std::string& name, const void* p, size_t bytes) {
+        FILE* f = fopen((dir + name).c_str(), "wb");
+        const bool ok = f && fwrite(p, 1, bytes, f) == bytes;
+        if (f) fclose(f);
+        printf("pack %s bytes %zu\n", name.c_str(), bytes);
+        return ok;
+    };
+    // 16-bit ids: distinct within every run of 65536 elements (mul odd: a bijection of 0 .. 65535), and run r shifted by 0x1235 r, so
+    // that the two 256 x 256 tail passes of Wt differ at every (row, column)
+    auto ids = [](size_t n, unsigned mul, unsigned add) {
+        std::unique_ptr<uint16_t[]> v(new uint16_t[n]);
+        for (size_t i = 0; i < n; ++i) v[i] = (uint16_t)(i * mul + add + (i >> 16) * 0x1235);
+        return v;
+    };
+    auto fids = [](size_t n, float base) {
+        std::unique_ptr<float[]> v(new float[n]);
+        for (size_t i = 0; i < n; ++i) v[i] = base + (float)i;
+        return v;
+    };
+    for (int K : {32, 96}) {
+        const auto w = ids((size_t)3 * K, 1, 0);
+        std::unique_ptr<uint16_t[]> out(new uint16_t[(size_t)3 * K]);
+        opd_permute_k32(w.get(), out.get(), 3, K);
+        if (!dump("pack_permute_K" + std::to_string(K) + ".bin", out.get(), (size_t)3 * K * 2)) return 8;
+    }
+    for (const auto& nk : {std::pair<int, int>{16, 32}, std::pair<int, int>{32, 64}}) {   // values written by the test: pack_split_<N>x<K>.in, fp32
+        const size_t n = (size_t)nk.first * nk.second;
+        const std::string tag = std::to_string(nk.first) + "x" + std::to_string(nk.second);
+        std::unique_ptr<float[]> w(new float[n]);
+        FILE* f = fopen((dir + "pack_split_" + tag + ".in").c_str(), "rb");
+        const bool ok = f && fread(w.get(), 4, n, f) == n;
+        if (f) fclose(f);
+        if (!ok) return 9;
+        std::unique_ptr<uint16_t[]> out(new uint16_t[2 * n]);
+        opd_split_f16_frag(w.get(), nk.first, nk.second, out.get());
+        if (!dump("pack_split_" + tag + ".bin", out.get(), 2 * n * 2)) return 10;
+    }
+    for (int F : {128, 256}) {   // F = 128: no tail, no front; F = 256: two tail passes and a front
+        const int tail = F == 256 ? 2 : 0;
+        const auto w1 = ids((size_t)F * 256, 1, 0), w2 = ids((size_t)256 * F, 3, 1);
+        const auto b1 = fids(F, 1000.f);
+        std::unique_ptr<uint16_t[]> wt, wo;
+        std::unique_ptr<float[]> bt;
+        if (tail) { wt = ids((size_t)tail * 256 * 256, 5, 2); wo = ids((size_t)256 * 256, 7, 3); bt = fids((size_t)tail * 256, 5000.f); }
+        const size_t bytes = opd_encffn_pack_bytes(F, tail, wo != nullptr);
+        std::unique_ptr<unsigned char[]> out(new unsigned char[bytes]);
+        opd_encffn_pack(w1.get(), b1.get(), w2.get(), F, wt.get(), bt.get(), tail, wo.get(), out.get());
+        if (!dump("pack_encffn_F" + std::to_string(F) + ".bin", out.get(), bytes)) return 11;
+    }
     return 0;
 }

@@ -31,13 +31,100 @@ def _rewrite_header(src, dst, edit):
         f.write(struct.pack("<Q", len(h)) + h + data)
 
 
+# ---- the weight packers of csrc/opd_pack.cpp, restated in numpy from their layout comments (never from the C++) ----------------------------
+
+def _expect_permute_k32(w):
+    """Within each 32-block of K: slot 8g+e <- channel 4g+e, slot 8g+4+e <- channel 16+4g+e."""
+    rows, K = w.shape
+    return w.reshape(rows, K // 32, 2, 4, 4).transpose(0, 1, 3, 2, 4).reshape(rows, K)   # [n][block][half][g][e] -> [n][block][g][half][e]
+
+
+def _frag(tile, ks):
+    """One 1 KiB piece: lane L = 16 g + li holds tile[li][32 ks + 8 g .. + 7] (tile: 16 rows)."""
+    return np.ascontiguousarray(tile[:, 32 * ks:32 * ks + 32].reshape(16, 4, 8).transpose(1, 0, 2))
+
+
+def _split_values(N, K):
+    """fp32 inputs of opd_split_f16_frag: the edges of `hi` (signed zeros, 2^-14 and its fp32 neighbours, fp16 subnormal steps, the fp16
+    maximum), fp16-exact values, values whose `lo` lies exactly between two fp16 numbers (both parities), then weights-like random values."""
+    rng = np.random.default_rng(N * 1000 + K)
+    t = np.float32(2.0 ** -14)
+    edge = [0.0, t, np.nextafter(t, np.float32(0)), np.nextafter(t, np.float32(1)), 2.0 ** -24, 2.0 ** -25, 65504.0, 60000.0, 1.0, 0.333251953125]
+    ties = []
+    for h in (2.0 ** -4, 0.09375, 2.0 ** -9 * 1.5):          # fp16-exact hi with room below its half ulp for a 12-bit lo
+        ulp = 2.0 ** (np.floor(np.log2(h)) - 10)
+        for m in (2049, 2051, 4093):                          # lo = m * 2^e with a 12-bit odd m: a tie between two 11-bit neighbours
+            e = np.floor(np.log2(ulp / 2 * 2048 / m))        # the largest lo with (v - h) below half an fp16 ulp of h
+            v = h + m * 2.0 ** e / 2048
+            assert float(np.float32(v)) == v and float(np.float16(np.float32(v))) == h, (h, m)   # exact in fp32, and hi is h
+            ties.append(v)
+    special = np.asarray(edge + ties, np.float32)
+    special = np.concatenate([special, -special])
+    exact = rng.standard_normal(24).astype(np.float16).astype(np.float32)
+    w = (rng.standard_normal(N * K) * 0.05).astype(np.float32)
+    w[:special.size] = special
+    w[special.size:special.size + exact.size] = exact
+    return rng.permutation(w).reshape(N, K)
+
+
+def _expect_split_f16_frag(w):
+    """Per (16-row tile, 32-wide k-step): 1 KiB of hi, then 1 KiB of lo, each in fragment order; hi = 0 where |v| < 2^-14, else float16(v);
+    lo = float16((v - hi) * 2048)."""
+    N, K = w.shape
+    hi = np.where(np.abs(w) < np.float32(2.0 ** -14), np.float16(0), w.astype(np.float16))
+    with np.errstate(over="ignore"):
+        lo = ((w - hi.astype(np.float32)) * np.float32(2048)).astype(np.float16)
+    return np.stack([np.stack([np.stack([_frag(m[16 * nt:16 * nt + 16], ks) for m in (hi, lo)]) for ks in range(K // 32)]) for nt in range(N // 16)])
+
+
+def _expect_encffn_pack(w1, b1, w2, wt, bt, tail, wo):
+    """The eight per-wave streams of enc_ffn_kernel: [front] G0(0) G1(0) G0(1) { G1(c+1) G2(c) G3(c) G0(c+2) } [tail passes, five zero pieces]."""
+    nch = w1.shape[0] // 128
+    b = lambda a: np.ascontiguousarray(a).view(np.uint8).ravel()
+    zero = lambda n: np.zeros(n * 1024, np.uint8)
+    lanes_g, lanes_li = np.arange(64) >> 4, np.arange(64) & 15
+    out = []
+    for w in range(8):
+        def fc2_group(mat, row0, col0, i0):   # pieces 2 i + j: k-step i0 + i of the wave's 16-row tiles j = 0, 1
+            return [b(_frag(mat[row0 + (2 * w + j) * 16:row0 + (2 * w + j) * 16 + 16, col0:], i0 + i)) for i in range(2) for j in range(2)]
+
+        def g0(c):   # the bias piece (lane (g, li): b1[128 c + 16 w + 4 g .. + 3]), then k-steps 0 .. 3 of W1's tile
+            if c >= nch:
+                return [zero(5)]
+            bias = np.stack([b1[128 * c + 16 * w + 4 * g:128 * c + 16 * w + 4 * g + 4] for g in lanes_g])
+            return [b(bias)] + [b(_frag(w1[128 * c + 16 * w:128 * c + 16 * w + 16], ks)) for ks in range(4)]
+
+        def g1(c):
+            return [zero(4)] if c >= nch else [b(_frag(w1[128 * c + 16 * w:128 * c + 16 * w + 16], ks)) for ks in range(4, 8)]
+
+        s = []
+        if wo is not None:
+            for q in range(4):
+                s += fc2_group(wo, 0, 0, 2 * q)
+        s += g0(0) + g1(0) + g0(1)
+        for c in range(nch):
+            s += g1(c + 1) + fc2_group(w2, 0, 128 * c, 0) + fc2_group(w2, 0, 128 * c, 2) + g0(c + 2)
+        for t in range(tail):
+            s.append(b(np.stack([bt[256 * t + (2 * w + (li >> 3)) * 16 + 4 * g:][:4] for g, li in zip(lanes_g, lanes_li)])))
+            for q in range(4):
+                s += fc2_group(wt, 256 * t, 0, 2 * q)
+        if tail:
+            s.append(zero(5))
+        out.append(np.concatenate(s))
+    assert len({o.size for o in out}) == 1
+    return np.concatenate(out)
+
+
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++ for the sanitizer build")
 def test_host_code_under_address_and_ub_sanitizers(tmp_path):
     exe = str(tmp_path / "host_asan_driver")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
            os.path.join(ROOT, "tests", "native", "host_asan_driver.cpp"), os.path.join(CSRC, "opd_loader.cpp"), os.path.join(CSRC, "opd_host.cpp"),
-           "-o", exe]
+           os.path.join(CSRC, "opd_pack.cpp"), "-o", exe]
     subprocess.run(cmd, check=True, capture_output=True, text=True)
+    split_in = {(N, K): _split_values(N, K) for N, K in ((16, 32), (32, 64))}
+    for (N, K), w in split_in.items():
+        w.tofile(str(tmp_path / f"pack_split_{N}x{K}.in"))
 
     files, expect = [], {}
     # (1) a real (shallow) architecture: well-formed, then header edits that violate the schema
@@ -134,3 +221,21 @@ def test_host_code_under_address_and_ub_sanitizers(tmp_path):
         if name.startswith(("cut_", "hlen_")) and name not in ("hlen_5.safetensors",):
             assert parse != 0 or schema != 0, name
     assert "nms kept" in run.stdout and "position embedding sum" in run.stdout
+    # the weight packers: the bytes the driver wrote against numpy restatements of the layout comments in csrc/opd_pack.cpp
+    packed = lambda name, dt: np.fromfile(str(tmp_path / name), dt)
+    for K in (32, 96):
+        assert np.array_equal(packed(f"pack_permute_K{K}.bin", np.uint16), _expect_permute_k32(np.arange(3 * K, dtype=np.uint16).reshape(3, K)).ravel()), K
+    for (N, K), w in split_in.items():
+        got, exp = packed(f"pack_split_{N}x{K}.bin", np.uint16), _expect_split_f16_frag(w).view(np.uint16).ravel()
+        assert got.size == 2 * N * K and np.array_equal(got, exp), (N, K, np.flatnonzero(got != exp)[:8])
+    for F, tail, front in ((128, 0, False), (256, 2, True)):
+        # distinct inside every run of 65536 elements, run r shifted by 0x1235 r: the two tail passes of Wt differ at every (row, column)
+        ids = lambda n, mul, add: ((np.arange(n, dtype=np.uint64) * mul + add + (np.arange(n, dtype=np.uint64) >> 16) * 0x1235) & 0xffff).astype(np.uint16)
+        exp = _expect_encffn_pack(ids(F * 256, 1, 0).reshape(F, 256), 1000 + np.arange(F, dtype=np.float32), ids(256 * F, 3, 1).reshape(256, F),
+                                  ids(tail * 65536, 5, 2).reshape(tail * 256, 256), 5000 + np.arange(tail * 256, dtype=np.float32), tail,
+                                  ids(65536, 7, 3).reshape(256, 256) if front else None)
+        got = packed(f"pack_encffn_F{F}.bin", np.uint8)
+        pieces = (16 if front else 0) + 14 + 17 * (F // 128) + (17 * tail + 5 if tail else 0)   # per wave: opd_pack.h
+        assert got.size == exp.size == 8 * pieces * 1024, (F, got.size, exp.size)   # = opd_encffn_pack_bytes: the driver allocated and wrote that many
+        assert f"pack pack_encffn_F{F}.bin bytes {8 * pieces * 1024}\n" in run.stdout
+        assert np.array_equal(got, exp), (F, np.flatnonzero(got != exp)[:8])

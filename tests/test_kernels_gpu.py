@@ -991,13 +991,13 @@ def test_conv_dual_source_integer_exact(lib):
     np.testing.assert_array_equal(got, yu)
 
 
-# ---- output kernels in isolation (kernels_misc.hip): heads, post-process, ROI features ---------------------------------------------
+# ---- output kernels in isolation (kernels_untyped.hip): heads, post-process, ROI features ---------------------------------------------
 @pytest.mark.parametrize("split", [1, 0])
 @pytest.mark.parametrize("rows,ln", [(800, True), (100, False), (37, True), (1, True)])
 def test_heads_kernel_matches_torch(lib, rows, ln, split):
     """class_labels_classifier + DetrMLPPredictionHead + sigmoid (HF:models/detr/modeling_detr.py:1284-1300, 1410-1411), with and
     without the decoder's final LayerNorm inside, against float64 torch.  split = 1: kernels_dec.hip::heads2_kernel (the 256-wide layers
-    on split fp16 pairs through the decoder's rings: fp32-grade products); split = 0: kernels_misc.hip::heads_kernel (fp32 matrix pipe)."""
+    on split fp16 pairs through the decoder's rings: fp32-grade products); split = 0: kernels_untyped.hip::heads_kernel (fp32 matrix pipe)."""
     logits, boxes, want_logits, want_boxes = heads_case(lib, rows, ln, split)
     np.testing.assert_allclose(logits, want_logits, atol=2e-5, rtol=1e-5)
     np.testing.assert_allclose(boxes, want_boxes, atol=2e-6)
