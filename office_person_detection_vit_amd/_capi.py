@@ -276,6 +276,9 @@ TEST_API = {
     "opd_test_set_gemm_ln_kloop": (C.c_int, [C.c_int]),
     "opd_test_set_encffn_wprefetch": (C.c_int, [C.c_int]),
     "opd_test_set_pos_frames": (C.c_int, [C.c_int]),
+    "opd_test_set_repeat": (C.c_int, [C.c_int]),
+    "opd_test_repeat_result": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "opd_test_repeat_selftest": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "opd_test_conv_splitk": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 13),
     "opd_test_reduce_act16": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p]),
     "opd_test_gemm_alt": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5),

@@ -1,7 +1,9 @@
 // opd_test_api.cpp — kernel-level test hooks (host buffers in, host buffers out).  NOT part of the drop-in boundary
 // (include/opd_detr.h) and NOT part of the product library: this file is linked only into libopd_hip_test.so (csrc/build.py), which
 // tests/ and tools/ load instead of libopd_hip.so, so that tests/test_kernels_gpu.py can check each hand-written kernel against the
-// oracle on identical inputs.  Every kernel hook allocates its own device buffers, runs ONE kernel on the null stream and frees.
+// oracle on identical inputs.  Every kernel hook allocates its own device buffers, runs ONE kernel on the null stream and frees; the hooks of
+// the kernels that order LDS-DMA by counted waits launch through launch_repeated (opd_test_util.h), which is that one launch unless
+// opd_test_set_repeat turned the race screen on.
 // Beside it: opd_test_bench_api.cpp (the timing and trace hooks of tools/) and opd_test_model_api.cpp (host-only helpers, and the hooks
 // that reach into a model handle).
 #include <string.h>
@@ -22,6 +24,140 @@ TAPI int opd_test_set_conv_flags(int flags) { g_conv_flags = flags; return OPD_O
 TAPI int opd_test_set_gemm_ln_kloop(int on) { g_gemm_ln_kloop = on ? 1 : 0; return OPD_OK; }
 // opd_test_btail / opd_test_btail_repeat: the residual of the 64 / 128-channel tails through register loads (BtailParams::dbg bit 16) instead of LDS-DMA
 TAPI int opd_test_set_btail_res_regs(int on) { g_btail_dbg = on ? 16 : 0; return OPD_OK; }
+
+// ---- the race screen (opd_test_util.h: launch_repeated) ----------------------------------------------------------------------------------
+// g_repeat: the repeat count of the hooks (0 = off); g_rep_launches / g_rep_diff: what the last launch_repeated did and found;
+// g_rep_keep: the self-test's switch that leaves the in-place buffers as the previous repetition left them
+static int g_repeat = 0, g_rep_launches = 0, g_rep_diff = 0, g_rep_keep = 0;
+TAPI int opd_test_set_repeat(int reps) {
+    g_repeat = reps >= 2 ? reps : 0;
+    g_rep_launches = g_rep_diff = 0;
+    return OPD_OK;
+}
+// (launches, n_diff) of the last hook call, 0 launches when that hook did not launch through launch_repeated.  The hooks that do not use it
+// cannot clear the record, so the READ clears it (as does opd_test_set_repeat): a test sets the count, calls ONE hook and reads once.
+TAPI int opd_test_repeat_result(int* launches, int* n_diff) {
+    if (!launches || !n_diff) return fail(OPD_EINVAL, "repeat_result: null pointer");
+    *launches = g_rep_launches; *n_diff = g_rep_diff;
+    g_rep_launches = g_rep_diff = 0;
+    return OPD_OK;
+}
+
+const char* opd::g_launch_expr = nullptr;
+// launch(rep), a failure reported under the text of the launcher call that failed (LAUNCHED)
+static int launch_checked(const std::function<hipError_t(int)>& launch, int rep) {
+    g_launch_expr = nullptr;
+    const hipError_t e = launch(rep);
+    if (e == hipSuccess) return OPD_OK;
+    return fail(OPD_EHIP, std::string(g_launch_expr ? g_launch_expr : "launch") + " failed: " + hipGetErrorString(e) + " (" + __FILE__ + ", repetition " +
+                              std::to_string(rep) + ")");
+}
+
+int opd::launch_repeated(const std::function<hipError_t(int)>& launch, const std::vector<RepOut>& outs, const std::vector<RepInPlace>& inplace,
+                         int reps) {
+    if (reps == REPEAT_DEFAULT) reps = g_repeat;
+    g_rep_launches = g_rep_diff = 0;
+    if (reps < 2) {
+        RCCHK(launch_checked(launch, 0));
+        g_rep_launches = 1;
+        return OPD_OK;
+    }
+    struct Buf { void* ptr; size_t bytes; int fill; void* pristine; };
+    std::vector<Buf> bufs;
+    for (const RepOut& o : outs)
+        if (o.ptr && o.bytes) bufs.push_back({o.ptr, o.bytes, o.fill, nullptr});
+    const size_t n_out = bufs.size();
+    for (const RepInPlace& b : inplace)
+        if (b.ptr && b.bytes) bufs.push_back({b.ptr, b.bytes, 0, nullptr});
+    if (bufs.empty()) return fail(OPD_EINVAL, "launch_repeated: no buffer to compare");
+    for (const Buf& b : bufs)
+        if (b.bytes % 4) return fail(OPD_EINVAL, "launch_repeated: a buffer of " + std::to_string(b.bytes) + " bytes is no multiple of 4; the checksum would pass over its tail");
+    DevMem dm;
+    for (size_t i = n_out; i < bufs.size(); ++i) {
+        bufs[i].pristine = dm.alloc<unsigned char>(bufs[i].bytes);
+        if (bufs[i].pristine) HIPCHK(hipMemcpy(bufs[i].pristine, bufs[i].ptr, bufs[i].bytes, hipMemcpyDeviceToDevice));
+    }
+    const size_t noise_bytes = (size_t)256 << 20, block = bufs.size() * OPD_TAP_BLOCKS;
+    unsigned char* noise = dm.alloc<unsigned char>(2 * noise_bytes);
+    std::vector<unsigned long long> h((size_t)reps * block);
+    unsigned long long* sums = dm.alloc<unsigned long long>(h.size());
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    hipStream_t side = nullptr;
+    HIPCHK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+    auto run = [&]() -> int {
+        for (int r = 0; r < reps; ++r) {
+            for (size_t i = 0; i < bufs.size(); ++i) {
+                if (i < n_out) HIPCHK(hipMemsetAsync(bufs[i].ptr, bufs[i].fill, bufs[i].bytes, nullptr));
+                else if (!g_rep_keep) HIPCHK(hipMemcpyAsync(bufs[i].ptr, bufs[i].pristine, bufs[i].bytes, hipMemcpyDeviceToDevice, nullptr));
+            }
+            (void)hipMemcpyAsync(noise + ((r & 1) ? noise_bytes : 0), noise + ((r & 1) ? 0 : noise_bytes), noise_bytes, hipMemcpyDeviceToDevice, side);
+            RCCHK(launch_checked(launch, r));
+            for (size_t i = 0; i < bufs.size(); ++i)
+                HIPCHK(opd_launch_checksum(bufs[i].ptr, bufs[i].bytes, sums + (size_t)r * block + i * OPD_TAP_BLOCKS, nullptr));
+        }
+        HIPCHK(hipDeviceSynchronize());
+        return OPD_OK;
+    };
+    const int rc = run();
+    if (rc != OPD_OK) (void)hipDeviceSynchronize();   // (nothing of this call is in flight when its buffers go)
+    (void)hipStreamDestroy(side);
+    RCCHK(rc);
+    RCCHK(down(h.data(), sums, h.size()));
+    for (int r = 1; r < reps; ++r)
+        if (memcmp(h.data() + (size_t)r * block, h.data(), block * sizeof(unsigned long long)) != 0) ++g_rep_diff;
+    g_rep_launches = reps;
+    return OPD_OK;
+}
+
+// The screen's own test: launch_repeated on `bytes` of a fixed pattern written by plain copies instead of a kernel, with the repeat count of
+// opd_test_set_repeat (>= 8).  mode 0: every repetition writes the pattern (*n_diff = 0); 1: repetition 7 differs in the buffer's last 16-bit
+// value (1); 2: repetition 3 writes nothing, the 0xff refill survives (1); 3: repetitions 5 and 6 swap words 1 and 2, which share a checksum
+// slot (2); 4: an IN-PLACE buffer that every launch advances from what it finds (rotates by one word): 0 because of the restore, and the hook
+// runs it once more without the restore and fails unless every later repetition then differs; 5: that second run alone (reps - 1).
+TAPI int opd_test_repeat_selftest(int mode, int bytes, int* n_diff) {
+    if (mode < 0 || mode > 5 || bytes < 16 || !n_diff || g_repeat < 8) return fail(OPD_EINVAL, "repeat_selftest: bad arguments");
+    DevMem dm;
+    const size_t n = (size_t)bytes, words = (n + 3) / 4;
+    std::vector<uint32_t> pat(words + 1);
+    for (size_t i = 0; i < pat.size(); ++i) pat[i] = (uint32_t)(i * 2654435761u + 12345u) & 0x7f7f7f7fu;   // (no 0xff byte: the refill differs everywhere)
+    pat[words] = (pat[words - 1] >> 16) ^ 1u;   // the spare word: the buffer's last 16-bit value with one bit turned
+    unsigned char* src = (unsigned char*)dm.up(pat.data(), pat.size());
+    unsigned char* buf = (unsigned char*)dm.up(pat.data(), pat.size());
+    unsigned char* tmp = (unsigned char*)dm.alloc<uint32_t>(pat.size());
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    auto copy = [](void* dst, const void* from, size_t count) { return hipMemcpyAsync(dst, from, count, hipMemcpyDeviceToDevice, nullptr); };
+    auto write = [&](int rep) -> hipError_t {
+        if (mode == 2 && rep == 3) return hipSuccess;
+        hipError_t e = copy(buf, src, n);
+        if (e == hipSuccess && mode == 1 && rep == 7) e = copy(buf + n - 2, src + 4 * words, 2);   // (the pattern's spare word)
+        if (e == hipSuccess && mode == 3 && (rep == 5 || rep == 6)) {
+            e = copy(buf + 4, src + 8, 4);
+            if (e == hipSuccess) e = copy(buf + 8, src + 4, 4);
+        }
+        return e;
+    };
+    auto advance = [&](int) -> hipError_t {
+        hipError_t e = copy(tmp, buf + 4, n - 4);
+        if (e == hipSuccess) e = copy(tmp + n - 4, buf, 4);
+        return e == hipSuccess ? copy(buf, tmp, n) : e;
+    };
+    int rc = OPD_OK;
+    if (mode <= 3) rc = launch_repeated(write, {{buf, n, 0xff}});
+    if (mode == 4) rc = launch_repeated(advance, {}, {{buf, n}});
+    *n_diff = g_rep_diff;
+    if (rc == OPD_OK && mode >= 4) {
+        const int with_restore = g_rep_diff;
+        HIPCHK(copy(buf, src, n));
+        g_rep_keep = 1;
+        rc = launch_repeated(advance, {}, {{buf, n}});
+        g_rep_keep = 0;
+        if (rc == OPD_OK && g_rep_diff != g_repeat - 1)
+            return fail(OPD_ESTATE, "repeat_selftest: without the restore " + std::to_string(g_rep_diff) + " repetitions differ, not all but the first");
+        if (mode == 4) g_rep_diff = with_restore;
+        *n_diff = g_rep_diff;
+    }
+    return rc;
+}
 
 // B per-frame tables [B][rows][cols] fp32 -> one device copy and a device array of B pointers into it (bias_ptrs / pos_ptrs)
 static const float* const* upload_frame_tables(DevMem& dm, const float* tables, int B, size_t rows, size_t cols, const float** first) {
@@ -64,12 +200,10 @@ TAPI int opd_test_conv_gemm(const uint16_t* x, const uint16_t* w, const float* b
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     p.relu = relu; p.bias_period = bias_period; p.out_f32 = out_f32; p.stem = stem;
     apply_conv_flags(p, g_conv_flags);
-    if (g_conv_flags & (1 << 12)) {   // the eight-wave kernel (kernels_w8.hip)
-        if (!opd_conv_w8_supported(p)) return fail(OPD_EINVAL, "conv_w8: shape outside the kernel's contract");
-        HIPCHK(opd_launch_conv_w8(p, nullptr));
-    } else {
-        HIPCHK(opd_launch_conv_gemm(p, nullptr));
-    }
+    const bool w8 = g_conv_flags & (1 << 12);   // the eight-wave kernel (kernels_w8.hip)
+    if (w8 && !opd_conv_w8_supported(p)) return fail(OPD_EINVAL, "conv_w8: shape outside the kernel's contract");
+    RCCHK(launch_repeated([&](int) { return w8 ? LAUNCHED(opd_launch_conv_w8(p, nullptr)) : LAUNCHED(opd_launch_conv_gemm(p, nullptr)); },
+                          {{p.out, MN * (out_f32 ? 4 : 2), 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     return down_out(out, p.out, MN, out_f32);
 }
@@ -99,7 +233,7 @@ TAPI int opd_test_conv_dual(const uint16_t* x, const uint16_t* w1, const uint16_
     p.zero16 = zeros<uint32_t>(dm, 8);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     apply_conv_flags(p, g_conv_flags);
-    HIPCHK(opd_launch_conv_gemm(p, nullptr));
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_conv_gemm(p, nullptr)); }, {{dout, MN * 2, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     return down(out, dout, MN);
 }
@@ -123,8 +257,12 @@ TAPI int opd_test_conv_splitk(const uint16_t* x, const uint16_t* w, const float*
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     p.out = slab;
     apply_conv_flags(p, g_conv_flags);
-    HIPCHK(opd_launch_conv_gemm(p, nullptr));
-    HIPCHK(opd_launch_reduce_act16(slab, splits, MN, dout, MN, relu ? 1 : 0, nullptr, g_test_dtype));
+    RCCHK(launch_repeated(
+        [&](int) {
+            const hipError_t e = LAUNCHED(opd_launch_conv_gemm(p, nullptr));
+            return e != hipSuccess ? e : LAUNCHED(opd_launch_reduce_act16(slab, splits, MN, dout, MN, relu ? 1 : 0, nullptr, g_test_dtype));
+        },
+        {{slab, (size_t)splits * MN * 4, 0xff}, {dout, MN * 2, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     return down(out16, dout, MN);
 }
@@ -232,8 +370,12 @@ TAPI int opd_test_gemm_splitk_ln(const uint16_t* x, const uint16_t* w, const flo
     uint16_t* dy16 = dm.alloc<uint16_t>(MN);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     p.out = slab;
-    HIPCHK(opd_launch_conv_gemm(p, nullptr));
-    HIPCHK(opd_launch_reduce_ln(slab, splits, MN, dres, dg, db, dy, dy16, M, nullptr, g_test_dtype));
+    RCCHK(launch_repeated(
+        [&](int) {
+            const hipError_t e = LAUNCHED(opd_launch_conv_gemm(p, nullptr));
+            return e != hipSuccess ? e : LAUNCHED(opd_launch_reduce_ln(slab, splits, MN, dres, dg, db, dy, dy16, M, nullptr, g_test_dtype));
+        },
+        {{slab, (size_t)splits * MN * 4, 0xff}, {dy, MN * 4, 0xff}, {dy16, MN * 2, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(y, dy, MN));
     return down(y16, dy16, MN);
@@ -255,7 +397,7 @@ TAPI int opd_test_gemm_ln(const uint16_t* x, const uint16_t* w, const float* bia
     p.y16 = dm.alloc<uint16_t>(MN);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     p.M = M; p.K = K; p.kloop = g_gemm_ln_kloop;
-    HIPCHK(opd_launch_gemm_ln(p, nullptr));
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_gemm_ln(p, nullptr)); }, {{p.y32, MN * 4, 0xff}, {p.y16, MN * 2, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(y, p.y32, MN));
     return down(y16, p.y16, MN);
@@ -281,7 +423,10 @@ TAPI int opd_test_gemm_ln_deep(const uint16_t* x, const uint16_t* w, const float
     p.yp16 = pos ? dm.alloc<uint16_t>(MN) : nullptr;
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     p.M = M; p.K = K; p.deep_k = 1;
-    HIPCHK(opd_launch_gemm_ln(p, nullptr));
+    const bool alias = p.y32 == res;   // (in place: the launch reads the residual stream it overwrites)
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_gemm_ln(p, nullptr)); },
+                          {{alias ? nullptr : p.y32, MN * 4, 0xff}, {p.y16, MN * 2, 0xff}, {p.yp16, MN * 2, 0xff}},
+                          {{alias ? p.y32 : nullptr, MN * 4}}));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(y, p.y32, MN));
     RCCHK(down(y16, p.y16, MN));
@@ -329,7 +474,11 @@ TAPI int opd_test_enc_ffn(const uint16_t* x, const uint16_t* w1, const float* b1
         for (int t = 0; t < tail; ++t) p.tail_col[t] = 256 * t;
     }
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_enc_ffn(p, nullptr));
+    const bool a32 = p.y32 == res, a16 = p.y16 == dx;   // (in place: the launch reads what it overwrites)
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_enc_ffn(p, nullptr)); },
+                          {{a32 ? nullptr : p.y32, MN * 4, 0xff}, {a16 ? nullptr : p.y16, MN * 2, 0xff}, {p.yp16, MN * 2, 0xff},
+                           {p.tail_out, (size_t)M * p.tail_ld * 2, 0xff}},
+                          {{a32 ? p.y32 : nullptr, MN * 4}, {a16 ? p.y16 : nullptr, MN * 2}}));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(y, p.y32, MN));
     RCCHK(down(y16, p.y16, MN));
@@ -352,8 +501,13 @@ TAPI int opd_test_gemm_k256(const uint16_t* x, const uint16_t* w, const float* b
     float* sum = slices > 1 ? dm.alloc<float>(MN) : nullptr;
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     p.M = M; p.N = N; p.ldx = K; p.ldw = K; p.slices = slices; p.bias_period = bias_period; p.relu = relu;
-    HIPCHK(opd_launch_gemm_k256(p, nullptr));
-    if (slices > 1) HIPCHK(opd_launch_reduce_ln(p.out32, slices, MN, nullptr, nullptr, nullptr, sum, nullptr, M, nullptr));
+    RCCHK(launch_repeated(
+        [&](int) {
+            const hipError_t e = LAUNCHED(opd_launch_gemm_k256(p, nullptr));
+            if (e != hipSuccess || slices == 1) return e;
+            return LAUNCHED(opd_launch_reduce_ln(p.out32, slices, MN, nullptr, nullptr, nullptr, sum, nullptr, M, nullptr));
+        },
+        {{p.out16, MN * 2, 0xff}, {p.out32, (size_t)slices * MN * 4, 0xff}, {sum, MN * 4, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     return slices > 1 ? down(out32, sum, MN) : down(out16, p.out16, MN);
 }
@@ -380,7 +534,7 @@ TAPI int opd_test_btail(const uint16_t* x1, const uint16_t* w1, const float* b1,
     p.b3 = C3 ? dm.up(b3, C3) : nullptr;
     p.z = C3 ? dm.alloc<uint16_t>(M * C3) : nullptr;
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_btail(p, nullptr));
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_btail(p, nullptr)); }, {{p.y, M * C2 * 2, 0xff}, {p.z, M * C3 * 2, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(y, p.y, M * C2));
     return C3 ? down(z, p.z, M * C3) : OPD_OK;
@@ -403,34 +557,11 @@ TAPI int opd_test_btail_repeat(const uint16_t* x1, const uint16_t* w1, const flo
     btail_weights(dm, p, C1, C3, w2, w3);
     p.b2 = dm.up(b2, C2); p.res = dm.up(res, M * C2); p.y = dm.alloc<uint16_t>(M * C2);
     p.b3 = dm.up(b3, C3); p.z = dm.alloc<uint16_t>(M * C3);
-    const size_t noise_bytes = (size_t)256 << 20;
-    unsigned char* noise = dm.alloc<unsigned char>(2 * noise_bytes);
-    std::vector<unsigned long long> h((size_t)reps * 2 * OPD_TAP_BLOCKS);
-    unsigned long long* sums = dm.alloc<unsigned long long>(h.size());
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    hipStream_t side = nullptr;
-    HIPCHK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-    auto launches = [&]() -> int {
-        for (int r = 0; r < reps; ++r) {
-            p.rev = r & 1;
-            (void)hipMemcpyAsync(noise + ((r & 1) ? noise_bytes : 0), noise + ((r & 1) ? 0 : noise_bytes), noise_bytes, hipMemcpyDeviceToDevice, side);
-            HIPCHK(hipMemsetAsync(p.y, 0xff, M * C2 * 2, nullptr));
-            HIPCHK(hipMemsetAsync(p.z, 0xff, M * C3 * 2, nullptr));
-            HIPCHK(opd_launch_btail(p, nullptr));
-            HIPCHK(opd_launch_checksum(p.y, M * C2 * 2, sums + (size_t)(2 * r) * OPD_TAP_BLOCKS, nullptr));
-            HIPCHK(opd_launch_checksum(p.z, M * C3 * 2, sums + (size_t)(2 * r + 1) * OPD_TAP_BLOCKS, nullptr));
-        }
-        HIPCHK(hipDeviceSynchronize());
-        return OPD_OK;
-    };
-    const int rc = launches();
-    (void)hipStreamDestroy(side);
-    RCCHK(rc);
-    RCCHK(down(h.data(), sums, h.size()));
-    int diff = 0;
-    for (int r = 1; r < reps; ++r)
-        if (memcmp(h.data() + (size_t)(2 * r) * OPD_TAP_BLOCKS, h.data(), 2 * OPD_TAP_BLOCKS * 8) != 0) ++diff;
-    *n_diff = diff;
+    // (the tile walk alternates between repetitions: the outputs do not depend on it, the timing of every tile does)
+    RCCHK(launch_repeated([&](int rep) { p.rev = rep & 1; return LAUNCHED(opd_launch_btail(p, nullptr)); }, {{p.y, M * C2 * 2, 0xff}, {p.z, M * C3 * 2, 0xff}}, {},
+                          reps));
+    *n_diff = g_rep_diff;
     return OPD_OK;
 }
 
@@ -454,7 +585,7 @@ TAPI int opd_test_btail_sc(const uint16_t* x1, const uint16_t* w1, const float* 
     p.b3 = dm.up(b3, C3);
     p.z = dm.alloc<uint16_t>(M * C3);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_btail(p, nullptr));
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_btail(p, nullptr)); }, {{p.y, M * C2 * 2, 0xff}, {p.z, M * C3 * 2, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(y, p.y, M * C2));
     return down(z, p.z, M * C3);
@@ -539,7 +670,7 @@ static int run_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v
     const size_t n = (size_t)B * Lq * attention_params(dm, p, q, k, v, B, heads, Lq, Lk, scale, key_valid, key_row);
     p.o = dm.alloc<uint16_t>(n);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_attention(p, nullptr));
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_attention(p, nullptr)); }, {{p.o, n * 2, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     return down(o, p.o, n);
 }
@@ -561,7 +692,7 @@ TAPI int opd_test_attention_split(const uint16_t* q, const uint16_t* k, const ui
     const size_t no = (size_t)splits * B * Lq * D, nm = (size_t)splits * B * Lq * heads * 2;
     p.part_o = dm.alloc<float>(no); p.part_ml = dm.alloc<float>(nm); p.splits = splits;
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_attention(p, nullptr));
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_attention(p, nullptr)); }, {{p.part_o, no * 4, 0xff}, {p.part_ml, nm * 4, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(part_o, p.part_o, no));
     return down(part_ml, p.part_ml, nm);
@@ -679,9 +810,13 @@ TAPI int opd_test_stem_pool_u8(const uint8_t* frames, const int32_t* valid_hw, c
     uint16_t* d1 = dm.alloc<uint16_t>(n);
     uint16_t* d2 = dm.alloc<uint16_t>(n);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_stem_pool_u8(df, dv, dw, db, d1, B, H, W, OH, OW, PH, PW, nullptr, g_test_dtype));
-    HIPCHK(opd_launch_preprocess_u8(df, dx, B, H, W, Hp, Wp, dv, nullptr, g_test_dtype));
-    HIPCHK(opd_launch_stem_pool(dx, dw, db, d2, B, Hp, Wp, OH, OW, PH, PW, nullptr, g_test_dtype));
+    RCCHK(launch_repeated(
+        [&](int) {
+            hipError_t e = LAUNCHED(opd_launch_stem_pool_u8(df, dv, dw, db, d1, B, H, W, OH, OW, PH, PW, nullptr, g_test_dtype));
+            if (e == hipSuccess) e = LAUNCHED(opd_launch_preprocess_u8(df, dx, B, H, W, Hp, Wp, dv, nullptr, g_test_dtype));
+            return e != hipSuccess ? e : LAUNCHED(opd_launch_stem_pool(dx, dw, db, d2, B, Hp, Wp, OH, OW, PH, PW, nullptr, g_test_dtype));
+        },
+        {{d1, n * 2, 0xff}, {d2, n * 2, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(out_fused, d1, n));
     return down(out_split, d2, n);
@@ -709,15 +844,20 @@ TAPI int opd_test_stem_reduce(const uint8_t* frames, const int32_t* valid_hw, co
     c.x = p2; c.w = red.w0; c.bias = red.b0; c.out = z2; c.zero16 = zeros<uint32_t>(dm, 8); c.relu = 1;
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     HIPCHK(hipMemsetAsync(z1, 0xff, n * 2, nullptr));   // (a pixel the fused launch forgets stays NaN)
-    if (u8) {
-        HIPCHK(opd_launch_stem_pool_u8(df, dv, dw, db, p1, B, H, W, OH, OW, PH, PW, nullptr, g_test_dtype, red));
-        HIPCHK(opd_launch_stem_pool_u8(df, dv, dw, db, p2, B, H, W, OH, OW, PH, PW, nullptr, g_test_dtype));
-    } else {
-        HIPCHK(opd_launch_preprocess_u8(df, dx, B, H, W, Hp, Wp, dv, nullptr, g_test_dtype));
-        HIPCHK(opd_launch_stem_pool(dx, dw, db, p1, B, Hp, Wp, OH, OW, PH, PW, nullptr, g_test_dtype, red));
-        HIPCHK(opd_launch_stem_pool(dx, dw, db, p2, B, Hp, Wp, OH, OW, PH, PW, nullptr, g_test_dtype));
-    }
-    HIPCHK(opd_launch_conv_gemm(c, nullptr));
+    RCCHK(launch_repeated(
+        [&](int) {
+            hipError_t e;
+            if (u8) {
+                e = LAUNCHED(opd_launch_stem_pool_u8(df, dv, dw, db, p1, B, H, W, OH, OW, PH, PW, nullptr, g_test_dtype, red));
+                if (e == hipSuccess) e = LAUNCHED(opd_launch_stem_pool_u8(df, dv, dw, db, p2, B, H, W, OH, OW, PH, PW, nullptr, g_test_dtype));
+            } else {
+                e = LAUNCHED(opd_launch_preprocess_u8(df, dx, B, H, W, Hp, Wp, dv, nullptr, g_test_dtype));
+                if (e == hipSuccess) e = LAUNCHED(opd_launch_stem_pool(dx, dw, db, p1, B, Hp, Wp, OH, OW, PH, PW, nullptr, g_test_dtype, red));
+                if (e == hipSuccess) e = LAUNCHED(opd_launch_stem_pool(dx, dw, db, p2, B, Hp, Wp, OH, OW, PH, PW, nullptr, g_test_dtype));
+            }
+            return e != hipSuccess ? e : LAUNCHED(opd_launch_conv_gemm(c, nullptr));
+        },
+        {{p1, n * 2, 0xff}, {z1, n * 2, 0xff}, {p2, n * 2, 0xff}, {z2, n * 2, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(pool_fused, p1, n));
     RCCHK(down(z_fused, z1, n));
@@ -771,9 +911,15 @@ static void heads_params(DevMem& dm, HeadParams& p, const float* hs, const float
 }
 static int run_heads(DevMem& dm, const HeadParams& p, float* logits, float* boxes) {
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(heads_split16(p.ncls) ? opd_launch_heads2(p, nullptr) : opd_launch_heads(p, nullptr));
-    HIPCHK(hipDeviceSynchronize());
     const size_t all = (size_t)p.rows + g_test_heads_spare;
+    // (with spare rows the outputs start as the caller's arrays, which only a restore brings back; else they are merely allocated)
+    const bool spare = g_test_heads_spare > 0;
+    std::vector<RepOut> outs;
+    std::vector<RepInPlace> kept;
+    if (spare) kept = {{p.logits, all * p.ncls * 4}, {p.boxes, all * 16}};
+    else outs = {{p.logits, all * p.ncls * 4, 0xff}, {p.boxes, all * 16, 0xff}};
+    RCCHK(launch_repeated([&](int) { return heads_split16(p.ncls) ? LAUNCHED(opd_launch_heads2(p, nullptr)) : LAUNCHED(opd_launch_heads(p, nullptr)); }, outs, kept));
+    HIPCHK(hipDeviceSynchronize());
     RCCHK(down(logits, p.logits, all * p.ncls));
     return down(boxes, p.boxes, all * 4);
 }
@@ -852,7 +998,10 @@ TAPI int opd_test_dec_qkv(const float* h_in, const float* partials, int nsplit, 
     p.q16 = dm.alloc<uint16_t>(n); p.k16 = zeros<uint16_t>(dm, nv); p.vT = zeros<uint16_t>(dm, nv);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     p.M = M; p.Q = Q;
-    HIPCHK(opd_launch_dec_qkv(p, nullptr));
+    // (without the prologue the launch reads h_out; the padding keys of k16 / vT must keep the zero fill)
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_dec_qkv(p, nullptr)); },
+                          {{partials ? p.h_out : nullptr, n * 4, 0xff}, {p.q16, n * 2, 0xff}, {p.k16, nv * 2, 0}, {p.vT, nv * 2, 0}},
+                          {{partials ? nullptr : p.h_out, n * 4}}));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(h_out, p.h_out, n));
     RCCHK(down(q16, p.q16, n));
@@ -871,7 +1020,7 @@ TAPI int opd_test_dec_self(const uint16_t* q16, const uint16_t* k16, const uint1
     p.wo = up_frag(dm, wo, 256, 256); p.wq = up_frag(dm, wq, 256, 256);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     p.B = B; p.Q = Q; p.scale = scale; p.qc_bf16 = (g_test_dtype == OPD_DT_BF16);
-    HIPCHK(opd_launch_dec_self(p, nullptr));
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_dec_self(p, nullptr)); }, {{p.qc16, n * 2, 0xff}}, {{p.h, n * 4}}));
     HIPCHK(hipDeviceSynchronize());
     RCCHK(down(h, p.h, n));
     return down(qc16, p.qc16, n);
@@ -886,7 +1035,7 @@ TAPI int opd_test_dec_cross_out(const float* part_o, const float* part_ml, int s
     p.h = dm.alloc<float>(n); p.bo = dm.up(bo, 256); p.ln_g = dm.up(ln_g, 256); p.ln_b = dm.up(ln_b, 256); p.M = M;
     p.wo = up_frag(dm, wo, 256, 256);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_dec_cross_out(p, nullptr));
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_dec_cross_out(p, nullptr)); }, {{p.h, n * 4, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     return down(h, p.h, n);
 }
@@ -898,7 +1047,7 @@ TAPI int opd_test_dec_ffn(const float* h, const float* w1, const float* b1, cons
     p.h = dm.up(h, n); p.b1 = dm.up(b1, (size_t)F); p.partials = dm.alloc<float>(np); p.M = M; p.F = F;
     p.w1 = up_frag(dm, w1, F, 256); p.w2 = up_frag(dm, w2, 256, F);
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
-    HIPCHK(opd_launch_dec_ffn(p, nullptr));
+    RCCHK(launch_repeated([&](int) { return LAUNCHED(opd_launch_dec_ffn(p, nullptr)); }, {{p.partials, np * 4, 0xff}}));
     HIPCHK(hipDeviceSynchronize());
     return down(partials, p.partials, np);
 }

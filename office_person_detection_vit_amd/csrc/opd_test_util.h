@@ -3,6 +3,7 @@
 #pragma once
 #include <string.h>
 
+#include <functional>
 #include <vector>
 
 #include "opd_crop.h"
@@ -50,6 +51,33 @@ inline void* alloc_out(DevMem& dm, size_t count, int f32) { return f32 ? (void*)
 inline int down_out(void* host, const void* dev, size_t count, int f32) {
     return f32 ? down((float*)host, (const float*)dev, count) : down((uint16_t*)host, (const uint16_t*)dev, count);
 }
+
+// The race screen of the kernel hooks.  A kernel that orders its LDS-DMA traffic by counted waits and raw barriers can carry a wait that is one
+// too permissive and still pass every reference check as long as the data happens to land in time; what shows it is the same launch many times
+// under varying memory latency with bit-identical outputs required.  The hooks of those kernels in opd_test_api.cpp therefore launch through
+// launch_repeated: `launch(rep)` issues the hook's launch (or launches) on the null stream, `outs` are the buffers it only writes (`fill`: the
+// byte the hook initialises them with, 0xff for a buffer it merely allocates, so that a store that was skipped shows), `inplace` the buffers a
+// launch both reads and overwrites.  A null or empty buffer is ignored.
+//   repeat count off (the default): exactly launch(0), nothing else.
+//   reps >= 2 (opd_test_set_repeat, or the `reps` argument): a pristine device copy of every in-place buffer is taken; every repetition restores
+//     them, refills the outputs, starts a 256-MiB device-to-device copy on a second, non-blocking stream (so that DMA latencies vary between
+//     repetitions), launches, and takes opd_launch_checksum of every buffer into a slot block of its own.  After ONE device synchronisation the
+//     repetitions whose blocks differ from repetition 0's are counted; opd_test_repeat_result reports (launches, n_diff) of the last call.
+// The buffers are left as the last repetition wrote them, so the hook copies back and its test compares with the reference as ever.  A buffer
+// whose size is no multiple of 4 is refused under repetition: the checksum sums whole 32-bit words and would pass over its tail.
+// Inside `launch`, every launcher call is written LAUNCHED(opd_launch_x(...)): a failure is then reported under that call's text, as HIPCHK
+// reports it (a refused launch names its launcher in opd_last_error).
+extern __attribute__((visibility("hidden"))) const char* g_launch_expr;
+inline hipError_t launched(const char* expr, hipError_t e) {
+    if (e != hipSuccess) g_launch_expr = expr;
+    return e;
+}
+#define LAUNCHED(expr) opd::launched(#expr, (expr))
+struct RepOut { void* ptr; size_t bytes; int fill; };
+struct RepInPlace { void* ptr; size_t bytes; };
+constexpr int REPEAT_DEFAULT = -1;   // `reps`: what opd_test_set_repeat set
+int launch_repeated(const std::function<hipError_t(int)>& launch, const std::vector<RepOut>& outs, const std::vector<RepInPlace>& inplace = {},
+                    int reps = REPEAT_DEFAULT);
 
 // `warm` untimed launches, then `iters` launches back to back on the null stream between two events: *us = microseconds per launch.
 // `launch` returns a hipError_t; the events are destroyed on every path.

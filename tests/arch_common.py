@@ -60,6 +60,32 @@ def v_frag(v, pad=0.0):
     return x.transpose(0, 5, 1, 6, 3, 7, 2, 4).reshape(B, 8, 4, 2, 64, 8)   # -> [b][h][kb][dt][g][li][half][j4]
 
 
+# ---- race screen (csrc/opd_test_util.h: launch_repeated) ---------------------------------------------------------------------------------
+RACE_REPS = 40   # the project's figure (test_btail_repeated_launches_are_bit_identical), like the 256-MiB noise copy per repetition
+
+
+def repeat_result(lib):
+    """(launches, n_diff) of the last hook call; the read clears the record."""
+    launches, n_diff = C.c_int(-1), C.c_int(-1)
+    _capi.check(lib.opd_test_repeat_result(C.byref(launches), C.byref(n_diff)), "opd_test_repeat_result")
+    return launches.value, n_diff.value
+
+
+def race_screened(lib, call, *args, **kwargs):
+    """`call(*args, **kwargs)` -- a case builder or a test body that calls exactly ONE kernel hook -- with that hook's launch repeated RACE_REPS
+    times under memory noise: every repetition must leave the same bits in every output of the hook.  Returns what `call` returns (made from
+    the last repetition's outputs), so the caller goes on to compare with its reference."""
+    lib.opd_test_set_repeat(RACE_REPS)
+    try:
+        out = call(*args, **kwargs)
+        launches, n_diff = repeat_result(lib)
+    finally:
+        lib.opd_test_set_repeat(0)
+    assert launches == RACE_REPS, f"{launches} launches: the hook does not launch through launch_repeated, or more than one hook was called"
+    assert n_diff == 0, f"{n_diff} of {RACE_REPS - 1} repetitions differ from the first"
+    return out
+
+
 def _ln_params(rng):
     return (1.0 + 0.1 * rng.standard_normal(D)).astype(np.float32), (0.1 * rng.standard_normal(D)).astype(np.float32)
 
