@@ -597,6 +597,28 @@ OPD_API int opd_track_update(opd_track* t, const float* boxes_xywh, const float*
 /* The live tracks in creation order: out [capacity], *count = how many there are (OPD_EINVAL when capacity is smaller; out may be NULL
  * with capacity 0 to ask for the count).  Waits for the last update's second launch. */
 OPD_API int opd_track_get(opd_track* t, opd_track_rec* out, int capacity, int* count);
+
+/* Detection and tracking in ONE call with ONE host wait: the frame-list detect call with the suppression of
+ * opd_detr_set_nms, the feature stage of `feature_kind`, and one tracker update per frame, frame b into trackers[b] (B distinct handles:
+ * one camera each).  The kept records and their feature rows enter the tracker where they lie on the device; no feature row is returned.
+ * Records and counts come back as from opd_detr_detect_frames with the suppression on.  track_ids [B][num_queries]: the id of kept record
+ * i of frame b at [b * num_queries + i], -1 where opd_track_update writes -1; entries at i >= counts[b] are not written.  n_featured [B]:
+ * how many of the frame's kept records entered with a feature row: counts[b] for ENCODER and COLOR, 0 for NONE, for REID the number that
+ * got one of the `slots` crop slots (handed out in frame, score order; a record beyond them enters with has_feature = 0).  `r` and `slots`
+ * are read for REID only.  OPD_EINVAL before any device work: a null handle or output; the suppression off on `m`, or on for another label;
+ * one tracker named twice; a handle on another device; a tracker with max_dets < num_queries, or with a feature_dim other than the kind's
+ * row width (256 for ENCODER and COLOR, the Re-ID model's for REID); REID with r == NULL or slots outside 1 .. max_crops; ENCODER or COLOR
+ * with d_model != 256; COLOR with a frame edge above 4096; an unknown kind; and what opd_detr_detect_frames refuses.  A tracker that would
+ * exceed max_tracks behaves as under opd_track_update: records and counts are delivered, its ids are all -1, the frame counts as one
+ * without detections, the call returns OPD_EINVAL, and the other trackers of the batch are committed.  Afterwards opd_track_info reports
+ * last_waits = 0 (the wait was the detector's) and last_launches = the ingest, predict and commit launches that ran. */
+#define OPD_TRACK_FEAT_NONE 0    /* motion only: the tracker sees features == NULL */
+#define OPD_TRACK_FEAT_ENCODER 1 /* the ROI rows of opd_detr_detect_frames_features (D = 256) */
+#define OPD_TRACK_FEAT_COLOR 2   /* the colour-histogram rows of opd_detr_detect_frames_color (D = 256) */
+#define OPD_TRACK_FEAT_REID 3    /* the rows of `r` (D = its feature_dim), planned as opd_detr_detect_frames_reid plans them */
+OPD_API int opd_detr_detect_frames_track(opd_detr* m, opd_reid* r, opd_track* const* trackers, const uint8_t* const* frames, int B, int h,
+                                         int w, int H, int W, float threshold, int label, int feature_kind, int slots, opd_det* out,
+                                         int32_t* counts, int32_t* track_ids, int32_t* n_featured);
 /* The solver of the association on its own (host only): cost [rows][cols] row-major -> row_to_col [rows], -1 for a row left alone;
  * min(rows, cols) pairs of smallest total cost, as scipy.optimize.linear_sum_assignment. */
 OPD_API int opd_assign(const double* cost, int rows, int cols, int32_t* row_to_col);

@@ -23,6 +23,7 @@ OPD_FLAG_NO_GRAPH = 1
 OPD_FLAG_MULTI_STREAM = 2
 OPD_REID_MODEL_CLIP = 0
 OPD_REID_MODEL_OSNET = 1
+OPD_TRACK_FEAT_NONE, OPD_TRACK_FEAT_ENCODER, OPD_TRACK_FEAT_COLOR, OPD_TRACK_FEAT_REID = 0, 1, 2, 3   # feature_kind of opd_detr_detect_frames_track
 OPD_FLAG_BF16 = 4
 OPD_FLOOR_HOMOGRAPHY, OPD_FLOOR_PWA, OPD_FLOOR_TPS = 0, 1, 2
 OPD_FLOOR_VALID, OPD_FLOOR_WITHIN, OPD_FLOOR_EXTRAPOLATED = 1, 2, 4
@@ -210,6 +211,8 @@ API = {
     "opd_track_info": (C.c_int, [C.c_void_p, C.POINTER(OpdTrackStatus)]),
     "opd_track_update": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
     "opd_track_get": (C.c_int, [C.c_void_p, C.POINTER(OpdTrackRec), C.c_int, C.POINTER(C.c_int)]),
+    "opd_detr_detect_frames_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int, C.c_int,
+                                                C.POINTER(OpdDet), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "opd_assign": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "opd_lwt_create": (C.c_int, [C.POINTER(OpdLwtConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "opd_lwt_destroy": (None, [C.c_void_p]),
@@ -343,6 +346,8 @@ TEST_API = {
     # tracker hooks (csrc/opd_track_test_api.cpp)
     "opd_track_test_matrices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "opd_track_test_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    # device, records, n, Q, D, frame, rows_kind, rows, n_rows, slot_map, n_person, slots, capacity, boxes, foot, has, feat, n_out
+    "opd_track_test_ingest": (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     # hybrid-tracker hook (csrc/opd_lwt_test_api.cpp): handle, next_xy, status, records, capacity, count
     "opd_test_lwt_interpolate_scripted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OpdLwtRec), C.c_int, C.POINTER(C.c_int)]),
 }

@@ -1,4 +1,4 @@
-// kernels_track.hip — the two launches of one `Tracker.update` (src/tracking/tracker.py, track.py, kalman_filter.py, similarity.py of the
+// kernels_track.hip — the launches of one `Tracker.update` (src/tracking/tracker.py, track.py, kalman_filter.py, similarity.py of the
 // reference).  All state is float32 as the reference's numpy arrays are; the file is built with -ffp-contract=off, so every expression
 // below is evaluated operation by operation in the order written (tests/track_common.py restates the same order in numpy).
 //
@@ -17,6 +17,9 @@
 //         feature by one wave: lane l adds elements l, l + 64, ... in ascending order, then the butterfly; which wave takes which
 //         detection changes no bit.  app = float32(1.0 - double(clip(dot, -1, 1))), comb as `_compute_cost_matrix` in double.
 //   track_commit_kernel        one workgroup per matched or new track: Kalman (thread 0), feature ring (all threads).
+//   track_ingest_kernel        the fused detect-and-track call only: one wave per record slot of a frame turns the kept records, where the
+//       suppression kernel left them, into the staging image the two launches above read (boxes xywh, foot points, flags, feature rows) and
+//       leaves the kept count on the device for the predict launch.  Plain loads and stores: no LDS-DMA, no counted waits.
 #include <hip/hip_runtime.h>
 
 #include "opd_kprims.h"
@@ -76,7 +79,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_predict_cost_kernel(const
     __shared__ float wsum[TRACK_THREADS / 64];
     __shared__ float pos[2];
     const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int slot = p.slots[t], D = p.D, N = p.d.n;
+    const int slot = p.slots[t], D = p.D, N = p.n_dev ? *p.n_dev : p.d.n;   // (the fused call: the count is the ingest launch's, at most Q <= TRACK_MAX_DETS)
     if (tid == 0) {
         float x[4], P[16];
         for (int k = 0; k < 4; ++k) x[k] = p.s.x[4 * slot + k];
@@ -204,7 +207,66 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_commit_kernel(const Track
     }
 }
 
+// One workgroup of one wave per record slot of a frame.  A record is 32 bytes and a row at most 8 KB: the launch is bound by its latency, not by
+// bandwidth, so the geometry is many small workgroups that each finish in one round trip (64 lanes x 16 bytes = a 256-float row in one load each)
+// instead of few large ones that loop.  No LDS, no barrier: the slot search ends in a wave-wide maximum.
+__global__ __launch_bounds__(TRACK_INGEST_THREADS) void track_ingest_kernel(const TrackIngestParams p) {
+    const int i = blockIdx.x, lane = threadIdx.x, D = p.D;
+    int n = *p.count;
+    n = n < 0 ? 0 : (n > p.Q ? p.Q : n);
+    if (i == 0 && lane == 0) *p.n_out = n;
+    if (i >= n) return;   // (the whole workgroup)
+    const opd_det r = p.records[i];
+    const float* src = nullptr;
+    if (p.rows_kind == TRACK_ROWS_BY_QUERY) {
+        if ((unsigned)r.query_index < (unsigned)p.Q) src = p.rows + ((size_t)p.frame * p.Q + r.query_index) * D;
+    } else if (p.rows_kind == TRACK_ROWS_BY_SLOT) {
+        int filled = *p.n_person;
+        filled = filled < p.slots ? filled : p.slots;
+        const int want = p.frame * p.Q + r.query_index;
+        int k = -1;
+        if ((unsigned)r.query_index < (unsigned)p.Q)
+            for (int s = lane; s < filled; s += TRACK_INGEST_THREADS)
+                if (p.slot_map[s] == want) k = s;   // (a query index names one record of a frame at most)
+        for (int o = 32; o > 0; o >>= 1) {
+            const int other = __shfl_xor(k, o);
+            k = other > k ? other : k;
+        }
+        if (k >= 0) src = p.rows + (size_t)k * D;
+    }
+    if (lane == 0) {
+        // the values detector.py::_postprocess_batch and HipTracker.update hand to opd_track_update: differences and sums in double, rounded once
+        const double bw = (double)r.x2 - (double)r.x1, bh = (double)r.y2 - (double)r.y1;
+        p.boxes[4 * i] = r.x1;
+        p.boxes[4 * i + 1] = r.y1;
+        p.boxes[4 * i + 2] = (float)bw;
+        p.boxes[4 * i + 3] = (float)bh;
+        p.foot[2 * i] = (float)((double)r.x1 + bw / 2);
+        p.foot[2 * i + 1] = (float)((double)r.y1 + bh);
+        p.has[i] = src != nullptr;
+    }
+    if (src == nullptr) return;
+    float* dst = p.feat + (size_t)i * D;
+    if ((D & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        float4* d4 = reinterpret_cast<float4*>(dst);
+        for (int d = lane; d < D / 4; d += TRACK_INGEST_THREADS) d4[d] = s4[d];
+    } else {
+        for (int d = lane; d < D; d += TRACK_INGEST_THREADS) dst[d] = src[d];
+    }
+}
+
 }  // namespace
+
+hipError_t opd_launch_track_ingest(const TrackIngestParams& p, hipStream_t stream) {
+    if (p.Q < 1 || p.Q > TRACK_MAX_DETS || p.D < 1 || p.D > TRACK_MAX_DIM || p.frame < 0 || p.slots < 0) return hipErrorInvalidValue;
+    if (p.rows_kind != TRACK_ROWS_NONE && p.rows_kind != TRACK_ROWS_BY_QUERY && p.rows_kind != TRACK_ROWS_BY_SLOT) return hipErrorInvalidValue;
+    if (!p.records || !p.count || !p.boxes || !p.foot || !p.has || !p.n_out) return hipErrorInvalidValue;
+    if (p.rows_kind != TRACK_ROWS_NONE && (!p.rows || !p.feat)) return hipErrorInvalidValue;
+    if (p.rows_kind == TRACK_ROWS_BY_SLOT && (!p.slot_map || !p.n_person)) return hipErrorInvalidValue;
+    OPD_LAUNCH(track_ingest_kernel, dim3(p.Q), dim3(TRACK_INGEST_THREADS), 0, stream, p);
+    return hipGetLastError();
+}
 
 hipError_t opd_launch_track_predict_cost(const TrackPredictParams& p, hipStream_t stream) {
     if (p.T <= 0 || p.T > TRACK_MAX_TRACKS || p.d.n < 0 || p.d.n > TRACK_MAX_DETS || p.D < 1 || p.D > TRACK_MAX_DIM) return hipErrorInvalidValue;

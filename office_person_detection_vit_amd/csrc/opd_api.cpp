@@ -10,6 +10,7 @@
 #include "opd_nms.h"
 #include "opd_reid.h"
 #include "opd_tile.h"
+#include "opd_track.h"
 
 namespace opd {
 
@@ -202,6 +203,26 @@ static int fetch_records(opd_detr* m, opd_det* out, int32_t* counts, int mem_kin
     return OPD_OK;
 }
 
+// The tracker half of a fused detect-and-track call (opd_track.h), around the one wait of fetch_records.  Before it: every tracker's ingest and
+// predict / cost launches on m->stream, behind the feature stage.  After it: association and commit per tracker; a tracker out of slots does not
+// keep the others from being committed, and its error is the call's.
+static int enqueue_trackers(opd_detr* m, const RecordSink& s, const TrackFeatureSource& src) {
+    const int B = m->last_B, Q = m->arch.queries;
+    for (int b = 0; b < B; ++b) RCCHK(track_fused_enqueue(s.trackers[b], m->stream, m->d_records + (size_t)b * Q, m->d_counts + b, Q, b, src));
+    return OPD_OK;
+}
+static int finish_trackers(opd_detr* m, const RecordSink& s, bool with_features) {
+    const int B = m->last_B, Q = m->arch.queries;
+    int rc = OPD_OK;
+    std::string first;
+    for (int b = 0; b < B; ++b) {
+        const int n = std::max(0, std::min(s.counts[b], Q));
+        const int one = track_fused_finish(s.trackers[b], s.out + (size_t)b * Q, n, with_features, s.track_ids + (size_t)b * Q, "opd_detr_detect_frames_track");
+        if (one != OPD_OK && rc == OPD_OK) { rc = one; first = g_err; }
+    }
+    return rc == OPD_OK ? OPD_OK : fail(rc, first);
+}
+
 // The back half, on the outputs of the last forward (opd_detr_postprocess enters here): post-process, feature kernel, the sink's way of handing
 // the records over.  (h, w): the source's camera resolution (0: none); d_camera: its frames on the device at that resolution (FEAT_COLOR).
 static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera) {
@@ -227,9 +248,24 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
     if (s.feature == FEAT_REID) {   // select, plan and the Re-ID forward behind the post-process; the rows come back behind the records, before the one wait
         ReidFusedCall call(s.reid);
         RCCHK(call.enqueue(m->stream, m->d_records, m->d_counts, d_camera, B, Q, h, w, s.label, s.slots));
+        if (s.trackers) {   // the rows stay where the forward left them; the slot list alone comes back
+            call.with_rows = false;
+            RCCHK(enqueue_trackers(m, s, {TRACK_ROWS_BY_SLOT, reid_feature_dim(s.reid), call.dev_rows(), call.dev_slot_map(), call.dev_n_person(), s.slots}));
+        }
         RCCHK(fetch_records(m, s.out, s.counts, s.mem_kind, nullptr, nullptr, s.label, &call));
+        if (s.trackers) {
+            call.slots_per_frame(B, Q, s.n_featured);
+            return finish_trackers(m, s, true);
+        }
         call.deliver(s.features, s.slot_map, s.n_person);
         return OPD_OK;
+    }
+    if (s.trackers) {
+        const bool rows = s.feature != FEAT_NONE;
+        RCCHK(enqueue_trackers(m, s, {rows ? TRACK_ROWS_BY_QUERY : TRACK_ROWS_NONE, m->arch.d_model, rows ? m->d_feat_all : nullptr, nullptr, nullptr, 0}));
+        RCCHK(fetch_records(m, s.out, s.counts, s.mem_kind));
+        for (int b = 0; b < B; ++b) s.n_featured[b] = rows ? std::max(0, std::min(s.counts[b], Q)) : 0;
+        return finish_trackers(m, s, rows);
     }
     if (s.wait == WAIT_NONE) return OPD_OK;
     if (s.wait == WAIT_BLOCKING) return fetch_records(m, s.out, s.counts, s.mem_kind, s.features, s.fmap ? s.fmap_out : nullptr, s.label);   // records, counts and feature rows: one copy, one wait
@@ -740,6 +776,47 @@ int opd_detr_detect_frames_reid(opd_detr* m, opd_reid* r, const uint8_t* const* 
         return fail(OPD_EINVAL, "opd_detr_detect_frames_reid: source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
     HIPCHK(hipSetDevice(m->device));
     RecordSink sink{threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_REID, label, features, nullptr, nullptr, r, slots, slot_map, n_person};
+    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr, sink);
+}); }
+
+// The tracking twin: same upload, forward, post-process with suppression and feature stage; then, still before the one wait, every
+// tracker's ingest launch reads its frame's kept records and feature rows where they lie and its predict / cost launch follows, so that the wait
+// delivers records and cost matrices together.  Association and the commit launch (on the tracker's own stream, not waited for) follow it.
+int opd_detr_detect_frames_track(opd_detr* m, opd_reid* r, opd_track* const* trackers, const uint8_t* const* frames, int B, int h, int w, int H, int W,
+                                 float threshold, int label, int feature_kind, int slots, opd_det* out, int32_t* counts, int32_t* track_ids,
+                                 int32_t* n_featured) { return api_call("opd_detr_detect_frames_track", [&]() -> int {
+    const std::string me = "opd_detr_detect_frames_track";
+    // what needs no handle first, so that a null handle is the last thing reported without one
+    if (!trackers || !frames || !out || !counts || !track_ids || !n_featured) return fail(OPD_EINVAL, me + ": null argument (tracker list, frame list or an output)");
+    if (feature_kind != OPD_TRACK_FEAT_NONE && feature_kind != OPD_TRACK_FEAT_ENCODER && feature_kind != OPD_TRACK_FEAT_COLOR && feature_kind != OPD_TRACK_FEAT_REID)
+        return fail(OPD_EINVAL, me + ": unknown feature_kind " + std::to_string(feature_kind));
+    if (feature_kind == OPD_TRACK_FEAT_REID && !r) return fail(OPD_EINVAL, me + ": feature_kind OPD_TRACK_FEAT_REID with a null Re-ID handle");
+    if (h < 1 || w < 1 || (size_t)h * w > (size_t)1 << 26) return fail(OPD_EINVAL, me + ": source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
+    if (feature_kind == OPD_TRACK_FEAT_COLOR && (h > OPD_COLOR_MAX_EDGE || w > OPD_COLOR_MAX_EDGE))
+        return fail(OPD_EINVAL, me + ": frames of " + std::to_string(h) + " x " + std::to_string(w) + " are outside the 4096 x 4096 the exact integer sums of the colour histogram are sized for");
+    RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, true, me));
+    if (m->nms_threshold < 0.f)
+        return fail(OPD_EINVAL, me + ": opd_detr_set_nms is off on this handle; a tracker takes the kept records of a frame, which only the suppression on the device leaves there");
+    if (m->nms_label != label)
+        return fail(OPD_EINVAL, me + ": opd_detr_set_nms keeps label " + std::to_string(m->nms_label) + ", the call asks for label " + std::to_string(label));
+    int dim = 0;
+    if (feature_kind == OPD_TRACK_FEAT_REID) {
+        RCCHK(reid_fused_check(r, m->device, slots, me.c_str()));
+        dim = reid_feature_dim(r);
+    } else if (feature_kind != OPD_TRACK_FEAT_NONE) {
+        if (m->arch.d_model != OPD_COLOR_DIM) return fail(OPD_EINVAL, me + ": the feature area of the handle and both kernels that fill it are sized for d_model = 256");
+        dim = OPD_COLOR_DIM;
+    }
+    for (int b = 0; b < B; ++b) {
+        RCCHK(track_fused_check(trackers[b], m->device, m->arch.queries, dim, me.c_str()));
+        for (int a = 0; a < b; ++a)
+            if (trackers[a] == trackers[b]) return fail(OPD_EINVAL, me + ": frames " + std::to_string(a) + " and " + std::to_string(b) + " name the same tracker; a tracker takes one frame per call");
+    }
+    HIPCHK(hipSetDevice(m->device));
+    if (feature_kind == OPD_TRACK_FEAT_COLOR && !m->d_color_acc) RCCHK(dalloc(m, &m->d_color_acc, (size_t)m->cfg.max_batch * m->arch.queries * OPD_COLOR_ACC_WORDS, false));
+    const int feature = feature_kind == OPD_TRACK_FEAT_ENCODER ? FEAT_ROI : feature_kind == OPD_TRACK_FEAT_COLOR ? FEAT_COLOR : feature_kind == OPD_TRACK_FEAT_REID ? FEAT_REID : FEAT_NONE;
+    RecordSink sink{threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, feature, label, nullptr, nullptr, nullptr, feature == FEAT_REID ? r : nullptr, slots, nullptr, nullptr,
+                    trackers, track_ids, n_featured};
     return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr, sink);
 }); }
 

@@ -429,6 +429,9 @@ struct RecordSink {
     opd_reid* reid;               // FEAT_REID: the Re-ID handle; `features` is then [slots][feature_dim], one row per slot_map[k] = frame * queries + query_index,
     int slots;                    // k < min(*n_person, slots) (host; WAIT_BLOCKING)
     int32_t* slot_map; int32_t* n_person;
+    struct opd_track* const* trackers;   // non-null (opd_detr_detect_frames_track): frame b's kept records and feature rows enter trackers[b] where they lie; the feature
+    int32_t* track_ids;                  // stage runs but its rows are not downloaded (`features`, `slot_map`, `n_person` are null).  track_ids [B][queries], n_featured [B]
+    int32_t* n_featured;
 };
 int check_shape(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W);
 int detect_pipeline(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, const RecordSink& sink);

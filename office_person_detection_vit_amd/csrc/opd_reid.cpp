@@ -267,7 +267,7 @@ int ReidFusedCall::enqueue(hipStream_t s, const opd_det* records, const int32_t*
 int ReidFusedCall::copy_back(hipStream_t s) {
     const int C = r->cfg.max_crops, E = r->model->feature_dim();
     const size_t fb = (size_t)slots * E * 4;
-    HIPCHK(hipMemcpyAsync(r->up.host, r->model->features(), fb, hipMemcpyDeviceToHost, s));
+    if (with_rows) HIPCHK(hipMemcpyAsync(r->up.host, r->model->features(), fb, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(r->up.host + fb, r->up.dev + fused_sel_off(r), 4 * (2 * (size_t)C + 1), hipMemcpyDeviceToHost, s));
     return OPD_OK;
 }
@@ -279,6 +279,21 @@ void ReidFusedCall::deliver(float* features, int32_t* slot_map, int32_t* n_perso
     *n_person = np;
     memcpy(features, r->up.host, (size_t)n * E * 4);
     memcpy(slot_map, sel, (size_t)n * 4);
+}
+
+const float* ReidFusedCall::dev_rows() const { return r->model->features(); }
+const int32_t* ReidFusedCall::dev_slot_map() const { return reinterpret_cast<const int32_t*>(r->up.dev + fused_sel_off(r)); }
+const int32_t* ReidFusedCall::dev_n_person() const { return dev_slot_map() + 2 * (size_t)r->cfg.max_crops; }
+
+void ReidFusedCall::slots_per_frame(int B, int Q, int32_t* out) const {
+    const int C = r->cfg.max_crops, E = r->model->feature_dim();
+    const int32_t* sel = reinterpret_cast<const int32_t*>(r->up.host + (size_t)slots * E * 4);
+    const int n = std::min(sel[2 * C], slots);
+    for (int b = 0; b < B; ++b) out[b] = 0;
+    for (int k = 0; k < n; ++k) {
+        const int f = sel[C + k] / Q;   // (rec[k] = frame * Q + record index)
+        if (f >= 0 && f < B) ++out[f];
+    }
 }
 
 // test hook body (opd_reid_test_api.cpp): stage + pre-process only, the model's image of each crop back to the host

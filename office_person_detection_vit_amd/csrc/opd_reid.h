@@ -57,7 +57,7 @@ struct ReidModel {
 //              plan the crops of the first `slots` records labelled `label` into the handle's staging buffer, read in place from `frames`
 //              ([B][h][w][3] on the device); an event; the forward of bucket_of(slots) crops on the handle's own stream through its graph
 //              cache; an event back, which `s` waits for
-//   copy_back  on `s`: [slots][feature_dim] rows, the slot map and the person count into the handle's page-locked side
+//   copy_back  on `s`: [slots][feature_dim] rows (unless with_rows is off), the slot map and the person count into the handle's page-locked side
 //   deliver    after the caller's wait on `s`: rows and slot map of k < min(n_person, slots) into the caller's arrays
 int reid_fused_check(const opd_reid* r, int device, int slots, const char* who);
 int reid_feature_dim(const opd_reid* r);
@@ -69,6 +69,13 @@ struct ReidFusedCall {
     int enqueue(hipStream_t s, const opd_det* records, const int32_t* counts, const uint8_t* frames, int B, int Q, int h, int w, int label, int slots);
     int copy_back(hipStream_t s);
     void deliver(float* features, int32_t* slot_map, int32_t* n_person) const;
+    // the fused detect-and-track call: the rows stay on the device (copy_back then brings the slot list alone); where the rows, the slot map
+    // ([slots], filled up to min(*n_person, slots)) and the person count lie there; after the wait, how many slots each of the B frames got
+    bool with_rows = true;
+    const float* dev_rows() const;
+    const int32_t* dev_slot_map() const;
+    const int32_t* dev_n_person() const;
+    void slots_per_frame(int B, int Q, int32_t* out) const;
 };
 
 // Stage n <= max_crops boxes as opd_reid_extract does and run the pre-processing kernel alone: the model's image of each crop (fp16

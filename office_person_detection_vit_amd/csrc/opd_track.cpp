@@ -6,6 +6,10 @@
 // Why nothing needs a second wait: the list of the commit launch is written into its own region of the page-locked image AFTER the call's
 // wait, which also covers the previous call's upload of that region; the inputs are written before the wait, and their previous upload
 // was covered by the previous call's wait.
+//
+// The fused detect-and-track call (opd_detr_detect_frames_track, opd_api.cpp) runs the same three parts with another front: instead of the upload,
+// track_ingest_kernel writes the staging image from the detector's records on the DETECTOR's stream, the predict / cost launch follows there, and
+// the wait is the detect pipeline's.  An event recorded on the handle's stream orders that work behind the previous commit launch.
 #include <math.h>
 #include <string.h>
 
@@ -39,74 +43,69 @@ void drop_all(opd_track* t) {
     t->last_T = t->last_N = 0;
 }
 
-int update_body(opd_track* t, const float* boxes, const float* foot, const float* conf, const float* features, const uint8_t* has, int kind, int n,
-                int32_t* out_ids) {
-    const int T = (int)t->tracks.size(), D = t->D;
-    HIPCHK(hipSetDevice(t->device));
-    const bool with_features = features != nullptr && n > 0;
-    if (with_features && kind == OPD_MEM_DEVICE && !device_accessible(features))
-        return fail(OPD_EINVAL, "opd_track_update: OPD_MEM_DEVICE, but the features are not device-accessible memory");
+// ---- the three parts of an update; opd_track_update and the fused detect-and-track call are both made of them ---------------------------------
+
+// Part 1, before the wait, on stream `s`: the slot list (unless the caller's copy carried it), the predict / cost launch when tracks are alive, and
+// the three matrices, `n_cols` columns each.  `n_dev` (nullable): where the ingest launch left the detection count; `n_cols` is then its upper bound.
+int enqueue_predict(opd_track* t, hipStream_t s, int n_cols, bool with_features, const int32_t* n_dev, bool upload_slots) {
+    const int T = (int)t->tracks.size();
     uint8_t* h = t->io.host;
     uint8_t* d = t->io.dev;
-    t->last_launches = t->last_waits = 0;
-    // ---- upload: [slots | boxes | foot | has] in one copy (the regions are adjacent), the features in a second one
-    int32_t* h_slots = reinterpret_cast<int32_t*>(h + t->o_slots);
-    for (int i = 0; i < T; ++i) h_slots[i] = t->tracks[i].slot;
-    if (n > 0) {
-        memcpy(h + t->o_boxes, boxes, (size_t)n * 16);
-        memcpy(h + t->o_foot, foot, (size_t)n * 8);
-        if (with_features && has) memcpy(h + t->o_has, has, (size_t)n);
-        else memset(h + t->o_has, with_features ? 1 : 0, (size_t)n);
+    if (T == 0) return OPD_OK;
+    if (upload_slots) HIPCHK(hipMemcpyAsync(d + t->o_slots, h + t->o_slots, (size_t)T * 4, hipMemcpyHostToDevice, s));
+    TrackPredictParams p{};
+    p.s = t->st;
+    p.d = dets_of(t, d, n_cols, with_features);
+    p.T = T; p.D = t->D;
+    p.slots = reinterpret_cast<const int32_t*>(d + t->o_slots);
+    p.app = reinterpret_cast<float*>(d + t->o_app);
+    p.iou = reinterpret_cast<float*>(d + t->o_iou);
+    p.comb = reinterpret_cast<float*>(d + t->o_comb);
+    p.aw = t->aw; p.mw = t->mw;
+    p.max_dist = (float)t->max_dist;
+    p.n_dev = n_dev;
+    HIPCHK(opd_launch_track_predict_cost(p, s));
+    ++t->last_launches;
+    const size_t mat = (size_t)T * n_cols * 4;
+    if (mat) {
+        HIPCHK(hipMemcpyAsync(h + t->o_app, d + t->o_app, mat, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h + t->o_iou, d + t->o_iou, mat, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h + t->o_comb, d + t->o_comb, mat, hipMemcpyDeviceToHost, s));
     }
-    HIPCHK(hipMemcpyAsync(d + t->o_slots, h + t->o_slots, t->o_feat - t->o_slots, hipMemcpyHostToDevice, t->stream));
-    if (with_features) {
-        if (kind == OPD_MEM_HOST) {
-            memcpy(h + t->o_feat, features, (size_t)n * D * 4);
-            HIPCHK(hipMemcpyAsync(d + t->o_feat, h + t->o_feat, (size_t)n * D * 4, hipMemcpyHostToDevice, t->stream));
-        } else {
-            HIPCHK(hipMemcpyAsync(d + t->o_feat, features, (size_t)n * D * 4, hipMemcpyDeviceToDevice, t->stream));
-        }
-    }
-    // ---- launch 1 and the matrices
-    const size_t mat = (size_t)T * n * 4;
-    if (T > 0) {
-        TrackPredictParams p{};
-        p.s = t->st;
-        p.d = dets_of(t, d, n, with_features);
-        p.T = T; p.D = D;
-        p.slots = reinterpret_cast<const int32_t*>(d + t->o_slots);
-        p.app = reinterpret_cast<float*>(d + t->o_app);
-        p.iou = reinterpret_cast<float*>(d + t->o_iou);
-        p.comb = reinterpret_cast<float*>(d + t->o_comb);
-        p.aw = t->aw; p.mw = t->mw;
-        p.max_dist = (float)t->max_dist;
-        HIPCHK(opd_launch_track_predict_cost(p, t->stream));
-        ++t->last_launches;
-        if (mat) {
-            HIPCHK(hipMemcpyAsync(h + t->o_app, d + t->o_app, mat, hipMemcpyDeviceToHost, t->stream));
-            HIPCHK(hipMemcpyAsync(h + t->o_iou, d + t->o_iou, mat, hipMemcpyDeviceToHost, t->stream));
-            HIPCHK(hipMemcpyAsync(h + t->o_comb, d + t->o_comb, mat, hipMemcpyDeviceToHost, t->stream));
-        }
-    }
-    HIPCHK(hipStreamSynchronize(t->stream));
-    ++t->last_waits;
+    return OPD_OK;
+}
+
+void fill_slots(opd_track* t) {
+    int32_t* h_slots = reinterpret_cast<int32_t*>(t->io.host + t->o_slots);
+    for (size_t i = 0; i < t->tracks.size(); ++i) h_slots[i] = t->tracks[i].slot;
+}
+
+// Part 2, after the wait: the association over the [T][n] matrices in the page-locked image (row stride n), ids and counters.  `conf`: the
+// confidence of detection j at conf[j * conf_stride].  Leaves the list of the commit launch in the image and returns its length in *M.
+int associate_update(opd_track* t, const float* conf, int conf_stride, int n, int32_t* out_ids, const std::string& who, int* M_out) {
+    const int T = (int)t->tracks.size();
+    uint8_t* h = t->io.host;
     t->last_T = T; t->last_N = n;
-    // ---- association over the three matrices
     for (TrackEntry& e : t->tracks) ++e.tsu;   // `Track.predict`
     std::vector<int32_t> hits(T);
     for (int i = 0; i < T; ++i) hits[i] = t->tracks[i].hits;
+    std::vector<float> packed;
+    if (conf_stride != 1) {
+        packed.resize(n);
+        for (int j = 0; j < n; ++j) packed[j] = conf[(size_t)j * conf_stride];
+        conf = packed.data();
+    }
     AssocResult a;
     associate(reinterpret_cast<const float*>(h + t->o_app), reinterpret_cast<const float*>(h + t->o_iou), reinterpret_cast<const float*>(h + t->o_comb), T, n,
               hits.data(), conf, t->min_hits, t->high_conf, &a);
     for (int j = 0; j < n; ++j) out_ids[j] = -1;
     int rc = OPD_OK;
     if (a.new_dets.size() > t->free_slots.size()) {
-        rc = fail(OPD_EINVAL, "opd_track_update: " + std::to_string(T) + " live tracks and " + std::to_string(a.new_dets.size()) + " new ones exceed max_tracks = " +
+        rc = fail(OPD_EINVAL, who + ": " + std::to_string(T) + " live tracks and " + std::to_string(a.new_dets.size()) + " new ones exceed max_tracks = " +
                                   std::to_string(t->S) + "; the frame was counted as one without detections");
         a.matches.clear();
         a.new_dets.clear();
     }
-    // ---- counters, ids and the list of the commit launch
     int32_t* ops = reinterpret_cast<int32_t*>(h + t->o_ops);
     int M = 0;
     for (const auto& m : a.matches) {
@@ -124,27 +123,115 @@ int update_body(opd_track* t, const float* boxes, const float* foot, const float
         t->tracks.push_back(e);
         out_ids[j] = e.id;
     }
+    *M_out = M;
+    return rc;
+}
+
+// Part 3: the list and the commit launch on the handle's own stream, not waited for; then the tracks that went max_age frames without a match
+// leave, and their slots are free for the next frame.
+int enqueue_commit(opd_track* t, int M, int n, bool with_features) {
+    uint8_t* h = t->io.host;
+    uint8_t* d = t->io.dev;
     if (M > 0) {
         HIPCHK(hipMemcpyAsync(d + t->o_ops, h + t->o_ops, (size_t)M * 16, hipMemcpyHostToDevice, t->stream));
         TrackCommitParams c{};
         c.s = t->st;
         c.d = dets_of(t, d, n, with_features);
-        c.M = M; c.D = D;
+        c.M = M; c.D = t->D;
         c.ops = reinterpret_cast<const int32_t*>(d + t->o_ops);
         HIPCHK(opd_launch_track_commit(c, t->stream));
         ++t->last_launches;
     }
-    // ---- tracks that went max_age frames without a match leave; their slots are free for the next frame
     size_t keep = 0;
     for (size_t i = 0; i < t->tracks.size(); ++i) {
         if (t->tracks[i].tsu < t->max_age) t->tracks[keep++] = t->tracks[i];
         else t->free_slots.push_back(t->tracks[i].slot);
     }
     t->tracks.resize(keep);
+    return OPD_OK;
+}
+
+int update_body(opd_track* t, const float* boxes, const float* foot, const float* conf, const float* features, const uint8_t* has, int kind, int n,
+                int32_t* out_ids) {
+    const int D = t->D;
+    HIPCHK(hipSetDevice(t->device));
+    const bool with_features = features != nullptr && n > 0;
+    if (with_features && kind == OPD_MEM_DEVICE && !device_accessible(features))
+        return fail(OPD_EINVAL, "opd_track_update: OPD_MEM_DEVICE, but the features are not device-accessible memory");
+    uint8_t* h = t->io.host;
+    uint8_t* d = t->io.dev;
+    t->last_launches = t->last_waits = 0;
+    // ---- upload: [slots | boxes | foot | has] in one copy (the regions are adjacent), the features in a second one
+    fill_slots(t);
+    if (n > 0) {
+        memcpy(h + t->o_boxes, boxes, (size_t)n * 16);
+        memcpy(h + t->o_foot, foot, (size_t)n * 8);
+        if (with_features && has) memcpy(h + t->o_has, has, (size_t)n);
+        else memset(h + t->o_has, with_features ? 1 : 0, (size_t)n);
+    }
+    HIPCHK(hipMemcpyAsync(d + t->o_slots, h + t->o_slots, t->o_feat - t->o_slots, hipMemcpyHostToDevice, t->stream));
+    if (with_features) {
+        if (kind == OPD_MEM_HOST) {
+            memcpy(h + t->o_feat, features, (size_t)n * D * 4);
+            HIPCHK(hipMemcpyAsync(d + t->o_feat, h + t->o_feat, (size_t)n * D * 4, hipMemcpyHostToDevice, t->stream));
+        } else {
+            HIPCHK(hipMemcpyAsync(d + t->o_feat, features, (size_t)n * D * 4, hipMemcpyDeviceToDevice, t->stream));
+        }
+    }
+    // ---- launch 1 and the matrices
+    RCCHK(enqueue_predict(t, t->stream, n, with_features, nullptr, false));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    ++t->last_waits;
+    int M = 0;
+    const int rc = associate_update(t, conf, 1, n, out_ids, "opd_track_update", &M);
+    RCCHK(enqueue_commit(t, M, n, with_features));
     return rc;
 }
 
 }  // namespace
+
+namespace opd {
+
+int track_fused_check(const opd_track* t, int device, int Q, int feature_dim, const char* who) {
+    const std::string me = std::string(who) + ": ";
+    if (!t) return fail(OPD_EINVAL, me + "null tracker handle");
+    if (t->device != device) return fail(OPD_EINVAL, me + "the detector is on device " + std::to_string(device) + ", a tracker on device " + std::to_string(t->device));
+    if (t->NM < Q)
+        return fail(OPD_EINVAL, me + "a tracker was made for max_dets = " + std::to_string(t->NM) + ", the detector can keep num_queries = " + std::to_string(Q) + " records of a frame");
+    if (feature_dim > 0 && t->D != feature_dim)
+        return fail(OPD_EINVAL, me + "a tracker was made for feature_dim = " + std::to_string(t->D) + ", the rows of this feature kind have " + std::to_string(feature_dim) + " numbers");
+    return OPD_OK;
+}
+
+int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* count, int Q, int frame, const TrackFeatureSource& src) {
+    uint8_t* d = t->io.dev;
+    t->last_launches = t->last_waits = 0;
+    // behind whatever the handle's own stream still holds (the previous commit launch reads the staging image the ingest launch overwrites)
+    HIPCHK(hipEventRecord(t->ev_commit, t->stream));
+    HIPCHK(hipStreamWaitEvent(s, t->ev_commit, 0));
+    fill_slots(t);
+    TrackIngestParams p{};
+    p.records = records; p.count = count;
+    p.Q = Q; p.D = t->D; p.frame = frame;
+    p.rows_kind = src.rows_kind; p.rows = src.rows; p.slot_map = src.slot_map; p.n_person = src.n_person; p.slots = src.slots;
+    p.boxes = reinterpret_cast<float*>(d + t->o_boxes);
+    p.foot = reinterpret_cast<float*>(d + t->o_foot);
+    p.has = d + t->o_has;
+    p.feat = reinterpret_cast<float*>(d + t->o_feat);
+    p.n_out = reinterpret_cast<int32_t*>(d + t->o_n);
+    HIPCHK(opd_launch_track_ingest(p, s));
+    ++t->last_launches;
+    return enqueue_predict(t, s, Q, src.rows_kind != TRACK_ROWS_NONE, p.n_out, true);
+}
+
+int track_fused_finish(opd_track* t, const opd_det* recs, int n, int with_features, int32_t* out_ids, const char* who) {
+    int M = 0;
+    const int rc = associate_update(t, n > 0 ? &recs[0].score : nullptr, (int)(sizeof(opd_det) / sizeof(float)), n, out_ids, who, &M);
+    RCCHK(enqueue_commit(t, M, n, with_features != 0));
+    return rc;
+}
+
+}  // namespace opd
 
 extern "C" int opd_track_create(const opd_track_config* cfg, int device_ordinal, opd_track** out) { return api_call("opd_track_create", [&]() -> int {
     const std::string me = "opd_track_create: ";
@@ -176,6 +263,7 @@ extern "C" int opd_track_create(const opd_track_config* cfg, int device_ordinal,
     t->max_dist = c.max_position_distance == 0.0 ? 150.0 : c.max_position_distance;
     t->high_conf = c.high_conf_threshold != 0.0 ? c.high_conf_threshold : 0.5;
     RCCHK(made("opd_track_create", "stream creation", hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)));
+    RCCHK(made("opd_track_create", "event creation", hipEventCreateWithFlags(&t->ev_commit, hipEventDisableTiming)));
     // the state: one allocation, zeroed
     size_t off = 0;
     auto place = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
@@ -195,6 +283,7 @@ extern "C" int opd_track_create(const opd_track_config* cfg, int device_ordinal,
     t->o_slots = place((size_t)S * 4); t->o_boxes = place((size_t)NM * 16); t->o_foot = place((size_t)NM * 8); t->o_has = place((size_t)NM);
     t->o_feat = place((size_t)NM * D * 4); t->o_ops = place((size_t)S * 16);
     t->o_app = place((size_t)S * NM * 4); t->o_iou = place((size_t)S * NM * 4); t->o_comb = place((size_t)S * NM * 4);
+    t->o_n = place(4);   // the detection count of a fused call, left by its ingest launch for its predict launch
     t->io_bytes = off;
     RCCHK(t->io.reserve("opd_track_create", off, off, t->stream));
     memset(t->io.host, 0, off);
@@ -208,6 +297,7 @@ extern "C" void opd_track_destroy(opd_track* t) { (void)api_call("opd_track_dest
     if (!t) return OPD_OK;
     (void)hipSetDevice(t->device);
     if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
+    if (t->ev_commit) (void)hipEventDestroy(t->ev_commit);
     if (t->d_state) (void)hipFree(t->d_state);
     t->io.release();
     delete t;

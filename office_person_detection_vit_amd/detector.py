@@ -649,6 +649,51 @@ class HipDetrDetector:
             det.features = rows[i]
         return detections, rows
 
+    def detect_and_track(self, frame: np.ndarray, tracker, features: Optional[str] = "color", reid=None, reid_slots: int = 32) -> List[Detection]:
+        """``detect_with_features(frame)`` followed by ``tracker.update(detections)`` (the reference's loop, ``detection.py:91-94`` and
+        ``tracking.py:183-210``) as ONE native call with one host wait: the kept records and their feature rows enter ``tracker`` (a
+        ``HipTracker``) where they lie on the device (``opd_detr_detect_frames_track``).  Returns what ``tracker.update`` returns, the
+        detections that got an id; ``det.features`` stays ``None`` since the rows never leave the device.  ``features``: ``"encoder"``,
+        ``"color"``, ``"reid"`` (with ``reid=``) or ``None`` for motion only.  Needs ``device_nms=True``, a frame that goes down as a frame
+        list and all handles on one GPU; otherwise the two calls run one after the other, with the same ids and track states."""
+        self._require_model()
+        if features not in (None, "encoder", "color", "reid"):
+            raise ValueError(f"features must be None, 'encoder', 'color' or 'reid', got {features!r}")
+        if features == "reid" and reid is None:
+            raise ValueError("features='reid' needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
+        if features == "reid" and not reid.is_loaded:
+            raise RuntimeError("Re-ID model is not loaded: call load_model() first")
+        self._sync_nms()
+        target = self._frame_list_target([frame]) if (self.frame_lists and isinstance(frame, np.ndarray)) else None
+        Q = self._info.num_queries
+        width = {None: None, "encoder": self._info.d_model, "color": 256, "reid": int(reid.feature_dim) if reid is not None else None}[features]
+        fused = (self._nms_set is not None and target is not None and tracker.device_ordinal == self.device_ordinal and tracker.max_dets >= Q
+                 and (width is None or tracker.feature_dim == width))
+        if features in ("encoder", "color"):
+            fused = fused and self._info.d_model == 256 and not (features == "color" and max(frame.shape[:2]) > 4096)
+        if features == "reid":
+            fused = fused and reid._ordinal() == self.device_ordinal
+        if not fused:
+            if features is None:
+                return tracker.update(self.detect(frame))
+            return tracker.update(self.detect_with_features(frame, features=features, reid=reid, reid_slots=reid_slots)[0])
+        tracker._ensure()
+        kind = {None: _capi.OPD_TRACK_FEAT_NONE, "encoder": _capi.OPD_TRACK_FEAT_ENCODER, "color": _capi.OPD_TRACK_FEAT_COLOR, "reid": _capi.OPD_TRACK_FEAT_REID}[features]
+        slots = max(1, min(int(reid_slots), int(reid.max_crops), int(tracker.max_dets))) if features == "reid" else 0
+        recs, counts = (_capi.OpdDet * Q)(), (C.c_int32 * 1)()
+        ids, n_featured = np.full(Q, -1, np.int32), np.zeros(1, np.int32)
+        ptrs, handles = (C.c_void_p * 1)(frame.ctypes.data), (C.c_void_p * 1)(tracker._h.value)
+        rc = self._lib.opd_detr_detect_frames_track(C.c_void_p(self.model), reid._handle if features == "reid" else None, handles, ptrs, 1, int(frame.shape[0]),
+                                                    int(frame.shape[1]), target[0], target[1], float(self.confidence_threshold), PERSON_LABEL, kind, slots,
+                                                    recs, counts, ids.ctypes.data, n_featured.ctypes.data)
+        if rc != 0 and "counted as one without detections" in _capi.last_error():
+            tracker._apply([], ids[:0])   # out of slots: as in HipTracker.update, the mirror follows before the error is raised
+        _capi.check(rc, "opd_detr_detect_frames_track")
+        self._last_orig = [(int(frame.shape[0]), int(frame.shape[1]))]
+        detections = self._postprocess_batch(recs, counts, Q)[0]
+        tracker._apply(detections, ids[:len(detections)])
+        return [det for det in detections if det.track_id is not None]
+
     def extract_color_features(self, frame: np.ndarray, detections: List[Detection]) -> np.ndarray:
         """(N, 256) float32 colour-histogram features of the detections' crops of ``frame`` (BGR uint8 ``[H, W, 3]``), on the
         device: ``FeatureExtractor.extract_batch`` on the crops ``YOLOv8Detector.extract_features`` cuts
