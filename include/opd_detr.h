@@ -594,6 +594,18 @@ OPD_API int opd_track_info(const opd_track* t, opd_track_status* info);
  * without detections (every track aged, none matched or created), so the handle stays usable. */
 OPD_API int opd_track_update(opd_track* t, const float* boxes_xywh, const float* foot_xy, const float* confidence, const float* features,
                              const uint8_t* has_feature, int feat_mem_kind, int n, int32_t* out_ids);
+/* A run of F frames of one camera in ONE call with ONE host wait: what F calls of opd_track_update give, ids and state
+ * bit for bit, with the association on the device between the frames (track_assoc_kernel: the host's five stages and the host's solver, pair for
+ * pair, ties included).  The arrays are packed frame after frame: frame f occupies counts[f] rows, sum(counts) rows in all; out_ids likewise.
+ * features NULL: no detection of any frame has one; has_feature NULL: every one has.  All detections are uploaded once; per frame the launches are
+ * predict / cost, association, commit; then the ids and the track table come back and the handle adopts the table.  Afterwards opd_track_info
+ * reports last_waits = 1 and last_launches = the launches that ran.  OPD_EINVAL before any device work, changing nothing: F <= 0, a negative count,
+ * a counts[f] > max_dets, null counts, out_ids or frames_done.  A frame f that would exceed max_tracks counts as one without detections, as under
+ * opd_track_update; the frames after it are NOT applied and their ids are -1, *frames_done = f + 1, and the call returns OPD_EINVAL: the state is
+ * that of the per-frame loop that stopped at its error.  On success *frames_done = F. */
+OPD_API int opd_track_update_sequence(opd_track* t, const float* boxes_xywh, const float* foot_xy, const float* confidence, const float* features,
+                                      const uint8_t* has_feature, int feat_mem_kind, const int32_t* counts, int F, int32_t* out_ids,
+                                      int32_t* frames_done);
 /* The live tracks in creation order: out [capacity], *count = how many there are (OPD_EINVAL when capacity is smaller; out may be NULL
  * with capacity 0 to ask for the count).  Waits for the last update's second launch. */
 OPD_API int opd_track_get(opd_track* t, opd_track_rec* out, int capacity, int* count);
@@ -619,6 +631,15 @@ OPD_API int opd_track_get(opd_track* t, opd_track_rec* out, int capacity, int* c
 OPD_API int opd_detr_detect_frames_track(opd_detr* m, opd_reid* r, opd_track* const* trackers, const uint8_t* const* frames, int B, int h,
                                          int w, int H, int W, float threshold, int label, int feature_kind, int slots, opd_det* out,
                                          int32_t* counts, int32_t* track_ids, int32_t* n_featured);
+/* opd_detr_detect_frames_track for B CONSECUTIVE frames of ONE camera into ONE tracker, in frame order: one batched forward,
+ * suppression and feature stage; then per frame, on the detector's stream, ingest, predict / cost, association on the device and commit; ONE host
+ * wait; no matrix, box or feature row crosses the bus.  Records, counts, track_ids [B][num_queries] and n_featured [B] as above; for REID the
+ * `slots` crop slots are per call, handed out in (frame, score) order.  The refusals are those of opd_detr_detect_frames_track, in the same order.
+ * Out of slots at frame f: as opd_track_update_sequence (records and counts of all B frames are still delivered).  *frames_done = B on success.
+ * Afterwards opd_track_info reports last_waits = 0 and last_launches = the launches that ran. */
+OPD_API int opd_detr_detect_sequence_track(opd_detr* m, opd_reid* r, opd_track* t, const uint8_t* const* frames, int B, int h, int w, int H, int W,
+                                           float threshold, int label, int feature_kind, int slots, opd_det* out, int32_t* counts,
+                                           int32_t* track_ids, int32_t* n_featured, int32_t* frames_done);
 /* The solver of the association on its own (host only): cost [rows][cols] row-major -> row_to_col [rows], -1 for a row left alone;
  * min(rows, cols) pairs of smallest total cost, as scipy.optimize.linear_sum_assignment. */
 OPD_API int opd_assign(const double* cost, int rows, int cols, int32_t* row_to_col);

@@ -210,9 +210,13 @@ API = {
     "opd_track_reset": (C.c_int, [C.c_void_p]),
     "opd_track_info": (C.c_int, [C.c_void_p, C.POINTER(OpdTrackStatus)]),
     "opd_track_update": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
+    # boxes, foot, confidence, features, has_feature, feat_mem_kind, counts, F, out_ids, frames_done
+    "opd_track_update_sequence": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "opd_track_get": (C.c_int, [C.c_void_p, C.POINTER(OpdTrackRec), C.c_int, C.POINTER(C.c_int)]),
     "opd_detr_detect_frames_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int, C.c_int,
                                                 C.POINTER(OpdDet), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "opd_detr_detect_sequence_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(OpdDet), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
     "opd_assign": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "opd_lwt_create": (C.c_int, [C.POINTER(OpdLwtConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "opd_lwt_destroy": (None, [C.c_void_p]),
@@ -348,6 +352,12 @@ TEST_API = {
     "opd_track_test_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     # device, records, n, Q, D, frame, rows_kind, rows, n_rows, slot_map, n_person, slots, capacity, boxes, foot, has, feat, n_out
     "opd_track_test_ingest": (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    # app, iou, comb [T][N], T, N, hits [T], conf [N], min_hits, high_conf, n_free, then for the kernel and for the host: matches [min(T, N)][2], n_matches, new_dets [N],
+    # n_new, unmatched [T], n_unmatched
+    "opd_track_test_assoc": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 12),
+    # the same inputs, iters -> mean milliseconds of the kernel and of the host's associate()
+    "opd_track_test_bench_assoc": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int,
+                                              C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     # hybrid-tracker hook (csrc/opd_lwt_test_api.cpp): handle, next_xy, status, records, capacity, count
     "opd_test_lwt_interpolate_scripted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OpdLwtRec), C.c_int, C.POINTER(C.c_int)]),
 }

@@ -208,11 +208,13 @@ static int fetch_records(opd_detr* m, opd_det* out, int32_t* counts, int mem_kin
 // keep the others from being committed, and its error is the call's.
 static int enqueue_trackers(opd_detr* m, const RecordSink& s, const TrackFeatureSource& src) {
     const int B = m->last_B, Q = m->arch.queries;
+    if (s.seq_tracker) return track_sequence_enqueue(s.seq_tracker, m->stream, m->d_records, m->d_counts, Q, B, src, "opd_detr_detect_sequence_track");
     for (int b = 0; b < B; ++b) RCCHK(track_fused_enqueue(s.trackers[b], m->stream, m->d_records + (size_t)b * Q, m->d_counts + b, Q, b, src));
     return OPD_OK;
 }
 static int finish_trackers(opd_detr* m, const RecordSink& s, bool with_features) {
     const int B = m->last_B, Q = m->arch.queries;
+    if (s.seq_tracker) return track_sequence_finish(s.seq_tracker, s.counts, Q, B, s.track_ids, s.frames_done, "opd_detr_detect_sequence_track");
     int rc = OPD_OK;
     std::string first;
     for (int b = 0; b < B; ++b) {
@@ -248,19 +250,19 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
     if (s.feature == FEAT_REID) {   // select, plan and the Re-ID forward behind the post-process; the rows come back behind the records, before the one wait
         ReidFusedCall call(s.reid);
         RCCHK(call.enqueue(m->stream, m->d_records, m->d_counts, d_camera, B, Q, h, w, s.label, s.slots));
-        if (s.trackers) {   // the rows stay where the forward left them; the slot list alone comes back
+        if (s.trackers || s.seq_tracker) {   // the rows stay where the forward left them; the slot list alone comes back
             call.with_rows = false;
             RCCHK(enqueue_trackers(m, s, {TRACK_ROWS_BY_SLOT, reid_feature_dim(s.reid), call.dev_rows(), call.dev_slot_map(), call.dev_n_person(), s.slots}));
         }
         RCCHK(fetch_records(m, s.out, s.counts, s.mem_kind, nullptr, nullptr, s.label, &call));
-        if (s.trackers) {
+        if (s.trackers || s.seq_tracker) {
             call.slots_per_frame(B, Q, s.n_featured);
             return finish_trackers(m, s, true);
         }
         call.deliver(s.features, s.slot_map, s.n_person);
         return OPD_OK;
     }
-    if (s.trackers) {
+    if (s.trackers || s.seq_tracker) {
         const bool rows = s.feature != FEAT_NONE;
         RCCHK(enqueue_trackers(m, s, {rows ? TRACK_ROWS_BY_QUERY : TRACK_ROWS_NONE, m->arch.d_model, rows ? m->d_feat_all : nullptr, nullptr, nullptr, 0}));
         RCCHK(fetch_records(m, s.out, s.counts, s.mem_kind));
@@ -782,12 +784,9 @@ int opd_detr_detect_frames_reid(opd_detr* m, opd_reid* r, const uint8_t* const* 
 // The tracking twin: same upload, forward, post-process with suppression and feature stage; then, still before the one wait, every
 // tracker's ingest launch reads its frame's kept records and feature rows where they lie and its predict / cost launch follows, so that the wait
 // delivers records and cost matrices together.  Association and the commit launch (on the tracker's own stream, not waited for) follow it.
-int opd_detr_detect_frames_track(opd_detr* m, opd_reid* r, opd_track* const* trackers, const uint8_t* const* frames, int B, int h, int w, int H, int W,
-                                 float threshold, int label, int feature_kind, int slots, opd_det* out, int32_t* counts, int32_t* track_ids,
-                                 int32_t* n_featured) { return api_call("opd_detr_detect_frames_track", [&]() -> int {
-    const std::string me = "opd_detr_detect_frames_track";
-    // what needs no handle first, so that a null handle is the last thing reported without one
-    if (!trackers || !frames || !out || !counts || !track_ids || !n_featured) return fail(OPD_EINVAL, me + ": null argument (tracker list, frame list or an output)");
+// The refusals both tracking calls share, behind their own null-argument check and in this order; *dim: the width of a feature row of the kind (0: none)
+static int check_track_call(const std::string& me, opd_detr* m, opd_reid* r, const uint8_t* const* frames, int B, int h, int w, int H, int W, int label, int feature_kind,
+                            int slots, int* dim) {
     if (feature_kind != OPD_TRACK_FEAT_NONE && feature_kind != OPD_TRACK_FEAT_ENCODER && feature_kind != OPD_TRACK_FEAT_COLOR && feature_kind != OPD_TRACK_FEAT_REID)
         return fail(OPD_EINVAL, me + ": unknown feature_kind " + std::to_string(feature_kind));
     if (feature_kind == OPD_TRACK_FEAT_REID && !r) return fail(OPD_EINVAL, me + ": feature_kind OPD_TRACK_FEAT_REID with a null Re-ID handle");
@@ -799,14 +798,28 @@ int opd_detr_detect_frames_track(opd_detr* m, opd_reid* r, opd_track* const* tra
         return fail(OPD_EINVAL, me + ": opd_detr_set_nms is off on this handle; a tracker takes the kept records of a frame, which only the suppression on the device leaves there");
     if (m->nms_label != label)
         return fail(OPD_EINVAL, me + ": opd_detr_set_nms keeps label " + std::to_string(m->nms_label) + ", the call asks for label " + std::to_string(label));
-    int dim = 0;
+    *dim = 0;
     if (feature_kind == OPD_TRACK_FEAT_REID) {
         RCCHK(reid_fused_check(r, m->device, slots, me.c_str()));
-        dim = reid_feature_dim(r);
+        *dim = reid_feature_dim(r);
     } else if (feature_kind != OPD_TRACK_FEAT_NONE) {
         if (m->arch.d_model != OPD_COLOR_DIM) return fail(OPD_EINVAL, me + ": the feature area of the handle and both kernels that fill it are sized for d_model = 256");
-        dim = OPD_COLOR_DIM;
+        *dim = OPD_COLOR_DIM;
     }
+    return OPD_OK;
+}
+static int track_feature_of(int feature_kind) {
+    return feature_kind == OPD_TRACK_FEAT_ENCODER ? FEAT_ROI : feature_kind == OPD_TRACK_FEAT_COLOR ? FEAT_COLOR : feature_kind == OPD_TRACK_FEAT_REID ? FEAT_REID : FEAT_NONE;
+}
+
+int opd_detr_detect_frames_track(opd_detr* m, opd_reid* r, opd_track* const* trackers, const uint8_t* const* frames, int B, int h, int w, int H, int W,
+                                 float threshold, int label, int feature_kind, int slots, opd_det* out, int32_t* counts, int32_t* track_ids,
+                                 int32_t* n_featured) { return api_call("opd_detr_detect_frames_track", [&]() -> int {
+    const std::string me = "opd_detr_detect_frames_track";
+    // what needs no handle first, so that a null handle is the last thing reported without one
+    if (!trackers || !frames || !out || !counts || !track_ids || !n_featured) return fail(OPD_EINVAL, me + ": null argument (tracker list, frame list or an output)");
+    int dim = 0;
+    RCCHK(check_track_call(me, m, r, frames, B, h, w, H, W, label, feature_kind, slots, &dim));
     for (int b = 0; b < B; ++b) {
         RCCHK(track_fused_check(trackers[b], m->device, m->arch.queries, dim, me.c_str()));
         for (int a = 0; a < b; ++a)
@@ -814,9 +827,28 @@ int opd_detr_detect_frames_track(opd_detr* m, opd_reid* r, opd_track* const* tra
     }
     HIPCHK(hipSetDevice(m->device));
     if (feature_kind == OPD_TRACK_FEAT_COLOR && !m->d_color_acc) RCCHK(dalloc(m, &m->d_color_acc, (size_t)m->cfg.max_batch * m->arch.queries * OPD_COLOR_ACC_WORDS, false));
-    const int feature = feature_kind == OPD_TRACK_FEAT_ENCODER ? FEAT_ROI : feature_kind == OPD_TRACK_FEAT_COLOR ? FEAT_COLOR : feature_kind == OPD_TRACK_FEAT_REID ? FEAT_REID : FEAT_NONE;
+    const int feature = track_feature_of(feature_kind);
     RecordSink sink{threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, feature, label, nullptr, nullptr, nullptr, feature == FEAT_REID ? r : nullptr, slots, nullptr, nullptr,
                     trackers, track_ids, n_featured};
+    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr, sink);
+}); }
+
+// The sequence twin: B consecutive frames of ONE camera into ONE tracker.  One batched forward, suppression and feature stage as above; then per
+// frame, on the detector's stream, ingest -> predict / cost -> association on the device -> commit, and the table and the ids come back behind the one wait.
+int opd_detr_detect_sequence_track(opd_detr* m, opd_reid* r, opd_track* t, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
+                                   int label, int feature_kind, int slots, opd_det* out, int32_t* counts, int32_t* track_ids, int32_t* n_featured,
+                                   int32_t* frames_done) { return api_call("opd_detr_detect_sequence_track", [&]() -> int {
+    const std::string me = "opd_detr_detect_sequence_track";
+    // what needs no handle first, so that a null handle is the last thing reported without one
+    if (!frames || !out || !counts || !track_ids || !n_featured || !frames_done) return fail(OPD_EINVAL, me + ": null argument (frame list or an output)");
+    int dim = 0;
+    RCCHK(check_track_call(me, m, r, frames, B, h, w, H, W, label, feature_kind, slots, &dim));
+    RCCHK(track_fused_check(t, m->device, m->arch.queries, dim, me.c_str()));
+    HIPCHK(hipSetDevice(m->device));
+    if (feature_kind == OPD_TRACK_FEAT_COLOR && !m->d_color_acc) RCCHK(dalloc(m, &m->d_color_acc, (size_t)m->cfg.max_batch * m->arch.queries * OPD_COLOR_ACC_WORDS, false));
+    const int feature = track_feature_of(feature_kind);
+    RecordSink sink{threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, feature, label, nullptr, nullptr, nullptr, feature == FEAT_REID ? r : nullptr, slots, nullptr, nullptr,
+                    nullptr, track_ids, n_featured, t, frames_done};
     return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr, sink);
 }); }
 

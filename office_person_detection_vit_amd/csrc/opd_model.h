@@ -432,6 +432,8 @@ struct RecordSink {
     struct opd_track* const* trackers;   // non-null (opd_detr_detect_frames_track): frame b's kept records and feature rows enter trackers[b] where they lie; the feature
     int32_t* track_ids;                  // stage runs but its rows are not downloaded (`features`, `slot_map`, `n_person` are null).  track_ids [B][queries], n_featured [B]
     int32_t* n_featured;
+    struct opd_track* seq_tracker;       // non-null (opd_detr_detect_sequence_track, `trackers` null): the B frames enter this ONE tracker in frame order, the
+    int32_t* frames_done;                // association on the device between them; track_ids and n_featured as above, *frames_done = frames applied
 };
 int check_shape(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W);
 int detect_pipeline(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, const RecordSink& sink);

@@ -10,9 +10,14 @@
 // The fused detect-and-track call (opd_detr_detect_frames_track, opd_api.cpp) runs the same three parts with another front: instead of the upload,
 // track_ingest_kernel writes the staging image from the detector's records on the DETECTOR's stream, the predict / cost launch follows there, and
 // the wait is the detect pipeline's.  An event recorded on the handle's stream orders that work behind the previous commit launch.
+//
+// The sequence calls (opd_track_update_sequence here, opd_detr_detect_sequence_track in opd_api.cpp) take a run of frames with ONE wait:
+// the table of tracks goes to the device, track_assoc_kernel does part 2 there between the launches of every frame, and the table comes back and is
+// adopted after the wait.  Between calls the host's copy stays the authoritative one, so the per-frame calls above are untouched.
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
 #include <memory>
 #include <string>
 
@@ -188,9 +193,199 @@ int update_body(opd_track* t, const float* boxes, const float* foot, const float
     return rc;
 }
 
+// ---- sequence calls: the table goes to the device once, every frame is predict / cost -> association -> commit without a wait, the table
+// comes back behind the call's one wait -------------------------------------------------------------------------------------------------------------
+
+// t->seq, the same on both sides: [header | entries [S] | free-slot stack [S] | ids [n_ids] | boxes | foot points | confidences | flags | features].  The
+// part up to the ids travels both ways; the detections behind them are opd_track_update_sequence's (`rows` of them), read in place by the launches.
+struct SeqLayout { size_t o_hdr, o_tab, o_free, o_ids, o_boxes, o_foot, o_conf, o_has, o_feat, bytes; };
+
+SeqLayout seq_layout(const opd_track* t, size_t n_ids, size_t rows, bool feats) {
+    SeqLayout q{};
+    size_t off = 0;
+    auto place = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+    q.o_hdr = place(TRACK_HDR_INTS * 4); q.o_tab = place((size_t)t->S * sizeof(TrackEntry)); q.o_free = place((size_t)t->S * 4); q.o_ids = place(n_ids * 4);
+    q.o_boxes = place(rows * 16); q.o_foot = place(rows * 8); q.o_conf = place(rows * 4); q.o_has = place(rows);
+    q.o_feat = place(feats ? rows * t->D * 4 : 0);
+    q.bytes = off;
+    return q;
+}
+
+// The page-locked side of the table: the host's tracks, free slots and next id as they are, every id of the call -1
+int seq_begin(opd_track* t, const SeqLayout& q, size_t n_ids, const char* who) {
+    bool moved = false;
+    RCCHK(t->seq.reserve(who, q.bytes, q.bytes, t->stream, &moved));
+    if (moved) ++g_handle_epoch;   // device memory changed hands (opd_device.h)
+    uint8_t* h = t->seq.host;
+    int32_t* hdr = reinterpret_cast<int32_t*>(h + q.o_hdr);
+    memset(hdr, 0, TRACK_HDR_INTS * 4);
+    hdr[TRACK_HDR_T] = (int32_t)t->tracks.size();
+    hdr[TRACK_HDR_NEXT_ID] = t->next_id;
+    hdr[TRACK_HDR_N_FREE] = (int32_t)t->free_slots.size();
+    if (!t->tracks.empty()) memcpy(h + q.o_tab, t->tracks.data(), t->tracks.size() * sizeof(TrackEntry));
+    if (!t->free_slots.empty()) memcpy(h + q.o_free, t->free_slots.data(), t->free_slots.size() * 4);
+    int32_t* ids = reinterpret_cast<int32_t*>(h + q.o_ids);
+    for (size_t j = 0; j < n_ids; ++j) ids[j] = -1;
+    t->last_launches = t->last_waits = 0;
+    return OPD_OK;
+}
+
+// One frame on stream `s`.  `dets`: its detections on the device, dets.n of them at most (n_dev, nullable: where the exact count lies).  t_bound: an
+// upper bound of the tracks alive when the frame starts; the launches take the true numbers from the table.
+int seq_enqueue_frame(opd_track* t, hipStream_t s, const SeqLayout& q, const TrackDets& dets, const int32_t* n_dev, const float* conf, int conf_stride,
+                      int32_t* ids_dev, int frame, int t_bound) {
+    uint8_t* d = t->io.dev;
+    uint8_t* sq = t->seq.dev;
+    int32_t* hdr = reinterpret_cast<int32_t*>(sq + q.o_hdr);
+    int32_t* tab = reinterpret_cast<int32_t*>(sq + q.o_tab);
+    if (t_bound > 0) {
+        TrackPredictParams p{};
+        p.s = t->st; p.d = dets;
+        p.T = t_bound; p.D = t->D;
+        p.app = reinterpret_cast<float*>(d + t->o_app); p.iou = reinterpret_cast<float*>(d + t->o_iou); p.comb = reinterpret_cast<float*>(d + t->o_comb);
+        p.aw = t->aw; p.mw = t->mw;
+        p.max_dist = (float)t->max_dist;
+        p.n_dev = n_dev; p.hdr = hdr; p.tab = tab;
+        HIPCHK(opd_launch_track_predict_cost(p, s));
+        ++t->last_launches;
+    }
+    TrackAssocParams a{};
+    a.hdr = hdr; a.tab = tab; a.free_slots = reinterpret_cast<int32_t*>(sq + q.o_free);
+    a.app = reinterpret_cast<const float*>(d + t->o_app); a.iou = reinterpret_cast<const float*>(d + t->o_iou); a.comb = reinterpret_cast<const float*>(d + t->o_comb);
+    a.conf = conf; a.conf_stride = conf_stride;
+    a.n_dev = n_dev; a.n = dets.n;
+    a.ops = reinterpret_cast<int32_t*>(d + t->o_ops); a.ids = ids_dev;
+    a.S = t->S; a.min_hits = t->min_hits; a.max_age = t->max_age; a.frame = frame;
+    a.high_conf = t->high_conf;
+    HIPCHK(opd_launch_track_assoc(a, s));
+    ++t->last_launches;
+    const int m_bound = std::min<int>(t->S, dets.n);
+    if (m_bound > 0) {
+        TrackCommitParams c{};
+        c.s = t->st; c.d = dets;
+        c.M = m_bound; c.D = t->D;
+        c.ops = a.ops; c.hdr = hdr;
+        HIPCHK(opd_launch_track_commit(c, s));
+        ++t->last_launches;
+    }
+    return OPD_OK;
+}
+
+// After the wait that covered the download of [header | entries | stack | ids]: the host's copy becomes what the device left.  *frames_done: the frames
+// applied, the out-of-slots one included; that frame is the call's error, in opd_track_update's words.
+int seq_adopt(opd_track* t, const SeqLayout& q, int F, int32_t* frames_done, const std::string& who) {
+    const uint8_t* h = t->seq.host;
+    const int32_t* hdr = reinterpret_cast<const int32_t*>(h + q.o_hdr);
+    const int T = hdr[TRACK_HDR_T], n_free = hdr[TRACK_HDR_N_FREE];
+    if (T < 0 || n_free < 0 || T + n_free != t->S) return fail(OPD_EHIP, who + ": the track table came back with " + std::to_string(T) + " tracks and " + std::to_string(n_free) + " free slots of " + std::to_string(t->S));
+    const TrackEntry* e = reinterpret_cast<const TrackEntry*>(h + q.o_tab);
+    const int32_t* fs = reinterpret_cast<const int32_t*>(h + q.o_free);
+    t->tracks.assign(e, e + T);
+    t->free_slots.assign(fs, fs + n_free);
+    t->next_id = hdr[TRACK_HDR_NEXT_ID];
+    t->last_T = t->last_N = 0;   // (no matrix came to the host)
+    const bool stopped = hdr[TRACK_HDR_STOPPED] != 0;
+    *frames_done = stopped ? hdr[TRACK_HDR_FRAMES_DONE] : F;
+    if (stopped)
+        return fail(OPD_EINVAL, who + ": " + std::to_string(hdr[TRACK_HDR_STOP_T]) + " live tracks and " + std::to_string(hdr[TRACK_HDR_STOP_NEW]) + " new ones exceed max_tracks = " +
+                                    std::to_string(t->S) + "; the frame was counted as one without detections (frame " + std::to_string(hdr[TRACK_HDR_FRAMES_DONE] - 1) +
+                                    " of the call; the frames after it were not applied)");
+    return OPD_OK;
+}
+
+int update_sequence_body(opd_track* t, const float* boxes, const float* foot, const float* conf, const float* features, const uint8_t* has, int kind,
+                         const int32_t* counts, int F, int32_t* out_ids, int32_t* frames_done) {
+    const int D = t->D;
+    size_t total = 0;
+    for (int f = 0; f < F; ++f) total += (size_t)counts[f];
+    HIPCHK(hipSetDevice(t->device));
+    const bool feats = features != nullptr && total > 0;
+    if (feats && kind == OPD_MEM_DEVICE && !device_accessible(features))
+        return fail(OPD_EINVAL, "opd_track_update_sequence: OPD_MEM_DEVICE, but the features are not device-accessible memory");
+    const SeqLayout q = seq_layout(t, total, total, feats);
+    RCCHK(seq_begin(t, q, total, "opd_track_update_sequence"));
+    uint8_t* h = t->seq.host;
+    uint8_t* sq = t->seq.dev;
+    // ---- upload: table, ids and every frame's detections in one copy, device features in a second one
+    if (total > 0) {
+        memcpy(h + q.o_boxes, boxes, total * 16);
+        memcpy(h + q.o_foot, foot, total * 8);
+        memcpy(h + q.o_conf, conf, total * 4);
+        if (feats && has) memcpy(h + q.o_has, has, total);
+        else memset(h + q.o_has, feats ? 1 : 0, total);
+        if (feats && kind == OPD_MEM_HOST) memcpy(h + q.o_feat, features, total * D * 4);
+    }
+    const bool feats_by_host = feats && kind == OPD_MEM_HOST;
+    HIPCHK(hipMemcpyAsync(sq, h, feats_by_host ? q.bytes : q.o_feat, hipMemcpyHostToDevice, t->stream));
+    if (feats && !feats_by_host) HIPCHK(hipMemcpyAsync(sq + q.o_feat, features, total * D * 4, hipMemcpyDeviceToDevice, t->stream));
+    // ---- the frames, in stream order
+    size_t row = 0;
+    int t_bound = (int)t->tracks.size();
+    for (int f = 0; f < F; ++f) {
+        const int n = counts[f];
+        TrackDets d{};
+        d.boxes = reinterpret_cast<const float*>(sq + q.o_boxes) + row * 4;
+        d.foot = reinterpret_cast<const float*>(sq + q.o_foot) + row * 2;
+        d.feat = feats && n > 0 ? reinterpret_cast<const float*>(sq + q.o_feat) + row * D : nullptr;
+        d.has = sq + q.o_has + row;
+        d.n = n;
+        RCCHK(seq_enqueue_frame(t, t->stream, q, d, nullptr, reinterpret_cast<const float*>(sq + q.o_conf) + row, 1, reinterpret_cast<int32_t*>(sq + q.o_ids) + row, f, t_bound));
+        row += (size_t)n;
+        t_bound = std::min<int>(t->S, t_bound + n);
+    }
+    // ---- one download, one wait
+    HIPCHK(hipMemcpyAsync(h, sq, q.o_ids + total * 4, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    ++t->last_waits;
+    if (total > 0) memcpy(out_ids, h + q.o_ids, total * 4);
+    return seq_adopt(t, q, F, frames_done, "opd_track_update_sequence");
+}
+
 }  // namespace
 
 namespace opd {
+
+int track_sequence_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* counts, int Q, int B, const TrackFeatureSource& src, const char* who) {
+    const SeqLayout q = seq_layout(t, (size_t)B * Q, 0, false);
+    RCCHK(seq_begin(t, q, (size_t)B * Q, who));
+    uint8_t* d = t->io.dev;
+    uint8_t* sq = t->seq.dev;
+    // behind whatever the handle's own stream still holds (the previous commit launch reads the staging image the first ingest launch overwrites)
+    HIPCHK(hipEventRecord(t->ev_commit, t->stream));
+    HIPCHK(hipStreamWaitEvent(s, t->ev_commit, 0));
+    HIPCHK(hipMemcpyAsync(sq, t->seq.host, q.o_ids + (size_t)B * Q * 4, hipMemcpyHostToDevice, s));
+    const bool with_features = src.rows_kind != TRACK_ROWS_NONE;
+    int t_bound = (int)t->tracks.size();
+    for (int b = 0; b < B; ++b) {
+        TrackIngestParams p{};
+        p.records = records + (size_t)b * Q; p.count = counts + b;
+        p.Q = Q; p.D = t->D; p.frame = b;
+        p.rows_kind = src.rows_kind; p.rows = src.rows; p.slot_map = src.slot_map; p.n_person = src.n_person; p.slots = src.slots;
+        p.boxes = reinterpret_cast<float*>(d + t->o_boxes);
+        p.foot = reinterpret_cast<float*>(d + t->o_foot);
+        p.has = d + t->o_has;
+        p.feat = reinterpret_cast<float*>(d + t->o_feat);
+        p.n_out = reinterpret_cast<int32_t*>(d + t->o_n);
+        p.hdr = reinterpret_cast<const int32_t*>(sq + q.o_hdr);
+        HIPCHK(opd_launch_track_ingest(p, s));
+        ++t->last_launches;
+        RCCHK(seq_enqueue_frame(t, s, q, dets_of(t, d, Q, with_features), p.n_out, &records[(size_t)b * Q].score, (int)(sizeof(opd_det) / sizeof(float)),
+                                reinterpret_cast<int32_t*>(sq + q.o_ids) + (size_t)b * Q, b, t_bound));
+        t_bound = std::min<int>(t->S, t_bound + Q);
+    }
+    HIPCHK(hipMemcpyAsync(t->seq.host, sq, q.o_ids + (size_t)B * Q * 4, hipMemcpyDeviceToHost, s));
+    return OPD_OK;
+}
+
+int track_sequence_finish(opd_track* t, const int32_t* counts, int Q, int B, int32_t* track_ids, int32_t* frames_done, const char* who) {
+    const SeqLayout q = seq_layout(t, (size_t)B * Q, 0, false);
+    const int32_t* ids = reinterpret_cast<const int32_t*>(t->seq.host + q.o_ids);
+    for (int b = 0; b < B; ++b) {
+        const int n = std::max(0, std::min(counts[b], Q));
+        if (n > 0) memcpy(track_ids + (size_t)b * Q, ids + (size_t)b * Q, (size_t)n * 4);
+    }
+    return seq_adopt(t, q, B, frames_done, who);
+}
 
 int track_fused_check(const opd_track* t, int device, int Q, int feature_dim, const char* who) {
     const std::string me = std::string(who) + ": ";
@@ -300,6 +495,7 @@ extern "C" void opd_track_destroy(opd_track* t) { (void)api_call("opd_track_dest
     if (t->ev_commit) (void)hipEventDestroy(t->ev_commit);
     if (t->d_state) (void)hipFree(t->d_state);
     t->io.release();
+    t->seq.release();
     delete t;
     ++g_handle_epoch;
     return OPD_OK;
@@ -325,6 +521,26 @@ extern "C" int opd_track_update(opd_track* t, const float* boxes_xywh, const flo
     if (n > 0 && (!boxes_xywh || !foot_xy || !confidence || !out_ids)) return fail(OPD_EINVAL, "opd_track_update: null boxes, foot points, confidences or output");
     if (feat_mem_kind != OPD_MEM_HOST && feat_mem_kind != OPD_MEM_DEVICE) return fail(OPD_EINVAL, "opd_track_update: feat_mem_kind must be OPD_MEM_HOST or OPD_MEM_DEVICE");
     return update_body(t, boxes_xywh, foot_xy, confidence, features, has_feature, feat_mem_kind, n, out_ids);
+}); }
+
+extern "C" int opd_track_update_sequence(opd_track* t, const float* boxes_xywh, const float* foot_xy, const float* confidence, const float* features,
+                                         const uint8_t* has_feature, int feat_mem_kind, const int32_t* counts, int F, int32_t* out_ids, int32_t* frames_done) { return api_call("opd_track_update_sequence", [&]() -> int {
+    const std::string me = "opd_track_update_sequence: ";
+    // what needs no handle first, so that a null handle is the last thing reported without one
+    if (!counts || !out_ids || !frames_done) return fail(OPD_EINVAL, me + "null argument (counts or an output)");
+    if (F <= 0) return fail(OPD_EINVAL, me + "a sequence has at least one frame, got F = " + std::to_string(F));
+    if (feat_mem_kind != OPD_MEM_HOST && feat_mem_kind != OPD_MEM_DEVICE) return fail(OPD_EINVAL, me + "feat_mem_kind must be OPD_MEM_HOST or OPD_MEM_DEVICE");
+    size_t total = 0;
+    for (int f = 0; f < F; ++f) {
+        if (counts[f] < 0) return fail(OPD_EINVAL, me + "negative detection count of frame " + std::to_string(f));
+        total += (size_t)counts[f];
+    }
+    if (total > 0 && (!boxes_xywh || !foot_xy || !confidence)) return fail(OPD_EINVAL, me + "null boxes, foot points or confidences");
+    if (!t) return fail(OPD_EINVAL, me + "null handle");
+    for (int f = 0; f < F; ++f)
+        if (counts[f] > t->NM)
+            return fail(OPD_EINVAL, me + std::to_string(counts[f]) + " detections in frame " + std::to_string(f) + ", the handle was made for max_dets = " + std::to_string(t->NM));
+    return update_sequence_body(t, boxes_xywh, foot_xy, confidence, features, has_feature, feat_mem_kind, counts, F, out_ids, frames_done);
 }); }
 
 extern "C" int opd_track_get(opd_track* t, opd_track_rec* out, int capacity, int* count) { return api_call("opd_track_get", [&]() -> int {

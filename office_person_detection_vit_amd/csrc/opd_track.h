@@ -1,6 +1,11 @@
 // opd_track.h — PRIVATE header of the tracker handle (`opd_track`, include/opd_detr.h): the per-slot device state as kernels_track.hip
 // reads and writes it, the parameters of the three launches, the handle, and the tracker half of the fused detect-and-track call.  Included by
 // kernels_track.hip, opd_track.cpp, opd_track_test_api.cpp and opd_api.cpp.
+//
+// A sequence call (opd_track_update_sequence, opd_detr_detect_sequence_track) also keeps the track TABLE on the device for the length
+// of the call: the header ints below, the entries in creation order and the free-slot stack.  track_assoc_kernel then does between the two launches
+// what the host does in a per-frame call, so frame b + 1 needs no host wait behind frame b.  Between calls the host copy (opd_track::tracks) is
+// the authoritative one: a sequence call uploads it first and adopts the downloaded table last.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +16,11 @@
 
 enum { TRACK_RING = 10, TRACK_THREADS = 256, TRACK_INGEST_THREADS = 64, TRACK_MAX_TRACKS = 1024, TRACK_MAX_DETS = 1024, TRACK_MAX_DIM = 2048 };
 enum { TRACK_OP_MATCHED = 0, TRACK_OP_NEW = 1 };
+enum { TRACK_ASSOC_THREADS = 64, TRACK_ASSOC_CACHE_FLOATS = 28 * 1024 };   // one wave: the solver's column scan; dynamic LDS for the block of a stage (168 x 168)
+// Header of the device table (int32 each).  STOPPED: a frame ran out of slots; every later launch of the call returns at once.  FRAMES_DONE: frames
+// applied so far, the out-of-slots one included.  STOP_T / STOP_NEW: the live and the new tracks of that frame, for the error text.
+enum { TRACK_HDR_T = 0, TRACK_HDR_NEXT_ID, TRACK_HDR_N_FREE, TRACK_HDR_STOPPED, TRACK_HDR_M, TRACK_HDR_FRAMES_DONE, TRACK_HDR_STOP_T, TRACK_HDR_STOP_NEW, TRACK_HDR_INTS = 16 };
+enum { TRACK_ENTRY_INTS = 5 };       // slot, id, age, hits, tsu: a TrackEntry
 
 // Numeric state of every slot, in ONE device allocation that lives as long as the handle
 struct TrackState {
@@ -41,6 +51,8 @@ struct TrackPredictParams {
     double aw, mw;             // appearance and motion weight
     float max_dist;            // <= 0: no gate
     const int32_t* n_dev;      // non-null: the detection count lies there (track_ingest_kernel left it), d.n is not read
+    const int32_t* hdr;        // non-null (sequence call): the device table.  T is then the grid's upper bound, the row count is hdr[TRACK_HDR_T],
+    const int32_t* tab;        //   row t's slot is tab[TRACK_ENTRY_INTS * t], `slots` is not read; a set TRACK_HDR_STOPPED ends the launch at once
 };
 
 // The ingest launch of the fused detect-and-track call: one frame's kept records, where the suppression kernel left them, -> the staging image
@@ -56,6 +68,7 @@ struct TrackIngestParams {
     int32_t slots;
     float* boxes; float* foot; uint8_t* has; float* feat;   // the staging regions dets_of() describes
     int32_t* n_out;            // min(count, Q), for the predict launch
+    const int32_t* hdr;        // non-null (sequence call): a set TRACK_HDR_STOPPED ends the launch at once
 };
 
 struct TrackCommitParams {
@@ -63,13 +76,34 @@ struct TrackCommitParams {
     TrackDets d;
     int32_t M, D;
     const int32_t* ops;        // [M][4]: slot, detection, TRACK_OP_*, frames since the last update (after this frame's predict)
+    const int32_t* hdr;        // non-null (sequence call): M is the grid's upper bound, the list's length is hdr[TRACK_HDR_M]; TRACK_HDR_STOPPED as above
+};
+
+// The association of one frame on the device: what associate_update and the deletion loop of enqueue_commit (opd_track.cpp) do on the host, on the
+// matrices where the predict launch left them.  One workgroup of one wave.
+struct TrackAssocParams {
+    int32_t* hdr;              // [TRACK_HDR_INTS]
+    int32_t* tab;              // [S][TRACK_ENTRY_INTS] entries in creation order
+    int32_t* free_slots;       // [S] stack, handed out from the back
+    const float *app, *iou, *comb;   // [T][N], row stride N
+    const float* conf;         // confidence of detection j at conf[j * conf_stride]
+    int32_t conf_stride;
+    const int32_t* n_dev;      // non-null: N lies there; else n
+    int32_t n;
+    int32_t* ops;              // [S][4] out: the list of the commit launch
+    int32_t* ids;              // [N] out: the id of each detection, -1 where none
+    int32_t S, min_hits, max_age, frame;
+    double high_conf;
+    int32_t* unmatched;        // test hook only (else null): [1 + S] out, the count and the rows of the tracks no stage matched
 };
 
 hipError_t opd_launch_track_predict_cost(const TrackPredictParams& p, hipStream_t stream);
 hipError_t opd_launch_track_commit(const TrackCommitParams& p, hipStream_t stream);
 hipError_t opd_launch_track_ingest(const TrackIngestParams& p, hipStream_t stream);
+hipError_t opd_launch_track_assoc(const TrackAssocParams& p, hipStream_t stream);
 
 struct TrackEntry { int32_t slot, id, age, hits, tsu; };
+static_assert(sizeof(TrackEntry) == TRACK_ENTRY_INTS * 4, "the device table holds TrackEntry as it lies");
 
 struct opd_track {
     int32_t S = 0, NM = 0, D = 0;             // slots, detections per call, feature width
@@ -81,6 +115,7 @@ struct opd_track {
     TrackState st{};
     opd::Staging io;                          // one layout on both sides, fixed at creation (offsets below)
     size_t o_slots = 0, o_boxes = 0, o_foot = 0, o_has = 0, o_feat = 0, o_ops = 0, o_app = 0, o_iou = 0, o_comb = 0, o_n = 0, io_bytes = 0;
+    opd::Staging seq;                         // sequence calls: [table | ids | the call's detections], grown lazily to the largest call so far
     hipEvent_t ev_commit = nullptr;           // fused call: recorded on `stream` behind everything enqueued there, waited for by the detector's stream
     std::vector<TrackEntry> tracks;           // creation order: the reference's `self.tracks`
     std::vector<int32_t> free_slots;          // (popped from the back)
@@ -107,5 +142,13 @@ struct TrackFeatureSource {
 int track_fused_check(const opd_track* t, int device, int Q, int feature_dim, const char* who);
 int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* count, int Q, int frame, const TrackFeatureSource& src);
 int track_fused_finish(opd_track* t, const opd_det* recs, int n, int with_features, int32_t* out_ids, const char* who);
+
+// The tracker half of opd_detr_detect_sequence_track: B consecutive frames of one camera into ONE tracker, in frame order.
+//   track_sequence_enqueue  on the detector's stream `s`, behind the feature stage: the table upload, then per frame ingest -> predict / cost ->
+//                           association -> commit, then the download of table and ids (all before the caller's one wait)
+//   track_sequence_finish   after that wait: ids of the kept records into track_ids [B][Q], the table adopted, *frames_done; OPD_EINVAL where a
+//                           frame ran out of slots
+int track_sequence_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* counts, int Q, int B, const TrackFeatureSource& src, const char* who);
+int track_sequence_finish(opd_track* t, const int32_t* counts, int Q, int B, int32_t* track_ids, int32_t* frames_done, const char* who);
 
 }  // namespace opd

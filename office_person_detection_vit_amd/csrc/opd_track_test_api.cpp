@@ -1,7 +1,12 @@
 // opd_track_test_api.cpp — what the tracker computed, for tests/ and tools/ (exported from libopd_hip_test.so only): the three cost
-// matrices of the last update, the device state of one track, and the ingest launch of the fused detect-and-track call on records of the caller.
+// matrices of the last update, the device state of one track, the ingest launch of the fused detect-and-track call on records of the caller, and the
+// association kernel of the sequence calls next to the host's association on matrices of the caller.
 #include <string.h>
+#include <time.h>
 
+#include <algorithm>
+
+#include "opd_assoc.h"
 #include "opd_track.h"
 
 using namespace opd;
@@ -76,5 +81,132 @@ TAPI int opd_track_test_ingest(int device, const opd_det* records, int n, int Q,
     HIPCHK(hipMemcpy(has, p.has, (size_t)Q, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(feat, p.feat, (size_t)Q * D * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(n_out, p.n_out, 4, hipMemcpyDeviceToHost));
+    return OPD_OK;
+}
+
+// The inputs of track_assoc_kernel for the two hooks below: a table of T tracks (row i in slot i, hits[i] matches so far) and n_free free slots, the
+// matrices and confidences of the caller on the device, room for every output
+struct AssocRig {
+    DevMem tmp;
+    TrackAssocParams p{};
+    std::vector<int32_t> hdr, tab, stack;
+    int S = 1;
+    bool make(const float* app, const float* iou, const float* comb, int T, int N, const int32_t* hits, const float* conf, int min_hits, double high_conf, int n_free) {
+        S = std::max(1, T + n_free);
+        hdr.assign(TRACK_HDR_INTS, 0); tab.assign((size_t)S * TRACK_ENTRY_INTS, 0); stack.assign(S, 0);
+        hdr[TRACK_HDR_T] = T; hdr[TRACK_HDR_NEXT_ID] = T + 1; hdr[TRACK_HDR_N_FREE] = n_free;
+        for (int i = 0; i < T; ++i) { int32_t* e = &tab[(size_t)i * TRACK_ENTRY_INTS]; e[0] = i; e[1] = i + 1; e[2] = 1; e[3] = hits[i]; e[4] = 0; }
+        for (int k = 0; k < n_free; ++k) stack[k] = T + n_free - 1 - k;   // (slot T is handed out first)
+        const size_t cells = std::max<size_t>(1, (size_t)T * N);
+        p.hdr = tmp.up(hdr.data(), hdr.size());
+        p.tab = tmp.up(tab.data(), tab.size());
+        p.free_slots = tmp.up(stack.data(), stack.size());
+        p.app = tmp.up(T > 0 && N > 0 ? app : nullptr, cells);
+        p.iou = tmp.up(T > 0 && N > 0 ? iou : nullptr, cells);
+        p.comb = tmp.up(T > 0 && N > 0 ? comb : nullptr, cells);
+        p.conf = tmp.up(N > 0 ? conf : nullptr, (size_t)std::max(1, N));
+        p.conf_stride = 1;
+        p.n = N;
+        p.ops = tmp.alloc<int32_t>((size_t)S * 4);
+        p.ids = tmp.alloc<int32_t>((size_t)std::max(1, N));
+        p.unmatched = tmp.alloc<int32_t>((size_t)S + 1);
+        p.S = S; p.min_hits = min_hits; p.max_age = 1 << 30; p.frame = 0;
+        p.high_conf = high_conf;
+        return tmp.ok;
+    }
+};
+
+// track_assoc_kernel alone, and the host's associate() on the same inputs: app / iou / comb [T][N] (host), hits [T], conf [N]; the table the kernel sees
+// has T tracks (row i in slot i) and n_free free slots.  Per side (k_*: the kernel, h_*: the host): matches [min(T, N)][2] as (track row, detection) in
+// order, new detections [N], unmatched tracks [T], each with its count.  Both sides after the out-of-slots rule (more new detections than free
+// slots drops matches and new detections); the unmatched tracks are what the stages left, before that rule.
+TAPI int opd_track_test_assoc(int device, const float* app, const float* iou, const float* comb, int T, int N, const int32_t* hits, const float* conf, int min_hits,
+                              double high_conf, int n_free, int32_t* k_matches, int32_t* k_n_matches, int32_t* k_new, int32_t* k_n_new, int32_t* k_unmatched,
+                              int32_t* k_n_unmatched, int32_t* h_matches, int32_t* h_n_matches, int32_t* h_new, int32_t* h_n_new, int32_t* h_unmatched,
+                              int32_t* h_n_unmatched) {
+    ApiScope api_scope;
+    if (T < 0 || N < 0 || n_free < 0 || T + n_free > TRACK_MAX_TRACKS || N > TRACK_MAX_DETS) return fail(OPD_EINVAL, "opd_track_test_assoc: size out of range");
+    if ((T > 0 && N > 0 && (!app || !iou || !comb)) || (T > 0 && !hits) || (N > 0 && !conf)) return fail(OPD_EINVAL, "opd_track_test_assoc: null input");
+    if (!k_matches || !k_n_matches || !k_new || !k_n_new || !k_unmatched || !k_n_unmatched || !h_matches || !h_n_matches || !h_new || !h_n_new || !h_unmatched || !h_n_unmatched)
+        return fail(OPD_EINVAL, "opd_track_test_assoc: null output");
+    // ---- the host
+    AssocResult a;
+    associate(app, iou, comb, T, N, hits, conf, min_hits, high_conf, &a);
+    *h_n_unmatched = (int32_t)a.unmatched_tracks.size();
+    for (size_t k = 0; k < a.unmatched_tracks.size(); ++k) h_unmatched[k] = a.unmatched_tracks[k];
+    if (a.new_dets.size() > (size_t)n_free) { a.matches.clear(); a.new_dets.clear(); }
+    *h_n_matches = (int32_t)a.matches.size();
+    for (size_t k = 0; k < a.matches.size(); ++k) { h_matches[2 * k] = a.matches[k].first; h_matches[2 * k + 1] = a.matches[k].second; }
+    *h_n_new = (int32_t)a.new_dets.size();
+    for (size_t k = 0; k < a.new_dets.size(); ++k) h_new[k] = a.new_dets[k];
+    // ---- the kernel
+    RCCHK(use_device("opd_track_test_assoc", device));
+    AssocRig rig;
+    if (!rig.make(app, iou, comb, T, N, hits, conf, min_hits, high_conf, n_free)) return fail(OPD_ENOMEM, "opd_track_test_assoc: device allocation failed");
+    const TrackAssocParams& p = rig.p;
+    const int S = rig.S;
+    std::vector<int32_t>& hdr = rig.hdr;
+    HIPCHK(opd_launch_track_assoc(p, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<int32_t> ops((size_t)S * 4), un((size_t)S + 1);
+    HIPCHK(hipMemcpy(hdr.data(), p.hdr, hdr.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ops.data(), p.ops, ops.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(un.data(), p.unmatched, un.size() * 4, hipMemcpyDeviceToHost));
+    const int M = hdr[TRACK_HDR_M];
+    if (M < 0 || M > S || un[0] < 0 || un[0] > T) return fail(OPD_EHIP, "opd_track_test_assoc: the kernel left " + std::to_string(M) + " list entries and " + std::to_string(un[0]) + " unmatched tracks");
+    *k_n_matches = *k_n_new = 0;
+    for (int k = 0; k < M; ++k) {
+        const int32_t* op = &ops[(size_t)k * 4];
+        if (op[2] == TRACK_OP_MATCHED) {
+            if (*k_n_matches >= std::min(T, N)) return fail(OPD_EHIP, "opd_track_test_assoc: more matches than min(T, N)");
+            k_matches[2 * *k_n_matches] = op[0]; k_matches[2 * *k_n_matches + 1] = op[1]; ++*k_n_matches;
+        } else {
+            if (*k_n_new >= N) return fail(OPD_EHIP, "opd_track_test_assoc: more new detections than N");
+            k_new[(*k_n_new)++] = op[1];
+        }
+    }
+    *k_n_unmatched = un[0];
+    for (int k = 0; k < un[0]; ++k) k_unmatched[k] = un[1 + k];
+    return OPD_OK;
+}
+
+// Time of track_assoc_kernel alone and of the host's associate() on the same inputs (tools/bench_track_sequence.py): the mean of `iters` runs each, in
+// milliseconds.  The kernel between two events per launch (the table is put back before each, outside the events); the host by its own clock.
+TAPI int opd_track_test_bench_assoc(int device, const float* app, const float* iou, const float* comb, int T, int N, const int32_t* hits, const float* conf, int min_hits,
+                                    double high_conf, int n_free, int iters, float* kernel_ms, float* host_ms) {
+    ApiScope api_scope;
+    if (T < 1 || N < 1 || n_free < 0 || T + n_free > TRACK_MAX_TRACKS || N > TRACK_MAX_DETS || iters < 1) return fail(OPD_EINVAL, "opd_track_test_bench_assoc: size out of range");
+    if (!app || !iou || !comb || !hits || !conf || !kernel_ms || !host_ms) return fail(OPD_EINVAL, "opd_track_test_bench_assoc: null argument");
+    RCCHK(use_device("opd_track_test_bench_assoc", device));
+    AssocRig rig;
+    if (!rig.make(app, iou, comb, T, N, hits, conf, min_hits, high_conf, n_free)) return fail(OPD_ENOMEM, "opd_track_test_bench_assoc: device allocation failed");
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    double sum = 0.0;
+    int rc = OPD_OK;
+    for (int k = 0; k < iters + 3 && rc == OPD_OK; ++k) {   // (three launches to warm up)
+        hipError_t e = hipMemcpyAsync(rig.p.hdr, rig.hdr.data(), rig.hdr.size() * 4, hipMemcpyHostToDevice, nullptr);
+        if (e == hipSuccess) e = hipMemcpyAsync(rig.p.tab, rig.tab.data(), rig.tab.size() * 4, hipMemcpyHostToDevice, nullptr);
+        if (e == hipSuccess) e = hipMemcpyAsync(rig.p.free_slots, rig.stack.data(), rig.stack.size() * 4, hipMemcpyHostToDevice, nullptr);
+        if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
+        if (e == hipSuccess) e = opd_launch_track_assoc(rig.p, nullptr);
+        if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        if (e != hipSuccess) rc = fail(OPD_EHIP, std::string("opd_track_test_bench_assoc: ") + hipGetErrorString(e));
+        if (k >= 3) sum += ms;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    RCCHK(rc);
+    *kernel_ms = (float)(sum / iters);
+    AssocResult a;
+    timespec t0{}, t1{};
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    for (int k = 0; k < iters; ++k) associate(app, iou, comb, T, N, hits, conf, min_hits, high_conf, &a);
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    *host_ms = (float)(((double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6) / iters);
     return OPD_OK;
 }

@@ -664,15 +664,9 @@ class HipDetrDetector:
         if features == "reid" and not reid.is_loaded:
             raise RuntimeError("Re-ID model is not loaded: call load_model() first")
         self._sync_nms()
-        target = self._frame_list_target([frame]) if (self.frame_lists and isinstance(frame, np.ndarray)) else None
+        target = self._fused_track_target([frame], tracker, features, reid)
         Q = self._info.num_queries
-        width = {None: None, "encoder": self._info.d_model, "color": 256, "reid": int(reid.feature_dim) if reid is not None else None}[features]
-        fused = (self._nms_set is not None and target is not None and tracker.device_ordinal == self.device_ordinal and tracker.max_dets >= Q
-                 and (width is None or tracker.feature_dim == width))
-        if features in ("encoder", "color"):
-            fused = fused and self._info.d_model == 256 and not (features == "color" and max(frame.shape[:2]) > 4096)
-        if features == "reid":
-            fused = fused and reid._ordinal() == self.device_ordinal
+        fused = target is not None
         if not fused:
             if features is None:
                 return tracker.update(self.detect(frame))
@@ -693,6 +687,59 @@ class HipDetrDetector:
         detections = self._postprocess_batch(recs, counts, Q)[0]
         tracker._apply(detections, ids[:len(detections)])
         return [det for det in detections if det.track_id is not None]
+
+    def _fused_track_target(self, frames: Sequence[np.ndarray], tracker, features: Optional[str], reid) -> Optional[Tuple[int, int]]:
+        """The model input size when ``frames`` can enter ``tracker`` inside the detect call (``detect_and_track`` has the conditions), else None."""
+        target = self._frame_list_target(frames) if (self.frame_lists and all(isinstance(f, np.ndarray) for f in frames)) else None
+        Q = self._info.num_queries
+        width = {None: None, "encoder": self._info.d_model, "color": 256, "reid": int(reid.feature_dim) if reid is not None else None}[features]
+        fused = (self._nms_set is not None and target is not None and tracker.device_ordinal == self.device_ordinal and tracker.max_dets >= Q
+                 and (width is None or tracker.feature_dim == width))
+        if features in ("encoder", "color"):
+            fused = fused and self._info.d_model == 256 and not (features == "color" and max(frames[0].shape[:2]) > 4096)
+        if features == "reid":
+            fused = fused and reid._ordinal() == self.device_ordinal
+        return target if fused else None
+
+    def detect_and_track_batch(self, frames: Sequence[np.ndarray], tracker, features: Optional[str] = "color", reid=None, reid_slots: int = 32) -> List[List[Detection]]:
+        """``[self.detect_and_track(f, tracker, ...) for f in frames]`` for CONSECUTIVE frames of one camera, in chunks of ``max_batch``: each chunk
+        is ONE native call with one batched forward and one host wait (``opd_detr_detect_sequence_track``); the association between the frames
+        of a chunk runs on the device.  Same ids and track states as the loop.  For Re-ID a chunk shares
+        ``min(max_crops, max_dets, reid_slots * len(chunk))`` crop slots, handed out in (frame, score) order.  Where the conditions of the fused
+        single-frame call fail, the loop runs instead."""
+        self._require_model()
+        if features not in (None, "encoder", "color", "reid"):
+            raise ValueError(f"features must be None, 'encoder', 'color' or 'reid', got {features!r}")
+        if features == "reid" and reid is None:
+            raise ValueError("features='reid' needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
+        if features == "reid" and not reid.is_loaded:
+            raise RuntimeError("Re-ID model is not loaded: call load_model() first")
+        frames = list(frames)
+        out: List[List[Detection]] = []
+        kind = {None: _capi.OPD_TRACK_FEAT_NONE, "encoder": _capi.OPD_TRACK_FEAT_ENCODER, "color": _capi.OPD_TRACK_FEAT_COLOR, "reid": _capi.OPD_TRACK_FEAT_REID}[features]
+        for start in range(0, len(frames), self.max_batch):
+            chunk = frames[start:start + self.max_batch]
+            self._sync_nms()
+            target = self._fused_track_target(chunk, tracker, features, reid)
+            if target is None:
+                out.extend(self.detect_and_track(f, tracker, features=features, reid=reid, reid_slots=reid_slots) for f in chunk)
+                continue
+            tracker._ensure()
+            B, Q = len(chunk), self._info.num_queries
+            slots = max(1, min(int(reid.max_crops), int(tracker.max_dets), int(reid_slots) * B)) if features == "reid" else 0
+            recs, counts = (_capi.OpdDet * (B * Q))(), (C.c_int32 * B)()
+            ids, n_featured, done = np.full(B * Q, -1, np.int32), np.zeros(B, np.int32), C.c_int32(0)
+            ptrs = (C.c_void_p * B)(*[f.ctypes.data for f in chunk])
+            h, w = int(chunk[0].shape[0]), int(chunk[0].shape[1])
+            rc = self._lib.opd_detr_detect_sequence_track(C.c_void_p(self.model), reid._handle if features == "reid" else None, tracker._h, ptrs, B, h, w, target[0],
+                                                          target[1], float(self.confidence_threshold), PERSON_LABEL, kind, slots, recs, counts, ids.ctypes.data,
+                                                          n_featured.ctypes.data, C.byref(done))
+            if rc != 0 and "counted as one without detections" not in _capi.last_error():
+                _capi.check(rc, "opd_detr_detect_sequence_track")
+            self._last_orig = [(h, w)] * B
+            per_frame = self._postprocess_batch(recs, counts, Q)
+            out.extend(tracker._replay(per_frame, ids, done.value, rc, "opd_detr_detect_sequence_track", stride=Q))
+        return out
 
     def extract_color_features(self, frame: np.ndarray, detections: List[Detection]) -> np.ndarray:
         """(N, 256) float32 colour-histogram features of the detections' crops of ``frame`` (BGR uint8 ``[H, W, 3]``), on the

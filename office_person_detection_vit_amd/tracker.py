@@ -109,6 +109,61 @@ class HipTracker:
         self._apply(detections, ids[:n])
         return [det for det in detections if det.track_id is not None]
 
+    def update_sequence(self, detections_per_frame: List[List[Detection]]) -> List[List[Detection]]:
+        """``[self.update(d) for d in detections_per_frame]`` as ONE ``opd_track_update_sequence``: every frame's detections go to the device
+        once, the association runs there between the frames, and the host waits once.  Same ids, same track states.  In
+        ``TrackingPhase.execute`` the loop over ``tracker.update`` becomes this one call.  Where a frame runs out of slots the frames before
+        it are applied, that frame counts as one without detections, and the error is raised as ``update`` raises it."""
+        frames = [list(d) for d in detections_per_frame]
+        if not frames:
+            return []
+        D = self.feature_dim
+        counts = np.array([len(f) for f in frames], np.int32)
+        if counts.max() > self.max_dets:
+            raise ValueError(f"a frame has {int(counts.max())} detections, the tracker was made for max_dets = {self.max_dets}")
+        flat = [det for f in frames for det in f]
+        n = len(flat)
+        boxes, foot, conf = np.zeros((n, 4), np.float32), np.zeros((n, 2), np.float32), np.zeros(n, np.float32)
+        has = np.zeros(n, np.uint8)
+        feats = None
+        for j, det in enumerate(flat):
+            if det.camera_coords is None:
+                raise ValueError(f"detection {j} has no camera_coords: a track cannot be started or updated without a foot point")
+            boxes[j], foot[j], conf[j] = det.bbox, det.camera_coords, det.confidence
+            if det.features is not None:
+                f = np.asarray(det.features, np.float32).reshape(-1)
+                if f.shape[0] != D:
+                    raise ValueError(f"detection {j} has a feature of width {f.shape[0]}, the tracker was made for {D}")
+                if feats is None:
+                    feats = np.zeros((n, D), np.float32)
+                feats[j], has[j] = f, 1
+        self._ensure()
+        ids, done = np.full(max(n, 1), -1, np.int32), C.c_int32(0)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        rc = self._lib.opd_track_update_sequence(self._h, p(boxes), p(foot), p(conf), p(feats), p(has), _capi.OPD_MEM_HOST, p(counts), len(frames), p(ids),
+                                                 C.byref(done))
+        stopped = rc != 0 and "counted as one without detections" in _capi.last_error()
+        if rc != 0 and not stopped:
+            _capi.check(rc, "opd_track_update_sequence")
+        return self._replay(frames, ids, done.value, rc, "opd_track_update_sequence")
+
+    def _replay(self, frames: List[List[Detection]], ids: np.ndarray, done: int, rc: int, what: str, stride: Optional[int] = None) -> List[List[Detection]]:
+        """The mirror after a sequence call: ``_apply`` frame by frame for the ``done`` frames the native side applied (the last of them an empty
+        one when it ran out of slots, before the error is raised).  ``ids``: packed frame after frame, or ``stride`` apart."""
+        message = _capi.last_error() if rc != 0 else ""
+        out, at = [], 0
+        for f, dets in enumerate(frames[:done]):
+            last = f == done - 1
+            if rc != 0 and last:
+                self._apply([], ids[:0])
+            else:
+                self._apply(dets, ids[at:at + len(dets)], verify=last)
+                out.append([det for det in dets if det.track_id is not None])
+            at += stride if stride is not None else len(dets)
+        if rc != 0:
+            raise RuntimeError(f"{what} failed (code {rc}): {message}")
+        return out
+
     def get_tracks(self) -> List[HipTrack]:
         return self.tracks.copy()
 
@@ -145,8 +200,9 @@ class HipTracker:
                 return [float(v) for v in r.x]
         raise KeyError(f"track {track_id} is not alive")
 
-    def _apply(self, detections: List[Detection], ids: np.ndarray) -> None:
-        """Replay on the host objects what the native update did to its counters: predict, matches, new tracks, deletions."""
+    def _apply(self, detections: List[Detection], ids: np.ndarray, verify: bool = True) -> None:
+        """Replay on the host objects what the native update did to its counters: predict, matches, new tracks, deletions.  ``verify=False``:
+        a frame of a sequence call that is not its last, so the native side is already further on."""
         by_id: Dict[int, HipTrack] = {t.track_id: t for t in self.tracks}
         for t in self.tracks:
             t.time_since_update += 1
@@ -166,6 +222,8 @@ class HipTracker:
                 t.time_since_update = 0
                 t.trajectory.append(det.camera_coords)
         self.tracks = [t for t in self.tracks if t.time_since_update < self.max_age]
+        if not verify:
+            return
         info = _capi.OpdTrackStatus()
         _capi.check(self._lib.opd_track_info(self._h, C.byref(info)), "opd_track_info")
         self.next_id = info.next_id
