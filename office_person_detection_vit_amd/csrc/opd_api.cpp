@@ -1,8 +1,9 @@
 // opd_api.cpp — the C-ABI of include/opd_detr.h for the detector: handle creation / cloning / destruction, the argument checks of every
-// entry point, and the ONE detect pipeline behind them (frame source -> device pixels -> forward -> post-process -> feature step -> records).
+// entry point, and the ONE detect pipeline behind them (frame source -> device pixels -> forward -> the sink's stages -> one fetch; opd_model.h).
 // The model itself is opd_weights.cpp (the weights) and opd_model.cpp (workspace, plans, the forward and its graph cache).
 #include <algorithm>
 #include <new>
+#include <optional>
 #include <stdexcept>
 
 #include "opd_floor.h"
@@ -44,14 +45,10 @@ int check_shape(opd_detr* m, const void* pixels, int pixel_format, int mem_kind,
 
 static int stage_pixels(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W, const void** d_pixels) {
     if (pixels_on_device(mem_kind)) { *d_pixels = pixels; return OPD_OK; }
-    const size_t n = (size_t)B * H * W * 3;
-    if (pixel_format == OPD_PIXELS_U8_BGR_HWC) {
-        HIPCHK(hipMemcpyAsync(m->d_u8, pixels, n, hipMemcpyHostToDevice, m->stream));
-        *d_pixels = m->d_u8;
-    } else {
-        HIPCHK(hipMemcpyAsync(m->d_pv, pixels, n * 4, hipMemcpyHostToDevice, m->stream));
-        *d_pixels = m->d_pv;
-    }
+    const bool u8 = pixel_format == OPD_PIXELS_U8_BGR_HWC;
+    void* dst = u8 ? static_cast<void*>(m->d_u8) : m->d_pv;
+    HIPCHK(hipMemcpyAsync(dst, pixels, (size_t)B * H * W * 3 * (u8 ? 1 : 4), hipMemcpyHostToDevice, m->stream));
+    *d_pixels = dst;
     return OPD_OK;
 }
 
@@ -74,19 +71,25 @@ static int resize_tab(opd_detr* m, int h, int w, int oh, int ow, const opd_detr:
     return OPD_OK;
 }
 
+// A camera frame of h x w: what the resize tables and the byte counts of the source step are sized for (each entry words its own refusal)
+static inline bool frame_size_ok(int h, int w) { return h >= 1 && w >= 1 && (size_t)h * w <= (size_t)1 << 26; }
+
+// Host camera frames -> m->src, one behind the other: ONE block, or (`list` != null) one host pointer per frame
+static int upload_camera_frames(opd_detr* m, const uint8_t* block, const uint8_t* const* list, int n, int h, int w) {
+    const size_t n1 = (size_t)h * w * 3;
+    RCCHK(m->src.reserve("source frames", 0, n * n1, m->stream));
+    if (!list) HIPCHK(hipMemcpyAsync(m->src.dev, block, n * n1, hipMemcpyHostToDevice, m->stream));
+    else for (int b = 0; b < n; ++b) HIPCHK(hipMemcpyAsync(m->src.dev + b * n1, list[b], n1, hipMemcpyHostToDevice, m->stream));
+    return OPD_OK;
+}
+
 // Frames at camera resolution -> m->d_u8 at model resolution (Pillow-exact bilinear, kernels_untyped.hip).
 // (`list` != null: one host pointer per frame instead of the contiguous block `frames`)
 static int enqueue_resize(opd_detr* m, const uint8_t* frames, int mem_kind, int B, int h, int w, int oh, int ow, const uint8_t* const* list = nullptr) {
-    if (h < 1 || w < 1 || (size_t)h * w > (size_t)1 << 26) return fail(OPD_EINVAL, "source frame size out of range");
-    const size_t need = (size_t)B * h * w * 3;
+    if (!frame_size_ok(h, w)) return fail(OPD_EINVAL, "source frame size out of range");
     const uint8_t* d_in = frames;
     if (!pixels_on_device(mem_kind)) {
-        RCCHK(m->src.reserve("source frames", 0, need, m->stream));
-        if (list) {
-            for (int b = 0; b < B; ++b) HIPCHK(hipMemcpyAsync(m->src.dev + (size_t)b * h * w * 3, list[b], (size_t)h * w * 3, hipMemcpyHostToDevice, m->stream));
-        } else {
-            HIPCHK(hipMemcpyAsync(m->src.dev, frames, need, hipMemcpyHostToDevice, m->stream));
-        }
+        RCCHK(upload_camera_frames(m, frames, list, B, h, w));
         d_in = m->src.dev;
     }
     const opd_detr::ResizeTab* tab = nullptr;
@@ -95,13 +98,38 @@ static int enqueue_resize(opd_detr* m, const uint8_t* frames, int mem_kind, int 
     return OPD_OK;
 }
 
+// A small host table that rarely changes from call to call (the frame sizes, the tile windows of a video): uploaded only when it does
+static int upload_if_changed(opd_detr* m, const std::vector<int32_t>& now, std::vector<int32_t>* kept, int32_t* dev) {
+    if (now == *kept) return OPD_OK;
+    HIPCHK(hipStreamSynchronize(m->stream));   // (an earlier asynchronous copy may still be reading the old host vector)
+    *kept = now;                               // member: must outlive the async copy
+    HIPCHK(hipMemcpyAsync(dev, kept->data(), kept->size() * 4, hipMemcpyHostToDevice, m->stream));
+    return OPD_OK;
+}
+
+// SRC_TILES: every frame once, whole, into m->src; its windows, from where it lies, -> the stem's input block (kernels_tile.hip)
+static int enqueue_tiles(opd_detr* m, const FrameSource& src, int H, int W) {
+    RCCHK(upload_camera_frames(m, nullptr, static_cast<const uint8_t* const*>(src.frames), src.n_frames, src.h, src.w));
+    if (!m->d_tiles) RCCHK(dalloc(m, &m->d_tiles, (size_t)m->cfg.max_batch * 4, false));
+    RCCHK(upload_if_changed(m, std::vector<int32_t>(src.tiles, src.tiles + (size_t)src.n_tiles * 4), &m->h_tiles, m->d_tiles));
+    const int th = src.box_h(), tw = src.box_w();
+    const opd_detr::ResizeTab* tab = nullptr;
+    RCCHK(resize_tab(m, th, tw, H, W, &tab));
+    TileResizeParams rp{m->src.dev, m->d_u8, m->d_tiles, src.n_frames, src.n_tiles, src.h, src.w, th, tw, H, W, tab->bh, tab->kh, tab->bv, tab->kv, tab->ksh, tab->ksv};
+    return launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_tile_resize_u8(rp, m->stream); });
+}
+
 // The source step of every detect / forward entry point: the frames of `src` -> `*d_pixels`, device pixels at model resolution H x W.
 // `*d_camera`: where the camera-resolution frames now lie on the device (d_src, or the caller's block, when they were resized; d_u8 when not).
 static int stage_frames(opd_detr* m, const FrameSource& src, int B, int H, int W, const void** d_pixels, const uint8_t** d_camera) {
     if (src.kind == SRC_PIXELS) return stage_pixels(m, src.frames, src.pixel_format, src.mem_kind, B, H, W, d_pixels);
+    *d_pixels = *d_camera = m->d_u8;
+    if (src.kind == SRC_TILES) {
+        *d_camera = m->src.dev;   // (whole frames)
+        return enqueue_tiles(m, src, H, W);
+    }
     const uint8_t* block = src.kind == SRC_BLOCK ? static_cast<const uint8_t*>(src.frames) : nullptr;
     const uint8_t* const* list = src.kind == SRC_LIST ? static_cast<const uint8_t* const*>(src.frames) : nullptr;
-    *d_pixels = *d_camera = m->d_u8;
     if (list && src.h == H && src.w == W) {
         const size_t n1 = (size_t)H * W * 3;
         for (int b = 0; b < B; ++b) HIPCHK(hipMemcpyAsync(m->d_u8 + b * n1, list[b], n1, hipMemcpyHostToDevice, m->stream));
@@ -112,81 +140,165 @@ static int stage_frames(opd_detr* m, const FrameSource& src, int B, int H, int W
     return OPD_OK;
 }
 
+// ---- buffers of the optional stages: allocated by the first call of the stage that uses them (a page-locked twin of the same size with some) ----
+template <typename T>
+static int ensure(opd_detr* m, T** dev, size_t count, void** pinned = nullptr) {
+    if (*dev) return OPD_OK;
+    RCCHK(dalloc(m, dev, count, false));
+    if (pinned) HIPCHK(hipHostMalloc(pinned, count * sizeof(T), hipHostMallocDefault));
+    return OPD_OK;
+}
+static size_t slots_of(const opd_detr* m) { return (size_t)m->cfg.max_batch * m->arch.queries; }   // record slots of a full batch
+static int ensure_nms_flag(opd_detr* m) {
+    if (m->d_nms_flag) return OPD_OK;
+    RCCHK(ensure(m, &m->d_nms_flag, 1));
+    HIPCHK(hipMemsetAsync(m->d_nms_flag, 0, 4, m->stream));
+    return OPD_OK;
+}
+// The merged records of a tiled call lie as [counts of max_batch frames | records]
+static size_t tile_out_off(const opd_detr* m) { return align_up((size_t)m->cfg.max_batch * 4, 64); }   // where the records begin
+static int ensure_tile_out(opd_detr* m) { return ensure(m, &m->d_tile_out, tile_out_off(m) + slots_of(m) * sizeof(opd_tile_det), &m->tile_pinned); }
+// The records leave the device as ONE block, the d_records allocation as it lies: [records of max_batch frames | counts | feature rows]
+static size_t rec_bytes(const opd_detr* m) { return slots_of(m) * sizeof(opd_det); }   // = offset of the counts
+static size_t feat_off(const opd_detr* m) { return reinterpret_cast<const char*>(m->d_feat_all) - reinterpret_cast<const char*>(m->d_records); }
+static size_t feat_row(const opd_detr* m) { return (size_t)m->arch.queries * m->arch.d_model * 4; }   // a frame's feature rows
+static int ensure_sync_pinned(opd_detr* m) {
+    if (!m->sync_pinned) HIPCHK(hipHostMalloc(&m->sync_pinned, feat_off(m) + m->cfg.max_batch * feat_row(m), hipHostMallocDefault));
+    return OPD_OK;
+}
+
+// ---- the stages of the sink, in the order deliver_records runs them ----------------------------------------------------------------------
 // Person filter + greedy IoU-NMS in place on device records (kernels_nms.hip), through the launch helper like the post-process before it
 static int enqueue_nms(opd_detr* m, opd_det* dets, int32_t* counts, int n_frames, int stride, int label, float threshold) {
-    if (!m->d_nms_flag) {
-        RCCHK(dalloc(m, &m->d_nms_flag, 1, false));
-        HIPCHK(hipMemsetAsync(m->d_nms_flag, 0, 4, m->stream));
-    }
+    RCCHK(ensure_nms_flag(m));
     NmsParams np{dets, counts, m->d_nms_flag, n_frames, stride, label, threshold};
     return launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_person_nms(np, m->stream); });
 }
 
 // `orig_hw` (nullable): the frame sizes the boxes are scaled to, else h x w for every frame.  `dev_out` / `dev_counts` (nullable): device buffers of the
 // caller; the kernel then writes there directly instead of the library's own record buffers (no device-to-device copies afterwards).
-// `tiled` (nullable; opd_detr_detect_tiled): the suppression behind the post-process is this call's, not the handle's opd_detr_set_nms state.
-static int enqueue_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, int h, int w, opd_det* dev_out, int32_t* dev_counts,
-                               const opd_tile_params* tiled = nullptr) {
+// `nms_label`, `nms_threshold`: the suppression behind it (off while the threshold is negative)
+static int enqueue_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, int h, int w, opd_det* dev_out, int32_t* dev_counts, int nms_label,
+                               float nms_threshold) {
     const int B = m->last_B;
     std::vector<int32_t> hw((size_t)B * 2);
     for (int b = 0; b < B; ++b) {
         hw[2 * b] = orig_hw ? orig_hw[2 * b] : h;
         hw[2 * b + 1] = orig_hw ? orig_hw[2 * b + 1] : w;
     }
-    if (hw != m->h_orig_hw) {   // the frame sizes of a video do not change from call to call: upload only when they do
-        HIPCHK(hipStreamSynchronize(m->stream));   // (an earlier asynchronous copy may still be reading the old host vector)
-        m->h_orig_hw = hw;      // member: must outlive the async copy
-        HIPCHK(hipMemcpyAsync(m->d_orig_hw, m->h_orig_hw.data(), m->h_orig_hw.size() * 4, hipMemcpyHostToDevice, m->stream));
-    }
+    RCCHK(upload_if_changed(m, hw, &m->h_orig_hw, m->d_orig_hw));
     PostParams pp{};
     pp.logits = m->d_logits; pp.boxes = m->d_boxes; pp.orig_hw = m->d_orig_hw;
     pp.records = dev_out ? dev_out : m->d_records;
     pp.counts = dev_counts ? dev_counts : m->d_counts;
     pp.B = B; pp.Q = m->arch.queries; pp.ncls = m->arch.ncls; pp.threshold = threshold;
     RCCHK(launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_postprocess(pp, m->stream); }));
-    const int nms_label = tiled ? tiled->person_label : m->nms_label;
-    const float nms_threshold = tiled ? tiled->tile_nms_threshold : m->nms_threshold;
-    if (nms_threshold >= 0.f)   // opd_detr_set_nms: the stages behind, and the caller, see final records in score order (in front of mark 8: the
-        RCCHK(enqueue_nms(m, static_cast<opd_det*>(pp.records), pp.counts, B, pp.Q, nms_label, nms_threshold));   // kernel's time is part of stage_ms[7])
+    if (nms_threshold >= 0.f)   // the stages behind, and the caller, see final records in score order (in front of mark 8: the kernel's time is part of stage_ms[7])
+        RCCHK(enqueue_nms(m, static_cast<opd_det*>(pp.records), pp.counts, B, pp.Q, nms_label, nms_threshold));
     MARK(8);
     return OPD_OK;
 }
 
-// The records leave the device as ONE block, the d_records allocation as it lies: [records of max_batch frames | counts | feature rows]
-static size_t rec_bytes(const opd_detr* m) { return (size_t)m->cfg.max_batch * m->arch.queries * sizeof(opd_det); }   // = offset of the counts
-static size_t feat_off(const opd_detr* m) { return reinterpret_cast<const char*>(m->d_feat_all) - reinterpret_cast<const char*>(m->d_records); }
-static size_t feat_row(const opd_detr* m) { return (size_t)m->arch.queries * m->arch.d_model * 4; }   // a frame's feature rows
-// ... and a page-locked copy of it is taken apart into the caller's arrays here (fetch_records, opd_detr_wait)
+// What the seam merge takes from the caller's parameter block and sizes (the tile stage here, merge_tiles on host records)
+static void fill_tile_merge(TileMergeParams* mp, const opd_tile_params* p, int n_frames, int n_tiles, int stride, int h, int w) {
+    mp->n_frames = n_frames; mp->n_tiles = n_tiles; mp->stride = stride; mp->frame_h = h; mp->frame_w = w;
+    mp->merge_nms_threshold = p->merge_nms_threshold; mp->merge_threshold = p->merge_threshold; mp->edge_tolerance = p->edge_tolerance;
+}
+// The tile stage: the records of every frame's tiles (tile pixels, suppressed per tile) -> frame pixels, merged across the seams (kernels_tile.hip)
+static int enqueue_tile_merge(opd_detr* m, const TileStage& t) {
+    RCCHK(ensure_tile_out(m));
+    RCCHK(ensure_nms_flag(m));
+    TileMergeParams mp{};
+    mp.recs = m->d_records; mp.tile_counts = m->d_counts; mp.tiles_yxhw = m->d_tiles;
+    mp.counts = reinterpret_cast<int32_t*>(m->d_tile_out); mp.out = reinterpret_cast<opd_tile_det*>(m->d_tile_out + tile_out_off(m)); mp.flag = m->d_nms_flag;
+    fill_tile_merge(&mp, t.params, t.n_frames, t.n_tiles, m->arch.queries, t.frame_h, t.frame_w);
+    return launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_tile_merge(mp, m->stream); });
+}
+
+// The feature stage, on the records the post-process left on the device.  (h, w): the camera resolution of the frames at d_camera (FEAT_COLOR, FEAT_REID).
+// Returns in *rows what a tracker behind it may read: nothing, a row per query in d_feat_all, or a row per slot of the Re-ID call.  `reid` is
+// the caller's: the call holds the Re-ID handle's lock and must outlive the wait.
+static int enqueue_features(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera, std::optional<ReidFusedCall>* reid, TrackFeatureSource* rows) {
+    const int B = m->last_B, Q = m->arch.queries;
+    const FeatureStage& f = s.feature;
+    *rows = TrackFeatureSource{};
+    if (f.kind == FEAT_NONE) return OPD_OK;
+    if (f.kind == FEAT_REID) {   // select, plan and the Re-ID forward behind the post-process; the rows come back behind the records, before the one wait
+        reid->emplace(f.reid);
+        RCCHK((*reid)->enqueue(m->stream, m->d_records, m->d_counts, d_camera, B, Q, h, w, s.label, f.slots));
+        (*reid)->with_rows = !s.track.on();   // (a tracker reads the rows where the forward left them; the slot list alone comes back)
+        *rows = {TRACK_ROWS_BY_SLOT, reid_feature_dim(f.reid), (*reid)->dev_rows(), (*reid)->dev_slot_map(), (*reid)->dev_n_person(), f.slots};
+        return OPD_OK;
+    }
+    if (f.kind == FEAT_ROI)
+        HIPCHK(opd_launch_roi_features_records(m->d_x32, m->d_records, m->d_counts, m->d_orig_hw, s.label, m->d_feat_all, B, Q, m->last_fh, m->last_fw, m->stream));
+    if (f.kind == FEAT_COLOR) {   // the histogram kernels read the CAMERA-resolution frames under the boxes of the records
+        RCCHK(ensure(m, &m->d_color_acc, slots_of(m) * OPD_COLOR_ACC_WORDS));
+        ColorParams cp{};
+        cp.records = m->d_records; cp.counts = m->d_counts; cp.frames = d_camera; cp.acc = m->d_color_acc; cp.out = m->d_feat_all;
+        cp.Q = Q; cp.fh = h; cp.fw = w; cp.label = s.label; cp.n = B * Q;
+        HIPCHK(opd_launch_color_features(cp, std::min(64, (h + 15) / 16), m->stream));
+    }
+    rows->rows_kind = TRACK_ROWS_BY_QUERY; rows->D = m->arch.d_model; rows->rows = m->d_feat_all;
+    return OPD_OK;
+}
+
+// The floor stage: the floor record of every record of the class, from the box the Python shim derives, while the records are on the device
+static int enqueue_floor(opd_detr* m, const RecordSink& s) {
+    RCCHK(ensure(m, &m->d_floor, slots_of(m), (void**)&m->h_floor));
+    FloorParams fp{};
+    fp.m = s.floor.fmap->model; fp.mode = FLOOR_IN_RECORDS; fp.n = m->last_B * m->arch.queries;
+    fp.records = m->d_records; fp.counts = m->d_counts; fp.Q = m->arch.queries; fp.label = s.label; fp.out = m->d_floor;
+    HIPCHK(opd_launch_floor(fp, m->stream));
+    return OPD_OK;
+}
+
+// The tracker half of a fused detect-and-track call (opd_track.h), around the one wait of fetch_records.  Before it: every tracker's ingest and
+// predict / cost launches on m->stream, behind the feature stage.  After it: association and commit per tracker; a tracker out of slots does not
+// keep the others from being committed, and its error is the call's.
+static int enqueue_trackers(opd_detr* m, const TrackStage& t, const TrackFeatureSource& src) {
+    const int B = m->last_B, Q = m->arch.queries;
+    if (t.seq) return track_sequence_enqueue(t.seq, m->stream, m->d_records, m->d_counts, Q, B, src, "opd_detr_detect_sequence_track");
+    for (int b = 0; b < B; ++b) RCCHK(track_fused_enqueue(t.trackers[b], m->stream, m->d_records + (size_t)b * Q, m->d_counts + b, Q, b, src));
+    return OPD_OK;
+}
+static int finish_trackers(opd_detr* m, const RecordSink& s, bool with_features) {
+    const int B = m->last_B, Q = m->arch.queries;
+    const TrackStage& t = s.track;
+    if (t.seq) return track_sequence_finish(t.seq, s.counts, Q, B, t.track_ids, t.frames_done, "opd_detr_detect_sequence_track");
+    int rc = OPD_OK;
+    std::string first;
+    for (int b = 0; b < B; ++b) {
+        const int n = std::max(0, std::min(s.counts[b], Q));
+        const int one = track_fused_finish(t.trackers[b], s.out + (size_t)b * Q, n, with_features, t.track_ids + (size_t)b * Q, "opd_detr_detect_frames_track");
+        if (one != OPD_OK && rc == OPD_OK) { rc = one; first = g_err; }
+    }
+    return rc == OPD_OK ? OPD_OK : fail(rc, first);
+}
+
+// A page-locked copy of the record block is taken apart into the caller's arrays here (deliver_records, opd_detr_wait)
 static void unpack_records(const opd_detr* m, const void* pinned, int B, opd_det* out, int32_t* counts, float* features = nullptr) {
     const char* p = static_cast<const char*>(pinned);
     memcpy(out, p, (size_t)B * m->arch.queries * sizeof(opd_det));
     memcpy(counts, p + rec_bytes(m), (size_t)B * 4);
     if (features) memcpy(features, p + feat_off(m), (size_t)B * feat_row(m));
 }
+// The per-query feature rows that travel with the records (the Re-ID call brings its rows back itself, by slot)
+static float* query_rows_out(const RecordSink& s) { return s.feature.kind == FEAT_REID ? nullptr : s.feature.features; }
 
-// (`features` != null: the [B][Q][d_model] feature rows behind the counts travel in the same copy)
-// (`fmap_out` != null: the floor records of the batch follow in a copy of their own, before the same wait; only rows of records labelled `label` are handed on)
-// (`reid` != null: the Re-ID rows, slot map and person count of its call follow likewise)
-static int fetch_records(opd_detr* m, opd_det* out, int32_t* counts, int mem_kind, float* features = nullptr, opd_floor_rec* fmap_out = nullptr, int label = 0,
-                         ReidFusedCall* reid = nullptr) {
-    const int B = m->last_B;
-    if (!outputs_on_device(mem_kind)) {   // (device callers had the post-process kernel write into their buffers)
-        // one copy of [records of max_batch frames | counts (| features)] into page-locked memory (a copy into the caller's pageable arrays is
-        // staged by the runtime anyway, once per call), handed over after the wait
-        if (!m->sync_pinned) HIPCHK(hipHostMalloc(&m->sync_pinned, feat_off(m) + m->cfg.max_batch * feat_row(m), hipHostMallocDefault));
-        HIPCHK(hipMemcpyAsync(m->sync_pinned, m->d_records, features ? feat_off(m) + B * feat_row(m) : rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
-        if (fmap_out) HIPCHK(hipMemcpyAsync(m->h_floor, m->d_floor, (size_t)B * m->arch.queries * sizeof(opd_floor_rec), hipMemcpyDeviceToHost, m->stream));
+// The one fetch of a blocking call: what the sink's parts ask for comes back into page-locked memory (a copy into the caller's pageable arrays is staged by
+// the runtime anyway, once per call), then the call's ONE wait.  A tiled call: [counts | merged records] alone.  Host outputs: [records of max_batch frames |
+// counts (| per-query feature rows)] in one copy, the floor rows, the Re-ID call's slot list (and rows, unless a tracker reads them in place).  Device
+// outputs were written in place by the post-process kernel.
+static int fetch_records(opd_detr* m, const RecordSink& s, ReidFusedCall* reid) {
+    const int B = m->last_B, Q = m->arch.queries;
+    if (s.tile.params) {
+        HIPCHK(hipMemcpyAsync(m->tile_pinned, m->d_tile_out, tile_out_off(m) + (size_t)B * Q * sizeof(opd_tile_det), hipMemcpyDeviceToHost, m->stream));
+    } else if (!outputs_on_device(s.mem_kind)) {
+        RCCHK(ensure_sync_pinned(m));
+        HIPCHK(hipMemcpyAsync(m->sync_pinned, m->d_records, query_rows_out(s) ? feat_off(m) + B * feat_row(m) : rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
+        if (s.floor.fmap) HIPCHK(hipMemcpyAsync(m->h_floor, m->d_floor, (size_t)B * Q * sizeof(opd_floor_rec), hipMemcpyDeviceToHost, m->stream));
         if (reid) RCCHK(reid->copy_back(m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));
-        unpack_records(m, m->sync_pinned, B, out, counts, features);
-        if (fmap_out) {
-            const int Q = m->arch.queries;
-            for (int b = 0; b < B; ++b)
-                for (int i = 0; i < counts[b] && i < Q; ++i) {
-                    const opd_det& r = out[(size_t)b * Q + i];
-                    if (r.label == label && (unsigned)r.query_index < (unsigned)Q) fmap_out[(size_t)b * Q + r.query_index] = m->h_floor[(size_t)b * Q + r.query_index];
-                }
-        }
     }
     HIPCHK(hipStreamSynchronize(m->stream));
     if (m->profiling) {
@@ -203,80 +315,14 @@ static int fetch_records(opd_detr* m, opd_det* out, int32_t* counts, int mem_kin
     return OPD_OK;
 }
 
-// The tracker half of a fused detect-and-track call (opd_track.h), around the one wait of fetch_records.  Before it: every tracker's ingest and
-// predict / cost launches on m->stream, behind the feature stage.  After it: association and commit per tracker; a tracker out of slots does not
-// keep the others from being committed, and its error is the call's.
-static int enqueue_trackers(opd_detr* m, const RecordSink& s, const TrackFeatureSource& src) {
-    const int B = m->last_B, Q = m->arch.queries;
-    if (s.seq_tracker) return track_sequence_enqueue(s.seq_tracker, m->stream, m->d_records, m->d_counts, Q, B, src, "opd_detr_detect_sequence_track");
-    for (int b = 0; b < B; ++b) RCCHK(track_fused_enqueue(s.trackers[b], m->stream, m->d_records + (size_t)b * Q, m->d_counts + b, Q, b, src));
-    return OPD_OK;
-}
-static int finish_trackers(opd_detr* m, const RecordSink& s, bool with_features) {
-    const int B = m->last_B, Q = m->arch.queries;
-    if (s.seq_tracker) return track_sequence_finish(s.seq_tracker, s.counts, Q, B, s.track_ids, s.frames_done, "opd_detr_detect_sequence_track");
-    int rc = OPD_OK;
-    std::string first;
-    for (int b = 0; b < B; ++b) {
-        const int n = std::max(0, std::min(s.counts[b], Q));
-        const int one = track_fused_finish(s.trackers[b], s.out + (size_t)b * Q, n, with_features, s.track_ids + (size_t)b * Q, "opd_detr_detect_frames_track");
-        if (one != OPD_OK && rc == OPD_OK) { rc = one; first = g_err; }
-    }
-    return rc == OPD_OK ? OPD_OK : fail(rc, first);
-}
-
-// The back half, on the outputs of the last forward (opd_detr_postprocess enters here): post-process, feature kernel, the sink's way of handing
-// the records over.  (h, w): the source's camera resolution (0: none); d_camera: its frames on the device at that resolution (FEAT_COLOR).
-static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera) {
-    const int B = m->last_B, Q = m->arch.queries;
-    const bool dev = outputs_on_device(s.mem_kind);
-    RCCHK(enqueue_postprocess(m, s.threshold, s.orig_hw, h ? h : m->last_H, h ? w : m->last_W, dev ? s.out : nullptr, dev ? s.counts : nullptr));
-    if (s.feature == FEAT_ROI)
-        HIPCHK(opd_launch_roi_features_records(m->d_x32, m->d_records, m->d_counts, m->d_orig_hw, s.label, m->d_feat_all, B, Q, m->last_fh, m->last_fw, m->stream));
-    if (s.feature == FEAT_COLOR) {   // the histogram kernels read the CAMERA-resolution frames under the boxes of the records the post-process left
-        ColorParams cp{};
-        cp.records = m->d_records; cp.counts = m->d_counts; cp.frames = d_camera; cp.acc = m->d_color_acc; cp.out = m->d_feat_all;
-        cp.Q = Q; cp.fh = h; cp.fw = w; cp.label = s.label; cp.n = B * Q;
-        HIPCHK(opd_launch_color_features(cp, std::min(64, (h + 15) / 16), m->stream));
-    }
-    if (s.fmap) {   // the floor record of every record of the class, from the box the Python shim derives, while the records are on the device
-        FloorParams fp{};
-        fp.m = s.fmap->model;
-        fp.mode = FLOOR_IN_RECORDS; fp.n = B * Q;
-        fp.records = m->d_records; fp.counts = m->d_counts; fp.Q = Q; fp.label = s.label;
-        fp.out = m->d_floor;
-        HIPCHK(opd_launch_floor(fp, m->stream));
-    }
-    if (s.feature == FEAT_REID) {   // select, plan and the Re-ID forward behind the post-process; the rows come back behind the records, before the one wait
-        ReidFusedCall call(s.reid);
-        RCCHK(call.enqueue(m->stream, m->d_records, m->d_counts, d_camera, B, Q, h, w, s.label, s.slots));
-        if (s.trackers || s.seq_tracker) {   // the rows stay where the forward left them; the slot list alone comes back
-            call.with_rows = false;
-            RCCHK(enqueue_trackers(m, s, {TRACK_ROWS_BY_SLOT, reid_feature_dim(s.reid), call.dev_rows(), call.dev_slot_map(), call.dev_n_person(), s.slots}));
-        }
-        RCCHK(fetch_records(m, s.out, s.counts, s.mem_kind, nullptr, nullptr, s.label, &call));
-        if (s.trackers || s.seq_tracker) {
-            call.slots_per_frame(B, Q, s.n_featured);
-            return finish_trackers(m, s, true);
-        }
-        call.deliver(s.features, s.slot_map, s.n_person);
-        return OPD_OK;
-    }
-    if (s.trackers || s.seq_tracker) {
-        const bool rows = s.feature != FEAT_NONE;
-        RCCHK(enqueue_trackers(m, s, {rows ? TRACK_ROWS_BY_QUERY : TRACK_ROWS_NONE, m->arch.d_model, rows ? m->d_feat_all : nullptr, nullptr, nullptr, 0}));
-        RCCHK(fetch_records(m, s.out, s.counts, s.mem_kind));
-        for (int b = 0; b < B; ++b) s.n_featured[b] = rows ? std::max(0, std::min(s.counts[b], Q)) : 0;
-        return finish_trackers(m, s, rows);
-    }
-    if (s.wait == WAIT_NONE) return OPD_OK;
-    if (s.wait == WAIT_BLOCKING) return fetch_records(m, s.out, s.counts, s.mem_kind, s.features, s.fmap ? s.fmap_out : nullptr, s.label);   // records, counts and feature rows: one copy, one wait
+// WAIT_TICKET: the records go to async slot s.ticket behind an event of its own; opd_detr_wait delivers them
+static int hand_to_ticket(opd_detr* m, const RecordSink& s) {
     opd_detr::AsyncHost& slot = m->async_host[s.ticket];
     slot.out = nullptr;
-    if (!dev) {   // host outputs: pinned staging so that the copy stays asynchronous; delivered by opd_detr_wait
+    if (!outputs_on_device(s.mem_kind)) {   // host outputs: pinned staging so that the copy stays asynchronous
         if (!slot.pinned) HIPCHK(hipHostMalloc(&slot.pinned, rec_bytes(m) + (size_t)m->cfg.max_batch * 4, hipHostMallocDefault));
-        HIPCHK(hipMemcpyAsync(slot.pinned, m->d_records, rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));   // (records | counts: one copy)
-        slot.out = s.out; slot.counts = s.counts; slot.B = B;
+        HIPCHK(hipMemcpyAsync(slot.pinned, m->d_records, rec_bytes(m) + (size_t)m->last_B * 4, hipMemcpyDeviceToHost, m->stream));   // (records | counts: one copy)
+        slot.out = s.out; slot.counts = s.counts; slot.B = m->last_B;
     }
     HIPCHK(hipEventRecord(m->ev_async[s.ticket], m->stream));
     m->async_pending[s.ticket] = true;
@@ -284,9 +330,47 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
     return OPD_OK;
 }
 
-// The front half: the source step and the forward
+// The back half, on the outputs of the last forward (opd_detr_postprocess enters here): the stages of the sink in their one order, each skipped when its
+// part is absent.  (h, w): the size the boxes are scaled to (0: the model resolution); d_camera: the source's frames on the device at camera resolution.
+// The feature, floor, track and tile parts deliver to the host after the call's own wait: setting one with WAIT_TICKET or WAIT_NONE, or with device
+// outputs, is a programming error (no entry point does).
+static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera) {
+    const int B = m->last_B, Q = m->arch.queries;
+    const bool dev = outputs_on_device(s.mem_kind), tiled = s.tile.params != nullptr, tracked = s.track.on();
+    RCCHK(enqueue_postprocess(m, s.threshold, s.orig_hw, h ? h : m->last_H, h ? w : m->last_W, dev ? s.out : nullptr, dev ? s.counts : nullptr,
+                              tiled ? s.tile.params->person_label : m->nms_label, tiled ? s.tile.params->tile_nms_threshold : m->nms_threshold));
+    if (tiled) RCCHK(enqueue_tile_merge(m, s.tile));
+    std::optional<ReidFusedCall> reid;   // (lives until the rows are delivered)
+    TrackFeatureSource rows;
+    RCCHK(enqueue_features(m, s, tiled ? s.tile.frame_h : h, tiled ? s.tile.frame_w : w, d_camera, &reid, &rows));
+    if (s.floor.fmap) RCCHK(enqueue_floor(m, s));
+    if (tracked) RCCHK(enqueue_trackers(m, s.track, rows));
+    if (s.wait == WAIT_NONE) return OPD_OK;
+    if (s.wait == WAIT_TICKET) return hand_to_ticket(m, s);
+    RCCHK(fetch_records(m, s, reid ? &*reid : nullptr));
+    // behind the wait: into the caller's arrays
+    if (tiled) {
+        memcpy(s.tile.counts, m->tile_pinned, (size_t)s.tile.n_frames * 4);
+        memcpy(s.tile.out, static_cast<const char*>(m->tile_pinned) + tile_out_off(m), (size_t)B * Q * sizeof(opd_tile_det));
+    } else if (!dev) unpack_records(m, m->sync_pinned, B, s.out, s.counts, query_rows_out(s));
+    if (reid && !tracked) reid->deliver(s.feature.features, s.feature.slot_map, s.feature.n_person);
+    if (s.floor.fmap)   // only rows of records of the class are handed on
+        for (int b = 0; b < B; ++b)
+            for (int i = 0; i < s.counts[b] && i < Q; ++i) {
+                const opd_det& r = s.out[(size_t)b * Q + i];
+                if (r.label == s.label && (unsigned)r.query_index < (unsigned)Q) s.floor.out[(size_t)b * Q + r.query_index] = m->h_floor[(size_t)b * Q + r.query_index];
+            }
+    if (!tracked) return OPD_OK;
+    if (reid) reid->slots_per_frame(B, Q, s.track.n_featured);
+    else for (int b = 0; b < B; ++b) s.track.n_featured[b] = rows.rows_kind == TRACK_ROWS_NONE ? 0 : std::max(0, std::min(s.counts[b], Q));
+    return finish_trackers(m, s, rows.rows_kind != TRACK_ROWS_NONE);
+}
+
+// The front half: the source step and the forward.  The launch timer starts anew here, once per call: the source's launches, the forward's and the
+// sink's behind it make up the call's kernel table (profiling mode 1; with profiling off no launch leaves a mark and this empties an empty list).
 static int forward_frames(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, const uint8_t** d_camera) {
     const void* d_pixels = nullptr;
+    m->timer.reset();
     RCCHK(stage_frames(m, src, B, H, W, &d_pixels, d_camera));
     return run_forward(m, d_pixels, src.pixel_format, B, H, W, valid_hw);
 }
@@ -294,7 +378,7 @@ static int forward_frames(opd_detr* m, const FrameSource& src, int B, int H, int
 int detect_pipeline(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, const RecordSink& sink) {
     const uint8_t* d_camera = nullptr;
     RCCHK(forward_frames(m, src, B, H, W, valid_hw, &d_camera));
-    return deliver_records(m, sink, src.kind == SRC_PIXELS ? 0 : src.h, src.w, d_camera);
+    return deliver_records(m, sink, src.box_h(), src.box_w(), d_camera);
 }
 
 // The front half alone (opd_detr_forward*): the raw outputs go to host or device memory according to src.mem_kind
@@ -319,7 +403,7 @@ static int check_tiles(const std::string& who, const opd_tile_params* p, const i
     if (!p || !tiles) return fail(OPD_EINVAL, who + ": null argument");
     if (p->struct_size != (int32_t)sizeof(opd_tile_params)) return fail(OPD_EINVAL, who + ": opd_tile_params.struct_size mismatch");
     if (n_tiles < 1) return fail(OPD_EINVAL, who + ": n_tiles < 1");
-    if (h < 1 || w < 1 || (size_t)h * w > (size_t)1 << 26) return fail(OPD_EINVAL, who + ": frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
+    if (!frame_size_ok(h, w)) return fail(OPD_EINVAL, who + ": frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
     for (int t = 0; t < n_tiles; ++t) {
         const int32_t* g = tiles + 4 * t;
         if (g[0] < 0 || g[1] < 0 || g[2] < 1 || g[3] < 1 || (long long)g[0] + g[2] > h || (long long)g[1] + g[3] > w)
@@ -329,59 +413,6 @@ static int check_tiles(const std::string& who, const opd_tile_params* p, const i
             return fail(OPD_EINVAL, who + ": tiles of more than one size (" + std::to_string(tiles[2]) + " x " + std::to_string(tiles[3]) + " and " + std::to_string(g[2]) + " x " +
                                         std::to_string(g[3]) + "): one forward has one model size");
     }
-    return OPD_OK;
-}
-
-static size_t tile_out_off(const opd_detr* m) { return align_up((size_t)m->cfg.max_batch * 4, 64); }   // [counts | records]: where the records begin
-
-static int detect_tiled(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles, int n_tiles, int H, int W, float threshold,
-                        const opd_tile_params* p, opd_tile_det* out, int32_t* counts) {
-    const int B = n_frames * n_tiles, Q = m->arch.queries, th = tiles[2], tw = tiles[3];
-    const size_t off = tile_out_off(m), cap = off + (size_t)m->cfg.max_batch * Q * sizeof(opd_tile_det);
-    if (!m->d_tile_out) {
-        RCCHK(dalloc(m, &m->d_tiles, (size_t)m->cfg.max_batch * 4, false));
-        RCCHK(dalloc(m, &m->d_tile_out, cap, false));
-        HIPCHK(hipHostMalloc(&m->tile_pinned, cap, hipHostMallocDefault));
-    }
-    if (!m->d_nms_flag) {
-        RCCHK(dalloc(m, &m->d_nms_flag, 1, false));
-        HIPCHK(hipMemsetAsync(m->d_nms_flag, 0, 4, m->stream));
-    }
-    const std::vector<int32_t> win(tiles, tiles + (size_t)n_tiles * 4);
-    if (win != m->h_tiles) {   // the windows of a video do not change from call to call: upload only when they do
-        HIPCHK(hipStreamSynchronize(m->stream));   // (an earlier asynchronous copy may still be reading the old host vector)
-        m->h_tiles = win;
-        HIPCHK(hipMemcpyAsync(m->d_tiles, m->h_tiles.data(), m->h_tiles.size() * 4, hipMemcpyHostToDevice, m->stream));
-    }
-    // every frame once, whole
-    const size_t n1 = (size_t)h * w * 3;
-    RCCHK(m->src.reserve("source frames", 0, (size_t)n_frames * n1, m->stream));
-    for (int f = 0; f < n_frames; ++f) HIPCHK(hipMemcpyAsync(m->src.dev + f * n1, frames[f], n1, hipMemcpyHostToDevice, m->stream));
-    // its tiles from where it lies -> the stem's input block
-    const opd_detr::ResizeTab* tab = nullptr;
-    RCCHK(resize_tab(m, th, tw, H, W, &tab));
-    TileResizeParams rp{m->src.dev, m->d_u8, m->d_tiles, n_frames, n_tiles, h, w, th, tw, H, W, tab->bh, tab->kh, tab->bv, tab->kv, tab->ksh, tab->ksv};
-    m->timer.reset();
-    struct Hold { bool& b; explicit Hold(bool& x) : b(x) { b = true; } ~Hold() { b = false; } };
-    {
-        Hold hold(m->timer_hold);   // (the forward would drop the resize launch's event pair)
-        RCCHK(launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_tile_resize_u8(rp, m->stream); }));
-        RCCHK(run_forward(m, m->d_u8, OPD_PIXELS_U8_BGR_HWC, B, H, W));
-    }
-    // records in TILE pixels, filtered and suppressed per tile, then merged per frame
-    RCCHK(enqueue_postprocess(m, threshold, nullptr, th, tw, nullptr, nullptr, p));
-    TileMergeParams mp{};
-    mp.recs = m->d_records; mp.tile_counts = m->d_counts; mp.tiles_yxhw = m->d_tiles;
-    mp.counts = reinterpret_cast<int32_t*>(m->d_tile_out); mp.out = reinterpret_cast<opd_tile_det*>(m->d_tile_out + off); mp.flag = m->d_nms_flag;
-    mp.n_frames = n_frames; mp.n_tiles = n_tiles; mp.stride = Q; mp.frame_h = h; mp.frame_w = w;
-    mp.merge_nms_threshold = p->merge_nms_threshold; mp.merge_threshold = p->merge_threshold; mp.edge_tolerance = p->edge_tolerance;
-    RCCHK(launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_tile_merge(mp, m->stream); }));
-    const size_t rec = (size_t)B * Q * sizeof(opd_tile_det);
-    HIPCHK(hipMemcpyAsync(m->tile_pinned, m->d_tile_out, off + rec, hipMemcpyDeviceToHost, m->stream));   // [counts | records]: one copy, one wait
-    HIPCHK(hipStreamSynchronize(m->stream));
-    memcpy(counts, m->tile_pinned, (size_t)n_frames * 4);
-    memcpy(out, static_cast<const char*>(m->tile_pinned) + off, rec);
-    if (m->profiling == 1) timed_collect(m);
     return OPD_OK;
 }
 
@@ -396,8 +427,7 @@ static int merge_tiles(opd_detr* m, const opd_det* recs, const int32_t* tile_cou
     const int32_t zero = 0;
     mp.flag = tmp.up(&zero, 1);
     if (!tmp.ok) return fail(OPD_ENOMEM, "opd_detr_merge_tiles: device allocation failed");
-    mp.n_frames = n_frames; mp.n_tiles = n_tiles; mp.stride = stride; mp.frame_h = h; mp.frame_w = w;
-    mp.merge_nms_threshold = p->merge_nms_threshold; mp.merge_threshold = p->merge_threshold; mp.edge_tolerance = p->edge_tolerance;
+    fill_tile_merge(&mp, p, n_frames, n_tiles, stride, h, w);
     if (m->profiling == 1) m->timer.reset();
     RCCHK(launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_tile_merge(mp, m->stream); }));
     HIPCHK(hipStreamSynchronize(m->stream));
@@ -583,7 +613,7 @@ int opd_detr_postprocess(opd_detr* m, float threshold, const int32_t* orig_hw, o
     if (!m || !out || !counts) return fail(OPD_EINVAL, "opd_detr_postprocess: null argument");
     if (m->last_B == 0) return fail(OPD_ESTATE, "opd_detr_postprocess called before any forward");
     HIPCHK(hipSetDevice(m->device));
-    return deliver_records(m, {threshold, orig_hw, out, counts, OPD_MEM_HOST, WAIT_BLOCKING}, 0, 0, nullptr);
+    return deliver_records(m, RecordSink(threshold, orig_hw, out, counts, OPD_MEM_HOST), 0, 0, nullptr);
 }); }
 int opd_detr_set_nms(opd_detr* m, int person_label, float nms_threshold) { return api_call_unlocked("opd_detr_set_nms", [&]() -> int {
     if (!m) return fail(OPD_EINVAL, "null model handle");
@@ -627,7 +657,12 @@ int opd_detr_detect_tiled(opd_detr* m, const uint8_t* const* frames, int n_frame
         if (!frames[f]) return fail(OPD_EINVAL, "opd_detr_detect_tiled: null frame pointer");
     RCCHK(check_shape(m, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, n_frames * n_tiles, H, W));
     HIPCHK(hipSetDevice(m->device));
-    return detect_tiled(m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, out, counts);
+    FrameSource src{SRC_TILES, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w};
+    src.n_frames = n_frames; src.n_tiles = n_tiles; src.tiles = tiles_yxhw;
+    RecordSink sink(threshold, nullptr, nullptr, nullptr, OPD_MEM_HOST);   // (boxes in TILE pixels; the merge puts them on the frame)
+    sink.tile.params = p; sink.tile.n_frames = n_frames; sink.tile.n_tiles = n_tiles; sink.tile.frame_h = h; sink.tile.frame_w = w;
+    sink.tile.out = out; sink.tile.counts = counts;
+    return detect_pipeline(m, src, n_frames * n_tiles, H, W, nullptr, sink);
 }); }
 int opd_detr_merge_tiles(opd_detr* m, const opd_det* recs, const int32_t* tile_counts, int n_frames, int n_tiles, int stride, const int32_t* tiles_yxhw, int h, int w,
                          const opd_tile_params* p, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_merge_tiles", [&]() -> int {
@@ -667,7 +702,7 @@ int opd_detr_detect_ragged(opd_detr* m, const void* pixels, int pixel_format, in
     if (!out || !counts) return fail(OPD_EINVAL, "opd_detr_detect: null output buffer");
     RCCHK(check_device_outputs(mem_kind, out, counts, "opd_detr_detect"));
     HIPCHK(hipSetDevice(m->device));
-    return detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, valid_hw, {threshold, orig_hw, out, counts, mem_kind, WAIT_BLOCKING});
+    return detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, valid_hw, RecordSink(threshold, orig_hw, out, counts, mem_kind));
 }); }
 int opd_detr_detect_async(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W, float threshold,
                           const int32_t* orig_hw, opd_det* out, int32_t* counts, int* ticket) { return api_call("opd_detr_detect_async", [&]() -> int {
@@ -680,7 +715,7 @@ int opd_detr_detect_async(opd_detr* m, const void* pixels, int pixel_format, int
     if (m->async_pending[t])
         return fail(OPD_ESTATE, "opd_detr_detect_async: 4 submissions are outstanding on this handle; opd_detr_wait the oldest ticket first");
     if (!m->ev_async[t]) HIPCHK(hipEventCreateWithFlags(&m->ev_async[t], hipEventDisableTiming));
-    RCCHK(detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, nullptr, {threshold, orig_hw, out, counts, mem_kind, WAIT_TICKET, t}));
+    RCCHK(detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, nullptr, RecordSink(threshold, orig_hw, out, counts, mem_kind, WAIT_TICKET, t)));
     *ticket = t;
     return OPD_OK;
 }); }
@@ -703,10 +738,21 @@ int opd_detr_detect_resized(opd_detr* m, const uint8_t* frames, int mem_kind, in
     if (!out || !counts) return fail(OPD_EINVAL, "opd_detr_detect_resized: null output buffer");
     RCCHK(check_device_outputs(mem_kind, out, counts, "opd_detr_detect_resized"));
     HIPCHK(hipSetDevice(m->device));
-    return detect_pipeline(m, {SRC_BLOCK, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, h, w}, B, H, W, nullptr, {threshold, nullptr, out, counts, mem_kind, WAIT_BLOCKING});
+    return detect_pipeline(m, {SRC_BLOCK, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, h, w}, B, H, W, nullptr, RecordSink(threshold, nullptr, out, counts, mem_kind));
 }); }
 
-// The three frame-list entries: the argument checks they share, worded with the entry's own name
+// The frame-list entries with a stage behind the records (host frames, host outputs, blocking): the base of their sink, and its feature stage ...
+static RecordSink host_sink(float threshold, int label, opd_det* out, int32_t* counts, int feature = FEAT_NONE, float* features = nullptr) {
+    RecordSink s(threshold, nullptr, out, counts, OPD_MEM_HOST);
+    s.label = label; s.feature.kind = feature; s.feature.features = features;
+    return s;
+}
+// ... their one call of the pipeline, behind the last refusal ...
+static int detect_frames(opd_detr* m, const uint8_t* const* frames, int mem_kind, int B, int h, int w, int H, int W, const RecordSink& sink) {
+    HIPCHK(hipSetDevice(m->device));
+    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, h, w}, B, H, W, nullptr, sink);
+}
+// ... and the argument checks they share, worded with the entry's own name
 static int check_frame_list(opd_detr* m, const uint8_t* const* frames, int mem_kind, int B, int H, int W, bool have_outputs, const std::string& who) {
     RCCHK(check_shape(m, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, B, H, W));
     for (int b = 0; b < B; ++b)
@@ -720,21 +766,17 @@ int opd_detr_detect_frames(opd_detr* m, const uint8_t* const* frames, int mem_ki
     if (mem_kind != OPD_MEM_HOST && mem_kind != OPD_MEM_HOST_PIXELS_DEVICE_OUT) return fail(OPD_EINVAL, "opd_detr_detect_frames takes host frames");
     RCCHK(check_frame_list(m, frames, mem_kind, B, H, W, out && counts, "opd_detr_detect_frames"));
     RCCHK(check_device_outputs(mem_kind, out, counts, "opd_detr_detect_frames"));
-    HIPCHK(hipSetDevice(m->device));
-    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, mem_kind, h, w}, B, H, W, nullptr, {threshold, nullptr, out, counts, mem_kind, WAIT_BLOCKING});
+    return detect_frames(m, frames, mem_kind, B, h, w, H, W, RecordSink(threshold, nullptr, out, counts, mem_kind));
 }); }
 
 int opd_detr_detect_frames_features(opd_detr* m, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold, int label,
                                     opd_det* out, int32_t* counts, float* features) { return api_call("opd_detr_detect_frames_features", [&]() -> int {
     RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && features, "opd_detr_detect_frames_features"));
     if (m->arch.d_model != 256) return fail(OPD_EINVAL, "opd_detr_detect_frames_features: the pooling kernel is built for d_model = 256");
-    HIPCHK(hipSetDevice(m->device));
-    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr,
-                           {threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_ROI, label, features});
+    return detect_frames(m, frames, OPD_MEM_HOST, B, h, w, H, W, host_sink(threshold, label, out, counts, FEAT_ROI, features));
 }); }
 
-// The colour-histogram twin: same upload, same forward and post-process; the histogram kernels read the CAMERA-resolution frames this call
-// has just put on the device (d_src when it resizes, d_u8 when it does not) under the boxes of the records the post-process left there.
+// The colour-histogram twin: the feature stage reads the CAMERA-resolution frames the source step has just put on the device
 int opd_detr_detect_frames_color(opd_detr* m, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold, int label,
                                  opd_det* out, int32_t* counts, float* features) { return api_call("opd_detr_detect_frames_color", [&]() -> int {
     RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && features, "opd_detr_detect_frames_color"));
@@ -742,55 +784,42 @@ int opd_detr_detect_frames_color(opd_detr* m, const uint8_t* const* frames, int 
     if (h < 1 || w < 1 || h > OPD_COLOR_MAX_EDGE || w > OPD_COLOR_MAX_EDGE)
         return fail(OPD_EINVAL, "opd_detr_detect_frames_color: frames of " + std::to_string(h) + " x " + std::to_string(w) +
                                     " are outside the 4096 x 4096 the exact integer sums are sized for");
-    HIPCHK(hipSetDevice(m->device));
-    if (!m->d_color_acc) RCCHK(dalloc(m, &m->d_color_acc, (size_t)m->cfg.max_batch * m->arch.queries * OPD_COLOR_ACC_WORDS, false));
-    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr,
-                           {threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_COLOR, label, features});
+    return detect_frames(m, frames, OPD_MEM_HOST, B, h, w, H, W, host_sink(threshold, label, out, counts, FEAT_COLOR, features));
 }); }
 
-// The floor-map twin: same upload, forward and post-process; one wave per record slot then maps the foot point of every record of the class
-// with `f`'s model (read-only device tables: any stream may read them), and the rows travel behind the records before the one wait.
+// The floor-map twin: the floor stage maps the foot point of every record of the class with `f`'s model (read-only device tables: any stream may read them)
 int opd_detr_detect_frames_floor(opd_detr* m, opd_floor* f, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
                                  int label, opd_det* out, int32_t* counts, opd_floor_rec* floor) { return api_call("opd_detr_detect_frames_floor", [&]() -> int {
     if (!f) return fail(OPD_EINVAL, "opd_detr_detect_frames_floor: null floor-map handle");
     RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && floor, "opd_detr_detect_frames_floor"));
     if (f->device != m->device)
         return fail(OPD_EINVAL, "opd_detr_detect_frames_floor: the detector is on device " + std::to_string(m->device) + ", the floor map on device " + std::to_string(f->device));
-    HIPCHK(hipSetDevice(m->device));
-    if (!m->d_floor) {
-        const size_t n = (size_t)m->cfg.max_batch * m->arch.queries;
-        RCCHK(dalloc(m, &m->d_floor, n, false));
-        HIPCHK(hipHostMalloc((void**)&m->h_floor, n * sizeof(opd_floor_rec), hipHostMallocDefault));
-    }
-    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr,
-                           {threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_NONE, label, nullptr, f, floor});
+    RecordSink sink = host_sink(threshold, label, out, counts);
+    sink.floor.fmap = f; sink.floor.out = floor;
+    return detect_frames(m, frames, OPD_MEM_HOST, B, h, w, H, W, sink);
 }); }
 
-// The Re-ID twin: same upload, forward and post-process; two small kernels then pick the records of the class and plan their crops from the boxes
-// the Python shim derives, read in place from the CAMERA-resolution frames this call has just put on the device; `r`'s forward runs on its own
-// stream between two events, and its rows travel behind the records before the one wait.
+// The Re-ID twin: the feature stage is `r`'s fused call (opd_reid.h), crops read in place from the CAMERA-resolution frames, its forward on its own stream
 int opd_detr_detect_frames_reid(opd_detr* m, opd_reid* r, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold, int label,
                                 int slots, opd_det* out, int32_t* counts, float* features, int32_t* slot_map, int32_t* n_person) { return api_call("opd_detr_detect_frames_reid", [&]() -> int {
     if (!r) return fail(OPD_EINVAL, "opd_detr_detect_frames_reid: null Re-ID handle");
     RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, out && counts && features && slot_map && n_person, "opd_detr_detect_frames_reid"));
     RCCHK(reid_fused_check(r, m->device, slots, "opd_detr_detect_frames_reid"));
-    if (h < 1 || w < 1 || (size_t)h * w > (size_t)1 << 26)
+    if (!frame_size_ok(h, w))
         return fail(OPD_EINVAL, "opd_detr_detect_frames_reid: source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
-    HIPCHK(hipSetDevice(m->device));
-    RecordSink sink{threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, FEAT_REID, label, features, nullptr, nullptr, r, slots, slot_map, n_person};
-    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr, sink);
+    RecordSink sink = host_sink(threshold, label, out, counts, FEAT_REID, features);
+    sink.feature.reid = r; sink.feature.slots = slots; sink.feature.slot_map = slot_map; sink.feature.n_person = n_person;
+    return detect_frames(m, frames, OPD_MEM_HOST, B, h, w, H, W, sink);
 }); }
 
-// The tracking twin: same upload, forward, post-process with suppression and feature stage; then, still before the one wait, every
-// tracker's ingest launch reads its frame's kept records and feature rows where they lie and its predict / cost launch follows, so that the wait
-// delivers records and cost matrices together.  Association and the commit launch (on the tracker's own stream, not waited for) follow it.
-// The refusals both tracking calls share, behind their own null-argument check and in this order; *dim: the width of a feature row of the kind (0: none)
-static int check_track_call(const std::string& me, opd_detr* m, opd_reid* r, const uint8_t* const* frames, int B, int h, int w, int H, int W, int label, int feature_kind,
-                            int slots, int* dim) {
+// The tracking twins, behind their own null-argument check: the refusals they share, in this order, and the sink they build alike -- the
+// track stage `track` (a tracker per frame, or `seq` for all of them) behind the suppression and the feature stage of `feature_kind`
+static int detect_track(const std::string& me, opd_detr* m, opd_reid* r, const TrackStage& track, const uint8_t* const* frames, int B, int h, int w, int H, int W,
+                        float threshold, int label, int feature_kind, int slots, opd_det* out, int32_t* counts) {
     if (feature_kind != OPD_TRACK_FEAT_NONE && feature_kind != OPD_TRACK_FEAT_ENCODER && feature_kind != OPD_TRACK_FEAT_COLOR && feature_kind != OPD_TRACK_FEAT_REID)
         return fail(OPD_EINVAL, me + ": unknown feature_kind " + std::to_string(feature_kind));
     if (feature_kind == OPD_TRACK_FEAT_REID && !r) return fail(OPD_EINVAL, me + ": feature_kind OPD_TRACK_FEAT_REID with a null Re-ID handle");
-    if (h < 1 || w < 1 || (size_t)h * w > (size_t)1 << 26) return fail(OPD_EINVAL, me + ": source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
+    if (!frame_size_ok(h, w)) return fail(OPD_EINVAL, me + ": source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
     if (feature_kind == OPD_TRACK_FEAT_COLOR && (h > OPD_COLOR_MAX_EDGE || w > OPD_COLOR_MAX_EDGE))
         return fail(OPD_EINVAL, me + ": frames of " + std::to_string(h) + " x " + std::to_string(w) + " are outside the 4096 x 4096 the exact integer sums of the colour histogram are sized for");
     RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, true, me));
@@ -798,58 +827,45 @@ static int check_track_call(const std::string& me, opd_detr* m, opd_reid* r, con
         return fail(OPD_EINVAL, me + ": opd_detr_set_nms is off on this handle; a tracker takes the kept records of a frame, which only the suppression on the device leaves there");
     if (m->nms_label != label)
         return fail(OPD_EINVAL, me + ": opd_detr_set_nms keeps label " + std::to_string(m->nms_label) + ", the call asks for label " + std::to_string(label));
-    *dim = 0;
+    RecordSink sink = host_sink(threshold, label, out, counts);
+    sink.track = track;
+    int dim = 0;   // the width of a feature row of the kind
     if (feature_kind == OPD_TRACK_FEAT_REID) {
         RCCHK(reid_fused_check(r, m->device, slots, me.c_str()));
-        *dim = reid_feature_dim(r);
+        dim = reid_feature_dim(r);
+        sink.feature.kind = FEAT_REID; sink.feature.reid = r; sink.feature.slots = slots;
     } else if (feature_kind != OPD_TRACK_FEAT_NONE) {
         if (m->arch.d_model != OPD_COLOR_DIM) return fail(OPD_EINVAL, me + ": the feature area of the handle and both kernels that fill it are sized for d_model = 256");
-        *dim = OPD_COLOR_DIM;
+        dim = OPD_COLOR_DIM;
+        sink.feature.kind = feature_kind == OPD_TRACK_FEAT_ENCODER ? FEAT_ROI : FEAT_COLOR;
     }
-    return OPD_OK;
+    for (int b = 0; b < (track.trackers ? B : 1); ++b) {   // (a null tracker, `seq` too, is track_fused_check's to refuse)
+        RCCHK(track_fused_check(track.trackers ? track.trackers[b] : track.seq, m->device, m->arch.queries, dim, me.c_str()));
+        for (int a = 0; a < b; ++a)
+            if (track.trackers[a] == track.trackers[b])
+                return fail(OPD_EINVAL, me + ": frames " + std::to_string(a) + " and " + std::to_string(b) + " name the same tracker; a tracker takes one frame per call");
+    }
+    return detect_frames(m, frames, OPD_MEM_HOST, B, h, w, H, W, sink);
 }
-static int track_feature_of(int feature_kind) {
-    return feature_kind == OPD_TRACK_FEAT_ENCODER ? FEAT_ROI : feature_kind == OPD_TRACK_FEAT_COLOR ? FEAT_COLOR : feature_kind == OPD_TRACK_FEAT_REID ? FEAT_REID : FEAT_NONE;
-}
-
+// (both: what needs no handle first, so that a null handle is the last thing reported without one)
 int opd_detr_detect_frames_track(opd_detr* m, opd_reid* r, opd_track* const* trackers, const uint8_t* const* frames, int B, int h, int w, int H, int W,
                                  float threshold, int label, int feature_kind, int slots, opd_det* out, int32_t* counts, int32_t* track_ids,
                                  int32_t* n_featured) { return api_call("opd_detr_detect_frames_track", [&]() -> int {
     const std::string me = "opd_detr_detect_frames_track";
-    // what needs no handle first, so that a null handle is the last thing reported without one
     if (!trackers || !frames || !out || !counts || !track_ids || !n_featured) return fail(OPD_EINVAL, me + ": null argument (tracker list, frame list or an output)");
-    int dim = 0;
-    RCCHK(check_track_call(me, m, r, frames, B, h, w, H, W, label, feature_kind, slots, &dim));
-    for (int b = 0; b < B; ++b) {
-        RCCHK(track_fused_check(trackers[b], m->device, m->arch.queries, dim, me.c_str()));
-        for (int a = 0; a < b; ++a)
-            if (trackers[a] == trackers[b]) return fail(OPD_EINVAL, me + ": frames " + std::to_string(a) + " and " + std::to_string(b) + " name the same tracker; a tracker takes one frame per call");
-    }
-    HIPCHK(hipSetDevice(m->device));
-    if (feature_kind == OPD_TRACK_FEAT_COLOR && !m->d_color_acc) RCCHK(dalloc(m, &m->d_color_acc, (size_t)m->cfg.max_batch * m->arch.queries * OPD_COLOR_ACC_WORDS, false));
-    const int feature = track_feature_of(feature_kind);
-    RecordSink sink{threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, feature, label, nullptr, nullptr, nullptr, feature == FEAT_REID ? r : nullptr, slots, nullptr, nullptr,
-                    trackers, track_ids, n_featured};
-    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr, sink);
+    TrackStage track;
+    track.trackers = trackers; track.track_ids = track_ids; track.n_featured = n_featured;
+    return detect_track(me, m, r, track, frames, B, h, w, H, W, threshold, label, feature_kind, slots, out, counts);
 }); }
-
-// The sequence twin: B consecutive frames of ONE camera into ONE tracker.  One batched forward, suppression and feature stage as above; then per
-// frame, on the detector's stream, ingest -> predict / cost -> association on the device -> commit, and the table and the ids come back behind the one wait.
+// The sequence twin: B consecutive frames of ONE camera into ONE tracker, the association on the device between them
 int opd_detr_detect_sequence_track(opd_detr* m, opd_reid* r, opd_track* t, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
                                    int label, int feature_kind, int slots, opd_det* out, int32_t* counts, int32_t* track_ids, int32_t* n_featured,
                                    int32_t* frames_done) { return api_call("opd_detr_detect_sequence_track", [&]() -> int {
     const std::string me = "opd_detr_detect_sequence_track";
-    // what needs no handle first, so that a null handle is the last thing reported without one
     if (!frames || !out || !counts || !track_ids || !n_featured || !frames_done) return fail(OPD_EINVAL, me + ": null argument (frame list or an output)");
-    int dim = 0;
-    RCCHK(check_track_call(me, m, r, frames, B, h, w, H, W, label, feature_kind, slots, &dim));
-    RCCHK(track_fused_check(t, m->device, m->arch.queries, dim, me.c_str()));
-    HIPCHK(hipSetDevice(m->device));
-    if (feature_kind == OPD_TRACK_FEAT_COLOR && !m->d_color_acc) RCCHK(dalloc(m, &m->d_color_acc, (size_t)m->cfg.max_batch * m->arch.queries * OPD_COLOR_ACC_WORDS, false));
-    const int feature = track_feature_of(feature_kind);
-    RecordSink sink{threshold, nullptr, out, counts, OPD_MEM_HOST, WAIT_BLOCKING, 0, feature, label, nullptr, nullptr, nullptr, feature == FEAT_REID ? r : nullptr, slots, nullptr, nullptr,
-                    nullptr, track_ids, n_featured, t, frames_done};
-    return detect_pipeline(m, {SRC_LIST, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w}, B, H, W, nullptr, sink);
+    TrackStage track;
+    track.seq = t; track.track_ids = track_ids; track.n_featured = n_featured; track.frames_done = frames_done;
+    return detect_track(me, m, r, track, frames, B, h, w, H, W, threshold, label, feature_kind, slots, out, counts);
 }); }
 
 int opd_host_alloc(size_t bytes, void** out) { return api_call("opd_host_alloc", [&]() -> int {

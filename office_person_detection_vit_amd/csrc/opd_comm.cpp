@@ -267,7 +267,7 @@ int opd_comm_detect(opd_comm* c, int slot0, const void* pixels, int pixel_format
     const size_t Q = (size_t)m->arch.queries;
     opd_det* recs = reinterpret_cast<opd_det*>(s->d_send) + (size_t)slot0 * Q;
     int32_t* counts = s->d_send + (size_t)s->slots * Q * 8 + slot0;
-    return detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, nullptr, {threshold, orig_hw, recs, counts, OPD_MEM_DEVICE, WAIT_NONE});   // (into the lane's send buffer; the wait is opd_comm_wait's)
+    return detect_pipeline(m, {SRC_PIXELS, pixels, pixel_format, mem_kind, 0, 0}, B, H, W, nullptr, RecordSink(threshold, orig_hw, recs, counts, OPD_MEM_DEVICE, WAIT_NONE));   // (into the lane's send buffer; the wait is opd_comm_wait's)
 }); }
 
 int opd_comm_buffers(opd_comm* c, int slot0, void** records, void** counts) { return api_call_unlocked("opd_comm_buffers", [&]() -> int {

@@ -868,8 +868,7 @@ static int enqueue_forward(opd_detr* m, const void* d_pixels, int pixel_format, 
     const bool ragged = is_ragged(valid_hw, B, H, W);
     if (ragged) RCCHK(fwd_prepare_ragged(c, valid_hw));
     else RCCHK(get_plan(m, c.d.stage_h[3], c.d.stage_w[3], c.d.stage_h[3], c.d.stage_w[3], &c.plan));
-    if (!m->timer_hold) m->timer.reset();   // the event pairs and the taps of the last forward (held: opd_detr_detect_tiled has launched its resize)
-    m->tap_next = 0;
+    m->tap_next = 0;   // the taps of the last forward (its event pairs: the pipeline call resets the launch timer in front of its source step, opd_api.cpp)
     if (pixel_format == OPD_PIXELS_U8_BGR_HWC) RCCHK(tap(m, c.stream, {"pixels_u8", d_pixels, (size_t)B * H * W * 3}));
     MARK(0);
     RCCHK(fwd_stem(c, d_pixels, pixel_format));

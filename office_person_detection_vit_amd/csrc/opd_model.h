@@ -287,9 +287,10 @@ struct opd_detr : DetrWeights {
     // host-output submissions: the records travel device -> pinned slot (asynchronous) -> caller buffer (in opd_detr_wait)
     struct AsyncHost { void* pinned = nullptr; opd_det* out = nullptr; int32_t* counts = nullptr; int B = 0; };
     AsyncHost async_host[4];
-    void* sync_pinned = nullptr;   // page-locked staging of the blocking entry points: [records of max_batch frames | counts]
-    uint32_t* d_color_acc = nullptr;   // [max_batch][queries][OPD_COLOR_ACC_WORDS] integer sums of opd_detr_detect_frames_color (allocated by its first call)
-    opd_floor_rec* d_floor = nullptr;   // [max_batch][queries] floor records of opd_detr_detect_frames_floor (allocated, with its page-locked twin, by its first call)
+    // allocated by the first call of the stage that uses them (opd_api.cpp: ensure_*)
+    void* sync_pinned = nullptr;   // page-locked staging of the blocking entry points: [records of max_batch frames | counts | feature rows]
+    uint32_t* d_color_acc = nullptr;   // [max_batch][queries][OPD_COLOR_ACC_WORDS] integer sums of the colour feature stage
+    opd_floor_rec* d_floor = nullptr;   // [max_batch][queries] floor records of the floor stage, and their page-locked twin
     opd_floor_rec* h_floor = nullptr;
     float* d_feat_all = nullptr;   // [max_batch][queries][d_model] behind the counts in the d_records allocation: features of a batch's records (opd_detr_detect_frames_features)
     // device-side resize (camera resolution -> model resolution): source staging (device side only, grown on demand) and coefficient tables
@@ -302,17 +303,16 @@ struct opd_detr : DetrWeights {
     int32_t* d_rois = nullptr;
     float* d_roi_out = nullptr;
     std::vector<int32_t> h_orig_hw;
-    // device suppression (opd_detr_set_nms): off while nms_threshold < 0; the flag word of person_nms_kernel (allocated by the first use)
+    // device suppression (opd_detr_set_nms): off while nms_threshold < 0; the flag word of person_nms_kernel and tile_merge_kernel (ensure_nms_flag)
     int nms_label = 0;
     float nms_threshold = -1.0f;
     int32_t* d_nms_flag = nullptr;
-    // tiled detection (opd_detr_detect_tiled; allocated by its first call): the tile windows, [counts of max_batch frames | merged records of
-    // max_batch x queries candidates] and its page-locked twin.  timer_hold: the tiled call's resize launch keeps its row of the kernel table
+    // tiled detection: the tile windows of the SRC_TILES source; the tile stage's [counts of max_batch frames | merged records of
+    // max_batch x queries candidates] and its page-locked twin (ensure_tile_out)
     int32_t* d_tiles = nullptr;
     std::vector<int32_t> h_tiles;
     char* d_tile_out = nullptr;
     void* tile_pinned = nullptr;
-    bool timer_hold = false;
 
     // state of the last forward
     int last_B = 0, last_H = 0, last_W = 0, last_fh = 0, last_fw = 0;
@@ -403,37 +403,58 @@ void timed_collect(opd_detr* m);
         opd_dbg_skip_launch = (m->sw.dbg_skip >> (i)) & 1;           \
     } while (0)
 
-// The detect pipeline (opd_api.cpp): frame source -> device pixels -> forward -> post-process -> feature kernel -> record sink, all enqueued on
-// m->stream.  Every detect entry point, opd_comm_detect included, is its own argument checks plus ONE call of detect_pipeline.
-enum { SRC_PIXELS, SRC_BLOCK, SRC_LIST };
+// The detect pipeline (opd_api.cpp), all enqueued on m->stream.  Every detect entry point, opd_comm_detect included, is its own argument checks
+// plus ONE call of detect_pipeline:
+//   source   stage_frames: the frames of a FrameSource -> device pixels at model resolution (upload, resize, or the windows of whole frames)
+//   forward  run_forward, through the graph cache
+//   sink     deliver_records, a straight sequence in which a stage runs when its part of the RecordSink is set: post-process with suppression ->
+//            tile merge -> feature stage -> floor stage -> tracker enqueue -> ONE fetch (the copies back and the call's one wait) -> delivery
+//            into the caller's arrays, tracker finish
+enum { SRC_PIXELS, SRC_BLOCK, SRC_LIST, SRC_TILES };
 struct FrameSource {
     int kind;
     const void* frames;           // SRC_PIXELS: pixels of `pixel_format` at model resolution.  SRC_BLOCK: ONE block of camera frames [B][h][w][3], always resized.
-                                  // SRC_LIST: const uint8_t* const*, one HOST pointer per camera frame (resized when h x w is not the model size, else uploaded as is)
+                                  // SRC_LIST: const uint8_t* const*, one HOST pointer per camera frame (resized when h x w is not the model size, else uploaded as is).
+                                  // SRC_TILES: such a list of n_frames whole frames; the batch is the n_tiles windows of each, resized
     int pixel_format, mem_kind;   // (where the frames lie)
-    int h, w;                     // camera resolution, to which boxes are scaled (SRC_PIXELS: unused)
+    int h, w;                     // camera resolution (SRC_PIXELS: unused)
+    int n_frames = 0, n_tiles = 0;    // SRC_TILES: B = n_frames x n_tiles windows `tiles` [n_tiles][4] = y0, x0, th, tw (host), all of one size
+    const int32_t* tiles = nullptr;
+    // the size the post-process scales the boxes to: the camera frame, a tile's window; 0: none of its own
+    int box_h() const { return kind == SRC_PIXELS ? 0 : kind == SRC_TILES ? tiles[2] : h; }
+    int box_w() const { return kind == SRC_PIXELS ? 0 : kind == SRC_TILES ? tiles[3] : w; }
 };
 enum { WAIT_BLOCKING, WAIT_TICKET, WAIT_NONE };   // fetch the records and wait / hand them to async slot `ticket` (opd_detr_wait) / leave them on the stream
-enum { FEAT_NONE, FEAT_ROI, FEAT_COLOR, FEAT_REID };   // between post-process and fetch: nothing / ROI pooling on the records / their colour histograms /
-                                                       // the Re-ID model's rows of the first `slots` of them (opd_reid.h: ReidFusedCall)
+enum { FEAT_NONE, FEAT_ROI, FEAT_COLOR, FEAT_REID };   // nothing / ROI pooling on the records / their colour histograms / the Re-ID model's rows (opd_reid.h: ReidFusedCall)
+// The optional stages of a sink, absent by default.  They work on the records labelled RecordSink::label and deliver into HOST arrays.
+struct FeatureStage {
+    int kind = FEAT_NONE;
+    float* features = nullptr;    // rows to the caller, [B][queries][d_model] (null with a track stage: the rows stay on the device).  FEAT_REID: [slots][feature_dim],
+    opd_reid* reid = nullptr;     // row k of slot_map[k] = frame * queries + query_index, k < min(*n_person, slots)
+    int slots = 0;
+    int32_t *slot_map = nullptr, *n_person = nullptr;
+};
+struct FloorStage { const opd_floor* fmap = nullptr; opd_floor_rec* out = nullptr; };   // a floor record of every record of the class -> out [B][queries]
+struct TrackStage {   // the kept records and feature rows enter trackers where they lie: frame b into trackers[b], or the B frames in order into `seq`
+    struct opd_track* const* trackers = nullptr;
+    struct opd_track* seq = nullptr;
+    int32_t *track_ids = nullptr, *n_featured = nullptr, *frames_done = nullptr;   // [B][queries], [B]; seq: frames applied
+    bool on() const { return trackers || seq; }
+};
+struct TileStage {   // a SRC_TILES batch: the records of a frame's tiles, suppressed per tile with the PARAMETERS' label and threshold, merge across the seams
+    const opd_tile_params* params = nullptr;
+    int n_frames = 0, n_tiles = 0, frame_h = 0, frame_w = 0;
+    opd_tile_det* out = nullptr; int32_t* counts = nullptr;   // [n_frames][n_tiles x queries], [n_frames]; RecordSink::out / counts stay null: the per-tile records never leave the device
+};
 struct RecordSink {
     float threshold;
-    const int32_t* orig_hw;       // [B][2] frame sizes of the caller; null: the source's camera resolution, without one the model resolution
+    const int32_t* orig_hw;       // [B][2] frame sizes of the caller; null: the source's box size, without one the model resolution
     opd_det* out; int32_t* counts;
     int mem_kind;                 // where out / counts lie: device ones are written by the post-process kernel itself, host ones filled from the library's
-    int wait, ticket;
-    int feature, label;           // FEAT_*: feature rows of the records labelled `label` -> `features` (host; WAIT_BLOCKING)
-    float* features;
-    const opd_floor* fmap;        // non-null: a floor record of every record labelled `label` -> `fmap_out` [B][queries] (host; WAIT_BLOCKING)
-    opd_floor_rec* fmap_out;
-    opd_reid* reid;               // FEAT_REID: the Re-ID handle; `features` is then [slots][feature_dim], one row per slot_map[k] = frame * queries + query_index,
-    int slots;                    // k < min(*n_person, slots) (host; WAIT_BLOCKING)
-    int32_t* slot_map; int32_t* n_person;
-    struct opd_track* const* trackers;   // non-null (opd_detr_detect_frames_track): frame b's kept records and feature rows enter trackers[b] where they lie; the feature
-    int32_t* track_ids;                  // stage runs but its rows are not downloaded (`features`, `slot_map`, `n_person` are null).  track_ids [B][queries], n_featured [B]
-    int32_t* n_featured;
-    struct opd_track* seq_tracker;       // non-null (opd_detr_detect_sequence_track, `trackers` null): the B frames enter this ONE tracker in frame order, the
-    int32_t* frames_done;                // association on the device between them; track_ids and n_featured as above, *frames_done = frames applied
+    int wait, ticket, label = 0;
+    FeatureStage feature; FloorStage floor; TrackStage track; TileStage tile;
+    RecordSink(float threshold, const int32_t* orig_hw, opd_det* out, int32_t* counts, int mem_kind, int wait = WAIT_BLOCKING, int ticket = 0)
+        : threshold(threshold), orig_hw(orig_hw), out(out), counts(counts), mem_kind(mem_kind), wait(wait), ticket(ticket) {}
 };
 int check_shape(opd_detr* m, const void* pixels, int pixel_format, int mem_kind, int B, int H, int W);
 int detect_pipeline(opd_detr* m, const FrameSource& src, int B, int H, int W, const int32_t* valid_hw, const RecordSink& sink);

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import floor_common as F
+import track_common as TC
 from office_person_detection_vit_amd import _capi
 from office_person_detection_vit_amd.frames import structured_frames
 from office_person_detection_vit_amd.weights import DetrArch, ensure_weight_file
@@ -18,6 +20,8 @@ pytestmark = pytest.mark.gpu
 B, H, W = 2, 64, 96
 U8, HOST, DEVICE, DEVOUT = _capi.OPD_PIXELS_U8_BGR_HWC, _capi.OPD_MEM_HOST, _capi.OPD_MEM_DEVICE, _capi.OPD_MEM_HOST_PIXELS_DEVICE_OUT
 PERSON = 1
+NMS_IOU = 0.4
+TRACKER = dict(max_tracks=128, max_dets=128, min_hits=1, high_conf_threshold=0.5)   # (room for every query of both frames)
 DetP, I32P, F32P = C.POINTER(_capi.OpdDet), C.POINTER(C.c_int32), C.POINTER(C.c_float)
 
 
@@ -61,8 +65,17 @@ class _Out:
         return c.tobytes(), b"".join(r[b, :int(c[b])].tobytes() for b in range(B))
 
 
-def _entries(lib, h, info, frames, pix, host_only):
-    """name -> call(out) for every detect entry point on `frames` ([B][h][w][3] camera frames; `pix`: the same at model resolution)."""
+@pytest.fixture(scope="module")
+def floor(handle):
+    lib = handle[0]
+    f = F.create(lib, F.case_model(np.load(F.GOLDEN), "homography_config"))
+    yield f
+    lib.opd_floor_destroy(f)
+
+
+def _entries(lib, h, info, frames, pix, host_only, floor, nms):
+    """name -> call(out) for every detect entry point on `frames` ([B][h][w][3] camera frames; `pix`: the same at model resolution).
+    `nms`: the handle's suppression is on, which the tracking entries need: they join."""
     fh, fw = frames.shape[1:3]
     hw = np.asarray([[fh, fw]] * B, np.int32)
     hw_p = hw.ctypes.data_as(C.c_void_p)
@@ -70,7 +83,9 @@ def _entries(lib, h, info, frames, pix, host_only):
     d_frames = torch.from_numpy(frames).cuda()
     torch.cuda.synchronize()
     feats = np.empty((B, info.num_queries, info.d_model), np.float32)
-    keep = [hw, ptrs, d_frames, feats, frames, pix]
+    rows = np.empty(B * info.num_queries, F.REC_DTYPE)
+    ids, nf, done = np.empty((B, info.num_queries), np.int32), np.empty(B, np.int32), np.empty(1, np.int32)
+    keep = [hw, ptrs, d_frames, feats, frames, pix, rows, ids, nf, done]
 
     def async_(kind):
         def call(o):
@@ -78,6 +93,20 @@ def _entries(lib, h, info, frames, pix, host_only):
             _capi.check(lib.opd_detr_detect_async(h, pix.ctypes.data, U8, kind, B, H, W, 0.05, hw_p, o.recs, o.cnts, C.byref(t)), "opd_detr_detect_async")
             _capi.check(lib.opd_detr_wait(h, t.value), "opd_detr_wait")
             return 0
+        return call
+
+    def track(kind, sequence):
+        def call(o):   # a fresh tracker per call (one per frame, or one for the run): what an earlier call left in one is not this call's input
+            ts = [TC.create(lib, _capi, info.d_model, **TRACKER) for _ in range(1 if sequence else B)]
+            try:
+                if sequence:
+                    return lib.opd_detr_detect_sequence_track(h, None, ts[0], ptrs, B, fh, fw, H, W, 0.05, PERSON, kind, 0, o.recs, o.cnts, ids.ctypes.data,
+                                                              nf.ctypes.data, done.ctypes.data)
+                return lib.opd_detr_detect_frames_track(h, None, (C.c_void_p * B)(*[t.value for t in ts]), ptrs, B, fh, fw, H, W, 0.05, PERSON, kind, 0, o.recs,
+                                                        o.cnts, ids.ctypes.data, nf.ctypes.data)
+            finally:
+                for t in ts:
+                    lib.opd_track_destroy(t)
         return call
 
     e = {
@@ -90,17 +119,26 @@ def _entries(lib, h, info, frames, pix, host_only):
                                                                                           feats.ctypes.data_as(F32P)),
         ("detect_frames_color", False): lambda o: lib.opd_detr_detect_frames_color(h, ptrs, B, fh, fw, H, W, 0.05, PERSON, o.recs, o.cnts,
                                                                                     feats.ctypes.data_as(F32P)),
+        ("detect_frames_floor", False): lambda o: lib.opd_detr_detect_frames_floor(h, floor, ptrs, B, fh, fw, H, W, 0.05, PERSON, o.recs, o.cnts, rows.ctypes.data),
         ("detect_async host", False): async_(HOST),
         ("detect_async device out", True): async_(DEVOUT),
     }
+    if nms:
+        e.update({("detect_frames_track none", False): track(_capi.OPD_TRACK_FEAT_NONE, False),
+                  ("detect_frames_track colour", False): track(_capi.OPD_TRACK_FEAT_COLOR, False),
+                  ("detect_sequence_track none", False): track(_capi.OPD_TRACK_FEAT_NONE, True),
+                  ("detect_sequence_track colour", False): track(_capi.OPD_TRACK_FEAT_COLOR, True)})
     return {k: v for k, v in e.items() if not (host_only and k[1])}, keep
 
 
-@pytest.mark.parametrize("cam", [(48, 64), (64, 96)], ids=["resize", "direct"])
-def test_all_entry_points_return_the_same_bytes(handle, cam):
+@pytest.mark.parametrize("cam,nms", [((48, 64), False), ((64, 96), False), ((48, 64), True), ((64, 96), True)],
+                         ids=["resize", "direct", "resize-nms", "direct-nms"])
+def test_all_entry_points_return_the_same_bytes(handle, floor, cam, nms):
     """Camera frames 48 x 64 (device resize) and 64 x 96 (straight upload) through every detect entry point, each called twice (eager, then
     the captured graph): counts and records are byte-identical to opd_detr_detect on the resized pixels with orig_hw = the camera size; the
-    two forward entries agree bit for bit; a clone of the handle returns the same through the host-output entries."""
+    two forward entries agree bit for bit; a clone of the handle returns the same through the host-output entries.  Once with the handle's
+    suppression off, once with opd_detr_set_nms(PERSON, 0.4): opd_detr_detect's bytes are then the suppressed ones, every frame keeps a
+    record, and the tracking entries (a fresh tracker per call, feature kinds none and colour) return them too."""
     lib, h, info = handle
     Q, ncls = info.num_queries, info.num_classes_plus1
     fh, fw = cam
@@ -115,7 +153,9 @@ def test_all_entry_points_return_the_same_bytes(handle, cam):
     try:
         want = None
         for hd, host_only in ((h, False), (clone, True)):
-            entries, keep = _entries(lib, hd, info, frames, pix, host_only)
+            if nms:
+                _capi.check(lib.opd_detr_set_nms(hd, PERSON, NMS_IOU), "opd_detr_set_nms")
+            entries, keep = _entries(lib, hd, info, frames, pix, host_only, floor, nms)
             for (name, device), call in entries.items():
                 for rep in range(2):
                     out = _Out(Q, device)
@@ -124,6 +164,9 @@ def test_all_entry_points_return_the_same_bytes(handle, cam):
                     if want is None:
                         want = got
                         assert len(want[1]) > 0, "no record at threshold 0.05: nothing to compare"
+                        if nms:
+                            kept = np.frombuffer(want[0], np.int32)
+                            assert (kept > 0).all(), f"suppression left a frame without a record (counts {kept.tolist()}): nothing for a tracker to take"
                     assert got == want, f"{name} (call {rep + 1}{', clone' if host_only else ''}) differs from opd_detr_detect"
             fw_out = []
             for rep in range(2):
@@ -139,6 +182,7 @@ def test_all_entry_points_return_the_same_bytes(handle, cam):
             del keep
     finally:
         lib.opd_detr_destroy(clone)
+        _capi.check(lib.opd_detr_set_nms(h, PERSON, -1.0), "opd_detr_set_nms")
 
 
 def test_refusals_keep_their_code_and_wording(handle):
