@@ -249,6 +249,7 @@ TEST_API = {
     "opd_test_trace_conv": (C.c_int, [C.c_int] * 10 + [C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
     "opd_test_btail": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 6),
     "opd_test_bench_btail": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_float)]),
+    "opd_test_bench_btail_sc2": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_float)]),
     "opd_test_btail_repeat": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 6 + [C.POINTER(C.c_int)]),
     "opd_test_attention": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float]),
     "opd_test_layernorm": (C.c_int, [C.c_void_p] * 5 + [C.c_int]),
@@ -269,10 +270,12 @@ TEST_API = {
     "opd_test_resize_coeffs": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "opd_test_valid_prefix": (C.c_int, [C.c_int] * 3),
     "opd_test_trunk_plan": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "opd_test_trunk_plan_one_launch": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_int]),
     "opd_test_transformer_plan": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_int]),
     "opd_test_sine_pos_embed": (C.c_int, [C.c_int] * 5 + [C.c_void_p]),
     "opd_test_conv_dual": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 13),
     "opd_test_btail_sc": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 3),
+    "opd_test_btail_sc2": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 4),
     "opd_test_btail_chain": (C.c_int, [C.c_void_p] * 13 + [C.c_int] * 4),
     "opd_test_bench_attention": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float, C.c_int, C.POINTER(C.c_float)]),
     "opd_test_trace_attention": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),

@@ -75,6 +75,11 @@ __device__ __forceinline__ void lds_read16x4_raw(const unsigned char* const (&pt
 // that a separate launch wrote (274 MB at batch 8) and this kernel read back: the 64 shortcut channels of the wave's 32 pixels sit
 // in 16 VGPRs as B fragments, the 64 x 64 slice of Wsc travels with the W2 / W3 chunk operands.  The shortcut is no longer
 // rounded to fp16 on the way (one rounding fewer than the unfused path; the reference rounds nothing).
+// SC at C1 == 128 (SC2; first block of stage 2: stride-2 3x3, shortcut input of 256 channels on the 3x3's input grid, read at (2 oh, 2 ow)):
+// the same second GEMM, with the 256 channels in 64 VGPRs.  A chunk's operands (W2 16 KiB + Wsc 32 KiB + W3 16 KiB) do not fit a 32-KiB stage
+// buffer, so a chunk runs as two HALF STEPS with a barrier each (see `issue_w2` / `issue_wsc_w3`): 80 KiB of LDS, two workgroups per CU.  The k
+// order -- bias, a1's blocks, then the shortcut input's -- is that of the dual-source expand it replaces (Block::w2sc = [W2 | Wsc]): same bits.
+// Measured (tools/bench_btail.py --sc2, batch 8): 149 us against 55 + 83 + 34 us for 3x3, dual-source expand and the next reduce.
 // TRACE (tools/trace_btail.py): wave 0 stamps the shader clock at the phase boundaries and writes p.trace[blockIdx.x][16] at the end:
 // {wall clock in, entry, prologue done, 3x3 loop done, chunk 0 .. NCH-1 done, stores retired, ..., [15] wall clock out}.
 // RC = 1 (round 5; second block of stage 1): the residual is not read but REBUILT.  The previous block's output y' = relu(W2' . a1' + Wsc . xs +
@@ -93,7 +98,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     stamp(1);
     static_assert(!RDMA || C1 == 64 || C1 == 128, "residual staging buffers are budgeted for C1 == 64 and C1 == 128 (80 KiB of LDS per workgroup)");
     static_assert(!RDMA || RC == 0, "a rebuilt residual is not staged");
-    static_assert(!SC || (C1 == 64 && !RDMA), "fused shortcut: 64-channel tails only; it replaces the residual");
+    static_assert(!SC || ((C1 == 64 || C1 == 128) && !RDMA), "fused shortcut: first block of stage 1 or 2; it replaces the residual");
+    constexpr bool SC2 = SC && C1 == 128;      // first block of stage 2: stride-2 shortcut over 256 channels, chunk operands in half steps (below)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int C2 = 4 * C1;
     constexpr int NT1 = C1 / 16;               // c1 accumulator tiles per wave (all C1 channels)
@@ -111,7 +117,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     constexpr int NT3 = C3 / 16;
     constexpr int WSC_BYTES = SC ? 64 * ROW_BYTES : 0;   // chunk of Wsc: [64 rows][64 halfs]
     constexpr int CHUNK_BYTES = W2C_BYTES + C3 * ROW_BYTES + WSC_BYTES + RC_BYTES;
-    constexpr int STAGE_BYTES = (A_BYTES + C1 * ROW_BYTES) > CHUNK_BYTES ? (A_BYTES + C1 * ROW_BYTES) : CHUNK_BYTES;   // a stage buffer holds a 3x3 k-step's tiles or a chunk's operands
+    // a stage buffer holds a 3x3 k-step's tiles or a chunk's operands (SC2: a half step's, with the W3 slice behind the two buffers)
+    constexpr int STAGE_BYTES = SC2 || (A_BYTES + C1 * ROW_BYTES) > CHUNK_BYTES ? (A_BYTES + C1 * ROW_BYTES) : CHUNK_BYTES;
+    static_assert(!SC2 || 2 * STAGE_BYTES + C3 * ROW_BYTES <= 80 * 1024, "SC2 tails: at most 80 KiB of LDS, two workgroups per CU");
     static_assert(RC == 0 || (RC == 1 && C1 == 64 && !RDMA && !SC), "residual rebuild: second block of stage 1");
     // RDMA at C1 == 128: the stage buffers are 32 KiB each, which leaves room for ONE wave-private residual buffer (RB1) at two workgroups per CU
     constexpr bool RB1 = RDMA && C1 == 128;
@@ -136,7 +144,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     const __amdgpu_buffer_rsrc_t rsrc_w1 = buf_rsrc(p.w1, (unsigned)(C1 * 9 * C1 * 2));
     const __amdgpu_buffer_rsrc_t rsrc_w2 = buf_rsrc(p.w2p, (unsigned)(C2 * C1 * 2));
     const __amdgpu_buffer_rsrc_t rsrc_w3 = buf_rsrc(C3 ? p.w3p : p.w2p, (unsigned)((C3 ? C3 : 1) * C2 * 2));
-    const __amdgpu_buffer_rsrc_t rsrc_sc = buf_rsrc(SC ? p.wsc : RC ? p.rc_wsc : p.w2p, (unsigned)(C2 * 64 * 2));
+    const __amdgpu_buffer_rsrc_t rsrc_sc = buf_rsrc(SC ? p.wsc : RC ? p.rc_wsc : p.w2p, (unsigned)(C2 * (SC2 ? 256 : 64) * 2));
     const __amdgpu_buffer_rsrc_t rsrc_rw = buf_rsrc(RC ? p.rc_w2 : p.w2p, (unsigned)(C2 * 64 * 2));
     unsigned rowoff[4], rowmask[4], woff1[W1_PIECES], woff2[W2_PIECES], woff3[W3_PIECES ? W3_PIECES : 1], woffsc[2];
 #pragma unroll
@@ -258,7 +266,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     // SC: the shortcut's input channels of this wave's 32 pixels as B fragments (k in natural order: Wsc is not permuted);
     // loaded in front of everything else, complete at the first barrier's vmcnt(0)
     half8 xs[2][2], a1p[2][2];   // RC: the same for the previous block: its shortcut input and its a1
-    if constexpr (SC || RC != 0) {
+    if constexpr ((SC && !SC2) || RC != 0) {
         const f16_t* xsrc = SC ? p.xs : p.rc_xs;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
@@ -308,13 +316,55 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
         __syncthreads();
     }
     // last k-step: the free stage buffer receives chunk 0's operands; residual chunks 0 and 1 (RB1: chunk 0) start their trip
-    float4v b2n[4];   // RB1: the expand bias of the next chunk step, loaded in front of that step's LDS-DMA requests
-    if constexpr (RB1) {
+    float4v b2n[4];   // RB1 / SC2: the expand bias of the next chunk step, loaded in front of that step's LDS-DMA requests
+    // SC2: the shortcut's 256 input channels of this wave's 32 pixels as B fragments, gathered at (stride oh, stride ow) of the H x W grid of
+    // the previous stage's output.  Requested here, where acc1 is about to die; complete at the vmcnt(0) that ends the 3x3 loop.
+    half8 xs2[2][SC2 ? 8 : 1];
+    if constexpr (SC2) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const int m = wm0 + mt * 16 + li;
+            const int mm = m < p.M ? m : 0;   // (rows >= M: any valid pixel, never stored)
+            const int b = fdiv(mm, p.fd_ohw);
+            const int r = mm - b * (p.OH * p.OW);
+            const int oh = fdiv(r, p.fd_ow), ow = r - oh * p.OW;
+            const f16_t* src = p.xs + ((size_t)(b * p.H + oh * p.stride) * p.W + ow * p.stride) * 256 + g * 8;
+#pragma unroll
+            for (int kb = 0; kb < 8; ++kb) xs2[mt][kb] = *reinterpret_cast<const half8*>(src + kb * 32);
+        }
+    }
+    if constexpr (RB1 || SC2) {
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) b2n[nt] = *reinterpret_cast<const float4v*>(p.b2 + own_ch(nt, g));
         compiler_fence();
     }
-    issue_chunk(0, nk & 1);
+    // SC2 half steps.  A chunk's operands are W2 16 KiB + Wsc 32 KiB + W3 16 KiB against 32-KiB stage buffers, so chunk j runs as two steps
+    // with a barrier each: the EVEN step reads W2[j] (buffer 0) while Wsc[j] (buffer 1) and the W3 slice (behind the buffers) are on their way,
+    // the ODD step reads those while W2[j + 1] is.  One per-lane offset per matrix: own_row of a piece's rows is (piece part) + (lane part),
+    // and the piece part is a wave-uniform displacement.
+    const unsigned own_lrow = (unsigned)(8 * (lrow >> 2) + (lrow & 3));
+    const unsigned voff2 = ((32u * (wave & 1) + own_lrow) * C1 + (wave >> 1) * 64u) * 2u + (unsigned)lchunk * 16u;   // wave: sub-tile wave >> 1, rows 32 (wave & 1) ..
+    const unsigned voffw = (own_lrow * 256u + wave * 64u) * 2u + (unsigned)lchunk * 16u;                            // wave: the whole sub-tile `wave` of Wsc
+    const unsigned voff3 = (32u * wave + own_lrow) * (unsigned)C2 * 2u + (unsigned)lchunk * 16u;                    // wave: rows 32 wave .. of W3
+    auto piece_rows = [](const int i) { return 16 * (i & 1) + 4 * ((i >> 1) & 1) + 32 * (i >> 2); };                // own_row(8 i) for i < 8
+    auto issue_w2 = [&](int j) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dma16_buf(rsrc_w2, smem + (wave * 4 + i) * 1024, voff2, j * (64 * C1 * 2) + piece_rows(i) * C1 * 2);
+    };
+    auto issue_wsc_w3 = [&](int j) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) dma16_buf(rsrc_sc, smem + STAGE_BYTES + (wave * 8 + i) * 1024, voffw, j * (64 * 256 * 2) + piece_rows(i) * 256 * 2);
+        if constexpr (C3 > 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dma16_buf(rsrc_w3, smem + 2 * STAGE_BYTES + (wave * 4 + i) * 1024, voff3, j * 128 + piece_rows(i) * C2 * 2);
+        }
+    };
+    if constexpr (SC2) {
+        static_assert((nk & 1) == 0, "SC2: chunk 0's W2 goes into buffer 0, the one the last k-step does not read");
+        issue_w2(0);
+    } else {
+        issue_chunk(0, nk & 1);
+    }
     compiler_fence();
     if constexpr (RC == 0) {
         load_res(0, res[0]);
@@ -363,6 +413,91 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
 
     // ---- chunk steps: 64 channels of y each ------------------------------------------------------------------------------
     if (p.dbg & 8) return;
+    if constexpr (SC2) {
+        // ---- SC2: y = relu((b2 + bsc) + W2 . a1 + Wsc . xs), k order a1's blocks then xs's (the dual-source expand's), in half steps ---------
+        const unsigned char* const W2s = smem;
+        const unsigned char* const Wscs = smem + STAGE_BYTES;
+        const unsigned char* const W3s = smem + 2 * STAGE_BYTES;
+        float4v acc2[4][2];
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            // even step: W2[j] has landed (the barrier before); buffer 1 and the W3 slice were last read before that barrier
+            issue_wsc_w3(j);
+            compiler_fence();
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                acc2[nt][0] = b2n[nt];
+                acc2[nt][1] = b2n[nt];
+            }
+#pragma unroll
+            for (int kk = 0; kk < KK1; ++kk) {
+                half8 wf[4];
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) wf[nt] = *reinterpret_cast<const half8*>(W2s + (kk >> 1) * 8192 + swz(nt * 16 + li, (kk & 1) * 4 + g));
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt) acc2[nt][mt] = OPD_MFMA_16x16x32(wf[nt], a1[mt][kk], acc2[nt][mt]);
+            }
+            wait_vmcnt<0>();   // Wsc[j] and the W3 slice landed (and the previous step's y stores retired: nothing else is in flight)
+            __builtin_amdgcn_s_barrier();
+            // odd step: the next chunk's bias in front of the requests, W2[j + 1] into buffer 0
+            compiler_fence();
+            if (j + 1 < NCH) {
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) b2n[nt] = *reinterpret_cast<const float4v*>(p.b2 + (j + 1) * 64 + own_ch(nt, g));
+                compiler_fence();
+                issue_w2(j + 1);
+            }
+            compiler_fence();
+#pragma unroll
+            for (int kb = 0; kb < 8; ++kb) {
+                half8 wf[4];
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) wf[nt] = *reinterpret_cast<const half8*>(Wscs + (kb >> 1) * 8192 + swz(nt * 16 + li, (kb & 1) * 4 + g));
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt) acc2[nt][mt] = OPD_MFMA_16x16x32(wf[nt], xs2[mt][kb], acc2[nt][mt]);
+            }
+            half8 yf[2][2];   // [q][mt]
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) {
+                    float4v v0 = acc2[2 * q][mt], v1 = acc2[2 * q + 1][mt];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        v0[r] = v0[r] > 0.f ? v0[r] : 0.f;
+                        v1[r] = v1[r] > 0.f ? v1[r] : 0.f;
+                    }
+                    yf[q][mt] = as_half8(pack2h(v0[0], v0[1]), pack2h(v0[2], v0[3]), pack2h(v1[0], v1[1]), pack2h(v1[2], v1[3]));
+                }
+            if constexpr (C3 > 0) {
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+                    for (int nt = 0; nt < NT3; ++nt) {
+                        const half8 wf = *reinterpret_cast<const half8*>(W3s + swz(nt * 16 + li, kk * 4 + g));
+#pragma unroll
+                        for (int mt = 0; mt < 2; ++mt) accz[nt][mt] = OPD_MFMA_16x16x32(wf, yf[kk][mt], accz[nt][mt]);
+                    }
+                }
+            }
+            if (j + 1 < NCH) {
+                wait_vmcnt<0>();   // W2[j + 1] landed
+                __builtin_amdgcn_s_barrier();
+            }
+            // the y stores go out behind the wait: they fly during the next even step
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+                    if (y_ok[mt] && !(p.dbg & 2)) *reinterpret_cast<half8*>(p.y + pr_row[mt] + j * 64 + q * 32) = yf[q][mt];
+            stamp(4 + j);
+        }
+    }
+    if constexpr (!SC2)
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
         const int buf = (nk + j) & 1;
@@ -556,7 +691,8 @@ template <int C1, int C3, bool RDMA, bool SC = false, bool TRACE = false, int RC
 hipError_t launch_btail_t(const BtailParams& p, hipStream_t stream) {
     constexpr int BM = 32 * NW;
     constexpr int MAIN = (BM + C1) * ROW_BYTES, CHUNK = 64 * C1 * 2 + C3 * ROW_BYTES + (SC ? 64 * ROW_BYTES : 0) + (RC ? 2 * 64 * ROW_BYTES : 0);
-    constexpr int LDS = 2 * (MAIN > CHUNK ? MAIN : CHUNK) + (RDMA ? (C1 == 128 ? 1 : 2) * NW * 4096 : 0);   // C1 == 128: one residual buffer
+    constexpr int LDS = SC && C1 == 128 ? 2 * MAIN + C3 * ROW_BYTES                                           // half steps: the W3 slice behind the stage buffers
+                                        : 2 * (MAIN > CHUNK ? MAIN : CHUNK) + (RDMA ? (C1 == 128 ? 1 : 2) * NW * 4096 : 0);   // C1 == 128: one residual buffer
     static_assert(LDS <= 160 * 1024 && (!RDMA || LDS == 80 * 1024), "LDS per workgroup");
     OPD_SET_MAX_LDS_ONCE((btail_kernel<C1, C3, RDMA, SC, TRACE, RC>), LDS);
     OPD_LAUNCH((btail_kernel<C1, C3, RDMA, SC, TRACE, RC>), dim3((p.M + BM - 1) / BM), dim3(64 * NW), LDS, stream, p);
@@ -583,6 +719,10 @@ hipError_t OPD_SYM(opd_launch_btail)(const BtailParams& p_in, hipStream_t stream
             p.trace || (size_t)p.M * 64 * 2 >= 0x7fffff00ull)
             return hipErrorInvalidValue;
         return launch_btail_t<64, 64, false, false, false, 1>(p, stream);
+    }
+    if (p.xs && p.C1 == 128) {   // fused shortcut convolution: stride 2, 256 -> 512 channels next to a 128-channel 3x3 (first block of stage 2)
+        if (!opd_btail_sc_supported(p.C1, p.C3, 256, p.stride) || !p.wsc || p.res || !p.y || p.a1_out || p.trace) return hipErrorInvalidValue;
+        return p.C3 ? launch_btail_t<128, 128, false, true>(p, stream) : launch_btail_t<128, 0, false, true>(p, stream);
     }
     if (p.xs) {   // fused shortcut convolution: stride 1, 64 -> 256 channels next to a 64-channel 3x3 (first block of stage 1)
         if (p.C1 != 64 || p.C3 != 64 || p.stride != 1 || !p.wsc || p.res || (size_t)p.M * 64 * 2 >= 0x7fffff00ull) return hipErrorInvalidValue;

@@ -458,6 +458,7 @@ Switches opd::read_switches(int flags) {
     Switches sw;
     auto env = [](const char* name, int* v) { if (const char* e = getenv(name)) *v = atoi(e); };
     env("OPD_DUAL_OVER_TAIL", &sw.dual_over_tail);
+    env("OPD_SC2_TAIL", &sw.sc2_tail);
     env("OPD_TAIL_REV", &sw.tail_rev);
     env("OPD_TAIL3", &sw.tail3);
     env("OPD_TAIL_RC", &sw.tail_rc);

@@ -132,8 +132,9 @@ struct BtailParams {
     const f16_t* w2p;  // [4*C1][C1]
     const float* b2;
     const f16_t* res;  // [M][4*C1] or null
-    const f16_t* xs;   // optional fused shortcut (C1 == 64, C3 == 64, stride 1, res == null): its input [M][64] fp16 ...
-    const f16_t* wsc;  // ... and its folded 1x1 weights [4*C1][64] (plain K order); b2 then holds b2 + the shortcut's bias
+    const f16_t* xs;   // optional fused shortcut (opd_btail_sc_supported, res == null): its input, [M][64] fp16 for C1 == 64 (stride 1),
+                       // [B][H][W][256] for C1 == 128 (stride 2: read at the pixels (2 oh, 2 ow) of the 3x3's input grid) ...
+    const f16_t* wsc;  // ... and its folded 1x1 weights [4*C1][64 / 256] (plain K order); b2 then holds b2 + the shortcut's bias
     f16_t* y;          // [M][4*C1]
     const f16_t* w3p;  // [C3][4*C1] (C3 > 0)
     const float* b3;
@@ -165,6 +166,10 @@ struct BtailParams {
 inline bool opd_btail256_supported(int C1, int C3) { return C1 == 256 && (C3 == 0 || C3 == 256); }
 inline bool opd_btail_supported(int C1, int C3) {
     return (C1 == 64 && (C3 == 0 || C3 == 64 || C3 == 128)) || (C1 == 128 && (C3 == 0 || C3 == 128)) || opd_btail256_supported(C1, C3);
+}
+// the block's 1x1 shortcut convolution (Csc input channels, the 3x3's stride) inside the tail: first block of stage 1 / of stage 2
+inline bool opd_btail_sc_supported(int C1, int C3, int Csc, int stride) {
+    return (C1 == 64 && C3 == 64 && Csc == 64 && stride == 1) || (C1 == 128 && (C3 == 0 || C3 == 128) && Csc == 256 && stride == 2);
 }
 hipError_t opd_launch_btail(const BtailParams& p, hipStream_t stream);
 // 256-channel blocks (stage 3): eight-wave form, kernels_btail3.hip; reached through opd_launch_btail

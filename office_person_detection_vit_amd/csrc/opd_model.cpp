@@ -376,6 +376,8 @@ TrunkPlan plan_trunk(const Arch& a, const std::vector<Block>& blocks, const opd_
                                     nbk->c0.Cin == 256 && nbk->c0.Cout == 64;
             bool tail = sw.fuse_btail && b.c1.KH == 3 && b.c1.Cout == C1 && b.c2.Cin == C1 && b.c2.Cout == 4 * C1 && conv_has_kperm(b.c2) &&
                         opd_btail_supported(C1, 0);
+            // what the one-launch form of the dual-source route needs of the block (below): a 128-channel tail shape
+            const bool tail128 = tail && C1 == 128;
             // first block of stage 2: 3x3 + dual-source expand (+ the next reduce on its own) beats shortcut launch + fused tail
             // (stage 2: 0.674 -> 0.657 ms; OPD_DUAL_OVER_TAIL=0 restores the tail)
             if (sw.dual_over_tail && tail && b.has_sc && !sc_in_tail && block_has_w2sc(b)) tail = false;
@@ -400,6 +402,17 @@ TrunkPlan plan_trunk(const Arch& a, const std::vector<Block>& blocks, const opd_
             t.store = STORE_Y;
             t.C3 = 0;
             if (tail && nbk && conv_has_kperm(nbk->c0) && nbk->c0.Cin == 4 * C1 && opd_btail_supported(C1, nbk->c0.Cout)) t.C3 = nbk->c0.Cout;
+            // First block of stage 2 (256 -> 512 channels, stride 2) on the dual-source route: its 3x3, its expand over [a1 | block input] and the
+            // next block's reduce are issued as ONE launch of the fused tail with the shortcut inside (kernels_btail.hip, SC2).  The route is
+            // still the dual-source one -- same operands (bias2sc), same K order, same rounding points, hence the same bits -- so the step stays
+            // PATH_DUAL / SC_EXPAND and `one_launch` says how it is issued; OPD_SC2_TAIL=0 restores the three launches.
+            t.one_launch = t.one_C3 = t.one_rev = 0;
+            if (t.path == PATH_DUAL && sw.sc2_tail && sw.fuse_btail && tail128 && b.sc.KH == 1 && b.sc.stride == b.c1.stride &&
+                opd_btail_sc_supported(C1, 0, b.sc.Cin, b.c1.stride) && (size_t)B * ch * cw * b.sc.Cin * 2 < 0x7ff00000ull) {
+                t.one_launch = 1;
+                if (nbk && conv_has_kperm(nbk->c0) && nbk->c0.Cin == 4 * C1 && opd_btail_sc_supported(C1, nbk->c0.Cout, b.sc.Cin, b.c1.stride)) t.one_C3 = nbk->c0.Cout;
+                t.one_rev = sw.tail_rev ? 1 : 0;   // from the rows stage 1's last tail wrote last (measured: the other direction reads the same)
+            }
             // The last block of stage 1 hands the next stage its reduce output z (fused above); the block output itself is then read
             // by that stage's stride-2 shortcut only, i.e. at even (oh, ow): the other three quarters of its 274 MB are not stored.
             if (tail && sw.y_stride2 && t.C3 && b.c1.stride == 1 && l + 1 == a.depths[s] && nbk && nbk->has_sc && nbk->sc.stride == 2 && nbk->sc.KH == 1 &&
@@ -604,7 +617,7 @@ static int trunk_blocks(const Fwd& c, const TrunkPlan& tp, int s, int b0, int nb
         const TrunkStep& t = tp.steps[bi];
         const int ch = st.ch, cw = st.cw;
         const int oh = (b.c1.stride == 2) ? down2(ch) : ch, ow = (b.c1.stride == 2) ? down2(cw) : cw;
-        const int C1 = b.c1.Cin, C2 = b.c2.Cout, C3 = t.C3;
+        const int C1 = b.c1.Cin, C2 = b.c2.Cout, C3 = t.one_launch ? t.one_C3 : t.C3;
         const f16_t* cur = trunk(st.cur_id, (size_t)ch * cw * b.c0.Cin);
         const int out_id = st.cur_id == 1 ? 2 : 1;
         f16_t* out = trunk(out_id, (size_t)oh * ow * C2);
@@ -622,12 +635,12 @@ static int trunk_blocks(const Fwd& c, const TrunkPlan& tp, int s, int b0, int nb
             x1 = c0out;
         }
         st.z_id = -1;
-        if (t.path == PATH_TAIL) {
+        if (t.path == PATH_TAIL || t.one_launch) {
             const Block* nbk = C3 ? &m->blocks[bi + 1] : nullptr;
             BtailParams p{}; p.dtype = m->dtype;
             p.x1 = x1; p.w1 = b.c1.w; p.b1 = b.c1.bias; p.w2p = C1 == 256 ? b.c2.wp : b.c2.w; p.b2 = b.c2.bias; p.res = res;   // (K-permuted copies: stage-3 kernel only)
             p.y = t.store == STORE_A1 ? nullptr : out;
-            if (t.sc == SC_TAIL) { p.xs = cur; p.wsc = b.sc.w; p.b2 = b.bias2sc; }
+            if (t.sc == SC_TAIL || t.one_launch) { p.xs = cur; p.wsc = b.sc.w; p.b2 = b.bias2sc; }
             f16_t* z = mid(1 - x1_id, (size_t)oh * ow * C3);
             if (C3) { p.w3p = C1 == 256 ? nbk->c0.wp : nbk->c0.w; p.b3 = nbk->c0.bias; p.z = z; }
             // stage 1's a1 hand-over (STORE_A1 -> RES_REBUILD) lives in the shortcut buffer, which a fused shortcut leaves unused
@@ -639,9 +652,9 @@ static int trunk_blocks(const Fwd& c, const TrunkPlan& tp, int s, int b0, int nb
             }
             p.y_stride2 = t.store == STORE_Y_STRIDE2;
             p.B = nb; p.H = ch; p.W = cw; p.OH = oh; p.OW = ow; p.stride = b.c1.stride; p.M = nb * oh * ow; p.C1 = C1; p.C3 = C3;
-            p.rev = b0 ? t.rev_b : t.rev;
+            p.rev = t.one_launch ? t.one_rev : b0 ? t.rev_b : t.rev;
             p.dbg = m->sw.dbg_btail | (C1 == 128 && !m->sw.res_dma128 ? 16 : 0);   // (bit 16: the residual through register loads)
-            RCCHK(c.launch(CLS_CONV, 2.0 * p.M * ((double)C1 * 9 * C1 + 4.0 * C1 * C1 + 4.0 * C1 * C3 + (t.sc == SC_TAIL ? 64.0 * 256 : 0.0)),
+            RCCHK(c.launch(CLS_CONV, 2.0 * p.M * ((double)C1 * 9 * C1 + 4.0 * C1 * C1 + 4.0 * C1 * C3 + (p.xs ? (double)b.sc.Cin * C2 : 0.0)),
                            [&] { return opd_launch_btail(p, c.stream); },
                            {{"btail_y", p.y ? out : nullptr, (size_t)p.M * 4 * C1 * 2}, {"btail_z", C3 ? z : nullptr, (size_t)p.M * C3 * 2}}));
             if (C3) st.z_id = 1 - x1_id;

@@ -116,6 +116,8 @@ struct Switches {
     int fuse_btail = 1;      // stages 1-2: 3x3 -> expand + residual -> next reduce in one kernel (0: three launches)
     int fuse_shortcut = 1;   // first block of stage 1: the shortcut convolution as a second GEMM inside the fused tail (0: own launch)
     int dual_over_tail = 1;  // first block of stage 2: 3x3 + dual-source expand instead of shortcut launch + fused tail (-17 us)
+    int sc2_tail = 1;        // ... and that dual-source route issued as one launch of the fused tail with the stride-2 shortcut inside
+                             // (kernels_btail.hip, SC2; env OPD_SC2_TAIL, 0: three launches)
     int tail_rev = 1;        // consecutive fused tails walk their tiles in opposite directions (Infinity Cache reuse of the block output)
     int tail3 = 1;           // stage 3 (256-channel blocks) through the eight-wave fused tail (kernels_btail3.hip) where it pays (plan_trunk);
                              // 0: never (three launches per block), 2: always
@@ -155,6 +157,10 @@ struct TrunkStep {
     int path, sc, res, store;
     int C3;           // fused tails: channels of the next block's reduce, computed here as z (0: none)
     int rev, rev_b;   // BtailParams::rev of the launch; rev_b: of its launch in the stage-3 split's second chain
+    int one_launch;   // PATH_DUAL, first block of stage 2: 3x3, dual-source expand and the next block's reduce issued as ONE launch of the fused
+                      // tail with the shortcut inside (kernels_btail.hip, SC2): the dual route's arithmetic and bits, one launch instead of three
+    int one_C3;       // ... channels of that reduce, computed there as z (0: the reduce keeps its launch)
+    int one_rev;      // ... BtailParams::rev of that launch (it stands outside the alternation of the PATH_TAIL launches)
 };
 struct TrunkPlan {
     std::vector<TrunkStep> steps;   // one per block, in stage order

@@ -591,6 +591,33 @@ TAPI int opd_test_btail_sc(const uint16_t* x1, const uint16_t* w1, const float* 
     return down(z, p.z, M * C3);
 }
 
+// ... and the first block of stage 2 (kernels_btail.hip, SC2): x1 [B][H][W][128] under a stride-2 3x3, xs [B][H][W][256] = the shortcut's input on
+// the same grid (read at (2 oh, 2 ow)), wsc [512][256]; b2sc = b2 + the shortcut's bias.  C3 = 128, or 0: no z.
+TAPI int opd_test_btail_sc2(const uint16_t* x1, const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2sc, const uint16_t* xs,
+                            const uint16_t* wsc, const uint16_t* w3, const float* b3, uint16_t* y, uint16_t* z, int B, int H, int W, int C3) {
+    const int C1 = 128, C2 = 512, Csc = 256;
+    if (!opd_btail_sc_supported(C1, C3, Csc, 2) || B < 1 || H < 1 || W < 1) return fail(OPD_EINVAL, "btail_sc2: unsupported C3 or shape");
+    DevMem dm;
+    BtailParams p{}; p.dtype = g_test_dtype;
+    btail_geometry(p, B, H, W, 2, C1, C3);
+    const size_t M = (size_t)p.M, HW = (size_t)B * H * W;
+    p.x1 = dm.up(x1, HW * C1);
+    p.w1 = dm.up(w1, (size_t)C1 * 9 * C1);
+    p.b1 = dm.up(b1, C1);
+    btail_weights(dm, p, C1, C3, w2, w3);
+    p.b2 = dm.up(b2sc, C2);
+    p.xs = dm.up(xs, HW * Csc);
+    p.wsc = dm.up(wsc, (size_t)C2 * Csc);
+    p.y = dm.alloc<uint16_t>(M * C2);
+    p.b3 = C3 ? dm.up(b3, C3) : nullptr;
+    p.z = C3 ? dm.alloc<uint16_t>(M * C3) : nullptr;
+    if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
+    RCCHK(launch_repeated([&](int rep) { p.rev = rep & 1; return LAUNCHED(opd_launch_btail(p, nullptr)); }, {{p.y, M * C2 * 2, 0xff}, {p.z, M * C3 * 2, 0xff}}));
+    HIPCHK(hipDeviceSynchronize());
+    RCCHK(down(y, p.y, M * C2));
+    return C3 ? down(z, p.z, M * C3) : OPD_OK;
+}
+
 // Stage 1's first two tails and its last one, both ways (kernels_btail.hip, round 5).  Blocks a (shortcut inside), b, c on x1 [B][H][W][64] /
 // xs [M][64]; weights as in opd_test_btail_sc / opd_test_btail (w3a, w3b: [64][256], w3c: [128][256]).
 //   old: tail a stores y_a -> tail b reads it back as its residual -> tail c stores all of y_c;

@@ -153,6 +153,38 @@ TAPI int opd_test_bench_btail(int B, int H, int W, int C1, int C3, int stride, i
     return OPD_OK;
 }
 
+// Stage 2's first block: the fused tail with the stride-2 shortcut inside (us_out[0]; kernels_btail.hip, SC2) and the three launches it replaces
+// (us_out[1..3]: 3x3 stride 2, dual-source expand over [a1 | block input], the next block's reduce) on x1 [B][H][W][128], xs [B][H][W][256].
+TAPI int opd_test_bench_btail_sc2(int B, int H, int W, int C3, int dbg, int iters, float* us_out) {
+    const int C1 = 128, C2 = 512, Csc = 256;
+    if (!opd_btail_sc_supported(C1, C3, Csc, 2)) return fail(OPD_EINVAL, "btail_sc2: unsupported C3");
+    DevMem dm;
+    BtailParams p{};
+    btail_layer(dm, p, B, H, W, C1, C3, 2, dbg);
+    p.res = nullptr;
+    p.xs = filled16(dm, (size_t)B * H * W * Csc, 0x2c);
+    p.wsc = filled16(dm, (size_t)C2 * Csc, 0x1c);
+    uint16_t* a1 = dm.alloc<uint16_t>((size_t)p.M * C1);
+    uint16_t* w2sc = filled16(dm, (size_t)C2 * (C1 + Csc), 0x1c);
+    float* zero = zeros<float>(dm, 4096);
+    if (!dm.ok) return fail(OPD_ENOMEM, "bench alloc failed");
+    ConvGemmParams c[3] = {};
+    c[0].x = p.x1; c[0].w = p.w1; c[0].out = a1;
+    conv_geometry(c[0], B, H, W, C1, p.OH, p.OW, C1, 3, 3, 2, 1);
+    c[1].x = a1; c[1].w = w2sc; c[1].out = p.y; c[1].x2 = p.xs;
+    conv_geometry(c[1], B, p.OH, p.OW, C1, p.OH, p.OW, C2, 1, 1, 1, 0);
+    c[1].K = C1 + Csc; c[1].K1 = C1; c[1].H2 = H; c[1].W2 = W; c[1].Cin2 = Csc; c[1].stride2 = 2;
+    c[2].x = p.y; c[2].w = p.w3p; c[2].out = p.z;
+    conv_geometry(c[2], B, p.OH, p.OW, C2, p.OH, p.OW, C3 ? C3 : 64, 1, 1, 1, 0);
+    for (auto& q : c) { q.dtype = g_test_dtype; q.bias = p.b1; q.zero16 = zero; q.relu = 1; }
+    for (int k = 0; k < 4; ++k) {
+        us_out[k] = 0.f;
+        if (k > 0 && dbg) continue;
+        RCCHK(time_launches(2, iters, [&] { return k == 0 ? opd_launch_btail(p, nullptr) : opd_launch_conv_gemm(c[k - 1], nullptr); }, &us_out[k]));
+    }
+    return OPD_OK;
+}
+
 // The operands of an attention launch with leading dimension ldq / ldkv (768 = the fused QKV buffer) from the caller's q, k, v
 static void attention_operands(DevMem& dm, AttnParams& p, const uint16_t* q, const uint16_t* k, const uint16_t* v, int B, int heads, int Lq, int Lk,
                                int ldq, int ldkv, float scale) {

@@ -59,8 +59,8 @@ TAPI int opd_test_round_f16_diffused(float* w, int rows, int taps, int cin) {
 // plan_trunk (opd_model.cpp) for a ResNet trunk of the given stage depths with the bottleneck shapes infer_arch demands, default switches, a
 // branch stream, no taps, no profiling; a batch of B frames of H x W in a handle of max_batch frames.  steps_out[block][7] = path, shortcut,
 // residual, store, C3, rev, rev_b (opd_model.h); *split_out = TrunkPlan::split.  Returns the number of blocks.
-TAPI int opd_test_trunk_plan(const int* depths, int max_batch, int flags, int B, int H, int W, int num_cus, int* steps_out, int max_steps, int* split_out) {
-    if (!depths || !steps_out || !split_out || B < 1 || H < 1 || W < 1 || num_cus < 1) return fail(OPD_EINVAL, "bad trunk_plan arguments");
+static int test_trunk_plan(const int* depths, int max_batch, int flags, int B, int H, int W, int num_cus, const Switches& sw, int max_steps, TrunkPlan* out) {
+    if (!depths || B < 1 || H < 1 || W < 1 || num_cus < 1) return fail(OPD_EINVAL, "bad trunk_plan arguments");
     Arch a;
     std::vector<Block> blocks;
     auto conv = [](int cin, int cout, int k, int stride) {
@@ -85,14 +85,36 @@ TAPI int opd_test_trunk_plan(const int* depths, int max_batch, int flags, int B,
     if ((int)blocks.size() > max_steps) return fail(OPD_EINVAL, "steps_out too small");
     opd_config cfg{};
     cfg.struct_size = sizeof(opd_config); cfg.max_batch = max_batch; cfg.max_height = H; cfg.max_width = W; cfg.flags = flags;
-    const TrunkPlan plan = plan_trunk(a, blocks, cfg, Switches{}, B, down2(down2(H)), down2(down2(W)), num_cus, false, 0, true);
+    *out = plan_trunk(a, blocks, cfg, sw, B, down2(down2(H)), down2(down2(W)), num_cus, false, 0, true);
+    return (int)blocks.size();
+}
+TAPI int opd_test_trunk_plan(const int* depths, int max_batch, int flags, int B, int H, int W, int num_cus, int* steps_out, int max_steps, int* split_out) {
+    if (!steps_out || !split_out) return fail(OPD_EINVAL, "bad trunk_plan arguments");
+    TrunkPlan plan;
+    const int n = test_trunk_plan(depths, max_batch, flags, B, H, W, num_cus, Switches{}, max_steps, &plan);
+    if (n < 0) return n;
     for (size_t i = 0; i < plan.steps.size(); ++i) {
         const TrunkStep& t = plan.steps[i];
         const int row[7] = {t.path, t.sc, t.res, t.store, t.C3, t.rev, t.rev_b};
         memcpy(steps_out + 7 * i, row, sizeof(row));
     }
     *split_out = plan.split;
-    return (int)blocks.size();
+    return n;
+}
+// ... with the switches as opd_detr_create reads them (defaults overridden by the environment): one_out[block][3] = one_launch, one_C3, one_rev of
+// every step (opd_model.h: the dual-source route of stage 2's first block issued as one launch), steps_out as above (null: not wanted)
+TAPI int opd_test_trunk_plan_one_launch(const int* depths, int max_batch, int flags, int B, int H, int W, int num_cus, int* steps_out, int* one_out, int max_steps) {
+    if (!one_out) return fail(OPD_EINVAL, "bad trunk_plan arguments");
+    TrunkPlan plan;
+    const int n = test_trunk_plan(depths, max_batch, flags, B, H, W, num_cus, read_switches(flags), max_steps, &plan);
+    if (n < 0) return n;
+    for (size_t i = 0; i < plan.steps.size(); ++i) {
+        const TrunkStep& t = plan.steps[i];
+        const int row[7] = {t.path, t.sc, t.res, t.store, t.C3, t.rev, t.rev_b}, one[3] = {t.one_launch, t.one_C3, t.one_rev};
+        if (steps_out) memcpy(steps_out + 7 * i, row, sizeof(row));
+        memcpy(one_out + 3 * i, one, sizeof(one));
+    }
+    return n;
 }
 // plan_transformer (opd_model.cpp) for arch7 = d_model, heads, ffn, encoder layers, decoder layers, queries, classifier rows in a handle of
 // max_batch frames of at most max_height x max_width with `flags`, for a call of B frames of H x W; the switches as opd_detr_create reads

@@ -1,7 +1,9 @@
 """Times the fused bottleneck tail against the three launches it replaces, at the batch-8 800x1333 trunk shapes.
 Run on the GPU box:  python tools/bench_btail.py
 --res-path: instead, the residual by LDS-DMA (default) against register loads (dbg bit 16) for the stage-2 tail shapes and one 64-channel
-shape, four interleaved rounds in one process."""
+shape, four interleaved rounds in one process.
+--sc2: instead, stage 2's first block with the stride-2 shortcut inside the tail against the 3x3, the dual-source expand and the next reduce
+it replaces, four interleaved rounds in one process; each figure is the minimum over the rounds."""
 import ctypes as C
 import os
 import sys
@@ -31,6 +33,19 @@ if "--res-path" in sys.argv:
                 t[dbg].append(us[0])
         f = lambda v: " ".join("%7.1f" % x for x in v)
         print(f"{str(s):>28s}  LDS-DMA: {f(t[0])}  registers: {f(t[16])}  min {min(t[0]):.1f} / {min(t[16]):.1f} us = {min(t[0]) / min(t[16]):.4f}", flush=True)
+    sys.exit(0)
+if "--sc2" in sys.argv:
+    for B, H, W, C3 in [(8, 200, 334, 128), (8, 200, 334, 0)]:
+        rounds = []
+        for _ in range(4):
+            us = (C.c_float * 4)()
+            _capi.check(lib.opd_test_bench_btail_sc2(B, H, W, C3, 0, 20, us), "bench_btail_sc2")
+            rounds.append(list(us))
+        best = [min(r[k] for r in rounds) for k in range(4)]
+        chain = best[1] + best[2] + (best[3] if C3 else 0.0)
+        print(f"{str((B, H, W, 128, C3, 2)):>28s}  fused {best[0]:7.1f} us   3x3 {best[1]:6.1f} + dual expand {best[2]:6.1f}" +
+              (f" + reduce {best[3]:6.1f}" if C3 else "") + f" = {chain:7.1f} us   ratio {best[0] / chain:.3f}   fused per round: " +
+              " ".join("%.1f" % r[0] for r in rounds), flush=True)
     sys.exit(0)
 if "--s3" in sys.argv:
     SHAPES = SHAPES[-3:]

@@ -30,6 +30,7 @@ def main():
         path = ensure_weight_file(cache, DetrArch(depths=depths), 0, 1.0, name)
         rows = []
         for label, env, calls in (("default", {}, ()),
+                                  ("stage-2 first block as three launches", {"OPD_SC2_TAIL": "0"}, ()),
                                   ("stage-2 first block through the fused tail", {"OPD_DUAL_OVER_TAIL": "0"}, ()),
                                   ("shortcut fusions off", {}, (("opd_test_set_fuse_btail", 1),)),
                                   ("tails + shortcut fusions off", {}, (("opd_test_set_fuse_btail", 0),)),

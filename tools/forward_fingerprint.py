@@ -147,7 +147,7 @@ def main(out_path):
         for v in values:
             configs[f"{hook}({v})"] = {"hook": (hook, v)}
     for env in ({"OPD_TAIL3": "2"}, {"OPD_ENC_TAIL": "1"}, {"OPD_ENC_FRONT": "0"}, {"OPD_FUSED_ENC_FFN": "0"}, {"OPD_DEEP_FC2": "0"}, {"OPD_HEADS2": "0"},
-                {"OPD_W8": "7"}, {"OPD_DUAL_OVER_TAIL": "0"}, {"OPD_TAIL_RC": "0", "OPD_Y_STRIDE2": "0"}, {"OPD_FUSED_DEC": "0"}):
+                {"OPD_W8": "7"}, {"OPD_DUAL_OVER_TAIL": "0"}, {"OPD_SC2_TAIL": "0"}, {"OPD_TAIL_RC": "0", "OPD_Y_STRIDE2": "0"}, {"OPD_FUSED_DEC": "0"}):
         configs[" ".join(f"{k}={v}" for k, v in env.items())] = {"env": env}
     configs["OPD_TAIL3=2 multi_stream"] = {"env": {"OPD_TAIL3": "2"}, "flags": _capi.OPD_FLAG_MULTI_STREAM}
     configs["f32_pixels"] = {"f32": True}
