@@ -640,6 +640,35 @@ OPD_API int opd_detr_detect_frames_track(opd_detr* m, opd_reid* r, opd_track* co
 OPD_API int opd_detr_detect_sequence_track(opd_detr* m, opd_reid* r, opd_track* t, const uint8_t* const* frames, int B, int h, int w, int H, int W,
                                            float threshold, int label, int feature_kind, int slots, opd_det* out, int32_t* counts,
                                            int32_t* track_ids, int32_t* n_featured, int32_t* frames_done);
+/* opd_detr_detect_tiled with the colour-feature, floor and track stages on the MERGED records, all on the detector's stream in front of the call's
+ * ONE host wait (DESIGN.md sections 7a, 7k): what detect_tiled + opd_color_features + opd_floor_transform + opd_track_update give in four calls.
+ * With S = n_tiles x num_queries, the feature, floor and track-id row of merged record k of frame f is row f x S + k -- by POSITION, since two
+ * tiles of a frame use the same query numbers; rows at or behind counts[f] are unspecified.  Arithmetic, operation for operation that of the
+ * separate calls: a box is x, y, w, h each rounded from float64 to float32 ONCE; the colour crop is cut from the whole frame f with those four
+ * floats (widened back; the width is not re-derived); the floor foot point is taken from the rounded box; the tracker's foot point is
+ * (x + w / 2, y + h) in float64 from the UNROUNDED doubles, then rounded to float32; the confidence is the record's score.
+ *   feature_kind  OPD_TRACK_FEAT_NONE or OPD_TRACK_FEAT_COLOR (256 numbers per row)
+ *   features      NULL, or host [n_frames][S][256]: the rows to the caller (with trackers and NULL here no row leaves the device)
+ *   floor         NULL, or a floor-map handle; floor_out host [n_frames][S]
+ *   trackers      NULL, or [n_frames] distinct handles, frame f into trackers[f]; track_ids host [n_frames][S] (-1 where opd_track_update writes
+ *                 -1), n_featured host [n_frames]: counts[f] with COLOR, 0 with NONE.  A tracker out of slots: as opd_detr_detect_frames_track.
+ * OPD_EINVAL before any device call, besides everything opd_detr_detect_tiled refuses: NULL `stages` or a wrong struct_size; another
+ * feature_kind (a box merged from two tiles' maps has no encoder row; Re-ID is a call of its own); `features` with FEAT_NONE; COLOR on a frame
+ * with a side above 4096 or a handle with d_model != 256; floor_out NULL with `floor`, a floor map on another device; track_ids or n_featured
+ * NULL with `trackers`; a NULL tracker, one on another device, one named twice, one with max_dets < S, one with feature_dim != 256 under COLOR. */
+typedef struct opd_tile_stages {
+    int32_t struct_size;  /* = sizeof of this struct */
+    int32_t feature_kind;
+    float* features;
+    opd_floor* floor;
+    opd_floor_rec* floor_out;
+    opd_track* const* trackers;
+    int32_t* track_ids;
+    int32_t* n_featured;
+} opd_tile_stages;
+OPD_API int opd_detr_detect_tiled_stages(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw,
+                                         int n_tiles, int H, int W, float threshold, const opd_tile_params* p, const opd_tile_stages* stages,
+                                         opd_tile_det* out, int32_t* counts);
 /* The solver of the association on its own (host only): cost [rows][cols] row-major -> row_to_col [rows], -1 for a row left alone;
  * min(rows, cols) pairs of smallest total cost, as scipy.optimize.linear_sum_assignment. */
 OPD_API int opd_assign(const double* cost, int rows, int cols, int32_t* row_to_col);

@@ -79,6 +79,11 @@ class OpdFlowConfig(C.Structure):   # opd_flow_config (zeros = the defaults of c
                 ("max_iter", C.c_int), ("epsilon", C.c_float), ("min_eig_threshold", C.c_float)]
 
 
+class OpdTileStages(C.Structure):   # opd_tile_stages (56 bytes): the feature, floor and track stages of opd_detr_detect_tiled_stages
+    _fields_ = [("struct_size", C.c_int32), ("feature_kind", C.c_int32), ("features", C.c_void_p), ("floor", C.c_void_p), ("floor_out", C.c_void_p),
+                ("trackers", C.c_void_p), ("track_ids", C.c_void_p), ("n_featured", C.c_void_p)]
+
+
 class OpdFloorConfig(C.Structure):   # opd_floor_config: everything is copied at creation
     _fields_ = [("method", C.c_int32), ("n_points", C.c_int32), ("n_triangles", C.c_int32), ("n_zones", C.c_int32), ("has_distortion", C.c_int32),
                 ("allow_overlap", C.c_int32), ("width_px", C.c_int32), ("height_px", C.c_int32), ("H", C.c_double * 9),
@@ -163,6 +168,8 @@ API = {
     # frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, params, out, counts
     "opd_detr_detect_tiled": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                         C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
+    "opd_detr_detect_tiled_stages": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                               C.POINTER(OpdTileParams), C.POINTER(OpdTileStages), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
     # recs, tile_counts, n_frames, n_tiles, stride, tiles_yxhw, h, w, params, out, counts
     "opd_detr_merge_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
@@ -346,6 +353,10 @@ TEST_API = {
     "opd_test_tile_merge_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                            C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
     "opd_test_tile_resize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # stage kernels of a tiled call on merged records of the caller (csrc/opd_tile_stages_test_api.cpp): device, frames, n_frames, h, w, merged, counts, S,
+    # floor, with_rows, color, floor_out, boxes, foot, has, feat, n_out
+    "opd_test_tile_stages": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # optical-flow hook (csrc/opd_flow_test_api.cpp)
     "opd_flow_test_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     # floor-map hook (csrc/opd_floor_test_api.cpp)

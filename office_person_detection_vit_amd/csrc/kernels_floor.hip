@@ -68,6 +68,14 @@ __global__ __launch_bounds__(64) void floor_kernel(const FloorParams p) {
         x = (double)r.x1 + (double)bw / 2.0;
         y = (double)r.y1 + (double)bh;
         row = f * p.Q + r.query_index;
+    } else if (p.mode == FLOOR_IN_MERGED) {
+        const int f = idx / p.Q, i = idx - f * p.Q;
+        if (i >= p.counts[f]) return;
+        const opd_tile_det r = p.merged[idx];
+        // np.asarray(d.bbox, np.float32) of HipFloorMapper.transform_records, then the boxes mode above
+        const float bx = (float)r.x, by = (float)r.y, bw = (float)r.w, bh = (float)r.h;
+        x = (double)bx + (double)bw / 2.0;
+        y = (double)by + (double)bh;
     } else {
         x = p.pts[2 * (size_t)idx];
         y = p.pts[2 * (size_t)idx + 1];

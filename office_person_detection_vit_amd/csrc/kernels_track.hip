@@ -214,9 +214,20 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_commit_kernel(const Track
     }
 }
 
-// One workgroup of one wave per record slot of a frame.  A record is 32 bytes and a row at most 8 KB: the launch is bound by its latency, not by
-// bandwidth, so the geometry is many small workgroups that each finish in one round trip (64 lanes x 16 bytes = a 256-float row in one load each)
-// instead of few large ones that loop.  No LDS, no barrier: the slot search ends in a wave-wide maximum.
+// A feature row into the staging image: 64 lanes x 16 bytes = a 256-float row in one load each where both sides are 16-byte aligned
+__device__ __forceinline__ void ingest_row(const float* src, float* dst, int D, int lane) {
+    if ((D & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        float4* d4 = reinterpret_cast<float4*>(dst);
+        for (int d = lane; d < D / 4; d += TRACK_INGEST_THREADS) d4[d] = s4[d];
+    } else {
+        for (int d = lane; d < D; d += TRACK_INGEST_THREADS) dst[d] = src[d];
+    }
+}
+
+// One workgroup of one wave per record slot of a frame.  A record is 32 bytes (a merged one 48) and a row at most 8 KB: the launch is bound by its
+// latency, not by bandwidth, so the geometry is many small workgroups that each finish in one round trip instead of few large ones that loop.  No LDS,
+// no barrier: the slot search ends in a wave-wide maximum.
 __global__ __launch_bounds__(TRACK_INGEST_THREADS) void track_ingest_kernel(const TrackIngestParams p) {
     const int i = blockIdx.x, lane = threadIdx.x, D = p.D;
     if (p.hdr && p.hdr[TRACK_HDR_STOPPED] != 0) return;
@@ -224,6 +235,23 @@ __global__ __launch_bounds__(TRACK_INGEST_THREADS) void track_ingest_kernel(cons
     n = n < 0 ? 0 : (n > p.Q ? p.Q : n);
     if (i == 0 && lane == 0) *p.n_out = n;
     if (i >= n) return;   // (the whole workgroup)
+    if (p.merged) {   // a tiled call: the frame's merged records in frame pixels (float64), feature rows by position
+        const opd_tile_det g = p.merged[i];
+        const float* row = p.rows_kind == TRACK_ROWS_BY_POSITION ? p.rows + ((size_t)p.frame * p.Q + i) * D : nullptr;
+        if (lane == 0) {
+            // the box as HipTracker.update's float32 array takes det.bbox, each double rounded once; the foot point as detect_tiled fills camera_coords, in
+            // float64 from the unrounded doubles, rounded where update stores it (not the foot point of the rounded box)
+            p.boxes[4 * i] = (float)g.x;
+            p.boxes[4 * i + 1] = (float)g.y;
+            p.boxes[4 * i + 2] = (float)g.w;
+            p.boxes[4 * i + 3] = (float)g.h;
+            p.foot[2 * i] = (float)(g.x + g.w / 2);
+            p.foot[2 * i + 1] = (float)(g.y + g.h);
+            p.has[i] = row != nullptr;
+        }
+        if (row) ingest_row(row, p.feat + (size_t)i * D, D, lane);
+        return;
+    }
     const opd_det r = p.records[i];
     const float* src = nullptr;
     if (p.rows_kind == TRACK_ROWS_BY_QUERY) {
@@ -253,15 +281,7 @@ __global__ __launch_bounds__(TRACK_INGEST_THREADS) void track_ingest_kernel(cons
         p.foot[2 * i + 1] = (float)((double)r.y1 + bh);
         p.has[i] = src != nullptr;
     }
-    if (src == nullptr) return;
-    float* dst = p.feat + (size_t)i * D;
-    if ((D & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-        const float4* s4 = reinterpret_cast<const float4*>(src);
-        float4* d4 = reinterpret_cast<float4*>(dst);
-        for (int d = lane; d < D / 4; d += TRACK_INGEST_THREADS) d4[d] = s4[d];
-    } else {
-        for (int d = lane; d < D; d += TRACK_INGEST_THREADS) dst[d] = src[d];
-    }
+    if (src != nullptr) ingest_row(src, p.feat + (size_t)i * D, D, lane);
 }
 
 // ---- the association on the device (sequence calls) -------------------------------------------------------------------------------------------
@@ -616,8 +636,10 @@ hipError_t opd_launch_track_assoc(const TrackAssocParams& p, hipStream_t stream)
 
 hipError_t opd_launch_track_ingest(const TrackIngestParams& p, hipStream_t stream) {
     if (p.Q < 1 || p.Q > TRACK_MAX_DETS || p.D < 1 || p.D > TRACK_MAX_DIM || p.frame < 0 || p.slots < 0) return hipErrorInvalidValue;
-    if (p.rows_kind != TRACK_ROWS_NONE && p.rows_kind != TRACK_ROWS_BY_QUERY && p.rows_kind != TRACK_ROWS_BY_SLOT) return hipErrorInvalidValue;
-    if (!p.records || !p.count || !p.boxes || !p.foot || !p.has || !p.n_out) return hipErrorInvalidValue;
+    if (p.rows_kind != TRACK_ROWS_NONE && p.rows_kind != TRACK_ROWS_BY_QUERY && p.rows_kind != TRACK_ROWS_BY_SLOT && p.rows_kind != TRACK_ROWS_BY_POSITION) return hipErrorInvalidValue;
+    // (merged records carry no usable query index: their rows go by position, and only theirs)
+    if (p.merged ? (p.rows_kind != TRACK_ROWS_NONE && p.rows_kind != TRACK_ROWS_BY_POSITION) : (p.rows_kind == TRACK_ROWS_BY_POSITION || !p.records)) return hipErrorInvalidValue;
+    if (!p.count || !p.boxes || !p.foot || !p.has || !p.n_out) return hipErrorInvalidValue;
     if (p.rows_kind != TRACK_ROWS_NONE && (!p.rows || !p.feat)) return hipErrorInvalidValue;
     if (p.rows_kind == TRACK_ROWS_BY_SLOT && (!p.slot_map || !p.n_person)) return hipErrorInvalidValue;
     OPD_LAUNCH(track_ingest_kernel, dim3(p.Q), dim3(TRACK_INGEST_THREADS), 0, stream, p);

@@ -125,8 +125,9 @@ static int stage_frames(opd_detr* m, const FrameSource& src, int B, int H, int W
     if (src.kind == SRC_PIXELS) return stage_pixels(m, src.frames, src.pixel_format, src.mem_kind, B, H, W, d_pixels);
     *d_pixels = *d_camera = m->d_u8;
     if (src.kind == SRC_TILES) {
-        *d_camera = m->src.dev;   // (whole frames)
-        return enqueue_tiles(m, src, H, W);
+        RCCHK(enqueue_tiles(m, src, H, W));
+        *d_camera = m->src.dev;   // (whole frames; read AFTER the upload, which is what allocates or grows the staging buffer)
+        return OPD_OK;
     }
     const uint8_t* block = src.kind == SRC_BLOCK ? static_cast<const uint8_t*>(src.frames) : nullptr;
     const uint8_t* const* list = src.kind == SRC_LIST ? static_cast<const uint8_t* const*>(src.frames) : nullptr;
@@ -158,6 +159,9 @@ static int ensure_nms_flag(opd_detr* m) {
 // The merged records of a tiled call lie as [counts of max_batch frames | records]
 static size_t tile_out_off(const opd_detr* m) { return align_up((size_t)m->cfg.max_batch * 4, 64); }   // where the records begin
 static int ensure_tile_out(opd_detr* m) { return ensure(m, &m->d_tile_out, tile_out_off(m) + slots_of(m) * sizeof(opd_tile_det), &m->tile_pinned); }
+// ... and are what the feature, floor and track stages of a tiled call read, where tile_merge_kernel left them: [n_frames][S], S = n_tiles x queries, rows by position
+static const int32_t* merged_counts(const opd_detr* m) { return reinterpret_cast<const int32_t*>(m->d_tile_out); }
+static const opd_tile_det* merged_records(const opd_detr* m) { return reinterpret_cast<const opd_tile_det*>(m->d_tile_out + tile_out_off(m)); }
 // The records leave the device as ONE block, the d_records allocation as it lies: [records of max_batch frames | counts | feature rows]
 static size_t rec_bytes(const opd_detr* m) { return slots_of(m) * sizeof(opd_det); }   // = offset of the counts
 static size_t feat_off(const opd_detr* m) { return reinterpret_cast<const char*>(m->d_feat_all) - reinterpret_cast<const char*>(m->d_records); }
@@ -223,6 +227,15 @@ static int enqueue_features(opd_detr* m, const RecordSink& s, int h, int w, cons
     const FeatureStage& f = s.feature;
     *rows = TrackFeatureSource{};
     if (f.kind == FEAT_NONE) return OPD_OK;
+    if (s.tile.params) {   // a tiled call (FEAT_COLOR, the entry's check): crops of the merged records, cut from the WHOLE frames at d_camera; a row per position
+        RCCHK(ensure(m, &m->d_color_acc, slots_of(m) * OPD_COLOR_ACC_WORDS));
+        ColorParams cp{};
+        cp.merged = merged_records(m); cp.counts = merged_counts(m); cp.frames = d_camera; cp.acc = m->d_color_acc; cp.out = m->d_feat_all;
+        cp.Q = s.tile.n_tiles * Q; cp.fh = h; cp.fw = w; cp.label = s.label; cp.n = B * Q;
+        HIPCHK(opd_launch_color_features(cp, std::min(64, (h + 15) / 16), m->stream));
+        *rows = {TRACK_ROWS_BY_POSITION, OPD_COLOR_DIM, m->d_feat_all, nullptr, nullptr, 0};
+        return OPD_OK;
+    }
     if (f.kind == FEAT_REID) {   // select, plan and the Re-ID forward behind the post-process; the rows come back behind the records, before the one wait
         reid->emplace(f.reid);
         RCCHK((*reid)->enqueue(m->stream, m->d_records, m->d_counts, d_camera, B, Q, h, w, s.label, f.slots));
@@ -249,6 +262,9 @@ static int enqueue_floor(opd_detr* m, const RecordSink& s) {
     FloorParams fp{};
     fp.m = s.floor.fmap->model; fp.mode = FLOOR_IN_RECORDS; fp.n = m->last_B * m->arch.queries;
     fp.records = m->d_records; fp.counts = m->d_counts; fp.Q = m->arch.queries; fp.label = s.label; fp.out = m->d_floor;
+    if (s.tile.params) {   // a tiled call: the merged records, a row per position
+        fp.mode = FLOOR_IN_MERGED; fp.merged = merged_records(m); fp.counts = merged_counts(m); fp.Q = s.tile.n_tiles * m->arch.queries;
+    }
     HIPCHK(opd_launch_floor(fp, m->stream));
     return OPD_OK;
 }
@@ -256,8 +272,15 @@ static int enqueue_floor(opd_detr* m, const RecordSink& s) {
 // The tracker half of a fused detect-and-track call (opd_track.h), around the one wait of fetch_records.  Before it: every tracker's ingest and
 // predict / cost launches on m->stream, behind the feature stage.  After it: association and commit per tracker; a tracker out of slots does not
 // keep the others from being committed, and its error is the call's.
-static int enqueue_trackers(opd_detr* m, const TrackStage& t, const TrackFeatureSource& src) {
+static int enqueue_trackers(opd_detr* m, const RecordSink& s, const TrackFeatureSource& src) {
     const int B = m->last_B, Q = m->arch.queries;
+    const TrackStage& t = s.track;
+    if (s.tile.params) {   // a tiled call: a tracker per FRAME, on its merged records
+        const int S = s.tile.n_tiles * Q;
+        for (int f = 0; f < s.tile.n_frames; ++f)
+            RCCHK(track_fused_enqueue(t.trackers[f], m->stream, nullptr, merged_counts(m) + f, S, f, src, merged_records(m) + (size_t)f * S));
+        return OPD_OK;
+    }
     if (t.seq) return track_sequence_enqueue(t.seq, m->stream, m->d_records, m->d_counts, Q, B, src, "opd_detr_detect_sequence_track");
     for (int b = 0; b < B; ++b) RCCHK(track_fused_enqueue(t.trackers[b], m->stream, m->d_records + (size_t)b * Q, m->d_counts + b, Q, b, src));
     return OPD_OK;
@@ -268,9 +291,15 @@ static int finish_trackers(opd_detr* m, const RecordSink& s, bool with_features)
     if (t.seq) return track_sequence_finish(t.seq, s.counts, Q, B, t.track_ids, t.frames_done, "opd_detr_detect_sequence_track");
     int rc = OPD_OK;
     std::string first;
-    for (int b = 0; b < B; ++b) {
-        const int n = std::max(0, std::min(s.counts[b], Q));
-        const int one = track_fused_finish(t.trackers[b], s.out + (size_t)b * Q, n, with_features, t.track_ids + (size_t)b * Q, "opd_detr_detect_frames_track");
+    // the confidences of the records the call delivered: per frame [Q] opd_det, or (a tiled call) [S] merged records
+    const bool tiled = s.tile.params != nullptr;
+    const int frames = tiled ? s.tile.n_frames : B, stride = tiled ? s.tile.n_tiles * Q : Q;
+    const int32_t* counts = tiled ? s.tile.counts : s.counts;
+    for (int b = 0; b < frames; ++b) {
+        const int n = std::max(0, std::min(counts[b], stride));
+        const float* conf = tiled ? &s.tile.out[(size_t)b * stride].score : &s.out[(size_t)b * stride].score;
+        const int one = track_fused_finish(t.trackers[b], conf, (int)((tiled ? sizeof(opd_tile_det) : sizeof(opd_det)) / sizeof(float)), n, with_features,
+                                           t.track_ids + (size_t)b * stride, tiled ? "opd_detr_detect_tiled_stages" : "opd_detr_detect_frames_track");
         if (one != OPD_OK && rc == OPD_OK) { rc = one; first = g_err; }
     }
     return rc == OPD_OK ? OPD_OK : fail(rc, first);
@@ -287,13 +316,19 @@ static void unpack_records(const opd_detr* m, const void* pinned, int B, opd_det
 static float* query_rows_out(const RecordSink& s) { return s.feature.kind == FEAT_REID ? nullptr : s.feature.features; }
 
 // The one fetch of a blocking call: what the sink's parts ask for comes back into page-locked memory (a copy into the caller's pageable arrays is staged by
-// the runtime anyway, once per call), then the call's ONE wait.  A tiled call: [counts | merged records] alone.  Host outputs: [records of max_batch frames |
+// the runtime anyway, once per call), then the call's ONE wait.  A tiled call: [counts | merged records], and of its stages the rows by position (unless
+// a tracker alone reads them) and the floor rows.  Host outputs: [records of max_batch frames |
 // counts (| per-query feature rows)] in one copy, the floor rows, the Re-ID call's slot list (and rows, unless a tracker reads them in place).  Device
 // outputs were written in place by the post-process kernel.
 static int fetch_records(opd_detr* m, const RecordSink& s, ReidFusedCall* reid) {
     const int B = m->last_B, Q = m->arch.queries;
     if (s.tile.params) {
         HIPCHK(hipMemcpyAsync(m->tile_pinned, m->d_tile_out, tile_out_off(m) + (size_t)B * Q * sizeof(opd_tile_det), hipMemcpyDeviceToHost, m->stream));
+        if (query_rows_out(s)) {   // the rows by position, where the per-query rows of a frame-list call travel
+            RCCHK(ensure_sync_pinned(m));
+            HIPCHK(hipMemcpyAsync(static_cast<char*>(m->sync_pinned) + feat_off(m), m->d_feat_all, B * feat_row(m), hipMemcpyDeviceToHost, m->stream));
+        }
+        if (s.floor.fmap) HIPCHK(hipMemcpyAsync(m->h_floor, m->d_floor, (size_t)B * Q * sizeof(opd_floor_rec), hipMemcpyDeviceToHost, m->stream));
     } else if (!outputs_on_device(s.mem_kind)) {
         RCCHK(ensure_sync_pinned(m));
         HIPCHK(hipMemcpyAsync(m->sync_pinned, m->d_records, query_rows_out(s) ? feat_off(m) + B * feat_row(m) : rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
@@ -332,6 +367,7 @@ static int hand_to_ticket(opd_detr* m, const RecordSink& s) {
 
 // The back half, on the outputs of the last forward (opd_detr_postprocess enters here): the stages of the sink in their one order, each skipped when its
 // part is absent.  (h, w): the size the boxes are scaled to (0: the model resolution); d_camera: the source's frames on the device at camera resolution.
+// In a tiled call the feature, floor and track stages read the MERGED records (rows by position), not d_records.
 // The feature, floor, track and tile parts deliver to the host after the call's own wait: setting one with WAIT_TICKET or WAIT_NONE, or with device
 // outputs, is a programming error (no entry point does).
 static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera) {
@@ -344,7 +380,7 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
     TrackFeatureSource rows;
     RCCHK(enqueue_features(m, s, tiled ? s.tile.frame_h : h, tiled ? s.tile.frame_w : w, d_camera, &reid, &rows));
     if (s.floor.fmap) RCCHK(enqueue_floor(m, s));
-    if (tracked) RCCHK(enqueue_trackers(m, s.track, rows));
+    if (tracked) RCCHK(enqueue_trackers(m, s, rows));
     if (s.wait == WAIT_NONE) return OPD_OK;
     if (s.wait == WAIT_TICKET) return hand_to_ticket(m, s);
     RCCHK(fetch_records(m, s, reid ? &*reid : nullptr));
@@ -352,6 +388,14 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
     if (tiled) {
         memcpy(s.tile.counts, m->tile_pinned, (size_t)s.tile.n_frames * 4);
         memcpy(s.tile.out, static_cast<const char*>(m->tile_pinned) + tile_out_off(m), (size_t)B * Q * sizeof(opd_tile_det));
+        const int S = s.tile.n_tiles * Q;   // the stages' rows of a tiled call go by position: row f * S + k of merged record k of frame f
+        if (query_rows_out(s)) memcpy(query_rows_out(s), static_cast<const char*>(m->sync_pinned) + feat_off(m), B * feat_row(m));
+        for (int f = 0; f < s.tile.n_frames; ++f) {
+            const int n = std::max(0, std::min(s.tile.counts[f], S));
+            if (s.floor.fmap) memcpy(s.floor.out + (size_t)f * S, m->h_floor + (size_t)f * S, (size_t)n * sizeof(opd_floor_rec));
+            if (tracked) s.track.n_featured[f] = rows.rows_kind == TRACK_ROWS_NONE ? 0 : n;
+        }
+        return tracked ? finish_trackers(m, s, rows.rows_kind != TRACK_ROWS_NONE) : OPD_OK;
     } else if (!dev) unpack_records(m, m->sync_pinned, B, s.out, s.counts, query_rows_out(s));
     if (reid && !tracked) reid->deliver(s.feature.features, s.feature.slot_map, s.feature.n_person);
     if (s.floor.fmap)   // only rows of records of the class are handed on
@@ -642,28 +686,73 @@ int opd_detr_nms_records(opd_detr* m, opd_det* dets, int32_t* counts, int n_fram
     }
     return OPD_OK;
 }); }
-// Tiled detection: every refusal comes before the first device call (check_tiles; check_shape makes none for host pixels)
-int opd_detr_detect_tiled(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W, float threshold,
-                          const opd_tile_params* p, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled", [&]() -> int {
-    if (!frames || !out || !counts) return fail(OPD_EINVAL, "opd_detr_detect_tiled: null argument");
-    RCCHK(check_tiles("opd_detr_detect_tiled", p, tiles_yxhw, n_tiles, h, w, true));
-    if (!(p->tile_nms_threshold >= 0.f)) return fail(OPD_EINVAL, "opd_detr_detect_tiled: tile_nms_threshold is negative or NaN");
+// Tiled detection: every refusal comes before the first device call (check_tiles; check_shape makes none for host pixels).  `st` (null: opd_detr_detect_tiled
+// itself): the feature, floor and track parts of the sink, which then read the merged records where the merge left them, rows by position
+static int detect_tiled(const std::string& me, opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W,
+                        float threshold, const opd_tile_params* p, const opd_tile_stages* st, opd_tile_det* out, int32_t* counts) {
+    if (!frames || !out || !counts) return fail(OPD_EINVAL, me + ": null argument");
+    const bool color = st && st->feature_kind == OPD_TRACK_FEAT_COLOR;
+    if (st) {   // what needs neither the handle nor the windows
+        if (st->struct_size != (int32_t)sizeof(opd_tile_stages)) return fail(OPD_EINVAL, me + ": opd_tile_stages.struct_size mismatch");
+        if (st->feature_kind != OPD_TRACK_FEAT_NONE && !color)
+            return fail(OPD_EINVAL, me + ": feature_kind " + std::to_string(st->feature_kind) + "; a tiled call takes OPD_TRACK_FEAT_NONE or OPD_TRACK_FEAT_COLOR (a box merged from two "
+                                         "tiles' maps has no encoder row, and Re-ID is a call of its own)");
+        if (st->features && !color) return fail(OPD_EINVAL, me + ": features given with feature_kind OPD_TRACK_FEAT_NONE");
+        if (st->floor && !st->floor_out) return fail(OPD_EINVAL, me + ": floor_out is null while a floor-map handle is given");
+        if (st->trackers && (!st->track_ids || !st->n_featured)) return fail(OPD_EINVAL, me + ": track_ids or n_featured is null while trackers are given");
+    }
+    RCCHK(check_tiles(me, p, tiles_yxhw, n_tiles, h, w, true));
+    if (!(p->tile_nms_threshold >= 0.f)) return fail(OPD_EINVAL, me + ": tile_nms_threshold is negative or NaN");
+    if (color && (h > OPD_COLOR_MAX_EDGE || w > OPD_COLOR_MAX_EDGE))
+        return fail(OPD_EINVAL, me + ": feature_kind OPD_TRACK_FEAT_COLOR on frames of " + std::to_string(h) + " x " + std::to_string(w) +
+                                     ", outside the 4096 x 4096 the exact integer sums of the colour histogram are sized for");
     if (!m) return fail(OPD_EINVAL, "null model handle");
     if ((long long)n_tiles * m->arch.queries > OPD_TILE_MAX_CAND)
-        return fail(OPD_EINVAL, "opd_detr_detect_tiled: " + std::to_string(n_tiles) + " tiles x " + std::to_string(m->arch.queries) + " queries exceed the 1024 candidates a frame's merge holds");
+        return fail(OPD_EINVAL, me + ": " + std::to_string(n_tiles) + " tiles x " + std::to_string(m->arch.queries) + " queries exceed the 1024 candidates a frame's merge holds");
     if (n_frames < 1 || (long long)n_frames * n_tiles > m->cfg.max_batch)
-        return fail(OPD_EINVAL, "opd_detr_detect_tiled: " + std::to_string(n_frames) + " frames x " + std::to_string(n_tiles) + " tiles outside [1, max_batch = " +
-                                    std::to_string(m->cfg.max_batch) + "]");
+        return fail(OPD_EINVAL, me + ": " + std::to_string(n_frames) + " frames x " + std::to_string(n_tiles) + " tiles outside [1, max_batch = " + std::to_string(m->cfg.max_batch) + "]");
     for (int f = 0; f < n_frames; ++f)
-        if (!frames[f]) return fail(OPD_EINVAL, "opd_detr_detect_tiled: null frame pointer");
+        if (!frames[f]) return fail(OPD_EINVAL, me + ": null frame pointer");
     RCCHK(check_shape(m, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, n_frames * n_tiles, H, W));
-    HIPCHK(hipSetDevice(m->device));
     FrameSource src{SRC_TILES, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w};
     src.n_frames = n_frames; src.n_tiles = n_tiles; src.tiles = tiles_yxhw;
     RecordSink sink(threshold, nullptr, nullptr, nullptr, OPD_MEM_HOST);   // (boxes in TILE pixels; the merge puts them on the frame)
     sink.tile.params = p; sink.tile.n_frames = n_frames; sink.tile.n_tiles = n_tiles; sink.tile.frame_h = h; sink.tile.frame_w = w;
     sink.tile.out = out; sink.tile.counts = counts;
+    if (st) {   // the stages' own refusals that need the handle, then their parts of the sink
+        const int S = n_tiles * m->arch.queries;
+        if (color && m->arch.d_model != OPD_COLOR_DIM) return fail(OPD_EINVAL, me + ": feature_kind OPD_TRACK_FEAT_COLOR: the feature area of the handle is sized for d_model = 256");
+        if (st->floor && st->floor->device != m->device)
+            return fail(OPD_EINVAL, me + ": the detector is on device " + std::to_string(m->device) + ", the floor map `floor` on device " + std::to_string(st->floor->device));
+        for (int f = 0; st->trackers && f < n_frames; ++f) {
+            const opd_track* t = st->trackers[f];
+            const std::string who = me + ": trackers[" + std::to_string(f) + "] ";
+            if (!t) return fail(OPD_EINVAL, who + "is null");
+            if (t->device != m->device) return fail(OPD_EINVAL, who + "is on device " + std::to_string(t->device) + ", the detector on device " + std::to_string(m->device));
+            if (t->NM < S)
+                return fail(OPD_EINVAL, who + "was made for max_dets = " + std::to_string(t->NM) + ", a tiled frame can keep n_tiles x num_queries = " + std::to_string(S) + " records");
+            if (color && t->D != OPD_COLOR_DIM)
+                return fail(OPD_EINVAL, who + "was made for feature_dim = " + std::to_string(t->D) + ", the rows of feature_kind OPD_TRACK_FEAT_COLOR have 256 numbers");
+            for (int a = 0; a < f; ++a)
+                if (st->trackers[a] == t) return fail(OPD_EINVAL, who + "is trackers[" + std::to_string(a) + "] too; a tracker takes one frame per call");
+        }
+        sink.label = p->person_label;
+        sink.feature.kind = color ? FEAT_COLOR : FEAT_NONE; sink.feature.features = st->features;
+        sink.floor.fmap = st->floor; sink.floor.out = st->floor_out;
+        sink.track.trackers = st->trackers; sink.track.track_ids = st->track_ids; sink.track.n_featured = st->n_featured;
+    }
+    HIPCHK(hipSetDevice(m->device));
     return detect_pipeline(m, src, n_frames * n_tiles, H, W, nullptr, sink);
+}
+int opd_detr_detect_tiled(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W, float threshold,
+                          const opd_tile_params* p, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled", [&]() -> int {
+    return detect_tiled("opd_detr_detect_tiled", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, nullptr, out, counts);
+}); }
+// ... with the feature, floor and track stages on the merged records, in front of the same one wait
+int opd_detr_detect_tiled_stages(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W, float threshold,
+                                 const opd_tile_params* p, const opd_tile_stages* stages, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled_stages", [&]() -> int {
+    if (!stages) return fail(OPD_EINVAL, "opd_detr_detect_tiled_stages: null argument (stages)");
+    return detect_tiled("opd_detr_detect_tiled_stages", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, stages, out, counts);
 }); }
 int opd_detr_merge_tiles(opd_detr* m, const opd_det* recs, const int32_t* tile_counts, int n_frames, int n_tiles, int stride, const int32_t* tiles_yxhw, int h, int w,
                          const opd_tile_params* p, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_merge_tiles", [&]() -> int {

@@ -28,16 +28,18 @@ struct FloorModel {
     const int32_t* zone_rank;              // [n_zones]: position of the zone when sorted by (priority or +inf, index)
 };
 
-enum { FLOOR_IN_BOXES, FLOOR_IN_POINTS, FLOOR_IN_RECORDS, FLOOR_IN_FLOOR };   // what a wave starts from
+enum { FLOOR_IN_BOXES, FLOOR_IN_POINTS, FLOOR_IN_RECORDS, FLOOR_IN_FLOOR, FLOOR_IN_MERGED };   // what a wave starts from
 struct FloorParams {
     FloorModel m;
     int32_t mode, n;
     const float* boxes;        // FLOOR_IN_BOXES: [n][4] x, y, w, h
     const double* pts;         // FLOOR_IN_POINTS: [n][2] camera pixels.  FLOOR_IN_FLOOR: [n][2] floor pixels (zones only)
     const opd_det* records;    // FLOOR_IN_RECORDS: [n / Q][Q] records of the post-process, counts per frame; only those labelled `label`
+    const opd_tile_det* merged;   // FLOOR_IN_MERGED: [n / Q][Q] merged records of a tiled call (Q = n_tiles x queries), counts per frame; the box is
+                                  // x, y, w, h each rounded to float32 once, then the foot point of FLOOR_IN_BOXES
     const int32_t* counts;
     int32_t Q, label;
-    opd_floor_rec* out;        // [n]; FLOOR_IN_RECORDS: row frame * Q + query_index
+    opd_floor_rec* out;        // [n]; FLOOR_IN_RECORDS: row frame * Q + query_index.  FLOOR_IN_MERGED: row frame * Q + position
     uint64_t* masks;           // FLOOR_IN_FLOOR: [n]
 };
 

@@ -371,6 +371,9 @@ struct ColorParams {
     // box (x1, y1, float32(x2 - x1), float32(y2 - y1)) as the Python shim hands a Detection.bbox to opd_color_features; output row
     // b * Q + query_index; other rows are not written
     const void* records;      // opd_det [B][Q]
+    // merged mode (opd_detr_detect_tiled_stages; `merged` non-null, `records` unused): crop f * Q + k = merged record k of frame f when k < counts[f],
+    // Q = n_tiles x queries; box = its x, y, w, h each rounded to float32 once (np.asarray(d.bbox, np.float32)); output row f * Q + k, by POSITION
+    const void* merged;       // opd_tile_det [B][Q]
     const int32_t* counts;    // [B]
     const uint8_t* frames;    // [B][fh][fw][3]
     int Q, fh, fw, label;

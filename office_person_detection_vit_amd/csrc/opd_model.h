@@ -372,6 +372,8 @@ inline int dalloc(opd_detr* m, T** p, size_t count, bool weight) {
     (to_weights ? m->weights->allocs : m->allocs).push_back(q);   // (the base pointer: what hipFree takes)
     if (poison >= 0) {
         HIPCHK(hipMemset(q, poison, total));
+        HIPCHK(hipDeviceSynchronize());   // (the fill runs on the null stream and may return before it is done; the handle's streams do not wait for that one: a buffer
+                                          //  a stage allocates in the middle of a call would else be poisoned AFTER the stage's own memset or first launch)
         (to_weights ? m->weights->zoned : m->zoned).push_back({q, bytes ? bytes : 16, poison});
     }
     (weight ? m->weight_bytes : m->workspace_bytes) += (int64_t)bytes;

@@ -398,7 +398,8 @@ int track_fused_check(const opd_track* t, int device, int Q, int feature_dim, co
     return OPD_OK;
 }
 
-int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* count, int Q, int frame, const TrackFeatureSource& src) {
+int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* count, int Q, int frame, const TrackFeatureSource& src,
+                        const opd_tile_det* merged) {
     uint8_t* d = t->io.dev;
     t->last_launches = t->last_waits = 0;
     // behind whatever the handle's own stream still holds (the previous commit launch reads the staging image the ingest launch overwrites)
@@ -406,7 +407,7 @@ int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, con
     HIPCHK(hipStreamWaitEvent(s, t->ev_commit, 0));
     fill_slots(t);
     TrackIngestParams p{};
-    p.records = records; p.count = count;
+    p.records = records; p.merged = merged; p.count = count;
     p.Q = Q; p.D = t->D; p.frame = frame;
     p.rows_kind = src.rows_kind; p.rows = src.rows; p.slot_map = src.slot_map; p.n_person = src.n_person; p.slots = src.slots;
     p.boxes = reinterpret_cast<float*>(d + t->o_boxes);
@@ -419,9 +420,9 @@ int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, con
     return enqueue_predict(t, s, Q, src.rows_kind != TRACK_ROWS_NONE, p.n_out, true);
 }
 
-int track_fused_finish(opd_track* t, const opd_det* recs, int n, int with_features, int32_t* out_ids, const char* who) {
+int track_fused_finish(opd_track* t, const float* conf, int conf_stride, int n, int with_features, int32_t* out_ids, const char* who) {
     int M = 0;
-    const int rc = associate_update(t, n > 0 ? &recs[0].score : nullptr, (int)(sizeof(opd_det) / sizeof(float)), n, out_ids, who, &M);
+    const int rc = associate_update(t, n > 0 ? conf : nullptr, conf_stride, n, out_ids, who, &M);
     RCCHK(enqueue_commit(t, M, n, with_features != 0));
     return rc;
 }

@@ -56,13 +56,16 @@ struct TrackPredictParams {
 };
 
 // The ingest launch of the fused detect-and-track call: one frame's kept records, where the suppression kernel left them, -> the staging image
-enum { TRACK_ROWS_NONE = 0, TRACK_ROWS_BY_QUERY = 1, TRACK_ROWS_BY_SLOT = 2 };
+enum { TRACK_ROWS_NONE = 0, TRACK_ROWS_BY_QUERY = 1, TRACK_ROWS_BY_SLOT = 2, TRACK_ROWS_BY_POSITION = 3 };
 struct TrackIngestParams {
     const opd_det* records;    // [Q] records of the frame
+    const opd_tile_det* merged;   // non-null (a tiled call): the frame's [Q] MERGED records instead, Q = n_tiles x queries; `records` is not read.  Box: x, y, w, h
+                                  // each rounded to float32 once; foot point (x + w / 2, y + h) in float64 from the UNROUNDED doubles, then rounded
     const int32_t* count;      // its kept count
     int32_t Q, D, frame;
     int32_t rows_kind;         // TRACK_ROWS_*
-    const float* rows;         // BY_QUERY: [..][Q][D], row frame * Q + query_index.  BY_SLOT: [slots][D], row k of slot_map[k] = frame * Q + query_index
+    const float* rows;         // BY_QUERY: [..][Q][D], row frame * Q + query_index.  BY_SLOT: [slots][D], row k of slot_map[k] = frame * Q + query_index.
+                               // BY_POSITION (merged records only: two tiles of a frame use the same query numbers): [..][Q][D], row frame * Q + i of record i
     const int32_t* slot_map;   // BY_SLOT: [slots], of which min(*n_person, slots) are filled
     const int32_t* n_person;
     int32_t slots;
@@ -140,8 +143,11 @@ struct TrackFeatureSource {
     int slots = 0;
 };
 int track_fused_check(const opd_track* t, int device, int Q, int feature_dim, const char* who);
-int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* count, int Q, int frame, const TrackFeatureSource& src);
-int track_fused_finish(opd_track* t, const opd_det* recs, int n, int with_features, int32_t* out_ids, const char* who);
+// `merged` (non-null: a tiled call): the frame's merged records, read instead of `records`; Q is then n_tiles x queries.  `conf`: the confidence of
+// returned record i at conf[i * conf_stride] (floats): the score member of the opd_det or opd_tile_det records the call delivered
+int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* count, int Q, int frame, const TrackFeatureSource& src,
+                        const opd_tile_det* merged = nullptr);
+int track_fused_finish(opd_track* t, const float* conf, int conf_stride, int n, int with_features, int32_t* out_ids, const char* who);
 
 // The tracker half of opd_detr_detect_sequence_track: B consecutive frames of one camera into ONE tracker, in frame order.
 //   track_sequence_enqueue  on the detector's stream `s`, behind the feature stage: the table upload, then per frame ingest -> predict / cost ->

@@ -534,6 +534,126 @@ class HipDetrDetector:
             logger.error(f"Detection failed: {e}")
             raise
 
+    def detect_tiled_stages(self, frames: Sequence[np.ndarray], tiles: Sequence[Tuple[int, int, int, int]], nms_threshold: float = 0.4,
+                            merge_threshold: float = 0.5, edge_tolerance: float = 0.01, features: Optional[str] = None, floor_map=None,
+                            trackers=None) -> List[List[Detection]]:
+        """``detect_tiled`` with the stages behind it in the same call.  (A method of its own: ``detect_tiled`` keeps the parameter list it has.)
+        ``features="color"``, ``floor_map=`` (a ``HipFloorMapper``) and ``trackers=`` (one ``HipTracker`` per frame) run the stages of
+        ``extract_color_features``, ``floor_map.apply`` and ``tracker.update`` on the merged records INSIDE the call, behind the same one host
+        wait (``opd_detr_detect_tiled_stages``): ``det.features``, the four floor fields and ``track_id`` come back filled, with the bits the
+        separate calls give.  With trackers the colour rows enter them on the device and ``det.features`` stays ``None``, as in
+        ``detect_and_track``.  Where the fused conditions fail (a tracker or floor map on another GPU, ``max_dets`` below ``tiles x queries``, a
+        ``feature_dim`` other than 256 with colour features, a frame side above 4096 with colour features) the separate calls run one after the
+        other, with the same results.  With none of the three given this is ``detect_tiled`` itself."""
+        self._require_model()
+        frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
+        if features not in (None, "color"):
+            if features == "encoder":
+                raise ValueError("features='encoder' does not exist for tiled detection: a box merged from two tiles' maps has no encoder row")
+            raise ValueError(f"features must be None or 'color', got {features!r}")
+        if trackers is not None:
+            trackers = list(trackers)
+            if len(trackers) != len(frames):
+                raise ValueError(f"{len(trackers)} trackers for {len(frames)} frames: frame f enters trackers[f]")
+            if len({id(t) for t in trackers}) != len(trackers):
+                raise ValueError("a tracker is named twice: a tracker takes one frame per call")
+        if not tiles or any(len(t) != 4 for t in tiles):
+            raise ValueError("tiles must be a non-empty list of (y0, x0, h, w)")
+        if len(tiles) > self.max_batch:
+            raise ValueError(f"the {len(tiles)} tiles of one frame exceed max_batch = {self.max_batch}")
+        if len({(t[2], t[3]) for t in tiles}) != 1:
+            raise ValueError("tiles of more than one size: one forward has one model size")
+        if len(frames) == 0:
+            return []
+        f0 = frames[0]
+        for f in frames:
+            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != f0.shape or not f.flags.c_contiguous:
+                raise ValueError("frames must be contiguous uint8 numpy arrays of shape (H, W, 3) in BGR order, all of one size")
+        h, w = int(f0.shape[0]), int(f0.shape[1])
+        th, tw = tiles[0][2], tiles[0][3]
+        H, W = model_input_size(th, tw, self.max_size[0], self.max_size[1]) if self.resize else (th, tw)
+        T, Q = len(tiles), self._info.num_queries
+        S = T * Q
+        if features is None and floor_map is None and trackers is None:
+            return self.detect_tiled(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
+        if not self._tiled_stages_fused(h, w, S, features, floor_map, trackers):
+            out = self.detect_tiled(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
+            for b, dets in enumerate(out):
+                if features == "color":
+                    for det, row in zip(dets, self.extract_color_features(frames[b], dets)):
+                        det.features = row
+                if floor_map is not None:
+                    floor_map.apply(dets)
+                if trackers is not None:
+                    trackers[b].update(dets)
+            return out
+        win = np.asarray(tiles, dtype=np.int32).reshape(T, 4)
+        params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
+                                     merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
+        per = max(1, self.max_batch // T)
+        out: List[List[Detection]] = []
+        try:
+            for i in range(0, len(frames), per):
+                chunk = frames[i:i + per]
+                n = len(chunk)
+                recs, counts = (_capi.OpdTileDet * (n * S))(), (C.c_int32 * n)()
+                ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in chunk])
+                args = (C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, H, W, float(self.confidence_threshold), C.byref(params))
+                # the feature, floor and track stages on the merged records, rows by position: row b * S + k of record k of frame b
+                feats = floor = ids = None
+                st = _capi.OpdTileStages(struct_size=C.sizeof(_capi.OpdTileStages),
+                                         feature_kind=_capi.OPD_TRACK_FEAT_COLOR if features == "color" else _capi.OPD_TRACK_FEAT_NONE)
+                if features == "color" and trackers is None:
+                    feats = np.empty((n, S, 256), np.float32)
+                    st.features = feats.ctypes.data
+                if floor_map is not None:
+                    floor = np.zeros(n * S, floor_map.REC_DTYPE)
+                    st.floor, st.floor_out = floor_map._require().value, floor.ctypes.data
+                if trackers is not None:
+                    for t in trackers[i:i + n]:
+                        t._ensure()
+                    handles = (C.c_void_p * n)(*[t._h.value for t in trackers[i:i + n]])
+                    ids, n_featured = np.full(n * S, -1, np.int32), np.zeros(n, np.int32)
+                    st.trackers, st.track_ids, st.n_featured = C.addressof(handles), ids.ctypes.data, n_featured.ctypes.data
+                rc = self._lib.opd_detr_detect_tiled_stages(*args, C.byref(st), recs, counts)
+                if not (rc != 0 and trackers is not None and "counted as one without detections" in _capi.last_error()):
+                    _capi.check(rc, "opd_detr_detect_tiled_stages")   # (out of slots: records, rows and ids were delivered; the mirrors follow first)
+                message = _capi.last_error() if rc != 0 else ""
+                for b in range(n):
+                    dets = []
+                    cnt = int(counts[b])
+                    rows = feats[b, :cnt].copy() if feats is not None else None
+                    for k in range(cnt):
+                        r = recs[b * S + k]
+                        bbox = (r.x, r.y, r.w, r.h)
+                        dets.append(Detection(bbox=bbox, confidence=float(r.score), class_id=int(r.label), class_name="person",
+                                              camera_coords=(bbox[0] + bbox[2] / 2, bbox[1] + bbox[3]), features=None if rows is None else rows[k],
+                                              query_index=int(r.query_index)))
+                        if floor is not None:
+                            floor_map._fill(dets[-1], floor[b * S + k])
+                    if ids is not None:   # (a tracker out of slots gave every record -1: its mirror ages like the native side)
+                        trackers[i + b]._apply(dets, ids[b * S:b * S + cnt])
+                    out.append(dets)
+                if rc != 0:
+                    raise RuntimeError(f"opd_detr_detect_tiled_stages failed (code {rc}): {message}")
+            self._last_orig = [(h, w)] * len(frames)
+            return out
+        except Exception as e:
+            logger.error(f"Detection failed: {e}")
+            raise
+
+    def _tiled_stages_fused(self, h: int, w: int, S: int, features: Optional[str], floor_map, trackers) -> bool:
+        """Whether the stages of a tiled call can run inside it (``detect_tiled`` has the conditions)."""
+        color = features == "color"
+        if color and (max(h, w) > 4096 or self._info.d_model != 256):
+            return False
+        if floor_map is not None and int(floor_map.device) != self.device_ordinal:
+            return False
+        for t in trackers or []:
+            if t.device_ordinal != self.device_ordinal or t.max_dets < S or (color and t.feature_dim != 256):
+                return False
+        return True
+
     def _detect_chunks_overlapped(self, chunks: List[List[np.ndarray]], floor_map=None) -> List[List[Detection]]:
         """Chunk k runs on handle ``k % streams``; one worker thread per handle drives its chunks in order.
 

@@ -123,17 +123,28 @@ class TiledDetector:
         self.detector, self.rows, self.cols, self.nms_threshold = detector, rows, cols, nms_threshold
         self.overlap, self.merge_threshold, self.native = overlap, merge_threshold, bool(native)
 
-    def detect_batch(self, frames: Sequence[np.ndarray]) -> List[List[Detection]]:
+    def _need_detect_tiled(self, staged: bool = False) -> None:
+        if not hasattr(self.detector, "detect_tiled") or (staged and not hasattr(self.detector, "detect_tiled_stages")):
+            raise ValueError("native=True needs a detector with detect_tiled (a HipDetrDetector); "
+                             f"{type(self.detector).__name__} has none")
+
+    def _native_grid(self, frames: Sequence[np.ndarray], staged: bool = False):
+        self._need_detect_tiled(staged)
+        if len({(f.shape[0], f.shape[1]) for f in frames}) != 1:
+            raise ValueError("native=True takes frames of one size")
+        return tile_grid(frames[0].shape[0], frames[0].shape[1], self.rows, self.cols, self.overlap)
+
+    def detect_batch(self, frames: Sequence[np.ndarray], floor_map=None) -> List[List[Detection]]:
+        """``floor_map``: a ``HipFloorMapper``; the merged detections come back with its four fields filled (``native=True``: inside the call)."""
         if self.native:
-            if not hasattr(self.detector, "detect_tiled"):
-                raise ValueError("native=True needs a detector with detect_tiled (a HipDetrDetector); "
-                                 f"{type(self.detector).__name__} has none")
+            self._need_detect_tiled()
             if len(frames) == 0:
                 return []
-            if len({(f.shape[0], f.shape[1]) for f in frames}) != 1:
-                raise ValueError("native=True takes frames of one size")
-            grid = tile_grid(frames[0].shape[0], frames[0].shape[1], self.rows, self.cols, self.overlap)
-            return self.detector.detect_tiled(frames, grid, self.nms_threshold, self.merge_threshold)
+            grid = self._native_grid(frames)
+            if floor_map is None:
+                return self.detector.detect_tiled(frames, grid, self.nms_threshold, self.merge_threshold)
+            self._need_detect_tiled(staged=True)
+            return self.detector.detect_tiled_stages(frames, grid, self.nms_threshold, self.merge_threshold, floor_map=floor_map)
         tiles, origins, sizes = [], [], []
         for f in frames:
             t, o = split_tiles(f, self.rows, self.cols, self.overlap)
@@ -142,8 +153,52 @@ class TiledDetector:
             sizes.append([(x.shape[0], x.shape[1]) for x in t])
         per_tile = self.detector.detect_batch(tiles) if tiles else []
         n = self.rows * self.cols
-        return [merge_tile_detections(per_tile[i * n:(i + 1) * n], origins[i], self.nms_threshold, sizes[i],
-                                      (frames[i].shape[0], frames[i].shape[1]), self.merge_threshold) for i in range(len(frames))]
+        out = [merge_tile_detections(per_tile[i * n:(i + 1) * n], origins[i], self.nms_threshold, sizes[i],
+                                     (frames[i].shape[0], frames[i].shape[1]), self.merge_threshold) for i in range(len(frames))]
+        if floor_map is not None:
+            for dets in out:
+                floor_map.apply(dets)
+        return out
 
-    def detect(self, frame: np.ndarray) -> List[Detection]:
-        return self.detect_batch([frame])[0]
+    def detect(self, frame: np.ndarray, floor_map=None) -> List[Detection]:
+        return self.detect_batch([frame], floor_map=floor_map)[0] if floor_map is not None else self.detect_batch([frame])[0]
+
+    def _check_features(self, features: Optional[str], reid, allow_none: bool) -> None:
+        if features == "encoder":
+            raise ValueError("features='encoder' does not exist for tiled detection: a box merged from two tiles' maps has no encoder row")
+        if features not in (("color", "reid") + ((None,) if allow_none else ())):
+            raise ValueError(f"features must be {'None, ' if allow_none else ''}'color' or 'reid', got {features!r}")
+        if features == "reid" and reid is None:
+            raise ValueError("features='reid' needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
+
+    def _host_features(self, frame: np.ndarray, dets: List[Detection], features: Optional[str], reid) -> np.ndarray:
+        """The separate feature call on merged detections: the colour histograms of the wrapped detector, or the rows of ``reid``."""
+        if features is None or not dets:
+            return np.array([])
+        rows = reid.extract_features(frame, [d.bbox for d in dets]) if features == "reid" else self.detector.extract_color_features(frame, dets)
+        for det, row in zip(dets, rows):
+            det.features = row
+        return rows
+
+    def detect_with_features(self, frame: np.ndarray, features: str = "color", reid=None) -> Tuple[List[Detection], np.ndarray]:
+        """Merged detections + their (N, 256) colour-histogram rows (``features="reid"``: the (N, 512) rows of ``reid``), assigned to
+        ``det.features``.  ``native=True`` with colour: inside the wrapped detector's one tiled call (``detect_tiled_stages``)."""
+        self._check_features(features, reid, allow_none=False)
+        if self.native and features == "color":
+            grid = self._native_grid([frame], staged=True)   # (refuses a detector without detect_tiled)
+            dets = self.detector.detect_tiled_stages([frame], grid, self.nms_threshold, self.merge_threshold, features="color")[0]
+            return dets, (np.stack([d.features for d in dets]) if dets else np.array([]))
+        dets = self.detect(frame)
+        return dets, self._host_features(frame, dets, features, reid)
+
+    def detect_and_track(self, frame: np.ndarray, tracker, features: Optional[str] = "color", reid=None) -> List[Detection]:
+        """``detect_with_features(frame)`` then ``tracker.update(detections)``; ``native=True`` (colour rows or motion only): ONE tiled call with
+        one host wait, the merged records and their rows entering ``tracker`` where they lie.  Returns the detections that got an id."""
+        self._check_features(features, reid, allow_none=True)
+        if self.native and features != "reid":
+            grid = self._native_grid([frame], staged=True)
+            dets = self.detector.detect_tiled_stages([frame], grid, self.nms_threshold, self.merge_threshold, features=features, trackers=[tracker])[0]
+            return [d for d in dets if d.track_id is not None]
+        dets = self.detect(frame)
+        self._host_features(frame, dets, features, reid)
+        return tracker.update(dets)
