@@ -653,7 +653,7 @@ OPD_API int opd_detr_detect_sequence_track(opd_detr* m, opd_reid* r, opd_track* 
  *   trackers      NULL, or [n_frames] distinct handles, frame f into trackers[f]; track_ids host [n_frames][S] (-1 where opd_track_update writes
  *                 -1), n_featured host [n_frames]: counts[f] with COLOR, 0 with NONE.  A tracker out of slots: as opd_detr_detect_frames_track.
  * OPD_EINVAL before any device call, besides everything opd_detr_detect_tiled refuses: NULL `stages` or a wrong struct_size; another
- * feature_kind (a box merged from two tiles' maps has no encoder row; Re-ID is a call of its own); `features` with FEAT_NONE; COLOR on a frame
+ * feature_kind (a box merged from two tiles' maps has no encoder row; Re-ID is the entry opd_detr_detect_tiled_reid below); `features` with FEAT_NONE; COLOR on a frame
  * with a side above 4096 or a handle with d_model != 256; floor_out NULL with `floor`, a floor map on another device; track_ids or n_featured
  * NULL with `trackers`; a NULL tracker, one on another device, one named twice, one with max_dets < S, one with feature_dim != 256 under COLOR. */
 typedef struct opd_tile_stages {
@@ -669,6 +669,41 @@ typedef struct opd_tile_stages {
 OPD_API int opd_detr_detect_tiled_stages(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw,
                                          int n_tiles, int H, int W, float threshold, const opd_tile_params* p, const opd_tile_stages* stages,
                                          opd_tile_det* out, int32_t* counts);
+/* opd_detr_detect_tiled with the Re-ID rows of the MERGED records inside the call (DESIGN.md sections 7a, 7k): what detect_tiled +
+ * opd_reid_extract (+ opd_floor_transform + opd_track_update) give in separate calls, behind the call's ONE host wait.  The crops are planned on the
+ * device from the merged records and cut from the WHOLE frames where the source step left them (the tile windows play no part); the Re-ID forward runs
+ * on the Re-ID handle's own stream between two events, and the call holds that handle for its duration.  With S = n_tiles x num_queries:
+ *   slots      crop slots of the call, 1 .. max_crops of `reid`.  They go to the merged records in (frame, position) order, within a frame the
+ *              merge's own descending-score order.  *n_person = the merged records of the call (the sum of the counts; it may exceed slots, which
+ *              is no error); rows and slot_map entries at k >= min(*n_person, slots) are not written
+ *   slot_map   host [slots]: row k belongs to merged record slot_map[k] = f x S + position
+ *   features   host [slots][feature_dim], or NULL with trackers (then no row leaves the device).  A record's box is x, y, w, h each rounded from
+ *              float64 to float32 ONCE and widened back (the width is not re-derived); row k equals, bit for bit, the row opd_reid_extract
+ *              returns on the same handle for that frame and that float32 box
+ *   floor, floor_out, trackers, track_ids, n_featured   as in opd_tile_stages, rows by position: the floor foot point from the rounded box, the
+ *              tracker's from the unrounded doubles.  The Re-ID rows enter the trackers where the forward left them; a record beyond the slots
+ *              enters with has_feature = 0; n_featured[f] = the records of frame f that got a slot.  A tracker out of slots: as
+ *              opd_detr_detect_frames_track.
+ * OPD_EINVAL before any device call, besides everything opd_detr_detect_tiled refuses: NULL `stages` or a wrong struct_size; NULL `reid`, slots
+ * outside 1 .. max_crops, a Re-ID handle on another device; NULL slot_map or n_person; NULL `features` without trackers; floor_out NULL with
+ * `floor`, a floor map on another device; track_ids or n_featured NULL with `trackers`; a NULL tracker, one on another device, one named twice,
+ * one with max_dets < S, one whose feature_dim differs from the Re-ID model's. */
+typedef struct opd_tile_reid_stages {
+    int32_t struct_size;  /* = sizeof of this struct */
+    int32_t slots;
+    opd_reid* reid;
+    float* features;
+    int32_t* slot_map;
+    int32_t* n_person;
+    opd_floor* floor;
+    opd_floor_rec* floor_out;
+    opd_track* const* trackers;
+    int32_t* track_ids;
+    int32_t* n_featured;
+} opd_tile_reid_stages;
+OPD_API int opd_detr_detect_tiled_reid(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw,
+                                       int n_tiles, int H, int W, float threshold, const opd_tile_params* p, const opd_tile_reid_stages* stages,
+                                       opd_tile_det* out, int32_t* counts);
 /* The solver of the association on its own (host only): cost [rows][cols] row-major -> row_to_col [rows], -1 for a row left alone;
  * min(rows, cols) pairs of smallest total cost, as scipy.optimize.linear_sum_assignment. */
 OPD_API int opd_assign(const double* cost, int rows, int cols, int32_t* row_to_col);

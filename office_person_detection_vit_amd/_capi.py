@@ -84,6 +84,11 @@ class OpdTileStages(C.Structure):   # opd_tile_stages (56 bytes): the feature, f
                 ("trackers", C.c_void_p), ("track_ids", C.c_void_p), ("n_featured", C.c_void_p)]
 
 
+class OpdTileReidStages(C.Structure):   # opd_tile_reid_stages (80 bytes): the Re-ID, floor and track stages of opd_detr_detect_tiled_reid
+    _fields_ = [("struct_size", C.c_int32), ("slots", C.c_int32), ("reid", C.c_void_p), ("features", C.c_void_p), ("slot_map", C.c_void_p), ("n_person", C.c_void_p),
+                ("floor", C.c_void_p), ("floor_out", C.c_void_p), ("trackers", C.c_void_p), ("track_ids", C.c_void_p), ("n_featured", C.c_void_p)]
+
+
 class OpdFloorConfig(C.Structure):   # opd_floor_config: everything is copied at creation
     _fields_ = [("method", C.c_int32), ("n_points", C.c_int32), ("n_triangles", C.c_int32), ("n_zones", C.c_int32), ("has_distortion", C.c_int32),
                 ("allow_overlap", C.c_int32), ("width_px", C.c_int32), ("height_px", C.c_int32), ("H", C.c_double * 9),
@@ -170,6 +175,8 @@ API = {
                                         C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
     "opd_detr_detect_tiled_stages": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                                C.POINTER(OpdTileParams), C.POINTER(OpdTileStages), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
+    "opd_detr_detect_tiled_reid": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                             C.POINTER(OpdTileParams), C.POINTER(OpdTileReidStages), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
     # recs, tile_counts, n_frames, n_tiles, stride, tiles_yxhw, h, w, params, out, counts
     "opd_detr_merge_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
@@ -357,6 +364,9 @@ TEST_API = {
     # floor, with_rows, color, floor_out, boxes, foot, has, feat, n_out
     "opd_test_tile_stages": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the Re-ID stage of a tiled call on merged records of the caller (csrc/opd_tile_reid_test_api.cpp): device, reid, frames, n_frames, h, w, merged, counts, S,
+    # slots, slot_map, rec, n_person, geom, rows, boxes, foot, has, feat, n_out
+    "opd_test_tile_reid": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10),
     # optical-flow hook (csrc/opd_flow_test_api.cpp)
     "opd_flow_test_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     # floor-map hook (csrc/opd_floor_test_api.cpp)

@@ -4,7 +4,8 @@
 // pragma below): every thread evaluates the shared routines of opd_crop.h, so the tables are the host's bit for bit.
 //
 //   crop_select_kernel  ONE workgroup of 256 walks the [B][Q] record slots in (frame, record index) order, 256 at a time: ballot per wave,
-//                       prefix counts over the lanes and the four waves.  The order of the list depends on the records alone.
+//                       prefix counts over the lanes and the four waves.  The order of the list depends on the records alone.  A tiled call
+//                       (opd_detr_detect_tiled_reid) hands both kernels the MERGED records instead: slots by position, boxes in float64.
 //   crop_plan_kernel    one workgroup of 256 per crop slot.  Every thread repeats the box's geometry (scalar work on the same bits); thread
 //                       j then evaluates output column j and output row j (at most out_w, out_h <= 256 each: a loop covers any spec), its
 //                       taps summed one after the other.  The source window is the min / max over the bounds (integer atomics in LDS: the
@@ -33,7 +34,14 @@ __global__ __launch_bounds__(256) void crop_select_kernel(const CropSelectParams
         int target = 0;
         if (i < n) {
             const int f = i / p.Q, q = i - f * p.Q;
-            if (q < p.counts[f]) {
+            if (p.merged) {   // a tiled call: position q of frame f, named by its position (query numbers repeat between the tiles of a frame)
+                int cnt = p.counts[f];
+                cnt = cnt < 0 ? 0 : (cnt > p.Q ? p.Q : cnt);
+                if (q < cnt) {
+                    keep = p.merged[i].label == p.label;
+                    target = i;
+                }
+            } else if (q < p.counts[f]) {
                 const opd_det r = p.records[i];
                 keep = r.label == p.label && (unsigned)r.query_index < (unsigned)p.Q;
                 target = f * p.Q + r.query_index;
@@ -82,12 +90,18 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const CropPlanParams p) 
             return;
         }
         const int i = p.rec[k];
-        const opd_det r = p.records[i];
         frame = i / p.Q;
-        // Detection.bbox = (x1, y1, x2 - x1, y2 - y1) in Python floats, handed on as float32
-        bx = (double)r.x1; by = (double)r.y1;
-        bw = (double)(float)((double)r.x2 - (double)r.x1);
-        bh = (double)(float)((double)r.y2 - (double)r.y1);
+        if (p.merged) {   // Detection.bbox of a merged record = (x, y, w, h) in float64, handed on as float32: each rounded once, the width not re-derived
+            const opd_tile_det g = p.merged[i];
+            bx = (double)(float)g.x; by = (double)(float)g.y;
+            bw = (double)(float)g.w; bh = (double)(float)g.h;
+        } else {
+            const opd_det r = p.records[i];
+            // Detection.bbox = (x1, y1, x2 - x1, y2 - y1) in Python floats, handed on as float32
+            bx = (double)r.x1; by = (double)r.y1;
+            bw = (double)(float)((double)r.x2 - (double)r.x1);
+            bh = (double)(float)((double)r.y2 - (double)r.y1);
+        }
     }
     ReidGeom g;
     crop_box_geometry(p.spec, bx, by, bw, bh, p.h, p.w, &g);

@@ -238,6 +238,19 @@ __global__ __launch_bounds__(TRACK_INGEST_THREADS) void track_ingest_kernel(cons
     if (p.merged) {   // a tiled call: the frame's merged records in frame pixels (float64), feature rows by position
         const opd_tile_det g = p.merged[i];
         const float* row = p.rows_kind == TRACK_ROWS_BY_POSITION ? p.rows + ((size_t)p.frame * p.Q + i) * D : nullptr;
+        if (p.rows_kind == TRACK_ROWS_BY_SLOT) {   // the Re-ID rows of a tiled call: the slot whose entry names this position, as the record form below
+            int filled = *p.n_person;
+            filled = filled < p.slots ? filled : p.slots;
+            const int want = p.frame * p.Q + i;
+            int k = -1;
+            for (int s = lane; s < filled; s += TRACK_INGEST_THREADS)
+                if (p.slot_map[s] == want) k = s;   // (a position gets one slot at most)
+            for (int o = 32; o > 0; o >>= 1) {
+                const int other = __shfl_xor(k, o);
+                k = other > k ? other : k;
+            }
+            if (k >= 0) row = p.rows + (size_t)k * D;
+        }
         if (lane == 0) {
             // the box as HipTracker.update's float32 array takes det.bbox, each double rounded once; the foot point as detect_tiled fills camera_coords, in
             // float64 from the unrounded doubles, rounded where update stores it (not the foot point of the rounded box)
@@ -637,8 +650,8 @@ hipError_t opd_launch_track_assoc(const TrackAssocParams& p, hipStream_t stream)
 hipError_t opd_launch_track_ingest(const TrackIngestParams& p, hipStream_t stream) {
     if (p.Q < 1 || p.Q > TRACK_MAX_DETS || p.D < 1 || p.D > TRACK_MAX_DIM || p.frame < 0 || p.slots < 0) return hipErrorInvalidValue;
     if (p.rows_kind != TRACK_ROWS_NONE && p.rows_kind != TRACK_ROWS_BY_QUERY && p.rows_kind != TRACK_ROWS_BY_SLOT && p.rows_kind != TRACK_ROWS_BY_POSITION) return hipErrorInvalidValue;
-    // (merged records carry no usable query index: their rows go by position, and only theirs)
-    if (p.merged ? (p.rows_kind != TRACK_ROWS_NONE && p.rows_kind != TRACK_ROWS_BY_POSITION) : (p.rows_kind == TRACK_ROWS_BY_POSITION || !p.records)) return hipErrorInvalidValue;
+    // (merged records carry no usable query index: their rows go by position, and only theirs, or by slots that name positions)
+    if (p.merged ? p.rows_kind == TRACK_ROWS_BY_QUERY : (p.rows_kind == TRACK_ROWS_BY_POSITION || !p.records)) return hipErrorInvalidValue;
     if (!p.count || !p.boxes || !p.foot || !p.has || !p.n_out) return hipErrorInvalidValue;
     if (p.rows_kind != TRACK_ROWS_NONE && (!p.rows || !p.feat)) return hipErrorInvalidValue;
     if (p.rows_kind == TRACK_ROWS_BY_SLOT && (!p.slot_map || !p.n_person)) return hipErrorInvalidValue;

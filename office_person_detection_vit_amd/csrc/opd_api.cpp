@@ -227,6 +227,17 @@ static int enqueue_features(opd_detr* m, const RecordSink& s, int h, int w, cons
     const FeatureStage& f = s.feature;
     *rows = TrackFeatureSource{};
     if (f.kind == FEAT_NONE) return OPD_OK;
+    if (f.kind == FEAT_REID) {   // select, plan and the Re-ID forward behind the post-process; the rows come back behind the records, before the one wait
+        const bool tiled = s.tile.params != nullptr;   // a tiled call: the MERGED records, crops cut from the WHOLE frames at d_camera; a slot names a position
+        const ReidRecordView view = tiled ? ReidRecordView{nullptr, merged_records(m), merged_counts(m), s.tile.n_frames, s.tile.n_tiles * Q}
+                                          : ReidRecordView{m->d_records, nullptr, m->d_counts, B, Q};
+        reid->emplace(f.reid);
+        RCCHK((*reid)->enqueue(m->stream, view, d_camera, h, w, s.label, f.slots));
+        // (a tracker reads the rows where the forward left them; the slot list alone comes back, unless a tiled call asks for the rows as well)
+        (*reid)->with_rows = tiled ? f.features != nullptr : !s.track.on();
+        *rows = {TRACK_ROWS_BY_SLOT, reid_feature_dim(f.reid), (*reid)->dev_rows(), (*reid)->dev_slot_map(), (*reid)->dev_n_person(), f.slots};
+        return OPD_OK;
+    }
     if (s.tile.params) {   // a tiled call (FEAT_COLOR, the entry's check): crops of the merged records, cut from the WHOLE frames at d_camera; a row per position
         RCCHK(ensure(m, &m->d_color_acc, slots_of(m) * OPD_COLOR_ACC_WORDS));
         ColorParams cp{};
@@ -234,13 +245,6 @@ static int enqueue_features(opd_detr* m, const RecordSink& s, int h, int w, cons
         cp.Q = s.tile.n_tiles * Q; cp.fh = h; cp.fw = w; cp.label = s.label; cp.n = B * Q;
         HIPCHK(opd_launch_color_features(cp, std::min(64, (h + 15) / 16), m->stream));
         *rows = {TRACK_ROWS_BY_POSITION, OPD_COLOR_DIM, m->d_feat_all, nullptr, nullptr, 0};
-        return OPD_OK;
-    }
-    if (f.kind == FEAT_REID) {   // select, plan and the Re-ID forward behind the post-process; the rows come back behind the records, before the one wait
-        reid->emplace(f.reid);
-        RCCHK((*reid)->enqueue(m->stream, m->d_records, m->d_counts, d_camera, B, Q, h, w, s.label, f.slots));
-        (*reid)->with_rows = !s.track.on();   // (a tracker reads the rows where the forward left them; the slot list alone comes back)
-        *rows = {TRACK_ROWS_BY_SLOT, reid_feature_dim(f.reid), (*reid)->dev_rows(), (*reid)->dev_slot_map(), (*reid)->dev_n_person(), f.slots};
         return OPD_OK;
     }
     if (f.kind == FEAT_ROI)
@@ -299,7 +303,7 @@ static int finish_trackers(opd_detr* m, const RecordSink& s, bool with_features)
         const int n = std::max(0, std::min(counts[b], stride));
         const float* conf = tiled ? &s.tile.out[(size_t)b * stride].score : &s.out[(size_t)b * stride].score;
         const int one = track_fused_finish(t.trackers[b], conf, (int)((tiled ? sizeof(opd_tile_det) : sizeof(opd_det)) / sizeof(float)), n, with_features,
-                                           t.track_ids + (size_t)b * stride, tiled ? "opd_detr_detect_tiled_stages" : "opd_detr_detect_frames_track");
+                                           t.track_ids + (size_t)b * stride, tiled ? s.tile.entry : "opd_detr_detect_frames_track");
         if (one != OPD_OK && rc == OPD_OK) { rc = one; first = g_err; }
     }
     return rc == OPD_OK ? OPD_OK : fail(rc, first);
@@ -317,7 +321,7 @@ static float* query_rows_out(const RecordSink& s) { return s.feature.kind == FEA
 
 // The one fetch of a blocking call: what the sink's parts ask for comes back into page-locked memory (a copy into the caller's pageable arrays is staged by
 // the runtime anyway, once per call), then the call's ONE wait.  A tiled call: [counts | merged records], and of its stages the rows by position (unless
-// a tracker alone reads them) and the floor rows.  Host outputs: [records of max_batch frames |
+// a tracker alone reads them), the floor rows, and the Re-ID call's slot list (with its rows when the caller takes them).  Host outputs: [records of max_batch frames |
 // counts (| per-query feature rows)] in one copy, the floor rows, the Re-ID call's slot list (and rows, unless a tracker reads them in place).  Device
 // outputs were written in place by the post-process kernel.
 static int fetch_records(opd_detr* m, const RecordSink& s, ReidFusedCall* reid) {
@@ -329,6 +333,7 @@ static int fetch_records(opd_detr* m, const RecordSink& s, ReidFusedCall* reid) 
             HIPCHK(hipMemcpyAsync(static_cast<char*>(m->sync_pinned) + feat_off(m), m->d_feat_all, B * feat_row(m), hipMemcpyDeviceToHost, m->stream));
         }
         if (s.floor.fmap) HIPCHK(hipMemcpyAsync(m->h_floor, m->d_floor, (size_t)B * Q * sizeof(opd_floor_rec), hipMemcpyDeviceToHost, m->stream));
+        if (reid) RCCHK(reid->copy_back(m->stream));   // the slot list (and the rows by slot, when the caller takes them)
     } else if (!outputs_on_device(s.mem_kind)) {
         RCCHK(ensure_sync_pinned(m));
         HIPCHK(hipMemcpyAsync(m->sync_pinned, m->d_records, query_rows_out(s) ? feat_off(m) + B * feat_row(m) : rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
@@ -394,6 +399,10 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
             const int n = std::max(0, std::min(s.tile.counts[f], S));
             if (s.floor.fmap) memcpy(s.floor.out + (size_t)f * S, m->h_floor + (size_t)f * S, (size_t)n * sizeof(opd_floor_rec));
             if (tracked) s.track.n_featured[f] = rows.rows_kind == TRACK_ROWS_NONE ? 0 : n;
+        }
+        if (reid) {   // rows by slot: slot_map[k] = f * S + position; a frame's featured records are those that got a slot
+            reid->deliver(s.feature.features, s.feature.slot_map, s.feature.n_person);
+            if (tracked) reid->slots_per_frame(s.tile.n_frames, S, s.track.n_featured);
         }
         return tracked ? finish_trackers(m, s, rows.rows_kind != TRACK_ROWS_NONE) : OPD_OK;
     } else if (!dev) unpack_records(m, m->sync_pinned, B, s.out, s.counts, query_rows_out(s));
@@ -687,17 +696,27 @@ int opd_detr_nms_records(opd_detr* m, opd_det* dets, int32_t* counts, int n_fram
     return OPD_OK;
 }); }
 // Tiled detection: every refusal comes before the first device call (check_tiles; check_shape makes none for host pixels).  `st` (null: opd_detr_detect_tiled
-// itself): the feature, floor and track parts of the sink, which then read the merged records where the merge left them, rows by position
+// itself): the feature, floor and track parts of the sink, which then read the merged records where the merge left them, rows by position.  `rs`
+// (opd_detr_detect_tiled_reid; `st` is then null): the same with the Re-ID rows as the feature kind, rows by slot, a slot naming a position
 static int detect_tiled(const std::string& me, opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W,
-                        float threshold, const opd_tile_params* p, const opd_tile_stages* st, opd_tile_det* out, int32_t* counts) {
+                        float threshold, const opd_tile_params* p, const opd_tile_stages* st, const opd_tile_reid_stages* rs, opd_tile_det* out, int32_t* counts) {
     if (!frames || !out || !counts) return fail(OPD_EINVAL, me + ": null argument");
+    opd_tile_stages of_reid{};   // the floor and track parts of the Re-ID entry's block, as the checks below read them
+    if (rs) {   // (opd_detr_detect_tiled_reid: `st` is null)
+        if (rs->struct_size != (int32_t)sizeof(opd_tile_reid_stages)) return fail(OPD_EINVAL, me + ": opd_tile_reid_stages.struct_size mismatch");
+        if (!rs->reid) return fail(OPD_EINVAL, me + ": null Re-ID handle");
+        if (!rs->slot_map || !rs->n_person) return fail(OPD_EINVAL, me + ": slot_map or n_person is null");
+        if (!rs->features && !rs->trackers) return fail(OPD_EINVAL, me + ": features is null while no trackers are given (the rows would go nowhere)");
+        of_reid = opd_tile_stages{(int32_t)sizeof(opd_tile_stages), OPD_TRACK_FEAT_REID, rs->features, rs->floor, rs->floor_out, rs->trackers, rs->track_ids, rs->n_featured};
+        st = &of_reid;
+    }
     const bool color = st && st->feature_kind == OPD_TRACK_FEAT_COLOR;
     if (st) {   // what needs neither the handle nor the windows
         if (st->struct_size != (int32_t)sizeof(opd_tile_stages)) return fail(OPD_EINVAL, me + ": opd_tile_stages.struct_size mismatch");
-        if (st->feature_kind != OPD_TRACK_FEAT_NONE && !color)
+        if (st->feature_kind != OPD_TRACK_FEAT_NONE && !color && !rs)
             return fail(OPD_EINVAL, me + ": feature_kind " + std::to_string(st->feature_kind) + "; a tiled call takes OPD_TRACK_FEAT_NONE or OPD_TRACK_FEAT_COLOR (a box merged from two "
                                          "tiles' maps has no encoder row, and Re-ID is a call of its own)");
-        if (st->features && !color) return fail(OPD_EINVAL, me + ": features given with feature_kind OPD_TRACK_FEAT_NONE");
+        if (st->features && !color && !rs) return fail(OPD_EINVAL, me + ": features given with feature_kind OPD_TRACK_FEAT_NONE");
         if (st->floor && !st->floor_out) return fail(OPD_EINVAL, me + ": floor_out is null while a floor-map handle is given");
         if (st->trackers && (!st->track_ids || !st->n_featured)) return fail(OPD_EINVAL, me + ": track_ids or n_featured is null while trackers are given");
     }
@@ -718,9 +737,11 @@ static int detect_tiled(const std::string& me, opd_detr* m, const uint8_t* const
     src.n_frames = n_frames; src.n_tiles = n_tiles; src.tiles = tiles_yxhw;
     RecordSink sink(threshold, nullptr, nullptr, nullptr, OPD_MEM_HOST);   // (boxes in TILE pixels; the merge puts them on the frame)
     sink.tile.params = p; sink.tile.n_frames = n_frames; sink.tile.n_tiles = n_tiles; sink.tile.frame_h = h; sink.tile.frame_w = w;
-    sink.tile.out = out; sink.tile.counts = counts;
+    sink.tile.out = out; sink.tile.counts = counts; sink.tile.entry = me.c_str();
     if (st) {   // the stages' own refusals that need the handle, then their parts of the sink
         const int S = n_tiles * m->arch.queries;
+        if (rs) RCCHK(reid_fused_check(rs->reid, m->device, rs->slots, me.c_str()));
+        const int reid_dim = rs ? reid_feature_dim(rs->reid) : 0;
         if (color && m->arch.d_model != OPD_COLOR_DIM) return fail(OPD_EINVAL, me + ": feature_kind OPD_TRACK_FEAT_COLOR: the feature area of the handle is sized for d_model = 256");
         if (st->floor && st->floor->device != m->device)
             return fail(OPD_EINVAL, me + ": the detector is on device " + std::to_string(m->device) + ", the floor map `floor` on device " + std::to_string(st->floor->device));
@@ -733,11 +754,14 @@ static int detect_tiled(const std::string& me, opd_detr* m, const uint8_t* const
                 return fail(OPD_EINVAL, who + "was made for max_dets = " + std::to_string(t->NM) + ", a tiled frame can keep n_tiles x num_queries = " + std::to_string(S) + " records");
             if (color && t->D != OPD_COLOR_DIM)
                 return fail(OPD_EINVAL, who + "was made for feature_dim = " + std::to_string(t->D) + ", the rows of feature_kind OPD_TRACK_FEAT_COLOR have 256 numbers");
+            if (rs && t->D != reid_dim)
+                return fail(OPD_EINVAL, who + "was made for feature_dim = " + std::to_string(t->D) + ", the rows of the Re-ID model have " + std::to_string(reid_dim) + " numbers");
             for (int a = 0; a < f; ++a)
                 if (st->trackers[a] == t) return fail(OPD_EINVAL, who + "is trackers[" + std::to_string(a) + "] too; a tracker takes one frame per call");
         }
         sink.label = p->person_label;
-        sink.feature.kind = color ? FEAT_COLOR : FEAT_NONE; sink.feature.features = st->features;
+        sink.feature.kind = color ? FEAT_COLOR : rs ? FEAT_REID : FEAT_NONE; sink.feature.features = st->features;
+        if (rs) { sink.feature.reid = rs->reid; sink.feature.slots = rs->slots; sink.feature.slot_map = rs->slot_map; sink.feature.n_person = rs->n_person; }
         sink.floor.fmap = st->floor; sink.floor.out = st->floor_out;
         sink.track.trackers = st->trackers; sink.track.track_ids = st->track_ids; sink.track.n_featured = st->n_featured;
     }
@@ -746,13 +770,20 @@ static int detect_tiled(const std::string& me, opd_detr* m, const uint8_t* const
 }
 int opd_detr_detect_tiled(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W, float threshold,
                           const opd_tile_params* p, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled", [&]() -> int {
-    return detect_tiled("opd_detr_detect_tiled", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, nullptr, out, counts);
+    return detect_tiled("opd_detr_detect_tiled", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, nullptr, nullptr, out, counts);
 }); }
 // ... with the feature, floor and track stages on the merged records, in front of the same one wait
 int opd_detr_detect_tiled_stages(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W, float threshold,
                                  const opd_tile_params* p, const opd_tile_stages* stages, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled_stages", [&]() -> int {
     if (!stages) return fail(OPD_EINVAL, "opd_detr_detect_tiled_stages: null argument (stages)");
-    return detect_tiled("opd_detr_detect_tiled_stages", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, stages, out, counts);
+    return detect_tiled("opd_detr_detect_tiled_stages", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, stages, nullptr, out, counts);
+}); }
+// ... with the Re-ID rows of the merged records instead: crops planned on the device from the merged records, cut from the whole frames in m->src, the
+// forward on the Re-ID handle's stream between two events, rows by slot into the caller's array and / or the trackers
+int opd_detr_detect_tiled_reid(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W, float threshold,
+                               const opd_tile_params* p, const opd_tile_reid_stages* stages, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled_reid", [&]() -> int {
+    if (!stages) return fail(OPD_EINVAL, "opd_detr_detect_tiled_reid: null argument (stages)");
+    return detect_tiled("opd_detr_detect_tiled_reid", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, nullptr, stages, out, counts);
 }); }
 int opd_detr_merge_tiles(opd_detr* m, const opd_det* recs, const int32_t* tile_counts, int n_frames, int n_tiles, int stride, const int32_t* tiles_yxhw, int h, int w,
                          const opd_tile_params* p, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_merge_tiles", [&]() -> int {

@@ -452,6 +452,7 @@ struct TrackStage {   // the kept records and feature rows enter trackers where 
 struct TileStage {   // a SRC_TILES batch: the records of a frame's tiles, suppressed per tile with the PARAMETERS' label and threshold, merge across the seams
     const opd_tile_params* params = nullptr;
     int n_frames = 0, n_tiles = 0, frame_h = 0, frame_w = 0;
+    const char* entry = "opd_detr_detect_tiled_stages";   // the entry a tracker's error is worded for
     opd_tile_det* out = nullptr; int32_t* counts = nullptr;   // [n_frames][n_tiles x queries], [n_frames]; RecordSink::out / counts stay null: the per-tile records never leave the device
 };
 struct RecordSink {

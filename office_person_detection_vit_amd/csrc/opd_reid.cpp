@@ -236,7 +236,7 @@ ReidFusedCall::ReidFusedCall(opd_reid* r_) : r(r_), lk(r_->call_mu, std::defer_l
     lk.lock();
 }
 
-int ReidFusedCall::enqueue(hipStream_t s, const opd_det* records, const int32_t* counts, const uint8_t* frames, int B, int Q, int h, int w, int label, int slots_) {
+int ReidFusedCall::enqueue(hipStream_t s, const ReidRecordView& v, const uint8_t* frames, int h, int w, int label, int slots_, int32_t* geom) {
     slots = slots_;
     const int C = r->cfg.max_crops, E = r->model->feature_dim();
     const CropSpec& spec = r->model->crop();
@@ -246,13 +246,13 @@ int ReidFusedCall::enqueue(hipStream_t s, const opd_det* records, const int32_t*
     const int nb = bucket_of(r, slots);
     int32_t* sel = reinterpret_cast<int32_t*>(r->up.dev + fused_sel_off(r));
     CropSelectParams sp{};
-    sp.records = records; sp.counts = counts; sp.B = B; sp.Q = Q; sp.label = label; sp.slots = slots;
+    sp.records = v.records; sp.merged = v.merged; sp.counts = v.counts; sp.B = v.B; sp.Q = v.Q; sp.label = label; sp.slots = slots;
     sp.slot = sel; sp.rec = sel + C; sp.n_person = sel + 2 * C;
     HIPCHK(opd_launch_crop_select(sp, s));
     CropPlanParams pp{};
     pp.spec = spec;
-    pp.records = records; pp.rec = sp.rec; pp.n_person = sp.n_person;
-    pp.frames = frames; pp.Q = Q; pp.h = h; pp.w = w; pp.slots = slots;
+    pp.records = v.records; pp.merged = v.merged; pp.rec = sp.rec; pp.n_person = sp.n_person;
+    pp.frames = frames; pp.Q = v.Q; pp.h = h; pp.w = w; pp.slots = slots; pp.geom = geom;
     pp.base = r->up.dev; pp.tables_off = fused_tables_off(r); pp.stride = cs.stride;
     pp.ksh_max = cs.ksh_max; pp.ksv_max = cs.ksv_max;
     HIPCHK(opd_launch_crop_plan(pp, nb, s));
@@ -277,12 +277,13 @@ void ReidFusedCall::deliver(float* features, int32_t* slot_map, int32_t* n_perso
     const int32_t* sel = reinterpret_cast<const int32_t*>(r->up.host + (size_t)slots * E * 4);
     const int np = sel[2 * C], n = std::min(np, slots);
     *n_person = np;
-    memcpy(features, r->up.host, (size_t)n * E * 4);
+    if (features && with_rows) memcpy(features, r->up.host, (size_t)n * E * 4);
     memcpy(slot_map, sel, (size_t)n * 4);
 }
 
 const float* ReidFusedCall::dev_rows() const { return r->model->features(); }
 const int32_t* ReidFusedCall::dev_slot_map() const { return reinterpret_cast<const int32_t*>(r->up.dev + fused_sel_off(r)); }
+const int32_t* ReidFusedCall::dev_rec() const { return dev_slot_map() + (size_t)r->cfg.max_crops; }
 const int32_t* ReidFusedCall::dev_n_person() const { return dev_slot_map() + 2 * (size_t)r->cfg.max_crops; }
 
 void ReidFusedCall::slots_per_frame(int B, int Q, int32_t* out) const {

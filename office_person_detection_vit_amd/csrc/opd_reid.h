@@ -50,23 +50,32 @@ struct ReidModel {
     virtual void fill_info(opd_reid_model_info* info) const = 0;   // model and the architecture fields (the rest are the handle's)
 };
 
-// The Re-ID half of opd_detr_detect_frames_reid (opd_api.cpp runs the detector half and the one wait).  reid_fused_check: the argument
-// checks that need the handle, before any HIP call.  A ReidFusedCall holds the handle for the duration of the call (one call at a time:
-// a second thread waits in the constructor):
+// The Re-ID half of opd_detr_detect_frames_reid and opd_detr_detect_tiled_reid (opd_api.cpp runs the detector half and the one wait).
+// reid_fused_check: the argument checks that need the handle, before any HIP call.  A ReidFusedCall holds the handle for the duration of
+// the call (one call at a time: a second thread waits in the constructor):
 //   enqueue    on the detector's stream `s`, behind the post-process kernel: crop_select_kernel and crop_plan_kernel (kernels_crop.hip)
-//              plan the crops of the first `slots` records labelled `label` into the handle's staging buffer, read in place from `frames`
-//              ([B][h][w][3] on the device); an event; the forward of bucket_of(slots) crops on the handle's own stream through its graph
-//              cache; an event back, which `s` waits for
+//              plan the crops of the first `slots` records of the view labelled `label` into the handle's staging buffer, read in place
+//              from `frames` ([B][h][w][3] on the device; a tiled call: the whole camera frames); an event; the forward of
+//              bucket_of(slots) crops on the handle's own stream through its graph cache; an event back, which `s` waits for
 //   copy_back  on `s`: [slots][feature_dim] rows (unless with_rows is off), the slot map and the person count into the handle's page-locked side
 //   deliver    after the caller's wait on `s`: rows and slot map of k < min(n_person, slots) into the caller's arrays
 int reid_fused_check(const opd_reid* r, int device, int slots, const char* who);
 int reid_feature_dim(const opd_reid* r);
+// The records a fused call plans its crops from, on the device: [B][Q] records of the post-process with their counts, or (`merged` non-null: a tiled
+// call, opd_detr_detect_tiled_reid) the [B][Q] MERGED records in frame pixels, Q = n_tiles x queries.  Then slot_map[k] = rec[k] = frame * Q + position.
+struct ReidRecordView {
+    const opd_det* records;
+    const opd_tile_det* merged;
+    const int32_t* counts;
+    int B, Q;
+};
 struct ReidFusedCall {
     opd_reid* r;
     std::unique_lock<std::mutex> lk;
     int slots = 0;
     explicit ReidFusedCall(opd_reid* r);
-    int enqueue(hipStream_t s, const opd_det* records, const int32_t* counts, const uint8_t* frames, int B, int Q, int h, int w, int label, int slots);
+    // `geom` (nullable; the test hook of opd_tile_reid_test_api.cpp): device [slots][13], the plan's geometry words of every filled slot
+    int enqueue(hipStream_t s, const ReidRecordView& v, const uint8_t* frames, int h, int w, int label, int slots, int32_t* geom = nullptr);
     int copy_back(hipStream_t s);
     void deliver(float* features, int32_t* slot_map, int32_t* n_person) const;
     // the fused detect-and-track call: the rows stay on the device (copy_back then brings the slot list alone); where the rows, the slot map
@@ -74,6 +83,7 @@ struct ReidFusedCall {
     bool with_rows = true;
     const float* dev_rows() const;
     const int32_t* dev_slot_map() const;
+    const int32_t* dev_rec() const;
     const int32_t* dev_n_person() const;
     void slots_per_frame(int B, int Q, int32_t* out) const;
 };

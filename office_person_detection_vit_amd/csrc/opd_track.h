@@ -64,7 +64,8 @@ struct TrackIngestParams {
     const int32_t* count;      // its kept count
     int32_t Q, D, frame;
     int32_t rows_kind;         // TRACK_ROWS_*
-    const float* rows;         // BY_QUERY: [..][Q][D], row frame * Q + query_index.  BY_SLOT: [slots][D], row k of slot_map[k] = frame * Q + query_index.
+    const float* rows;         // BY_QUERY: [..][Q][D], row frame * Q + query_index.  BY_SLOT: [slots][D], row k of slot_map[k] = frame * Q + query_index
+                               // (merged records: slot_map[k] = frame * Q + i, the record's POSITION; a record without a slot enters with has = 0).
                                // BY_POSITION (merged records only: two tiles of a frame use the same query numbers): [..][Q][D], row frame * Q + i of record i
     const int32_t* slot_map;   // BY_SLOT: [slots], of which min(*n_person, slots) are filled
     const int32_t* n_person;

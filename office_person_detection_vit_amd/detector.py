@@ -654,6 +654,137 @@ class HipDetrDetector:
                 return False
         return True
 
+    def detect_tiled_reid(self, frames: Sequence[np.ndarray], tiles: Sequence[Tuple[int, int, int, int]], reid, nms_threshold: float = 0.4,
+                          merge_threshold: float = 0.5, edge_tolerance: float = 0.01, reid_slots: int = 32, floor_map=None,
+                          trackers=None) -> List[List[Detection]]:
+        """``detect_tiled`` with the Re-ID rows of ``reid`` (a loaded ``HipReIDExtractor`` / ``HipOSNetReIDExtractor``) for the merged records INSIDE
+        the call (``opd_detr_detect_tiled_reid``): the crops are planned on the device from the merged records and cut from the whole frames where
+        they were uploaded, the Re-ID forward runs in front of the call's one host wait.  Frames go in chunks of ``max_batch // len(tiles)``; a chunk
+        of n frames shares ``min(reid_slots * n, reid.max_crops)`` crop slots, handed out in (frame, score) order.  Without ``trackers`` every
+        detection comes back with ``det.features`` filled (records beyond the slots through one standalone ``reid.extract_features_batch``), so the
+        lists equal ``detect_tiled`` + ``reid.extract_features`` (+ ``floor_map.apply``) whatever ``reid_slots`` is.  With ``trackers`` (one
+        ``HipTracker`` per frame) the rows enter them on the device, ``det.features`` stays ``None`` and ``track_id`` is filled, as in
+        ``detect_and_track``; a record beyond the slots enters without a feature.  Where the fused conditions fail (``reid`` without a native
+        handle or on another GPU; a tracker on another GPU, with ``max_dets`` below ``tiles x queries`` or with a ``feature_dim`` other than the
+        Re-ID model's; a floor map on another GPU) the separate calls run one after the other, with the same results."""
+        self._require_model()
+        frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
+        if reid is None:
+            raise ValueError("detect_tiled_reid needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
+        if trackers is not None:
+            trackers = list(trackers)
+            if len(trackers) != len(frames):
+                raise ValueError(f"{len(trackers)} trackers for {len(frames)} frames: frame f enters trackers[f]")
+            if len({id(t) for t in trackers}) != len(trackers):
+                raise ValueError("a tracker is named twice: a tracker takes one frame per call")
+        if not tiles or any(len(t) != 4 for t in tiles):
+            raise ValueError("tiles must be a non-empty list of (y0, x0, h, w)")
+        if len(tiles) > self.max_batch:
+            raise ValueError(f"the {len(tiles)} tiles of one frame exceed max_batch = {self.max_batch}")
+        if len({(t[2], t[3]) for t in tiles}) != 1:
+            raise ValueError("tiles of more than one size: one forward has one model size")
+        if not getattr(reid, "is_loaded", True):
+            raise RuntimeError("Re-ID model is not loaded: call load_model() first")
+        if len(frames) == 0:
+            return []
+        f0 = frames[0]
+        for f in frames:
+            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != f0.shape or not f.flags.c_contiguous:
+                raise ValueError("frames must be contiguous uint8 numpy arrays of shape (H, W, 3) in BGR order, all of one size")
+        h, w = int(f0.shape[0]), int(f0.shape[1])
+        th, tw = tiles[0][2], tiles[0][3]
+        H, W = model_input_size(th, tw, self.max_size[0], self.max_size[1]) if self.resize else (th, tw)
+        T, Q = len(tiles), self._info.num_queries
+        S = T * Q
+        if not self._tiled_reid_fused(S, reid, floor_map, trackers):
+            out = self.detect_tiled(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
+            for b, dets in enumerate(out):
+                for det, row in zip(dets, reid.extract_features(frames[b], [d.bbox for d in dets])):
+                    det.features = row
+                if floor_map is not None:
+                    floor_map.apply(dets)
+                if trackers is not None:
+                    trackers[b].update(dets)
+            return out
+        E = int(reid.feature_dim)
+        win = np.asarray(tiles, dtype=np.int32).reshape(T, 4)
+        params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
+                                     merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
+        per = max(1, self.max_batch // T)
+        out: List[List[Detection]] = []
+        try:
+            for i in range(0, len(frames), per):
+                chunk = frames[i:i + per]
+                n = len(chunk)
+                slots = max(1, min(int(reid_slots) * n, int(reid.max_crops)))
+                recs, counts = (_capi.OpdTileDet * (n * S))(), (C.c_int32 * n)()
+                ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in chunk])
+                args = (C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, H, W, float(self.confidence_threshold), C.byref(params))
+                # rows by slot: row k belongs to merged record slot_map[k] = b * S + position; floor and track-id rows by position
+                feats = floor = ids = None
+                slot_map, n_person = np.full(slots, -1, np.int32), np.zeros(1, np.int32)
+                st = _capi.OpdTileReidStages(struct_size=C.sizeof(_capi.OpdTileReidStages), slots=slots, reid=reid._handle.value,
+                                             slot_map=slot_map.ctypes.data, n_person=n_person.ctypes.data)
+                if trackers is None:
+                    feats = np.empty((slots, E), np.float32)
+                    st.features = feats.ctypes.data
+                if floor_map is not None:
+                    floor = np.zeros(n * S, floor_map.REC_DTYPE)
+                    st.floor, st.floor_out = floor_map._require().value, floor.ctypes.data
+                if trackers is not None:
+                    for t in trackers[i:i + n]:
+                        t._ensure()
+                    handles = (C.c_void_p * n)(*[t._h.value for t in trackers[i:i + n]])
+                    ids, n_featured = np.full(n * S, -1, np.int32), np.zeros(n, np.int32)
+                    st.trackers, st.track_ids, st.n_featured = C.addressof(handles), ids.ctypes.data, n_featured.ctypes.data
+                rc = self._lib.opd_detr_detect_tiled_reid(*args, C.byref(st), recs, counts)
+                if not (rc != 0 and trackers is not None and "counted as one without detections" in _capi.last_error()):
+                    _capi.check(rc, "opd_detr_detect_tiled_reid")   # (out of slots: records and ids were delivered; the mirrors follow first)
+                message = _capi.last_error() if rc != 0 else ""
+                row_of = {int(p): k for k, p in enumerate(slot_map[:min(int(n_person[0]), slots)])}
+                chunk_dets, missing = [], []
+                for b in range(n):
+                    dets = []
+                    cnt = int(counts[b])
+                    for k in range(cnt):
+                        r = recs[b * S + k]
+                        bbox = (r.x, r.y, r.w, r.h)
+                        dets.append(Detection(bbox=bbox, confidence=float(r.score), class_id=int(r.label), class_name="person",
+                                              camera_coords=(bbox[0] + bbox[2] / 2, bbox[1] + bbox[3]), features=None, query_index=int(r.query_index)))
+                        if feats is not None:
+                            if b * S + k in row_of:
+                                dets[-1].features = feats[row_of[b * S + k]].copy()
+                            else:
+                                missing.append((b, k))
+                        if floor is not None:
+                            floor_map._fill(dets[-1], floor[b * S + k])
+                    if ids is not None:   # (a tracker out of slots gave every record -1: its mirror ages like the native side)
+                        trackers[i + b]._apply(dets, ids[b * S:b * S + cnt])
+                    chunk_dets.append(dets)
+                if missing:   # more merged records than slots: the remainder through ONE standalone call
+                    rows = reid.extract_features_batch(chunk, [[chunk_dets[b][k].bbox for (bb, k) in missing if bb == b] for b in range(n)])
+                    for (b, k), row in zip(missing, rows):
+                        chunk_dets[b][k].features = row
+                out.extend(chunk_dets)
+                if rc != 0:
+                    raise RuntimeError(f"opd_detr_detect_tiled_reid failed (code {rc}): {message}")
+            self._last_orig = [(h, w)] * len(frames)
+            return out
+        except Exception as e:
+            logger.error(f"Detection failed: {e}")
+            raise
+
+    def _tiled_reid_fused(self, S: int, reid, floor_map, trackers) -> bool:
+        """Whether the Re-ID stage of a tiled call can run inside it (``detect_tiled_reid`` has the conditions)."""
+        if getattr(reid, "_handle", None) is None or reid._ordinal() != self.device_ordinal:
+            return False
+        if floor_map is not None and int(floor_map.device) != self.device_ordinal:
+            return False
+        for t in trackers or []:
+            if t.device_ordinal != self.device_ordinal or t.max_dets < S or t.feature_dim != int(reid.feature_dim):
+                return False
+        return True
+
     def _detect_chunks_overlapped(self, chunks: List[List[np.ndarray]], floor_map=None) -> List[List[Detection]]:
         """Chunk k runs on handle ``k % streams``; one worker thread per handle drives its chunks in order.
 

@@ -180,10 +180,23 @@ class TiledDetector:
             det.features = row
         return rows
 
-    def detect_with_features(self, frame: np.ndarray, features: str = "color", reid=None) -> Tuple[List[Detection], np.ndarray]:
+    def _native_reid(self, features: Optional[str], reid) -> bool:
+        """Whether the Re-ID rows can come from inside the wrapped detector's tiled call (``detect_tiled_reid``): ``native=True``, a detector with
+        that method, and ``reid`` a loaded ``HipReIDExtractor`` / ``HipOSNetReIDExtractor``."""
+        if not (self.native and features == "reid" and hasattr(self.detector, "detect_tiled_reid")):
+            return False
+        from .reid import _ReIDExtractorBase
+        return isinstance(reid, _ReIDExtractorBase) and reid.is_loaded
+
+    def detect_with_features(self, frame: np.ndarray, features: str = "color", reid=None, reid_slots: int = 32) -> Tuple[List[Detection], np.ndarray]:
         """Merged detections + their (N, 256) colour-histogram rows (``features="reid"``: the (N, 512) rows of ``reid``), assigned to
-        ``det.features``.  ``native=True`` with colour: inside the wrapped detector's one tiled call (``detect_tiled_stages``)."""
+        ``det.features``.  ``native=True`` with colour: inside the wrapped detector's one tiled call (``detect_tiled_stages``); with a loaded
+        ``HipReIDExtractor`` / ``HipOSNetReIDExtractor``: inside ``detect_tiled_reid``, for the first ``reid_slots`` merged records."""
         self._check_features(features, reid, allow_none=False)
+        if self._native_reid(features, reid):
+            grid = self._native_grid([frame])
+            dets = self.detector.detect_tiled_reid([frame], grid, reid, self.nms_threshold, self.merge_threshold, reid_slots=reid_slots)[0]
+            return dets, (np.stack([d.features for d in dets]) if dets else np.array([]))
         if self.native and features == "color":
             grid = self._native_grid([frame], staged=True)   # (refuses a detector without detect_tiled)
             dets = self.detector.detect_tiled_stages([frame], grid, self.nms_threshold, self.merge_threshold, features="color")[0]
@@ -191,10 +204,15 @@ class TiledDetector:
         dets = self.detect(frame)
         return dets, self._host_features(frame, dets, features, reid)
 
-    def detect_and_track(self, frame: np.ndarray, tracker, features: Optional[str] = "color", reid=None) -> List[Detection]:
-        """``detect_with_features(frame)`` then ``tracker.update(detections)``; ``native=True`` (colour rows or motion only): ONE tiled call with
-        one host wait, the merged records and their rows entering ``tracker`` where they lie.  Returns the detections that got an id."""
+    def detect_and_track(self, frame: np.ndarray, tracker, features: Optional[str] = "color", reid=None, reid_slots: int = 32) -> List[Detection]:
+        """``detect_with_features(frame)`` then ``tracker.update(detections)``; ``native=True`` (colour rows, motion only, or the rows of a loaded
+        ``HipReIDExtractor`` / ``HipOSNetReIDExtractor``): ONE tiled call with one host wait, the merged records and their rows entering ``tracker``
+        where they lie.  Returns the detections that got an id."""
         self._check_features(features, reid, allow_none=True)
+        if self._native_reid(features, reid):
+            grid = self._native_grid([frame])
+            dets = self.detector.detect_tiled_reid([frame], grid, reid, self.nms_threshold, self.merge_threshold, reid_slots=reid_slots, trackers=[tracker])[0]
+            return [d for d in dets if d.track_id is not None]
         if self.native and features != "reid":
             grid = self._native_grid([frame], staged=True)
             dets = self.detector.detect_tiled_stages([frame], grid, self.nms_threshold, self.merge_threshold, features=features, trackers=[tracker])[0]
