@@ -704,6 +704,19 @@ typedef struct opd_tile_reid_stages {
 OPD_API int opd_detr_detect_tiled_reid(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw,
                                        int n_tiles, int H, int W, float threshold, const opd_tile_params* p, const opd_tile_reid_stages* stages,
                                        opd_tile_det* out, int32_t* counts);
+/* opd_detr_detect_tiled for a grid whose tiles DIFFER in size (a grid with interior tiles at the default overlap, a frame side that does not
+ * divide): `tile_HW` [n_tiles][2] is the model size of each tile, where the other entries take one H x W.  Each frame is uploaded once; tile t is
+ * resampled from its window to tile_HW[t] into the top-left corner of a canvas of max H x max W with zeros around it (byte for byte the canvas of
+ * opd_detr_detect_ragged's caller: Pillow's resize of contiguous copies of the windows), the forward runs as a ragged batch with
+ * valid_hw = tile_HW (eagerly, as every ragged batch), the boxes of tile t are scaled to ITS window, and the suppression, merge and wait are
+ * those of opd_detr_detect_tiled.  Windows of one size with one model size take that entry's path, with its records byte for byte.
+ * `stages`: NULL, or the colour-feature, floor and track stages on the merged records exactly as in opd_detr_detect_tiled_stages (rows by
+ * position).  Re-ID rows are not offered for such a grid: opd_reid_extract on the merged records is the way.
+ * OPD_EINVAL before any device call: everything opd_detr_detect_tiled (with `stages`: opd_detr_detect_tiled_stages) refuses except windows of
+ * more than one size; NULL `tile_HW`; a model size below 1; a canvas outside the handle's maximum. */
+OPD_API int opd_detr_detect_tiled_ragged(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw,
+                                         int n_tiles, const int32_t* tile_HW, float threshold, const opd_tile_params* p,
+                                         const opd_tile_stages* stages, opd_tile_det* out, int32_t* counts);
 /* The solver of the association on its own (host only): cost [rows][cols] row-major -> row_to_col [rows], -1 for a row left alone;
  * min(rows, cols) pairs of smallest total cost, as scipy.optimize.linear_sum_assignment. */
 OPD_API int opd_assign(const double* cost, int rows, int cols, int32_t* row_to_col);

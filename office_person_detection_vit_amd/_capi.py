@@ -177,6 +177,9 @@ API = {
                                                C.POINTER(OpdTileParams), C.POINTER(OpdTileStages), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
     "opd_detr_detect_tiled_reid": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                              C.POINTER(OpdTileParams), C.POINTER(OpdTileReidStages), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
+    # frames, n_frames, h, w, tiles_yxhw, n_tiles, tile_HW, threshold, params, stages (nullable), out, counts
+    "opd_detr_detect_tiled_ragged": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
+                                               C.POINTER(OpdTileParams), C.POINTER(OpdTileStages), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
     # recs, tile_counts, n_frames, n_tiles, stride, tiles_yxhw, h, w, params, out, counts
     "opd_detr_merge_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
@@ -360,6 +363,8 @@ TEST_API = {
     "opd_test_tile_merge_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                            C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
     "opd_test_tile_resize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # ... and the one for tiles of several sizes: frames, n_frames, h, w, tiles_yxhw, n_tiles, tile_HW, H, W, out (the canvas, read first)
+    "opd_test_tile_resize_ragged": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     # stage kernels of a tiled call on merged records of the caller (csrc/opd_tile_stages_test_api.cpp): device, frames, n_frames, h, w, merged, counts, S,
     # floor, with_rows, color, floor_out, boxes, foot, has, feat, n_out
     "opd_test_tile_stages": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,

@@ -112,6 +112,21 @@ static int enqueue_tiles(opd_detr* m, const FrameSource& src, int H, int W) {
     RCCHK(upload_camera_frames(m, nullptr, static_cast<const uint8_t* const*>(src.frames), src.n_frames, src.h, src.w));
     if (!m->d_tiles) RCCHK(dalloc(m, &m->d_tiles, (size_t)m->cfg.max_batch * 4, false));
     RCCHK(upload_if_changed(m, std::vector<int32_t>(src.tiles, src.tiles + (size_t)src.n_tiles * 4), &m->h_tiles, m->d_tiles));
+    if (src.tile_HW) {   // tiles of several sizes: a descriptor per tile, with the tables of its own (th, tw, oh, ow); the canvas of a ragged batch
+        std::vector<int32_t> desc((size_t)src.n_tiles * (sizeof(TileRaggedDesc) / 4));
+        for (int t = 0; t < src.n_tiles; ++t) {
+            const int32_t* g = src.tiles + 4 * t;
+            const opd_detr::ResizeTab* tab = nullptr;
+            RCCHK(resize_tab(m, g[2], g[3], src.tile_HW[2 * t], src.tile_HW[2 * t + 1], &tab));
+            // (copied out at once: the next tile's lookup may grow the vector `tab` points into)
+            const TileRaggedDesc d{g[0], g[1], g[2], g[3], tab->oh, tab->ow, tab->ksh, tab->ksv, tab->bh, tab->kh, tab->bv, tab->kv};
+            memcpy(desc.data() + (size_t)t * (sizeof d / 4), &d, sizeof d);
+        }
+        if (!m->d_tile_desc) RCCHK(dalloc(m, &m->d_tile_desc, (size_t)m->cfg.max_batch * (sizeof(TileRaggedDesc) / 4), false));
+        RCCHK(upload_if_changed(m, desc, &m->h_tile_desc, m->d_tile_desc));
+        TileRaggedParams rp{m->src.dev, m->d_u8, reinterpret_cast<const TileRaggedDesc*>(m->d_tile_desc), src.n_frames, src.n_tiles, src.h, src.w, H, W};
+        return launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_tile_resize_ragged_u8(rp, m->stream); });
+    }
     const int th = src.box_h(), tw = src.box_w();
     const opd_detr::ResizeTab* tab = nullptr;
     RCCHK(resize_tab(m, th, tw, H, W, &tab));
@@ -697,9 +712,11 @@ int opd_detr_nms_records(opd_detr* m, opd_det* dets, int32_t* counts, int n_fram
 }); }
 // Tiled detection: every refusal comes before the first device call (check_tiles; check_shape makes none for host pixels).  `st` (null: opd_detr_detect_tiled
 // itself): the feature, floor and track parts of the sink, which then read the merged records where the merge left them, rows by position.  `rs`
-// (opd_detr_detect_tiled_reid; `st` is then null): the same with the Re-ID rows as the feature kind, rows by slot, a slot naming a position
+// (opd_detr_detect_tiled_reid; `st` is then null): the same with the Re-ID rows as the feature kind, rows by slot, a slot naming a position.
+// `mixed` (opd_detr_detect_tiled_ragged): the windows may differ in size, `tile_HW` [n_tiles][2] is the model size of each and H x W, not read as given, the
+// canvas that holds them all; windows of one size with one model size take the path of the other entries, launch for launch
 static int detect_tiled(const std::string& me, opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W,
-                        float threshold, const opd_tile_params* p, const opd_tile_stages* st, const opd_tile_reid_stages* rs, opd_tile_det* out, int32_t* counts) {
+                        const int32_t* tile_HW, bool mixed, float threshold, const opd_tile_params* p, const opd_tile_stages* st, const opd_tile_reid_stages* rs, opd_tile_det* out, int32_t* counts) {
     if (!frames || !out || !counts) return fail(OPD_EINVAL, me + ": null argument");
     opd_tile_stages of_reid{};   // the floor and track parts of the Re-ID entry's block, as the checks below read them
     if (rs) {   // (opd_detr_detect_tiled_reid: `st` is null)
@@ -720,8 +737,19 @@ static int detect_tiled(const std::string& me, opd_detr* m, const uint8_t* const
         if (st->floor && !st->floor_out) return fail(OPD_EINVAL, me + ": floor_out is null while a floor-map handle is given");
         if (st->trackers && (!st->track_ids || !st->n_featured)) return fail(OPD_EINVAL, me + ": track_ids or n_featured is null while trackers are given");
     }
-    RCCHK(check_tiles(me, p, tiles_yxhw, n_tiles, h, w, true));
+    RCCHK(check_tiles(me, p, tiles_yxhw, n_tiles, h, w, !mixed));
     if (!(p->tile_nms_threshold >= 0.f)) return fail(OPD_EINVAL, me + ": tile_nms_threshold is negative or NaN");
+    bool one_size = true;   // one window size and one model size: the canvas is every tile's
+    if (mixed) {
+        if (!tile_HW) return fail(OPD_EINVAL, me + ": null argument (tile_HW)");
+        H = W = 0;
+        for (int t = 0; t < n_tiles; ++t) {
+            if (tile_HW[2 * t] < 1 || tile_HW[2 * t + 1] < 1)
+                return fail(OPD_EINVAL, me + ": tile " + std::to_string(t) + " has the model size " + std::to_string(tile_HW[2 * t]) + " x " + std::to_string(tile_HW[2 * t + 1]) + ", below 1");
+            H = std::max(H, (int)tile_HW[2 * t]); W = std::max(W, (int)tile_HW[2 * t + 1]);
+            one_size = one_size && tile_HW[2 * t] == tile_HW[0] && tile_HW[2 * t + 1] == tile_HW[1] && tiles_yxhw[4 * t + 2] == tiles_yxhw[2] && tiles_yxhw[4 * t + 3] == tiles_yxhw[3];
+        }
+    }
     if (color && (h > OPD_COLOR_MAX_EDGE || w > OPD_COLOR_MAX_EDGE))
         return fail(OPD_EINVAL, me + ": feature_kind OPD_TRACK_FEAT_COLOR on frames of " + std::to_string(h) + " x " + std::to_string(w) +
                                      ", outside the 4096 x 4096 the exact integer sums of the colour histogram are sized for");
@@ -735,7 +763,16 @@ static int detect_tiled(const std::string& me, opd_detr* m, const uint8_t* const
     RCCHK(check_shape(m, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, n_frames * n_tiles, H, W));
     FrameSource src{SRC_TILES, frames, OPD_PIXELS_U8_BGR_HWC, OPD_MEM_HOST, h, w};
     src.n_frames = n_frames; src.n_tiles = n_tiles; src.tiles = tiles_yxhw;
-    RecordSink sink(threshold, nullptr, nullptr, nullptr, OPD_MEM_HOST);   // (boxes in TILE pixels; the merge puts them on the frame)
+    std::vector<int32_t> valid_hw, window_hw;   // tiles of several sizes, [B][2]: image b's model size inside the canvas; its window, which its boxes are scaled to
+    if (!one_size) {
+        src.tile_HW = tile_HW;
+        for (int b = 0; b < n_frames * n_tiles; ++b) {
+            const int t = b % n_tiles;
+            valid_hw.insert(valid_hw.end(), {tile_HW[2 * t], tile_HW[2 * t + 1]});
+            window_hw.insert(window_hw.end(), {tiles_yxhw[4 * t + 2], tiles_yxhw[4 * t + 3]});
+        }
+    }
+    RecordSink sink(threshold, one_size ? nullptr : window_hw.data(), nullptr, nullptr, OPD_MEM_HOST);   // (boxes in TILE pixels; the merge puts them on the frame)
     sink.tile.params = p; sink.tile.n_frames = n_frames; sink.tile.n_tiles = n_tiles; sink.tile.frame_h = h; sink.tile.frame_w = w;
     sink.tile.out = out; sink.tile.counts = counts; sink.tile.entry = me.c_str();
     if (st) {   // the stages' own refusals that need the handle, then their parts of the sink
@@ -766,24 +803,30 @@ static int detect_tiled(const std::string& me, opd_detr* m, const uint8_t* const
         sink.track.trackers = st->trackers; sink.track.track_ids = st->track_ids; sink.track.n_featured = st->n_featured;
     }
     HIPCHK(hipSetDevice(m->device));
-    return detect_pipeline(m, src, n_frames * n_tiles, H, W, nullptr, sink);
+    return detect_pipeline(m, src, n_frames * n_tiles, H, W, one_size ? nullptr : valid_hw.data(), sink);
 }
 int opd_detr_detect_tiled(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W, float threshold,
                           const opd_tile_params* p, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled", [&]() -> int {
-    return detect_tiled("opd_detr_detect_tiled", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, nullptr, nullptr, out, counts);
+    return detect_tiled("opd_detr_detect_tiled", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, nullptr, false, threshold, p, nullptr, nullptr, out, counts);
 }); }
 // ... with the feature, floor and track stages on the merged records, in front of the same one wait
 int opd_detr_detect_tiled_stages(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W, float threshold,
                                  const opd_tile_params* p, const opd_tile_stages* stages, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled_stages", [&]() -> int {
     if (!stages) return fail(OPD_EINVAL, "opd_detr_detect_tiled_stages: null argument (stages)");
-    return detect_tiled("opd_detr_detect_tiled_stages", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, stages, nullptr, out, counts);
+    return detect_tiled("opd_detr_detect_tiled_stages", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, nullptr, false, threshold, p, stages, nullptr, out, counts);
 }); }
 // ... with the Re-ID rows of the merged records instead: crops planned on the device from the merged records, cut from the whole frames in m->src, the
 // forward on the Re-ID handle's stream between two events, rows by slot into the caller's array and / or the trackers
 int opd_detr_detect_tiled_reid(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W, float threshold,
                                const opd_tile_params* p, const opd_tile_reid_stages* stages, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled_reid", [&]() -> int {
     if (!stages) return fail(OPD_EINVAL, "opd_detr_detect_tiled_reid: null argument (stages)");
-    return detect_tiled("opd_detr_detect_tiled_reid", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, threshold, p, nullptr, stages, out, counts);
+    return detect_tiled("opd_detr_detect_tiled_reid", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, nullptr, false, threshold, p, nullptr, stages, out, counts);
+}); }
+// ... for a grid whose tiles differ in size: every tile at the model size of its own inside one canvas, a ragged batch; `stages` as in
+// opd_detr_detect_tiled_stages, or null
+int opd_detr_detect_tiled_ragged(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, const int32_t* tile_HW,
+                                 float threshold, const opd_tile_params* p, const opd_tile_stages* stages, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled_ragged", [&]() -> int {
+    return detect_tiled("opd_detr_detect_tiled_ragged", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, 0, 0, tile_HW, true, threshold, p, stages, nullptr, out, counts);
 }); }
 int opd_detr_merge_tiles(opd_detr* m, const opd_det* recs, const int32_t* tile_counts, int n_frames, int n_tiles, int stride, const int32_t* tiles_yxhw, int h, int w,
                          const opd_tile_params* p, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_merge_tiles", [&]() -> int {

@@ -317,6 +317,8 @@ struct opd_detr : DetrWeights {
     // max_batch x queries candidates] and its page-locked twin (ensure_tile_out)
     int32_t* d_tiles = nullptr;
     std::vector<int32_t> h_tiles;
+    int32_t* d_tile_desc = nullptr;      // tiles of several sizes: [max_batch] TileRaggedDesc (opd_tile.h) as 16 int32 words each, and what was uploaded last
+    std::vector<int32_t> h_tile_desc;
     char* d_tile_out = nullptr;
     void* tile_pinned = nullptr;
 
@@ -426,11 +428,13 @@ struct FrameSource {
                                   // SRC_TILES: such a list of n_frames whole frames; the batch is the n_tiles windows of each, resized
     int pixel_format, mem_kind;   // (where the frames lie)
     int h, w;                     // camera resolution (SRC_PIXELS: unused)
-    int n_frames = 0, n_tiles = 0;    // SRC_TILES: B = n_frames x n_tiles windows `tiles` [n_tiles][4] = y0, x0, th, tw (host), all of one size
+    int n_frames = 0, n_tiles = 0;    // SRC_TILES: B = n_frames x n_tiles windows `tiles` [n_tiles][4] = y0, x0, th, tw (host), all of one size unless `tile_HW` is set
     const int32_t* tiles = nullptr;
-    // the size the post-process scales the boxes to: the camera frame, a tile's window; 0: none of its own
-    int box_h() const { return kind == SRC_PIXELS ? 0 : kind == SRC_TILES ? tiles[2] : h; }
-    int box_w() const { return kind == SRC_PIXELS ? 0 : kind == SRC_TILES ? tiles[3] : w; }
+    const int32_t* tile_HW = nullptr; // SRC_TILES, nullable: [n_tiles][2] the model size of each tile inside the H x W canvas (windows and sizes may then differ: the
+                                      // batch is ragged, valid_hw[b] = tile_HW[b % n_tiles], and the sink's orig_hw names each tile's window)
+    // the size the post-process scales the boxes to: the camera frame, a tile's window; 0: none of its own (tiles of several sizes: the sink's orig_hw has them)
+    int box_h() const { return kind == SRC_PIXELS || tile_HW ? 0 : kind == SRC_TILES ? tiles[2] : h; }
+    int box_w() const { return kind == SRC_PIXELS || tile_HW ? 0 : kind == SRC_TILES ? tiles[3] : w; }
 };
 enum { WAIT_BLOCKING, WAIT_TICKET, WAIT_NONE };   // fetch the records and wait / hand them to async slot `ticket` (opd_detr_wait) / leave them on the stream
 enum { FEAT_NONE, FEAT_ROI, FEAT_COLOR, FEAT_REID };   // nothing / ROI pooling on the records / their colour histograms / the Re-ID model's rows (opd_reid.h: ReidFusedCall)

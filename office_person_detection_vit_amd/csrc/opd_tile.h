@@ -212,6 +212,22 @@ struct TileResizeParams {
     int ksize_h, ksize_v;
 };
 hipError_t opd_launch_tile_resize_u8(const TileResizeParams& p, hipStream_t stream);
+// The same for tiles that differ in size: batch image b = frame * n_tiles + tile has the descriptor desc[tile] (device memory, 64 bytes: it travels
+// as 16 int32 words) and writes out[b][H][W][3], the canvas of a ragged batch: the resize of its window to oh x ow in the top-left corner, 0 elsewhere.
+// The caller has checked that every window lies inside the frame, that 1 <= oh <= H and 1 <= ow <= W, and that the tables are opd_resize_coeffs(tw, ow)
+// and opd_resize_coeffs(th, oh).
+struct TileRaggedDesc {
+    int32_t y0, x0, th, tw, oh, ow, ksize_h, ksize_v;
+    const int32_t *bounds_h, *coeff_h, *bounds_v, *coeff_v;   // device
+};
+static_assert(sizeof(TileRaggedDesc) == 64, "TileRaggedDesc is uploaded as 16 int32 words");
+struct TileRaggedParams {
+    const uint8_t* frames;
+    uint8_t* out;
+    const TileRaggedDesc* desc;   // device, [n_tiles]
+    int n_frames, n_tiles, frame_h, frame_w, H, W;
+};
+hipError_t opd_launch_tile_resize_ragged_u8(const TileRaggedParams& p, hipStream_t stream);
 #endif
 
 }  // namespace opd

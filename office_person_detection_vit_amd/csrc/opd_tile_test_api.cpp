@@ -3,6 +3,8 @@
 //                              list: opd_detr_merge_tiles's arguments and conventions without a handle and without a HIP call, so that a
 //                              machine without a GPU can hold the rule to tiling.merge_tile_detections.  (Compiled with -ffp-contract=off.)
 //   opd_test_tile_resize       tile_resize_u8_kernel alone: host frames [n_frames][h][w][3] and windows of one size -> [n_frames * n_tiles][oh][ow][3]
+//   opd_test_tile_resize_ragged  tile_resize_ragged_u8_kernel alone: windows of any sizes, tile t to tile_HW[t] inside an H x W canvas ->
+//                              [n_frames * n_tiles][H][W][3] into the caller's array, which is uploaded first (a byte the kernel leaves out keeps its value)
 #include <memory>
 
 #include "opd_test_util.h"
@@ -53,6 +55,32 @@ TAPI int opd_test_tile_resize(const uint8_t* frames, int n_frames, int h, int w,
                         dm.up(bh.data(), bh.size()), dm.up(kh.data(), kh.size()), dm.up(bv.data(), bv.size()), dm.up(kv.data(), kv.size()), ksh, ksv};
     if (!dm.ok) return fail(OPD_ENOMEM, "opd_test_tile_resize: device allocation failed");
     HIPCHK(opd_launch_tile_resize_u8(rp, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    return down(out, rp.out, n_out);
+}
+
+TAPI int opd_test_tile_resize_ragged(const uint8_t* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, const int32_t* tile_HW, int H, int W,
+                                     uint8_t* out) {
+    RCCHK(check_windows("opd_test_tile_resize_ragged", tiles_yxhw, n_tiles, h, w));
+    if (!frames || !out || !tile_HW || n_frames < 1 || H < 1 || W < 1) return fail(OPD_EINVAL, "opd_test_tile_resize_ragged: bad arguments");
+    for (int t = 0; t < n_tiles; ++t)
+        if (tile_HW[2 * t] < 1 || tile_HW[2 * t] > H || tile_HW[2 * t + 1] < 1 || tile_HW[2 * t + 1] > W)
+            return fail(OPD_EINVAL, "opd_test_tile_resize_ragged: a tile's output size lies outside the canvas");
+    DevMem dm;
+    std::vector<TileRaggedDesc> desc((size_t)n_tiles);
+    for (int t = 0; t < n_tiles; ++t) {
+        const int32_t* g = tiles_yxhw + 4 * t;
+        std::vector<int32_t> bh, kh, bv, kv;
+        int ksh = 0, ksv = 0;
+        opd_resize_coeffs(g[3], tile_HW[2 * t + 1], &bh, &kh, &ksh);
+        opd_resize_coeffs(g[2], tile_HW[2 * t], &bv, &kv, &ksv);
+        desc[t] = TileRaggedDesc{g[0], g[1], g[2], g[3], tile_HW[2 * t], tile_HW[2 * t + 1], ksh, ksv,
+                                 dm.up(bh.data(), bh.size()), dm.up(kh.data(), kh.size()), dm.up(bv.data(), bv.size()), dm.up(kv.data(), kv.size())};
+    }
+    const size_t n_out = (size_t)n_frames * n_tiles * H * W * 3;
+    TileRaggedParams rp{dm.up(frames, (size_t)n_frames * h * w * 3), dm.up(out, n_out), dm.up(desc.data(), desc.size()), n_frames, n_tiles, h, w, H, W};
+    if (!dm.ok) return fail(OPD_ENOMEM, "opd_test_tile_resize_ragged: device allocation failed");
+    HIPCHK(opd_launch_tile_resize_ragged_u8(rp, nullptr));
     HIPCHK(hipDeviceSynchronize());
     return down(out, rp.out, n_out);
 }

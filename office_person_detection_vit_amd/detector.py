@@ -587,6 +587,18 @@ class HipDetrDetector:
                 if trackers is not None:
                     trackers[b].update(dets)
             return out
+        return self._tiled_staged_chunks("opd_detr_detect_tiled_stages", (H, W), frames, tiles, nms_threshold, merge_threshold, edge_tolerance, features, floor_map, trackers)
+
+    def _tiled_staged_chunks(self, entry: str, sizes: tuple, frames, tiles, nms_threshold: float, merge_threshold: float, edge_tolerance: float,
+                             features: Optional[str], floor_map, trackers, staged: bool = True) -> List[List[Detection]]:
+        """The calls of ``detect_tiled_stages`` and ``detect_tiled_ragged``, a chunk of ``max_batch // len(tiles)`` checked frames each: ``entry``
+        with ``sizes`` where the model size goes (``(H, W)``, or ``(tile_HW,)`` as a pointer), the stages block filled from ``features``,
+        ``floor_map`` and ``trackers`` (``staged=False``: a null block, ``opd_detr_detect_tiled_ragged`` alone takes one), and the records,
+        rows by position, made into detections."""
+        h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
+        T = len(tiles)
+        S = T * self._info.num_queries
+        call = getattr(self._lib, entry)
         win = np.asarray(tiles, dtype=np.int32).reshape(T, 4)
         params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
                                      merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
@@ -598,26 +610,27 @@ class HipDetrDetector:
                 n = len(chunk)
                 recs, counts = (_capi.OpdTileDet * (n * S))(), (C.c_int32 * n)()
                 ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in chunk])
-                args = (C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, H, W, float(self.confidence_threshold), C.byref(params))
+                args = (C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, *sizes, float(self.confidence_threshold), C.byref(params))
                 # the feature, floor and track stages on the merged records, rows by position: row b * S + k of record k of frame b
-                feats = floor = ids = None
-                st = _capi.OpdTileStages(struct_size=C.sizeof(_capi.OpdTileStages),
-                                         feature_kind=_capi.OPD_TRACK_FEAT_COLOR if features == "color" else _capi.OPD_TRACK_FEAT_NONE)
-                if features == "color" and trackers is None:
-                    feats = np.empty((n, S, 256), np.float32)
-                    st.features = feats.ctypes.data
-                if floor_map is not None:
-                    floor = np.zeros(n * S, floor_map.REC_DTYPE)
-                    st.floor, st.floor_out = floor_map._require().value, floor.ctypes.data
-                if trackers is not None:
-                    for t in trackers[i:i + n]:
-                        t._ensure()
-                    handles = (C.c_void_p * n)(*[t._h.value for t in trackers[i:i + n]])
-                    ids, n_featured = np.full(n * S, -1, np.int32), np.zeros(n, np.int32)
-                    st.trackers, st.track_ids, st.n_featured = C.addressof(handles), ids.ctypes.data, n_featured.ctypes.data
-                rc = self._lib.opd_detr_detect_tiled_stages(*args, C.byref(st), recs, counts)
+                feats = floor = ids = st = None
+                if staged:
+                    st = _capi.OpdTileStages(struct_size=C.sizeof(_capi.OpdTileStages),
+                                             feature_kind=_capi.OPD_TRACK_FEAT_COLOR if features == "color" else _capi.OPD_TRACK_FEAT_NONE)
+                    if features == "color" and trackers is None:
+                        feats = np.empty((n, S, 256), np.float32)
+                        st.features = feats.ctypes.data
+                    if floor_map is not None:
+                        floor = np.zeros(n * S, floor_map.REC_DTYPE)
+                        st.floor, st.floor_out = floor_map._require().value, floor.ctypes.data
+                    if trackers is not None:
+                        for t in trackers[i:i + n]:
+                            t._ensure()
+                        handles = (C.c_void_p * n)(*[t._h.value for t in trackers[i:i + n]])
+                        ids, n_featured = np.full(n * S, -1, np.int32), np.zeros(n, np.int32)
+                        st.trackers, st.track_ids, st.n_featured = C.addressof(handles), ids.ctypes.data, n_featured.ctypes.data
+                rc = call(*args, C.byref(st) if st is not None else None, recs, counts)
                 if not (rc != 0 and trackers is not None and "counted as one without detections" in _capi.last_error()):
-                    _capi.check(rc, "opd_detr_detect_tiled_stages")   # (out of slots: records, rows and ids were delivered; the mirrors follow first)
+                    _capi.check(rc, entry)   # (out of slots: records, rows and ids were delivered; the mirrors follow first)
                 message = _capi.last_error() if rc != 0 else ""
                 for b in range(n):
                     dets = []
@@ -635,12 +648,74 @@ class HipDetrDetector:
                         trackers[i + b]._apply(dets, ids[b * S:b * S + cnt])
                     out.append(dets)
                 if rc != 0:
-                    raise RuntimeError(f"opd_detr_detect_tiled_stages failed (code {rc}): {message}")
+                    raise RuntimeError(f"{entry} failed (code {rc}): {message}")
             self._last_orig = [(h, w)] * len(frames)
             return out
         except Exception as e:
             logger.error(f"Detection failed: {e}")
             raise
+
+    def tile_model_sizes(self, tiles: Sequence[Tuple[int, int, int, int]]) -> List[Tuple[int, int]]:
+        """The model size (H, W) of each ``(y0, x0, h, w)`` tile: ``model_input_size`` of its window under ``max_size``, the window itself with
+        ``resize=False`` -- what ``detect_batch`` gives contiguous copies of the tiles."""
+        return [model_input_size(int(t[2]), int(t[3]), self.max_size[0], self.max_size[1]) if self.resize else (int(t[2]), int(t[3])) for t in tiles]
+
+    def detect_tiled_ragged(self, frames: Sequence[np.ndarray], tiles: Sequence[Tuple[int, int, int, int]], nms_threshold: float = 0.4,
+                            merge_threshold: float = 0.5, edge_tolerance: float = 0.01, features: Optional[str] = None, floor_map=None,
+                            trackers=None) -> List[List[Detection]]:
+        """``detect_tiled`` / ``detect_tiled_stages`` for ``tiles`` that DIFFER in size (``opd_detr_detect_tiled_ragged``): a grid with interior
+        tiles at the default overlap (2 x 3, 3 x 3, ...) or a frame side that does not divide.  Every tile gets the model size ``detect_batch``
+        would give a contiguous copy of it (``tile_model_sizes``); the device resamples each window to that size into one zero-padded canvas,
+        the forward runs as a ragged batch, and suppression, merge and the stages run as in the other tiled calls, behind one host wait.  The
+        lists are those of ``TiledDetector(native=False)``, field for field.  Frames go in chunks of ``max_batch // len(tiles)``.
+        ``features`` (``None`` or ``"color"``), ``floor_map`` and ``trackers`` as in ``detect_tiled_stages``, with the same fallback to the
+        separate calls where the fused conditions fail.  Re-ID rows inside the call are not offered for such a grid."""
+        self._require_model()
+        frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
+        if features not in (None, "color"):
+            if features == "encoder":
+                raise ValueError("features='encoder' does not exist for tiled detection: a box merged from two tiles' maps has no encoder row")
+            raise ValueError(f"features must be None or 'color', got {features!r}")
+        if trackers is not None:
+            trackers = list(trackers)
+            if len(trackers) != len(frames):
+                raise ValueError(f"{len(trackers)} trackers for {len(frames)} frames: frame f enters trackers[f]")
+            if len({id(t) for t in trackers}) != len(trackers):
+                raise ValueError("a tracker is named twice: a tracker takes one frame per call")
+        if not tiles or any(len(t) != 4 for t in tiles):
+            raise ValueError("tiles must be a non-empty list of (y0, x0, h, w)")
+        if len(tiles) > self.max_batch:
+            raise ValueError(f"the {len(tiles)} tiles of one frame exceed max_batch = {self.max_batch}")
+        if any(t[2] < 1 or t[3] < 1 for t in tiles):
+            raise ValueError("tiles must have a height and a width of at least 1")
+        if len(frames) == 0:
+            return []
+        f0 = frames[0]
+        for f in frames:
+            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != f0.shape or not f.flags.c_contiguous:
+                raise ValueError("frames must be contiguous uint8 numpy arrays of shape (H, W, 3) in BGR order, all of one size")
+        h, w = int(f0.shape[0]), int(f0.shape[1])
+        sizes = self.tile_model_sizes(tiles)
+        H, W = max(s[0] for s in sizes), max(s[1] for s in sizes)
+        if max(H, W) > max(self.max_size) or H * W > self.max_size[0] * self.max_size[1]:
+            raise ValueError(f"ragged batch canvas {H}x{W} exceeds the configured maximum {self.max_size} (either orientation)")
+        T, Q = len(tiles), self._info.num_queries
+        S = T * Q
+        staged = not (features is None and floor_map is None and trackers is None)
+        if staged and not self._tiled_stages_fused(h, w, S, features, floor_map, trackers):
+            out = self.detect_tiled_ragged(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
+            for b, dets in enumerate(out):
+                if features == "color":
+                    for det, row in zip(dets, self.extract_color_features(frames[b], dets)):
+                        det.features = row
+                if floor_map is not None:
+                    floor_map.apply(dets)
+                if trackers is not None:
+                    trackers[b].update(dets)
+            return out
+        tile_hw = np.asarray(sizes, dtype=np.int32).reshape(T, 2)
+        return self._tiled_staged_chunks("opd_detr_detect_tiled_ragged", (tile_hw.ctypes.data_as(C.c_void_p),), frames, tiles, nms_threshold, merge_threshold, edge_tolerance,
+                                         features, floor_map, trackers, staged=staged)
 
     def _tiled_stages_fused(self, h: int, w: int, S: int, features: Optional[str], floor_map, trackers) -> bool:
         """Whether the stages of a tiled call can run inside it (``detect_tiled`` has the conditions)."""

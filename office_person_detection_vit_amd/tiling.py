@@ -116,12 +116,17 @@ class TiledDetector:
 
     ``native=True``: a frame is ONE call of the wrapped detector's ``detect_tiled`` (``HipDetrDetector``: the frame is uploaded once, its
     tiles are cut and resampled on the device and the merge below runs there in a kernel, the same lists field for field); a wrapped
-    detector without ``detect_tiled`` is refused, there is no silent fallback to the host path."""
+    detector without ``detect_tiled`` is refused, there is no silent fallback to the host path.
+
+    ``mixed_sizes=True`` (with ``native=True``): a grid whose tiles differ in size (interior tiles at the default overlap: 2 x 3, 3 x 3, ...; a
+    frame side that does not divide) goes through the wrapped detector's ``detect_tiled_ragged`` instead of being refused: every tile at its
+    own model size inside one canvas, one ragged forward, the same lists field for field.  A grid of one size takes the calls it always took.
+    ``features="reid"`` on such a grid runs the Re-ID rows as a separate call on the merged detections."""
 
     def __init__(self, detector, rows: int = 2, cols: int = 2, nms_threshold: float = 0.4, overlap: float = DEFAULT_OVERLAP,
-                 merge_threshold: float = 0.5, native: bool = False):
+                 merge_threshold: float = 0.5, native: bool = False, mixed_sizes: bool = False):
         self.detector, self.rows, self.cols, self.nms_threshold = detector, rows, cols, nms_threshold
-        self.overlap, self.merge_threshold, self.native = overlap, merge_threshold, bool(native)
+        self.overlap, self.merge_threshold, self.native, self.mixed_sizes = overlap, merge_threshold, bool(native), bool(mixed_sizes)
 
     def _need_detect_tiled(self, staged: bool = False) -> None:
         if not hasattr(self.detector, "detect_tiled") or (staged and not hasattr(self.detector, "detect_tiled_stages")):
@@ -134,6 +139,15 @@ class TiledDetector:
             raise ValueError("native=True takes frames of one size")
         return tile_grid(frames[0].shape[0], frames[0].shape[1], self.rows, self.cols, self.overlap)
 
+    def _mixed(self, grid) -> bool:
+        """Whether ``grid`` goes through ``detect_tiled_ragged``: ``mixed_sizes=True`` and tiles of more than one size (without the keyword the
+        wrapped detector's calls refuse such a grid, as they always did)."""
+        if not self.mixed_sizes or len({(t[2], t[3]) for t in grid}) == 1:
+            return False
+        if not hasattr(self.detector, "detect_tiled_ragged"):
+            raise ValueError(f"mixed_sizes=True needs a detector with detect_tiled_ragged (a HipDetrDetector); {type(self.detector).__name__} has none")
+        return True
+
     def detect_batch(self, frames: Sequence[np.ndarray], floor_map=None) -> List[List[Detection]]:
         """``floor_map``: a ``HipFloorMapper``; the merged detections come back with its four fields filled (``native=True``: inside the call)."""
         if self.native:
@@ -141,6 +155,8 @@ class TiledDetector:
             if len(frames) == 0:
                 return []
             grid = self._native_grid(frames)
+            if self._mixed(grid):
+                return self.detector.detect_tiled_ragged(frames, grid, self.nms_threshold, self.merge_threshold, floor_map=floor_map)
             if floor_map is None:
                 return self.detector.detect_tiled(frames, grid, self.nms_threshold, self.merge_threshold)
             self._need_detect_tiled(staged=True)
@@ -193,13 +209,14 @@ class TiledDetector:
         ``det.features``.  ``native=True`` with colour: inside the wrapped detector's one tiled call (``detect_tiled_stages``); with a loaded
         ``HipReIDExtractor`` / ``HipOSNetReIDExtractor``: inside ``detect_tiled_reid``, for the first ``reid_slots`` merged records."""
         self._check_features(features, reid, allow_none=False)
-        if self._native_reid(features, reid):
+        if self._native_reid(features, reid) and not self._mixed(self._native_grid([frame])):
             grid = self._native_grid([frame])
             dets = self.detector.detect_tiled_reid([frame], grid, reid, self.nms_threshold, self.merge_threshold, reid_slots=reid_slots)[0]
             return dets, (np.stack([d.features for d in dets]) if dets else np.array([]))
         if self.native and features == "color":
             grid = self._native_grid([frame], staged=True)   # (refuses a detector without detect_tiled)
-            dets = self.detector.detect_tiled_stages([frame], grid, self.nms_threshold, self.merge_threshold, features="color")[0]
+            call = self.detector.detect_tiled_ragged if self._mixed(grid) else self.detector.detect_tiled_stages
+            dets = call([frame], grid, self.nms_threshold, self.merge_threshold, features="color")[0]
             return dets, (np.stack([d.features for d in dets]) if dets else np.array([]))
         dets = self.detect(frame)
         return dets, self._host_features(frame, dets, features, reid)
@@ -209,13 +226,14 @@ class TiledDetector:
         ``HipReIDExtractor`` / ``HipOSNetReIDExtractor``): ONE tiled call with one host wait, the merged records and their rows entering ``tracker``
         where they lie.  Returns the detections that got an id."""
         self._check_features(features, reid, allow_none=True)
-        if self._native_reid(features, reid):
+        if self._native_reid(features, reid) and not self._mixed(self._native_grid([frame])):
             grid = self._native_grid([frame])
             dets = self.detector.detect_tiled_reid([frame], grid, reid, self.nms_threshold, self.merge_threshold, reid_slots=reid_slots, trackers=[tracker])[0]
             return [d for d in dets if d.track_id is not None]
         if self.native and features != "reid":
             grid = self._native_grid([frame], staged=True)
-            dets = self.detector.detect_tiled_stages([frame], grid, self.nms_threshold, self.merge_threshold, features=features, trackers=[tracker])[0]
+            call = self.detector.detect_tiled_ragged if self._mixed(grid) else self.detector.detect_tiled_stages
+            dets = call([frame], grid, self.nms_threshold, self.merge_threshold, features=features, trackers=[tracker])[0]
             return [d for d in dets if d.track_id is not None]
         dets = self.detect(frame)
         self._host_features(frame, dets, features, reid)
