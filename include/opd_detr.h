@@ -781,6 +781,48 @@ OPD_API int opd_lwt_update(opd_lwt* t, const uint8_t* bgr, int mem_kind, int h, 
 /* `interpolate`: recs_out [capacity] host, *count records, one per live track in creation order (OPD_EINVAL when capacity is smaller;
  * *count then says how many there are). */
 OPD_API int opd_lwt_interpolate(opd_lwt* t, const uint8_t* bgr, int mem_kind, int h, int w, opd_lwt_rec* recs_out, int capacity, int* count);
+/* F calls of opd_lwt_interpolate on frames[0 .. F) behind ONE host wait: records, states, ids and the counts of opd_lwt_info afterwards
+ * are those of the per-frame loop, bit for bit.  recs_out [F][capacity] host and counts [F]: frame f's records at recs_out + f * capacity,
+ * counts[f] of them (the number of live tracks, the same for every frame).  Per frame, on the handle's stream: gray, pyramid, LK and the
+ * track kernel; the two pyramids alternate, the LK launches are sized for the points held at entry while the device-resident count decides
+ * which of their waves work, and all records travel in one download.  All frames have the size h x w and the same mem_kind; host frames are
+ * uploaded from where they lie and must stay unchanged until the call returns.  Without optical flow no frame is read and `frames` may be
+ * NULL.  As in the per-frame call, a handle that holds no points at entry reads no frame either.  OPD_EINVAL before any device work: F
+ * outside 1 .. 64; capacity below the handle's max_tracks; whatever opd_lwt_interpolate refuses for one of the frames. */
+OPD_API int opd_lwt_interpolate_sequence(opd_lwt* t, const uint8_t* const* frames, int mem_kind, int F, int h, int w, opd_lwt_rec* recs_out,
+                                         int capacity, int32_t* counts);
+/* A detection frame of the hybrid tracker INSIDE the detect call: opd_detr_detect_frames (suppression on) followed, per frame b, by
+ * opd_lwt_update(trackers[b], frames[b], the kept records' boxes), with ONE host wait for all of it and bit for bit the same ids, track
+ * states, flow points and reference frame.  B distinct handles, one camera each.  Behind the suppression, per tracker, on the detector's
+ * stream: an ingest launch writes the kept records as the float32 xywh boxes the per-frame path hands over (corners as they are, width
+ * and height as differences in double, rounded once) and leaves their count on the device; gray and pyramid are built from the
+ * camera-resolution frame where the detector's source step put it (no second upload); the update kernel reads the count on the device.
+ * The ids and every tracker's head travel in the call's one fetch.  out / counts: as from opd_detr_detect_frames.  track_ids
+ * [B][num_queries]: the id of kept record i of frame b at [b][i]; entries at i >= counts[b] are not written.  No feature rows.
+ * OPD_EINVAL before any device work: a null handle or output; opd_detr_set_nms off on `m`, or on for another label; a tracker named
+ * twice, on another device, or made with max_dets < num_queries; with optical flow, a frame larger than a tracker was made for; whatever
+ * opd_detr_detect_frames refuses.  New tracks that do not fit (as under opd_lwt_update): that tracker's state, points and reference
+ * frame are as before and its ids are all -1; records and counts are delivered, the other trackers are committed, and the call returns
+ * OPD_EINVAL.  The trackers' last_waits is 0 afterwards: the wait is the detector's. */
+OPD_API int opd_detr_detect_frames_hybrid(opd_detr* m, opd_lwt* const* trackers, const uint8_t* const* frames, int B, int h, int w, int H,
+                                          int W, float threshold, int label, opd_det* out, int32_t* counts, int32_t* track_ids);
+/* A run of F consecutive frames of ONE camera, key frames (is_key[f] != 0: detection frames) and in-between frames, with ONE host wait:
+ * what the per-frame loop of opd_detr_detect_frames + opd_lwt_update on the key frames and opd_lwt_interpolate on the others gives, bit for
+ * bit.  The K key frames (K <= max_batch; K = 0 is opd_lwt_interpolate_sequence and runs no forward) go through ONE batched forward,
+ * suppression included.  Then, in frame order on the detector's stream: a key frame runs ingest, gray + pyramid and the update; an
+ * in-between frame is uploaded from where it lies (host memory) and runs gray + pyramid, LK and the track kernel.  The LK launches are
+ * sized for the points held at entry in front of the first key frame and for num_queries behind it; the device-resident count decides.
+ * The first frame need not be a key frame.  out [K][num_queries], counts [K], track_ids [K][num_queries]: per key frame, as from
+ * opd_detr_detect_frames_hybrid.  recs_out [F - K][capacity], rec_counts [F - K]: per in-between frame, as from
+ * opd_lwt_interpolate_sequence.  *frames_done = F on success, and a per-frame or another sequence call afterwards continues bit for bit.
+ * A key frame f whose new tracks do not fit changes nothing, as under opd_lwt_update, and ends the run: the update kernel raises a sticky
+ * word on the device at which every launch of the frames behind it leaves at once, so the tracker (state, points, reference frame) is
+ * that of the per-frame loop that stopped at its error.  *frames_done = f + 1, the ids of frame f and of later key frames are -1, the
+ * record counts of later in-between frames are 0, the records and counts of ALL key frames are delivered, and the call returns
+ * OPD_EINVAL.  OPD_EINVAL before any device work: whatever opd_lwt_interpolate_sequence and opd_detr_detect_frames_hybrid refuse. */
+OPD_API int opd_detr_detect_sequence_hybrid(opd_detr* m, opd_lwt* t, const uint8_t* const* frames, const uint8_t* is_key, int F, int h, int w,
+                                            int H, int W, float threshold, int label, opd_det* out, int32_t* counts, int32_t* track_ids,
+                                            opd_lwt_rec* recs_out, int capacity, int32_t* rec_counts, int32_t* frames_done);
 /* The live tracks in creation order (out may be NULL with capacity 0 to ask for the count).  A read-back for inspection: one more wait. */
 OPD_API int opd_lwt_get(opd_lwt* t, opd_lwt_track* out, int capacity, int* count);
 

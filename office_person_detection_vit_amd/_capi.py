@@ -241,6 +241,12 @@ API = {
     "opd_lwt_info": (C.c_int, [C.c_void_p, C.POINTER(OpdLwtStatus)]),
     "opd_lwt_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "opd_lwt_interpolate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(OpdLwtRec), C.c_int, C.POINTER(C.c_int)]),
+    "opd_lwt_interpolate_sequence": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OpdLwtRec), C.c_int,
+                                              C.POINTER(C.c_int32)]),
+    "opd_detr_detect_frames_hybrid": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.POINTER(OpdDet),
+                                                 C.POINTER(C.c_int32), C.c_void_p]),
+    "opd_detr_detect_sequence_hybrid": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_int, C.POINTER(OpdDet),
+                                                   C.POINTER(C.c_int32), C.c_void_p, C.POINTER(OpdLwtRec), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "opd_lwt_get": (C.c_int, [C.c_void_p, C.POINTER(OpdLwtTrack), C.c_int, C.POINTER(C.c_int)]),
     "opd_detr_detect_frames_floor": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.POINTER(OpdDet), C.POINTER(C.c_int32),
                                                 C.c_void_p]),
@@ -388,6 +394,8 @@ TEST_API = {
     "opd_track_test_bench_assoc": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int,
                                               C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     # hybrid-tracker hook (csrc/opd_lwt_test_api.cpp): handle, next_xy, status, records, capacity, count
+    # the ingest launch of the fused hybrid detect call (csrc/opd_lwt_ingest_test_api.cpp): device, records, n, Q, boxes, n_out
+    "opd_lwt_test_ingest": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "opd_test_lwt_interpolate_scripted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OpdLwtRec), C.c_int, C.POINTER(C.c_int)]),
 }
 

@@ -13,7 +13,9 @@
 //                        level), and every lane keeps the bilinear I, Sx, Sy of its <= 7 window samples in registers.  An iteration
 //                        reads the new frame's level through the cache (4 bytes per sample), and adds the two mismatch sums over the
 //                        wave by an xor butterfly: every lane holds the same bits, so all decisions are wave-uniform, and a point's
-//                        result depends on nothing but its own coordinates and the two pyramids.
+//                        result depends on nothing but its own coordinates and the two pyramids.  With FlowParams::count the launch
+//                        is sized for an upper bound and the device-resident count decides which waves have a point.
+//   All three take a nullable `stop` word (a sequence call's: set by a refused frame, it makes every launch behind it leave at once).
 #include <float.h>
 #include <hip/hip_runtime.h>
 
@@ -34,7 +36,11 @@ __device__ __forceinline__ int reflect101(int i, int n) {
 
 __device__ __forceinline__ unsigned gray_of(unsigned b, unsigned g, unsigned r) { return (1868u * b + 9617u * g + 4899u * r + 8192u) >> 14; }
 
-__global__ __launch_bounds__(256) void flow_gray_kernel(const uint8_t* __restrict__ bgr, uint8_t* __restrict__ gray, int h, int w, int pitch) {
+// `stop` (nullable, here and in the two kernels below): a device word that a sequence call raises when a frame of its is refused; the
+// launches of the frames behind it, already enqueued, find it set and leave at once, before any barrier and any store.
+__global__ __launch_bounds__(256) void flow_gray_kernel(const uint8_t* __restrict__ bgr, uint8_t* __restrict__ gray, int h, int w, int pitch,
+                                                        const int32_t* __restrict__ stop) {
+    if (stop && *stop) return;
     const int x = 4 * (int)(blockIdx.x * 64 + threadIdx.x), y = blockIdx.y * 4 + threadIdx.y;
     if (x >= w || y >= h) return;
     const uint8_t* src = bgr + ((size_t)y * w + x) * 3;
@@ -54,7 +60,8 @@ __global__ __launch_bounds__(256) void flow_gray_kernel(const uint8_t* __restric
 }
 
 __global__ __launch_bounds__(256) void flow_pyrdown_kernel(const uint8_t* __restrict__ src, int sh, int sw, int spitch, uint8_t* __restrict__ dst,
-                                                           int oh, int ow, int dpitch) {
+                                                           int oh, int ow, int dpitch, const int32_t* __restrict__ stop) {
+    if (stop && *stop) return;
     const int t = blockIdx.x * 64 + threadIdx.x, oy = blockIdx.y * 4 + threadIdx.y;
     if (4 * t >= ow || oy >= oh) return;
     const int c0 = 8 * t - 2;                       // first source column of the group; it needs c0 .. c0 + 10
@@ -90,6 +97,8 @@ __global__ __launch_bounds__(64) void flow_lk_kernel(const FlowParams p) {
     __shared__ float dxs[(OPD_FLOW_MAX_WIN + 1) * DERIV_LD];     // Scharr x at floor(q) .. floor(q) + win
     __shared__ float dys[(OPD_FLOW_MAX_WIN + 1) * DERIV_LD];
     const int pt = blockIdx.x, lane = threadIdx.x;
+    if (p.stop && *p.stop) return;
+    if (p.count && pt >= *p.count) return;   // (the whole wave, before the first barrier: the launch was sized for a bound)
     const int win = p.win, nwin = win * win;
     const float half = (float)((win - 1) / 2), fwin = (float)win;
     const float px = p.pts[2 * pt], py = p.pts[2 * pt + 1];
@@ -206,14 +215,14 @@ __global__ __launch_bounds__(64) void flow_lk_kernel(const FlowParams p) {
 
 }  // namespace
 
-hipError_t opd_launch_flow_gray(const uint8_t* bgr, uint8_t* gray, int h, int w, int pitch, hipStream_t stream) {
-    OPD_LAUNCH(flow_gray_kernel, dim3(((w + 3) / 4 + 63) / 64, (h + 3) / 4), dim3(64, 4), 0, stream, bgr, gray, h, w, pitch);
+hipError_t opd_launch_flow_gray(const uint8_t* bgr, uint8_t* gray, int h, int w, int pitch, hipStream_t stream, const int32_t* stop) {
+    OPD_LAUNCH(flow_gray_kernel, dim3(((w + 3) / 4 + 63) / 64, (h + 3) / 4), dim3(64, 4), 0, stream, bgr, gray, h, w, pitch, stop);
     return hipGetLastError();
 }
 
-hipError_t opd_launch_flow_pyrdown(const uint8_t* src, int sh, int sw, int spitch, uint8_t* dst, int dpitch, hipStream_t stream) {
+hipError_t opd_launch_flow_pyrdown(const uint8_t* src, int sh, int sw, int spitch, uint8_t* dst, int dpitch, hipStream_t stream, const int32_t* stop) {
     const int oh = (sh + 1) / 2, ow = (sw + 1) / 2;
-    OPD_LAUNCH(flow_pyrdown_kernel, dim3(((ow + 3) / 4 + 63) / 64, (oh + 3) / 4), dim3(64, 4), 0, stream, src, sh, sw, spitch, dst, oh, ow, dpitch);
+    OPD_LAUNCH(flow_pyrdown_kernel, dim3(((ow + 3) / 4 + 63) / 64, (oh + 3) / 4), dim3(64, 4), 0, stream, src, sh, sw, spitch, dst, oh, ow, dpitch, stop);
     return hipGetLastError();
 }
 

@@ -17,6 +17,10 @@
 //       position in the OTHER bank; one thread per unmatched detection: a new track.  (f) ids, flow points, head.
 //   lwt_interp_kernel   `interpolate`: one workgroup, one thread per track.  A track whose id has a followed point moves its box there and
 //       is updated with the point; any other track is predicted.  Then the point list is compacted to the followed points in order.
+//   lwt_ingest_kernel   the fused detect call only (opd_detr_detect_frames_hybrid): one wave turns the kept records of a frame, where the
+//       suppression kernel left them, into the float32 [n][4] xywh image `np.array([d.bbox for d in dets], np.float32)` is -- corners as they
+//       are, width and height as differences in double rounded once (track_ingest_kernel's box rule) -- and leaves the kept count on the
+//       device, where lwt_update_kernel (LwtUpdateParams::count) reads it.
 #include <hip/hip_runtime.h>
 
 #include "opd_kprims.h"
@@ -186,7 +190,12 @@ __global__ __launch_bounds__(LWT_THREADS) void lwt_update_kernel(const LwtUpdate
     __shared__ int wi[LWT_THREADS / 64];
     __shared__ int wtot[LWT_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int N = p.N;
+    if (p.stop && *p.stop) return;   // (every thread, before the first barrier: a frame of the sequence call before this one was refused)
+    int N = p.N;
+    if (p.count) {   // the detection count lives on the device (the fused detect call); p.N is the bound the buffers were sized for
+        const int n = __builtin_amdgcn_readfirstlane(*p.count);   // (a scalar, like p.N: every loop bound below stays wave-uniform)
+        N = n < 0 ? 0 : (n > N ? N : n);
+    }
     int T = p.head[LWT_HEAD_TRACKS];
     T = T < 0 ? 0 : (T > p.max_tracks ? p.max_tracks : T);
     const int next_id = p.head[LWT_HEAD_NEXT_ID], old_points = p.head[LWT_HEAD_POINTS];
@@ -237,6 +246,7 @@ __global__ __launch_bounds__(LWT_THREADS) void lwt_update_kernel(const LwtUpdate
             p.result[LWT_HEAD_NEXT_ID] = next_id;
             p.result[LWT_HEAD_POINTS] = old_points;
             p.result[LWT_HEAD_ERROR] = 1;
+            if (p.stop) *p.stop = 1;   // sticky: every launch the sequence call has enqueued behind this one leaves at once
         }
         return;
     }
@@ -318,6 +328,7 @@ __global__ __launch_bounds__(LWT_THREADS) void lwt_interp_kernel(const LwtInterp
     __shared__ int flag[LWT_MAX_DETS];
     __shared__ int wtot[LWT_THREADS / 64];
     const int tid = threadIdx.x;
+    if (p.stop && *p.stop) return;
     int T = p.head[LWT_HEAD_TRACKS], np = p.next ? p.head[LWT_HEAD_POINTS] : 0;
     T = T < 0 ? 0 : (T > LWT_MAX_TRACKS ? LWT_MAX_TRACKS : T);
     np = np < 0 ? 0 : (np > LWT_MAX_DETS ? LWT_MAX_DETS : np);
@@ -394,7 +405,28 @@ __global__ __launch_bounds__(LWT_THREADS) void lwt_interp_kernel(const LwtInterp
     }
 }
 
+__global__ __launch_bounds__(64) void lwt_ingest_kernel(const LwtIngestParams p) {
+    if (p.stop && *p.stop) return;
+    int n = *p.count;
+    n = n < 0 ? 0 : (n > p.Q ? p.Q : n);
+    if (threadIdx.x == 0) *p.n_out = n;
+    for (int i = threadIdx.x; i < n; i += 64) {
+        const opd_det r = p.records[i];
+        const double bw = (double)r.x2 - (double)r.x1, bh = (double)r.y2 - (double)r.y1;
+        p.boxes[4 * i] = r.x1;
+        p.boxes[4 * i + 1] = r.y1;
+        p.boxes[4 * i + 2] = (float)bw;
+        p.boxes[4 * i + 3] = (float)bh;
+    }
+}
+
 }  // namespace
+
+hipError_t opd_launch_lwt_ingest(const LwtIngestParams& p, hipStream_t stream) {
+    if (p.Q < 1 || p.Q > LWT_MAX_DETS || !p.records || !p.count || !p.boxes || !p.n_out) return hipErrorInvalidValue;
+    OPD_LAUNCH(lwt_ingest_kernel, dim3(1), dim3(64), 0, stream, p);
+    return hipGetLastError();
+}
 
 hipError_t opd_launch_lwt_update(const LwtUpdateParams& p, hipStream_t stream) {
     if (p.N < 0 || p.N > LWT_MAX_DETS || p.max_tracks < 1 || p.max_tracks > LWT_MAX_TRACKS) return hipErrorInvalidValue;

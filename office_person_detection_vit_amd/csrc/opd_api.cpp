@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "opd_floor.h"
+#include "opd_lwt.h"
 #include "opd_model.h"
 #include "opd_nms.h"
 #include "opd_reid.h"
@@ -324,6 +325,31 @@ static int finish_trackers(opd_detr* m, const RecordSink& s, bool with_features)
     return rc == OPD_OK ? OPD_OK : fail(rc, first);
 }
 
+// The hybrid-tracker half of a fused detect call (opd_lwt.h), around the one wait of fetch_records like the track stage.  Before it, per tracker on
+// m->stream: ingest of the frame's kept records, gray + pyramid of its camera-resolution frame where the source step left it, the update with the
+// count read on the device.  After it: adoption per tracker; a tracker whose new tracks did not fit keeps its state and reference frame, gets -1
+// for every id and does not keep the others from being committed; its error is the call's.
+static int enqueue_hybrid(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera) {
+    const int B = m->last_B, Q = m->arch.queries;
+    if (s.hybrid.seq) return lwt_sequence_enqueue(s.hybrid.seq, m->stream, *s.hybrid.call, m->d_records, m->d_counts, d_camera, s.hybrid.entry);
+    for (int b = 0; b < B; ++b)
+        RCCHK(lwt_fused_enqueue(s.hybrid.trackers[b], m->stream, m->d_records + (size_t)b * Q, m->d_counts + b, Q, d_camera + (size_t)b * h * w * 3, h, w,
+                                "opd_detr_detect_frames_hybrid"));
+    return OPD_OK;
+}
+static int finish_hybrid(opd_detr* m, const RecordSink& s) {
+    const int B = m->last_B, Q = m->arch.queries;
+    const HybridStage& y = s.hybrid;
+    if (y.seq) return lwt_sequence_finish(y.seq, *y.call, s.counts, y.track_ids, y.recs_out, y.capacity, y.rec_counts, y.frames_done, y.entry);
+    int rc = OPD_OK;
+    std::string first;
+    for (int b = 0; b < B; ++b) {
+        const int one = lwt_fused_finish(s.hybrid.trackers[b], std::max(0, std::min(s.counts[b], Q)), s.hybrid.track_ids + (size_t)b * Q, "opd_detr_detect_frames_hybrid");
+        if (one != OPD_OK && rc == OPD_OK) { rc = one; first = g_err; }
+    }
+    return rc == OPD_OK ? OPD_OK : fail(rc, first);
+}
+
 // A page-locked copy of the record block is taken apart into the caller's arrays here (deliver_records, opd_detr_wait)
 static void unpack_records(const opd_detr* m, const void* pinned, int B, opd_det* out, int32_t* counts, float* features = nullptr) {
     const char* p = static_cast<const char*>(pinned);
@@ -354,6 +380,9 @@ static int fetch_records(opd_detr* m, const RecordSink& s, ReidFusedCall* reid) 
         HIPCHK(hipMemcpyAsync(m->sync_pinned, m->d_records, query_rows_out(s) ? feat_off(m) + B * feat_row(m) : rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
         if (s.floor.fmap) HIPCHK(hipMemcpyAsync(m->h_floor, m->d_floor, (size_t)B * Q * sizeof(opd_floor_rec), hipMemcpyDeviceToHost, m->stream));
         if (reid) RCCHK(reid->copy_back(m->stream));
+        if (s.hybrid.seq) RCCHK(lwt_sequence_fetch(s.hybrid.seq, m->stream, s.hybrid.call->F));   // a slot per frame: [head | ids] or [head | records]
+        else if (s.hybrid.on())   // every tracker's [head | ids]
+            for (int b = 0; b < B; ++b) RCCHK(lwt_fused_fetch(s.hybrid.trackers[b], m->stream, Q));
     }
     HIPCHK(hipStreamSynchronize(m->stream));
     if (m->profiling) {
@@ -401,6 +430,7 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
     RCCHK(enqueue_features(m, s, tiled ? s.tile.frame_h : h, tiled ? s.tile.frame_w : w, d_camera, &reid, &rows));
     if (s.floor.fmap) RCCHK(enqueue_floor(m, s));
     if (tracked) RCCHK(enqueue_trackers(m, s, rows));
+    if (s.hybrid.on()) RCCHK(enqueue_hybrid(m, s, h, w, d_camera));
     if (s.wait == WAIT_NONE) return OPD_OK;
     if (s.wait == WAIT_TICKET) return hand_to_ticket(m, s);
     RCCHK(fetch_records(m, s, reid ? &*reid : nullptr));
@@ -428,6 +458,7 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
                 const opd_det& r = s.out[(size_t)b * Q + i];
                 if (r.label == s.label && (unsigned)r.query_index < (unsigned)Q) s.floor.out[(size_t)b * Q + r.query_index] = m->h_floor[(size_t)b * Q + r.query_index];
             }
+    if (s.hybrid.on()) return finish_hybrid(m, s);   // (no entry sets both tracker stages)
     if (!tracked) return OPD_OK;
     if (reid) reid->slots_per_frame(B, Q, s.track.n_featured);
     else for (int b = 0; b < B; ++b) s.track.n_featured[b] = rows.rows_kind == TRACK_ROWS_NONE ? 0 : std::max(0, std::min(s.counts[b], Q));
@@ -1030,6 +1061,69 @@ int opd_detr_detect_sequence_track(opd_detr* m, opd_reid* r, opd_track* t, const
     TrackStage track;
     track.seq = t; track.track_ids = track_ids; track.n_featured = n_featured; track.frames_done = frames_done;
     return detect_track(me, m, r, track, frames, B, h, w, H, W, threshold, label, feature_kind, slots, out, counts);
+}); }
+
+// The hybrid twin: frame b's kept records and its camera-resolution frame enter hybrid tracker b inside the call
+int opd_detr_detect_frames_hybrid(opd_detr* m, opd_lwt* const* trackers, const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold,
+                                  int label, opd_det* out, int32_t* counts, int32_t* track_ids) { return api_call("opd_detr_detect_frames_hybrid", [&]() -> int {
+    const std::string me = "opd_detr_detect_frames_hybrid";
+    if (!trackers || !frames || !out || !counts || !track_ids) return fail(OPD_EINVAL, me + ": null argument (tracker list, frame list or an output)");
+    if (!frame_size_ok(h, w)) return fail(OPD_EINVAL, me + ": source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
+    RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, true, me));
+    if (m->nms_threshold < 0.f)
+        return fail(OPD_EINVAL, me + ": opd_detr_set_nms is off on this handle; a tracker takes the kept records of a frame, which only the suppression on the device leaves there");
+    if (m->nms_label != label)
+        return fail(OPD_EINVAL, me + ": opd_detr_set_nms keeps label " + std::to_string(m->nms_label) + ", the call asks for label " + std::to_string(label));
+    for (int b = 0; b < B; ++b) {
+        RCCHK(lwt_fused_check(trackers[b], m->device, m->arch.queries, h, w, me));
+        for (int a = 0; a < b; ++a)
+            if (trackers[a] == trackers[b])
+                return fail(OPD_EINVAL, me + ": frames " + std::to_string(a) + " and " + std::to_string(b) + " name the same tracker; a tracker takes one frame per call");
+    }
+    RecordSink sink = host_sink(threshold, label, out, counts);
+    sink.hybrid.trackers = trackers; sink.hybrid.track_ids = track_ids;
+    return detect_frames(m, frames, OPD_MEM_HOST, B, h, w, H, W, sink);
+}); }
+
+// The sequence twin: F consecutive frames of ONE camera; the key frames among them go through one batched forward, and then every frame, key or
+// in-between, enters the tracker in frame order behind the one wait (opd_lwt.h: lwt_sequence_*)
+int opd_detr_detect_sequence_hybrid(opd_detr* m, opd_lwt* t, const uint8_t* const* frames, const uint8_t* is_key, int F, int h, int w, int H, int W,
+                                    float threshold, int label, opd_det* out, int32_t* counts, int32_t* track_ids, opd_lwt_rec* recs_out, int capacity,
+                                    int32_t* rec_counts, int32_t* frames_done) { return api_call("opd_detr_detect_sequence_hybrid", [&]() -> int {
+    const std::string me = "opd_detr_detect_sequence_hybrid";
+    if (F < 1 || F > LWT_MAX_SEQUENCE) return fail(OPD_EINVAL, me + ": " + std::to_string(F) + " frames, a call takes 1 .. " + std::to_string(LWT_MAX_SEQUENCE));
+    if (capacity < 1) return fail(OPD_EINVAL, me + ": capacity " + std::to_string(capacity) + " is below the tracker's max_tracks");
+    if (!frames || !is_key || !frames_done) return fail(OPD_EINVAL, me + ": null argument (frame list, key flags or frames_done)");
+    std::vector<const uint8_t*> keys;
+    for (int f = 0; f < F; ++f)
+        if (is_key[f]) keys.push_back(frames[f]);
+    const int K = (int)keys.size();
+    if (K > 0 && (!out || !counts || !track_ids)) return fail(OPD_EINVAL, me + ": null output of the key frames");
+    if (K < F && (!recs_out || !rec_counts)) return fail(OPD_EINVAL, me + ": null output of the in-between frames");
+    if (!frame_size_ok(h, w)) return fail(OPD_EINVAL, me + ": source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
+    if (!m) return fail(OPD_EINVAL, "null model handle");
+    if (K > 0) {
+        RCCHK(check_frame_list(m, keys.data(), OPD_MEM_HOST, K, H, W, true, me));   // (more key frames than max_batch among them)
+        if (m->nms_threshold < 0.f)
+            return fail(OPD_EINVAL, me + ": opd_detr_set_nms is off on this handle; a tracker takes the kept records of a frame, which only the suppression on the device leaves there");
+        if (m->nms_label != label)
+            return fail(OPD_EINVAL, me + ": opd_detr_set_nms keeps label " + std::to_string(m->nms_label) + ", the call asks for label " + std::to_string(label));
+    }
+    const LwtSeqCall call{frames, is_key, F, h, w, m->arch.queries};
+    RCCHK(lwt_sequence_check(t, call, capacity, m->device, me));
+    *frames_done = 0;
+    if (K == 0) {   // no forward: the run on the tracker's own stream, which is opd_lwt_interpolate_sequence
+        HIPCHK(hipSetDevice(t->device));
+        RCCHK(lwt_sequence_enqueue(t, t->stream(), call, nullptr, nullptr, nullptr, me.c_str()));
+        RCCHK(lwt_sequence_fetch(t, t->stream(), F));
+        HIPCHK(hipStreamSynchronize(t->stream()));
+        t->last_waits = 1;
+        return lwt_sequence_finish(t, call, nullptr, nullptr, recs_out, capacity, rec_counts, frames_done, me);
+    }
+    RecordSink sink = host_sink(threshold, label, out, counts);
+    sink.hybrid.seq = t; sink.hybrid.call = &call; sink.hybrid.track_ids = track_ids; sink.hybrid.entry = "opd_detr_detect_sequence_hybrid";
+    sink.hybrid.recs_out = recs_out; sink.hybrid.capacity = capacity; sink.hybrid.rec_counts = rec_counts; sink.hybrid.frames_done = frames_done;
+    return detect_frames(m, keys.data(), OPD_MEM_HOST, K, h, w, H, W, sink);
 }); }
 
 int opd_host_alloc(size_t bytes, void** out) { return api_call("opd_host_alloc", [&]() -> int {

@@ -43,20 +43,25 @@ int check_frame(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, 
 }
 
 // gray + pyramid of `bgr` into pyr[which] (whose levels are planned for h x w), enqueued on the handle's stream.  The `pts_bytes` of points the caller has put at the head of the
-// staging image and a host frame (behind the points region) travel as two copies of exactly their bytes on the same stream.
-int enqueue_pyramid(opd_flow* f, int which, const uint8_t* bgr, int mem_kind, int h, int w, size_t pts_bytes) {
+// staging image and a host frame (behind the points region) travel as two copies of exactly their bytes on the same stream.  `in_place`:
+// the host frame is uploaded from where it lies, not through the staging image (which holds one frame: a caller that enqueues several
+// frames before it waits cannot reuse it; the device side can be reused, the stream orders the upload behind the gray launch before it).
+// `on`: another stream than the handle's (the detector's, in a fused detect call, which has ordered itself against the handle's).
+int enqueue_pyramid(opd_flow* f, int which, const uint8_t* bgr, int mem_kind, int h, int w, size_t pts_bytes, bool in_place = false, hipStream_t on = nullptr,
+                    const int32_t* stop = nullptr) {
+    hipStream_t s = on ? on : f->stream;
     const uint8_t* d_bgr = bgr;
-    if (pts_bytes) HIPCHK(hipMemcpyAsync(f->io.dev, f->io.host, pts_bytes, hipMemcpyHostToDevice, f->stream));
+    if (pts_bytes) HIPCHK(hipMemcpyAsync(f->io.dev, f->io.host, pts_bytes, hipMemcpyHostToDevice, s));
     if (mem_kind == OPD_MEM_HOST) {
         const size_t bytes = (size_t)h * w * 3;
-        memcpy(f->io.host + f->frame_off, bgr, bytes);
+        if (!in_place) memcpy(f->io.host + f->frame_off, bgr, bytes);
         d_bgr = f->io.dev + f->frame_off;
-        HIPCHK(hipMemcpyAsync(f->io.dev + f->frame_off, f->io.host + f->frame_off, bytes, hipMemcpyHostToDevice, f->stream));
+        HIPCHK(hipMemcpyAsync(f->io.dev + f->frame_off, in_place ? bgr : f->io.host + f->frame_off, bytes, hipMemcpyHostToDevice, s));
     }
     const FlowPyramid& p = f->pyr[which];
-    HIPCHK(opd_launch_flow_gray(d_bgr, p.base + p.off[0], h, w, p.lp[0], f->stream));
+    HIPCHK(opd_launch_flow_gray(d_bgr, p.base + p.off[0], h, w, p.lp[0], s, stop));
     for (int l = 1; l <= p.top; ++l)
-        HIPCHK(opd_launch_flow_pyrdown(p.base + p.off[l - 1], p.lh[l - 1], p.lw[l - 1], p.lp[l - 1], p.base + p.off[l], p.lp[l], f->stream));
+        HIPCHK(opd_launch_flow_pyrdown(p.base + p.off[l - 1], p.lh[l - 1], p.lw[l - 1], p.lp[l - 1], p.base + p.off[l], p.lp[l], s, stop));
     return OPD_OK;
 }
 
@@ -118,12 +123,12 @@ extern "C" void opd_flow_destroy(opd_flow* f) { (void)api_call("opd_flow_destroy
 
 // ---- the two entry points in halves: everything up to the wait (enqueue) and what follows it (finish).  opd_lwt.cpp puts launches of its
 //      own on the handle's stream between the two and waits itself.
-int opd::flow_enqueue_reference(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, int which) {
+int opd::flow_enqueue_reference(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, int which, hipStream_t on, const int32_t* stop) {
     RCCHK(check_frame(f, who, bgr, mem_kind, h, w));
     HIPCHK(hipSetDevice(f->device));
     f->pyr[which].valid = false;   // (which == ref: a failure below leaves no reference)
     plan_levels(&f->pyr[which], h, w, f->cfg.win, f->cfg.max_level);
-    return enqueue_pyramid(f, which, bgr, mem_kind, h, w, 0);
+    return enqueue_pyramid(f, which, bgr, mem_kind, h, w, 0, false, on, stop);
 }
 
 void opd::flow_finish_reference(opd_flow* f, int which) {
@@ -131,8 +136,7 @@ void opd::flow_finish_reference(opd_flow* f, int which) {
     f->pyr[which].valid = true;
 }
 
-int opd::flow_enqueue_track(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, const float* host_pts, int n, const float* d_pts,
-                            float* d_next, uint8_t* d_status) {
+int opd::flow_check_track(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, int n) {
     const std::string me(who);
     RCCHK(check_frame(f, who, bgr, mem_kind, h, w));
     if (n < 0 || n > f->cfg.max_points)
@@ -142,13 +146,19 @@ int opd::flow_enqueue_track(opd_flow* f, const char* who, const uint8_t* bgr, in
     if (h != ref.h || w != ref.w)
         return fail(OPD_EINVAL, me + ": frame of " + std::to_string(h) + " x " + std::to_string(w) + " pixels, the reference has " +
                                     std::to_string(ref.h) + " x " + std::to_string(ref.w));
+    return OPD_OK;
+}
+
+int opd::flow_enqueue_track_from(opd_flow* f, int ref_slot, const uint8_t* bgr, int mem_kind, int h, int w, bool in_place, const float* host_pts, int n,
+                                 const int32_t* d_count, const float* d_pts, float* d_next, uint8_t* d_status, hipStream_t on, const int32_t* stop) {
     HIPCHK(hipSetDevice(f->device));
-    const int cur = 1 - f->ref;
+    const FlowPyramid& ref = f->pyr[ref_slot];
+    const int cur = 1 - ref_slot;
     f->pyr[cur].valid = false;
     plan_levels(&f->pyr[cur], h, w, f->cfg.win, f->cfg.max_level);   // (the reference's size: the same levels)
     const size_t pts_bytes = host_pts ? (size_t)n * 8 : 0;
     if (pts_bytes) memcpy(f->io.host, host_pts, pts_bytes);
-    RCCHK(enqueue_pyramid(f, cur, bgr, mem_kind, h, w, pts_bytes));
+    RCCHK(enqueue_pyramid(f, cur, bgr, mem_kind, h, w, pts_bytes, in_place, on, stop));
     if (n) {
         FlowParams p{};
         for (int l = 0; l <= ref.top; ++l)
@@ -162,14 +172,27 @@ int opd::flow_enqueue_track(opd_flow* f, const char* who, const uint8_t* bgr, in
         p.pts = d_pts;
         p.next = d_next;
         p.status = d_status;
-        HIPCHK(opd_launch_flow_lk(p, f->stream));
+        p.count = d_count;
+        p.stop = stop;
+        HIPCHK(opd_launch_flow_lk(p, on ? on : f->stream));
     }
     return OPD_OK;
+}
+
+int opd::flow_enqueue_track(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, const float* host_pts, int n, const float* d_pts,
+                            float* d_next, uint8_t* d_status) {
+    RCCHK(flow_check_track(f, who, bgr, mem_kind, h, w, n));
+    return flow_enqueue_track_from(f, f->ref, bgr, mem_kind, h, w, false, host_pts, n, nullptr, d_pts, d_next, d_status);
 }
 
 void opd::flow_finish_track(opd_flow* f) {
     f->ref = 1 - f->ref;   // the frame just seen is the reference of the next call; the old reference stays valid behind it
     f->pyr[f->ref].valid = true;
+}
+
+void opd::flow_finish_sequence(opd_flow* f, int frames) {
+    f->ref = (f->ref + frames) & 1;   // the last frame is the reference; the other pyramid holds the frame before it
+    f->pyr[0].valid = f->pyr[1].valid = true;
 }
 
 extern "C" int opd_flow_set_reference(opd_flow* f, const uint8_t* bgr, int mem_kind, int h, int w) { return api_call("opd_flow_set_reference", [&]() -> int {

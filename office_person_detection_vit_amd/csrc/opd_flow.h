@@ -22,10 +22,13 @@ struct FlowParams {
     const float* pts;     // [n][2] (x, y) in the reference frame
     float* next;          // [n][2]
     uint8_t* status;      // [n]
+    const int32_t* count; // null: all n points are followed.  Else the device-resident number of points (<= n, the launch's bound): the
+                          // waves of the points at or beyond it leave at once
+    const int32_t* stop;  // null, or the sticky word of a sequence call: while it is set every wave leaves at once
 };
 
-hipError_t opd_launch_flow_gray(const uint8_t* bgr, uint8_t* gray, int h, int w, int pitch, hipStream_t stream);
-hipError_t opd_launch_flow_pyrdown(const uint8_t* src, int sh, int sw, int spitch, uint8_t* dst, int dpitch, hipStream_t stream);
+hipError_t opd_launch_flow_gray(const uint8_t* bgr, uint8_t* gray, int h, int w, int pitch, hipStream_t stream, const int32_t* stop = nullptr);
+hipError_t opd_launch_flow_pyrdown(const uint8_t* src, int sh, int sw, int spitch, uint8_t* dst, int dpitch, hipStream_t stream, const int32_t* stop = nullptr);
 hipError_t opd_launch_flow_lk(const FlowParams& p, hipStream_t stream);
 
 inline int flow_pitch(int w) { return (w + 15) / 16 * 16; }
@@ -56,10 +59,21 @@ struct opd_flow {
 // the finish has changed nothing but the contents of the pyramid the reference does not use).  The track half
 // reads its points at `d_pts` on the device (`host_pts`, when given, are staged and uploaded there first: d_pts is then the head of io.dev)
 // and leaves LK's results at `d_next` / `d_status` on the device.
+//
+// A run of track frames behind ONE wait (opd_lwt_interpolate_sequence) takes the track half in its two parts: flow_check_track is every
+// refusal of flow_enqueue_track and touches nothing; flow_enqueue_track_from is its device work with the reference named by the caller
+// (`ref`, which the caller alternates: no finish has run between the frames), a host frame uploaded from where it lies (the staging image
+// holds one frame, and the host does not wait between two), and LK launched for the bound `n` while `d_count` on the device says how many
+// points there are by then.  flow_finish_sequence is `frames` finishes at once.
 namespace opd {
-int flow_enqueue_reference(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, int which);
+int flow_enqueue_reference(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, int which, hipStream_t on = nullptr,
+                           const int32_t* stop = nullptr);   // `on`: a stream other than f->stream; `stop`: the sticky word of a sequence call (FlowParams::stop)
 void flow_finish_reference(opd_flow* f, int which);
+int flow_check_track(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, int n);
 int flow_enqueue_track(opd_flow* f, const char* who, const uint8_t* bgr, int mem_kind, int h, int w, const float* host_pts, int n, const float* d_pts,
                        float* d_next, uint8_t* d_status);
+int flow_enqueue_track_from(opd_flow* f, int ref, const uint8_t* bgr, int mem_kind, int h, int w, bool in_place, const float* host_pts, int n,
+                            const int32_t* d_count, const float* d_pts, float* d_next, uint8_t* d_status, hipStream_t on = nullptr, const int32_t* stop = nullptr);
 void flow_finish_track(opd_flow* f);
+void flow_finish_sequence(opd_flow* f, int frames);
 }  // namespace opd

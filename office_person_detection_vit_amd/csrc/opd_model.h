@@ -352,6 +352,7 @@ struct opd_detr : DetrWeights {
     std::vector<std::string> tap_names;
 };
 enum { OPD_MAX_TAPS = 512 };
+struct LwtSeqCall;   // opd_lwt.h: a run of frames of one camera (HybridStage::call)
 
 namespace opd {
 
@@ -418,8 +419,8 @@ void timed_collect(opd_detr* m);
 //   source   stage_frames: the frames of a FrameSource -> device pixels at model resolution (upload, resize, or the windows of whole frames)
 //   forward  run_forward, through the graph cache
 //   sink     deliver_records, a straight sequence in which a stage runs when its part of the RecordSink is set: post-process with suppression ->
-//            tile merge -> feature stage -> floor stage -> tracker enqueue -> ONE fetch (the copies back and the call's one wait) -> delivery
-//            into the caller's arrays, tracker finish
+//            tile merge -> feature stage -> floor stage -> tracker enqueue -> hybrid-tracker enqueue -> ONE fetch (the copies back and the
+//            call's one wait) -> delivery into the caller's arrays, tracker finish, hybrid-tracker finish
 enum { SRC_PIXELS, SRC_BLOCK, SRC_LIST, SRC_TILES };
 struct FrameSource {
     int kind;
@@ -453,6 +454,16 @@ struct TrackStage {   // the kept records and feature rows enter trackers where 
     int32_t *track_ids = nullptr, *n_featured = nullptr, *frames_done = nullptr;   // [B][queries], [B]; seq: frames applied
     bool on() const { return trackers || seq; }
 };
+struct HybridStage {   // the kept records and the camera-resolution frames enter hybrid trackers (opd_lwt.h) where they lie: frame b into trackers[b], or
+    struct opd_lwt* const* trackers = nullptr;   // (`seq`) as the key frames of the run of frames `call` of one camera, its in-between frames around them
+    struct opd_lwt* seq = nullptr;
+    const ::LwtSeqCall* call = nullptr;
+    int32_t* track_ids = nullptr;   // [B][queries]
+    opd_lwt_rec* recs_out = nullptr; int capacity = 0;           // seq: the in-between frames' records [F - B][capacity], their counts, frames applied
+    int32_t *rec_counts = nullptr, *frames_done = nullptr;
+    const char* entry = "opd_detr_detect_frames_hybrid";         // the entry errors are worded for
+    bool on() const { return trackers || seq; }
+};
 struct TileStage {   // a SRC_TILES batch: the records of a frame's tiles, suppressed per tile with the PARAMETERS' label and threshold, merge across the seams
     const opd_tile_params* params = nullptr;
     int n_frames = 0, n_tiles = 0, frame_h = 0, frame_w = 0;
@@ -465,7 +476,7 @@ struct RecordSink {
     opd_det* out; int32_t* counts;
     int mem_kind;                 // where out / counts lie: device ones are written by the post-process kernel itself, host ones filled from the library's
     int wait, ticket, label = 0;
-    FeatureStage feature; FloorStage floor; TrackStage track; TileStage tile;
+    FeatureStage feature; FloorStage floor; TrackStage track; HybridStage hybrid; TileStage tile;
     RecordSink(float threshold, const int32_t* orig_hw, opd_det* out, int32_t* counts, int mem_kind, int wait = WAIT_BLOCKING, int ticket = 0)
         : threshold(threshold), orig_hw(orig_hw), out(out), counts(counts), mem_kind(mem_kind), wait(wait), ticket(ticket) {}
 };

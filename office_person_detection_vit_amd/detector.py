@@ -1014,6 +1014,85 @@ class HipDetrDetector:
         tracker._apply(detections, ids[:len(detections)])
         return [det for det in detections if det.track_id is not None]
 
+    def detect_and_track_hybrid(self, frame: np.ndarray, lwt) -> List[Detection]:
+        """``dets = self.detect(frame); lwt.update_with_detections(frame, dets)`` (the detection frame of the reference's hybrid mode,
+        ``tracking.py`` with ``hybrid_mode.enabled``) as ONE native call with one host wait (``opd_detr_detect_frames_hybrid``): the kept
+        records enter ``lwt`` (a ``HipLightweightTracker``) where they lie on the device, and the gray pyramid of the new reference frame
+        is built from the frame the detector has uploaded already.  Returns the detections with ``track_id`` set; same ids, track states
+        and flow points as the two calls.  Needs ``device_nms=True``, a frame that goes down as a frame list, both handles on one GPU and
+        ``lwt.max_tracks >= num_queries``; otherwise the two calls run one after the other.  No feature rows: ``det.features`` is None."""
+        self._require_model()
+        self._sync_nms()
+        target = self._frame_list_target([frame]) if (self.frame_lists and isinstance(frame, np.ndarray)) else None
+        Q = self._info.num_queries
+        if self._nms_set is None or target is None or lwt.device != self.device_ordinal or lwt.max_tracks < Q:
+            return lwt.update_with_detections(frame, self.detect(frame))
+        h, w = int(frame.shape[0]), int(frame.shape[1])
+        lwt._ensure(h, w)
+        recs, counts = (_capi.OpdDet * Q)(), (C.c_int32 * 1)()
+        ids = np.full(Q, -1, np.int32)
+        ptrs, handles = (C.c_void_p * 1)(frame.ctypes.data), (C.c_void_p * 1)(lwt._h.value)
+        rc = self._lib.opd_detr_detect_frames_hybrid(C.c_void_p(self.model), handles, ptrs, 1, h, w, target[0], target[1], float(self.confidence_threshold),
+                                                     PERSON_LABEL, recs, counts, ids.ctypes.data)
+        _capi.check(rc, "opd_detr_detect_frames_hybrid")
+        self._last_orig = [(h, w)]
+        detections = self._postprocess_batch(recs, counts, Q)[0]
+        return lwt._adopt(detections, ids[:len(detections)].tolist())
+
+    def track_hybrid_batch(self, frames: Sequence[np.ndarray], lwt, key_frames: Sequence) -> list:
+        """The reference's hybrid loop over CONSECUTIVE frames of one camera: ``key_frames[f]`` true makes frame f a detection frame
+        (``detect_and_track_hybrid``), false an in-between frame (``lwt.interpolate``).  Returns one entry per frame: a ``List[Detection]``
+        for a key frame, a ``List[(track_id, bbox)]`` for an in-between frame -- what the per-frame loop returns, ids and track states
+        included.  The frames go down in runs of at most ``max_batch`` key frames and 64 frames, each run ONE native call with one batched
+        forward and one host wait (``opd_detr_detect_sequence_hybrid``).  Where the conditions of ``detect_and_track_hybrid`` fail, the
+        per-frame loop runs instead."""
+        self._require_model()
+        frames, keys = list(frames), [bool(k) for k in key_frames]
+        if len(keys) != len(frames):
+            raise ValueError(f"{len(frames)} frames, {len(keys)} key flags")
+        out: list = []
+        start = 0
+        while start < len(frames):
+            end, n_key = start, 0   # the longest run from `start` within the limits of one call
+            while end < len(frames) and end - start < lwt.SEQUENCE_MAX and (not keys[end] or n_key < self.max_batch):
+                n_key += keys[end]
+                end += 1
+            out.extend(self._track_hybrid_run(frames[start:end], lwt, keys[start:end]))
+            start = end
+        return out
+
+    def _track_hybrid_run(self, frames: List[np.ndarray], lwt, keys: List[bool]) -> list:
+        self._sync_nms()
+        target = self._frame_list_target(frames) if (self.frame_lists and all(isinstance(f, np.ndarray) for f in frames)) else None
+        Q = self._info.num_queries
+        fused = self._nms_set is not None and target is not None and lwt.device == self.device_ordinal and lwt.max_tracks >= Q
+        h, w = (int(frames[0].shape[0]), int(frames[0].shape[1])) if target is not None else (0, 0)
+        if fused and not any(keys) and not lwt._h:   # (no handle yet and no detection frame to make one: nothing to interpolate)
+            fused = False
+        if not fused:
+            return [lwt.update_with_detections(f, self.detect(f)) if k else lwt.interpolate(f) for f, k in zip(frames, keys)]
+        lwt._ensure(h, w)
+        F, K = len(frames), sum(keys)
+        cap = lwt.max_tracks
+        recs, counts, ids = (_capi.OpdDet * (max(K, 1) * Q))(), (C.c_int32 * max(K, 1))(), np.full(max(K, 1) * Q, -1, np.int32)
+        lrecs, lcounts, done = (_capi.OpdLwtRec * (max(F - K, 1) * cap))(), (C.c_int32 * max(F - K, 1))(), C.c_int32(0)
+        ptrs = (C.c_void_p * F)(*[f.ctypes.data for f in frames])
+        flags = (C.c_uint8 * F)(*[int(k) for k in keys])
+        rc = self._lib.opd_detr_detect_sequence_hybrid(C.c_void_p(self.model), lwt._h, ptrs, flags, F, h, w, target[0], target[1], float(self.confidence_threshold),
+                                                       PERSON_LABEL, recs, counts, ids.ctypes.data, lrecs, cap, lcounts, C.byref(done))
+        _capi.check(rc, "opd_detr_detect_sequence_hybrid")
+        self._last_orig = [(h, w)] * K
+        per_key = self._postprocess_batch(recs, counts, Q) if K else []
+        out, k, j = [], 0, 0
+        for f in range(F):
+            if keys[f]:
+                out.append(lwt._adopt(per_key[k], ids[k * Q:k * Q + len(per_key[k])].tolist()))
+                k += 1
+            else:
+                out.append([(int(lrecs[j * cap + i].track_id), tuple(float(v) for v in lrecs[j * cap + i].bbox)) for i in range(lcounts[j])])
+                j += 1
+        return out
+
     def _fused_track_target(self, frames: Sequence[np.ndarray], tracker, features: Optional[str], reid) -> Optional[Tuple[int, int]]:
         """The model input size when ``frames`` can enter ``tracker`` inside the detect call (``detect_and_track`` has the conditions), else None."""
         target = self._frame_list_target(frames) if (self.frame_lists and all(isinstance(f, np.ndarray) for f in frames)) else None

@@ -4,7 +4,9 @@ on the device.
 ``update_with_detections`` is one ``opd_lwt_update`` and ``interpolate`` one ``opd_lwt_interpolate`` (``csrc/kernels_lwt.hip``,
 ``csrc/opd_lwt.cpp``): Kalman filters, IoU matching, ids, counters and the flow points live in the handle's device memory, the gray
 pyramid and Lucas-Kanade launches of the flow handle run on the same stream, and each call waits for the device once.  What comes back is
-what the reference returns: ids, and ``(track_id, bbox)`` pairs.  ``tracks`` reads the device state back on demand.  In
+what the reference returns: ids, and ``(track_id, bbox)`` pairs.  ``tracks`` reads the device state back on demand.
+``interpolate_sequence`` runs up to 64 in-between frames behind one wait (``opd_lwt_interpolate_sequence``), and
+``HipDetrDetector.detect_and_track_hybrid`` / ``track_hybrid_batch`` take the tracker inside the detect call, with the same results.  In
 ``TrackingPhase.initialize`` the swap is one line:
 
     self.lightweight_tracker = HipLightweightTracker(max_age=..., iou_threshold=..., use_optical_flow=...)"""
@@ -84,7 +86,11 @@ class HipLightweightTracker:
         self._ensure(h, w)
         ids = np.full(max(n, 1), -1, np.int32)
         _capi.check(self._lib.opd_lwt_update(self._h, ptr, kind, h, w, boxes.ctypes.data_as(C.c_void_p), n, ids.ctypes.data_as(C.c_void_p)), "opd_lwt_update")
-        for det, tid in zip(detections, ids[:n].tolist()):
+        return self._adopt(detections, ids[:n].tolist())
+
+    def _adopt(self, detections: Sequence, ids: Sequence[int]) -> Sequence:
+        """The host half of a detection frame, behind ``opd_lwt_update`` or the fused detect call (``detect_and_track_hybrid``)."""
+        for det, tid in zip(detections, ids):
             det.track_id = tid
             if det.features is not None:
                 self._features.setdefault(tid, det.features)   # (a track keeps the feature it was created with)
@@ -101,6 +107,29 @@ class HipLightweightTracker:
         recs, n = (_capi.OpdLwtRec * max(cap, 1))(), C.c_int()
         _capi.check(self._lib.opd_lwt_interpolate(self._h, ptr, kind, h, w, recs, cap, C.byref(n)), "opd_lwt_interpolate")
         return [(int(recs[i].track_id), tuple(float(v) for v in recs[i].bbox)) for i in range(n.value)]
+
+    SEQUENCE_MAX = 64   # frames of one opd_lwt_interpolate_sequence
+
+    def interpolate_sequence(self, frames: Sequence) -> List[List[Tuple[int, Tuple[float, float, float, float]]]]:
+        """What ``[self.interpolate(f) for f in frames]`` returns, bit for bit, with one host wait for every 64 frames (one
+        ``opd_lwt_interpolate_sequence``) instead of one per frame.  With optical flow the frames share one size and lie all on the host or all
+        on the device."""
+        frames = list(frames)
+        if not self._h:
+            return [[] for _ in frames]
+        out: list = []
+        for k in range(0, len(frames), self.SEQUENCE_MAX):
+            run = [self._frame(f) for f in frames[k:k + self.SEQUENCE_MAX]]
+            if len({(kind, h, w) for _, kind, h, w, _ in run}) != 1:
+                raise ValueError("interpolate_sequence: the frames must share one size and lie all on the host or all on the device")
+            _, kind, h, w, _ = run[0]
+            ptrs = (C.c_void_p * len(run))(*[r[0] for r in run]) if self.use_optical_flow else None
+            cap = self.max_tracks
+            recs, counts = (_capi.OpdLwtRec * (cap * len(run)))(), (C.c_int32 * len(run))()
+            _capi.check(self._lib.opd_lwt_interpolate_sequence(self._h, ptrs, kind, len(run), h, w, recs, cap, counts), "opd_lwt_interpolate_sequence")
+            for f in range(len(run)):
+                out.append([(int(recs[f * cap + i].track_id), tuple(float(v) for v in recs[f * cap + i].bbox)) for i in range(counts[f])])
+        return out
 
     def reset(self) -> None:
         if self._h:
