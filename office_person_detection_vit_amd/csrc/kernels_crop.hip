@@ -3,9 +3,8 @@
 // opd_reid.cpp::stage builds on the host for opd_reid_extract.  float64, no fused multiply-adds (compiled with -ffp-contract=off, and the
 // pragma below): every thread evaluates the shared routines of opd_crop.h, so the tables are the host's bit for bit.
 //
-//   crop_select_kernel  ONE workgroup of 256 walks the [B][Q] record slots in (frame, record index) order, 256 at a time: ballot per wave,
-//                       prefix counts over the lanes and the four waves.  The order of the list depends on the records alone.  A tiled call
-//                       (opd_detr_detect_tiled_reid) hands both kernels the MERGED records instead: slots by position, boxes in float64.
+//   crop_select_kernel  ONE workgroup of 256 walks the record slots of the view (opd_records.h) in (frame, record index) order, 256 at a time:
+//                       ballot per wave, prefix counts over the lanes and the four waves.  The order of the list depends on the records alone.
 //   crop_plan_kernel    one workgroup of 256 per crop slot.  Every thread repeats the box's geometry (scalar work on the same bits); thread
 //                       j then evaluates output column j and output row j (at most out_w, out_h <= 256 each: a loop covers any spec), its
 //                       taps summed one after the other.  The source window is the min / max over the bounds (integer atomics in LDS: the
@@ -26,25 +25,18 @@ using namespace opd;
 __global__ __launch_bounds__(256) void crop_select_kernel(const CropSelectParams p) {
     __shared__ int wave_count[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = p.B * p.Q;
+    const int S = p.view.stride, n = p.view.n_frames * S;
     int seen = 0;   // persons before this round (the same in every thread)
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + tid;
         bool keep = false;
         int target = 0;
         if (i < n) {
-            const int f = i / p.Q, q = i - f * p.Q;
-            if (p.merged) {   // a tiled call: position q of frame f, named by its position (query numbers repeat between the tiles of a frame)
-                int cnt = p.counts[f];
-                cnt = cnt < 0 ? 0 : (cnt > p.Q ? p.Q : cnt);
-                if (q < cnt) {
-                    keep = p.merged[i].label == p.label;
-                    target = i;
-                }
-            } else if (q < p.counts[f]) {
-                const opd_det r = p.records[i];
-                keep = r.label == p.label && (unsigned)r.query_index < (unsigned)p.Q;
-                target = f * p.Q + r.query_index;
+            const int f = i / S, q = i - f * S;
+            if (q < record_count(p.view, f)) {
+                const int key = record_key(p.view, i);
+                keep = record_label(p.view, i) == p.label && (unsigned)key < (unsigned)S;
+                target = f * S + key;
             }
         }
         const unsigned long long mask = __ballot(keep);
@@ -90,18 +82,11 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const CropPlanParams p) 
             return;
         }
         const int i = p.rec[k];
-        frame = i / p.Q;
-        if (p.merged) {   // Detection.bbox of a merged record = (x, y, w, h) in float64, handed on as float32: each rounded once, the width not re-derived
-            const opd_tile_det g = p.merged[i];
-            bx = (double)(float)g.x; by = (double)(float)g.y;
-            bw = (double)(float)g.w; bh = (double)(float)g.h;
-        } else {
-            const opd_det r = p.records[i];
-            // Detection.bbox = (x1, y1, x2 - x1, y2 - y1) in Python floats, handed on as float32
-            bx = (double)r.x1; by = (double)r.y1;
-            bw = (double)(float)((double)r.x2 - (double)r.x1);
-            bh = (double)(float)((double)r.y2 - (double)r.y1);
-        }
+        frame = i / p.view.stride;
+        double box[4];   // Detection.bbox, handed on as float32
+        record_box64(p.view, i, box);
+        bx = (double)(float)box[0]; by = (double)(float)box[1];
+        bw = (double)(float)box[2]; bh = (double)(float)box[3];
     }
     ReidGeom g;
     crop_box_geometry(p.spec, bx, by, bw, bh, p.h, p.w, &g);

@@ -59,23 +59,15 @@ __global__ __launch_bounds__(64) void floor_kernel(const FloorParams p) {
         x = (double)b[0] + (double)b[2] / 2.0;
         y = (double)b[1] + (double)b[3];
     } else if (p.mode == FLOOR_IN_RECORDS) {
-        const int f = idx / p.Q, i = idx - f * p.Q;
-        if (i >= p.counts[f]) return;   // (uniform over the wave, as every exit here)
-        const opd_det r = p.records[idx];
-        if (r.label != p.label || (unsigned)r.query_index >= (unsigned)p.Q) return;
-        // Detection.bbox = (x1, y1, x2 - x1, y2 - y1) in Python floats, handed on as float32
-        const float bw = (float)((double)r.x2 - (double)r.x1), bh = (float)((double)r.y2 - (double)r.y1);
-        x = (double)r.x1 + (double)bw / 2.0;
-        y = (double)r.y1 + (double)bh;
-        row = f * p.Q + r.query_index;
-    } else if (p.mode == FLOOR_IN_MERGED) {
-        const int f = idx / p.Q, i = idx - f * p.Q;
-        if (i >= p.counts[f]) return;
-        const opd_tile_det r = p.merged[idx];
-        // np.asarray(d.bbox, np.float32) of HipFloorMapper.transform_records, then the boxes mode above
-        const float bx = (float)r.x, by = (float)r.y, bw = (float)r.w, bh = (float)r.h;
-        x = (double)bx + (double)bw / 2.0;
-        y = (double)by + (double)bh;
+        const int S = p.view.stride, f = idx / S, i = idx - f * S;
+        if (i >= opd::record_count(p.view, f)) return;   // (uniform over the wave, as every exit here)
+        const int key = opd::record_key(p.view, idx);
+        if ((!p.any_label && opd::record_label(p.view, idx) != p.label) || (unsigned)key >= (unsigned)S) return;
+        double box[4];   // np.asarray(d.bbox, np.float32) of HipFloorMapper.transform_records, then the boxes mode above
+        opd::record_box64(p.view, idx, box);
+        x = (double)(float)box[0] + (double)(float)box[2] / 2.0;
+        y = (double)(float)box[1] + (double)(float)box[3];
+        row = f * S + key;
     } else {
         x = p.pts[2 * (size_t)idx];
         y = p.pts[2 * (size_t)idx + 1];

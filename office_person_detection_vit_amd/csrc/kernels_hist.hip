@@ -28,27 +28,14 @@ __device__ __forceinline__ bool load_crop(const ColorParams& p, int idx, ColorCr
         *c = p.crops[idx];
         return c->row >= 0;
     }
-    const int b = idx / p.Q, i = idx - b * p.Q;
-    if (i >= p.counts[b]) return false;
-    if (p.merged) {   // a merged record of a tiled call, on the WHOLE frame b: the four doubles rounded to float32 once, as the box travels to opd_color_features
-        const opd_tile_det r = reinterpret_cast<const opd_tile_det*>(p.merged)[idx];
-        const float bx = (float)r.x, by = (float)r.y, bw = (float)r.w, bh = (float)r.h;
-        int x1, y1, x2, y2;
-        const bool ok = opd_color_rect((double)bx, (double)by, (double)bw, (double)bh, p.fh, p.fw, &x1, &y1, &x2, &y2);
-        c->row = idx;
-        c->pitch = 3 * p.fw;
-        c->w = ok ? x2 - x1 : 0;
-        c->h = ok ? y2 - y1 : 0;
-        c->src = ok ? p.frames + ((size_t)b * p.fh * p.fw + (size_t)y1 * p.fw + x1) * 3 : p.frames;
-        return true;
-    }
-    const opd_det r = reinterpret_cast<const opd_det*>(p.records)[idx];
-    if (r.label != p.label) return false;
-    // Detection.bbox = (x1, y1, x2 - x1, y2 - y1) in Python floats, handed on as float32
-    const double bw = (double)(float)((double)r.x2 - (double)r.x1), bh = (double)(float)((double)r.y2 - (double)r.y1);
+    const int b = idx / p.view.stride, i = idx - b * p.view.stride;
+    if (i >= opd::record_count(p.view, b)) return false;
+    if (!p.any_label && opd::record_label(p.view, idx) != p.label) return false;
+    double box[4];   // the box as it travels to opd_color_features: float32
+    opd::record_box64(p.view, idx, box);
     int x1, y1, x2, y2;
-    const bool ok = opd_color_rect((double)r.x1, (double)r.y1, bw, bh, p.fh, p.fw, &x1, &y1, &x2, &y2);
-    c->row = b * p.Q + r.query_index;
+    const bool ok = opd_color_rect((double)(float)box[0], (double)(float)box[1], (double)(float)box[2], (double)(float)box[3], p.fh, p.fw, &x1, &y1, &x2, &y2);
+    c->row = b * p.view.stride + opd::record_key(p.view, idx);
     c->pitch = 3 * p.fw;
     c->w = ok ? x2 - x1 : 0;
     c->h = ok ? y2 - y1 : 0;

@@ -411,12 +411,9 @@ __global__ __launch_bounds__(64) void lwt_ingest_kernel(const LwtIngestParams p)
     n = n < 0 ? 0 : (n > p.Q ? p.Q : n);
     if (threadIdx.x == 0) *p.n_out = n;
     for (int i = threadIdx.x; i < n; i += 64) {
-        const opd_det r = p.records[i];
-        const double bw = (double)r.x2 - (double)r.x1, bh = (double)r.y2 - (double)r.y1;
-        p.boxes[4 * i] = r.x1;
-        p.boxes[4 * i + 1] = r.y1;
-        p.boxes[4 * i + 2] = (float)bw;
-        p.boxes[4 * i + 3] = (float)bh;
+        double box[4];
+        opd::record_box64(p.records[i], box);
+        for (int k = 0; k < 4; ++k) p.boxes[4 * i + k] = (float)box[k];
     }
 }
 

@@ -225,58 +225,28 @@ __device__ __forceinline__ void ingest_row(const float* src, float* dst, int D, 
     }
 }
 
-// One workgroup of one wave per record slot of a frame.  A record is 32 bytes (a merged one 48) and a row at most 8 KB: the launch is bound by its
+// One workgroup of one wave per record slot of a frame (p.view: that frame alone).  A record is 32 bytes (a merged one 48) and a row at most 8 KB: the launch is bound by its
 // latency, not by bandwidth, so the geometry is many small workgroups that each finish in one round trip instead of few large ones that loop.  No LDS,
 // no barrier: the slot search ends in a wave-wide maximum.
 __global__ __launch_bounds__(TRACK_INGEST_THREADS) void track_ingest_kernel(const TrackIngestParams p) {
-    const int i = blockIdx.x, lane = threadIdx.x, D = p.D;
+    const int i = blockIdx.x, lane = threadIdx.x, D = p.D, Q = p.view.stride;
     if (p.hdr && p.hdr[TRACK_HDR_STOPPED] != 0) return;
-    int n = *p.count;
-    n = n < 0 ? 0 : (n > p.Q ? p.Q : n);
+    const int n = opd::record_count(p.view, 0);
     if (i == 0 && lane == 0) *p.n_out = n;
     if (i >= n) return;   // (the whole workgroup)
-    if (p.merged) {   // a tiled call: the frame's merged records in frame pixels (float64), feature rows by position
-        const opd_tile_det g = p.merged[i];
-        const float* row = p.rows_kind == TRACK_ROWS_BY_POSITION ? p.rows + ((size_t)p.frame * p.Q + i) * D : nullptr;
-        if (p.rows_kind == TRACK_ROWS_BY_SLOT) {   // the Re-ID rows of a tiled call: the slot whose entry names this position, as the record form below
-            int filled = *p.n_person;
-            filled = filled < p.slots ? filled : p.slots;
-            const int want = p.frame * p.Q + i;
-            int k = -1;
-            for (int s = lane; s < filled; s += TRACK_INGEST_THREADS)
-                if (p.slot_map[s] == want) k = s;   // (a position gets one slot at most)
-            for (int o = 32; o > 0; o >>= 1) {
-                const int other = __shfl_xor(k, o);
-                k = other > k ? other : k;
-            }
-            if (k >= 0) row = p.rows + (size_t)k * D;
-        }
-        if (lane == 0) {
-            // the box as HipTracker.update's float32 array takes det.bbox, each double rounded once; the foot point as detect_tiled fills camera_coords, in
-            // float64 from the unrounded doubles, rounded where update stores it (not the foot point of the rounded box)
-            p.boxes[4 * i] = (float)g.x;
-            p.boxes[4 * i + 1] = (float)g.y;
-            p.boxes[4 * i + 2] = (float)g.w;
-            p.boxes[4 * i + 3] = (float)g.h;
-            p.foot[2 * i] = (float)(g.x + g.w / 2);
-            p.foot[2 * i + 1] = (float)(g.y + g.h);
-            p.has[i] = row != nullptr;
-        }
-        if (row) ingest_row(row, p.feat + (size_t)i * D, D, lane);
-        return;
-    }
-    const opd_det r = p.records[i];
+    const int key = opd::record_key(p.view, i);
+    const bool named = (unsigned)key < (unsigned)Q;
     const float* src = nullptr;
-    if (p.rows_kind == TRACK_ROWS_BY_QUERY) {
-        if ((unsigned)r.query_index < (unsigned)p.Q) src = p.rows + ((size_t)p.frame * p.Q + r.query_index) * D;
-    } else if (p.rows_kind == TRACK_ROWS_BY_SLOT) {
+    if (p.rows_kind == TRACK_ROWS_BY_KEY) {
+        if (named) src = p.rows + ((size_t)p.frame * Q + key) * D;
+    } else if (p.rows_kind == TRACK_ROWS_BY_SLOT) {   // the slot whose entry names this record; a record without one enters with has = 0
         int filled = *p.n_person;
         filled = filled < p.slots ? filled : p.slots;
-        const int want = p.frame * p.Q + r.query_index;
+        const int want = p.frame * Q + key;
         int k = -1;
-        if ((unsigned)r.query_index < (unsigned)p.Q)
+        if (named)
             for (int s = lane; s < filled; s += TRACK_INGEST_THREADS)
-                if (p.slot_map[s] == want) k = s;   // (a query index names one record of a frame at most)
+                if (p.slot_map[s] == want) k = s;   // (a key names one record of a frame at most)
         for (int o = 32; o > 0; o >>= 1) {
             const int other = __shfl_xor(k, o);
             k = other > k ? other : k;
@@ -284,14 +254,13 @@ __global__ __launch_bounds__(TRACK_INGEST_THREADS) void track_ingest_kernel(cons
         if (k >= 0) src = p.rows + (size_t)k * D;
     }
     if (lane == 0) {
-        // the values detector.py::_postprocess_batch and HipTracker.update hand to opd_track_update: differences and sums in double, rounded once
-        const double bw = (double)r.x2 - (double)r.x1, bh = (double)r.y2 - (double)r.y1;
-        p.boxes[4 * i] = r.x1;
-        p.boxes[4 * i + 1] = r.y1;
-        p.boxes[4 * i + 2] = (float)bw;
-        p.boxes[4 * i + 3] = (float)bh;
-        p.foot[2 * i] = (float)((double)r.x1 + bw / 2);
-        p.foot[2 * i + 1] = (float)((double)r.y1 + bh);
+        // the values HipTracker.update hands to opd_track_update: the float32 box, and the foot point as camera_coords holds it, in float64 from the
+        // UNROUNDED box and rounded where update stores it (not the foot point of the rounded box)
+        double box[4];
+        opd::record_box64(p.view, i, box);
+        for (int k = 0; k < 4; ++k) p.boxes[4 * i + k] = (float)box[k];
+        p.foot[2 * i] = (float)(box[0] + box[2] / 2);
+        p.foot[2 * i + 1] = (float)(box[1] + box[3]);
         p.has[i] = src != nullptr;
     }
     if (src != nullptr) ingest_row(src, p.feat + (size_t)i * D, D, lane);
@@ -648,14 +617,13 @@ hipError_t opd_launch_track_assoc(const TrackAssocParams& p, hipStream_t stream)
 }
 
 hipError_t opd_launch_track_ingest(const TrackIngestParams& p, hipStream_t stream) {
-    if (p.Q < 1 || p.Q > TRACK_MAX_DETS || p.D < 1 || p.D > TRACK_MAX_DIM || p.frame < 0 || p.slots < 0) return hipErrorInvalidValue;
-    if (p.rows_kind != TRACK_ROWS_NONE && p.rows_kind != TRACK_ROWS_BY_QUERY && p.rows_kind != TRACK_ROWS_BY_SLOT && p.rows_kind != TRACK_ROWS_BY_POSITION) return hipErrorInvalidValue;
-    // (merged records carry no usable query index: their rows go by position, and only theirs, or by slots that name positions)
-    if (p.merged ? p.rows_kind == TRACK_ROWS_BY_QUERY : (p.rows_kind == TRACK_ROWS_BY_POSITION || !p.records)) return hipErrorInvalidValue;
-    if (!p.count || !p.boxes || !p.foot || !p.has || !p.n_out) return hipErrorInvalidValue;
+    const int Q = p.view.stride;
+    if (Q < 1 || Q > TRACK_MAX_DETS || p.D < 1 || p.D > TRACK_MAX_DIM || p.frame < 0 || p.slots < 0) return hipErrorInvalidValue;
+    if (p.rows_kind != TRACK_ROWS_NONE && p.rows_kind != TRACK_ROWS_BY_KEY && p.rows_kind != TRACK_ROWS_BY_SLOT) return hipErrorInvalidValue;
+    if (!p.view.records == !p.view.merged || !p.view.counts || !p.boxes || !p.foot || !p.has || !p.n_out) return hipErrorInvalidValue;
     if (p.rows_kind != TRACK_ROWS_NONE && (!p.rows || !p.feat)) return hipErrorInvalidValue;
     if (p.rows_kind == TRACK_ROWS_BY_SLOT && (!p.slot_map || !p.n_person)) return hipErrorInvalidValue;
-    OPD_LAUNCH(track_ingest_kernel, dim3(p.Q), dim3(TRACK_INGEST_THREADS), 0, stream, p);
+    OPD_LAUNCH(track_ingest_kernel, dim3(Q), dim3(TRACK_INGEST_THREADS), 0, stream, p);
     return hipGetLastError();
 }
 

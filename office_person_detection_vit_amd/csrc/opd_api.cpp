@@ -235,56 +235,62 @@ static int enqueue_tile_merge(opd_detr* m, const TileStage& t) {
     return launch(m, m->stream, CLS_OTHER, 0.0, [&] { return opd_launch_tile_merge(mp, m->stream); });
 }
 
-// The feature stage, on the records the post-process left on the device.  (h, w): the camera resolution of the frames at d_camera (FEAT_COLOR, FEAT_REID).
-// Returns in *rows what a tracker behind it may read: nothing, a row per query in d_feat_all, or a row per slot of the Re-ID call.  `reid` is
+// The records of a call behind the tile merge, said once for the stages below.  `view` (opd_records.h): where they lie on the device, d_records / d_counts
+// [B][Q], or (a tiled call) the merged records [n_frames][n_tiles x Q].  `any_label`: the colour and floor stages take every record of a tiled call, not
+// only those labelled s.label.  The rest describes the copy the call delivers to the host, for finish_trackers: record i of frame f has its confidence
+// at score[(f * view.stride + i) * score_stride] (floats), frame f has counts[f] records; `entry`: the entry point's name, for errors.
+struct CallRecords {
+    RecordView view;
+    int any_label;
+    const float* score;
+    int score_stride;
+    const int32_t* counts;
+    const char* entry;
+};
+static CallRecords call_records(const opd_detr* m, const RecordSink& s, bool tiled) {
+    if (tiled)
+        return {RecordView{nullptr, merged_records(m), merged_counts(m), s.tile.n_frames, s.tile.n_tiles * m->arch.queries}, 1,
+                s.tile.out ? &s.tile.out->score : nullptr, (int)(sizeof(opd_tile_det) / sizeof(float)), s.tile.counts, s.tile.entry};
+    return {RecordView{m->d_records, nullptr, m->d_counts, m->last_B, m->arch.queries}, 0,
+            s.out ? &s.out->score : nullptr, (int)(sizeof(opd_det) / sizeof(float)), s.counts, "opd_detr_detect_frames_track"};
+}
+
+// The feature stage, on the records of the call.  (h, w): the camera resolution of the frames at d_camera (FEAT_COLOR, FEAT_REID; a tiled call: the WHOLE frames).
+// Returns in *rows what a tracker behind it may read: nothing, a row per key in d_feat_all, or a row per slot of the Re-ID call.  `reid` is
 // the caller's: the call holds the Re-ID handle's lock and must outlive the wait.
-static int enqueue_features(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera, std::optional<ReidFusedCall>* reid, TrackFeatureSource* rows) {
-    const int B = m->last_B, Q = m->arch.queries;
+static int enqueue_features(opd_detr* m, const RecordSink& s, const CallRecords& c, int h, int w, const uint8_t* d_camera, std::optional<ReidFusedCall>* reid,
+                            TrackFeatureSource* rows) {
     const FeatureStage& f = s.feature;
     *rows = TrackFeatureSource{};
     if (f.kind == FEAT_NONE) return OPD_OK;
-    if (f.kind == FEAT_REID) {   // select, plan and the Re-ID forward behind the post-process; the rows come back behind the records, before the one wait
-        const bool tiled = s.tile.params != nullptr;   // a tiled call: the MERGED records, crops cut from the WHOLE frames at d_camera; a slot names a position
-        const ReidRecordView view = tiled ? ReidRecordView{nullptr, merged_records(m), merged_counts(m), s.tile.n_frames, s.tile.n_tiles * Q}
-                                          : ReidRecordView{m->d_records, nullptr, m->d_counts, B, Q};
+    if (f.kind == FEAT_REID) {   // select, plan and the Re-ID forward behind the records; the rows come back behind the records, before the one wait
         reid->emplace(f.reid);
-        RCCHK((*reid)->enqueue(m->stream, view, d_camera, h, w, s.label, f.slots));
-        // (a tracker reads the rows where the forward left them; the slot list alone comes back, unless a tiled call asks for the rows as well)
-        (*reid)->with_rows = tiled ? f.features != nullptr : !s.track.on();
+        RCCHK((*reid)->enqueue(m->stream, c.view, d_camera, h, w, s.label, f.slots));
+        // (the rows come back only where the caller takes them: a tracker reads them where the forward left them, and the slot list alone comes back)
+        // (this rests on the entries: opd_detr_detect_frames_reid refuses a null `features`, detect_track never sets it, the tiled entry passes the caller's)
+        (*reid)->with_rows = f.features != nullptr;
         *rows = {TRACK_ROWS_BY_SLOT, reid_feature_dim(f.reid), (*reid)->dev_rows(), (*reid)->dev_slot_map(), (*reid)->dev_n_person(), f.slots};
         return OPD_OK;
     }
-    if (s.tile.params) {   // a tiled call (FEAT_COLOR, the entry's check): crops of the merged records, cut from the WHOLE frames at d_camera; a row per position
-        RCCHK(ensure(m, &m->d_color_acc, slots_of(m) * OPD_COLOR_ACC_WORDS));
-        ColorParams cp{};
-        cp.merged = merged_records(m); cp.counts = merged_counts(m); cp.frames = d_camera; cp.acc = m->d_color_acc; cp.out = m->d_feat_all;
-        cp.Q = s.tile.n_tiles * Q; cp.fh = h; cp.fw = w; cp.label = s.label; cp.n = B * Q;
-        HIPCHK(opd_launch_color_features(cp, std::min(64, (h + 15) / 16), m->stream));
-        *rows = {TRACK_ROWS_BY_POSITION, OPD_COLOR_DIM, m->d_feat_all, nullptr, nullptr, 0};
-        return OPD_OK;
-    }
-    if (f.kind == FEAT_ROI)
-        HIPCHK(opd_launch_roi_features_records(m->d_x32, m->d_records, m->d_counts, m->d_orig_hw, s.label, m->d_feat_all, B, Q, m->last_fh, m->last_fw, m->stream));
+    if (f.kind == FEAT_ROI)   // (no tiled entry asks for it: the pooled map is a tile's)
+        HIPCHK(opd_launch_roi_features_records(m->d_x32, m->d_records, m->d_counts, m->d_orig_hw, s.label, m->d_feat_all, m->last_B, m->arch.queries, m->last_fh, m->last_fw, m->stream));
     if (f.kind == FEAT_COLOR) {   // the histogram kernels read the CAMERA-resolution frames under the boxes of the records
         RCCHK(ensure(m, &m->d_color_acc, slots_of(m) * OPD_COLOR_ACC_WORDS));
         ColorParams cp{};
-        cp.records = m->d_records; cp.counts = m->d_counts; cp.frames = d_camera; cp.acc = m->d_color_acc; cp.out = m->d_feat_all;
-        cp.Q = Q; cp.fh = h; cp.fw = w; cp.label = s.label; cp.n = B * Q;
+        cp.view = c.view; cp.frames = d_camera; cp.acc = m->d_color_acc; cp.out = m->d_feat_all;
+        cp.fh = h; cp.fw = w; cp.label = s.label; cp.any_label = c.any_label; cp.n = c.view.n_frames * c.view.stride;
         HIPCHK(opd_launch_color_features(cp, std::min(64, (h + 15) / 16), m->stream));
     }
-    rows->rows_kind = TRACK_ROWS_BY_QUERY; rows->D = m->arch.d_model; rows->rows = m->d_feat_all;
+    rows->rows_kind = TRACK_ROWS_BY_KEY; rows->D = m->arch.d_model; rows->rows = m->d_feat_all;
     return OPD_OK;
 }
 
-// The floor stage: the floor record of every record of the class, from the box the Python shim derives, while the records are on the device
-static int enqueue_floor(opd_detr* m, const RecordSink& s) {
+// The floor stage: the floor record of every record the stage takes, from the box the Python shim derives, while the records are on the device
+static int enqueue_floor(opd_detr* m, const RecordSink& s, const CallRecords& c) {
     RCCHK(ensure(m, &m->d_floor, slots_of(m), (void**)&m->h_floor));
     FloorParams fp{};
-    fp.m = s.floor.fmap->model; fp.mode = FLOOR_IN_RECORDS; fp.n = m->last_B * m->arch.queries;
-    fp.records = m->d_records; fp.counts = m->d_counts; fp.Q = m->arch.queries; fp.label = s.label; fp.out = m->d_floor;
-    if (s.tile.params) {   // a tiled call: the merged records, a row per position
-        fp.mode = FLOOR_IN_MERGED; fp.merged = merged_records(m); fp.counts = merged_counts(m); fp.Q = s.tile.n_tiles * m->arch.queries;
-    }
+    fp.m = s.floor.fmap->model; fp.mode = FLOOR_IN_RECORDS; fp.n = c.view.n_frames * c.view.stride;
+    fp.view = c.view; fp.label = s.label; fp.any_label = c.any_label; fp.out = m->d_floor;
     HIPCHK(opd_launch_floor(fp, m->stream));
     return OPD_OK;
 }
@@ -292,34 +298,21 @@ static int enqueue_floor(opd_detr* m, const RecordSink& s) {
 // The tracker half of a fused detect-and-track call (opd_track.h), around the one wait of fetch_records.  Before it: every tracker's ingest and
 // predict / cost launches on m->stream, behind the feature stage.  After it: association and commit per tracker; a tracker out of slots does not
 // keep the others from being committed, and its error is the call's.
-static int enqueue_trackers(opd_detr* m, const RecordSink& s, const TrackFeatureSource& src) {
-    const int B = m->last_B, Q = m->arch.queries;
+static int enqueue_trackers(opd_detr* m, const RecordSink& s, const CallRecords& c, const TrackFeatureSource& src) {
     const TrackStage& t = s.track;
-    if (s.tile.params) {   // a tiled call: a tracker per FRAME, on its merged records
-        const int S = s.tile.n_tiles * Q;
-        for (int f = 0; f < s.tile.n_frames; ++f)
-            RCCHK(track_fused_enqueue(t.trackers[f], m->stream, nullptr, merged_counts(m) + f, S, f, src, merged_records(m) + (size_t)f * S));
-        return OPD_OK;
-    }
-    if (t.seq) return track_sequence_enqueue(t.seq, m->stream, m->d_records, m->d_counts, Q, B, src, "opd_detr_detect_sequence_track");
-    for (int b = 0; b < B; ++b) RCCHK(track_fused_enqueue(t.trackers[b], m->stream, m->d_records + (size_t)b * Q, m->d_counts + b, Q, b, src));
+    if (t.seq) return track_sequence_enqueue(t.seq, m->stream, c.view.records, c.view.counts, c.view.stride, c.view.n_frames, src, "opd_detr_detect_sequence_track");
+    for (int f = 0; f < c.view.n_frames; ++f) RCCHK(track_fused_enqueue(t.trackers[f], m->stream, record_frame(c.view, f), f, src));
     return OPD_OK;
 }
-static int finish_trackers(opd_detr* m, const RecordSink& s, bool with_features) {
-    const int B = m->last_B, Q = m->arch.queries;
+static int finish_trackers(opd_detr* m, const RecordSink& s, const CallRecords& c, bool with_features) {
     const TrackStage& t = s.track;
-    if (t.seq) return track_sequence_finish(t.seq, s.counts, Q, B, t.track_ids, t.frames_done, "opd_detr_detect_sequence_track");
+    const int frames = c.view.n_frames, stride = c.view.stride;
+    if (t.seq) return track_sequence_finish(t.seq, c.counts, stride, frames, t.track_ids, t.frames_done, "opd_detr_detect_sequence_track");
     int rc = OPD_OK;
     std::string first;
-    // the confidences of the records the call delivered: per frame [Q] opd_det, or (a tiled call) [S] merged records
-    const bool tiled = s.tile.params != nullptr;
-    const int frames = tiled ? s.tile.n_frames : B, stride = tiled ? s.tile.n_tiles * Q : Q;
-    const int32_t* counts = tiled ? s.tile.counts : s.counts;
     for (int b = 0; b < frames; ++b) {
-        const int n = std::max(0, std::min(counts[b], stride));
-        const float* conf = tiled ? &s.tile.out[(size_t)b * stride].score : &s.out[(size_t)b * stride].score;
-        const int one = track_fused_finish(t.trackers[b], conf, (int)((tiled ? sizeof(opd_tile_det) : sizeof(opd_det)) / sizeof(float)), n, with_features,
-                                           t.track_ids + (size_t)b * stride, tiled ? s.tile.entry : "opd_detr_detect_frames_track");
+        const int n = std::max(0, std::min(c.counts[b], stride));
+        const int one = track_fused_finish(t.trackers[b], c.score + (size_t)b * stride * c.score_stride, c.score_stride, n, with_features, t.track_ids + (size_t)b * stride, c.entry);
         if (one != OPD_OK && rc == OPD_OK) { rc = one; first = g_err; }
     }
     return rc == OPD_OK ? OPD_OK : fail(rc, first);
@@ -416,7 +409,7 @@ static int hand_to_ticket(opd_detr* m, const RecordSink& s) {
 
 // The back half, on the outputs of the last forward (opd_detr_postprocess enters here): the stages of the sink in their one order, each skipped when its
 // part is absent.  (h, w): the size the boxes are scaled to (0: the model resolution); d_camera: the source's frames on the device at camera resolution.
-// In a tiled call the feature, floor and track stages read the MERGED records (rows by position), not d_records.
+// The feature, floor and track stages read the records of the call through ONE view (call_records): in a tiled call the MERGED records, not d_records.
 // The feature, floor, track and tile parts deliver to the host after the call's own wait: setting one with WAIT_TICKET or WAIT_NONE, or with device
 // outputs, is a programming error (no entry point does).
 static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera) {
@@ -427,9 +420,10 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
     if (tiled) RCCHK(enqueue_tile_merge(m, s.tile));
     std::optional<ReidFusedCall> reid;   // (lives until the rows are delivered)
     TrackFeatureSource rows;
-    RCCHK(enqueue_features(m, s, tiled ? s.tile.frame_h : h, tiled ? s.tile.frame_w : w, d_camera, &reid, &rows));
-    if (s.floor.fmap) RCCHK(enqueue_floor(m, s));
-    if (tracked) RCCHK(enqueue_trackers(m, s, rows));
+    const CallRecords recs = call_records(m, s, tiled);
+    RCCHK(enqueue_features(m, s, recs, tiled ? s.tile.frame_h : h, tiled ? s.tile.frame_w : w, d_camera, &reid, &rows));
+    if (s.floor.fmap) RCCHK(enqueue_floor(m, s, recs));
+    if (tracked) RCCHK(enqueue_trackers(m, s, recs, rows));
     if (s.hybrid.on()) RCCHK(enqueue_hybrid(m, s, h, w, d_camera));
     if (s.wait == WAIT_NONE) return OPD_OK;
     if (s.wait == WAIT_TICKET) return hand_to_ticket(m, s);
@@ -449,7 +443,7 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
             reid->deliver(s.feature.features, s.feature.slot_map, s.feature.n_person);
             if (tracked) reid->slots_per_frame(s.tile.n_frames, S, s.track.n_featured);
         }
-        return tracked ? finish_trackers(m, s, rows.rows_kind != TRACK_ROWS_NONE) : OPD_OK;
+        return tracked ? finish_trackers(m, s, recs, rows.rows_kind != TRACK_ROWS_NONE) : OPD_OK;
     } else if (!dev) unpack_records(m, m->sync_pinned, B, s.out, s.counts, query_rows_out(s));
     if (reid && !tracked) reid->deliver(s.feature.features, s.feature.slot_map, s.feature.n_person);
     if (s.floor.fmap)   // only rows of records of the class are handed on
@@ -462,7 +456,7 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
     if (!tracked) return OPD_OK;
     if (reid) reid->slots_per_frame(B, Q, s.track.n_featured);
     else for (int b = 0; b < B; ++b) s.track.n_featured[b] = rows.rows_kind == TRACK_ROWS_NONE ? 0 : std::max(0, std::min(s.counts[b], Q));
-    return finish_trackers(m, s, rows.rows_kind != TRACK_ROWS_NONE);
+    return finish_trackers(m, s, recs, rows.rows_kind != TRACK_ROWS_NONE);
 }
 
 // The front half: the source step and the forward.  The launch timer starts anew here, once per call: the source's launches, the forward's and the

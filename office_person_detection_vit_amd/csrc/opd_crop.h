@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/opd_detr.h"
+#include "opd_records.h"
 
 namespace opd {
 
@@ -147,24 +148,21 @@ inline CropSlots crop_slots(const CropSpec& spec, int h, int w) {
     return s;
 }
 
-// crop_select_kernel: the records [B][Q] labelled `label`, in (frame, record index) order -> slot[k] = frame * Q + query_index and
-// rec[k] = frame * Q + record index for k < slots, and their number *n_person (which may exceed slots).  `merged` (non-null: a tiled call, Q =
-// n_tiles x queries): the MERGED records [B][Q] instead, position k of frame f kept when k < clamp(counts[f], 0, Q) and its label is `label`;
-// slot[k'] = rec[k'] = f * Q + k (two tiles of a frame use the same query numbers: query_index names nothing here)
+// crop_select_kernel: the records of the view (opd_records.h) that count, are labelled `label` and have a valid key, in (frame, record index) order
+// -> slot[k] = frame * stride + record_key and rec[k] = frame * stride + record index for k < slots, and their number *n_person (which may exceed slots)
 struct CropSelectParams {
-    const opd_det* records; const opd_tile_det* merged; const int32_t* counts;
-    int B, Q, label, slots;
+    RecordView view;
+    int label, slots;
     int32_t *slot, *rec, *n_person;
 };
-// crop_plan_kernel: one workgroup per crop slot k < nb writes crops[k] and its tables at base + tables_off + k * stride.  The box is that
-// of record rec[k] (k < min(*n_person, slots), else a zero crop) or, for the test hook, boxes[k] on frame 0.  `merged` (non-null: a tiled call):
-// the box of MERGED record rec[k] instead, x, y, w, h each rounded to float32 once and widened back (the width is not re-derived).
+// crop_plan_kernel: one workgroup per crop slot k < nb writes crops[k] and its tables at base + tables_off + k * stride.  The box is the float32 box
+// of record rec[k] of the view (k < min(*n_person, slots), else a zero crop) or, for the test hook, boxes[k] on frame 0.
 struct CropPlanParams {
     CropSpec spec;
-    const opd_det* records; const opd_tile_det* merged; const int32_t* rec; const int32_t* n_person;
+    RecordView view; const int32_t* rec; const int32_t* n_person;
     const float* boxes;           // non-null: [nb][4] xywh instead of the records
-    const uint8_t* frames;        // [B][h][w][3]
-    int Q, h, w, slots;
+    const uint8_t* frames;        // [n_frames][h][w][3]
+    int h, w, slots;
     unsigned char* base;          // the upload base: crops at 0
     size_t tables_off, stride;
     int ksh_max, ksv_max;

@@ -85,7 +85,7 @@ TAPI int opd_test_crop_plan_device(int model, const float* boxes, int n, int H, 
     if (!dm.ok) return fail(OPD_ENOMEM, "test alloc failed");
     CropPlanParams p{};
     p.spec = *spec;
-    p.boxes = dboxes; p.frames = frame; p.Q = 1; p.h = H; p.w = W; p.slots = n;
+    p.boxes = dboxes; p.frames = frame; p.h = H; p.w = W; p.slots = n;
     p.base = base; p.tables_off = tables_off; p.stride = cs.stride; p.ksh_max = cs.ksh_max; p.ksv_max = cs.ksv_max;
     p.geom = dgeom;
     HIPCHK(opd_launch_crop_plan(p, n, nullptr));

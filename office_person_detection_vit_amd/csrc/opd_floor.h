@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "opd_device.h"
+#include "opd_records.h"
 
 enum { FLOOR_TRI_LD = 8, FLOOR_AFF_LD = 6, FLOOR_EDGE_LD = 4 };
 
@@ -28,18 +29,16 @@ struct FloorModel {
     const int32_t* zone_rank;              // [n_zones]: position of the zone when sorted by (priority or +inf, index)
 };
 
-enum { FLOOR_IN_BOXES, FLOOR_IN_POINTS, FLOOR_IN_RECORDS, FLOOR_IN_FLOOR, FLOOR_IN_MERGED };   // what a wave starts from
+enum { FLOOR_IN_BOXES, FLOOR_IN_POINTS, FLOOR_IN_RECORDS, FLOOR_IN_FLOOR };   // what a wave starts from
 struct FloorParams {
     FloorModel m;
     int32_t mode, n;
     const float* boxes;        // FLOOR_IN_BOXES: [n][4] x, y, w, h
     const double* pts;         // FLOOR_IN_POINTS: [n][2] camera pixels.  FLOOR_IN_FLOOR: [n][2] floor pixels (zones only)
-    const opd_det* records;    // FLOOR_IN_RECORDS: [n / Q][Q] records of the post-process, counts per frame; only those labelled `label`
-    const opd_tile_det* merged;   // FLOOR_IN_MERGED: [n / Q][Q] merged records of a tiled call (Q = n_tiles x queries), counts per frame; the box is
-                                  // x, y, w, h each rounded to float32 once, then the foot point of FLOOR_IN_BOXES
-    const int32_t* counts;
-    int32_t Q, label;
-    opd_floor_rec* out;        // [n]; FLOOR_IN_RECORDS: row frame * Q + query_index.  FLOOR_IN_MERGED: row frame * Q + position
+    opd::RecordView view;      // FLOOR_IN_RECORDS: the n = n_frames * stride record slots of a detect call (opd_records.h); of those that count, the ones
+                               // with a valid key and (unless any_label) labelled `label`: the float32 box, then the foot point of FLOOR_IN_BOXES
+    int32_t label, any_label;
+    opd_floor_rec* out;        // [n]; FLOOR_IN_RECORDS: row frame * stride + record_key
     uint64_t* masks;           // FLOOR_IN_FLOOR: [n]
 };
 

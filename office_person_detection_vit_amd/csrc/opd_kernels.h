@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
+#include "opd_records.h"
 #include "opd_pack.h"   // the host-side weight packers: opd_permute_k32, opd_split_f16_frag, opd_encffn_pack
 
 typedef uint16_t f16_t;  // raw 16-bit operand bits on the host side: IEEE half (default) or bfloat16 (OPD_FLAG_BF16)
@@ -366,18 +367,15 @@ __host__ __device__ inline bool opd_color_rect(double x, double y, double w, dou
     return *x2 > *x1 && *y2 > *y1;
 }
 struct ColorParams {
-    const ColorCrop* crops;   // [n] descriptors, or null: crops come from the records below
-    // records mode (opd_detr_detect_frames_color): crop b * Q + i = record i of frame b when i < counts[b] and its class is `label`;
-    // box (x1, y1, float32(x2 - x1), float32(y2 - y1)) as the Python shim hands a Detection.bbox to opd_color_features; output row
-    // b * Q + query_index; other rows are not written
-    const void* records;      // opd_det [B][Q]
-    // merged mode (opd_detr_detect_tiled_stages; `merged` non-null, `records` unused): crop f * Q + k = merged record k of frame f when k < counts[f],
-    // Q = n_tiles x queries; box = its x, y, w, h each rounded to float32 once (np.asarray(d.bbox, np.float32)); output row f * Q + k, by POSITION
-    const void* merged;       // opd_tile_det [B][Q]
-    const int32_t* counts;    // [B]
-    const uint8_t* frames;    // [B][fh][fw][3]
-    int Q, fh, fw, label;
-    int n;                    // crops (records mode: B * Q)
+    const ColorCrop* crops;   // [n] descriptors, or null: crops come from the records of `view` (opd_records.h)
+    // records mode (opd_detr_detect_frames_color, opd_detr_detect_tiled_stages): crop f * stride + i = record i of frame f when i < record_count and
+    // (unless any_label) its class is `label`; its box rounded to float32 as the Python shim hands a Detection.bbox to opd_color_features; output
+    // row f * stride + record_key; other rows are not written
+    opd::RecordView view;
+    const uint8_t* frames;    // [n_frames][fh][fw][3]
+    int fh, fw, label;
+    int any_label;            // records mode: take the records of every class (a tiled call); `label` is not read
+    int n;                    // crops (records mode: n_frames * stride)
     uint32_t* acc;            // [n][OPD_COLOR_ACC_WORDS] scratch (zeroed by the launcher)
     float* out;               // [rows][256]
 };

@@ -236,7 +236,7 @@ ReidFusedCall::ReidFusedCall(opd_reid* r_) : r(r_), lk(r_->call_mu, std::defer_l
     lk.lock();
 }
 
-int ReidFusedCall::enqueue(hipStream_t s, const ReidRecordView& v, const uint8_t* frames, int h, int w, int label, int slots_, int32_t* geom) {
+int ReidFusedCall::enqueue(hipStream_t s, const RecordView& v, const uint8_t* frames, int h, int w, int label, int slots_, int32_t* geom) {
     slots = slots_;
     const int C = r->cfg.max_crops, E = r->model->feature_dim();
     const CropSpec& spec = r->model->crop();
@@ -246,13 +246,13 @@ int ReidFusedCall::enqueue(hipStream_t s, const ReidRecordView& v, const uint8_t
     const int nb = bucket_of(r, slots);
     int32_t* sel = reinterpret_cast<int32_t*>(r->up.dev + fused_sel_off(r));
     CropSelectParams sp{};
-    sp.records = v.records; sp.merged = v.merged; sp.counts = v.counts; sp.B = v.B; sp.Q = v.Q; sp.label = label; sp.slots = slots;
+    sp.view = v; sp.label = label; sp.slots = slots;
     sp.slot = sel; sp.rec = sel + C; sp.n_person = sel + 2 * C;
     HIPCHK(opd_launch_crop_select(sp, s));
     CropPlanParams pp{};
     pp.spec = spec;
-    pp.records = v.records; pp.merged = v.merged; pp.rec = sp.rec; pp.n_person = sp.n_person;
-    pp.frames = frames; pp.Q = v.Q; pp.h = h; pp.w = w; pp.slots = slots; pp.geom = geom;
+    pp.view = v; pp.rec = sp.rec; pp.n_person = sp.n_person;
+    pp.frames = frames; pp.h = h; pp.w = w; pp.slots = slots; pp.geom = geom;
     pp.base = r->up.dev; pp.tables_off = fused_tables_off(r); pp.stride = cs.stride;
     pp.ksh_max = cs.ksh_max; pp.ksv_max = cs.ksv_max;
     HIPCHK(opd_launch_crop_plan(pp, nb, s));

@@ -61,21 +61,13 @@ struct ReidModel {
 //   deliver    after the caller's wait on `s`: rows and slot map of k < min(n_person, slots) into the caller's arrays
 int reid_fused_check(const opd_reid* r, int device, int slots, const char* who);
 int reid_feature_dim(const opd_reid* r);
-// The records a fused call plans its crops from, on the device: [B][Q] records of the post-process with their counts, or (`merged` non-null: a tiled
-// call, opd_detr_detect_tiled_reid) the [B][Q] MERGED records in frame pixels, Q = n_tiles x queries.  Then slot_map[k] = rec[k] = frame * Q + position.
-struct ReidRecordView {
-    const opd_det* records;
-    const opd_tile_det* merged;
-    const int32_t* counts;
-    int B, Q;
-};
 struct ReidFusedCall {
     opd_reid* r;
     std::unique_lock<std::mutex> lk;
     int slots = 0;
     explicit ReidFusedCall(opd_reid* r);
     // `geom` (nullable; the test hook of opd_tile_reid_test_api.cpp): device [slots][13], the plan's geometry words of every filled slot
-    int enqueue(hipStream_t s, const ReidRecordView& v, const uint8_t* frames, int h, int w, int label, int slots, int32_t* geom = nullptr);
+    int enqueue(hipStream_t s, const RecordView& v, const uint8_t* frames, int h, int w, int label, int slots, int32_t* geom = nullptr);
     int copy_back(hipStream_t s);
     void deliver(float* features, int32_t* slot_map, int32_t* n_person) const;
     // the fused detect-and-track call: the rows stay on the device (copy_back then brings the slot list alone); where the rows, the slot map

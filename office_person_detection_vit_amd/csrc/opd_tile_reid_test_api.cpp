@@ -1,6 +1,6 @@
 // opd_tile_reid_test_api.cpp — the Re-ID stage of a tiled call on hand-made MERGED records, for tests/ (exported from libopd_hip_test.so only):
-//   opd_test_tile_reid   the merged-record readers of crop_select_kernel and crop_plan_kernel, the Re-ID forward of a real handle and the rows-by-slot
-//                        reader of track_ingest_kernel's merged branch, launched as deliver_records launches them behind tile_merge_kernel
+//   opd_test_tile_reid   crop_select_kernel and crop_plan_kernel on a view of merged records (opd_records.h), the Re-ID forward of a real handle and
+//                        track_ingest_kernel with rows by slot on the same view, launched as deliver_records launches them behind tile_merge_kernel
 //                        (ReidFusedCall::enqueue, then one ingest per frame), without a model handle: host frames [n_frames][h][w][3], merged
 //                        [n_frames][S] and counts [n_frames] of the caller; the records labelled 1 are the persons.
 #include "opd_reid.h"
@@ -45,11 +45,11 @@ TAPI int opd_test_tile_reid(int device, opd_reid* reid, const uint8_t* frames, i
     HIPCHK(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
     {
         ReidFusedCall call(reid);
-        RCCHK(call.enqueue(own.s, ReidRecordView{nullptr, d_merged, d_counts, n_frames, S}, d_frames, h, w, 1, slots, d_geom));
+        const RecordView view{nullptr, d_merged, d_counts, n_frames, S};
+        RCCHK(call.enqueue(own.s, view, d_frames, h, w, 1, slots, d_geom));
         for (int f = 0; f < n_frames; ++f) {
             TrackIngestParams p{};
-            p.merged = d_merged + (size_t)f * S; p.count = d_counts + f;
-            p.Q = S; p.D = (int)E; p.frame = f;
+            p.view = record_frame(view, f); p.D = (int)E; p.frame = f;
             p.rows_kind = TRACK_ROWS_BY_SLOT; p.rows = call.dev_rows(); p.slot_map = call.dev_slot_map(); p.n_person = call.dev_n_person(); p.slots = slots;
             p.boxes = d_boxes + (size_t)f * S * 4; p.foot = d_foot + (size_t)f * S * 2; p.has = d_has + (size_t)f * S; p.feat = d_feat + (size_t)f * S * E;
             p.n_out = d_n + f;

@@ -1,6 +1,6 @@
 // opd_tile_stages_test_api.cpp — the stage kernels of a tiled call on hand-made MERGED records, for tests/ (exported from libopd_hip_test.so only):
-//   opd_test_tile_stages   the merged-record readers of color_hist_kernel / color_finish_kernel, floor_kernel (FLOOR_IN_MERGED) and
-//                          track_ingest_kernel (rows by position), launched as deliver_records launches them behind tile_merge_kernel, without a
+//   opd_test_tile_stages   color_hist_kernel / color_finish_kernel, floor_kernel and track_ingest_kernel (rows by key) on a view of merged
+//                          records (opd_records.h), launched as deliver_records launches them behind tile_merge_kernel, without a
 //                          model handle: host frames [n_frames][h][w][3], merged [n_frames][S] and counts [n_frames] of the caller.
 #include "opd_floor.h"
 #include "opd_test_util.h"
@@ -24,14 +24,15 @@ TAPI int opd_test_tile_stages(int device, const uint8_t* frames, int n_frames, i
     DevMem dm;
     const opd_tile_det* d_merged = dm.up(merged, n);
     const int32_t* d_counts = dm.up(counts, (size_t)n_frames);
+    const RecordView view{nullptr, d_merged, d_counts, n_frames, S};
     ColorParams cp{};
-    cp.merged = d_merged; cp.counts = d_counts; cp.frames = dm.up(frames, (size_t)n_frames * h * w * 3);
+    cp.view = view; cp.frames = dm.up(frames, (size_t)n_frames * h * w * 3);
     cp.acc = dm.alloc<uint32_t>(n * OPD_COLOR_ACC_WORDS); cp.out = dm.up(color, n * D);
-    cp.Q = S; cp.fh = h; cp.fw = w; cp.label = 1; cp.n = (int)n;
+    cp.fh = h; cp.fw = w; cp.label = 1; cp.any_label = 1; cp.n = (int)n;
     FloorParams fp{};
     if (floor) {
-        fp.m = floor->model; fp.mode = FLOOR_IN_MERGED; fp.n = (int)n;
-        fp.merged = d_merged; fp.counts = d_counts; fp.Q = S; fp.out = dm.up(floor_out, n);
+        fp.m = floor->model; fp.mode = FLOOR_IN_RECORDS; fp.n = (int)n;
+        fp.view = view; fp.any_label = 1; fp.out = dm.up(floor_out, n);
     }
     float *d_boxes = dm.up(boxes, n * 4), *d_foot = dm.up(foot, n * 2), *d_feat = dm.up(feat, n * D);
     uint8_t* d_has = dm.up(has, n);
@@ -41,9 +42,8 @@ TAPI int opd_test_tile_stages(int device, const uint8_t* frames, int n_frames, i
     if (floor) HIPCHK(opd_launch_floor(fp, nullptr));
     for (int f = 0; f < n_frames; ++f) {
         TrackIngestParams p{};
-        p.merged = d_merged + (size_t)f * S; p.count = d_counts + f;
-        p.Q = S; p.D = (int)D; p.frame = f;
-        p.rows_kind = with_rows ? TRACK_ROWS_BY_POSITION : TRACK_ROWS_NONE; p.rows = with_rows ? cp.out : nullptr;
+        p.view = record_frame(view, f); p.D = (int)D; p.frame = f;
+        p.rows_kind = with_rows ? TRACK_ROWS_BY_KEY : TRACK_ROWS_NONE; p.rows = with_rows ? cp.out : nullptr;
         p.boxes = d_boxes + (size_t)f * S * 4; p.foot = d_foot + (size_t)f * S * 2; p.has = d_has + (size_t)f * S; p.feat = d_feat + (size_t)f * S * D;
         p.n_out = d_n + f;
         HIPCHK(opd_launch_track_ingest(p, nullptr));

@@ -358,8 +358,7 @@ int track_sequence_enqueue(opd_track* t, hipStream_t s, const opd_det* records, 
     int t_bound = (int)t->tracks.size();
     for (int b = 0; b < B; ++b) {
         TrackIngestParams p{};
-        p.records = records + (size_t)b * Q; p.count = counts + b;
-        p.Q = Q; p.D = t->D; p.frame = b;
+        p.view = record_frame(RecordView{records, nullptr, counts, B, Q}, b); p.D = t->D; p.frame = b;
         p.rows_kind = src.rows_kind; p.rows = src.rows; p.slot_map = src.slot_map; p.n_person = src.n_person; p.slots = src.slots;
         p.boxes = reinterpret_cast<float*>(d + t->o_boxes);
         p.foot = reinterpret_cast<float*>(d + t->o_foot);
@@ -398,8 +397,7 @@ int track_fused_check(const opd_track* t, int device, int Q, int feature_dim, co
     return OPD_OK;
 }
 
-int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* count, int Q, int frame, const TrackFeatureSource& src,
-                        const opd_tile_det* merged) {
+int track_fused_enqueue(opd_track* t, hipStream_t s, const RecordView& frame_view, int frame, const TrackFeatureSource& src) {
     uint8_t* d = t->io.dev;
     t->last_launches = t->last_waits = 0;
     // behind whatever the handle's own stream still holds (the previous commit launch reads the staging image the ingest launch overwrites)
@@ -407,8 +405,7 @@ int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, con
     HIPCHK(hipStreamWaitEvent(s, t->ev_commit, 0));
     fill_slots(t);
     TrackIngestParams p{};
-    p.records = records; p.merged = merged; p.count = count;
-    p.Q = Q; p.D = t->D; p.frame = frame;
+    p.view = frame_view; p.D = t->D; p.frame = frame;
     p.rows_kind = src.rows_kind; p.rows = src.rows; p.slot_map = src.slot_map; p.n_person = src.n_person; p.slots = src.slots;
     p.boxes = reinterpret_cast<float*>(d + t->o_boxes);
     p.foot = reinterpret_cast<float*>(d + t->o_foot);
@@ -417,7 +414,7 @@ int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, con
     p.n_out = reinterpret_cast<int32_t*>(d + t->o_n);
     HIPCHK(opd_launch_track_ingest(p, s));
     ++t->last_launches;
-    return enqueue_predict(t, s, Q, src.rows_kind != TRACK_ROWS_NONE, p.n_out, true);
+    return enqueue_predict(t, s, frame_view.stride, src.rows_kind != TRACK_ROWS_NONE, p.n_out, true);
 }
 
 int track_fused_finish(opd_track* t, const float* conf, int conf_stride, int n, int with_features, int32_t* out_ids, const char* who) {

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "opd_device.h"
+#include "opd_records.h"
 
 enum { TRACK_RING = 10, TRACK_THREADS = 256, TRACK_INGEST_THREADS = 64, TRACK_MAX_TRACKS = 1024, TRACK_MAX_DETS = 1024, TRACK_MAX_DIM = 2048 };
 enum { TRACK_OP_MATCHED = 0, TRACK_OP_NEW = 1 };
@@ -56,22 +57,18 @@ struct TrackPredictParams {
 };
 
 // The ingest launch of the fused detect-and-track call: one frame's kept records, where the suppression kernel left them, -> the staging image
-enum { TRACK_ROWS_NONE = 0, TRACK_ROWS_BY_QUERY = 1, TRACK_ROWS_BY_SLOT = 2, TRACK_ROWS_BY_POSITION = 3 };
+enum { TRACK_ROWS_NONE = 0, TRACK_ROWS_BY_KEY = 1, TRACK_ROWS_BY_SLOT = 2 };
 struct TrackIngestParams {
-    const opd_det* records;    // [Q] records of the frame
-    const opd_tile_det* merged;   // non-null (a tiled call): the frame's [Q] MERGED records instead, Q = n_tiles x queries; `records` is not read.  Box: x, y, w, h
-                                  // each rounded to float32 once; foot point (x + w / 2, y + h) in float64 from the UNROUNDED doubles, then rounded
-    const int32_t* count;      // its kept count
-    int32_t Q, D, frame;
+    opd::RecordView view;      // ONE frame of the call's records (opd_records.h::record_frame): [Q = view.stride] records and their kept count
+    int32_t D, frame;          // `frame`: its index in the call, for the rows below
     int32_t rows_kind;         // TRACK_ROWS_*
-    const float* rows;         // BY_QUERY: [..][Q][D], row frame * Q + query_index.  BY_SLOT: [slots][D], row k of slot_map[k] = frame * Q + query_index
-                               // (merged records: slot_map[k] = frame * Q + i, the record's POSITION; a record without a slot enters with has = 0).
-                               // BY_POSITION (merged records only: two tiles of a frame use the same query numbers): [..][Q][D], row frame * Q + i of record i
+    const float* rows;         // BY_KEY: [..][Q][D], row frame * Q + record_key.  BY_SLOT: [slots][D], row k of slot_map[k] = frame * Q + record_key
+                               // (a record without a slot enters with has = 0)
     const int32_t* slot_map;   // BY_SLOT: [slots], of which min(*n_person, slots) are filled
     const int32_t* n_person;
     int32_t slots;
     float* boxes; float* foot; uint8_t* has; float* feat;   // the staging regions dets_of() describes
-    int32_t* n_out;            // min(count, Q), for the predict launch
+    int32_t* n_out;            // record_count of the frame, for the predict launch
     const int32_t* hdr;        // non-null (sequence call): a set TRACK_HDR_STOPPED ends the launch at once
 };
 
@@ -144,10 +141,9 @@ struct TrackFeatureSource {
     int slots = 0;
 };
 int track_fused_check(const opd_track* t, int device, int Q, int feature_dim, const char* who);
-// `merged` (non-null: a tiled call): the frame's merged records, read instead of `records`; Q is then n_tiles x queries.  `conf`: the confidence of
-// returned record i at conf[i * conf_stride] (floats): the score member of the opd_det or opd_tile_det records the call delivered
-int track_fused_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* count, int Q, int frame, const TrackFeatureSource& src,
-                        const opd_tile_det* merged = nullptr);
+// `frame_view`: frame `frame` of the call's records (record_frame).  `conf`: the confidence of returned record i at conf[i * conf_stride] (floats): the
+// score member of the opd_det or opd_tile_det records the call delivered
+int track_fused_enqueue(opd_track* t, hipStream_t s, const RecordView& frame_view, int frame, const TrackFeatureSource& src);
 int track_fused_finish(opd_track* t, const float* conf, int conf_stride, int n, int with_features, int32_t* out_ids, const char* who);
 
 // The tracker half of opd_detr_detect_sequence_track: B consecutive frames of one camera into ONE tracker, in frame order.

@@ -46,7 +46,7 @@ TAPI int opd_track_test_state(opd_track* t, int index, float* x, float* P, int32
 }
 
 // track_ingest_kernel alone on hand-made records: records [Q] (host) of which `n` count as kept, `frame` their index in the batch; rows [n_rows][D]
-// (host; TRACK_ROWS_BY_QUERY needs n_rows >= (frame + 1) * Q, TRACK_ROWS_BY_SLOT n_rows >= slots), slot_map [slots] and n_person as the crop
+// (host; TRACK_ROWS_BY_KEY needs n_rows >= (frame + 1) * Q, TRACK_ROWS_BY_SLOT n_rows >= slots), slot_map [slots] and n_person as the crop
 // selection leaves them.  boxes [Q][4], foot [Q][2], has [Q], feat [Q][D] and n_out are IN and OUT: the caller's bytes are uploaded first, so
 // what the launch does not write comes back as it went in.
 TAPI int opd_track_test_ingest(int device, const opd_det* records, int n, int Q, int D, int frame, int rows_kind, const float* rows, int n_rows,
@@ -55,14 +55,13 @@ TAPI int opd_track_test_ingest(int device, const opd_det* records, int n, int Q,
     if (!records || !boxes || !foot || !has || !feat || !n_out) return fail(OPD_EINVAL, "opd_track_test_ingest: null argument");
     if (Q < 1 || Q > TRACK_MAX_DETS || capacity != Q || D < 1 || D > TRACK_MAX_DIM || frame < 0 || slots < 0 || n_rows < 0)
         return fail(OPD_EINVAL, "opd_track_test_ingest: size out of range");
-    if (rows_kind == TRACK_ROWS_BY_QUERY && (!rows || (long long)n_rows < ((long long)frame + 1) * Q)) return fail(OPD_EINVAL, "opd_track_test_ingest: rows do not cover the frame");
+    if (rows_kind == TRACK_ROWS_BY_KEY && (!rows || (long long)n_rows < ((long long)frame + 1) * Q)) return fail(OPD_EINVAL, "opd_track_test_ingest: rows do not cover the frame");
     if (rows_kind == TRACK_ROWS_BY_SLOT && (!rows || !slot_map || n_rows < slots || slots < 1)) return fail(OPD_EINVAL, "opd_track_test_ingest: rows or slot map do not cover the slots");
     RCCHK(use_device("opd_track_test_ingest", device));
     DevMem tmp;
     TrackIngestParams p{};
-    p.records = tmp.up(records, (size_t)Q);
-    p.count = tmp.up(&n, 1);
-    p.Q = Q; p.D = D; p.frame = frame; p.rows_kind = rows_kind; p.slots = slots;
+    p.view = RecordView{tmp.up(records, (size_t)Q), nullptr, tmp.up(&n, 1), 1, Q};
+    p.D = D; p.frame = frame; p.rows_kind = rows_kind; p.slots = slots;
     if (rows_kind != TRACK_ROWS_NONE) p.rows = tmp.up(rows, (size_t)n_rows * D);
     if (rows_kind == TRACK_ROWS_BY_SLOT) {
         p.slot_map = tmp.up(slot_map, (size_t)slots);
