@@ -228,11 +228,12 @@ def records_equal(recs, ids, boxes, followed=None, tol=0.0):
 DUMMY_FRAME = np.zeros((24, 32, 3), np.uint8)   # what a flow-on handle is fed where only the track logic is under test
 
 
-def create(lib, capi, max_tracks=32, max_dets=32, max_h=24, max_w=32, device=0, **params):
+def create(lib, capi, max_tracks=32, max_dets=32, max_h=24, max_w=32, device=0, flow=None, **params):
+    """``flow``: further fields of opd_lwt_config.flow (win, max_level, max_iter, epsilon, min_eig_threshold; absent = the defaults)."""
     p = dict(DEFAULTS, **params)
     cfg = capi.OpdLwtConfig(struct_size=C.sizeof(capi.OpdLwtConfig), max_tracks=max_tracks, max_dets=max_dets, max_age=p["max_age"],
                             use_optical_flow=int(p["use_optical_flow"]), iou_threshold=p["iou_threshold"],
-                            flow=capi.OpdFlowConfig(max_h=max_h, max_w=max_w, max_points=1))
+                            flow=capi.OpdFlowConfig(max_h=max_h, max_w=max_w, max_points=1, **(flow or {})))
     h = C.c_void_p()
     capi.check(lib.opd_lwt_create(C.byref(cfg), device, C.byref(h)), "opd_lwt_create")
     return h

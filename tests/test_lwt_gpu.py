@@ -251,17 +251,23 @@ def _boxes_21(hh, ww):
     return np.stack([c[:, 0] - w / 2, c[:, 1] - h / 2, w, h], 1).astype(F32)
 
 
-@pytest.mark.parametrize("hw,seed,on_device", [((97, 131), 501, False), ((97, 131), 501, True), ((720, 1280), 502, False)])
-def test_fused_interpolate_equals_flow_track_fed_into_the_restatement(lib, hw, seed, on_device):
+@pytest.mark.parametrize("hw,seed,on_device,flow_cfg", [((97, 131), 501, False, {}), ((97, 131), 501, True, {}), ((720, 1280), 502, False, {}),
+                                                        ((97, 131), 501, False, dict(win=9, max_level=5))],
+                         ids=["hw0-501-False", "hw1-501-True", "hw2-502-False", "hw0-501-False-win9-level5"])   # (the first three: their ids from before flow_cfg)
+def test_fused_interpolate_equals_flow_track_fed_into_the_restatement(lib, hw, seed, on_device, flow_cfg):
+    """``flow_cfg``: fields of opd_lwt_config.flow other than the defaults (window 21, max_level 3), given to the tracker and to the
+    stand-alone flow handle alike."""
     hh, ww = hw
+    top = FC.top_level(hh, ww, flow_cfg.get("win", 21), flow_cfg.get("max_level", 3))
+    assert top == {(97, 131, 21): 2, (720, 1280, 21): 3, (97, 131, 9): 3}[(hh, ww, flow_cfg.get("win", 21))]
     frames = _three_frames(hh, ww, seed)
     keep = [torch.from_numpy(f).to("cuda") for f in frames] if on_device else None
     torch.cuda.synchronize()
     arg = (lambda i: (keep[i].data_ptr(), hh, ww)) if on_device else (lambda i: frames[i])
     p = dict(max_age=30, iou_threshold=0.3, use_optical_flow=True)
     r = LC.Restatement(**p)
-    h = LC.create(lib, _capi, max_tracks=32, max_dets=32, max_h=hh, max_w=ww, **p)
-    flow = FC.flow_create(lib, hh, ww, max_points=32)
+    h = LC.create(lib, _capi, max_tracks=32, max_dets=32, max_h=hh, max_w=ww, flow=flow_cfg, **p)
+    flow = FC.flow_create(lib, hh, ww, max_points=32, **flow_cfg)
     try:
         boxes = _boxes_21(hh, ww)
         rc, ids = LC.device_update(lib, _capi, h, boxes, arg(0))
@@ -274,7 +280,7 @@ def test_fused_interpolate_equals_flow_track_fed_into_the_restatement(lib, hw, s
             got = LC.device_interpolate(lib, _capi, h, arg(i))
             _recs_same(got, r.interpolate(nxt, status), (i, "records"))
             info = _same(r, lib, h, (i, "states"))
-            assert info.last_waits == 1 and info.last_launches == 2 + (4 if hw == (720, 1280) else 3)   # gray, pyramid levels, LK, the tracks
+            assert info.last_waits == 1 and info.last_launches == 1 + top + 1 + 1   # gray, one launch per pyramid level above 0, LK, the tracks
             assert info.n_points == int((status == 1).sum()) <= n_before
             lost_total += n_before - info.n_points
         assert 0 < lost_total < 21 and 0 < len(r.pt_ids)   # points were lost (the flat rectangle) and the compacted list carried over
