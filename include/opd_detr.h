@@ -711,12 +711,21 @@ OPD_API int opd_detr_detect_tiled_reid(opd_detr* m, const uint8_t* const* frames
  * valid_hw = tile_HW (eagerly, as every ragged batch), the boxes of tile t are scaled to ITS window, and the suppression, merge and wait are
  * those of opd_detr_detect_tiled.  Windows of one size with one model size take that entry's path, with its records byte for byte.
  * `stages`: NULL, or the colour-feature, floor and track stages on the merged records exactly as in opd_detr_detect_tiled_stages (rows by
- * position).  Re-ID rows are not offered for such a grid: opd_reid_extract on the merged records is the way.
+ * position).  Re-ID rows are refused here (feature_kind OPD_TRACK_FEAT_REID): for such a grid they are the entry opd_detr_detect_tiled_ragged_reid below.
  * OPD_EINVAL before any device call: everything opd_detr_detect_tiled (with `stages`: opd_detr_detect_tiled_stages) refuses except windows of
  * more than one size; NULL `tile_HW`; a model size below 1; a canvas outside the handle's maximum. */
 OPD_API int opd_detr_detect_tiled_ragged(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw,
                                          int n_tiles, const int32_t* tile_HW, float threshold, const opd_tile_params* p,
                                          const opd_tile_stages* stages, opd_tile_det* out, int32_t* counts);
+/* opd_detr_detect_tiled_reid for a grid whose tiles DIFFER in size: the source step, forward and records of opd_detr_detect_tiled_ragged (`tile_HW`
+ * [n_tiles][2] as there), and behind the seam merge the Re-ID, floor and track stages exactly as documented for opd_detr_detect_tiled_reid: slots,
+ * slot_map, rows by slot, floor and track-id rows by position, crops cut from the WHOLE frames (the windows and their sizes play no part).  Windows of
+ * one size with one model size take opd_detr_detect_tiled_reid's path and give its bytes.
+ * OPD_EINVAL before any device call: everything opd_detr_detect_tiled_ragged (without stages) and opd_detr_detect_tiled_reid refuse, except windows
+ * of more than one size. */
+OPD_API int opd_detr_detect_tiled_ragged_reid(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw,
+                                              int n_tiles, const int32_t* tile_HW, float threshold, const opd_tile_params* p,
+                                              const opd_tile_reid_stages* stages, opd_tile_det* out, int32_t* counts);
 /* The solver of the association on its own (host only): cost [rows][cols] row-major -> row_to_col [rows], -1 for a row left alone;
  * min(rows, cols) pairs of smallest total cost, as scipy.optimize.linear_sum_assignment. */
 OPD_API int opd_assign(const double* cost, int rows, int cols, int32_t* row_to_col);
@@ -823,6 +832,44 @@ OPD_API int opd_detr_detect_frames_hybrid(opd_detr* m, opd_lwt* const* trackers,
 OPD_API int opd_detr_detect_sequence_hybrid(opd_detr* m, opd_lwt* t, const uint8_t* const* frames, const uint8_t* is_key, int F, int h, int w,
                                             int H, int W, float threshold, int label, opd_det* out, int32_t* counts, int32_t* track_ids,
                                             opd_lwt_rec* recs_out, int capacity, int32_t* rec_counts, int32_t* frames_done);
+/* A detection frame of the hybrid tracker INSIDE a tiled call (DESIGN.md sections 7a, 7k, 7n).  With S = n_tiles x num_queries, per frame f the
+ * result equals, bit for bit, three steps: opd_detr_detect_tiled (`tile_HW` given: opd_detr_detect_tiled_ragged); opd_lwt_update(trackers[f],
+ * frames[f], boxes) with the boxes of the MERGED records, x, y, w, h each rounded from float64 to float32 ONCE (np.array([d.bbox ...], float32));
+ * and, with `floor`, opd_floor_transform as in opd_detr_detect_tiled_stages -- ids, every number of every track, the counts of opd_lwt_info, flow
+ * points and reference frame, merged records and counts, behind ONE host wait.  Behind the seam merge, per tracker, on the detector's stream: the
+ * ingest launch reads the merged records where the merge left them and clamps their device-resident count to S; gray and pyramid are built from the
+ * WHOLE h x w frame where the tiled source uploaded it (no second upload; no tile plays a part); the update kernel reads the count on the device.
+ *   tile_HW    NULL: tiles of one size at one model size H x W.  Else [n_tiles][2], the model size of each tile; H and W are ignored
+ *   trackers   [n_frames] distinct handles, frame f into trackers[f]
+ *   track_ids  host [n_frames][S], by POSITION: the id of merged record k of frame f at [f][k]; entries at k >= counts[f] are not written
+ *   floor      NULL, or a floor-map handle; floor_out host [n_frames][S], rows by position
+ * OPD_EINVAL before any device work: everything the plain tiled entry (uniform or ragged) refuses; NULL `hy` or a wrong struct_size; NULL trackers
+ * or track_ids; a tracker that is NULL, named twice, on another device, made with max_dets < S, or (with optical flow) made for frames smaller than
+ * h x w; floor_out NULL with `floor`, a floor map on another device.  New tracks that do not fit: as in opd_detr_detect_frames_hybrid (that tracker
+ * is left as it was and its ids are -1; records and counts are delivered, the other trackers are committed, the call returns OPD_EINVAL).  The
+ * trackers' last_waits is 0 afterwards: the wait is the detector's. */
+typedef struct opd_tile_hybrid {
+    int32_t struct_size, reserved; /* sizeof of this struct; zero */
+    opd_lwt* const* trackers;
+    int32_t* track_ids;
+    opd_floor* floor;
+    opd_floor_rec* floor_out;
+} opd_tile_hybrid;
+OPD_API int opd_detr_detect_tiled_hybrid(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw,
+                                         int n_tiles, int H, int W, const int32_t* tile_HW, float threshold, const opd_tile_params* p,
+                                         const opd_tile_hybrid* hy, opd_tile_det* out, int32_t* counts);
+/* opd_detr_detect_sequence_hybrid with TILED key frames: a run of F consecutive h x w frames of one camera.  The K key frames go through ONE tiled
+ * forward (K x n_tiles <= max_batch; `tile_HW` as above), suppression and seam merge.  Then, in frame order on the detector's stream: a key frame
+ * runs ingest (merged records of key frame k), gray + pyramid of its whole frame and the update; an in-between frame is uploaded from where it lies
+ * and runs gray + pyramid, LK and the track kernel.  The LK launches behind the first key frame are sized for S = n_tiles x num_queries points.  out
+ * [K][S], counts [K], track_ids [K][S]: per key frame, as from opd_detr_detect_tiled_hybrid; recs_out, capacity, rec_counts, frames_done, the
+ * sticky word at a key frame whose new tracks do not fit, and K = 0 (opd_lwt_interpolate_sequence; no forward, the windows are not read): as in
+ * opd_detr_detect_sequence_hybrid.  Results equal the per-frame loop of opd_detr_detect_tiled_hybrid's three steps and opd_lwt_interpolate, bit for
+ * bit.  OPD_EINVAL before any device work: whatever opd_detr_detect_sequence_hybrid and the plain tiled entry refuse; max_dets < S. */
+OPD_API int opd_detr_detect_tiled_sequence_hybrid(opd_detr* m, opd_lwt* t, const uint8_t* const* frames, const uint8_t* is_key, int F, int h, int w,
+                                                  const int32_t* tiles_yxhw, int n_tiles, int H, int W, const int32_t* tile_HW, float threshold,
+                                                  const opd_tile_params* p, opd_tile_det* out, int32_t* counts, int32_t* track_ids,
+                                                  opd_lwt_rec* recs_out, int capacity, int32_t* rec_counts, int32_t* frames_done);
 /* The live tracks in creation order (out may be NULL with capacity 0 to ask for the count).  A read-back for inspection: one more wait. */
 OPD_API int opd_lwt_get(opd_lwt* t, opd_lwt_track* out, int capacity, int* count);
 

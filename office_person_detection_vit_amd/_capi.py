@@ -89,6 +89,10 @@ class OpdTileReidStages(C.Structure):   # opd_tile_reid_stages (80 bytes): the R
                 ("floor", C.c_void_p), ("floor_out", C.c_void_p), ("trackers", C.c_void_p), ("track_ids", C.c_void_p), ("n_featured", C.c_void_p)]
 
 
+class OpdTileHybrid(C.Structure):   # opd_tile_hybrid (40 bytes): the hybrid trackers and the floor stage of opd_detr_detect_tiled_hybrid
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("trackers", C.c_void_p), ("track_ids", C.c_void_p), ("floor", C.c_void_p), ("floor_out", C.c_void_p)]
+
+
 class OpdFloorConfig(C.Structure):   # opd_floor_config: everything is copied at creation
     _fields_ = [("method", C.c_int32), ("n_points", C.c_int32), ("n_triangles", C.c_int32), ("n_zones", C.c_int32), ("has_distortion", C.c_int32),
                 ("allow_overlap", C.c_int32), ("width_px", C.c_int32), ("height_px", C.c_int32), ("H", C.c_double * 9),
@@ -180,6 +184,16 @@ API = {
     # frames, n_frames, h, w, tiles_yxhw, n_tiles, tile_HW, threshold, params, stages (nullable), out, counts
     "opd_detr_detect_tiled_ragged": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
                                                C.POINTER(OpdTileParams), C.POINTER(OpdTileStages), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
+    # frames, n_frames, h, w, tiles_yxhw, n_tiles, tile_HW, threshold, params, stages, out, counts
+    "opd_detr_detect_tiled_ragged_reid": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
+                                                    C.POINTER(OpdTileParams), C.POINTER(OpdTileReidStages), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
+    # frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, tile_HW (nullable), threshold, params, hybrid block, out, counts
+    "opd_detr_detect_tiled_hybrid": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,
+                                               C.POINTER(OpdTileParams), C.POINTER(OpdTileHybrid), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
+    # tracker, frames, is_key, F, h, w, tiles_yxhw, n_tiles, H, W, tile_HW (nullable), threshold, params, out, counts, track_ids, recs_out, capacity, rec_counts, frames_done
+    "opd_detr_detect_tiled_sequence_hybrid": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                        C.c_void_p, C.c_float, C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32), C.c_void_p,
+                                                        C.POINTER(OpdLwtRec), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     # recs, tile_counts, n_frames, n_tiles, stride, tiles_yxhw, h, w, params, out, counts
     "opd_detr_merge_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.POINTER(OpdTileParams), C.POINTER(OpdTileDet), C.POINTER(C.c_int32)]),
@@ -396,6 +410,8 @@ TEST_API = {
     # hybrid-tracker hook (csrc/opd_lwt_test_api.cpp): handle, next_xy, status, records, capacity, count
     # the ingest launch of the fused hybrid detect call (csrc/opd_lwt_ingest_test_api.cpp): device, records, n, Q, boxes, n_out
     "opd_lwt_test_ingest": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # ... and of the fused hybrid TILED call (csrc/opd_lwt_ingest_merged_test_api.cpp): device, merged records, n, S, boxes, n_out
+    "opd_lwt_test_ingest_merged": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "opd_test_lwt_interpolate_scripted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OpdLwtRec), C.c_int, C.POINTER(C.c_int)]),
 }
 

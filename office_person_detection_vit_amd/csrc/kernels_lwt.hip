@@ -17,8 +17,9 @@
 //       position in the OTHER bank; one thread per unmatched detection: a new track.  (f) ids, flow points, head.
 //   lwt_interp_kernel   `interpolate`: one workgroup, one thread per track.  A track whose id has a followed point moves its box there and
 //       is updated with the point; any other track is predicted.  Then the point list is compacted to the followed points in order.
-//   lwt_ingest_kernel   the fused detect call only (opd_detr_detect_frames_hybrid): one wave turns the kept records of a frame, where the
-//       suppression kernel left them, into the float32 [n][4] xywh image `np.array([d.bbox for d in dets], np.float32)` is -- corners as they
+//   lwt_ingest_kernel   the fused detect calls only (opd_detr_detect_frames_hybrid, opd_detr_detect_tiled_hybrid and their sequence forms): one
+//       wave turns the kept records of a frame, read through the call's RecordView where the suppression kernel or (a tiled call) the seam
+//       merge left them, into the float32 [n][4] xywh image `np.array([d.bbox for d in dets], np.float32)` is -- corners as they
 //       are, width and height as differences in double rounded once (track_ingest_kernel's box rule) -- and leaves the kept count on the
 //       device, where lwt_update_kernel (LwtUpdateParams::count) reads it.
 #include <hip/hip_runtime.h>
@@ -407,12 +408,11 @@ __global__ __launch_bounds__(LWT_THREADS) void lwt_interp_kernel(const LwtInterp
 
 __global__ __launch_bounds__(64) void lwt_ingest_kernel(const LwtIngestParams p) {
     if (p.stop && *p.stop) return;
-    int n = *p.count;
-    n = n < 0 ? 0 : (n > p.Q ? p.Q : n);
+    const int n = opd::record_count(p.view, 0);   // (clamped to the stride, whatever lies there)
     if (threadIdx.x == 0) *p.n_out = n;
     for (int i = threadIdx.x; i < n; i += 64) {
         double box[4];
-        opd::record_box64(p.records[i], box);
+        opd::record_box64(p.view, i, box);
         for (int k = 0; k < 4; ++k) p.boxes[4 * i + k] = (float)box[k];
     }
 }
@@ -420,7 +420,8 @@ __global__ __launch_bounds__(64) void lwt_ingest_kernel(const LwtIngestParams p)
 }  // namespace
 
 hipError_t opd_launch_lwt_ingest(const LwtIngestParams& p, hipStream_t stream) {
-    if (p.Q < 1 || p.Q > LWT_MAX_DETS || !p.records || !p.count || !p.boxes || !p.n_out) return hipErrorInvalidValue;
+    const opd::RecordView& v = p.view;
+    if (v.stride < 1 || v.stride > LWT_MAX_DETS || (v.records != nullptr) == (v.merged != nullptr) || !v.counts || !p.boxes || !p.n_out) return hipErrorInvalidValue;
     OPD_LAUNCH(lwt_ingest_kernel, dim3(1), dim3(64), 0, stream, p);
     return hipGetLastError();
 }

@@ -319,25 +319,24 @@ static int finish_trackers(opd_detr* m, const RecordSink& s, const CallRecords& 
 }
 
 // The hybrid-tracker half of a fused detect call (opd_lwt.h), around the one wait of fetch_records like the track stage.  Before it, per tracker on
-// m->stream: ingest of the frame's kept records, gray + pyramid of its camera-resolution frame where the source step left it, the update with the
-// count read on the device.  After it: adoption per tracker; a tracker whose new tracks did not fit keeps its state and reference frame, gets -1
-// for every id and does not keep the others from being committed; its error is the call's.
-static int enqueue_hybrid(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera) {
-    const int B = m->last_B, Q = m->arch.queries;
-    if (s.hybrid.seq) return lwt_sequence_enqueue(s.hybrid.seq, m->stream, *s.hybrid.call, m->d_records, m->d_counts, d_camera, s.hybrid.entry);
-    for (int b = 0; b < B; ++b)
-        RCCHK(lwt_fused_enqueue(s.hybrid.trackers[b], m->stream, m->d_records + (size_t)b * Q, m->d_counts + b, Q, d_camera + (size_t)b * h * w * 3, h, w,
-                                "opd_detr_detect_frames_hybrid"));
+// m->stream: ingest of the frame's kept records through the call's view (a tiled call: the merged records), gray + pyramid of its camera-resolution
+// frame of h x w where the source step left it (a tiled call: the WHOLE frame), the update with the count read on the device.  After it: adoption
+// per tracker with the counts the call delivers; a tracker whose new tracks did not fit keeps its state and reference frame, gets -1 for every id
+// and does not keep the others from being committed; its error is the call's.
+static int enqueue_hybrid(opd_detr* m, const RecordSink& s, const CallRecords& c, int h, int w, const uint8_t* d_camera) {
+    if (s.hybrid.seq) return lwt_sequence_enqueue(s.hybrid.seq, m->stream, *s.hybrid.call, &c.view, d_camera, s.hybrid.entry);
+    for (int f = 0; f < c.view.n_frames; ++f)
+        RCCHK(lwt_fused_enqueue(s.hybrid.trackers[f], m->stream, record_frame(c.view, f), d_camera + (size_t)f * h * w * 3, h, w, s.hybrid.entry));
     return OPD_OK;
 }
-static int finish_hybrid(opd_detr* m, const RecordSink& s) {
-    const int B = m->last_B, Q = m->arch.queries;
+static int finish_hybrid(const RecordSink& s, const CallRecords& c) {
+    const int frames = c.view.n_frames, stride = c.view.stride;
     const HybridStage& y = s.hybrid;
-    if (y.seq) return lwt_sequence_finish(y.seq, *y.call, s.counts, y.track_ids, y.recs_out, y.capacity, y.rec_counts, y.frames_done, y.entry);
+    if (y.seq) return lwt_sequence_finish(y.seq, *y.call, c.counts, y.track_ids, y.recs_out, y.capacity, y.rec_counts, y.frames_done, y.entry);
     int rc = OPD_OK;
     std::string first;
-    for (int b = 0; b < B; ++b) {
-        const int one = lwt_fused_finish(s.hybrid.trackers[b], std::max(0, std::min(s.counts[b], Q)), s.hybrid.track_ids + (size_t)b * Q, "opd_detr_detect_frames_hybrid");
+    for (int b = 0; b < frames; ++b) {
+        const int one = lwt_fused_finish(y.trackers[b], std::max(0, std::min(c.counts[b], stride)), y.track_ids + (size_t)b * stride, y.entry);
         if (one != OPD_OK && rc == OPD_OK) { rc = one; first = g_err; }
     }
     return rc == OPD_OK ? OPD_OK : fail(rc, first);
@@ -355,7 +354,8 @@ static float* query_rows_out(const RecordSink& s) { return s.feature.kind == FEA
 
 // The one fetch of a blocking call: what the sink's parts ask for comes back into page-locked memory (a copy into the caller's pageable arrays is staged by
 // the runtime anyway, once per call), then the call's ONE wait.  A tiled call: [counts | merged records], and of its stages the rows by position (unless
-// a tracker alone reads them), the floor rows, and the Re-ID call's slot list (with its rows when the caller takes them).  Host outputs: [records of max_batch frames |
+// a tracker alone reads them), the floor rows, the Re-ID call's slot list (with its rows when the caller takes them), and what the hybrid stage brings
+// back (below).  Host outputs: [records of max_batch frames |
 // counts (| per-query feature rows)] in one copy, the floor rows, the Re-ID call's slot list (and rows, unless a tracker reads them in place).  Device
 // outputs were written in place by the post-process kernel.
 static int fetch_records(opd_detr* m, const RecordSink& s, ReidFusedCall* reid) {
@@ -368,6 +368,9 @@ static int fetch_records(opd_detr* m, const RecordSink& s, ReidFusedCall* reid) 
         }
         if (s.floor.fmap) HIPCHK(hipMemcpyAsync(m->h_floor, m->d_floor, (size_t)B * Q * sizeof(opd_floor_rec), hipMemcpyDeviceToHost, m->stream));
         if (reid) RCCHK(reid->copy_back(m->stream));   // the slot list (and the rows by slot, when the caller takes them)
+        if (s.hybrid.seq) RCCHK(lwt_sequence_fetch(s.hybrid.seq, m->stream, s.hybrid.call->F));
+        else if (s.hybrid.on())   // every tracker's [head | ids], an id per slot of a merged frame
+            for (int f = 0; f < s.tile.n_frames; ++f) RCCHK(lwt_fused_fetch(s.hybrid.trackers[f], m->stream, s.tile.n_tiles * Q));
     } else if (!outputs_on_device(s.mem_kind)) {
         RCCHK(ensure_sync_pinned(m));
         HIPCHK(hipMemcpyAsync(m->sync_pinned, m->d_records, query_rows_out(s) ? feat_off(m) + B * feat_row(m) : rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
@@ -409,7 +412,7 @@ static int hand_to_ticket(opd_detr* m, const RecordSink& s) {
 
 // The back half, on the outputs of the last forward (opd_detr_postprocess enters here): the stages of the sink in their one order, each skipped when its
 // part is absent.  (h, w): the size the boxes are scaled to (0: the model resolution); d_camera: the source's frames on the device at camera resolution.
-// The feature, floor and track stages read the records of the call through ONE view (call_records): in a tiled call the MERGED records, not d_records.
+// The feature, floor, track and hybrid stages read the records of the call through ONE view (call_records): in a tiled call the MERGED records, not d_records.
 // The feature, floor, track and tile parts deliver to the host after the call's own wait: setting one with WAIT_TICKET or WAIT_NONE, or with device
 // outputs, is a programming error (no entry point does).
 static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera) {
@@ -424,7 +427,7 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
     RCCHK(enqueue_features(m, s, recs, tiled ? s.tile.frame_h : h, tiled ? s.tile.frame_w : w, d_camera, &reid, &rows));
     if (s.floor.fmap) RCCHK(enqueue_floor(m, s, recs));
     if (tracked) RCCHK(enqueue_trackers(m, s, recs, rows));
-    if (s.hybrid.on()) RCCHK(enqueue_hybrid(m, s, h, w, d_camera));
+    if (s.hybrid.on()) RCCHK(enqueue_hybrid(m, s, recs, tiled ? s.tile.frame_h : h, tiled ? s.tile.frame_w : w, d_camera));
     if (s.wait == WAIT_NONE) return OPD_OK;
     if (s.wait == WAIT_TICKET) return hand_to_ticket(m, s);
     RCCHK(fetch_records(m, s, reid ? &*reid : nullptr));
@@ -443,6 +446,7 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
             reid->deliver(s.feature.features, s.feature.slot_map, s.feature.n_person);
             if (tracked) reid->slots_per_frame(s.tile.n_frames, S, s.track.n_featured);
         }
+        if (s.hybrid.on()) return finish_hybrid(s, recs);   // (adoption by the MERGED counts; no entry sets both tracker stages)
         return tracked ? finish_trackers(m, s, recs, rows.rows_kind != TRACK_ROWS_NONE) : OPD_OK;
     } else if (!dev) unpack_records(m, m->sync_pinned, B, s.out, s.counts, query_rows_out(s));
     if (reid && !tracked) reid->deliver(s.feature.features, s.feature.slot_map, s.feature.n_person);
@@ -452,7 +456,7 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
                 const opd_det& r = s.out[(size_t)b * Q + i];
                 if (r.label == s.label && (unsigned)r.query_index < (unsigned)Q) s.floor.out[(size_t)b * Q + r.query_index] = m->h_floor[(size_t)b * Q + r.query_index];
             }
-    if (s.hybrid.on()) return finish_hybrid(m, s);   // (no entry sets both tracker stages)
+    if (s.hybrid.on()) return finish_hybrid(s, recs);   // (no entry sets both tracker stages)
     if (!tracked) return OPD_OK;
     if (reid) reid->slots_per_frame(B, Q, s.track.n_featured);
     else for (int b = 0; b < B; ++b) s.track.n_featured[b] = rows.rows_kind == TRACK_ROWS_NONE ? 0 : std::max(0, std::min(s.counts[b], Q));
@@ -735,13 +739,25 @@ int opd_detr_nms_records(opd_detr* m, opd_det* dets, int32_t* counts, int n_fram
     }
     return OPD_OK;
 }); }
+// A run of frames without a key frame (both sequence-hybrid entries, behind their checks): no forward; the run on the tracker's own stream, which is
+// opd_lwt_interpolate_sequence
+static int sequence_without_keys(opd_lwt* t, const LwtSeqCall& call, opd_lwt_rec* recs_out, int capacity, int32_t* rec_counts, int32_t* frames_done, const std::string& me) {
+    HIPCHK(hipSetDevice(t->device));
+    RCCHK(lwt_sequence_enqueue(t, t->stream(), call, nullptr, nullptr, me.c_str()));
+    RCCHK(lwt_sequence_fetch(t, t->stream(), call.F));
+    HIPCHK(hipStreamSynchronize(t->stream()));
+    t->last_waits = 1;
+    return lwt_sequence_finish(t, call, nullptr, nullptr, recs_out, capacity, rec_counts, frames_done, me);
+}
 // Tiled detection: every refusal comes before the first device call (check_tiles; check_shape makes none for host pixels).  `st` (null: opd_detr_detect_tiled
 // itself): the feature, floor and track parts of the sink, which then read the merged records where the merge left them, rows by position.  `rs`
 // (opd_detr_detect_tiled_reid; `st` is then null): the same with the Re-ID rows as the feature kind, rows by slot, a slot naming a position.
 // `mixed` (opd_detr_detect_tiled_ragged): the windows may differ in size, `tile_HW` [n_tiles][2] is the model size of each and H x W, not read as given, the
-// canvas that holds them all; windows of one size with one model size take the path of the other entries, launch for launch
+// canvas that holds them all; windows of one size with one model size take the path of the other entries, launch for launch.  `hyb` (the hybrid entries;
+// `st` then carries their floor part alone): the hybrid stage of the sink, a tracker per frame or `seq` with the run `hyb_call`, whose Q becomes S here
 static int detect_tiled(const std::string& me, opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W,
-                        const int32_t* tile_HW, bool mixed, float threshold, const opd_tile_params* p, const opd_tile_stages* st, const opd_tile_reid_stages* rs, opd_tile_det* out, int32_t* counts) {
+                        const int32_t* tile_HW, bool mixed, float threshold, const opd_tile_params* p, const opd_tile_stages* st, const opd_tile_reid_stages* rs, opd_tile_det* out, int32_t* counts,
+                        const HybridStage* hyb = nullptr, LwtSeqCall* hyb_call = nullptr) {
     if (!frames || !out || !counts) return fail(OPD_EINVAL, me + ": null argument");
     opd_tile_stages of_reid{};   // the floor and track parts of the Re-ID entry's block, as the checks below read them
     if (rs) {   // (opd_detr_detect_tiled_reid: `st` is null)
@@ -827,6 +843,22 @@ static int detect_tiled(const std::string& me, opd_detr* m, const uint8_t* const
         sink.floor.fmap = st->floor; sink.floor.out = st->floor_out;
         sink.track.trackers = st->trackers; sink.track.track_ids = st->track_ids; sink.track.n_featured = st->n_featured;
     }
+    if (hyb) {   // a merged frame enters a hybrid tracker with up to S records and its WHOLE frame of h x w
+        const int S = n_tiles * m->arch.queries;
+        if (hyb_call) {   // (a null tracker is lwt_fused_check's to refuse, inside)
+            hyb_call->Q = S;
+            RCCHK(lwt_sequence_check(hyb->seq, *hyb_call, hyb->capacity, m->device, me));
+            *hyb->frames_done = 0;
+        } else for (int f = 0; f < n_frames; ++f) {
+            RCCHK(lwt_fused_check(hyb->trackers[f], m->device, S, h, w, me + ": trackers[" + std::to_string(f) + "]"));
+            for (int a = 0; a < f; ++a)
+                if (hyb->trackers[a] == hyb->trackers[f])
+                    return fail(OPD_EINVAL, me + ": frames " + std::to_string(a) + " and " + std::to_string(f) + " name the same tracker; a tracker takes one frame per call");
+        }
+        sink.hybrid = *hyb;
+        sink.hybrid.entry = sink.tile.entry;
+        sink.label = p->person_label;
+    }
     HIPCHK(hipSetDevice(m->device));
     return detect_pipeline(m, src, n_frames * n_tiles, H, W, one_size ? nullptr : valid_hw.data(), sink);
 }
@@ -852,6 +884,57 @@ int opd_detr_detect_tiled_reid(opd_detr* m, const uint8_t* const* frames, int n_
 int opd_detr_detect_tiled_ragged(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, const int32_t* tile_HW,
                                  float threshold, const opd_tile_params* p, const opd_tile_stages* stages, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled_ragged", [&]() -> int {
     return detect_tiled("opd_detr_detect_tiled_ragged", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, 0, 0, tile_HW, true, threshold, p, stages, nullptr, out, counts);
+}); }
+// ... with the Re-ID rows on such a grid: opd_detr_detect_tiled_reid's stages behind the ragged forward (windows of one size with one model size: that entry's path)
+int opd_detr_detect_tiled_ragged_reid(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, const int32_t* tile_HW,
+                                      float threshold, const opd_tile_params* p, const opd_tile_reid_stages* stages, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled_ragged_reid", [&]() -> int {
+    if (!stages) return fail(OPD_EINVAL, "opd_detr_detect_tiled_ragged_reid: null argument (stages)");
+    return detect_tiled("opd_detr_detect_tiled_ragged_reid", m, frames, n_frames, h, w, tiles_yxhw, n_tiles, 0, 0, tile_HW, true, threshold, p, nullptr, stages, out, counts);
+}); }
+// ... with a detection frame of the hybrid tracker on the merged records: frame f's merged records and its WHOLE frame, where the tiled source
+// left it, enter hybrid tracker f in front of the same one wait.  `tile_HW` null: one size H x W; else the ragged form
+int opd_detr_detect_tiled_hybrid(opd_detr* m, const uint8_t* const* frames, int n_frames, int h, int w, const int32_t* tiles_yxhw, int n_tiles, int H, int W,
+                                 const int32_t* tile_HW, float threshold, const opd_tile_params* p, const opd_tile_hybrid* hy, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_detect_tiled_hybrid", [&]() -> int {
+    const std::string me = "opd_detr_detect_tiled_hybrid";
+    if (!hy) return fail(OPD_EINVAL, me + ": null argument (hy)");
+    if (hy->struct_size != (int32_t)sizeof(opd_tile_hybrid)) return fail(OPD_EINVAL, me + ": opd_tile_hybrid.struct_size mismatch");
+    if (!hy->trackers || !hy->track_ids) return fail(OPD_EINVAL, me + ": trackers or track_ids is null");
+    opd_tile_stages floor_part{};   // (floor_out without floor, a floor map on another device: detect_tiled's refusals)
+    floor_part.struct_size = (int32_t)sizeof(opd_tile_stages); floor_part.feature_kind = OPD_TRACK_FEAT_NONE; floor_part.floor = hy->floor; floor_part.floor_out = hy->floor_out;
+    HybridStage stage;
+    stage.trackers = hy->trackers; stage.track_ids = hy->track_ids;
+    return detect_tiled(me, m, frames, n_frames, h, w, tiles_yxhw, n_tiles, H, W, tile_HW, tile_HW != nullptr, threshold, p, &floor_part, nullptr, out, counts, &stage);
+}); }
+// The sequence twin on tiled frames: opd_detr_detect_sequence_hybrid whose K key frames go through ONE tiled forward, suppression and seam merge; a key
+// frame's merged records (up to S = n_tiles x num_queries) and its whole frame enter the tracker in frame order, the in-between frames around them
+int opd_detr_detect_tiled_sequence_hybrid(opd_detr* m, opd_lwt* t, const uint8_t* const* frames, const uint8_t* is_key, int F, int h, int w, const int32_t* tiles_yxhw,
+                                          int n_tiles, int H, int W, const int32_t* tile_HW, float threshold, const opd_tile_params* p, opd_tile_det* out, int32_t* counts,
+                                          int32_t* track_ids, opd_lwt_rec* recs_out, int capacity, int32_t* rec_counts, int32_t* frames_done) { return api_call("opd_detr_detect_tiled_sequence_hybrid", [&]() -> int {
+    const std::string me = "opd_detr_detect_tiled_sequence_hybrid";
+    if (F < 1 || F > LWT_MAX_SEQUENCE) return fail(OPD_EINVAL, me + ": " + std::to_string(F) + " frames, a call takes 1 .. " + std::to_string(LWT_MAX_SEQUENCE));
+    if (capacity < 1) return fail(OPD_EINVAL, me + ": capacity " + std::to_string(capacity) + " is below the tracker's max_tracks");
+    if (!frames || !is_key || !frames_done) return fail(OPD_EINVAL, me + ": null argument (frame list, key flags or frames_done)");
+    std::vector<const uint8_t*> keys;
+    for (int f = 0; f < F; ++f)
+        if (is_key[f]) keys.push_back(frames[f]);
+    const int K = (int)keys.size();
+    if (K > 0 && (!out || !counts || !track_ids)) return fail(OPD_EINVAL, me + ": null output of the key frames");
+    if (K < F && (!recs_out || !rec_counts)) return fail(OPD_EINVAL, me + ": null output of the in-between frames");
+    LwtSeqCall call{frames, is_key, F, h, w, 0};
+    if (K == 0) {   // no forward and no tiles: opd_lwt_interpolate_sequence, as in the frame-list entry
+        if (!frame_size_ok(h, w)) return fail(OPD_EINVAL, me + ": source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
+        if (!m) return fail(OPD_EINVAL, "null model handle");
+        if (n_tiles < 1 || (long long)n_tiles * m->arch.queries > OPD_TILE_MAX_CAND)
+            return fail(OPD_EINVAL, me + ": " + std::to_string(n_tiles) + " tiles x " + std::to_string(m->arch.queries) + " queries outside the 1024 candidates a frame's merge holds");
+        call.Q = n_tiles * m->arch.queries;
+        RCCHK(lwt_sequence_check(t, call, capacity, m->device, me));
+        *frames_done = 0;
+        return sequence_without_keys(t, call, recs_out, capacity, rec_counts, frames_done, me);
+    }
+    HybridStage stage;
+    stage.seq = t; stage.call = &call; stage.track_ids = track_ids;
+    stage.recs_out = recs_out; stage.capacity = capacity; stage.rec_counts = rec_counts; stage.frames_done = frames_done;
+    return detect_tiled(me, m, keys.data(), K, h, w, tiles_yxhw, n_tiles, H, W, tile_HW, tile_HW != nullptr, threshold, p, nullptr, nullptr, out, counts, &stage, &call);
 }); }
 int opd_detr_merge_tiles(opd_detr* m, const opd_det* recs, const int32_t* tile_counts, int n_frames, int n_tiles, int stride, const int32_t* tiles_yxhw, int h, int w,
                          const opd_tile_params* p, opd_tile_det* out, int32_t* counts) { return api_call("opd_detr_merge_tiles", [&]() -> int {
@@ -1106,14 +1189,7 @@ int opd_detr_detect_sequence_hybrid(opd_detr* m, opd_lwt* t, const uint8_t* cons
     const LwtSeqCall call{frames, is_key, F, h, w, m->arch.queries};
     RCCHK(lwt_sequence_check(t, call, capacity, m->device, me));
     *frames_done = 0;
-    if (K == 0) {   // no forward: the run on the tracker's own stream, which is opd_lwt_interpolate_sequence
-        HIPCHK(hipSetDevice(t->device));
-        RCCHK(lwt_sequence_enqueue(t, t->stream(), call, nullptr, nullptr, nullptr, me.c_str()));
-        RCCHK(lwt_sequence_fetch(t, t->stream(), F));
-        HIPCHK(hipStreamSynchronize(t->stream()));
-        t->last_waits = 1;
-        return lwt_sequence_finish(t, call, nullptr, nullptr, recs_out, capacity, rec_counts, frames_done, me);
-    }
+    if (K == 0) return sequence_without_keys(t, call, recs_out, capacity, rec_counts, frames_done, me);
     RecordSink sink = host_sink(threshold, label, out, counts);
     sink.hybrid.seq = t; sink.hybrid.call = &call; sink.hybrid.track_ids = track_ids; sink.hybrid.entry = "opd_detr_detect_sequence_hybrid";
     sink.hybrid.recs_out = recs_out; sink.hybrid.capacity = capacity; sink.hybrid.rec_counts = rec_counts; sink.hybrid.frames_done = frames_done;

@@ -6,8 +6,8 @@
 // call's launches and checks.  Nothing here computes on a track.
 //
 // Both calls are an enqueue half and an adopt half around their wait (opd_lwt.h), which three more entries share: opd_lwt_interpolate_sequence
-// (F in-between frames behind one wait, here), and the hybrid parts of the detector's fused calls, opd_detr_detect_frames_hybrid and
-// opd_detr_detect_sequence_hybrid (opd_api.cpp), whose launches run on the detector's stream behind its suppression and whose results ride
+// (F in-between frames behind one wait, here), and the hybrid parts of the detector's fused calls, opd_detr_detect_frames_hybrid,
+// opd_detr_detect_sequence_hybrid and their tiled twins (opd_api.cpp), whose launches run on the detector's stream behind its suppression and whose results ride
 // on the detector's one fetch (lwt_fused_*, lwt_sequence_*).
 #include <string.h>
 
@@ -234,14 +234,14 @@ static int order_own_stream_behind(opd_lwt* t, hipStream_t s) {
     return OPD_OK;
 }
 
-int lwt_fused_enqueue(opd_lwt* t, hipStream_t s, const opd_det* d_records, const int32_t* d_count, int Q, const uint8_t* d_bgr, int h, int w, const char* who) {
+int lwt_fused_enqueue(opd_lwt* t, hipStream_t s, const RecordView& frame, const uint8_t* d_bgr, int h, int w, const char* who) {
     RCCHK(order_behind_own_stream(t, s));
     t->last_launches = t->last_waits = 0;
-    LwtIngestParams ip{d_records, d_count, Q, reinterpret_cast<float*>(t->io.dev + t->o_boxes), t->d_ndet};
+    LwtIngestParams ip{frame, reinterpret_cast<float*>(t->io.dev + t->o_boxes), t->d_ndet};
     HIPCHK(opd_launch_lwt_ingest(ip, s));
     ++t->last_launches;
     RCCHK(lwt_enqueue_reference(t, s, who, d_bgr, OPD_MEM_DEVICE, h, w, &t->fused_which));
-    return lwt_enqueue_update(t, s, Q, t->d_ndet);
+    return lwt_enqueue_update(t, s, frame.stride, t->d_ndet);
 }
 
 int lwt_fused_fetch(opd_lwt* t, hipStream_t s, int Q) {
@@ -275,7 +275,7 @@ int lwt_sequence_check(const opd_lwt* t, const LwtSeqCall& c, int capacity, int 
     return OPD_OK;
 }
 
-int lwt_sequence_enqueue(opd_lwt* t, hipStream_t s, const LwtSeqCall& c, const opd_det* d_records, const int32_t* d_counts, const uint8_t* d_camera, const char* who) {
+int lwt_sequence_enqueue(opd_lwt* t, hipStream_t s, const LwtSeqCall& c, const RecordView* view, const uint8_t* d_camera, const char* who) {
     RCCHK(t->seq.reserve(who, seq_bytes(t), seq_bytes(t), t->stream()));
     RCCHK(order_behind_own_stream(t, s));
     t->last_launches = t->last_waits = 0;
@@ -290,7 +290,7 @@ int lwt_sequence_enqueue(opd_lwt* t, hipStream_t s, const LwtSeqCall& c, const o
     for (int f = 0; f < c.F; ++f) {
         uint8_t* d_slot = t->seq.dev + (size_t)f * slot;
         if (c.is_key[f]) {
-            LwtIngestParams ip{d_records + (size_t)k * c.Q, d_counts + k, c.Q, reinterpret_cast<float*>(t->io.dev + t->o_boxes), t->d_ndet, t->d_stop};
+            LwtIngestParams ip{record_frame(*view, k), reinterpret_cast<float*>(t->io.dev + t->o_boxes), t->d_ndet, t->d_stop};
             HIPCHK(opd_launch_lwt_ingest(ip, s));
             ++t->last_launches;
             if (t->flow) {

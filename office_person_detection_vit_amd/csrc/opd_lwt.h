@@ -9,6 +9,7 @@
 
 #include "opd_device.h"
 #include "opd_flow.h"
+#include "opd_records.h"
 
 enum { LWT_THREADS = 256, LWT_MAX_TRACKS = 1024, LWT_MAX_DETS = 1024, LWT_MAX_SEQUENCE = 64 };
 enum { LWT_ID = 0, LWT_AGE = 1, LWT_HITS = 2, LWT_TSU = 3, LWT_F32 = 4, LWT_META = 5 };   // columns of LwtBank::meta
@@ -58,11 +59,10 @@ struct LwtInterpParams {
     const int32_t* stop;     // null, or the sticky word of a sequence call
 };
 
-// the kept records of one frame [Q] and their device-resident count -> boxes [n][4] xywh float32 and the clamped count (the fused detect call)
+// the kept records of ONE frame (a view of n_frames = 1: post-process records [Q], or the merged records of a tiled frame [n_tiles x Q]) and their
+// device-resident count -> boxes [n][4] xywh float32 and the count clamped to the view's stride (the fused detect calls)
 struct LwtIngestParams {
-    const opd_det* records;
-    const int32_t* count;
-    int32_t Q;
+    opd::RecordView view;
     float* boxes;
     int32_t* n_out;
     const int32_t* stop;     // null, or the sticky word of a sequence call
@@ -119,14 +119,16 @@ int lwt_adopt_update(opd_lwt* t, const std::string& who, int which, int n);
 // stream `s`.  lwt_fused_check: the refusals, before any device work.  lwt_fused_enqueue: ingest of the frame's kept records (where the
 // suppression left them, `d_count` of them), gray + pyramid of the camera-resolution frame at `d_bgr`, the update.  lwt_fused_fetch: the
 // [head | ids] image joins the call's fetch.  lwt_fused_finish, behind the wait: adoption, and the ids of the `n` kept records (-1 each
-// for an update the kernel refused, which is the return code).
+// for an update the kernel refused, which is the return code).  `frame`: the records of the tracker's frame through the call's view
+// (record_frame, opd_records.h); its stride is the Q of the other three: num_queries, or n_tiles x num_queries of a tiled call, whose
+// d_bgr is the WHOLE frame.
 int lwt_fused_check(const opd_lwt* t, int device, int Q, int h, int w, const std::string& who);
-int lwt_fused_enqueue(opd_lwt* t, hipStream_t s, const opd_det* d_records, const int32_t* d_count, int Q, const uint8_t* d_bgr, int h, int w, const char* who);
+int lwt_fused_enqueue(opd_lwt* t, hipStream_t s, const opd::RecordView& frame, const uint8_t* d_bgr, int h, int w, const char* who);
 int lwt_fused_fetch(opd_lwt* t, hipStream_t s, int Q);
 int lwt_fused_finish(opd_lwt* t, int n, int32_t* ids_out, const std::string& who);
 
-// A run of F frames of ONE camera in one call (opd_detr_detect_sequence_hybrid), in the same four steps.  The K key frames (is_key[f] != 0)
-// have gone through one batched forward: their kept records lie at d_records [K][Q] with d_counts [K], their camera-resolution frames at
+// A run of F frames of ONE camera in one call (opd_detr_detect_sequence_hybrid, opd_detr_detect_tiled_sequence_hybrid), in the same four steps.
+// The K key frames (is_key[f] != 0) have gone through one batched forward: their kept records are the K frames of `view` (stride Q; null with K = 0), their camera-resolution frames lie at
 // d_camera [K][h][w][3].  In frame order on `s`: a key frame runs ingest, gray + pyramid and the update; an in-between frame is uploaded
 // from where it lies and runs gray + pyramid, LK and the track kernel.  Every launch carries the handle's sticky word: the update of a key
 // frame whose new tracks do not fit raises it, and all launches behind leave at once, so the state and the reference frame stay those of
@@ -134,10 +136,10 @@ int lwt_fused_finish(opd_lwt* t, int n, int32_t* ids_out, const std::string& who
 struct LwtSeqCall {
     const uint8_t* const* frames;   // [F] host
     const uint8_t* is_key;          // [F]
-    int F, h, w, Q;
+    int F, h, w, Q;                 // Q: the record slots of a key frame (num_queries; a tiled call: n_tiles x num_queries)
 };
 int lwt_sequence_check(const opd_lwt* t, const LwtSeqCall& c, int capacity, int device, const std::string& who);
-int lwt_sequence_enqueue(opd_lwt* t, hipStream_t s, const LwtSeqCall& c, const opd_det* d_records, const int32_t* d_counts, const uint8_t* d_camera, const char* who);
+int lwt_sequence_enqueue(opd_lwt* t, hipStream_t s, const LwtSeqCall& c, const opd::RecordView* view, const uint8_t* d_camera, const char* who);
 int lwt_sequence_fetch(opd_lwt* t, hipStream_t s, int F);
 // behind the wait.  key_counts [K] (host): the kept records of the key frames; track_ids [K][Q]; recs_out [F - K][capacity], rec_counts [F - K]
 int lwt_sequence_finish(opd_lwt* t, const LwtSeqCall& c, const int32_t* key_counts, int32_t* track_ids, opd_lwt_rec* recs_out, int capacity, int32_t* rec_counts,

@@ -16,9 +16,7 @@ TAPI int opd_lwt_test_ingest(int device, const opd_det* records, int n, int Q, f
     RCCHK(use_device("opd_lwt_test_ingest", device));
     DevMem tmp;
     LwtIngestParams p{};
-    p.records = tmp.up(records, (size_t)Q);
-    p.count = tmp.up(&n, 1);
-    p.Q = Q;
+    p.view = RecordView{tmp.up(records, (size_t)Q), nullptr, tmp.up(&n, 1), 1, Q};
     p.boxes = tmp.up(boxes, (size_t)Q * 4);
     p.n_out = tmp.up(n_out, 1);
     if (!tmp.ok) return fail(OPD_ENOMEM, "opd_lwt_test_ingest: device allocation failed");

@@ -458,7 +458,7 @@ struct HybridStage {   // the kept records and the camera-resolution frames ente
     struct opd_lwt* const* trackers = nullptr;   // (`seq`) as the key frames of the run of frames `call` of one camera, its in-between frames around them
     struct opd_lwt* seq = nullptr;
     const ::LwtSeqCall* call = nullptr;
-    int32_t* track_ids = nullptr;   // [B][queries]
+    int32_t* track_ids = nullptr;   // [B][queries]; a tiled call: [n_frames][n_tiles x queries], by position in the merged records, which the stage then reads
     opd_lwt_rec* recs_out = nullptr; int capacity = 0;           // seq: the in-between frames' records [F - B][capacity], their counts, frames applied
     int32_t *rec_counts = nullptr, *frames_done = nullptr;
     const char* entry = "opd_detr_detect_frames_hybrid";         // the entry errors are worded for

@@ -669,7 +669,8 @@ class HipDetrDetector:
         the forward runs as a ragged batch, and suppression, merge and the stages run as in the other tiled calls, behind one host wait.  The
         lists are those of ``TiledDetector(native=False)``, field for field.  Frames go in chunks of ``max_batch // len(tiles)``.
         ``features`` (``None`` or ``"color"``), ``floor_map`` and ``trackers`` as in ``detect_tiled_stages``, with the same fallback to the
-        separate calls where the fused conditions fail.  Re-ID rows inside the call are not offered for such a grid."""
+        separate calls where the fused conditions fail.  Re-ID rows inside the call are a method of their own for such a grid,
+        ``detect_tiled_ragged_reid``."""
         self._require_model()
         frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
         if features not in (None, "color"):
@@ -682,23 +683,9 @@ class HipDetrDetector:
                 raise ValueError(f"{len(trackers)} trackers for {len(frames)} frames: frame f enters trackers[f]")
             if len({id(t) for t in trackers}) != len(trackers):
                 raise ValueError("a tracker is named twice: a tracker takes one frame per call")
-        if not tiles or any(len(t) != 4 for t in tiles):
-            raise ValueError("tiles must be a non-empty list of (y0, x0, h, w)")
-        if len(tiles) > self.max_batch:
-            raise ValueError(f"the {len(tiles)} tiles of one frame exceed max_batch = {self.max_batch}")
-        if any(t[2] < 1 or t[3] < 1 for t in tiles):
-            raise ValueError("tiles must have a height and a width of at least 1")
+        h, w, sizes = self._ragged_geometry(frames, tiles)
         if len(frames) == 0:
             return []
-        f0 = frames[0]
-        for f in frames:
-            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != f0.shape or not f.flags.c_contiguous:
-                raise ValueError("frames must be contiguous uint8 numpy arrays of shape (H, W, 3) in BGR order, all of one size")
-        h, w = int(f0.shape[0]), int(f0.shape[1])
-        sizes = self.tile_model_sizes(tiles)
-        H, W = max(s[0] for s in sizes), max(s[1] for s in sizes)
-        if max(H, W) > max(self.max_size) or H * W > self.max_size[0] * self.max_size[1]:
-            raise ValueError(f"ragged batch canvas {H}x{W} exceeds the configured maximum {self.max_size} (either orientation)")
         T, Q = len(tiles), self._info.num_queries
         S = T * Q
         staged = not (features is None and floor_map is None and trackers is None)
@@ -781,6 +768,17 @@ class HipDetrDetector:
                 if trackers is not None:
                     trackers[b].update(dets)
             return out
+        return self._tiled_reid_chunks("opd_detr_detect_tiled_reid", (H, W), frames, tiles, reid, nms_threshold, merge_threshold, edge_tolerance, reid_slots, floor_map, trackers)
+
+    def _tiled_reid_chunks(self, entry: str, sizes: tuple, frames, tiles, reid, nms_threshold: float, merge_threshold: float, edge_tolerance: float,
+                           reid_slots: int, floor_map, trackers) -> List[List[Detection]]:
+        """The calls of ``detect_tiled_reid`` and ``detect_tiled_ragged_reid``, a chunk of ``max_batch // len(tiles)`` checked frames each: ``entry``
+        with ``sizes`` where the model size goes (``(H, W)``, or ``(tile_HW,)`` as a pointer), the Re-ID stages block, and the records, rows by
+        slot, made into detections."""
+        h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
+        T = len(tiles)
+        S = T * self._info.num_queries
+        call = getattr(self._lib, entry)
         E = int(reid.feature_dim)
         win = np.asarray(tiles, dtype=np.int32).reshape(T, 4)
         params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
@@ -794,7 +792,7 @@ class HipDetrDetector:
                 slots = max(1, min(int(reid_slots) * n, int(reid.max_crops)))
                 recs, counts = (_capi.OpdTileDet * (n * S))(), (C.c_int32 * n)()
                 ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in chunk])
-                args = (C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, H, W, float(self.confidence_threshold), C.byref(params))
+                args = (C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, *sizes, float(self.confidence_threshold), C.byref(params))
                 # rows by slot: row k belongs to merged record slot_map[k] = b * S + position; floor and track-id rows by position
                 feats = floor = ids = None
                 slot_map, n_person = np.full(slots, -1, np.int32), np.zeros(1, np.int32)
@@ -812,9 +810,9 @@ class HipDetrDetector:
                     handles = (C.c_void_p * n)(*[t._h.value for t in trackers[i:i + n]])
                     ids, n_featured = np.full(n * S, -1, np.int32), np.zeros(n, np.int32)
                     st.trackers, st.track_ids, st.n_featured = C.addressof(handles), ids.ctypes.data, n_featured.ctypes.data
-                rc = self._lib.opd_detr_detect_tiled_reid(*args, C.byref(st), recs, counts)
+                rc = call(*args, C.byref(st), recs, counts)
                 if not (rc != 0 and trackers is not None and "counted as one without detections" in _capi.last_error()):
-                    _capi.check(rc, "opd_detr_detect_tiled_reid")   # (out of slots: records and ids were delivered; the mirrors follow first)
+                    _capi.check(rc, entry)   # (out of slots: records and ids were delivered; the mirrors follow first)
                 message = _capi.last_error() if rc != 0 else ""
                 row_of = {int(p): k for k, p in enumerate(slot_map[:min(int(n_person[0]), slots)])}
                 chunk_dets, missing = [], []
@@ -842,12 +840,213 @@ class HipDetrDetector:
                         chunk_dets[b][k].features = row
                 out.extend(chunk_dets)
                 if rc != 0:
-                    raise RuntimeError(f"opd_detr_detect_tiled_reid failed (code {rc}): {message}")
+                    raise RuntimeError(f"{entry} failed (code {rc}): {message}")
             self._last_orig = [(h, w)] * len(frames)
             return out
         except Exception as e:
             logger.error(f"Detection failed: {e}")
             raise
+
+    def detect_tiled_ragged_reid(self, frames: Sequence[np.ndarray], tiles: Sequence[Tuple[int, int, int, int]], reid, nms_threshold: float = 0.4,
+                                 merge_threshold: float = 0.5, edge_tolerance: float = 0.01, reid_slots: int = 32, floor_map=None,
+                                 trackers=None) -> List[List[Detection]]:
+        """``detect_tiled_reid`` for ``tiles`` that DIFFER in size (``opd_detr_detect_tiled_ragged_reid``): the source step and forward of
+        ``detect_tiled_ragged``, and behind the seam merge the Re-ID, floor and track stages of ``detect_tiled_reid``, slots, rows and fallback
+        to the separate calls included.  The lists equal ``detect_tiled_ragged`` + ``reid.extract_features`` (+ ``floor_map.apply``,
+        + ``tracker.update``)."""
+        self._require_model()
+        frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
+        if reid is None:
+            raise ValueError("detect_tiled_ragged_reid needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
+        if trackers is not None:
+            trackers = list(trackers)
+            if len(trackers) != len(frames):
+                raise ValueError(f"{len(trackers)} trackers for {len(frames)} frames: frame f enters trackers[f]")
+            if len({id(t) for t in trackers}) != len(trackers):
+                raise ValueError("a tracker is named twice: a tracker takes one frame per call")
+        if not getattr(reid, "is_loaded", True):
+            raise RuntimeError("Re-ID model is not loaded: call load_model() first")
+        h, w, sizes = self._ragged_geometry(frames, tiles)
+        if len(frames) == 0:
+            return []
+        S = len(tiles) * self._info.num_queries
+        if not self._tiled_reid_fused(S, reid, floor_map, trackers):
+            out = self.detect_tiled_ragged(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
+            for b, dets in enumerate(out):
+                for det, row in zip(dets, reid.extract_features(frames[b], [d.bbox for d in dets])):
+                    det.features = row
+                if floor_map is not None:
+                    floor_map.apply(dets)
+                if trackers is not None:
+                    trackers[b].update(dets)
+            return out
+        tile_hw = np.asarray(sizes, dtype=np.int32).reshape(len(tiles), 2)
+        return self._tiled_reid_chunks("opd_detr_detect_tiled_ragged_reid", (tile_hw.ctypes.data_as(C.c_void_p),), frames, tiles, reid, nms_threshold, merge_threshold,
+                                       edge_tolerance, reid_slots, floor_map, trackers)
+
+    def _ragged_geometry(self, frames: list, tiles: list):
+        """The checks of a tiled call whose tiles may differ in size (``detect_tiled_ragged`` has them): ``(h, w, model size of every tile)``;
+        ``h = w = 0`` without frames."""
+        if not tiles or any(len(t) != 4 for t in tiles):
+            raise ValueError("tiles must be a non-empty list of (y0, x0, h, w)")
+        if len(tiles) > self.max_batch:
+            raise ValueError(f"the {len(tiles)} tiles of one frame exceed max_batch = {self.max_batch}")
+        if any(t[2] < 1 or t[3] < 1 for t in tiles):
+            raise ValueError("tiles must have a height and a width of at least 1")
+        sizes = self.tile_model_sizes(tiles)
+        if len(frames) == 0:
+            return 0, 0, sizes
+        f0 = frames[0]
+        for f in frames:
+            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != f0.shape or not f.flags.c_contiguous:
+                raise ValueError("frames must be contiguous uint8 numpy arrays of shape (H, W, 3) in BGR order, all of one size")
+        H, W = max(s[0] for s in sizes), max(s[1] for s in sizes)
+        if max(H, W) > max(self.max_size) or H * W > self.max_size[0] * self.max_size[1]:
+            raise ValueError(f"ragged batch canvas {H}x{W} exceeds the configured maximum {self.max_size} (either orientation)")
+        return int(f0.shape[0]), int(f0.shape[1]), sizes
+
+    # ---- the hybrid tracker inside a tiled call --------------------------------------------------------------------------------------
+    def _detect_tiled_any(self, frames, tiles, nms_threshold: float, merge_threshold: float, edge_tolerance: float) -> List[List[Detection]]:
+        """``detect_tiled``, or for tiles of more than one size ``detect_tiled_ragged``: the separate call the hybrid tiled methods equal."""
+        call = self.detect_tiled if len({(t[2], t[3]) for t in tiles}) == 1 else self.detect_tiled_ragged
+        return call(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
+
+    def _tiled_hybrid_call(self, tiles: list, sizes: list):
+        """What the hybrid tiled entries take for the windows and the model size: ``(win, H, W, tile_HW pointer or None, what must stay alive)``."""
+        T = len(tiles)
+        win = np.asarray(tiles, dtype=np.int32).reshape(T, 4)
+        if len({(t[2], t[3]) for t in tiles}) == 1:
+            return win, int(sizes[0][0]), int(sizes[0][1]), None, None
+        tile_hw = np.asarray(sizes, dtype=np.int32).reshape(T, 2)
+        return win, 0, 0, tile_hw.ctypes.data_as(C.c_void_p), tile_hw
+
+    def _tile_records(self, recs, base: int, cnt: int) -> List[Detection]:
+        dets = []
+        for k in range(cnt):
+            r = recs[base + k]
+            bbox = (r.x, r.y, r.w, r.h)
+            dets.append(Detection(bbox=bbox, confidence=float(r.score), class_id=int(r.label), class_name="person",
+                                  camera_coords=(bbox[0] + bbox[2] / 2, bbox[1] + bbox[3]), features=None, query_index=int(r.query_index)))
+        return dets
+
+    def detect_tiled_hybrid(self, frames: Sequence[np.ndarray], tiles: Sequence[Tuple[int, int, int, int]], lwts, nms_threshold: float = 0.4,
+                            merge_threshold: float = 0.5, edge_tolerance: float = 0.01, floor_map=None) -> List[List[Detection]]:
+        """``detect_tiled`` (tiles of several sizes: ``detect_tiled_ragged``) and, per frame f, ``lwts[f].update_with_detections(frames[f], dets)``
+        (+ ``floor_map.apply``) as ONE native call per chunk with one host wait (``opd_detr_detect_tiled_hybrid``): the merged records enter the
+        ``HipLightweightTracker`` where the seam merge left them, and the gray pyramid of the new reference frame is built from the WHOLE frame
+        the tiled source uploaded, not uploaded again.  Returns the merged detections with ``track_id`` set: same ids, track states and flow
+        points as the separate calls.  Where a tracker is on another GPU or has ``max_tracks`` below ``tiles x queries`` (or the floor map is on
+        another GPU) the separate calls run one after the other."""
+        self._require_model()
+        frames, tiles, lwts = list(frames), [tuple(int(v) for v in t) for t in tiles], list(lwts)
+        if len(lwts) != len(frames):
+            raise ValueError(f"{len(lwts)} trackers for {len(frames)} frames: frame f enters lwts[f]")
+        if len({id(t) for t in lwts}) != len(lwts):
+            raise ValueError("a tracker is named twice: a tracker takes one frame per call")
+        h, w, sizes = self._ragged_geometry(frames, tiles)
+        if len(frames) == 0:
+            return []
+        T = len(tiles)
+        S = T * self._info.num_queries
+        fused = all(t.device == self.device_ordinal and t.max_tracks >= S for t in lwts) and (floor_map is None or int(floor_map.device) == self.device_ordinal)
+        if not fused:
+            out = self._detect_tiled_any(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
+            for b, dets in enumerate(out):
+                lwts[b].update_with_detections(frames[b], dets)
+                if floor_map is not None:
+                    floor_map.apply(dets)
+            return out
+        win, H, W, hw_ptr, _keep = self._tiled_hybrid_call(tiles, sizes)
+        params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
+                                     merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
+        per = max(1, self.max_batch // T)
+        out: List[List[Detection]] = []
+        for i in range(0, len(frames), per):
+            chunk, trackers = frames[i:i + per], lwts[i:i + per]
+            n = len(chunk)
+            for t in trackers:
+                t._ensure(h, w)
+            recs, counts = (_capi.OpdTileDet * (n * S))(), (C.c_int32 * n)()
+            ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in chunk])
+            handles = (C.c_void_p * n)(*[t._h.value for t in trackers])
+            ids = np.full(n * S, -1, np.int32)
+            hy = _capi.OpdTileHybrid(struct_size=C.sizeof(_capi.OpdTileHybrid), trackers=C.addressof(handles), track_ids=ids.ctypes.data)
+            floor = None
+            if floor_map is not None:
+                floor = np.zeros(n * S, floor_map.REC_DTYPE)
+                hy.floor, hy.floor_out = floor_map._require().value, floor.ctypes.data
+            rc = self._lib.opd_detr_detect_tiled_hybrid(C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, H, W, hw_ptr,
+                                                        float(self.confidence_threshold), C.byref(params), C.byref(hy), recs, counts)
+            _capi.check(rc, "opd_detr_detect_tiled_hybrid")
+            for b in range(n):
+                dets = self._tile_records(recs, b * S, int(counts[b]))
+                if floor is not None:
+                    for k, det in enumerate(dets):
+                        floor_map._fill(det, floor[b * S + k])
+                out.append(trackers[b]._adopt(dets, ids[b * S:b * S + len(dets)].tolist()))
+        self._last_orig = [(h, w)] * len(frames)
+        return out
+
+    def track_tiled_hybrid_batch(self, frames: Sequence[np.ndarray], tiles: Sequence[Tuple[int, int, int, int]], lwt, key_frames: Sequence,
+                                 nms_threshold: float = 0.4, merge_threshold: float = 0.5, edge_tolerance: float = 0.01) -> list:
+        """``track_hybrid_batch`` on TILED frames of one camera: ``key_frames[f]`` true makes frame f a detection frame (``detect_tiled_hybrid``),
+        false an in-between frame (``lwt.interpolate``).  One entry per frame: a ``List[Detection]`` (merged, ``track_id`` set) for a key frame, a
+        ``List[(track_id, bbox)]`` for an in-between frame, ids and track states those of the per-frame loop.  The frames go down in runs of at
+        most ``max_batch // len(tiles)`` key frames and 64 frames, each run ONE native call with one tiled forward and one host wait
+        (``opd_detr_detect_tiled_sequence_hybrid``).  Where the conditions of ``detect_tiled_hybrid`` fail, the per-frame loop runs instead."""
+        self._require_model()
+        frames, tiles, keys = list(frames), [tuple(int(v) for v in t) for t in tiles], [bool(k) for k in key_frames]
+        if len(keys) != len(frames):
+            raise ValueError(f"{len(frames)} frames, {len(keys)} key flags")
+        h, w, sizes = self._ragged_geometry(frames, tiles)
+        per = max(1, self.max_batch // len(tiles))
+        out: list = []
+        start = 0
+        while start < len(frames):
+            end, n_key = start, 0   # the longest run from `start` within the limits of one call
+            while end < len(frames) and end - start < lwt.SEQUENCE_MAX and (not keys[end] or n_key < per):
+                n_key += keys[end]
+                end += 1
+            out.extend(self._track_tiled_hybrid_run(frames[start:end], tiles, sizes, lwt, keys[start:end], nms_threshold, merge_threshold, edge_tolerance))
+            start = end
+        return out
+
+    def _track_tiled_hybrid_run(self, frames: list, tiles: list, sizes: list, lwt, keys: List[bool], nms_threshold: float, merge_threshold: float,
+                                edge_tolerance: float) -> list:
+        T = len(tiles)
+        S = T * self._info.num_queries
+        h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
+        fused = lwt.device == self.device_ordinal and lwt.max_tracks >= S
+        if fused and not any(keys) and not lwt._h:   # (no handle yet and no detection frame to make one: nothing to interpolate)
+            fused = False
+        if not fused:
+            return [lwt.update_with_detections(f, self._detect_tiled_any([f], tiles, nms_threshold, merge_threshold, edge_tolerance)[0]) if k else lwt.interpolate(f)
+                    for f, k in zip(frames, keys)]
+        lwt._ensure(h, w)
+        win, H, W, hw_ptr, _keep = self._tiled_hybrid_call(tiles, sizes)
+        params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
+                                     merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
+        F, K = len(frames), sum(keys)
+        cap = lwt.max_tracks
+        recs, counts, ids = (_capi.OpdTileDet * (max(K, 1) * S))(), (C.c_int32 * max(K, 1))(), np.full(max(K, 1) * S, -1, np.int32)
+        lrecs, lcounts, done = (_capi.OpdLwtRec * (max(F - K, 1) * cap))(), (C.c_int32 * max(F - K, 1))(), C.c_int32(0)
+        ptrs = (C.c_void_p * F)(*[f.ctypes.data for f in frames])
+        flags = (C.c_uint8 * F)(*[int(k) for k in keys])
+        rc = self._lib.opd_detr_detect_tiled_sequence_hybrid(C.c_void_p(self.model), lwt._h, ptrs, flags, F, h, w, win.ctypes.data_as(C.c_void_p), T, H, W, hw_ptr,
+                                                             float(self.confidence_threshold), C.byref(params), recs, counts, ids.ctypes.data, lrecs, cap, lcounts,
+                                                             C.byref(done))
+        _capi.check(rc, "opd_detr_detect_tiled_sequence_hybrid")
+        self._last_orig = [(h, w)] * K
+        out, k, j = [], 0, 0
+        for f in range(F):
+            if keys[f]:
+                dets = self._tile_records(recs, k * S, int(counts[k]))
+                out.append(lwt._adopt(dets, ids[k * S:k * S + len(dets)].tolist()))
+                k += 1
+            else:
+                out.append([(int(lrecs[j * cap + i].track_id), tuple(float(v) for v in lrecs[j * cap + i].bbox)) for i in range(lcounts[j])])
+                j += 1
+        return out
 
     def _tiled_reid_fused(self, S: int, reid, floor_map, trackers) -> bool:
         """Whether the Re-ID stage of a tiled call can run inside it (``detect_tiled_reid`` has the conditions)."""

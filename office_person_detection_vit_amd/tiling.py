@@ -121,7 +121,11 @@ class TiledDetector:
     ``mixed_sizes=True`` (with ``native=True``): a grid whose tiles differ in size (interior tiles at the default overlap: 2 x 3, 3 x 3, ...; a
     frame side that does not divide) goes through the wrapped detector's ``detect_tiled_ragged`` instead of being refused: every tile at its
     own model size inside one canvas, one ragged forward, the same lists field for field.  A grid of one size takes the calls it always took.
-    ``features="reid"`` on such a grid runs the Re-ID rows as a separate call on the merged detections."""
+    ``features="reid"`` on such a grid goes to ``detect_tiled_ragged_reid`` where the wrapped detector has it, else the Re-ID rows are a separate
+    call on the merged detections.
+
+    ``detect_and_track_hybrid`` / ``track_hybrid_batch`` take a ``HipLightweightTracker``: the reference's hybrid mode on tiled frames, inside the
+    wrapped detector's tiled call where that is possible."""
 
     def __init__(self, detector, rows: int = 2, cols: int = 2, nms_threshold: float = 0.4, overlap: float = DEFAULT_OVERLAP,
                  merge_threshold: float = 0.5, native: bool = False, mixed_sizes: bool = False):
@@ -204,14 +208,26 @@ class TiledDetector:
         from .reid import _ReIDExtractorBase
         return isinstance(reid, _ReIDExtractorBase) and reid.is_loaded
 
+    def _reid_call(self, frame: np.ndarray, features: Optional[str], reid):
+        """``(method, grid)`` of the wrapped detector's tiled call that brings the Re-ID rows itself, or ``(None, None)``: ``detect_tiled_reid`` for
+        a grid of one size, ``detect_tiled_ragged_reid`` for a mixed grid under ``mixed_sizes=True`` where the detector has it."""
+        if not self._native_reid(features, reid):
+            return None, None
+        grid = self._native_grid([frame])
+        if not self._mixed(grid):
+            return self.detector.detect_tiled_reid, grid
+        if hasattr(self.detector, "detect_tiled_ragged_reid"):
+            return self.detector.detect_tiled_ragged_reid, grid
+        return None, None
+
     def detect_with_features(self, frame: np.ndarray, features: str = "color", reid=None, reid_slots: int = 32) -> Tuple[List[Detection], np.ndarray]:
         """Merged detections + their (N, 256) colour-histogram rows (``features="reid"``: the (N, 512) rows of ``reid``), assigned to
         ``det.features``.  ``native=True`` with colour: inside the wrapped detector's one tiled call (``detect_tiled_stages``); with a loaded
         ``HipReIDExtractor`` / ``HipOSNetReIDExtractor``: inside ``detect_tiled_reid``, for the first ``reid_slots`` merged records."""
         self._check_features(features, reid, allow_none=False)
-        if self._native_reid(features, reid) and not self._mixed(self._native_grid([frame])):
-            grid = self._native_grid([frame])
-            dets = self.detector.detect_tiled_reid([frame], grid, reid, self.nms_threshold, self.merge_threshold, reid_slots=reid_slots)[0]
+        call, grid = self._reid_call(frame, features, reid)
+        if call is not None:
+            dets = call([frame], grid, reid, self.nms_threshold, self.merge_threshold, reid_slots=reid_slots)[0]
             return dets, (np.stack([d.features for d in dets]) if dets else np.array([]))
         if self.native and features == "color":
             grid = self._native_grid([frame], staged=True)   # (refuses a detector without detect_tiled)
@@ -226,9 +242,9 @@ class TiledDetector:
         ``HipReIDExtractor`` / ``HipOSNetReIDExtractor``): ONE tiled call with one host wait, the merged records and their rows entering ``tracker``
         where they lie.  Returns the detections that got an id."""
         self._check_features(features, reid, allow_none=True)
-        if self._native_reid(features, reid) and not self._mixed(self._native_grid([frame])):
-            grid = self._native_grid([frame])
-            dets = self.detector.detect_tiled_reid([frame], grid, reid, self.nms_threshold, self.merge_threshold, reid_slots=reid_slots, trackers=[tracker])[0]
+        call, grid = self._reid_call(frame, features, reid)
+        if call is not None:
+            dets = call([frame], grid, reid, self.nms_threshold, self.merge_threshold, reid_slots=reid_slots, trackers=[tracker])[0]
             return [d for d in dets if d.track_id is not None]
         if self.native and features != "reid":
             grid = self._native_grid([frame], staged=True)
@@ -238,3 +254,38 @@ class TiledDetector:
         dets = self.detect(frame)
         self._host_features(frame, dets, features, reid)
         return tracker.update(dets)
+
+    def _native_hybrid(self, method: str, frames: Sequence[np.ndarray], lwt):
+        """The grid when ``lwt`` (a ``HipLightweightTracker``) can enter the wrapped detector's tiled call ``method``, else None: ``native=True``, a
+        detector with the method, the tracker on its device with room for ``tiles x queries`` records, and a grid of one size or ``mixed_sizes=True``."""
+        if not (self.native and hasattr(self.detector, method)) or len(frames) == 0:
+            return None
+        if any(not isinstance(f, np.ndarray) for f in frames) or len({(f.shape[0], f.shape[1]) for f in frames}) != 1:
+            return None
+        grid = tile_grid(frames[0].shape[0], frames[0].shape[1], self.rows, self.cols, self.overlap)
+        if len({(t[2], t[3]) for t in grid}) != 1 and not self.mixed_sizes:
+            return None
+        slots = len(grid) * int(getattr(self.detector, "num_queries", 0) or 0)
+        if slots < 1 or getattr(lwt, "device", None) != getattr(self.detector, "device_ordinal", None) or getattr(lwt, "max_tracks", 0) < slots:
+            return None
+        return grid
+
+    def detect_and_track_hybrid(self, frame: np.ndarray, lwt) -> List[Detection]:
+        """``lwt.update_with_detections(frame, self.detect(frame))``, the detection frame of the reference's hybrid mode on a tiled frame;
+        ``native=True``: ONE tiled call with one host wait (``detect_tiled_hybrid``), the merged records entering ``lwt`` where they lie and its
+        gray pyramid built from the frame as uploaded.  Same ids and track states either way."""
+        grid = self._native_hybrid("detect_tiled_hybrid", [frame], lwt)
+        if grid is None:
+            return lwt.update_with_detections(frame, self.detect(frame))
+        return self.detector.detect_tiled_hybrid([frame], grid, [lwt], self.nms_threshold, self.merge_threshold)[0]
+
+    def track_hybrid_batch(self, frames: Sequence[np.ndarray], lwt, key_frames: Sequence) -> list:
+        """The reference's hybrid loop over consecutive tiled frames of one camera: a ``List[Detection]`` per key frame, a ``List[(track_id, bbox)]``
+        per in-between frame (``lwt.interpolate``).  ``native=True``: runs of frames in one call each (``track_tiled_hybrid_batch``)."""
+        frames, keys = list(frames), [bool(k) for k in key_frames]
+        if len(keys) != len(frames):
+            raise ValueError(f"{len(frames)} frames, {len(keys)} key flags")
+        grid = self._native_hybrid("track_tiled_hybrid_batch", frames, lwt)
+        if grid is None:
+            return [lwt.update_with_detections(f, self.detect(f)) if k else lwt.interpolate(f) for f, k in zip(frames, keys)]
+        return self.detector.track_tiled_hybrid_batch(frames, grid, lwt, keys, self.nms_threshold, self.merge_threshold)
