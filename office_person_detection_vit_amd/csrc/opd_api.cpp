@@ -358,27 +358,25 @@ static float* query_rows_out(const RecordSink& s) { return s.feature.kind == FEA
 // back (below).  Host outputs: [records of max_batch frames |
 // counts (| per-query feature rows)] in one copy, the floor rows, the Re-ID call's slot list (and rows, unless a tracker reads them in place).  Device
 // outputs were written in place by the post-process kernel.
-static int fetch_records(opd_detr* m, const RecordSink& s, ReidFusedCall* reid) {
-    const int B = m->last_B, Q = m->arch.queries;
-    if (s.tile.params) {
-        HIPCHK(hipMemcpyAsync(m->tile_pinned, m->d_tile_out, tile_out_off(m) + (size_t)B * Q * sizeof(opd_tile_det), hipMemcpyDeviceToHost, m->stream));
-        if (query_rows_out(s)) {   // the rows by position, where the per-query rows of a frame-list call travel
+static int fetch_records(opd_detr* m, const RecordSink& s, const CallRecords& c, ReidFusedCall* reid) {
+    const int B = m->last_B, frames = c.view.n_frames, stride = c.view.stride;   // (B x Q = frames x stride record slots either way)
+    const bool tiled = s.tile.params != nullptr;
+    if (tiled || !outputs_on_device(s.mem_kind)) {
+        if (tiled) {
+            HIPCHK(hipMemcpyAsync(m->tile_pinned, m->d_tile_out, tile_out_off(m) + (size_t)frames * stride * sizeof(opd_tile_det), hipMemcpyDeviceToHost, m->stream));
+            if (query_rows_out(s)) {   // the rows by position, where the per-query rows of a frame-list call travel
+                RCCHK(ensure_sync_pinned(m));
+                HIPCHK(hipMemcpyAsync(static_cast<char*>(m->sync_pinned) + feat_off(m), m->d_feat_all, B * feat_row(m), hipMemcpyDeviceToHost, m->stream));
+            }
+        } else {
             RCCHK(ensure_sync_pinned(m));
-            HIPCHK(hipMemcpyAsync(static_cast<char*>(m->sync_pinned) + feat_off(m), m->d_feat_all, B * feat_row(m), hipMemcpyDeviceToHost, m->stream));
+            HIPCHK(hipMemcpyAsync(m->sync_pinned, m->d_records, query_rows_out(s) ? feat_off(m) + B * feat_row(m) : rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
         }
-        if (s.floor.fmap) HIPCHK(hipMemcpyAsync(m->h_floor, m->d_floor, (size_t)B * Q * sizeof(opd_floor_rec), hipMemcpyDeviceToHost, m->stream));
+        if (s.floor.fmap) HIPCHK(hipMemcpyAsync(m->h_floor, m->d_floor, (size_t)frames * stride * sizeof(opd_floor_rec), hipMemcpyDeviceToHost, m->stream));
         if (reid) RCCHK(reid->copy_back(m->stream));   // the slot list (and the rows by slot, when the caller takes them)
-        if (s.hybrid.seq) RCCHK(lwt_sequence_fetch(s.hybrid.seq, m->stream, s.hybrid.call->F));
-        else if (s.hybrid.on())   // every tracker's [head | ids], an id per slot of a merged frame
-            for (int f = 0; f < s.tile.n_frames; ++f) RCCHK(lwt_fused_fetch(s.hybrid.trackers[f], m->stream, s.tile.n_tiles * Q));
-    } else if (!outputs_on_device(s.mem_kind)) {
-        RCCHK(ensure_sync_pinned(m));
-        HIPCHK(hipMemcpyAsync(m->sync_pinned, m->d_records, query_rows_out(s) ? feat_off(m) + B * feat_row(m) : rec_bytes(m) + (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
-        if (s.floor.fmap) HIPCHK(hipMemcpyAsync(m->h_floor, m->d_floor, (size_t)B * Q * sizeof(opd_floor_rec), hipMemcpyDeviceToHost, m->stream));
-        if (reid) RCCHK(reid->copy_back(m->stream));
         if (s.hybrid.seq) RCCHK(lwt_sequence_fetch(s.hybrid.seq, m->stream, s.hybrid.call->F));   // a slot per frame: [head | ids] or [head | records]
-        else if (s.hybrid.on())   // every tracker's [head | ids]
-            for (int b = 0; b < B; ++b) RCCHK(lwt_fused_fetch(s.hybrid.trackers[b], m->stream, Q));
+        else if (s.hybrid.on())   // every tracker's [head | ids], an id per record slot of its frame
+            for (int f = 0; f < frames; ++f) RCCHK(lwt_fused_fetch(s.hybrid.trackers[f], m->stream, stride));
     }
     HIPCHK(hipStreamSynchronize(m->stream));
     if (m->profiling) {
@@ -416,7 +414,7 @@ static int hand_to_ticket(opd_detr* m, const RecordSink& s) {
 // The feature, floor, track and tile parts deliver to the host after the call's own wait: setting one with WAIT_TICKET or WAIT_NONE, or with device
 // outputs, is a programming error (no entry point does).
 static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const uint8_t* d_camera) {
-    const int B = m->last_B, Q = m->arch.queries;
+    const int B = m->last_B;
     const bool dev = outputs_on_device(s.mem_kind), tiled = s.tile.params != nullptr, tracked = s.track.on();
     RCCHK(enqueue_postprocess(m, s.threshold, s.orig_hw, h ? h : m->last_H, h ? w : m->last_W, dev ? s.out : nullptr, dev ? s.counts : nullptr,
                               tiled ? s.tile.params->person_label : m->nms_label, tiled ? s.tile.params->tile_nms_threshold : m->nms_threshold));
@@ -430,37 +428,35 @@ static int deliver_records(opd_detr* m, const RecordSink& s, int h, int w, const
     if (s.hybrid.on()) RCCHK(enqueue_hybrid(m, s, recs, tiled ? s.tile.frame_h : h, tiled ? s.tile.frame_w : w, d_camera));
     if (s.wait == WAIT_NONE) return OPD_OK;
     if (s.wait == WAIT_TICKET) return hand_to_ticket(m, s);
-    RCCHK(fetch_records(m, s, reid ? &*reid : nullptr));
-    // behind the wait: into the caller's arrays
+    RCCHK(fetch_records(m, s, recs, reid ? &*reid : nullptr));
+    // behind the wait: into the caller's arrays, the stages' rows over the frames and the record slots per frame of the call's view
+    const int frames = recs.view.n_frames, stride = recs.view.stride;
     if (tiled) {
-        memcpy(s.tile.counts, m->tile_pinned, (size_t)s.tile.n_frames * 4);
-        memcpy(s.tile.out, static_cast<const char*>(m->tile_pinned) + tile_out_off(m), (size_t)B * Q * sizeof(opd_tile_det));
-        const int S = s.tile.n_tiles * Q;   // the stages' rows of a tiled call go by position: row f * S + k of merged record k of frame f
+        memcpy(s.tile.counts, m->tile_pinned, (size_t)frames * 4);
+        memcpy(s.tile.out, static_cast<const char*>(m->tile_pinned) + tile_out_off(m), (size_t)frames * stride * sizeof(opd_tile_det));
         if (query_rows_out(s)) memcpy(query_rows_out(s), static_cast<const char*>(m->sync_pinned) + feat_off(m), B * feat_row(m));
-        for (int f = 0; f < s.tile.n_frames; ++f) {
-            const int n = std::max(0, std::min(s.tile.counts[f], S));
-            if (s.floor.fmap) memcpy(s.floor.out + (size_t)f * S, m->h_floor + (size_t)f * S, (size_t)n * sizeof(opd_floor_rec));
-            if (tracked) s.track.n_featured[f] = rows.rows_kind == TRACK_ROWS_NONE ? 0 : n;
-        }
-        if (reid) {   // rows by slot: slot_map[k] = f * S + position; a frame's featured records are those that got a slot
-            reid->deliver(s.feature.features, s.feature.slot_map, s.feature.n_person);
-            if (tracked) reid->slots_per_frame(s.tile.n_frames, S, s.track.n_featured);
-        }
-        if (s.hybrid.on()) return finish_hybrid(s, recs);   // (adoption by the MERGED counts; no entry sets both tracker stages)
-        return tracked ? finish_trackers(m, s, recs, rows.rows_kind != TRACK_ROWS_NONE) : OPD_OK;
     } else if (!dev) unpack_records(m, m->sync_pinned, B, s.out, s.counts, query_rows_out(s));
-    if (reid && !tracked) reid->deliver(s.feature.features, s.feature.slot_map, s.feature.n_person);
-    if (s.floor.fmap)   // only rows of records of the class are handed on
-        for (int b = 0; b < B; ++b)
-            for (int i = 0; i < s.counts[b] && i < Q; ++i) {
-                const opd_det& r = s.out[(size_t)b * Q + i];
-                if (r.label == s.label && (unsigned)r.query_index < (unsigned)Q) s.floor.out[(size_t)b * Q + r.query_index] = m->h_floor[(size_t)b * Q + r.query_index];
-            }
-    if (s.hybrid.on()) return finish_hybrid(s, recs);   // (no entry sets both tracker stages)
+    // the Re-ID rows by slot and the slot list (a tiled call: slot_map[k] = f * S + position), where the caller takes the list: a frame-list call that
+    // hands the rows to a tracker leaves it null
+    if (reid && s.feature.slot_map) reid->deliver(s.feature.features, s.feature.slot_map, s.feature.n_person);
+    for (int f = 0; f < frames && s.floor.fmap; ++f) {
+        const int n = std::max(0, std::min(recs.counts[f], stride));
+        const size_t at = (size_t)f * stride;
+        if (tiled) {   // by position: row f * S + k of merged record k of frame f
+            memcpy(s.floor.out + at, m->h_floor + at, (size_t)n * sizeof(opd_floor_rec));
+            continue;
+        }
+        for (int i = 0; i < n; ++i) {   // by query, and only rows of records of the class are handed on
+            const opd_det& r = s.out[at + i];
+            if (r.label == s.label && (unsigned)r.query_index < (unsigned)stride) s.floor.out[at + r.query_index] = m->h_floor[at + r.query_index];
+        }
+    }
+    if (s.hybrid.on()) return finish_hybrid(s, recs);   // (adoption by the counts the call delivers; no entry sets both tracker stages)
     if (!tracked) return OPD_OK;
-    if (reid) reid->slots_per_frame(B, Q, s.track.n_featured);
-    else for (int b = 0; b < B; ++b) s.track.n_featured[b] = rows.rows_kind == TRACK_ROWS_NONE ? 0 : std::max(0, std::min(s.counts[b], Q));
-    return finish_trackers(m, s, recs, rows.rows_kind != TRACK_ROWS_NONE);
+    const bool featured = rows.rows_kind != TRACK_ROWS_NONE;
+    if (reid) reid->slots_per_frame(frames, stride, s.track.n_featured);   // a frame's featured records are those that got a slot
+    else for (int f = 0; f < frames; ++f) s.track.n_featured[f] = featured ? std::max(0, std::min(recs.counts[f], stride)) : 0;
+    return finish_trackers(m, s, recs, featured);
 }
 
 // The front half: the source step and the forward.  The launch timer starts anew here, once per call: the source's launches, the forward's and the
@@ -749,6 +745,28 @@ static int sequence_without_keys(opd_lwt* t, const LwtSeqCall& call, opd_lwt_rec
     t->last_waits = 1;
     return lwt_sequence_finish(t, call, nullptr, nullptr, recs_out, capacity, rec_counts, frames_done, me);
 }
+// What both sequence-hybrid entries refuse first, without a handle: the F range, the capacity, the null lists; then the key frames of the run into *keys,
+// and a null output among those their number asks for (`key_outputs`: out, counts and track_ids are there; `between_outputs`: recs_out and rec_counts)
+static int sequence_keys(const std::string& me, const uint8_t* const* frames, const uint8_t* is_key, int F, int capacity, const int32_t* frames_done, bool key_outputs,
+                         bool between_outputs, std::vector<const uint8_t*>* keys) {
+    if (F < 1 || F > LWT_MAX_SEQUENCE) return fail(OPD_EINVAL, me + ": " + std::to_string(F) + " frames, a call takes 1 .. " + std::to_string(LWT_MAX_SEQUENCE));
+    if (capacity < 1) return fail(OPD_EINVAL, me + ": capacity " + std::to_string(capacity) + " is below the tracker's max_tracks");
+    if (!frames || !is_key || !frames_done) return fail(OPD_EINVAL, me + ": null argument (frame list, key flags or frames_done)");
+    for (int f = 0; f < F; ++f)
+        if (is_key[f]) keys->push_back(frames[f]);
+    const int K = (int)keys->size();
+    if (K > 0 && !key_outputs) return fail(OPD_EINVAL, me + ": null output of the key frames");
+    if (K < F && !between_outputs) return fail(OPD_EINVAL, me + ": null output of the in-between frames");
+    return OPD_OK;
+}
+// A tracker inside a frame-list call takes the records the suppression on the device has kept, of the label it keeps
+static int check_device_nms(const opd_detr* m, int label, const std::string& me) {
+    if (m->nms_threshold < 0.f)
+        return fail(OPD_EINVAL, me + ": opd_detr_set_nms is off on this handle; a tracker takes the kept records of a frame, which only the suppression on the device leaves there");
+    if (m->nms_label != label)
+        return fail(OPD_EINVAL, me + ": opd_detr_set_nms keeps label " + std::to_string(m->nms_label) + ", the call asks for label " + std::to_string(label));
+    return OPD_OK;
+}
 // Tiled detection: every refusal comes before the first device call (check_tiles; check_shape makes none for host pixels).  `st` (null: opd_detr_detect_tiled
 // itself): the feature, floor and track parts of the sink, which then read the merged records where the merge left them, rows by position.  `rs`
 // (opd_detr_detect_tiled_reid; `st` is then null): the same with the Re-ID rows as the feature kind, rows by slot, a slot naming a position.
@@ -911,15 +929,9 @@ int opd_detr_detect_tiled_sequence_hybrid(opd_detr* m, opd_lwt* t, const uint8_t
                                           int n_tiles, int H, int W, const int32_t* tile_HW, float threshold, const opd_tile_params* p, opd_tile_det* out, int32_t* counts,
                                           int32_t* track_ids, opd_lwt_rec* recs_out, int capacity, int32_t* rec_counts, int32_t* frames_done) { return api_call("opd_detr_detect_tiled_sequence_hybrid", [&]() -> int {
     const std::string me = "opd_detr_detect_tiled_sequence_hybrid";
-    if (F < 1 || F > LWT_MAX_SEQUENCE) return fail(OPD_EINVAL, me + ": " + std::to_string(F) + " frames, a call takes 1 .. " + std::to_string(LWT_MAX_SEQUENCE));
-    if (capacity < 1) return fail(OPD_EINVAL, me + ": capacity " + std::to_string(capacity) + " is below the tracker's max_tracks");
-    if (!frames || !is_key || !frames_done) return fail(OPD_EINVAL, me + ": null argument (frame list, key flags or frames_done)");
     std::vector<const uint8_t*> keys;
-    for (int f = 0; f < F; ++f)
-        if (is_key[f]) keys.push_back(frames[f]);
+    RCCHK(sequence_keys(me, frames, is_key, F, capacity, frames_done, out && counts && track_ids, recs_out && rec_counts, &keys));
     const int K = (int)keys.size();
-    if (K > 0 && (!out || !counts || !track_ids)) return fail(OPD_EINVAL, me + ": null output of the key frames");
-    if (K < F && (!recs_out || !rec_counts)) return fail(OPD_EINVAL, me + ": null output of the in-between frames");
     LwtSeqCall call{frames, is_key, F, h, w, 0};
     if (K == 0) {   // no forward and no tiles: opd_lwt_interpolate_sequence, as in the frame-list entry
         if (!frame_size_ok(h, w)) return fail(OPD_EINVAL, me + ": source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
@@ -1095,10 +1107,7 @@ static int detect_track(const std::string& me, opd_detr* m, opd_reid* r, const T
     if (feature_kind == OPD_TRACK_FEAT_COLOR && (h > OPD_COLOR_MAX_EDGE || w > OPD_COLOR_MAX_EDGE))
         return fail(OPD_EINVAL, me + ": frames of " + std::to_string(h) + " x " + std::to_string(w) + " are outside the 4096 x 4096 the exact integer sums of the colour histogram are sized for");
     RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, true, me));
-    if (m->nms_threshold < 0.f)
-        return fail(OPD_EINVAL, me + ": opd_detr_set_nms is off on this handle; a tracker takes the kept records of a frame, which only the suppression on the device leaves there");
-    if (m->nms_label != label)
-        return fail(OPD_EINVAL, me + ": opd_detr_set_nms keeps label " + std::to_string(m->nms_label) + ", the call asks for label " + std::to_string(label));
+    RCCHK(check_device_nms(m, label, me));
     RecordSink sink = host_sink(threshold, label, out, counts);
     sink.track = track;
     int dim = 0;   // the width of a feature row of the kind
@@ -1147,10 +1156,7 @@ int opd_detr_detect_frames_hybrid(opd_detr* m, opd_lwt* const* trackers, const u
     if (!trackers || !frames || !out || !counts || !track_ids) return fail(OPD_EINVAL, me + ": null argument (tracker list, frame list or an output)");
     if (!frame_size_ok(h, w)) return fail(OPD_EINVAL, me + ": source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
     RCCHK(check_frame_list(m, frames, OPD_MEM_HOST, B, H, W, true, me));
-    if (m->nms_threshold < 0.f)
-        return fail(OPD_EINVAL, me + ": opd_detr_set_nms is off on this handle; a tracker takes the kept records of a frame, which only the suppression on the device leaves there");
-    if (m->nms_label != label)
-        return fail(OPD_EINVAL, me + ": opd_detr_set_nms keeps label " + std::to_string(m->nms_label) + ", the call asks for label " + std::to_string(label));
+    RCCHK(check_device_nms(m, label, me));
     for (int b = 0; b < B; ++b) {
         RCCHK(lwt_fused_check(trackers[b], m->device, m->arch.queries, h, w, me));
         for (int a = 0; a < b; ++a)
@@ -1168,23 +1174,14 @@ int opd_detr_detect_sequence_hybrid(opd_detr* m, opd_lwt* t, const uint8_t* cons
                                     float threshold, int label, opd_det* out, int32_t* counts, int32_t* track_ids, opd_lwt_rec* recs_out, int capacity,
                                     int32_t* rec_counts, int32_t* frames_done) { return api_call("opd_detr_detect_sequence_hybrid", [&]() -> int {
     const std::string me = "opd_detr_detect_sequence_hybrid";
-    if (F < 1 || F > LWT_MAX_SEQUENCE) return fail(OPD_EINVAL, me + ": " + std::to_string(F) + " frames, a call takes 1 .. " + std::to_string(LWT_MAX_SEQUENCE));
-    if (capacity < 1) return fail(OPD_EINVAL, me + ": capacity " + std::to_string(capacity) + " is below the tracker's max_tracks");
-    if (!frames || !is_key || !frames_done) return fail(OPD_EINVAL, me + ": null argument (frame list, key flags or frames_done)");
     std::vector<const uint8_t*> keys;
-    for (int f = 0; f < F; ++f)
-        if (is_key[f]) keys.push_back(frames[f]);
+    RCCHK(sequence_keys(me, frames, is_key, F, capacity, frames_done, out && counts && track_ids, recs_out && rec_counts, &keys));
     const int K = (int)keys.size();
-    if (K > 0 && (!out || !counts || !track_ids)) return fail(OPD_EINVAL, me + ": null output of the key frames");
-    if (K < F && (!recs_out || !rec_counts)) return fail(OPD_EINVAL, me + ": null output of the in-between frames");
     if (!frame_size_ok(h, w)) return fail(OPD_EINVAL, me + ": source frame size " + std::to_string(h) + " x " + std::to_string(w) + " out of range");
     if (!m) return fail(OPD_EINVAL, "null model handle");
     if (K > 0) {
         RCCHK(check_frame_list(m, keys.data(), OPD_MEM_HOST, K, H, W, true, me));   // (more key frames than max_batch among them)
-        if (m->nms_threshold < 0.f)
-            return fail(OPD_EINVAL, me + ": opd_detr_set_nms is off on this handle; a tracker takes the kept records of a frame, which only the suppression on the device leaves there");
-        if (m->nms_label != label)
-            return fail(OPD_EINVAL, me + ": opd_detr_set_nms keeps label " + std::to_string(m->nms_label) + ", the call asks for label " + std::to_string(label));
+        RCCHK(check_device_nms(m, label, me));
     }
     const LwtSeqCall call{frames, is_key, F, h, w, m->arch.queries};
     RCCHK(lwt_sequence_check(t, call, capacity, m->device, me));

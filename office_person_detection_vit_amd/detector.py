@@ -19,6 +19,7 @@ from __future__ import annotations
 
 from concurrent.futures import ThreadPoolExecutor
 import ctypes as C
+from dataclasses import dataclass
 import logging
 import os
 from typing import List, Optional, Sequence, Tuple
@@ -58,6 +59,126 @@ def resize_frame(frame: np.ndarray, out_h: int, out_w: int) -> np.ndarray:
     from PIL import Image
 
     return np.asarray(Image.fromarray(frame).resize((out_w, out_h), resample=Image.BILINEAR))
+
+
+# The native tiled entries that take a chunk of frames (``HipDetrDetector._tiled_chunks`` runs them all): how each spells the model size in its
+# argument list ("HW": H, W; "tile_HW": the per-tile sizes; "HW,tile_HW": H, W, and the per-tile sizes or NULL) and the stage block it takes behind
+# the parameters.  A further entry is a row here, its block (if new) in ``_tiled_chunks`` and a public method that checks its arguments.
+_TILED_ENTRIES = {
+    "opd_detr_detect_tiled": ("HW", None),
+    "opd_detr_detect_tiled_stages": ("HW", _capi.OpdTileStages),
+    "opd_detr_detect_tiled_ragged": ("tile_HW", _capi.OpdTileStages),   # (the one entry whose block may be null)
+    "opd_detr_detect_tiled_reid": ("HW", _capi.OpdTileReidStages),
+    "opd_detr_detect_tiled_ragged_reid": ("tile_HW", _capi.OpdTileReidStages),
+    "opd_detr_detect_tiled_hybrid": ("HW,tile_HW", _capi.OpdTileHybrid),
+}
+
+
+@dataclass
+class _TileGrid:
+    """The checked geometry of a tiled call (``HipDetrDetector._tiled_geometry``)."""
+    h: int   # frame size
+    w: int
+    T: int   # tiles per frame
+    S: int   # merged-record slots per frame: tiles x queries
+    win: np.ndarray   # [T, 4] int32 windows (y0, x0, h, w)
+    sizes: List[Tuple[int, int]]   # the model size of every tile (``tile_model_sizes``)
+    one_size: bool   # whether all windows have one size
+    tile_hw: np.ndarray   # [T, 2] int32 ``sizes``
+
+    def size_args(self, spelling: str) -> tuple:
+        """The model size as an entry spells it (``_TILED_ENTRIES``)."""
+        if spelling == "HW":
+            return self.sizes[0]
+        ptr = self.tile_hw.ctypes.data_as(C.c_void_p)
+        if spelling == "tile_HW":
+            return (ptr,)
+        return (*self.sizes[0], None) if self.one_size else (0, 0, ptr)
+
+
+def _check_tracker_list(items, n_frames: int, name: str) -> Optional[list]:
+    """``items`` (``trackers=`` or ``lwts=``) as a list with one distinct tracker per frame; ``None`` stays ``None``."""
+    if items is None:
+        return None
+    items = list(items)
+    if len(items) != n_frames:
+        raise ValueError(f"{len(items)} trackers for {n_frames} frames: frame f enters {name}[f]")
+    if len({id(t) for t in items}) != len(items):
+        raise ValueError("a tracker is named twice: a tracker takes one frame per call")
+    return items
+
+
+def _check_tiled_features(features: Optional[str]) -> None:
+    if features not in (None, "color"):
+        if features == "encoder":
+            raise ValueError("features='encoder' does not exist for tiled detection: a box merged from two tiles' maps has no encoder row")
+        raise ValueError(f"features must be None or 'color', got {features!r}")
+
+
+def _track_feature_kind(features: Optional[str], reid) -> int:
+    """The checks of ``features=`` / ``reid=`` of the detect-and-track calls, and the ``OPD_TRACK_FEAT_*`` value of ``features``."""
+    if features not in (None, "encoder", "color", "reid"):
+        raise ValueError(f"features must be None, 'encoder', 'color' or 'reid', got {features!r}")
+    if features == "reid" and reid is None:
+        raise ValueError("features='reid' needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
+    if features == "reid" and not reid.is_loaded:
+        raise RuntimeError("Re-ID model is not loaded: call load_model() first")
+    return {None: _capi.OPD_TRACK_FEAT_NONE, "encoder": _capi.OPD_TRACK_FEAT_ENCODER, "color": _capi.OPD_TRACK_FEAT_COLOR, "reid": _capi.OPD_TRACK_FEAT_REID}[features]
+
+
+def _floor_fields(block, floor_map, rows: int) -> np.ndarray:
+    """``floor`` / ``floor_out`` of a stage block: the mapper's handle and ``rows`` zeroed floor records for the call to fill by position."""
+    floor = np.zeros(rows, floor_map.REC_DTYPE)
+    block.floor, block.floor_out = floor_map._require().value, floor.ctypes.data
+    return floor
+
+
+def _tracker_fields(block, trackers: list, S: int):
+    """``trackers`` / ``track_ids`` (/ ``n_featured`` where the block has it) of a stage block for the trackers of one chunk, handles made already:
+    ``(ids [n * S], handle array, n_featured)``, which the caller holds until the call has returned."""
+    n = len(trackers)
+    handles = (C.c_void_p * n)(*[t._h.value for t in trackers])
+    ids, n_featured = np.full(n * S, -1, np.int32), np.zeros(n, np.int32)
+    block.trackers, block.track_ids = C.addressof(handles), ids.ctypes.data
+    if hasattr(block, "n_featured"):
+        block.n_featured = n_featured.ctypes.data
+    return ids, handles, n_featured
+
+
+def _hybrid_runs(keys: List[bool], max_frames: int, max_keys: int):
+    """The runs a hybrid sequence goes down in: from each start the longest run within ``max_frames`` frames and ``max_keys`` key frames."""
+    start = 0
+    while start < len(keys):
+        end, n_key = start, 0
+        while end < len(keys) and end - start < max_frames and (not keys[end] or n_key < max_keys):
+            n_key += keys[end]
+            end += 1
+        yield start, end
+        start = end
+
+
+def _hybrid_run_buffers(frames: list, keys: List[bool], Rec, stride: int, cap: int):
+    """Inputs and outputs of one hybrid-sequence call: the frame pointers and key flags, ``stride`` records of type ``Rec``, a count and ``stride``
+    ids per key frame, ``cap`` tracker records and a count per in-between frame, and ``frames_done``."""
+    F, K = len(frames), sum(keys)
+    recs, counts, ids = (Rec * (max(K, 1) * stride))(), (C.c_int32 * max(K, 1))(), np.full(max(K, 1) * stride, -1, np.int32)
+    lrecs, lcounts, done = (_capi.OpdLwtRec * (max(F - K, 1) * cap))(), (C.c_int32 * max(F - K, 1))(), C.c_int32(0)
+    ptrs = (C.c_void_p * F)(*[f.ctypes.data for f in frames])
+    flags = (C.c_uint8 * F)(*[int(k) for k in keys])
+    return ptrs, flags, recs, counts, ids, lrecs, lcounts, done
+
+
+def _hybrid_run_results(lwt, keys: List[bool], per_key: List[List[Detection]], ids: np.ndarray, stride: int, lrecs, lcounts, cap: int) -> list:
+    """One entry per frame of a run: the detections of a key frame with their ids adopted by ``lwt``, the ``(track_id, bbox)`` list of an in-between frame."""
+    out, k, j = [], 0, 0
+    for key in keys:
+        if key:
+            out.append(lwt._adopt(per_key[k], ids[k * stride:k * stride + len(per_key[k])].tolist()))
+            k += 1
+        else:
+            out.append([(int(lrecs[j * cap + i].track_id), tuple(float(v) for v in lrecs[j * cap + i].bbox)) for i in range(lcounts[j])])
+            j += 1
+    return out
 
 
 class HipDetrDetector:
@@ -490,49 +611,150 @@ class HipDetrDetector:
         what ``TiledDetector.detect_batch`` builds on the host, field for field."""
         self._require_model()
         frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
+        grid = self._tiled_geometry(frames, tiles, one_size=True)
+        if grid is None:
+            return []
+        return self._tiled_chunks("opd_detr_detect_tiled", frames, grid, (nms_threshold, merge_threshold, edge_tolerance))
+
+    def _tiled_geometry(self, frames: list, tiles: list, one_size: bool, reid=None) -> Optional[_TileGrid]:
+        """The checks of every tiled call, in one order: the tiles, ``reid`` loaded (where the call has one), the frames, and for tiles that may
+        differ in size (``one_size=False``) the canvas of their model sizes.  ``None`` without frames.  ``one_size=True`` refuses a grid of more than
+        one size and leaves a tile without height or width to the native refusal; ``one_size=False`` refuses such a tile here."""
         if not tiles or any(len(t) != 4 for t in tiles):
             raise ValueError("tiles must be a non-empty list of (y0, x0, h, w)")
         if len(tiles) > self.max_batch:
             raise ValueError(f"the {len(tiles)} tiles of one frame exceed max_batch = {self.max_batch}")
-        if len({(t[2], t[3]) for t in tiles}) != 1:
+        uniform = len({(t[2], t[3]) for t in tiles}) == 1
+        if one_size and not uniform:
             raise ValueError("tiles of more than one size: one forward has one model size")
+        if not one_size and any(t[2] < 1 or t[3] < 1 for t in tiles):
+            raise ValueError("tiles must have a height and a width of at least 1")
+        if reid is not None and not getattr(reid, "is_loaded", True):
+            raise RuntimeError("Re-ID model is not loaded: call load_model() first")
         if len(frames) == 0:
-            return []
+            return None
         f0 = frames[0]
         for f in frames:
             if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != f0.shape or not f.flags.c_contiguous:
                 raise ValueError("frames must be contiguous uint8 numpy arrays of shape (H, W, 3) in BGR order, all of one size")
-        h, w = int(f0.shape[0]), int(f0.shape[1])
-        th, tw = tiles[0][2], tiles[0][3]
-        H, W = model_input_size(th, tw, self.max_size[0], self.max_size[1]) if self.resize else (th, tw)
-        T, Q = len(tiles), self._info.num_queries
-        win = np.asarray(tiles, dtype=np.int32).reshape(T, 4)
-        params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
-                                     merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
-        per = max(1, self.max_batch // T)
+        sizes = self.tile_model_sizes(tiles)
+        H, W = max(s[0] for s in sizes), max(s[1] for s in sizes)
+        if not one_size and (max(H, W) > max(self.max_size) or H * W > self.max_size[0] * self.max_size[1]):
+            raise ValueError(f"ragged batch canvas {H}x{W} exceeds the configured maximum {self.max_size} (either orientation)")
+        T = len(tiles)
+        return _TileGrid(h=int(f0.shape[0]), w=int(f0.shape[1]), T=T, S=T * self._info.num_queries, win=np.asarray(tiles, dtype=np.int32).reshape(T, 4),
+                         sizes=sizes, one_size=uniform, tile_hw=np.asarray(sizes, dtype=np.int32).reshape(T, 2))
+
+    def _tile_params(self, nms_threshold: float, merge_threshold: float, edge_tolerance: float) -> _capi.OpdTileParams:
+        return _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
+                                   merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
+
+    def _tiled_chunks(self, entry: str, frames: list, grid: _TileGrid, thresholds: tuple, staged: bool = True, features: Optional[str] = None, reid=None,
+                      reid_slots: int = 0, floor_map=None, trackers=None) -> List[List[Detection]]:
+        """Every fused tiled call: ``entry`` (a row of ``_TILED_ENTRIES``) on chunks of ``max_batch // tiles`` checked frames, its stage block filled
+        from ``features`` / ``reid``, ``floor_map`` and ``trackers`` (``HipTracker``s, for the hybrid entry ``HipLightweightTracker``s; ``staged=False``:
+        a null block, which ``opd_detr_detect_tiled_ragged`` alone takes), and the merged records made into detections: feature rows by position
+        (colour) or by slot (Re-ID), floor rows and track ids by position, row ``b * S + k`` for record k of frame b.  Everything the native call
+        reads or writes is a local of the loop and so outlives the call."""
+        spelling, Block = _TILED_ENTRIES[entry]
+        hybrid = Block is _capi.OpdTileHybrid
+        call = getattr(self._lib, entry)
+        S = grid.S
+        params = self._tile_params(*thresholds)
+        head = (grid.h, grid.w, grid.win.ctypes.data_as(C.c_void_p), grid.T, *grid.size_args(spelling), float(self.confidence_threshold), C.byref(params))
+        per = max(1, self.max_batch // grid.T)
         out: List[List[Detection]] = []
         try:
             for i in range(0, len(frames), per):
                 chunk = frames[i:i + per]
                 n = len(chunk)
-                recs, counts = (_capi.OpdTileDet * (n * T * Q))(), (C.c_int32 * n)()
+                recs, counts = (_capi.OpdTileDet * (n * S))(), (C.c_int32 * n)()
                 ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in chunk])
-                rc = self._lib.opd_detr_detect_tiled(C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, H, W,
-                                                     float(self.confidence_threshold), C.byref(params), recs, counts)
-                _capi.check(rc, "opd_detr_detect_tiled")
-                for b in range(n):
-                    dets = []
-                    for k in range(int(counts[b])):
-                        r = recs[b * T * Q + k]
-                        bbox = (r.x, r.y, r.w, r.h)
-                        dets.append(Detection(bbox=bbox, confidence=float(r.score), class_id=int(r.label), class_name="person",
-                                              camera_coords=(bbox[0] + bbox[2] / 2, bbox[1] + bbox[3]), features=None, query_index=int(r.query_index)))
-                    out.append(dets)
-            self._last_orig = [(h, w)] * len(frames)
+                st = feats = slot_map = n_person = floor = ids = None
+                if Block is _capi.OpdTileStages and staged:
+                    st = Block(struct_size=C.sizeof(Block), feature_kind=_capi.OPD_TRACK_FEAT_COLOR if features == "color" else _capi.OPD_TRACK_FEAT_NONE)
+                    if features == "color" and trackers is None:
+                        feats = np.empty((n, S, 256), np.float32)
+                elif Block is _capi.OpdTileReidStages:   # a chunk shares its crop slots; with trackers the rows stay on the device
+                    slots = max(1, min(int(reid_slots) * n, int(reid.max_crops)))
+                    slot_map, n_person = np.full(slots, -1, np.int32), np.zeros(1, np.int32)
+                    st = Block(struct_size=C.sizeof(Block), slots=slots, reid=reid._handle.value, slot_map=slot_map.ctypes.data, n_person=n_person.ctypes.data)
+                    if trackers is None:
+                        feats = np.empty((slots, int(reid.feature_dim)), np.float32)
+                elif hybrid:
+                    st = Block(struct_size=C.sizeof(Block))
+                if feats is not None:
+                    st.features = feats.ctypes.data
+                if floor_map is not None:
+                    floor = _floor_fields(st, floor_map, n * S)
+                if trackers is not None:
+                    for t in trackers[i:i + n]:
+                        t._ensure(grid.h, grid.w) if hybrid else t._ensure()
+                    ids, handles, n_featured = _tracker_fields(st, trackers[i:i + n], S)
+                blocks = () if Block is None else (C.byref(st) if st is not None else None,)
+                rc = call(C.c_void_p(self.model), ptrs, n, *head, *blocks, recs, counts)
+                # a tracker out of slots: records, rows and ids were delivered (every record of that tracker -1: its mirror ages like the native side),
+                # so the mirrors follow first and the error is raised behind them, with the message as the call left it
+                if not (rc != 0 and ids is not None and not hybrid and "counted as one without detections" in _capi.last_error()):
+                    _capi.check(rc, entry)
+                message = _capi.last_error() if rc != 0 else ""
+                chunk_dets = [self._tile_records(recs, b * S, int(counts[b])) for b in range(n)]
+                for b, dets in enumerate(chunk_dets):
+                    if floor is not None:
+                        for k, det in enumerate(dets):
+                            floor_map._fill(det, floor[b * S + k])
+                    if hybrid:
+                        chunk_dets[b] = trackers[i + b]._adopt(dets, ids[b * S:b * S + len(dets)].tolist())
+                    elif ids is not None:
+                        trackers[i + b]._apply(dets, ids[b * S:b * S + len(dets)])
+                if slot_map is not None and feats is not None:
+                    self._rows_by_slot(chunk, chunk_dets, S, feats, slot_map[:min(int(n_person[0]), len(slot_map))], reid)
+                elif feats is not None:
+                    for b, dets in enumerate(chunk_dets):
+                        for det, row in zip(dets, feats[b, :len(dets)].copy()):
+                            det.features = row
+                out.extend(chunk_dets)
+                if rc != 0:
+                    raise RuntimeError(f"{entry} failed (code {rc}): {message}")
+            self._last_orig = [(grid.h, grid.w)] * len(frames)
             return out
         except Exception as e:
             logger.error(f"Detection failed: {e}")
             raise
+
+    @staticmethod
+    def _rows_by_slot(chunk: list, chunk_dets: List[List[Detection]], S: int, feats: np.ndarray, slot_map: np.ndarray, reid) -> None:
+        """Re-ID rows of a chunk: row k of ``feats`` belongs to merged record ``slot_map[k] = b * S + position``; the records beyond the slots get
+        theirs through ONE standalone ``reid.extract_features_batch``."""
+        row_of = {int(p): k for k, p in enumerate(slot_map)}
+        missing = []
+        for b, dets in enumerate(chunk_dets):
+            for k, det in enumerate(dets):
+                if b * S + k in row_of:
+                    det.features = feats[row_of[b * S + k]].copy()
+                else:
+                    missing.append((b, k))
+        if missing:
+            rows = reid.extract_features_batch(chunk, [[chunk_dets[b][k].bbox for (bb, k) in missing if bb == b] for b in range(len(chunk))])
+            for (b, k), row in zip(missing, rows):
+                chunk_dets[b][k].features = row
+
+    def _tiled_separate(self, plain, frames: list, tiles: list, thresholds: tuple, rows=None, floor_map=None, trackers=None, lwts=None) -> List[List[Detection]]:
+        """Where the fused conditions fail, the separate calls one after the other: ``plain`` (``self.detect_tiled`` or ``self.detect_tiled_ragged``,
+        looked up on the instance by the caller), then per frame ``lwts[f].update_with_detections``, the feature rows ``rows(frame, dets)``,
+        ``floor_map.apply`` and ``trackers[f].update``, each where given."""
+        out = plain(frames, tiles, *thresholds)
+        for b, dets in enumerate(out):
+            if lwts is not None:
+                lwts[b].update_with_detections(frames[b], dets)
+            if rows is not None:
+                for det, row in zip(dets, rows(frames[b], dets)):
+                    det.features = row
+            if floor_map is not None:
+                floor_map.apply(dets)
+            if trackers is not None:
+                trackers[b].update(dets)
+        return out
 
     def detect_tiled_stages(self, frames: Sequence[np.ndarray], tiles: Sequence[Tuple[int, int, int, int]], nms_threshold: float = 0.4,
                             merge_threshold: float = 0.5, edge_tolerance: float = 0.01, features: Optional[str] = None, floor_map=None,
@@ -545,115 +767,24 @@ class HipDetrDetector:
         ``detect_and_track``.  Where the fused conditions fail (a tracker or floor map on another GPU, ``max_dets`` below ``tiles x queries``, a
         ``feature_dim`` other than 256 with colour features, a frame side above 4096 with colour features) the separate calls run one after the
         other, with the same results.  With none of the three given this is ``detect_tiled`` itself."""
+        return self._tiled_staged("opd_detr_detect_tiled_stages", self.detect_tiled, frames, tiles, (nms_threshold, merge_threshold, edge_tolerance), features, floor_map, trackers)
+
+    def _tiled_staged(self, entry: str, plain, frames, tiles, thresholds: tuple, features: Optional[str], floor_map, trackers) -> List[List[Detection]]:
+        """``detect_tiled_stages`` and ``detect_tiled_ragged``: ``entry`` for a grid of one size or for any grid, ``plain`` the method without stages."""
         self._require_model()
         frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
-        if features not in (None, "color"):
-            if features == "encoder":
-                raise ValueError("features='encoder' does not exist for tiled detection: a box merged from two tiles' maps has no encoder row")
-            raise ValueError(f"features must be None or 'color', got {features!r}")
-        if trackers is not None:
-            trackers = list(trackers)
-            if len(trackers) != len(frames):
-                raise ValueError(f"{len(trackers)} trackers for {len(frames)} frames: frame f enters trackers[f]")
-            if len({id(t) for t in trackers}) != len(trackers):
-                raise ValueError("a tracker is named twice: a tracker takes one frame per call")
-        if not tiles or any(len(t) != 4 for t in tiles):
-            raise ValueError("tiles must be a non-empty list of (y0, x0, h, w)")
-        if len(tiles) > self.max_batch:
-            raise ValueError(f"the {len(tiles)} tiles of one frame exceed max_batch = {self.max_batch}")
-        if len({(t[2], t[3]) for t in tiles}) != 1:
-            raise ValueError("tiles of more than one size: one forward has one model size")
-        if len(frames) == 0:
+        _check_tiled_features(features)
+        trackers = _check_tracker_list(trackers, len(frames), "trackers")
+        one_size = entry == "opd_detr_detect_tiled_stages"
+        grid = self._tiled_geometry(frames, tiles, one_size)
+        if grid is None:
             return []
-        f0 = frames[0]
-        for f in frames:
-            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != f0.shape or not f.flags.c_contiguous:
-                raise ValueError("frames must be contiguous uint8 numpy arrays of shape (H, W, 3) in BGR order, all of one size")
-        h, w = int(f0.shape[0]), int(f0.shape[1])
-        th, tw = tiles[0][2], tiles[0][3]
-        H, W = model_input_size(th, tw, self.max_size[0], self.max_size[1]) if self.resize else (th, tw)
-        T, Q = len(tiles), self._info.num_queries
-        S = T * Q
-        if features is None and floor_map is None and trackers is None:
-            return self.detect_tiled(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
-        if not self._tiled_stages_fused(h, w, S, features, floor_map, trackers):
-            out = self.detect_tiled(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
-            for b, dets in enumerate(out):
-                if features == "color":
-                    for det, row in zip(dets, self.extract_color_features(frames[b], dets)):
-                        det.features = row
-                if floor_map is not None:
-                    floor_map.apply(dets)
-                if trackers is not None:
-                    trackers[b].update(dets)
-            return out
-        return self._tiled_staged_chunks("opd_detr_detect_tiled_stages", (H, W), frames, tiles, nms_threshold, merge_threshold, edge_tolerance, features, floor_map, trackers)
-
-    def _tiled_staged_chunks(self, entry: str, sizes: tuple, frames, tiles, nms_threshold: float, merge_threshold: float, edge_tolerance: float,
-                             features: Optional[str], floor_map, trackers, staged: bool = True) -> List[List[Detection]]:
-        """The calls of ``detect_tiled_stages`` and ``detect_tiled_ragged``, a chunk of ``max_batch // len(tiles)`` checked frames each: ``entry``
-        with ``sizes`` where the model size goes (``(H, W)``, or ``(tile_HW,)`` as a pointer), the stages block filled from ``features``,
-        ``floor_map`` and ``trackers`` (``staged=False``: a null block, ``opd_detr_detect_tiled_ragged`` alone takes one), and the records,
-        rows by position, made into detections."""
-        h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
-        T = len(tiles)
-        S = T * self._info.num_queries
-        call = getattr(self._lib, entry)
-        win = np.asarray(tiles, dtype=np.int32).reshape(T, 4)
-        params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
-                                     merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
-        per = max(1, self.max_batch // T)
-        out: List[List[Detection]] = []
-        try:
-            for i in range(0, len(frames), per):
-                chunk = frames[i:i + per]
-                n = len(chunk)
-                recs, counts = (_capi.OpdTileDet * (n * S))(), (C.c_int32 * n)()
-                ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in chunk])
-                args = (C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, *sizes, float(self.confidence_threshold), C.byref(params))
-                # the feature, floor and track stages on the merged records, rows by position: row b * S + k of record k of frame b
-                feats = floor = ids = st = None
-                if staged:
-                    st = _capi.OpdTileStages(struct_size=C.sizeof(_capi.OpdTileStages),
-                                             feature_kind=_capi.OPD_TRACK_FEAT_COLOR if features == "color" else _capi.OPD_TRACK_FEAT_NONE)
-                    if features == "color" and trackers is None:
-                        feats = np.empty((n, S, 256), np.float32)
-                        st.features = feats.ctypes.data
-                    if floor_map is not None:
-                        floor = np.zeros(n * S, floor_map.REC_DTYPE)
-                        st.floor, st.floor_out = floor_map._require().value, floor.ctypes.data
-                    if trackers is not None:
-                        for t in trackers[i:i + n]:
-                            t._ensure()
-                        handles = (C.c_void_p * n)(*[t._h.value for t in trackers[i:i + n]])
-                        ids, n_featured = np.full(n * S, -1, np.int32), np.zeros(n, np.int32)
-                        st.trackers, st.track_ids, st.n_featured = C.addressof(handles), ids.ctypes.data, n_featured.ctypes.data
-                rc = call(*args, C.byref(st) if st is not None else None, recs, counts)
-                if not (rc != 0 and trackers is not None and "counted as one without detections" in _capi.last_error()):
-                    _capi.check(rc, entry)   # (out of slots: records, rows and ids were delivered; the mirrors follow first)
-                message = _capi.last_error() if rc != 0 else ""
-                for b in range(n):
-                    dets = []
-                    cnt = int(counts[b])
-                    rows = feats[b, :cnt].copy() if feats is not None else None
-                    for k in range(cnt):
-                        r = recs[b * S + k]
-                        bbox = (r.x, r.y, r.w, r.h)
-                        dets.append(Detection(bbox=bbox, confidence=float(r.score), class_id=int(r.label), class_name="person",
-                                              camera_coords=(bbox[0] + bbox[2] / 2, bbox[1] + bbox[3]), features=None if rows is None else rows[k],
-                                              query_index=int(r.query_index)))
-                        if floor is not None:
-                            floor_map._fill(dets[-1], floor[b * S + k])
-                    if ids is not None:   # (a tracker out of slots gave every record -1: its mirror ages like the native side)
-                        trackers[i + b]._apply(dets, ids[b * S:b * S + cnt])
-                    out.append(dets)
-                if rc != 0:
-                    raise RuntimeError(f"{entry} failed (code {rc}): {message}")
-            self._last_orig = [(h, w)] * len(frames)
-            return out
-        except Exception as e:
-            logger.error(f"Detection failed: {e}")
-            raise
+        staged = not (features is None and floor_map is None and trackers is None)
+        if one_size and not staged:
+            return plain(frames, tiles, *thresholds)
+        if staged and not self._tiled_stages_fused(grid.h, grid.w, grid.S, features, floor_map, trackers):
+            return self._tiled_separate(plain, frames, tiles, thresholds, self.extract_color_features if features == "color" else None, floor_map, trackers)
+        return self._tiled_chunks(entry, frames, grid, thresholds, staged=staged, features=features, floor_map=floor_map, trackers=trackers)
 
     def tile_model_sizes(self, tiles: Sequence[Tuple[int, int, int, int]]) -> List[Tuple[int, int]]:
         """The model size (H, W) of each ``(y0, x0, h, w)`` tile: ``model_input_size`` of its window under ``max_size``, the window itself with
@@ -671,38 +802,8 @@ class HipDetrDetector:
         ``features`` (``None`` or ``"color"``), ``floor_map`` and ``trackers`` as in ``detect_tiled_stages``, with the same fallback to the
         separate calls where the fused conditions fail.  Re-ID rows inside the call are a method of their own for such a grid,
         ``detect_tiled_ragged_reid``."""
-        self._require_model()
-        frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
-        if features not in (None, "color"):
-            if features == "encoder":
-                raise ValueError("features='encoder' does not exist for tiled detection: a box merged from two tiles' maps has no encoder row")
-            raise ValueError(f"features must be None or 'color', got {features!r}")
-        if trackers is not None:
-            trackers = list(trackers)
-            if len(trackers) != len(frames):
-                raise ValueError(f"{len(trackers)} trackers for {len(frames)} frames: frame f enters trackers[f]")
-            if len({id(t) for t in trackers}) != len(trackers):
-                raise ValueError("a tracker is named twice: a tracker takes one frame per call")
-        h, w, sizes = self._ragged_geometry(frames, tiles)
-        if len(frames) == 0:
-            return []
-        T, Q = len(tiles), self._info.num_queries
-        S = T * Q
-        staged = not (features is None and floor_map is None and trackers is None)
-        if staged and not self._tiled_stages_fused(h, w, S, features, floor_map, trackers):
-            out = self.detect_tiled_ragged(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
-            for b, dets in enumerate(out):
-                if features == "color":
-                    for det, row in zip(dets, self.extract_color_features(frames[b], dets)):
-                        det.features = row
-                if floor_map is not None:
-                    floor_map.apply(dets)
-                if trackers is not None:
-                    trackers[b].update(dets)
-            return out
-        tile_hw = np.asarray(sizes, dtype=np.int32).reshape(T, 2)
-        return self._tiled_staged_chunks("opd_detr_detect_tiled_ragged", (tile_hw.ctypes.data_as(C.c_void_p),), frames, tiles, nms_threshold, merge_threshold, edge_tolerance,
-                                         features, floor_map, trackers, staged=staged)
+        return self._tiled_staged("opd_detr_detect_tiled_ragged", self.detect_tiled_ragged, frames, tiles, (nms_threshold, merge_threshold, edge_tolerance), features, floor_map,
+                                  trackers)
 
     def _tiled_stages_fused(self, h: int, w: int, S: int, features: Optional[str], floor_map, trackers) -> bool:
         """Whether the stages of a tiled call can run inside it (``detect_tiled`` has the conditions)."""
@@ -729,123 +830,22 @@ class HipDetrDetector:
         ``detect_and_track``; a record beyond the slots enters without a feature.  Where the fused conditions fail (``reid`` without a native
         handle or on another GPU; a tracker on another GPU, with ``max_dets`` below ``tiles x queries`` or with a ``feature_dim`` other than the
         Re-ID model's; a floor map on another GPU) the separate calls run one after the other, with the same results."""
+        return self._tiled_with_reid("opd_detr_detect_tiled_reid", self.detect_tiled, frames, tiles, reid, (nms_threshold, merge_threshold, edge_tolerance), reid_slots, floor_map,
+                                     trackers)
+
+    def _tiled_with_reid(self, entry: str, plain, frames, tiles, reid, thresholds: tuple, reid_slots: int, floor_map, trackers) -> List[List[Detection]]:
+        """``detect_tiled_reid`` and ``detect_tiled_ragged_reid``: ``entry`` for a grid of one size or for any grid, ``plain`` the method without Re-ID."""
         self._require_model()
         frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
         if reid is None:
-            raise ValueError("detect_tiled_reid needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
-        if trackers is not None:
-            trackers = list(trackers)
-            if len(trackers) != len(frames):
-                raise ValueError(f"{len(trackers)} trackers for {len(frames)} frames: frame f enters trackers[f]")
-            if len({id(t) for t in trackers}) != len(trackers):
-                raise ValueError("a tracker is named twice: a tracker takes one frame per call")
-        if not tiles or any(len(t) != 4 for t in tiles):
-            raise ValueError("tiles must be a non-empty list of (y0, x0, h, w)")
-        if len(tiles) > self.max_batch:
-            raise ValueError(f"the {len(tiles)} tiles of one frame exceed max_batch = {self.max_batch}")
-        if len({(t[2], t[3]) for t in tiles}) != 1:
-            raise ValueError("tiles of more than one size: one forward has one model size")
-        if not getattr(reid, "is_loaded", True):
-            raise RuntimeError("Re-ID model is not loaded: call load_model() first")
-        if len(frames) == 0:
+            raise ValueError(f"{entry[len('opd_detr_'):]} needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
+        trackers = _check_tracker_list(trackers, len(frames), "trackers")
+        grid = self._tiled_geometry(frames, tiles, entry == "opd_detr_detect_tiled_reid", reid)
+        if grid is None:
             return []
-        f0 = frames[0]
-        for f in frames:
-            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != f0.shape or not f.flags.c_contiguous:
-                raise ValueError("frames must be contiguous uint8 numpy arrays of shape (H, W, 3) in BGR order, all of one size")
-        h, w = int(f0.shape[0]), int(f0.shape[1])
-        th, tw = tiles[0][2], tiles[0][3]
-        H, W = model_input_size(th, tw, self.max_size[0], self.max_size[1]) if self.resize else (th, tw)
-        T, Q = len(tiles), self._info.num_queries
-        S = T * Q
-        if not self._tiled_reid_fused(S, reid, floor_map, trackers):
-            out = self.detect_tiled(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
-            for b, dets in enumerate(out):
-                for det, row in zip(dets, reid.extract_features(frames[b], [d.bbox for d in dets])):
-                    det.features = row
-                if floor_map is not None:
-                    floor_map.apply(dets)
-                if trackers is not None:
-                    trackers[b].update(dets)
-            return out
-        return self._tiled_reid_chunks("opd_detr_detect_tiled_reid", (H, W), frames, tiles, reid, nms_threshold, merge_threshold, edge_tolerance, reid_slots, floor_map, trackers)
-
-    def _tiled_reid_chunks(self, entry: str, sizes: tuple, frames, tiles, reid, nms_threshold: float, merge_threshold: float, edge_tolerance: float,
-                           reid_slots: int, floor_map, trackers) -> List[List[Detection]]:
-        """The calls of ``detect_tiled_reid`` and ``detect_tiled_ragged_reid``, a chunk of ``max_batch // len(tiles)`` checked frames each: ``entry``
-        with ``sizes`` where the model size goes (``(H, W)``, or ``(tile_HW,)`` as a pointer), the Re-ID stages block, and the records, rows by
-        slot, made into detections."""
-        h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
-        T = len(tiles)
-        S = T * self._info.num_queries
-        call = getattr(self._lib, entry)
-        E = int(reid.feature_dim)
-        win = np.asarray(tiles, dtype=np.int32).reshape(T, 4)
-        params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
-                                     merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
-        per = max(1, self.max_batch // T)
-        out: List[List[Detection]] = []
-        try:
-            for i in range(0, len(frames), per):
-                chunk = frames[i:i + per]
-                n = len(chunk)
-                slots = max(1, min(int(reid_slots) * n, int(reid.max_crops)))
-                recs, counts = (_capi.OpdTileDet * (n * S))(), (C.c_int32 * n)()
-                ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in chunk])
-                args = (C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, *sizes, float(self.confidence_threshold), C.byref(params))
-                # rows by slot: row k belongs to merged record slot_map[k] = b * S + position; floor and track-id rows by position
-                feats = floor = ids = None
-                slot_map, n_person = np.full(slots, -1, np.int32), np.zeros(1, np.int32)
-                st = _capi.OpdTileReidStages(struct_size=C.sizeof(_capi.OpdTileReidStages), slots=slots, reid=reid._handle.value,
-                                             slot_map=slot_map.ctypes.data, n_person=n_person.ctypes.data)
-                if trackers is None:
-                    feats = np.empty((slots, E), np.float32)
-                    st.features = feats.ctypes.data
-                if floor_map is not None:
-                    floor = np.zeros(n * S, floor_map.REC_DTYPE)
-                    st.floor, st.floor_out = floor_map._require().value, floor.ctypes.data
-                if trackers is not None:
-                    for t in trackers[i:i + n]:
-                        t._ensure()
-                    handles = (C.c_void_p * n)(*[t._h.value for t in trackers[i:i + n]])
-                    ids, n_featured = np.full(n * S, -1, np.int32), np.zeros(n, np.int32)
-                    st.trackers, st.track_ids, st.n_featured = C.addressof(handles), ids.ctypes.data, n_featured.ctypes.data
-                rc = call(*args, C.byref(st), recs, counts)
-                if not (rc != 0 and trackers is not None and "counted as one without detections" in _capi.last_error()):
-                    _capi.check(rc, entry)   # (out of slots: records and ids were delivered; the mirrors follow first)
-                message = _capi.last_error() if rc != 0 else ""
-                row_of = {int(p): k for k, p in enumerate(slot_map[:min(int(n_person[0]), slots)])}
-                chunk_dets, missing = [], []
-                for b in range(n):
-                    dets = []
-                    cnt = int(counts[b])
-                    for k in range(cnt):
-                        r = recs[b * S + k]
-                        bbox = (r.x, r.y, r.w, r.h)
-                        dets.append(Detection(bbox=bbox, confidence=float(r.score), class_id=int(r.label), class_name="person",
-                                              camera_coords=(bbox[0] + bbox[2] / 2, bbox[1] + bbox[3]), features=None, query_index=int(r.query_index)))
-                        if feats is not None:
-                            if b * S + k in row_of:
-                                dets[-1].features = feats[row_of[b * S + k]].copy()
-                            else:
-                                missing.append((b, k))
-                        if floor is not None:
-                            floor_map._fill(dets[-1], floor[b * S + k])
-                    if ids is not None:   # (a tracker out of slots gave every record -1: its mirror ages like the native side)
-                        trackers[i + b]._apply(dets, ids[b * S:b * S + cnt])
-                    chunk_dets.append(dets)
-                if missing:   # more merged records than slots: the remainder through ONE standalone call
-                    rows = reid.extract_features_batch(chunk, [[chunk_dets[b][k].bbox for (bb, k) in missing if bb == b] for b in range(n)])
-                    for (b, k), row in zip(missing, rows):
-                        chunk_dets[b][k].features = row
-                out.extend(chunk_dets)
-                if rc != 0:
-                    raise RuntimeError(f"{entry} failed (code {rc}): {message}")
-            self._last_orig = [(h, w)] * len(frames)
-            return out
-        except Exception as e:
-            logger.error(f"Detection failed: {e}")
-            raise
+        if not self._tiled_reid_fused(grid.S, reid, floor_map, trackers):
+            return self._tiled_separate(plain, frames, tiles, thresholds, lambda frame, dets: reid.extract_features(frame, [d.bbox for d in dets]), floor_map, trackers)
+        return self._tiled_chunks(entry, frames, grid, thresholds, reid=reid, reid_slots=reid_slots, floor_map=floor_map, trackers=trackers)
 
     def detect_tiled_ragged_reid(self, frames: Sequence[np.ndarray], tiles: Sequence[Tuple[int, int, int, int]], reid, nms_threshold: float = 0.4,
                                  merge_threshold: float = 0.5, edge_tolerance: float = 0.01, reid_slots: int = 32, floor_map=None,
@@ -854,71 +854,14 @@ class HipDetrDetector:
         ``detect_tiled_ragged``, and behind the seam merge the Re-ID, floor and track stages of ``detect_tiled_reid``, slots, rows and fallback
         to the separate calls included.  The lists equal ``detect_tiled_ragged`` + ``reid.extract_features`` (+ ``floor_map.apply``,
         + ``tracker.update``)."""
-        self._require_model()
-        frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
-        if reid is None:
-            raise ValueError("detect_tiled_ragged_reid needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
-        if trackers is not None:
-            trackers = list(trackers)
-            if len(trackers) != len(frames):
-                raise ValueError(f"{len(trackers)} trackers for {len(frames)} frames: frame f enters trackers[f]")
-            if len({id(t) for t in trackers}) != len(trackers):
-                raise ValueError("a tracker is named twice: a tracker takes one frame per call")
-        if not getattr(reid, "is_loaded", True):
-            raise RuntimeError("Re-ID model is not loaded: call load_model() first")
-        h, w, sizes = self._ragged_geometry(frames, tiles)
-        if len(frames) == 0:
-            return []
-        S = len(tiles) * self._info.num_queries
-        if not self._tiled_reid_fused(S, reid, floor_map, trackers):
-            out = self.detect_tiled_ragged(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
-            for b, dets in enumerate(out):
-                for det, row in zip(dets, reid.extract_features(frames[b], [d.bbox for d in dets])):
-                    det.features = row
-                if floor_map is not None:
-                    floor_map.apply(dets)
-                if trackers is not None:
-                    trackers[b].update(dets)
-            return out
-        tile_hw = np.asarray(sizes, dtype=np.int32).reshape(len(tiles), 2)
-        return self._tiled_reid_chunks("opd_detr_detect_tiled_ragged_reid", (tile_hw.ctypes.data_as(C.c_void_p),), frames, tiles, reid, nms_threshold, merge_threshold,
-                                       edge_tolerance, reid_slots, floor_map, trackers)
-
-    def _ragged_geometry(self, frames: list, tiles: list):
-        """The checks of a tiled call whose tiles may differ in size (``detect_tiled_ragged`` has them): ``(h, w, model size of every tile)``;
-        ``h = w = 0`` without frames."""
-        if not tiles or any(len(t) != 4 for t in tiles):
-            raise ValueError("tiles must be a non-empty list of (y0, x0, h, w)")
-        if len(tiles) > self.max_batch:
-            raise ValueError(f"the {len(tiles)} tiles of one frame exceed max_batch = {self.max_batch}")
-        if any(t[2] < 1 or t[3] < 1 for t in tiles):
-            raise ValueError("tiles must have a height and a width of at least 1")
-        sizes = self.tile_model_sizes(tiles)
-        if len(frames) == 0:
-            return 0, 0, sizes
-        f0 = frames[0]
-        for f in frames:
-            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != f0.shape or not f.flags.c_contiguous:
-                raise ValueError("frames must be contiguous uint8 numpy arrays of shape (H, W, 3) in BGR order, all of one size")
-        H, W = max(s[0] for s in sizes), max(s[1] for s in sizes)
-        if max(H, W) > max(self.max_size) or H * W > self.max_size[0] * self.max_size[1]:
-            raise ValueError(f"ragged batch canvas {H}x{W} exceeds the configured maximum {self.max_size} (either orientation)")
-        return int(f0.shape[0]), int(f0.shape[1]), sizes
+        return self._tiled_with_reid("opd_detr_detect_tiled_ragged_reid", self.detect_tiled_ragged, frames, tiles, reid, (nms_threshold, merge_threshold, edge_tolerance), reid_slots,
+                                     floor_map, trackers)
 
     # ---- the hybrid tracker inside a tiled call --------------------------------------------------------------------------------------
     def _detect_tiled_any(self, frames, tiles, nms_threshold: float, merge_threshold: float, edge_tolerance: float) -> List[List[Detection]]:
         """``detect_tiled``, or for tiles of more than one size ``detect_tiled_ragged``: the separate call the hybrid tiled methods equal."""
         call = self.detect_tiled if len({(t[2], t[3]) for t in tiles}) == 1 else self.detect_tiled_ragged
         return call(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
-
-    def _tiled_hybrid_call(self, tiles: list, sizes: list):
-        """What the hybrid tiled entries take for the windows and the model size: ``(win, H, W, tile_HW pointer or None, what must stay alive)``."""
-        T = len(tiles)
-        win = np.asarray(tiles, dtype=np.int32).reshape(T, 4)
-        if len({(t[2], t[3]) for t in tiles}) == 1:
-            return win, int(sizes[0][0]), int(sizes[0][1]), None, None
-        tile_hw = np.asarray(sizes, dtype=np.int32).reshape(T, 2)
-        return win, 0, 0, tile_hw.ctypes.data_as(C.c_void_p), tile_hw
 
     def _tile_records(self, recs, base: int, cnt: int) -> List[Detection]:
         dets = []
@@ -938,54 +881,16 @@ class HipDetrDetector:
         points as the separate calls.  Where a tracker is on another GPU or has ``max_tracks`` below ``tiles x queries`` (or the floor map is on
         another GPU) the separate calls run one after the other."""
         self._require_model()
-        frames, tiles, lwts = list(frames), [tuple(int(v) for v in t) for t in tiles], list(lwts)
-        if len(lwts) != len(frames):
-            raise ValueError(f"{len(lwts)} trackers for {len(frames)} frames: frame f enters lwts[f]")
-        if len({id(t) for t in lwts}) != len(lwts):
-            raise ValueError("a tracker is named twice: a tracker takes one frame per call")
-        h, w, sizes = self._ragged_geometry(frames, tiles)
-        if len(frames) == 0:
+        frames, tiles = list(frames), [tuple(int(v) for v in t) for t in tiles]
+        lwts = _check_tracker_list(lwts, len(frames), "lwts")
+        grid = self._tiled_geometry(frames, tiles, one_size=False)
+        if grid is None:
             return []
-        T = len(tiles)
-        S = T * self._info.num_queries
-        fused = all(t.device == self.device_ordinal and t.max_tracks >= S for t in lwts) and (floor_map is None or int(floor_map.device) == self.device_ordinal)
+        thresholds = (nms_threshold, merge_threshold, edge_tolerance)
+        fused = all(t.device == self.device_ordinal and t.max_tracks >= grid.S for t in lwts) and (floor_map is None or int(floor_map.device) == self.device_ordinal)
         if not fused:
-            out = self._detect_tiled_any(frames, tiles, nms_threshold, merge_threshold, edge_tolerance)
-            for b, dets in enumerate(out):
-                lwts[b].update_with_detections(frames[b], dets)
-                if floor_map is not None:
-                    floor_map.apply(dets)
-            return out
-        win, H, W, hw_ptr, _keep = self._tiled_hybrid_call(tiles, sizes)
-        params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
-                                     merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
-        per = max(1, self.max_batch // T)
-        out: List[List[Detection]] = []
-        for i in range(0, len(frames), per):
-            chunk, trackers = frames[i:i + per], lwts[i:i + per]
-            n = len(chunk)
-            for t in trackers:
-                t._ensure(h, w)
-            recs, counts = (_capi.OpdTileDet * (n * S))(), (C.c_int32 * n)()
-            ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in chunk])
-            handles = (C.c_void_p * n)(*[t._h.value for t in trackers])
-            ids = np.full(n * S, -1, np.int32)
-            hy = _capi.OpdTileHybrid(struct_size=C.sizeof(_capi.OpdTileHybrid), trackers=C.addressof(handles), track_ids=ids.ctypes.data)
-            floor = None
-            if floor_map is not None:
-                floor = np.zeros(n * S, floor_map.REC_DTYPE)
-                hy.floor, hy.floor_out = floor_map._require().value, floor.ctypes.data
-            rc = self._lib.opd_detr_detect_tiled_hybrid(C.c_void_p(self.model), ptrs, n, h, w, win.ctypes.data_as(C.c_void_p), T, H, W, hw_ptr,
-                                                        float(self.confidence_threshold), C.byref(params), C.byref(hy), recs, counts)
-            _capi.check(rc, "opd_detr_detect_tiled_hybrid")
-            for b in range(n):
-                dets = self._tile_records(recs, b * S, int(counts[b]))
-                if floor is not None:
-                    for k, det in enumerate(dets):
-                        floor_map._fill(det, floor[b * S + k])
-                out.append(trackers[b]._adopt(dets, ids[b * S:b * S + len(dets)].tolist()))
-        self._last_orig = [(h, w)] * len(frames)
-        return out
+            return self._tiled_separate(self._detect_tiled_any, frames, tiles, thresholds, floor_map=floor_map, lwts=lwts)
+        return self._tiled_chunks("opd_detr_detect_tiled_hybrid", frames, grid, thresholds, floor_map=floor_map, trackers=lwts)
 
     def track_tiled_hybrid_batch(self, frames: Sequence[np.ndarray], tiles: Sequence[Tuple[int, int, int, int]], lwt, key_frames: Sequence,
                                  nms_threshold: float = 0.4, merge_threshold: float = 0.5, edge_tolerance: float = 0.01) -> list:
@@ -998,55 +903,31 @@ class HipDetrDetector:
         frames, tiles, keys = list(frames), [tuple(int(v) for v in t) for t in tiles], [bool(k) for k in key_frames]
         if len(keys) != len(frames):
             raise ValueError(f"{len(frames)} frames, {len(keys)} key flags")
-        h, w, sizes = self._ragged_geometry(frames, tiles)
-        per = max(1, self.max_batch // len(tiles))
+        grid = self._tiled_geometry(frames, tiles, one_size=False)
+        if grid is None:
+            return []
         out: list = []
-        start = 0
-        while start < len(frames):
-            end, n_key = start, 0   # the longest run from `start` within the limits of one call
-            while end < len(frames) and end - start < lwt.SEQUENCE_MAX and (not keys[end] or n_key < per):
-                n_key += keys[end]
-                end += 1
-            out.extend(self._track_tiled_hybrid_run(frames[start:end], tiles, sizes, lwt, keys[start:end], nms_threshold, merge_threshold, edge_tolerance))
-            start = end
+        for start, end in _hybrid_runs(keys, lwt.SEQUENCE_MAX, max(1, self.max_batch // len(tiles))):
+            out.extend(self._track_tiled_hybrid_run(frames[start:end], tiles, grid, lwt, keys[start:end], (nms_threshold, merge_threshold, edge_tolerance)))
         return out
 
-    def _track_tiled_hybrid_run(self, frames: list, tiles: list, sizes: list, lwt, keys: List[bool], nms_threshold: float, merge_threshold: float,
-                                edge_tolerance: float) -> list:
-        T = len(tiles)
-        S = T * self._info.num_queries
-        h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
+    def _track_tiled_hybrid_run(self, frames: list, tiles: list, grid: _TileGrid, lwt, keys: List[bool], thresholds: tuple) -> list:
+        S = grid.S
         fused = lwt.device == self.device_ordinal and lwt.max_tracks >= S
         if fused and not any(keys) and not lwt._h:   # (no handle yet and no detection frame to make one: nothing to interpolate)
             fused = False
         if not fused:
-            return [lwt.update_with_detections(f, self._detect_tiled_any([f], tiles, nms_threshold, merge_threshold, edge_tolerance)[0]) if k else lwt.interpolate(f)
-                    for f, k in zip(frames, keys)]
-        lwt._ensure(h, w)
-        win, H, W, hw_ptr, _keep = self._tiled_hybrid_call(tiles, sizes)
-        params = _capi.OpdTileParams(struct_size=C.sizeof(_capi.OpdTileParams), person_label=PERSON_LABEL, tile_nms_threshold=float(self.nms_threshold),
-                                     merge_nms_threshold=float(nms_threshold), merge_threshold=float(merge_threshold), edge_tolerance=float(edge_tolerance))
-        F, K = len(frames), sum(keys)
-        cap = lwt.max_tracks
-        recs, counts, ids = (_capi.OpdTileDet * (max(K, 1) * S))(), (C.c_int32 * max(K, 1))(), np.full(max(K, 1) * S, -1, np.int32)
-        lrecs, lcounts, done = (_capi.OpdLwtRec * (max(F - K, 1) * cap))(), (C.c_int32 * max(F - K, 1))(), C.c_int32(0)
-        ptrs = (C.c_void_p * F)(*[f.ctypes.data for f in frames])
-        flags = (C.c_uint8 * F)(*[int(k) for k in keys])
-        rc = self._lib.opd_detr_detect_tiled_sequence_hybrid(C.c_void_p(self.model), lwt._h, ptrs, flags, F, h, w, win.ctypes.data_as(C.c_void_p), T, H, W, hw_ptr,
-                                                             float(self.confidence_threshold), C.byref(params), recs, counts, ids.ctypes.data, lrecs, cap, lcounts,
-                                                             C.byref(done))
+            return [lwt.update_with_detections(f, self._detect_tiled_any([f], tiles, *thresholds)[0]) if k else lwt.interpolate(f) for f, k in zip(frames, keys)]
+        lwt._ensure(grid.h, grid.w)
+        params = self._tile_params(*thresholds)
+        K, cap = sum(keys), lwt.max_tracks
+        ptrs, flags, recs, counts, ids, lrecs, lcounts, done = _hybrid_run_buffers(frames, keys, _capi.OpdTileDet, S, cap)
+        rc = self._lib.opd_detr_detect_tiled_sequence_hybrid(C.c_void_p(self.model), lwt._h, ptrs, flags, len(frames), grid.h, grid.w, grid.win.ctypes.data_as(C.c_void_p), grid.T,
+                                                             *grid.size_args("HW,tile_HW"), float(self.confidence_threshold), C.byref(params), recs, counts, ids.ctypes.data,
+                                                             lrecs, cap, lcounts, C.byref(done))
         _capi.check(rc, "opd_detr_detect_tiled_sequence_hybrid")
-        self._last_orig = [(h, w)] * K
-        out, k, j = [], 0, 0
-        for f in range(F):
-            if keys[f]:
-                dets = self._tile_records(recs, k * S, int(counts[k]))
-                out.append(lwt._adopt(dets, ids[k * S:k * S + len(dets)].tolist()))
-                k += 1
-            else:
-                out.append([(int(lrecs[j * cap + i].track_id), tuple(float(v) for v in lrecs[j * cap + i].bbox)) for i in range(lcounts[j])])
-                j += 1
-        return out
+        self._last_orig = [(grid.h, grid.w)] * K
+        return _hybrid_run_results(lwt, keys, [self._tile_records(recs, k * S, int(counts[k])) for k in range(K)], ids, S, lrecs, lcounts, cap)
 
     def _tiled_reid_fused(self, S: int, reid, floor_map, trackers) -> bool:
         """Whether the Re-ID stage of a tiled call can run inside it (``detect_tiled_reid`` has the conditions)."""
@@ -1182,12 +1063,7 @@ class HipDetrDetector:
         ``"color"``, ``"reid"`` (with ``reid=``) or ``None`` for motion only.  Needs ``device_nms=True``, a frame that goes down as a frame
         list and all handles on one GPU; otherwise the two calls run one after the other, with the same ids and track states."""
         self._require_model()
-        if features not in (None, "encoder", "color", "reid"):
-            raise ValueError(f"features must be None, 'encoder', 'color' or 'reid', got {features!r}")
-        if features == "reid" and reid is None:
-            raise ValueError("features='reid' needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
-        if features == "reid" and not reid.is_loaded:
-            raise RuntimeError("Re-ID model is not loaded: call load_model() first")
+        kind = _track_feature_kind(features, reid)
         self._sync_nms()
         target = self._fused_track_target([frame], tracker, features, reid)
         Q = self._info.num_queries
@@ -1197,7 +1073,6 @@ class HipDetrDetector:
                 return tracker.update(self.detect(frame))
             return tracker.update(self.detect_with_features(frame, features=features, reid=reid, reid_slots=reid_slots)[0])
         tracker._ensure()
-        kind = {None: _capi.OPD_TRACK_FEAT_NONE, "encoder": _capi.OPD_TRACK_FEAT_ENCODER, "color": _capi.OPD_TRACK_FEAT_COLOR, "reid": _capi.OPD_TRACK_FEAT_REID}[features]
         slots = max(1, min(int(reid_slots), int(reid.max_crops), int(tracker.max_dets))) if features == "reid" else 0
         recs, counts = (_capi.OpdDet * Q)(), (C.c_int32 * 1)()
         ids, n_featured = np.full(Q, -1, np.int32), np.zeros(1, np.int32)
@@ -1250,14 +1125,8 @@ class HipDetrDetector:
         if len(keys) != len(frames):
             raise ValueError(f"{len(frames)} frames, {len(keys)} key flags")
         out: list = []
-        start = 0
-        while start < len(frames):
-            end, n_key = start, 0   # the longest run from `start` within the limits of one call
-            while end < len(frames) and end - start < lwt.SEQUENCE_MAX and (not keys[end] or n_key < self.max_batch):
-                n_key += keys[end]
-                end += 1
+        for start, end in _hybrid_runs(keys, lwt.SEQUENCE_MAX, self.max_batch):
             out.extend(self._track_hybrid_run(frames[start:end], lwt, keys[start:end]))
-            start = end
         return out
 
     def _track_hybrid_run(self, frames: List[np.ndarray], lwt, keys: List[bool]) -> list:
@@ -1271,26 +1140,13 @@ class HipDetrDetector:
         if not fused:
             return [lwt.update_with_detections(f, self.detect(f)) if k else lwt.interpolate(f) for f, k in zip(frames, keys)]
         lwt._ensure(h, w)
-        F, K = len(frames), sum(keys)
-        cap = lwt.max_tracks
-        recs, counts, ids = (_capi.OpdDet * (max(K, 1) * Q))(), (C.c_int32 * max(K, 1))(), np.full(max(K, 1) * Q, -1, np.int32)
-        lrecs, lcounts, done = (_capi.OpdLwtRec * (max(F - K, 1) * cap))(), (C.c_int32 * max(F - K, 1))(), C.c_int32(0)
-        ptrs = (C.c_void_p * F)(*[f.ctypes.data for f in frames])
-        flags = (C.c_uint8 * F)(*[int(k) for k in keys])
-        rc = self._lib.opd_detr_detect_sequence_hybrid(C.c_void_p(self.model), lwt._h, ptrs, flags, F, h, w, target[0], target[1], float(self.confidence_threshold),
+        K, cap = sum(keys), lwt.max_tracks
+        ptrs, flags, recs, counts, ids, lrecs, lcounts, done = _hybrid_run_buffers(frames, keys, _capi.OpdDet, Q, cap)
+        rc = self._lib.opd_detr_detect_sequence_hybrid(C.c_void_p(self.model), lwt._h, ptrs, flags, len(frames), h, w, target[0], target[1], float(self.confidence_threshold),
                                                        PERSON_LABEL, recs, counts, ids.ctypes.data, lrecs, cap, lcounts, C.byref(done))
         _capi.check(rc, "opd_detr_detect_sequence_hybrid")
         self._last_orig = [(h, w)] * K
-        per_key = self._postprocess_batch(recs, counts, Q) if K else []
-        out, k, j = [], 0, 0
-        for f in range(F):
-            if keys[f]:
-                out.append(lwt._adopt(per_key[k], ids[k * Q:k * Q + len(per_key[k])].tolist()))
-                k += 1
-            else:
-                out.append([(int(lrecs[j * cap + i].track_id), tuple(float(v) for v in lrecs[j * cap + i].bbox)) for i in range(lcounts[j])])
-                j += 1
-        return out
+        return _hybrid_run_results(lwt, keys, self._postprocess_batch(recs, counts, Q) if K else [], ids, Q, lrecs, lcounts, cap)
 
     def _fused_track_target(self, frames: Sequence[np.ndarray], tracker, features: Optional[str], reid) -> Optional[Tuple[int, int]]:
         """The model input size when ``frames`` can enter ``tracker`` inside the detect call (``detect_and_track`` has the conditions), else None."""
@@ -1312,15 +1168,9 @@ class HipDetrDetector:
         ``min(max_crops, max_dets, reid_slots * len(chunk))`` crop slots, handed out in (frame, score) order.  Where the conditions of the fused
         single-frame call fail, the loop runs instead."""
         self._require_model()
-        if features not in (None, "encoder", "color", "reid"):
-            raise ValueError(f"features must be None, 'encoder', 'color' or 'reid', got {features!r}")
-        if features == "reid" and reid is None:
-            raise ValueError("features='reid' needs reid= a loaded HipReIDExtractor or HipOSNetReIDExtractor")
-        if features == "reid" and not reid.is_loaded:
-            raise RuntimeError("Re-ID model is not loaded: call load_model() first")
+        kind = _track_feature_kind(features, reid)
         frames = list(frames)
         out: List[List[Detection]] = []
-        kind = {None: _capi.OPD_TRACK_FEAT_NONE, "encoder": _capi.OPD_TRACK_FEAT_ENCODER, "color": _capi.OPD_TRACK_FEAT_COLOR, "reid": _capi.OPD_TRACK_FEAT_REID}[features]
         for start in range(0, len(frames), self.max_batch):
             chunk = frames[start:start + self.max_batch]
             self._sync_nms()

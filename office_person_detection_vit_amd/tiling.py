@@ -152,6 +152,10 @@ class TiledDetector:
             raise ValueError(f"mixed_sizes=True needs a detector with detect_tiled_ragged (a HipDetrDetector); {type(self.detector).__name__} has none")
         return True
 
+    def _staged_call(self, grid):
+        """The wrapped detector's tiled method that runs the feature and track stages inside the call for ``grid``."""
+        return self.detector.detect_tiled_ragged if self._mixed(grid) else self.detector.detect_tiled_stages
+
     def detect_batch(self, frames: Sequence[np.ndarray], floor_map=None) -> List[List[Detection]]:
         """``floor_map``: a ``HipFloorMapper``; the merged detections come back with its four fields filled (``native=True``: inside the call)."""
         if self.native:
@@ -231,7 +235,7 @@ class TiledDetector:
             return dets, (np.stack([d.features for d in dets]) if dets else np.array([]))
         if self.native and features == "color":
             grid = self._native_grid([frame], staged=True)   # (refuses a detector without detect_tiled)
-            call = self.detector.detect_tiled_ragged if self._mixed(grid) else self.detector.detect_tiled_stages
+            call = self._staged_call(grid)
             dets = call([frame], grid, self.nms_threshold, self.merge_threshold, features="color")[0]
             return dets, (np.stack([d.features for d in dets]) if dets else np.array([]))
         dets = self.detect(frame)
@@ -248,7 +252,7 @@ class TiledDetector:
             return [d for d in dets if d.track_id is not None]
         if self.native and features != "reid":
             grid = self._native_grid([frame], staged=True)
-            call = self.detector.detect_tiled_ragged if self._mixed(grid) else self.detector.detect_tiled_stages
+            call = self._staged_call(grid)
             dets = call([frame], grid, self.nms_threshold, self.merge_threshold, features=features, trackers=[tracker])[0]
             return [d for d in dets if d.track_id is not None]
         dets = self.detect(frame)
