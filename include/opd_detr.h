@@ -606,6 +606,21 @@ OPD_API int opd_track_update(opd_track* t, const float* boxes_xywh, const float*
 OPD_API int opd_track_update_sequence(opd_track* t, const float* boxes_xywh, const float* foot_xy, const float* confidence, const float* features,
                                       const uint8_t* has_feature, int feat_mem_kind, const int32_t* counts, int F, int32_t* out_ids,
                                       int32_t* frames_done);
+/* opd_track_update_sequence for SEVERAL cameras in ONE call with ONE host wait: F frames in call order, frame f a frame of
+ * trackers[camera_of[f]] (C distinct handles on one device, 1 <= C <= 64; they may differ in feature_dim, max_tracks, max_dets and every threshold).
+ * The frames of one camera are taken in the order in which they appear; the cameras run side by side: step s of the call is the s-th frame of every
+ * camera that has one, in at most four launches whatever C is (track_*_multi_kernel: the one-tracker kernels' code, a camera per blockIdx.y), so the
+ * call takes as many steps as its longest camera has frames.  The arrays are packed frame after frame as above; a feature row is as wide as its
+ * frame's own tracker's feature_dim.  Ids and states are those of one opd_track_update_sequence call per camera, bit for bit.  frames_done [C].
+ * OPD_EINVAL before any device work, changing nothing: what opd_track_update_sequence refuses, a null list, C outside 1 .. 64, a camera_of entry
+ * outside 0 .. C - 1, a null handle, a tracker named twice, a tracker that gets no frame, trackers on different devices.  A camera c that runs out
+ * of slots at its frame f stops as under opd_track_update_sequence (that frame counts as one without detections, its later frames are not applied
+ * and keep id -1, frames_done[c] = f + 1); every OTHER camera runs to its end and is adopted; the call returns OPD_EINVAL with that sentence for
+ * the lowest-numbered stopped camera, naming it, and the list of all stopped cameras.  Afterwards opd_track_info reports on every tracker of the
+ * call last_launches = the launches that ran for the call, and last_waits = 1 on trackers[0] (whose stream carried the call), 0 on the others. */
+OPD_API int opd_track_update_streams(opd_track* const* trackers, int C, const int32_t* camera_of, int F, const float* boxes_xywh, const float* foot_xy,
+                                     const float* confidence, const float* features, const uint8_t* has_feature, int feat_mem_kind,
+                                     const int32_t* counts, int32_t* out_ids, int32_t* frames_done);
 /* The live tracks in creation order: out [capacity], *count = how many there are (OPD_EINVAL when capacity is smaller; out may be NULL
  * with capacity 0 to ask for the count).  Waits for the last update's second launch. */
 OPD_API int opd_track_get(opd_track* t, opd_track_rec* out, int capacity, int* count);
@@ -640,6 +655,17 @@ OPD_API int opd_detr_detect_frames_track(opd_detr* m, opd_reid* r, opd_track* co
 OPD_API int opd_detr_detect_sequence_track(opd_detr* m, opd_reid* r, opd_track* t, const uint8_t* const* frames, int B, int h, int w, int H, int W,
                                            float threshold, int label, int feature_kind, int slots, opd_det* out, int32_t* counts,
                                            int32_t* track_ids, int32_t* n_featured, int32_t* frames_done);
+/* opd_detr_detect_sequence_track for SEVERAL cameras: B frames in call order, frame b a frame of trackers[camera_of[b]]
+ * (C distinct handles, 1 <= C <= 64, every one with a frame).  One batched forward, suppression and feature stage over all B frames; then, on the
+ * detector's stream in front of the ONE host wait, the steps of opd_track_update_streams with an ingest launch in front of each.  Records, counts,
+ * track_ids [B][num_queries] and n_featured [B] are what one opd_detr_detect_sequence_track call per camera gives (the `frame` member of a record
+ * is its position in THIS call); for REID the `slots` crop slots are per call, in (frame, score) order.  The refusals are those of
+ * opd_detr_detect_frames_track per tracker, in the same order, then those of opd_track_update_streams for the list.  Out of slots in camera c: as
+ * opd_track_update_streams, frames_done [C] (records and counts of all B frames are still delivered).  Afterwards opd_track_info reports
+ * last_waits = 0 and last_launches = the launches that ran for the call, on every tracker. */
+OPD_API int opd_detr_detect_streams_track(opd_detr* m, opd_reid* r, opd_track* const* trackers, int C, const int32_t* camera_of,
+                                          const uint8_t* const* frames, int B, int h, int w, int H, int W, float threshold, int label, int feature_kind,
+                                          int slots, opd_det* out, int32_t* counts, int32_t* track_ids, int32_t* n_featured, int32_t* frames_done);
 /* opd_detr_detect_tiled with the colour-feature, floor and track stages on the MERGED records, all on the detector's stream in front of the call's
  * ONE host wait (DESIGN.md sections 7a, 7k): what detect_tiled + opd_color_features + opd_floor_transform + opd_track_update give in four calls.
  * With S = n_tiles x num_queries, the feature, floor and track-id row of merged record k of frame f is row f x S + k -- by POSITION, since two

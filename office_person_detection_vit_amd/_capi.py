@@ -243,11 +243,14 @@ API = {
     "opd_track_update": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
     # boxes, foot, confidence, features, has_feature, feat_mem_kind, counts, F, out_ids, frames_done
     "opd_track_update_sequence": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "opd_track_update_streams": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "opd_track_get": (C.c_int, [C.c_void_p, C.POINTER(OpdTrackRec), C.c_int, C.POINTER(C.c_int)]),
     "opd_detr_detect_frames_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int, C.c_int,
                                                 C.POINTER(OpdDet), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "opd_detr_detect_sequence_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int, C.c_int,
                                                   C.POINTER(OpdDet), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "opd_detr_detect_streams_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 +
+                                      [C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(OpdDet), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
     "opd_assign": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "opd_lwt_create": (C.c_int, [C.POINTER(OpdLwtConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "opd_lwt_destroy": (None, [C.c_void_p]),
@@ -404,6 +407,12 @@ TEST_API = {
     # app, iou, comb [T][N], T, N, hits [T], conf [N], min_hits, high_conf, n_free, then for the kernel and for the host: matches [min(T, N)][2], n_matches, new_dets [N],
     # n_new, unmatched [T], n_unmatched
     "opd_track_test_assoc": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 12),
+    # the schedule of a streams call: camera_of [F], F, C -> out [capacity] as [steps][C] frame indices (-1: none), *steps.  No device.
+    "opd_track_test_streams_schedule": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    # track_assoc_multi_kernel, C cameras in ONE launch, next to the host's associate() per camera: device, C, T [C], N [C], n_free [C], the cameras' app / iou / comb,
+    # hits and conf one behind the other, min_hits, high_conf; per side matches, new detections and unmatched tracks at the offsets of max(min(T, N), 1),
+    # max(N, 1) and max(T, 1) rows a camera, each with its counts [C]
+    "opd_track_test_assoc_multi": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_double] + [C.c_void_p] * 12),
     # the same inputs, iters -> mean milliseconds of the kernel and of the host's associate()
     "opd_track_test_bench_assoc": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int,
                                               C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -13,11 +13,11 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
-SOURCES = ["kernels_gemm.hip", "kernels_w8.hip", "kernels_btail.hip", "kernels_btail3.hip", "kernels_rowln.hip", "kernels_attn.hip", "kernels_misc.hip", "kernels_untyped.hip", "kernels_dec.hip", "kernels_reid.hip", "kernels_osnet.hip", "kernels_hist.hip", "kernels_flow.hip", "kernels_floor.hip", "kernels_track.hip", "kernels_lwt.hip", "kernels_crop.hip", "kernels_nms.hip", "kernels_tile.hip", "opd_loader.cpp", "opd_host.cpp", "opd_pack.cpp", "opd_model.cpp", "opd_weights.cpp", "opd_api.cpp", "opd_comm.cpp", "opd_dispatch.cpp", "opd_crop.cpp", "opd_reid.cpp", "opd_clip.cpp", "opd_osnet.cpp", "opd_color.cpp", "opd_flow.cpp", "opd_floor.cpp", "opd_assoc.cpp", "opd_track.cpp", "opd_lwt.cpp", "opd_test_api.cpp", "opd_test_bench_api.cpp", "opd_test_model_api.cpp", "opd_reid_test_api.cpp", "opd_osnet_test_api.cpp", "opd_flow_test_api.cpp", "opd_floor_test_api.cpp", "opd_track_test_api.cpp", "opd_lwt_test_api.cpp", "opd_lwt_ingest_test_api.cpp", "opd_lwt_ingest_merged_test_api.cpp", "opd_crop_test_api.cpp", "opd_nms_test_api.cpp", "opd_tile_test_api.cpp", "opd_tile_stages_test_api.cpp", "opd_tile_reid_test_api.cpp"]
-TEST_ONLY = {"opd_test_api.cpp", "opd_test_bench_api.cpp", "opd_test_model_api.cpp", "opd_reid_test_api.cpp", "opd_osnet_test_api.cpp", "opd_flow_test_api.cpp", "opd_floor_test_api.cpp", "opd_track_test_api.cpp", "opd_lwt_test_api.cpp", "opd_lwt_ingest_test_api.cpp", "opd_lwt_ingest_merged_test_api.cpp", "opd_crop_test_api.cpp", "opd_nms_test_api.cpp", "opd_tile_test_api.cpp", "opd_tile_stages_test_api.cpp", "opd_tile_reid_test_api.cpp"}
+SOURCES = ["kernels_gemm.hip", "kernels_w8.hip", "kernels_btail.hip", "kernels_btail3.hip", "kernels_rowln.hip", "kernels_attn.hip", "kernels_misc.hip", "kernels_untyped.hip", "kernels_dec.hip", "kernels_reid.hip", "kernels_osnet.hip", "kernels_hist.hip", "kernels_flow.hip", "kernels_floor.hip", "kernels_track.hip", "kernels_lwt.hip", "kernels_crop.hip", "kernels_nms.hip", "kernels_tile.hip", "opd_loader.cpp", "opd_host.cpp", "opd_pack.cpp", "opd_model.cpp", "opd_weights.cpp", "opd_api.cpp", "opd_comm.cpp", "opd_dispatch.cpp", "opd_crop.cpp", "opd_reid.cpp", "opd_clip.cpp", "opd_osnet.cpp", "opd_color.cpp", "opd_flow.cpp", "opd_floor.cpp", "opd_assoc.cpp", "opd_track.cpp", "opd_lwt.cpp", "opd_test_api.cpp", "opd_test_bench_api.cpp", "opd_test_model_api.cpp", "opd_reid_test_api.cpp", "opd_osnet_test_api.cpp", "opd_flow_test_api.cpp", "opd_floor_test_api.cpp", "opd_track_test_api.cpp", "opd_track_streams_test_api.cpp", "opd_lwt_test_api.cpp", "opd_lwt_ingest_test_api.cpp", "opd_lwt_ingest_merged_test_api.cpp", "opd_crop_test_api.cpp", "opd_nms_test_api.cpp", "opd_tile_test_api.cpp", "opd_tile_stages_test_api.cpp", "opd_tile_reid_test_api.cpp"]
+TEST_ONLY = {"opd_test_api.cpp", "opd_test_bench_api.cpp", "opd_test_model_api.cpp", "opd_reid_test_api.cpp", "opd_osnet_test_api.cpp", "opd_flow_test_api.cpp", "opd_floor_test_api.cpp", "opd_track_test_api.cpp", "opd_track_streams_test_api.cpp", "opd_lwt_test_api.cpp", "opd_lwt_ingest_test_api.cpp", "opd_lwt_ingest_merged_test_api.cpp", "opd_crop_test_api.cpp", "opd_nms_test_api.cpp", "opd_tile_test_api.cpp", "opd_tile_stages_test_api.cpp", "opd_tile_reid_test_api.cpp"}
 # kernel files with 16-bit operands: ONE source, compiled for fp16 and (-DOPD_ELEM_BF16) for bf16 (opd_elem.h)
 ELEM_SOURCES = ["kernels_gemm.hip", "kernels_w8.hip", "kernels_btail.hip", "kernels_btail3.hip", "kernels_rowln.hip", "kernels_attn.hip", "kernels_misc.hip"]
-HEADERS = ["opd_kernels.h", "opd_elem.h", "opd_kprims.h", "opd_loader.h", "opd_host.h", "opd_pack.h", "opd_device.h", "opd_model.h", "opd_crop.h", "opd_nms.h", "opd_records.h", "opd_tile.h", "opd_reid.h", "opd_clip.h", "opd_osnet.h", "opd_flow.h", "opd_floor.h", "opd_assoc.h", "opd_track.h", "opd_lwt.h", "opd_test_util.h", os.path.join("..", "..", "include", "opd_detr.h")]
+HEADERS = ["opd_kernels.h", "opd_elem.h", "opd_kprims.h", "opd_loader.h", "opd_host.h", "opd_pack.h", "opd_device.h", "opd_model.h", "opd_crop.h", "opd_nms.h", "opd_records.h", "opd_tile.h", "opd_reid.h", "opd_clip.h", "opd_osnet.h", "opd_flow.h", "opd_floor.h", "opd_assoc.h", "opd_track.h", "opd_lwt.h", "opd_test_util.h", "opd_track_test_rig.h", os.path.join("..", "..", "include", "opd_detr.h")]
 # code-generation flags of every translation unit, and per file: the attention kernel consumes its S = K.Q^T accumulators with VALU right
 # away, so its MFMAs should write VGPRs (the default AGPR form costs 56 v_accvgpr moves per key tile in a VALU-bound loop).
 # tools/scan_dma_waits.py imports these: the ISA it checks must be the ISA that ships.

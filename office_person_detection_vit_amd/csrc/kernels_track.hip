@@ -24,6 +24,8 @@
 //       association stages with the host's solver, ids and counters, new slots, deletions) on a track table that stays on the device for the
 //       call.  The predict and commit launches then take their row count, slots and list from that table (`hdr` set), under a grid that is an
 //       upper bound.  Plain loads and stores here too.
+//   track_*_multi_kernel       streams calls only: the four above for C trackers in one launch each.  blockIdx.y is the camera; its parameter block comes
+//       out of a descriptor array in device memory; the arithmetic is the body of the one-tracker kernel, called on that block.
 #include <hip/hip_runtime.h>
 
 #include "opd_kprims.h"
@@ -76,7 +78,9 @@ __device__ void kalman_update(float* x, float* P, float z0, float z1) {
     for (int k = 0; k < 16; ++k) P[k] = N[k];
 }
 
-__global__ __launch_bounds__(TRACK_THREADS) void track_predict_cost_kernel(const TrackPredictParams p) {
+// The bodies of the four launches take their parameters by reference: the one-tracker kernels below hand them their by-value argument, the camera-batched
+// ones (track_*_multi_kernel, at the end of the file) the block of blockIdx.y's camera out of a descriptor array.  blockIdx.x means the same in both.
+__device__ __forceinline__ void track_predict_cost_body(const TrackPredictParams& p) {
     __shared__ float sm[TRACK_MAX_DIM];          // the smoothed feature
     __shared__ double iou_d[TRACK_MAX_DETS];     // IoU distance per detection, before rounding
     __shared__ uint8_t gated[TRACK_MAX_DETS];
@@ -165,7 +169,9 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_predict_cost_kernel(const
     }
 }
 
-__global__ __launch_bounds__(TRACK_THREADS) void track_commit_kernel(const TrackCommitParams p) {
+__global__ __launch_bounds__(TRACK_THREADS) void track_predict_cost_kernel(const TrackPredictParams p) { track_predict_cost_body(p); }
+
+__device__ __forceinline__ void track_commit_body(const TrackCommitParams& p) {
     const int tid = threadIdx.x, D = p.D;
     if (p.hdr && (p.hdr[TRACK_HDR_STOPPED] != 0 || (int)blockIdx.x >= p.hdr[TRACK_HDR_M])) return;   // (sequence call: the grid is an upper bound)
     const int32_t* op = p.ops + 4 * blockIdx.x;
@@ -214,6 +220,8 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_commit_kernel(const Track
     }
 }
 
+__global__ __launch_bounds__(TRACK_THREADS) void track_commit_kernel(const TrackCommitParams p) { track_commit_body(p); }
+
 // A feature row into the staging image: 64 lanes x 16 bytes = a 256-float row in one load each where both sides are 16-byte aligned
 __device__ __forceinline__ void ingest_row(const float* src, float* dst, int D, int lane) {
     if ((D & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
@@ -228,7 +236,7 @@ __device__ __forceinline__ void ingest_row(const float* src, float* dst, int D, 
 // One workgroup of one wave per record slot of a frame (p.view: that frame alone).  A record is 32 bytes (a merged one 48) and a row at most 8 KB: the launch is bound by its
 // latency, not by bandwidth, so the geometry is many small workgroups that each finish in one round trip instead of few large ones that loop.  No LDS,
 // no barrier: the slot search ends in a wave-wide maximum.
-__global__ __launch_bounds__(TRACK_INGEST_THREADS) void track_ingest_kernel(const TrackIngestParams p) {
+__device__ __forceinline__ void track_ingest_body(const TrackIngestParams& p) {
     const int i = blockIdx.x, lane = threadIdx.x, D = p.D, Q = p.view.stride;
     if (p.hdr && p.hdr[TRACK_HDR_STOPPED] != 0) return;
     const int n = opd::record_count(p.view, 0);
@@ -265,6 +273,8 @@ __global__ __launch_bounds__(TRACK_INGEST_THREADS) void track_ingest_kernel(cons
     }
     if (src != nullptr) ingest_row(src, p.feat + (size_t)i * D, D, lane);
 }
+
+__global__ __launch_bounds__(TRACK_INGEST_THREADS) void track_ingest_kernel(const TrackIngestParams p) { track_ingest_body(p); }
 
 // ---- the association on the device (sequence calls) -------------------------------------------------------------------------------------------
 // opd_assoc.cpp by ONE wave, pair for pair: the same five stages over the same sub-blocks with the same comparisons, and a solver that takes the
@@ -512,9 +522,9 @@ __device__ void assoc_stage(AssocLds& L, float* cache, const float* m, int N, ui
     n_dl = n_rest;
 }
 
-__global__ __launch_bounds__(TRACK_ASSOC_THREADS) void track_assoc_kernel(const TrackAssocParams p) {
+// `cache`: the kernel's dynamic LDS, [TRACK_ASSOC_CACHE_FLOATS]: the block a stage solves, when it fits
+__device__ __forceinline__ void track_assoc_body(const TrackAssocParams& p, float* cache) {
     __shared__ AssocLds L;
-    extern __shared__ float cache[];   // [TRACK_ASSOC_CACHE_FLOATS]: the block a stage solves, when it fits
     const int lane = threadIdx.x, S = p.S, E = TRACK_ENTRY_INTS;
     if (p.hdr[TRACK_HDR_STOPPED] != 0) return;
     int T = p.hdr[TRACK_HDR_T], N = p.n_dev ? *p.n_dev : p.n, n_free = p.hdr[TRACK_HDR_N_FREE], next_id = p.hdr[TRACK_HDR_NEXT_ID];
@@ -606,37 +616,136 @@ __global__ __launch_bounds__(TRACK_ASSOC_THREADS) void track_assoc_kernel(const 
     }
 }
 
+__global__ __launch_bounds__(TRACK_ASSOC_THREADS) void track_assoc_kernel(const TrackAssocParams p) {
+    extern __shared__ float cache[];
+    track_assoc_body(p, cache);
+}
+
+// ---- several cameras in one launch (opd_track_update_streams, opd_detr_detect_streams_track) ---------------------------------------
+// blockIdx.y is the camera, blockIdx.x what it is above, under a grid that covers the largest bound among the cameras of the step.  The workgroup copies
+// its camera's block out of descs [gridDim.y] (a uniform load: it lands in scalar registers as a kernel argument does) and runs the body above on it.
+// It leaves at once where the camera has nothing to do in this launch (`hdr` null: no frame at this step, or a bound of zero), where it lies beyond the
+// camera's own bound, and, inside the body, where the camera's TRACK_HDR_STOPPED is set.  Cameras share no memory: each block names its own tracker's
+// table, staging image and slot state.
+__global__ __launch_bounds__(TRACK_THREADS) void track_predict_cost_multi_kernel(const TrackPredictParams* __restrict__ descs) {
+    const TrackPredictParams p = descs[blockIdx.y];
+    if (!p.hdr || (int)blockIdx.x >= p.T) return;
+    track_predict_cost_body(p);
+}
+
+__global__ __launch_bounds__(TRACK_THREADS) void track_commit_multi_kernel(const TrackCommitParams* __restrict__ descs) {
+    const TrackCommitParams p = descs[blockIdx.y];
+    if (!p.hdr || (int)blockIdx.x >= p.M) return;
+    track_commit_body(p);
+}
+
+__global__ __launch_bounds__(TRACK_INGEST_THREADS) void track_ingest_multi_kernel(const TrackIngestParams* __restrict__ descs) {
+    const TrackIngestParams p = descs[blockIdx.y];
+    if (!p.hdr || (int)blockIdx.x >= p.view.stride) return;
+    track_ingest_body(p);
+}
+
+__global__ __launch_bounds__(TRACK_ASSOC_THREADS) void track_assoc_multi_kernel(const TrackAssocParams* __restrict__ descs) {
+    extern __shared__ float cache[];
+    const TrackAssocParams p = descs[blockIdx.y];
+    if (!p.hdr) return;
+    track_assoc_body(p, cache);
+}
+
 }  // namespace
 
+// What a launcher refuses, per parameter block: the one-tracker launchers and the camera-batched ones (on the host's copy of every block) share it
+static bool assoc_params_ok(const TrackAssocParams& p) {
+    if (p.S < 1 || p.S > TRACK_MAX_TRACKS || p.n < 0 || p.n > TRACK_MAX_DETS || p.conf_stride < 1 || p.frame < 0) return false;
+    return p.hdr && p.tab && p.free_slots && p.app && p.iou && p.comb && p.ops && p.ids && (p.conf || (!p.n_dev && p.n == 0));
+}
+static bool ingest_params_ok(const TrackIngestParams& p) {
+    const int Q = p.view.stride;
+    if (Q < 1 || Q > TRACK_MAX_DETS || p.D < 1 || p.D > TRACK_MAX_DIM || p.frame < 0 || p.slots < 0) return false;
+    if (p.rows_kind != TRACK_ROWS_NONE && p.rows_kind != TRACK_ROWS_BY_KEY && p.rows_kind != TRACK_ROWS_BY_SLOT) return false;
+    if (!p.view.records == !p.view.merged || !p.view.counts || !p.boxes || !p.foot || !p.has || !p.n_out) return false;
+    if (p.rows_kind != TRACK_ROWS_NONE && (!p.rows || !p.feat)) return false;
+    return p.rows_kind != TRACK_ROWS_BY_SLOT || (p.slot_map && p.n_person);
+}
+static bool predict_params_ok(const TrackPredictParams& p) {
+    if (p.T <= 0 || p.T > TRACK_MAX_TRACKS || p.d.n < 0 || p.d.n > TRACK_MAX_DETS || p.D < 1 || p.D > TRACK_MAX_DIM) return false;
+    return p.hdr ? p.tab != nullptr : p.slots != nullptr;
+}
+static bool commit_params_ok(const TrackCommitParams& p) { return p.M > 0 && p.M <= TRACK_MAX_TRACKS && p.D >= 1 && p.D <= TRACK_MAX_DIM && p.ops; }
+
 hipError_t opd_launch_track_assoc(const TrackAssocParams& p, hipStream_t stream) {
-    if (p.S < 1 || p.S > TRACK_MAX_TRACKS || p.n < 0 || p.n > TRACK_MAX_DETS || p.conf_stride < 1 || p.frame < 0) return hipErrorInvalidValue;
-    if (!p.hdr || !p.tab || !p.free_slots || !p.app || !p.iou || !p.comb || !p.ops || !p.ids || (!p.conf && (p.n_dev || p.n > 0))) return hipErrorInvalidValue;
+    if (!assoc_params_ok(p)) return hipErrorInvalidValue;
     OPD_SET_MAX_LDS_ONCE(track_assoc_kernel, TRACK_ASSOC_CACHE_FLOATS * 4);
     OPD_LAUNCH(track_assoc_kernel, dim3(1), dim3(TRACK_ASSOC_THREADS), TRACK_ASSOC_CACHE_FLOATS * 4, stream, p);
     return hipGetLastError();
 }
 
 hipError_t opd_launch_track_ingest(const TrackIngestParams& p, hipStream_t stream) {
-    const int Q = p.view.stride;
-    if (Q < 1 || Q > TRACK_MAX_DETS || p.D < 1 || p.D > TRACK_MAX_DIM || p.frame < 0 || p.slots < 0) return hipErrorInvalidValue;
-    if (p.rows_kind != TRACK_ROWS_NONE && p.rows_kind != TRACK_ROWS_BY_KEY && p.rows_kind != TRACK_ROWS_BY_SLOT) return hipErrorInvalidValue;
-    if (!p.view.records == !p.view.merged || !p.view.counts || !p.boxes || !p.foot || !p.has || !p.n_out) return hipErrorInvalidValue;
-    if (p.rows_kind != TRACK_ROWS_NONE && (!p.rows || !p.feat)) return hipErrorInvalidValue;
-    if (p.rows_kind == TRACK_ROWS_BY_SLOT && (!p.slot_map || !p.n_person)) return hipErrorInvalidValue;
-    OPD_LAUNCH(track_ingest_kernel, dim3(Q), dim3(TRACK_INGEST_THREADS), 0, stream, p);
+    if (!ingest_params_ok(p)) return hipErrorInvalidValue;
+    OPD_LAUNCH(track_ingest_kernel, dim3(p.view.stride), dim3(TRACK_INGEST_THREADS), 0, stream, p);
     return hipGetLastError();
 }
 
 hipError_t opd_launch_track_predict_cost(const TrackPredictParams& p, hipStream_t stream) {
-    if (p.T <= 0 || p.T > TRACK_MAX_TRACKS || p.d.n < 0 || p.d.n > TRACK_MAX_DETS || p.D < 1 || p.D > TRACK_MAX_DIM) return hipErrorInvalidValue;
-    if (p.hdr ? !p.tab : !p.slots) return hipErrorInvalidValue;
+    if (!predict_params_ok(p)) return hipErrorInvalidValue;
     OPD_LAUNCH(track_predict_cost_kernel, dim3(p.T), dim3(TRACK_THREADS), 0, stream, p);
     return hipGetLastError();
 }
 
 hipError_t opd_launch_track_commit(const TrackCommitParams& p, hipStream_t stream) {
-    if (p.M <= 0 || p.M > TRACK_MAX_TRACKS || p.D < 1 || p.D > TRACK_MAX_DIM) return hipErrorInvalidValue;
-    if (!p.ops) return hipErrorInvalidValue;
+    if (!commit_params_ok(p)) return hipErrorInvalidValue;
     OPD_LAUNCH(track_commit_kernel, dim3(p.M), dim3(TRACK_THREADS), 0, stream, p);
+    return hipGetLastError();
+}
+
+// The camera-batched launches.  `host`: the C blocks of the step as the host built them, `dev` the same bytes on the device.  A block with a null `hdr`
+// is a camera without work in this launch; every other block passes the one-tracker launcher's checks.  grid.x: the largest bound among them.
+// *launched (nullable): whether a launch was made (none where no camera has work).
+template <typename P, typename Ok, typename Bound>
+static hipError_t multi_grid(const P* host, const P* dev, int C, Ok ok, Bound bound, int* grid_x) {
+    *grid_x = 0;
+    if (!host || !dev || C < 1 || C > TRACK_MAX_CAMERAS) return hipErrorInvalidValue;
+    for (int c = 0; c < C; ++c) {
+        if (!host[c].hdr) continue;
+        if (!ok(host[c])) return hipErrorInvalidValue;
+        *grid_x = bound(host[c]) > *grid_x ? bound(host[c]) : *grid_x;
+    }
+    return hipSuccess;
+}
+
+hipError_t opd_launch_track_assoc_multi(const TrackAssocParams* host, const TrackAssocParams* dev, int C, hipStream_t stream, int* launched) {
+    int gx = 0;
+    const hipError_t e = multi_grid(host, dev, C, assoc_params_ok, [](const TrackAssocParams&) { return 1; }, &gx);
+    if (launched) *launched = e == hipSuccess && gx > 0;
+    if (e != hipSuccess || gx == 0) return e;
+    OPD_SET_MAX_LDS_ONCE(track_assoc_multi_kernel, TRACK_ASSOC_CACHE_FLOATS * 4);
+    OPD_LAUNCH(track_assoc_multi_kernel, dim3(1, C), dim3(TRACK_ASSOC_THREADS), TRACK_ASSOC_CACHE_FLOATS * 4, stream, dev);
+    return hipGetLastError();
+}
+
+hipError_t opd_launch_track_ingest_multi(const TrackIngestParams* host, const TrackIngestParams* dev, int C, hipStream_t stream, int* launched) {
+    int gx = 0;
+    const hipError_t e = multi_grid(host, dev, C, ingest_params_ok, [](const TrackIngestParams& p) { return (int)p.view.stride; }, &gx);
+    if (launched) *launched = e == hipSuccess && gx > 0;
+    if (e != hipSuccess || gx == 0) return e;
+    OPD_LAUNCH(track_ingest_multi_kernel, dim3(gx, C), dim3(TRACK_INGEST_THREADS), 0, stream, dev);
+    return hipGetLastError();
+}
+
+hipError_t opd_launch_track_predict_cost_multi(const TrackPredictParams* host, const TrackPredictParams* dev, int C, hipStream_t stream, int* launched) {
+    int gx = 0;
+    const hipError_t e = multi_grid(host, dev, C, predict_params_ok, [](const TrackPredictParams& p) { return (int)p.T; }, &gx);
+    if (launched) *launched = e == hipSuccess && gx > 0;
+    if (e != hipSuccess || gx == 0) return e;
+    OPD_LAUNCH(track_predict_cost_multi_kernel, dim3(gx, C), dim3(TRACK_THREADS), 0, stream, dev);
+    return hipGetLastError();
+}
+
+hipError_t opd_launch_track_commit_multi(const TrackCommitParams* host, const TrackCommitParams* dev, int C, hipStream_t stream, int* launched) {
+    int gx = 0;
+    const hipError_t e = multi_grid(host, dev, C, commit_params_ok, [](const TrackCommitParams& p) { return (int)p.M; }, &gx);
+    if (launched) *launched = e == hipSuccess && gx > 0;
+    if (e != hipSuccess || gx == 0) return e;
+    OPD_LAUNCH(track_commit_multi_kernel, dim3(gx, C), dim3(TRACK_THREADS), 0, stream, dev);
     return hipGetLastError();
 }

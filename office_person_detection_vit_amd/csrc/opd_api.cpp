@@ -300,6 +300,7 @@ static int enqueue_floor(opd_detr* m, const RecordSink& s, const CallRecords& c)
 // keep the others from being committed, and its error is the call's.
 static int enqueue_trackers(opd_detr* m, const RecordSink& s, const CallRecords& c, const TrackFeatureSource& src) {
     const TrackStage& t = s.track;
+    if (t.cams) return track_streams_enqueue(t.cams, t.n_cams, t.camera_of, m->stream, c.view.records, c.view.counts, c.view.stride, c.view.n_frames, src, "opd_detr_detect_streams_track");
     if (t.seq) return track_sequence_enqueue(t.seq, m->stream, c.view.records, c.view.counts, c.view.stride, c.view.n_frames, src, "opd_detr_detect_sequence_track");
     for (int f = 0; f < c.view.n_frames; ++f) RCCHK(track_fused_enqueue(t.trackers[f], m->stream, record_frame(c.view, f), f, src));
     return OPD_OK;
@@ -307,6 +308,7 @@ static int enqueue_trackers(opd_detr* m, const RecordSink& s, const CallRecords&
 static int finish_trackers(opd_detr* m, const RecordSink& s, const CallRecords& c, bool with_features) {
     const TrackStage& t = s.track;
     const int frames = c.view.n_frames, stride = c.view.stride;
+    if (t.cams) return track_streams_finish(t.cams, t.n_cams, t.camera_of, c.counts, stride, frames, t.track_ids, t.frames_done, "opd_detr_detect_streams_track");
     if (t.seq) return track_sequence_finish(t.seq, c.counts, stride, frames, t.track_ids, t.frames_done, "opd_detr_detect_sequence_track");
     int rc = OPD_OK;
     std::string first;
@@ -1120,7 +1122,11 @@ static int detect_track(const std::string& me, opd_detr* m, opd_reid* r, const T
         dim = OPD_COLOR_DIM;
         sink.feature.kind = feature_kind == OPD_TRACK_FEAT_ENCODER ? FEAT_ROI : FEAT_COLOR;
     }
-    for (int b = 0; b < (track.trackers ? B : 1); ++b) {   // (a null tracker, `seq` too, is track_fused_check's to refuse)
+    if (track.cams) {   // (every tracker of the list by the same checks, then the list against camera_of)
+        for (int c = 0; c < track.n_cams; ++c) RCCHK(track_fused_check(track.cams[c], m->device, m->arch.queries, dim, me.c_str()));
+        RCCHK(track_streams_check(track.cams, track.n_cams, track.camera_of, B, me.c_str()));
+    }
+    for (int b = 0; b < (track.trackers ? B : 1) && !track.cams; ++b) {   // (a null tracker, `seq` too, is track_fused_check's to refuse)
         RCCHK(track_fused_check(track.trackers ? track.trackers[b] : track.seq, m->device, m->arch.queries, dim, me.c_str()));
         for (int a = 0; a < b; ++a)
             if (track.trackers[a] == track.trackers[b])
@@ -1146,6 +1152,19 @@ int opd_detr_detect_sequence_track(opd_detr* m, opd_reid* r, opd_track* t, const
     if (!frames || !out || !counts || !track_ids || !n_featured || !frames_done) return fail(OPD_EINVAL, me + ": null argument (frame list or an output)");
     TrackStage track;
     track.seq = t; track.track_ids = track_ids; track.n_featured = n_featured; track.frames_done = frames_done;
+    return detect_track(me, m, r, track, frames, B, h, w, H, W, threshold, label, feature_kind, slots, out, counts);
+}); }
+
+// The streams twin: K_c frames each of C cameras in one call, frame b into trackers[camera_of[b]], the cameras' steps side by side on the device
+int opd_detr_detect_streams_track(opd_detr* m, opd_reid* r, opd_track* const* trackers, int C, const int32_t* camera_of, const uint8_t* const* frames, int B, int h, int w,
+                                  int H, int W, float threshold, int label, int feature_kind, int slots, opd_det* out, int32_t* counts, int32_t* track_ids,
+                                  int32_t* n_featured, int32_t* frames_done) { return api_call("opd_detr_detect_streams_track", [&]() -> int {
+    const std::string me = "opd_detr_detect_streams_track";
+    if (!trackers || !camera_of || !frames || !out || !counts || !track_ids || !n_featured || !frames_done)
+        return fail(OPD_EINVAL, me + ": null argument (tracker list, camera_of, frame list or an output)");
+    if (C < 1 || C > TRACK_MAX_CAMERAS) return fail(OPD_EINVAL, me + ": C = " + std::to_string(C) + " outside 1 .. " + std::to_string((int)TRACK_MAX_CAMERAS) + " trackers a call");
+    TrackStage track;
+    track.cams = trackers; track.n_cams = C; track.camera_of = camera_of; track.track_ids = track_ids; track.n_featured = n_featured; track.frames_done = frames_done;
     return detect_track(me, m, r, track, frames, B, h, w, H, W, threshold, label, feature_kind, slots, out, counts);
 }); }
 

@@ -448,11 +448,12 @@ struct FeatureStage {
     int32_t *slot_map = nullptr, *n_person = nullptr;
 };
 struct FloorStage { const opd_floor* fmap = nullptr; opd_floor_rec* out = nullptr; };   // a floor record of every record of the class -> out [B][queries]
-struct TrackStage {   // the kept records and feature rows enter trackers where they lie: frame b into trackers[b], or the B frames in order into `seq`
-    struct opd_track* const* trackers = nullptr;
+struct TrackStage {   // the kept records and feature rows enter trackers where they lie: frame b into trackers[b], or the B frames in order into `seq`,
+    struct opd_track* const* trackers = nullptr;   // or (`cams`) frame b into cams[camera_of[b]], every camera's frames in their order, the cameras side by side
     struct opd_track* seq = nullptr;
-    int32_t *track_ids = nullptr, *n_featured = nullptr, *frames_done = nullptr;   // [B][queries], [B]; seq: frames applied
-    bool on() const { return trackers || seq; }
+    struct opd_track* const* cams = nullptr; int n_cams = 0; const int32_t* camera_of = nullptr;
+    int32_t *track_ids = nullptr, *n_featured = nullptr, *frames_done = nullptr;   // [B][queries], [B]; seq: frames applied; cams: [n_cams]
+    bool on() const { return trackers || seq || cams; }
 };
 struct HybridStage {   // the kept records and the camera-resolution frames enter hybrid trackers (opd_lwt.h) where they lie: frame b into trackers[b], or
     struct opd_lwt* const* trackers = nullptr;   // (`seq`) as the key frames of the run of frames `call` of one camera, its in-between frames around them

@@ -14,6 +14,9 @@
 // The sequence calls (opd_track_update_sequence here, opd_detr_detect_sequence_track in opd_api.cpp) take a run of frames with ONE wait:
 // the table of tracks goes to the device, track_assoc_kernel does part 2 there between the launches of every frame, and the table comes back and is
 // adopted after the wait.  Between calls the host's copy stays the authoritative one, so the per-frame calls above are untouched.
+//
+// The streams calls (opd_track_update_streams here, opd_detr_detect_streams_track in opd_api.cpp) are sequence calls of C trackers side by side:
+// step s is the s-th frame of every camera that has one, in at most four launches over C parameter blocks in device memory (StreamsDescs), one wait.
 #include <math.h>
 #include <string.h>
 
@@ -230,26 +233,27 @@ int seq_begin(opd_track* t, const SeqLayout& q, size_t n_ids, const char* who) {
     return OPD_OK;
 }
 
-// One frame on stream `s`.  `dets`: its detections on the device, dets.n of them at most (n_dev, nullable: where the exact count lies).  t_bound: an
-// upper bound of the tracks alive when the frame starts; the launches take the true numbers from the table.
-int seq_enqueue_frame(opd_track* t, hipStream_t s, const SeqLayout& q, const TrackDets& dets, const int32_t* n_dev, const float* conf, int conf_stride,
-                      int32_t* ids_dev, int frame, int t_bound) {
+// The parameter blocks of one frame of a sequence.  `dets`: its detections on the device, dets.n of them at most (n_dev, nullable: where the exact count lies).
+// t_bound: an upper bound of the tracks alive when the frame starts; the launches take the true numbers from the table.  `predict` / `commit`: whether
+// that launch has anything to do under these bounds.  seq_enqueue_frame launches them one tracker at a time, a streams call C trackers at a time.
+struct SeqFrameParams { TrackPredictParams p; TrackAssocParams a; TrackCommitParams c; bool predict, commit; };
+
+SeqFrameParams seq_frame_params(const opd_track* t, const SeqLayout& q, const TrackDets& dets, const int32_t* n_dev, const float* conf, int conf_stride, int32_t* ids_dev,
+                                int frame, int t_bound) {
     uint8_t* d = t->io.dev;
     uint8_t* sq = t->seq.dev;
     int32_t* hdr = reinterpret_cast<int32_t*>(sq + q.o_hdr);
     int32_t* tab = reinterpret_cast<int32_t*>(sq + q.o_tab);
-    if (t_bound > 0) {
-        TrackPredictParams p{};
-        p.s = t->st; p.d = dets;
-        p.T = t_bound; p.D = t->D;
-        p.app = reinterpret_cast<float*>(d + t->o_app); p.iou = reinterpret_cast<float*>(d + t->o_iou); p.comb = reinterpret_cast<float*>(d + t->o_comb);
-        p.aw = t->aw; p.mw = t->mw;
-        p.max_dist = (float)t->max_dist;
-        p.n_dev = n_dev; p.hdr = hdr; p.tab = tab;
-        HIPCHK(opd_launch_track_predict_cost(p, s));
-        ++t->last_launches;
-    }
-    TrackAssocParams a{};
+    SeqFrameParams f{};
+    f.predict = t_bound > 0;
+    TrackPredictParams& p = f.p;
+    p.s = t->st; p.d = dets;
+    p.T = t_bound; p.D = t->D;
+    p.app = reinterpret_cast<float*>(d + t->o_app); p.iou = reinterpret_cast<float*>(d + t->o_iou); p.comb = reinterpret_cast<float*>(d + t->o_comb);
+    p.aw = t->aw; p.mw = t->mw;
+    p.max_dist = (float)t->max_dist;
+    p.n_dev = n_dev; p.hdr = hdr; p.tab = tab;
+    TrackAssocParams& a = f.a;
     a.hdr = hdr; a.tab = tab; a.free_slots = reinterpret_cast<int32_t*>(sq + q.o_free);
     a.app = reinterpret_cast<const float*>(d + t->o_app); a.iou = reinterpret_cast<const float*>(d + t->o_iou); a.comb = reinterpret_cast<const float*>(d + t->o_comb);
     a.conf = conf; a.conf_stride = conf_stride;
@@ -257,15 +261,27 @@ int seq_enqueue_frame(opd_track* t, hipStream_t s, const SeqLayout& q, const Tra
     a.ops = reinterpret_cast<int32_t*>(d + t->o_ops); a.ids = ids_dev;
     a.S = t->S; a.min_hits = t->min_hits; a.max_age = t->max_age; a.frame = frame;
     a.high_conf = t->high_conf;
-    HIPCHK(opd_launch_track_assoc(a, s));
-    ++t->last_launches;
     const int m_bound = std::min<int>(t->S, dets.n);
-    if (m_bound > 0) {
-        TrackCommitParams c{};
-        c.s = t->st; c.d = dets;
-        c.M = m_bound; c.D = t->D;
-        c.ops = a.ops; c.hdr = hdr;
-        HIPCHK(opd_launch_track_commit(c, s));
+    f.commit = m_bound > 0;
+    TrackCommitParams& c = f.c;
+    c.s = t->st; c.d = dets;
+    c.M = m_bound; c.D = t->D;
+    c.ops = a.ops; c.hdr = hdr;
+    return f;
+}
+
+// One frame on stream `s`
+int seq_enqueue_frame(opd_track* t, hipStream_t s, const SeqLayout& q, const TrackDets& dets, const int32_t* n_dev, const float* conf, int conf_stride,
+                      int32_t* ids_dev, int frame, int t_bound) {
+    const SeqFrameParams f = seq_frame_params(t, q, dets, n_dev, conf, conf_stride, ids_dev, frame, t_bound);
+    if (f.predict) {
+        HIPCHK(opd_launch_track_predict_cost(f.p, s));
+        ++t->last_launches;
+    }
+    HIPCHK(opd_launch_track_assoc(f.a, s));
+    ++t->last_launches;
+    if (f.commit) {
+        HIPCHK(opd_launch_track_commit(f.c, s));
         ++t->last_launches;
     }
     return OPD_OK;
@@ -341,9 +357,265 @@ int update_sequence_body(opd_track* t, const float* boxes, const float* foot, co
     return seq_adopt(t, q, F, frames_done, "opd_track_update_sequence");
 }
 
+// The ingest block of frame b of a call's records into t's staging image, inside a sequence (`hdr` set)
+TrackIngestParams seq_ingest_params(const opd_track* t, const SeqLayout& q, const RecordView& view, int b, const TrackFeatureSource& src) {
+    uint8_t* d = t->io.dev;
+    TrackIngestParams p{};
+    p.view = record_frame(view, b); p.D = t->D; p.frame = b;
+    p.rows_kind = src.rows_kind; p.rows = src.rows; p.slot_map = src.slot_map; p.n_person = src.n_person; p.slots = src.slots;
+    p.boxes = reinterpret_cast<float*>(d + t->o_boxes);
+    p.foot = reinterpret_cast<float*>(d + t->o_foot);
+    p.has = d + t->o_has;
+    p.feat = reinterpret_cast<float*>(d + t->o_feat);
+    p.n_out = reinterpret_cast<int32_t*>(d + t->o_n);
+    p.hdr = reinterpret_cast<const int32_t*>(t->seq.dev + q.o_hdr);
+    return p;
+}
+
+// ---- streams calls: the sequence call's steps for C trackers side by side ------------------------------------------------------------
+// The parameter blocks of every step and all four kinds, [steps][C] each, in the page-locked half of trackers[0]->desc; one copy takes them to the device
+// half, and each step is at most four launches over them, whatever C is.  A zeroed block (`hdr` null) is a camera without work in that launch.
+struct StreamsDescs {
+    opd_track* owner = nullptr;
+    int C = 0, steps = 0;
+    bool ingest = false;
+    size_t o_in = 0, o_p = 0, o_a = 0, o_c = 0, bytes = 0;
+    int begin(opd_track* t0, int C_, int steps_, bool ingest_, const char* who) {
+        owner = t0; C = C_; steps = steps_; ingest = ingest_;
+        const size_t n = (size_t)steps * C;
+        size_t off = 0;
+        auto place = [&](size_t b) { const size_t o = off; off += align_up(b, 256); return o; };
+        o_in = place(ingest ? n * sizeof(TrackIngestParams) : 0); o_p = place(n * sizeof(TrackPredictParams)); o_a = place(n * sizeof(TrackAssocParams));
+        o_c = place(n * sizeof(TrackCommitParams));
+        bytes = off;
+        bool moved = false;
+        RCCHK(t0->desc.reserve(who, bytes, bytes, t0->stream, &moved));
+        if (moved) ++g_handle_epoch;   // device memory changed hands (opd_device.h)
+        memset(t0->desc.host, 0, bytes);
+        return OPD_OK;
+    }
+    template <typename P> P* at(uint8_t* base, size_t o, int s) const { return reinterpret_cast<P*>(base + o) + (size_t)s * C; }
+    void set(int s, int c, const SeqFrameParams& f) {
+        if (f.predict) at<TrackPredictParams>(owner->desc.host, o_p, s)[c] = f.p;
+        at<TrackAssocParams>(owner->desc.host, o_a, s)[c] = f.a;
+        if (f.commit) at<TrackCommitParams>(owner->desc.host, o_c, s)[c] = f.c;
+    }
+    void set(int s, int c, const TrackIngestParams& p) { at<TrackIngestParams>(owner->desc.host, o_in, s)[c] = p; }
+    // the upload and the steps on stream `st`; *launches: the launches made
+    int run(hipStream_t st, int* launches) const {
+        uint8_t* h = owner->desc.host;
+        uint8_t* d = owner->desc.dev;
+        HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+        *launches = 0;
+        for (int s = 0; s < steps; ++s) {
+            int made = 0;
+            if (ingest) {
+                HIPCHK(opd_launch_track_ingest_multi(at<TrackIngestParams>(h, o_in, s), at<TrackIngestParams>(d, o_in, s), C, st, &made));
+                *launches += made;
+            }
+            HIPCHK(opd_launch_track_predict_cost_multi(at<TrackPredictParams>(h, o_p, s), at<TrackPredictParams>(d, o_p, s), C, st, &made));   // (none where no camera can have a live track)
+            *launches += made;
+            HIPCHK(opd_launch_track_assoc_multi(at<TrackAssocParams>(h, o_a, s), at<TrackAssocParams>(d, o_a, s), C, st, &made));
+            *launches += made;
+            HIPCHK(opd_launch_track_commit_multi(at<TrackCommitParams>(h, o_c, s), at<TrackCommitParams>(d, o_c, s), C, st, &made));
+            *launches += made;
+        }
+        return OPD_OK;
+    }
+};
+
+// `s` behind whatever each tracker's own stream still holds (its previous commit launch reads the staging image this call overwrites)
+int streams_order(opd_track* const* trackers, int C, hipStream_t s) {
+    for (int c = 0; c < C; ++c) {
+        if (trackers[c]->stream == s) continue;
+        HIPCHK(hipEventRecord(trackers[c]->ev_commit, trackers[c]->stream));
+        HIPCHK(hipStreamWaitEvent(s, trackers[c]->ev_commit, 0));
+    }
+    return OPD_OK;
+}
+
+// seq_adopt per camera: every camera that ran to its end is adopted whatever another one did; the error is the lowest-numbered failing camera's,
+// under a name that says which, with the list of every camera that ran out of slots behind it
+int streams_adopt(opd_track* const* trackers, int C, const std::vector<SeqLayout>& q, const std::vector<int>& n_frames, int launches, int32_t* frames_done, const char* who) {
+    int rc = OPD_OK;
+    std::string first, stopped;
+    for (int c = 0; c < C; ++c) {
+        trackers[c]->last_launches = launches;
+        const int one = seq_adopt(trackers[c], q[c], n_frames[c], &frames_done[c], std::string(who) + ": camera " + std::to_string(c));
+        if (one != OPD_OK && rc == OPD_OK) { rc = one; first = g_err; }
+        if (one == OPD_EINVAL) stopped += (stopped.empty() ? "" : ", ") + std::to_string(c);
+    }
+    if (rc == OPD_OK) return OPD_OK;
+    return fail(rc, stopped.empty() ? first : first + "; cameras out of slots: " + stopped);
+}
+
+int update_streams_body(opd_track* const* trackers, int C, const int32_t* camera_of, int F, const float* boxes, const float* foot, const float* conf, const float* features,
+                        const uint8_t* has, int kind, const int32_t* counts, int32_t* out_ids, int32_t* frames_done) {
+    const char* who = "opd_track_update_streams";
+    opd_track* t0 = trackers[0];
+    hipStream_t s = t0->stream;
+    const std::vector<std::vector<int32_t>> sched = streams_schedule(camera_of, F, C);
+    const int steps = (int)sched.size();
+    // where frame f lies in the packed arrays: its first detection, and its first feature float (rows as wide as its own tracker's feature_dim)
+    std::vector<size_t> det_at(F + 1, 0), feat_at(F + 1, 0);
+    for (int f = 0; f < F; ++f) {
+        det_at[f + 1] = det_at[f] + (size_t)counts[f];
+        feat_at[f + 1] = feat_at[f] + (size_t)counts[f] * trackers[camera_of[f]]->D;
+    }
+    std::vector<size_t> total(C, 0);
+    std::vector<int> n_frames(C, 0);
+    for (int f = 0; f < F; ++f) { total[camera_of[f]] += (size_t)counts[f]; ++n_frames[camera_of[f]]; }
+    HIPCHK(hipSetDevice(t0->device));
+    const bool any_feats = features != nullptr && det_at[F] > 0;
+    if (any_feats && kind == OPD_MEM_DEVICE && !device_accessible(features))
+        return fail(OPD_EINVAL, std::string(who) + ": OPD_MEM_DEVICE, but the features are not device-accessible memory");
+    const bool feats_by_host = any_feats && kind == OPD_MEM_HOST;
+    std::vector<SeqLayout> q(C);
+    for (int c = 0; c < C; ++c) {
+        q[c] = seq_layout(trackers[c], total[c], total[c], any_feats && total[c] > 0);
+        RCCHK(seq_begin(trackers[c], q[c], total[c], who));
+    }
+    StreamsDescs descs;
+    RCCHK(descs.begin(t0, C, steps, false, who));
+    RCCHK(streams_order(trackers, C, s));
+    // ---- per camera: its frames gathered in its own order behind its table, the blocks of its steps, one copy up (device features: a copy per frame)
+    for (int c = 0; c < C; ++c) {
+        opd_track* t = trackers[c];
+        const bool feats = any_feats && total[c] > 0;
+        const int D = t->D;
+        uint8_t* h = t->seq.host;
+        uint8_t* sq = t->seq.dev;
+        size_t row = 0;
+        int t_bound = (int)t->tracks.size();
+        for (int k = 0; k < n_frames[c]; ++k) {
+            const int f = sched[k][c], n = counts[f];
+            if (n > 0) {
+                memcpy(h + q[c].o_boxes + row * 16, boxes + det_at[f] * 4, (size_t)n * 16);
+                memcpy(h + q[c].o_foot + row * 8, foot + det_at[f] * 2, (size_t)n * 8);
+                memcpy(h + q[c].o_conf + row * 4, conf + det_at[f], (size_t)n * 4);
+                if (feats && has) memcpy(h + q[c].o_has + row, has + det_at[f], (size_t)n);
+                else memset(h + q[c].o_has + row, feats ? 1 : 0, (size_t)n);
+                if (feats && feats_by_host) memcpy(h + q[c].o_feat + row * D * 4, features + feat_at[f], (size_t)n * D * 4);
+                if (feats && !feats_by_host) HIPCHK(hipMemcpyAsync(sq + q[c].o_feat + row * D * 4, features + feat_at[f], (size_t)n * D * 4, hipMemcpyDeviceToDevice, s));
+            }
+            TrackDets d{};
+            d.boxes = reinterpret_cast<const float*>(sq + q[c].o_boxes) + row * 4;
+            d.foot = reinterpret_cast<const float*>(sq + q[c].o_foot) + row * 2;
+            d.feat = feats && n > 0 ? reinterpret_cast<const float*>(sq + q[c].o_feat) + row * D : nullptr;
+            d.has = sq + q[c].o_has + row;
+            d.n = n;
+            descs.set(k, c, seq_frame_params(t, q[c], d, nullptr, reinterpret_cast<const float*>(sq + q[c].o_conf) + row, 1, reinterpret_cast<int32_t*>(sq + q[c].o_ids) + row, k, t_bound));
+            row += (size_t)n;
+            t_bound = std::min<int>(t->S, t_bound + n);
+        }
+        HIPCHK(hipMemcpyAsync(sq, h, feats && feats_by_host ? q[c].bytes : q[c].o_feat, hipMemcpyHostToDevice, s));
+    }
+    // ---- the steps, every tracker's table back, one wait
+    int launches = 0;
+    RCCHK(descs.run(s, &launches));
+    for (int c = 0; c < C; ++c) HIPCHK(hipMemcpyAsync(trackers[c]->seq.host, trackers[c]->seq.dev, q[c].o_ids + total[c] * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    ++t0->last_waits;
+    for (int c = 0; c < C; ++c) {
+        const int32_t* ids = reinterpret_cast<const int32_t*>(trackers[c]->seq.host + q[c].o_ids);
+        size_t row = 0;
+        for (int k = 0; k < n_frames[c]; ++k) {
+            const int f = sched[k][c];
+            if (counts[f] > 0) memcpy(out_ids + det_at[f], ids + row, (size_t)counts[f] * 4);
+            row += (size_t)counts[f];
+        }
+    }
+    return streams_adopt(trackers, C, q, n_frames, launches, frames_done, who);
+}
+
 }  // namespace
 
 namespace opd {
+
+std::vector<std::vector<int32_t>> streams_schedule(const int32_t* camera_of, int F, int C) {
+    std::vector<std::vector<int32_t>> steps;
+    std::vector<int> seen(C > 0 ? C : 0, 0);
+    for (int f = 0; f < F; ++f) {
+        const int c = camera_of[f];
+        if (c < 0 || c >= C) continue;
+        const int k = seen[c]++;
+        if (k >= (int)steps.size()) steps.emplace_back(C, -1);
+        steps[k][c] = f;
+    }
+    return steps;
+}
+
+int track_streams_check(opd_track* const* trackers, int C, const int32_t* camera_of, int F, const char* who) {
+    const std::string me = std::string(who) + ": ";
+    std::vector<int> n_frames(C, 0);
+    for (int f = 0; f < F; ++f) {
+        if (camera_of[f] < 0 || camera_of[f] >= C)
+            return fail(OPD_EINVAL, me + "camera_of[" + std::to_string(f) + "] = " + std::to_string(camera_of[f]) + " outside 0 .. C - 1 = " + std::to_string(C - 1));
+        ++n_frames[camera_of[f]];
+    }
+    for (int b = 0; b < C; ++b)
+        for (int a = 0; a < b; ++a)
+            if (trackers[a] == trackers[b])
+                return fail(OPD_EINVAL, me + "cameras " + std::to_string(a) + " and " + std::to_string(b) + " name the same tracker; a tracker follows one camera");
+    for (int c = 0; c < C; ++c)
+        if (n_frames[c] == 0) return fail(OPD_EINVAL, me + "camera " + std::to_string(c) + " gets no frame of the call; leave its tracker out of the list");
+    return OPD_OK;
+}
+
+int track_streams_enqueue(opd_track* const* trackers, int C, const int32_t* camera_of, hipStream_t s, const opd_det* records, const int32_t* counts, int Q, int B,
+                          const TrackFeatureSource& src, const char* who) {
+    const std::vector<std::vector<int32_t>> sched = streams_schedule(camera_of, B, C);
+    const bool with_features = src.rows_kind != TRACK_ROWS_NONE;
+    const RecordView view{records, nullptr, counts, B, Q};
+    std::vector<SeqLayout> q(C);
+    std::vector<int> n_frames(C, 0);
+    for (int b = 0; b < B; ++b) ++n_frames[camera_of[b]];
+    for (int c = 0; c < C; ++c) {
+        q[c] = seq_layout(trackers[c], (size_t)n_frames[c] * Q, 0, false);
+        RCCHK(seq_begin(trackers[c], q[c], (size_t)n_frames[c] * Q, who));
+    }
+    StreamsDescs descs;
+    RCCHK(descs.begin(trackers[0], C, (int)sched.size(), true, who));
+    RCCHK(streams_order(trackers, C, s));
+    for (int c = 0; c < C; ++c) {
+        opd_track* t = trackers[c];
+        uint8_t* sq = t->seq.dev;
+        HIPCHK(hipMemcpyAsync(sq, t->seq.host, q[c].o_ids + (size_t)n_frames[c] * Q * 4, hipMemcpyHostToDevice, s));
+        int t_bound = (int)t->tracks.size();
+        for (int k = 0; k < n_frames[c]; ++k) {
+            const int b = sched[k][c];
+            const TrackIngestParams p = seq_ingest_params(t, q[c], view, b, src);
+            descs.set(k, c, p);
+            descs.set(k, c, seq_frame_params(t, q[c], dets_of(t, t->io.dev, Q, with_features), p.n_out, &records[(size_t)b * Q].score, (int)(sizeof(opd_det) / sizeof(float)),
+                                             reinterpret_cast<int32_t*>(sq + q[c].o_ids) + (size_t)k * Q, k, t_bound));
+            t_bound = std::min<int>(t->S, t_bound + Q);
+        }
+    }
+    int launches = 0;
+    RCCHK(descs.run(s, &launches));
+    for (int c = 0; c < C; ++c) {
+        trackers[c]->last_launches = launches;
+        HIPCHK(hipMemcpyAsync(trackers[c]->seq.host, trackers[c]->seq.dev, q[c].o_ids + (size_t)n_frames[c] * Q * 4, hipMemcpyDeviceToHost, s));
+    }
+    return OPD_OK;
+}
+
+int track_streams_finish(opd_track* const* trackers, int C, const int32_t* camera_of, const int32_t* counts, int Q, int B, int32_t* track_ids, int32_t* frames_done,
+                         const char* who) {
+    const std::vector<std::vector<int32_t>> sched = streams_schedule(camera_of, B, C);
+    std::vector<SeqLayout> q(C);
+    std::vector<int> n_frames(C, 0);
+    for (int b = 0; b < B; ++b) ++n_frames[camera_of[b]];
+    for (int c = 0; c < C; ++c) {
+        q[c] = seq_layout(trackers[c], (size_t)n_frames[c] * Q, 0, false);
+        const int32_t* ids = reinterpret_cast<const int32_t*>(trackers[c]->seq.host + q[c].o_ids);
+        for (int k = 0; k < n_frames[c]; ++k) {
+            const int b = sched[k][c], n = std::max(0, std::min(counts[b], Q));
+            if (n > 0) memcpy(track_ids + (size_t)b * Q, ids + (size_t)k * Q, (size_t)n * 4);
+        }
+    }
+    return streams_adopt(trackers, C, q, n_frames, trackers[0]->last_launches, frames_done, who);
+}
 
 int track_sequence_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* counts, int Q, int B, const TrackFeatureSource& src, const char* who) {
     const SeqLayout q = seq_layout(t, (size_t)B * Q, 0, false);
@@ -357,15 +629,7 @@ int track_sequence_enqueue(opd_track* t, hipStream_t s, const opd_det* records, 
     const bool with_features = src.rows_kind != TRACK_ROWS_NONE;
     int t_bound = (int)t->tracks.size();
     for (int b = 0; b < B; ++b) {
-        TrackIngestParams p{};
-        p.view = record_frame(RecordView{records, nullptr, counts, B, Q}, b); p.D = t->D; p.frame = b;
-        p.rows_kind = src.rows_kind; p.rows = src.rows; p.slot_map = src.slot_map; p.n_person = src.n_person; p.slots = src.slots;
-        p.boxes = reinterpret_cast<float*>(d + t->o_boxes);
-        p.foot = reinterpret_cast<float*>(d + t->o_foot);
-        p.has = d + t->o_has;
-        p.feat = reinterpret_cast<float*>(d + t->o_feat);
-        p.n_out = reinterpret_cast<int32_t*>(d + t->o_n);
-        p.hdr = reinterpret_cast<const int32_t*>(sq + q.o_hdr);
+        const TrackIngestParams p = seq_ingest_params(t, q, RecordView{records, nullptr, counts, B, Q}, b, src);
         HIPCHK(opd_launch_track_ingest(p, s));
         ++t->last_launches;
         RCCHK(seq_enqueue_frame(t, s, q, dets_of(t, d, Q, with_features), p.n_out, &records[(size_t)b * Q].score, (int)(sizeof(opd_det) / sizeof(float)),
@@ -494,6 +758,7 @@ extern "C" void opd_track_destroy(opd_track* t) { (void)api_call("opd_track_dest
     if (t->d_state) (void)hipFree(t->d_state);
     t->io.release();
     t->seq.release();
+    t->desc.release();
     delete t;
     ++g_handle_epoch;
     return OPD_OK;
@@ -539,6 +804,37 @@ extern "C" int opd_track_update_sequence(opd_track* t, const float* boxes_xywh, 
         if (counts[f] > t->NM)
             return fail(OPD_EINVAL, me + std::to_string(counts[f]) + " detections in frame " + std::to_string(f) + ", the handle was made for max_dets = " + std::to_string(t->NM));
     return update_sequence_body(t, boxes_xywh, foot_xy, confidence, features, has_feature, feat_mem_kind, counts, F, out_ids, frames_done);
+}); }
+
+extern "C" int opd_track_update_streams(opd_track* const* trackers, int C, const int32_t* camera_of, int F, const float* boxes_xywh, const float* foot_xy,
+                                        const float* confidence, const float* features, const uint8_t* has_feature, int feat_mem_kind, const int32_t* counts,
+                                        int32_t* out_ids, int32_t* frames_done) { return api_call("opd_track_update_streams", [&]() -> int {
+    const std::string me = "opd_track_update_streams: ";
+    // what needs no handle first, as in opd_track_update_sequence
+    if (!trackers || !camera_of || !counts || !out_ids || !frames_done) return fail(OPD_EINVAL, me + "null argument (tracker list, camera_of, counts or an output)");
+    if (C < 1 || C > TRACK_MAX_CAMERAS) return fail(OPD_EINVAL, me + "C = " + std::to_string(C) + " outside 1 .. " + std::to_string((int)TRACK_MAX_CAMERAS) + " trackers a call");
+    if (F <= 0) return fail(OPD_EINVAL, me + "a call has at least one frame, got F = " + std::to_string(F));
+    if (feat_mem_kind != OPD_MEM_HOST && feat_mem_kind != OPD_MEM_DEVICE) return fail(OPD_EINVAL, me + "feat_mem_kind must be OPD_MEM_HOST or OPD_MEM_DEVICE");
+    size_t total = 0;
+    for (int f = 0; f < F; ++f) {
+        if (counts[f] < 0) return fail(OPD_EINVAL, me + "negative detection count of frame " + std::to_string(f));
+        total += (size_t)counts[f];
+    }
+    if (total > 0 && (!boxes_xywh || !foot_xy || !confidence)) return fail(OPD_EINVAL, me + "null boxes, foot points or confidences");
+    for (int f = 0; f < F; ++f)   // (before a handle is read: an entry names the handle to read)
+        if (camera_of[f] < 0 || camera_of[f] >= C) return track_streams_check(trackers, C, camera_of, F, "opd_track_update_streams");
+    for (int c = 0; c < C; ++c)
+        if (!trackers[c]) return fail(OPD_EINVAL, me + "null handle (camera " + std::to_string(c) + ")");
+    RCCHK(track_streams_check(trackers, C, camera_of, F, "opd_track_update_streams"));
+    for (int c = 1; c < C; ++c)
+        if (trackers[c]->device != trackers[0]->device)
+            return fail(OPD_EINVAL, me + "camera 0's tracker is on device " + std::to_string(trackers[0]->device) + ", camera " + std::to_string(c) + "'s on device " +
+                                        std::to_string(trackers[c]->device) + "; the trackers of a call share one device");
+    for (int f = 0; f < F; ++f)
+        if (counts[f] > trackers[camera_of[f]]->NM)
+            return fail(OPD_EINVAL, me + std::to_string(counts[f]) + " detections in frame " + std::to_string(f) + ", the handle of camera " + std::to_string(camera_of[f]) +
+                                        " was made for max_dets = " + std::to_string(trackers[camera_of[f]]->NM));
+    return update_streams_body(trackers, C, camera_of, F, boxes_xywh, foot_xy, confidence, features, has_feature, feat_mem_kind, counts, out_ids, frames_done);
 }); }
 
 extern "C" int opd_track_get(opd_track* t, opd_track_rec* out, int capacity, int* count) { return api_call("opd_track_get", [&]() -> int {

@@ -1,11 +1,13 @@
 // opd_track.h — PRIVATE header of the tracker handle (`opd_track`, include/opd_detr.h): the per-slot device state as kernels_track.hip
-// reads and writes it, the parameters of the three launches, the handle, and the tracker half of the fused detect-and-track call.  Included by
+// reads and writes it, the parameters of the launches, the handle, and the tracker half of the fused detect-and-track call.  Included by
 // kernels_track.hip, opd_track.cpp, opd_track_test_api.cpp and opd_api.cpp.
 //
 // A sequence call (opd_track_update_sequence, opd_detr_detect_sequence_track) also keeps the track TABLE on the device for the length
 // of the call: the header ints below, the entries in creation order and the free-slot stack.  track_assoc_kernel then does between the two launches
 // what the host does in a per-frame call, so frame b + 1 needs no host wait behind frame b.  Between calls the host copy (opd_track::tracks) is
-// the authoritative one: a sequence call uploads it first and adopts the downloaded table last.
+// the authoritative one: a sequence call uploads it first and adopts the downloaded table last.  A streams call (opd_track_update_streams,
+// opd_detr_detect_streams_track) does the same for C trackers at once, their frames side by side: the launches read each tracker's parameter block,
+// the structs below, from an array in device memory.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +24,7 @@ enum { TRACK_ASSOC_THREADS = 64, TRACK_ASSOC_CACHE_FLOATS = 28 * 1024 };   // on
 // applied so far, the out-of-slots one included.  STOP_T / STOP_NEW: the live and the new tracks of that frame, for the error text.
 enum { TRACK_HDR_T = 0, TRACK_HDR_NEXT_ID, TRACK_HDR_N_FREE, TRACK_HDR_STOPPED, TRACK_HDR_M, TRACK_HDR_FRAMES_DONE, TRACK_HDR_STOP_T, TRACK_HDR_STOP_NEW, TRACK_HDR_INTS = 16 };
 enum { TRACK_ENTRY_INTS = 5 };       // slot, id, age, hits, tsu: a TrackEntry
+enum { TRACK_MAX_CAMERAS = 64 };     // trackers of one streams call (opd_track_update_streams, opd_detr_detect_streams_track): blockIdx.y of its launches
 
 // Numeric state of every slot, in ONE device allocation that lives as long as the handle
 struct TrackState {
@@ -102,6 +105,14 @@ hipError_t opd_launch_track_predict_cost(const TrackPredictParams& p, hipStream_
 hipError_t opd_launch_track_commit(const TrackCommitParams& p, hipStream_t stream);
 hipError_t opd_launch_track_ingest(const TrackIngestParams& p, hipStream_t stream);
 hipError_t opd_launch_track_assoc(const TrackAssocParams& p, hipStream_t stream);
+// The same four for C cameras in ONE launch each (a streams call): blockIdx.y is the camera, and every workgroup reads its camera's block, the struct
+// above with `hdr` set, from `dev` [C] in device memory (64 blocks do not fit a kernel-argument block).  `host`: the same C blocks on the host, for the
+// checks and the grid (blockIdx.x runs to the largest bound among them).  A block whose `hdr` is null is a camera without work in this launch.
+// *launched: 0 where no camera had work and nothing was launched.
+hipError_t opd_launch_track_predict_cost_multi(const TrackPredictParams* host, const TrackPredictParams* dev, int C, hipStream_t stream, int* launched);
+hipError_t opd_launch_track_commit_multi(const TrackCommitParams* host, const TrackCommitParams* dev, int C, hipStream_t stream, int* launched);
+hipError_t opd_launch_track_ingest_multi(const TrackIngestParams* host, const TrackIngestParams* dev, int C, hipStream_t stream, int* launched);
+hipError_t opd_launch_track_assoc_multi(const TrackAssocParams* host, const TrackAssocParams* dev, int C, hipStream_t stream, int* launched);
 
 struct TrackEntry { int32_t slot, id, age, hits, tsu; };
 static_assert(sizeof(TrackEntry) == TRACK_ENTRY_INTS * 4, "the device table holds TrackEntry as it lies");
@@ -117,6 +128,7 @@ struct opd_track {
     opd::Staging io;                          // one layout on both sides, fixed at creation (offsets below)
     size_t o_slots = 0, o_boxes = 0, o_foot = 0, o_has = 0, o_feat = 0, o_ops = 0, o_app = 0, o_iou = 0, o_comb = 0, o_n = 0, io_bytes = 0;
     opd::Staging seq;                         // sequence calls: [table | ids | the call's detections], grown lazily to the largest call so far
+    opd::Staging desc;                        // streams calls, on trackers[0] alone: the parameter blocks of every step, cameras side by side
     hipEvent_t ev_commit = nullptr;           // fused call: recorded on `stream` behind everything enqueued there, waited for by the detector's stream
     std::vector<TrackEntry> tracks;           // creation order: the reference's `self.tracks`
     std::vector<int32_t> free_slots;          // (popped from the back)
@@ -153,5 +165,20 @@ int track_fused_finish(opd_track* t, const float* conf, int conf_stride, int n, 
 //                           frame ran out of slots
 int track_sequence_enqueue(opd_track* t, hipStream_t s, const opd_det* records, const int32_t* counts, int Q, int B, const TrackFeatureSource& src, const char* who);
 int track_sequence_finish(opd_track* t, const int32_t* counts, int Q, int B, int32_t* track_ids, int32_t* frames_done, const char* who);
+
+// ---- streams calls: K_c frames each of C cameras, camera c into trackers[c], the cameras side by side ----
+// The schedule: camera_of [F] names the camera of every frame of the call, in call order.  Step s holds the s-th frame of every camera that has one:
+// the result is [steps][C] frame indices, -1 where a camera has no frame at that step; steps = the most frames any camera has.  (Entries outside
+// 0 .. C - 1 are the caller's to refuse first.)
+std::vector<std::vector<int32_t>> streams_schedule(const int32_t* camera_of, int F, int C);
+// The checks of the tracker list that both streams entries make, after their own: C, camera_of, a tracker named twice or without a frame.  (Null handles
+// and devices are track_fused_check's in the detect entry.)
+int track_streams_check(opd_track* const* trackers, int C, const int32_t* camera_of, int F, const char* who);
+// The tracker half of opd_detr_detect_streams_track, around the caller's one wait on `s` like track_sequence_*: frame b of the call is a frame of
+// trackers[camera_of[b]].  frames_done [C]; OPD_EINVAL with the first stopped camera's sentence where a camera ran out of slots.
+int track_streams_enqueue(opd_track* const* trackers, int C, const int32_t* camera_of, hipStream_t s, const opd_det* records, const int32_t* counts, int Q, int B,
+                          const TrackFeatureSource& src, const char* who);
+int track_streams_finish(opd_track* const* trackers, int C, const int32_t* camera_of, const int32_t* counts, int Q, int B, int32_t* track_ids, int32_t* frames_done,
+                         const char* who);
 
 }  // namespace opd

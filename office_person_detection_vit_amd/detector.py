@@ -1195,6 +1195,65 @@ class HipDetrDetector:
             out.extend(tracker._replay(per_frame, ids, done.value, rc, "opd_detr_detect_sequence_track", stride=Q))
         return out
 
+    def detect_and_track_streams(self, frames_per_camera: Sequence[Sequence[np.ndarray]], trackers: Sequence, features: Optional[str] = "color", reid=None,
+                                 reid_slots: int = 32) -> List[List[List[Detection]]]:
+        """``[self.detect_and_track_batch(f, t, ...) for f, t in zip(frames_per_camera, trackers)]`` with the cameras in ONE native call
+        (``opd_detr_detect_streams_track``): one forward over up to ``max_batch`` frames of up to 64 cameras, one host wait, and the cameras'
+        tracker steps side by side on the device.  ``tracker.plan_stream_calls`` cuts longer runs into calls; the results do not depend on
+        the cut.  Same ids and track states as the per-camera calls.  Where the conditions of ``detect_and_track`` fail for a tracker, or the
+        cameras' frames differ in size, the per-camera ``detect_and_track_batch`` runs instead.  Where a camera runs out of slots it stops
+        as under ``detect_and_track_batch``; the other cameras of that call finish, then the error is raised."""
+        from .tracker import HipTracker, plan_stream_calls
+        self._require_model()
+        kind = _track_feature_kind(features, reid)
+        per_camera, trackers = [list(f) for f in frames_per_camera], list(trackers)
+        if len(trackers) != len(per_camera):
+            raise ValueError(f"{len(trackers)} trackers for {len(per_camera)} cameras")
+        if len({id(t) for t in trackers}) != len(trackers):
+            raise ValueError("a tracker is named twice; a tracker follows one camera")
+        self._sync_nms()
+        every = [f for cam in per_camera for f in cam]
+        sizes = {(f.shape[0], f.shape[1]) if isinstance(f, np.ndarray) else None for f in every}
+        if not every or len(sizes) != 1 or any(self._fused_track_target(every[:1], t, features, reid) is None for t in trackers):
+            return [self.detect_and_track_batch(f, t, features=features, reid=reid, reid_slots=reid_slots) for f, t in zip(per_camera, trackers)]
+        out: List[List[List[Detection]]] = [[] for _ in trackers]
+        Q = self._info.num_queries
+        for call in plan_stream_calls([len(cam) for cam in per_camera], self.max_batch):
+            cams = [trackers[c] for c, _, _ in call]
+            runs = [per_camera[c][a:b] for c, a, b in call]
+            chunk = [f for run in runs for f in run]   # camera after camera; the native side steps across them
+            target = self._fused_track_target(chunk, cams[0], features, reid)
+            if target is None:   # (a frame that cannot go down as a frame list)
+                for (c, a, b), t in zip(call, cams):
+                    out[c].extend(self.detect_and_track_batch(per_camera[c][a:b], t, features=features, reid=reid, reid_slots=reid_slots))
+                continue
+            for t in cams:
+                t._ensure()
+            B = len(chunk)
+            camera_of = np.array([i for i, run in enumerate(runs) for _ in run], np.int32)
+            slots = max(1, min(int(reid.max_crops), min(int(t.max_dets) for t in cams), int(reid_slots) * B)) if features == "reid" else 0
+            recs, counts = (_capi.OpdDet * (B * Q))(), (C.c_int32 * B)()
+            ids, n_featured, done = np.full(B * Q, -1, np.int32), np.zeros(B, np.int32), np.zeros(len(cams), np.int32)
+            ptrs = (C.c_void_p * B)(*[f.ctypes.data for f in chunk])
+            handles = (C.c_void_p * len(cams))(*[t._h.value for t in cams])
+            h, w = int(chunk[0].shape[0]), int(chunk[0].shape[1])
+            rc = self._lib.opd_detr_detect_streams_track(C.c_void_p(self.model), reid._handle if features == "reid" else None, handles, len(cams),
+                                                         camera_of.ctypes.data_as(C.c_void_p), ptrs, B, h, w, target[0], target[1], float(self.confidence_threshold),
+                                                         PERSON_LABEL, kind, slots, recs, counts, ids.ctypes.data, n_featured.ctypes.data, done.ctypes.data)
+            if rc != 0 and "counted as one without detections" not in _capi.last_error():
+                _capi.check(rc, "opd_detr_detect_streams_track")
+            message = _capi.last_error() if rc != 0 else ""
+            self._last_orig = [(h, w)] * B
+            per_frame = self._postprocess_batch(recs, counts, Q)
+            dets, at = [], 0
+            for run in runs:
+                dets.append(per_frame[at:at + len(run)])
+                at += len(run)
+            err = HipTracker._replay_streams(cams, dets, ids, done, rc, "opd_detr_detect_streams_track", out, [c for c, _, _ in call], stride=Q, message=message)
+            if err is not None:
+                raise err
+        return out
+
     def extract_color_features(self, frame: np.ndarray, detections: List[Detection]) -> np.ndarray:
         """(N, 256) float32 colour-histogram features of the detections' crops of ``frame`` (BGR uint8 ``[H, W, 3]``), on the
         device: ``FeatureExtractor.extract_batch`` on the crops ``YOLOv8Detector.extract_features`` cuts

@@ -13,9 +13,10 @@ one from every detection in that one case)."""
 from __future__ import annotations
 
 import ctypes as C
+import re
 from dataclasses import dataclass, field
 import logging
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -23,6 +24,37 @@ from . import _capi
 from .data_models import Detection
 
 logger = logging.getLogger(__name__)
+
+
+MAX_STREAM_TRACKERS = 64   # trackers of one streams call (the native TRACK_MAX_CAMERAS)
+
+
+def plan_stream_calls(lengths: Sequence[int], max_batch: Optional[int] = None, max_trackers: int = MAX_STREAM_TRACKERS) -> List[List[Tuple[int, int, int]]]:
+    """Cut the cameras' runs of ``lengths[c]`` frames into streams calls: a list of calls, each a list of ``(camera, start, stop)`` with at most
+    ``max_batch`` frames (None: no limit) and at most ``max_trackers`` cameras in all.  Every frame is in exactly one call, a camera's frames keep
+    their order across the calls, and a camera without frames is in none.  The policy: every call takes the cameras that still have frames, in
+    camera order (at most ``max_trackers``, and no more than there is room for), and shares its room among them evenly, so that the cameras advance
+    side by side and a call has as few steps as its frames allow; room a short camera leaves goes to the ones behind it."""
+    if max_batch is not None and max_batch < 1:
+        raise ValueError(f"max_batch must be at least 1, got {max_batch}")
+    if not 1 <= max_trackers <= MAX_STREAM_TRACKERS:
+        raise ValueError(f"max_trackers must be 1 .. {MAX_STREAM_TRACKERS}, got {max_trackers}")
+    at = [0] * len(lengths)
+    calls: List[List[Tuple[int, int, int]]] = []
+    first = 0   # the camera a call starts with: round robin, so that no camera waits for the others to finish
+    while any(at[c] < n for c, n in enumerate(lengths)):
+        order = [c % len(lengths) for c in range(first, first + len(lengths))]
+        cams = [c for c in order if at[c] < lengths[c]][:max_trackers if max_batch is None else min(max_trackers, max_batch)]
+        room = sum(lengths[c] - at[c] for c in cams) if max_batch is None else max_batch
+        call = []
+        for i, c in enumerate(cams):
+            take = lengths[c] - at[c] if max_batch is None else min(lengths[c] - at[c], max(1, room // (len(cams) - i)))
+            call.append((c, at[c], at[c] + take))
+            at[c] += take
+            room -= take
+        calls.append(sorted(call))
+        first = (cams[-1] + 1) % len(lengths)
+    return calls
 
 
 @dataclass
@@ -146,6 +178,91 @@ class HipTracker:
         if rc != 0 and not stopped:
             _capi.check(rc, "opd_track_update_sequence")
         return self._replay(frames, ids, done.value, rc, "opd_track_update_sequence")
+
+    @staticmethod
+    def update_streams(trackers: Sequence["HipTracker"], detections_per_camera: Sequence[List[List[Detection]]]) -> List[List[List[Detection]]]:
+        """``[t.update_sequence(d) for t, d in zip(trackers, detections_per_camera)]`` with the cameras side by side on the device
+        (``opd_track_update_streams``): one native call and one host wait for up to 64 cameras, as many steps as the longest camera has frames.
+        Same ids, same track states.  In ``TrackingPhase.execute`` with several cameras, the loop over cameras and frames becomes this one call.
+        Where a camera runs out of slots it stops as ``update_sequence`` does; every other camera runs to its end, then the error is raised."""
+        trackers, per_camera = list(trackers), [[list(d) for d in cam] for cam in detections_per_camera]
+        if len(trackers) != len(per_camera):
+            raise ValueError(f"{len(trackers)} trackers for {len(per_camera)} cameras")
+        if len({id(t) for t in trackers}) != len(trackers):
+            raise ValueError("a tracker is named twice; a tracker follows one camera")
+        for c, (t, cam) in enumerate(zip(trackers, per_camera)):
+            if cam and max(len(f) for f in cam) > t.max_dets:
+                raise ValueError(f"a frame of camera {c} has {max(len(f) for f in cam)} detections, its tracker was made for max_dets = {t.max_dets}")
+        out: List[List[List[Detection]]] = [[] for _ in trackers]
+        failed: Optional[RuntimeError] = None
+        for call in plan_stream_calls([len(cam) for cam in per_camera]):
+            cams = [trackers[c] for c, _, _ in call]
+            if len({t.device_ordinal for t in cams}) > 1:   # (the native call wants one device: camera by camera instead)
+                for c, a, b in call:
+                    out[c].extend(trackers[c].update_sequence(per_camera[c][a:b]))
+                continue
+            runs = [per_camera[c][a:b] for c, a, b in call]
+            camera_of = np.array([i for i, run in enumerate(runs) for _ in run], np.int32)   # camera after camera; the native side steps across them
+            frames = [f for run in runs for f in run]
+            counts = np.array([len(f) for f in frames], np.int32)
+            n = int(counts.sum())
+            with_feats = any(det.features is not None for f in frames for det in f)
+            boxes, foot, conf, has = np.zeros((n, 4), np.float32), np.zeros((n, 2), np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint8)
+            widths = np.array([cams[i].feature_dim for i in camera_of], np.int64)
+            feats = np.zeros(int((counts * widths).sum()), np.float32) if with_feats else None
+            j = at = 0
+            for i, f in zip(camera_of, frames):
+                D = cams[i].feature_dim
+                for det in f:
+                    if det.camera_coords is None:
+                        raise ValueError(f"detection {j} has no camera_coords: a track cannot be started or updated without a foot point")
+                    boxes[j], foot[j], conf[j] = det.bbox, det.camera_coords, det.confidence
+                    if det.features is not None:
+                        v = np.asarray(det.features, np.float32).reshape(-1)
+                        if v.shape[0] != D:
+                            raise ValueError(f"detection {j} has a feature of width {v.shape[0]}, its tracker was made for {D}")
+                        feats[at:at + D], has[j] = v, 1
+                    j += 1
+                    at += D
+            for t in cams:
+                t._ensure()
+            lib = cams[0]._lib
+            handles = (C.c_void_p * len(cams))(*[t._h.value for t in cams])
+            ids, done = np.full(max(n, 1), -1, np.int32), np.zeros(len(cams), np.int32)
+            p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+            rc = lib.opd_track_update_streams(handles, len(cams), p(camera_of), len(frames), p(boxes), p(foot), p(conf), p(feats), p(has), _capi.OPD_MEM_HOST, p(counts),
+                                              p(ids), p(done))
+            err = HipTracker._replay_streams(cams, runs, ids, done, rc, "opd_track_update_streams", out, [c for c, _, _ in call])
+            failed = failed or err
+            if err is not None:
+                break
+        if failed is not None:
+            raise failed
+        return out
+
+    @staticmethod
+    def _replay_streams(cams, runs, ids: np.ndarray, done: np.ndarray, rc: int, what: str, out: list, into: List[int], stride: Optional[int] = None,
+                        message: Optional[str] = None) -> Optional[RuntimeError]:
+        """``_replay`` per camera after a streams call whose frames lay camera after camera (``ids`` likewise): the cameras that ran to their end
+        first, then the stopped ones, each of which raises as ``update_sequence`` does; returns the first such error instead of raising it, so
+        that every camera's mirror follows its native tracker."""
+        if message is None:
+            message = _capi.last_error() if rc != 0 else ""
+        stopped = rc != 0 and "counted as one without detections" in message
+        if rc != 0 and not stopped:
+            _capi.check(rc, what)
+        named = re.search(r"cameras out of slots: ([0-9, ]+)", message)
+        out_of_slots = {int(v) for v in named.group(1).split(",")} if named else set()
+        failed: Optional[RuntimeError] = None
+        at = 0
+        for i, (t, run) in enumerate(zip(cams, runs)):
+            rows = sum(stride if stride is not None else len(f) for f in run)
+            try:
+                out[into[i]].extend(t._replay(run, ids[at:at + rows], int(done[i]), rc if i in out_of_slots else 0, what, stride=stride))
+            except RuntimeError:
+                failed = failed or RuntimeError(f"{what} failed (code {rc}): {message}")
+            at += rows
+        return failed
 
     def _replay(self, frames: List[List[Detection]], ids: np.ndarray, done: int, rc: int, what: str, stride: Optional[int] = None) -> List[List[Detection]]:
         """The mirror after a sequence call: ``_apply`` frame by frame for the ``done`` frames the native side applied (the last of them an empty
