@@ -242,11 +242,11 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     const bool has_res = RC ? true : (!SC && p.res != nullptr && !(p.dbg & 4));
     // Counted waits (the rule: opd_kprims.h -- only YOUNGER LDS-DMA requests may be among the N operations a vmcnt(N) leaves in flight).
     // Here: N = the residual pieces of chunk j + 2 when they travel by LDS-DMA, otherwise 0; and the y stores of a step are issued AFTER its
-    // wait, so that a vmcnt(0) never waits for them.
+    // wait, so that a vmcnt(0) never waits for them.  The chunk steps issue no loads into registers: the biases come once per tile (`b2p`).
     // RB1 (one residual buffer): chunk j+1's pieces are requested in step j, right after chunk j has been read out of the buffer.  The barrier
     // wait of step j leaves those four in flight (wave-private, the youngest requests); the wait in front of step j+1's read leaves the
     // OP_PIECES operand requests of chunk j+2 in flight, which step j+1 has issued just before.  Nothing but LDS-DMA requests may sit among the
-    // counted ones, so a step's y stores and bias loads are fenced in front of its operand requests.
+    // counted ones, so a step's y stores are fenced in front of its operand requests.
     const bool res_dma = RDMA && has_res;
     auto load_res = [&](int j, uint4 (&r)[4]) {
         if constexpr (RDMA) {
@@ -291,6 +291,14 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
         acc1[nt][0] = b;
         acc1[nt][1] = b;
     }
+    // The expand bias of the WHOLE tile, once: within a lane-row every lane needs the same 16 floats per chunk, so lane (g, li) fetches the
+    // float4 of (chunk, tile) = (li >> 2, li & 3) and a chunk step takes its four from lane 4 (j & 3) + nt of its own row (row_bcast4: a DPP
+    // move, no vector-memory instruction in the chunk steps).  C1 == 128: a second set for chunks 4-7.  RC: the previous block's bias likewise.
+    constexpr int NB2 = NCH / 4;   // sets of four chunks
+    float4v b2p[NB2], rcbp = {};
+#pragma unroll
+    for (int s = 0; s < NB2; ++s) b2p[s] = *reinterpret_cast<const float4v*>(p.b2 + s * 256 + (li >> 2) * 64 + own_ch(li & 3, g));
+    if constexpr (RC != 0) rcbp = *reinterpret_cast<const float4v*>(p.rc_b + (li >> 2) * 64 + own_ch(li & 3, g));
     OPD_DMA_BARRIER();   // (the bias loads above are younger than the first stage's requests: the compiler's own wait would let them fly)
     uint4 res[3][4];  // residual of chunk j lives in res[j % 3], fetched two chunk steps ahead
     auto compute_main = [&](int buf) {
@@ -316,7 +324,6 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
         __syncthreads();
     }
     // last k-step: the free stage buffer receives chunk 0's operands; residual chunks 0 and 1 (RB1: chunk 0) start their trip
-    float4v b2n[4];   // RB1 / SC2: the expand bias of the next chunk step, loaded in front of that step's LDS-DMA requests
     // SC2: the shortcut's 256 input channels of this wave's 32 pixels as B fragments, gathered at (stride oh, stride ow) of the H x W grid of
     // the previous stage's output.  Requested here, where acc1 is about to die; complete at the vmcnt(0) that ends the 3x3 loop.
     half8 xs2[2][SC2 ? 8 : 1];
@@ -332,11 +339,6 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
 #pragma unroll
             for (int kb = 0; kb < 8; ++kb) xs2[mt][kb] = *reinterpret_cast<const half8*>(src + kb * 32);
         }
-    }
-    if constexpr (RB1 || SC2) {
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) b2n[nt] = *reinterpret_cast<const float4v*>(p.b2 + own_ch(nt, g));
-        compiler_fence();
     }
     // SC2 half steps.  A chunk's operands are W2 16 KiB + Wsc 32 KiB + W3 16 KiB against 32-KiB stage buffers, so chunk j runs as two steps
     // with a barrier each: the EVEN step reads W2[j] (buffer 0) while Wsc[j] (buffer 1) and the W3 slice (behind the buffers) are on their way,
@@ -426,8 +428,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
             compiler_fence();
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
-                acc2[nt][0] = b2n[nt];
-                acc2[nt][1] = b2n[nt];
+                const float4v b = row_bcast4(b2p[j >> 2], bias_pack_lane(j, nt));
+                acc2[nt][0] = b;
+                acc2[nt][1] = b;
             }
 #pragma unroll
             for (int kk = 0; kk < KK1; ++kk) {
@@ -441,14 +444,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
             }
             wait_vmcnt<0>();   // Wsc[j] and the W3 slice landed (and the previous step's y stores retired: nothing else is in flight)
             __builtin_amdgcn_s_barrier();
-            // odd step: the next chunk's bias in front of the requests, W2[j + 1] into buffer 0
+            // odd step: W2[j + 1] into buffer 0
             compiler_fence();
-            if (j + 1 < NCH) {
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) b2n[nt] = *reinterpret_cast<const float4v*>(p.b2 + (j + 1) * 64 + own_ch(nt, g));
-                compiler_fence();
-                issue_w2(j + 1);
-            }
+            if (j + 1 < NCH) issue_w2(j + 1);
             compiler_fence();
 #pragma unroll
             for (int kb = 0; kb < 8; ++kb) {
@@ -502,17 +500,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
     for (int j = 0; j < NCH; ++j) {
         const int buf = (nk + j) & 1;
         uint4 (&res_cur)[4] = res[j % 3];
-        float4v b2c[4];
-        if constexpr (RB1) {   // (behind the previous step's y stores, in front of this step's requests)
-            compiler_fence();
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) b2c[nt] = b2n[nt];
-            if (j + 1 < NCH) {
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) b2n[nt] = *reinterpret_cast<const float4v*>(p.b2 + (j + 1) * 64 + own_ch(nt, g));
-            }
-            compiler_fence();
-        }
+        if constexpr (RB1) compiler_fence();   // (the previous step's y stores stay in front of this step's requests: they must not be among the counted ones)
         if (j + 1 < NCH) issue_chunk(j + 1, buf ^ 1);
         compiler_fence();
         if constexpr (RDMA) {
@@ -545,7 +533,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
             float4v accr[4][2];
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
-                const float4v b = *reinterpret_cast<const float4v*>(p.rc_b + j * 64 + own_ch(nt, g));
+                const float4v b = row_bcast4(rcbp, bias_pack_lane(j, nt));
                 accr[nt][0] = b;
                 accr[nt][1] = b;
             }
@@ -577,9 +565,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void btail_kernel(BtailParams p) {
         float4v acc2[4][2];
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-            float4v b;
-            if constexpr (RB1) b = b2c[nt];
-            else b = *reinterpret_cast<const float4v*>(p.b2 + j * 64 + own_ch(nt, g));
+            const float4v b = row_bcast4(b2p[j >> 2], bias_pack_lane(j, nt));
             acc2[nt][0] = b;
             acc2[nt][1] = b;
         }

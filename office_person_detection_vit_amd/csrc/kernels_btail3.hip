@@ -206,12 +206,23 @@ __global__ __launch_bounds__(512) void btail256_kernel(BtailParams p) {
         st_cur = st_cur == 2 * STAGE_BYTES ? 0 : st_cur + STAGE_BYTES;
         st_next2 = st_next2 == 2 * STAGE_BYTES ? 0 : st_next2 + STAGE_BYTES;
     }
-    // (biases are fetched like operands, ahead of their use and IN FRONT of the DMA requests of their step: a load issued right before its
-    //  use would make the compiler wait for everything older, i.e. drain the DMA queue in the middle of a step)
+    // (biases are fetched ahead of their use, with the first residuals: a load issued right before its use would make the compiler wait for
+    //  everything older, i.e. drain the DMA queue in the middle of a step)
     float4v acc2[2][2];   // expand accumulators; [tile][0] receives the bias of the NEXT chunk one step ahead (it is dead from the y epilogue on)
+    // The expand bias of the whole tile in two loads per lane: a lane-row needs 8 floats per chunk (two tiles), 128 for the 16 chunks; lane
+    // (g, li) of set s holds the float4 of (chunk, tile) = (q >> 1, q & 1), q = 16 s + li, and chunk j, tile nt comes out of lane (2 j + nt) & 15
+    // of set j >> 3 of the lane's own row (row_bcast4: a DPP move, no vector-memory instruction in the chunk steps).
+    float4v b2p[2];
+    auto load_bias2_tile = [&]() {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int q = 16 * s + li;
+            b2p[s] = *reinterpret_cast<const float4v*>(p.b2 + (q >> 1) * 64 + half * 32 + (q & 1) * 16 + g * 4);
+        }
+    };
     auto load_bias2 = [&](int j) {
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt) acc2[nt][0] = *reinterpret_cast<const float4v*>(p.b2 + j * 64 + half * 32 + nt * 16 + g * 4);
+        for (int nt = 0; nt < 2; ++nt) acc2[nt][0] = row_bcast4(b2p[j >> 3], 2 * j + nt);
     };
     float4v accz[C3 ? 8 : 1][2];
     // k-step nk-2 (stage 1): stage 0 is free (WAR rule above) -> W2 of chunk 0 into [0, 32K)
@@ -230,7 +241,7 @@ __global__ __launch_bounds__(512) void btail256_kernel(BtailParams p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) issue_w3_piece(0, i);
     compiler_fence();
-    load_bias2(0);
+    load_bias2_tile();
     if constexpr (C3 > 0) {
 #pragma unroll
         for (int nt = 0; nt < 8; ++nt) accz[nt][0] = *reinterpret_cast<const float4v*>(p.b3 + half * 128 + nt * 16 + g * 4);
@@ -243,6 +254,8 @@ __global__ __launch_bounds__(512) void btail256_kernel(BtailParams p) {
     mfma_phase(no_issue);
     if (group == 0) lds_barrier();   // the groups are aligned again: every wave has passed the same number of barriers
     wait_vmcnt<0>();
+    asm volatile("" : "+v"(b2p[0]), "+v"(b2p[1]));   // (in their registers here, like b3 below)
+    load_bias2(0);
     if constexpr (C3 > 0) {
 #pragma unroll
         for (int nt = 0; nt < 8; ++nt) {

@@ -188,6 +188,29 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+// Every lane of a 16-lane row <- lane `src` (0..15) of its own row: one DPP move (row_newbcast) per dword, no LDS and no memory instruction.
+// `src` must fold to a constant where the call is inlined (an unrolled loop index); all 64 lanes must be active.
+__device__ __forceinline__ float row_bcast(const float v, const int src) {
+#define OPD_ROW_BCAST_CASE(n) \
+    case n: return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150 + n, 0xf, 0xf, false))
+    switch (src & 15) {
+        OPD_ROW_BCAST_CASE(0); OPD_ROW_BCAST_CASE(1); OPD_ROW_BCAST_CASE(2); OPD_ROW_BCAST_CASE(3);
+        OPD_ROW_BCAST_CASE(4); OPD_ROW_BCAST_CASE(5); OPD_ROW_BCAST_CASE(6); OPD_ROW_BCAST_CASE(7);
+        OPD_ROW_BCAST_CASE(8); OPD_ROW_BCAST_CASE(9); OPD_ROW_BCAST_CASE(10); OPD_ROW_BCAST_CASE(11);
+        OPD_ROW_BCAST_CASE(12); OPD_ROW_BCAST_CASE(13); OPD_ROW_BCAST_CASE(14);
+        default: OPD_ROW_BCAST_CASE(15);
+    }
+#undef OPD_ROW_BCAST_CASE
+}
+__device__ __forceinline__ float4v row_bcast4(const float4v& v, const int src) {
+    const float4v r = {row_bcast(v[0], src), row_bcast(v[1], src), row_bcast(v[2], src), row_bcast(v[3], src)};
+    return r;
+}
+// Lane-packed bias of a tile's 64-channel chunks in the fused tails: lane (g, li) of set s holds the float4 that lane-row g needs for chunk
+// 4 s + (li >> 2), accumulator tile li & 3; chunk j, tile nt is then row_bcast4(set j >> 2, bias_pack_lane(j, nt)).  One 16-byte load per
+// lane and set for the whole tile instead of four per chunk step.
+__device__ __forceinline__ int bias_pack_lane(const int j, const int nt) { return 4 * (j & 3) + nt; }
+
 // D = A . B + C on 16 x 16 x 32 fragments of the translation unit's operand type
 __device__ __forceinline__ float4v mfma16(const half8& a, const half8& b, const float4v& c) { return OPD_MFMA_16x16x32(a, b, c); }
 
